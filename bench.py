@@ -3,6 +3,7 @@
 
   python bench.py                                   # N = 1, BASELINE.json configs[2] + every 1-GPU leg
   python bench.py --gpus 1 --steps 192 --warmup 32
+  python bench.py --gpus 1 --steps 20 --warmup 5 --dump-outputs bench_outputs   # + the last timed step's outputs as .npy
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
       --master-port P bench.py --gpus N --steps K --warmup W [--config 3|4]
   python bench.py --gpus N ...                      # no launcher (WORLD_SIZE unset): bench.py starts the N ranks itself
@@ -230,6 +231,7 @@ class Rollout:
     wall, live, ev_ms, ev_exposed_ms = [], [], [], []
     ev0 = torch.cuda.Event(enable_timing=True); ev1 = torch.cuda.Event(enable_timing=True); evk = torch.cuda.Event(enable_timing=True)
     plan = self.plan(self.warmup, self.warmup + self.steps)
+    self.timed_plan = plan            # (its reward / terminal rows: the last repetition's, read by --dump-outputs)
     g0 = (self.gatherer.gathers, self.gatherer.rows_gathered) if self.gatherer is not None else (0, 0)
     # The wall-clock repetitions carry no event records (two records cost ~10 us of host time per region: 2.4 % of a
     # 20-step region); the kernel's own duration comes from separate, event-bracketed repetitions of the same region.
@@ -299,6 +301,33 @@ class Rollout:
             'live_env_fraction_end': self.live_fraction_end, 'decode_ms': self.decode_ms,
             'gathers_per_region': self.gathers_per_region, 'rows_gathered_per_region': self.rows_gathered_per_region,
             'launches_per_region': self.launches_per_region, 'per_rank': per_rank}
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, roll):
+  """--dump-outputs: what the timed path returned in its last timed step -- the reward and terminal rows of that step and the
+  environment state it left -- as out_dir/<name>.npy, this rank's environments.  float32, float64 for the integer fields that
+  float32 would round (time, episode start).  Above DUMP_LIMIT_BYTES a fixed, seeded sample of the environments is written;
+  env_index.npy names the rows either way.  Every repetition restarts from the same snapshot, so the last one's rows are
+  every repetition's."""
+  np = roll.np
+  _, _, rewards, terminals = roll.timed_plan[-1]
+  arrays = {'reward': rewards[-1], 'terminal': terminals[-1]}
+  arrays.update(('state_' + k, t) for k, t in roll.sim.state.items())
+  host = {}
+  for k, t in arrays.items():
+    a = t.cpu().numpy()
+    host[k] = a.astype(np.float32 if a.dtype in (np.float32, np.uint8) else np.float64)
+  per_env = 8 + sum(a.itemsize for a in host.values())
+  idx = np.arange(roll.n)
+  if roll.n * per_env > DUMP_LIMIT_BYTES:
+    idx = np.sort(np.random.default_rng(0).choice(roll.n, DUMP_LIMIT_BYTES // per_env, replace=False))
+  os.makedirs(out_dir, exist_ok=True)
+  np.save(os.path.join(out_dir, 'env_index.npy'), idx.astype(np.float64))
+  for k, a in host.items():
+    np.save(os.path.join(out_dir, k + '.npy'), a[idx])
 
 
 def observe_leg(roll, pairs, world, measure=False):
@@ -576,6 +605,9 @@ def main():
   ap.add_argument('--noise-seed', type=int, default=None,
                   help='fly the HEADLINE in the ground-truth wind (noise generated in-kernel) instead of the forecast; the default '
                        'run reports both (config.ground_truth_wind)')
+  ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                  help='write what the headline path computed in its last timed step (rewards, terminals, the state of rank 0\'s '
+                       'environments) to DIR/<name>.npy; the inputs are the same in every run with the same arguments')
   args = ap.parse_args()
   PMC_BUDGET_S[0] = args.pmc_budget_s
 
@@ -638,6 +670,8 @@ def main():
   # ---- headline leg
   head = make(args.config, n=args.envs_per_gpu, noise_seed=args.noise_seed)
   hs = head.summary(args.reps)
+  if args.dump_outputs and rank == 0:
+    dump_outputs(args.dump_outputs, head)
   tick('headline leg')
   n = head.n
   bytes_per_launch = ALGORITHMIC_BYTES_PER_ENV_STEP * (hs['live_env_steps_per_repetition'] / world / head.launches_per_region)

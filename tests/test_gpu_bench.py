@@ -121,6 +121,24 @@ def test_bench_under_the_drivers_launcher_command():
   assert out['value'] > 1e6 and out['config']['exchanges']['agent_step_rows_gathered_per_timed_region'] == 20
 
 
+def test_bench_dump_outputs_are_the_same_in_two_runs(tmp_path):
+  """--dump-outputs: the last timed step's rewards, terminals and state as float32 / float64 .npy files, the same bits in two runs
+  with the same arguments (the inputs are seeded), --steps timed steps per repetition and ms_per_step on the line."""
+  import numpy as np
+  for run in ('a', 'b'):
+    out = _bench(['--gpus', '1', '--steps', '12', '--warmup', '3', '--reps', '3', '--no-extras', '--envs-per-gpu', '8192',
+                  '--dump-outputs', str(tmp_path / run)])
+    assert out['steps'] == 12 and out['repetitions']['steps_per_repetition'] == 12 and out['ms_per_step'] > 0
+  files = sorted(os.listdir(tmp_path / 'a'))
+  assert files == sorted(os.listdir(tmp_path / 'b')) and {'reward.npy', 'terminal.npy', 'state_x.npy', 'env_index.npy'} <= set(files)
+  assert sum(os.path.getsize(tmp_path / 'a' / f) for f in files) <= 64 << 20
+  for f in files:
+    a, b = np.load(tmp_path / 'a' / f), np.load(tmp_path / 'b' / f)
+    assert a.dtype in (np.float32, np.float64) and a.shape == (8192,), f
+    assert a.tobytes() == b.tobytes(), f
+  assert np.isfinite(np.load(tmp_path / 'a' / 'reward.npy')).all()
+
+
 def test_bench_refuses_a_world_that_is_not_gpus():
   env = dict(os.environ, WORLD_SIZE='1', RANK='0', LOCAL_RANK='0')
   r = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '2', '--steps', '4', '--warmup', '1', '--no-extras'],
