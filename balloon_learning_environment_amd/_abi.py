@@ -97,3 +97,28 @@ class BleNoiseGen(ctypes.Structure):
   """struct ble_noise_gen: the wind-noise generator of a fused rollout (ble_step_n_f32, ABI 3)."""
   _fields_ = [('seed', ctypes.c_uint64), ('episode', ctypes.c_void_p), ('harmonic_cache', ctypes.c_void_p),
               ('env_offset', ctypes.c_int64)]       # (ABI 4: the shard's first environment in the global batch; default 0)
+
+
+FLEET_MAX_VEHICLES = 16      # BLE_FLEET_MAX_VEHICLES
+
+
+class BleFleet(ctypes.Structure):
+  """struct ble_fleet: a palette of up to FLEET_MAX_VEHICLES vehicles (a HOST array of BleVehicle, read when a call is made) and the
+  DEVICE uint8 index of the entry each environment flies; sample_index makes ble_reset_fleet_at_f32 draw the index per episode."""
+  _fields_ = [('palette', ctypes.POINTER(BleVehicle)), ('n_vehicles', ctypes.c_int32), ('sample_index', ctypes.c_int32),
+              ('vehicle_index', ctypes.c_void_p)]
+
+
+def vehicle_full(**overrides) -> 'BleVehicle':
+  """A BleVehicle with the reference's defaults and the given fields replaced -- always a struct (a fleet's palette entry), unlike
+  vehicle_struct."""
+  return vehicle_struct(**overrides) or BleVehicle(reserved_=0, **VEHICLE_DEFAULTS)
+
+
+def fleet_struct(vehicles, index_ptr: int, sample_index: bool = False) -> BleFleet:
+  """A BleFleet over the vehicles (override dicts in set_vehicle's form); the struct keeps its palette array alive."""
+  n = len(vehicles)
+  palette = (BleVehicle * max(n, 1))(*[vehicle_full(**v) for v in vehicles])
+  f = BleFleet(ctypes.cast(palette, ctypes.POINTER(BleVehicle)), n, 1 if sample_index else 0, int(index_ptr) or None)
+  f._palette_keepalive = palette
+  return f

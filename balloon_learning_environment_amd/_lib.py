@@ -27,6 +27,7 @@ NOISE_PRIMITIVE_VERSION = 2     # BLE_NOISE_PRIMITIVE_VERSION this mirror, oracl
 BLE_OK = 0
 FLAG_PRESSURE_RANGE, FLAG_ABSORPTIVITY, FLAG_SOLAR_RANGE, FLAG_POWER_TABLE, FLAG_NONFINITE = 1, 2, 4, 16, 32
 FLAG_GP_WINDOW, FLAG_PRESSURE_SEARCH, FLAG_DAY_CYCLE = 64, 128, 256
+FLAG_VEHICLE_INDEX = 512
 OBS_DIM, GP_CAPACITY, GP_CHOL_STRIDE = 1099, 128, 7620
 ROW_DOUBLES = 26        # BLE_ROW_DOUBLES
 NOISE_CACHE_ROWS = 53
@@ -35,7 +36,7 @@ NOISE_CACHE_ROWS = 53
 EXPORTS = ('ble_abi_version', 'ble_noise_primitive_version', 'ble_vehicle_default', 'ble_last_hip_error', 'ble_device_count', 'ble_set_step_form', 'ble_step_f32', 'ble_step_n_f32', 'ble_reset_f32', 'ble_reset_at_f32', 'ble_wind_noise_at_f32', 'ble_observe_f32', 'ble_observe_forecast_f32', 'ble_decode_flow_fields_f32', 'ble_wind_noise_f32', 'ble_forecast_f32',
            'ble_forecast_column_f32', 'ble_state_rows_f64', 'ble_power_table_f32', 'ble_probe_atmosphere_f32', 'ble_probe_atmosphere_at_height_f64', 'ble_probe_solar_f32', 'ble_probe_latlng_f64',
            'ble_probe_solar_power_f32', 'ble_probe_thermal_f32', 'ble_probe_sp_volume_f32', 'ble_probe_thermal_vehicle_f32', 'ble_probe_sp_volume_vehicle_f32', 'ble_probe_acs_f32', 'ble_probe_safety_f32',
-           'ble_probe_f64_prims')
+           'ble_probe_f64_prims', 'ble_step_fleet_f32', 'ble_step_n_fleet_f32', 'ble_reset_fleet_at_f32', 'ble_observe_forecast_fleet_f32')
 
 
 class BleLibraryError(RuntimeError):
@@ -117,6 +118,11 @@ def lib():
   l.ble_probe_f64_prims.argtypes = [_vp, _vp, _int, _i64, _vp]
   l.ble_set_step_form.argtypes = [_int]
   l.ble_vehicle_default.argtypes = [ctypes.POINTER(_abi.BleVehicle)]
+  fleet = ctypes.POINTER(_abi.BleFleet)
+  l.ble_step_fleet_f32.argtypes = [st, fleet] + l.ble_step_f32.argtypes[1:]
+  l.ble_step_n_fleet_f32.argtypes = [st, fleet] + l.ble_step_n_f32.argtypes[1:]
+  l.ble_reset_fleet_at_f32.argtypes = [st, fleet] + l.ble_reset_at_f32.argtypes[1:]
+  l.ble_observe_forecast_fleet_f32.argtypes = [st, fleet] + l.ble_observe_forecast_f32.argtypes[1:]
   for name in EXPORTS:
     getattr(l, name).restype = _int
   _lib = l

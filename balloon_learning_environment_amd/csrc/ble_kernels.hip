@@ -75,7 +75,10 @@ struct StepNoiseShared {
   uint32_t draws[50 * kStepBlock];      // the harmonics' seeds and offsets of the workgroup's environments, fetched once per launch
 };
 // V: the flight vehicle's constants -- VehicleDefault (compile-time: ble_state_f32.vehicle == NULL) or VehicleRt (a kernel argument, i.e.
-// scalar registers: ABI 5) -- as the LAST argument, so that the default instantiation's argument layout is what it was.
+// scalar registers: ABI 5) -- as the LAST argument, so that the default instantiation's argument layout is what it was.  VehicleFleet (a
+// fleet call, ble_fleet): the palette's field-major image is copied into LDS next to the ACS table, and every lane reads the VehicleRt of
+// its own entry from there once, after the barrier; from then on the lane flies what the VehicleRt instantiation flies, in vector
+// registers instead of scalar ones (profiles/fleet_resource_usage.txt).
 template <bool kNoise, class V = VehicleDefault>
 __global__ __launch_bounds__(kStepBlock) void ble_step_kernel(StateDev st, const uint8_t* __restrict__ action,
                                                           const float* __restrict__ wind_grid,
@@ -98,6 +101,12 @@ __global__ __launch_bounds__(kStepBlock) void ble_step_kernel(StateDev st, const
     __shared__ double acs_poly_lds[kAcsPolyDoubles];
     __shared__ float term_save_lds[kTermSaveRows * kStepBlock];
     acs_poly = acs_poly_lds; term_save = term_save_lds;
+  }
+  constexpr bool kFleet = IsFleet<V>::value;
+  double* fleet_lds = nullptr;
+  if constexpr (kFleet) {
+    __shared__ double fleet_lds_[kFleetRtFields * kFleetMaxVehicles];
+    fleet_lds = fleet_lds_;
   }
   const int wave = (int)threadIdx.x >> 6, lane = (int)threadIdx.x & 63;
   const int64_t i = ((int64_t)blockIdx.x * (kStepBlock / 64) + wave) * lanes + lane;
@@ -122,6 +131,18 @@ __global__ __launch_bounds__(kStepBlock) void ble_step_kernel(StateDev st, const
     if (st.episode_cache != nullptr) cached = episode_cache_load(st.episode_cache, n, i);
     live = s.status == kOk;
   }
+  int vidx = 0;             // (a fleet) the palette entry of this lane's environment
+  if constexpr (kFleet) {
+    if (in_range) {
+      vidx = veh.index[i];
+      if (vidx >= veh.n_vehicles) {          // frozen like a non-OK lane, reads entry 0 (nothing outside the palette)
+        flags |= kFlagVehicleIndex;
+        live = false;
+        vidx = 0;
+      }
+    }
+    for (int j = (int)threadIdx.x; j < kFleetRtFields * kFleetMaxVehicles; j += kStepBlock) fleet_lds[j] = (&veh.f[0][0])[j];
+  }
   // the ACS table's piecewise cubics: a compile-time table, constant memory -> LDS (the loop reads it by a per-lane index)
   for (int j = (int)threadIdx.x; j < kAcsPolyDoubles; j += kStepBlock) acs_poly[j] = kAcsPoly.c[j];
   if (kNoise) grad_lut_fill(grad_lut, (int)threadIdx.x, kStepBlock);
@@ -130,6 +151,7 @@ __global__ __launch_bounds__(kStepBlock) void ble_step_kernel(StateDev st, const
   BLE_STEP_MARK(2);
   const bool was_live = live;
   int last_act = 0;
+  const auto& lveh = lane_vehicle(veh, fleet_lds, vidx);      // the vehicle argument itself, or (a fleet) this lane's palette entry
   EnvHoisted hc;
   if (live) {
     // per-episode constants: from the cache unless its entry belongs to other constants (then: recompute, store)
@@ -143,7 +165,7 @@ __global__ __launch_bounds__(kStepBlock) void ble_step_kernel(StateDev st, const
   if (kNoise && in_range)
     noise_draws_fetch(gen.seed, (uint64_t)i, (uint64_t)(i + gen.env_offset), gen.episode ? gen.episode[i] : 0u, gen.harmonic_cache, n,
                       noise_draws + threadIdx.x, kStepBlock);
-  const StrideK K = stride_k_vreg(veh.dry_mass, veh.lift, veh.v0);      // the stride loop's fp64 constants as register pairs, once per launch (see d_vreg)
+  const StrideK K = stride_k_vreg(lveh.dry_mass, lveh.lift, lveh.v0);      // the stride loop's fp64 constants as register pairs, once per launch (see d_vreg)
   BLE_STEP_MARK(3);
 #pragma unroll 1
   for (int k = 0; k < n_steps; ++k) {
@@ -163,7 +185,7 @@ __global__ __launch_bounds__(kStepBlock) void ble_step_kernel(StateDev st, const
         asm volatile("" : "+v"(nu), "+v"(nv));
       } else if (noise_uv) { nu = noise_uv[2 * i]; nv = noise_uv[2 * i + 1]; }
       float r;
-      const int eff = agent_step(s, c, hc, act, corners, wq, nu, nv, substeps, acs_poly, K, term_save + wave * (kTermSaveRows * kTermSaveStride) + lane, &r, &flags, veh);
+      const int eff = agent_step(s, c, hc, act, corners, wq, nu, nv, substeps, acs_poly, K, term_save + wave * (kTermSaveRows * kTermSaveStride) + lane, &r, &flags, lveh);
       if (!(isfinite(s.p) && isfinite(s.t_int) && isfinite(s.x) && isfinite(s.y) && isfinite(s.batt)))
         flags |= kFlagNonFinite;
       reward[o] = r;
@@ -544,13 +566,41 @@ __global__ __launch_bounds__(256) void ble_wind_noise_kernel(const float* __rest
 // Philox(seed, env, episode[i]); sample == 0: keep x, y, pressure, centre lat/lng, IR, alpha,
 // start_unix as they are.  Then the Newton cold start (stable_init.py:132-157), the sunrise /
 // sunset search of PowerSafetyLayer.__init__ and fresh clocks / FSMs / battery (balloon.py:175-215).
+// VehicleFleet: every lane cold-starts with its own palette entry (staged in LDS as in ble_step_kernel); with sample_index the entry is
+// first drawn for the new episode from Philox(seed ^ kFleetDrawKey, env, episode[i]) -- a stream of its own, so the initial conditions
+// are the draws of the other instantiations bit for bit.
+constexpr unsigned long long kFleetDrawKey = 0xF1EE7C0DEull;
 template <class V = VehicleDefault>
 __global__ __launch_bounds__(kBlock) void ble_reset_kernel(StateDev st, const uint8_t* __restrict__ mask,
                                                            unsigned long long seed, uint32_t* episode, int sample,
                                                            uint32_t* err_flags, int64_t n, int64_t env_offset, V veh) {
   const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
   uint32_t flags = 0;
-  if (i < n && (mask == nullptr || mask[i] != 0)) {
+  double* fleet_lds = nullptr;
+  int vidx = 0;
+  bool frozen = false;          // (a fleet) an index outside the palette
+  if constexpr (IsFleet<V>::value) {
+    __shared__ double fleet_lds_[kFleetRtFields * kFleetMaxVehicles];
+    fleet_lds = fleet_lds_;
+    for (int j = (int)threadIdx.x; j < kFleetRtFields * kFleetMaxVehicles; j += kBlock) fleet_lds[j] = (&veh.f[0][0])[j];
+    __syncthreads();
+    if (i < n && (mask == nullptr || mask[i] != 0)) {
+      if (sample && veh.sample_index) {
+        Philox g = philox_init(seed ^ kFleetDrawKey, (uint64_t)(i + env_offset), episode ? episode[i] : 0u);
+        vidx = (int)(((uint64_t)philox_u32(g) * (uint64_t)veh.n_vehicles) >> 32);        // uniform in [0, n_vehicles)
+        veh.index[i] = (uint8_t)vidx;
+      } else {
+        vidx = veh.index[i];
+        if (vidx >= veh.n_vehicles) {          // the lane is left as it is (its episode counter included)
+          flags |= kFlagVehicleIndex;
+          frozen = true;
+          vidx = 0;
+        }
+      }
+    }
+  }
+  const auto& lveh = lane_vehicle(veh, fleet_lds, vidx);
+  if (i < n && (mask == nullptr || mask[i] != 0) && (!IsFleet<V>::value || !frozen)) {      // (the other carriers: the condition it always was)
     float alpha, x, y, p, lat0, lng0, ir;
     int64_t start;
     if (sample) {
@@ -591,7 +641,7 @@ __global__ __launch_bounds__(kBlock) void ble_reset_kernel(StateDev st, const ui
     latlng_f64((double)lat0, (double)lng0, (double)x, (double)y, &site.sin_lat, &site.cos_lat, &site.lng_deg);
     double flux;
     const double el = solar_elevation_f64(site.sin_lat, site.cos_lat, site.lng_deg, start, &flux);
-    const StableParams sp = stable_params((double)alpha, (double)p, el, flux, (double)ir, &flags, veh);
+    const StableParams sp = stable_params((double)alpha, (double)p, el, flux, (double)ir, &flags, lveh);
     int64_t sunrise, sunset;
     next_sunrise_sunset(site, start, &sunrise, &sunset);
     st.ambient_temperature[i] = (float)sp.t_amb; st.internal_temperature[i] = (float)sp.t_int;
@@ -758,6 +808,35 @@ inline VehicleRt make_vehicle_rt(const ble_vehicle* v) {
   r.sp_hi = r.max_sp - 250.0;
   return r;
 }
+
+// ble_fleet -> the kernels' VehicleFleet: every entry through make_vehicle_rt (the doubles a single-vehicle call derives), transposed into
+// the field-major image; entries beyond n_vehicles stay zero and are never read (an index >= n_vehicles freezes its lane).
+static_assert(kFleetMaxVehicles == BLE_FLEET_MAX_VEHICLES, "ble_physics.h and ble_abi.h disagree on the fleet size");
+inline bool fleet_ok(const ble_state_f32* st, const ble_fleet* f) {
+  if (f == nullptr || f->palette == nullptr || f->vehicle_index == nullptr || f->n_vehicles < 1 || f->n_vehicles > BLE_FLEET_MAX_VEHICLES)
+    return false;
+  if (st->vehicle != nullptr) return false;                // two sources of the vehicle: refused, not merged
+  for (int k = 0; k < f->n_vehicles; ++k)
+    if (!vehicle_ok(&f->palette[k])) return false;
+  return true;
+}
+inline VehicleFleet make_fleet(const ble_fleet* f) {
+  VehicleFleet v;
+  __builtin_memset(&v, 0, sizeof v);
+  for (int k = 0; k < f->n_vehicles; ++k) {
+    const VehicleRt r = make_vehicle_rt(&f->palette[k]);
+#define BLE_FLEET_PUT(j, m) v.f[j][k] = (double)r.m;
+    BLE_FLEET_RT_FIELDS(BLE_FLEET_PUT)
+#undef BLE_FLEET_PUT
+  }
+  v.index = f->vehicle_index; v.n_vehicles = f->n_vehicles; v.sample_index = f->sample_index != 0;
+  return v;
+}
+// The palette travels as a kernel argument (3 KB).  HIP bounds a launch's argument block by 4 KB; the largest fleet argument lists --
+// the transition's and the observation's -- stay below it (a bound on their sizes: every scalar argument counted as 8 bytes).
+constexpr size_t kKernargLimit = 4096;
+static_assert(sizeof(StateDev) + 12 * 8 + sizeof(StepNoise) + sizeof(VehicleFleet) <= kKernargLimit, "ble_step_kernel<VehicleFleet>'s arguments");
+static_assert(sizeof(StateDev) + 10 * 8 + sizeof(GpHistory) + sizeof(VehicleFleet) <= kKernargLimit, "ble_observe_kernel<VehicleFleet>'s arguments");
 
 }  // namespace
 
@@ -1067,6 +1146,67 @@ int ble_probe_safety_f32(int layer, const uint8_t* action, const float* value, c
   if (n == 0) return BLE_OK;
   BLE_LAUNCH(probe_safety_kernel, dim3(blocks(n, 256)), dim3(256), 0, (hipStream_t)stream, layer, action, value, alpha,
                      clocks, night_load_w, capacity_wh, fsm, effective_action, err_flags, n);
+  return launch_status();
+}
+
+// ---- fleets (include/ble_abi.h::ble_fleet): the one-lane transition, the reset and the observation with a palette
+int ble_step_fleet_f32(const ble_state_f32* st, const ble_fleet* fleet, const uint8_t* action, const float* wind_grid, int64_t grid_env_stride,
+                       const float* noise_uv, float* reward, uint8_t* terminal, uint8_t* effective_action, uint32_t* err_flags,
+                       unsigned long long* active_count, int64_t n, int substeps, void* stream) {
+  if (!state_ok(st) || !action || !wind_grid || !reward || !terminal || n < 0 || substeps < 1 || substeps > BLE_MAX_SUBSTEPS ||
+      grid_env_stride < 0 || !fleet_ok(st, fleet))
+    return BLE_E_INVALID_ARG;
+  if (n == 0) return BLE_OK;
+  const int lanes = env_lanes();
+  BLE_LAUNCH((ble_step_kernel<false, VehicleFleet>), dim3(blocks(n, lanes * (kStepBlock / 64))), dim3(kStepBlock), 0, (hipStream_t)stream,
+             state_dev(st), action, wind_grid, grid_env_stride, noise_uv, reward, terminal, effective_action, err_flags, active_count, n, substeps,
+             lanes, 1, StepNoise{0ull, nullptr, nullptr, 0ll}, make_fleet(fleet));
+  return launch_status();
+}
+
+int ble_step_n_fleet_f32(const ble_state_f32* st, const ble_fleet* fleet, const uint8_t* action, const float* wind_grid, int64_t grid_env_stride,
+                         const ble_noise_gen* noise, float* reward, uint8_t* terminal, uint32_t* err_flags, unsigned long long* active_count,
+                         int64_t n, int substeps, int n_steps, void* stream) {
+  if (!state_ok(st) || !action || !wind_grid || !reward || !terminal || n < 0 || substeps < 1 || substeps > BLE_MAX_SUBSTEPS || n_steps < 0 ||
+      grid_env_stride < 0 || (noise != nullptr && noise->env_offset < 0) || !fleet_ok(st, fleet))
+    return BLE_E_INVALID_ARG;
+  if (n == 0 || n_steps == 0) return BLE_OK;
+  const int lanes = env_lanes();
+  const VehicleFleet veh = make_fleet(fleet);
+  if (noise != nullptr)
+    BLE_LAUNCH((ble_step_kernel<true, VehicleFleet>), dim3(blocks(n, lanes * (kStepBlock / 64))), dim3(kStepBlock), 0, (hipStream_t)stream,
+               state_dev(st), action, wind_grid, grid_env_stride, (const float*)nullptr, reward, terminal, (uint8_t*)nullptr, err_flags, active_count,
+               n, substeps, lanes, n_steps, StepNoise{noise->seed, noise->episode, noise->harmonic_cache, (long long)noise->env_offset}, veh);
+  else
+    BLE_LAUNCH((ble_step_kernel<false, VehicleFleet>), dim3(blocks(n, lanes * (kStepBlock / 64))), dim3(kStepBlock), 0, (hipStream_t)stream,
+               state_dev(st), action, wind_grid, grid_env_stride, (const float*)nullptr, reward, terminal, (uint8_t*)nullptr, err_flags, active_count,
+               n, substeps, lanes, n_steps, StepNoise{0ull, nullptr, nullptr, 0ll}, veh);
+  return launch_status();
+}
+
+int ble_reset_fleet_at_f32(const ble_state_f32* st, const ble_fleet* fleet, const uint8_t* mask, unsigned long long seed, uint32_t* episode,
+                           int sample, uint32_t* err_flags, int64_t env_offset, int64_t n, void* stream) {
+  if (!state_ok(st) || n < 0 || env_offset < 0 || !fleet_ok(st, fleet)) return BLE_E_INVALID_ARG;
+  if (n == 0) return BLE_OK;
+  BLE_LAUNCH(ble_reset_kernel<VehicleFleet>, dim3(blocks(n, kBlock)), dim3(kBlock), 0, (hipStream_t)stream, state_dev(st), mask, seed,
+             episode, sample, err_flags, n, env_offset, make_fleet(fleet));
+  return launch_status();
+}
+
+int ble_observe_forecast_fleet_f32(const ble_state_f32* st, const ble_fleet* fleet, const float* wind_grid, int64_t grid_env_stride,
+                                   const float* forecast_levels, const float* noise_uv, const uint8_t* reset_mask, const ble_gp_history_f32* hist,
+                                   int append, float* obs, uint32_t* err_flags, int64_t n, void* stream) {
+  if (!state_ok(st) || !wind_grid || !hist || !hist->xyp || !hist->elapsed_s || !hist->err_uv || !hist->count || !obs ||
+      n < 0 || grid_env_stride < 0 || !fleet_ok(st, fleet))
+    return BLE_E_INVALID_ARG;
+  GpHistory h;
+  h.xyp = hist->xyp; h.elapsed_s = hist->elapsed_s; h.err_uv = hist->err_uv; h.count = hist->count;
+  h.chol = hist->chol; h.n_chol = hist->n_chol; h.chol_stride = hist->chol_stride;
+  if (h.chol != nullptr && (h.n_chol == nullptr || h.chol_stride < (int64_t)kCholStride || (h.chol_stride & 1) != 0))
+    return BLE_E_INVALID_ARG;
+  if (n == 0) return BLE_OK;
+  BLE_LAUNCH(ble_observe_kernel<VehicleFleet>, dim3((unsigned)n), dim3(kObsBlock), 0, (hipStream_t)stream, state_dev(st), wind_grid,
+             grid_env_stride, noise_uv, reset_mask, h, append, obs, err_flags, n, make_fleet(fleet), forecast_levels);
   return launch_status();
 }
 

@@ -342,7 +342,7 @@ __global__ __launch_bounds__(kObsBlock, 2) void ble_observe_kernel(StateDev st, 
                                                                 const float* __restrict__ noise_uv,
                                                                 const uint8_t* __restrict__ reset_mask, GpHistory hist,
                                                                 int append, float* __restrict__ obs,
-                                                                uint32_t* err_flags, int64_t n, Veh veh,
+                                                                uint32_t* err_flags, int64_t n, Veh veh_arg,
                                                                 const float* __restrict__ forecast_levels) {
   __shared__ ObsShared sh;
   BLE_OBS_INSTR_BEGIN();        // (profiling builds only; nothing in the product build)
@@ -354,6 +354,17 @@ __global__ __launch_bounds__(kObsBlock, 2) void ble_observe_kernel(StateDev st, 
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);          // scalar: `if (wave == ...)` is a real branch, not an exec mask
   uint32_t flags = 0;
+  // the vehicle: the argument itself, or (a fleet) this environment's palette entry -- uniform over the workgroup, so its VehicleRt is
+  // read with scalar loads from the argument and the code from here on is the VehicleRt instantiation's
+  int vidx = 0;
+  if constexpr (IsFleet<Veh>::value) {
+    vidx = __builtin_amdgcn_readfirstlane((int)veh_arg.index[env]);
+    if (vidx >= veh_arg.n_vehicles) {              // frozen: history and observation untouched (the whole workgroup leaves)
+      if (tid == 0 && err_flags != nullptr) atomicOr(err_flags, (uint32_t)kFlagVehicleIndex);
+      return;
+    }
+  }
+  const auto& veh = lane_vehicle(veh_arg, fleet_image(veh_arg), vidx);
 
   // ---- state of this environment (uniform loads)
   const float xf = st.x[env], yf = st.y[env], pf = st.pressure[env];

@@ -89,12 +89,50 @@ struct VehicleRt {
   bool power_layer;
   double inv_capacity, ceiling_target, sp_hi;
 };
+// The third carrier (include/ble_abi.h::ble_fleet): a palette of up to kFleetMaxVehicles VehicleRt, derived on the host by the same
+// make_vehicle_rt, and a device byte per environment naming its entry.  It is the kernel ARGUMENT of the fleet instantiations; the lane
+// functions never see it: a kernel resolves it into the VehicleRt of each lane (transition, reset: per lane, through LDS) or of its
+// workgroup (observation: one environment per workgroup, scalar) and hands that on -- the same lane functions, the same arithmetic.
+constexpr int kFleetMaxVehicles = 16;
+// VehicleRt's members in the order of the fleet's field-major image (a cast to double is exact for each: floats, the bool)
+#define BLE_FLEET_RT_FIELDS(X) X(0, v0) X(1, dvdp) X(2, four_dvdp) X(3, inv_dvdp) X(4, inv_cbrt_v0) X(5, lift) X(6, dry_mass) \
+  X(7, envelope_mass) X(8, payload_mass) X(9, he_mass) X(10, max_sp) X(11, drag_arg) X(12, thermal_scale) X(13, valve_k) X(14, night_load_d) \
+  X(15, capacity_d) X(16, day_load_d) X(17, day_load) X(18, night_load) X(19, capacity) X(20, power_layer) X(21, inv_capacity) \
+  X(22, ceiling_target) X(23, sp_hi)
+constexpr int kFleetRtFields = 24;
+// The palette as the kernels receive it: field-major, [field][kFleetMaxVehicles] doubles -- the image the transition and the reset copy
+// into LDS as it is (lanes on different vehicles then read consecutive banks, lanes on the same one broadcast) and the observation reads
+// one column of with scalar loads
+struct VehicleFleet {
+  double f[kFleetRtFields][kFleetMaxVehicles];
+  uint8_t* index;              // [n] device (the reset writes it when it draws)
+  int32_t n_vehicles;
+  int32_t sample_index;        // the reset draws index[i] per episode
+};
+template <class V> struct IsFleet { static constexpr bool value = false; };
+template <> struct IsFleet<VehicleFleet> { static constexpr bool value = true; };
+// column k of a field-major palette image (LDS or the kernel argument) -> the VehicleRt that vehicle's lanes fly
+BLE_FN VehicleRt fleet_rt_from(const double* image, int k) {
+  VehicleRt r;
+#define BLE_FLEET_GET(j, m) r.m = (decltype(r.m))image[(j) * kFleetMaxVehicles + k];
+  BLE_FLEET_RT_FIELDS(BLE_FLEET_GET)
+#undef BLE_FLEET_GET
+  return r;
+}
+// the vehicle a lane flies: the kernel's vehicle argument itself, or -- a fleet -- its palette entry `k`
+template <class V>
+BLE_FN const V& lane_vehicle(const V& v, const double*, int) { return v; }
+BLE_FN VehicleRt lane_vehicle(const VehicleFleet&, const double* image, int k) { return fleet_rt_from(image, k); }
+// the palette image of a fleet argument as it arrived (kernel argument memory), nullptr for the other carriers
+template <class V>
+BLE_FN const double* fleet_image(const V&) { return nullptr; }
+BLE_FN const double* fleet_image(const VehicleFleet& v) { return &v.f[0][0]; }
 
 // control.py / balloon.py enums
 enum : int { kDown = 0, kStay = 1, kUp = 2 };
 enum : int { kOk = 0, kOutOfPower = 1, kBurst = 2, kZeroPressure = 3 };
 enum : uint32_t { kFlagPressureRange = 1u, kFlagAbsorptivity = 2u, kFlagSolarRange = 4u,
-                  kFlagPowerTable = 16u, kFlagNonFinite = 32u };
+                  kFlagPowerTable = 16u, kFlagNonFinite = 32u, kFlagVehicleIndex = 512u };
 
 // ---------------------------------------------------------------- fp64 helpers over the intrinsic layer
 // fp64 reciprocal / reciprocal-sqrt: hardware seed (v_rcp_f64 / v_rsq_f64, measured 4.3e-8 /

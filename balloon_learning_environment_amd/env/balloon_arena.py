@@ -49,11 +49,20 @@ class VecBalloonArena:
   lane flies in its previous field)."""
 
   def __init__(self, num_envs: int, wind_field_instance: Optional[grid_based_wind_field.GridBasedWindField] = None,
-               seed: Optional[int] = None, device='cuda:0', per_env_fields: bool = False, env_offset: int = 0):
+               seed: Optional[int] = None, device='cuda:0', per_env_fields: bool = False, env_offset: int = 0,
+               vehicles=None, vehicle_index=None, sample_vehicles: bool = False):
     """env_offset: this arena's environment 0 in the global batch of a sharded job (vec_state.VecSimulator): with one seed for
-    the job the shards reset and fly in the noise exactly as the unsharded batch would."""
+    the job the shards reset and fly in the noise exactly as the unsharded batch would.
+    vehicles: a fleet -- 1 .. 16 vehicles (dicts in VecSimulator.set_vehicle's keyword form) flown in one batch; vehicle_index (uint8
+    [num_envs], default all 0) names each environment's; sample_vehicles=True draws every environment's vehicle anew at each reset
+    (domain randomisation over the palette).  The palette is read by each call: a captured graph keeps the one it was recorded with
+    (VecSimulator.set_fleet)."""
     self.num_envs = int(num_envs)
     self.sim = vec_state.VecSimulator(self.num_envs, device, env_offset=env_offset)
+    if vehicles is not None:
+      self.sim.set_fleet(vehicles, vehicle_index, sample_vehicles)
+    elif vehicle_index is not None or sample_vehicles:
+      raise ValueError('vehicle_index / sample_vehicles need a fleet: pass vehicles=[...]')
     self.device = self.sim.device
     if wind_field_instance is None:
       from balloon_learning_environment_amd.env import generative_wind_field
@@ -177,13 +186,25 @@ class VecBalloonArena:
     return self.sim.row_dict(self.sim.rows(i, 1)[0].cpu().tolist())
 
   def get_balloon_state(self, i: int = 0) -> balloon.BalloonState:
-    return balloon.state_from_row(self.row(i), self.sim.vehicle)
+    """Environment i's BalloonState, with the vehicle it flies (its fleet entry when the batch is a fleet)."""
+    return balloon.state_from_row(self.row(i), self.sim.vehicle_of(i))
 
   def set_balloon_state(self, new_state: balloon.BalloonState, i: int = 0) -> None:
-    # the state's flight-vehicle constants (balloon.py:156-173,183,200): one vehicle per batch (ble_state_f32.vehicle)
+    """Writes a BalloonState into environment i.  Its flight-vehicle constants (balloon.py:156-173,183,200): in a fleet, the state's
+    vehicle is looked up in the palette or appended to it (at most 16; a captured graph then needs capturing again) and becomes
+    environment i's entry; without a fleet the batch flies one vehicle, which a batch of one takes over and a larger batch refuses
+    to change."""
     veh = _abi.vehicle_struct(**balloon.vehicle_of(new_state))
     overrides = {} if veh is None else {k: getattr(veh, k) for k in _abi.VEHICLE_DEFAULTS if getattr(veh, k) != _abi.VEHICLE_DEFAULTS[k]}
-    if overrides != self.sim.vehicle:
+    if self.sim.has_fleet:
+      palette = list(self.sim.fleet_vehicles)
+      if overrides not in palette:
+        if len(palette) == _abi.FLEET_MAX_VEHICLES:
+          raise ValueError(f'the fleet palette holds {_abi.FLEET_MAX_VEHICLES} vehicles already: this one is not among them')
+        palette.append(overrides)
+        self.sim.set_fleet(palette, self.sim.vehicle_index, self.sim.sample_vehicles)
+      self.sim.vehicle_index[i] = palette.index(overrides)
+    elif overrides != self.sim.vehicle:
       if self.num_envs != 1:
         raise ValueError('all environments of a batch fly one vehicle: VecSimulator.set_vehicle(...) sets it for the batch')
       self.sim.set_vehicle(**overrides)

@@ -150,12 +150,17 @@ class VecBalloonEnv:
   """
 
   def __init__(self, num_envs: int, *, seed: int = 0, wind_field=None, wind_noise: bool = True,
-               auto_reset: bool = True, per_env_fields: bool = False, field_refresh_every: int = 32, device='cuda:0'):
+               auto_reset: bool = True, per_env_fields: bool = False, field_refresh_every: int = 32, device='cuda:0',
+               vehicles=None, vehicle_index=None, sample_vehicles: bool = False):
     """wind_noise=True (default, as the reference): ground truth = forecast + SimplexWindNoise, so the WindGP
     has an error signal to model; False is the opt-out (forecast == truth, every GP error exactly 0).
     Wind fields: see VecBalloonArena (default: generative sampler, one shared field per reset();
-    per_env_fields=True: one decoded field per environment and per episode)."""
-    self.arena = balloon_arena.VecBalloonArena(num_envs, wind_field, seed=seed, device=device, per_env_fields=per_env_fields)
+    per_env_fields=True: one decoded field per environment and per episode).
+    vehicles / vehicle_index / sample_vehicles: a fleet of up to 16 vehicles in the batch, each environment's entry given or (sample_vehicles)
+    drawn at every reset, auto-resets included -- under capture_graph() replay too, the index being device memory.  The palette is read
+    when a call is made: a graph captured before a palette change keeps the old palette, so capture again (VecBalloonArena)."""
+    self.arena = balloon_arena.VecBalloonArena(num_envs, wind_field, seed=seed, device=device, per_env_fields=per_env_fields,
+                                               vehicles=vehicles, vehicle_index=vehicle_index, sample_vehicles=sample_vehicles)
     self.num_envs, self.device = self.arena.num_envs, self.arena.device
     self._seed, self._wind_noise, self._auto_reset = int(seed), bool(wind_noise), bool(auto_reset)
     self._field_refresh_every, self._steps_since_refresh = int(field_refresh_every), 0

@@ -40,6 +40,8 @@ def raise_for_flags(flags: int) -> None:
     raise ValueError('Unable to find safe pressure for balloon.')       # pressure_range_builder.py:180-182
   if flags & _lib.FLAG_DAY_CYCLE:
     raise ZeroDivisionError('float division by zero')                     # features.py:432-437 at a station in polar night
+  if flags & _lib.FLAG_VEHICLE_INDEX:
+    raise ValueError('vehicle_index outside the fleet palette: those environments were not stepped, reset or observed')
   if flags & _lib.FLAG_GP_WINDOW:
     raise OverflowError('WindGP window holds more than 120 observations (agent steps shorter than 180 s)')
 
@@ -77,6 +79,12 @@ class VecSimulator:
       self.episode_cache = torch.zeros(_abi.EPISODE_CACHE_ROWS, self.n, dtype=torch.float64, device=self.device)
     self._struct = dev.state_struct(self.state, self.episode_cache)
     self.vehicle: Dict[str, float] = {}     # the BalloonState vehicle fields that differ from the reference's defaults (set_vehicle)
+    # a fleet (set_fleet): the palette (override dicts), the device index of each environment's entry, the per-episode draw -- and the ONE
+    # ble_fleet struct every call gets (updated in place, so that prepared launches see a new palette)
+    self.fleet_vehicles: Optional[list] = None
+    self.vehicle_index: Optional[torch.Tensor] = None
+    self.sample_vehicles = False
+    self._fleet: Optional[_abi.BleFleet] = None
     self._noise_cache = None        # per-episode draws of the wind noise's harmonics (allocated by the first wind_noise())
     self._noise_gens = []           # the ble_noise_gen structs handed out (prepared launches hold them): load_state_dict re-keys them
     self._gp = None                 # WindGP history ring (allocated by the first observe())
@@ -140,6 +148,60 @@ class VecSimulator:
     veh = _abi.vehicle_struct(**fields)
     _abi.set_vehicle(self._struct, veh)
     self.vehicle = {} if veh is None else {k: getattr(veh, k) for k in _abi.VEHICLE_DEFAULTS if getattr(veh, k) != _abi.VEHICLE_DEFAULTS[k]}
+    self.fleet_vehicles, self.sample_vehicles = None, False        # one vehicle for the batch: no fleet
+    if self._fleet is not None:
+      self._fleet.n_vehicles = 0                                  # (a launch prepared for the fleet would be refused, not misflown)
+
+  @staticmethod
+  def vehicle_overrides(fields: dict) -> Dict[str, float]:
+    """set_vehicle's keyword form, normalised: the fields that differ from the reference's defaults, with their stored types."""
+    veh = _abi.vehicle_struct(**fields)
+    return {} if veh is None else {k: getattr(veh, k) for k in _abi.VEHICLE_DEFAULTS if getattr(veh, k) != _abi.VEHICLE_DEFAULTS[k]}
+
+  def set_fleet(self, vehicles, index: Optional[torch.Tensor] = None, sample_per_episode: bool = False) -> None:
+    """Environments on DIFFERENT vehicles in one batch (ble_fleet): `vehicles` is a palette of 1 .. 16 vehicles, each a dict in
+    set_vehicle's keyword form ({} = the reference's defaults); `index` a uint8 tensor [n] naming each environment's entry (None: all
+    0).  From now on step, step_n, prepare_step_n's launches, reset_device and observe call the fleet entry points; set_vehicle(...)
+    ends the fleet.  sample_per_episode: every device reset with sampling (reset_device(sample=True)) draws each reset environment's
+    entry anew, uniformly, from a Philox stream keyed by (seed, env_offset + i, episode) that leaves the initial conditions as they are.
+    The index lives in device memory (`vehicle_index`): a captured HIP graph sees its changes, redrawn ones included.  The palette is
+    read by each call on the host: launches prepared by prepare_step_n see a new palette, a captured graph does NOT (it keeps the
+    palette it was recorded with) -- capture again after set_fleet, as after set_vehicle."""
+    vehicles = [self.vehicle_overrides(dict(v)) for v in vehicles]
+    if not 1 <= len(vehicles) <= _abi.FLEET_MAX_VEHICLES:
+      raise ValueError(f'a fleet has 1 .. {_abi.FLEET_MAX_VEHICLES} vehicles, not {len(vehicles)}')
+    if self.vehicle_index is None:
+      with torch.cuda.device(self.device):
+        self.vehicle_index = torch.zeros(self.n, dtype=torch.uint8, device=self.device)
+    if index is None:
+      self.vehicle_index.zero_()
+    else:
+      index = torch.as_tensor(index)
+      assert tuple(index.shape) == (self.n,), index.shape
+      self.vehicle_index.copy_(index.to(torch.uint8))             # in place: prepared launches and graphs hold its address
+    _abi.set_vehicle(self._struct, None)
+    self.vehicle = {}
+    self.fleet_vehicles, self.sample_vehicles = vehicles, bool(sample_per_episode)
+    fleet = _abi.fleet_struct(vehicles, self.vehicle_index.data_ptr(), self.sample_vehicles)
+    if self._fleet is None:
+      self._fleet = fleet
+    else:                        # the same struct, new contents
+      for name, _ in _abi.BleFleet._fields_:
+        setattr(self._fleet, name, getattr(fleet, name))
+      self._fleet._palette_keepalive = fleet._palette_keepalive
+
+  @property
+  def has_fleet(self) -> bool:
+    return self.fleet_vehicles is not None
+
+  def vehicle_of(self, i: int) -> Dict[str, float]:
+    """The vehicle environment i flies (override dict): its fleet entry, or the batch's vehicle."""
+    if not self.has_fleet:
+      return dict(self.vehicle)
+    k = int(self.vehicle_index[i].item())
+    if k >= len(self.fleet_vehicles):
+      raise ValueError(f'environment {i}: vehicle_index {k} outside the palette of {len(self.fleet_vehicles)}')
+    return dict(self.fleet_vehicles[k])
 
   # ------------------------------------------------------------------ reset on the device
   @_on_own_device
@@ -148,10 +210,16 @@ class VecSimulator:
     draws (if `sample`), Newton cold start, sunrise/sunset search, fresh clocks and FSMs."""
     if mask is not None:
       assert mask.dtype == torch.uint8 and mask.is_contiguous() and mask.numel() == self.n
-    code = self.lib.ble_reset_at_f32(ctypes.byref(self._struct), dev.ptr(mask), int(seed) & (2 ** 64 - 1),
-                                     self.episode.data_ptr(), 1 if sample else 0, self.err_flags.data_ptr(), self.env_offset, self.n,
-                                     dev.stream_ptr(self.device))
-    _lib.check(code, 'ble_reset_at_f32')
+    if self.has_fleet:
+      code = self.lib.ble_reset_fleet_at_f32(ctypes.byref(self._struct), ctypes.byref(self._fleet), dev.ptr(mask), int(seed) & (2 ** 64 - 1),
+                                             self.episode.data_ptr(), 1 if sample else 0, self.err_flags.data_ptr(), self.env_offset, self.n,
+                                             dev.stream_ptr(self.device))
+      _lib.check(code, 'ble_reset_fleet_at_f32')
+    else:
+      code = self.lib.ble_reset_at_f32(ctypes.byref(self._struct), dev.ptr(mask), int(seed) & (2 ** 64 - 1),
+                                       self.episode.data_ptr(), 1 if sample else 0, self.err_flags.data_ptr(), self.env_offset, self.n,
+                                       dev.stream_ptr(self.device))
+      _lib.check(code, 'ble_reset_at_f32')
     if self._gp is not None:        # a new episode gets a new feature constructor (balloon_arena.py:171-177)
       if mask is None:
         self._obs_reset.fill_(1)
@@ -179,11 +247,12 @@ class VecSimulator:
     assert out.dtype == torch.float32 and out.is_contiguous() and tuple(out.shape) == (self.n, _lib.OBS_DIM)
     if forecast_levels is not None:
       assert forecast_levels.dtype == torch.float32 and forecast_levels.is_contiguous() and tuple(forecast_levels.shape) == (self.n, 181, 2)
-    code = self.lib.ble_observe_forecast_f32(ctypes.byref(self._struct), self.grid.data_ptr(), self.grid_env_stride, dev.ptr(forecast_levels),
-                                             dev.ptr(noise_uv), self._obs_reset.data_ptr(), ctypes.byref(self._gp_struct),
-                                             1 if append else 0, out.data_ptr(), self.err_flags.data_ptr(), self.n,
-                                             dev.stream_ptr(self.device))
-    _lib.check(code, 'ble_observe_forecast_f32')
+    args = (self.grid.data_ptr(), self.grid_env_stride, dev.ptr(forecast_levels), dev.ptr(noise_uv), self._obs_reset.data_ptr(),
+            ctypes.byref(self._gp_struct), 1 if append else 0, out.data_ptr(), self.err_flags.data_ptr(), self.n, dev.stream_ptr(self.device))
+    if self.has_fleet:
+      _lib.check(self.lib.ble_observe_forecast_fleet_f32(ctypes.byref(self._struct), ctypes.byref(self._fleet), *args), 'ble_observe_forecast_fleet_f32')
+    else:
+      _lib.check(self.lib.ble_observe_forecast_f32(ctypes.byref(self._struct), *args), 'ble_observe_forecast_f32')
     self._obs_reset.zero_()         # stream-ordered after the kernel
     return out
 
@@ -217,7 +286,9 @@ class VecSimulator:
     d = {'n': self.n, 'env_offset': self.env_offset, 'vehicle': dict(self.vehicle), 'noise_primitive_version': _lib.NOISE_PRIMITIVE_VERSION,
          'state': {k: t.clone() for k, t in self.state.items()}, 'episode': self.episode.clone(),
          'active_slots': self.active_slots.clone(), 'err_flags': self.err_flags.clone(),
-         'grid': None if self.grid is None else self.grid.clone(), 'grid_env_stride': self.grid_env_stride, 'gp': None}
+         'grid': None if self.grid is None else self.grid.clone(), 'grid_env_stride': self.grid_env_stride, 'gp': None,
+         'fleet': None if not self.has_fleet else {'vehicles': [dict(v) for v in self.fleet_vehicles], 'index': self.vehicle_index.clone(),
+                                                   'sample': self.sample_vehicles}}
     if self._gp is not None:
       d['gp'] = {k: t.clone() for k, t in self._gp.items()}
       d['obs_reset'] = self._obs_reset.clone()
@@ -244,6 +315,8 @@ class VecSimulator:
       for gen in self._noise_gens:
         gen.env_offset = offset
     self.set_vehicle(**d.get('vehicle', {}))
+    if d.get('fleet') is not None:          # (a checkpoint without a fleet -- every one before fleets existed -- loads as before)
+      self.set_fleet(d['fleet']['vehicles'], d['fleet']['index'], bool(d['fleet']['sample']))
     for k, t in self.state.items():
       t.copy_(d['state'][k])
     self.episode.copy_(d['episode']); self.active_slots.copy_(d['active_slots']); self.err_flags.copy_(d['err_flags'])
@@ -302,12 +375,13 @@ class VecSimulator:
     assert action.device == self.device
     if noise_uv is not None:
       assert noise_uv.dtype == torch.float32 and noise_uv.is_contiguous() and tuple(noise_uv.shape) == (self.n, 2)
-    code = self.lib.ble_step_f32(ctypes.byref(self._struct), action.data_ptr(), self.grid.data_ptr(),
-                                 self.grid_env_stride, dev.ptr(noise_uv), self.reward.data_ptr(),
-                                 self.terminal.data_ptr(), self.effective_action.data_ptr(),
-                                 self.err_flags.data_ptr(), self.active_slots.data_ptr(), self.n, substeps,
-                                 dev.stream_ptr(self.device))
-    _lib.check(code, 'ble_step_f32')
+    args = (action.data_ptr(), self.grid.data_ptr(), self.grid_env_stride, dev.ptr(noise_uv), self.reward.data_ptr(),
+            self.terminal.data_ptr(), self.effective_action.data_ptr(), self.err_flags.data_ptr(), self.active_slots.data_ptr(), self.n,
+            substeps, dev.stream_ptr(self.device))
+    if self.has_fleet:
+      _lib.check(self.lib.ble_step_fleet_f32(ctypes.byref(self._struct), ctypes.byref(self._fleet), *args), 'ble_step_fleet_f32')
+    else:
+      _lib.check(self.lib.ble_step_f32(ctypes.byref(self._struct), *args), 'ble_step_f32')
     return self.reward, self.terminal
 
   def _noise_gen(self, noise_seed: Optional[int], prepared: bool = False):
@@ -337,11 +411,12 @@ class VecSimulator:
       assert active_counts.dtype == torch.int64 and tuple(active_counts.shape) == (k, COUNT_SLOTS)
       assert active_counts.is_contiguous()
     gen = self._noise_gen(noise_seed)
-    code = self.lib.ble_step_n_f32(ctypes.byref(self._struct), actions.data_ptr(), self.grid.data_ptr(),
-                                   self.grid_env_stride, None if gen is None else ctypes.byref(gen), rewards.data_ptr(),
-                                   terminals.data_ptr(), self.err_flags.data_ptr(), dev.ptr(active_counts), self.n, substeps, k,
-                                   dev.stream_ptr(self.device))
-    _lib.check(code, 'ble_step_n_f32')
+    args = (actions.data_ptr(), self.grid.data_ptr(), self.grid_env_stride, None if gen is None else ctypes.byref(gen), rewards.data_ptr(),
+            terminals.data_ptr(), self.err_flags.data_ptr(), dev.ptr(active_counts), self.n, substeps, k, dev.stream_ptr(self.device))
+    if self.has_fleet:
+      _lib.check(self.lib.ble_step_n_fleet_f32(ctypes.byref(self._struct), ctypes.byref(self._fleet), *args), 'ble_step_n_fleet_f32')
+    else:
+      _lib.check(self.lib.ble_step_n_f32(ctypes.byref(self._struct), *args), 'ble_step_n_f32')
 
   def prepare_step_n(self, actions: torch.Tensor, rewards: torch.Tensor, terminals: torch.Tensor,
                      active_counts: Optional[torch.Tensor] = None, substeps: int = SUBSTEPS, noise_seed: Optional[int] = None):
@@ -357,11 +432,16 @@ class VecSimulator:
       assert active_counts.dtype == torch.int64 and tuple(active_counts.shape) == (k, COUNT_SLOTS)
       assert active_counts.is_contiguous()
     assert self.grid is not None, 'Must call set_grid (reset) before step.'
-    fn, struct = self.lib.ble_step_n_f32, ctypes.byref(self._struct)
+    # a fleet: the fleet entry point, with the simulator's one ble_fleet struct (set_fleet updates it in place).  Whether there IS a
+    # fleet is decided here: prepare again after set_fleet on a simulator without one, or after set_vehicle on one with a fleet
+    if self.has_fleet:
+      fn, struct = self.lib.ble_step_n_fleet_f32, (ctypes.byref(self._struct), ctypes.byref(self._fleet))
+    else:
+      fn, struct = self.lib.ble_step_n_f32, (ctypes.byref(self._struct),)
     gen = self._noise_gen(noise_seed, prepared=True)            # (kept alive by the closure)
     grid = self.grid                             # the closure reads THIS tensor: load_state_dict restores it in place
-    args = (struct, actions.data_ptr(), grid.data_ptr(), self.grid_env_stride, None if gen is None else ctypes.byref(gen),
-            rewards.data_ptr(), terminals.data_ptr(), self.err_flags.data_ptr(), dev.ptr(active_counts), self.n, substeps, k)
+    args = struct + (actions.data_ptr(), grid.data_ptr(), self.grid_env_stride, None if gen is None else ctypes.byref(gen),
+                     rewards.data_ptr(), terminals.data_ptr(), self.err_flags.data_ptr(), dev.ptr(active_counts), self.n, substeps, k)
     device, index = self.device, self.device.index
 
     def launch():
@@ -371,7 +451,7 @@ class VecSimulator:
       else:
         code = fn(*args, dev.stream_ptr(device))
       if code != 0:
-        _lib.check(code, 'ble_step_n_f32')
+        _lib.check(code, fn.__name__)
     return launch
 
   @property

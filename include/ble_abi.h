@@ -67,6 +67,8 @@ extern "C" {
 #define BLE_FLAG_PRESSURE_SEARCH 128u /* pressure_range_builder.py:104-108,180-182 ValueError */
 #define BLE_FLAG_DAY_CYCLE 256u    /* features.py:432-437 ZeroDivisionError: the next sunrise exactly one day after the next sunset
                                       (polar night); the two day-cycle features of that environment are NaN */
+#define BLE_FLAG_VEHICLE_INDEX 512u /* a fleet call (ble_fleet): an environment's vehicle_index >= n_vehicles -- the lane is frozen
+                                       (state, history and observation untouched), nothing is read outside the palette */
 
 /* wind grid geometry: generative/vae.py:30-38,77-93 (FieldShape defaults) */
 #define BLE_GRID_NX 21 /* x (lat axis of the grid), -500..500 km step 50 */
@@ -456,6 +458,47 @@ int ble_probe_safety_f32(int layer, const uint8_t* action, const float* value, c
  * sincos), element-wise on device doubles.  op: 0 rcp seed, 1 rcp, 2 rsq seed, 3 rsqrt,
  * 4 sqrt, 5 log, 6 exp, 7 sin, 8 cos.  Test-only. */
 int ble_probe_f64_prims(const double* x, double* y, int op, int64_t n, void* stream);
+
+/*
+ * Fleets: a batch whose environments fly DIFFERENT vehicles, in one call (additive to ABI 5; the single-vehicle entry points and
+ * ble_state_f32 are unchanged).  The reference builds one BalloonState per balloon, each with its own vehicle constants
+ * (balloon.py:156-173,183,200); a fleet is a palette of up to BLE_FLEET_MAX_VEHICLES such vehicles and, per environment, the index of
+ * the entry it flies.  Every palette entry is derived on the host exactly as ble_state_f32.vehicle is, so an environment flies bit
+ * for bit what a single-vehicle call with its entry as st->vehicle flies.
+ *   palette        HOST array [n_vehicles], read when the call is made, not retained (like ble_state_f32.vehicle): a captured graph
+ *                  keeps the palette it was recorded with
+ *   n_vehicles     1 .. BLE_FLEET_MAX_VEHICLES
+ *   sample_index   honoured by ble_reset_fleet_at_f32 only: != 0 together with sample != 0 draws vehicle_index[i] uniformly in
+ *                  [0, n_vehicles) for the new episode, from a Philox stream keyed by (seed, env_offset + i, episode[i]) that is
+ *                  disjoint from the initial conditions' (those stay bit for bit ble_reset_at_f32's), and writes it back
+ *   vehicle_index  DEVICE uint8[n]: the palette entry each environment flies.  An entry >= n_vehicles sets BLE_FLAG_VEHICLE_INDEX and
+ *                  freezes that environment for the call (reward 0, terminal 1, effective action = action; state untouched)
+ * The fleet entry points take the arguments of their single-vehicle counterparts plus `fleet` after `st`, and answer
+ * BLE_E_INVALID_ARG (before any HIP call) for a NULL fleet, palette or vehicle_index, n_vehicles outside 1 .. 16, a palette entry
+ * that ble_state_f32.vehicle would refuse, or st->vehicle != NULL (two sources of the vehicle are refused, not merged).
+ * The transition flies the one-lane-per-environment form at every batch size (as a run-time vehicle does).
+ */
+#define BLE_FLEET_MAX_VEHICLES 16
+typedef struct ble_fleet {
+  const ble_vehicle* palette;
+  int32_t n_vehicles;
+  int32_t sample_index;
+  uint8_t* vehicle_index;
+} ble_fleet;
+int ble_step_fleet_f32(const ble_state_f32* st, const ble_fleet* fleet, const uint8_t* action, const float* wind_grid,
+                       int64_t grid_env_stride, const float* noise_uv, float* reward, uint8_t* terminal,
+                       uint8_t* effective_action, uint32_t* err_flags, unsigned long long* active_count,
+                       int64_t n, int substeps, void* stream);
+int ble_step_n_fleet_f32(const ble_state_f32* st, const ble_fleet* fleet, const uint8_t* action, const float* wind_grid,
+                         int64_t grid_env_stride, const ble_noise_gen* noise, float* reward, uint8_t* terminal,
+                         uint32_t* err_flags, unsigned long long* active_count, int64_t n, int substeps, int n_steps,
+                         void* stream);
+int ble_reset_fleet_at_f32(const ble_state_f32* st, const ble_fleet* fleet, const uint8_t* mask, unsigned long long seed,
+                           uint32_t* episode, int sample, uint32_t* err_flags, int64_t env_offset, int64_t n, void* stream);
+int ble_observe_forecast_fleet_f32(const ble_state_f32* st, const ble_fleet* fleet, const float* wind_grid, int64_t grid_env_stride,
+                                   const float* forecast_levels, const float* noise_uv, const uint8_t* reset_mask,
+                                   const ble_gp_history_f32* hist, int append, float* obs, uint32_t* err_flags, int64_t n,
+                                   void* stream);
 
 #ifdef __cplusplus
 }

@@ -15,12 +15,13 @@ for b in blocks:
   mangled = b.split()[0]
   m = re.search(r'(\d+)(ble_\w+kernel|probe_\w+kernel)', mangled)
   name = mangled
-  if m:      # template arguments: a bool (noise generated in-kernel) and / or the vehicle carrier (ABI 5: compile-time defaults | run-time struct)
+  if m:      # template arguments: a bool (noise generated in-kernel) and / or the vehicle carrier (ABI 5: compile-time defaults | run-time struct | a fleet's palette)
     targs = mangled[m.end():].split('StateDev')[0].split('SplitArgs')[0]          # (what stands between the name and the first parameter)
     args = []
     if targs.startswith('ILb1E'): args.append('noise')
     elif targs.startswith('ILb0E'): args.append('no noise')
-    if 'VehicleRt' in targs: args.append('VehicleRt')
+    if 'VehicleFleet' in targs: args.append('VehicleFleet')
+    elif 'VehicleRt' in targs: args.append('VehicleRt')
     elif 'VehicleDefault' in targs: args.append('VehicleDefault')
     name = m.group(2) + ('<' + ', '.join(args) + '>' if args else '')
   out.append('| `' + name + '` | ' + ' | '.join(re.search(pat + r': (\d+)', b).group(1) for _, pat in keys) + ' |')
