@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
 """Headline benchmark: env-steps/s of the vectorised BLE transition on MI355X.
 
-  python bench.py                                   # N = 1, BASELINE.json configs[2] + every 1-GPU leg
+  python bench.py                                   # N = 1, BASELINE.json configs[2]: the headline leg alone
+  python bench.py --full                            # the same + every 1-GPU leg, the profiler passes and the CPU baseline
   python bench.py --gpus 1 --steps 192 --warmup 32
   python bench.py --gpus 1 --steps 20 --warmup 5 --dump-outputs bench_outputs   # + the last timed step's outputs as .npy
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
@@ -32,7 +33,10 @@ Terminated environments are frozen by the kernel and are NOT counted.
 
 `n_gpus` is the number of ranks that actually joined (an all-reduce), and must equal --gpus.
 
-Besides `value`, the default run reports (rank 0; every leg is the same code path as the headline):
+A run without --full times the headline leg alone: set-up, warm-up, the timed regions, --dump-outputs, the result line.
+Its `roofline.frac` is then the labelled figure of the latest committed profile (profiles/rNN_summary.json), not a measurement.
+
+Besides `value`, a --full run reports (rank 0; every leg is the same code path as the headline):
   `policy_in_the_loop`  ONE launch per agent step (ble_step_f32, what an agent loop issues): >= 200 launches, the median
                  HIP-event time of a launch and the rate of the back-to-back sequence
   `roofline.traffic`    HBM bytes per launch MEASURED IN THIS RUN: two rocprofv3 --pmc passes (FETCH_SIZE, WRITE_SIZE;
@@ -591,15 +595,17 @@ def main():
   ap.add_argument('--config', type=int, default=2, choices=sorted(PRESETS), help='BASELINE.json configs[i] (see the module docstring)')
   ap.add_argument('--reps', type=int, default=31, help='repetitions of the timed K-step region (median reported)')
   ap.add_argument('--envs-per-gpu', type=int, default=None, help='override the preset size')
-  ap.add_argument('--no-cpu-baseline', action='store_true')
-  ap.add_argument('--no-extras', action='store_true', help='only the headline leg (profiling)')
+  ap.add_argument('--full', action='store_true',
+                  help='besides the headline: the other legs, the nested profiler passes and the CPU baseline (see the module docstring)')
+  ap.add_argument('--no-cpu-baseline', action='store_true', help='--full without the CPU baseline')
+  ap.add_argument('--no-extras', action='store_true', help='only the headline leg, even with --full (profiling)')
   ap.add_argument('--substeps', type=int, default=18, help='analysis only: physics substeps per agent step (18 = the metric)')
   ap.add_argument('--per-env-grids', action='store_true', help='same as --config 4 data layout at the chosen size')
   ap.add_argument('--observe', type=int, default=8, metavar='N',
                   help='timed step+observation pairs of the observation leg (0 = skip)')
   ap.add_argument('--traffic', choices=('auto', 'off'), default='auto',
                   help='auto: measure roofline.traffic and roofline.instruction_issue in this run with nested rocprofv3 --pmc passes '
-                       '(N = 1, full run only; three of the headline, two of the observation leg)')
+                       '(N = 1, --full only; three of the headline, two of the observation leg)')
   ap.add_argument('--pmc-budget-s', type=float, default=240.0,
                   help='wall-clock budget of all nested profiler passes together; passes that no longer fit are skipped and say so')
   ap.add_argument('--noise-seed', type=int, default=None,
@@ -610,6 +616,7 @@ def main():
                        'environments) to DIR/<name>.npy; the inputs are the same in every run with the same arguments')
   args = ap.parse_args()
   PMC_BUDGET_S[0] = args.pmc_budget_s
+  extras = args.full and not args.no_extras
 
   # ---- `python bench.py --gpus N` without a launcher: start the N ranks here, one process per GPU, and hand the
   # result line of rank 0 through.  (Under torch.distributed.run WORLD_SIZE is set and this branch is not taken.)
@@ -678,7 +685,7 @@ def main():
   achieved = bytes_per_launch / (hs['kernel_ms_mean'] * 1e-3) / 1e9      # the AVERAGE launch duration (HIP events on the launch stream)
   # HBM traffic of the launch shape timed above, measured in this run (rank 0 of a 1-GPU full run; see measure_traffic)
   traffic, traffic_detail, traffic_note = None, None, None
-  if world == 1 and args.traffic == 'auto' and not args.no_extras:
+  if world == 1 and args.traffic == 'auto' and extras:
     child = [sys.executable, os.path.abspath(__file__), '--gpus', '1', '--steps', str(args.steps), '--warmup', str(args.warmup),
              '--config', str(args.config), '--reps', '3', '--no-extras', '--traffic', 'off', '--substeps', str(args.substeps)]
     if args.envs_per_gpu:
@@ -690,10 +697,10 @@ def main():
     traffic_detail, traffic_note = measure_traffic('ble_step_kernel', child, head.launches_per_region, groups=6)
     traffic = traffic_detail['bytes'] if traffic_detail else None
   else:
-    traffic_note = 'not measured in this run (N > 1, --no-extras or --traffic off)'
+    traffic_note = 'not measured in this run (N > 1, no --full, --no-extras or --traffic off)'
   # the bound that actually applies (instruction issue at one wave per SIMD): a third PMC pass of the same child run
   issue, issue_note = None, None
-  if world == 1 and args.traffic == 'auto' and not args.no_extras:
+  if world == 1 and args.traffic == 'auto' and extras:
     issue, issue_note = measure_issue('ble_step_kernel', child, head.launches_per_region, groups=3,
                                       agent_steps_per_launch=args.steps / head.launches_per_region)
   tick('nested PMC passes')
@@ -705,7 +712,7 @@ def main():
         issue = {'wave_issue_utilisation': d['active_inst_any_quad'] / d['wave_cycles_per_wave_quad'],
                  'valu_issue_frac': d['active_inst_valu_quad'] / d['wave_cycles_per_wave_quad'],
                  'valu_insts_per_env_step': d['valu_insts_per_wave'] / per, 'salu_insts_per_env_step': d['salu_insts_per_wave'] / per,
-                 'source': f'NOT measured in this run ({issue_note or "N > 1, --no-extras or --traffic off"}): profiles/{tag}_summary.json '
+                 'source': f'NOT measured in this run ({issue_note or "N > 1, no --full, --no-extras or --traffic off"}): profiles/{tag}_summary.json '
                            f'(rocprofv3 --pmc, per {int(per)}-step launch)'}
         break
       except Exception:
@@ -717,7 +724,7 @@ def main():
   observe = None
   observe_configs = {}
   policy = None
-  if not args.no_extras:
+  if extras:
     extra_reps = max(5, min(11, args.reps))
     if rank == 0 and world == 1:
       policy = policy_in_the_loop_leg(head)
@@ -862,7 +869,7 @@ def main():
       out['observe'] = observe
     if observe_configs:
       out['observe_configs'] = observe_configs
-    if world == 1 and not args.no_cpu_baseline and not args.no_extras:
+    if world == 1 and not args.no_cpu_baseline and extras:
       acts = np.random.default_rng(7).integers(0, 3, (64, n)).astype(np.uint8)
       out['cpu_baseline'] = cpu_baseline(head_initial_host_state, list(acts), field)     # the SAME initial states the GPU flew
       tick('cpu baseline')

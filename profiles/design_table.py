@@ -3,7 +3,7 @@
   python profiles/design_table.py r05            # prints the table
   python profiles/design_table.py r05 --write    # replaces the block between the table markers of DESIGN.md
 
-Inputs: profiles/<tag>_bench.json (default run), profiles/<tag>_bench_driver_shape.json (the driver's flags),
+Inputs: profiles/<tag>_bench.json (bench.py --full), profiles/<tag>_bench_driver_shape.json (the driver's flags + --full),
 profiles/<tag>_summary.json (rocprofv3 averages, profiles/summarize.py)."""
 import json
 import os

@@ -53,11 +53,11 @@ def test_bench_gpus_2_without_a_launcher_spawns_two_ranks_and_gathers_the_partia
 
 
 def test_bench_gpus_2_default_legs_run_sharded():
-  """What the driver's N > 1 command runs beyond the headline (no --no-extras): the ground-truth-wind leg, the observation
+  """What --full runs beyond the headline with N > 1: the ground-truth-wind leg, the observation
   leg with its three consumers of the observation blocks (gather to the learner rank, all_to_all for a data-parallel
   learner, rank-local), and the configs[3] / configs[4] legs -- two ranks on the box's one GPU over gloo, a small headline
   batch so that the test stays short."""
-  out = _bench(['--gpus', '2', '--steps', '20', '--warmup', '5', '--reps', '3', '--observe', '2', '--envs-per-gpu', '2048'],
+  out = _bench(['--gpus', '2', '--steps', '20', '--warmup', '5', '--reps', '3', '--full', '--observe', '2', '--envs-per-gpu', '2048'],
                {'BLE_DIST_BACKEND': 'gloo', 'BLE_BENCH_SIDE_ENVS': '4096', 'BLE_BENCH_SIDE_STEPS': '32'}, timeout=900)
   # (side legs at 4 096 environments per rank and 32-step regions: the code path, not the rate -- over gloo every one of a 192-step
   #  region's 24 gathers crosses the host, 0.1 s each: 57 s of this test's 60 were that)
@@ -83,8 +83,8 @@ def test_bench_gpus_2_default_legs_run_sharded():
 def test_bench_gpus_8_every_leg_with_eight_ranks():
   """The driver's 8-GPU command shape with EIGHT ranks -- the node size the scaling run uses -- on the box's one GPU over gloo, small
   batches: the rank / offset arithmetic (contiguous shards of the global index range), the eight-way gathers and all_to_all, the per-rank
-  decomposition and every default leg run with world = 8, not only with 2."""
-  out = _bench(['--gpus', '8', '--steps', '20', '--warmup', '5', '--reps', '3', '--observe', '2', '--envs-per-gpu', '1024'],
+  decomposition and every --full leg run with world = 8, not only with 2."""
+  out = _bench(['--gpus', '8', '--steps', '20', '--warmup', '5', '--reps', '3', '--full', '--observe', '2', '--envs-per-gpu', '1024'],
                {'BLE_DIST_BACKEND': 'gloo', 'BLE_BENCH_SIDE_ENVS': '1024', 'BLE_BENCH_SIDE_STEPS': '32', 'OMP_NUM_THREADS': '2'}, timeout=900)
   assert out['n_gpus'] == 8 and out['config']['envs_per_gpu'] == 1024 and out['config']['global_envs'] == 8192 and out['scaling'] == 'weak'
   ex = out['config']['exchanges']
@@ -137,6 +137,17 @@ def test_bench_dump_outputs_are_the_same_in_two_runs(tmp_path):
     assert a.dtype in (np.float32, np.float64) and a.shape == (8192,), f
     assert a.tobytes() == b.tobytes(), f
   assert np.isfinite(np.load(tmp_path / 'a' / 'reward.npy')).all()
+
+
+def test_bench_without_full_runs_the_headline_leg_alone():
+  """A run without --full: the headline's result line and nothing the other legs, the profiler passes or the CPU baseline add."""
+  out = _bench(['--gpus', '1', '--steps', '12', '--warmup', '3', '--reps', '3', '--envs-per-gpu', '8192'])
+  assert out['unit'] == 'env-steps/s' and out['higher_is_better'] is True and out['dtype'] == 'f32+f64'
+  assert out['value'] > 1e6 and out['ms_per_step'] > 0 and out['steps'] == 12 and out['warmup'] == 3
+  assert list(out['configs']) == ['configs[2]'] and out['config']['ground_truth_wind'] is None
+  assert out['roofline']['traffic'] is None and 'no --full' in out['roofline']['traffic_note']
+  for key in ('policy_in_the_loop', 'observe', 'observe_configs', 'cpu_baseline'):
+    assert key not in out, key
 
 
 def test_bench_refuses_a_world_that_is_not_gpus():
