@@ -416,7 +416,7 @@ __global__ __launch_bounds__(256) void probe_thermal_kernel(const float* volume,
     const double vol = (double)volume[i];
     double yc = (double)f_exp2((-1.0f / 3.0f) * f_log2(volume[i]));
     yc = yc * d_fma(-vol * yc, yc * yc, 4.0) * (1.0 / 3.0);
-    flags |= (t_int[i] < 12.3f) ? kFlagAbsorptivity : 0u;
+    flags |= absorptivity_out_of_range((double)t_int[i]) ? kFlagAbsorptivity : 0u;
     dtdt[i] = (float)(0.1 * thermal_increment_f64(vol, yc, (double)t_int[i], (double)t_amb[i], (double)pressure[i],
                                                   (double)((flux[i] * att) * (0.25f * kSolarAbsorptivityTotal)),
                                                   earth_heat_per_area_f64((double)ir[i], &flags), stride_k_literal(), thermal_scale));

@@ -1226,10 +1226,23 @@ BLE_FN double d_inv_root10(double a, double eleven = 11.0, double scale = 0.1) {
 // solar geometry's own floor), q_earth_area = earth_heat_per_area(IR) (per-episode constant).
 constexpr double kStefanBoltzmannD = 0.000000056704;
 BLE_FN double total_absorptivity_d(double a) { return a * d_fma(-a, 1.0 / (1.0 - 0.0291), 2.0); }   // a (1 + (1-a-r)/(1-r))
+// total_absorptivity's range check (thermal.py:142-145) as the reference evaluates it in float64.  The factor a (2 - a / 0.9709)
+// never exceeds 0.9709, so it leaves [0, 1] only below zero: for a = absorptivity_ir(T) < 0 (T below ~12.2845 K) and for
+// a > 2 x 0.9709 (T above ~8382.11 K).  The reference's rounded factor is monotone in T on either side, so the check is two
+// thresholds on T: kAbsTLo is the smallest double the reference accepts, kAbsTHi the largest (tests/test_kernel_numerics_host.py
+// re-derives both from the reference's own arithmetic).  NaN passes, as in the reference (kFlagNonFinite reports it).
+constexpr double kAbsTLo = 0x1.891a7b9611a78p+3;    // 12.284482758620683 K
+constexpr double kAbsTHi = 0x1.05f0e58469ee5p+13;   // 8382.112068965516 K
+BLE_FN bool absorptivity_out_of_range(double t_k) { return t_k < kAbsTLo || t_k > kAbsTHi; }
+// the same check on absorptivity_ir(black_body_flux_to_temperature(IR)) of the Earth term (thermal.py:209-213), as thresholds on
+// the float32 upwelling IR the ABI carries: the smallest and the largest float32 the reference accepts
+constexpr float kAbsIrLo = 0x1.52847cp-10f;          // 0.00129134185 W/m^2
+constexpr float kAbsIrHi = 0x1.0af2d6p+28f;          // 279915872 W/m^2
+BLE_FN bool earth_ir_out_of_range(double ir) { return ir < (double)kAbsIrLo || ir > (double)kAbsIrHi; }
 BLE_FN double earth_heat_per_area_f64(double upwelling_ir, uint32_t* flags) {   // thermal.py:209-213
   const double t_bb = d_sqrt(d_sqrt(upwelling_ir * (1.0 / kStefanBoltzmannD)));
   const double f = total_absorptivity_d(d_fma(0.000232, t_bb - 210.0, 0.04587));
-  *flags |= (f < 0.0 || f > 1.0) ? kFlagAbsorptivity : 0u;
+  *flags |= earth_ir_out_of_range(upwelling_ir) ? kFlagAbsorptivity : 0u;
   return upwelling_ir * 0.4605 * f;
 }
 template <bool kExactTwelfthRoot = false>

@@ -109,10 +109,13 @@ BLE_FN StableParams stable_params(double alpha, double p, double el_deg, double 
   const double att = solar_attenuation_f64(el_deg, p);
   double ti = 206.0;
   const double delta = 0.01;
-  uint32_t ignored = 0;                                     // total_absorptivity of the Earth term: checked by the transition
-  const double q_earth = earth_heat_per_area_f64(ir, &ignored);
+  // total_absorptivity's range checks (thermal.py:142-145): cold_start_to_stable_params evaluates the Earth term and the balloon's
+  // own term at every Newton probe temperature, so the reference raises here, at the reset, before any transition
+  const double q_earth = earth_heat_per_area_f64(ir, flags);
+  bool abs_bad = false;
 #pragma unroll 1
   for (int k = 0; k < 10; ++k) {
+    abs_bad = abs_bad || absorptivity_out_of_range(ti - delta / 2) || absorptivity_out_of_range(ti + delta / 2);
     const double d1 = thermal_dtdt_f64(veh.v0, veh.inv_cbrt_v0, ti - delta / 2, o.t_amb, p, att, flux, q_earth, veh.thermal_scale);
     const double d2 = thermal_dtdt_f64(veh.v0, veh.inv_cbrt_v0, ti + delta / 2, o.t_amb, p, att, flux, q_earth, veh.thermal_scale);
     const double d2t = (d2 - d1) / delta;
@@ -120,6 +123,7 @@ BLE_FN StableParams stable_params(double alpha, double p, double el_deg, double 
     if (fabs(d2t) > 0.0) ti -= mean / d2t;
     if (fabs(mean) < 1e-5) break;
   }
+  *flags |= abs_bad ? kFlagAbsorptivity : 0u;
   o.t_int = ti;
   superpressure_volume_f64(o.mols_air, ti, p, 1.0 / p, &o.volume, &o.sp, stride_k_literal(veh.dry_mass, veh.lift, veh.v0), veh.dvdp, veh.four_dvdp,
                            veh.inv_dvdp);

@@ -295,7 +295,8 @@ BLE_FN float step_reward(int action, float x, float y, float p, float batt, floa
   return r;
 }
 
-constexpr int kTermSaveRows = 14, kTermSaveStride = 64;   // agent_step's parking area: 13 state / output floats + (status | strides << 8), one column per lane
+constexpr int kTermSaveRows = 14, kTermSaveStride = 64;   // agent_step's parking area: 13 state / output floats + (status | strides << 8 | kTermAbsBit), one column per lane
+constexpr int kTermAbsBit = 1 << 16;                       // (strides <= BLE_MAX_SUBSTEPS < 256)
 // Returns the effective action (after the safety layers).  `reward` gets the post-step
 // reward; `s` is advanced in place.  Precondition: s.status == kOk.
 // The wind is handed over as the 16 gathered grid corners + weights (+ additive noise): the
@@ -346,14 +347,14 @@ BLE_FN int agent_step(EnvRegs& s, const EnvConst& c, const EnvHoisted& hc, int a
   };
   const double q_earth = hc.q_earth;
   *flags |= hc.flags;
-  // total_absorptivity's range check (thermal.py:142-145) on the balloon's own temperature: the
-  // factor leaves [0, 1] only for T_int < 12.3 K; T_int moves < 1 K per step, so checking the
-  // step's first and last value is checking every stride
-  *flags |= (s.t_int < 12.3f) ? kFlagAbsorptivity : 0u;
 
   // ---- fp64 carried chain
   double t_amb = (double)s.t_amb, t_int = (double)s.t_int, n_air = (double)s.n_air, vol = (double)s.vol,
          sp = (double)s.sp;
+  // total_absorptivity's range check (thermal.py:142-145) on the balloon's own temperature, which the reference evaluates on the
+  // pre-stride T_int of every stride it runs: the lowest and the highest of those values, checked once after the loop (two
+  // v_min/v_max per stride instead of two compares and a select)
+  double t_int_lo = t_int, t_int_hi = t_int;
   float x = s.x, y = s.y, batt = s.batt;
   float acs_w = s.acs_power, mdot = s.mdot, charge = s.charge, load = s.load;
   int status = kOk;
@@ -367,6 +368,7 @@ BLE_FN int agent_step(EnvRegs& s, const EnvConst& c, const EnvHoisted& hc, int a
   auto stride = [&](const int k) __attribute__((always_inline)) {
     const float pf = (float)p;
     const double rp = d_rcp(p);
+    t_int_lo = d_min(t_int_lo, t_int); t_int_hi = d_max(t_int_hi, t_int);
     // ---- sun position at (x, y, date_time) of the OLD state (balloon.py:451-452)
     const float fk = (float)k;
     const SunState sun = sun_at(k);
@@ -415,7 +417,9 @@ BLE_FN int agent_step(EnvRegs& s, const EnvConst& c, const EnvHoisted& hc, int a
 #pragma unroll
       for (int j = 0; j < kTermSaveRows - 1; ++j) term_save[j * kTermSaveStride] = parked[j];
       const int strides = i_opaque(k + 1);          // (otherwise the common path carries (k + 1) << 8 as an induction variable for this block)
-      *term_word = __builtin_bit_cast(float, st | (strides << 8));
+      // the temperature range of the strides run so far: the reference stops after this one (kTermAbsBit: above status and strides)
+      const int abs_bad = absorptivity_out_of_range(t_int_lo) || absorptivity_out_of_range(t_int_hi) ? kTermAbsBit : 0;
+      *term_word = __builtin_bit_cast(float, st | (strides << 8) | abs_bad);
     }
   };
   // two strides per iteration: the loop-carried values alternate between two sets of registers instead of being copied
@@ -430,16 +434,17 @@ BLE_FN int agent_step(EnvRegs& s, const EnvConst& c, const EnvHoisted& hc, int a
   int k = substeps;                      // strides this lane ran (>= 1: the host entry point checks substeps >= 1)
   const int word = __builtin_bit_cast(int, *term_word);
   const bool done = word != 0;
+  bool abs_bad = absorptivity_out_of_range(t_int_lo) || absorptivity_out_of_range(t_int_hi);
   if (__builtin_expect(wave_any(done), 0)) if (done) {
     s.x = term_save[0]; s.y = term_save[kTermSaveStride]; s.p = term_save[2 * kTermSaveStride]; s.t_amb = term_save[3 * kTermSaveStride];
     s.t_int = term_save[4 * kTermSaveStride]; s.vol = term_save[5 * kTermSaveStride]; s.sp = term_save[6 * kTermSaveStride];
     s.n_air = term_save[7 * kTermSaveStride]; s.batt = term_save[8 * kTermSaveStride]; s.acs_power = term_save[9 * kTermSaveStride];
     s.mdot = term_save[10 * kTermSaveStride]; s.charge = term_save[11 * kTermSaveStride]; s.load = term_save[12 * kTermSaveStride];
-    status = word & 0xff; k = word >> 8;
+    status = word & 0xff; k = (word >> 8) & 0xff; abs_bad = (word & kTermAbsBit) != 0;
   }
   s.t_elapsed += 10 * k;
   s.status = (uint8_t)status;
-  *flags |= (s.t_int < 12.3f) ? kFlagAbsorptivity : 0u;
+  *flags |= abs_bad ? kFlagAbsorptivity : 0u;
 
   // solar_atmospheric_attenuation's range check (solar.py:194-197); p moves < 3 kPa per step
   *flags |= (s.p > 101325.0f || s.p < 0.0f || p0_in > 101325.0f || p0_in < 0.0f) ? kFlagSolarRange : 0u;

@@ -207,8 +207,6 @@ BLE_FN uint32_t split_agent_steps(const SplitArgs& a, SplitShared& sh, SplitNois
       // what the hour-angle nodes of the step need of it (solar_nodes_time)
       sh.eot_min[lane] = e0.eot_min; sh.eph[0][lane] = e0.eot_min_rate; sh.eph[1][lane] = e0.sin_decl; sh.eph[2][lane] = e0.sin_decl_rate;
       step_flags |= hc.flags;
-      // total_absorptivity's range check (thermal.py:142-145) on the balloon's own temperature, first value of the step
-      step_flags |= (s.t_int < 12.3f) ? kFlagAbsorptivity : 0u;
     }
     if (r3) {
       // the power and envelope layers on the pre-step state (balloon.py:304-313); both state machines move independently of
@@ -294,6 +292,7 @@ BLE_FN uint32_t split_agent_steps(const SplitArgs& a, SplitShared& sh, SplitNois
 
     // ================================================================ the strides
     bool active = live;
+    bool abs_bad = false;                             // wave 1: total_absorptivity's range check on the pre-stride T_int of a stride run
     int k_done = 0, last_rd = 0, status = kOk;        // strides this lane ran; the exchange parity and the status of its last one
     const StrideK K = stride_k_vreg();                // (a role keeps the members its right-hand sides read; see d_vreg)
 #pragma unroll 1
@@ -316,6 +315,7 @@ BLE_FN uint32_t split_agent_steps(const SplitArgs& a, SplitShared& sh, SplitNois
         if (publish) { sh.p[wr][lane] = p_n; sh.t_amb[wr][lane] = t_amb_n; sh.x[wr][lane] = x_n; sh.y[wr][lane] = y_n; }
       }
       if (r1) {
+        abs_bad = abs_bad || (active && absorptivity_out_of_range(t_int));     // thermal.py:142-145, every stride the reference runs
         const float flux = f_fma((float)k, dfl, fl0);
         const double yc = inv_cbrt_volume(vol);
         const float att = solar_attenuation(sun_sin, (float)p, sun_day);
@@ -376,7 +376,7 @@ BLE_FN uint32_t split_agent_steps(const SplitArgs& a, SplitShared& sh, SplitNois
       s.batt = sh.batt[rd][lane]; s.x = sh.x[rd][lane]; s.y = sh.y[rd][lane];
       s.t_elapsed += 10 * k_done;
       s.status = (uint8_t)status;
-      if (r1) flags |= (s.t_int < 12.3f) ? kFlagAbsorptivity : 0u;
+      if (r1) flags |= abs_bad ? kFlagAbsorptivity : 0u;
       if (r0) {       // (the vertical wave: its per-step part is the lightest)
         s.acs_power = sh.acs_w[rd][lane];
         // solar_atmospheric_attenuation's range check (solar.py:194-197); p moves < 3 kPa per step

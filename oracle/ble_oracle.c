@@ -868,22 +868,32 @@ static double perciatelli_reward(const sub_state* s, int last_command, double la
  * ORC_ERR_TERMINAL_STEP reported) where the reference raises AssertionError.
  * `noise_uv` (n x 2) may be NULL.  `field` may be NULL if `wind_uv` (n x 2) is given
  * (fixed wind per step, used by trajectory fixtures).  Returns OR of error bits.
+ * Per environment (each may be NULL): err_env[i] = the OR of env i's error bits over the step; err_first[i] = the bits of the
+ * first evaluation that failed -- where the reference raises --, err_where[i] = where that was (0 the safety layers before the
+ * strides, 1 a stride, 2 the reward, -1 none) and err_stride[i] = the strides completed when it failed (the partly advanced
+ * state's time_elapsed / 10).
  */
-ORC_API int orc_step_vehicle(const orc_state* st, const uint8_t* action, const float* field,
-                             const double* wind_uv, const double* noise_uv, double* reward,
-                             uint8_t* terminal, uint8_t* effective_action, int64_t n, int substeps,
-                             int n_threads, const orc_vehicle* veh) {
+ORC_API int orc_step_vehicle_err(const orc_state* st, const uint8_t* action, const float* field,
+                                 const double* wind_uv, const double* noise_uv, double* reward,
+                                 uint8_t* terminal, uint8_t* effective_action, int64_t n, int substeps,
+                                 int n_threads, const orc_vehicle* veh, int32_t* err_env, int32_t* err_first,
+                                 int32_t* err_where, int32_t* err_stride) {
   int err_all = 0;
   if (veh == NULL) veh = &ORC_VEHICLE_DEFAULT;
   (void)n_threads;
 #pragma omp parallel for schedule(static) reduction(| : err_all) num_threads(n_threads > 0 ? n_threads : 1)
   for (int64_t i = 0; i < n; ++i) {
-    int err = 0;
+    int err = 0, first = 0, where = -1, at = 0;
+#define ORC_FIRST(w, k) do { if (err && !first) { first = err; where = (w); at = (k); } } while (0)
     if (st->status[i] != ST_OK) {
       reward[i] = 0.0;
       terminal[i] = 1;
       if (effective_action) effective_action[i] = action[i];
       err_all |= ORC_ERR_TERMINAL_STEP;
+      if (err_env) err_env[i] = ORC_ERR_TERMINAL_STEP;
+      if (err_first) err_first[i] = ORC_ERR_TERMINAL_STEP;
+      if (err_where) err_where[i] = 0;
+      if (err_stride) err_stride[i] = 0;
       continue;
     }
     orc_atm atm;
@@ -908,6 +918,7 @@ ORC_API int orc_step_vehicle(const orc_state* st, const uint8_t* action, const f
                          &st->sunrise_h[i], &st->sunset[i], &st->power_paused[i]);
     eff = envelope_safety(eff, st->superpressure[i], veh->envelope_max_superpressure, &st->env_fsm[i]);
     eff = altitude_safety(eff, &atm, st->pressure[i], &st->alt_fsm[i], &err);
+    ORC_FIRST(0, 0);
     if (effective_action) effective_action[i] = (uint8_t)eff;
 
     sub_state s;
@@ -917,9 +928,11 @@ ORC_API int orc_step_vehicle(const orc_state* st, const uint8_t* action, const f
     s.acs_power = st->acs_power[i]; s.mdot = st->acs_mass_flow[i];
     s.charge = st->solar_charging[i]; s.load = st->power_load[i];
     s.t_elapsed = st->time_elapsed_s[i]; s.status = ST_OK;
+    const int64_t st0_elapsed = s.t_elapsed;
     for (int k = 0; k < substeps; ++k) { /* balloon.py:321-328 */
       err |= simulate_step_internal(&s, u, v, &atm, eff, lat0, lng0, st->start_unix[i],
                                     st->upwelling_infrared[i], 10.0, veh);
+      ORC_FIRST(1, k);
       if (s.status != ST_OK) break;
     }
     st->x[i] = s.x; st->y[i] = s.y; st->pressure[i] = s.p; st->ambient_temperature[i] = s.t_amb;
@@ -929,10 +942,24 @@ ORC_API int orc_step_vehicle(const orc_state* st, const uint8_t* action, const f
     st->solar_charging[i] = s.charge; st->power_load[i] = s.load;
     st->time_elapsed_s[i] = s.t_elapsed; st->status[i] = (uint8_t)s.status;
     reward[i] = perciatelli_reward(&s, action[i], lat0, lng0, st->start_unix[i], &err, veh);
+    ORC_FIRST(2, (int)((s.t_elapsed - st0_elapsed) / 10));
+#undef ORC_FIRST
     terminal[i] = s.status != ST_OK;
     err_all |= err;
+    if (err_env) err_env[i] = err;
+    if (err_first) err_first[i] = first;
+    if (err_where) err_where[i] = where;
+    if (err_stride) err_stride[i] = at;
   }
   return err_all;
+}
+
+ORC_API int orc_step_vehicle(const orc_state* st, const uint8_t* action, const float* field,
+                             const double* wind_uv, const double* noise_uv, double* reward,
+                             uint8_t* terminal, uint8_t* effective_action, int64_t n, int substeps,
+                             int n_threads, const orc_vehicle* veh) {
+  return orc_step_vehicle_err(st, action, field, wind_uv, noise_uv, reward, terminal, effective_action, n, substeps, n_threads, veh,
+                              NULL, NULL, NULL, NULL);
 }
 
 ORC_API int orc_step(const orc_state* st, const uint8_t* action, const float* field,
@@ -946,11 +973,12 @@ ORC_API int orc_step(const orc_state* st, const uint8_t* action, const float* fi
 /* ------------------------------------------------------------------------- */
 /* Reset path: stable_init.py:40-157                                          */
 /* ------------------------------------------------------------------------- */
-ORC_API int orc_stable_init_vehicle(int64_t n, const double* pressure, const double* center_lat_deg,
-                                    const double* center_lng_deg, const double* x, const double* y,
-                                    const int64_t* unix_s, const double* ir, const double* alpha,
-                                    double* t_amb, double* t_int, double* mols_air, double* volume,
-                                    double* sp, const orc_vehicle* veh) {
+/* err_env (may be NULL): the error bits of each environment */
+ORC_API int orc_stable_init_vehicle_err(int64_t n, const double* pressure, const double* center_lat_deg,
+                                        const double* center_lng_deg, const double* x, const double* y,
+                                        const int64_t* unix_s, const double* ir, const double* alpha,
+                                        double* t_amb, double* t_int, double* mols_air, double* volume,
+                                        double* sp, const orc_vehicle* veh, int32_t* err_env) {
   int err_all = 0;
   if (veh == NULL) veh = &ORC_VEHICLE_DEFAULT;
 #pragma omp parallel for schedule(static) reduction(| : err_all)
@@ -985,8 +1013,17 @@ ORC_API int orc_stable_init_vehicle(int64_t n, const double* pressure, const dou
     superpressure_and_volume(veh->mols_lift_gas, ma, ti, pressure[i], veh->envelope_volume_base,
                              veh->envelope_volume_dv_pressure, &volume[i], &sp[i]);
     err_all |= err;
+    if (err_env) err_env[i] = err;
   }
   return err_all;
+}
+ORC_API int orc_stable_init_vehicle(int64_t n, const double* pressure, const double* center_lat_deg,
+                                    const double* center_lng_deg, const double* x, const double* y,
+                                    const int64_t* unix_s, const double* ir, const double* alpha,
+                                    double* t_amb, double* t_int, double* mols_air, double* volume,
+                                    double* sp, const orc_vehicle* veh) {
+  return orc_stable_init_vehicle_err(n, pressure, center_lat_deg, center_lng_deg, x, y, unix_s, ir, alpha, t_amb, t_int, mols_air,
+                                     volume, sp, veh, NULL);
 }
 ORC_API int orc_stable_init(int64_t n, const double* pressure, const double* center_lat_deg,
                             const double* center_lng_deg, const double* x, const double* y,

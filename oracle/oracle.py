@@ -223,14 +223,19 @@ def wind_forecast(field, x_m, y_m, p, elapsed_s):
   return u, v
 
 
-def stable_init(pressure, lat_deg, lng_deg, x, y, unix_s, ir, alpha, vehicle=None):
+def stable_init(pressure, lat_deg, lng_deg, x, y, unix_s, ir, alpha, vehicle=None, per_env=False):
+  """per_env: return the error bits of each environment (an int32 array) instead of their OR."""
   arrs = [_d(np.atleast_1d(a)) for a in (pressure, lat_deg, lng_deg, x, y)]
   t = np.ascontiguousarray(np.atleast_1d(unix_s), np.int64)
   ir, alpha = _d(np.atleast_1d(ir)), _d(np.atleast_1d(alpha))
   n = t.size
   outs = [np.empty(n) for _ in range(5)]
-  err = lib().orc_stable_init_vehicle(ctypes.c_int64(n), *[_pd(a) for a in arrs], _p(t, ctypes.c_int64),
-                                      _pd(ir), _pd(alpha), *[_pd(o) for o in outs], _vehicle(vehicle))
+  err_env = np.zeros(n, np.int32)
+  err = lib().orc_stable_init_vehicle_err(ctypes.c_int64(n), *[_pd(a) for a in arrs], _p(t, ctypes.c_int64),
+                                          _pd(ir), _pd(alpha), *[_pd(o) for o in outs], _vehicle(vehicle),
+                                          _p(err_env, ctypes.c_int32))
+  if per_env:
+    err = err_env
   return dict(zip(('ambient_temperature', 'internal_temperature', 'mols_air', 'envelope_volume',
                    'superpressure'), outs)), err
 
@@ -266,9 +271,12 @@ def coerce_state(state):
   return out
 
 
-def step(state, action, field=None, wind_uv=None, noise_uv=None, substeps=18, threads=1, vehicle=None):
+def step(state, action, field=None, wind_uv=None, noise_uv=None, substeps=18, threads=1, vehicle=None, per_env=False):
   """In-place agent step on an oracle state dict. Returns (reward, terminal, effective_action, err).
-  vehicle: None or a dict of the BalloonState vehicle fields that differ from the reference's defaults (VEHICLE_DEFAULTS)."""
+  vehicle: None or a dict of the BalloonState vehicle fields that differ from the reference's defaults (VEHICLE_DEFAULTS).
+  per_env: `err` is a dict of int32 arrays instead of the OR over the batch: 'env' (each environment's bits over the step),
+  'first' (the bits of the first failing evaluation: where the reference raises), 'where' (0 the safety layers, 1 a stride,
+  2 the reward, -1 none) and 'stride' (the strides completed when it failed)."""
   n = state['x'].size
   cst = _State()
   for f in FLOAT_FIELDS:
@@ -297,7 +305,11 @@ def step(state, action, field=None, wind_uv=None, noise_uv=None, substeps=18, th
     noise_uv = _d(noise_uv); assert noise_uv.shape == (n, 2)
     nptr = _pd(noise_uv)
   reward = np.empty(n); terminal = np.empty(n, np.uint8); eff = np.empty(n, np.uint8)
-  err = lib().orc_step_vehicle(ctypes.byref(cst), _p(action, ctypes.c_uint8), fptr, wptr, nptr, _pd(reward),
-                               _p(terminal, ctypes.c_uint8), _p(eff, ctypes.c_uint8), ctypes.c_int64(n),
-                               ctypes.c_int(substeps), ctypes.c_int(threads), _vehicle(vehicle))
+  per = {k: np.zeros(n, np.int32) for k in ('env', 'first', 'where', 'stride')}
+  err = lib().orc_step_vehicle_err(ctypes.byref(cst), _p(action, ctypes.c_uint8), fptr, wptr, nptr, _pd(reward),
+                                   _p(terminal, ctypes.c_uint8), _p(eff, ctypes.c_uint8), ctypes.c_int64(n),
+                                   ctypes.c_int(substeps), ctypes.c_int(threads), _vehicle(vehicle),
+                                   *[_p(per[k], ctypes.c_int32) for k in ('env', 'first', 'where', 'stride')])
+  if per_env:
+    err = per
   return reward, terminal, eff, err

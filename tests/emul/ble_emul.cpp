@@ -10,12 +10,14 @@
 
 using namespace ble;
 
-extern "C" int emul_step_f32(const ble_state_f32* st, const uint8_t* action, const float* wind_grid,
-                             const float* wind_uv, float* reward, uint8_t* terminal, uint8_t* effective_action,
-                             uint32_t* err_flags, int64_t n, int substeps) {
+// err_env (may be NULL): each environment's flag word, as a launch of n = 1 reports it
+extern "C" int emul_step_f32_env(const ble_state_f32* st, const uint8_t* action, const float* wind_grid,
+                                 const float* wind_uv, float* reward, uint8_t* terminal, uint8_t* effective_action,
+                                 uint32_t* err_flags, int64_t n, int substeps, uint32_t* err_env) {
   uint32_t flags_all = 0;
   const double* acs_poly = kAcsPoly.c;       // the compile-time table (the device copies it into LDS)
   for (int64_t i = 0; i < n; ++i) {
+    if (err_env) err_env[i] = 0;
     if (st->status[i] != kOk) { reward[i] = 0.0f; terminal[i] = 1; if (effective_action) effective_action[i] = action[i]; continue; }
     EnvRegs s;
     s.x = st->x[i]; s.y = st->y[i]; s.p = st->pressure[i]; s.t_amb = st->ambient_temperature[i];
@@ -37,7 +39,9 @@ extern "C" int emul_step_f32(const ble_state_f32* st, const uint8_t* action, con
     uint32_t flags = 0; float r;
     float term_save[kTermSaveRows * kTermSaveStride];       // (the kernel's LDS parking area of a lane whose episode ends inside the step)
     int eff = agent_step(s, c, hoist_constants(c), action[i], wc, wq, nu, nv, substeps, acs_poly, stride_k_literal(), term_save, &r, &flags);
+    if (!(isfinite(s.p) && isfinite(s.t_int) && isfinite(s.x) && isfinite(s.y) && isfinite(s.batt))) flags |= kFlagNonFinite;   // (as the kernel)
     flags_all |= flags;
+    if (err_env) err_env[i] = flags;
     st->x[i] = s.x; st->y[i] = s.y; st->pressure[i] = s.p; st->ambient_temperature[i] = s.t_amb;
     st->internal_temperature[i] = s.t_int; st->envelope_volume[i] = s.vol; st->superpressure[i] = s.sp;
     st->mols_air[i] = s.n_air; st->battery_charge[i] = s.batt; st->acs_power[i] = s.acs_power;
@@ -50,6 +54,11 @@ extern "C" int emul_step_f32(const ble_state_f32* st, const uint8_t* action, con
   }
   if (err_flags) *err_flags |= flags_all;
   return 0;
+}
+extern "C" int emul_step_f32(const ble_state_f32* st, const uint8_t* action, const float* wind_grid,
+                             const float* wind_uv, float* reward, uint8_t* terminal, uint8_t* effective_action,
+                             uint32_t* err_flags, int64_t n, int substeps) {
+  return emul_step_f32_env(st, action, wind_grid, wind_uv, reward, terminal, effective_action, err_flags, n, substeps, nullptr);
 }
 
 extern "C" void emul_solar(int64_t n, const float* lat0, const float* lng0, const float* x, const float* y,
@@ -88,10 +97,11 @@ extern "C" void emul_ephemeris(int64_t t, double* out4) {
 
 // ---- reset path (ble_reset.h) on the host ----
 #include "../../balloon_learning_environment_amd/csrc/ble_reset.h"
-extern "C" void emul_reset_derive(int64_t n, const float* alpha, const float* x, const float* y, const float* p,
-                                  const float* lat0, const float* lng0, const float* ir, const int64_t* start,
-                                  double* t_amb, double* t_int, double* mols_air, double* volume, double* sp,
-                                  int64_t* sunrise, int64_t* sunset, double* el_out) {
+// flags_out (may be NULL): each environment's flag word
+extern "C" void emul_reset_derive_flags(int64_t n, const float* alpha, const float* x, const float* y, const float* p,
+                                        const float* lat0, const float* lng0, const float* ir, const int64_t* start,
+                                        double* t_amb, double* t_int, double* mols_air, double* volume, double* sp,
+                                        int64_t* sunrise, int64_t* sunset, double* el_out, uint32_t* flags_out) {
   for (int64_t i = 0; i < n; ++i) {
     SunSite site;
     latlng_f64((double)lat0[i], (double)lng0[i], (double)x[i], (double)y[i], &site.sin_lat, &site.cos_lat, &site.lng_deg);
@@ -102,7 +112,14 @@ extern "C" void emul_reset_derive(int64_t n, const float* alpha, const float* x,
     t_amb[i] = s.t_amb; t_int[i] = s.t_int; mols_air[i] = s.mols_air; volume[i] = s.volume; sp[i] = s.sp;
     next_sunrise_sunset(site, start[i], &sunrise[i], &sunset[i]);
     el_out[i] = el;
+    if (flags_out) flags_out[i] = flags;
   }
+}
+extern "C" void emul_reset_derive(int64_t n, const float* alpha, const float* x, const float* y, const float* p,
+                                  const float* lat0, const float* lng0, const float* ir, const int64_t* start,
+                                  double* t_amb, double* t_int, double* mols_air, double* volume, double* sp,
+                                  int64_t* sunrise, int64_t* sunset, double* el_out) {
+  emul_reset_derive_flags(n, alpha, x, y, p, lat0, lng0, ir, start, t_amb, t_int, mols_air, volume, sp, sunrise, sunset, el_out, nullptr);
 }
 extern "C" void emul_philox(uint64_t seed, uint64_t env, uint32_t episode, int64_t n, double* uniform, double* normal,
                             double* gamma12) {

@@ -69,7 +69,8 @@ def oracle_from_state(st):
   return ost
 
 
-def step(st, action, field=None, wind_uv=None, substeps=18):
+def step(st, action, field=None, wind_uv=None, substeps=18, per_env=False):
+  """per_env: the flag word of each environment (a uint32 array) instead of their OR."""
   n = st['x'].size
   cst = _abi.state_struct({k: v.ctypes.data for k, v in st.items()})
   action = np.ascontiguousarray(action, np.uint8)
@@ -80,8 +81,9 @@ def step(st, action, field=None, wind_uv=None, substeps=18):
     field = np.ascontiguousarray(field, np.float32); fp = field.ctypes.data_as(ctypes.c_void_p)
   if wind_uv is not None:
     wind_uv = np.ascontiguousarray(wind_uv, np.float32); wp = wind_uv.ctypes.data_as(ctypes.c_void_p)
-  lib().emul_step_f32(ctypes.byref(cst), action.ctypes.data_as(ctypes.c_void_p), fp, wp,
-                      reward.ctypes.data_as(ctypes.c_void_p), terminal.ctypes.data_as(ctypes.c_void_p),
-                      eff.ctypes.data_as(ctypes.c_void_p), flags.ctypes.data_as(ctypes.c_void_p),
-                      ctypes.c_int64(n), ctypes.c_int(substeps))
-  return reward, terminal, eff, int(flags[0])
+  env = np.zeros(n, np.uint32)
+  lib().emul_step_f32_env(ctypes.byref(cst), action.ctypes.data_as(ctypes.c_void_p), fp, wp,
+                          reward.ctypes.data_as(ctypes.c_void_p), terminal.ctypes.data_as(ctypes.c_void_p),
+                          eff.ctypes.data_as(ctypes.c_void_p), flags.ctypes.data_as(ctypes.c_void_p),
+                          ctypes.c_int64(n), ctypes.c_int(substeps), env.ctypes.data_as(ctypes.c_void_p))
+  return reward, terminal, eff, (env if per_env else int(flags[0]))

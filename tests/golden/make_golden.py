@@ -16,6 +16,7 @@ wind field, F10 reset path (stable_init, sunrise/sunset).
 import datetime as dt
 import os
 import sys
+import traceback
 
 # One BLAS / OpenMP thread, whatever the caller's environment says: a threaded matrix product sums in an order that depends on the
 # thread count, and the fixtures are held to their generator BYTE for byte (tests/test_golden_reproducible.py) -- F15's float64 MLP and
@@ -881,6 +882,163 @@ def f17_static_wind_features(n_env=2, n_steps=14):
        start_unix=start_unix, **consts, **cols)
 
 
+# ----------------------------------------------------------------------------- F18
+F18_EXC = {None: 0, AssertionError: 1, ValueError: 2}   # the class the reference raised (0: none)
+
+
+def f32(v):
+  return float(np.float32(v))
+
+
+def f18_round_state(st):
+  """Every float field of the state to a float32 value, so that the device and the reference start from the same numbers."""
+  st.x = units.Distance(m=f32(st.x.meters)); st.y = units.Distance(m=f32(st.y.meters))
+  for k in ('pressure', 'ambient_temperature', 'internal_temperature', 'envelope_volume', 'superpressure', 'mols_air',
+            'acs_mass_flow'):
+    setattr(st, k, f32(getattr(st, k)))
+  st.battery_charge = units.Energy(watt_hours=f32(st.battery_charge.watt_hours))
+  for k in ('acs_power', 'solar_charging', 'power_load'):
+    setattr(st, k, units.Power(watts=f32(getattr(st, k).watts)))
+
+
+def f18_where(exc):
+  """0: raised before the strides (the terminal-step assert, the safety layers), 1: inside a stride, 2: the reward."""
+  frames = [f.name for f in traceback.extract_tb(exc.__traceback__)]
+  if '_simulate_step_internal' in frames:
+    return 1
+  return 0 if 'simulate_step' in frames else 2
+
+
+def f18_step(b, atm, su, action, wind, substeps):
+  """One agent step as the arena takes it: (exception class id, where, strides completed, reward)."""
+  t0 = int(b.state.time_elapsed.total_seconds())
+  w = wind_field.WindVector(units.Velocity(mps=wind[0]), units.Velocity(mps=wind[1]))
+  try:
+    b.simulate_step(w, atm, control.AltitudeControlCommand(action), dt.timedelta(seconds=10 * substeps))
+    reward = balloon_env.perciatelli_reward_function(simulator_data.SimulatorState(b.state, None, atm))
+  except (AssertionError, ValueError) as e:
+    return F18_EXC[type(e)], f18_where(e), (int(b.state.time_elapsed.total_seconds()) - t0) // 10, 0.0
+  return 0, -1, (int(b.state.time_elapsed.total_seconds()) - t0) // 10, float(reward)
+
+
+def f18_hot_temperature(st, target_sp):
+  """The float32 internal temperature at which the state's superpressure is about target_sp (bisection)."""
+  lo, hi = 10.0, 20000.0
+  for _ in range(200):
+    mid = 0.5 * (lo + hi)
+    _, sp = balloon.calculate_superpressure_and_volume(6830.0, st.mols_air, mid, st.pressure, 1804, 0.0199)
+    lo, hi = (mid, hi) if sp < target_sp else (lo, mid)
+  return f32(0.5 * (lo + hi))
+
+
+def f18_failures():
+  """Cases on both sides of every raise site of the transition and the reset, stepped by the reference's own
+  Balloon.simulate_step and perciatelli_reward_function (transition) or BalloonState + cold_start_to_stable_params (reset).
+  Every input is a float32 value.  Thresholds are straddled by one float32 ulp where the input reaches them."""
+  day = units.datetime(2013, 3, 25, 9, 25, 32)
+  base = dict(lat=f32(1.0), lng=f32(10.0), start=day, pressure=f32(9000.0), x=f32(-3e4), y=f32(2e4), ir=f32(255.0),
+              alpha=f32(0.5), tweak=None)
+  nx = lambda v, d: float(np.nextafter(np.float32(v), np.float32(d)))   # the float32 neighbour of v towards d
+  t_lo, t_hi = float.fromhex('0x1.891a7b9611a78p+3'), float.fromhex('0x1.05f0e58469ee5p+13')         # the reference's absorptivity range of T (thermal.py:142-145)
+  ir_lo, ir_hi = float.fromhex('0x1.52847cp-10'), float.fromhex('0x1.0af2d6p+28')
+  p_sol, p_atm = 101325.0, f32(108870.8213)                          # solar.py:194-197; the atmosphere's first transition
+  cases = []   # (name, scenario overrides, state overrides, action, wind, substeps)
+  for name, t in (('t_int_lo_in', f32(t_lo)), ('t_int_lo_out', nx(t_lo, 0)), ('t_int_12_28', 12.28), ('t_int_12_29', 12.29),
+                  ('t_int_12_3', 12.3), ('t_int_hi_in', nx(t_hi, 0)), ('t_int_hi_out', nx(t_hi, 1e9)), ('t_int_8000', 8000.0),
+                  ('t_int_8400', 8400.0)):
+    cases.append((name, {}, {'internal_temperature': f32(t)}, 1, (3.0, -2.0), 18))
+  # a hot balloon low in the atmosphere (superpressure in range): the first stride cools it below 12.28 K, so the reference raises in
+  # the SECOND stride -- the last stride of a 2-stride step, the middle one of 3, an early one of 18 -- and the episode ends there
+  for sub in (2, 3, 18):
+    cases.append((f'hot_stride1_of_{sub}', {'pressure': f32(80000.0)}, {'internal_temperature': 'hot'}, 1, (0.0, 0.0), sub))
+  cases.append(('hot_stride1_down', {'pressure': f32(80000.0)}, {'internal_temperature': 'hot'}, 0, (0.0, 0.0), 18))
+  # a cold balloon high up in 1 K air: the first stride cools it from 12.35 K to ~12.25 K, so the reference raises in the SECOND stride,
+  # and the episode goes on (superpressure ~85 Pa): the raise is not also an ending -- a stride's own temperature check, nothing else
+  for sub in (2, 3, 18):
+    cases.append((f'cool_stride1_of_{sub}_flies_on', {}, {'pressure': f32(300.0), 'ambient_temperature': f32(1.0), 'mols_air': 0.0,
+                                                           'internal_temperature': f32(12.35), 'upwelling_infrared': f32(0.0013)},
+                  1, (0.0, 0.0), sub))
+  for name, ir in (('ir_lo_in', ir_lo), ('ir_lo_out', nx(ir_lo, 0)), ('ir_hi_in', ir_hi), ('ir_hi_out', nx(ir_hi, 1e30))):
+    cases.append((name, {}, {'upwelling_infrared': f32(ir)}, 1, (1.0, 1.0), 18))   # (after the cold start, which raises on it too)
+  for name, p in (('p_solar_in', p_sol), ('p_solar_out', nx(p_sol, 1e6)), ('p_atm_in', p_atm), ('p_atm_out', nx(p_atm, 1e6))):
+    for action in (0, 1):
+      cases.append((f'{name}_{"down" if action == 0 else "stay"}', {}, {'pressure': f32(p)}, action, (2.0, 2.0), 18))
+  cases.append(('terminal_on_entry', {}, {'status': balloon.BalloonStatus.BURST}, 1, (0.0, 0.0), 18))
+  cases.append(('clean', {}, {}, 2, (4.0, -1.0), 18))
+
+  n = len(cases)
+  names = []
+  cols = {k: np.zeros(n) for k in STATE_FLOATS}
+  for k in ('time_elapsed_s', 'sunrise_h', 'sunset'):
+    cols[k] = np.zeros(n, np.int64)
+  for k in ('status', 'last_command', 'alt_fsm', 'env_fsm', 'power_paused'):
+    cols[k] = np.zeros(n, np.uint8)
+  nxt = {k: np.zeros_like(v) for k, v in cols.items()}
+  consts = {k: np.zeros(n) for k in ('center_lat_deg', 'center_lng_deg', 'upwelling_infrared', 'alpha')}
+  start_unix = np.zeros(n, np.int64); actions = np.zeros(n, np.uint8); wind = np.zeros((n, 2)); substeps = np.zeros(n, np.int32)
+  exc = np.zeros(n, np.int8); where = np.zeros(n, np.int8); stride = np.zeros(n, np.int32); reward = np.zeros(n)
+  exc_next = np.full(n, -1, np.int8)   # the class of the NEXT step (same action and wind) where this one neither raised nor ended
+  for j, (name, sc_over, st_over, action, w, sub) in enumerate(cases):
+    s = dict(base, **sc_over)
+    atm = ref_shims.make_atmosphere(s['alpha'])
+    st = build_state(s, atm)
+    for k, v in st_over.items():
+      if v == 'hot':   # no air ballast: the lift gas alone at the temperature that puts the superpressure at 1000 Pa
+        st.mols_air = 0.0
+        st.internal_temperature = f18_hot_temperature(st, 1000.0)
+        st.envelope_volume, st.superpressure = balloon.calculate_superpressure_and_volume(
+            6830.0, 0.0, st.internal_temperature, st.pressure, 1804, 0.0199)
+      else:
+        setattr(st, k, v)
+    f18_round_state(st)
+    b = balloon.Balloon(st)
+    su = int(s['start'].timestamp())
+    names.append(name); start_unix[j] = su; actions[j] = action; wind[j] = w; substeps[j] = sub
+    consts['center_lat_deg'][j] = s['lat']; consts['center_lng_deg'][j] = s['lng']
+    consts['upwelling_infrared'][j] = st.upwelling_infrared; consts['alpha'][j] = s['alpha']
+    snap = snapshot(b.state, su)
+    for k in SNAP_KEYS:
+      cols[k][j] = snap[k]
+    exc[j], where[j], stride[j], reward[j] = f18_step(b, atm, su, action, w, sub)
+    if exc[j] == 0:
+      snap = snapshot(b.state, su)
+      for k in SNAP_KEYS:
+        nxt[k][j] = snap[k]
+      if b.state.status == balloon.BalloonStatus.OK:
+        exc_next[j] = f18_step(b, atm, su, action, w, sub)[0]
+
+  # the reset: BalloonState (its power safety layer asks for the next sunrise: |lat| < 60, solar.py:449) + cold_start_to_stable_params
+  r_cases = [('reset_clean', {}), ('reset_ir_lo_in', {'ir': ir_lo}), ('reset_ir_lo_out', {'ir': nx(ir_lo, 0)}),
+             ('reset_ir_hi_in', {'ir': ir_hi}), ('reset_ir_hi_out', {'ir': nx(ir_hi, 1e30)}),
+             ('reset_p_atm_out', {'pressure': nx(p_atm, 1e6)}), ('reset_lat_59', {'lat': f32(59.5)}), ('reset_lat_60', {'lat': 60.0}),
+             ('reset_lat_m75', {'lat': -75.0})]
+  m = len(r_cases)
+  r_in = {k: np.zeros(m) for k in ('center_lat_deg', 'center_lng_deg', 'pressure', 'x', 'y', 'upwelling_infrared', 'alpha')}
+  r_unix = np.zeros(m, np.int64); r_exc = np.zeros(m, np.int8)
+  r_out = {k: np.zeros(m) for k in ('ambient_temperature', 'internal_temperature', 'mols_air', 'envelope_volume', 'superpressure')}
+  for j, (name, over) in enumerate(r_cases):
+    s = dict(base, **over)
+    names.append(name)
+    for k, v in (('center_lat_deg', s['lat']), ('center_lng_deg', s['lng']), ('pressure', s['pressure']), ('x', s['x']),
+                 ('y', s['y']), ('upwelling_infrared', s['ir']), ('alpha', s['alpha'])):
+      r_in[k][j] = v
+    r_unix[j] = int(s['start'].timestamp())
+    try:
+      atm = ref_shims.make_atmosphere(s['alpha'])
+      st = balloon.BalloonState(center_latlng=s2.LatLng.from_degrees(s['lat'], s['lng']), date_time=s['start'],
+                                x=units.Distance(m=s['x']), y=units.Distance(m=s['y']), pressure=s['pressure'],
+                                upwelling_infrared=s['ir'])
+      stable_init.cold_start_to_stable_params(st, atm)
+      for k in r_out:
+        r_out[k][j] = getattr(st, k)
+    except (AssertionError, ValueError) as e:
+      r_exc[j] = F18_EXC[type(e)]
+  save('f18_failures', names=np.array(names), actions=actions, wind_uv=wind, substeps=substeps, start_unix=start_unix,
+       exc=exc, exc_where=where, exc_stride=stride, exc_next=exc_next, reward=reward, **consts, **cols,
+       **{'next_' + k: v for k, v in nxt.items()}, reset_unix_s=r_unix, reset_exc=r_exc,
+       **{'reset_' + k: v for k, v in r_in.items()}, **{'reset_out_' + k: v for k, v in r_out.items()})
+
+
 if __name__ == '__main__':
   which = sys.argv[1:] or ['all']
   if 'all' in which:
@@ -896,3 +1054,5 @@ if __name__ == '__main__':
     f16_vehicles()
   if 'all' in which or 'f17' in which:
     f17_static_wind_features()
+  if 'all' in which or 'f18' in which:
+    f18_failures()

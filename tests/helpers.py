@@ -149,3 +149,49 @@ def fixture_vehicle(d, vi):
     if v != oracle.VEHICLE_DEFAULTS[k]:
       out[k] = v
   return out
+
+
+# F18 (tests/golden/f18_failures.npz): the reference's exceptions, case by case.  exc: 0 none, 1 AssertionError, 2 ValueError.
+F18_CLASSES = (None, AssertionError, ValueError)
+
+
+def f18_step_cases(d):
+  return int(d['exc'].size)
+
+
+def f18_state(d, rows):
+  """Oracle-typed state dict of the transition cases `rows` of F18 (their pre-step states)."""
+  import oracle
+  rows = np.atleast_1d(rows)
+  st = oracle.new_state(len(rows))
+  for k in STATE_FLOATS + STATE_INTS + STATE_U8 + CONSTS:
+    st[k][:] = d[k][rows]
+  st['start_unix'][:] = d['start_unix'][rows]
+  return st
+
+
+def f18_oracle_class(first):
+  """The exception class the reference raises for the oracle's first failing bits (oracle.step(..., per_env=True)['first']):
+  its stride evaluates the pressure asserts before anything that raises ValueError; power_table's range check is an assert too."""
+  import oracle
+  if first & (oracle.ERR_PRESSURE_RANGE | oracle.ERR_TERMINAL_STEP | oracle.ERR_POWER_TABLE):
+    return 1
+  return 2 if first else 0
+
+
+# Where the device's flag word deliberately differs from the oracle's per-environment bits (INTEGRATION.md, errors):
+#  - a step of an episode that is already over: the reference asserts (balloon.py:288-290), a vectorised environment freezes
+#    the lane and reports nothing;
+#  - within 1 Pa below the atmosphere's first transition pressure the reference's finite-difference probe at p + 1 Pa asserts
+#    (balloon.py:437-441); the device has no probe there and reports what the same stride also raises, SOLAR_RANGE.
+F18_DEVICE_WORD = {'terminal_on_entry': 0, 'p_atm_in_down': 4, 'p_atm_in_stay': 4}
+F18_DEVICE_BITS = 1 | 2 | 4 | 16      # the BLE_FLAG_* bits the oracle also reports (ERR_TERMINAL_STEP = 8 has no device bit)
+
+
+def f18_device_word(d, j, oracle_env):
+  """The flag word a launch of F18 step case j alone must report: the oracle's per-environment bits, but for F18_DEVICE_WORD."""
+  return F18_DEVICE_WORD.get(str(d['names'][j]), int(oracle_env) & F18_DEVICE_BITS)
+
+
+def f18_reference_class(d, j):
+  return F18_CLASSES[int(d['exc'][j])]

@@ -6,6 +6,8 @@ intrinsic layer, so the same source builds with g++.  This covers the arithmetic
 on machines without a GPU.  It is not the product path -- the -m gpu tests exercise the
 real library through the C ABI -- and libm here stands in for v_exp/v_log/v_rcp/v_sqrt.
 """
+import os
+
 import numpy as np
 import pytest
 
@@ -325,3 +327,96 @@ def test_constant_divisions_are_correctly_rounded():
   lib = _load_emul().lib()
   lib.emul_check_constant_divisions.restype = ctypes.c_longlong
   assert lib.emul_check_constant_divisions() == 0
+
+
+# ----------------------------------------------------------------------------- err_flags against the reference (F18)
+def _class_of(word):
+  from balloon_learning_environment_amd import vec_state
+  try:
+    vec_state.raise_for_flags(int(word))
+  except Exception as exc:      # noqa: BLE001 -- the class is what is compared
+    return type(exc)
+  return None
+
+
+def test_absorptivity_thresholds_are_the_reference_predicate():
+  """kAbsTLo / kAbsTHi (csrc/ble_physics.h) are the smallest and the largest double T the reference's
+  total_absorptivity(absorptivity_ir(T), 0.0291) accepts, in its own float64 arithmetic (thermal.py:65-147)."""
+  import re
+  src = open(os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), 'balloon_learning_environment_amd', 'csrc',
+                          'ble_physics.h')).read()
+  lo = float.fromhex(re.search(r'kAbsTLo = (0x[0-9a-fp.+-]+);', src).group(1))
+  hi = float.fromhex(re.search(r'kAbsTHi = (0x[0-9a-fp.+-]+);', src).group(1))
+
+  def raises(t):
+    a = 0.04587 + 0.000232 * (t - 210)
+    f = a * (1.0 + (1.0 - a - 0.0291) / (1.0 - 0.0291))
+    return f < 0.0 or f > 1.0
+  assert not raises(lo) and raises(np.nextafter(lo, 0.0))
+  assert not raises(hi) and raises(np.nextafter(hi, np.inf))
+  assert not any(raises(t) for t in np.linspace(lo, hi, 100001))
+  assert raises(12.28) and not raises(12.29) and raises(8400.0) and not raises(8000.0)
+
+
+def test_f18_error_flags_host_build():
+  """Every F18 transition case through the host build of agent_step, one environment per call: the flag word is the oracle's
+  bits of that environment (helpers.F18_DEVICE_WORD: the deliberate differences), raise_for_flags raises the reference's
+  class, and a clean case's next state is the reference's.  The 12.29 K case failed with the former T_int < 12.3 K predicate."""
+  from helpers import f18_device_word, f18_reference_class, f18_state, f18_step_cases
+  e = _load_emul()
+  d = golden('f18_failures')
+  for j in range(f18_step_cases(d)):
+    name = str(d['names'][j])
+    ost = f18_state(d, j)
+    st = e.state_from_oracle(ost)
+    sub = int(d['substeps'][j])
+    _, _, _, env = e.step(st, d['actions'][j:j + 1], wind_uv=d['wind_uv'][j:j + 1], substeps=sub, per_env=True)
+    _, _, _, err = oracle.step(ost, d['actions'][j:j + 1], wind_uv=d['wind_uv'][j:j + 1], substeps=sub, per_env=True)
+    want = f18_device_word(d, j, err['env'][0])
+    assert int(env[0]) == want, (name, int(env[0]), want)
+    if name not in ('terminal_on_entry', 'p_atm_in_down', 'p_atm_in_stay'):
+      assert _class_of(env[0]) is f18_reference_class(d, j), name
+    if d['exc'][j] == 0:
+      assert st['status'][0] == d['next_status'][j] and st['time_elapsed_s'][0] == d['next_time_elapsed_s'][j], name
+      for k in STATE_FLOATS:
+        assert rel_err(st[k], d['next_' + k][j], FLOORS[k]).max() <= 1e-5, (name, k)
+
+
+def test_f18_reset_flags_host_build():
+  """The reset's range checks (ble_reset.h) on F18's reset cases: the Earth-IR absorptivity and the pressure range raise at the
+  reset, as in the reference; a station at |lat| >= 60 deg is computed."""
+  import ctypes
+  e = _load_emul()
+  d = golden('f18_failures')
+  n0 = int(d['exc'].size)
+  names = [str(s) for s in d['names'][n0:]]
+  m = len(names)
+  f32 = {k: np.ascontiguousarray(d['reset_' + k], np.float32) for k in ('alpha', 'x', 'y', 'pressure', 'center_lat_deg',
+                                                                         'center_lng_deg', 'upwelling_infrared')}
+  start = np.ascontiguousarray(d['reset_unix_s'], np.int64)
+  outs = [np.empty(m) for _ in range(5)]; sr = np.empty(m, np.int64); ss = np.empty(m, np.int64); el = np.empty(m)
+  flags = np.zeros(m, np.uint32)
+  P = lambda a: a.ctypes.data_as(ctypes.c_void_p)
+  e.lib().emul_reset_derive_flags(ctypes.c_int64(m), P(f32['alpha']), P(f32['x']), P(f32['y']), P(f32['pressure']),
+                                  P(f32['center_lat_deg']), P(f32['center_lng_deg']), P(f32['upwelling_infrared']), P(start),
+                                  *[P(o) for o in outs], P(sr), P(ss), P(el), P(flags))
+  for j, name in enumerate(names):
+    want = None if name in ('reset_lat_60', 'reset_lat_m75') else (None, AssertionError, ValueError)[int(d['reset_exc'][j])]
+    assert _class_of(flags[j]) is want, (name, int(flags[j]))
+    if d['reset_exc'][j] == 0:
+      assert abs(outs[1][j] - d['reset_out_internal_temperature'][j]) <= 1e-6 * d['reset_out_internal_temperature'][j], name
+
+
+def test_nonfinite_state_flags_host_build():
+  """A NaN in the state (no reference analogue) is reported as BLE_FLAG_NONFINITE, and only that: the absorptivity check
+  lets NaN pass as the reference's comparisons do.  NaN inputs are kept off the GPU; this is their test."""
+  from helpers import f18_state
+  e = _load_emul()
+  d = golden('f18_failures')
+  clean = [str(s) for s in d['names']].index('clean')
+  for k in ('internal_temperature', 'x'):
+    st = e.state_from_oracle(f18_state(d, clean))
+    st[k][0] = np.nan
+    _, _, _, env = e.step(st, d['actions'][clean:clean + 1], wind_uv=d['wind_uv'][clean:clean + 1], per_env=True)
+    assert int(env[0]) == 32, (k, int(env[0]))
+    assert _class_of(env[0]) is FloatingPointError

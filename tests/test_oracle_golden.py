@@ -599,3 +599,56 @@ def test_f15_kernel_tail_host_build_matches_reference():
   emul.lib().emul_decode_flow(ctypes.c_int64(flow.shape[0]), flow.ctypes.data_as(ctypes.c_void_p), grid.ctypes.data_as(ctypes.c_void_p))
   scale = np.abs(d['fields']).max()
   assert np.abs(grid - d['fields']).max() <= 2e-6 * scale
+
+
+# ----------------------------------------------------------------------------- F18: where the reference raises
+# Cases the oracle deliberately does not follow: a station at |lat| >= 60 deg (BalloonState's power safety layer asserts,
+# solar.py:449) is computed, not raised -- the device does the same (errors).
+F18_ORACLE_COMPUTES = ('reset_lat_60', 'reset_lat_m75')
+
+
+def test_f18_oracle_raises_what_and_where_the_reference_raises():
+  d = golden('f18_failures')
+  n = helpers.f18_step_cases(d)
+  st = helpers.f18_state(d, np.arange(n))
+  start = {k: st[k].copy() for k in ('time_elapsed_s',)}
+  for j in range(n):
+    one = {k: v[j:j + 1].copy() for k, v in st.items()}
+    r, t, e, err = oracle.step(one, d['actions'][j:j + 1], wind_uv=d['wind_uv'][j:j + 1], substeps=int(d['substeps'][j]), per_env=True)
+    name = str(d['names'][j])
+    assert helpers.f18_oracle_class(err['first'][0]) == d['exc'][j], name
+    if d['exc'][j]:
+      assert (err['where'][0], err['stride'][0]) == (d['exc_where'][j], d['exc_stride'][j]), name
+    else:
+      assert err['env'][0] == 0 and err['where'][0] == -1, name
+      for k in STATE_FLOATS:
+        np.testing.assert_allclose(one[k][0], d['next_' + k][j], rtol=1e-9, atol=1e-9, err_msg=f'{name} {k}')
+      for k in ('status', 'time_elapsed_s'):
+        assert one[k][0] == d['next_' + k][j], (name, k)
+      assert abs(r[0] - d['reward'][j]) <= 1e-12, name
+  assert np.array_equal(st['time_elapsed_s'], start['time_elapsed_s'])
+  # the reset: the Newton cold start and the range checks of BalloonState / cold_start_to_stable_params
+  names = [str(s) for s in d['names'][n:]]
+  out, err = oracle.stable_init(d['reset_pressure'], d['reset_center_lat_deg'], d['reset_center_lng_deg'], d['reset_x'], d['reset_y'],
+                                d['reset_unix_s'], d['reset_upwelling_infrared'], d['reset_alpha'], per_env=True)
+  for j, name in enumerate(names):
+    want = 0 if name in F18_ORACLE_COMPUTES else d['reset_exc'][j]
+    assert helpers.f18_oracle_class(err[j]) == want, name
+    if d['reset_exc'][j] == 0:
+      np.testing.assert_allclose(out['internal_temperature'][j], d['reset_out_internal_temperature'][j], rtol=1e-9, err_msg=name)
+  assert [n_ for n_ in F18_ORACLE_COMPUTES if d['reset_exc'][names.index(n_)] != 1] == []    # the reference does raise there
+
+
+def test_f18_oracle_per_env_errors_are_independent_of_the_batch():
+  """oracle.step(per_env=True) over the whole batch gives each case what it gives alone; the OR is the batch's return value."""
+  d = golden('f18_failures')
+  n = helpers.f18_step_cases(d)
+  sub = d['substeps'] == 18
+  rows = np.flatnonzero(sub)
+  st = helpers.f18_state(d, rows)
+  st2 = {k: v.copy() for k, v in st.items()}
+  _, _, _, per = oracle.step(st, d['actions'][rows], wind_uv=d['wind_uv'][rows], per_env=True)
+  _, _, _, err_or = oracle.step(st2, d['actions'][rows], wind_uv=d['wind_uv'][rows])
+  assert int(np.bitwise_or.reduce(per['env'])) == err_or
+  for i, j in enumerate(rows):
+    assert helpers.f18_oracle_class(per['first'][i]) == d['exc'][j], d['names'][j]
