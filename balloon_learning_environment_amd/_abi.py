@@ -99,6 +99,12 @@ class BleNoiseGen(ctypes.Structure):
               ('env_offset', ctypes.c_int64)]       # (ABI 4: the shard's first environment in the global batch; default 0)
 
 
+class BleEvalAcc(ctypes.Structure):
+  """struct ble_eval_acc: the per-environment accumulators of an evaluation (ble_eval_accumulate_f32), device pointers."""
+  _fields_ = [('cumulative_reward', ctypes.c_void_p), ('steps_within_radius', ctypes.c_void_p), ('final_timestep', ctypes.c_void_p),
+              ('done', ctypes.c_void_p), ('end_status', ctypes.c_void_p)]
+
+
 FLEET_MAX_VEHICLES = 16      # BLE_FLEET_MAX_VEHICLES
 
 

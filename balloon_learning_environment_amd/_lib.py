@@ -19,7 +19,7 @@ from balloon_learning_environment_amd import _abi
 _PKG_DIR = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get('BLE_HIP_LIB') or os.path.join(_PKG_DIR, 'libble_hip.so')   # override: experiments only
 _SOURCES = [os.path.join(_PKG_DIR, 'csrc', f) for f in ('ble_kernels.hip', 'ble_step_core.h', 'ble_physics.h', 'ble_intrinsics.h', 'ble_reset.h',
-                                                          'ble_observe.h', 'ble_noise.h', 'ble_decode.h', 'ble_step_split.h')]
+                                                          'ble_observe.h', 'ble_noise.h', 'ble_decode.h', 'ble_step_split.h', 'ble_agent.h')]
 _HEADER = os.path.join(os.path.dirname(_PKG_DIR), 'include', 'ble_abi.h')
 
 ABI_VERSION = 5
@@ -28,6 +28,8 @@ BLE_OK = 0
 FLAG_PRESSURE_RANGE, FLAG_ABSORPTIVITY, FLAG_SOLAR_RANGE, FLAG_POWER_TABLE, FLAG_NONFINITE = 1, 2, 4, 16, 32
 FLAG_GP_WINDOW, FLAG_PRESSURE_SEARCH, FLAG_DAY_CYCLE = 64, 128, 256
 FLAG_VEHICLE_INDEX = 512
+FLAG_AGENT_NO_LEVEL = 1024
+SEEKER_LEVELS = 361
 OBS_DIM, GP_CAPACITY, GP_CHOL_STRIDE = 1099, 128, 7620
 ROW_DOUBLES = 26        # BLE_ROW_DOUBLES
 NOISE_CACHE_ROWS = 53
@@ -36,7 +38,9 @@ NOISE_CACHE_ROWS = 53
 EXPORTS = ('ble_abi_version', 'ble_noise_primitive_version', 'ble_vehicle_default', 'ble_last_hip_error', 'ble_device_count', 'ble_set_step_form', 'ble_step_f32', 'ble_step_n_f32', 'ble_reset_f32', 'ble_reset_at_f32', 'ble_wind_noise_at_f32', 'ble_observe_f32', 'ble_observe_forecast_f32', 'ble_decode_flow_fields_f32', 'ble_wind_noise_f32', 'ble_forecast_f32',
            'ble_forecast_column_f32', 'ble_state_rows_f64', 'ble_power_table_f32', 'ble_probe_atmosphere_f32', 'ble_probe_atmosphere_at_height_f64', 'ble_probe_solar_f32', 'ble_probe_latlng_f64',
            'ble_probe_solar_power_f32', 'ble_probe_thermal_f32', 'ble_probe_sp_volume_f32', 'ble_probe_thermal_vehicle_f32', 'ble_probe_sp_volume_vehicle_f32', 'ble_probe_acs_f32', 'ble_probe_safety_f32',
-           'ble_probe_f64_prims', 'ble_step_fleet_f32', 'ble_step_n_fleet_f32', 'ble_reset_fleet_at_f32', 'ble_observe_forecast_fleet_f32')
+           'ble_probe_f64_prims', 'ble_step_fleet_f32', 'ble_step_n_fleet_f32', 'ble_reset_fleet_at_f32', 'ble_observe_forecast_fleet_f32',
+           'ble_station_seeker_f32', 'ble_eval_accumulate_f32', 'ble_reset_seeded_f32', 'ble_wind_noise_seeded_f32',
+           'ble_observe_live_f32')
 
 
 class BleLibraryError(RuntimeError):
@@ -123,6 +127,11 @@ def lib():
   l.ble_step_n_fleet_f32.argtypes = [st, fleet] + l.ble_step_n_f32.argtypes[1:]
   l.ble_reset_fleet_at_f32.argtypes = [st, fleet] + l.ble_reset_at_f32.argtypes[1:]
   l.ble_observe_forecast_fleet_f32.argtypes = [st, fleet] + l.ble_observe_forecast_f32.argtypes[1:]
+  l.ble_observe_live_f32.argtypes = list(l.ble_observe_f32.argtypes)
+  l.ble_station_seeker_f32.argtypes = [_vp, _i64, _vp, _vp, _vp, _vp, _i64, _vp]
+  l.ble_eval_accumulate_f32.argtypes = [st, _vp, ctypes.POINTER(_abi.BleEvalAcc), ctypes.c_double, _int, _int, _vp, _i64, _vp]
+  l.ble_reset_seeded_f32.argtypes = [st, _vp, _vp, _vp, _int, _vp, _i64, _vp]
+  l.ble_wind_noise_seeded_f32.argtypes = [_vp, _vp, _vp, _vp, _vp, _vp, _int, _vp, _i64, _vp]
   for name in EXPORTS:
     getattr(l, name).restype = _int
   _lib = l

@@ -32,6 +32,7 @@
 #include "ble_step_split.h"
 #include "ble_observe.h"
 #include "ble_decode.h"
+#include "ble_agent.h"
 
 using namespace ble;
 
@@ -534,11 +535,29 @@ __global__ __launch_bounds__(kDecodeThreads) void ble_decode_flow_kernel(const f
   }
 }
 
+// Where a lane's Philox streams come from.  ScalarSeed: one seed for the batch, streams keyed by the GLOBAL environment index
+// (env_offset + i).  EnvSeed: a seed per environment, every stream keyed as environment 0 -- environment i draws what environment 0 of
+// a one-environment batch with seed env_seed[i] draws (an evaluation's seed flies the same episode in any batch, at any position).
+struct ScalarSeed {
+  unsigned long long seed;
+  static constexpr bool kPerEnv = false;
+  __device__ __forceinline__ uint64_t of(int64_t) const { return seed; }
+  __device__ __forceinline__ uint64_t key(int64_t i, int64_t env_offset) const { return (uint64_t)(i + env_offset); }
+};
+struct EnvSeed {
+  const unsigned long long* __restrict__ seed;
+  static constexpr bool kPerEnv = true;
+  __device__ __forceinline__ uint64_t of(int64_t i) const { return seed[i]; }
+  __device__ __forceinline__ uint64_t key(int64_t, int64_t) const { return 0; }
+};
+
 // mode 0: the wind noise (u, v) of every environment at its (x, y, pressure, elapsed);
 // mode 1 (test probe): noise_uv[2 i] = simplex4(x, y, pressure, elapsed as float, seed) -- raw primitive.
+// EnvSeed: the harmonic cache is not used (its entries are keyed by (seed, episode), not by the stream's environment index).
+template <class S = ScalarSeed>
 __global__ __launch_bounds__(256) void ble_wind_noise_kernel(const float* __restrict__ x, const float* __restrict__ y,
                                                              const float* __restrict__ pressure,
-                                                             const int32_t* __restrict__ elapsed, unsigned long long seed,
+                                                             const int32_t* __restrict__ elapsed, S seed,
                                                              const uint32_t* __restrict__ episode, int mode,
                                                              uint32_t* harmonic_cache, float* __restrict__ noise_uv, int64_t n,
                                                              int64_t env_offset) {
@@ -550,12 +569,13 @@ __global__ __launch_bounds__(256) void ble_wind_noise_kernel(const float* __rest
   float u, v;
   if (mode == 0) {
     const uint32_t ep = episode ? episode[i] : 0u;
-    if (harmonic_cache != nullptr)
-      wind_noise_cached(x[i], y[i], pressure[i], elapsed[i], seed, (uint64_t)i, (uint64_t)(i + env_offset), ep, harmonic_cache, n, grad_lut, &u, &v);
+    if (!S::kPerEnv && harmonic_cache != nullptr)
+      wind_noise_cached(x[i], y[i], pressure[i], elapsed[i], seed.of(i), (uint64_t)i, seed.key(i, env_offset), ep, harmonic_cache, n, grad_lut,
+                        &u, &v);
     else
-      wind_noise(x[i], y[i], pressure[i], elapsed[i], seed, (uint64_t)(i + env_offset), ep, grad_lut, &u, &v);
+      wind_noise(x[i], y[i], pressure[i], elapsed[i], seed.of(i), seed.key(i, env_offset), ep, grad_lut, &u, &v);
   } else {
-    u = simplex4(x[i], y[i], pressure[i], (float)elapsed[i] * (1.0f / 3600.0f), (uint32_t)seed, grad_lut);
+    u = simplex4(x[i], y[i], pressure[i], (float)elapsed[i] * (1.0f / 3600.0f), (uint32_t)seed.of(i), grad_lut);
     v = 0.0f;
   }
   noise_uv[2 * i] = u; noise_uv[2 * i + 1] = v;
@@ -570,9 +590,10 @@ __global__ __launch_bounds__(256) void ble_wind_noise_kernel(const float* __rest
 // first drawn for the new episode from Philox(seed ^ kFleetDrawKey, env, episode[i]) -- a stream of its own, so the initial conditions
 // are the draws of the other instantiations bit for bit.
 constexpr unsigned long long kFleetDrawKey = 0xF1EE7C0DEull;
-template <class V = VehicleDefault>
+// S: the seed source (ScalarSeed / EnvSeed above).
+template <class V = VehicleDefault, class S = ScalarSeed>
 __global__ __launch_bounds__(kBlock) void ble_reset_kernel(StateDev st, const uint8_t* __restrict__ mask,
-                                                           unsigned long long seed, uint32_t* episode, int sample,
+                                                           S seed, uint32_t* episode, int sample,
                                                            uint32_t* err_flags, int64_t n, int64_t env_offset, V veh) {
   const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
   uint32_t flags = 0;
@@ -586,7 +607,7 @@ __global__ __launch_bounds__(kBlock) void ble_reset_kernel(StateDev st, const ui
     __syncthreads();
     if (i < n && (mask == nullptr || mask[i] != 0)) {
       if (sample && veh.sample_index) {
-        Philox g = philox_init(seed ^ kFleetDrawKey, (uint64_t)(i + env_offset), episode ? episode[i] : 0u);
+        Philox g = philox_init(seed.of(i) ^ kFleetDrawKey, seed.key(i, env_offset), episode ? episode[i] : 0u);
         vidx = (int)(((uint64_t)philox_u32(g) * (uint64_t)veh.n_vehicles) >> 32);        // uniform in [0, n_vehicles)
         veh.index[i] = (uint8_t)vidx;
       } else {
@@ -606,7 +627,7 @@ __global__ __launch_bounds__(kBlock) void ble_reset_kernel(StateDev st, const ui
     if (sample) {
       const uint32_t ep = episode ? episode[i] : 0u;
       if (episode) episode[i] = ep + 1u;
-      Philox g = philox_init(seed, (uint64_t)(i + env_offset), ep);        // keyed by the GLOBAL environment index
+      Philox g = philox_init(seed.of(i), seed.key(i, env_offset), ep);     // ScalarSeed: keyed by the GLOBAL environment index
       alpha = (float)philox_uniform(g);                                                  // standard_atmosphere.py:82
       start = 1293840000LL + (int64_t)(philox_uniform(g) * (double)(1419984000LL - 1293840000LL));   // sampling.py:65-83
       const double ga = philox_gamma(g, 1.2), gb = philox_gamma(g, 2.0);                // Beta(1.2, 2.0)
@@ -659,6 +680,43 @@ __global__ __launch_bounds__(kBlock) void ble_reset_kernel(StateDev st, const ui
     }
   }
   report_flags(flags, err_flags);
+}
+
+// StationSeekerAgent.pick_action (csrc/ble_agent.h): one wave per environment, four per workgroup.
+constexpr int kSeekerBlock = 256;
+__global__ __launch_bounds__(kSeekerBlock) void ble_station_seeker_kernel(const float* __restrict__ obs, int64_t stride,
+                                                                          uint8_t* __restrict__ action, int32_t* __restrict__ level,
+                                                                          double* __restrict__ scores, uint32_t* err_flags, int64_t n) {
+  const int lane = (int)(threadIdx.x & 63);
+  const int64_t i = (int64_t)blockIdx.x * (kSeekerBlock / 64) + (threadIdx.x >> 6);
+  if (i >= n) return;                                       // (a whole wave: no barrier follows)
+  bool bad;
+  const int lv = seeker_best_level(obs + i * stride, lane, scores != nullptr ? scores + i * kSeekerLevels : nullptr, &bad);
+  if (lane == 0) {
+    action[i] = seeker_action(lv);
+    if (level != nullptr) level[i] = lv;
+    if (bad && err_flags != nullptr) atomicOr(err_flags, kFlagAgentNoLevel);
+  }
+}
+
+// eval_agent's per-step bookkeeping (eval_lib.py:157-190) for the environments that are not yet done: one lane per environment.
+__global__ __launch_bounds__(256) void ble_eval_accumulate_kernel(StateDev st, const float* __restrict__ reward, ble_eval_acc acc,
+                                                                  double radius_m, int step_index, int max_steps, float* __restrict__ path,
+                                                                  double battery_capacity_wh, int64_t n) {
+  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (i >= n || acc.done[i]) return;
+  const int t = step_index + 1;
+  acc.cumulative_reward[i] += (double)reward[i];
+  acc.steps_within_radius[i] += within_radius(st.x[i], st.y[i], radius_m) ? 1 : 0;
+  acc.final_timestep[i] = t;
+  const uint8_t status = st.status[i];
+  if (status != kOk) acc.end_status[i] = status;
+  if (status != kOk || t == max_steps) acc.done[i] = 1;
+  if (path != nullptr) {                                    // SimpleBalloonState.from_balloon_state (eval_lib.py:68-77)
+    float* r = path + i * 6;
+    r[0] = st.x[i]; r[1] = st.y[i]; r[2] = st.pressure[i]; r[3] = st.superpressure[i]; r[4] = (float)st.time_elapsed_s[i];
+    r[5] = (float)((double)st.battery_charge[i] / battery_capacity_wh);
+  }
 }
 
 }  // namespace
@@ -957,9 +1015,12 @@ int ble_forecast_column_f32(const float* wind_grid, int64_t grid_env_stride, con
   return launch_status();
 }
 
-int ble_observe_forecast_f32(const ble_state_f32* st, const float* wind_grid, int64_t grid_env_stride, const float* forecast_levels,
-                             const float* noise_uv, const uint8_t* reset_mask, const ble_gp_history_f32* hist, int append, float* obs,
-                             uint32_t* err_flags, int64_t n, void* stream) {
+extern "C++" {
+namespace {
+template <bool kLiveOnly>
+int launch_observe(const ble_state_f32* st, const float* wind_grid, int64_t grid_env_stride, const float* forecast_levels,
+                   const float* noise_uv, const uint8_t* reset_mask, const ble_gp_history_f32* hist, int append, float* obs,
+                   uint32_t* err_flags, int64_t n, void* stream) {
   if (!state_ok(st) || !wind_grid || !hist || !hist->xyp || !hist->elapsed_s || !hist->err_uv || !hist->count || !obs ||
       n < 0 || grid_env_stride < 0)
     return BLE_E_INVALID_ARG;
@@ -972,13 +1033,27 @@ int ble_observe_forecast_f32(const ble_state_f32* st, const float* wind_grid, in
     return BLE_E_INVALID_ARG;
   if (st->vehicle != nullptr) {
     if (!vehicle_ok(st->vehicle)) return BLE_E_INVALID_ARG;
-    BLE_LAUNCH(ble_observe_kernel<VehicleRt>, dim3((unsigned)n), dim3(kObsBlock), 0, (hipStream_t)stream, state_dev(st), wind_grid,
-               grid_env_stride, noise_uv, reset_mask, h, append, obs, err_flags, n, make_vehicle_rt(st->vehicle), forecast_levels);
+    BLE_LAUNCH((ble_observe_kernel<VehicleRt, kLiveOnly>), dim3((unsigned)n), dim3(kObsBlock), 0, (hipStream_t)stream, state_dev(st),
+               wind_grid, grid_env_stride, noise_uv, reset_mask, h, append, obs, err_flags, n, make_vehicle_rt(st->vehicle), forecast_levels);
   } else {
-    BLE_LAUNCH(ble_observe_kernel<VehicleDefault>, dim3((unsigned)n), dim3(kObsBlock), 0, (hipStream_t)stream, state_dev(st), wind_grid,
-               grid_env_stride, noise_uv, reset_mask, h, append, obs, err_flags, n, VehicleDefault{}, forecast_levels);
+    BLE_LAUNCH((ble_observe_kernel<VehicleDefault, kLiveOnly>), dim3((unsigned)n), dim3(kObsBlock), 0, (hipStream_t)stream, state_dev(st),
+               wind_grid, grid_env_stride, noise_uv, reset_mask, h, append, obs, err_flags, n, VehicleDefault{}, forecast_levels);
   }
   return launch_status();
+}
+}  // namespace
+}  // extern "C++"
+
+int ble_observe_forecast_f32(const ble_state_f32* st, const float* wind_grid, int64_t grid_env_stride, const float* forecast_levels,
+                             const float* noise_uv, const uint8_t* reset_mask, const ble_gp_history_f32* hist, int append, float* obs,
+                             uint32_t* err_flags, int64_t n, void* stream) {
+  return launch_observe<false>(st, wind_grid, grid_env_stride, forecast_levels, noise_uv, reset_mask, hist, append, obs, err_flags, n, stream);
+}
+
+int ble_observe_live_f32(const ble_state_f32* st, const float* wind_grid, int64_t grid_env_stride, const float* noise_uv,
+                         const uint8_t* reset_mask, const ble_gp_history_f32* hist, int append, float* obs, uint32_t* err_flags, int64_t n,
+                         void* stream) {
+  return launch_observe<true>(st, wind_grid, grid_env_stride, nullptr, noise_uv, reset_mask, hist, append, obs, err_flags, n, stream);
 }
 
 int ble_observe_f32(const ble_state_f32* st, const float* wind_grid, int64_t grid_env_stride, const float* noise_uv,
@@ -999,8 +1074,17 @@ int ble_wind_noise_at_f32(const float* x_m, const float* y_m, const float* press
                           float* noise_uv, int64_t env_offset, int64_t n, void* stream) {
   if (!x_m || !y_m || !pressure || !elapsed_s || !noise_uv || n < 0 || env_offset < 0 || mode < 0 || mode > 1) return BLE_E_INVALID_ARG;
   if (n == 0) return BLE_OK;
-  BLE_LAUNCH(ble_wind_noise_kernel, dim3(blocks(n, 256)), dim3(256), 0, (hipStream_t)stream, x_m, y_m, pressure,
-             elapsed_s, seed, episode, mode, harmonic_cache, noise_uv, n, env_offset);
+  BLE_LAUNCH(ble_wind_noise_kernel<ScalarSeed>, dim3(blocks(n, 256)), dim3(256), 0, (hipStream_t)stream, x_m, y_m, pressure,
+             elapsed_s, ScalarSeed{seed}, episode, mode, harmonic_cache, noise_uv, n, env_offset);
+  return launch_status();
+}
+
+int ble_wind_noise_seeded_f32(const float* x_m, const float* y_m, const float* pressure, const int32_t* elapsed_s,
+                              const unsigned long long* env_seed, const uint32_t* episode, int mode, float* noise_uv, int64_t n, void* stream) {
+  if (!x_m || !y_m || !pressure || !elapsed_s || !env_seed || !noise_uv || n < 0 || mode < 0 || mode > 1) return BLE_E_INVALID_ARG;
+  if (n == 0) return BLE_OK;
+  BLE_LAUNCH(ble_wind_noise_kernel<EnvSeed>, dim3(blocks(n, 256)), dim3(256), 0, (hipStream_t)stream, x_m, y_m, pressure,
+             elapsed_s, EnvSeed{env_seed}, episode, mode, (uint32_t*)nullptr, noise_uv, n, (int64_t)0);
   return launch_status();
 }
 
@@ -1109,11 +1193,47 @@ int ble_reset_at_f32(const ble_state_f32* st, const uint8_t* mask, unsigned long
   if (st->vehicle != nullptr && !vehicle_ok(st->vehicle)) return BLE_E_INVALID_ARG;
   if (n == 0) return BLE_OK;
   if (st->vehicle != nullptr)
-    BLE_LAUNCH(ble_reset_kernel<VehicleRt>, dim3(blocks(n, kBlock)), dim3(kBlock), 0, (hipStream_t)stream, state_dev(st), mask, seed,
-               episode, sample, err_flags, n, env_offset, make_vehicle_rt(st->vehicle));
+    BLE_LAUNCH((ble_reset_kernel<VehicleRt, ScalarSeed>), dim3(blocks(n, kBlock)), dim3(kBlock), 0, (hipStream_t)stream, state_dev(st), mask,
+               ScalarSeed{seed}, episode, sample, err_flags, n, env_offset, make_vehicle_rt(st->vehicle));
   else
-    BLE_LAUNCH(ble_reset_kernel<VehicleDefault>, dim3(blocks(n, kBlock)), dim3(kBlock), 0, (hipStream_t)stream, state_dev(st), mask, seed,
-               episode, sample, err_flags, n, env_offset, VehicleDefault{});
+    BLE_LAUNCH((ble_reset_kernel<VehicleDefault, ScalarSeed>), dim3(blocks(n, kBlock)), dim3(kBlock), 0, (hipStream_t)stream, state_dev(st), mask,
+               ScalarSeed{seed}, episode, sample, err_flags, n, env_offset, VehicleDefault{});
+  return launch_status();
+}
+
+int ble_reset_seeded_f32(const ble_state_f32* st, const uint8_t* mask, const unsigned long long* env_seed, uint32_t* episode,
+                         int sample, uint32_t* err_flags, int64_t n, void* stream) {
+  if (!state_ok(st) || !env_seed || n < 0) return BLE_E_INVALID_ARG;
+  if (st->vehicle != nullptr && !vehicle_ok(st->vehicle)) return BLE_E_INVALID_ARG;
+  if (n == 0) return BLE_OK;
+  if (st->vehicle != nullptr)
+    BLE_LAUNCH((ble_reset_kernel<VehicleRt, EnvSeed>), dim3(blocks(n, kBlock)), dim3(kBlock), 0, (hipStream_t)stream, state_dev(st), mask,
+               EnvSeed{env_seed}, episode, sample, err_flags, n, (int64_t)0, make_vehicle_rt(st->vehicle));
+  else
+    BLE_LAUNCH((ble_reset_kernel<VehicleDefault, EnvSeed>), dim3(blocks(n, kBlock)), dim3(kBlock), 0, (hipStream_t)stream, state_dev(st), mask,
+               EnvSeed{env_seed}, episode, sample, err_flags, n, (int64_t)0, VehicleDefault{});
+  return launch_status();
+}
+
+int ble_station_seeker_f32(const float* obs, int64_t obs_row_stride, uint8_t* action, int32_t* level, double* scores, uint32_t* err_flags,
+                           int64_t n, void* stream) {
+  if (!obs || !action || n < 0 || obs_row_stride < BLE_OBS_DIM || n > 4LL * 2147483647LL) return BLE_E_INVALID_ARG;
+  if (n == 0) return BLE_OK;
+  BLE_LAUNCH(ble_station_seeker_kernel, dim3(blocks(n, kSeekerBlock / 64)), dim3(kSeekerBlock), 0, (hipStream_t)stream, obs, obs_row_stride,
+             action, level, scores, err_flags, n);
+  return launch_status();
+}
+
+int ble_eval_accumulate_f32(const ble_state_f32* st, const float* reward, const ble_eval_acc* acc, double radius_m, int step_index,
+                            int max_steps, float* flight_path, int64_t n, void* stream) {
+  if (!state_ok(st) || !reward || !acc || !acc->cumulative_reward || !acc->steps_within_radius || !acc->final_timestep || !acc->done ||
+      !acc->end_status || n < 0 || step_index < 0 || max_steps <= step_index)
+    return BLE_E_INVALID_ARG;
+  if (st->vehicle != nullptr && !vehicle_ok(st->vehicle)) return BLE_E_INVALID_ARG;
+  if (n == 0) return BLE_OK;
+  const double capacity = st->vehicle != nullptr ? st->vehicle->battery_capacity_wh : 3058.56;     // balloon.py:173
+  BLE_LAUNCH(ble_eval_accumulate_kernel, dim3(blocks(n, 256)), dim3(256), 0, (hipStream_t)stream, state_dev(st), reward, *acc, radius_m,
+             step_index, max_steps, flight_path, capacity, n);
   return launch_status();
 }
 
@@ -1188,8 +1308,8 @@ int ble_reset_fleet_at_f32(const ble_state_f32* st, const ble_fleet* fleet, cons
                            int sample, uint32_t* err_flags, int64_t env_offset, int64_t n, void* stream) {
   if (!state_ok(st) || n < 0 || env_offset < 0 || !fleet_ok(st, fleet)) return BLE_E_INVALID_ARG;
   if (n == 0) return BLE_OK;
-  BLE_LAUNCH(ble_reset_kernel<VehicleFleet>, dim3(blocks(n, kBlock)), dim3(kBlock), 0, (hipStream_t)stream, state_dev(st), mask, seed,
-             episode, sample, err_flags, n, env_offset, make_fleet(fleet));
+  BLE_LAUNCH((ble_reset_kernel<VehicleFleet, ScalarSeed>), dim3(blocks(n, kBlock)), dim3(kBlock), 0, (hipStream_t)stream, state_dev(st), mask,
+             ScalarSeed{seed}, episode, sample, err_flags, n, env_offset, make_fleet(fleet));
   return launch_status();
 }
 
@@ -1205,7 +1325,7 @@ int ble_observe_forecast_fleet_f32(const ble_state_f32* st, const ble_fleet* fle
   if (h.chol != nullptr && (h.n_chol == nullptr || h.chol_stride < (int64_t)kCholStride || (h.chol_stride & 1) != 0))
     return BLE_E_INVALID_ARG;
   if (n == 0) return BLE_OK;
-  BLE_LAUNCH(ble_observe_kernel<VehicleFleet>, dim3((unsigned)n), dim3(kObsBlock), 0, (hipStream_t)stream, state_dev(st), wind_grid,
+  BLE_LAUNCH((ble_observe_kernel<VehicleFleet, false>), dim3((unsigned)n), dim3(kObsBlock), 0, (hipStream_t)stream, state_dev(st), wind_grid,
              grid_env_stride, noise_uv, reset_mask, h, append, obs, err_flags, n, make_fleet(fleet), forecast_levels);
   return launch_status();
 }

@@ -336,7 +336,9 @@ __device__ inline double safe_pressure_search_wave(double lev_l, double sp_l, in
   return fabs((target - s1) / (s2 - s1)) * (p2 - p1) + p1;
 }
 
-template <class Veh = VehicleDefault>
+// kLiveOnly (ble_observe_live_f32): an environment whose status is not OK is not observed -- the whole workgroup leaves before it
+// touches the history or the observation row, as the fleet form leaves for an index outside the palette.
+template <class Veh = VehicleDefault, bool kLiveOnly = false>
 __global__ __launch_bounds__(kObsBlock, 2) void ble_observe_kernel(StateDev st, const float* __restrict__ wind_grid,
                                                                 int64_t grid_env_stride,
                                                                 const float* __restrict__ noise_uv,
@@ -363,6 +365,9 @@ __global__ __launch_bounds__(kObsBlock, 2) void ble_observe_kernel(StateDev st, 
       if (tid == 0 && err_flags != nullptr) atomicOr(err_flags, (uint32_t)kFlagVehicleIndex);
       return;
     }
+  }
+  if constexpr (kLiveOnly) {
+    if (st.status[env] != kOk) return;             // (uniform over the workgroup: no barrier has been reached)
   }
   const auto& veh = lane_vehicle(veh_arg, fleet_image(veh_arg), vidx);
 

@@ -92,13 +92,24 @@ class GenerativeWindFieldSampler(grid_wind_field_sampler.GridWindFieldSampler):
     the fields the unsharded batch flies in, and a masked refresh draws what a full one would."""
     g = global_index.to(self.device, torch.int64).reshape(-1, 1)
     e = episode.to(self.device, torch.int64).reshape(-1, 1)
+    return self._keyed_normals(torch.full_like(g, int(seed) & 0x7FFFFFFFFFFFFFFF), g, e)
 
+  @dev.on_own_device
+  def sample_latents_seeded(self, seeds: torch.Tensor, episode: torch.Tensor) -> torch.Tensor:
+    """sample_latents_keyed with a seed per row: row i is sample_latents_keyed(global_index=0, episode[i], seed=seeds[i]) -- the
+    latent of the first environment of a one-environment batch seeded with seeds[i], whatever the batch this row is in."""
+    s = seeds.to(self.device, torch.int64).reshape(-1, 1) & 0x7FFFFFFFFFFFFFFF
+    e = episode.to(self.device, torch.int64).reshape(-1, 1)
+    return self._keyed_normals(s, torch.zeros_like(s), e)
+
+  def _keyed_normals(self, seed: torch.Tensor, g: torch.Tensor, e: torch.Tensor) -> torch.Tensor:
+    """The counter-based normals of both samplers above: seed, g, e are int64 [n, 1] columns (seed already masked to 63 bits)."""
     def mix(z):                                   # splitmix64's finaliser on int64 tensors (two's-complement wrap = mod 2^64)
       z = (z ^ ((z >> 30) & 0x3FFFFFFFF)) * (-4658895280553007687)        # 0xBF58476D1CE4E5B9
       z = (z ^ ((z >> 27) & 0x1FFFFFFFFF)) * (-7723592293110705685)       # 0x94D049BB133111EB
       return z ^ ((z >> 31) & 0x1FFFFFFFF)
     k = torch.arange(NUM_LATENTS, dtype=torch.int64, device=self.device).reshape(1, -1)
-    base = mix(mix(torch.full_like(g, int(seed) & 0x7FFFFFFFFFFFFFFF) + e * (-7046029254386353131)) + g)   # (0x9E3779B97F4A7C15)
+    base = mix(mix(seed + e * (-7046029254386353131)) + g)                # (0x9E3779B97F4A7C15)
     h1, h2 = mix(base + (2 * k + 1) * (-7046029254386353131)), mix(base + (2 * k + 2) * (-7046029254386353131))
     u1 = (((h1 >> 11) & ((1 << 53) - 1)).to(torch.float64) + 0.5) * (1.0 / 9007199254740992.0)           # (0, 1)
     u2 = (((h2 >> 11) & ((1 << 53) - 1)).to(torch.float64)) * (1.0 / 9007199254740992.0)                 # [0, 1)

@@ -1,0 +1,302 @@
+"""Evaluation library (eval/eval_lib.py of the reference): fly an agent over an evaluation suite and report each seed's flight.
+
+`eval_agent` is the reference's serial loop over a BalloonEnv, one seed after another.  `eval_agent_vec` flies every seed of a suite
+at once on the device: a batch of environments reset by seed (`ble_reset_seeded_f32`), the transition, the wind noise, the
+observation, the agent (`ble_station_seeker_f32` or any device callable) and the loop's bookkeeping (`ble_eval_accumulate_f32`), with
+no host synchronisation until the batch has flown.  Seed s flies the first episode of
+VecBalloonEnv(1, seed=s, per_env_fields=True, auto_reset=False) -- the same episode in any batch, at any position.
+"""
+import ctypes
+import dataclasses
+import datetime as dt
+import json
+import logging
+from typing import Any, Callable, List, Optional, Sequence, Union
+
+import numpy as np
+import torch
+
+from balloon_learning_environment_amd import _abi
+from balloon_learning_environment_amd import _lib
+from balloon_learning_environment_amd import device as dev
+from balloon_learning_environment_amd import vec_state
+from balloon_learning_environment_amd.agents import agent as base_agent
+from balloon_learning_environment_amd.agents import station_seeker_agent
+from balloon_learning_environment_amd.env.balloon import balloon
+from balloon_learning_environment_amd.eval import suites
+from balloon_learning_environment_amd.utils import units
+
+
+def _path_row(state: 'SimpleBalloonState') -> dict:
+  return {'x': state.x.kilometers, 'y': state.y.kilometers, 'pressure': state.pressure, 'superpressure': state.superpressure,
+          'elapsed_seconds': state.time_elapsed.total_seconds(), 'power': state.battery_soc}
+
+
+class EvalResultEncoder(json.JSONEncoder):
+  """json.dumps(results, cls=EvalResultEncoder): an EvaluationResult as its fields, a flight-path entry as a row in km / Pa / s /
+  state of charge, a one-element array or tensor as its number (the reference's JSON shape)."""
+
+  def default(self, o: Any):
+    if isinstance(o, SimpleBalloonState):
+      return _path_row(o)
+    if dataclasses.is_dataclass(o):
+      return dict(vars(o))               # one level only: the encoder comes back for the nested values
+    if isinstance(o, (np.ndarray, np.generic, torch.Tensor)) and np.size(o) == 1:
+      return o.item()
+    return super().default(o)
+
+
+@dataclasses.dataclass
+class SimpleBalloonState:
+  """The part of a balloon's state an evaluation keeps for each step of a flight."""
+  x: units.Distance
+  y: units.Distance
+  pressure: float
+  superpressure: float
+  time_elapsed: dt.timedelta
+  battery_soc: float
+
+  @classmethod
+  def from_balloon_state(cls, balloon_state: balloon.BalloonState) -> 'SimpleBalloonState':
+    b = balloon_state
+    return cls(x=b.x, y=b.y, pressure=b.pressure, superpressure=b.superpressure, time_elapsed=b.time_elapsed, battery_soc=b.battery_soc)
+
+
+@dataclasses.dataclass
+class EvaluationResult:
+  """One evaluation flight.
+
+  seed: the seed flown; cumulative_reward: the sum of its rewards; time_within_radius: the share of its steps that ended within the
+  station-keeping radius, in [0, 1]; out_of_power / envelope_burst / zeropressure: the terminal status the flight ended in, if any;
+  final_timestep: the number of steps flown; flight_path: the state after every step (empty unless asked for)."""
+  seed: int
+  cumulative_reward: float
+  time_within_radius: float
+  out_of_power: bool
+  envelope_burst: bool
+  zeropressure: bool
+  final_timestep: int
+  flight_path: Sequence[SimpleBalloonState]
+
+  def __str__(self) -> str:
+    shown = ('seed', 'cumulative_reward', 'time_within_radius', 'out_of_power', 'final_timestep')
+    return 'EvaluationResult(' + ', '.join(f'{k}={getattr(self, k)}' for k in shown) + ')'
+
+
+def _within(balloon_state: balloon.BalloonState, radius: units.Distance) -> bool:
+  return units.relative_distance(balloon_state.x, balloon_state.y) <= radius
+
+
+def _fly_one(agent: base_agent.Agent, env, seed: int, max_steps: int, render_period: int, keep_path: bool) -> EvaluationResult:
+  env.seed(seed)
+  action = agent.begin_episode(env.reset())
+  total, inside, path = 0.0, 0, []
+  reward, terminal, info, steps = 0.0, False, {}, 0
+  while steps < max_steps and not terminal:
+    observation, reward, terminal, info = env.step(action)
+    action = agent.step(reward, observation)
+    state = env.get_simulator_state().balloon_state
+    total += reward
+    inside += _within(state, env.radius)
+    if keep_path:
+      path.append(SimpleBalloonState.from_balloon_state(state))
+    if steps % render_period == 0:
+      env.render()
+    steps += 1
+  agent.end_episode(reward, terminal)
+  ended = (lambda key: bool(info.get(key, False))) if terminal else (lambda key: False)
+  return EvaluationResult(seed=seed, cumulative_reward=total, time_within_radius=inside / steps, out_of_power=ended('out_of_power'),
+                          envelope_burst=ended('envelope_burst'), zeropressure=ended('zeropressure'), final_timestep=steps,
+                          flight_path=path)
+
+
+def eval_agent(agent: base_agent.Agent, env, eval_suite: suites.EvaluationSuite, *, render_period: int = 10,
+               calculate_flight_path: bool = True) -> List[EvaluationResult]:
+  """The reference's serial evaluation (eval/eval_lib.py:122-205) over a BalloonEnv: for each seed, env.seed(seed) and env.reset(), then
+  up to max_episode_length steps, stopping at the first terminal one; the agent sees host observations.  eval_agent_vec flies the
+  seeds side by side on the device."""
+  assert eval_suite.max_episode_length > 0, 'max_episode_length must be > 0.'
+  logging.info('Evaluating %s on %s', agent.get_name(), eval_suite)
+  agent.set_mode(base_agent.AgentMode.EVAL)
+  results = []
+  for k, seed in enumerate(eval_suite.seeds):
+    results.append(_fly_one(agent, env, seed, eval_suite.max_episode_length, render_period, calculate_flight_path))
+    logging.info('%d / %d: (seed %d) %s', k + 1, len(eval_suite.seeds), seed, results[-1])
+  return results
+
+
+# ------------------------------------------------------------------------------------------------------------------ the device loop
+DeviceAgent = Callable[[torch.Tensor], torch.Tensor]
+
+
+def _shared_grid(wind_field, device) -> torch.Tensor:
+  """A wind field flown by every seed of the batch: a GridBasedWindField (its current grid) or a (21, 21, 10, 9, 2) array."""
+  g = getattr(wind_field, 'grid', wind_field)
+  if g is None:
+    raise ValueError('eval_agent_vec: the wind field has no grid yet (set_field / reset it first)')
+  g = g if isinstance(g, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(g, np.float32))
+  g = g.to(device=device, dtype=torch.float32).contiguous()
+  if tuple(g.shape) != tuple(vec_state.GRID_SHAPE):
+    raise ValueError(f'eval_agent_vec: a shared wind field is one grid of shape {vec_state.GRID_SHAPE}, not {tuple(g.shape)}')
+  return g
+
+
+class VecEvaluator:
+  """The device state of one batch of `n` evaluation flights, reusable for batch after batch of the same size.
+
+  run(seeds) flies seeds (a list of n ints) for max_steps steps:
+    seeded reset -> [field decode] -> noise -> observe -> agent -> (step -> noise -> observe -> agent -> accumulate) x max_steps
+  The observation skips the environments whose flight has terminated (status not OK: `ble_observe_live_f32`), as the reference's loop
+  stops at the terminal step; their lanes stay frozen in the step kernel and the bookkeeping counts nothing after that step.
+  Every launch goes to the current stream of `device`; with capture_graph the part in brackets before the bookkeeping is one HIP
+  graph, replayed every step (the bookkeeping takes the step's index as an argument and is launched after it)."""
+
+  def __init__(self, n: int, agent: Union['DeviceAgent', Any], max_steps: int, *, wind_field=None, wind_noise: bool = True,
+               radius_km: float = 50.0, calculate_flight_path: bool = False, capture_graph: bool = True, device='cuda:0'):
+    self.device = dev.require_gpu(device)
+    self.n, self.max_steps, self.agent = int(n), int(max_steps), agent
+    assert self.n > 0 and self.max_steps > 0
+    self.radius_m = units.Distance(km=radius_km).meters
+    self.lib = _lib.lib()
+    with torch.cuda.device(self.device):
+      self.sim = vec_state.VecSimulator(self.n, self.device)
+      z = lambda dtype, *shape: torch.zeros(*shape, dtype=dtype, device=self.device)
+      self.seeds = z(torch.int64, self.n)
+      self.action = torch.ones(self.n, dtype=torch.uint8, device=self.device)
+      self.obs = z(torch.float32, self.n, _lib.OBS_DIM)
+      self.noise = z(torch.float32, self.n, 2) if wind_noise else None
+      self.cumulative_reward = z(torch.float64, self.n)
+      self.steps_within_radius = z(torch.int32, self.n)
+      self.final_timestep = z(torch.int32, self.n)
+      self.done = z(torch.uint8, self.n)
+      self.end_status = z(torch.uint8, self.n)
+      self.path = z(torch.float32, self.max_steps, self.n, 6) if calculate_flight_path else None
+      self.sampler = None
+      if wind_field is None:             # the generative field, one per seed (VecBalloonArena(per_env_fields=True))
+        from balloon_learning_environment_amd.env import generative_wind_field
+        self.sampler = generative_wind_field.GenerativeWindFieldSampler(device=self.device)
+        self.grids = torch.empty((self.n,) + tuple(vec_state.GRID_SHAPE), dtype=torch.float32, device=self.device)
+      else:
+        self.sim.set_grid(_shared_grid(wind_field, self.device))
+    self._acc = _abi.BleEvalAcc(self.cumulative_reward.data_ptr(), self.steps_within_radius.data_ptr(), self.final_timestep.data_ptr(),
+                                self.done.data_ptr(), self.end_status.data_ptr())
+    self.capture_graph = bool(capture_graph)
+    self._graph = None
+
+  def _act(self, obs: torch.Tensor) -> None:
+    if isinstance(self.agent, station_seeker_agent.VecStationSeekerAgent):
+      self.agent.act(obs, out=self.action)
+    else:
+      a = self.agent(obs)
+      assert isinstance(a, torch.Tensor) and a.dtype == torch.uint8 and a.numel() == self.n and a.device == self.device, \
+          'an evaluated agent maps the [N, 1099] device observation to uint8 [N] device actions'
+      self.action.copy_(a.reshape(-1))
+
+  def _observe_and_act(self) -> None:
+    if self.noise is not None:
+      self.sim.wind_noise_seeded(self.seeds, out=self.noise)
+    self.sim.observe(self.noise, out=self.obs, live_only=True)     # (a finished flight is not observed again)
+    self._act(self.obs)
+
+  def _step(self) -> None:
+    self.sim.step(self.action, self.noise)
+    self._observe_and_act()
+
+  def _capture(self) -> None:
+    side = torch.cuda.Stream(device=self.device)
+    side.wait_stream(torch.cuda.current_stream(self.device))
+    graph = torch.cuda.CUDAGraph()
+    with torch.cuda.stream(side):
+      with torch.cuda.graph(graph, stream=side):
+        self._step()
+    torch.cuda.current_stream(self.device).wait_stream(side)
+    self._graph = graph
+
+  def _accumulate(self, t: int) -> None:
+    path = 0 if self.path is None else self.path[t].data_ptr()
+    _lib.check(self.lib.ble_eval_accumulate_f32(ctypes.byref(self.sim._struct), self.sim.reward.data_ptr(), ctypes.byref(self._acc),
+                                                self.radius_m, t, self.max_steps, path, self.n, dev.stream_ptr(self.device)),
+               'ble_eval_accumulate_f32')
+
+  @dev.on_own_device
+  def launch(self, seeds: Sequence[int]) -> None:
+    """Enqueues the flights of `seeds` (n ints, each taken mod 2^64); nothing is synchronised."""
+    assert len(seeds) == self.n
+    s = np.array([int(v) & (2 ** 64 - 1) for v in seeds], dtype=np.uint64).view(np.int64)
+    self.seeds.copy_(torch.from_numpy(s), non_blocking=False)
+    self.sim.episode.zero_()
+    self.sim.reset_device_seeded(self.seeds)
+    if self.sampler is not None:          # after the reset: the latent of episode counter 1, as VecBalloonArena decodes it
+      self.sampler.decode(self.sampler.sample_latents_seeded(self.seeds, self.sim.episode), self.grids)
+      self.sim.set_grid(self.grids, per_env=True)
+    for t in (self.cumulative_reward, self.steps_within_radius, self.final_timestep, self.done, self.end_status):
+      t.zero_()
+    self._observe_and_act()
+    if self.capture_graph and self._graph is None:
+      self._capture()
+    for t in range(self.max_steps):
+      if self._graph is not None:
+        self._graph.replay()
+      else:
+        self._step()
+      self._accumulate(t)
+
+  def results(self, seeds: Sequence[int]) -> List[EvaluationResult]:
+    """Synchronises, raises what the reference would have raised, and reads the flights back."""
+    self.sim.check_errors()
+    check = getattr(self.agent, 'check_errors', None)
+    if check is not None:
+      check()
+    reward = self.cumulative_reward.cpu().numpy()
+    within = self.steps_within_radius.cpu().numpy()
+    final = self.final_timestep.cpu().numpy()
+    status = self.end_status.cpu().numpy()
+    path = None if self.path is None else self.path.cpu().numpy()
+    out = []
+    for i, seed in enumerate(seeds):
+      steps = int(final[i])
+      fp = []
+      if path is not None:
+        for r in path[:steps, i].tolist():
+          fp.append(SimpleBalloonState(units.Distance(m=r[0]), units.Distance(m=r[1]), r[2], r[3], dt.timedelta(seconds=int(r[4])), r[5]))
+      out.append(EvaluationResult(seed=seed, cumulative_reward=float(reward[i]), time_within_radius=int(within[i]) / steps,
+                                  out_of_power=bool(status[i] == balloon.BalloonStatus.OUT_OF_POWER.value),
+                                  envelope_burst=bool(status[i] == balloon.BalloonStatus.BURST.value),
+                                  zeropressure=bool(status[i] == balloon.BalloonStatus.ZEROPRESSURE.value),
+                                  final_timestep=steps, flight_path=fp))
+    return out
+
+
+def eval_agent_vec(agent, suite: suites.EvaluationSuite, *, batch_size: Optional[int] = None, wind_field=None, wind_noise: bool = True,
+                   radius_km: float = 50.0, calculate_flight_path: bool = False, capture_graph: bool = True,
+                   device='cuda:0') -> List[EvaluationResult]:
+  """Flies every seed of `suite` on the device, `batch_size` seeds at a time (default: all of them, up to 16 384), and returns one
+  EvaluationResult per seed in the suite's order -- what eval_agent returns for a deterministic agent over
+  VecBalloonEnv(1, seed=s, per_env_fields=True, auto_reset=False)-shaped environments.
+
+  agent: a VecStationSeekerAgent, or any callable from the [N, 1099] float32 device observation to uint8 [N] device actions that
+    needs no host synchronisation (it is captured in a graph with capture_graph).
+  wind_field: None (default) -- the generative field, one decoded per seed; otherwise a wind field every seed flies in (a
+    GridBasedWindField's current grid, or one (21, 21, 10, 9, 2) grid), not resampled per seed.
+  wind_noise: ground truth = forecast + the seed's SimplexWindNoise (default, as the reference); False: forecast == truth.
+  radius_km: the station-keeping radius of time_within_radius (the reward's radius is the kernel's 50 km).
+  calculate_flight_path: keep every step's SimpleBalloonState (24 bytes per seed and step of device memory)."""
+  device = dev.require_gpu(device)
+  seeds = list(suite.seeds)
+  assert suite.max_episode_length > 0, 'max_episode_length must be > 0.'
+  if not seeds:
+    return []
+  batch_size = min(len(seeds), 16384) if batch_size is None else int(batch_size)
+  assert batch_size > 0
+  evaluators = {}
+  results: List[EvaluationResult] = []
+  for lo in range(0, len(seeds), batch_size):
+    chunk = seeds[lo:lo + batch_size]
+    ev = evaluators.get(len(chunk))
+    if ev is None:
+      ev = evaluators[len(chunk)] = VecEvaluator(len(chunk), agent, suite.max_episode_length, wind_field=wind_field,
+                                                 wind_noise=wind_noise, radius_km=radius_km, calculate_flight_path=calculate_flight_path,
+                                                 capture_graph=capture_graph, device=device)
+    ev.launch(chunk)
+    results.extend(ev.results(chunk))
+  return results

@@ -42,6 +42,8 @@ def raise_for_flags(flags: int) -> None:
     raise ZeroDivisionError('float division by zero')                     # features.py:432-437 at a station in polar night
   if flags & _lib.FLAG_VEHICLE_INDEX:
     raise ValueError('vehicle_index outside the fleet palette: those environments were not stepped, reset or observed')
+  if flags & _lib.FLAG_AGENT_NO_LEVEL:
+    raise AssertionError('At least one pressure level should be valid.')   # station_seeker_agent.py:113-115 (or a non-finite feature)
   if flags & _lib.FLAG_GP_WINDOW:
     raise OverflowError('WindGP window holds more than 120 observations (agent steps shorter than 180 s)')
 
@@ -226,17 +228,40 @@ class VecSimulator:
       else:
         torch.maximum(self._obs_reset, mask, out=self._obs_reset)
 
+  @_on_own_device
+  def reset_device_seeded(self, env_seed: torch.Tensor, mask: Optional[torch.Tensor] = None, sample: bool = True) -> None:
+    """reset_device with a seed per environment (`env_seed`: int64 device [n], read as uint64): environment i draws what environment 0
+    of a one-environment simulator reset with seed env_seed[i] draws (`ble_reset_seeded_f32`).  Not for fleets."""
+    if self.has_fleet:
+      raise ValueError('reset_device_seeded: a fleet resets with one seed for the batch (reset_device)')
+    self._check_env_seed(env_seed)
+    if mask is not None:
+      assert mask.dtype == torch.uint8 and mask.is_contiguous() and mask.numel() == self.n
+    _lib.check(self.lib.ble_reset_seeded_f32(ctypes.byref(self._struct), dev.ptr(mask), env_seed.data_ptr(), self.episode.data_ptr(),
+                                             1 if sample else 0, self.err_flags.data_ptr(), self.n, dev.stream_ptr(self.device)),
+               'ble_reset_seeded_f32')
+    if self._gp is not None:
+      if mask is None:
+        self._obs_reset.fill_(1)
+      else:
+        torch.maximum(self._obs_reset, mask, out=self._obs_reset)
+
+  def _check_env_seed(self, env_seed: torch.Tensor) -> None:
+    assert env_seed.dtype == torch.int64 and env_seed.is_contiguous() and env_seed.numel() == self.n and env_seed.device == self.device
+
   # ------------------------------------------------------------------ observation
   @_on_own_device
   def observe(self, noise_uv: Optional[torch.Tensor] = None, append: bool = True,
               out: Optional[torch.Tensor] = None, carry_factor: bool = True,
-              forecast_levels: Optional[torch.Tensor] = None) -> torch.Tensor:
+              forecast_levels: Optional[torch.Tensor] = None, live_only: bool = False) -> torch.Tensor:
     """PerciatelliFeatureConstructor.observe + get_features for every env: [n, 1099] float32
     device tensor.  `noise_uv` [n, 2]: measured wind minus forecast at the balloons (None = 0).
     carry_factor (fixed by the first call): keep each env's WindGP Cholesky factor in HBM (61 KB per
     env) and slide it from step to step instead of refactoring the whole window every call.
     forecast_levels [n, 181, 2] float32: the forecast (u, v) at the 181 levels 5 000 .. 14 000 Pa above every balloon as the
-    CALLER's WindField gives it (a forecast that is not a grid: `ble_observe_forecast_f32`); None: from the grid."""
+    CALLER's WindField gives it (a forecast that is not a grid: `ble_observe_forecast_f32`); None: from the grid.
+    live_only: observe only the environments whose status is OK (`ble_observe_live_f32`): a terminated environment's history,
+    observation row and pending history restart are left as they are (an evaluation stops observing a finished flight)."""
     assert self.grid is not None, 'Must call set_grid (reset) before observe.'
     if self._gp is None:
       self._allocate_history(carry_factor)
@@ -249,6 +274,13 @@ class VecSimulator:
       assert forecast_levels.dtype == torch.float32 and forecast_levels.is_contiguous() and tuple(forecast_levels.shape) == (self.n, 181, 2)
     args = (self.grid.data_ptr(), self.grid_env_stride, dev.ptr(forecast_levels), dev.ptr(noise_uv), self._obs_reset.data_ptr(),
             ctypes.byref(self._gp_struct), 1 if append else 0, out.data_ptr(), self.err_flags.data_ptr(), self.n, dev.stream_ptr(self.device))
+    if live_only:
+      if self.has_fleet or forecast_levels is not None:
+        raise ValueError('observe(live_only=True) is for a single-vehicle batch over its grid')
+      args = args[:2] + args[3:]
+      _lib.check(self.lib.ble_observe_live_f32(ctypes.byref(self._struct), *args), 'ble_observe_live_f32')
+      self._obs_reset.masked_fill_(self.state['status'] == 0, 0)        # (the lanes observed)
+      return out
     if self.has_fleet:
       _lib.check(self.lib.ble_observe_forecast_fleet_f32(ctypes.byref(self._struct), ctypes.byref(self._fleet), *args), 'ble_observe_forecast_fleet_f32')
     else:
@@ -353,6 +385,20 @@ class VecSimulator:
                                           0, self._noise_cache.data_ptr(), out.data_ptr(), self.env_offset, self.n,
                                           dev.stream_ptr(self.device))
     _lib.check(code, 'ble_wind_noise_at_f32')
+    return out
+
+  @_on_own_device
+  def wind_noise_seeded(self, env_seed: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """wind_noise with a seed per environment (`ble_wind_noise_seeded_f32`): environment i gets the noise environment 0 of a
+    one-environment simulator gets from wind_noise(env_seed[i]) at the same position, time and episode."""
+    self._check_env_seed(env_seed)
+    if out is None:
+      out = torch.empty(self.n, 2, dtype=torch.float32, device=self.device)
+    assert out.dtype == torch.float32 and out.is_contiguous() and tuple(out.shape) == (self.n, 2)
+    s = self.state
+    _lib.check(self.lib.ble_wind_noise_seeded_f32(s['x'].data_ptr(), s['y'].data_ptr(), s['pressure'].data_ptr(),
+                                                  s['time_elapsed_s'].data_ptr(), env_seed.data_ptr(), self.episode.data_ptr(), 0,
+                                                  out.data_ptr(), self.n, dev.stream_ptr(self.device)), 'ble_wind_noise_seeded_f32')
     return out
 
   def reset_observation_history(self, mask: Optional[torch.Tensor] = None) -> None:

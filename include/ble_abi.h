@@ -69,6 +69,8 @@ extern "C" {
                                       (polar night); the two day-cycle features of that environment are NaN */
 #define BLE_FLAG_VEHICLE_INDEX 512u /* a fleet call (ble_fleet): an environment's vehicle_index >= n_vehicles -- the lane is frozen
                                        (state, history and observation untouched), nothing is read outside the palette */
+#define BLE_FLAG_AGENT_NO_LEVEL 1024u /* ble_station_seeker_f32: no valid pressure level (station_seeker_agent.py:113-115 assert), or a
+                                         feature the score reads is not finite -- action STAY (1), level -1 */
 
 /* wind grid geometry: generative/vae.py:30-38,77-93 (FieldShape defaults) */
 #define BLE_GRID_NX 21 /* x (lat axis of the grid), -500..500 km step 50 */
@@ -499,6 +501,61 @@ int ble_observe_forecast_fleet_f32(const ble_state_f32* st, const ble_fleet* fle
                                    const float* forecast_levels, const float* noise_uv, const uint8_t* reset_mask,
                                    const ble_gp_history_f32* hist, int append, float* obs, uint32_t* err_flags, int64_t n,
                                    void* stream);
+
+/*
+ * Evaluation (additive to ABI 5): the StationSeeker controller, eval_agent's per-step bookkeeping and per-environment seeds.
+ *
+ * ble_station_seeker_f32: StationSeekerAgent.pick_action / find_best_pressure_level / altitude_score / wind_score
+ * (agents/station_seeker_agent.py:72-186) on the feature decoding of env/features.py:146-266, in float64 on the float32 features.
+ *   obs             device float32 [n] rows of BLE_OBS_DIM features, obs_row_stride (>= BLE_OBS_DIM) floats apart
+ *   action          device uint8 [n]: UP (2) below the centre level 180, DOWN (0) above it, STAY (1) at it
+ *   level           optional device int32 [n]: the chosen relative level 0 .. 360 (the reference's first strict maximum)
+ *   scores          optional device double [n][361]: every level's altitude_score, 0 where the level is not valid
+ *   err_flags       optional device uint32: BLE_FLAG_AGENT_NO_LEVEL (action 1, level -1 for that environment)
+ */
+int ble_station_seeker_f32(const float* obs, int64_t obs_row_stride, uint8_t* action, int32_t* level, double* scores,
+                           uint32_t* err_flags, int64_t n, void* stream);
+
+/*
+ * ble_eval_accumulate_f32: the body of eval_agent's step loop (eval/eval_lib.py:157-190) after a transition, for every environment
+ * with done[i] == 0: cumulative_reward += reward (float64), steps_within_radius += (sqrt(x^2 + y^2) <= radius_m, float64 on the
+ * float32 state, not contracted), final_timestep = step_index + 1; a status other than OK is stored in end_status and sets done, and so
+ * does step_index + 1 == max_steps.  Nothing of an environment that is done is touched.  All five arrays are device [n] and required.
+ *   flight_path     optional device float32 [n][6]: this step's SimpleBalloonState row of every environment not done before the call --
+ *                   x [m], y [m], pressure [Pa], superpressure [Pa], elapsed [s], battery state of charge (st->vehicle's capacity)
+ */
+typedef struct ble_eval_acc {
+  double* cumulative_reward;
+  int32_t* steps_within_radius;
+  int32_t* final_timestep;
+  uint8_t* done;
+  uint8_t* end_status;
+} ble_eval_acc;
+int ble_eval_accumulate_f32(const ble_state_f32* st, const float* reward, const ble_eval_acc* acc, double radius_m, int step_index,
+                            int max_steps, float* flight_path, int64_t n, void* stream);
+
+/*
+ * ble_observe_live_f32: ble_observe_f32 for the environments whose status is OK only.  An environment that has terminated (status
+ * OUT_OF_POWER, BURST or ZEROPRESSURE) is not observed: its WindGP history, its observation row and err_flags are left as they are --
+ * the reference's eval_agent stops observing a balloon once its episode is done (eval/eval_lib.py:185-190), and the step kernels
+ * freeze such a lane's clock, so observing it again would add entries at one frozen time.
+ */
+int ble_observe_live_f32(const ble_state_f32* st, const float* wind_grid, int64_t grid_env_stride, const float* noise_uv,
+                         const uint8_t* reset_mask, const ble_gp_history_f32* hist, int append, float* obs, uint32_t* err_flags, int64_t n,
+                         void* stream);
+
+/*
+ * Per-environment seeds: ble_reset_f32 and ble_wind_noise_f32 with a device seed per environment (env_seed, uint64 [n]) in place of the
+ * batch's scalar seed.  Environment i draws from the Philox streams that environment 0 of a one-environment batch with scalar seed
+ * env_seed[i] draws from: key (env_seed[i], 0, episode[i]) -- a seed flies the same episode in any batch and at any position.
+ * st->vehicle is honoured as by ble_reset_f32 (fleets are not).  The noise form keeps no harmonic cache: it draws the harmonics from
+ * the Philox stream on every call (same values).
+ */
+int ble_reset_seeded_f32(const ble_state_f32* st, const uint8_t* mask, const unsigned long long* env_seed, uint32_t* episode,
+                         int sample, uint32_t* err_flags, int64_t n, void* stream);
+int ble_wind_noise_seeded_f32(const float* x_m, const float* y_m, const float* pressure, const int32_t* elapsed_s,
+                              const unsigned long long* env_seed, const uint32_t* episode, int mode, float* noise_uv, int64_t n,
+                              void* stream);
 
 #ifdef __cplusplus
 }
