@@ -128,3 +128,11 @@ def fleet_struct(vehicles, index_ptr: int, sample_index: bool = False) -> BleFle
   f = BleFleet(ctypes.cast(palette, ctypes.POINTER(BleVehicle)), n, 1 if sample_index else 0, int(index_ptr) or None)
   f._palette_keepalive = palette
   return f
+
+
+class BleQnetF32(ctypes.Structure):
+  """struct ble_qnet_f32: the shape of a QuantileNetwork / MLPNetwork and the DEVICE pointer to its packed weights
+  (ble_qnet_pack_f32's image)."""
+  _fields_ = [('num_layers', ctypes.c_int32), ('input_dim', ctypes.c_int32), ('hidden_units', ctypes.c_int32),
+              ('num_actions', ctypes.c_int32), ('num_atoms', ctypes.c_int32), ('reserved_', ctypes.c_int32),
+              ('weights', ctypes.c_void_p)]

@@ -19,7 +19,7 @@ from balloon_learning_environment_amd import _abi
 _PKG_DIR = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get('BLE_HIP_LIB') or os.path.join(_PKG_DIR, 'libble_hip.so')   # override: experiments only
 _SOURCES = [os.path.join(_PKG_DIR, 'csrc', f) for f in ('ble_kernels.hip', 'ble_step_core.h', 'ble_physics.h', 'ble_intrinsics.h', 'ble_reset.h',
-                                                          'ble_observe.h', 'ble_noise.h', 'ble_decode.h', 'ble_step_split.h', 'ble_agent.h')]
+                                                          'ble_observe.h', 'ble_noise.h', 'ble_decode.h', 'ble_step_split.h', 'ble_agent.h', 'ble_qnet.h')]
 _HEADER = os.path.join(os.path.dirname(_PKG_DIR), 'include', 'ble_abi.h')
 
 ABI_VERSION = 5
@@ -40,7 +40,7 @@ EXPORTS = ('ble_abi_version', 'ble_noise_primitive_version', 'ble_vehicle_defaul
            'ble_probe_solar_power_f32', 'ble_probe_thermal_f32', 'ble_probe_sp_volume_f32', 'ble_probe_thermal_vehicle_f32', 'ble_probe_sp_volume_vehicle_f32', 'ble_probe_acs_f32', 'ble_probe_safety_f32',
            'ble_probe_f64_prims', 'ble_step_fleet_f32', 'ble_step_n_fleet_f32', 'ble_reset_fleet_at_f32', 'ble_observe_forecast_fleet_f32',
            'ble_station_seeker_f32', 'ble_eval_accumulate_f32', 'ble_reset_seeded_f32', 'ble_wind_noise_seeded_f32',
-           'ble_observe_live_f32')
+           'ble_observe_live_f32', 'ble_qnet_workspace_f32', 'ble_qnet_pack_f32', 'ble_qnet_forward_f32')
 
 
 class BleLibraryError(RuntimeError):
@@ -132,6 +132,10 @@ def lib():
   l.ble_eval_accumulate_f32.argtypes = [st, _vp, ctypes.POINTER(_abi.BleEvalAcc), ctypes.c_double, _int, _int, _vp, _i64, _vp]
   l.ble_reset_seeded_f32.argtypes = [st, _vp, _vp, _vp, _int, _vp, _i64, _vp]
   l.ble_wind_noise_seeded_f32.argtypes = [_vp, _vp, _vp, _vp, _vp, _vp, _int, _vp, _i64, _vp]
+  qnet = ctypes.POINTER(_abi.BleQnetF32)
+  l.ble_qnet_workspace_f32.argtypes = [qnet, _i64, ctypes.POINTER(_i64), ctypes.POINTER(_i64)]
+  l.ble_qnet_pack_f32.argtypes = [qnet, ctypes.POINTER(_vp), ctypes.POINTER(_vp), _vp]
+  l.ble_qnet_forward_f32.argtypes = [qnet, _vp, _i64, _vp, _vp, _vp, _i64, _vp]
   for name in EXPORTS:
     getattr(l, name).restype = _int
   _lib = l

@@ -33,6 +33,7 @@
 #include "ble_observe.h"
 #include "ble_decode.h"
 #include "ble_agent.h"
+#include "ble_qnet.h"
 
 using namespace ble;
 
@@ -898,6 +899,24 @@ static_assert(sizeof(StateDev) + 10 * 8 + sizeof(GpHistory) + sizeof(VehicleFlee
 
 }  // namespace
 
+// Q-network agents: the descriptor checks and sizes of ble_qnet_*_f32
+namespace {
+bool qnet_ok(const ble_qnet_f32* net) {
+  return net != nullptr && net->num_layers >= 1 && net->num_layers <= kQnetMaxLayers && net->input_dim == BLE_OBS_DIM &&
+         net->num_actions == 3 && net->num_atoms >= 1 && net->num_atoms <= kQnetMaxAtoms &&
+         (net->num_layers == 1 || (net->hidden_units >= 1 && net->hidden_units <= kQnetMaxHidden));
+}
+QnetLayerDims qnet_dims(const ble_qnet_f32* net, int l) {
+  return qnet_layer(net->num_layers, net->input_dim, net->hidden_units, net->num_actions, net->num_atoms, l);
+}
+// floats per scratch row: the widest padded output of any layer
+int64_t qnet_scratch_ld(const ble_qnet_f32* net) {
+  int64_t ld = 0;
+  for (int l = 0; l < net->num_layers; ++l) ld = std::max<int64_t>(ld, qnet_dims(net, l).mp);
+  return ld;
+}
+}  // namespace
+
 extern "C" {
 
 int ble_abi_version(void) { return BLE_ABI_VERSION; }
@@ -1221,6 +1240,57 @@ int ble_station_seeker_f32(const float* obs, int64_t obs_row_stride, uint8_t* ac
   if (n == 0) return BLE_OK;
   BLE_LAUNCH(ble_station_seeker_kernel, dim3(blocks(n, kSeekerBlock / 64)), dim3(kSeekerBlock), 0, (hipStream_t)stream, obs, obs_row_stride,
              action, level, scores, err_flags, n);
+  return launch_status();
+}
+
+// ---------------------------------------------------------------------------------------------------------------- Q-network agents
+int ble_qnet_workspace_f32(const ble_qnet_f32* net, int64_t n, int64_t* packed_floats, int64_t* scratch_floats) {
+  if (!qnet_ok(net) || n < 0) return BLE_E_INVALID_ARG;
+  if (packed_floats != nullptr) {
+    const QnetLayerDims last = qnet_dims(net, net->num_layers - 1);
+    *packed_floats = last.offset + (int64_t)last.kp * last.mp + last.mp;
+  }
+  if (scratch_floats != nullptr) *scratch_floats = 2 * n * qnet_scratch_ld(net);
+  return BLE_OK;
+}
+
+int ble_qnet_pack_f32(const ble_qnet_f32* net, const float* const* kernel, const float* const* bias, float* packed) {
+  if (!qnet_ok(net) || !kernel || !bias || !packed) return BLE_E_INVALID_ARG;
+  for (int l = 0; l < net->num_layers; ++l)
+    if (!kernel[l] || !bias[l]) return BLE_E_INVALID_ARG;
+  qnet_pack(net->num_layers, net->input_dim, net->hidden_units, net->num_actions, net->num_atoms, kernel, bias, packed);
+  return BLE_OK;
+}
+
+int ble_qnet_forward_f32(const ble_qnet_f32* net, const float* obs, int64_t obs_row_stride, float* scratch, uint8_t* action,
+                         float* q_values, int64_t n, void* stream) {
+  if (!qnet_ok(net) || !net->weights || !obs || !scratch || !action || n < 0 || obs_row_stride < BLE_OBS_DIM) return BLE_E_INVALID_ARG;
+  if ((reinterpret_cast<uintptr_t>(net->weights) | reinterpret_cast<uintptr_t>(scratch)) & 15) return BLE_E_INVALID_ARG;
+  if (n == 0) return BLE_OK;
+  const int64_t ld = qnet_scratch_ld(net);
+  if ((ld / kQnetCols) * ((n + kQnetRows - 1) / kQnetRows) > 2147483647LL) return BLE_E_INVALID_ARG;
+  float* buf[2] = {scratch, scratch + n * ld};
+  const hipStream_t s = (hipStream_t)stream;
+  for (int l = 0; l < net->num_layers; ++l) {
+    const QnetLayerDims d = qnet_dims(net, l);
+    const int groups = d.mp / kQnetCols;
+    const dim3 grid((unsigned)(groups * ((n + kQnetRows - 1) / kQnetRows)));
+    const float* w = net->weights + d.offset;
+    const bool last = l == net->num_layers - 1;
+    float* y = buf[l & 1];
+    if (l == 0 && last)
+      BLE_LAUNCH((ble_qnet_dense_kernel<true, false>), grid, dim3(kQnetBlock), 0, s, obs, obs_row_stride, d.k, d.kp, w, y, ld, groups, n);
+    else if (l == 0)
+      BLE_LAUNCH((ble_qnet_dense_kernel<true, true>), grid, dim3(kQnetBlock), 0, s, obs, obs_row_stride, d.k, d.kp, w, y, ld, groups, n);
+    else if (last)
+      BLE_LAUNCH((ble_qnet_dense_kernel<false, false>), grid, dim3(kQnetBlock), 0, s, buf[(l - 1) & 1], ld, d.k, d.kp, w, y, ld, groups, n);
+    else
+      BLE_LAUNCH((ble_qnet_dense_kernel<false, true>), grid, dim3(kQnetBlock), 0, s, buf[(l - 1) & 1], ld, d.k, d.kp, w, y, ld, groups, n);
+    const int status = launch_status();        // (the next BLE_LAUNCH drains the error word)
+    if (status != BLE_OK) return status;
+  }
+  BLE_LAUNCH(ble_qnet_head_kernel, dim3(blocks(n, kQnetHeadBlock)), dim3(kQnetHeadBlock), 0, s, buf[(net->num_layers - 1) & 1], ld,
+             net->num_actions, net->num_atoms, action, q_values, n);
   return launch_status();
 }
 

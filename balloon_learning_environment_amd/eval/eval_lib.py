@@ -2,7 +2,7 @@
 
 `eval_agent` is the reference's serial loop over a BalloonEnv, one seed after another.  `eval_agent_vec` flies every seed of a suite
 at once on the device: a batch of environments reset by seed (`ble_reset_seeded_f32`), the transition, the wind noise, the
-observation, the agent (`ble_station_seeker_f32` or any device callable) and the loop's bookkeeping (`ble_eval_accumulate_f32`), with
+observation, the agent (`ble_station_seeker_f32`, `ble_qnet_forward_f32` or any device callable) and the loop's bookkeeping (`ble_eval_accumulate_f32`), with
 no host synchronisation until the batch has flown.  Seed s flies the first episode of
 VecBalloonEnv(1, seed=s, per_env_fields=True, auto_reset=False) -- the same episode in any batch, at any position.
 """
@@ -21,7 +21,6 @@ from balloon_learning_environment_amd import _lib
 from balloon_learning_environment_amd import device as dev
 from balloon_learning_environment_amd import vec_state
 from balloon_learning_environment_amd.agents import agent as base_agent
-from balloon_learning_environment_amd.agents import station_seeker_agent
 from balloon_learning_environment_amd.env.balloon import balloon
 from balloon_learning_environment_amd.eval import suites
 from balloon_learning_environment_amd.utils import units
@@ -184,7 +183,7 @@ class VecEvaluator:
     self._graph = None
 
   def _act(self, obs: torch.Tensor) -> None:
-    if isinstance(self.agent, station_seeker_agent.VecStationSeekerAgent):
+    if hasattr(self.agent, 'act'):       # a device agent (VecStationSeekerAgent, VecQNetworkAgent): it writes the actions in place
       self.agent.act(obs, out=self.action)
     else:
       a = self.agent(obs)
@@ -274,8 +273,9 @@ def eval_agent_vec(agent, suite: suites.EvaluationSuite, *, batch_size: Optional
   EvaluationResult per seed in the suite's order -- what eval_agent returns for a deterministic agent over
   VecBalloonEnv(1, seed=s, per_env_fields=True, auto_reset=False)-shaped environments.
 
-  agent: a VecStationSeekerAgent, or any callable from the [N, 1099] float32 device observation to uint8 [N] device actions that
-    needs no host synchronisation (it is captured in a graph with capture_graph).
+  agent: a device agent with act(obs, out=actions) -- VecStationSeekerAgent, VecQNetworkAgent -- or any callable from the [N, 1099]
+    float32 device observation to uint8 [N] device actions; either needs no host synchronisation (it is captured in a graph with
+    capture_graph).
   wind_field: None (default) -- the generative field, one decoded per seed; otherwise a wind field every seed flies in (a
     GridBasedWindField's current grid, or one (21, 21, 10, 9, 2) grid), not resampled per seed.
   wind_noise: ground truth = forecast + the seed's SimplexWindNoise (default, as the reference); False: forecast == truth.

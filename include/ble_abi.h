@@ -557,6 +557,47 @@ int ble_wind_noise_seeded_f32(const float* x_m, const float* y_m, const float* p
                               const unsigned long long* env_seed, const uint32_t* episode, int mode, float* noise_uv, int64_t n,
                               void* stream);
 
+/*
+ * Q-network agents (additive to ABI 5): the eval-mode forward pass of the reference's QuantileNetwork and MLPNetwork
+ * (agents/networks.py) -- the policy of its QR-DQN (quantile, perciatelli44, finetune_perciatelli), DQN and MLP agents.
+ *
+ * ble_qnet_f32 describes a network: num_layers Dense layers (>= 1), input_dim -> hidden_units -> ... -> num_actions * num_atoms, ReLU
+ * after every layer but the last.  Supported: input_dim == BLE_OBS_DIM, num_actions == 3, num_layers 1 .. 64, hidden_units 1 .. 8192
+ * (ignored when num_layers == 1), num_atoms 1 .. 4096 (1: MLPNetwork, q equals the logits); anything else is BLE_E_INVALID_ARG.
+ * weights is the DEVICE image ble_qnet_pack_f32 made (zero-padded, fragment-ordered; its layout is private to the library).
+ */
+typedef struct ble_qnet_f32 {
+  int32_t num_layers;
+  int32_t input_dim;
+  int32_t hidden_units;
+  int32_t num_actions;
+  int32_t num_atoms;
+  int32_t reserved_;         /* 0 */
+  const float* weights;
+} ble_qnet_f32;
+
+/* Sizes, in floats, of the packed weights and of the scratch a forward pass over n rows needs (either pointer may be NULL). */
+int ble_qnet_workspace_f32(const ble_qnet_f32* net, int64_t n, int64_t* packed_floats, int64_t* scratch_floats);
+
+/* HOST: packs the reference's parameters -- kernel[l] row-major [in][out] float32, bias[l] [out] float32, host pointers -- into
+ * packed (host, ble_qnet_workspace_f32's packed_floats); net->weights is not read.  Copy the image to the device once. */
+int ble_qnet_pack_f32(const ble_qnet_f32* net, const float* const* kernel, const float* const* bias, float* packed);
+
+/*
+ * ble_qnet_forward_f32: the network on n observation rows, then q[a] = the mean of action a's num_atoms logits (summed in ascending
+ * atom order, divided by num_atoms, float32) and action = argmax q with jnp.argmax's rule (the lowest index among equal maxima; the
+ * first NaN if a q is NaN; no error flag).  float32 in, float32 accumulation on v_mfma_f32_32x32x2_f32.  Batch invariant: every
+ * output's reduction order depends on the network's shape only, so a row's q and action are the same bits at any n, at any position
+ * and at any row stride.
+ *   obs             device float32 [n] rows of BLE_OBS_DIM features, obs_row_stride (>= BLE_OBS_DIM) floats apart; nothing past a
+ *                   row's BLE_OBS_DIM features is read
+ *   scratch         device float32, ble_qnet_workspace_f32(net, n)'s scratch_floats, 256-byte aligned (the activations)
+ *   action          device uint8 [n]
+ *   q_values        optional device float32 [n][num_actions]
+ */
+int ble_qnet_forward_f32(const ble_qnet_f32* net, const float* obs, int64_t obs_row_stride, float* scratch, uint8_t* action,
+                         float* q_values, int64_t n, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
