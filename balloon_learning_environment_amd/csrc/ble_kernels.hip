@@ -11,6 +11,7 @@
 #include <stddef.h>
 #include <stdlib.h>
 #include <atomic>
+#include <type_traits>
 
 // Instrumentation hooks of ble_step_kernel: empty in the product build.  A profiling build
 // (profiles/build_variant.sh ... -DBLE_STEP_BLOCK=64 -DBLE_STEP_INSTR_HEADER='"../../profiles/instr/ble_step_instr.h"') takes per-wave clock
@@ -751,7 +752,6 @@ inline StateDev state_dev(const ble_state_f32* st) {
   __builtin_memcpy(&d, st, sizeof d);
   return d;
 }
-inline int env_lanes() { return kBlock; }   // one environment per lane, all 64 lanes (32 was measured: slower)
 // Below BLE_SPLIT_MAX_ENVS environments the one-lane kernel leaves most SIMDs idle (n / 64 waves on 1 024 SIMDs) and the
 // four-wave kernel still fits one wave per SIMD: it is the faster one (bit-identical results).  ble_set_step_form() forces a
 // form (A/B runs and the parity test); BLE_STEP_SPLIT=0 / 1 / 2 / 4 in the process environment is read ONCE, when the
@@ -783,47 +783,24 @@ inline int split_waves(int64_t n) {
   const int f = step_form();
   return f != 0 ? f : (n <= BLE_SPLIT_MAX_ENVS ? 4 : 1);
 }
-inline int launch_split(const ble_state_f32* st, const uint8_t* action, const float* wind_grid, int64_t grid_env_stride,
-                        const float* noise_uv, float* reward, uint8_t* terminal, uint8_t* effective_action, uint32_t* err_flags,
-                        unsigned long long* active_count, int64_t n, int substeps, int n_steps, void* stream, int waves,
-                        const ble_noise_gen* noise = nullptr);
 // hipGetLastError is per-thread and sticky: an error left behind by an unrelated runtime call
 // of the host application (torch probes pointers / peers at start-up) must not be reported as
 // ours, so every launch first drains it, and the launch's own status is kept for
 // ble_last_hip_error().
 thread_local int g_last_hip_error = 0;
-inline int launch_status() {
+template <class... P, class... A>
+int launch_grid(void (*kernel)(P...), dim3 grid, int threads, void* stream, const A&... args) {
+  (void)hipGetLastError();
+  hipLaunchKernelGGL(kernel, grid, dim3(threads), 0, (hipStream_t)stream, args...);
   const hipError_t e = hipGetLastError();
   g_last_hip_error = (int)e;
   return e == hipSuccess ? BLE_OK : BLE_E_LAUNCH;
 }
-#define BLE_LAUNCH(...)            \
-  do {                             \
-    (void)hipGetLastError();       \
-    hipLaunchKernelGGL(__VA_ARGS__); \
-  } while (0)
-inline unsigned blocks(int64_t n, int block) { return (unsigned)((n + block - 1) / block); }
-inline int launch_split(const ble_state_f32* st, const uint8_t* action, const float* wind_grid, int64_t grid_env_stride,
-                        const float* noise_uv, float* reward, uint8_t* terminal, uint8_t* effective_action, uint32_t* err_flags,
-                        unsigned long long* active_count, int64_t n, int substeps, int n_steps, void* stream, int waves,
-                        const ble_noise_gen* noise) {
-  SplitArgs a;
-  a.st = state_dev(st); a.action = action; a.wind_grid = wind_grid; a.grid_env_stride = grid_env_stride; a.noise_uv = noise_uv;
-  a.reward = reward; a.terminal = terminal; a.effective_action = effective_action; a.err_flags = err_flags;
-  a.active_count = active_count; a.n = n; a.substeps = substeps; a.n_steps = n_steps;
-  a.gen = noise ? StepNoise{noise->seed, noise->episode, noise->harmonic_cache, (long long)noise->env_offset} : StepNoise{0ull, nullptr, nullptr, 0ll};
-  const dim3 grid(blocks(n, kSplitLanes));
-#ifdef BLE_WITH_PAIR_FORM
-  if (waves == 2) {
-    if (noise != nullptr) BLE_LAUNCH(ble_step_pair_kernel<true>, grid, dim3(2 * kSplitLanes), 0, (hipStream_t)stream, a);
-    else BLE_LAUNCH(ble_step_pair_kernel<false>, grid, dim3(2 * kSplitLanes), 0, (hipStream_t)stream, a);
-    return launch_status();
-  }
-#endif
-  (void)waves;
-  if (noise != nullptr) BLE_LAUNCH(ble_step_split_kernel<true>, grid, dim3(kSplitWaves * kSplitLanes), 0, (hipStream_t)stream, a);
-  else BLE_LAUNCH(ble_step_split_kernel<false>, grid, dim3(kSplitWaves * kSplitLanes), 0, (hipStream_t)stream, a);
-  return launch_status();
+// `kernel` over n environments (or elements), `per_block` of them per workgroup of `threads` threads; n == 0 launches nothing
+template <class... P, class... A>
+int launch(void (*kernel)(P...), int64_t n, int per_block, int threads, void* stream, const A&... args) {
+  if (n == 0) return BLE_OK;
+  return launch_grid(kernel, dim3((unsigned)((n + per_block - 1) / per_block)), threads, stream, args...);
 }
 inline bool state_ok(const ble_state_f32* st) {
   if (!st) return false;
@@ -897,6 +874,90 @@ constexpr size_t kKernargLimit = 4096;
 static_assert(sizeof(StateDev) + 12 * 8 + sizeof(StepNoise) + sizeof(VehicleFleet) <= kKernargLimit, "ble_step_kernel<VehicleFleet>'s arguments");
 static_assert(sizeof(StateDev) + 10 * 8 + sizeof(GpHistory) + sizeof(VehicleFleet) <= kKernargLimit, "ble_observe_kernel<VehicleFleet>'s arguments");
 
+// The vehicle a call flies, checked and handed to f as the kernels' carrier: VehicleDefault (st->vehicle == NULL: compile-time constants),
+// VehicleRt (st->vehicle) or -- for the fleet entry points, kFleet -- VehicleFleet (`fleet`).  A compile-time choice, so that no kernel
+// is instantiated for a carrier its entry point cannot fly.
+template <bool kFleet, class F>
+int with_vehicle(const ble_state_f32* st, const ble_fleet* fleet, F&& f) {
+  if constexpr (kFleet) {
+    if (!fleet_ok(st, fleet)) return BLE_E_INVALID_ARG;
+    return f(make_fleet(fleet));
+  } else {
+    if (st->vehicle == nullptr) return f(VehicleDefault{});
+    if (!vehicle_ok(st->vehicle)) return BLE_E_INVALID_ARG;
+    return f(make_vehicle_rt(st->vehicle));
+  }
+}
+// The wind-noise generator of a fused rollout (NULL: none), handed to f as the kernels' kNoise switch and their StepNoise argument
+template <class F>
+int with_noise(const ble_noise_gen* g, F&& f) {
+  if (g == nullptr) return f(std::false_type{}, StepNoise{0ull, nullptr, nullptr, 0ll});
+  return f(std::true_type{}, StepNoise{g->seed, g->episode, g->harmonic_cache, (long long)g->env_offset});
+}
+// ble_gp_history_f32 -> the observation kernel's GpHistory; false for a missing array or a carried factor whose slab is too short or
+// misaligned (a slab shorter than the kernel's layout would be overrun, and overlap the next environment's)
+inline bool gp_history(const ble_gp_history_f32* hist, GpHistory* h) {
+  if (!hist || !hist->xyp || !hist->elapsed_s || !hist->err_uv || !hist->count) return false;
+  if (hist->chol != nullptr && (hist->n_chol == nullptr || hist->chol_stride < (int64_t)kCholStride || (hist->chol_stride & 1) != 0))
+    return false;
+  *h = GpHistory{hist->xyp, hist->elapsed_s, hist->err_uv, hist->count, hist->chol, hist->n_chol, hist->chol_stride};
+  return true;
+}
+
+// ble_step_f32 / ble_step_n_f32 and their fleet forms.  The default vehicle flies the form split_waves picks (read once per launch: a
+// concurrent ble_set_step_form cannot split the decision); a run-time vehicle or a fleet flies the one-lane form at every batch size.
+// The one-lane kernel gets kBlock (64) environments per wave.
+template <bool kFleet>
+int launch_step(const ble_state_f32* st, const ble_fleet* fleet, const uint8_t* action, const float* wind_grid, int64_t grid_env_stride,
+                const ble_noise_gen* noise, const float* noise_uv, float* reward, uint8_t* terminal, uint8_t* effective_action,
+                uint32_t* err_flags, unsigned long long* active_count, int64_t n, int substeps, int n_steps, void* stream) {
+  if (!state_ok(st) || !action || !wind_grid || !reward || !terminal || n < 0 || substeps < 1 || substeps > BLE_MAX_SUBSTEPS || n_steps < 0 ||
+      grid_env_stride < 0 || (noise != nullptr && noise->env_offset < 0))      // (a negative offset would key other streams than the reset did)
+    return BLE_E_INVALID_ARG;
+  return with_vehicle<kFleet>(st, fleet, [&](auto veh) {
+    if (n == 0 || n_steps == 0) return BLE_OK;
+    return with_noise(noise, [&](auto noise_on, StepNoise gen) {
+      constexpr bool kNoise = decltype(noise_on)::value;
+      if constexpr (std::is_same_v<decltype(veh), VehicleDefault>) {
+        const int waves = split_waves(n);
+        if (waves != 1) {
+          const SplitArgs a{state_dev(st), action, wind_grid, grid_env_stride, noise_uv, reward, terminal, effective_action, err_flags,
+                            active_count, n, substeps, n_steps, gen};
+#ifdef BLE_WITH_PAIR_FORM
+          if (waves == 2) return launch(ble_step_pair_kernel<kNoise>, n, kSplitLanes, 2 * kSplitLanes, stream, a);
+#endif
+          return launch(ble_step_split_kernel<kNoise>, n, kSplitLanes, kSplitWaves * kSplitLanes, stream, a);
+        }
+      }
+      return launch(ble_step_kernel<kNoise, decltype(veh)>, n, kBlock * (kStepBlock / 64), kStepBlock, stream, state_dev(st), action,
+                    wind_grid, grid_env_stride, noise_uv, reward, terminal, effective_action, err_flags, active_count, n, substeps, kBlock,
+                    n_steps, gen, veh);
+    });
+  });
+}
+// ble_reset_at_f32 / ble_reset_seeded_f32 / ble_reset_fleet_at_f32: S is the seed (ScalarSeed or EnvSeed)
+template <bool kFleet, class S>
+int launch_reset(const ble_state_f32* st, const ble_fleet* fleet, const uint8_t* mask, S seed, uint32_t* episode, int sample,
+                 uint32_t* err_flags, int64_t env_offset, int64_t n, void* stream) {
+  if (!state_ok(st) || n < 0 || env_offset < 0) return BLE_E_INVALID_ARG;
+  return with_vehicle<kFleet>(st, fleet, [&](auto veh) {
+    return launch(ble_reset_kernel<decltype(veh), S>, n, kBlock, kBlock, stream, state_dev(st), mask, seed, episode, sample, err_flags, n,
+                  env_offset, veh);
+  });
+}
+// ble_observe_f32 / _forecast / _live / _forecast_fleet: one workgroup per environment
+template <bool kFleet, bool kLiveOnly>
+int launch_observe(const ble_state_f32* st, const ble_fleet* fleet, const float* wind_grid, int64_t grid_env_stride,
+                   const float* forecast_levels, const float* noise_uv, const uint8_t* reset_mask, const ble_gp_history_f32* hist, int append,
+                   float* obs, uint32_t* err_flags, int64_t n, void* stream) {
+  GpHistory h;
+  if (!state_ok(st) || !wind_grid || !gp_history(hist, &h) || !obs || n < 0 || grid_env_stride < 0) return BLE_E_INVALID_ARG;
+  return with_vehicle<kFleet>(st, fleet, [&](auto veh) {
+    return launch(ble_observe_kernel<decltype(veh), kLiveOnly>, n, 1, kObsBlock, stream, state_dev(st), wind_grid, grid_env_stride, noise_uv,
+                  reset_mask, h, append, obs, err_flags, n, veh, forecast_levels);
+  });
+}
+
 }  // namespace
 
 // Q-network agents: the descriptor checks and sizes of ble_qnet_*_f32
@@ -951,75 +1012,22 @@ int ble_device_count(void) {
 int ble_step_f32(const ble_state_f32* st, const uint8_t* action, const float* wind_grid, int64_t grid_env_stride,
                  const float* noise_uv, float* reward, uint8_t* terminal, uint8_t* effective_action,
                  uint32_t* err_flags, unsigned long long* active_count, int64_t n, int substeps, void* stream) {
-  if (!state_ok(st) || !action || !wind_grid || !reward || !terminal || n < 0 || substeps < 1 || substeps > BLE_MAX_SUBSTEPS ||
-      grid_env_stride < 0)
-    return BLE_E_INVALID_ARG;
-  if (st->vehicle != nullptr && !vehicle_ok(st->vehicle)) return BLE_E_INVALID_ARG;
-  if (n == 0) return BLE_OK;
-  const int lanes = env_lanes();
-  if (st->vehicle != nullptr) {              // a run-time vehicle (ABI 5): the one-lane form's second instantiation, whatever the batch size
-    BLE_LAUNCH((ble_step_kernel<false, VehicleRt>), dim3(blocks(n, lanes * (kStepBlock / 64))), dim3(kStepBlock), 0, (hipStream_t)stream, state_dev(st), action,
-               wind_grid, grid_env_stride, noise_uv, reward, terminal, effective_action, err_flags,
-               active_count, n, substeps, lanes, 1, StepNoise{0ull, nullptr, nullptr, 0ll}, make_vehicle_rt(st->vehicle));
-    return launch_status();
-  }
-  const int waves = split_waves(n);          // (read once per launch: a concurrent ble_set_step_form cannot split the decision)
-  if (waves != 1)
-    return launch_split(st, action, wind_grid, grid_env_stride, noise_uv, reward, terminal, effective_action, err_flags, active_count, n,
-                        substeps, 1, stream, waves);
-  BLE_LAUNCH(ble_step_kernel<false>, dim3(blocks(n, lanes * (kStepBlock / 64))), dim3(kStepBlock), 0, (hipStream_t)stream, state_dev(st), action,
-                     wind_grid, grid_env_stride, noise_uv, reward, terminal, effective_action, err_flags,
-                     active_count, n, substeps, lanes, 1, StepNoise{0ull, nullptr, nullptr, 0ll}, VehicleDefault{});
-  return launch_status();
+  return launch_step<false>(st, nullptr, action, wind_grid, grid_env_stride, nullptr, noise_uv, reward, terminal, effective_action, err_flags,
+                            active_count, n, substeps, 1, stream);
 }
 
 int ble_step_n_f32(const ble_state_f32* st, const uint8_t* action, const float* wind_grid, int64_t grid_env_stride,
                    const ble_noise_gen* noise, float* reward, uint8_t* terminal, uint32_t* err_flags,
                    unsigned long long* active_count, int64_t n, int substeps, int n_steps, void* stream) {
-  if (!state_ok(st) || !action || !wind_grid || !reward || !terminal || n < 0 || substeps < 1 || substeps > BLE_MAX_SUBSTEPS || n_steps < 0 ||
-      grid_env_stride < 0 || (noise != nullptr && noise->env_offset < 0))      // (a negative offset would key other streams than the reset did)
-    return BLE_E_INVALID_ARG;
-  if (st->vehicle != nullptr && !vehicle_ok(st->vehicle)) return BLE_E_INVALID_ARG;
-  if (n == 0) return BLE_OK;
-  if (n_steps == 0) return BLE_OK;
-  const int lanes = env_lanes();
-  if (st->vehicle != nullptr) {
-    const VehicleRt veh = make_vehicle_rt(st->vehicle);
-    if (noise != nullptr)
-      BLE_LAUNCH((ble_step_kernel<true, VehicleRt>), dim3(blocks(n, lanes * (kStepBlock / 64))), dim3(kStepBlock), 0, (hipStream_t)stream, state_dev(st), action,
-                 wind_grid, grid_env_stride, (const float*)nullptr, reward, terminal, (uint8_t*)nullptr, err_flags,
-                 active_count, n, substeps, lanes, n_steps, StepNoise{noise->seed, noise->episode, noise->harmonic_cache, (long long)noise->env_offset}, veh);
-    else
-      BLE_LAUNCH((ble_step_kernel<false, VehicleRt>), dim3(blocks(n, lanes * (kStepBlock / 64))), dim3(kStepBlock), 0, (hipStream_t)stream, state_dev(st), action,
-                 wind_grid, grid_env_stride, (const float*)nullptr, reward, terminal, (uint8_t*)nullptr, err_flags,
-                 active_count, n, substeps, lanes, n_steps, StepNoise{0ull, nullptr, nullptr, 0ll}, veh);
-    return launch_status();
-  }
-  const int waves = split_waves(n);
-  if (waves != 1)          // (with or without the in-kernel noise generator)
-    return launch_split(st, action, wind_grid, grid_env_stride, nullptr, reward, terminal, nullptr, err_flags, active_count, n, substeps,
-                        n_steps, stream, waves, noise);
-  if (noise != nullptr) {
-    BLE_LAUNCH(ble_step_kernel<true>, dim3(blocks(n, lanes * (kStepBlock / 64))), dim3(kStepBlock), 0, (hipStream_t)stream, state_dev(st), action,
-               wind_grid, grid_env_stride, (const float*)nullptr, reward, terminal, (uint8_t*)nullptr, err_flags,
-               active_count, n, substeps, lanes, n_steps, StepNoise{noise->seed, noise->episode, noise->harmonic_cache, (long long)noise->env_offset},
-               VehicleDefault{});
-  } else {
-    BLE_LAUNCH(ble_step_kernel<false>, dim3(blocks(n, lanes * (kStepBlock / 64))), dim3(kStepBlock), 0, (hipStream_t)stream, state_dev(st), action,
-               wind_grid, grid_env_stride, (const float*)nullptr, reward, terminal, (uint8_t*)nullptr, err_flags,
-               active_count, n, substeps, lanes, n_steps, StepNoise{0ull, nullptr, nullptr, 0ll}, VehicleDefault{});
-  }
-  return launch_status();
+  return launch_step<false>(st, nullptr, action, wind_grid, grid_env_stride, noise, nullptr, reward, terminal, nullptr, err_flags, active_count,
+                            n, substeps, n_steps, stream);
 }
 
 int ble_forecast_f32(const float* wind_grid, int64_t grid_env_stride, const float* x_m, const float* y_m,
                      const float* pressure, const int32_t* elapsed_s, float* u, float* v, int64_t n, void* stream) {
   if (!wind_grid || !x_m || !y_m || !pressure || !elapsed_s || !u || !v || n < 0 || grid_env_stride < 0)
     return BLE_E_INVALID_ARG;
-  if (n == 0) return BLE_OK;
-  BLE_LAUNCH(ble_forecast_kernel, dim3(blocks(n, 256)), dim3(256), 0, (hipStream_t)stream, wind_grid,
-                     grid_env_stride, x_m, y_m, pressure, elapsed_s, u, v, n);
-  return launch_status();
+  return launch(ble_forecast_kernel, n, 256, 256, stream, wind_grid, grid_env_stride, x_m, y_m, pressure, elapsed_s, u, v, n);
 }
 
 int ble_forecast_column_f32(const float* wind_grid, int64_t grid_env_stride, const float* x_m, const float* y_m,
@@ -1028,51 +1036,21 @@ int ble_forecast_column_f32(const float* wind_grid, int64_t grid_env_stride, con
   if (!wind_grid || !x_m || !y_m || !elapsed_s || !levels_pa || !out_uv || n < 0 || n_levels < 1 ||
       grid_env_stride < 0)
     return BLE_E_INVALID_ARG;
-  if (n == 0) return BLE_OK;
-  BLE_LAUNCH(ble_forecast_column_kernel, dim3((unsigned)n), dim3(kBlock), 0, (hipStream_t)stream, wind_grid,
-                     grid_env_stride, x_m, y_m, elapsed_s, levels_pa, n_levels, out_uv, n);
-  return launch_status();
+  return launch(ble_forecast_column_kernel, n, 1, kBlock, stream, wind_grid, grid_env_stride, x_m, y_m, elapsed_s, levels_pa, n_levels, out_uv, n);
 }
-
-extern "C++" {
-namespace {
-template <bool kLiveOnly>
-int launch_observe(const ble_state_f32* st, const float* wind_grid, int64_t grid_env_stride, const float* forecast_levels,
-                   const float* noise_uv, const uint8_t* reset_mask, const ble_gp_history_f32* hist, int append, float* obs,
-                   uint32_t* err_flags, int64_t n, void* stream) {
-  if (!state_ok(st) || !wind_grid || !hist || !hist->xyp || !hist->elapsed_s || !hist->err_uv || !hist->count || !obs ||
-      n < 0 || grid_env_stride < 0)
-    return BLE_E_INVALID_ARG;
-  if (n == 0) return BLE_OK;
-  GpHistory h;
-  h.xyp = hist->xyp; h.elapsed_s = hist->elapsed_s; h.err_uv = hist->err_uv; h.count = hist->count;
-  h.chol = hist->chol; h.n_chol = hist->n_chol; h.chol_stride = hist->chol_stride;
-  // a slab shorter than the kernel's layout would be overrun (and overlap the next environment's)
-  if (h.chol != nullptr && (h.n_chol == nullptr || h.chol_stride < (int64_t)kCholStride || (h.chol_stride & 1) != 0))
-    return BLE_E_INVALID_ARG;
-  if (st->vehicle != nullptr) {
-    if (!vehicle_ok(st->vehicle)) return BLE_E_INVALID_ARG;
-    BLE_LAUNCH((ble_observe_kernel<VehicleRt, kLiveOnly>), dim3((unsigned)n), dim3(kObsBlock), 0, (hipStream_t)stream, state_dev(st),
-               wind_grid, grid_env_stride, noise_uv, reset_mask, h, append, obs, err_flags, n, make_vehicle_rt(st->vehicle), forecast_levels);
-  } else {
-    BLE_LAUNCH((ble_observe_kernel<VehicleDefault, kLiveOnly>), dim3((unsigned)n), dim3(kObsBlock), 0, (hipStream_t)stream, state_dev(st),
-               wind_grid, grid_env_stride, noise_uv, reset_mask, h, append, obs, err_flags, n, VehicleDefault{}, forecast_levels);
-  }
-  return launch_status();
-}
-}  // namespace
-}  // extern "C++"
 
 int ble_observe_forecast_f32(const ble_state_f32* st, const float* wind_grid, int64_t grid_env_stride, const float* forecast_levels,
                              const float* noise_uv, const uint8_t* reset_mask, const ble_gp_history_f32* hist, int append, float* obs,
                              uint32_t* err_flags, int64_t n, void* stream) {
-  return launch_observe<false>(st, wind_grid, grid_env_stride, forecast_levels, noise_uv, reset_mask, hist, append, obs, err_flags, n, stream);
+  return launch_observe<false, false>(st, nullptr, wind_grid, grid_env_stride, forecast_levels, noise_uv, reset_mask, hist, append, obs,
+                                      err_flags, n, stream);
 }
 
 int ble_observe_live_f32(const ble_state_f32* st, const float* wind_grid, int64_t grid_env_stride, const float* noise_uv,
                          const uint8_t* reset_mask, const ble_gp_history_f32* hist, int append, float* obs, uint32_t* err_flags, int64_t n,
                          void* stream) {
-  return launch_observe<true>(st, wind_grid, grid_env_stride, nullptr, noise_uv, reset_mask, hist, append, obs, err_flags, n, stream);
+  return launch_observe<false, true>(st, nullptr, wind_grid, grid_env_stride, nullptr, noise_uv, reset_mask, hist, append, obs, err_flags, n,
+                                     stream);
 }
 
 int ble_observe_f32(const ble_state_f32* st, const float* wind_grid, int64_t grid_env_stride, const float* noise_uv,
@@ -1083,28 +1061,22 @@ int ble_observe_f32(const ble_state_f32* st, const float* wind_grid, int64_t gri
 
 int ble_decode_flow_fields_f32(const float* flow, float* wind_grid, int64_t n, void* stream) {
   if (!flow || !wind_grid || n < 0 || n > 2147483647LL) return BLE_E_INVALID_ARG;
-  if (n == 0) return BLE_OK;
-  BLE_LAUNCH(ble_decode_flow_kernel, dim3((unsigned)n), dim3(kDecodeThreads), 0, (hipStream_t)stream, flow, wind_grid, n);
-  return launch_status();
+  return launch(ble_decode_flow_kernel, n, 1, kDecodeThreads, stream, flow, wind_grid, n);
 }
 
 int ble_wind_noise_at_f32(const float* x_m, const float* y_m, const float* pressure, const int32_t* elapsed_s,
                           unsigned long long seed, const uint32_t* episode, int mode, uint32_t* harmonic_cache,
                           float* noise_uv, int64_t env_offset, int64_t n, void* stream) {
   if (!x_m || !y_m || !pressure || !elapsed_s || !noise_uv || n < 0 || env_offset < 0 || mode < 0 || mode > 1) return BLE_E_INVALID_ARG;
-  if (n == 0) return BLE_OK;
-  BLE_LAUNCH(ble_wind_noise_kernel<ScalarSeed>, dim3(blocks(n, 256)), dim3(256), 0, (hipStream_t)stream, x_m, y_m, pressure,
-             elapsed_s, ScalarSeed{seed}, episode, mode, harmonic_cache, noise_uv, n, env_offset);
-  return launch_status();
+  return launch(ble_wind_noise_kernel<ScalarSeed>, n, 256, 256, stream, x_m, y_m, pressure, elapsed_s, ScalarSeed{seed}, episode, mode,
+                harmonic_cache, noise_uv, n, env_offset);
 }
 
 int ble_wind_noise_seeded_f32(const float* x_m, const float* y_m, const float* pressure, const int32_t* elapsed_s,
                               const unsigned long long* env_seed, const uint32_t* episode, int mode, float* noise_uv, int64_t n, void* stream) {
   if (!x_m || !y_m || !pressure || !elapsed_s || !env_seed || !noise_uv || n < 0 || mode < 0 || mode > 1) return BLE_E_INVALID_ARG;
-  if (n == 0) return BLE_OK;
-  BLE_LAUNCH(ble_wind_noise_kernel<EnvSeed>, dim3(blocks(n, 256)), dim3(256), 0, (hipStream_t)stream, x_m, y_m, pressure,
-             elapsed_s, EnvSeed{env_seed}, episode, mode, (uint32_t*)nullptr, noise_uv, n, (int64_t)0);
-  return launch_status();
+  return launch(ble_wind_noise_kernel<EnvSeed>, n, 256, 256, stream, x_m, y_m, pressure, elapsed_s, EnvSeed{env_seed}, episode, mode,
+                nullptr, noise_uv, n, 0);
 }
 
 int ble_wind_noise_f32(const float* x_m, const float* y_m, const float* pressure, const int32_t* elapsed_s,
@@ -1115,63 +1087,44 @@ int ble_wind_noise_f32(const float* x_m, const float* y_m, const float* pressure
 
 int ble_state_rows_f64(const ble_state_f32* st, int64_t first, int64_t count, double* out, int64_t n, void* stream) {
   if (!state_ok(st) || !out || first < 0 || count < 0 || n < 0 || first + count > n) return BLE_E_INVALID_ARG;
-  if (count == 0) return BLE_OK;
-  BLE_LAUNCH(ble_state_rows_kernel, dim3(blocks(count, 64)), dim3(64), 0, (hipStream_t)stream, state_dev(st), first, count, out);
-  return launch_status();
+  return launch(ble_state_rows_kernel, count, 64, 64, stream, state_dev(st), first, count, out);
 }
 
 int ble_power_table_f32(const float* pressure_ratio, const float* state_of_charge, float* watts, uint32_t* err_flags,
                         int64_t n, void* stream) {
   if (!pressure_ratio || !state_of_charge || !watts || n < 0) return BLE_E_INVALID_ARG;
-  if (n == 0) return BLE_OK;
-  BLE_LAUNCH(ble_power_table_kernel, dim3(blocks(n, 256)), dim3(256), 0, (hipStream_t)stream, pressure_ratio,
-                     state_of_charge, watts, err_flags, n);
-  return launch_status();
+  return launch(ble_power_table_kernel, n, 256, 256, stream, pressure_ratio, state_of_charge, watts, err_flags, n);
 }
 
 int ble_probe_atmosphere_f32(const float* alpha, const float* pressure, float* height, float* temperature,
                              uint32_t* err_flags, int64_t n, void* stream) {
   if (!alpha || !pressure || !height || !temperature || n < 0) return BLE_E_INVALID_ARG;
-  if (n == 0) return BLE_OK;
-  BLE_LAUNCH(probe_atmosphere_kernel, dim3(blocks(n, 256)), dim3(256), 0, (hipStream_t)stream, alpha, pressure,
-                     height, temperature, err_flags, n);
-  return launch_status();
+  return launch(probe_atmosphere_kernel, n, 256, 256, stream, alpha, pressure, height, temperature, err_flags, n);
 }
 
 int ble_probe_atmosphere_at_height_f64(const float* alpha, const double* height_m, double* pressure, double* temperature, uint32_t* err_flags,
                                        int64_t n, void* stream) {
   if (!alpha || !height_m || !pressure || !temperature || n < 0) return BLE_E_INVALID_ARG;
-  if (n == 0) return BLE_OK;
-  BLE_LAUNCH(probe_at_height_kernel, dim3(blocks(n, 256)), dim3(256), 0, (hipStream_t)stream, alpha, height_m, pressure, temperature, err_flags, n);
-  return launch_status();
+  return launch(probe_at_height_kernel, n, 256, 256, stream, alpha, height_m, pressure, temperature, err_flags, n);
 }
 
 int ble_probe_solar_f32(const float* center_lat_deg, const float* center_lng_deg, const float* x_m, const float* y_m,
                         const int64_t* unix_s, float* el_deg, float* flux, int64_t n, void* stream) {
   if (!center_lat_deg || !center_lng_deg || !x_m || !y_m || !unix_s || !el_deg || !flux || n < 0)
     return BLE_E_INVALID_ARG;
-  if (n == 0) return BLE_OK;
-  BLE_LAUNCH(probe_solar_kernel, dim3(blocks(n, 256)), dim3(256), 0, (hipStream_t)stream, center_lat_deg,
-                     center_lng_deg, x_m, y_m, unix_s, el_deg, flux, n);
-  return launch_status();
+  return launch(probe_solar_kernel, n, 256, 256, stream, center_lat_deg, center_lng_deg, x_m, y_m, unix_s, el_deg, flux, n);
 }
 
 int ble_probe_latlng_f64(const float* center_lat_deg, const float* center_lng_deg, const float* x_m, const float* y_m,
                          double* lat_deg, double* lng_deg, int64_t n, void* stream) {
   if (!center_lat_deg || !center_lng_deg || !x_m || !y_m || !lat_deg || !lng_deg || n < 0) return BLE_E_INVALID_ARG;
-  if (n == 0) return BLE_OK;
-  BLE_LAUNCH(probe_latlng_kernel, dim3(blocks(n, 256)), dim3(256), 0, (hipStream_t)stream, center_lat_deg, center_lng_deg, x_m,
-             y_m, lat_deg, lng_deg, n);
-  return launch_status();
+  return launch(probe_latlng_kernel, n, 256, 256, stream, center_lat_deg, center_lng_deg, x_m, y_m, lat_deg, lng_deg, n);
 }
 
 int ble_probe_solar_power_f32(const float* el_deg, const float* pressure, float* attenuation, float* power_w,
                               int64_t n, void* stream) {
   if (!el_deg || !pressure || !attenuation || !power_w || n < 0) return BLE_E_INVALID_ARG;
-  if (n == 0) return BLE_OK;
-  BLE_LAUNCH(probe_solar_power_kernel, dim3(blocks(n, 256)), dim3(256), 0, (hipStream_t)stream, el_deg,
-                     pressure, attenuation, power_w, n);
-  return launch_status();
+  return launch(probe_solar_power_kernel, n, 256, 256, stream, el_deg, pressure, attenuation, power_w, n);
 }
 
 int ble_probe_thermal_vehicle_f32(const ble_vehicle* vehicle, const float* volume, const float* t_int, const float* t_amb, const float* pressure,
@@ -1179,11 +1132,9 @@ int ble_probe_thermal_vehicle_f32(const ble_vehicle* vehicle, const float* volum
                                   uint32_t* err_flags, int64_t n, void* stream) {
   if (!volume || !t_int || !t_amb || !pressure || !el_deg || !flux || !upwelling_ir || !dtdt || n < 0 || (vehicle != nullptr && !vehicle_ok(vehicle)))
     return BLE_E_INVALID_ARG;
-  if (n == 0) return BLE_OK;
-  BLE_LAUNCH(probe_thermal_kernel, dim3(blocks(n, 256)), dim3(256), 0, (hipStream_t)stream, volume, t_int,
-                     t_amb, pressure, el_deg, flux, upwelling_ir, dtdt, err_flags, n,
-                     vehicle != nullptr ? make_vehicle_rt(vehicle).thermal_scale : VehicleDefault::thermal_scale);
-  return launch_status();
+  const double thermal_scale = vehicle != nullptr ? make_vehicle_rt(vehicle).thermal_scale : VehicleDefault::thermal_scale;
+  return launch(probe_thermal_kernel, n, 256, 256, stream, volume, t_int, t_amb, pressure, el_deg, flux, upwelling_ir, dtdt, err_flags, n,
+                thermal_scale);
 }
 int ble_probe_thermal_f32(const float* volume, const float* t_int, const float* t_amb, const float* pressure,
                           const float* el_deg, const float* flux, const float* upwelling_ir, float* dtdt,
@@ -1194,12 +1145,9 @@ int ble_probe_thermal_f32(const float* volume, const float* t_int, const float* 
 int ble_probe_sp_volume_vehicle_f32(const ble_vehicle* vehicle, const float* mols_air, const float* t_int, const float* pressure, float* volume,
                                     float* superpressure, int64_t n, void* stream) {
   if (!mols_air || !t_int || !pressure || !volume || !superpressure || n < 0 || (vehicle != nullptr && !vehicle_ok(vehicle))) return BLE_E_INVALID_ARG;
-  if (n == 0) return BLE_OK;
   const double lift = vehicle ? vehicle->mols_lift_gas : VehicleDefault::lift, v0 = vehicle ? vehicle->envelope_volume_base : VehicleDefault::v0;
   const double dvdp = vehicle ? vehicle->envelope_volume_dv_pressure : VehicleDefault::dvdp;
-  BLE_LAUNCH(probe_sp_volume_kernel, dim3(blocks(n, 256)), dim3(256), 0, (hipStream_t)stream, mols_air, t_int,
-                     pressure, volume, superpressure, n, lift, v0, dvdp);
-  return launch_status();
+  return launch(probe_sp_volume_kernel, n, 256, 256, stream, mols_air, t_int, pressure, volume, superpressure, n, lift, v0, dvdp);
 }
 int ble_probe_sp_volume_f32(const float* mols_air, const float* t_int, const float* pressure, float* volume,
                             float* superpressure, int64_t n, void* stream) {
@@ -1208,39 +1156,19 @@ int ble_probe_sp_volume_f32(const float* mols_air, const float* t_int, const flo
 
 int ble_reset_at_f32(const ble_state_f32* st, const uint8_t* mask, unsigned long long seed, uint32_t* episode,
                      int sample, uint32_t* err_flags, int64_t env_offset, int64_t n, void* stream) {
-  if (!state_ok(st) || n < 0 || env_offset < 0) return BLE_E_INVALID_ARG;
-  if (st->vehicle != nullptr && !vehicle_ok(st->vehicle)) return BLE_E_INVALID_ARG;
-  if (n == 0) return BLE_OK;
-  if (st->vehicle != nullptr)
-    BLE_LAUNCH((ble_reset_kernel<VehicleRt, ScalarSeed>), dim3(blocks(n, kBlock)), dim3(kBlock), 0, (hipStream_t)stream, state_dev(st), mask,
-               ScalarSeed{seed}, episode, sample, err_flags, n, env_offset, make_vehicle_rt(st->vehicle));
-  else
-    BLE_LAUNCH((ble_reset_kernel<VehicleDefault, ScalarSeed>), dim3(blocks(n, kBlock)), dim3(kBlock), 0, (hipStream_t)stream, state_dev(st), mask,
-               ScalarSeed{seed}, episode, sample, err_flags, n, env_offset, VehicleDefault{});
-  return launch_status();
+  return launch_reset<false>(st, nullptr, mask, ScalarSeed{seed}, episode, sample, err_flags, env_offset, n, stream);
 }
 
 int ble_reset_seeded_f32(const ble_state_f32* st, const uint8_t* mask, const unsigned long long* env_seed, uint32_t* episode,
                          int sample, uint32_t* err_flags, int64_t n, void* stream) {
-  if (!state_ok(st) || !env_seed || n < 0) return BLE_E_INVALID_ARG;
-  if (st->vehicle != nullptr && !vehicle_ok(st->vehicle)) return BLE_E_INVALID_ARG;
-  if (n == 0) return BLE_OK;
-  if (st->vehicle != nullptr)
-    BLE_LAUNCH((ble_reset_kernel<VehicleRt, EnvSeed>), dim3(blocks(n, kBlock)), dim3(kBlock), 0, (hipStream_t)stream, state_dev(st), mask,
-               EnvSeed{env_seed}, episode, sample, err_flags, n, (int64_t)0, make_vehicle_rt(st->vehicle));
-  else
-    BLE_LAUNCH((ble_reset_kernel<VehicleDefault, EnvSeed>), dim3(blocks(n, kBlock)), dim3(kBlock), 0, (hipStream_t)stream, state_dev(st), mask,
-               EnvSeed{env_seed}, episode, sample, err_flags, n, (int64_t)0, VehicleDefault{});
-  return launch_status();
+  if (!env_seed) return BLE_E_INVALID_ARG;
+  return launch_reset<false>(st, nullptr, mask, EnvSeed{env_seed}, episode, sample, err_flags, 0, n, stream);
 }
 
 int ble_station_seeker_f32(const float* obs, int64_t obs_row_stride, uint8_t* action, int32_t* level, double* scores, uint32_t* err_flags,
                            int64_t n, void* stream) {
   if (!obs || !action || n < 0 || obs_row_stride < BLE_OBS_DIM || n > 4LL * 2147483647LL) return BLE_E_INVALID_ARG;
-  if (n == 0) return BLE_OK;
-  BLE_LAUNCH(ble_station_seeker_kernel, dim3(blocks(n, kSeekerBlock / 64)), dim3(kSeekerBlock), 0, (hipStream_t)stream, obs, obs_row_stride,
-             action, level, scores, err_flags, n);
-  return launch_status();
+  return launch(ble_station_seeker_kernel, n, kSeekerBlock / 64, kSeekerBlock, stream, obs, obs_row_stride, action, level, scores, err_flags, n);
 }
 
 // ---------------------------------------------------------------------------------------------------------------- Q-network agents
@@ -1266,32 +1194,24 @@ int ble_qnet_forward_f32(const ble_qnet_f32* net, const float* obs, int64_t obs_
                          float* q_values, int64_t n, void* stream) {
   if (!qnet_ok(net) || !net->weights || !obs || !scratch || !action || n < 0 || obs_row_stride < BLE_OBS_DIM) return BLE_E_INVALID_ARG;
   if ((reinterpret_cast<uintptr_t>(net->weights) | reinterpret_cast<uintptr_t>(scratch)) & 15) return BLE_E_INVALID_ARG;
-  if (n == 0) return BLE_OK;
   const int64_t ld = qnet_scratch_ld(net);
   if ((ld / kQnetCols) * ((n + kQnetRows - 1) / kQnetRows) > 2147483647LL) return BLE_E_INVALID_ARG;
+  if (n == 0) return BLE_OK;
   float* buf[2] = {scratch, scratch + n * ld};
-  const hipStream_t s = (hipStream_t)stream;
   for (int l = 0; l < net->num_layers; ++l) {
     const QnetLayerDims d = qnet_dims(net, l);
     const int groups = d.mp / kQnetCols;
     const dim3 grid((unsigned)(groups * ((n + kQnetRows - 1) / kQnetRows)));
-    const float* w = net->weights + d.offset;
-    const bool last = l == net->num_layers - 1;
-    float* y = buf[l & 1];
-    if (l == 0 && last)
-      BLE_LAUNCH((ble_qnet_dense_kernel<true, false>), grid, dim3(kQnetBlock), 0, s, obs, obs_row_stride, d.k, d.kp, w, y, ld, groups, n);
-    else if (l == 0)
-      BLE_LAUNCH((ble_qnet_dense_kernel<true, true>), grid, dim3(kQnetBlock), 0, s, obs, obs_row_stride, d.k, d.kp, w, y, ld, groups, n);
-    else if (last)
-      BLE_LAUNCH((ble_qnet_dense_kernel<false, false>), grid, dim3(kQnetBlock), 0, s, buf[(l - 1) & 1], ld, d.k, d.kp, w, y, ld, groups, n);
-    else
-      BLE_LAUNCH((ble_qnet_dense_kernel<false, true>), grid, dim3(kQnetBlock), 0, s, buf[(l - 1) & 1], ld, d.k, d.kp, w, y, ld, groups, n);
-    const int status = launch_status();        // (the next BLE_LAUNCH drains the error word)
+    // the first layer reads the observation rows, the others the previous layer's activations; ReLU after every layer but the last
+    const bool first = l == 0, last = l == net->num_layers - 1;
+    const auto dense = first ? (last ? ble_qnet_dense_kernel<true, false> : ble_qnet_dense_kernel<true, true>)
+                             : (last ? ble_qnet_dense_kernel<false, false> : ble_qnet_dense_kernel<false, true>);
+    const int status = launch_grid(dense, grid, kQnetBlock, stream, first ? obs : buf[(l - 1) & 1], first ? obs_row_stride : ld, d.k, d.kp,
+                                   net->weights + d.offset, buf[l & 1], ld, groups, n);
     if (status != BLE_OK) return status;
   }
-  BLE_LAUNCH(ble_qnet_head_kernel, dim3(blocks(n, kQnetHeadBlock)), dim3(kQnetHeadBlock), 0, s, buf[(net->num_layers - 1) & 1], ld,
-             net->num_actions, net->num_atoms, action, q_values, n);
-  return launch_status();
+  return launch(ble_qnet_head_kernel, n, kQnetHeadBlock, kQnetHeadBlock, stream, buf[(net->num_layers - 1) & 1], ld, net->num_actions,
+                net->num_atoms, action, q_values, n);
 }
 
 int ble_eval_accumulate_f32(const ble_state_f32* st, const float* reward, const ble_eval_acc* acc, double radius_m, int step_index,
@@ -1300,11 +1220,9 @@ int ble_eval_accumulate_f32(const ble_state_f32* st, const float* reward, const 
       !acc->end_status || n < 0 || step_index < 0 || max_steps <= step_index)
     return BLE_E_INVALID_ARG;
   if (st->vehicle != nullptr && !vehicle_ok(st->vehicle)) return BLE_E_INVALID_ARG;
-  if (n == 0) return BLE_OK;
-  const double capacity = st->vehicle != nullptr ? st->vehicle->battery_capacity_wh : 3058.56;     // balloon.py:173
-  BLE_LAUNCH(ble_eval_accumulate_kernel, dim3(blocks(n, 256)), dim3(256), 0, (hipStream_t)stream, state_dev(st), reward, *acc, radius_m,
-             step_index, max_steps, flight_path, capacity, n);
-  return launch_status();
+  const double capacity = st->vehicle != nullptr ? st->vehicle->battery_capacity_wh : VehicleDefault::capacity_d;     // balloon.py:173
+  return launch(ble_eval_accumulate_kernel, n, 256, 256, stream, state_dev(st), reward, *acc, radius_m, step_index, max_steps, flight_path,
+                capacity, n);
 }
 
 int ble_reset_f32(const ble_state_f32* st, const uint8_t* mask, unsigned long long seed, uint32_t* episode,
@@ -1314,18 +1232,13 @@ int ble_reset_f32(const ble_state_f32* st, const uint8_t* mask, unsigned long lo
 
 int ble_probe_f64_prims(const double* x, double* y, int op, int64_t n, void* stream) {
   if (!x || !y || n < 0 || op < 0 || op > 8) return BLE_E_INVALID_ARG;
-  if (n == 0) return BLE_OK;
-  BLE_LAUNCH(probe_f64_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, x, y, op, n);
-  return launch_status();
+  return launch(probe_f64_kernel, n, 256, 256, stream, x, y, op, n);
 }
 
 int ble_probe_acs_f32(const float* pressure_ratio, float* power_w, float* efficiency, float* mass_flow, int64_t n,
                       void* stream) {
   if (!pressure_ratio || !power_w || !efficiency || !mass_flow || n < 0) return BLE_E_INVALID_ARG;
-  if (n == 0) return BLE_OK;
-  BLE_LAUNCH(probe_acs_kernel, dim3(blocks(n, 256)), dim3(256), 0, (hipStream_t)stream, pressure_ratio,
-                     power_w, efficiency, mass_flow, n);
-  return launch_status();
+  return launch(probe_acs_kernel, n, 256, 256, stream, pressure_ratio, power_w, efficiency, mass_flow, n);
 }
 
 int ble_probe_safety_f32(int layer, const uint8_t* action, const float* value, const float* alpha, int32_t* clocks,
@@ -1333,71 +1246,35 @@ int ble_probe_safety_f32(int layer, const uint8_t* action, const float* value, c
                          uint32_t* err_flags, int64_t n, void* stream) {
   if (layer < 0 || layer > 2 || !action || !value || !fsm || !effective_action || n < 0) return BLE_E_INVALID_ARG;
   if ((layer == 0 && !alpha) || (layer == 2 && (!clocks || !(capacity_wh > 0.0)))) return BLE_E_INVALID_ARG;
-  if (n == 0) return BLE_OK;
-  BLE_LAUNCH(probe_safety_kernel, dim3(blocks(n, 256)), dim3(256), 0, (hipStream_t)stream, layer, action, value, alpha,
-                     clocks, night_load_w, capacity_wh, fsm, effective_action, err_flags, n);
-  return launch_status();
+  return launch(probe_safety_kernel, n, 256, 256, stream, layer, action, value, alpha, clocks, night_load_w, capacity_wh, fsm, effective_action,
+                err_flags, n);
 }
 
 // ---- fleets (include/ble_abi.h::ble_fleet): the one-lane transition, the reset and the observation with a palette
 int ble_step_fleet_f32(const ble_state_f32* st, const ble_fleet* fleet, const uint8_t* action, const float* wind_grid, int64_t grid_env_stride,
                        const float* noise_uv, float* reward, uint8_t* terminal, uint8_t* effective_action, uint32_t* err_flags,
                        unsigned long long* active_count, int64_t n, int substeps, void* stream) {
-  if (!state_ok(st) || !action || !wind_grid || !reward || !terminal || n < 0 || substeps < 1 || substeps > BLE_MAX_SUBSTEPS ||
-      grid_env_stride < 0 || !fleet_ok(st, fleet))
-    return BLE_E_INVALID_ARG;
-  if (n == 0) return BLE_OK;
-  const int lanes = env_lanes();
-  BLE_LAUNCH((ble_step_kernel<false, VehicleFleet>), dim3(blocks(n, lanes * (kStepBlock / 64))), dim3(kStepBlock), 0, (hipStream_t)stream,
-             state_dev(st), action, wind_grid, grid_env_stride, noise_uv, reward, terminal, effective_action, err_flags, active_count, n, substeps,
-             lanes, 1, StepNoise{0ull, nullptr, nullptr, 0ll}, make_fleet(fleet));
-  return launch_status();
+  return launch_step<true>(st, fleet, action, wind_grid, grid_env_stride, nullptr, noise_uv, reward, terminal, effective_action, err_flags,
+                           active_count, n, substeps, 1, stream);
 }
 
 int ble_step_n_fleet_f32(const ble_state_f32* st, const ble_fleet* fleet, const uint8_t* action, const float* wind_grid, int64_t grid_env_stride,
                          const ble_noise_gen* noise, float* reward, uint8_t* terminal, uint32_t* err_flags, unsigned long long* active_count,
                          int64_t n, int substeps, int n_steps, void* stream) {
-  if (!state_ok(st) || !action || !wind_grid || !reward || !terminal || n < 0 || substeps < 1 || substeps > BLE_MAX_SUBSTEPS || n_steps < 0 ||
-      grid_env_stride < 0 || (noise != nullptr && noise->env_offset < 0) || !fleet_ok(st, fleet))
-    return BLE_E_INVALID_ARG;
-  if (n == 0 || n_steps == 0) return BLE_OK;
-  const int lanes = env_lanes();
-  const VehicleFleet veh = make_fleet(fleet);
-  if (noise != nullptr)
-    BLE_LAUNCH((ble_step_kernel<true, VehicleFleet>), dim3(blocks(n, lanes * (kStepBlock / 64))), dim3(kStepBlock), 0, (hipStream_t)stream,
-               state_dev(st), action, wind_grid, grid_env_stride, (const float*)nullptr, reward, terminal, (uint8_t*)nullptr, err_flags, active_count,
-               n, substeps, lanes, n_steps, StepNoise{noise->seed, noise->episode, noise->harmonic_cache, (long long)noise->env_offset}, veh);
-  else
-    BLE_LAUNCH((ble_step_kernel<false, VehicleFleet>), dim3(blocks(n, lanes * (kStepBlock / 64))), dim3(kStepBlock), 0, (hipStream_t)stream,
-               state_dev(st), action, wind_grid, grid_env_stride, (const float*)nullptr, reward, terminal, (uint8_t*)nullptr, err_flags, active_count,
-               n, substeps, lanes, n_steps, StepNoise{0ull, nullptr, nullptr, 0ll}, veh);
-  return launch_status();
+  return launch_step<true>(st, fleet, action, wind_grid, grid_env_stride, noise, nullptr, reward, terminal, nullptr, err_flags, active_count, n,
+                           substeps, n_steps, stream);
 }
 
 int ble_reset_fleet_at_f32(const ble_state_f32* st, const ble_fleet* fleet, const uint8_t* mask, unsigned long long seed, uint32_t* episode,
                            int sample, uint32_t* err_flags, int64_t env_offset, int64_t n, void* stream) {
-  if (!state_ok(st) || n < 0 || env_offset < 0 || !fleet_ok(st, fleet)) return BLE_E_INVALID_ARG;
-  if (n == 0) return BLE_OK;
-  BLE_LAUNCH((ble_reset_kernel<VehicleFleet, ScalarSeed>), dim3(blocks(n, kBlock)), dim3(kBlock), 0, (hipStream_t)stream, state_dev(st), mask,
-             ScalarSeed{seed}, episode, sample, err_flags, n, env_offset, make_fleet(fleet));
-  return launch_status();
+  return launch_reset<true>(st, fleet, mask, ScalarSeed{seed}, episode, sample, err_flags, env_offset, n, stream);
 }
 
 int ble_observe_forecast_fleet_f32(const ble_state_f32* st, const ble_fleet* fleet, const float* wind_grid, int64_t grid_env_stride,
                                    const float* forecast_levels, const float* noise_uv, const uint8_t* reset_mask, const ble_gp_history_f32* hist,
                                    int append, float* obs, uint32_t* err_flags, int64_t n, void* stream) {
-  if (!state_ok(st) || !wind_grid || !hist || !hist->xyp || !hist->elapsed_s || !hist->err_uv || !hist->count || !obs ||
-      n < 0 || grid_env_stride < 0 || !fleet_ok(st, fleet))
-    return BLE_E_INVALID_ARG;
-  GpHistory h;
-  h.xyp = hist->xyp; h.elapsed_s = hist->elapsed_s; h.err_uv = hist->err_uv; h.count = hist->count;
-  h.chol = hist->chol; h.n_chol = hist->n_chol; h.chol_stride = hist->chol_stride;
-  if (h.chol != nullptr && (h.n_chol == nullptr || h.chol_stride < (int64_t)kCholStride || (h.chol_stride & 1) != 0))
-    return BLE_E_INVALID_ARG;
-  if (n == 0) return BLE_OK;
-  BLE_LAUNCH((ble_observe_kernel<VehicleFleet, false>), dim3((unsigned)n), dim3(kObsBlock), 0, (hipStream_t)stream, state_dev(st), wind_grid,
-             grid_env_stride, noise_uv, reset_mask, h, append, obs, err_flags, n, make_fleet(fleet), forecast_levels);
-  return launch_status();
+  return launch_observe<true, false>(st, fleet, wind_grid, grid_env_stride, forecast_levels, noise_uv, reset_mask, hist, append, obs, err_flags,
+                                     n, stream);
 }
 
 }  // extern "C"

@@ -196,6 +196,17 @@ class VecSimulator:
   def has_fleet(self) -> bool:
     return self.fleet_vehicles is not None
 
+  # the fleet form of each entry point that has one: the same arguments with the ble_fleet after the state
+  _FLEET_FORMS = {'ble_step_f32': 'ble_step_fleet_f32', 'ble_step_n_f32': 'ble_step_n_fleet_f32', 'ble_reset_at_f32': 'ble_reset_fleet_at_f32',
+                  'ble_observe_forecast_f32': 'ble_observe_forecast_fleet_f32'}
+
+  def _entry(self, name: str):
+    """(entry point, its leading struct arguments): `name` with the state, or -- with a fleet -- its fleet form with the state and the
+    simulator's one ble_fleet struct (set_fleet updates it in place)."""
+    if self.has_fleet:
+      return getattr(self.lib, self._FLEET_FORMS[name]), (ctypes.byref(self._struct), ctypes.byref(self._fleet))
+    return getattr(self.lib, name), (ctypes.byref(self._struct),)
+
   def vehicle_of(self, i: int) -> Dict[str, float]:
     """The vehicle environment i flies (override dict): its fleet entry, or the batch's vehicle."""
     if not self.has_fleet:
@@ -212,21 +223,10 @@ class VecSimulator:
     draws (if `sample`), Newton cold start, sunrise/sunset search, fresh clocks and FSMs."""
     if mask is not None:
       assert mask.dtype == torch.uint8 and mask.is_contiguous() and mask.numel() == self.n
-    if self.has_fleet:
-      code = self.lib.ble_reset_fleet_at_f32(ctypes.byref(self._struct), ctypes.byref(self._fleet), dev.ptr(mask), int(seed) & (2 ** 64 - 1),
-                                             self.episode.data_ptr(), 1 if sample else 0, self.err_flags.data_ptr(), self.env_offset, self.n,
-                                             dev.stream_ptr(self.device))
-      _lib.check(code, 'ble_reset_fleet_at_f32')
-    else:
-      code = self.lib.ble_reset_at_f32(ctypes.byref(self._struct), dev.ptr(mask), int(seed) & (2 ** 64 - 1),
-                                       self.episode.data_ptr(), 1 if sample else 0, self.err_flags.data_ptr(), self.env_offset, self.n,
-                                       dev.stream_ptr(self.device))
-      _lib.check(code, 'ble_reset_at_f32')
-    if self._gp is not None:        # a new episode gets a new feature constructor (balloon_arena.py:171-177)
-      if mask is None:
-        self._obs_reset.fill_(1)
-      else:
-        torch.maximum(self._obs_reset, mask, out=self._obs_reset)
+    fn, lead = self._entry('ble_reset_at_f32')
+    _lib.check(fn(*lead, dev.ptr(mask), int(seed) & (2 ** 64 - 1), self.episode.data_ptr(), 1 if sample else 0, self.err_flags.data_ptr(),
+                  self.env_offset, self.n, dev.stream_ptr(self.device)), fn.__name__)
+    self.reset_observation_history(mask)        # a new episode gets a new feature constructor (balloon_arena.py:171-177)
 
   @_on_own_device
   def reset_device_seeded(self, env_seed: torch.Tensor, mask: Optional[torch.Tensor] = None, sample: bool = True) -> None:
@@ -240,11 +240,7 @@ class VecSimulator:
     _lib.check(self.lib.ble_reset_seeded_f32(ctypes.byref(self._struct), dev.ptr(mask), env_seed.data_ptr(), self.episode.data_ptr(),
                                              1 if sample else 0, self.err_flags.data_ptr(), self.n, dev.stream_ptr(self.device)),
                'ble_reset_seeded_f32')
-    if self._gp is not None:
-      if mask is None:
-        self._obs_reset.fill_(1)
-      else:
-        torch.maximum(self._obs_reset, mask, out=self._obs_reset)
+    self.reset_observation_history(mask)
 
   def _check_env_seed(self, env_seed: torch.Tensor) -> None:
     assert env_seed.dtype == torch.int64 and env_seed.is_contiguous() and env_seed.numel() == self.n and env_seed.device == self.device
@@ -281,10 +277,8 @@ class VecSimulator:
       _lib.check(self.lib.ble_observe_live_f32(ctypes.byref(self._struct), *args), 'ble_observe_live_f32')
       self._obs_reset.masked_fill_(self.state['status'] == 0, 0)        # (the lanes observed)
       return out
-    if self.has_fleet:
-      _lib.check(self.lib.ble_observe_forecast_fleet_f32(ctypes.byref(self._struct), ctypes.byref(self._fleet), *args), 'ble_observe_forecast_fleet_f32')
-    else:
-      _lib.check(self.lib.ble_observe_forecast_f32(ctypes.byref(self._struct), *args), 'ble_observe_forecast_f32')
+    fn, lead = self._entry('ble_observe_forecast_f32')
+    _lib.check(fn(*lead, *args), fn.__name__)
     self._obs_reset.zero_()         # stream-ordered after the kernel
     return out
 
@@ -421,13 +415,10 @@ class VecSimulator:
     assert action.device == self.device
     if noise_uv is not None:
       assert noise_uv.dtype == torch.float32 and noise_uv.is_contiguous() and tuple(noise_uv.shape) == (self.n, 2)
-    args = (action.data_ptr(), self.grid.data_ptr(), self.grid_env_stride, dev.ptr(noise_uv), self.reward.data_ptr(),
-            self.terminal.data_ptr(), self.effective_action.data_ptr(), self.err_flags.data_ptr(), self.active_slots.data_ptr(), self.n,
-            substeps, dev.stream_ptr(self.device))
-    if self.has_fleet:
-      _lib.check(self.lib.ble_step_fleet_f32(ctypes.byref(self._struct), ctypes.byref(self._fleet), *args), 'ble_step_fleet_f32')
-    else:
-      _lib.check(self.lib.ble_step_f32(ctypes.byref(self._struct), *args), 'ble_step_f32')
+    fn, lead = self._entry('ble_step_f32')
+    _lib.check(fn(*lead, action.data_ptr(), self.grid.data_ptr(), self.grid_env_stride, dev.ptr(noise_uv), self.reward.data_ptr(),
+                  self.terminal.data_ptr(), self.effective_action.data_ptr(), self.err_flags.data_ptr(), self.active_slots.data_ptr(), self.n,
+                  substeps, dev.stream_ptr(self.device)), fn.__name__)
     return self.reward, self.terminal
 
   def _noise_gen(self, noise_seed: Optional[int], prepared: bool = False):
@@ -444,32 +435,8 @@ class VecSimulator:
       del self._noise_gens[:-4096]          # (bounded: a long-lived simulator may prepare launches again and again)
     return gen
 
-  @_on_own_device
-  def step_n(self, actions: torch.Tensor, rewards: torch.Tensor, terminals: torch.Tensor,
-             active_counts: Optional[torch.Tensor] = None, substeps: int = SUBSTEPS, noise_seed: Optional[int] = None) -> None:
-    """`actions` [K, n] uint8 -> K agent steps enqueued by one library call.  noise_seed: fly in the ground-truth wind
-    (WindField.get_ground_truth: the noise of wind_noise(noise_seed) evaluated in the kernel before every step)."""
-    k = actions.shape[0]
-    assert actions.dtype == torch.uint8 and actions.is_contiguous() and tuple(actions.shape) == (k, self.n)
-    assert rewards.dtype == torch.float32 and tuple(rewards.shape) == (k, self.n) and rewards.is_contiguous()
-    assert terminals.dtype == torch.uint8 and tuple(terminals.shape) == (k, self.n) and terminals.is_contiguous()
-    if active_counts is not None:
-      assert active_counts.dtype == torch.int64 and tuple(active_counts.shape) == (k, COUNT_SLOTS)
-      assert active_counts.is_contiguous()
-    gen = self._noise_gen(noise_seed)
-    args = (actions.data_ptr(), self.grid.data_ptr(), self.grid_env_stride, None if gen is None else ctypes.byref(gen), rewards.data_ptr(),
-            terminals.data_ptr(), self.err_flags.data_ptr(), dev.ptr(active_counts), self.n, substeps, k, dev.stream_ptr(self.device))
-    if self.has_fleet:
-      _lib.check(self.lib.ble_step_n_fleet_f32(ctypes.byref(self._struct), ctypes.byref(self._fleet), *args), 'ble_step_n_fleet_f32')
-    else:
-      _lib.check(self.lib.ble_step_n_f32(ctypes.byref(self._struct), *args), 'ble_step_n_f32')
-
-  def prepare_step_n(self, actions: torch.Tensor, rewards: torch.Tensor, terminals: torch.Tensor,
-                     active_counts: Optional[torch.Tensor] = None, substeps: int = SUBSTEPS, noise_seed: Optional[int] = None):
-    """step_n with everything but the launch done NOW: the checks run once and the arguments are marshalled once;
-    the returned callable enqueues the K agent steps on the stream that is current when IT is called (~3 us of host
-    time instead of ~10).  For loops that launch the same buffers again and again (rollouts, the benchmark); the
-    caller keeps the tensors, the grid and the simulator alive and unchanged in shape."""
+  def _step_n_args(self, actions, rewards, terminals, active_counts, substeps, noise_seed, prepared: bool = False) -> tuple:
+    """step_n's and prepare_step_n's checks; returns their arguments of ble_step_n_f32 between the state and the stream."""
     k = actions.shape[0]
     assert actions.dtype == torch.uint8 and actions.is_contiguous() and tuple(actions.shape) == (k, self.n)
     assert rewards.dtype == torch.float32 and tuple(rewards.shape) == (k, self.n) and rewards.is_contiguous()
@@ -478,16 +445,29 @@ class VecSimulator:
       assert active_counts.dtype == torch.int64 and tuple(active_counts.shape) == (k, COUNT_SLOTS)
       assert active_counts.is_contiguous()
     assert self.grid is not None, 'Must call set_grid (reset) before step.'
-    # a fleet: the fleet entry point, with the simulator's one ble_fleet struct (set_fleet updates it in place).  Whether there IS a
-    # fleet is decided here: prepare again after set_fleet on a simulator without one, or after set_vehicle on one with a fleet
-    if self.has_fleet:
-      fn, struct = self.lib.ble_step_n_fleet_f32, (ctypes.byref(self._struct), ctypes.byref(self._fleet))
-    else:
-      fn, struct = self.lib.ble_step_n_f32, (ctypes.byref(self._struct),)
-    gen = self._noise_gen(noise_seed, prepared=True)            # (kept alive by the closure)
-    grid = self.grid                             # the closure reads THIS tensor: load_state_dict restores it in place
-    args = struct + (actions.data_ptr(), grid.data_ptr(), self.grid_env_stride, None if gen is None else ctypes.byref(gen),
-                     rewards.data_ptr(), terminals.data_ptr(), self.err_flags.data_ptr(), dev.ptr(active_counts), self.n, substeps, k)
+    gen = self._noise_gen(noise_seed, prepared)
+    return (actions.data_ptr(), self.grid.data_ptr(), self.grid_env_stride, None if gen is None else ctypes.byref(gen), rewards.data_ptr(),
+            terminals.data_ptr(), self.err_flags.data_ptr(), dev.ptr(active_counts), self.n, substeps, k)
+
+  @_on_own_device
+  def step_n(self, actions: torch.Tensor, rewards: torch.Tensor, terminals: torch.Tensor,
+             active_counts: Optional[torch.Tensor] = None, substeps: int = SUBSTEPS, noise_seed: Optional[int] = None) -> None:
+    """`actions` [K, n] uint8 -> K agent steps enqueued by one library call.  noise_seed: fly in the ground-truth wind
+    (WindField.get_ground_truth: the noise of wind_noise(noise_seed) evaluated in the kernel before every step)."""
+    fn, lead = self._entry('ble_step_n_f32')
+    _lib.check(fn(*lead, *self._step_n_args(actions, rewards, terminals, active_counts, substeps, noise_seed), dev.stream_ptr(self.device)),
+               fn.__name__)
+
+  def prepare_step_n(self, actions: torch.Tensor, rewards: torch.Tensor, terminals: torch.Tensor,
+                     active_counts: Optional[torch.Tensor] = None, substeps: int = SUBSTEPS, noise_seed: Optional[int] = None):
+    """step_n with everything but the launch done NOW: the checks run once and the arguments are marshalled once;
+    the returned callable enqueues the K agent steps on the stream that is current when IT is called (~3 us of host
+    time instead of ~10).  For loops that launch the same buffers again and again (rollouts, the benchmark); the
+    caller keeps the tensors, the grid and the simulator alive and unchanged in shape."""
+    # whether there IS a fleet is decided here: prepare again after set_fleet on a simulator without one, or after set_vehicle on one with
+    # a fleet.  The closure holds the grid's address (load_state_dict restores the grid in place) and the generator (kept alive by its byref)
+    fn, lead = self._entry('ble_step_n_f32')
+    args = lead + self._step_n_args(actions, rewards, terminals, active_counts, substeps, noise_seed, prepared=True)
     device, index = self.device, self.device.index
 
     def launch():

@@ -19,8 +19,12 @@
  *    which the reference raises *inside* the arithmetic (range checks) are OR-ed into
  *    the device word `err_flags` (BLE_FLAG_*), which the host mirror turns back into the
  *    reference's exceptions.
- *  - Re-entrant: no global mutable state; different streams may run concurrently on
- *    disjoint buffers.
+ *  - Arguments are checked before anything else: an invalid one answers BLE_E_INVALID_ARG
+ *    whatever n is, n == 0 included; valid arguments with n == 0 answer BLE_OK and launch
+ *    nothing.
+ *  - Thread-safe.  The library's global state is the step form (ble_set_step_form:
+ *    process-global, atomic) and the status of each thread's last launch (ble_last_hip_error:
+ *    per thread).  Different streams may run concurrently on disjoint buffers.
  *  - Units and encodings follow the reference: metres, Pa, K, mol, Wh, W, kg/s, seconds;
  *    actions 0=DOWN 1=STAY 2=UP (env/balloon/control.py:21-25); status 0=OK
  *    1=OUT_OF_POWER 2=BURST 3=ZEROPRESSURE (env/balloon/balloon.py:66-70).
@@ -166,7 +170,8 @@ typedef struct ble_state_f32 {
 /* Up to this many environments ble_step_f32 / ble_step_n_f32 -- with or without a wind-noise generator -- run the
  * four-wavefronts-per-environment form of the transition (csrc/ble_step_split.h: 4 x n / 64 waves -- one per SIMD up to
  * 16 384 environments, two up to 32 768), above it the one-lane-per-environment kernel (one wave per SIMD at 65 536).
- * The forms are bit-identical; ble_set_step_form() forces one. */
+ * The forms are bit-identical; ble_set_step_form() forces one.  A run-time vehicle (st->vehicle) or a fleet always flies the
+ * one-lane form, whatever ble_set_step_form or the automatic choice says. */
 #define BLE_SPLIT_MAX_ENVS 32768
 
 int ble_abi_version(void);
@@ -186,8 +191,10 @@ int ble_last_hip_error(void);
  * only -- profiles/build_variant.sh -DBLE_WITH_PAIR_FORM; the product library answers BLE_E_INVALID_ARG since ABI 5: the form was
  * never selected and measured slower at every batch size.)
  * Process-global, thread-safe; takes effect with the next launch.  Returns the previous setting (>= 0) or
- * BLE_E_INVALID_ARG.  The initial value is 0, or what BLE_STEP_SPLIT (0 -> one lane, 1 / 4, 2) in the process environment
- * says when the library first looks at it -- once, not per launch.  (ABI 4; ABI 3 re-read the variable on every launch.) */
+ * BLE_E_INVALID_ARG.  The initial value comes from BLE_STEP_SPLIT in the process environment when the library first looks at
+ * it -- once, not per launch: 0 -> one lane, 1 or 4 -> four wavefronts, anything else (2 included, in the product library) or
+ * unset -> automatic.  (ABI 4; ABI 3 re-read the variable on every launch.)  Honoured for the default vehicle only: a run-time
+ * vehicle or a fleet always flies the one-lane form. */
 int ble_set_step_form(int waves_per_env);
 
 /* Number of visible HIP devices (>= 0) or BLE_E_NO_DEVICE. */
@@ -225,6 +232,8 @@ int ble_device_count(void);
  *                 the caller sums the slots
  * Envs whose status != OK on entry are skipped: state untouched, reward 0, terminal 1
  * (the reference raises AssertionError, balloon.py:288-290; the host mirror does too).
+ * The form of the kernel: BLE_SPLIT_MAX_ENVS and ble_set_step_form above; a run-time vehicle flies the one-lane form
+ * whatever they say.
  */
 int ble_step_f32(const ble_state_f32* st, const uint8_t* action, const float* wind_grid,
                  int64_t grid_env_stride, const float* noise_uv, float* reward, uint8_t* terminal,
@@ -402,7 +411,7 @@ int ble_power_table_f32(const float* pressure_ratio, const float* state_of_charg
 int ble_probe_atmosphere_f32(const float* alpha, const float* pressure, float* height,
                              float* temperature, uint32_t* err_flags, int64_t n, void* stream);
 /* Atmosphere.at_height (standard_atmosphere.py:89-120): pressure [Pa] and temperature [K] at heights [m], float64 (ABI 5; until then the
- * host mirror inverted ble_probe_atmosphere_f32 by bracketing its float32 outputs: 1e-7).  Heights outside [-610 m, 84 852 m) set
+ * host mirror inverted ble_probe_atmosphere_f32 by bracketing its float32 outputs: 1e-7).  Heights outside [-610 m, 85 000 m) set
  * BLE_FLAG_PRESSURE_RANGE (the reference asserts, :94-95). */
 int ble_probe_atmosphere_at_height_f64(const float* alpha, const double* height_m, double* pressure, double* temperature,
                                        uint32_t* err_flags, int64_t n, void* stream);
@@ -478,7 +487,8 @@ int ble_probe_f64_prims(const double* x, double* y, int op, int64_t n, void* str
  * The fleet entry points take the arguments of their single-vehicle counterparts plus `fleet` after `st`, and answer
  * BLE_E_INVALID_ARG (before any HIP call) for a NULL fleet, palette or vehicle_index, n_vehicles outside 1 .. 16, a palette entry
  * that ble_state_f32.vehicle would refuse, or st->vehicle != NULL (two sources of the vehicle are refused, not merged).
- * The transition flies the one-lane-per-environment form at every batch size (as a run-time vehicle does).
+ * The transition flies the one-lane-per-environment form at every batch size, whatever ble_set_step_form says (as a run-time
+ * vehicle does).
  */
 #define BLE_FLEET_MAX_VEHICLES 16
 typedef struct ble_fleet {
