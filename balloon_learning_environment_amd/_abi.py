@@ -136,3 +136,38 @@ class BleQnetF32(ctypes.Structure):
   _fields_ = [('num_layers', ctypes.c_int32), ('input_dim', ctypes.c_int32), ('hidden_units', ctypes.c_int32),
               ('num_actions', ctypes.c_int32), ('num_atoms', ctypes.c_int32), ('reserved_', ctypes.c_int32),
               ('weights', ctypes.c_void_p)]
+
+
+class BleReplayF32(ctypes.Structure):
+  """struct ble_replay_f32: the per-environment n-step replay ring (device pointers) and its sizes."""
+  _fields_ = [('capacity', ctypes.c_int64), ('num_envs', ctypes.c_int64), ('update_horizon', ctypes.c_int32),
+              ('obs_stride', ctypes.c_int32), ('gamma', ctypes.c_double), ('max_tries', ctypes.c_int32),
+              ('reserved_', ctypes.c_int32),
+              ('obs', ctypes.c_void_p), ('action', ctypes.c_void_p), ('reward', ctypes.c_void_p), ('terminal', ctypes.c_void_p),
+              ('episode_end', ctypes.c_void_p), ('count', ctypes.c_void_p), ('counter', ctypes.c_void_p)]
+
+
+class BleTrainBatchF32(ctypes.Structure):
+  """struct ble_train_batch_f32: one batch of B transitions (device pointers)."""
+  _fields_ = [('batch', ctypes.c_int64), ('state_stride', ctypes.c_int64), ('state', ctypes.c_void_p), ('next_state', ctypes.c_void_p),
+              ('ret', ctypes.c_void_p), ('discount', ctypes.c_void_p), ('action', ctypes.c_void_p), ('index', ctypes.c_void_p)]
+
+
+class BleQnetTrainF32(ctypes.Structure):
+  """struct ble_qnet_train_f32: the trainer's device buffers and Adam's hyperparameters."""
+  _fields_ = [('net', BleQnetF32), ('target', ctypes.c_void_p), ('weights_t', ctypes.c_void_p), ('grad', ctypes.c_void_p),
+              ('adam_m', ctypes.c_void_p), ('adam_v', ctypes.c_void_p), ('adam_step', ctypes.c_void_p), ('workspace', ctypes.c_void_p),
+              ('adam_b1', ctypes.c_double), ('adam_b2', ctypes.c_double), ('lr', ctypes.c_float), ('adam_eps', ctypes.c_float),
+              ('kappa', ctypes.c_float), ('apply_update', ctypes.c_int32)]
+
+
+class BleQnetTrainLayout(ctypes.Structure):
+  """struct ble_qnet_train_layout: offsets, in floats, into the trainer's workspace."""
+  _fields_ = [(name, ctypes.c_int64) for name in ('ld', 'acts', 'target_logits', 'targets', 'dlogits', 'scratch', 'partial', 'slabs',
+                                                  'corrections', 'total', 'transposed_floats')]
+
+
+class BleExploreF32(ctypes.Structure):
+  """struct ble_explore_f32: epsilon-greedy over n actions, keyed by (seed, env, step)."""
+  _fields_ = [('n', ctypes.c_int64), ('epsilon', ctypes.c_float), ('reserved_', ctypes.c_int32), ('seed', ctypes.c_uint64),
+              ('step', ctypes.c_uint64)]

@@ -19,7 +19,8 @@ from balloon_learning_environment_amd import _abi
 _PKG_DIR = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get('BLE_HIP_LIB') or os.path.join(_PKG_DIR, 'libble_hip.so')   # override: experiments only
 _SOURCES = [os.path.join(_PKG_DIR, 'csrc', f) for f in ('ble_kernels.hip', 'ble_step_core.h', 'ble_physics.h', 'ble_intrinsics.h', 'ble_reset.h',
-                                                          'ble_observe.h', 'ble_noise.h', 'ble_decode.h', 'ble_step_split.h', 'ble_agent.h', 'ble_qnet.h')]
+                                                          'ble_observe.h', 'ble_noise.h', 'ble_decode.h', 'ble_step_split.h', 'ble_agent.h', 'ble_qnet.h',
+                                                          'ble_train.h')]
 _HEADER = os.path.join(os.path.dirname(_PKG_DIR), 'include', 'ble_abi.h')
 
 ABI_VERSION = 5
@@ -29,6 +30,7 @@ FLAG_PRESSURE_RANGE, FLAG_ABSORPTIVITY, FLAG_SOLAR_RANGE, FLAG_POWER_TABLE, FLAG
 FLAG_GP_WINDOW, FLAG_PRESSURE_SEARCH, FLAG_DAY_CYCLE = 64, 128, 256
 FLAG_VEHICLE_INDEX = 512
 FLAG_AGENT_NO_LEVEL = 1024
+FLAG_REPLAY_EMPTY, FLAG_TRAIN_ACTION = 2048, 4096
 SEEKER_LEVELS = 361
 OBS_DIM, GP_CAPACITY, GP_CHOL_STRIDE = 1099, 128, 7620
 ROW_DOUBLES = 26        # BLE_ROW_DOUBLES
@@ -40,7 +42,9 @@ EXPORTS = ('ble_abi_version', 'ble_noise_primitive_version', 'ble_vehicle_defaul
            'ble_probe_solar_power_f32', 'ble_probe_thermal_f32', 'ble_probe_sp_volume_f32', 'ble_probe_thermal_vehicle_f32', 'ble_probe_sp_volume_vehicle_f32', 'ble_probe_acs_f32', 'ble_probe_safety_f32',
            'ble_probe_f64_prims', 'ble_step_fleet_f32', 'ble_step_n_fleet_f32', 'ble_reset_fleet_at_f32', 'ble_observe_forecast_fleet_f32',
            'ble_station_seeker_f32', 'ble_eval_accumulate_f32', 'ble_reset_seeded_f32', 'ble_wind_noise_seeded_f32',
-           'ble_observe_live_f32', 'ble_qnet_workspace_f32', 'ble_qnet_pack_f32', 'ble_qnet_forward_f32')
+           'ble_observe_live_f32', 'ble_qnet_workspace_f32', 'ble_qnet_pack_f32', 'ble_qnet_forward_f32',
+           'ble_qnet_unpack_f32', 'ble_replay_sample_f32', 'ble_qnet_train_workspace_f32', 'ble_qnet_transpose_f32',
+           'ble_qnet_train_step_f32', 'ble_qnet_explore_u8')
 
 
 class BleLibraryError(RuntimeError):
@@ -136,6 +140,15 @@ def lib():
   l.ble_qnet_workspace_f32.argtypes = [qnet, _i64, ctypes.POINTER(_i64), ctypes.POINTER(_i64)]
   l.ble_qnet_pack_f32.argtypes = [qnet, ctypes.POINTER(_vp), ctypes.POINTER(_vp), _vp]
   l.ble_qnet_forward_f32.argtypes = [qnet, _vp, _i64, _vp, _vp, _vp, _i64, _vp]
+  # training: every size travels in a descriptor (no int64_t argument)
+  batch = ctypes.POINTER(_abi.BleTrainBatchF32)
+  train = ctypes.POINTER(_abi.BleQnetTrainF32)
+  l.ble_qnet_unpack_f32.argtypes = [qnet, _vp, ctypes.POINTER(_vp), ctypes.POINTER(_vp)]
+  l.ble_replay_sample_f32.argtypes = [ctypes.POINTER(_abi.BleReplayF32), batch, ctypes.c_uint64, _vp, _vp]
+  l.ble_qnet_train_workspace_f32.argtypes = [train, batch, ctypes.POINTER(_abi.BleQnetTrainLayout)]
+  l.ble_qnet_transpose_f32.argtypes = [qnet, _vp, _vp]
+  l.ble_qnet_train_step_f32.argtypes = [train, batch, _vp, _vp, _vp]
+  l.ble_qnet_explore_u8.argtypes = [ctypes.POINTER(_abi.BleExploreF32), _vp, _vp]
   for name in EXPORTS:
     getattr(l, name).restype = _int
   _lib = l

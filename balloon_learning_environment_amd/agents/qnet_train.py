@@ -1,0 +1,330 @@
+"""Training QR-DQN / DQN policies on the device: Dopamine 4.0.0's JaxQuantileAgent update (configs/quantile.gin) without JAX.
+
+`VecReplayBuffer` is an n-step replay ring of N environments stepped in lockstep (VecBalloonEnv's tensors, one ring column per
+environment); `QNetworkTrainer` holds the online and target images, the gradient, Adam's moments and the device counters, and runs one
+update -- uniform n-step sample, target and online forward, quantile Huber loss, backprop, Adam -- as a handful of HIP kernels
+(csrc/ble_train.h) with no host synchronisation, capturable as one graph.  Every reduction has one order fixed by the
+shapes and no kernel uses floating-point atomics: a run is a pure function of (initial parameters, replay contents, seeds).
+
+With num_atoms == 1 the loss is the one-quantile QR loss, i.e. half the Huber loss of DQN's TD error (tau = 1/2); DQN's own loss is not
+implemented.
+"""
+import ctypes
+from typing import Dict, Optional
+
+import numpy as np
+import torch
+
+from balloon_learning_environment_amd import _abi
+from balloon_learning_environment_amd import _lib
+from balloon_learning_environment_amd import device as dev
+from balloon_learning_environment_amd.agents import qnet
+
+ROW_FLOATS = 1104          # a stored observation row: the 1099 features zero-padded to a multiple of 4 (aligned float4 rows)
+MAX_TRIES = 64
+
+
+def _check_flags(flags: torch.Tensor) -> None:
+  f = int(flags.item())
+  if f:
+    flags.zero_()
+  if f & _lib.FLAG_REPLAY_EMPTY:
+    raise RuntimeError('replay: no valid n-step window to sample (too few steps written, or every window crosses a time-limit end)')
+  if f & _lib.FLAG_TRAIN_ACTION:
+    raise ValueError('train step: a batch action is not below num_actions')
+
+
+class TrainBatch:
+  """One batch of B transitions on the device (what the sampler writes, what the train step reads)."""
+
+  def __init__(self, batch_size: int, device):
+    b = int(batch_size)
+    self.batch_size = b
+    self.state = torch.zeros(b, ROW_FLOATS, dtype=torch.float32, device=device)
+    self.next_state = torch.zeros(b, ROW_FLOATS, dtype=torch.float32, device=device)
+    self.ret = torch.zeros(b, dtype=torch.float32, device=device)
+    self.discount = torch.zeros(b, dtype=torch.float32, device=device)
+    self.action = torch.zeros(b, dtype=torch.uint8, device=device)
+    self.index = torch.zeros(b, 2, dtype=torch.int64, device=device)
+    self.struct = _abi.BleTrainBatchF32(b, ROW_FLOATS, self.state.data_ptr(), self.next_state.data_ptr(), self.ret.data_ptr(),
+                                        self.discount.data_ptr(), self.action.data_ptr(), self.index.data_ptr())
+
+  @classmethod
+  def from_tensors(cls, state, next_state, ret, discount, action, device) -> 'TrainBatch':
+    """A batch given on the host or device (state rows of 1099 features); for tests and offline data."""
+    bt = cls(len(action), device)
+    bt.state[:, :_lib.OBS_DIM].copy_(torch.as_tensor(np.asarray(state, np.float32)))
+    bt.next_state[:, :_lib.OBS_DIM].copy_(torch.as_tensor(np.asarray(next_state, np.float32)))
+    bt.ret.copy_(torch.as_tensor(np.asarray(ret, np.float32)))
+    bt.discount.copy_(torch.as_tensor(np.asarray(discount, np.float32)))
+    bt.action.copy_(torch.as_tensor(np.asarray(action, np.uint8)))
+    bt.index.fill_(-1)
+    return bt
+
+
+class VecReplayBuffer:
+  """The replay memory of N environments: a ring of capacity_steps vector steps (capacity_steps x num_envs transitions).
+
+  add(obs, action, reward, terminal, episode_end) appends one VecBalloonEnv step: obs is the observation the actions were taken on,
+  episode_end marks the steps that end an episode (a terminal or the time limit; default: terminal).  sample(B, seed, counter) draws B
+  valid n-step windows uniformly (ble_replay_sample_f32): a window never reads past an episode's end, and one that reaches a time-limit
+  end without a terminal is not drawn."""
+
+  def __init__(self, num_envs: int, capacity_steps: int, update_horizon: int = 5, gamma: float = 0.993, device='cuda:0'):
+    self.device = dev.require_gpu(device)
+    self.num_envs, self.capacity = int(num_envs), int(capacity_steps)
+    self.update_horizon, self.gamma = int(update_horizon), float(gamma)
+    if self.capacity < self.update_horizon + 1:
+      raise ValueError(f'capacity_steps must be at least update_horizon + 1 = {self.update_horizon + 1}')
+    t, n, d = self.capacity, self.num_envs, self.device
+    with torch.cuda.device(d):
+      self.obs = torch.zeros(t, n, ROW_FLOATS, dtype=torch.float32, device=d)
+      self.action = torch.zeros(t, n, dtype=torch.uint8, device=d)
+      self.reward = torch.zeros(t, n, dtype=torch.float32, device=d)
+      self.terminal = torch.zeros(t, n, dtype=torch.uint8, device=d)
+      self.episode_end = torch.zeros(t, n, dtype=torch.uint8, device=d)
+      self.count = torch.zeros(1, dtype=torch.int64, device=d)
+      self.counter = torch.zeros(1, dtype=torch.int64, device=d)        # (read as uint64 by the kernel)
+      self.err_flags = torch.zeros(1, dtype=torch.int32, device=d)
+    self.cursor = 0                      # host mirror of count
+    self._batches: Dict[int, TrainBatch] = {}
+    self.lib = _lib.lib()
+
+  def __len__(self) -> int:
+    """Transitions held."""
+    return min(self.cursor, self.capacity) * self.num_envs
+
+  def struct(self, counter: torch.Tensor) -> _abi.BleReplayF32:
+    return _abi.BleReplayF32(self.capacity, self.num_envs, self.update_horizon, ROW_FLOATS, self.gamma, MAX_TRIES, 0, self.obs.data_ptr(),
+                             self.action.data_ptr(), self.reward.data_ptr(), self.terminal.data_ptr(), self.episode_end.data_ptr(),
+                             self.count.data_ptr(), counter.data_ptr())
+
+  @dev.on_own_device
+  def add(self, obs: torch.Tensor, action: torch.Tensor, reward: torch.Tensor, terminal: torch.Tensor,
+          episode_end: Optional[torch.Tensor] = None) -> None:
+    row = self.cursor % self.capacity
+    self.obs[row, :, :_lib.OBS_DIM].copy_(obs[:, :_lib.OBS_DIM])
+    self.action[row].copy_(action)
+    self.reward[row].copy_(reward)
+    self.terminal[row].copy_(terminal)
+    self.episode_end[row].copy_(terminal if episode_end is None else episode_end)
+    self.count.add_(1)
+    self.cursor += 1
+
+  def batch_buffers(self, batch_size: int) -> TrainBatch:
+    bt = self._batches.get(batch_size)
+    if bt is None:
+      if torch.cuda.is_current_stream_capturing():
+        raise RuntimeError(f'VecReplayBuffer: sample once at batch size {batch_size} before capturing it in a graph')
+      bt = self._batches[batch_size] = TrainBatch(batch_size, self.device)
+    return bt
+
+  @dev.on_own_device
+  def sample(self, batch_size: int, seed: int, counter: Optional[torch.Tensor] = None) -> TrainBatch:
+    """B transitions into this buffer's batch buffers of that size (overwritten by the next sample at that size).  counter: the
+    int64 [1] device update counter the draw is keyed by and advances (default: the buffer's own)."""
+    bt = self.batch_buffers(int(batch_size))
+    rp = self.struct(self.counter if counter is None else counter)
+    _lib.check(self.lib.ble_replay_sample_f32(ctypes.byref(rp), ctypes.byref(bt.struct), int(seed) & (2 ** 64 - 1), self.err_flags.data_ptr(),
+                                              dev.stream_ptr(self.device)), 'ble_replay_sample_f32')
+    return bt
+
+  def check_errors(self) -> None:
+    _check_flags(self.err_flags)
+
+  def state_dict(self) -> dict:
+    return {'num_envs': self.num_envs, 'capacity': self.capacity, 'update_horizon': self.update_horizon, 'gamma': self.gamma,
+            'cursor': self.cursor, 'obs': self.obs.clone(), 'action': self.action.clone(), 'reward': self.reward.clone(),
+            'terminal': self.terminal.clone(), 'episode_end': self.episode_end.clone(), 'counter': self.counter.clone()}
+
+  def load_state_dict(self, d: dict) -> None:
+    assert (d['num_envs'], d['capacity'], d['update_horizon']) == (self.num_envs, self.capacity, self.update_horizon)
+    for k in ('obs', 'action', 'reward', 'terminal', 'episode_end', 'counter'):
+      getattr(self, k).copy_(d[k])
+    self.cursor = int(d['cursor'])
+    self.count.fill_(self.cursor)
+
+
+class QNetworkTrainer:
+  """QR-DQN training of a QNetwork's parameters on its device (defaults: configs/quantile.gin -- Adam lr 2e-6, eps 2e-5, gamma 0.993,
+  update horizon 5, kappa 1).
+
+    trainer = QNetworkTrainer(QNetwork.from_params(init_params('quantile')))
+    loss = trainer.train_step(replay, 32)          # per-row losses [32], on the device
+    trainer.sync_target()
+    policy = trainer.network()                     # a QNetwork: VecQNetworkAgent, QuantileAgent, eval_agent_vec, save_npz
+  """
+
+  def __init__(self, network: qnet.QNetwork, *, lr: float = 2e-6, eps: float = 2e-5, gamma: float = 0.993, update_horizon: int = 5,
+               kappa: float = 1.0, seed: int = 0, b1: float = 0.9, b2: float = 0.999):
+    self.device = dev.require_gpu(network.device)
+    self.num_layers, self.hidden_units, self.num_atoms = network.num_layers, network.hidden_units, network.num_atoms
+    self.lr, self.eps, self.b1, self.b2, self.kappa = float(lr), float(eps), float(b1), float(b2), float(kappa)
+    self.gamma, self.update_horizon, self.seed = float(gamma), int(update_horizon), int(seed)
+    self.lib = _lib.lib()
+    self._net = _abi.BleQnetF32(self.num_layers, _lib.OBS_DIM, self.hidden_units, qnet.NUM_ACTIONS, self.num_atoms, 0, None)
+    d = self.device
+    with torch.cuda.device(d):
+      self.weights = torch.from_numpy(network.packed_host.copy()).to(d)
+      self.target = self.weights.clone()
+      self.grad = torch.zeros_like(self.weights)
+      self.adam_m = torch.zeros_like(self.weights)
+      self.adam_v = torch.zeros_like(self.weights)
+      self.adam_step = torch.zeros(1, dtype=torch.int64, device=d)
+      self.counter = torch.zeros(1, dtype=torch.int64, device=d)      # the update counter the replay draw is keyed by
+      self.err_flags = torch.zeros(1, dtype=torch.int32, device=d)
+      self.weights_t = torch.zeros(max(self._layout(0).transposed_floats, 4), dtype=torch.float32, device=d)
+    self._net.weights = self.weights.data_ptr()
+    self._retranspose()
+    self._ws: Dict[int, tuple] = {}
+    self._scratch: Dict[int, torch.Tensor] = {}
+    self._graphs: Dict[int, tuple] = {}
+
+  # ---- plumbing
+  def _struct(self, workspace: Optional[torch.Tensor], apply_update: bool = True) -> _abi.BleQnetTrainF32:
+    return _abi.BleQnetTrainF32(self._net, self.target.data_ptr(), self.weights_t.data_ptr(), self.grad.data_ptr(), self.adam_m.data_ptr(),
+                                self.adam_v.data_ptr(), self.adam_step.data_ptr(), dev.ptr(workspace), self.b1, self.b2, self.lr,
+                                self.eps, self.kappa, 1 if apply_update else 0)
+
+  def _layout(self, batch_size: int) -> _abi.BleQnetTrainLayout:
+    bt = _abi.BleTrainBatchF32(int(batch_size), ROW_FLOATS)
+    out = _abi.BleQnetTrainLayout()
+    tr = _abi.BleQnetTrainF32(self._net)
+    _lib.check(self.lib.ble_qnet_train_workspace_f32(ctypes.byref(tr), ctypes.byref(bt), ctypes.byref(out)),
+               'ble_qnet_train_workspace_f32')
+    return out
+
+  def _retranspose(self) -> None:
+    """weights_t from the online image (host transpose; at construction and after a load)."""
+    host_t = np.zeros(self.weights_t.numel(), np.float32)
+    w = self.weights.cpu().numpy()
+    _lib.check(self.lib.ble_qnet_transpose_f32(ctypes.byref(self._net), w.ctypes.data, host_t.ctypes.data), 'ble_qnet_transpose_f32')
+    self.weights_t.copy_(torch.from_numpy(host_t))
+
+  def workspace(self, batch_size: int):
+    """(workspace tensor, layout) of a batch size (allocated on first use, which must not be inside a graph capture)."""
+    w = self._ws.get(batch_size)
+    if w is None:
+      if torch.cuda.is_current_stream_capturing():
+        raise RuntimeError(f'QNetworkTrainer: run one update at batch size {batch_size} before capturing it')
+      lay = self._layout(batch_size)
+      with torch.cuda.device(self.device):
+        ws = torch.zeros(max(lay.total, 64), dtype=torch.float32, device=self.device)
+        loss = torch.zeros(max(batch_size, 1), dtype=torch.float32, device=self.device)
+      w = self._ws[batch_size] = (ws, lay, loss)
+    return w
+
+  def views(self, batch_size: int) -> dict:
+    """The workspace's tensors of the last update at this batch size: 'acts' (every online layer's output, [B, ld] each), 'logits'
+    [B, 3 * atoms] (online), 'target_logits',
+    'targets' [B, atoms], 'dlogits' [B, 3 * atoms], 'loss' [B]."""
+    ws, lay, loss = self.workspace(batch_size)
+    b, ld, out = batch_size, lay.ld, qnet.NUM_ACTIONS * self.num_atoms
+
+    def mat(off, cols, width):
+      return ws[off:off + b * cols].view(b, cols)[:, :width]
+    return {'acts': [mat(lay.acts + l * b * ld, ld, ld) for l in range(self.num_layers)],
+            'logits': mat(lay.acts + (self.num_layers - 1) * b * ld, ld, out), 'target_logits': mat(lay.target_logits, ld, out),
+            'targets': mat(lay.targets, self.num_atoms, self.num_atoms), 'dlogits': mat(lay.dlogits, ld, ld), 'loss': loss[:b]}
+
+  # ---- the update
+  @dev.on_own_device
+  def train_on_batch(self, batch: TrainBatch, apply_update: bool = True) -> torch.Tensor:
+    """One update on a given batch: the per-row losses [B] (a view of a buffer the next update at this size overwrites)."""
+    ws, _, loss = self.workspace(batch.batch_size)
+    tr = self._struct(ws, apply_update)
+    _lib.check(self.lib.ble_qnet_train_step_f32(ctypes.byref(tr), ctypes.byref(batch.struct), loss.data_ptr(), self.err_flags.data_ptr(),
+                                                dev.stream_ptr(self.device)), 'ble_qnet_train_step_f32')
+    return loss[:batch.batch_size]
+
+  @dev.on_own_device
+  def train_step(self, replay: VecReplayBuffer, batch_size: int = 32) -> torch.Tensor:
+    """Sample a batch (keyed by (seed, update counter)) and update: per-row losses [B] on the device, no host synchronisation.  A
+    captured graph of this batch size (capture()) replays it."""
+    g = self._graphs.get(batch_size)
+    if g is not None and g[1] is replay:
+      g[0].replay()
+      return g[2]
+    batch = replay.sample(batch_size, self.seed, self.counter)
+    return self.train_on_batch(batch)
+
+  def capture(self, replay: VecReplayBuffer, batch_size: int = 32) -> None:
+    """Records one update (sample + train step) into a HIP graph that train_step(replay, batch_size) replays from then on: the
+    counters are device memory, so each replay draws a new batch and takes a new Adam step.  Runs one eager update first (the lazy
+    allocations) -- that is a real update."""
+    self.train_step(replay, batch_size)
+    d = self.device
+    side = torch.cuda.Stream(device=d)
+    side.wait_stream(torch.cuda.current_stream(d))
+    graph = torch.cuda.CUDAGraph()
+    with torch.cuda.stream(side):
+      with torch.cuda.graph(graph, stream=side):
+        loss = self.train_on_batch(replay.sample(batch_size, self.seed, self.counter))
+    torch.cuda.current_stream(d).wait_stream(side)
+    self._graphs[batch_size] = (graph, replay, loss)
+
+  def sync_target(self) -> None:
+    self.target.copy_(self.weights)
+
+  def check_errors(self) -> None:
+    _check_flags(self.err_flags)
+
+  # ---- acting
+  @dev.on_own_device
+  def act(self, obs: torch.Tensor, out: torch.Tensor) -> torch.Tensor:
+    """The online network's greedy actions (ble_qnet_forward_f32 on the live image) into out (uint8 [N])."""
+    n = obs.shape[0]
+    s = self._scratch.get(n)
+    if s is None:
+      sf = ctypes.c_int64()
+      _lib.check(self.lib.ble_qnet_workspace_f32(ctypes.byref(self._net), n, None, ctypes.byref(sf)), 'ble_qnet_workspace_f32')
+      s = self._scratch[n] = torch.empty(max(sf.value, 1), dtype=torch.float32, device=self.device)
+    stride = obs.stride(0) if n > 1 else max(obs.stride(0), _lib.OBS_DIM)
+    _lib.check(self.lib.ble_qnet_forward_f32(ctypes.byref(self._net), obs.data_ptr(), stride, s.data_ptr(), out.data_ptr(), None, n,
+                                             dev.stream_ptr(self.device)), 'ble_qnet_forward_f32')
+    return out
+
+  # ---- export and checkpoints
+  def params(self) -> dict:
+    """The flax-shaped tree of the online parameters (ble_qnet_unpack_f32)."""
+    return unpack(self._net, self.weights.cpu().numpy())
+
+  def network(self, device=None) -> qnet.QNetwork:
+    return qnet.QNetwork.from_params(self.params(), num_atoms=self.num_atoms, device=self.device if device is None else device)
+
+  def state_dict(self) -> dict:
+    return {'shape': (self.num_layers, self.hidden_units, self.num_atoms), 'seed': self.seed,
+            'hyper': (self.lr, self.eps, self.b1, self.b2, self.kappa, self.gamma, self.update_horizon),
+            'weights': self.weights.clone(), 'target': self.target.clone(), 'adam_m': self.adam_m.clone(), 'adam_v': self.adam_v.clone(),
+            'adam_step': self.adam_step.clone(), 'counter': self.counter.clone()}
+
+  def load_state_dict(self, d: dict) -> None:
+    """Restores in place (every tensor keeps its address: captured graphs stay valid)."""
+    assert tuple(d['shape']) == (self.num_layers, self.hidden_units, self.num_atoms), 'checkpoint of another network shape'
+    hyper = tuple(d['hyper'])
+    if int(d['seed']) != self.seed or hyper != (self.lr, self.eps, self.b1, self.b2, self.kappa, self.gamma, self.update_horizon):
+      self._graphs.clear()                     # (the seed and hyperparameters are arguments of the captured launches)
+    self.seed = int(d['seed'])
+    self.lr, self.eps, self.b1, self.b2, self.kappa, self.gamma, self.update_horizon = hyper
+    for k in ('weights', 'target', 'adam_m', 'adam_v', 'adam_step', 'counter'):
+      getattr(self, k).copy_(d[k])
+    self._retranspose()
+
+
+def unpack(net: _abi.BleQnetF32, packed: np.ndarray) -> dict:
+  """The flax-shaped tree {'params': {'Dense_i': {'kernel', 'bias'}}} of a host packed image (ble_qnet_unpack_f32)."""
+  packed = np.ascontiguousarray(packed, np.float32)
+  dims = [net.input_dim] + [net.hidden_units] * (net.num_layers - 1) + [net.num_actions * net.num_atoms]
+  kernels = [np.zeros((dims[i], dims[i + 1]), np.float32) for i in range(net.num_layers)]
+  biases = [np.zeros(dims[i + 1], np.float32) for i in range(net.num_layers)]
+  kp = (ctypes.c_void_p * net.num_layers)(*[k.ctypes.data for k in kernels])
+  bp = (ctypes.c_void_p * net.num_layers)(*[b.ctypes.data for b in biases])
+  _lib.check(_lib.lib().ble_qnet_unpack_f32(ctypes.byref(net), packed.ctypes.data, kp, bp), 'ble_qnet_unpack_f32')
+  return {'params': {f'Dense_{i}': {'kernel': k, 'bias': b} for i, (k, b) in enumerate(zip(kernels, biases))}}
+
+
+def explore(actions: torch.Tensor, epsilon: float, seed: int, step: int) -> torch.Tensor:
+  """epsilon-greedy in place on uint8 device actions (ble_qnet_explore_u8): keyed by (seed, environment, step)."""
+  ex = _abi.BleExploreF32(actions.numel(), float(epsilon), 0, int(seed) & (2 ** 64 - 1), int(step) & (2 ** 64 - 1))
+  _lib.check(_lib.lib().ble_qnet_explore_u8(ctypes.byref(ex), actions.data_ptr(), dev.stream_ptr(actions.device)), 'ble_qnet_explore_u8')
+  return actions

@@ -2,8 +2,9 @@
 
 The reference's agent trains Dopamine's JaxQuantileAgent; here only its eval-mode decision exists (epsilon_eval = 0: q = the mean of
 each action's atoms, argmax), on `ble_qnet_forward_f32` at N = 1 -- the kernel VecQNetworkAgent runs on a batch, so a serial decision
-is the batched one bit for bit.  Training (replay, optimiser, target network, exploration) is not part of this package:
-set_mode('train') raises NotImplementedError.
+is the batched one bit for bit.  This agent does not train: set_mode('train') raises NotImplementedError.  Batched training
+(replay, optimiser, target network, exploration) is agents/qnet_train.py with train_lib.run_training_loop_vec; its
+QNetworkTrainer.network() loads here through params=.
 """
 from typing import Optional, Sequence, Union
 

@@ -10,7 +10,9 @@
 #include <hip/hip_runtime.h>
 #include <stddef.h>
 #include <stdlib.h>
+#include <algorithm>
 #include <atomic>
+#include <cmath>
 #include <type_traits>
 
 // Instrumentation hooks of ble_step_kernel: empty in the product build.  A profiling build
@@ -35,6 +37,7 @@
 #include "ble_decode.h"
 #include "ble_agent.h"
 #include "ble_qnet.h"
+#include "ble_train.h"
 
 using namespace ble;
 
@@ -976,6 +979,56 @@ int64_t qnet_scratch_ld(const ble_qnet_f32* net) {
   for (int l = 0; l < net->num_layers; ++l) ld = std::max<int64_t>(ld, qnet_dims(net, l).mp);
   return ld;
 }
+bool replay_ok(const ble_replay_f32* rp) {
+  return rp != nullptr && rp->update_horizon >= 1 && rp->update_horizon <= BLE_REPLAY_MAX_HORIZON && rp->capacity >= rp->update_horizon + 1 &&
+         rp->capacity <= (1LL << 40) && rp->num_envs >= 1 && rp->num_envs <= (1LL << 32) && rp->obs_stride >= BLE_OBS_DIM &&
+         rp->obs_stride % 4 == 0 && std::isfinite(rp->gamma) && rp->max_tries >= 1 && rp->max_tries <= BLE_REPLAY_MAX_TRIES && rp->obs &&
+         (reinterpret_cast<uintptr_t>(rp->obs) & 15) == 0 && rp->action && rp->reward && rp->terminal && rp->episode_end && rp->count &&
+         rp->counter;
+}
+bool batch_ok(const ble_train_batch_f32* bt) {
+  return bt != nullptr && bt->batch >= 0 && bt->batch <= BLE_TRAIN_MAX_BATCH && bt->state_stride >= BLE_OBS_DIM && bt->state_stride % 4 == 0 &&
+         bt->state_stride <= (1LL << 20) && bt->state && bt->next_state && bt->ret && bt->discount && bt->action &&
+         ((reinterpret_cast<uintptr_t>(bt->state) | reinterpret_cast<uintptr_t>(bt->next_state)) & 15) == 0;
+}
+TrainDims train_dims(const ble_qnet_f32* net) {
+  TrainDims t{};
+  t.layers = net->num_layers;
+  int64_t toff = 0;
+  for (int l = 0; l < net->num_layers; ++l) {
+    const QnetLayerDims d = qnet_dims(net, l);
+    t.offset[l] = d.offset;
+    t.offset[l + 1] = d.offset + (int64_t)d.kp * d.mp + d.mp;
+    t.k[l] = d.k; t.m[l] = d.m; t.kp[l] = d.kp; t.mp[l] = d.mp;
+    t.toffset[l] = toff;
+    if (l > 0) toff += qnet_round_up(d.m, kQnetChunk) * qnet_dims(net, l - 1).mp;      // kp' = round8(M_l), mp' = round64(K_l)
+  }
+  return t;
+}
+ble_qnet_train_layout train_layout(const ble_qnet_f32* net, int64_t n) {
+  ble_qnet_train_layout y{};
+  const int64_t ld = qnet_scratch_ld(net), L = net->num_layers;
+  int64_t blk = 0, tfl = 0;
+  for (int l = 0; l < L; ++l) {
+    const QnetLayerDims d = qnet_dims(net, l);
+    blk = std::max<int64_t>(blk, (int64_t)d.kp * d.mp + d.mp);
+    if (l > 0) tfl += qnet_round_up(d.m, kQnetChunk) * qnet_dims(net, l - 1).mp;
+  }
+  y.ld = ld;
+  y.slabs = wgrad_slabs(n);
+  int64_t at = 0;
+  auto take = [&](int64_t floats) { const int64_t o = at; at += qnet_round_up(floats, 64); return o; };
+  y.acts = take(L * n * ld);
+  y.target_logits = take(n * ld);
+  y.targets = take(n * net->num_atoms);
+  y.dlogits = take(n * ld);
+  y.scratch = take(4 * n * ld);
+  y.partial = take(y.slabs > 1 ? y.slabs * blk : 0);
+  y.corrections = take(4);
+  y.total = at;
+  y.transposed_floats = tfl;
+  return y;
+}
 }  // namespace
 
 extern "C" {
@@ -1212,6 +1265,132 @@ int ble_qnet_forward_f32(const ble_qnet_f32* net, const float* obs, int64_t obs_
   }
   return launch(ble_qnet_head_kernel, n, kQnetHeadBlock, kQnetHeadBlock, stream, buf[(net->num_layers - 1) & 1], ld, net->num_actions,
                 net->num_atoms, action, q_values, n);
+}
+
+// ---------------------------------------------------------------------------------------------------------------- Q-network training
+int ble_qnet_unpack_f32(const ble_qnet_f32* net, const float* packed, float* const* kernel, float* const* bias) {
+  if (!qnet_ok(net) || !packed || !kernel || !bias) return BLE_E_INVALID_ARG;
+  for (int l = 0; l < net->num_layers; ++l)
+    if (!kernel[l] || !bias[l]) return BLE_E_INVALID_ARG;
+  qnet_unpack(net->num_layers, net->input_dim, net->hidden_units, net->num_actions, net->num_atoms, packed, kernel, bias);
+  return BLE_OK;
+}
+
+int ble_replay_sample_f32(const ble_replay_f32* rp, const ble_train_batch_f32* bt, unsigned long long seed, uint32_t* err_flags,
+                          void* stream) {
+  if (!replay_ok(rp) || !batch_ok(bt)) return BLE_E_INVALID_ARG;
+  if (bt->batch == 0) return BLE_OK;
+  const int status = launch_grid(ble_replay_sample_kernel, dim3((unsigned)bt->batch), kReplayBlock, stream, *rp, *bt, (uint64_t)seed, err_flags);
+  if (status != BLE_OK) return status;
+  return launch_grid(ble_train_advance_kernel, dim3(1), 1, stream, rp->counter);
+}
+
+int ble_qnet_train_workspace_f32(const ble_qnet_train_f32* tr, const ble_train_batch_f32* bt, ble_qnet_train_layout* out) {
+  if (!tr || !qnet_ok(&tr->net) || !bt || bt->batch < 0 || bt->batch > BLE_TRAIN_MAX_BATCH || !out) return BLE_E_INVALID_ARG;
+  *out = train_layout(&tr->net, bt->batch);
+  return BLE_OK;
+}
+
+int ble_qnet_transpose_f32(const ble_qnet_f32* net, const float* packed, float* packed_t) {
+  if (!qnet_ok(net) || !packed || !packed_t) return BLE_E_INVALID_ARG;
+  const TrainDims dims = train_dims(net);
+  for (int l = 1; l < dims.layers; ++l) {
+    const int kpt = (int)qnet_round_up(dims.m[l], kQnetChunk), mpt = dims.mp[l - 1];
+    for (int64_t e = 0; e < (int64_t)kpt * mpt; ++e) packed_t[dims.toffset[l] + e] = 0.0f;
+    const float* p = packed + dims.offset[l];
+    for (int g = 0; g < dims.mp[l] / kQnetCols; ++g)
+      for (int c = 0; c < dims.kp[l] / kQnetChunk; ++c)
+        for (int t = 0; t < 2; ++t)
+          for (int lane = 0; lane < 64; ++lane)
+            for (int j = 0; j < 4; ++j) {
+              const int k = kQnetChunk * c + 4 * (lane >> 5) + j, m = kQnetCols * g + 32 * t + (lane & 31);
+              const float v = *p++;
+              if (k < dims.k[l] && m < dims.m[l]) packed_t[dims.toffset[l] + qnet_transposed_index(k, m, kpt)] = v;
+            }
+  }
+  return BLE_OK;
+}
+
+int ble_qnet_train_step_f32(const ble_qnet_train_f32* tr, const ble_train_batch_f32* bt, float* loss, uint32_t* err_flags, void* stream) {
+  if (!tr || !qnet_ok(&tr->net) || !batch_ok(bt) || !loss || !tr->net.weights || !tr->target || !tr->grad || !tr->workspace ||
+      !(tr->kappa > 0.0f) || !std::isfinite(tr->kappa))
+    return BLE_E_INVALID_ARG;
+  if (tr->net.num_layers > 1 && !tr->weights_t) return BLE_E_INVALID_ARG;
+  if (tr->apply_update && (!tr->adam_m || !tr->adam_v || !tr->adam_step ||
+                           !std::isfinite(tr->lr) || !std::isfinite(tr->adam_b1) || !std::isfinite(tr->adam_b2) || !std::isfinite(tr->adam_eps)))
+    return BLE_E_INVALID_ARG;
+  const uintptr_t align = reinterpret_cast<uintptr_t>(tr->net.weights) | reinterpret_cast<uintptr_t>(tr->target) |
+                          reinterpret_cast<uintptr_t>(tr->grad) | reinterpret_cast<uintptr_t>(tr->workspace) |
+                          reinterpret_cast<uintptr_t>(tr->adam_m) | reinterpret_cast<uintptr_t>(tr->adam_v) |
+                          reinterpret_cast<uintptr_t>(tr->weights_t);
+  if (align & 15) return BLE_E_INVALID_ARG;
+  const int64_t n = bt->batch;
+  if (n == 0) return BLE_OK;
+  const ble_qnet_f32* net = &tr->net;
+  const ble_qnet_train_layout lay = train_layout(net, n);
+  const TrainDims dims = train_dims(net);
+  const int L = net->num_layers;
+  const int64_t ld = lay.ld;
+  float* ws = tr->workspace;
+  float* acts = ws + lay.acts;
+  float* tbuf[2] = {ws + lay.scratch, ws + lay.scratch + n * ld};
+  float* dyb[2] = {ws + lay.scratch + 2 * n * ld, ws + lay.scratch + 3 * n * ld};
+  const unsigned row_tiles = (unsigned)((n + kQnetRows - 1) / kQnetRows);
+  int status = BLE_OK;
+  // the two forward passes: the target's on next_state (ping-pong, its logits end in target_logits), the online one on state (kept)
+  for (int pass = 0; pass < 2; ++pass) {
+    const bool online = pass == 1;
+    const float* wimg = online ? net->weights : tr->target;
+    for (int l = 0; l < L && status == BLE_OK; ++l) {
+      const QnetLayerDims d = qnet_dims(net, l);
+      const int groups = d.mp / kQnetCols;
+      const bool first = l == 0, last = l == L - 1;
+      const auto dense = first ? (last ? ble_qnet_dense_kernel<true, false> : ble_qnet_dense_kernel<true, true>)
+                               : (last ? ble_qnet_dense_kernel<false, false> : ble_qnet_dense_kernel<false, true>);
+      const float* x = first ? (online ? bt->state : bt->next_state) : (online ? acts + (l - 1) * n * ld : tbuf[(l - 1) & 1]);
+      float* y = online ? acts + l * n * ld : (last ? ws + lay.target_logits : tbuf[l & 1]);
+      status = launch_grid(dense, dim3((unsigned)groups * row_tiles), kQnetBlock, stream, x, first ? bt->state_stride : ld, d.k, d.kp,
+                           wimg + d.offset, y, ld, groups, n);
+    }
+  }
+  if (status != BLE_OK) return status;
+  status = launch_grid(ble_qr_loss_kernel, dim3((unsigned)n), kTrainLossBlock, stream, acts + (L - 1) * n * ld,
+                       (const float*)(ws + lay.target_logits), ld, net->num_actions, net->num_atoms, (const float*)bt->ret,
+                       (const float*)bt->discount, (const uint8_t*)bt->action, tr->kappa, n, ws + lay.targets, ws + lay.dlogits, loss,
+                       err_flags);
+  // backward, from the last layer
+  const int slabs = (int)lay.slabs;
+  const int64_t slab_rows = slabs == 1 ? n : (n + slabs - 1) / slabs;
+  const float* dy = ws + lay.dlogits;
+  for (int l = L - 1; l >= 0 && status == BLE_OK; --l) {
+    const QnetLayerDims d = qnet_dims(net, l);
+    const int64_t blk = (int64_t)d.kp * d.mp + d.mp;
+    float* dst = slabs == 1 ? tr->grad + d.offset : ws + lay.partial;
+    const float* x = l == 0 ? bt->state : acts + (l - 1) * n * ld;
+    status = launch_grid(ble_qnet_wgrad_kernel, dim3((unsigned)((d.kp + 31) / 32), (unsigned)(d.mp / kQnetCols), (unsigned)slabs), 64, stream,
+                         x, l == 0 ? bt->state_stride : ld, d.k, d.kp, dy, ld, d.m, d.mp, n, slab_rows, dst, blk);
+    if (status == BLE_OK && slabs > 1)
+      status = launch(ble_wgrad_reduce_kernel, blk, 256, 256, stream, (const float*)(ws + lay.partial), slabs, blk, blk, tr->grad + d.offset);
+    if (status == BLE_OK && l > 0) {
+      const int kpt = (int)qnet_round_up(d.m, kQnetChunk), groups = dims.mp[l - 1] / kQnetCols;
+      float* dx = dyb[l & 1];
+      status = launch_grid(ble_qnet_dgrad_kernel, dim3((unsigned)groups * row_tiles), kQnetBlock, stream, dy, ld, kpt,
+                           (const float*)(tr->weights_t + dims.toffset[l]), (const float*)(acts + (l - 1) * n * ld), dx, groups, n);
+      dy = dx;
+    }
+  }
+  if (status != BLE_OK || !tr->apply_update) return status;
+  float* corr = ws + lay.corrections;
+  status = launch_grid(ble_adam_prologue_kernel, dim3(1), 1, stream, tr->adam_step, tr->adam_b1, tr->adam_b2, corr);
+  if (status != BLE_OK) return status;
+  return launch(ble_adam_kernel, dims.offset[L], kAdamBlock, kAdamBlock, stream, const_cast<float*>(net->weights),
+                tr->weights_t, (const float*)tr->grad, tr->adam_m, tr->adam_v, (const float*)corr, tr->lr, (float)tr->adam_b1,
+                (float)(1.0 - tr->adam_b1), (float)tr->adam_b2, (float)(1.0 - tr->adam_b2), tr->adam_eps, dims);
+}
+
+int ble_qnet_explore_u8(const ble_explore_f32* ex, uint8_t* action, void* stream) {
+  if (!ex || !action || ex->n < 0 || ex->n > 4LL * 2147483647LL * 256 || !(ex->epsilon >= 0.0f && ex->epsilon <= 1.0f)) return BLE_E_INVALID_ARG;
+  return launch(ble_explore_kernel, ex->n, 256, 256, stream, action, (int64_t)ex->n, ex->epsilon, (uint64_t)ex->seed, (uint64_t)ex->step);
 }
 
 int ble_eval_accumulate_f32(const ble_state_f32* st, const float* reward, const ble_eval_acc* acc, double radius_m, int step_index,

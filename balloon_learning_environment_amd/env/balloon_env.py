@@ -210,25 +210,35 @@ class VecBalloonEnv:
     call (non-finite state, pressure out of range, WindGP window overflow, failed pressure-range search...)."""
     self.arena.sim.check_errors()
 
-  def _step_eager(self, actions, obs_out=None):
+  def _step_eager(self, actions, obs_out=None, end_mask=None):
     noise = None
     if self._wind_noise:
       noise = self._noise if self._noise is not None else self._noise_now()     # step() before reset()
     reward, terminal = self.arena.step(actions, noise)
     if self._auto_reset:
       self._terminal_buf.copy_(terminal)
+      if end_mask is not None:
+        self._terminal_buf.bitwise_or_(end_mask)
       self.arena.reset_lanes(self._terminal_buf)
     return self.arena.observe(self._noise_now(), out=obs_out), reward, terminal
 
-  def step(self, actions):
+  def step(self, actions, end_mask=None):
     """actions: uint8 device tensor [N] in {0, 1, 2}.  Returns (obs [N, 1099], reward [N], terminal [N] u8);
     `terminal` refers to the transition just made; with auto_reset the returned observation of a
     terminated environment is the first one of its next episode.  With `capture_graph()` the three
     tensors are static buffers that the next step overwrites.  Error conditions are latched on the device:
-    call check_errors() (reset() does) to have them raised."""
+    call check_errors() (reset() does) to have them raised.
+    end_mask: optional uint8 device [N] (auto_reset, no captured graph): these environments' episodes end after this step
+    without a terminal (a time limit) and restart as a terminated one does."""
     if not hasattr(self, '_terminal_buf'):
       self._terminal_buf = torch.zeros(self.num_envs, dtype=torch.uint8, device=self.device)
-    if self._graph is not None:
+    if end_mask is not None:
+      if not self._auto_reset or self._graph is not None:
+        raise ValueError('step(end_mask=...) needs auto_reset and eager steps (no captured graph)')
+      assert end_mask.dtype == torch.uint8 and end_mask.numel() == self.num_envs
+      obs, reward, terminal = self._step_eager(actions, end_mask=end_mask)
+      out = obs, reward.clone(), terminal.clone()
+    elif self._graph is not None:
       self._g_actions.copy_(actions)
       self._graph.replay()
       out = self._g_obs, self._g_reward, self._g_terminal

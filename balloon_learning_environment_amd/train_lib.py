@@ -1,0 +1,90 @@
+"""The training loop of a device QR-DQN learner over a VecBalloonEnv: the reference's train_lib.run_training_loop with
+JaxQuantileAgent's schedule (min_replay_history, update_period, target_update_period counted in transitions), N environments per step.
+"""
+from typing import Callable, List, Optional, Union
+
+import torch
+
+from balloon_learning_environment_amd.agents import qnet_train
+
+WITHIN_RADIUS_REWARD = 0.5     # perciatelli_reward_function: 1.0 inside the radius, at most reward_dropoff = 0.4 outside
+
+
+def run_training_loop_vec(env, trainer: qnet_train.QNetworkTrainer, replay: qnet_train.VecReplayBuffer, *, num_iterations: int,
+                          steps_per_iteration: int, max_episode_length: int = 960, min_replay_history: int = 500,
+                          update_period: int = 4, target_update_period: int = 100,
+                          epsilon: Union[float, Callable[[int], float]] = 0.01, updates_per_step: Optional[int] = None,
+                          batch_size: int = 32, seed: int = 0, capture_graph: bool = True) -> List[dict]:
+  """Trains `trainer` on `env` (auto_reset) for num_iterations x steps_per_iteration vector steps.  Each step: the online network's
+  greedy actions, epsilon-greedy (ble_qnet_explore_u8, keyed by (seed, environment, step)), env.step, replay.add, then the updates.
+
+  Dopamine counts agent steps: one update per update_period transitions once min_replay_history transitions are held, and a target
+  sync every target_update_period transitions, i.e. every target_update_period / update_period updates.  Here a vector step adds N
+  transitions, so it runs N / update_period updates (the fraction carried over); updates_per_step overrides that count.  The
+  reference's 960-step episode limit is enforced per environment: a lane reaching it ends its episode (episode_end without terminal)
+  and restarts.  epsilon: a float or a function of the transitions added so far.
+
+  Returns one dict per iteration: mean_loss (over the iteration's updates), updates, episodes (finished), mean_return (of the finished
+  episodes), time_within_radius (the fraction of the iteration's transitions with reward > 0.5, i.e. inside the radius), transitions."""
+  n, dev_ = env.num_envs, env.device
+  assert replay.num_envs == n, 'the replay ring has one column per environment'
+  sync_every = max(1, target_update_period // update_period)
+  obs = env.reset()
+  actions = torch.zeros(n, dtype=torch.uint8, device=dev_)
+  ep_steps = torch.zeros(n, dtype=torch.int32, device=dev_)
+  ep_return = torch.zeros(n, dtype=torch.float32, device=dev_)
+  transitions, updates, pending, step = 0, 0, 0.0, 0
+  captured = False
+  stats = []
+  for _ in range(num_iterations):
+    loss_sum = torch.zeros((), dtype=torch.float32, device=dev_)
+    done_returns = torch.zeros((), dtype=torch.float32, device=dev_)
+    episodes = torch.zeros((), dtype=torch.int64, device=dev_)
+    within = torch.zeros((), dtype=torch.int64, device=dev_)
+    it_updates = 0
+    for _ in range(steps_per_iteration):
+      trainer.act(obs, actions)
+      eps = epsilon(transitions) if callable(epsilon) else epsilon
+      qnet_train.explore(actions, eps, seed, step)
+      end_mask = (ep_steps + 1 >= max_episode_length).to(torch.uint8)
+      next_obs, reward, terminal = env.step(actions, end_mask=end_mask)
+      episode_end = terminal | end_mask
+      replay.add(obs, actions, reward, terminal, episode_end)
+      ep_return += reward
+      ep_steps += 1
+      ended = episode_end.bool()
+      episodes += ended.sum()
+      done_returns += torch.where(ended, ep_return, torch.zeros_like(ep_return)).sum()
+      ep_return.masked_fill_(ended, 0.0)
+      ep_steps.masked_fill_(ended, 0)
+      within += (reward > WITHIN_RADIUS_REWARD).sum()
+      obs = next_obs
+      transitions += n
+      step += 1
+      if transitions >= min_replay_history and replay.cursor > replay.update_horizon:
+        if updates_per_step is not None:
+          todo = int(updates_per_step)
+        else:
+          pending += n / update_period
+          todo = int(pending)
+          pending -= todo
+        for _ in range(todo):
+          if capture_graph and not captured:
+            trainer.capture(replay, batch_size)        # (its first, eager update is a real one)
+            captured = True
+            loss = trainer.views(batch_size)['loss']
+          else:
+            loss = trainer.train_step(replay, batch_size)
+          loss_sum += loss.mean()
+          updates += 1
+          it_updates += 1
+          if updates % sync_every == 0:
+            trainer.sync_target()
+    env.check_errors()
+    replay.check_errors()
+    trainer.check_errors()
+    ne = int(episodes.item())
+    stats.append({'mean_loss': float(loss_sum.item()) / max(it_updates, 1), 'updates': it_updates, 'episodes': ne,
+                  'mean_return': float(done_returns.item()) / ne if ne else float('nan'),
+                  'time_within_radius': float(within.item()) / (n * steps_per_iteration), 'transitions': transitions})
+  return stats

@@ -608,6 +608,127 @@ int ble_qnet_pack_f32(const ble_qnet_f32* net, const float* const* kernel, const
 int ble_qnet_forward_f32(const ble_qnet_f32* net, const float* obs, int64_t obs_row_stride, float* scratch, uint8_t* action,
                          float* q_values, int64_t n, void* stream);
 
+/*
+ * Q-network training (additive to ABI 5): Dopamine 4.0.0's JaxQuantileAgent update -- uniform n-step replay, the QR-DQN target and
+ * quantile Huber loss, backprop through the Dense stack, optax 0.0.9 Adam -- on the device.  fp32 data, fp32 accumulation, no
+ * floating-point atomics: every reduction has one order fixed by the shapes, so an update is a pure function of (parameters, replay,
+ * seeds, counters).  Sizes and counts travel inside the descriptors below (no int64_t argument).
+ */
+#define BLE_FLAG_REPLAY_EMPTY 2048u  /* ble_replay_sample_f32: no valid n-step window in max_tries draws -- the row is all zeros,
+                                        discount 0, index (-1, -1) */
+#define BLE_FLAG_TRAIN_ACTION 4096u  /* ble_qnet_train_step_f32: a batch action >= num_actions -- the row's loss and gradient are 0 */
+#define BLE_REPLAY_MAX_HORIZON 64
+#define BLE_REPLAY_MAX_TRIES 1024
+#define BLE_TRAIN_MAX_BATCH 1048576
+
+/* HOST: the inverse of ble_qnet_pack_f32 -- kernel[l] row-major [in][out] and bias[l] [out] (host) from the host image packed. */
+int ble_qnet_unpack_f32(const ble_qnet_f32* net, const float* packed, float* const* kernel, float* const* bias);
+
+/*
+ * The replay ring of N environments stepped in lockstep: row s % capacity holds step s of every environment.  Steps
+ * max(0, count - capacity) .. count - 1 are held.  obs[s] is the observation action[s] was taken on; reward[s], terminal[s] and
+ * episode_end[s] (!= 0: the episode ended at this step, by a terminal or by the time limit) describe the transition.  With auto
+ * reset obs[s + 1] after an episode end is the first observation of the next episode.
+ */
+typedef struct ble_replay_f32 {
+  int64_t capacity;          /* T >= update_horizon + 1 */
+  int64_t num_envs;          /* N >= 1 */
+  int32_t update_horizon;    /* n, 1 .. BLE_REPLAY_MAX_HORIZON */
+  int32_t obs_stride;        /* floats per stored observation, >= BLE_OBS_DIM, a multiple of 4; columns past BLE_OBS_DIM not read */
+  double gamma;              /* finite; gamma^k is the float32 rounding of the float64 power, as Dopamine's table */
+  int32_t max_tries;         /* draws per batch row before BLE_FLAG_REPLAY_EMPTY, 1 .. BLE_REPLAY_MAX_TRIES */
+  int32_t reserved_;         /* 0 */
+  const float* obs;          /* device [T][N][obs_stride], 16-byte aligned */
+  const uint8_t* action;     /* device [T][N] */
+  const float* reward;       /* device [T][N] */
+  const uint8_t* terminal;   /* device [T][N] */
+  const uint8_t* episode_end;/* device [T][N] */
+  const int64_t* count;      /* device: steps written */
+  unsigned long long* counter; /* device: the update counter; each sample call draws with it, then advances it by one */
+} ble_replay_f32;
+
+/* One batch of B transitions (what ble_replay_sample_f32 writes and ble_qnet_train_step_f32 reads). */
+typedef struct ble_train_batch_f32 {
+  int64_t batch;             /* B, 0 .. BLE_TRAIN_MAX_BATCH */
+  int64_t state_stride;      /* floats per state row, >= BLE_OBS_DIM, a multiple of 4; the sampler zero-fills columns >= BLE_OBS_DIM */
+  float* state;              /* device [B][state_stride], 16-byte aligned */
+  float* next_state;         /* device [B][state_stride], 16-byte aligned */
+  float* ret;                /* device [B]: sum_{k<m} gamma^k r_{t+k} */
+  float* discount;           /* device [B]: gamma^n, 0 if a terminal ends the window */
+  uint8_t* action;           /* device [B] */
+  int64_t* index;            /* optional device [B][2]: the sampled (t, env) */
+} ble_train_batch_f32;
+
+/*
+ * ble_replay_sample_f32: B uniform draws of (t, env) from the Philox stream keyed by (seed, batch row, *counter), each redrawn until
+ * its window is valid (at most max_tries draws).  A window is valid when steps t .. t + n are held and, among t .. t + n - 1, no
+ * episode end comes before the first terminal (a time-limit end without a terminal invalidates it).  m = n, or 1 + the position of the
+ * first terminal.  state = obs[t], next_state = obs[t + m] (Dopamine's next_state_index), ret and discount as above.  Two launches
+ * (the draw and gather, then the counter's advance).
+ */
+int ble_replay_sample_f32(const ble_replay_f32* replay, const ble_train_batch_f32* batch, unsigned long long seed, uint32_t* err_flags,
+                          void* stream);
+
+/*
+ * The trainer: the online image net.weights (updated in place), the target image, the gradient, Adam's m and v (all of
+ * ble_qnet_workspace_f32's packed_floats, device, 16-byte aligned, the padding of every one zero), weights_t (the transposed image of
+ * layers 1 .. L-1 that dX = dY W^T reads: ble_qnet_transpose_f32 makes it, the update rewrites it), adam_step (device: the step count,
+ * advanced before each update) and the workspace (ble_qnet_train_workspace_f32's layout).
+ */
+typedef struct ble_qnet_train_f32 {
+  ble_qnet_f32 net;
+  const float* target;
+  float* weights_t;
+  float* grad;
+  float* adam_m;
+  float* adam_v;
+  unsigned long long* adam_step;
+  float* workspace;
+  double adam_b1, adam_b2;                 /* optax.adam(lr, b1, b2, eps, eps_root=0): 1 - b and 1 - b^t are float64, rounded to float32 */
+  float lr, adam_eps;
+  float kappa;                             /* Huber threshold, > 0 */
+  int32_t apply_update;                    /* 0: the gradient only (weights, weights_t, m, v and adam_step untouched) */
+} ble_qnet_train_f32;
+
+/* Offsets (floats from tr->workspace) of the workspace of a batch of B rows. */
+typedef struct ble_qnet_train_layout {
+  int64_t ld;                /* floats per activation row (the widest padded layer) */
+  int64_t acts;              /* [L][B][ld]: every online layer's output (ReLU applied but on the last: the logits) */
+  int64_t target_logits;     /* [B][ld]: the target network's logits on next_state */
+  int64_t targets;           /* [B][num_atoms]: T_j = ret + discount * z_target(s')[a*, j] */
+  int64_t dlogits;           /* [B][ld]: dL/dlogits of the objective mean_b L_b (zero off the batch action's atoms) */
+  int64_t scratch;           /* the target ping-pong and the backward dY ping-pong */
+  int64_t partial;           /* [slabs][largest layer block]: dW / db partial sums of batch slabs, combined in slab order */
+  int64_t slabs;             /* batch slabs of the dW reduction (a function of B alone) */
+  int64_t corrections;       /* [4]: 1 - b1^t, 1 - b2^t of the current Adam step */
+  int64_t total;             /* floats of the whole workspace */
+  int64_t transposed_floats; /* floats of weights_t */
+} ble_qnet_train_layout;
+
+int ble_qnet_train_workspace_f32(const ble_qnet_train_f32* tr, const ble_train_batch_f32* batch, ble_qnet_train_layout* layout);
+
+/* HOST: weights_t from a host image packed (ble_qnet_train_workspace_f32's transposed_floats floats). */
+int ble_qnet_transpose_f32(const ble_qnet_f32* net, const float* packed, float* packed_t);
+
+/*
+ * ble_qnet_train_step_f32: one QR-DQN update on batch: the target forward on next_state, the online forward on state
+ * (the eval forward's instructions: the same logits' bits), the loss and dL/dlogits, dW / db into grad (the packed layout) and dX
+ * layer by layer, then Adam on every packed element (apply_update != 0).  loss: device float32 [B], the per-row loss L_b.
+ */
+int ble_qnet_train_step_f32(const ble_qnet_train_f32* tr, const ble_train_batch_f32* batch, float* loss, uint32_t* err_flags, void* stream);
+
+/* epsilon-greedy: action[i] (the greedy action in, the taken action out) becomes uniform in {0, 1, 2} when a uniform u < epsilon; u and
+ * the random action come from the Philox stream keyed by (seed, i, step). */
+typedef struct ble_explore_f32 {
+  int64_t n;
+  float epsilon;             /* 0 .. 1 */
+  int32_t reserved_;         /* 0 */
+  unsigned long long seed;
+  unsigned long long step;
+} ble_explore_f32;
+
+int ble_qnet_explore_u8(const ble_explore_f32* ex, uint8_t* action, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
