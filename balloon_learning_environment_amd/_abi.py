@@ -171,3 +171,16 @@ class BleExploreF32(ctypes.Structure):
   """struct ble_explore_f32: epsilon-greedy over n actions, keyed by (seed, env, step)."""
   _fields_ = [('n', ctypes.c_int64), ('epsilon', ctypes.c_float), ('reserved_', ctypes.c_int32), ('seed', ctypes.c_uint64),
               ('step', ctypes.c_uint64)]
+
+
+class BleSumTreeF64(ctypes.Structure):
+  """struct ble_sum_tree_f64: the prioritized replay's fp64 sum tree (device pointers) and its sizes."""
+  _fields_ = [('leaves', ctypes.c_int64), ('padded', ctypes.c_int64), ('nodes', ctypes.c_void_p), ('max_priority', ctypes.c_void_p)]
+
+
+class BleMarcoPoloF32(ctypes.Structure):
+  """struct ble_marco_polo_f32: Marco Polo exploration over n environments (device pointers)."""
+  _fields_ = [('n', ctypes.c_int64), ('obs_stride', ctypes.c_int32), ('reserved_', ctypes.c_int32),
+              ('exploratory_episode_probability', ctypes.c_double), ('seed', ctypes.c_uint64), ('obs', ctypes.c_void_p),
+              ('begin', ctypes.c_void_p), ('step', ctypes.c_void_p), ('phase_clock', ctypes.c_void_p), ('walk_clock', ctypes.c_void_p),
+              ('exploratory_episode', ctypes.c_void_p), ('exploratory_phase', ctypes.c_void_p), ('target', ctypes.c_void_p)]

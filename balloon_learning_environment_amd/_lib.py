@@ -20,7 +20,7 @@ _PKG_DIR = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get('BLE_HIP_LIB') or os.path.join(_PKG_DIR, 'libble_hip.so')   # override: experiments only
 _SOURCES = [os.path.join(_PKG_DIR, 'csrc', f) for f in ('ble_kernels.hip', 'ble_step_core.h', 'ble_physics.h', 'ble_intrinsics.h', 'ble_reset.h',
                                                           'ble_observe.h', 'ble_noise.h', 'ble_decode.h', 'ble_step_split.h', 'ble_agent.h', 'ble_qnet.h',
-                                                          'ble_train.h')]
+                                                          'ble_train.h', 'ble_replay.h')]
 _HEADER = os.path.join(os.path.dirname(_PKG_DIR), 'include', 'ble_abi.h')
 
 ABI_VERSION = 5
@@ -31,6 +31,7 @@ FLAG_GP_WINDOW, FLAG_PRESSURE_SEARCH, FLAG_DAY_CYCLE = 64, 128, 256
 FLAG_VEHICLE_INDEX = 512
 FLAG_AGENT_NO_LEVEL = 1024
 FLAG_REPLAY_EMPTY, FLAG_TRAIN_ACTION = 2048, 4096
+FLAG_REPLAY_PRIORITY = 8192
 SEEKER_LEVELS = 361
 OBS_DIM, GP_CAPACITY, GP_CHOL_STRIDE = 1099, 128, 7620
 ROW_DOUBLES = 26        # BLE_ROW_DOUBLES
@@ -44,7 +45,8 @@ EXPORTS = ('ble_abi_version', 'ble_noise_primitive_version', 'ble_vehicle_defaul
            'ble_station_seeker_f32', 'ble_eval_accumulate_f32', 'ble_reset_seeded_f32', 'ble_wind_noise_seeded_f32',
            'ble_observe_live_f32', 'ble_qnet_workspace_f32', 'ble_qnet_pack_f32', 'ble_qnet_forward_f32',
            'ble_qnet_unpack_f32', 'ble_replay_sample_f32', 'ble_qnet_train_workspace_f32', 'ble_qnet_transpose_f32',
-           'ble_qnet_train_step_f32', 'ble_qnet_explore_u8')
+           'ble_qnet_train_step_f32', 'ble_qnet_explore_u8',
+           'ble_replay_tree_add_f64', 'ble_replay_sample_prioritized_f32', 'ble_replay_set_priority_f32', 'ble_marco_polo_u8')
 
 
 class BleLibraryError(RuntimeError):
@@ -149,6 +151,12 @@ def lib():
   l.ble_qnet_transpose_f32.argtypes = [qnet, _vp, _vp]
   l.ble_qnet_train_step_f32.argtypes = [train, batch, _vp, _vp, _vp]
   l.ble_qnet_explore_u8.argtypes = [ctypes.POINTER(_abi.BleExploreF32), _vp, _vp]
+  # prioritized replay and Marco Polo exploration (sizes in descriptors, as above)
+  replay, tree = ctypes.POINTER(_abi.BleReplayF32), ctypes.POINTER(_abi.BleSumTreeF64)
+  l.ble_replay_tree_add_f64.argtypes = [replay, tree, _vp]
+  l.ble_replay_sample_prioritized_f32.argtypes = [replay, tree, batch, _vp, ctypes.c_uint64, _vp, _vp]
+  l.ble_replay_set_priority_f32.argtypes = [replay, tree, batch, _vp, _vp, _vp, _vp, _vp]
+  l.ble_marco_polo_u8.argtypes = [ctypes.POINTER(_abi.BleMarcoPoloF32), _vp, _vp]
   for name in EXPORTS:
     getattr(l, name).restype = _int
   _lib = l

@@ -1,0 +1,61 @@
+"""Marco Polo exploration on the device: the reference's MarcoPoloExploration over a RandomWalkAgent (configs/quantile.gin), one lane
+per environment of a VecBalloonEnv (ble_marco_polo_u8, csrc/ble_train.h).
+
+An episode is exploratory with probability exploratory_episode_probability.  It starts in the RL phase (the agent's actions), and an
+exploratory episode alternates 4 h of RL with 2 h of a random walk in pressure: a target drawn in [6500, 11400) Pa at the episode's
+begin drifts by (seconds walked) x 0.1666 x N(0, 1) per exploratory step, and the balloon goes UP / DOWN / STAY with 100 Pa of
+hysteresis around it.  The draws come from Philox keyed by (seed, environment, step), not from JAX's stream.
+"""
+import ctypes
+
+import torch
+
+from balloon_learning_environment_amd import _abi
+from balloon_learning_environment_amd import _lib
+from balloon_learning_environment_amd import device as dev
+
+
+class VecMarcoPoloExploration:
+  """explorer(obs, actions, begin) rewrites the uint8 device actions in place: begin (uint8 [N], nonzero where obs is an episode's
+  first observation) runs begin_episode on those lanes, every other lane steps.  No host synchronisation: capturable in a graph (the
+  step counter that keys the draws is device memory)."""
+
+  def __init__(self, num_envs: int, exploratory_episode_probability: float = 0.8, seed: int = 0, device='cuda:0'):
+    self.device = dev.require_gpu(device)
+    self.num_envs, self.probability, self.seed = int(num_envs), float(exploratory_episode_probability), int(seed)
+    if not 0.0 <= self.probability <= 1.0:
+      raise ValueError('exploratory_episode_probability must be in [0, 1]')
+    n, d = self.num_envs, self.device
+    with torch.cuda.device(d):
+      self.step = torch.zeros(1, dtype=torch.int64, device=d)          # (read as uint64 by the kernel)
+      self.phase_clock = torch.zeros(n, dtype=torch.int32, device=d)
+      self.walk_clock = torch.zeros(n, dtype=torch.int32, device=d)
+      self.exploratory_episode = torch.zeros(n, dtype=torch.uint8, device=d)
+      self.exploratory_phase = torch.zeros(n, dtype=torch.uint8, device=d)
+      self.target = torch.zeros(n, dtype=torch.float64, device=d)
+    self.lib = _lib.lib()
+
+  @dev.on_own_device
+  def __call__(self, obs: torch.Tensor, actions: torch.Tensor, begin: torch.Tensor) -> torch.Tensor:
+    n = self.num_envs
+    assert obs.shape[0] == n and actions.numel() == n and begin.numel() == n, 'one lane per environment'
+    assert obs.dtype == torch.float32 and actions.dtype == torch.uint8 and begin.dtype == torch.uint8
+    stride = obs.stride(0) if obs.dim() > 1 else 1
+    mp = _abi.BleMarcoPoloF32(n, stride, 0, self.probability, self.seed & (2 ** 64 - 1), obs.data_ptr(), begin.data_ptr(),
+                              self.step.data_ptr(), self.phase_clock.data_ptr(), self.walk_clock.data_ptr(),
+                              self.exploratory_episode.data_ptr(), self.exploratory_phase.data_ptr(), self.target.data_ptr())
+    _lib.check(self.lib.ble_marco_polo_u8(ctypes.byref(mp), actions.data_ptr(), dev.stream_ptr(self.device)), 'ble_marco_polo_u8')
+    return actions
+
+  _STATE = ('step', 'phase_clock', 'walk_clock', 'exploratory_episode', 'exploratory_phase', 'target')
+
+  def state_dict(self) -> dict:
+    return {'num_envs': self.num_envs, 'probability': self.probability, 'seed': self.seed,
+            **{k: getattr(self, k).clone() for k in self._STATE}}
+
+  def load_state_dict(self, d: dict) -> None:
+    """Restores in place (tensors keep their addresses)."""
+    assert int(d['num_envs']) == self.num_envs
+    self.probability, self.seed = float(d['probability']), int(d['seed'])
+    for k in self._STATE:
+      getattr(self, k).copy_(d[k])

@@ -32,6 +32,8 @@ def _check_flags(flags: torch.Tensor) -> None:
     raise RuntimeError('replay: no valid n-step window to sample (too few steps written, or every window crosses a time-limit end)')
   if f & _lib.FLAG_TRAIN_ACTION:
     raise ValueError('train step: a batch action is not below num_actions')
+  if f & _lib.FLAG_REPLAY_PRIORITY:
+    raise ValueError('set_priority: a non-finite or negative loss (its leaf was left unchanged)')
 
 
 class TrainBatch:
@@ -145,6 +147,80 @@ class VecReplayBuffer:
     self.count.fill_(self.cursor)
 
 
+
+class VecPrioritizedReplayBuffer(VecReplayBuffer):
+  """VecReplayBuffer with Dopamine's prioritized replay (configs/quantile.gin's OutOfGraphPrioritizedReplayBuffer), DESIGN §3g.
+
+  An fp64 sum tree over capacity_steps x num_envs leaves (one per n-step window).  add() also enters the windows that have just become
+  complete at the max recorded priority (ble_replay_tree_add_f64); sample() draws stratified by priority and the batch carries each
+  row's priority (batch.priority); set_priority(batch, loss) sets leaf = sqrt(loss + 1e-10) and returns the importance-weighted
+  per-row losses Dopamine reports (the gradient itself is not weighted)."""
+
+  prioritized = True
+
+  def __init__(self, num_envs: int, capacity_steps: int, update_horizon: int = 5, gamma: float = 0.993, device='cuda:0'):
+    super().__init__(num_envs, capacity_steps, update_horizon, gamma, device)
+    leaves = self.capacity * self.num_envs
+    if leaves > 2 ** 31:
+      raise ValueError('capacity_steps x num_envs must be at most 2^31')
+    self.padded = 1 << (leaves - 1).bit_length()
+    with torch.cuda.device(self.device):
+      self.tree = torch.zeros(2 * self.padded, dtype=torch.float64, device=self.device)
+      self.max_priority = torch.ones(1, dtype=torch.float64, device=self.device)
+    self._tree = _abi.BleSumTreeF64(leaves, self.padded, self.tree.data_ptr(), self.max_priority.data_ptr())
+    self._weighted: Dict[int, torch.Tensor] = {}
+
+  def leaf_priorities(self) -> torch.Tensor:
+    """The leaves as [capacity_steps, num_envs] (a view)."""
+    return self.tree[self.padded:self.padded + self.capacity * self.num_envs].view(self.capacity, self.num_envs)
+
+  @dev.on_own_device
+  def add(self, obs, action, reward, terminal, episode_end=None) -> None:
+    super().add(obs, action, reward, terminal, episode_end)
+    rp = self.struct(self.counter)
+    _lib.check(self.lib.ble_replay_tree_add_f64(ctypes.byref(rp), ctypes.byref(self._tree), dev.stream_ptr(self.device)),
+               'ble_replay_tree_add_f64')
+
+  def batch_buffers(self, batch_size: int) -> TrainBatch:
+    bt = super().batch_buffers(batch_size)
+    if not hasattr(bt, 'priority'):
+      bt.priority = torch.zeros(max(batch_size, 1), dtype=torch.float32, device=self.device)[:batch_size]
+      self._weighted[batch_size] = torch.zeros(max(batch_size, 1), dtype=torch.float32, device=self.device)
+    return bt
+
+  @dev.on_own_device
+  def sample(self, batch_size: int, seed: int, counter: Optional[torch.Tensor] = None) -> TrainBatch:
+    """B stratified prioritized draws (ble_replay_sample_prioritized_f32) into this size's batch buffers; batch.priority [B] holds
+    each row's leaf (fp32)."""
+    bt = self.batch_buffers(int(batch_size))
+    rp = self.struct(self.counter if counter is None else counter)
+    _lib.check(self.lib.ble_replay_sample_prioritized_f32(ctypes.byref(rp), ctypes.byref(self._tree), ctypes.byref(bt.struct),
+                                                          bt.priority.data_ptr(), int(seed) & (2 ** 64 - 1), self.err_flags.data_ptr(),
+                                                          dev.stream_ptr(self.device)), 'ble_replay_sample_prioritized_f32')
+    return bt
+
+  @dev.on_own_device
+  def set_priority(self, batch: TrainBatch, loss: torch.Tensor) -> torch.Tensor:
+    """Leaves of the batch's rows = sqrt(loss + 1e-10) (ble_replay_set_priority_f32); returns the weighted per-row losses [B] (a
+    buffer the next call at this size overwrites)."""
+    b = batch.batch_size
+    out = self._weighted[b]
+    rp = self.struct(self.counter)
+    _lib.check(self.lib.ble_replay_set_priority_f32(ctypes.byref(rp), ctypes.byref(self._tree), ctypes.byref(batch.struct),
+                                                    batch.priority.data_ptr(), loss.data_ptr(), out.data_ptr(), self.err_flags.data_ptr(),
+                                                    dev.stream_ptr(self.device)), 'ble_replay_set_priority_f32')
+    return out[:b]
+
+  def state_dict(self) -> dict:
+    d = super().state_dict()
+    d['tree'], d['max_priority'] = self.tree.clone(), self.max_priority.clone()
+    return d
+
+  def load_state_dict(self, d: dict) -> None:
+    super().load_state_dict(d)
+    self.tree.copy_(d['tree'])
+    self.max_priority.copy_(d['max_priority'])
+
 class QNetworkTrainer:
   """QR-DQN training of a QNetwork's parameters on its device (defaults: configs/quantile.gin -- Adam lr 2e-6, eps 2e-5, gamma 0.993,
   update horizon 5, kappa 1).
@@ -240,28 +316,36 @@ class QNetworkTrainer:
   @dev.on_own_device
   def train_step(self, replay: VecReplayBuffer, batch_size: int = 32) -> torch.Tensor:
     """Sample a batch (keyed by (seed, update counter)) and update: per-row losses [B] on the device, no host synchronisation.  A
-    captured graph of this batch size (capture()) replays it."""
+    captured graph of this batch size (capture()) replays it.  With a VecPrioritizedReplayBuffer the update is followed by
+    set_priority and the losses returned are the importance-weighted ones (Dopamine's reported QuantileLoss)."""
     g = self._graphs.get(batch_size)
     if g is not None and g[1] is replay:
       g[0].replay()
       return g[2]
-    batch = replay.sample(batch_size, self.seed, self.counter)
-    return self.train_on_batch(batch)
+    return self._update(replay, batch_size)
 
-  def capture(self, replay: VecReplayBuffer, batch_size: int = 32) -> None:
-    """Records one update (sample + train step) into a HIP graph that train_step(replay, batch_size) replays from then on: the
-    counters are device memory, so each replay draws a new batch and takes a new Adam step.  Runs one eager update first (the lazy
-    allocations) -- that is a real update."""
-    self.train_step(replay, batch_size)
+  def _update(self, replay: VecReplayBuffer, batch_size: int) -> torch.Tensor:
+    batch = replay.sample(batch_size, self.seed, self.counter)
+    loss = self.train_on_batch(batch)
+    if getattr(replay, 'prioritized', False):       # sample -> update -> set_priority; the reported loss is the weighted one
+      return replay.set_priority(batch, loss)
+    return loss
+
+  def capture(self, replay: VecReplayBuffer, batch_size: int = 32) -> torch.Tensor:
+    """Records one update (sample + train step, + set_priority with a VecPrioritizedReplayBuffer) into a HIP graph that
+    train_step(replay, batch_size) replays from then on: the counters are device memory, so each replay draws a new batch and takes a
+    new Adam step.  Runs one eager update first (the lazy allocations) -- that is a real update; returns its per-row losses."""
+    first = self.train_step(replay, batch_size)
     d = self.device
     side = torch.cuda.Stream(device=d)
     side.wait_stream(torch.cuda.current_stream(d))
     graph = torch.cuda.CUDAGraph()
     with torch.cuda.stream(side):
       with torch.cuda.graph(graph, stream=side):
-        loss = self.train_on_batch(replay.sample(batch_size, self.seed, self.counter))
+        loss = self._update(replay, batch_size)
     torch.cuda.current_stream(d).wait_stream(side)
     self._graphs[batch_size] = (graph, replay, loss)
+    return first
 
   def sync_target(self) -> None:
     self.target.copy_(self.weights)

@@ -38,6 +38,7 @@
 #include "ble_agent.h"
 #include "ble_qnet.h"
 #include "ble_train.h"
+#include "ble_replay.h"
 
 using namespace ble;
 
@@ -1391,6 +1392,50 @@ int ble_qnet_train_step_f32(const ble_qnet_train_f32* tr, const ble_train_batch_
 int ble_qnet_explore_u8(const ble_explore_f32* ex, uint8_t* action, void* stream) {
   if (!ex || !action || ex->n < 0 || ex->n > 4LL * 2147483647LL * 256 || !(ex->epsilon >= 0.0f && ex->epsilon <= 1.0f)) return BLE_E_INVALID_ARG;
   return launch(ble_explore_kernel, ex->n, 256, 256, stream, action, (int64_t)ex->n, ex->epsilon, (uint64_t)ex->seed, (uint64_t)ex->step);
+}
+
+// ---------------------------------------------------------------------------------------------------------------- prioritized replay
+namespace {
+bool tree_ok(const ble_replay_f32* rp, const ble_sum_tree_f64* tr) {
+  return tr != nullptr && tr->leaves == rp->capacity * rp->num_envs && tr->leaves <= BLE_SUM_TREE_MAX_LEAVES && tr->padded >= tr->leaves &&
+         (tr->padded & (tr->padded - 1)) == 0 && (tr->padded == 1 || tr->padded / 2 < tr->leaves) && tr->nodes && tr->max_priority &&
+         ((reinterpret_cast<uintptr_t>(tr->nodes) | reinterpret_cast<uintptr_t>(tr->max_priority)) & 7) == 0;
+}
+}  // namespace
+
+int ble_replay_tree_add_f64(const ble_replay_f32* rp, const ble_sum_tree_f64* tr, void* stream) {
+  if (!replay_ok(rp) || !tree_ok(rp, tr)) return BLE_E_INVALID_ARG;
+  return launch_grid(ble_tree_add_kernel, dim3(1), kTreeBlock, stream, *rp, *tr);
+}
+
+int ble_replay_sample_prioritized_f32(const ble_replay_f32* rp, const ble_sum_tree_f64* tr, const ble_train_batch_f32* bt, float* priority,
+                                      unsigned long long seed, uint32_t* err_flags, void* stream) {
+  if (!replay_ok(rp) || !tree_ok(rp, tr) || !batch_ok(bt) || !bt->index || !priority) return BLE_E_INVALID_ARG;
+  if (bt->batch == 0) return BLE_OK;
+  const int status = launch_grid(ble_replay_sample_prio_kernel, dim3((unsigned)bt->batch), kReplayBlock, stream, *rp, *tr, *bt, priority,
+                                 (uint64_t)seed, err_flags);
+  if (status != BLE_OK) return status;
+  return launch_grid(ble_train_advance_kernel, dim3(1), 1, stream, rp->counter);
+}
+
+int ble_replay_set_priority_f32(const ble_replay_f32* rp, const ble_sum_tree_f64* tr, const ble_train_batch_f32* bt, const float* priority,
+                                const float* loss, float* weighted_loss, uint32_t* err_flags, void* stream) {
+  if (!replay_ok(rp) || !tree_ok(rp, tr) || !batch_ok(bt) || !bt->index || !priority || !loss || !weighted_loss) return BLE_E_INVALID_ARG;
+  if (bt->batch == 0) return BLE_OK;
+  return launch_grid(ble_set_priority_kernel, dim3(1), kTreeBlock, stream, (int64_t)rp->capacity, (int64_t)rp->num_envs, *tr,
+                     (const int64_t*)bt->index, (int64_t)bt->batch, priority, loss, weighted_loss, err_flags);
+}
+
+int ble_marco_polo_u8(const ble_marco_polo_f32* mp, uint8_t* action, void* stream) {
+  if (!mp || !action || mp->n < 0 || mp->n > 4LL * 2147483647LL * 256 || mp->obs_stride < 1 ||
+      !(mp->exploratory_episode_probability >= 0.0 && mp->exploratory_episode_probability <= 1.0) || !mp->obs || !mp->begin || !mp->step ||
+      !mp->phase_clock || !mp->walk_clock || !mp->exploratory_episode || !mp->exploratory_phase || !mp->target ||
+      (reinterpret_cast<uintptr_t>(mp->target) & 7) != 0)
+    return BLE_E_INVALID_ARG;
+  if (mp->n == 0) return BLE_OK;
+  const int status = launch(ble_marco_polo_kernel, mp->n, 256, 256, stream, *mp, action);
+  if (status != BLE_OK) return status;
+  return launch_grid(ble_train_advance_kernel, dim3(1), 1, stream, mp->step);
 }
 
 int ble_eval_accumulate_f32(const ble_state_f32* st, const float* reward, const ble_eval_acc* acc, double radius_m, int step_index,

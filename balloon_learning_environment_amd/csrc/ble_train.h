@@ -36,61 +36,48 @@ inline int wgrad_slabs(int64_t b) {
 }
 
 // ------------------------------------------------------------------------------------------------------------ replay sampling
-// One workgroup per batch row: lane 0 draws (t, env) until the window is valid, then the workgroup gathers obs[t] and obs[t + m].
-__global__ __launch_bounds__(kReplayBlock) void ble_replay_sample_kernel(ble_replay_f32 rp, ble_train_batch_f32 bt, uint64_t seed,
-                                                                        uint32_t* __restrict__ err_flags) {
-  __shared__ int64_t s_t, s_env;
-  __shared__ int s_m;
-  const int64_t b = blockIdx.x;
-  if (threadIdx.x == 0) {
-    const int64_t count = *rp.count;
-    const uint64_t counter = *rp.counter;
-    const int64_t lo = count > rp.capacity ? count - rp.capacity : 0;
-    const int64_t span = count - rp.update_horizon - lo;            // candidates t: t + n <= count - 1
-    Philox g = philox_init(seed, (uint64_t)b, (uint32_t)counter);
-    g.c3 = (uint32_t)(counter >> 32);                                // (b < 2^32: the env key's high word is free)
-    int64_t t = -1, env = -1;
-    int m = 0, term = 0;
-    for (int tries = 0; span > 0 && tries < rp.max_tries; ++tries) {
-      const uint64_t hi = philox_u32(g), lo32 = philox_u32(g), e32 = philox_u32(g);
-      const int64_t tt = lo + (int64_t)__umul64hi((hi << 32) | lo32, (uint64_t)span);
-      const int64_t ee = (int64_t)(((uint64_t)e32 * (uint64_t)rp.num_envs) >> 32);
-      int mm = rp.update_horizon, tm = 0;
-      bool ok = true;
-      for (int k = 0; k < rp.update_horizon; ++k) {
-        const int64_t at = ((tt + k) % rp.capacity) * rp.num_envs + ee;
-        if (rp.terminal[at]) { mm = k + 1; tm = 1; break; }
-        if (rp.episode_end[at]) { ok = false; break; }                 // a time-limit end without a terminal
-      }
-      if (ok) { t = tt; env = ee; m = mm; term = tm; break; }
-    }
-    float ret = 0.0f, disc = 0.0f;
-    uint8_t act = 0;
-    if (t < 0) {
-      if (err_flags != nullptr) atomicOr(err_flags, kFlagReplayEmpty);
-    } else {
-      for (int k = 0; k < m; ++k) {                                    // Dopamine: np.sum(float32 gamma^k table * rewards), k ascending
-        const float gk = (float)pow(rp.gamma, (double)k);
-        ret = __fadd_rn(ret, __fmul_rn(gk, rp.reward[((t + k) % rp.capacity) * rp.num_envs + env]));   // (rounded apart: no fma)
-      }
-      disc = term ? 0.0f : (float)pow(rp.gamma, (double)rp.update_horizon);
-      act = rp.action[(t % rp.capacity) * rp.num_envs + env];
-    }
-    bt.ret[b] = ret;
-    bt.discount[b] = disc;
-    bt.action[b] = act;
-    if (bt.index != nullptr) { bt.index[2 * b] = t; bt.index[2 * b + 1] = env; }
-    s_t = t; s_env = env; s_m = m;
+// The n-step window that starts at step t of environment env: valid when, among t .. t + n - 1, no episode end comes before the first
+// terminal (a time-limit end without a terminal invalidates it); m = n, or 1 + the position of the first terminal (term = 1).
+__device__ inline bool replay_window(const ble_replay_f32& rp, int64_t t, int64_t env, int* m, int* term) {
+  int mm = rp.update_horizon, tm = 0;
+  for (int k = 0; k < rp.update_horizon; ++k) {
+    const int64_t at = ((t + k) % rp.capacity) * rp.num_envs + env;
+    if (rp.terminal[at]) { mm = k + 1; tm = 1; break; }
+    if (rp.episode_end[at]) return false;
   }
-  __syncthreads();
-  const int64_t t = s_t, env = s_env;
-  const int m = s_m;
+  *m = mm; *term = tm;
+  return true;
+}
+
+// Lane 0: row b's return, discount, action and index (t < 0: a failed draw -- zeros, index (-1, -1), BLE_FLAG_REPLAY_EMPTY).
+__device__ inline void replay_emit(const ble_replay_f32& rp, const ble_train_batch_f32& bt, int64_t b, int64_t t, int64_t env, int m,
+                                   int term, uint32_t* __restrict__ err_flags) {
+  float ret = 0.0f, disc = 0.0f;
+  uint8_t act = 0;
+  if (t < 0) {
+    if (err_flags != nullptr) atomicOr(err_flags, kFlagReplayEmpty);
+  } else {
+    for (int k = 0; k < m; ++k) {                                      // Dopamine: np.sum(float32 gamma^k table * rewards), k ascending
+      const float gk = (float)pow(rp.gamma, (double)k);
+      ret = __fadd_rn(ret, __fmul_rn(gk, rp.reward[((t + k) % rp.capacity) * rp.num_envs + env]));     // (rounded apart: no fma)
+    }
+    disc = term ? 0.0f : (float)pow(rp.gamma, (double)rp.update_horizon);
+    act = rp.action[(t % rp.capacity) * rp.num_envs + env];
+  }
+  bt.ret[b] = ret;
+  bt.discount[b] = disc;
+  bt.action[b] = act;
+  if (bt.index != nullptr) { bt.index[2 * b] = t; bt.index[2 * b + 1] = env; }
+}
+
+// The whole workgroup: state row b = obs[t], next_state row b = obs[t + m] (zeros when t < 0; columns >= BLE_OBS_DIM zero).
+__device__ inline void replay_gather(const ble_replay_f32& rp, const ble_train_batch_f32& bt, int64_t b, int64_t t, int64_t env, int m) {
   const int quads = (int)(bt.state_stride / 4);
   float4* __restrict__ so = reinterpret_cast<float4*>(bt.state + b * bt.state_stride);
   float4* __restrict__ no = reinterpret_cast<float4*>(bt.next_state + b * bt.state_stride);
   const float4* si = t < 0 ? nullptr : reinterpret_cast<const float4*>(rp.obs + ((t % rp.capacity) * rp.num_envs + env) * rp.obs_stride);
   const float4* ni = t < 0 ? nullptr : reinterpret_cast<const float4*>(rp.obs + (((t + m) % rp.capacity) * rp.num_envs + env) * rp.obs_stride);
-  for (int q = threadIdx.x; q < quads; q += kReplayBlock) {
+  for (int q = threadIdx.x; q < quads; q += blockDim.x) {
     float4 a = make_float4(0.0f, 0.0f, 0.0f, 0.0f), c = a;
     if (si != nullptr && 4 * q < BLE_OBS_DIM) {                      // (obs_stride is a multiple of 4 >= BLE_OBS_DIM: quad q is in the row)
       a = si[q]; c = ni[q];
@@ -99,6 +86,40 @@ __global__ __launch_bounds__(kReplayBlock) void ble_replay_sample_kernel(ble_rep
     so[q] = a;
     no[q] = c;
   }
+}
+
+// The Philox stream of batch row b: keyed by (seed, b, the update counter).
+__device__ inline Philox replay_stream(uint64_t seed, int64_t b, uint64_t counter) {
+  Philox g = philox_init(seed, (uint64_t)b, (uint32_t)counter);
+  g.c3 = (uint32_t)(counter >> 32);                                  // (b < 2^32: the env key's high word is free)
+  return g;
+}
+
+// One workgroup per batch row: lane 0 draws (t, env) uniformly until the window is valid, then the workgroup gathers obs[t] and obs[t + m].
+__global__ __launch_bounds__(kReplayBlock) void ble_replay_sample_kernel(ble_replay_f32 rp, ble_train_batch_f32 bt, uint64_t seed,
+                                                                        uint32_t* __restrict__ err_flags) {
+  __shared__ int64_t s_t, s_env;
+  __shared__ int s_m;
+  const int64_t b = blockIdx.x;
+  if (threadIdx.x == 0) {
+    const int64_t count = *rp.count;
+    const int64_t lo = count > rp.capacity ? count - rp.capacity : 0;
+    const int64_t span = count - rp.update_horizon - lo;            // candidates t: t + n <= count - 1
+    Philox g = replay_stream(seed, b, *rp.counter);
+    int64_t t = -1, env = -1;
+    int m = 0, term = 0;
+    for (int tries = 0; span > 0 && tries < rp.max_tries; ++tries) {
+      const uint64_t hi = philox_u32(g), lo32 = philox_u32(g), e32 = philox_u32(g);
+      const int64_t tt = lo + (int64_t)__umul64hi((hi << 32) | lo32, (uint64_t)span);
+      const int64_t ee = (int64_t)(((uint64_t)e32 * (uint64_t)rp.num_envs) >> 32);
+      if (replay_window(rp, tt, ee, &m, &term)) { t = tt; env = ee; break; }
+    }
+    if (t < 0) { m = 0; term = 0; }
+    replay_emit(rp, bt, b, t, env, m, term, err_flags);
+    s_t = t; s_env = env; s_m = m;
+  }
+  __syncthreads();
+  replay_gather(rp, bt, b, s_t, s_env, s_m);
 }
 
 // ------------------------------------------------------------------------------------------------------------ counters
@@ -351,6 +372,46 @@ __global__ __launch_bounds__(256) void ble_explore_kernel(uint8_t* __restrict__ 
   const uint32_t u = philox_u32(g), r = philox_u32(g);
   const float uf = (float)(u >> 8) * (1.0f / 16777216.0f);             // [0, 1), 24 bits
   if (uf < epsilon) action[i] = (uint8_t)(((uint64_t)r * 3u) >> 32);
+}
+
+// Marco Polo exploration (the reference's MarcoPoloExploration over a RandomWalkAgent, one step = 3 min), one lane per environment.
+// The Philox stream of (seed, env, step): block 0 holds the begin-of-episode uniforms (target, then episode), block 1 on the normal.
+constexpr int kMarcoPoloRlSteps = 80, kMarcoPoloExploreSteps = 40;     // 4 h and 2 h
+__host__ __device__ inline float marco_polo_u24(double u) { return (float)(uint32_t)(u * 16777216.0) * (1.0f / 16777216.0f); }
+
+__global__ __launch_bounds__(256) void ble_marco_polo_kernel(ble_marco_polo_f32 mp, uint8_t* __restrict__ action) {
+  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (i >= mp.n) return;
+  const uint64_t step = *mp.step;
+  Philox g = philox_init(mp.seed, (uint64_t)i, (uint32_t)step);
+  g.key1 ^= (uint32_t)(step >> 32);
+  if (mp.begin[i]) {
+    // RandomWalkAgent.begin_episode: clock 0, target U[6500, 11400) (jax.random.uniform in float32); then phase clock 0, the
+    // episode is exploratory when u <= p, RL phase; the agent's action is kept.
+    const float ut = marco_polo_u24(philox_uniform(g)), ue = marco_polo_u24(philox_uniform(g));
+    mp.walk_clock[i] = 0;
+    mp.target[i] = (double)fmaxf(6500.0f, __fadd_rn(__fmul_rn(ut, 4900.0f), 6500.0f));
+    mp.phase_clock[i] = 0;
+    mp.exploratory_episode[i] = (double)ue <= mp.exploratory_episode_probability ? 1 : 0;
+    mp.exploratory_phase[i] = 0;
+    return;
+  }
+  int clock = mp.phase_clock[i] + 1;
+  uint8_t phase = mp.exploratory_phase[i];
+  if (mp.exploratory_episode[i] && clock >= (phase ? kMarcoPoloExploreSteps : kMarcoPoloRlSteps)) { phase ^= 1; clock = 0; }
+  mp.phase_clock[i] = clock;
+  mp.exploratory_phase[i] = phase;
+  if (!phase) return;
+  // RandomWalkAgent.step: clock += 180 s, target += seconds * 0.1666 * z (float64), then the hysteresis rule on p = 5000 + 9000 f0
+  // (float32, NamedPerciatelliFeatures.balloon_pressure)
+  const int walk = mp.walk_clock[i] + 1;
+  mp.walk_clock[i] = walk;
+  g.c0 = 1;
+  const double z = philox_normal(g);
+  const double target = mp.target[i] + ((double)walk * 180.0) * 0.1666 * z;
+  mp.target[i] = target;
+  const float p = __fadd_rn(5000.0f, __fmul_rn(mp.obs[i * mp.obs_stride], 9000.0f));
+  action[i] = (double)__fsub_rn(p, 100.0f) > target ? 2 : ((double)__fadd_rn(p, 100.0f) < target ? 0 : 1);
 }
 
 // ------------------------------------------------------------------------------------------------------------ host

@@ -14,7 +14,7 @@ def run_training_loop_vec(env, trainer: qnet_train.QNetworkTrainer, replay: qnet
                           steps_per_iteration: int, max_episode_length: int = 960, min_replay_history: int = 500,
                           update_period: int = 4, target_update_period: int = 100,
                           epsilon: Union[float, Callable[[int], float]] = 0.01, updates_per_step: Optional[int] = None,
-                          batch_size: int = 32, seed: int = 0, capture_graph: bool = True) -> List[dict]:
+                          batch_size: int = 32, seed: int = 0, capture_graph: bool = True, exploration=None) -> List[dict]:
   """Trains `trainer` on `env` (auto_reset) for num_iterations x steps_per_iteration vector steps.  Each step: the online network's
   greedy actions, epsilon-greedy (ble_qnet_explore_u8, keyed by (seed, environment, step)), env.step, replay.add, then the updates.
 
@@ -23,6 +23,10 @@ def run_training_loop_vec(env, trainer: qnet_train.QNetworkTrainer, replay: qnet
   transitions, so it runs N / update_period updates (the fraction carried over); updates_per_step overrides that count.  The
   reference's 960-step episode limit is enforced per environment: a lane reaching it ends its episode (episode_end without terminal)
   and restarts.  epsilon: a float or a function of the transitions added so far.
+
+  exploration: None, or a VecMarcoPoloExploration (configs/quantile.gin: with epsilon=0.0 and a VecPrioritizedReplayBuffer).  Each
+  step then runs the greedy actions, epsilon-greedy (skipped when epsilon is 0), then the explorer, whose begin mask is all ones at the
+  first step and the previous step's episode_end after; the replay stores the action actually taken.
 
   Returns one dict per iteration: mean_loss (over the iteration's updates), updates, episodes (finished), mean_return (of the finished
   episodes), time_within_radius (the fraction of the iteration's transitions with reward > 0.5, i.e. inside the radius), transitions."""
@@ -33,6 +37,7 @@ def run_training_loop_vec(env, trainer: qnet_train.QNetworkTrainer, replay: qnet
   actions = torch.zeros(n, dtype=torch.uint8, device=dev_)
   ep_steps = torch.zeros(n, dtype=torch.int32, device=dev_)
   ep_return = torch.zeros(n, dtype=torch.float32, device=dev_)
+  begin = torch.ones(n, dtype=torch.uint8, device=dev_)
   transitions, updates, pending, step = 0, 0, 0.0, 0
   captured = False
   stats = []
@@ -45,10 +50,17 @@ def run_training_loop_vec(env, trainer: qnet_train.QNetworkTrainer, replay: qnet
     for _ in range(steps_per_iteration):
       trainer.act(obs, actions)
       eps = epsilon(transitions) if callable(epsilon) else epsilon
-      qnet_train.explore(actions, eps, seed, step)
+      if exploration is None:
+        qnet_train.explore(actions, eps, seed, step)
+      else:
+        if eps > 0.0:
+          qnet_train.explore(actions, eps, seed, step)
+        exploration(obs, actions, begin)
       end_mask = (ep_steps + 1 >= max_episode_length).to(torch.uint8)
       next_obs, reward, terminal = env.step(actions, end_mask=end_mask)
       episode_end = terminal | end_mask
+      if exploration is not None:
+        begin.copy_(episode_end)
       replay.add(obs, actions, reward, terminal, episode_end)
       ep_return += reward
       ep_steps += 1
@@ -70,9 +82,8 @@ def run_training_loop_vec(env, trainer: qnet_train.QNetworkTrainer, replay: qnet
           pending -= todo
         for _ in range(todo):
           if capture_graph and not captured:
-            trainer.capture(replay, batch_size)        # (its first, eager update is a real one)
+            loss = trainer.capture(replay, batch_size)        # (its first, eager update is a real one)
             captured = True
-            loss = trainer.views(batch_size)['loss']
           else:
             loss = trainer.train_step(replay, batch_size)
           loss_sum += loss.mean()

@@ -729,6 +729,77 @@ typedef struct ble_explore_f32 {
 
 int ble_qnet_explore_u8(const ble_explore_f32* ex, uint8_t* action, void* stream);
 
+/*
+ * Prioritized n-step replay (additive to ABI 5): Dopamine 4.0.0's OutOfGraphPrioritizedReplayBuffer over the ring above.
+ * An fp64 sum tree over capacity x num_envs leaves: leaf (t % capacity) num_envs + env is the n-step window that starts at ring row t
+ * of that environment.  A heap padded to a power of two: nodes[1] is the root, nodes[padded + i] leaf i, nodes[0] unused, the padded
+ * leaves 0.  Every parent is recomputed as left + right, never updated by a delta.  Initial state: all nodes 0, *max_priority = 1.
+ */
+#define BLE_FLAG_REPLAY_PRIORITY 8192u  /* ble_replay_set_priority_f32: a non-finite or negative loss -- its leaf is left unchanged */
+#define BLE_SUM_TREE_MAX_LEAVES (1LL << 31)
+
+typedef struct ble_sum_tree_f64 {
+  int64_t leaves;            /* capacity x num_envs of the replay it indexes */
+  int64_t padded;            /* the smallest power of two >= leaves */
+  double* nodes;             /* device [2 padded], 8-byte aligned */
+  double* max_priority;      /* device [1]: max_recorded_priority, never falls */
+} ble_sum_tree_f64;
+
+/*
+ * ble_replay_tree_add_f64, after each vector step is added (*count = s + 1): zeroes row s % capacity (its windows are overwritten) and
+ * gives row (s - n) % capacity, whose windows have just become complete, *max_priority -- 0 for a window that is not valid (one that
+ * crosses a time-limit end without a terminal).  Every nonzero leaf is a valid window.  One workgroup: the two leaf rows, then their
+ * ancestors level by level.
+ */
+int ble_replay_tree_add_f64(const ble_replay_f32* replay, const ble_sum_tree_f64* tree, void* stream);
+
+/*
+ * ble_replay_sample_prioritized_f32: stratified draws.  Row b draws q = total (b + u) / B from the Philox stream keyed by (seed, b,
+ * *counter) and walks the tree down in fp64 (left if q < left sum, else q -= left sum and right; a child whose sum is 0 is never
+ * entered); a draw on an invalid window is redrawn from the whole tree (q = total u), at most max_tries draws (BLE_FLAG_REPLAY_EMPTY as
+ * the uniform sampler).  Writes the batch as ble_replay_sample_f32 does (batch->index is required) and priority[b] (device float32 [B]):
+ * the sampled leaf, 0 for a failed row.  Advances *counter by one.
+ */
+int ble_replay_sample_prioritized_f32(const ble_replay_f32* replay, const ble_sum_tree_f64* tree, const ble_train_batch_f32* batch,
+                                      float* priority, unsigned long long seed, uint32_t* err_flags, void* stream);
+
+/*
+ * ble_replay_set_priority_f32, after an update on that batch: leaf = sqrt(loss[b] + 1e-10) (float32, then stored as fp64), in batch
+ * order (the later row wins on a duplicate index); rows with index -1 are skipped; a non-finite or negative loss leaves its leaf and
+ * sets BLE_FLAG_REPLAY_PRIORITY; *max_priority rises to the largest new leaf; ancestors recomputed.  weighted_loss[b] (device float32
+ * [B]) = (w_b / max w) loss[b], w_b = 1 / sqrt(priority[b] + 1e-10): the loss Dopamine reports -- the gradient is NOT weighted.
+ * Failed rows: 0, and out of the max.  One workgroup, no atomics.
+ */
+int ble_replay_set_priority_f32(const ble_replay_f32* replay, const ble_sum_tree_f64* tree, const ble_train_batch_f32* batch,
+                                const float* priority, const float* loss, float* weighted_loss, uint32_t* err_flags, void* stream);
+
+/*
+ * Marco Polo exploration (the reference's MarcoPoloExploration with a RandomWalkAgent; one call = one 3-minute agent step), one lane
+ * per environment.  begin[i] != 0: begin_episode -- walk clock 0, target U[6500, 11400) Pa (float32), phase clock 0, exploratory episode
+ * when u <= exploratory_episode_probability, RL phase; action[i] is kept.  Otherwise step -- phase clock + 1; in an exploratory episode
+ * the phase toggles when it has run out (RL >= 80 steps, exploratory >= 40) and the clock restarts; in the exploratory phase walk clock
+ * + 1, target += (180 walk) 0.1666 z (fp64), action[i] = UP (2) if p - 100 > target, DOWN (0) if p + 100 < target, else STAY (1), with
+ * p = 5000 + 9000 obs[i][0] in float32.  Draws: Philox keyed by (seed, i, *step); block 0 holds the two begin uniforms (target, then
+ * episode; 24 bits), block 1 on the normal.  Advances *step by one.
+ */
+typedef struct ble_marco_polo_f32 {
+  int64_t n;
+  int32_t obs_stride;                      /* floats between observation rows, >= 1 (feature 0 is read) */
+  int32_t reserved_;                       /* 0 */
+  double exploratory_episode_probability;  /* 0 .. 1 */
+  unsigned long long seed;
+  const float* obs;                        /* device [n][obs_stride] */
+  const uint8_t* begin;                    /* device [n] */
+  unsigned long long* step;                /* device: the draw key's step */
+  int32_t* phase_clock;                    /* device [n]: agent steps in the current phase */
+  int32_t* walk_clock;                     /* device [n]: the random walk's steps this episode */
+  uint8_t* exploratory_episode;            /* device [n] */
+  uint8_t* exploratory_phase;              /* device [n] */
+  double* target;                          /* device [n]: the random walk's target pressure, Pa */
+} ble_marco_polo_f32;
+
+int ble_marco_polo_u8(const ble_marco_polo_f32* mp, uint8_t* action, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
