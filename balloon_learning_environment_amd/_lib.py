@@ -20,7 +20,7 @@ _PKG_DIR = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get('BLE_HIP_LIB') or os.path.join(_PKG_DIR, 'libble_hip.so')   # override: experiments only
 _SOURCES = [os.path.join(_PKG_DIR, 'csrc', f) for f in ('ble_kernels.hip', 'ble_step_core.h', 'ble_physics.h', 'ble_intrinsics.h', 'ble_reset.h',
                                                           'ble_observe.h', 'ble_noise.h', 'ble_decode.h', 'ble_step_split.h', 'ble_agent.h', 'ble_qnet.h',
-                                                          'ble_train.h', 'ble_replay.h')]
+                                                          'ble_train.h', 'ble_replay.h', 'ble_explore.h')]
 _HEADER = os.path.join(os.path.dirname(_PKG_DIR), 'include', 'ble_abi.h')
 
 ABI_VERSION = 5
@@ -167,6 +167,11 @@ def check(code: int, what: str) -> None:
   if code != BLE_OK:
     hip = _lib.ble_last_hip_error() if _lib is not None else 0
     raise BleLibraryError(f'{what} failed with BLE error {code} (hipError_t {hip})')
+
+
+def call(name: str, *args) -> None:
+  """Looks up the export `name`, calls it and raises BleLibraryError unless it answers BLE_OK."""
+  check(getattr(lib(), name)(*args), name)
 
 
 class step_form:

@@ -1,5 +1,5 @@
 """Marco Polo exploration on the device: the reference's MarcoPoloExploration over a RandomWalkAgent (configs/quantile.gin), one lane
-per environment of a VecBalloonEnv (ble_marco_polo_u8, csrc/ble_train.h).
+per environment of a VecBalloonEnv (ble_marco_polo_u8, csrc/ble_explore.h).
 
 An episode is exploratory with probability exploratory_episode_probability.  It starts in the RL phase (the agent's actions), and an
 exploratory episode alternates 4 h of RL with 2 h of a random walk in pressure: a target drawn in [6500, 11400) Pa at the episode's
@@ -33,7 +33,6 @@ class VecMarcoPoloExploration:
       self.exploratory_episode = torch.zeros(n, dtype=torch.uint8, device=d)
       self.exploratory_phase = torch.zeros(n, dtype=torch.uint8, device=d)
       self.target = torch.zeros(n, dtype=torch.float64, device=d)
-    self.lib = _lib.lib()
 
   @dev.on_own_device
   def __call__(self, obs: torch.Tensor, actions: torch.Tensor, begin: torch.Tensor) -> torch.Tensor:
@@ -44,7 +43,7 @@ class VecMarcoPoloExploration:
     mp = _abi.BleMarcoPoloF32(n, stride, 0, self.probability, self.seed & (2 ** 64 - 1), obs.data_ptr(), begin.data_ptr(),
                               self.step.data_ptr(), self.phase_clock.data_ptr(), self.walk_clock.data_ptr(),
                               self.exploratory_episode.data_ptr(), self.exploratory_phase.data_ptr(), self.target.data_ptr())
-    _lib.check(self.lib.ble_marco_polo_u8(ctypes.byref(mp), actions.data_ptr(), dev.stream_ptr(self.device)), 'ble_marco_polo_u8')
+    _lib.call('ble_marco_polo_u8', ctypes.byref(mp), actions.data_ptr(), dev.stream_ptr(self.device))
     return actions
 
   _STATE = ('step', 'phase_clock', 'walk_clock', 'exploratory_episode', 'exploratory_phase', 'target')

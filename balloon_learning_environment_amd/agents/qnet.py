@@ -54,15 +54,14 @@ class QNetwork:
     self.num_layers = len(self.kernels)
     self.num_atoms = int(num_atoms)
     self.hidden_units = int(self.kernels[0].shape[1]) if self.num_layers > 1 else 0
-    self.lib = _lib.lib()
     self._struct = _abi.BleQnetF32(self.num_layers, _lib.OBS_DIM, self.hidden_units, NUM_ACTIONS, self.num_atoms, 0, None)
     packed_floats = ctypes.c_int64()
-    _lib.check(self.lib.ble_qnet_workspace_f32(ctypes.byref(self._struct), 0, ctypes.byref(packed_floats), None), 'ble_qnet_workspace_f32')
+    _lib.call('ble_qnet_workspace_f32', ctypes.byref(self._struct), 0, ctypes.byref(packed_floats), None)
     # the packed image, made once on the host (ble_qnet_pack_f32); it goes to the device on the first use there
     self.packed_host = np.zeros(packed_floats.value, np.float32)
     kp = (ctypes.c_void_p * self.num_layers)(*[k.ctypes.data for k in self.kernels])
     bp = (ctypes.c_void_p * self.num_layers)(*[b.ctypes.data for b in self.biases])
-    _lib.check(self.lib.ble_qnet_pack_f32(ctypes.byref(self._struct), kp, bp, self.packed_host.ctypes.data), 'ble_qnet_pack_f32')
+    _lib.call('ble_qnet_pack_f32', ctypes.byref(self._struct), kp, bp, self.packed_host.ctypes.data)
     self.packed: Optional[torch.Tensor] = None
 
   def to_device(self) -> 'QNetwork':
@@ -138,19 +137,6 @@ class QNetwork:
     """2 x the multiply-adds of one forward pass (the reference's shapes, no padding)."""
     return sum(2 * k.shape[0] * k.shape[1] for k in self.kernels)
 
-  def scratch_floats(self, n: int) -> int:
-    out = ctypes.c_int64()
-    _lib.check(self.lib.ble_qnet_workspace_f32(ctypes.byref(self._struct), int(n), None, ctypes.byref(out)), 'ble_qnet_workspace_f32')
-    return out.value
-
-  def forward(self, obs: torch.Tensor, scratch: torch.Tensor, out: torch.Tensor, q_values: Optional[torch.Tensor] = None) -> None:
-    """One ble_qnet_forward_f32 launch on the current stream of the network's device (no checks beyond the library's)."""
-    assert self.packed is not None, 'QNetwork.to_device() first'
-    n = obs.shape[0]
-    stride = obs.stride(0) if n > 1 else max(obs.stride(0), _lib.OBS_DIM)
-    _lib.check(self.lib.ble_qnet_forward_f32(ctypes.byref(self._struct), obs.data_ptr(), stride, scratch.data_ptr(), out.data_ptr(),
-                                             dev.ptr(q_values), n, dev.stream_ptr(self.device)), 'ble_qnet_forward_f32')
-
 
 def init_params(kind: str, seed: int = 0, num_layers: int = 8, hidden_units: int = 600, num_atoms: int = 51) -> dict:
   """Parameters of the reference's initialisation with zero biases (flax Dense's bias_init): 'quantile' -- QuantileNetwork's
@@ -173,24 +159,40 @@ def init_params(kind: str, seed: int = 0, num_layers: int = 8, hidden_units: int
   return {'params': tree}
 
 
+class Forward:
+  """ble_qnet_forward_f32 on a network descriptor whose image is on the device, with the scratch it needs: the activations of a batch
+  size (2 x N x the widest padded layer, float32) are allocated on the first call at that size, which must not be inside a graph
+  capture; later calls allocate nothing, so they can be captured.  `owner` names the caller's class in that refusal."""
+
+  def __init__(self, struct: _abi.BleQnetF32, device: torch.device, owner: str):
+    self.struct, self.device, self.owner = struct, device, owner
+    self._scratch: Dict[int, torch.Tensor] = {}
+
+  def _allocate(self, n: int) -> torch.Tensor:
+    floats = ctypes.c_int64()
+    _lib.call('ble_qnet_workspace_f32', ctypes.byref(self.struct), n, None, ctypes.byref(floats))
+    return torch.empty(max(floats.value, 1), dtype=torch.float32, device=self.device)
+
+  def __call__(self, obs: torch.Tensor, out: torch.Tensor, q_values: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """One launch on the current stream of the network's device (no checks beyond the library's): the actions of obs's rows into out."""
+    n = obs.shape[0]
+    scratch = dev.first_use(self._scratch, n, lambda: self._allocate(n),
+                            f'{self.owner}: call act once at batch size {n} before capturing it in a graph (scratch allocation)')
+    stride = obs.stride(0) if n > 1 else max(obs.stride(0), _lib.OBS_DIM)      # (torch gives a one-row tensor any stride)
+    _lib.call('ble_qnet_forward_f32', ctypes.byref(self.struct), obs.data_ptr(), stride, scratch.data_ptr(), out.data_ptr(),
+              dev.ptr(q_values), n, dev.stream_ptr(self.device))
+    return out
+
+
 class VecQNetworkAgent:
   """A Q-network policy for N environments at once: act(obs [N, 1099] float32 device) -> uint8 [N] device.
 
-  The scratch of a batch size (the activations, 2 x N x the widest padded layer, float32) is allocated on the first call at that
-  size, which must not be inside a graph capture; later calls allocate nothing, so they can be captured."""
+  The scratch of a batch size is allocated on the first call at that size, which must not be inside a graph capture (Forward)."""
 
   def __init__(self, network: QNetwork):
     self.network = network.to_device()
     self.device = network.device
-    self._scratch: Dict[int, torch.Tensor] = {}
-
-  def _scratch_for(self, n: int) -> torch.Tensor:
-    s = self._scratch.get(n)
-    if s is None:
-      if torch.cuda.is_current_stream_capturing():
-        raise RuntimeError(f'VecQNetworkAgent: call act once at batch size {n} before capturing it in a graph (scratch allocation)')
-      s = self._scratch[n] = torch.empty(max(self.network.scratch_floats(n), 1), dtype=torch.float32, device=self.device)
-    return s
+    self._forward = Forward(network._struct, self.device, 'VecQNetworkAgent')
 
   @dev.on_own_device
   def act(self, obs: torch.Tensor, out: Optional[torch.Tensor] = None, q_values: Optional[torch.Tensor] = None) -> torch.Tensor:
@@ -206,8 +208,7 @@ class VecQNetworkAgent:
       assert q_values.dtype == torch.float32 and q_values.is_contiguous() and q_values.numel() == n * NUM_ACTIONS
     if n == 0:
       return out
-    self.network.forward(obs, self._scratch_for(n), out, q_values)
-    return out
+    return self._forward(obs, out, q_values)
 
   __call__ = act
 

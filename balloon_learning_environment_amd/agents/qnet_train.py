@@ -37,9 +37,10 @@ def _check_flags(flags: torch.Tensor) -> None:
 
 
 class TrainBatch:
-  """One batch of B transitions on the device (what the sampler writes, what the train step reads)."""
+  """One batch of B transitions on the device (what the sampler writes, what the train step reads).  A prioritized batch also holds
+  each row's sampled priority and the weighted losses set_priority reports; both are None otherwise."""
 
-  def __init__(self, batch_size: int, device):
+  def __init__(self, batch_size: int, device, prioritized: bool = False):
     b = int(batch_size)
     self.batch_size = b
     self.state = torch.zeros(b, ROW_FLOATS, dtype=torch.float32, device=device)
@@ -48,6 +49,8 @@ class TrainBatch:
     self.discount = torch.zeros(b, dtype=torch.float32, device=device)
     self.action = torch.zeros(b, dtype=torch.uint8, device=device)
     self.index = torch.zeros(b, 2, dtype=torch.int64, device=device)
+    self.priority = torch.zeros(max(b, 1), dtype=torch.float32, device=device)[:b] if prioritized else None
+    self.weighted_loss = torch.zeros(max(b, 1), dtype=torch.float32, device=device)[:b] if prioritized else None
     self.struct = _abi.BleTrainBatchF32(b, ROW_FLOATS, self.state.data_ptr(), self.next_state.data_ptr(), self.ret.data_ptr(),
                                         self.discount.data_ptr(), self.action.data_ptr(), self.index.data_ptr())
 
@@ -72,6 +75,9 @@ class VecReplayBuffer:
   valid n-step windows uniformly (ble_replay_sample_f32): a window never reads past an episode's end, and one that reaches a time-limit
   end without a terminal is not drawn."""
 
+  prioritized = False
+  _TENSORS = ('obs', 'action', 'reward', 'terminal', 'episode_end', 'counter')      # the checkpoint's tensors
+
   def __init__(self, num_envs: int, capacity_steps: int, update_horizon: int = 5, gamma: float = 0.993, device='cuda:0'):
     self.device = dev.require_gpu(device)
     self.num_envs, self.capacity = int(num_envs), int(capacity_steps)
@@ -90,7 +96,6 @@ class VecReplayBuffer:
       self.err_flags = torch.zeros(1, dtype=torch.int32, device=d)
     self.cursor = 0                      # host mirror of count
     self._batches: Dict[int, TrainBatch] = {}
-    self.lib = _lib.lib()
 
   def __len__(self) -> int:
     """Transitions held."""
@@ -114,38 +119,34 @@ class VecReplayBuffer:
     self.cursor += 1
 
   def batch_buffers(self, batch_size: int) -> TrainBatch:
-    bt = self._batches.get(batch_size)
-    if bt is None:
-      if torch.cuda.is_current_stream_capturing():
-        raise RuntimeError(f'VecReplayBuffer: sample once at batch size {batch_size} before capturing it in a graph')
-      bt = self._batches[batch_size] = TrainBatch(batch_size, self.device)
-    return bt
+    return dev.first_use(self._batches, batch_size, lambda: TrainBatch(batch_size, self.device, self.prioritized),
+                         f'VecReplayBuffer: sample once at batch size {batch_size} before capturing it in a graph')
 
   @dev.on_own_device
   def sample(self, batch_size: int, seed: int, counter: Optional[torch.Tensor] = None) -> TrainBatch:
     """B transitions into this buffer's batch buffers of that size (overwritten by the next sample at that size).  counter: the
     int64 [1] device update counter the draw is keyed by and advances (default: the buffer's own)."""
     bt = self.batch_buffers(int(batch_size))
-    rp = self.struct(self.counter if counter is None else counter)
-    _lib.check(self.lib.ble_replay_sample_f32(ctypes.byref(rp), ctypes.byref(bt.struct), int(seed) & (2 ** 64 - 1), self.err_flags.data_ptr(),
-                                              dev.stream_ptr(self.device)), 'ble_replay_sample_f32')
+    self._draw(self.struct(self.counter if counter is None else counter), bt, int(seed) & (2 ** 64 - 1))
     return bt
+
+  def _draw(self, rp: _abi.BleReplayF32, bt: TrainBatch, seed: int) -> None:
+    _lib.call('ble_replay_sample_f32', ctypes.byref(rp), ctypes.byref(bt.struct), seed, self.err_flags.data_ptr(),
+              dev.stream_ptr(self.device))
 
   def check_errors(self) -> None:
     _check_flags(self.err_flags)
 
   def state_dict(self) -> dict:
     return {'num_envs': self.num_envs, 'capacity': self.capacity, 'update_horizon': self.update_horizon, 'gamma': self.gamma,
-            'cursor': self.cursor, 'obs': self.obs.clone(), 'action': self.action.clone(), 'reward': self.reward.clone(),
-            'terminal': self.terminal.clone(), 'episode_end': self.episode_end.clone(), 'counter': self.counter.clone()}
+            'cursor': self.cursor, **{k: getattr(self, k).clone() for k in self._TENSORS}}
 
   def load_state_dict(self, d: dict) -> None:
     assert (d['num_envs'], d['capacity'], d['update_horizon']) == (self.num_envs, self.capacity, self.update_horizon)
-    for k in ('obs', 'action', 'reward', 'terminal', 'episode_end', 'counter'):
+    for k in self._TENSORS:
       getattr(self, k).copy_(d[k])
     self.cursor = int(d['cursor'])
     self.count.fill_(self.cursor)
-
 
 
 class VecPrioritizedReplayBuffer(VecReplayBuffer):
@@ -157,6 +158,7 @@ class VecPrioritizedReplayBuffer(VecReplayBuffer):
   per-row losses Dopamine reports (the gradient itself is not weighted)."""
 
   prioritized = True
+  _TENSORS = VecReplayBuffer._TENSORS + ('tree', 'max_priority')
 
   def __init__(self, num_envs: int, capacity_steps: int, update_horizon: int = 5, gamma: float = 0.993, device='cuda:0'):
     super().__init__(num_envs, capacity_steps, update_horizon, gamma, device)
@@ -168,7 +170,6 @@ class VecPrioritizedReplayBuffer(VecReplayBuffer):
       self.tree = torch.zeros(2 * self.padded, dtype=torch.float64, device=self.device)
       self.max_priority = torch.ones(1, dtype=torch.float64, device=self.device)
     self._tree = _abi.BleSumTreeF64(leaves, self.padded, self.tree.data_ptr(), self.max_priority.data_ptr())
-    self._weighted: Dict[int, torch.Tensor] = {}
 
   def leaf_priorities(self) -> torch.Tensor:
     """The leaves as [capacity_steps, num_envs] (a view)."""
@@ -177,49 +178,23 @@ class VecPrioritizedReplayBuffer(VecReplayBuffer):
   @dev.on_own_device
   def add(self, obs, action, reward, terminal, episode_end=None) -> None:
     super().add(obs, action, reward, terminal, episode_end)
-    rp = self.struct(self.counter)
-    _lib.check(self.lib.ble_replay_tree_add_f64(ctypes.byref(rp), ctypes.byref(self._tree), dev.stream_ptr(self.device)),
-               'ble_replay_tree_add_f64')
+    _lib.call('ble_replay_tree_add_f64', ctypes.byref(self.struct(self.counter)), ctypes.byref(self._tree), dev.stream_ptr(self.device))
 
-  def batch_buffers(self, batch_size: int) -> TrainBatch:
-    bt = super().batch_buffers(batch_size)
-    if not hasattr(bt, 'priority'):
-      bt.priority = torch.zeros(max(batch_size, 1), dtype=torch.float32, device=self.device)[:batch_size]
-      self._weighted[batch_size] = torch.zeros(max(batch_size, 1), dtype=torch.float32, device=self.device)
-    return bt
-
-  @dev.on_own_device
-  def sample(self, batch_size: int, seed: int, counter: Optional[torch.Tensor] = None) -> TrainBatch:
-    """B stratified prioritized draws (ble_replay_sample_prioritized_f32) into this size's batch buffers; batch.priority [B] holds
-    each row's leaf (fp32)."""
-    bt = self.batch_buffers(int(batch_size))
-    rp = self.struct(self.counter if counter is None else counter)
-    _lib.check(self.lib.ble_replay_sample_prioritized_f32(ctypes.byref(rp), ctypes.byref(self._tree), ctypes.byref(bt.struct),
-                                                          bt.priority.data_ptr(), int(seed) & (2 ** 64 - 1), self.err_flags.data_ptr(),
-                                                          dev.stream_ptr(self.device)), 'ble_replay_sample_prioritized_f32')
-    return bt
+  def _draw(self, rp: _abi.BleReplayF32, bt: TrainBatch, seed: int) -> None:
+    """sample()'s draw: B stratified prioritized draws (ble_replay_sample_prioritized_f32); batch.priority [B] holds each row's leaf
+    (fp32)."""
+    _lib.call('ble_replay_sample_prioritized_f32', ctypes.byref(rp), ctypes.byref(self._tree), ctypes.byref(bt.struct),
+              bt.priority.data_ptr(), seed, self.err_flags.data_ptr(), dev.stream_ptr(self.device))
 
   @dev.on_own_device
   def set_priority(self, batch: TrainBatch, loss: torch.Tensor) -> torch.Tensor:
     """Leaves of the batch's rows = sqrt(loss + 1e-10) (ble_replay_set_priority_f32); returns the weighted per-row losses [B] (a
     buffer the next call at this size overwrites)."""
-    b = batch.batch_size
-    out = self._weighted[b]
-    rp = self.struct(self.counter)
-    _lib.check(self.lib.ble_replay_set_priority_f32(ctypes.byref(rp), ctypes.byref(self._tree), ctypes.byref(batch.struct),
-                                                    batch.priority.data_ptr(), loss.data_ptr(), out.data_ptr(), self.err_flags.data_ptr(),
-                                                    dev.stream_ptr(self.device)), 'ble_replay_set_priority_f32')
-    return out[:b]
+    _lib.call('ble_replay_set_priority_f32', ctypes.byref(self.struct(self.counter)), ctypes.byref(self._tree), ctypes.byref(batch.struct),
+              batch.priority.data_ptr(), loss.data_ptr(), batch.weighted_loss.data_ptr(), self.err_flags.data_ptr(),
+              dev.stream_ptr(self.device))
+    return batch.weighted_loss
 
-  def state_dict(self) -> dict:
-    d = super().state_dict()
-    d['tree'], d['max_priority'] = self.tree.clone(), self.max_priority.clone()
-    return d
-
-  def load_state_dict(self, d: dict) -> None:
-    super().load_state_dict(d)
-    self.tree.copy_(d['tree'])
-    self.max_priority.copy_(d['max_priority'])
 
 class QNetworkTrainer:
   """QR-DQN training of a QNetwork's parameters on its device (defaults: configs/quantile.gin -- Adam lr 2e-6, eps 2e-5, gamma 0.993,
@@ -231,13 +206,14 @@ class QNetworkTrainer:
     policy = trainer.network()                     # a QNetwork: VecQNetworkAgent, QuantileAgent, eval_agent_vec, save_npz
   """
 
+  _TENSORS = ('weights', 'target', 'adam_m', 'adam_v', 'adam_step', 'counter')      # the checkpoint's tensors
+
   def __init__(self, network: qnet.QNetwork, *, lr: float = 2e-6, eps: float = 2e-5, gamma: float = 0.993, update_horizon: int = 5,
                kappa: float = 1.0, seed: int = 0, b1: float = 0.9, b2: float = 0.999):
     self.device = dev.require_gpu(network.device)
     self.num_layers, self.hidden_units, self.num_atoms = network.num_layers, network.hidden_units, network.num_atoms
     self.lr, self.eps, self.b1, self.b2, self.kappa = float(lr), float(eps), float(b1), float(b2), float(kappa)
     self.gamma, self.update_horizon, self.seed = float(gamma), int(update_horizon), int(seed)
-    self.lib = _lib.lib()
     self._net = _abi.BleQnetF32(self.num_layers, _lib.OBS_DIM, self.hidden_units, qnet.NUM_ACTIONS, self.num_atoms, 0, None)
     d = self.device
     with torch.cuda.device(d):
@@ -253,7 +229,7 @@ class QNetworkTrainer:
     self._net.weights = self.weights.data_ptr()
     self._retranspose()
     self._ws: Dict[int, tuple] = {}
-    self._scratch: Dict[int, torch.Tensor] = {}
+    self._forward = qnet.Forward(self._net, d, 'QNetworkTrainer')
     self._graphs: Dict[int, tuple] = {}
 
   # ---- plumbing
@@ -266,29 +242,24 @@ class QNetworkTrainer:
     bt = _abi.BleTrainBatchF32(int(batch_size), ROW_FLOATS)
     out = _abi.BleQnetTrainLayout()
     tr = _abi.BleQnetTrainF32(self._net)
-    _lib.check(self.lib.ble_qnet_train_workspace_f32(ctypes.byref(tr), ctypes.byref(bt), ctypes.byref(out)),
-               'ble_qnet_train_workspace_f32')
+    _lib.call('ble_qnet_train_workspace_f32', ctypes.byref(tr), ctypes.byref(bt), ctypes.byref(out))
     return out
 
   def _retranspose(self) -> None:
     """weights_t from the online image (host transpose; at construction and after a load)."""
     host_t = np.zeros(self.weights_t.numel(), np.float32)
     w = self.weights.cpu().numpy()
-    _lib.check(self.lib.ble_qnet_transpose_f32(ctypes.byref(self._net), w.ctypes.data, host_t.ctypes.data), 'ble_qnet_transpose_f32')
+    _lib.call('ble_qnet_transpose_f32', ctypes.byref(self._net), w.ctypes.data, host_t.ctypes.data)
     self.weights_t.copy_(torch.from_numpy(host_t))
 
   def workspace(self, batch_size: int):
     """(workspace tensor, layout) of a batch size (allocated on first use, which must not be inside a graph capture)."""
-    w = self._ws.get(batch_size)
-    if w is None:
-      if torch.cuda.is_current_stream_capturing():
-        raise RuntimeError(f'QNetworkTrainer: run one update at batch size {batch_size} before capturing it')
+    def make():
       lay = self._layout(batch_size)
       with torch.cuda.device(self.device):
-        ws = torch.zeros(max(lay.total, 64), dtype=torch.float32, device=self.device)
-        loss = torch.zeros(max(batch_size, 1), dtype=torch.float32, device=self.device)
-      w = self._ws[batch_size] = (ws, lay, loss)
-    return w
+        return (torch.zeros(max(lay.total, 64), dtype=torch.float32, device=self.device), lay,
+                torch.zeros(max(batch_size, 1), dtype=torch.float32, device=self.device))
+    return dev.first_use(self._ws, batch_size, make, f'QNetworkTrainer: run one update at batch size {batch_size} before capturing it')
 
   def views(self, batch_size: int) -> dict:
     """The workspace's tensors of the last update at this batch size: 'acts' (every online layer's output, [B, ld] each), 'logits'
@@ -309,8 +280,8 @@ class QNetworkTrainer:
     """One update on a given batch: the per-row losses [B] (a view of a buffer the next update at this size overwrites)."""
     ws, _, loss = self.workspace(batch.batch_size)
     tr = self._struct(ws, apply_update)
-    _lib.check(self.lib.ble_qnet_train_step_f32(ctypes.byref(tr), ctypes.byref(batch.struct), loss.data_ptr(), self.err_flags.data_ptr(),
-                                                dev.stream_ptr(self.device)), 'ble_qnet_train_step_f32')
+    _lib.call('ble_qnet_train_step_f32', ctypes.byref(tr), ctypes.byref(batch.struct), loss.data_ptr(), self.err_flags.data_ptr(),
+              dev.stream_ptr(self.device))
     return loss[:batch.batch_size]
 
   @dev.on_own_device
@@ -327,7 +298,7 @@ class QNetworkTrainer:
   def _update(self, replay: VecReplayBuffer, batch_size: int) -> torch.Tensor:
     batch = replay.sample(batch_size, self.seed, self.counter)
     loss = self.train_on_batch(batch)
-    if getattr(replay, 'prioritized', False):       # sample -> update -> set_priority; the reported loss is the weighted one
+    if replay.prioritized:                          # sample -> update -> set_priority; the reported loss is the weighted one
       return replay.set_priority(batch, loss)
     return loss
 
@@ -357,16 +328,7 @@ class QNetworkTrainer:
   @dev.on_own_device
   def act(self, obs: torch.Tensor, out: torch.Tensor) -> torch.Tensor:
     """The online network's greedy actions (ble_qnet_forward_f32 on the live image) into out (uint8 [N])."""
-    n = obs.shape[0]
-    s = self._scratch.get(n)
-    if s is None:
-      sf = ctypes.c_int64()
-      _lib.check(self.lib.ble_qnet_workspace_f32(ctypes.byref(self._net), n, None, ctypes.byref(sf)), 'ble_qnet_workspace_f32')
-      s = self._scratch[n] = torch.empty(max(sf.value, 1), dtype=torch.float32, device=self.device)
-    stride = obs.stride(0) if n > 1 else max(obs.stride(0), _lib.OBS_DIM)
-    _lib.check(self.lib.ble_qnet_forward_f32(ctypes.byref(self._net), obs.data_ptr(), stride, s.data_ptr(), out.data_ptr(), None, n,
-                                             dev.stream_ptr(self.device)), 'ble_qnet_forward_f32')
-    return out
+    return self._forward(obs, out)
 
   # ---- export and checkpoints
   def params(self) -> dict:
@@ -379,8 +341,7 @@ class QNetworkTrainer:
   def state_dict(self) -> dict:
     return {'shape': (self.num_layers, self.hidden_units, self.num_atoms), 'seed': self.seed,
             'hyper': (self.lr, self.eps, self.b1, self.b2, self.kappa, self.gamma, self.update_horizon),
-            'weights': self.weights.clone(), 'target': self.target.clone(), 'adam_m': self.adam_m.clone(), 'adam_v': self.adam_v.clone(),
-            'adam_step': self.adam_step.clone(), 'counter': self.counter.clone()}
+            **{k: getattr(self, k).clone() for k in self._TENSORS}}
 
   def load_state_dict(self, d: dict) -> None:
     """Restores in place (every tensor keeps its address: captured graphs stay valid)."""
@@ -390,7 +351,7 @@ class QNetworkTrainer:
       self._graphs.clear()                     # (the seed and hyperparameters are arguments of the captured launches)
     self.seed = int(d['seed'])
     self.lr, self.eps, self.b1, self.b2, self.kappa, self.gamma, self.update_horizon = hyper
-    for k in ('weights', 'target', 'adam_m', 'adam_v', 'adam_step', 'counter'):
+    for k in self._TENSORS:
       getattr(self, k).copy_(d[k])
     self._retranspose()
 
@@ -403,12 +364,12 @@ def unpack(net: _abi.BleQnetF32, packed: np.ndarray) -> dict:
   biases = [np.zeros(dims[i + 1], np.float32) for i in range(net.num_layers)]
   kp = (ctypes.c_void_p * net.num_layers)(*[k.ctypes.data for k in kernels])
   bp = (ctypes.c_void_p * net.num_layers)(*[b.ctypes.data for b in biases])
-  _lib.check(_lib.lib().ble_qnet_unpack_f32(ctypes.byref(net), packed.ctypes.data, kp, bp), 'ble_qnet_unpack_f32')
+  _lib.call('ble_qnet_unpack_f32', ctypes.byref(net), packed.ctypes.data, kp, bp)
   return {'params': {f'Dense_{i}': {'kernel': k, 'bias': b} for i, (k, b) in enumerate(zip(kernels, biases))}}
 
 
 def explore(actions: torch.Tensor, epsilon: float, seed: int, step: int) -> torch.Tensor:
   """epsilon-greedy in place on uint8 device actions (ble_qnet_explore_u8): keyed by (seed, environment, step)."""
   ex = _abi.BleExploreF32(actions.numel(), float(epsilon), 0, int(seed) & (2 ** 64 - 1), int(step) & (2 ** 64 - 1))
-  _lib.check(_lib.lib().ble_qnet_explore_u8(ctypes.byref(ex), actions.data_ptr(), dev.stream_ptr(actions.device)), 'ble_qnet_explore_u8')
+  _lib.call('ble_qnet_explore_u8', ctypes.byref(ex), actions.data_ptr(), dev.stream_ptr(actions.device))
   return actions

@@ -38,6 +38,7 @@
 #include "ble_agent.h"
 #include "ble_qnet.h"
 #include "ble_train.h"
+#include "ble_explore.h"
 #include "ble_replay.h"
 
 using namespace ble;
@@ -964,74 +965,6 @@ int launch_observe(const ble_state_f32* st, const ble_fleet* fleet, const float*
 
 }  // namespace
 
-// Q-network agents: the descriptor checks and sizes of ble_qnet_*_f32
-namespace {
-bool qnet_ok(const ble_qnet_f32* net) {
-  return net != nullptr && net->num_layers >= 1 && net->num_layers <= kQnetMaxLayers && net->input_dim == BLE_OBS_DIM &&
-         net->num_actions == 3 && net->num_atoms >= 1 && net->num_atoms <= kQnetMaxAtoms &&
-         (net->num_layers == 1 || (net->hidden_units >= 1 && net->hidden_units <= kQnetMaxHidden));
-}
-QnetLayerDims qnet_dims(const ble_qnet_f32* net, int l) {
-  return qnet_layer(net->num_layers, net->input_dim, net->hidden_units, net->num_actions, net->num_atoms, l);
-}
-// floats per scratch row: the widest padded output of any layer
-int64_t qnet_scratch_ld(const ble_qnet_f32* net) {
-  int64_t ld = 0;
-  for (int l = 0; l < net->num_layers; ++l) ld = std::max<int64_t>(ld, qnet_dims(net, l).mp);
-  return ld;
-}
-bool replay_ok(const ble_replay_f32* rp) {
-  return rp != nullptr && rp->update_horizon >= 1 && rp->update_horizon <= BLE_REPLAY_MAX_HORIZON && rp->capacity >= rp->update_horizon + 1 &&
-         rp->capacity <= (1LL << 40) && rp->num_envs >= 1 && rp->num_envs <= (1LL << 32) && rp->obs_stride >= BLE_OBS_DIM &&
-         rp->obs_stride % 4 == 0 && std::isfinite(rp->gamma) && rp->max_tries >= 1 && rp->max_tries <= BLE_REPLAY_MAX_TRIES && rp->obs &&
-         (reinterpret_cast<uintptr_t>(rp->obs) & 15) == 0 && rp->action && rp->reward && rp->terminal && rp->episode_end && rp->count &&
-         rp->counter;
-}
-bool batch_ok(const ble_train_batch_f32* bt) {
-  return bt != nullptr && bt->batch >= 0 && bt->batch <= BLE_TRAIN_MAX_BATCH && bt->state_stride >= BLE_OBS_DIM && bt->state_stride % 4 == 0 &&
-         bt->state_stride <= (1LL << 20) && bt->state && bt->next_state && bt->ret && bt->discount && bt->action &&
-         ((reinterpret_cast<uintptr_t>(bt->state) | reinterpret_cast<uintptr_t>(bt->next_state)) & 15) == 0;
-}
-TrainDims train_dims(const ble_qnet_f32* net) {
-  TrainDims t{};
-  t.layers = net->num_layers;
-  int64_t toff = 0;
-  for (int l = 0; l < net->num_layers; ++l) {
-    const QnetLayerDims d = qnet_dims(net, l);
-    t.offset[l] = d.offset;
-    t.offset[l + 1] = d.offset + (int64_t)d.kp * d.mp + d.mp;
-    t.k[l] = d.k; t.m[l] = d.m; t.kp[l] = d.kp; t.mp[l] = d.mp;
-    t.toffset[l] = toff;
-    if (l > 0) toff += qnet_round_up(d.m, kQnetChunk) * qnet_dims(net, l - 1).mp;      // kp' = round8(M_l), mp' = round64(K_l)
-  }
-  return t;
-}
-ble_qnet_train_layout train_layout(const ble_qnet_f32* net, int64_t n) {
-  ble_qnet_train_layout y{};
-  const int64_t ld = qnet_scratch_ld(net), L = net->num_layers;
-  int64_t blk = 0, tfl = 0;
-  for (int l = 0; l < L; ++l) {
-    const QnetLayerDims d = qnet_dims(net, l);
-    blk = std::max<int64_t>(blk, (int64_t)d.kp * d.mp + d.mp);
-    if (l > 0) tfl += qnet_round_up(d.m, kQnetChunk) * qnet_dims(net, l - 1).mp;
-  }
-  y.ld = ld;
-  y.slabs = wgrad_slabs(n);
-  int64_t at = 0;
-  auto take = [&](int64_t floats) { const int64_t o = at; at += qnet_round_up(floats, 64); return o; };
-  y.acts = take(L * n * ld);
-  y.target_logits = take(n * ld);
-  y.targets = take(n * net->num_atoms);
-  y.dlogits = take(n * ld);
-  y.scratch = take(4 * n * ld);
-  y.partial = take(y.slabs > 1 ? y.slabs * blk : 0);
-  y.corrections = take(4);
-  y.total = at;
-  y.transposed_floats = tfl;
-  return y;
-}
-}  // namespace
-
 extern "C" {
 
 int ble_abi_version(void) { return BLE_ABI_VERSION; }
@@ -1225,168 +1158,247 @@ int ble_station_seeker_f32(const float* obs, int64_t obs_row_stride, uint8_t* ac
   return launch(ble_station_seeker_kernel, n, kSeekerBlock / 64, kSeekerBlock, stream, obs, obs_row_stride, action, level, scores, err_flags, n);
 }
 
+}  // extern "C"
+
+// ---------------------------------------------------------------------------------------------------------------- Q-network host code
+// The descriptor checks, the sizes and the launchers of ble_qnet_*_f32 and ble_replay_*.
+namespace {
+bool qnet_ok(const ble_qnet_f32* net) {
+  return net != nullptr && net->num_layers >= 1 && net->num_layers <= kQnetMaxLayers && net->input_dim == BLE_OBS_DIM &&
+         net->num_actions == 3 && net->num_atoms >= 1 && net->num_atoms <= kQnetMaxAtoms &&
+         (net->num_layers == 1 || (net->hidden_units >= 1 && net->hidden_units <= kQnetMaxHidden));
+}
+// the shape table of a checked descriptor
+QnetShape qnet_shape(const ble_qnet_f32* net) {
+  return ble::qnet_shape(net->num_layers, net->input_dim, net->hidden_units, net->num_actions, net->num_atoms);
+}
+// every pointer is a multiple of mask + 1 bytes (NULL is)
+template <class... T>
+bool aligned(uintptr_t mask, const T*... ptrs) {
+  return ((reinterpret_cast<uintptr_t>(ptrs) | ...) & mask) == 0;
+}
+bool replay_ok(const ble_replay_f32* rp) {
+  return rp != nullptr && rp->update_horizon >= 1 && rp->update_horizon <= BLE_REPLAY_MAX_HORIZON && rp->capacity >= rp->update_horizon + 1 &&
+         rp->capacity <= (1LL << 40) && rp->num_envs >= 1 && rp->num_envs <= (1LL << 32) && rp->obs_stride >= BLE_OBS_DIM &&
+         rp->obs_stride % 4 == 0 && std::isfinite(rp->gamma) && rp->max_tries >= 1 && rp->max_tries <= BLE_REPLAY_MAX_TRIES && rp->obs &&
+         aligned(15, rp->obs) && rp->action && rp->reward && rp->terminal && rp->episode_end && rp->count && rp->counter;
+}
+bool batch_ok(const ble_train_batch_f32* bt) {
+  return bt != nullptr && bt->batch >= 0 && bt->batch <= BLE_TRAIN_MAX_BATCH && bt->state_stride >= BLE_OBS_DIM && bt->state_stride % 4 == 0 &&
+         bt->state_stride <= (1LL << 20) && bt->state && bt->next_state && bt->ret && bt->discount && bt->action &&
+         aligned(15, bt->state, bt->next_state);
+}
+ble_qnet_train_layout train_layout(const QnetShape& s, int num_atoms, int64_t n) {
+  ble_qnet_train_layout y{};
+  const int64_t ld = s.ld, L = s.layers;
+  y.ld = ld;
+  y.slabs = wgrad_slabs(n);
+  int64_t at = 0;
+  auto take = [&](int64_t floats) { const int64_t o = at; at += qnet_round_up(floats, 64); return o; };
+  y.acts = take(L * n * ld);
+  y.target_logits = take(n * ld);
+  y.targets = take(n * num_atoms);
+  y.dlogits = take(n * ld);
+  y.scratch = take(4 * n * ld);
+  y.partial = take(y.slabs > 1 ? y.slabs * s.max_block : 0);
+  y.corrections = take(4);
+  y.total = at;
+  y.transposed_floats = s.transposed_floats;
+  return y;
+}
+bool tree_ok(const ble_replay_f32* rp, const ble_sum_tree_f64* tr) {
+  return tr != nullptr && tr->leaves == rp->capacity * rp->num_envs && tr->leaves <= BLE_SUM_TREE_MAX_LEAVES && tr->padded >= tr->leaves &&
+         (tr->padded & (tr->padded - 1)) == 0 && (tr->padded == 1 || tr->padded / 2 < tr->leaves) && tr->nodes && tr->max_priority &&
+         aligned(7, tr->nodes, tr->max_priority);
+}
+// the per-layer host arrays of ble_qnet_pack_f32 / ble_qnet_unpack_f32
+bool layers_ok(const ble_qnet_f32* net, const float* const* kernel, const float* const* bias) {
+  if (!kernel || !bias) return false;
+  for (int l = 0; l < net->num_layers; ++l)
+    if (!kernel[l] || !bias[l]) return false;
+  return true;
+}
+
+// A sampler kernel, one workgroup per batch row, then the update counter the draws are keyed by advances; B == 0 launches nothing.
+template <class... P, class... A>
+int launch_sample_then_advance(void (*kernel)(P...), const ble_replay_f32* rp, const ble_train_batch_f32* bt, void* stream, const A&... args) {
+  if (bt->batch == 0) return BLE_OK;
+  const int status = launch_grid(kernel, dim3((unsigned)bt->batch), kReplayBlock, stream, args...);
+  if (status != BLE_OK) return status;
+  return launch_grid(ble_train_advance_kernel, dim3(1), 1, stream, rp->counter);
+}
+
+// Where layer l of a Dense stack writes its n rows of ld floats: base + (keep ? l : l & 1) n ld -- every layer kept, or two buffers
+// in turn -- and the last layer to `last` instead when that is set.
+struct DenseOut {
+  float* base;
+  bool keep;
+  float* last;
+};
+// The Dense stack of shape s over the weight image w, on n rows of x (row stride ldx).  The first layer reads the caller's rows, the
+// others the previous layer's activations; ReLU after every layer but the last.  Returns the first failing status.
+int launch_dense_stack(const QnetShape& s, const float* w, const float* x, int64_t ldx, int64_t n, DenseOut out, void* stream) {
+  const unsigned row_tiles = (unsigned)((n + kQnetRows - 1) / kQnetRows);
+  for (int l = 0; l < s.layers; ++l) {
+    const int groups = s.mp[l] / kQnetCols;
+    const bool first = l == 0, last = l == s.layers - 1;
+    const auto dense = first ? (last ? ble_qnet_dense_kernel<true, false> : ble_qnet_dense_kernel<true, true>)
+                             : (last ? ble_qnet_dense_kernel<false, false> : ble_qnet_dense_kernel<false, true>);
+    float* y = last && out.last ? out.last : out.base + (out.keep ? l : l & 1) * n * s.ld;
+    const int status = launch_grid(dense, dim3((unsigned)groups * row_tiles), kQnetBlock, stream, x, ldx, s.k[l], s.kp[l], w + s.offset[l], y,
+                                   s.ld, groups, n);
+    if (status != BLE_OK) return status;
+    x = y;
+    ldx = s.ld;
+  }
+  return BLE_OK;
+}
+
+bool train_step_ok(const ble_qnet_train_f32* tr, const ble_train_batch_f32* bt, const float* loss) {
+  if (!tr || !qnet_ok(&tr->net) || !batch_ok(bt) || !loss || !tr->net.weights || !tr->target || !tr->grad || !tr->workspace ||
+      !(tr->kappa > 0.0f) || !std::isfinite(tr->kappa))
+    return false;
+  if (tr->net.num_layers > 1 && !tr->weights_t) return false;
+  if (tr->apply_update && (!tr->adam_m || !tr->adam_v || !tr->adam_step ||
+                           !std::isfinite(tr->lr) || !std::isfinite(tr->adam_b1) || !std::isfinite(tr->adam_b2) || !std::isfinite(tr->adam_eps)))
+    return false;
+  return aligned(15, tr->net.weights, tr->target, tr->grad, tr->workspace, tr->adam_m, tr->adam_v, tr->weights_t);
+}
+
+// One update of ble_qnet_train_step_f32 on a checked, non-empty batch: the shape, the workspace's parts and the four stages in launch
+// order.  Every stage returns the first failing status.
+struct TrainStep {
+  const ble_qnet_train_f32* tr;
+  const ble_train_batch_f32* bt;
+  void* stream;
+  const QnetShape s;
+  const ble_qnet_train_layout lay;
+  const int64_t n, ld;
+  float* const ws;
+
+  TrainStep(const ble_qnet_train_f32* tr_, const ble_train_batch_f32* bt_, void* stream_)
+      : tr(tr_), bt(bt_), stream(stream_), s(qnet_shape(&tr_->net)), lay(train_layout(s, tr_->net.num_atoms, bt_->batch)), n(bt_->batch),
+        ld(lay.ld), ws(tr_->workspace) {}
+  float* acts(int l) const { return ws + lay.acts + l * n * ld; }      // the online network's kept output of layer l
+
+  // the target's pass on next_state (ping-pong, its logits end in target_logits), then the online one on state (every layer kept)
+  int forward() const {
+    const int status = launch_dense_stack(s, tr->target, bt->next_state, bt->state_stride, n,
+                                          DenseOut{ws + lay.scratch, false, ws + lay.target_logits}, stream);
+    if (status != BLE_OK) return status;
+    return launch_dense_stack(s, tr->net.weights, bt->state, bt->state_stride, n, DenseOut{acts(0), true, nullptr}, stream);
+  }
+  int loss(float* row_loss, uint32_t* err_flags) const {
+    return launch_grid(ble_qr_loss_kernel, dim3((unsigned)n), kTrainLossBlock, stream, acts(s.layers - 1),
+                       (const float*)(ws + lay.target_logits), ld, tr->net.num_actions, tr->net.num_atoms, (const float*)bt->ret,
+                       (const float*)bt->discount, (const uint8_t*)bt->action, tr->kappa, n, ws + lay.targets, ws + lay.dlogits, row_loss,
+                       err_flags);
+  }
+  // from the last layer: dW (+ db) over the batch slabs, their reduction, then dX for the layer below
+  int backward() const {
+    float* dyb[2] = {ws + lay.scratch + 2 * n * ld, ws + lay.scratch + 3 * n * ld};
+    const unsigned row_tiles = (unsigned)((n + kQnetRows - 1) / kQnetRows);
+    const int slabs = (int)lay.slabs;
+    const int64_t slab_rows = slabs == 1 ? n : (n + slabs - 1) / slabs;
+    const float* dy = ws + lay.dlogits;
+    for (int l = s.layers - 1; l >= 0; --l) {
+      const int64_t blk = s.block(l);
+      float* dst = slabs == 1 ? tr->grad + s.offset[l] : ws + lay.partial;
+      const float* x = l == 0 ? bt->state : acts(l - 1);
+      int status = launch_grid(ble_qnet_wgrad_kernel, dim3((unsigned)((s.kp[l] + 31) / 32), (unsigned)(s.mp[l] / kQnetCols), (unsigned)slabs),
+                               64, stream, x, l == 0 ? bt->state_stride : ld, s.k[l], s.kp[l], dy, ld, s.m[l], s.mp[l], n, slab_rows, dst,
+                               blk);
+      if (status != BLE_OK) return status;
+      if (slabs > 1) {
+        status = launch(ble_wgrad_reduce_kernel, blk, 256, 256, stream, (const float*)(ws + lay.partial), slabs, blk, blk,
+                        tr->grad + s.offset[l]);
+        if (status != BLE_OK) return status;
+      }
+      if (l == 0) break;
+      const int groups = s.mpt(l) / kQnetCols;
+      float* dx = dyb[l & 1];
+      status = launch_grid(ble_qnet_dgrad_kernel, dim3((unsigned)groups * row_tiles), kQnetBlock, stream, dy, ld, s.kpt(l),
+                           (const float*)(tr->weights_t + s.toffset[l]), (const float*)acts(l - 1), dx, groups, n);
+      if (status != BLE_OK) return status;
+      dy = dx;
+    }
+    return BLE_OK;
+  }
+  int adam() const {
+    float* corr = ws + lay.corrections;
+    const int status = launch_grid(ble_adam_prologue_kernel, dim3(1), 1, stream, tr->adam_step, tr->adam_b1, tr->adam_b2, corr);
+    if (status != BLE_OK) return status;
+    return launch(ble_adam_kernel, s.offset[s.layers], kAdamBlock, kAdamBlock, stream, const_cast<float*>(tr->net.weights), tr->weights_t,
+                  (const float*)tr->grad, tr->adam_m, tr->adam_v, (const float*)corr, tr->lr, (float)tr->adam_b1,
+                  (float)(1.0 - tr->adam_b1), (float)tr->adam_b2, (float)(1.0 - tr->adam_b2), tr->adam_eps, s);
+  }
+};
+}  // namespace
+
+extern "C" {
+
 // ---------------------------------------------------------------------------------------------------------------- Q-network agents
 int ble_qnet_workspace_f32(const ble_qnet_f32* net, int64_t n, int64_t* packed_floats, int64_t* scratch_floats) {
   if (!qnet_ok(net) || n < 0) return BLE_E_INVALID_ARG;
-  if (packed_floats != nullptr) {
-    const QnetLayerDims last = qnet_dims(net, net->num_layers - 1);
-    *packed_floats = last.offset + (int64_t)last.kp * last.mp + last.mp;
-  }
-  if (scratch_floats != nullptr) *scratch_floats = 2 * n * qnet_scratch_ld(net);
+  const QnetShape s = qnet_shape(net);
+  if (packed_floats != nullptr) *packed_floats = s.offset[s.layers];
+  if (scratch_floats != nullptr) *scratch_floats = 2 * n * s.ld;
   return BLE_OK;
 }
 
 int ble_qnet_pack_f32(const ble_qnet_f32* net, const float* const* kernel, const float* const* bias, float* packed) {
-  if (!qnet_ok(net) || !kernel || !bias || !packed) return BLE_E_INVALID_ARG;
-  for (int l = 0; l < net->num_layers; ++l)
-    if (!kernel[l] || !bias[l]) return BLE_E_INVALID_ARG;
-  qnet_pack(net->num_layers, net->input_dim, net->hidden_units, net->num_actions, net->num_atoms, kernel, bias, packed);
+  if (!qnet_ok(net) || !layers_ok(net, kernel, bias) || !packed) return BLE_E_INVALID_ARG;
+  qnet_pack(qnet_shape(net), kernel, bias, packed);
   return BLE_OK;
 }
 
 int ble_qnet_forward_f32(const ble_qnet_f32* net, const float* obs, int64_t obs_row_stride, float* scratch, uint8_t* action,
                          float* q_values, int64_t n, void* stream) {
   if (!qnet_ok(net) || !net->weights || !obs || !scratch || !action || n < 0 || obs_row_stride < BLE_OBS_DIM) return BLE_E_INVALID_ARG;
-  if ((reinterpret_cast<uintptr_t>(net->weights) | reinterpret_cast<uintptr_t>(scratch)) & 15) return BLE_E_INVALID_ARG;
-  const int64_t ld = qnet_scratch_ld(net);
+  if (!aligned(15, net->weights, scratch)) return BLE_E_INVALID_ARG;
+  const QnetShape s = qnet_shape(net);
+  const int64_t ld = s.ld;
   if ((ld / kQnetCols) * ((n + kQnetRows - 1) / kQnetRows) > 2147483647LL) return BLE_E_INVALID_ARG;
   if (n == 0) return BLE_OK;
-  float* buf[2] = {scratch, scratch + n * ld};
-  for (int l = 0; l < net->num_layers; ++l) {
-    const QnetLayerDims d = qnet_dims(net, l);
-    const int groups = d.mp / kQnetCols;
-    const dim3 grid((unsigned)(groups * ((n + kQnetRows - 1) / kQnetRows)));
-    // the first layer reads the observation rows, the others the previous layer's activations; ReLU after every layer but the last
-    const bool first = l == 0, last = l == net->num_layers - 1;
-    const auto dense = first ? (last ? ble_qnet_dense_kernel<true, false> : ble_qnet_dense_kernel<true, true>)
-                             : (last ? ble_qnet_dense_kernel<false, false> : ble_qnet_dense_kernel<false, true>);
-    const int status = launch_grid(dense, grid, kQnetBlock, stream, first ? obs : buf[(l - 1) & 1], first ? obs_row_stride : ld, d.k, d.kp,
-                                   net->weights + d.offset, buf[l & 1], ld, groups, n);
-    if (status != BLE_OK) return status;
-  }
-  return launch(ble_qnet_head_kernel, n, kQnetHeadBlock, kQnetHeadBlock, stream, buf[(net->num_layers - 1) & 1], ld, net->num_actions,
+  const int status = launch_dense_stack(s, net->weights, obs, obs_row_stride, n, DenseOut{scratch, false, nullptr}, stream);
+  if (status != BLE_OK) return status;
+  return launch(ble_qnet_head_kernel, n, kQnetHeadBlock, kQnetHeadBlock, stream, scratch + ((s.layers - 1) & 1) * n * ld, ld, net->num_actions,
                 net->num_atoms, action, q_values, n);
 }
 
 // ---------------------------------------------------------------------------------------------------------------- Q-network training
 int ble_qnet_unpack_f32(const ble_qnet_f32* net, const float* packed, float* const* kernel, float* const* bias) {
-  if (!qnet_ok(net) || !packed || !kernel || !bias) return BLE_E_INVALID_ARG;
-  for (int l = 0; l < net->num_layers; ++l)
-    if (!kernel[l] || !bias[l]) return BLE_E_INVALID_ARG;
-  qnet_unpack(net->num_layers, net->input_dim, net->hidden_units, net->num_actions, net->num_atoms, packed, kernel, bias);
+  if (!qnet_ok(net) || !packed || !layers_ok(net, kernel, bias)) return BLE_E_INVALID_ARG;
+  qnet_unpack(qnet_shape(net), packed, kernel, bias);
   return BLE_OK;
 }
 
 int ble_replay_sample_f32(const ble_replay_f32* rp, const ble_train_batch_f32* bt, unsigned long long seed, uint32_t* err_flags,
                           void* stream) {
   if (!replay_ok(rp) || !batch_ok(bt)) return BLE_E_INVALID_ARG;
-  if (bt->batch == 0) return BLE_OK;
-  const int status = launch_grid(ble_replay_sample_kernel, dim3((unsigned)bt->batch), kReplayBlock, stream, *rp, *bt, (uint64_t)seed, err_flags);
-  if (status != BLE_OK) return status;
-  return launch_grid(ble_train_advance_kernel, dim3(1), 1, stream, rp->counter);
+  return launch_sample_then_advance(ble_replay_sample_kernel, rp, bt, stream, *rp, *bt, (uint64_t)seed, err_flags);
 }
 
 int ble_qnet_train_workspace_f32(const ble_qnet_train_f32* tr, const ble_train_batch_f32* bt, ble_qnet_train_layout* out) {
   if (!tr || !qnet_ok(&tr->net) || !bt || bt->batch < 0 || bt->batch > BLE_TRAIN_MAX_BATCH || !out) return BLE_E_INVALID_ARG;
-  *out = train_layout(&tr->net, bt->batch);
+  *out = train_layout(qnet_shape(&tr->net), tr->net.num_atoms, bt->batch);
   return BLE_OK;
 }
 
 int ble_qnet_transpose_f32(const ble_qnet_f32* net, const float* packed, float* packed_t) {
   if (!qnet_ok(net) || !packed || !packed_t) return BLE_E_INVALID_ARG;
-  const TrainDims dims = train_dims(net);
-  for (int l = 1; l < dims.layers; ++l) {
-    const int kpt = (int)qnet_round_up(dims.m[l], kQnetChunk), mpt = dims.mp[l - 1];
-    for (int64_t e = 0; e < (int64_t)kpt * mpt; ++e) packed_t[dims.toffset[l] + e] = 0.0f;
-    const float* p = packed + dims.offset[l];
-    for (int g = 0; g < dims.mp[l] / kQnetCols; ++g)
-      for (int c = 0; c < dims.kp[l] / kQnetChunk; ++c)
-        for (int t = 0; t < 2; ++t)
-          for (int lane = 0; lane < 64; ++lane)
-            for (int j = 0; j < 4; ++j) {
-              const int k = kQnetChunk * c + 4 * (lane >> 5) + j, m = kQnetCols * g + 32 * t + (lane & 31);
-              const float v = *p++;
-              if (k < dims.k[l] && m < dims.m[l]) packed_t[dims.toffset[l] + qnet_transposed_index(k, m, kpt)] = v;
-            }
-  }
+  qnet_transpose(qnet_shape(net), packed, packed_t);
   return BLE_OK;
 }
 
 int ble_qnet_train_step_f32(const ble_qnet_train_f32* tr, const ble_train_batch_f32* bt, float* loss, uint32_t* err_flags, void* stream) {
-  if (!tr || !qnet_ok(&tr->net) || !batch_ok(bt) || !loss || !tr->net.weights || !tr->target || !tr->grad || !tr->workspace ||
-      !(tr->kappa > 0.0f) || !std::isfinite(tr->kappa))
-    return BLE_E_INVALID_ARG;
-  if (tr->net.num_layers > 1 && !tr->weights_t) return BLE_E_INVALID_ARG;
-  if (tr->apply_update && (!tr->adam_m || !tr->adam_v || !tr->adam_step ||
-                           !std::isfinite(tr->lr) || !std::isfinite(tr->adam_b1) || !std::isfinite(tr->adam_b2) || !std::isfinite(tr->adam_eps)))
-    return BLE_E_INVALID_ARG;
-  const uintptr_t align = reinterpret_cast<uintptr_t>(tr->net.weights) | reinterpret_cast<uintptr_t>(tr->target) |
-                          reinterpret_cast<uintptr_t>(tr->grad) | reinterpret_cast<uintptr_t>(tr->workspace) |
-                          reinterpret_cast<uintptr_t>(tr->adam_m) | reinterpret_cast<uintptr_t>(tr->adam_v) |
-                          reinterpret_cast<uintptr_t>(tr->weights_t);
-  if (align & 15) return BLE_E_INVALID_ARG;
-  const int64_t n = bt->batch;
-  if (n == 0) return BLE_OK;
-  const ble_qnet_f32* net = &tr->net;
-  const ble_qnet_train_layout lay = train_layout(net, n);
-  const TrainDims dims = train_dims(net);
-  const int L = net->num_layers;
-  const int64_t ld = lay.ld;
-  float* ws = tr->workspace;
-  float* acts = ws + lay.acts;
-  float* tbuf[2] = {ws + lay.scratch, ws + lay.scratch + n * ld};
-  float* dyb[2] = {ws + lay.scratch + 2 * n * ld, ws + lay.scratch + 3 * n * ld};
-  const unsigned row_tiles = (unsigned)((n + kQnetRows - 1) / kQnetRows);
-  int status = BLE_OK;
-  // the two forward passes: the target's on next_state (ping-pong, its logits end in target_logits), the online one on state (kept)
-  for (int pass = 0; pass < 2; ++pass) {
-    const bool online = pass == 1;
-    const float* wimg = online ? net->weights : tr->target;
-    for (int l = 0; l < L && status == BLE_OK; ++l) {
-      const QnetLayerDims d = qnet_dims(net, l);
-      const int groups = d.mp / kQnetCols;
-      const bool first = l == 0, last = l == L - 1;
-      const auto dense = first ? (last ? ble_qnet_dense_kernel<true, false> : ble_qnet_dense_kernel<true, true>)
-                               : (last ? ble_qnet_dense_kernel<false, false> : ble_qnet_dense_kernel<false, true>);
-      const float* x = first ? (online ? bt->state : bt->next_state) : (online ? acts + (l - 1) * n * ld : tbuf[(l - 1) & 1]);
-      float* y = online ? acts + l * n * ld : (last ? ws + lay.target_logits : tbuf[l & 1]);
-      status = launch_grid(dense, dim3((unsigned)groups * row_tiles), kQnetBlock, stream, x, first ? bt->state_stride : ld, d.k, d.kp,
-                           wimg + d.offset, y, ld, groups, n);
-    }
-  }
-  if (status != BLE_OK) return status;
-  status = launch_grid(ble_qr_loss_kernel, dim3((unsigned)n), kTrainLossBlock, stream, acts + (L - 1) * n * ld,
-                       (const float*)(ws + lay.target_logits), ld, net->num_actions, net->num_atoms, (const float*)bt->ret,
-                       (const float*)bt->discount, (const uint8_t*)bt->action, tr->kappa, n, ws + lay.targets, ws + lay.dlogits, loss,
-                       err_flags);
-  // backward, from the last layer
-  const int slabs = (int)lay.slabs;
-  const int64_t slab_rows = slabs == 1 ? n : (n + slabs - 1) / slabs;
-  const float* dy = ws + lay.dlogits;
-  for (int l = L - 1; l >= 0 && status == BLE_OK; --l) {
-    const QnetLayerDims d = qnet_dims(net, l);
-    const int64_t blk = (int64_t)d.kp * d.mp + d.mp;
-    float* dst = slabs == 1 ? tr->grad + d.offset : ws + lay.partial;
-    const float* x = l == 0 ? bt->state : acts + (l - 1) * n * ld;
-    status = launch_grid(ble_qnet_wgrad_kernel, dim3((unsigned)((d.kp + 31) / 32), (unsigned)(d.mp / kQnetCols), (unsigned)slabs), 64, stream,
-                         x, l == 0 ? bt->state_stride : ld, d.k, d.kp, dy, ld, d.m, d.mp, n, slab_rows, dst, blk);
-    if (status == BLE_OK && slabs > 1)
-      status = launch(ble_wgrad_reduce_kernel, blk, 256, 256, stream, (const float*)(ws + lay.partial), slabs, blk, blk, tr->grad + d.offset);
-    if (status == BLE_OK && l > 0) {
-      const int kpt = (int)qnet_round_up(d.m, kQnetChunk), groups = dims.mp[l - 1] / kQnetCols;
-      float* dx = dyb[l & 1];
-      status = launch_grid(ble_qnet_dgrad_kernel, dim3((unsigned)groups * row_tiles), kQnetBlock, stream, dy, ld, kpt,
-                           (const float*)(tr->weights_t + dims.toffset[l]), (const float*)(acts + (l - 1) * n * ld), dx, groups, n);
-      dy = dx;
-    }
-  }
-  if (status != BLE_OK || !tr->apply_update) return status;
-  float* corr = ws + lay.corrections;
-  status = launch_grid(ble_adam_prologue_kernel, dim3(1), 1, stream, tr->adam_step, tr->adam_b1, tr->adam_b2, corr);
-  if (status != BLE_OK) return status;
-  return launch(ble_adam_kernel, dims.offset[L], kAdamBlock, kAdamBlock, stream, const_cast<float*>(net->weights),
-                tr->weights_t, (const float*)tr->grad, tr->adam_m, tr->adam_v, (const float*)corr, tr->lr, (float)tr->adam_b1,
-                (float)(1.0 - tr->adam_b1), (float)tr->adam_b2, (float)(1.0 - tr->adam_b2), tr->adam_eps, dims);
+  if (!train_step_ok(tr, bt, loss)) return BLE_E_INVALID_ARG;
+  if (bt->batch == 0) return BLE_OK;
+  const TrainStep t(tr, bt, stream);
+  if (const int status = t.forward(); status != BLE_OK) return status;
+  if (const int status = t.loss(loss, err_flags); status != BLE_OK) return status;
+  if (const int status = t.backward(); status != BLE_OK) return status;
+  return tr->apply_update ? t.adam() : BLE_OK;
 }
 
 int ble_qnet_explore_u8(const ble_explore_f32* ex, uint8_t* action, void* stream) {
@@ -1395,14 +1407,6 @@ int ble_qnet_explore_u8(const ble_explore_f32* ex, uint8_t* action, void* stream
 }
 
 // ---------------------------------------------------------------------------------------------------------------- prioritized replay
-namespace {
-bool tree_ok(const ble_replay_f32* rp, const ble_sum_tree_f64* tr) {
-  return tr != nullptr && tr->leaves == rp->capacity * rp->num_envs && tr->leaves <= BLE_SUM_TREE_MAX_LEAVES && tr->padded >= tr->leaves &&
-         (tr->padded & (tr->padded - 1)) == 0 && (tr->padded == 1 || tr->padded / 2 < tr->leaves) && tr->nodes && tr->max_priority &&
-         ((reinterpret_cast<uintptr_t>(tr->nodes) | reinterpret_cast<uintptr_t>(tr->max_priority)) & 7) == 0;
-}
-}  // namespace
-
 int ble_replay_tree_add_f64(const ble_replay_f32* rp, const ble_sum_tree_f64* tr, void* stream) {
   if (!replay_ok(rp) || !tree_ok(rp, tr)) return BLE_E_INVALID_ARG;
   return launch_grid(ble_tree_add_kernel, dim3(1), kTreeBlock, stream, *rp, *tr);
@@ -1411,11 +1415,7 @@ int ble_replay_tree_add_f64(const ble_replay_f32* rp, const ble_sum_tree_f64* tr
 int ble_replay_sample_prioritized_f32(const ble_replay_f32* rp, const ble_sum_tree_f64* tr, const ble_train_batch_f32* bt, float* priority,
                                       unsigned long long seed, uint32_t* err_flags, void* stream) {
   if (!replay_ok(rp) || !tree_ok(rp, tr) || !batch_ok(bt) || !bt->index || !priority) return BLE_E_INVALID_ARG;
-  if (bt->batch == 0) return BLE_OK;
-  const int status = launch_grid(ble_replay_sample_prio_kernel, dim3((unsigned)bt->batch), kReplayBlock, stream, *rp, *tr, *bt, priority,
-                                 (uint64_t)seed, err_flags);
-  if (status != BLE_OK) return status;
-  return launch_grid(ble_train_advance_kernel, dim3(1), 1, stream, rp->counter);
+  return launch_sample_then_advance(ble_replay_sample_prio_kernel, rp, bt, stream, *rp, *tr, *bt, priority, (uint64_t)seed, err_flags);
 }
 
 int ble_replay_set_priority_f32(const ble_replay_f32* rp, const ble_sum_tree_f64* tr, const ble_train_batch_f32* bt, const float* priority,
@@ -1429,8 +1429,7 @@ int ble_replay_set_priority_f32(const ble_replay_f32* rp, const ble_sum_tree_f64
 int ble_marco_polo_u8(const ble_marco_polo_f32* mp, uint8_t* action, void* stream) {
   if (!mp || !action || mp->n < 0 || mp->n > 4LL * 2147483647LL * 256 || mp->obs_stride < 1 ||
       !(mp->exploratory_episode_probability >= 0.0 && mp->exploratory_episode_probability <= 1.0) || !mp->obs || !mp->begin || !mp->step ||
-      !mp->phase_clock || !mp->walk_clock || !mp->exploratory_episode || !mp->exploratory_phase || !mp->target ||
-      (reinterpret_cast<uintptr_t>(mp->target) & 7) != 0)
+      !mp->phase_clock || !mp->walk_clock || !mp->exploratory_episode || !mp->exploratory_phase || !mp->target || !aligned(7, mp->target))
     return BLE_E_INVALID_ARG;
   if (mp->n == 0) return BLE_OK;
   const int status = launch(ble_marco_polo_kernel, mp->n, 256, 256, stream, *mp, action);

@@ -31,24 +31,58 @@ typedef float qnet_f32x16 __attribute__((ext_vector_type(16)));
 
 __host__ __device__ inline int64_t qnet_round_up(int64_t v, int64_t m) { return (v + m - 1) / m * m; }
 
-// Padded sizes of layer l of a network: inputs (Kp) and outputs (Mp) of the packed block.
-struct QnetLayerDims {
-  int k, m;            // the reference's in / out features
-  int kp, mp;          // padded
-  int64_t offset;      // of the layer's packed kernel, in floats from the start of the weights; its bias follows at offset + kp * mp
+// The per-layer shape of a network (the part of the shape table ble_adam_kernel takes by value): layer l maps k[l] inputs to m[l] outputs,
+// padded to kp[l] and mp[l].
+struct TrainDims {
+  int layers;
+  int64_t offset[kQnetMaxLayers + 1];        // packed block of layer l (its bias follows at + kp * mp); offset[layers] = the image's size
+  int64_t toffset[kQnetMaxLayers];           // its transposed block in weights_t (l >= 1)
+  int k[kQnetMaxLayers], m[kQnetMaxLayers], kp[kQnetMaxLayers], mp[kQnetMaxLayers];
 };
 
-inline QnetLayerDims qnet_layer(int num_layers, int input_dim, int hidden, int num_actions, int num_atoms, int l) {
-  QnetLayerDims d;
-  d.offset = 0;
-  for (int i = 0; i <= l; ++i) {
-    d.k = i == 0 ? input_dim : hidden;
-    d.m = i == num_layers - 1 ? num_actions * num_atoms : hidden;
-    d.kp = (int)qnet_round_up(d.k, kQnetChunk);
-    d.mp = (int)qnet_round_up(d.m, kQnetCols);
-    if (i < l) d.offset += (int64_t)d.kp * d.mp + d.mp;
+// The shape table of a network: every size the host code needs, built once per entry-point call by qnet_shape.
+struct QnetShape : TrainDims {
+  int64_t ld;                  // floats per activation row: the widest mp
+  int64_t max_block;           // the largest packed block (kernel + bias)
+  int64_t transposed_floats;   // the size of weights_t
+  int64_t block(int l) const { return offset[l + 1] - offset[l]; }
+  // the transposed block of layer l >= 1 (W^T as a K' = M_l by M' = K_l layer, no bias): kp' = round8(M_l), mp' = round64(K_l) = mp[l - 1]
+  int kpt(int l) const { return (int)qnet_round_up(m[l], kQnetChunk); }
+  int mpt(int l) const { return mp[l - 1]; }
+};
+
+inline QnetShape qnet_shape(int num_layers, int input_dim, int hidden, int num_actions, int num_atoms) {
+  QnetShape s{};
+  s.layers = num_layers;
+  for (int l = 0; l < num_layers; ++l) {
+    s.k[l] = l == 0 ? input_dim : hidden;
+    s.m[l] = l == num_layers - 1 ? num_actions * num_atoms : hidden;
+    s.kp[l] = (int)qnet_round_up(s.k[l], kQnetChunk);
+    s.mp[l] = (int)qnet_round_up(s.m[l], kQnetCols);
+    s.offset[l + 1] = s.offset[l] + (int64_t)s.kp[l] * s.mp[l] + s.mp[l];
+    s.toffset[l] = s.transposed_floats;
+    if (l > 0) s.transposed_floats += (int64_t)s.kpt(l) * s.mpt(l);
+    s.ld = s.ld > s.mp[l] ? s.ld : s.mp[l];
+    s.max_block = s.max_block > s.block(l) ? s.max_block : s.block(l);
   }
-  return d;
+  return s;
+}
+
+// The layout, stated once: float r of the packed kernel block ([groups][chunks][2 tiles][64 lanes][4]) of a layer with kp padded inputs
+// holds W[*k][*m].
+__host__ __device__ inline void qnet_slot_km(int64_t r, int kp, int* k, int* m) {
+  const int j = (int)(r & 3), lane = (int)((r >> 2) & 63), t = (int)((r >> 8) & 1);
+  const int64_t gc = r >> 9;
+  const int chunks = kp / kQnetChunk;
+  const int c = (int)(gc % chunks), g = (int)(gc / chunks);
+  *k = kQnetChunk * c + 4 * (lane >> 5) + j;
+  *m = kQnetCols * g + 32 * t + (lane & 31);
+}
+
+// Position of W^T[m][k] (= W[k][m]) in the transposed block of a layer with K inputs, M outputs: K' = M (kp' = round8(M)), M' = K.
+__host__ __device__ inline int64_t qnet_transposed_index(int k, int m, int kpt) {
+  const int c = m / kQnetChunk, j = m & 3, ln = (k & 31) + 32 * ((m & 7) >> 2), t = (k >> 5) & 1, g = k >> 6;
+  return (((int64_t)g * (kpt / kQnetChunk) + c) * 2 + t) * 256 + ln * 4 + j;
 }
 
 // The A operand of one chunk: x[k0 .. k0 + 3] of this lane's row.  kObs: the caller's observation rows (any stride, so no vector load;
@@ -149,22 +183,45 @@ __global__ __launch_bounds__(kQnetHeadBlock) void ble_qnet_head_kernel(const flo
   action[i] = (uint8_t)best;
 }
 
-// Host: the packed image of a network (layout above) from its row-major kernels [k][m] and biases [m].
-inline void qnet_pack(int num_layers, int input_dim, int hidden, int num_actions, int num_atoms, const float* const* kernel,
-                      const float* const* bias, float* packed) {
-  for (int l = 0; l < num_layers; ++l) {
-    const QnetLayerDims d = qnet_layer(num_layers, input_dim, hidden, num_actions, num_atoms, l);
-    float* p = packed + d.offset;
-    const float* W = kernel[l];
-    for (int g = 0; g < d.mp / kQnetCols; ++g)
-      for (int c = 0; c < d.kp / kQnetChunk; ++c)
-        for (int t = 0; t < 2; ++t)
-          for (int lane = 0; lane < 64; ++lane)
-            for (int j = 0; j < 4; ++j) {
-              const int kk = kQnetChunk * c + 4 * (lane >> 5) + j, mm = kQnetCols * g + 32 * t + (lane & 31);
-              *p++ = (kk < d.k && mm < d.m) ? W[(int64_t)kk * d.m + mm] : 0.0f;
-            }
-    for (int mm = 0; mm < d.mp; ++mm) *p++ = mm < d.m ? bias[l][mm] : 0.0f;
+// ------------------------------------------------------------------------------------------------------------ host: the packed images
+// f(r, k, m, inside) for every float r of layer l's packed kernel block in storage order; inside: W has an element [k][m] (else padding).
+template <class F>
+inline void qnet_for_each_slot(const TrainDims& s, int l, F&& f) {
+  for (int64_t r = 0; r < (int64_t)s.kp[l] * s.mp[l]; ++r) {
+    int k, m;
+    qnet_slot_km(r, s.kp[l], &k, &m);
+    f(r, k, m, k < s.k[l] && m < s.m[l]);
+  }
+}
+
+// The packed image of a network (layout above) from its row-major kernels [k][m] and biases [m].
+inline void qnet_pack(const QnetShape& s, const float* const* kernel, const float* const* bias, float* packed) {
+  for (int l = 0; l < s.layers; ++l) {
+    float* p = packed + s.offset[l];
+    qnet_for_each_slot(s, l, [&](int64_t r, int k, int m, bool inside) { p[r] = inside ? kernel[l][(int64_t)k * s.m[l] + m] : 0.0f; });
+    p += (int64_t)s.kp[l] * s.mp[l];
+    for (int m = 0; m < s.mp[l]; ++m) p[m] = m < s.m[l] ? bias[l][m] : 0.0f;
+  }
+}
+
+// Its inverse: the kernels and biases of a packed image.
+inline void qnet_unpack(const QnetShape& s, const float* packed, float* const* kernel, float* const* bias) {
+  for (int l = 0; l < s.layers; ++l) {
+    const float* p = packed + s.offset[l];
+    qnet_for_each_slot(s, l, [&](int64_t r, int k, int m, bool inside) { if (inside) kernel[l][(int64_t)k * s.m[l] + m] = p[r]; });
+    p += (int64_t)s.kp[l] * s.mp[l];
+    for (int m = 0; m < s.m[l]; ++m) bias[l][m] = p[m];
+  }
+}
+
+// weights_t of a packed image: the packed image of W^T of layers 1 .. L - 1, zero outside W^T (ble_train.h's dgrad reads it; the Adam
+// kernel keeps it current).
+inline void qnet_transpose(const QnetShape& s, const float* packed, float* packed_t) {
+  for (int l = 1; l < s.layers; ++l) {
+    const float* p = packed + s.offset[l];
+    float* pt = packed_t + s.toffset[l];
+    for (int64_t e = 0; e < (int64_t)s.kpt(l) * s.mpt(l); ++e) pt[e] = 0.0f;
+    qnet_for_each_slot(s, l, [&](int64_t r, int k, int m, bool inside) { if (inside) pt[qnet_transposed_index(k, m, s.kpt(l))] = p[r]; });
   }
 }
 

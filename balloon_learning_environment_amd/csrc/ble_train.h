@@ -318,19 +318,6 @@ __global__ __launch_bounds__(kQnetBlock) void ble_qnet_dgrad_kernel(const float*
 }
 
 // ------------------------------------------------------------------------------------------------------------ Adam
-struct TrainDims {
-  int layers;
-  int64_t offset[kQnetMaxLayers + 1];        // packed block of layer l; offset[layers] = the image's size
-  int64_t toffset[kQnetMaxLayers];           // its transposed block in weights_t (l >= 1)
-  int k[kQnetMaxLayers], m[kQnetMaxLayers], kp[kQnetMaxLayers], mp[kQnetMaxLayers];
-};
-
-// Position of W^T[m][k] (= W[k][m]) in the transposed block of a layer with K inputs, M outputs: K' = M (kp' = round8(M)), M' = K.
-__host__ __device__ inline int64_t qnet_transposed_index(int k, int m, int kpt) {
-  const int c = m / kQnetChunk, j = m & 3, ln = (k & 31) + 32 * ((m & 7) >> 2), t = (k >> 5) & 1, g = k >> 6;
-  return (((int64_t)g * (kpt / kQnetChunk) + c) * 2 + t) * 256 + ln * 4 + j;
-}
-
 // optax.adam (scale_by_adam, then scale(-lr)): m = (1 - b1) g + b1 m, v = (1 - b2) g^2 + b2 v,
 // w += -lr (m / c1) / (sqrt(v / c2) + eps), omb = 1 - b (float64, then rounded, as optax's Python float); a kernel element also goes
 // to weights_t.
@@ -354,87 +341,9 @@ __global__ __launch_bounds__(kAdamBlock) void ble_adam_kernel(float* __restrict_
   while (l + 1 < dims.layers && e >= dims.offset[l + 1]) ++l;
   const int64_t r = e - dims.offset[l];
   if (l == 0 || r >= (int64_t)dims.kp[l] * dims.mp[l]) return;
-  const int j = (int)(r & 3), lane = (int)((r >> 2) & 63), t = (int)((r >> 8) & 1);
-  const int64_t gc = r >> 9;
-  const int chunks = dims.kp[l] / kQnetChunk;
-  const int c = (int)(gc % chunks), g64 = (int)(gc / chunks);
-  const int k = kQnetChunk * c + 4 * (lane >> 5) + j, mm = kQnetCols * g64 + 32 * t + (lane & 31);
+  int k, mm;
+  qnet_slot_km(r, dims.kp[l], &k, &mm);
   if (k < dims.k[l] && mm < dims.m[l]) wt[dims.toffset[l] + qnet_transposed_index(k, mm, (int)qnet_round_up(dims.m[l], kQnetChunk))] = nw;
-}
-
-// ------------------------------------------------------------------------------------------------------------ exploration
-__global__ __launch_bounds__(256) void ble_explore_kernel(uint8_t* __restrict__ action, int64_t n, float epsilon, uint64_t seed,
-                                                          uint64_t step) {
-  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  if (i >= n) return;
-  Philox g = philox_init(seed, (uint64_t)i, (uint32_t)step);
-  g.key1 ^= (uint32_t)(step >> 32);
-  const uint32_t u = philox_u32(g), r = philox_u32(g);
-  const float uf = (float)(u >> 8) * (1.0f / 16777216.0f);             // [0, 1), 24 bits
-  if (uf < epsilon) action[i] = (uint8_t)(((uint64_t)r * 3u) >> 32);
-}
-
-// Marco Polo exploration (the reference's MarcoPoloExploration over a RandomWalkAgent, one step = 3 min), one lane per environment.
-// The Philox stream of (seed, env, step): block 0 holds the begin-of-episode uniforms (target, then episode), block 1 on the normal.
-constexpr int kMarcoPoloRlSteps = 80, kMarcoPoloExploreSteps = 40;     // 4 h and 2 h
-__host__ __device__ inline float marco_polo_u24(double u) { return (float)(uint32_t)(u * 16777216.0) * (1.0f / 16777216.0f); }
-
-__global__ __launch_bounds__(256) void ble_marco_polo_kernel(ble_marco_polo_f32 mp, uint8_t* __restrict__ action) {
-  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  if (i >= mp.n) return;
-  const uint64_t step = *mp.step;
-  Philox g = philox_init(mp.seed, (uint64_t)i, (uint32_t)step);
-  g.key1 ^= (uint32_t)(step >> 32);
-  if (mp.begin[i]) {
-    // RandomWalkAgent.begin_episode: clock 0, target U[6500, 11400) (jax.random.uniform in float32); then phase clock 0, the
-    // episode is exploratory when u <= p, RL phase; the agent's action is kept.
-    const float ut = marco_polo_u24(philox_uniform(g)), ue = marco_polo_u24(philox_uniform(g));
-    mp.walk_clock[i] = 0;
-    mp.target[i] = (double)fmaxf(6500.0f, __fadd_rn(__fmul_rn(ut, 4900.0f), 6500.0f));
-    mp.phase_clock[i] = 0;
-    mp.exploratory_episode[i] = (double)ue <= mp.exploratory_episode_probability ? 1 : 0;
-    mp.exploratory_phase[i] = 0;
-    return;
-  }
-  int clock = mp.phase_clock[i] + 1;
-  uint8_t phase = mp.exploratory_phase[i];
-  if (mp.exploratory_episode[i] && clock >= (phase ? kMarcoPoloExploreSteps : kMarcoPoloRlSteps)) { phase ^= 1; clock = 0; }
-  mp.phase_clock[i] = clock;
-  mp.exploratory_phase[i] = phase;
-  if (!phase) return;
-  // RandomWalkAgent.step: clock += 180 s, target += seconds * 0.1666 * z (float64), then the hysteresis rule on p = 5000 + 9000 f0
-  // (float32, NamedPerciatelliFeatures.balloon_pressure)
-  const int walk = mp.walk_clock[i] + 1;
-  mp.walk_clock[i] = walk;
-  g.c0 = 1;
-  const double z = philox_normal(g);
-  const double target = mp.target[i] + ((double)walk * 180.0) * 0.1666 * z;
-  mp.target[i] = target;
-  const float p = __fadd_rn(5000.0f, __fmul_rn(mp.obs[i * mp.obs_stride], 9000.0f));
-  action[i] = (double)__fsub_rn(p, 100.0f) > target ? 2 : ((double)__fadd_rn(p, 100.0f) < target ? 0 : 1);
-}
-
-// ------------------------------------------------------------------------------------------------------------ host
-inline void qnet_unpack(int num_layers, int input_dim, int hidden, int num_actions, int num_atoms, const float* packed,
-                        float* const* kernel, float* const* bias) {
-  for (int l = 0; l < num_layers; ++l) {
-    const QnetLayerDims d = qnet_layer(num_layers, input_dim, hidden, num_actions, num_atoms, l);
-    const float* p = packed + d.offset;
-    float* W = kernel[l];
-    for (int g = 0; g < d.mp / kQnetCols; ++g)
-      for (int c = 0; c < d.kp / kQnetChunk; ++c)
-        for (int t = 0; t < 2; ++t)
-          for (int lane = 0; lane < 64; ++lane)
-            for (int j = 0; j < 4; ++j) {
-              const int kk = kQnetChunk * c + 4 * (lane >> 5) + j, mm = kQnetCols * g + 32 * t + (lane & 31);
-              const float v = *p++;
-              if (kk < d.k && mm < d.m) W[(int64_t)kk * d.m + mm] = v;
-            }
-    for (int mm = 0; mm < d.mp; ++mm) {
-      const float v = *p++;
-      if (mm < d.m) bias[l][mm] = v;
-    }
-  }
 }
 
 }  // namespace ble

@@ -37,6 +37,17 @@ def on_own_device(method):
   return wrapped
 
 
+def first_use(cache: dict, key, make, refusal: str):
+  """cache[key], made by make() on the first use of `key`.  That use allocates, so it must not be inside a graph capture:
+  RuntimeError(refusal) there.  Later uses allocate nothing and can be captured."""
+  value = cache.get(key)
+  if value is None:
+    if torch.cuda.is_current_stream_capturing():
+      raise RuntimeError(refusal)
+    value = cache[key] = make()
+  return value
+
+
 def stream_ptr(device) -> int:
   return torch.cuda.current_stream(device).cuda_stream
 

@@ -1,4 +1,4 @@
-// Host build of the Philox draws of ble_marco_polo_u8 (csrc/ble_train.h), for tests/test_gpu_marco_polo.py: TEST TOOLING, compiled with
+// Host build of the Philox draws of ble_marco_polo_u8 (csrc/ble_explore.h), for tests/test_gpu_marco_polo.py: TEST TOOLING, compiled with
 // g++ and tests/emul/ble_intrinsics.h as tests/emul/ble_emul.cpp is.  Stream (seed, env, step): block 0 holds the begin uniforms
 // (target, then episode), block 1 on the normal.
 #include "../balloon_learning_environment_amd/csrc/ble_step_core.h"

@@ -33,6 +33,98 @@ def test_unpack_inverts_pack(layers, hidden, atoms):
       assert np.array_equal(got.view(np.uint32), leaf[k].view(np.uint32)), (name, k)
 
 
+@pytest.mark.parametrize('layers,hidden,atoms', [(8, 600, 51), (1, 0, 1), (3, 37, 7), (2, 5, 3)])
+def test_pack_is_the_layout_formula(layers, hidden, atoms):
+  """ble_qnet_pack_f32 against the layout written in numpy: block l is [mp / 64][kp / 8][2][64 lanes][4] floats, element
+  (g, c, t, lane, j) = W[8c + 4 (lane >> 5) + j][64g + 32t + (lane & 31)], then the bias padded to mp -- bit for bit, padding zeros
+  (+0.0) included."""
+  params = _random_params(layers, hidden, atoms, seed=2)
+  got = qnet.QNetwork.from_params(params).packed_host
+  t, lane, j = np.arange(2).reshape(-1, 1, 1), np.arange(64).reshape(-1, 1), np.arange(4)
+  off = 0
+  for l in range(layers):
+    w, b = params['params'][f'Dense_{l}']['kernel'], params['params'][f'Dense_{l}']['bias']
+    k, m = w.shape
+    kp, mp = -(-k // 8) * 8, -(-m // 64) * 64
+    g, c = np.arange(mp // 64).reshape(-1, 1, 1, 1, 1), np.arange(kp // 8).reshape(1, -1, 1, 1, 1)
+    kk, mm = 8 * c + 4 * (lane >> 5) + j, 64 * g + 32 * t + (lane & 31)
+    want = np.where((kk < k) & (mm < m), w[np.minimum(kk, k - 1), np.minimum(mm, m - 1)], np.float32(0.0)).astype(np.float32)
+    assert want.shape == (mp // 64, kp // 8, 2, 64, 4)
+    assert np.array_equal(got[off:off + kp * mp].view(np.uint32), want.ravel().view(np.uint32)), l
+    off += kp * mp
+    want_b = np.zeros(mp, np.float32)
+    want_b[:m] = b
+    assert np.array_equal(got[off:off + mp].view(np.uint32), want_b.view(np.uint32)), l
+    off += mp
+  assert off == got.size
+
+
+# Every size the Q-network entry points answer, per network shape and batch size: (every field of ble_qnet_train_layout in declaration
+# order, (packed_floats, scratch_floats) of ble_qnet_workspace_f32).  The literals were printed by the library built from the commit
+# before the host code got its one shape table, loaded through BLE_HIP_LIB: they pin the ABI's sizes, not this build's arithmetic.
+_LAYOUT_FIELDS = ('ld', 'acts', 'target_logits', 'targets', 'dlogits', 'scratch', 'partial', 'slabs', 'corrections', 'total',
+                  'transposed_floats')
+_SIZE_BATCHES = (0, 1, 32, 300, 4096, 5000)
+_SIZES = {
+    (8, 600, 51): [
+        ((640, 0, 0, 0, 0, 0, 0, 1, 0, 64, 2406400), (3130432, 0)),      # B = 0
+        ((640, 0, 5120, 5760, 5824, 6464, 9024, 1, 9024, 9088, 2406400), (3130432, 1280)),      # B = 1
+        ((640, 0, 163840, 184320, 185984, 206464, 288384, 1, 288384, 288448, 2406400), (3130432, 40960)),      # B = 32
+        ((640, 0, 1536000, 1728000, 1743360, 1935360, 2703360, 1, 2703360, 2703424, 2406400), (3130432, 384000)),      # B = 300
+        ((640, 0, 20971520, 23592960, 23801856, 26423296, 36909056, 16, 48224256, 48224320, 2406400), (3130432, 5242880)),      # B = 4096
+        ((640, 0, 25600000, 28800000, 29055040, 32255040, 45055040, 16, 56370240, 56370304, 2406400), (3130432, 6400000)),      # B = 5000
+    ],
+    (1, 0, 1): [
+        ((64, 0, 0, 0, 0, 0, 0, 1, 0, 64, 0), (70720, 0)),      # B = 0
+        ((64, 0, 64, 128, 192, 256, 512, 1, 512, 576, 0), (70720, 128)),      # B = 1
+        ((64, 0, 2048, 4096, 4160, 6208, 14400, 1, 14400, 14464, 0), (70720, 4096)),      # B = 32
+        ((64, 0, 19200, 38400, 38720, 57920, 134720, 1, 134720, 134784, 0), (70720, 38400)),      # B = 300
+        ((64, 0, 262144, 524288, 528384, 790528, 1839104, 16, 2970624, 2970688, 0), (70720, 524288)),      # B = 4096
+        ((64, 0, 320000, 640000, 645056, 965056, 2245056, 16, 3376576, 3376640, 0), (70720, 640000)),      # B = 5000
+    ],
+    (3, 37, 7): [
+        ((64, 0, 0, 0, 0, 0, 0, 1, 0, 64, 4096), (75968, 0)),      # B = 0
+        ((64, 0, 192, 256, 320, 384, 640, 1, 640, 704, 4096), (75968, 128)),      # B = 1
+        ((64, 0, 6144, 8192, 8448, 10496, 18688, 1, 18688, 18752, 4096), (75968, 4096)),      # B = 32
+        ((64, 0, 57600, 76800, 78912, 98112, 174912, 1, 174912, 174976, 4096), (75968, 38400)),      # B = 300
+        ((64, 0, 786432, 1048576, 1077248, 1339392, 2387968, 16, 3519488, 3519552, 4096), (75968, 524288)),      # B = 4096
+        ((64, 0, 960000, 1280000, 1315008, 1635008, 2915008, 16, 4046528, 4046592, 4096), (75968, 640000)),      # B = 5000
+    ],
+    (2, 5, 3): [
+        ((64, 0, 0, 0, 0, 0, 0, 1, 0, 64, 1024), (71296, 0)),      # B = 0
+        ((64, 0, 128, 192, 256, 320, 576, 1, 576, 640, 1024), (71296, 128)),      # B = 1
+        ((64, 0, 4096, 6144, 6272, 8320, 16512, 1, 16512, 16576, 1024), (71296, 4096)),      # B = 32
+        ((64, 0, 38400, 57600, 58560, 77760, 154560, 1, 154560, 154624, 1024), (71296, 38400)),      # B = 300
+        ((64, 0, 524288, 786432, 798720, 1060864, 2109440, 16, 3240960, 3241024, 1024), (71296, 524288)),      # B = 4096
+        ((64, 0, 640000, 960000, 975040, 1295040, 2575040, 16, 3706560, 3706624, 1024), (71296, 640000)),      # B = 5000
+    ],
+    (2, 70, 3): [
+        ((128, 0, 0, 0, 0, 0, 0, 1, 0, 64, 2048), (146112, 0)),      # B = 0
+        ((128, 0, 256, 384, 448, 576, 1088, 1, 1088, 1152, 2048), (146112, 256)),      # B = 1
+        ((128, 0, 8192, 12288, 12416, 16512, 32896, 1, 32896, 32960, 2048), (146112, 8192)),      # B = 32
+        ((128, 0, 76800, 115200, 116160, 154560, 308160, 1, 308160, 308224, 2048), (146112, 76800)),      # B = 300
+        ((128, 0, 1048576, 1572864, 1585152, 2109440, 4206592, 16, 6469632, 6469696, 2048), (146112, 1048576)),      # B = 4096
+        ((128, 0, 1280000, 1920000, 1935040, 2575040, 5135040, 16, 7398080, 7398144, 2048), (146112, 1280000)),      # B = 5000
+    ],
+}
+
+
+@pytest.mark.parametrize('shape', sorted(_SIZES))
+def test_sizes_are_pinned(shape):
+  assert _LAYOUT_FIELDS == tuple(name for name, _ in _abi.BleQnetTrainLayout._fields_)
+  lib = _lib.lib()
+  layers, hidden, atoms = shape
+  net = _abi.BleQnetF32(layers, _lib.OBS_DIM, hidden, 3, atoms, 0, None)
+  for b, (want_layout, want_workspace) in zip(_SIZE_BATCHES, _SIZES[shape]):
+    lay = _abi.BleQnetTrainLayout()
+    assert lib.ble_qnet_train_workspace_f32(ctypes.byref(_abi.BleQnetTrainF32(net)), ctypes.byref(_abi.BleTrainBatchF32(b, 1104)),
+                                            ctypes.byref(lay)) == 0
+    assert tuple(getattr(lay, name) for name in _LAYOUT_FIELDS) == want_layout, b
+    packed, scratch = ctypes.c_int64(-1), ctypes.c_int64(-1)
+    assert lib.ble_qnet_workspace_f32(ctypes.byref(net), b, ctypes.byref(packed), ctypes.byref(scratch)) == 0
+    assert (packed.value, scratch.value) == want_workspace, b
+
+
 @pytest.mark.parametrize('layers,hidden,atoms', [(3, 37, 7), (2, 70, 3)])
 def test_transposed_image(layers, hidden, atoms):
   """ble_qnet_transpose_f32 packs W^T of layers 1 .. L-1: packing W_l^T as a layer of its own gives the same floats."""
