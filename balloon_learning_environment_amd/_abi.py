@@ -167,6 +167,16 @@ class BleQnetTrainLayout(ctypes.Structure):
                                                   'corrections', 'total', 'transposed_floats')]
 
 
+TD_DQN_MSE, TD_DQN_HUBER, TD_SARSA_MSE = 0, 1, 2     # BLE_TD_*
+TD_OPT_ADAM, TD_OPT_SGD = 0, 1                        # BLE_TD_OPT_*
+
+
+class BleTdF32(ctypes.Structure):
+  """struct ble_td_f32: the loss kind and optimiser of ble_qnet_td_step_f32, SARSA's gamma and device pointers."""
+  _fields_ = [('kind', ctypes.c_int32), ('optimizer', ctypes.c_int32), ('gamma', ctypes.c_float), ('reserved_', ctypes.c_int32),
+              ('next_action', ctypes.c_void_p), ('mask', ctypes.c_void_p)]
+
+
 class BleExploreF32(ctypes.Structure):
   """struct ble_explore_f32: epsilon-greedy over n actions, keyed by (seed, env, step)."""
   _fields_ = [('n', ctypes.c_int64), ('epsilon', ctypes.c_float), ('reserved_', ctypes.c_int32), ('seed', ctypes.c_uint64),

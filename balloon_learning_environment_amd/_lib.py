@@ -45,7 +45,7 @@ EXPORTS = ('ble_abi_version', 'ble_noise_primitive_version', 'ble_vehicle_defaul
            'ble_station_seeker_f32', 'ble_eval_accumulate_f32', 'ble_reset_seeded_f32', 'ble_wind_noise_seeded_f32',
            'ble_observe_live_f32', 'ble_qnet_workspace_f32', 'ble_qnet_pack_f32', 'ble_qnet_forward_f32',
            'ble_qnet_unpack_f32', 'ble_replay_sample_f32', 'ble_qnet_train_workspace_f32', 'ble_qnet_transpose_f32',
-           'ble_qnet_train_step_f32', 'ble_qnet_explore_u8',
+           'ble_qnet_train_step_f32', 'ble_qnet_explore_u8', 'ble_qnet_td_workspace_f32', 'ble_qnet_td_step_f32',
            'ble_replay_tree_add_f64', 'ble_replay_sample_prioritized_f32', 'ble_replay_set_priority_f32', 'ble_marco_polo_u8')
 
 
@@ -151,6 +151,9 @@ def lib():
   l.ble_qnet_transpose_f32.argtypes = [qnet, _vp, _vp]
   l.ble_qnet_train_step_f32.argtypes = [train, batch, _vp, _vp, _vp]
   l.ble_qnet_explore_u8.argtypes = [ctypes.POINTER(_abi.BleExploreF32), _vp, _vp]
+  td = ctypes.POINTER(_abi.BleTdF32)
+  l.ble_qnet_td_workspace_f32.argtypes = [train, td, batch, ctypes.POINTER(_abi.BleQnetTrainLayout)]
+  l.ble_qnet_td_step_f32.argtypes = [train, td, batch, _vp, _vp, _vp]
   # prioritized replay and Marco Polo exploration (sizes in descriptors, as above)
   replay, tree = ctypes.POINTER(_abi.BleReplayF32), ctypes.POINTER(_abi.BleSumTreeF64)
   l.ble_replay_tree_add_f64.argtypes = [replay, tree, _vp]

@@ -6,8 +6,8 @@ update -- uniform n-step sample, target and online forward, quantile Huber loss,
 (csrc/ble_train.h) with no host synchronisation, capturable as one graph.  Every reduction has one order fixed by the
 shapes and no kernel uses floating-point atomics: a run is a pure function of (initial parameters, replay contents, seeds).
 
-With num_atoms == 1 the loss is the one-quantile QR loss, i.e. half the Huber loss of DQN's TD error (tau = 1/2); DQN's own loss is not
-implemented.
+With num_atoms == 1 the loss is the one-quantile QR loss, i.e. half the Huber loss of DQN's TD error (tau = 1/2); DQN's own losses
+(Dopamine's 'mse' and 'huber') are agents/dqn_agent.py's DQNTrainer, a subclass of the trainer here.
 """
 import ctypes
 from typing import Dict, Optional

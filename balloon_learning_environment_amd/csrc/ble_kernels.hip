@@ -1206,6 +1206,25 @@ ble_qnet_train_layout train_layout(const QnetShape& s, int num_atoms, int64_t n)
   y.transposed_floats = s.transposed_floats;
   return y;
 }
+// SARSA's workspace (ble_qnet_td_workspace_f32): both branches kept, the partial sums of the state branch's slabs then next_state's
+ble_qnet_train_layout sarsa_layout(const QnetShape& s, int64_t n) {
+  ble_qnet_train_layout y{};
+  const int64_t ld = s.ld, L = s.layers;
+  y.ld = ld;
+  y.slabs = wgrad_slabs(n);
+  int64_t at = 0;
+  auto take = [&](int64_t floats) { const int64_t o = at; at += qnet_round_up(floats, 64); return o; };
+  y.acts = take(2 * L * n * ld);
+  y.target_logits = take(0);
+  y.targets = take(n);
+  y.dlogits = take(2 * n * ld);
+  y.scratch = take(4 * n * ld);
+  y.partial = take(2 * y.slabs * s.max_block);
+  y.corrections = take(4);
+  y.total = at;
+  y.transposed_floats = s.transposed_floats;
+  return y;
+}
 bool tree_ok(const ble_replay_f32* rp, const ble_sum_tree_f64* tr) {
   return tr != nullptr && tr->leaves == rp->capacity * rp->num_envs && tr->leaves <= BLE_SUM_TREE_MAX_LEAVES && tr->padded >= tr->leaves &&
          (tr->padded & (tr->padded - 1)) == 0 && (tr->padded == 1 || tr->padded / 2 < tr->leaves) && tr->nodes && tr->max_priority &&
@@ -1229,11 +1248,13 @@ int launch_sample_then_advance(void (*kernel)(P...), const ble_replay_f32* rp, c
 }
 
 // Where layer l of a Dense stack writes its n rows of ld floats: base + (keep ? l : l & 1) n ld -- every layer kept, or two buffers
-// in turn -- and the last layer to `last` instead when that is set.
+// in turn -- and the last layer to `last` instead when that is set.  layer_stride, when set, replaces n ld (kept layers that lie further
+// apart: the two branches of SARSA).
 struct DenseOut {
   float* base;
   bool keep;
   float* last;
+  int64_t layer_stride = 0;
 };
 // The Dense stack of shape s over the weight image w, on n rows of x (row stride ldx).  The first layer reads the caller's rows, the
 // others the previous layer's activations; ReLU after every layer but the last.  Returns the first failing status.
@@ -1244,7 +1265,7 @@ int launch_dense_stack(const QnetShape& s, const float* w, const float* x, int64
     const bool first = l == 0, last = l == s.layers - 1;
     const auto dense = first ? (last ? ble_qnet_dense_kernel<true, false> : ble_qnet_dense_kernel<true, true>)
                              : (last ? ble_qnet_dense_kernel<false, false> : ble_qnet_dense_kernel<false, true>);
-    float* y = last && out.last ? out.last : out.base + (out.keep ? l : l & 1) * n * s.ld;
+    float* y = last && out.last ? out.last : out.base + (out.keep ? l : l & 1) * (out.layer_stride ? out.layer_stride : n * s.ld);
     const int status = launch_grid(dense, dim3((unsigned)groups * row_tiles), kQnetBlock, stream, x, ldx, s.k[l], s.kp[l], w + s.offset[l], y,
                                    s.ld, groups, n);
     if (status != BLE_OK) return status;
@@ -1265,21 +1286,41 @@ bool train_step_ok(const ble_qnet_train_f32* tr, const ble_train_batch_f32* bt, 
   return aligned(15, tr->net.weights, tr->target, tr->grad, tr->workspace, tr->adam_m, tr->adam_v, tr->weights_t);
 }
 
-// One update of ble_qnet_train_step_f32 on a checked, non-empty batch: the shape, the workspace's parts and the four stages in launch
-// order.  Every stage returns the first failing status.
+bool td_ok(const ble_td_f32* td) {
+  return td != nullptr && td->kind >= BLE_TD_DQN_MSE && td->kind <= BLE_TD_SARSA_MSE &&
+         (td->optimizer == BLE_TD_OPT_ADAM || td->optimizer == BLE_TD_OPT_SGD) &&
+         (td->kind != BLE_TD_SARSA_MSE || (td->next_action != nullptr && std::isfinite(td->gamma)));
+}
+bool td_step_ok(const ble_qnet_train_f32* tr, const ble_td_f32* td, const ble_train_batch_f32* bt, const float* loss) {
+  if (!tr || !qnet_ok(&tr->net) || tr->net.num_atoms != 1 || !td_ok(td) || !batch_ok(bt) || !loss || !tr->net.weights || !tr->grad ||
+      !tr->workspace || !std::isfinite(tr->lr))
+    return false;
+  if (td->kind != BLE_TD_SARSA_MSE && !tr->target) return false;
+  if (tr->net.num_layers > 1 && !tr->weights_t) return false;
+  if (tr->apply_update && td->optimizer == BLE_TD_OPT_ADAM &&
+      (!tr->adam_m || !tr->adam_v || !tr->adam_step || !std::isfinite(tr->adam_b1) || !std::isfinite(tr->adam_b2) || !std::isfinite(tr->adam_eps)))
+    return false;
+  return aligned(15, tr->net.weights, tr->target, tr->grad, tr->workspace, tr->adam_m, tr->adam_v, tr->weights_t);
+}
+
+// One update of ble_qnet_train_step_f32 or ble_qnet_td_step_f32 on a checked, non-empty batch: the shape, the workspace's parts and the
+// stages in launch order.  Every stage returns the first failing status.  branches: 1, or 2 for SARSA, whose online network runs on
+// state (branch 0) and on next_state (branch 1) -- layer l's kept output is then 2 n stacked rows, branch 0 first.
 struct TrainStep {
   const ble_qnet_train_f32* tr;
   const ble_train_batch_f32* bt;
   void* stream;
   const QnetShape s;
+  const int branches;
   const ble_qnet_train_layout lay;
   const int64_t n, ld;
   float* const ws;
 
-  TrainStep(const ble_qnet_train_f32* tr_, const ble_train_batch_f32* bt_, void* stream_)
-      : tr(tr_), bt(bt_), stream(stream_), s(qnet_shape(&tr_->net)), lay(train_layout(s, tr_->net.num_atoms, bt_->batch)), n(bt_->batch),
-        ld(lay.ld), ws(tr_->workspace) {}
-  float* acts(int l) const { return ws + lay.acts + l * n * ld; }      // the online network's kept output of layer l
+  TrainStep(const ble_qnet_train_f32* tr_, const ble_train_batch_f32* bt_, void* stream_, int branches_ = 1)
+      : tr(tr_), bt(bt_), stream(stream_), s(qnet_shape(&tr_->net)), branches(branches_),
+        lay(branches_ == 2 ? sarsa_layout(s, bt_->batch) : train_layout(s, tr_->net.num_atoms, bt_->batch)), n(bt_->batch), ld(lay.ld),
+        ws(tr_->workspace) {}
+  float* acts(int l, int br = 0) const { return ws + lay.acts + (branches * l + br) * n * ld; }      // the online network's kept output of layer l
 
   // the target's pass on next_state (ping-pong, its logits end in target_logits), then the online one on state (every layer kept)
   int forward() const {
@@ -1294,23 +1335,46 @@ struct TrainStep {
                        (const float*)bt->discount, (const uint8_t*)bt->action, tr->kappa, n, ws + lay.targets, ws + lay.dlogits, row_loss,
                        err_flags);
   }
-  // from the last layer: dW (+ db) over the batch slabs, their reduction, then dX for the layer below
+  // SARSA: the online network on state, then on next_state, every layer of both kept
+  int forward_both() const {
+    for (int br = 0; br < 2; ++br) {
+      const int status = launch_dense_stack(s, tr->net.weights, br == 0 ? bt->state : bt->next_state, bt->state_stride, n,
+                                            DenseOut{acts(0, br), true, nullptr, 2 * n * ld}, stream);
+      if (status != BLE_OK) return status;
+    }
+    return BLE_OK;
+  }
+  int td_loss(const ble_td_f32* td, float* row_loss, uint32_t* err_flags) const {
+    const auto kernel = td->kind == BLE_TD_DQN_MSE ? ble_td_loss_kernel<kTdDqnMse>
+                        : td->kind == BLE_TD_DQN_HUBER ? ble_td_loss_kernel<kTdDqnHuber> : ble_td_loss_kernel<kTdSarsaMse>;
+    const float* logits = acts(s.layers - 1);
+    const float* other = branches == 2 ? acts(s.layers - 1, 1) : ws + lay.target_logits;
+    return launch_grid(kernel, dim3((unsigned)n), kTrainLossBlock, stream, logits, other, ld, tr->net.num_actions, (const float*)bt->ret,
+                       (const float*)bt->discount, (const uint8_t*)bt->action, td->next_action, td->mask, td->gamma, n, ws + lay.targets,
+                       ws + lay.dlogits, row_loss, err_flags);
+  }
+  // from the last layer: dW (+ db) over the batch slabs of each branch (branch 0's slabs first), their reduction in that order, then dX
+  // for the layer below over every row of every branch
   int backward() const {
-    float* dyb[2] = {ws + lay.scratch + 2 * n * ld, ws + lay.scratch + 3 * n * ld};
-    const unsigned row_tiles = (unsigned)((n + kQnetRows - 1) / kQnetRows);
-    const int slabs = (int)lay.slabs;
+    const int64_t rows = branches * n;
+    float* dyb[2] = {ws + lay.scratch + (branches == 1 ? 2 : 0) * n * ld, ws + lay.scratch + (branches == 1 ? 3 : 2) * n * ld};
+    const unsigned row_tiles = (unsigned)((rows + kQnetRows - 1) / kQnetRows);
+    const int slabs = (int)lay.slabs, parts = branches * slabs;
     const int64_t slab_rows = slabs == 1 ? n : (n + slabs - 1) / slabs;
     const float* dy = ws + lay.dlogits;
     for (int l = s.layers - 1; l >= 0; --l) {
       const int64_t blk = s.block(l);
-      float* dst = slabs == 1 ? tr->grad + s.offset[l] : ws + lay.partial;
-      const float* x = l == 0 ? bt->state : acts(l - 1);
-      int status = launch_grid(ble_qnet_wgrad_kernel, dim3((unsigned)((s.kp[l] + 31) / 32), (unsigned)(s.mp[l] / kQnetCols), (unsigned)slabs),
-                               64, stream, x, l == 0 ? bt->state_stride : ld, s.k[l], s.kp[l], dy, ld, s.m[l], s.mp[l], n, slab_rows, dst,
-                               blk);
-      if (status != BLE_OK) return status;
-      if (slabs > 1) {
-        status = launch(ble_wgrad_reduce_kernel, blk, 256, 256, stream, (const float*)(ws + lay.partial), slabs, blk, blk,
+      float* dst = parts == 1 ? tr->grad + s.offset[l] : ws + lay.partial;
+      int status;
+      for (int br = 0; br < branches; ++br) {
+        const float* x = l == 0 ? (br == 0 ? bt->state : bt->next_state) : acts(l - 1, br);
+        status = launch_grid(ble_qnet_wgrad_kernel, dim3((unsigned)((s.kp[l] + 31) / 32), (unsigned)(s.mp[l] / kQnetCols), (unsigned)slabs),
+                             64, stream, x, l == 0 ? bt->state_stride : ld, s.k[l], s.kp[l], dy + br * n * ld, ld, s.m[l], s.mp[l], n,
+                             slab_rows, dst + br * slabs * blk, blk);
+        if (status != BLE_OK) return status;
+      }
+      if (parts > 1) {
+        status = launch(ble_wgrad_reduce_kernel, blk, 256, 256, stream, (const float*)(ws + lay.partial), parts, blk, blk,
                         tr->grad + s.offset[l]);
         if (status != BLE_OK) return status;
       }
@@ -1318,7 +1382,7 @@ struct TrainStep {
       const int groups = s.mpt(l) / kQnetCols;
       float* dx = dyb[l & 1];
       status = launch_grid(ble_qnet_dgrad_kernel, dim3((unsigned)groups * row_tiles), kQnetBlock, stream, dy, ld, s.kpt(l),
-                           (const float*)(tr->weights_t + s.toffset[l]), (const float*)acts(l - 1), dx, groups, n);
+                           (const float*)(tr->weights_t + s.toffset[l]), (const float*)acts(l - 1), dx, groups, rows);
       if (status != BLE_OK) return status;
       dy = dx;
     }
@@ -1331,6 +1395,10 @@ struct TrainStep {
     return launch(ble_adam_kernel, s.offset[s.layers], kAdamBlock, kAdamBlock, stream, const_cast<float*>(tr->net.weights), tr->weights_t,
                   (const float*)tr->grad, tr->adam_m, tr->adam_v, (const float*)corr, tr->lr, (float)tr->adam_b1,
                   (float)(1.0 - tr->adam_b1), (float)tr->adam_b2, (float)(1.0 - tr->adam_b2), tr->adam_eps, s);
+  }
+  int sgd() const {
+    return launch(ble_sgd_kernel, s.offset[s.layers], kAdamBlock, kAdamBlock, stream, const_cast<float*>(tr->net.weights), tr->weights_t,
+                  (const float*)tr->grad, tr->lr, s);
   }
 };
 }  // namespace
@@ -1399,6 +1467,28 @@ int ble_qnet_train_step_f32(const ble_qnet_train_f32* tr, const ble_train_batch_
   if (const int status = t.loss(loss, err_flags); status != BLE_OK) return status;
   if (const int status = t.backward(); status != BLE_OK) return status;
   return tr->apply_update ? t.adam() : BLE_OK;
+}
+
+int ble_qnet_td_workspace_f32(const ble_qnet_train_f32* tr, const ble_td_f32* td, const ble_train_batch_f32* bt, ble_qnet_train_layout* out) {
+  if (!tr || !qnet_ok(&tr->net) || tr->net.num_atoms != 1 || !td || td->kind < BLE_TD_DQN_MSE || td->kind > BLE_TD_SARSA_MSE || !bt ||
+      bt->batch < 0 || bt->batch > BLE_TRAIN_MAX_BATCH || !out)
+    return BLE_E_INVALID_ARG;
+  const QnetShape s = qnet_shape(&tr->net);
+  *out = td->kind == BLE_TD_SARSA_MSE ? sarsa_layout(s, bt->batch) : train_layout(s, 1, bt->batch);
+  return BLE_OK;
+}
+
+int ble_qnet_td_step_f32(const ble_qnet_train_f32* tr, const ble_td_f32* td, const ble_train_batch_f32* bt, float* loss, uint32_t* err_flags,
+                         void* stream) {
+  if (!td_step_ok(tr, td, bt, loss)) return BLE_E_INVALID_ARG;
+  if (bt->batch == 0) return BLE_OK;
+  const bool sarsa = td->kind == BLE_TD_SARSA_MSE;
+  const TrainStep t(tr, bt, stream, sarsa ? 2 : 1);
+  if (const int status = sarsa ? t.forward_both() : t.forward(); status != BLE_OK) return status;
+  if (const int status = t.td_loss(td, loss, err_flags); status != BLE_OK) return status;
+  if (const int status = t.backward(); status != BLE_OK) return status;
+  if (!tr->apply_update) return BLE_OK;
+  return td->optimizer == BLE_TD_OPT_SGD ? t.sgd() : t.adam();
 }
 
 int ble_qnet_explore_u8(const ble_explore_f32* ex, uint8_t* action, void* stream) {

@@ -1,5 +1,6 @@
 // ble_train.h -- the QR-DQN update of Dopamine 4.0.0's JaxQuantileAgent on the device: the n-step replay sampler, the
-// quantile Huber loss and its dL/dlogits, the backward pass of the Dense stack on v_mfma_f32_32x32x2_f32 and optax 0.0.9's Adam.
+// quantile Huber loss and its dL/dlogits, the backward pass of the Dense stack on v_mfma_f32_32x32x2_f32 and optax 0.0.9's Adam; for
+// one-atom networks also DQN's TD losses (JaxDQNAgent), the reference MLP agent's SARSA loss and optax's plain SGD.
 //
 // Determinism: no floating-point atomics anywhere.  Every sum below runs in one order fixed by the shapes (B, the layer widths, the
 // number of batch slabs, itself a function of B): an update is a pure function of its inputs, and a captured graph computes the bits
@@ -206,6 +207,88 @@ __global__ __launch_bounds__(kTrainLossBlock) void ble_qr_loss_kernel(const floa
   }
 }
 
+// ------------------------------------------------------------------------------------------------------------ TD losses (one atom)
+// The logits [B, 3] of a one-atom network are its Q-values.  One wave per row b; lane 0 evaluates, in the order written:
+//   DQN (Dopamine 4.0.0 dqn_agent.train; `other` = the target network's logits on next_state):
+//     a* = argmax_a q'(s')[a] (ble_qnet_head_kernel's rule), T = ret + discount q'(s')[a*], u = T - q(s)[action],
+//     kTdDqnMse:   L_b = u^2,                                            dL/dq = -((2 u) / B)
+//     kTdDqnHuber: L_b = u^2 / 2 if |u| <= 1 else |u| - 1/2 (a select),  dL/dq = -(clip(u, -1, 1) / B)
+//   kTdSarsaMse (the reference's mlp_agent.train; logits holds 2 B rows, the online network on state then on next_state, and so does
+//   dlogits; `other` = logits + B ld):
+//     T = ret + gamma q(s')[next_action], delta = q(s)[action] - T, L_b = delta^2,
+//     dL/dq(s)[action] = (2 delta) / B, dL/dq(s')[next_action] = -((gamma (2 delta)) / B); mask[b] != 0: L_b and both rows are 0.
+// An action >= actions (either one, for SARSA) sets BLE_FLAG_TRAIN_ACTION and zeroes the row.  targets[b] = T.
+enum : int { kTdDqnMse = 0, kTdDqnHuber = 1, kTdSarsaMse = 2 };
+
+template <int kKind>
+__global__ __launch_bounds__(kTrainLossBlock) void ble_td_loss_kernel(const float* __restrict__ logits, const float* __restrict__ other,
+                                                                     int64_t ld, int actions, const float* __restrict__ ret,
+                                                                     const float* __restrict__ discount, const uint8_t* __restrict__ action,
+                                                                     const uint8_t* __restrict__ next_action, const uint8_t* __restrict__ mask,
+                                                                     float gamma, int64_t batch, float* __restrict__ targets,
+                                                                     float* __restrict__ dlogits, float* __restrict__ loss,
+                                                                     uint32_t* __restrict__ err_flags) {
+  constexpr bool kSarsa = kKind == kTdSarsaMse;
+  const int64_t b = blockIdx.x;
+  const int lane = threadIdx.x;
+  float* __restrict__ dl = dlogits + b * ld;
+  float* __restrict__ dn = dlogits + (batch + b) * ld;                // (SARSA: the next_state branch's row)
+  for (int c = lane; c < ld; c += kTrainLossBlock) {
+    dl[c] = 0.0f;
+    if (kSarsa) dn[c] = 0.0f;
+  }
+  __syncthreads();
+  if (lane != 0) return;
+  const float* __restrict__ z = logits + b * ld;
+  const float* __restrict__ zo = other + b * ld;
+  const int act = action[b];
+  const int nact = kSarsa ? (int)next_action[b] : 0;
+  const bool valid = act < actions && nact < actions;
+  if (!valid && err_flags != nullptr) atomicOr(err_flags, kFlagTrainAction);
+  const bool live = valid && !(kSarsa && mask != nullptr && mask[b] != 0);
+  const float r = ret[b];
+  const float fb = (float)batch;
+  float l = 0.0f;
+  if (kSarsa) {
+    const float qn = valid ? zo[nact] : 0.0f;
+    const float p = gamma * qn;
+    const float t = r + p;
+    targets[b] = t;
+    if (live) {
+      const float delta = z[act] - t;
+      const float d2 = 2.0f * delta;
+      const float gd = gamma * d2;
+      l = delta * delta;
+      dl[act] = d2 / fb;
+      dn[nact] = -(gd / fb);
+    }
+  } else {
+    int best = 0;
+    float qb = 0.0f;
+    for (int a = 0; a < actions; ++a) {
+      const float qa = zo[a];
+      if (a == 0 || (qb == qb && (qa != qa || qa > qb))) { best = a; qb = qa; }
+    }
+    const float p = discount[b] * zo[best];
+    const float t = r + p;
+    targets[b] = t;
+    if (live) {
+      const float u = t - z[act];
+      if (kKind == kTdDqnMse) {
+        const float u2 = 2.0f * u;
+        l = u * u;
+        dl[act] = -(u2 / fb);
+      } else {
+        const float au = fabsf(u);
+        l = au <= 1.0f ? 0.5f * u * u : au - 0.5f;
+        const float cl = au <= 1.0f ? u : (u < 0.0f ? -1.0f : 1.0f);
+        dl[act] = -(cl / fb);
+      }
+    }
+  }
+  loss[b] = l;
+}
+
 // ------------------------------------------------------------------------------------------------------------ backward
 // dW (+ db) of one layer over the batch rows of slab `blockIdx.z`, one wave per (32 k) x (64 m) tile: out is the layer's packed block
 // (kp x mp kernel then mp bias) of the gradient, or of the slab's partial sums.  k >= K or m >= M is written as 0.0.
@@ -335,6 +418,25 @@ __global__ __launch_bounds__(kAdamBlock) void ble_adam_kernel(float* __restrict_
   vel[e] = v;
   const float mh = m / corr[0], vh = v / corr[1];
   const float step = lr * (mh / (sqrtf(vh) + eps));
+  const float nw = w[e] - step;
+  w[e] = nw;
+  int l = 0;
+  while (l + 1 < dims.layers && e >= dims.offset[l + 1]) ++l;
+  const int64_t r = e - dims.offset[l];
+  if (l == 0 || r >= (int64_t)dims.kp[l] * dims.mp[l]) return;
+  int k, mm;
+  qnet_slot_km(r, dims.kp[l], &k, &mm);
+  if (k < dims.k[l] && mm < dims.m[l]) wt[dims.toffset[l] + qnet_transposed_index(k, mm, (int)qnet_round_up(dims.m[l], kQnetChunk))] = nw;
+}
+
+// ------------------------------------------------------------------------------------------------------------ SGD
+// optax.sgd(lr) without momentum: w += -lr g, the product rounded before the sum; a kernel element also goes to weights_t, as in Adam.
+// The gradient's padding is zero, so the image's stays zero.
+__global__ __launch_bounds__(kAdamBlock) void ble_sgd_kernel(float* __restrict__ w, float* __restrict__ wt, const float* __restrict__ grad,
+                                                             float lr, TrainDims dims) {
+  const int64_t e = (int64_t)blockIdx.x * kAdamBlock + threadIdx.x;
+  if (e >= dims.offset[dims.layers]) return;
+  const float step = lr * grad[e];
   const float nw = w[e] - step;
   w[e] = nw;
   int l = 0;

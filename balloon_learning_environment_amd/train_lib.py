@@ -1,5 +1,6 @@
-"""The training loop of a device QR-DQN learner over a VecBalloonEnv: the reference's train_lib.run_training_loop with
-JaxQuantileAgent's schedule (min_replay_history, update_period, target_update_period counted in transitions), N environments per step.
+"""The training loops of the device learners over a VecBalloonEnv: the reference's train_lib.run_training_loop with Dopamine's
+schedule (min_replay_history, update_period, target_update_period counted in transitions) for the replay learners (QNetworkTrainer,
+DQNTrainer), and the loop of an online learner (VecMLPAgent); N environments per step.
 """
 from typing import Callable, List, Optional, Union
 
@@ -94,6 +95,53 @@ def run_training_loop_vec(env, trainer: qnet_train.QNetworkTrainer, replay: qnet
     env.check_errors()
     replay.check_errors()
     trainer.check_errors()
+    ne = int(episodes.item())
+    stats.append({'mean_loss': float(loss_sum.item()) / max(it_updates, 1), 'updates': it_updates, 'episodes': ne,
+                  'mean_return': float(done_returns.item()) / ne if ne else float('nan'),
+                  'time_within_radius': float(within.item()) / (n * steps_per_iteration), 'transitions': transitions})
+  return stats
+
+
+def run_online_loop_vec(env, agent, *, num_iterations: int, steps_per_iteration: int, max_episode_length: int = 960) -> List[dict]:
+  """Runs an online learner (VecMLPAgent: begin_episode / step) on `env` (auto_reset) for num_iterations x steps_per_iteration vector
+  steps; in train mode every step is one update on the N transitions just made.  The episode limit is run_training_loop_vec's: a lane
+  reaching it ends its episode without a terminal and restarts; the agent is told of every episode end, whose row it does not train on.
+
+  Returns run_training_loop_vec's dicts: mean_loss (the objective, i.e. the mean of the N rows' losses, averaged over the iteration's
+  updates), updates, episodes, mean_return, time_within_radius, transitions."""
+  n, dev_ = env.num_envs, env.device
+  assert agent.num_envs == n, 'the agent holds one row per environment'
+  training = agent._mode.value == 'train'
+  actions = agent.begin_episode(env.reset())
+  ep_steps = torch.zeros(n, dtype=torch.int32, device=dev_)
+  ep_return = torch.zeros(n, dtype=torch.float32, device=dev_)
+  transitions = 0
+  stats = []
+  for _ in range(num_iterations):
+    loss_sum = torch.zeros((), dtype=torch.float32, device=dev_)
+    done_returns = torch.zeros((), dtype=torch.float32, device=dev_)
+    episodes = torch.zeros((), dtype=torch.int64, device=dev_)
+    within = torch.zeros((), dtype=torch.int64, device=dev_)
+    it_updates = 0
+    for _ in range(steps_per_iteration):
+      end_mask = (ep_steps + 1 >= max_episode_length).to(torch.uint8)
+      obs, reward, terminal = env.step(actions, end_mask=end_mask)
+      episode_end = terminal | end_mask
+      actions = agent.step(reward, obs, episode_end)
+      if training:
+        loss_sum += agent.loss.mean()
+        it_updates += 1
+      ep_return += reward
+      ep_steps += 1
+      ended = episode_end.bool()
+      episodes += ended.sum()
+      done_returns += torch.where(ended, ep_return, torch.zeros_like(ep_return)).sum()
+      ep_return.masked_fill_(ended, 0.0)
+      ep_steps.masked_fill_(ended, 0)
+      within += (reward > WITHIN_RADIUS_REWARD).sum()
+      transitions += n
+    env.check_errors()
+    agent.check_errors()
     ne = int(episodes.item())
     stats.append({'mean_loss': float(loss_sum.item()) / max(it_updates, 1), 'updates': it_updates, 'episodes': ne,
                   'mean_return': float(done_returns.item()) / ne if ne else float('nan'),

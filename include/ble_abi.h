@@ -717,6 +717,52 @@ int ble_qnet_transpose_f32(const ble_qnet_f32* net, const float* packed, float* 
  */
 int ble_qnet_train_step_f32(const ble_qnet_train_f32* tr, const ble_train_batch_f32* batch, float* loss, uint32_t* err_flags, void* stream);
 
+/*
+ * TD learners of one-atom networks (additive to ABI 5; DESIGN §3g "DQN and SARSA"): the logits [B][3] are the Q-values.
+ *   BLE_TD_DQN_MSE    Dopamine 4.0.0 JaxDQNAgent with loss_type = 'mse' (configs/dqn.gin): T = ret + discount max_a q_target(s')[a],
+ *                     L_b = (T - q(s)[action])^2
+ *   BLE_TD_DQN_HUBER  the same target, L_b = Huber_1(T - q(s)[action]) (JaxDQNAgent's default loss_type)
+ *   BLE_TD_SARSA_MSE  the reference's agents/mlp_agent.py train(): L_b = (q(s)[action] - (ret + gamma q(s')[next_action]))^2 with the
+ *                     online parameters on both sides and the gradient through both; batch->ret is the reward, batch->discount is
+ *                     not read, tr->target is not read
+ * The objective is mean_b L_b (masked rows counted in B).  The optimiser is the trainer's Adam (adam_* of ble_qnet_train_f32) or
+ * optax.sgd(tr->lr): w -= lr g, which needs no Adam state.
+ */
+#define BLE_TD_DQN_MSE 0
+#define BLE_TD_DQN_HUBER 1
+#define BLE_TD_SARSA_MSE 2
+#define BLE_TD_OPT_ADAM 0
+#define BLE_TD_OPT_SGD 1
+
+typedef struct ble_td_f32 {
+  int32_t kind;               /* BLE_TD_* */
+  int32_t optimizer;          /* BLE_TD_OPT_* */
+  float gamma;                /* SARSA's discount, finite (not read by the DQN kinds) */
+  int32_t reserved_;          /* 0 */
+  const uint8_t* next_action; /* SARSA: device [B], the action taken at next_state */
+  const uint8_t* mask;        /* SARSA, optional: device [B]; mask[b] != 0: row b's loss and both of its dlogits rows are exactly 0 */
+} ble_td_f32;
+
+/*
+ * HOST: the workspace of ble_qnet_td_step_f32 for a batch of B rows.  The DQN kinds answer ble_qnet_train_workspace_f32's layout.
+ * SARSA keeps both branches: acts is [L][2][B][ld] (layer l: the B rows of state, then the B rows of next_state), dlogits [2 B][ld] in
+ * that order, targets [B], scratch the backward dY ping-pong of 2 B rows, partial [2 slabs][largest layer block] with slabs the batch
+ * slabs of ONE branch (state's slabs first), target_logits empty.
+ */
+int ble_qnet_td_workspace_f32(const ble_qnet_train_f32* tr, const ble_td_f32* td, const ble_train_batch_f32* batch,
+                              ble_qnet_train_layout* layout);
+
+/*
+ * ble_qnet_td_step_f32: one update of a one-atom network (net.num_atoms == 1) on batch.  DQN kinds: ble_qnet_train_step_f32's
+ * stages with the TD loss in place of the quantile loss.  SARSA: the online forward on state and on next_state (every layer kept), the
+ * loss and dL/dlogits of both branches, dW / db of each layer as the sum of the state branch's batch slabs then the next_state
+ * branch's, in that order, dX over the 2 B rows.  Then the optimiser (apply_update != 0).  No floating-point atomics; every sum in an
+ * order fixed by the shapes and B.  loss: device float32 [B].  An action >= num_actions (either action, for SARSA) sets
+ * BLE_FLAG_TRAIN_ACTION and zeroes the row.  tr->kappa is not read.
+ */
+int ble_qnet_td_step_f32(const ble_qnet_train_f32* tr, const ble_td_f32* td, const ble_train_batch_f32* batch, float* loss,
+                         uint32_t* err_flags, void* stream);
+
 /* epsilon-greedy: action[i] (the greedy action in, the taken action out) becomes uniform in {0, 1, 2} when a uniform u < epsilon; u and
  * the random action come from the Philox stream keyed by (seed, i, step). */
 typedef struct ble_explore_f32 {

@@ -4,7 +4,9 @@
 
 Both sides are compiled to assembly with the flags of balloon_learning_environment_amd/_lib.py::build (hipcc -S --cuda-device-only),
 every kernel's body is cut out of the two .s files by its symbol, and the bodies of the kernels present on both sides are compared
-line by line (comments and blank lines dropped).  Prints one line per kernel and exits 1 if any common kernel differs.  Kernels present
+line by line (comments and blank lines dropped; the function's ordinal in its local labels, .LBB<ordinal>_<block>, is dropped too: it
+counts the functions emitted before this one, so a kernel added to the file renumbers the labels of every later one without changing
+an instruction).  Prints one line per kernel and exits 1 if any common kernel differs.  Kernels present
 on one side only are listed, not compared."""
 import os
 import re
@@ -33,7 +35,7 @@ def kernels(asm: str) -> dict:
     for line in body.splitlines():
       line = line.split(';')[0].rstrip()
       if line.strip():
-        lines.append(line.strip())
+        lines.append(re.sub(r'\.(LBB|LJTI|LCPI)\d+_', r'.\1_', line.strip()))
     out[name] = lines
   return out
 
