@@ -11,14 +11,11 @@ backprop, Adam, graph capture, checkpoints -- is the parent's:
 
 is configs/dqn.gin (Adam 2e-6 / 2e-5, gamma 0.993, horizon 5, epsilon 0.01, 500 / 4 / 100).
 """
-import ctypes
 from typing import Sequence
 
 import torch
 
 from balloon_learning_environment_amd import _abi
-from balloon_learning_environment_amd import _lib
-from balloon_learning_environment_amd import device as dev
 from balloon_learning_environment_amd.agents import qnet
 from balloon_learning_environment_amd.agents import qnet_train
 from balloon_learning_environment_amd.agents import quantile_agent
@@ -36,20 +33,11 @@ class DQNTrainer(qnet_train.QNetworkTrainer):
       raise ValueError(f'DQNTrainer trains one-atom networks (an MLPNetwork), not {network.num_atoms} atoms: QNetworkTrainer is QR-DQN')
     if loss_type not in _KINDS:
       raise ValueError(f"loss_type is 'mse' or 'huber', not {loss_type!r}")
-    super().__init__(network, lr=lr, eps=eps, gamma=gamma, update_horizon=update_horizon, seed=seed, b1=b1, b2=b2)
     self.loss_type = loss_type
+    super().__init__(network, lr=lr, eps=eps, gamma=gamma, update_horizon=update_horizon, seed=seed, b1=b1, b2=b2)
 
   def _td(self) -> _abi.BleTdF32:
     return _abi.BleTdF32(_KINDS[self.loss_type], _abi.TD_OPT_ADAM, 0.0, 0, None, None)
-
-  @dev.on_own_device
-  def train_on_batch(self, batch: qnet_train.TrainBatch, apply_update: bool = True) -> torch.Tensor:
-    """One DQN update on a given batch: the per-row losses [B] (a view of a buffer the next update at this size overwrites)."""
-    ws, _, loss = self.workspace(batch.batch_size)
-    tr, td = self._struct(ws, apply_update), self._td()
-    _lib.call('ble_qnet_td_step_f32', ctypes.byref(tr), ctypes.byref(td), ctypes.byref(batch.struct), loss.data_ptr(),
-              self.err_flags.data_ptr(), dev.stream_ptr(self.device))
-    return loss[:batch.batch_size]
 
   def _update(self, replay: qnet_train.VecReplayBuffer, batch_size: int) -> torch.Tensor:
     if replay.prioritized:

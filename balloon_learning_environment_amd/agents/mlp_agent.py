@@ -8,7 +8,6 @@ N rows' losses -- at N = 1 the reference's update exactly.  A row whose episode 
 does not train, and the next call is begin_episode): it adds nothing to the gradient but still counts in N.  `MLPAgent` is the
 reference's class over VecMLPAgent(1).
 """
-import ctypes
 import time
 from typing import Optional, Sequence, Union
 
@@ -25,7 +24,7 @@ from balloon_learning_environment_amd.agents import qnet_train
 ROW_FLOATS = qnet_train.ROW_FLOATS
 
 
-class VecMLPAgent:
+class VecMLPAgent(qnet_train.QNetworkLearner):
   """SARSA over N environments and one shared one-atom network (default: the reference's mlp.gin, a single Dense 1099 -> 3).
 
     agent = VecMLPAgent(env.num_envs)
@@ -36,7 +35,7 @@ class VecMLPAgent:
   The actions returned are a uint8 [N] device buffer the next call overwrites; `loss` holds the last update's per-row losses.  No call
   synchronises with the host.  capture() records step()'s device work as one HIP graph that later steps replay."""
 
-  _TENSORS = ('weights', 'last_obs', 'last_action')      # the checkpoint's tensors
+  _TENSORS = ('weights', 'last_obs', 'last_action')
 
   def __init__(self, num_envs: int, network: Optional[qnet.QNetwork] = None, *, gamma: float = 0.9, learning_rate: float = 0.001,
                seed: int = 0, device='cuda:0'):
@@ -44,18 +43,14 @@ class VecMLPAgent:
       network = qnet.QNetwork.from_params(qnet.init_params('mlp', seed, num_layers=1), device=device)
     if network.num_atoms != 1:
       raise ValueError(f'VecMLPAgent trains one-atom networks (an MLPNetwork), not {network.num_atoms} atoms')
-    self.device = dev.require_gpu(network.device)
     self.num_envs = n = int(num_envs)
     if n < 1:
       raise ValueError('num_envs >= 1')
-    self.num_layers, self.hidden_units, self.num_atoms = network.num_layers, network.hidden_units, 1
-    self.gamma, self.learning_rate, self.seed = float(gamma), float(learning_rate), int(seed)
-    self._net = _abi.BleQnetF32(self.num_layers, _lib.OBS_DIM, self.hidden_units, qnet.NUM_ACTIONS, 1, 0, None)
+    self.gamma, self.lr, self.seed = float(gamma), float(learning_rate), int(seed)
+    self._sarsa = _abi.BleTdF32(_abi.TD_SARSA_MSE, _abi.TD_OPT_SGD, self.gamma, 0, None, None)
+    super().__init__(network)
     d = self.device
     with torch.cuda.device(d):
-      self.weights = torch.from_numpy(network.packed_host.copy()).to(d)
-      self.grad = torch.zeros_like(self.weights)
-      self.err_flags = torch.zeros(1, dtype=torch.int32, device=d)
       self.last_obs = torch.zeros(n, ROW_FLOATS, dtype=torch.float32, device=d)      # s, then (after a step) s'
       self.obs = torch.zeros(n, ROW_FLOATS, dtype=torch.float32, device=d)           # s'
       self.last_action = torch.zeros(n, dtype=torch.uint8, device=d)
@@ -63,32 +58,19 @@ class VecMLPAgent:
       self.reward = torch.zeros(n, dtype=torch.float32, device=d)
       self.mask = torch.zeros(n, dtype=torch.uint8, device=d)
       self.loss = torch.zeros(n, dtype=torch.float32, device=d)
-      self._net.weights = self.weights.data_ptr()
-      self._td = _abi.BleTdF32(_abi.TD_SARSA_MSE, _abi.TD_OPT_SGD, self.gamma, 0, self.action.data_ptr(), self.mask.data_ptr())
+      self._sarsa.next_action, self._sarsa.mask = self.action.data_ptr(), self.mask.data_ptr()
       self._batch = _abi.BleTrainBatchF32(n, ROW_FLOATS, self.last_obs.data_ptr(), self.obs.data_ptr(), self.reward.data_ptr(),
                                           self.reward.data_ptr(), self.last_action.data_ptr(), None)      # (discount is not read)
-      self.layout = _abi.BleQnetTrainLayout()
-      _lib.call('ble_qnet_td_workspace_f32', ctypes.byref(_abi.BleQnetTrainF32(self._net)), ctypes.byref(self._td),
-                ctypes.byref(self._batch), ctypes.byref(self.layout))
+      self.layout = self._layout(n)
       self.workspace = torch.zeros(max(self.layout.total, 64), dtype=torch.float32, device=d)
-      self.weights_t = torch.zeros(max(self.layout.transposed_floats, 4), dtype=torch.float32, device=d)
-    self._retranspose()
-    self._forward = qnet.Forward(self._net, d, 'VecMLPAgent')
     self._mode = agent.AgentMode.TRAIN
     self._begun = False
-    self._graphs = {}
+
+  learning_rate = property(lambda self: self.lr)
 
   # ---- plumbing
-  def _struct(self, apply_update: bool = True) -> _abi.BleQnetTrainF32:
-    return _abi.BleQnetTrainF32(self._net, None, self.weights_t.data_ptr(), self.grad.data_ptr(), None, None, None,
-                                self.workspace.data_ptr(), 0.0, 0.0, self.learning_rate, 0.0, 0.0, 1 if apply_update else 0)
-
-  def _retranspose(self) -> None:
-    """weights_t from the online image (host transpose; at construction and after a load)."""
-    host_t = np.zeros(self.weights_t.numel(), np.float32)
-    w = self.weights.cpu().numpy()
-    _lib.call('ble_qnet_transpose_f32', ctypes.byref(self._net), w.ctypes.data, host_t.ctypes.data)
-    self.weights_t.copy_(torch.from_numpy(host_t))
+  def _td(self) -> _abi.BleTdF32:
+    return self._sarsa
 
   def _load(self, dst: torch.Tensor, obs: torch.Tensor) -> None:
     assert obs.dim() == 2 and obs.shape[0] == self.num_envs and obs.shape[1] >= _lib.OBS_DIM, tuple(obs.shape)
@@ -118,9 +100,7 @@ class VecMLPAgent:
   @dev.on_own_device
   def train_on_transitions(self, apply_update: bool = True) -> torch.Tensor:
     """One SARSA update on the agent's own buffers (last_obs, last_action, reward, obs, action, mask): the per-row losses [N]."""
-    tr = self._struct(apply_update)
-    _lib.call('ble_qnet_td_step_f32', ctypes.byref(tr), ctypes.byref(self._td), ctypes.byref(self._batch), self.loss.data_ptr(),
-              self.err_flags.data_ptr(), dev.stream_ptr(self.device))
+    self._launch_update(self.workspace, self._batch, self.loss, apply_update)
     return self.loss
 
   def _body(self, train: bool) -> None:
@@ -158,44 +138,23 @@ class VecMLPAgent:
     if not self._begun:
       raise RuntimeError('VecMLPAgent.capture before begin_episode (the forward scratch is allocated there)')
     train = self._mode == agent.AgentMode.TRAIN
-    d = self.device
-    side = torch.cuda.Stream(device=d)
-    side.wait_stream(torch.cuda.current_stream(d))
-    graph = torch.cuda.CUDAGraph()
-    with torch.cuda.stream(side):
-      with torch.cuda.graph(graph, stream=side):
-        self._body(train)
-    torch.cuda.current_stream(d).wait_stream(side)
+    graph, _ = dev.capture(self.device, lambda: self._body(train))
     self._graphs[train] = graph
 
-  def check_errors(self) -> None:
-    qnet_train._check_flags(self.err_flags)
-
-  # ---- export and checkpoints
-  def params(self) -> dict:
-    return qnet_train.unpack(self._net, self.weights.cpu().numpy())
-
-  def network(self, device=None) -> qnet.QNetwork:
-    return qnet.QNetwork.from_params(self.params(), num_atoms=1, device=self.device if device is None else device)
-
+  # ---- checkpoints
   def state_dict(self) -> dict:
-    return {'shape': (self.num_layers, self.hidden_units, 1), 'num_envs': self.num_envs, 'seed': self.seed,
-            'hyper': (self.gamma, self.learning_rate), 'begun': self._begun, 'mode': self._mode.value,
-            **{k: getattr(self, k).clone() for k in self._TENSORS}}
+    return {**super().state_dict(), 'num_envs': self.num_envs, 'hyper': (self.gamma, self.lr), 'begun': self._begun,
+            'mode': self._mode.value}
 
   def load_state_dict(self, d: dict) -> None:
-    """Restores in place (every tensor keeps its address)."""
-    assert tuple(d['shape']) == (self.num_layers, self.hidden_units, 1), 'checkpoint of another network shape'
     assert int(d['num_envs']) == self.num_envs, 'checkpoint of another number of environments'
     hyper = tuple(float(h) for h in d['hyper'])
-    if hyper != (self.gamma, self.learning_rate):
+    if hyper != (self.gamma, self.lr):
       self._graphs.clear()                     # (the hyperparameters are arguments of the captured launches)
-    self.gamma, self.learning_rate = hyper
-    self._td.gamma = self.gamma
-    self.seed, self._begun, self._mode = int(d['seed']), bool(d['begun']), agent.AgentMode(d['mode'])
-    for k in self._TENSORS:
-      getattr(self, k).copy_(d[k])
-    self._retranspose()
+    self.gamma, self.lr = hyper
+    self._sarsa.gamma = self.gamma
+    self._begun, self._mode = bool(d['begun']), agent.AgentMode(d['mode'])
+    super().load_state_dict(d)
 
 
 class MLPAgent(agent.Agent):

@@ -1,7 +1,8 @@
 """Training QR-DQN / DQN policies on the device: Dopamine 4.0.0's JaxQuantileAgent update (configs/quantile.gin) without JAX.
 
 `VecReplayBuffer` is an n-step replay ring of N environments stepped in lockstep (VecBalloonEnv's tensors, one ring column per
-environment); `QNetworkTrainer` holds the online and target images, the gradient, Adam's moments and the device counters, and runs one
+environment); `QNetworkLearner` is what every device learner holds (the online image, its gradient and transposed image, the update's
+descriptors, acting, export, checkpoints); `QNetworkTrainer` adds the target image, Adam's moments and the device counters, and runs one
 update -- uniform n-step sample, target and online forward, quantile Huber loss, backprop, Adam -- as a handful of HIP kernels
 (csrc/ble_train.h) with no host synchronisation, capturable as one graph.  Every reduction has one order fixed by the
 shapes and no kernel uses floating-point atomics: a run is a pure function of (initial parameters, replay contents, seeds).
@@ -196,7 +197,93 @@ class VecPrioritizedReplayBuffer(VecReplayBuffer):
     return batch.weighted_loss
 
 
-class QNetworkTrainer:
+class QNetworkLearner:
+  """What the device learners share: a network's online image with its gradient and transposed image on the network's device, the
+  descriptors of one update (ble_qnet_train_step_f32, or ble_qnet_td_step_f32 when _td() gives a BleTdF32), acting, export and the
+  tensors of a checkpoint (_TENSORS).  A subclass sets the optimiser state it has; what it lacks stays None / 0."""
+
+  _TENSORS = ('weights',)      # the checkpoint's tensors
+  target = adam_m = adam_v = adam_step = None
+  lr = eps = b1 = b2 = kappa = 0.0
+
+  def __init__(self, network: qnet.QNetwork):
+    self.device = d = dev.require_gpu(network.device)
+    self.num_layers, self.hidden_units, self.num_atoms = network.num_layers, network.hidden_units, network.num_atoms
+    self._net = _abi.BleQnetF32(self.num_layers, _lib.OBS_DIM, self.hidden_units, qnet.NUM_ACTIONS, self.num_atoms, 0, None)
+    with torch.cuda.device(d):
+      self.weights = torch.from_numpy(network.packed_host.copy()).to(d)
+      self.grad = torch.zeros_like(self.weights)
+      self.err_flags = torch.zeros(1, dtype=torch.int32, device=d)
+      self.weights_t = torch.zeros(max(self._layout(0).transposed_floats, 4), dtype=torch.float32, device=d)
+    self._net.weights = self.weights.data_ptr()
+    self._retranspose()
+    self._forward = qnet.Forward(self._net, d, type(self).__name__)
+    self._graphs: dict = {}
+
+  # ---- plumbing
+  def _td(self) -> Optional[_abi.BleTdF32]:
+    """The TD descriptor of this learner's update; None: the QR-DQN update, which has none."""
+    return None
+
+  def _struct(self, workspace: Optional[torch.Tensor], apply_update: bool = True) -> _abi.BleQnetTrainF32:
+    return _abi.BleQnetTrainF32(self._net, dev.ptr(self.target), self.weights_t.data_ptr(), self.grad.data_ptr(), dev.ptr(self.adam_m),
+                                dev.ptr(self.adam_v), dev.ptr(self.adam_step), dev.ptr(workspace), self.b1, self.b2, self.lr,
+                                self.eps, self.kappa, 1 if apply_update else 0)
+
+  def _layout(self, batch_size: int) -> _abi.BleQnetTrainLayout:
+    bt = _abi.BleTrainBatchF32(int(batch_size), ROW_FLOATS)
+    out = _abi.BleQnetTrainLayout()
+    tr, td = _abi.BleQnetTrainF32(self._net), self._td()
+    if td is None:
+      _lib.call('ble_qnet_train_workspace_f32', ctypes.byref(tr), ctypes.byref(bt), ctypes.byref(out))
+    else:
+      _lib.call('ble_qnet_td_workspace_f32', ctypes.byref(tr), ctypes.byref(td), ctypes.byref(bt), ctypes.byref(out))
+    return out
+
+  def _launch_update(self, workspace: torch.Tensor, batch: _abi.BleTrainBatchF32, loss: torch.Tensor, apply_update: bool = True) -> None:
+    """One update on a batch descriptor, the per-row losses into `loss`."""
+    tr, td = self._struct(workspace, apply_update), self._td()
+    head = ('ble_qnet_train_step_f32', ctypes.byref(tr)) if td is None else ('ble_qnet_td_step_f32', ctypes.byref(tr), ctypes.byref(td))
+    _lib.call(*head, ctypes.byref(batch), loss.data_ptr(), self.err_flags.data_ptr(), dev.stream_ptr(self.device))
+
+  def _retranspose(self) -> None:
+    """weights_t from the online image (host transpose; at construction and after a load)."""
+    host_t = np.zeros(self.weights_t.numel(), np.float32)
+    w = self.weights.cpu().numpy()
+    _lib.call('ble_qnet_transpose_f32', ctypes.byref(self._net), w.ctypes.data, host_t.ctypes.data)
+    self.weights_t.copy_(torch.from_numpy(host_t))
+
+  def check_errors(self) -> None:
+    _check_flags(self.err_flags)
+
+  # ---- acting
+  @dev.on_own_device
+  def act(self, obs: torch.Tensor, out: torch.Tensor) -> torch.Tensor:
+    """The online network's greedy actions (ble_qnet_forward_f32 on the live image) into out (uint8 [N])."""
+    return self._forward(obs, out)
+
+  # ---- export and checkpoints
+  def params(self) -> dict:
+    """The flax-shaped tree of the online parameters (ble_qnet_unpack_f32)."""
+    return unpack(self._net, self.weights.cpu().numpy())
+
+  def network(self, device=None) -> qnet.QNetwork:
+    return qnet.QNetwork.from_params(self.params(), num_atoms=self.num_atoms, device=self.device if device is None else device)
+
+  def state_dict(self) -> dict:
+    return {'shape': (self.num_layers, self.hidden_units, self.num_atoms), 'seed': self.seed,
+            **{k: getattr(self, k).clone() for k in self._TENSORS}}
+
+  def load_state_dict(self, d: dict) -> None:
+    """Restores in place (every tensor keeps its address: captured graphs stay valid)."""
+    assert tuple(d['shape']) == (self.num_layers, self.hidden_units, self.num_atoms), 'checkpoint of another network shape'
+    self.seed = int(d['seed'])
+    for k in self._TENSORS:
+      getattr(self, k).copy_(d[k])
+    self._retranspose()
+
+
+class QNetworkTrainer(QNetworkLearner):
   """QR-DQN training of a QNetwork's parameters on its device (defaults: configs/quantile.gin -- Adam lr 2e-6, eps 2e-5, gamma 0.993,
   update horizon 5, kappa 1).
 
@@ -206,51 +293,21 @@ class QNetworkTrainer:
     policy = trainer.network()                     # a QNetwork: VecQNetworkAgent, QuantileAgent, eval_agent_vec, save_npz
   """
 
-  _TENSORS = ('weights', 'target', 'adam_m', 'adam_v', 'adam_step', 'counter')      # the checkpoint's tensors
+  _TENSORS = ('weights', 'target', 'adam_m', 'adam_v', 'adam_step', 'counter')
 
   def __init__(self, network: qnet.QNetwork, *, lr: float = 2e-6, eps: float = 2e-5, gamma: float = 0.993, update_horizon: int = 5,
                kappa: float = 1.0, seed: int = 0, b1: float = 0.9, b2: float = 0.999):
-    self.device = dev.require_gpu(network.device)
-    self.num_layers, self.hidden_units, self.num_atoms = network.num_layers, network.hidden_units, network.num_atoms
+    super().__init__(network)
     self.lr, self.eps, self.b1, self.b2, self.kappa = float(lr), float(eps), float(b1), float(b2), float(kappa)
     self.gamma, self.update_horizon, self.seed = float(gamma), int(update_horizon), int(seed)
-    self._net = _abi.BleQnetF32(self.num_layers, _lib.OBS_DIM, self.hidden_units, qnet.NUM_ACTIONS, self.num_atoms, 0, None)
     d = self.device
     with torch.cuda.device(d):
-      self.weights = torch.from_numpy(network.packed_host.copy()).to(d)
       self.target = self.weights.clone()
-      self.grad = torch.zeros_like(self.weights)
       self.adam_m = torch.zeros_like(self.weights)
       self.adam_v = torch.zeros_like(self.weights)
       self.adam_step = torch.zeros(1, dtype=torch.int64, device=d)
       self.counter = torch.zeros(1, dtype=torch.int64, device=d)      # the update counter the replay draw is keyed by
-      self.err_flags = torch.zeros(1, dtype=torch.int32, device=d)
-      self.weights_t = torch.zeros(max(self._layout(0).transposed_floats, 4), dtype=torch.float32, device=d)
-    self._net.weights = self.weights.data_ptr()
-    self._retranspose()
     self._ws: Dict[int, tuple] = {}
-    self._forward = qnet.Forward(self._net, d, 'QNetworkTrainer')
-    self._graphs: Dict[int, tuple] = {}
-
-  # ---- plumbing
-  def _struct(self, workspace: Optional[torch.Tensor], apply_update: bool = True) -> _abi.BleQnetTrainF32:
-    return _abi.BleQnetTrainF32(self._net, self.target.data_ptr(), self.weights_t.data_ptr(), self.grad.data_ptr(), self.adam_m.data_ptr(),
-                                self.adam_v.data_ptr(), self.adam_step.data_ptr(), dev.ptr(workspace), self.b1, self.b2, self.lr,
-                                self.eps, self.kappa, 1 if apply_update else 0)
-
-  def _layout(self, batch_size: int) -> _abi.BleQnetTrainLayout:
-    bt = _abi.BleTrainBatchF32(int(batch_size), ROW_FLOATS)
-    out = _abi.BleQnetTrainLayout()
-    tr = _abi.BleQnetTrainF32(self._net)
-    _lib.call('ble_qnet_train_workspace_f32', ctypes.byref(tr), ctypes.byref(bt), ctypes.byref(out))
-    return out
-
-  def _retranspose(self) -> None:
-    """weights_t from the online image (host transpose; at construction and after a load)."""
-    host_t = np.zeros(self.weights_t.numel(), np.float32)
-    w = self.weights.cpu().numpy()
-    _lib.call('ble_qnet_transpose_f32', ctypes.byref(self._net), w.ctypes.data, host_t.ctypes.data)
-    self.weights_t.copy_(torch.from_numpy(host_t))
 
   def workspace(self, batch_size: int):
     """(workspace tensor, layout) of a batch size (allocated on first use, which must not be inside a graph capture)."""
@@ -279,9 +336,7 @@ class QNetworkTrainer:
   def train_on_batch(self, batch: TrainBatch, apply_update: bool = True) -> torch.Tensor:
     """One update on a given batch: the per-row losses [B] (a view of a buffer the next update at this size overwrites)."""
     ws, _, loss = self.workspace(batch.batch_size)
-    tr = self._struct(ws, apply_update)
-    _lib.call('ble_qnet_train_step_f32', ctypes.byref(tr), ctypes.byref(batch.struct), loss.data_ptr(), self.err_flags.data_ptr(),
-              dev.stream_ptr(self.device))
+    self._launch_update(ws, batch.struct, loss, apply_update)
     return loss[:batch.batch_size]
 
   @dev.on_own_device
@@ -307,53 +362,22 @@ class QNetworkTrainer:
     train_step(replay, batch_size) replays from then on: the counters are device memory, so each replay draws a new batch and takes a
     new Adam step.  Runs one eager update first (the lazy allocations) -- that is a real update; returns its per-row losses."""
     first = self.train_step(replay, batch_size)
-    d = self.device
-    side = torch.cuda.Stream(device=d)
-    side.wait_stream(torch.cuda.current_stream(d))
-    graph = torch.cuda.CUDAGraph()
-    with torch.cuda.stream(side):
-      with torch.cuda.graph(graph, stream=side):
-        loss = self._update(replay, batch_size)
-    torch.cuda.current_stream(d).wait_stream(side)
+    graph, loss = dev.capture(self.device, lambda: self._update(replay, batch_size))
     self._graphs[batch_size] = (graph, replay, loss)
     return first
 
   def sync_target(self) -> None:
     self.target.copy_(self.weights)
 
-  def check_errors(self) -> None:
-    _check_flags(self.err_flags)
-
-  # ---- acting
-  @dev.on_own_device
-  def act(self, obs: torch.Tensor, out: torch.Tensor) -> torch.Tensor:
-    """The online network's greedy actions (ble_qnet_forward_f32 on the live image) into out (uint8 [N])."""
-    return self._forward(obs, out)
-
-  # ---- export and checkpoints
-  def params(self) -> dict:
-    """The flax-shaped tree of the online parameters (ble_qnet_unpack_f32)."""
-    return unpack(self._net, self.weights.cpu().numpy())
-
-  def network(self, device=None) -> qnet.QNetwork:
-    return qnet.QNetwork.from_params(self.params(), num_atoms=self.num_atoms, device=self.device if device is None else device)
-
   def state_dict(self) -> dict:
-    return {'shape': (self.num_layers, self.hidden_units, self.num_atoms), 'seed': self.seed,
-            'hyper': (self.lr, self.eps, self.b1, self.b2, self.kappa, self.gamma, self.update_horizon),
-            **{k: getattr(self, k).clone() for k in self._TENSORS}}
+    return {**super().state_dict(), 'hyper': (self.lr, self.eps, self.b1, self.b2, self.kappa, self.gamma, self.update_horizon)}
 
   def load_state_dict(self, d: dict) -> None:
-    """Restores in place (every tensor keeps its address: captured graphs stay valid)."""
-    assert tuple(d['shape']) == (self.num_layers, self.hidden_units, self.num_atoms), 'checkpoint of another network shape'
     hyper = tuple(d['hyper'])
     if int(d['seed']) != self.seed or hyper != (self.lr, self.eps, self.b1, self.b2, self.kappa, self.gamma, self.update_horizon):
       self._graphs.clear()                     # (the seed and hyperparameters are arguments of the captured launches)
-    self.seed = int(d['seed'])
     self.lr, self.eps, self.b1, self.b2, self.kappa, self.gamma, self.update_horizon = hyper
-    for k in self._TENSORS:
-      getattr(self, k).copy_(d[k])
-    self._retranspose()
+    super().load_state_dict(d)
 
 
 def unpack(net: _abi.BleQnetF32, packed: np.ndarray) -> dict:

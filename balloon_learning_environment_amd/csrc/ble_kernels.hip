@@ -1188,38 +1188,22 @@ bool batch_ok(const ble_train_batch_f32* bt) {
          bt->state_stride <= (1LL << 20) && bt->state && bt->next_state && bt->ret && bt->discount && bt->action &&
          aligned(15, bt->state, bt->next_state);
 }
-ble_qnet_train_layout train_layout(const QnetShape& s, int num_atoms, int64_t n) {
+// The workspace of one update on n rows.  branches: how often the online network runs -- 1, or 2 for SARSA (state, then next_state),
+// which keeps both branches' activations, dlogits and slabs of partial sums (branch 0's first) and has no target network's logits.
+ble_qnet_train_layout train_layout(const QnetShape& s, int branches, int num_atoms, int64_t n) {
   ble_qnet_train_layout y{};
   const int64_t ld = s.ld, L = s.layers;
   y.ld = ld;
   y.slabs = wgrad_slabs(n);
+  const int64_t parts = branches * y.slabs;
   int64_t at = 0;
   auto take = [&](int64_t floats) { const int64_t o = at; at += qnet_round_up(floats, 64); return o; };
-  y.acts = take(L * n * ld);
-  y.target_logits = take(n * ld);
+  y.acts = take(branches * L * n * ld);
+  y.target_logits = take(branches == 1 ? n * ld : 0);
   y.targets = take(n * num_atoms);
-  y.dlogits = take(n * ld);
+  y.dlogits = take(branches * n * ld);
   y.scratch = take(4 * n * ld);
-  y.partial = take(y.slabs > 1 ? y.slabs * s.max_block : 0);
-  y.corrections = take(4);
-  y.total = at;
-  y.transposed_floats = s.transposed_floats;
-  return y;
-}
-// SARSA's workspace (ble_qnet_td_workspace_f32): both branches kept, the partial sums of the state branch's slabs then next_state's
-ble_qnet_train_layout sarsa_layout(const QnetShape& s, int64_t n) {
-  ble_qnet_train_layout y{};
-  const int64_t ld = s.ld, L = s.layers;
-  y.ld = ld;
-  y.slabs = wgrad_slabs(n);
-  int64_t at = 0;
-  auto take = [&](int64_t floats) { const int64_t o = at; at += qnet_round_up(floats, 64); return o; };
-  y.acts = take(2 * L * n * ld);
-  y.target_logits = take(0);
-  y.targets = take(n);
-  y.dlogits = take(2 * n * ld);
-  y.scratch = take(4 * n * ld);
-  y.partial = take(2 * y.slabs * s.max_block);
+  y.partial = take(parts > 1 ? parts * s.max_block : 0);
   y.corrections = take(4);
   y.total = at;
   y.transposed_floats = s.transposed_floats;
@@ -1275,80 +1259,79 @@ int launch_dense_stack(const QnetShape& s, const float* w, const float* x, int64
   return BLE_OK;
 }
 
-bool train_step_ok(const ble_qnet_train_f32* tr, const ble_train_batch_f32* bt, const float* loss) {
-  if (!tr || !qnet_ok(&tr->net) || !batch_ok(bt) || !loss || !tr->net.weights || !tr->target || !tr->grad || !tr->workspace ||
-      !(tr->kappa > 0.0f) || !std::isfinite(tr->kappa))
-    return false;
-  if (tr->net.num_layers > 1 && !tr->weights_t) return false;
-  if (tr->apply_update && (!tr->adam_m || !tr->adam_v || !tr->adam_step ||
-                           !std::isfinite(tr->lr) || !std::isfinite(tr->adam_b1) || !std::isfinite(tr->adam_b2) || !std::isfinite(tr->adam_eps)))
-    return false;
-  return aligned(15, tr->net.weights, tr->target, tr->grad, tr->workspace, tr->adam_m, tr->adam_v, tr->weights_t);
-}
-
+// The descriptor of ble_qnet_td_*: td_kind_ok is all the workspace query reads; nothing else knows the kind and optimiser ranges.
+bool td_kind_ok(const ble_td_f32* td) { return td != nullptr && td->kind >= BLE_TD_DQN_MSE && td->kind <= BLE_TD_SARSA_MSE; }
 bool td_ok(const ble_td_f32* td) {
-  return td != nullptr && td->kind >= BLE_TD_DQN_MSE && td->kind <= BLE_TD_SARSA_MSE &&
-         (td->optimizer == BLE_TD_OPT_ADAM || td->optimizer == BLE_TD_OPT_SGD) &&
+  return td_kind_ok(td) && (td->optimizer == BLE_TD_OPT_ADAM || td->optimizer == BLE_TD_OPT_SGD) &&
          (td->kind != BLE_TD_SARSA_MSE || (td->next_action != nullptr && std::isfinite(td->gamma)));
 }
-bool td_step_ok(const ble_qnet_train_f32* tr, const ble_td_f32* td, const ble_train_batch_f32* bt, const float* loss) {
-  if (!tr || !qnet_ok(&tr->net) || tr->net.num_atoms != 1 || !td_ok(td) || !batch_ok(bt) || !loss || !tr->net.weights || !tr->grad ||
-      !tr->workspace || !std::isfinite(tr->lr))
-    return false;
-  if (td->kind != BLE_TD_SARSA_MSE && !tr->target) return false;
+// The loss of an update: a kind of ble_td_f32, or QR-DQN's (ble_qnet_train_step_f32, which has no ble_td_f32: td == nullptr).
+constexpr int kKindQr = -1;
+int update_kind(const ble_td_f32* td) { return td != nullptr ? td->kind : kKindQr; }
+int update_branches(int kind) { return kind == BLE_TD_SARSA_MSE ? 2 : 1; }
+
+// The arguments of one update, td == nullptr for ble_qnet_train_step_f32.  Where the two entry points differ, each keeps the answer
+// it was published with (a caller may rely on either):
+//  * kappa is the QR loss's alone, and a ble_td_f32 needs a one-atom network: each form checks what its loss kernel reads;
+//  * SARSA has no target network, so it alone accepts target == NULL;
+//  * lr: the QR form's only reader is Adam, so it checks lr under apply_update; the TD form, which has SGD too, checks it always;
+//  * Adam's state and hyperparameters are wanted when Adam runs: under apply_update, and not with BLE_TD_OPT_SGD.
+bool update_ok(const ble_qnet_train_f32* tr, const ble_td_f32* td, const ble_train_batch_f32* bt, const float* loss) {
+  if (!tr || !qnet_ok(&tr->net) || !batch_ok(bt) || !loss || !tr->net.weights || !tr->grad || !tr->workspace) return false;
+  if (td == nullptr ? (!(tr->kappa > 0.0f) || !std::isfinite(tr->kappa)) : (tr->net.num_atoms != 1 || !td_ok(td))) return false;
+  if (update_branches(update_kind(td)) == 1 && !tr->target) return false;
   if (tr->net.num_layers > 1 && !tr->weights_t) return false;
-  if (tr->apply_update && td->optimizer == BLE_TD_OPT_ADAM &&
+  if ((td != nullptr || tr->apply_update) && !std::isfinite(tr->lr)) return false;
+  if (tr->apply_update && (td == nullptr || td->optimizer == BLE_TD_OPT_ADAM) &&
       (!tr->adam_m || !tr->adam_v || !tr->adam_step || !std::isfinite(tr->adam_b1) || !std::isfinite(tr->adam_b2) || !std::isfinite(tr->adam_eps)))
     return false;
   return aligned(15, tr->net.weights, tr->target, tr->grad, tr->workspace, tr->adam_m, tr->adam_v, tr->weights_t);
 }
 
-// One update of ble_qnet_train_step_f32 or ble_qnet_td_step_f32 on a checked, non-empty batch: the shape, the workspace's parts and the
-// stages in launch order.  Every stage returns the first failing status.  branches: 1, or 2 for SARSA, whose online network runs on
-// state (branch 0) and on next_state (branch 1) -- layer l's kept output is then 2 n stacked rows, branch 0 first.
+// One update on a checked, non-empty batch: the shape, the workspace's parts and the stages in launch order.  Every stage returns the
+// first failing status.  branches: 1, or 2 for SARSA, whose online network runs on state (branch 0) and on next_state (branch 1) --
+// layer l's kept output is then 2 n stacked rows, branch 0 first.
 struct TrainStep {
   const ble_qnet_train_f32* tr;
+  const ble_td_f32* td;
   const ble_train_batch_f32* bt;
   void* stream;
   const QnetShape s;
-  const int branches;
+  const int kind, branches;
   const ble_qnet_train_layout lay;
   const int64_t n, ld;
   float* const ws;
 
-  TrainStep(const ble_qnet_train_f32* tr_, const ble_train_batch_f32* bt_, void* stream_, int branches_ = 1)
-      : tr(tr_), bt(bt_), stream(stream_), s(qnet_shape(&tr_->net)), branches(branches_),
-        lay(branches_ == 2 ? sarsa_layout(s, bt_->batch) : train_layout(s, tr_->net.num_atoms, bt_->batch)), n(bt_->batch), ld(lay.ld),
-        ws(tr_->workspace) {}
+  TrainStep(const ble_qnet_train_f32* tr_, const ble_td_f32* td_, const ble_train_batch_f32* bt_, void* stream_)
+      : tr(tr_), td(td_), bt(bt_), stream(stream_), s(qnet_shape(&tr_->net)), kind(update_kind(td_)), branches(update_branches(kind)),
+        lay(train_layout(s, branches, tr_->net.num_atoms, bt_->batch)), n(bt_->batch), ld(lay.ld), ws(tr_->workspace) {}
   float* acts(int l, int br = 0) const { return ws + lay.acts + (branches * l + br) * n * ld; }      // the online network's kept output of layer l
 
-  // the target's pass on next_state (ping-pong, its logits end in target_logits), then the online one on state (every layer kept)
+  // a kind with a target network: the target's pass on next_state (ping-pong, its logits end in target_logits); then the online
+  // network once per branch, on state and (SARSA) on next_state, every layer kept
   int forward() const {
-    const int status = launch_dense_stack(s, tr->target, bt->next_state, bt->state_stride, n,
-                                          DenseOut{ws + lay.scratch, false, ws + lay.target_logits}, stream);
-    if (status != BLE_OK) return status;
-    return launch_dense_stack(s, tr->net.weights, bt->state, bt->state_stride, n, DenseOut{acts(0), true, nullptr}, stream);
-  }
-  int loss(float* row_loss, uint32_t* err_flags) const {
-    return launch_grid(ble_qr_loss_kernel, dim3((unsigned)n), kTrainLossBlock, stream, acts(s.layers - 1),
-                       (const float*)(ws + lay.target_logits), ld, tr->net.num_actions, tr->net.num_atoms, (const float*)bt->ret,
-                       (const float*)bt->discount, (const uint8_t*)bt->action, tr->kappa, n, ws + lay.targets, ws + lay.dlogits, row_loss,
-                       err_flags);
-  }
-  // SARSA: the online network on state, then on next_state, every layer of both kept
-  int forward_both() const {
-    for (int br = 0; br < 2; ++br) {
+    if (branches == 1) {
+      const int status = launch_dense_stack(s, tr->target, bt->next_state, bt->state_stride, n,
+                                            DenseOut{ws + lay.scratch, false, ws + lay.target_logits}, stream);
+      if (status != BLE_OK) return status;
+    }
+    for (int br = 0; br < branches; ++br) {
       const int status = launch_dense_stack(s, tr->net.weights, br == 0 ? bt->state : bt->next_state, bt->state_stride, n,
-                                            DenseOut{acts(0, br), true, nullptr, 2 * n * ld}, stream);
+                                            DenseOut{acts(0, br), true, nullptr, branches * n * ld}, stream);
       if (status != BLE_OK) return status;
     }
     return BLE_OK;
   }
-  int td_loss(const ble_td_f32* td, float* row_loss, uint32_t* err_flags) const {
-    const auto kernel = td->kind == BLE_TD_DQN_MSE ? ble_td_loss_kernel<kTdDqnMse>
-                        : td->kind == BLE_TD_DQN_HUBER ? ble_td_loss_kernel<kTdDqnHuber> : ble_td_loss_kernel<kTdSarsaMse>;
+  // the loss kernel of the kind, one wave per row; `other`: the target network's logits, or (SARSA) the next_state branch's
+  int loss(float* row_loss, uint32_t* err_flags) const {
     const float* logits = acts(s.layers - 1);
     const float* other = branches == 2 ? acts(s.layers - 1, 1) : ws + lay.target_logits;
+    if (kind == kKindQr)
+      return launch_grid(ble_qr_loss_kernel, dim3((unsigned)n), kTrainLossBlock, stream, logits, other, ld, tr->net.num_actions,
+                         tr->net.num_atoms, (const float*)bt->ret, (const float*)bt->discount, (const uint8_t*)bt->action, tr->kappa, n,
+                         ws + lay.targets, ws + lay.dlogits, row_loss, err_flags);
+    const auto kernel = kind == BLE_TD_DQN_MSE ? ble_td_loss_kernel<kTdDqnMse>
+                        : kind == BLE_TD_DQN_HUBER ? ble_td_loss_kernel<kTdDqnHuber> : ble_td_loss_kernel<kTdSarsaMse>;
     return launch_grid(kernel, dim3((unsigned)n), kTrainLossBlock, stream, logits, other, ld, tr->net.num_actions, (const float*)bt->ret,
                        (const float*)bt->discount, (const uint8_t*)bt->action, td->next_action, td->mask, td->gamma, n, ws + lay.targets,
                        ws + lay.dlogits, row_loss, err_flags);
@@ -1388,7 +1371,11 @@ struct TrainStep {
     }
     return BLE_OK;
   }
-  int adam() const {
+  // Adam (its prologue first), or plain SGD for BLE_TD_OPT_SGD
+  int optimise() const {
+    if (td != nullptr && td->optimizer == BLE_TD_OPT_SGD)
+      return launch(ble_sgd_kernel, s.offset[s.layers], kAdamBlock, kAdamBlock, stream, const_cast<float*>(tr->net.weights), tr->weights_t,
+                    (const float*)tr->grad, tr->lr, s);
     float* corr = ws + lay.corrections;
     const int status = launch_grid(ble_adam_prologue_kernel, dim3(1), 1, stream, tr->adam_step, tr->adam_b1, tr->adam_b2, corr);
     if (status != BLE_OK) return status;
@@ -1396,11 +1383,19 @@ struct TrainStep {
                   (const float*)tr->grad, tr->adam_m, tr->adam_v, (const float*)corr, tr->lr, (float)tr->adam_b1,
                   (float)(1.0 - tr->adam_b1), (float)tr->adam_b2, (float)(1.0 - tr->adam_b2), tr->adam_eps, s);
   }
-  int sgd() const {
-    return launch(ble_sgd_kernel, s.offset[s.layers], kAdamBlock, kAdamBlock, stream, const_cast<float*>(tr->net.weights), tr->weights_t,
-                  (const float*)tr->grad, tr->lr, s);
-  }
 };
+
+// ble_qnet_train_step_f32 (td == nullptr) and ble_qnet_td_step_f32: forward, loss, backward, optimiser.
+int launch_update(const ble_qnet_train_f32* tr, const ble_td_f32* td, const ble_train_batch_f32* bt, float* loss, uint32_t* err_flags,
+                  void* stream) {
+  if (!update_ok(tr, td, bt, loss)) return BLE_E_INVALID_ARG;
+  if (bt->batch == 0) return BLE_OK;
+  const TrainStep t(tr, td, bt, stream);
+  if (const int status = t.forward(); status != BLE_OK) return status;
+  if (const int status = t.loss(loss, err_flags); status != BLE_OK) return status;
+  if (const int status = t.backward(); status != BLE_OK) return status;
+  return tr->apply_update ? t.optimise() : BLE_OK;
+}
 }  // namespace
 
 extern "C" {
@@ -1449,7 +1444,7 @@ int ble_replay_sample_f32(const ble_replay_f32* rp, const ble_train_batch_f32* b
 
 int ble_qnet_train_workspace_f32(const ble_qnet_train_f32* tr, const ble_train_batch_f32* bt, ble_qnet_train_layout* out) {
   if (!tr || !qnet_ok(&tr->net) || !bt || bt->batch < 0 || bt->batch > BLE_TRAIN_MAX_BATCH || !out) return BLE_E_INVALID_ARG;
-  *out = train_layout(qnet_shape(&tr->net), tr->net.num_atoms, bt->batch);
+  *out = train_layout(qnet_shape(&tr->net), 1, tr->net.num_atoms, bt->batch);
   return BLE_OK;
 }
 
@@ -1460,35 +1455,19 @@ int ble_qnet_transpose_f32(const ble_qnet_f32* net, const float* packed, float* 
 }
 
 int ble_qnet_train_step_f32(const ble_qnet_train_f32* tr, const ble_train_batch_f32* bt, float* loss, uint32_t* err_flags, void* stream) {
-  if (!train_step_ok(tr, bt, loss)) return BLE_E_INVALID_ARG;
-  if (bt->batch == 0) return BLE_OK;
-  const TrainStep t(tr, bt, stream);
-  if (const int status = t.forward(); status != BLE_OK) return status;
-  if (const int status = t.loss(loss, err_flags); status != BLE_OK) return status;
-  if (const int status = t.backward(); status != BLE_OK) return status;
-  return tr->apply_update ? t.adam() : BLE_OK;
+  return launch_update(tr, nullptr, bt, loss, err_flags, stream);
 }
 
 int ble_qnet_td_workspace_f32(const ble_qnet_train_f32* tr, const ble_td_f32* td, const ble_train_batch_f32* bt, ble_qnet_train_layout* out) {
-  if (!tr || !qnet_ok(&tr->net) || tr->net.num_atoms != 1 || !td || td->kind < BLE_TD_DQN_MSE || td->kind > BLE_TD_SARSA_MSE || !bt ||
-      bt->batch < 0 || bt->batch > BLE_TRAIN_MAX_BATCH || !out)
+  if (!tr || !qnet_ok(&tr->net) || tr->net.num_atoms != 1 || !td_kind_ok(td) || !bt || bt->batch < 0 || bt->batch > BLE_TRAIN_MAX_BATCH || !out)
     return BLE_E_INVALID_ARG;
-  const QnetShape s = qnet_shape(&tr->net);
-  *out = td->kind == BLE_TD_SARSA_MSE ? sarsa_layout(s, bt->batch) : train_layout(s, 1, bt->batch);
+  *out = train_layout(qnet_shape(&tr->net), update_branches(td->kind), 1, bt->batch);
   return BLE_OK;
 }
 
 int ble_qnet_td_step_f32(const ble_qnet_train_f32* tr, const ble_td_f32* td, const ble_train_batch_f32* bt, float* loss, uint32_t* err_flags,
                          void* stream) {
-  if (!td_step_ok(tr, td, bt, loss)) return BLE_E_INVALID_ARG;
-  if (bt->batch == 0) return BLE_OK;
-  const bool sarsa = td->kind == BLE_TD_SARSA_MSE;
-  const TrainStep t(tr, bt, stream, sarsa ? 2 : 1);
-  if (const int status = sarsa ? t.forward_both() : t.forward(); status != BLE_OK) return status;
-  if (const int status = t.td_loss(td, loss, err_flags); status != BLE_OK) return status;
-  if (const int status = t.backward(); status != BLE_OK) return status;
-  if (!tr->apply_update) return BLE_OK;
-  return td->optimizer == BLE_TD_OPT_SGD ? t.sgd() : t.adam();
+  return td != nullptr ? launch_update(tr, td, bt, loss, err_flags, stream) : BLE_E_INVALID_ARG;
 }
 
 int ble_qnet_explore_u8(const ble_explore_f32* ex, uint8_t* action, void* stream) {

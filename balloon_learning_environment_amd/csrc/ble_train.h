@@ -163,7 +163,7 @@ __global__ __launch_bounds__(kTrainLossBlock) void ble_qr_loss_kernel(const floa
       float s = 0.0f;
       for (int j = 0; j < atoms; ++j) s += zt[a * atoms + j];
       const float qa = s / (float)atoms;
-      if (a == 0 || (qb == qb && (qa != qa || qa > qb))) { best = a; qb = qa; }
+      if (a == 0 || (qb == qb && (qa != qa || qa > qb))) { best = a; qb = qa; }      // (the rule: ble_qnet_head_kernel states it)
     }
     s_best = best;
     if (act >= actions && err_flags != nullptr) atomicOr(err_flags, kFlagTrainAction);
@@ -267,7 +267,7 @@ __global__ __launch_bounds__(kTrainLossBlock) void ble_td_loss_kernel(const floa
     float qb = 0.0f;
     for (int a = 0; a < actions; ++a) {
       const float qa = zo[a];
-      if (a == 0 || (qb == qb && (qa != qa || qa > qb))) { best = a; qb = qa; }
+      if (a == 0 || (qb == qb && (qa != qa || qa > qb))) { best = a; qb = qa; }      // (the rule: ble_qnet_head_kernel states it)
     }
     const float p = discount[b] * zo[best];
     const float t = r + p;
@@ -401,6 +401,18 @@ __global__ __launch_bounds__(kQnetBlock) void ble_qnet_dgrad_kernel(const float*
 }
 
 // ------------------------------------------------------------------------------------------------------------ Adam
+// The optimisers' common end: element e of the packed image has become nw; when e is a kernel element (k, m) of a layer l >= 1 it
+// also goes to its slot of weights_t.
+__device__ __forceinline__ void mirror_weight_t(float* __restrict__ wt, int64_t e, float nw, const TrainDims& dims) {
+  int l = 0;
+  while (l + 1 < dims.layers && e >= dims.offset[l + 1]) ++l;
+  const int64_t r = e - dims.offset[l];
+  if (l == 0 || r >= (int64_t)dims.kp[l] * dims.mp[l]) return;
+  int k, mm;
+  qnet_slot_km(r, dims.kp[l], &k, &mm);
+  if (k < dims.k[l] && mm < dims.m[l]) wt[dims.toffset[l] + qnet_transposed_index(k, mm, (int)qnet_round_up(dims.m[l], kQnetChunk))] = nw;
+}
+
 // optax.adam (scale_by_adam, then scale(-lr)): m = (1 - b1) g + b1 m, v = (1 - b2) g^2 + b2 v,
 // w += -lr (m / c1) / (sqrt(v / c2) + eps), omb = 1 - b (float64, then rounded, as optax's Python float); a kernel element also goes
 // to weights_t.
@@ -420,13 +432,7 @@ __global__ __launch_bounds__(kAdamBlock) void ble_adam_kernel(float* __restrict_
   const float step = lr * (mh / (sqrtf(vh) + eps));
   const float nw = w[e] - step;
   w[e] = nw;
-  int l = 0;
-  while (l + 1 < dims.layers && e >= dims.offset[l + 1]) ++l;
-  const int64_t r = e - dims.offset[l];
-  if (l == 0 || r >= (int64_t)dims.kp[l] * dims.mp[l]) return;
-  int k, mm;
-  qnet_slot_km(r, dims.kp[l], &k, &mm);
-  if (k < dims.k[l] && mm < dims.m[l]) wt[dims.toffset[l] + qnet_transposed_index(k, mm, (int)qnet_round_up(dims.m[l], kQnetChunk))] = nw;
+  mirror_weight_t(wt, e, nw, dims);
 }
 
 // ------------------------------------------------------------------------------------------------------------ SGD
@@ -439,13 +445,7 @@ __global__ __launch_bounds__(kAdamBlock) void ble_sgd_kernel(float* __restrict__
   const float step = lr * grad[e];
   const float nw = w[e] - step;
   w[e] = nw;
-  int l = 0;
-  while (l + 1 < dims.layers && e >= dims.offset[l + 1]) ++l;
-  const int64_t r = e - dims.offset[l];
-  if (l == 0 || r >= (int64_t)dims.kp[l] * dims.mp[l]) return;
-  int k, mm;
-  qnet_slot_km(r, dims.kp[l], &k, &mm);
-  if (k < dims.k[l] && mm < dims.m[l]) wt[dims.toffset[l] + qnet_transposed_index(k, mm, (int)qnet_round_up(dims.m[l], kQnetChunk))] = nw;
+  mirror_weight_t(wt, e, nw, dims);
 }
 
 }  // namespace ble

@@ -48,6 +48,19 @@ def first_use(cache: dict, key, make, refusal: str):
   return value
 
 
+def capture(device, body):
+  """Records body()'s launches into a HIP graph, on a side stream of `device` that joins its current stream before and after:
+  (graph, what body() returned).  Recording runs nothing, and body() must allocate only what it returns to be kept."""
+  side = torch.cuda.Stream(device=device)
+  side.wait_stream(torch.cuda.current_stream(device))
+  graph = torch.cuda.CUDAGraph()
+  with torch.cuda.stream(side):
+    with torch.cuda.graph(graph, stream=side):
+      out = body()
+  torch.cuda.current_stream(device).wait_stream(side)
+  return graph, out
+
+
 def stream_ptr(device) -> int:
   return torch.cuda.current_stream(device).cuda_stream
 

@@ -13,6 +13,7 @@ import numpy as np
 import torch
 
 from balloon_learning_environment_amd import _abi
+from balloon_learning_environment_amd import device as dev
 from balloon_learning_environment_amd import vec_state
 from balloon_learning_environment_amd.env import features
 from balloon_learning_environment_amd.env import grid_based_wind_field
@@ -317,7 +318,7 @@ class BalloonArena(BalloonArenaInterface):
   def _launch_noise(self, out: torch.Tensor) -> None:
     """SimplexWindNoise.get_wind_noise at the balloon's CURRENT position and time, device to device: the launch
     env/simplex_wind_noise.py::SimplexWindNoise.get_wind_noise makes, on the state where it lives."""
-    from balloon_learning_environment_amd import _lib, device as dev
+    from balloon_learning_environment_amd import _lib
     s, sim = self._vec.sim.state, self._vec.sim
     _lib.check(sim.lib.ble_wind_noise_f32(s['x'].data_ptr(), s['y'].data_ptr(), s['pressure'].data_ptr(), s['time_elapsed_s'].data_ptr(),
                                           int(self._wind_field.noise_model._seed), 0, 0, 0, out.data_ptr(), 1, dev.stream_ptr(sim.device)),
@@ -359,14 +360,7 @@ class BalloonArena(BalloonArenaInterface):
     if f['graph'] is None and f['eager_steps'] >= 2:
       # buffers exist and every lazy allocation has happened: record the step once (recording does not execute it), replay from now on
       stream.synchronize()
-      side = torch.cuda.Stream(device=sim.device)
-      side.wait_stream(stream)
-      graph = torch.cuda.CUDAGraph()
-      with torch.cuda.stream(side):
-        with torch.cuda.graph(graph, stream=side):
-          self._fast_body(f)
-      stream.wait_stream(side)
-      f['graph'] = graph
+      f['graph'], _ = dev.capture(sim.device, lambda: self._fast_body(f))
     f['action_np'][0] = int(action)
     if f['graph'] is not None:
       f['graph'].replay()

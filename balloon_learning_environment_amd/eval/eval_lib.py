@@ -202,14 +202,7 @@ class VecEvaluator:
     self._observe_and_act()
 
   def _capture(self) -> None:
-    side = torch.cuda.Stream(device=self.device)
-    side.wait_stream(torch.cuda.current_stream(self.device))
-    graph = torch.cuda.CUDAGraph()
-    with torch.cuda.stream(side):
-      with torch.cuda.graph(graph, stream=side):
-        self._step()
-    torch.cuda.current_stream(self.device).wait_stream(side)
-    self._graph = graph
+    self._graph, _ = dev.capture(self.device, self._step)
 
   def _accumulate(self, t: int) -> None:
     path = 0 if self.path is None else self.path[t].data_ptr()

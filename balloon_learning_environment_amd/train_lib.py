@@ -11,6 +11,55 @@ from balloon_learning_environment_amd.agents import qnet_train
 WITHIN_RADIUS_REWARD = 0.5     # perciatelli_reward_function: 1.0 inside the radius, at most reward_dropoff = 0.4 outside
 
 
+class _EpisodeBook:
+  """The per-environment episode bookkeeping of both loops and the accumulators of one iteration, all on the device: nothing here
+  synchronises with the host but finish_iteration()."""
+
+  def __init__(self, num_envs: int, device, max_episode_length: int):
+    self.n, self.device, self.max_episode_length = num_envs, device, max_episode_length
+    self.ep_steps = torch.zeros(num_envs, dtype=torch.int32, device=device)
+    self.ep_return = torch.zeros(num_envs, dtype=torch.float32, device=device)
+    self.transitions = 0
+    self.begin_iteration()
+
+  def begin_iteration(self) -> None:
+    self.loss_sum = torch.zeros((), dtype=torch.float32, device=self.device)
+    self.done_returns = torch.zeros((), dtype=torch.float32, device=self.device)
+    self.episodes = torch.zeros((), dtype=torch.int64, device=self.device)
+    self.within = torch.zeros((), dtype=torch.int64, device=self.device)
+    self.updates = 0
+
+  def end_mask(self) -> torch.Tensor:
+    """uint8 [N]: the environments whose next step reaches the episode limit."""
+    return (self.ep_steps + 1 >= self.max_episode_length).to(torch.uint8)
+
+  def step(self, reward: torch.Tensor, episode_end: torch.Tensor) -> None:
+    """One vector step's rewards [N] and episode ends (uint8 [N]: a terminal or the time limit)."""
+    self.ep_return += reward
+    self.ep_steps += 1
+    ended = episode_end.bool()
+    self.episodes += ended.sum()
+    self.done_returns += torch.where(ended, self.ep_return, torch.zeros_like(self.ep_return)).sum()
+    self.ep_return.masked_fill_(ended, 0.0)
+    self.ep_steps.masked_fill_(ended, 0)
+    self.within += (reward > WITHIN_RADIUS_REWARD).sum()
+    self.transitions += self.n
+
+  def update(self, loss: torch.Tensor) -> None:
+    """The per-row losses of one update."""
+    self.loss_sum += loss.mean()
+    self.updates += 1
+
+  def finish_iteration(self, steps: int) -> dict:
+    """The iteration's dict (the loop's one host synchronisation), and the accumulators start again."""
+    ne = int(self.episodes.item())
+    stats = {'mean_loss': float(self.loss_sum.item()) / max(self.updates, 1), 'updates': self.updates, 'episodes': ne,
+             'mean_return': float(self.done_returns.item()) / ne if ne else float('nan'),
+             'time_within_radius': float(self.within.item()) / (self.n * steps), 'transitions': self.transitions}
+    self.begin_iteration()
+    return stats
+
+
 def run_training_loop_vec(env, trainer: qnet_train.QNetworkTrainer, replay: qnet_train.VecReplayBuffer, *, num_iterations: int,
                           steps_per_iteration: int, max_episode_length: int = 960, min_replay_history: int = 500,
                           update_period: int = 4, target_update_period: int = 100,
@@ -36,45 +85,31 @@ def run_training_loop_vec(env, trainer: qnet_train.QNetworkTrainer, replay: qnet
   sync_every = max(1, target_update_period // update_period)
   obs = env.reset()
   actions = torch.zeros(n, dtype=torch.uint8, device=dev_)
-  ep_steps = torch.zeros(n, dtype=torch.int32, device=dev_)
-  ep_return = torch.zeros(n, dtype=torch.float32, device=dev_)
+  book = _EpisodeBook(n, dev_, max_episode_length)
   begin = torch.ones(n, dtype=torch.uint8, device=dev_)
-  transitions, updates, pending, step = 0, 0, 0.0, 0
+  updates, pending, step = 0, 0.0, 0
   captured = False
   stats = []
   for _ in range(num_iterations):
-    loss_sum = torch.zeros((), dtype=torch.float32, device=dev_)
-    done_returns = torch.zeros((), dtype=torch.float32, device=dev_)
-    episodes = torch.zeros((), dtype=torch.int64, device=dev_)
-    within = torch.zeros((), dtype=torch.int64, device=dev_)
-    it_updates = 0
     for _ in range(steps_per_iteration):
       trainer.act(obs, actions)
-      eps = epsilon(transitions) if callable(epsilon) else epsilon
+      eps = epsilon(book.transitions) if callable(epsilon) else epsilon
       if exploration is None:
         qnet_train.explore(actions, eps, seed, step)
       else:
         if eps > 0.0:
           qnet_train.explore(actions, eps, seed, step)
         exploration(obs, actions, begin)
-      end_mask = (ep_steps + 1 >= max_episode_length).to(torch.uint8)
+      end_mask = book.end_mask()
       next_obs, reward, terminal = env.step(actions, end_mask=end_mask)
       episode_end = terminal | end_mask
       if exploration is not None:
         begin.copy_(episode_end)
       replay.add(obs, actions, reward, terminal, episode_end)
-      ep_return += reward
-      ep_steps += 1
-      ended = episode_end.bool()
-      episodes += ended.sum()
-      done_returns += torch.where(ended, ep_return, torch.zeros_like(ep_return)).sum()
-      ep_return.masked_fill_(ended, 0.0)
-      ep_steps.masked_fill_(ended, 0)
-      within += (reward > WITHIN_RADIUS_REWARD).sum()
+      book.step(reward, episode_end)
       obs = next_obs
-      transitions += n
       step += 1
-      if transitions >= min_replay_history and replay.cursor > replay.update_horizon:
+      if book.transitions >= min_replay_history and replay.cursor > replay.update_horizon:
         if updates_per_step is not None:
           todo = int(updates_per_step)
         else:
@@ -87,18 +122,14 @@ def run_training_loop_vec(env, trainer: qnet_train.QNetworkTrainer, replay: qnet
             captured = True
           else:
             loss = trainer.train_step(replay, batch_size)
-          loss_sum += loss.mean()
+          book.update(loss)
           updates += 1
-          it_updates += 1
           if updates % sync_every == 0:
             trainer.sync_target()
     env.check_errors()
     replay.check_errors()
     trainer.check_errors()
-    ne = int(episodes.item())
-    stats.append({'mean_loss': float(loss_sum.item()) / max(it_updates, 1), 'updates': it_updates, 'episodes': ne,
-                  'mean_return': float(done_returns.item()) / ne if ne else float('nan'),
-                  'time_within_radius': float(within.item()) / (n * steps_per_iteration), 'transitions': transitions})
+    stats.append(book.finish_iteration(steps_per_iteration))
   return stats
 
 
@@ -113,37 +144,18 @@ def run_online_loop_vec(env, agent, *, num_iterations: int, steps_per_iteration:
   assert agent.num_envs == n, 'the agent holds one row per environment'
   training = agent._mode.value == 'train'
   actions = agent.begin_episode(env.reset())
-  ep_steps = torch.zeros(n, dtype=torch.int32, device=dev_)
-  ep_return = torch.zeros(n, dtype=torch.float32, device=dev_)
-  transitions = 0
+  book = _EpisodeBook(n, dev_, max_episode_length)
   stats = []
   for _ in range(num_iterations):
-    loss_sum = torch.zeros((), dtype=torch.float32, device=dev_)
-    done_returns = torch.zeros((), dtype=torch.float32, device=dev_)
-    episodes = torch.zeros((), dtype=torch.int64, device=dev_)
-    within = torch.zeros((), dtype=torch.int64, device=dev_)
-    it_updates = 0
     for _ in range(steps_per_iteration):
-      end_mask = (ep_steps + 1 >= max_episode_length).to(torch.uint8)
+      end_mask = book.end_mask()
       obs, reward, terminal = env.step(actions, end_mask=end_mask)
       episode_end = terminal | end_mask
       actions = agent.step(reward, obs, episode_end)
       if training:
-        loss_sum += agent.loss.mean()
-        it_updates += 1
-      ep_return += reward
-      ep_steps += 1
-      ended = episode_end.bool()
-      episodes += ended.sum()
-      done_returns += torch.where(ended, ep_return, torch.zeros_like(ep_return)).sum()
-      ep_return.masked_fill_(ended, 0.0)
-      ep_steps.masked_fill_(ended, 0)
-      within += (reward > WITHIN_RADIUS_REWARD).sum()
-      transitions += n
+        book.update(agent.loss)
+      book.step(reward, episode_end)
     env.check_errors()
     agent.check_errors()
-    ne = int(episodes.item())
-    stats.append({'mean_loss': float(loss_sum.item()) / max(it_updates, 1), 'updates': it_updates, 'episodes': ne,
-                  'mean_return': float(done_returns.item()) / ne if ne else float('nan'),
-                  'time_within_radius': float(within.item()) / (n * steps_per_iteration), 'transitions': transitions})
+    stats.append(book.finish_iteration(steps_per_iteration))
   return stats

@@ -8,9 +8,7 @@ import ctypes
 import pytest
 
 from balloon_learning_environment_amd import _abi, _lib
-
-E_INVALID_ARG = -1
-_FAKE = 0x100000          # a non-NULL, 16-byte aligned address for every device pointer (never dereferenced)
+from descriptors_host import E_INVALID_ARG, _FAKE, _qnet
 MAX_SUBSTEPS = 60         # BLE_MAX_SUBSTEPS
 
 
@@ -44,12 +42,6 @@ def _fleet():
 
 def _acc(null=None):
   return _abi.BleEvalAcc(*[None if name == null else _FAKE for name, _ in _abi.BleEvalAcc._fields_])
-
-
-def _qnet(**fields):
-  d = dict(num_layers=2, input_dim=_lib.OBS_DIM, hidden_units=64, num_actions=3, num_atoms=51, reserved_=0, weights=_FAKE)
-  d.update(fields)
-  return _abi.BleQnetF32(**d)
 
 
 def _nulls(*params):
