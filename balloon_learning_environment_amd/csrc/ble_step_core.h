@@ -114,6 +114,23 @@ BLE_FN double inv_cbrt_volume(double vol) {
   double yc = (double)f_exp2((-1.0f / 3.0f) * f_log2((float)vol));              // fp32 seed
   return yc * d_fma(-vol * yc, yc * yc, 4.0) * (1.0 / 3.0);
 }
+// v_min_f64 / v_max_f64 as they are: fmin / fmax on a loop-carried value put a canonicalising v_max_f64 x, x in front of every operand
+// the compiler cannot prove quiet (three per stride for the T_int range below).  Operands are results of arithmetic, never signalling;
+// a quiet NaN operand loses against a number, like fmin / fmax.  (The host build of the test tooling takes fmin / fmax.)
+BLE_FN double d_min_raw(double a, double b) {
+#if defined(__HIP_DEVICE_COMPILE__)
+  double r; asm("v_min_f64 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b)); return r;
+#else
+  return d_min(a, b);
+#endif
+}
+BLE_FN double d_max_raw(double a, double b) {
+#if defined(__HIP_DEVICE_COMPILE__)
+  double r; asm("v_max_f64 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b)); return r;
+#else
+  return d_max(a, b);
+#endif
+}
 // the layer of the atmosphere window that holds p, carried from stride to stride
 struct LayerCursor {
   int lay;                 // -1, 0, +1 relative to the window's centre layer
@@ -128,7 +145,10 @@ BLE_FN double stride_pressure(const AtmWindow& win, const LayerCursor& lc, doubl
                               double t_amb, double t_at_p, double yc, const StrideK& K, double drag_arg = VehicleDefault::drag_arg) {
   const double mass = d_fma(kAirMolarMassD, n_air, K.dry_mass);
   const double num = d_fma(p * vol, K.m_over_r, -mass * t_amb);
-  const double dir = num >= 0.0 ? 1.0 : -1.0;
+  // the direction is num's sign on 1.0: one bit-field insert instead of a compare and a select.  num is the result of an fma: an exact
+  // zero is +0, so the two forms agree for every num that is not NaN (a NaN gave -1 and now gives its sign bit: the lane is already
+  // lost, p_new is NaN either way and the step ends it with kFlagNonFinite)
+  const double dir = __builtin_copysign(1.0, num);
   // dh/dt = dir sqrt(|2 (rho V - m) g / (rho drag)|) = dir sqrt(2 g |num| (R/M) (1/p) V^(-2/3) / cod); drag_arg = 2 g (R/M) / cod (cod = 0.25: 8 g R/M)
   const double arg = drag_arg * __builtin_fabs(num) * rp * (yc * yc);
   const double dh_dt = d_sqrt_rs(d_max(arg, 1e-30));                      // arg == 0 (exact equilibrium): 1e-15 m/s, p unchanged
@@ -353,10 +373,11 @@ BLE_FN int agent_step(EnvRegs& s, const EnvConst& c, const EnvHoisted& hc, int a
          sp = (double)s.sp;
   // total_absorptivity's range check (thermal.py:142-145) on the balloon's own temperature, which the reference evaluates on the
   // pre-stride T_int of every stride it runs: the lowest and the highest of those values, checked once after the loop (two
-  // v_min/v_max per stride instead of two compares and a select)
+  // v_min/v_max per stride instead of two compares and a select; d_min_raw: without the canonicalising copies)
   double t_int_lo = t_int, t_int_hi = t_int;
   float x = s.x, y = s.y, batt = s.batt;
-  float acs_w = s.acs_power, mdot = s.mdot, charge = s.charge, load = s.load;
+  float acs_w = s.acs_power, charge = s.charge, load = s.load;
+  double mdot_d = (double)s.mdot;        // the mass flow of the last stride run; float32 where it is read: parked, or after the loop
   int status = kOk;
 
   // The stride loop is wave-uniform: every lane runs all `substeps` strides and the loop index is a scalar.  A lane whose episode ends
@@ -368,7 +389,7 @@ BLE_FN int agent_step(EnvRegs& s, const EnvConst& c, const EnvHoisted& hc, int a
   auto stride = [&](const int k) __attribute__((always_inline)) {
     const float pf = (float)p;
     const double rp = d_rcp(p);
-    t_int_lo = d_min(t_int_lo, t_int); t_int_hi = d_max(t_int_hi, t_int);
+    t_int_lo = d_min_raw(t_int_lo, t_int); t_int_hi = d_max_raw(t_int_hi, t_int);
     // ---- sun position at (x, y, date_time) of the OLD state (balloon.py:451-452)
     const float fk = (float)k;
     const SunState sun = sun_at(k);
@@ -389,9 +410,7 @@ BLE_FN int agent_step(EnvRegs& s, const EnvConst& c, const EnvHoisted& hc, int a
     bool terminal = !(sp_new <= veh.max_sp) || sp_new <= 0.0;
 
     // ---- step 5: ACS (balloon.py:487-519)
-    double mdot_d;
     stride_acs(acs_poly, eff, sp, p, rp, t_int, &acs_w, &mdot_d, K, veh.valve_k);
-    mdot = (float)mdot_d;
     const double n_air_new = stride_mols_air(n_air, mdot_d);
 
     // ---- step 6: power (balloon.py:524-542)
@@ -413,7 +432,7 @@ BLE_FN int agent_step(EnvRegs& s, const EnvConst& c, const EnvHoisted& hc, int a
       if (sp <= 0.0) st = kZeroPressure;
       if (batt <= 0.0f) st = kOutOfPower;
       const float parked[kTermSaveRows - 1] = {x, y, (float)p, (float)t_amb, (float)t_int, (float)vol, (float)sp, (float)n_air, batt,
-                                               acs_w, mdot, charge, load};
+                                               acs_w, (float)mdot_d, charge, load};
 #pragma unroll
       for (int j = 0; j < kTermSaveRows - 1; ++j) term_save[j * kTermSaveStride] = parked[j];
       const int strides = i_opaque(k + 1);          // (otherwise the common path carries (k + 1) << 8 as an induction variable for this block)
@@ -430,7 +449,7 @@ BLE_FN int agent_step(EnvRegs& s, const EnvConst& c, const EnvHoisted& hc, int a
   BLE_STEP_TICK(5);
   s.x = x; s.y = y; s.p = (float)p; s.t_amb = (float)t_amb; s.t_int = (float)t_int; s.vol = (float)vol;
   s.sp = (float)sp; s.n_air = (float)n_air; s.batt = batt;
-  s.acs_power = acs_w; s.mdot = mdot; s.charge = charge; s.load = load;
+  s.acs_power = acs_w; s.mdot = (float)mdot_d; s.charge = charge; s.load = load;
   int k = substeps;                      // strides this lane ran (>= 1: the host entry point checks substeps >= 1)
   const int word = __builtin_bit_cast(int, *term_word);
   const bool done = word != 0;
