@@ -178,10 +178,9 @@ def call(name: str, *args) -> None:
 
 
 class step_form:
-  """`with _lib.step_form(waves): ...` forces the transition kernel's form (0 automatic, 1 one lane per environment,
-  4 / 2 wavefronts per environment: `ble_set_step_form`) for the launches inside the block and restores the previous
-  setting.  A/B runs and the bit-identity tests; the automatic choice is by batch size (BLE_SPLIT_MAX_ENVS).  (2 exists in
-  experiment builds only: the product library refuses it since ABI 5.)"""
+  """`with _lib.step_form(waves): ...` forces the transition kernel's form (`ble_set_step_form`) for the launches inside the
+  block and restores the previous setting: the only way to force one.  A/B runs and the bit-identity tests; the automatic
+  choice is by batch size (BLE_SPLIT_MAX_ENVS).  The legal values are those the ValueError below names."""
 
   def __init__(self, waves_per_env: int):
     self.waves = int(waves_per_env)
@@ -189,20 +188,9 @@ class step_form:
   def __enter__(self):
     self.before = lib().ble_set_step_form(self.waves)
     if self.before < 0:
-      raise ValueError(f'step form must be 0, 1 or 4, not {self.waves}')
+      raise ValueError(f'step form must be 0 (automatic), 1 (one lane per environment) or 4 (four wavefronts per environment), not {self.waves}')
     return self
 
   def __exit__(self, *exc):
     lib().ble_set_step_form(self.before)
     return False
-
-
-def set_step_form(mode) -> int:
-  """`ble_set_step_form` with the spelling of the former BLE_STEP_SPLIT switch: None / 'auto' -> automatic, '0' -> one lane per
-  environment, '1' / '4' -> four wavefronts ('2' -> two: experiment builds only, BLE_E_INVALID_ARG from the product library).  Returns
-  the previous setting; raises ValueError when the library refuses the form."""
-  waves = {None: 0, 'auto': 0, '0': 1, '1': 4, '4': 4, '2': 2}[mode if mode is None else str(mode)]
-  before = lib().ble_set_step_form(waves)
-  if before < 0:
-    raise ValueError(f'this library has no step form {mode!r}')
-  return before

@@ -231,39 +231,20 @@ __global__ __launch_bounds__(kStepBlock) void ble_step_kernel(StateDev st, const
 }
 
 // The same transition for small batches: one environment on the four wavefronts of a 256-thread workgroup (ble_step_split.h).
-#ifndef BLE_SPLIT_WAVES_PER_EU
-#define BLE_SPLIT_WAVES_PER_EU 2
-#endif
+// Launch bound: two waves per SIMD, what BLE_SPLIT_MAX_ENVS environments put there; three / four spill (profiles/HISTORY.md).
 template <bool kNoise>
-__global__ __launch_bounds__(kSplitWaves * kSplitLanes, BLE_SPLIT_WAVES_PER_EU) void ble_step_split_kernel(SplitArgs a) {
+__global__ __launch_bounds__(kSplitWaves * kSplitLanes, 2) void ble_step_split_kernel(SplitArgs a) {
   __shared__ SplitShared sh;
   __shared__ SplitNoiseShared<kNoise> shn;
   uint32_t flags;
   switch (__builtin_amdgcn_readfirstlane((int)threadIdx.x >> 6)) {       // (scalar: one role per wave)
-    case 0: flags = split_agent_steps<4, 0, kNoise>(a, sh, shn); break;
-    case 1: flags = split_agent_steps<4, 1, kNoise>(a, sh, shn); break;
-    case 2: flags = split_agent_steps<4, 2, kNoise>(a, sh, shn); break;
-    default: flags = split_agent_steps<4, 3, kNoise>(a, sh, shn); break;
+    case 0: flags = split_agent_steps<0, kNoise>(a, sh, shn); break;
+    case 1: flags = split_agent_steps<1, kNoise>(a, sh, shn); break;
+    case 2: flags = split_agent_steps<2, kNoise>(a, sh, shn); break;
+    default: flags = split_agent_steps<3, kNoise>(a, sh, shn); break;
   }
   report_flags(flags, a.err_flags);
 }
-// ... and on two: {vertical, thermal} | {sun + envelope, ACS + power}, 128-thread workgroups (two waves per SIMD at 65 536 environments).
-// An A/B form that the automatic choice never took and that measured slower at every batch size (profiles/HISTORY.md): since round 6 it is
-// NOT part of the product library -- profiles/build_variant.sh -DBLE_WITH_PAIR_FORM builds it for experiments (ble_set_step_form(2)).
-#ifdef BLE_WITH_PAIR_FORM
-template <bool kNoise>
-__global__ __launch_bounds__(2 * kSplitLanes) void ble_step_pair_kernel(SplitArgs a) {
-  __shared__ SplitShared sh;
-  __shared__ SplitNoiseShared<kNoise> shn;
-  uint32_t flags;
-  if (__builtin_amdgcn_readfirstlane((int)threadIdx.x >> 6) == 0) flags = split_agent_steps<2, 0, kNoise>(a, sh, shn);
-  else flags = split_agent_steps<2, 1, kNoise>(a, sh, shn);
-  report_flags(flags, a.err_flags);
-}
-constexpr bool kHavePairForm = true;
-#else
-constexpr bool kHavePairForm = false;
-#endif
 
 __global__ __launch_bounds__(256) void ble_forecast_kernel(const float* __restrict__ wind_grid,
                                                            int64_t grid_env_stride, const float* __restrict__ x,
@@ -759,17 +740,16 @@ inline StateDev state_dev(const ble_state_f32* st) {
 }
 // Below BLE_SPLIT_MAX_ENVS environments the one-lane kernel leaves most SIMDs idle (n / 64 waves on 1 024 SIMDs) and the
 // four-wave kernel still fits one wave per SIMD: it is the faster one (bit-identical results).  ble_set_step_form() forces a
-// form (A/B runs and the parity test); BLE_STEP_SPLIT=0 / 1 / 2 / 4 in the process environment is read ONCE, when the
+// form (A/B runs and the parity test); BLE_STEP_SPLIT=0 / 1 / 4 in the process environment is read ONCE, when the
 // library first needs it, as that switch's initial value (it used to be re-read by getenv on every launch: host work on the
 // 3 us launch path and a data race with a concurrent setenv).
-// g_step_form: -1 not initialised, 0 automatic, 1 / 2 / 4 wavefronts per environment.
+// g_step_form: -1 not initialised, 0 automatic, 1 / 4 wavefronts per environment.
 std::atomic<int> g_step_form{-1};
 inline int step_form_from_environment() {
   const char* e = getenv("BLE_STEP_SPLIT");
   if (e != nullptr && e[0] != 0 && e[1] == 0) {
     if (e[0] == '0') return 1;
     if (e[0] == '1' || e[0] == '4') return 4;
-    if (kHavePairForm && e[0] == '2') return 2;
   }
   return 0;
 }
@@ -783,7 +763,7 @@ inline int step_form() {
   }
   return f;
 }
-// returns the number of waves per environment: 1 (ble_step_kernel) or 4 (ble_step_split_kernel); 2 (ble_step_pair_kernel) in -DBLE_WITH_PAIR_FORM builds only
+// returns the number of waves per environment: 1 (ble_step_kernel) or 4 (ble_step_split_kernel)
 inline int split_waves(int64_t n) {
   const int f = step_form();
   return f != 0 ? f : (n <= BLE_SPLIT_MAX_ENVS ? 4 : 1);
@@ -928,9 +908,6 @@ int launch_step(const ble_state_f32* st, const ble_fleet* fleet, const uint8_t* 
         if (waves != 1) {
           const SplitArgs a{state_dev(st), action, wind_grid, grid_env_stride, noise_uv, reward, terminal, effective_action, err_flags,
                             active_count, n, substeps, n_steps, gen};
-#ifdef BLE_WITH_PAIR_FORM
-          if (waves == 2) return launch(ble_step_pair_kernel<kNoise>, n, kSplitLanes, 2 * kSplitLanes, stream, a);
-#endif
           return launch(ble_step_split_kernel<kNoise>, n, kSplitLanes, kSplitWaves * kSplitLanes, stream, a);
         }
       }
@@ -983,8 +960,7 @@ int ble_vehicle_default(ble_vehicle* v) {
 int ble_last_hip_error(void) { return g_last_hip_error; }
 
 int ble_set_step_form(int waves_per_env) {
-  if (waves_per_env != 0 && waves_per_env != 1 && waves_per_env != 4 && !(kHavePairForm && waves_per_env == 2))
-    return BLE_E_INVALID_ARG;
+  if (waves_per_env != 0 && waves_per_env != 1 && waves_per_env != 4) return BLE_E_INVALID_ARG;
   const int before = step_form();
   g_step_form.store(waves_per_env, std::memory_order_relaxed);
   return before;

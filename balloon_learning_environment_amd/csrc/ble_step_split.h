@@ -20,8 +20,7 @@
 // ephemeris | wind lookup | power + envelope layers; then the altitude layer and one solar node each on waves 1, 2, 3, wave 2
 // the sun of stride 0 with it); the safety layers publish their action MAPS (a layer is a function of the action alone once
 // its state machine has moved).  With a wind-noise generator (ABI 3) a step starts with the ten harmonic values, one 4-D
-// simplex evaluation each, spread over the waves, and one more barrier.  The same template runs as TWO wavefronts per
-// environment ({vertical, thermal} | {sun + envelope, ACS + power}: ble_step_pair_kernel, experiment builds only -- -DBLE_WITH_PAIR_FORM).
+// simplex evaluation each, spread over the waves, and one more barrier.
 // Between agent steps every value goes through float32, exactly where ble_step_kernel keeps its state as float32.
 //
 // The stride loops are straight-line: a lane whose episode ended (or was over on entry) keeps computing on a shadow of its
@@ -53,11 +52,6 @@
 namespace ble {
 
 constexpr int kSplitWaves = 4;
-// Which role evaluates the sun of the NEXT stride (it depends on the stride index alone): 2 = the envelope wave (rounds 4-5),
-// 1 = the thermal wave, 3 = the ACS + power wave.  A/B knob (profiles/r05_raw/split_sun_role_ab.txt).
-#ifndef BLE_SPLIT_SUN_ROLE
-#define BLE_SPLIT_SUN_ROLE 2
-#endif
 constexpr int kSplitLanes = 64;
 
 // LDS of one workgroup (12.6 KB)
@@ -75,8 +69,8 @@ struct SplitShared {
   uint32_t code_batt[2][kSplitLanes];                                        // wave 3: kOutOfPower after the stride, or 0
   // ---- step exchange (written in the per-step part, read after its barriers; rewritten a step later, many barriers on)
   double eot_min[kSplitLanes]; float eph[3][kSplitLanes];                    // wave 1 -> waves 2, 3: the ephemeris fields the hour-angle nodes need
-  double node_f[2][kSplitLanes];                                             // waves 1, 3 -> the sun role: the middle and end nodes of the step
-  double node_f0[kSplitLanes];                                               // wave 2 -> the sun role (when that is another wave): the first node
+  double node_f[2][kSplitLanes];                                             // waves 1, 3 -> wave 2: the middle and end nodes of the step
+  double node_f0[kSplitLanes];                                               // unused since the sun stays on wave 2; kept: without it the LDS layout shifts and the noise kernel's registers and schedule change
   float u[kSplitLanes], v[kSplitLanes];                                      // wave 2 -> all: the wind of the step
   float sin_el0[kSplitLanes], panel0[kSplitLanes]; uint32_t day0[kSplitLanes];   // wave 2 -> waves 1, 3: the sun of stride 0
   uint32_t map_alt[kSplitLanes];                                             // wave 0 -> wave 3: the altitude layer's action map
@@ -120,13 +114,11 @@ struct SplitArgs {
 // One wave of a workgroup of 256 threads = 4 waves x 64 lanes; returns this thread's error flags.  `wave` is a
 // compile-time constant: every role is its own instantiation -- its own registers, its own loops -- and the four agree on
 // the number of barriers per step (two in the per-step part -- three with the noise generator --, one per stride) by construction.
-template <int kWaves, int wave, bool kNoise>
+template <int wave, bool kNoise>
 BLE_FN uint32_t split_agent_steps(const SplitArgs& a, SplitShared& sh, SplitNoiseShared<kNoise>& shn) {
-  static_assert((kWaves == 4 || kWaves == 2) && wave >= 0 && wave < kWaves, "four waves = one role each, two waves = two roles each");
-  // the roles this wave plays: 0 vertical, 1 thermal, 2 sun + envelope, 3 ACS + power (kWaves == 2: {0, 1} and {2, 3})
-  constexpr bool r0 = kWaves == 4 ? wave == 0 : wave == 0, r1 = kWaves == 4 ? wave == 1 : wave == 0;
-  constexpr bool r2 = kWaves == 4 ? wave == 2 : wave == 1, r3 = kWaves == 4 ? wave == 3 : wave == 1;
-  constexpr bool rs = BLE_SPLIT_SUN_ROLE == 1 ? r1 : (BLE_SPLIT_SUN_ROLE == 3 ? r3 : r2);      // the role that evaluates the strides' sun
+  static_assert(wave >= 0 && wave < kSplitWaves, "one role per wave");
+  // the role this wave plays: 0 vertical, 1 thermal, 2 sun + envelope, 3 ACS + power
+  constexpr bool r0 = wave == 0, r1 = wave == 1, r2 = wave == 2, r3 = wave == 3;
   const int lane = (int)threadIdx.x & 63;
   const int64_t i = (int64_t)blockIdx.x * kSplitLanes + lane;
   const int64_t n = a.n;
@@ -155,9 +147,9 @@ BLE_FN uint32_t split_agent_steps(const SplitArgs& a, SplitShared& sh, SplitNois
     if (st.episode_cache != nullptr) cached = episode_cache_load(st.episode_cache, n, i);
     live = s.status == kOk;
   }
-  for (int t = (int)threadIdx.x; t < kAcsPolyDoubles; t += kWaves * kSplitLanes) sh.acs_poly[t] = kAcsPoly.c[t];
+  for (int t = (int)threadIdx.x; t < kAcsPolyDoubles; t += kSplitWaves * kSplitLanes) sh.acs_poly[t] = kAcsPoly.c[t];
   if constexpr (kNoise) {            // the harmonics' seeds and offsets of the workgroup's environments, once per launch
-    grad_lut_fill(shn.grad_lut, (int)threadIdx.x, kWaves * kSplitLanes);
+    grad_lut_fill(shn.grad_lut, (int)threadIdx.x, kSplitWaves * kSplitLanes);
     if (wave == 0 && in_range)
       noise_draws_fetch(a.gen.seed, (uint64_t)i, (uint64_t)(i + a.gen.env_offset), a.gen.episode ? a.gen.episode[i] : 0u, a.gen.harmonic_cache, n,
                         &shn.draws[0][lane], kSplitLanes);
@@ -221,13 +213,13 @@ BLE_FN uint32_t split_agent_steps(const SplitArgs& a, SplitShared& sh, SplitNois
     }
     if constexpr (kNoise) {
       // WindField.get_ground_truth's noise term at the pre-step position (wind_field.py:125-145): the ten harmonic values,
-      // each one 4-D simplex evaluation, spread over the waves (harmonic k on wave k mod kWaves); role 2 adds them up below
+      // each one 4-D simplex evaluation, spread over the waves (harmonic k on wave k mod 4); role 2 adds them up below
       // in the reference's order -- the same functions in the same order as ble_wind_noise_f32
       if (in_range) {
         float x_km, y_km, t_h;
         noise_coords(s.x, s.y, s.t_elapsed, &x_km, &y_km, &t_h);
 #pragma unroll 1
-        for (int k = wave; k < 10; k += kWaves)
+        for (int k = wave; k < 10; k += kSplitWaves)
           shn.nz[k][lane] = noise_harmonic_value(k / 5, k % 5, harmonic_draw_from_rows(&shn.draws[0][lane], kSplitLanes, k), x_km, y_km, s.p, t_h,
                                                  shn.grad_lut);
       }
@@ -279,14 +271,13 @@ BLE_FN uint32_t split_agent_steps(const SplitArgs& a, SplitShared& sh, SplitNois
         const SunState sun0 = sun_at_stride(0, sq, c, u, v, x_start, y_start, t_start);
         sun_sin = sun0.sin_el; sun_panel = solar_panel_factor(sun0); sun_day = sun0.day;
         sh.sin_el0[lane] = sun_sin; sh.panel0[lane] = sun_panel; sh.day0[lane] = sun_day ? 1u : 0u;
-        if (!rs) sh.node_f0[lane] = node_f0;
       }
     }
     BLE_SPLIT_T(0);
     __syncthreads();                                   // ---- barrier 2: the nodes, the sun of stride 0, the altitude layer's map
     BLE_SPLIT_T(1);
-    if (rs) sq = solar_node_coefs(r2 ? node_f0 : sh.node_f0[lane], sh.node_f[0][lane], sh.node_f[1][lane], substeps);
-    if ((r1 || r3) && !r2) { sun_sin = sh.sin_el0[lane]; sun_panel = sh.panel0[lane]; sun_day = sh.day0[lane] != 0u; }
+    if (r2) sq = solar_node_coefs(node_f0, sh.node_f[0][lane], sh.node_f[1][lane], substeps);
+    if (r1 || r3) { sun_sin = sh.sin_el0[lane]; sun_panel = sh.panel0[lane]; sun_day = sh.day0[lane] != 0u; }
     if (r3) eff = action_apply_any(sh.map_alt[lane], map_pow_env, act);
     if (live) flags |= step_flags;
 
@@ -322,12 +313,10 @@ BLE_FN uint32_t split_agent_steps(const SplitArgs& a, SplitShared& sh, SplitNois
         t_int_n = stride_internal_temperature(vol, yc, t_int, t_amb, p, flux, att, hc.q_earth, K);
         if (publish) sh.t_int[wr][lane] = t_int_n;
       }
-      if (rs) {
+      if (r2) {
         const SunState sn = sun_at_stride(k + 1, sq, c, u, v, x_start, y_start, t_start);
         sun_sin_n = sn.sin_el; sun_panel_n = solar_panel_factor(sn); sun_day_n = sn.day;
         if (publish) { sh.sin_el[wr][lane] = sun_sin_n; sh.panel[wr][lane] = sun_panel_n; sh.day[wr][lane] = sun_day_n ? 1u : 0u; }
-      }
-      if (r2) {
         // step 4: superpressure and volume (balloon.py:470-482): burst above 2 380 Pa, zero pressure at <= 0 (the later check overrides)
         superpressure_volume_f64(n_air, t_int, p, rp, &vol_n, &sp_n, K);
         const uint32_t code = sp_n <= 0.0 ? (uint32_t)kZeroPressure : (!(sp_n <= 2380.0) ? (uint32_t)kBurst : 0u);
@@ -352,13 +341,12 @@ BLE_FN uint32_t split_agent_steps(const SplitArgs& a, SplitShared& sh, SplitNois
       ++xk;
       const int rd = xk & 1;
       // commit: what this wave advanced from its registers, what it needs of the others from LDS
-      if (r0) { p = p_n; t_amb = t_amb_n; t_at_p = t_at_p_n; x = x_n; y = y_n; } else if (r1 || r2 || r3) { p = sh.p[rd][lane]; }
-      if (r1 && !r0) t_amb = sh.t_amb[rd][lane];
-      if (r1) t_int = t_int_n; else if (r2 || r3) t_int = sh.t_int[rd][lane];
-      if (r2) { vol = vol_n; sp = sp_n; } else { if (r0 || r1) vol = sh.vol[rd][lane]; if (r3) sp = sh.sp[rd][lane]; }
+      if (r0) { p = p_n; t_amb = t_amb_n; t_at_p = t_at_p_n; x = x_n; y = y_n; } else { p = sh.p[rd][lane]; }
+      if (r1) { t_int = t_int_n; t_amb = sh.t_amb[rd][lane]; } else if (r2 || r3) t_int = sh.t_int[rd][lane];
+      if (r2) { vol = vol_n; sp = sp_n; sun_sin = sun_sin_n; sun_panel = sun_panel_n; sun_day = sun_day_n; }
+      else { if (r0 || r1) vol = sh.vol[rd][lane]; if (r3) sp = sh.sp[rd][lane]; }
       if (r3) { n_air = n_air_n; batt = batt_n; } else if (r0 || r2) n_air = sh.n_air[rd][lane];
-      if (rs) { sun_sin = sun_sin_n; sun_panel = sun_panel_n; sun_day = sun_day_n; }
-      else if (r1 || r3) { sun_sin = sh.sin_el[rd][lane]; sun_day = sh.day[rd][lane] != 0u; if (r3) sun_panel = sh.panel[rd][lane]; }
+      if (r1 || r3) { sun_sin = sh.sin_el[rd][lane]; sun_day = sh.day[rd][lane] != 0u; if (r3) sun_panel = sh.panel[rd][lane]; }
       // later checks override earlier ones (balloon.py:479-482, 541-542): burst, zero pressure, out of power
       const uint32_t cb = sh.code_batt[rd][lane], cs = sh.code_sp[rd][lane];
       const int code = (int)(cb != 0u ? cb : cs);

@@ -43,8 +43,8 @@ extern "C" {
 /* 3: ble_step_n_f32 gained `noise` (ble_noise_gen: the wind-noise generator evaluated inside the fused rollout). */
 /* 4: ble_set_step_form, ble_probe_latlng_f64, the shard forms ble_reset_at_f32 / ble_wind_noise_at_f32 / ble_noise_gen.env_offset. */
 /* 5: ble_state_f32 gained the optional `vehicle` (ble_vehicle: BalloonState's flight-vehicle constants and
- *    power_safety_layer_enabled as run-time inputs); ble_noise_primitive_version(); ble_set_step_form(2) is refused by the product
- *    library (the two-wavefront form is an experiment build); ble_step_n_f32 rejects a negative ble_noise_gen.env_offset. */
+ *    power_safety_layer_enabled as run-time inputs); ble_noise_primitive_version(); ble_set_step_form(2) is refused (the two-wavefront
+ *    form left the library); ble_step_n_f32 rejects a negative ble_noise_gen.env_offset. */
 #define BLE_ABI_VERSION 5
 
 /* Version of the wind-noise PRIMITIVE's bit pattern (csrc/ble_noise.h::simplex4 and the hash / draw streams under it).  The primitive
@@ -187,12 +187,11 @@ int ble_vehicle_default(ble_vehicle* v);
 int ble_last_hip_error(void);
 
 /* Which form of the transition kernel ble_step_f32 / ble_step_n_f32 launch: 0 = automatic (by batch size, above), 1 = one
- * lane per environment, 4 = four wavefronts per environment.  (2 = two wavefronts per environment exists in experiment builds
- * only -- profiles/build_variant.sh -DBLE_WITH_PAIR_FORM; the product library answers BLE_E_INVALID_ARG since ABI 5: the form was
- * never selected and measured slower at every batch size.)
+ * lane per environment, 4 = four wavefronts per environment.  2 is refused with BLE_E_INVALID_ARG since ABI 5, like every other
+ * value: the two-wavefront form was never selected and measured slower at every batch size.
  * Process-global, thread-safe; takes effect with the next launch.  Returns the previous setting (>= 0) or
  * BLE_E_INVALID_ARG.  The initial value comes from BLE_STEP_SPLIT in the process environment when the library first looks at
- * it -- once, not per launch: 0 -> one lane, 1 or 4 -> four wavefronts, anything else (2 included, in the product library) or
+ * it -- once, not per launch: 0 -> one lane, 1 or 4 -> four wavefronts, anything else (2 included) or
  * unset -> automatic.  (ABI 4; ABI 3 re-read the variable on every launch.)  Honoured for the default vehicle only: a run-time
  * vehicle or a fleet always flies the one-lane form. */
 int ble_set_step_form(int waves_per_env);

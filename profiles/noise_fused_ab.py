@@ -18,16 +18,15 @@ for n in sizes:
   init = reset_host.sample_initial_state(n, seed=1000)
   acts = torch.randint(0, 3, (32, n), dtype=torch.uint8, device='cuda')
   rew = torch.zeros((32, n), device='cuda'); term = torch.zeros((32, n), dtype=torch.uint8, device='cuda')
-  for split in ('0', '4'):
-    _lib.set_step_form(split)
-    sim = vec_state.VecSimulator(n); sim.set_grid(field); sim.set_state(init)
-    sim.step_n(acts, rew, term, noise_seed=5); torch.cuda.synchronize()
-    sim.set_state(init)
-    e0 = torch.cuda.Event(enable_timing=True); e1 = torch.cuda.Event(enable_timing=True)
-    e0.record()
-    for r in range(8):
-      sim.step_n(acts, rew, term, noise_seed=5)
-    e1.record(); torch.cuda.synchronize()
-    us = e0.elapsed_time(e1) * 1e3 / (8 * 32)
-    print(f'n={n:6d} waves={split}: ground-truth wind, fused {us:.2f} us/step = {n / us * 1e6:.3e} env-steps/s', flush=True)
-_lib.set_step_form(None)
+  for waves in (1, 4):
+    with _lib.step_form(waves):
+      sim = vec_state.VecSimulator(n); sim.set_grid(field); sim.set_state(init)
+      sim.step_n(acts, rew, term, noise_seed=5); torch.cuda.synchronize()
+      sim.set_state(init)
+      e0 = torch.cuda.Event(enable_timing=True); e1 = torch.cuda.Event(enable_timing=True)
+      e0.record()
+      for r in range(8):
+        sim.step_n(acts, rew, term, noise_seed=5)
+      e1.record(); torch.cuda.synchronize()
+      us = e0.elapsed_time(e1) * 1e3 / (8 * 32)
+      print(f'n={n:6d} waves={waves}: ground-truth wind, fused {us:.2f} us/step = {n / us * 1e6:.3e} env-steps/s', flush=True)

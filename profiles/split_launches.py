@@ -18,10 +18,10 @@ field = (np.random.default_rng(0).standard_normal(vec_state.GRID_SHAPE) * 5.0).a
 init = reset_host.sample_initial_state(n, seed=1000)
 acts = torch.randint(0, 3, (32, n), dtype=torch.uint8, device='cuda')
 rew = torch.zeros((32, n), device='cuda'); term = torch.zeros((32, n), dtype=torch.uint8, device='cuda')
-for split in ('1', '0'):
-  _lib.set_step_form(split)
-  sim = vec_state.VecSimulator(n); sim.set_grid(field); sim.set_state(init)
-  for _ in range(launches):
-    sim.step_n(acts, rew, term)
-  torch.cuda.synchronize()
-  sim.check_errors()
+for waves in (4, 1):
+  with _lib.step_form(waves):
+    sim = vec_state.VecSimulator(n); sim.set_grid(field); sim.set_state(init)
+    for _ in range(launches):
+      sim.step_n(acts, rew, term)
+    torch.cuda.synchronize()
+    sim.check_errors()

@@ -51,19 +51,16 @@ def _run_case(d, j, form, vehicle=None, launches=1):
   a = torch.from_numpy(d['actions'][j:j + 1].copy()).cuda()
   w = torch.from_numpy(d['wind_uv'][j:j + 1].astype(np.float32)).cuda()
   words = []
-  before = _lib.set_step_form(form)
-  try:
+  with _lib.step_form(form):
     for _ in range(launches):
       sim.err_flags.zero_()
       sim.step(a, noise_uv=w, substeps=int(d['substeps'][j]))
       torch.cuda.synchronize()
       words.append(int(sim.err_flags.item()))
-  finally:
-    _lib.set_step_form({0: None, 1: '0', 4: '4'}.get(before, None))
   return words, sim
 
 
-@pytest.mark.parametrize('form,vehicle', [('0', None), ('4', None), ('0', {'payload_mass': 95.0})], ids=['one_lane', 'four_wave', 'runtime'])
+@pytest.mark.parametrize('form,vehicle', [(1, None), (4, None), (1, {'payload_mass': 95.0})], ids=['one_lane', 'four_wave', 'runtime'])
 def test_f18_flag_word_per_case(form, vehicle):
   """The one-lane and the four-wave form with the compile-time vehicle, and a run-time (non-NULL) vehicle -- which always flies the
   one-lane form's second instantiation (ble_kernels.hip), so it has no four-wave variant."""
@@ -87,7 +84,7 @@ def test_f18_second_launch_reads_the_ir_flag_from_the_episode_cache():
   names = [str(s) for s in d['names']]
   for name in ('ir_lo_in', 'ir_lo_out', 'ir_hi_in', 'ir_hi_out'):
     j = names.index(name)
-    words, sim = _run_case(d, j, '0', launches=2)
+    words, sim = _run_case(d, j, 1, launches=2)
     if d['exc'][j]:
       assert words == [2, 2], (name, words)
     else:
@@ -147,7 +144,7 @@ def test_f18_device_reset_flags():
       assert abs(t - d['reset_out_internal_temperature'][j]) <= 1e-5 * d['reset_out_internal_temperature'][j], name
 
 
-@pytest.mark.parametrize('form', ['0', '4'])
+@pytest.mark.parametrize('form', [1, 4], ids=['0', '4'])
 def test_f18_isolation_in_a_large_batch(form):
   """4096 - 37 environments, about 5 % of them F18's offending cases (18 substeps), the rest the clean case with varied winds: the
   clean lanes fly bit for bit what the same batch flies with the offending lanes replaced by clean ones, and the flag word is the
@@ -169,12 +166,9 @@ def test_f18_isolation_in_a_large_batch(form):
 
   def fly(rws):
     sim = _sim_for(f18_state(d, rws))
-    before = _lib.set_step_form(form)
-    try:
+    with _lib.step_form(form):
       sim.step(torch.from_numpy(acts).cuda(), noise_uv=torch.from_numpy(wind).cuda(), substeps=18)
       torch.cuda.synchronize()
-    finally:
-      _lib.set_step_form({0: None, 1: '0', 4: '4'}.get(before, None))
     return sim.get_state(), sim.reward.cpu().numpy(), int(sim.err_flags.item())
 
   mixed, r_mixed, word = fly(rows)

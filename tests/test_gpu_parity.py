@@ -13,7 +13,7 @@ import os
 import numpy as np
 import pytest
 
-from balloon_learning_environment_amd import _lib      # (set_step_form)
+from balloon_learning_environment_amd import _lib      # (step_form)
 
 pytestmark = pytest.mark.gpu
 
@@ -718,7 +718,7 @@ def test_wide_domain_states_every_env(ble):
 
 def test_one_lane_kernel_episodes_ending_inside_a_step_match_oracle(ble):
   """The one-lane kernel's stride loop is wave-uniform: a lane whose episode ends inside an agent step parks its final state in LDS on a
-  rare path and takes it back after the loop (csrc/ble_step_core.h, agent_step).  Forced here (BLE_STEP_SPLIT=0: the host would pick the
+  rare path and takes it back after the loop (csrc/ble_step_core.h, agent_step).  Forced here (_lib.step_form(1): the host would pick the
   four-wave kernel at this size) on a batch in which a good part of the environments run out of power or burst inside the rollout, every
   environment against the oracle from the kernel's own pre-step state: status, strides run (time_elapsed_s), state, reward, terminal."""
   import reset_host
@@ -726,11 +726,8 @@ def test_one_lane_kernel_episodes_ending_inside_a_step_match_oracle(ble):
   init = reset_host.sample_initial_state(n, seed=4242)
   init['battery_charge'][: n // 4] = np.linspace(0.05, 30.0, n // 4).astype(np.float32)          # out of power within a few strides .. steps
   init['superpressure'][n // 4: n // 4 + 256] = np.linspace(2300.0, 2379.0, 256).astype(np.float32)   # close to the burst limit
-  _lib.set_step_form('0')
-  try:
+  with _lib.step_form(1):
     total, outliers, worst = _sampled_batch_parity(ble, n, 6, seed=4243, threads=8, init=init)
-  finally:
-    _lib.set_step_form(None)
   assert outliers == 0, (outliers, total, worst)
   assert total < 6 * n - 200                       # (episodes did end: the live count of later steps is smaller)
 
@@ -953,7 +950,7 @@ def test_fused_rollout_equals_single_steps(ble, wide):
   np.testing.assert_array_equal(term.cpu().numpy(), term_c.cpu().numpy())
 
 
-@pytest.mark.parametrize('waves', ['0', '4'])
+@pytest.mark.parametrize('waves', [1, 4], ids=['0', '4'])
 @pytest.mark.parametrize('with_cache', [True, False])
 def test_fused_rollout_in_ground_truth_wind_equals_noise_plus_single_steps(ble, with_cache, waves):
   """ABI 3: ble_step_n_f32 with a noise generator flies every step in WindField.get_ground_truth = forecast + SimplexWindNoise
@@ -977,16 +974,13 @@ def test_fused_rollout_in_ground_truth_wind_equals_noise_plus_single_steps(ble, 
     s = ble.VecSimulator(n); s.set_state(init); s.set_grid(field); s.episode.copy_(episodes); sims.append(s)
   a, b, c = sims
   rew = torch.zeros((k, n), dtype=torch.float32).cuda(); term = torch.zeros((k, n), dtype=torch.uint8).cuda()
-  _lib.set_step_form(waves)
-  try:
+  with _lib.step_form(waves):
     if with_cache:
       a.step_n(acts, rew, term, noise_seed=seed)
     else:                                              # harmonic_cache NULL: the draws come straight from the Philox stream
       gen = _abi.BleNoiseGen(seed, a.episode.data_ptr(), None)
       _lib.check(a.lib.ble_step_n_f32(ctypes.byref(a._struct), acts.data_ptr(), a.grid.data_ptr(), 0, ctypes.byref(gen), rew.data_ptr(),
                                       term.data_ptr(), a.err_flags.data_ptr(), None, n, 18, k, dev.stream_ptr(a.device)), 'ble_step_n_f32')
-  finally:
-    _lib.set_step_form(None)
   rb, tb = [], []
   for j in range(k):
     noise = b.wind_noise(seed)
@@ -1006,12 +1000,12 @@ def test_fused_rollout_in_ground_truth_wind_equals_noise_plus_single_steps(ble, 
   assert np.median(moved) > 100.0                   # ~1 m/s of noise over 18 minutes
 
 
-@pytest.mark.parametrize('waves', ['4'])
+@pytest.mark.parametrize('waves', [4])
 @pytest.mark.parametrize('wide', [False, True])
 def test_split_kernel_equals_one_lane_kernel(ble, wide, waves):
   """The small-batch form of the transition -- one environment on FOUR wavefronts (csrc/ble_step_split.h: vertical dynamics |
   thermal model | sun + power | envelope + ACS, exchanging through LDS once per stride), which ble_step_f32 / ble_step_n_f32
-  select up to BLE_SPLIT_MAX_ENVS environments -- against the one-lane-per-environment kernel, forced with BLE_STEP_SPLIT:
+  select up to BLE_SPLIT_MAX_ENVS environments -- against the one-lane-per-environment kernel, forced with _lib.step_form:
   every state array, reward, terminal, effective action, the live counters and the error word, BIT FOR BIT; fused launches
   and single steps with a noise term, action bytes outside 0 .. 2, environments that end inside the rollout (early in a
   step, so that their lane stops while its neighbours go on), a batch that does not fill its last workgroup."""
@@ -1030,8 +1024,7 @@ def test_split_kernel_equals_one_lane_kernel(ble, wide, waves):
   noise = torch.from_numpy((np.random.default_rng(4).standard_normal((n, 2)) * 1.5).astype(np.float32)).cuda()
 
   def fly(split):
-    _lib.set_step_form(waves if split else '0')      # 4 wavefronts per environment (csrc/ble_step_split.h) against 1
-    try:
+    with _lib.step_form(waves if split else 1):      # 4 wavefronts per environment (csrc/ble_step_split.h) against 1
       sim = ble.VecSimulator(n); sim.set_state(init); sim.set_grid(field)
       rew = torch.zeros((k, n), dtype=torch.float32).cuda(); term = torch.zeros((k, n), dtype=torch.uint8).cuda()
       cnt = torch.zeros((k, ble.COUNT_SLOTS), dtype=torch.int64).cuda()
@@ -1043,8 +1036,6 @@ def test_split_kernel_equals_one_lane_kernel(ble, wide, waves):
       torch.cuda.synchronize()
       flags = int(sim.err_flags.item()); sim.err_flags.zero_()
       return sim.get_state(), rew.cpu().numpy(), term.cpu().numpy(), cnt.cpu().numpy(), singles, flags, int(sim.active_count.item())
-    finally:
-      _lib.set_step_form(None)
   a, b = fly(True), fly(False)
   for name in a[0]:
     np.testing.assert_array_equal(a[0][name], b[0][name], err_msg=name)

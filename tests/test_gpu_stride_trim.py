@@ -33,18 +33,15 @@ def test_fused_one_lane_equals_split_bit_for_bit():
   acts = torch.from_numpy(acts_h).cuda()
 
   def fly(form):
-    _lib.set_step_form(form)
-    try:
+    with _lib.step_form(form):
       sim = ble.VecSimulator(n); sim.set_state(init); sim.set_grid(field)
       rew = torch.zeros((k, n), dtype=torch.float32).cuda(); term = torch.zeros((k, n), dtype=torch.uint8).cuda()
       cnt = torch.zeros((k, ble.COUNT_SLOTS), dtype=torch.int64).cuda()
       sim.step_n(acts, rew, term, cnt)
       torch.cuda.synchronize()
       return sim.get_state(), rew.cpu().numpy(), term.cpu().numpy(), int(sim.err_flags.item())
-    finally:
-      _lib.set_step_form(None)
 
-  one, split = fly('0'), fly('4')
+  one, split = fly(1), fly(4)
   for name in one[0]:
     np.testing.assert_array_equal(one[0][name], split[0][name], err_msg=name)
   np.testing.assert_array_equal(one[1].view(np.uint32), split[1].view(np.uint32))
