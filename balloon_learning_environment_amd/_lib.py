@@ -38,7 +38,7 @@ ROW_DOUBLES = 26        # BLE_ROW_DOUBLES
 NOISE_CACHE_ROWS = 53
 
 # every symbol include/ble_abi.h declares
-EXPORTS = ('ble_abi_version', 'ble_noise_primitive_version', 'ble_vehicle_default', 'ble_last_hip_error', 'ble_device_count', 'ble_set_step_form', 'ble_step_f32', 'ble_step_n_f32', 'ble_reset_f32', 'ble_reset_at_f32', 'ble_wind_noise_at_f32', 'ble_observe_f32', 'ble_observe_forecast_f32', 'ble_decode_flow_fields_f32', 'ble_wind_noise_f32', 'ble_forecast_f32',
+EXPORTS = ('ble_abi_version', 'ble_noise_primitive_version', 'ble_vehicle_default', 'ble_last_hip_error', 'ble_device_count', 'ble_set_step_form', 'ble_last_step_form', 'ble_step_f32', 'ble_step_n_f32', 'ble_reset_f32', 'ble_reset_at_f32', 'ble_wind_noise_at_f32', 'ble_observe_f32', 'ble_observe_forecast_f32', 'ble_decode_flow_fields_f32', 'ble_wind_noise_f32', 'ble_forecast_f32',
            'ble_forecast_column_f32', 'ble_state_rows_f64', 'ble_power_table_f32', 'ble_probe_atmosphere_f32', 'ble_probe_atmosphere_at_height_f64', 'ble_probe_solar_f32', 'ble_probe_latlng_f64',
            'ble_probe_solar_power_f32', 'ble_probe_thermal_f32', 'ble_probe_sp_volume_f32', 'ble_probe_thermal_vehicle_f32', 'ble_probe_sp_volume_vehicle_f32', 'ble_probe_acs_f32', 'ble_probe_safety_f32',
            'ble_probe_f64_prims', 'ble_step_fleet_f32', 'ble_step_n_fleet_f32', 'ble_reset_fleet_at_f32', 'ble_observe_forecast_fleet_f32',
@@ -47,6 +47,9 @@ EXPORTS = ('ble_abi_version', 'ble_noise_primitive_version', 'ble_vehicle_defaul
            'ble_qnet_unpack_f32', 'ble_replay_sample_f32', 'ble_qnet_train_workspace_f32', 'ble_qnet_transpose_f32',
            'ble_qnet_train_step_f32', 'ble_qnet_explore_u8', 'ble_qnet_td_workspace_f32', 'ble_qnet_td_step_f32',
            'ble_replay_tree_add_f64', 'ble_replay_sample_prioritized_f32', 'ble_replay_set_priority_f32', 'ble_marco_polo_u8')
+# Exports added without a new ABI version: a library of this ABI built before them (BLE_HIP_LIB: the parent's, in A/B runs) still loads.
+# build() checks every name of EXPORTS on the library it builds.
+ADDITIVE_EXPORTS = ('ble_last_step_form',)
 
 
 class BleLibraryError(RuntimeError):
@@ -93,7 +96,7 @@ def lib():
   except OSError as e:  # e.g. libamdhip64 missing
     raise BleLibraryError(f'cannot load {LIB_PATH}: {e}') from e
   for name in EXPORTS:
-    if not hasattr(l, name):
+    if not hasattr(l, name) and name not in ADDITIVE_EXPORTS:
       raise BleLibraryError(f'{LIB_PATH} does not export {name}')
   if l.ble_abi_version() != ABI_VERSION:
     raise BleLibraryError('ABI version mismatch between libble_hip.so and the Python mirror')
@@ -127,6 +130,8 @@ def lib():
   l.ble_probe_safety_f32.argtypes = [_int, _vp, _vp, _vp, _vp, ctypes.c_double, ctypes.c_double, _vp, _vp, _vp, _i64, _vp]
   l.ble_probe_f64_prims.argtypes = [_vp, _vp, _int, _i64, _vp]
   l.ble_set_step_form.argtypes = [_int]
+  if hasattr(l, 'ble_last_step_form'):
+    l.ble_last_step_form.argtypes = []
   l.ble_vehicle_default.argtypes = [ctypes.POINTER(_abi.BleVehicle)]
   fleet = ctypes.POINTER(_abi.BleFleet)
   l.ble_step_fleet_f32.argtypes = [st, fleet] + l.ble_step_f32.argtypes[1:]
@@ -161,7 +166,8 @@ def lib():
   l.ble_replay_set_priority_f32.argtypes = [replay, tree, batch, _vp, _vp, _vp, _vp, _vp]
   l.ble_marco_polo_u8.argtypes = [ctypes.POINTER(_abi.BleMarcoPoloF32), _vp, _vp]
   for name in EXPORTS:
-    getattr(l, name).restype = _int
+    if hasattr(l, name) or name not in ADDITIVE_EXPORTS:
+      getattr(l, name).restype = _int
   _lib = l
   return l
 
@@ -177,6 +183,9 @@ def call(name: str, *args) -> None:
   check(getattr(lib(), name)(*args), name)
 
 
+STEP_FORM_HELPER = 12      # BLE_STEP_FORM_HELPER (include/ble_abi.h)
+
+
 class step_form:
   """`with _lib.step_form(waves): ...` forces the transition kernel's form (`ble_set_step_form`) for the launches inside the
   block and restores the previous setting: the only way to force one.  A/B runs and the bit-identity tests; the automatic
@@ -188,7 +197,8 @@ class step_form:
   def __enter__(self):
     self.before = lib().ble_set_step_form(self.waves)
     if self.before < 0:
-      raise ValueError(f'step form must be 0 (automatic), 1 (one lane per environment) or 4 (four wavefronts per environment), not {self.waves}')
+      raise ValueError(f'step form must be 0 (automatic), 1 (one lane per environment), 4 (four wavefronts per environment) or '
+                       f'{STEP_FORM_HELPER} (one lane per environment and a helper wave per 64), not {self.waves}')
     return self
 
   def __exit__(self, *exc):

@@ -33,6 +33,7 @@
 #include "ble_step_core.h"
 #include "ble_noise.h"
 #include "ble_step_split.h"
+#include "ble_step_helper.h"
 #include "ble_observe.h"
 #include "ble_decode.h"
 #include "ble_agent.h"
@@ -227,6 +228,109 @@ __global__ __launch_bounds__(kStepBlock) void ble_step_kernel(StateDev st, const
     st.alt_fsm[i] = s.alt_fsm; st.env_fsm[i] = s.env_fsm; st.power_paused[i] = s.paused;
   }
   BLE_STEP_INSTR_END();
+  report_flags(flags, err_flags);
+}
+
+// The one-lane transition with a helper wave (ble_step_helper.h): 512-thread workgroups, two waves per SIMD -- M, the lane's environment
+// minus the solar block, and S, its sun.  One instantiation: no in-kernel noise, the default vehicle.  M below is ble_step_kernel's body
+// without its noise, fleet and clock-mark parts (the timing build instruments the one-lane kernel only).  The two bodies are kept as text
+// on purpose: moving the state load, the per-episode constants and the state store into functions shared by both changed the register
+// allocation and schedule of all six ble_step_kernel instantiations (profiles/isa_compare.py), which needs a timing run of every leg to accept.
+__global__ __launch_bounds__(kHelperBlock) void ble_step_helper_kernel(StateDev st, const uint8_t* __restrict__ action,
+                                                                     const float* __restrict__ wind_grid, int64_t grid_env_stride,
+                                                                     const float* __restrict__ noise_uv, float* __restrict__ reward,
+                                                                     uint8_t* __restrict__ terminal, uint8_t* __restrict__ effective_action,
+                                                                     uint32_t* err_flags, unsigned long long* active_count, int64_t n,
+                                                                     int substeps, int n_steps) {
+  __shared__ HelperShared sh;
+  __shared__ double acs_poly[kAcsPolyDoubles];
+  __shared__ float term_save[kTermSaveRows * kTermSaveStride * kHelperGroups];
+  const int hw_wave = __builtin_amdgcn_readfirstlane((int)threadIdx.x >> 6), lane = (int)threadIdx.x & 63;
+  for (int j = (int)threadIdx.x; j < kAcsPolyDoubles; j += kHelperBlock) acs_poly[j] = kAcsPoly.c[j];
+  const int role = helper_assign_roles(sh, hw_wave, lane);      // (its barriers cover the table)
+  const int group = role >> 1;
+  HelperGroupShared* const g = &sh.group[group];
+  const int64_t i = ((int64_t)blockIdx.x * kHelperGroups + group) * 64 + lane;
+  const bool in_range = i < n;
+  if (role & 1) {
+    helper_wave(st, g, lane, i, in_range, substeps, n_steps);
+    return;
+  }
+  uint32_t flags = 0;
+  EnvRegs s;
+  EnvConst c;
+  EpisodeCacheRow cached = {};
+  bool live = false;
+  if (in_range) {
+    s.status = st.status[i];
+    s.x = st.x[i]; s.y = st.y[i]; s.p = st.pressure[i]; s.t_amb = st.ambient_temperature[i];
+    s.t_int = st.internal_temperature[i]; s.vol = st.envelope_volume[i]; s.sp = st.superpressure[i];
+    s.n_air = st.mols_air[i]; s.batt = st.battery_charge[i];
+    s.acs_power = 0.0f; s.mdot = 0.0f; s.charge = 0.0f; s.load = 0.0f;
+    s.t_elapsed = st.time_elapsed_s[i]; s.sunrise_h = st.sunrise_h_rel[i]; s.sunset = st.sunset_rel[i];
+    s.alt_fsm = st.alt_fsm[i]; s.env_fsm = st.env_fsm[i]; s.paused = st.power_paused[i];
+    c.lat0_deg = st.center_lat_deg[i]; c.lng0_deg = st.center_lng_deg[i];
+    c.ir = st.upwelling_infrared[i]; c.alpha = st.alpha[i]; c.start_unix = st.start_unix[i];
+    if (st.episode_cache != nullptr) cached = episode_cache_load(st.episode_cache, n, i);
+    live = s.status == kOk;
+  }
+  const bool was_live = live;
+  int last_act = 0;
+  EnvHoisted hc;
+  if (live) {
+    if (st.episode_cache != nullptr && episode_cache_hit(cached, c)) {
+      hc = hoisted_from_cache(cached, c);
+    } else {
+      hc = hoist_constants(c);
+      if (st.episode_cache != nullptr) episode_cache_store(st.episode_cache, n, i, c, hc);
+    }
+  }
+  const StrideK K = stride_k_vreg();
+  HelperMain hm{g, lane, 0, 0, 0};
+#pragma unroll 1
+  for (int k = 0; k < n_steps; ++k) {
+    const int64_t o = (int64_t)k * n + i;
+    const bool any_live = wave_any(live);
+    hm.steps_done = k + 1;                     // (scalar, whole wave: what this step's publication stores, whichever lanes make it)
+    if (live) {
+      const int act = action[o];
+      last_act = act;
+      const WindQuery wq = wind_query(s.x, s.y, s.p, s.t_elapsed);
+      WindCorners corners;
+      wind_gather(wind_grid + i * grid_env_stride, wq, &corners);
+      float nu = 0.0f, nv = 0.0f;
+      if (noise_uv) { nu = noise_uv[2 * i]; nv = noise_uv[2 * i + 1]; }
+      float r;
+      const int eff = agent_step(s, c, hc, act, corners, wq, nu, nv, substeps, acs_poly, K, term_save + group * (kTermSaveRows * kTermSaveStride) + lane,
+                                 &r, &flags, VehicleDefault(), &hm);
+      if (!(isfinite(s.p) && isfinite(s.t_int) && isfinite(s.x) && isfinite(s.y) && isfinite(s.batt)))
+        flags |= kFlagNonFinite;
+      reward[o] = r;
+      terminal[o] = s.status != kOk;
+      if (effective_action) effective_action[o] = (uint8_t)eff;
+    } else if (in_range) {
+      reward[o] = 0.0f;
+      terminal[o] = 1;
+      if (effective_action) effective_action[o] = action[o];
+    }
+    if (!any_live) hm.publish_idle();          // S waits for every step's publication
+    if (BLE_STEP_COUNTS_LIVE && active_count) {
+      const unsigned long long m = __ballot(live);
+      if (lane == 0 && m)
+        atomicAdd(active_count + (int64_t)k * BLE_COUNT_SLOTS + (blockIdx.x & (BLE_COUNT_SLOTS - 1)), (unsigned long long)__popcll(m));
+    }
+    live = live && s.status == kOk;
+  }
+  if (was_live) {
+    st.x[i] = s.x; st.y[i] = s.y; st.pressure[i] = s.p; st.ambient_temperature[i] = s.t_amb;
+    st.internal_temperature[i] = s.t_int; st.envelope_volume[i] = s.vol; st.superpressure[i] = s.sp;
+    st.mols_air[i] = s.n_air; st.battery_charge[i] = s.batt;
+    st.acs_power[i] = s.acs_power; st.acs_mass_flow[i] = s.mdot; st.solar_charging[i] = s.charge;
+    st.power_load[i] = s.load;
+    st.time_elapsed_s[i] = s.t_elapsed; st.sunrise_h_rel[i] = s.sunrise_h; st.sunset_rel[i] = s.sunset;
+    st.status[i] = s.status; st.last_command[i] = (uint8_t)last_act;
+    st.alt_fsm[i] = s.alt_fsm; st.env_fsm[i] = s.env_fsm; st.power_paused[i] = s.paused;
+  }
   report_flags(flags, err_flags);
 }
 
@@ -743,7 +847,8 @@ inline StateDev state_dev(const ble_state_f32* st) {
 // form (A/B runs and the parity test); BLE_STEP_SPLIT=0 / 1 / 4 in the process environment is read ONCE, when the
 // library first needs it, as that switch's initial value (it used to be re-read by getenv on every launch: host work on the
 // 3 us launch path and a data race with a concurrent setenv).
-// g_step_form: -1 not initialised, 0 automatic, 1 / 4 wavefronts per environment.
+// g_step_form: -1 not initialised, 0 automatic, 1 / 4 wavefronts per environment, BLE_STEP_FORM_HELPER (12): one lane per environment plus a
+// helper wave per 64 of them (ble_step_helper.h; set by ble_set_step_form only, no environment spelling).
 std::atomic<int> g_step_form{-1};
 inline int step_form_from_environment() {
   const char* e = getenv("BLE_STEP_SPLIT");
@@ -763,16 +868,41 @@ inline int step_form() {
   }
   return f;
 }
-// returns the number of waves per environment: 1 (ble_step_kernel) or 4 (ble_step_split_kernel)
-inline int split_waves(int64_t n) {
-  const int f = step_form();
-  return f != 0 ? f : (n <= BLE_SPLIT_MAX_ENVS ? 4 : 1);
+// The helper form wants a free second wave slot on the SIMD of every 64 environments: ceil(n / 64) <= 4 x the device's CUs.  The count of
+// the calling thread's current device, asked of the runtime once per device; a failure is an error of the launch (BLE_E_NO_DEVICE), never
+// a quiet choice of another form.
+inline int compute_units() {
+  static std::atomic<int> cached[64];
+  int dev = 0;
+  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return BLE_E_NO_DEVICE;
+  int cus = cached[dev].load(std::memory_order_relaxed);
+  if (cus == 0) {
+    if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0) return BLE_E_NO_DEVICE;
+    cached[dev].store(cus, std::memory_order_relaxed);
+  }
+  return cus;
+}
+// The form a default-vehicle launch of n environments takes: 1 (ble_step_kernel), 4 (ble_step_split_kernel),
+// BLE_STEP_FORM_HELPER (ble_step_helper_kernel), or a negative BLE_E_*.  `noise`: with a wind-noise generator (the helper form has no such
+// instantiation: the one-lane form flies).
+inline int split_waves(int64_t n, bool noise) {
+  int f = step_form();
+  if (f == 0) {
+    if (n <= BLE_SPLIT_MAX_ENVS) return 4;
+    if (noise) return 1;
+    const int cus = compute_units();
+    if (cus < 0) return cus;
+    f = (n + 63) / 64 <= 4 * (int64_t)cus ? BLE_STEP_FORM_HELPER : 1;
+  }
+  return f == BLE_STEP_FORM_HELPER && noise ? 1 : f;
 }
 // hipGetLastError is per-thread and sticky: an error left behind by an unrelated runtime call
 // of the host application (torch probes pointers / peers at start-up) must not be reported as
 // ours, so every launch first drains it, and the launch's own status is kept for
 // ble_last_hip_error().
 thread_local int g_last_hip_error = 0;
+// the form of the calling thread's most recent transition launch (ble_last_step_form): 0 before the first one
+thread_local int g_last_step_form = 0;
 template <class... P, class... A>
 int launch_grid(void (*kernel)(P...), dim3 grid, int threads, void* stream, const A&... args) {
   (void)hipGetLastError();
@@ -904,13 +1034,20 @@ int launch_step(const ble_state_f32* st, const ble_fleet* fleet, const uint8_t* 
     return with_noise(noise, [&](auto noise_on, StepNoise gen) {
       constexpr bool kNoise = decltype(noise_on)::value;
       if constexpr (std::is_same_v<decltype(veh), VehicleDefault>) {
-        const int waves = split_waves(n);
-        if (waves != 1) {
+        const int waves = split_waves(n, kNoise);
+        if (waves < 0) return waves;
+        g_last_step_form = waves;
+        if (waves == BLE_STEP_FORM_HELPER) {
+          if constexpr (!kNoise)                  // (split_waves never answers it with noise)
+            return launch(ble_step_helper_kernel, n, 64 * kHelperGroups, kHelperBlock, stream, state_dev(st), action, wind_grid, grid_env_stride,
+                          noise_uv, reward, terminal, effective_action, err_flags, active_count, n, substeps, n_steps);
+        } else if (waves != 1) {
           const SplitArgs a{state_dev(st), action, wind_grid, grid_env_stride, noise_uv, reward, terminal, effective_action, err_flags,
                             active_count, n, substeps, n_steps, gen};
           return launch(ble_step_split_kernel<kNoise>, n, kSplitLanes, kSplitWaves * kSplitLanes, stream, a);
         }
       }
+      g_last_step_form = 1;
       return launch(ble_step_kernel<kNoise, decltype(veh)>, n, kBlock * (kStepBlock / 64), kStepBlock, stream, state_dev(st), action,
                     wind_grid, grid_env_stride, noise_uv, reward, terminal, effective_action, err_flags, active_count, n, substeps, kBlock,
                     n_steps, gen, veh);
@@ -960,11 +1097,13 @@ int ble_vehicle_default(ble_vehicle* v) {
 int ble_last_hip_error(void) { return g_last_hip_error; }
 
 int ble_set_step_form(int waves_per_env) {
-  if (waves_per_env != 0 && waves_per_env != 1 && waves_per_env != 4) return BLE_E_INVALID_ARG;
+  if (waves_per_env != 0 && waves_per_env != 1 && waves_per_env != 4 && waves_per_env != BLE_STEP_FORM_HELPER) return BLE_E_INVALID_ARG;
   const int before = step_form();
   g_step_form.store(waves_per_env, std::memory_order_relaxed);
   return before;
 }
+
+int ble_last_step_form(void) { return g_last_step_form; }
 
 int ble_device_count(void) {
   int n = 0;

@@ -1167,14 +1167,21 @@ BLE_FN SunState sun_exact(double lat0_deg, double lng0_deg, double x, double y, 
 
 // solar_atmospheric_attenuation (solar.py:177-209) from sin(el); 0 at night (`day` false).
 // The reference's pressure range check (:194-197) is done by the caller once per agent step.
-BLE_FN float solar_attenuation(float sin_el, float pressure, bool day) {
+// Its two halves, cut at an operation boundary (every rounding stays): what the sun alone decides -- sqrt(1229 + t^2) - t, t = 614 sin(el)
+// (ble_step_helper.h evaluates it on the helper wave) -- and the pressure's share.
+BLE_FN float solar_airmass_diff(float sin_el) {
   const float t = 614.0f * sin_el;
   const float root = f_sqrt(f_fma(t, t, 1229.0f));
   // sqrt(1229 + t^2) - t, written without cancellation for t > 0
-  const float diff = t > 0.0f ? 1229.0f * f_rcp(root + t) : root - t;
+  return t > 0.0f ? 1229.0f * f_rcp(root + t) : root - t;
+}
+BLE_FN float solar_attenuation_from_diff(float diff, float pressure, bool day) {
   const float airmass = (pressure * (0.34764f / 101325.0f)) * diff;
   const float att = 0.5f * (f_exp2(airmass * (-0.65f * kLog2e)) + f_exp2(airmass * (-0.95f * kLog2e)));   // constants folded: 3 multiplies fewer
   return day ? att : 0.0f;
+}
+BLE_FN float solar_attenuation(float sin_el, float pressure, bool day) {
+  return solar_attenuation_from_diff(solar_airmass_diff(sin_el), pressure, day);
 }
 // solar_power (solar.py:515-536) with balloon_shadow (:212-236) folded in.
 // the part that depends on the sun alone: projected, shadowed panel area per unit (ble_step_split.h evaluates it a stride ahead)

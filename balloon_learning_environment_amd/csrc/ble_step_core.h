@@ -299,13 +299,13 @@ BLE_FN bool battery_above_99_percent(float batt, double capacity_wh = VehicleDef
 }
 // perciatelli_reward_function (env/balloon_env.py:44-102) on the post-step state; `sun` = the sun at the end of the step
 // (only read when the raw action was DOWN: last_command is the RAW action, balloon.py:286)
-template <typename SunFn>
-BLE_FN float step_reward(int action, float x, float y, float p, float batt, float acs_power, SunFn sun_end,
-                         float day_load = VehicleDefault::day_load, double capacity_wh = VehicleDefault::capacity_d) {
+// (power_end: the solar power at the end of the step, at the post-step pressure)
+template <typename PowerFn>
+BLE_FN float step_reward_from_power(int action, float x, float y, float batt, float acs_power, PowerFn power_end,
+                                    float day_load = VehicleDefault::day_load, double capacity_wh = VehicleDefault::capacity_d) {
   float r = reward_distance(x, y);
   if (action == kDown) {
-    const SunState sun = sun_end();
-    const float pw = solar_power(sun, solar_attenuation(sun.sin_el, p, sun.day));
+    const float pw = power_end();
     const bool excess = (pw > day_load) && battery_above_99_percent(batt, capacity_wh);   // balloon.py:231-238
     if (!excess) {
       const float scale = f_clamp((acs_power - 100.0f) * (1.0f / 200.0f), 0.0f, 1.0f);
@@ -313,6 +313,14 @@ BLE_FN float step_reward(int action, float x, float y, float p, float batt, floa
     }
   }
   return r;
+}
+template <typename SunFn>
+BLE_FN float step_reward(int action, float x, float y, float p, float batt, float acs_power, SunFn sun_end,
+                         float day_load = VehicleDefault::day_load, double capacity_wh = VehicleDefault::capacity_d) {
+  return step_reward_from_power(action, x, y, batt, acs_power, [&]() {
+    const SunState sun = sun_end();
+    return solar_power(sun, solar_attenuation(sun.sin_el, p, sun.day));
+  }, day_load, capacity_wh);
 }
 
 constexpr int kTermSaveRows = 14, kTermSaveStride = 64;   // agent_step's parking area: 13 state / output floats + (status | strides << 8 | kTermAbsBit), one column per lane
@@ -322,10 +330,15 @@ constexpr int kTermAbsBit = 1 << 16;                       // (strides <= BLE_MA
 // The wind is handed over as the 16 gathered grid corners + weights (+ additive noise): the
 // blend happens after the per-step constants so that the gather's latency is covered.
 // `veh`: the flight vehicle (VehicleDefault: compile-time constants -- the code and the bits of every round before ABI 5 --, or VehicleRt).
-template <class V = VehicleDefault>
+// `helper` (ble_step_helper.h, HelperMain): the sun of every stride comes from a co-resident helper wave as one SunRecord per stride
+// instead of being evaluated here -- the same lane functions on the same inputs, cut at operation boundaries, hence the same bits.
+struct NoHelper { static constexpr bool kOn = false; };
+// what the helper wave hands over per stride: the attenuation's pressure-independent half, the panel factor (the two shadows folded in), the flux, bit 0 of `bits` = day
+struct SunRecord { float diff, panel_factor, flux; uint32_t bits; };
+template <class V = VehicleDefault, class H = NoHelper>
 BLE_FN int agent_step(EnvRegs& s, const EnvConst& c, const EnvHoisted& hc, int action, const WindCorners& corners, const WindQuery& wq,
                       float noise_u, float noise_v, int substeps, const double* acs_poly, const StrideK& K, float* term_save,
-                      float* reward, uint32_t* flags, const V& veh = V()) {
+                      float* reward, uint32_t* flags, const V& veh = V(), H* helper = nullptr) {
   BLE_STEP_TICK(0);
   // ---- atmosphere at the pre-step pressure, fp64 (altitude layer + start of T(p) chain)
   const float p0_in = s.p;
@@ -359,6 +372,9 @@ BLE_FN int agent_step(EnvRegs& s, const EnvConst& c, const EnvHoisted& hc, int a
   const SolarNodes nodes = solar_nodes_time(e0, t0, c.lng0_deg, step_s);
   const SunQuadratic sq = solar_nodes_site(nodes, hc.sin_lat0, hc.cos_lat0, s.x, s.y, u, v, substeps);
   BLE_STEP_TICK(4);
+  // With a helper wave the block above is dead but for the wind (nothing below reads e0, nodes or sq): the helper holds this step's
+  // ephemeris already and needs the position and the wind for the three solar nodes.
+  if constexpr (H::kOn) helper->publish(s.x, s.y, u, v, s.t_elapsed);
   // (position and time at the START of the step, by value: the reward below calls this after s has been advanced)
   const float x_start = s.x, y_start = s.y;
   const int32_t t_start = s.t_elapsed;
@@ -391,16 +407,26 @@ BLE_FN int agent_step(EnvRegs& s, const EnvConst& c, const EnvHoisted& hc, int a
     const double rp = d_rcp(p);
     t_int_lo = d_min_raw(t_int_lo, t_int); t_int_hi = d_max_raw(t_int_hi, t_int);
     // ---- sun position at (x, y, date_time) of the OLD state (balloon.py:451-452)
-    const float fk = (float)k;
-    const SunState sun = sun_at(k);
-    const float flux = f_fma(fk, dfl, fl0);
+    SunState sun;
+    SunRecord rec;
+    float flux;
+    if constexpr (!H::kOn) {
+      const float fk = (float)k;
+      sun = sun_at(k);
+      flux = f_fma(fk, dfl, fl0);
+    } else {
+      rec = helper->record(k);
+      flux = rec.flux;
+    }
 
     // ---- step 2: buoyancy -> dh/dt -> dp (balloon.py:412-445)
     const double yc = inv_cbrt_volume(vol);
     const double p_new = stride_pressure(win, lc, p, rp, vol, n_air, t_amb, t_at_p, yc, K, veh.drag_arg);
 
     // ---- step 3: temperatures (balloon.py:451-467)
-    const float att = solar_attenuation(sun.sin_el, pf, sun.day);
+    float att;
+    if constexpr (!H::kOn) att = solar_attenuation(sun.sin_el, pf, sun.day);
+    else att = solar_attenuation_from_diff(rec.diff, pf, (rec.bits & 1u) != 0);
     const double t_int_new = stride_internal_temperature(vol, yc, t_int, t_amb, p, flux, att, q_earth, K, veh.thermal_scale);
 
     // ---- step 4: superpressure and volume (balloon.py:470-482)
@@ -414,7 +440,8 @@ BLE_FN int agent_step(EnvRegs& s, const EnvConst& c, const EnvHoisted& hc, int a
     const double n_air_new = stride_mols_air(n_air, mdot_d);
 
     // ---- step 6: power (balloon.py:524-542)
-    stride_power(sun, att, acs_w, &charge, &load, &batt, veh.day_load, veh.night_load, veh.capacity);
+    if constexpr (!H::kOn) stride_power(sun, att, acs_w, &charge, &load, &batt, veh.day_load, veh.night_load, veh.capacity);
+    else stride_power_from_factor((rec.bits & 1u) != 0, rec.panel_factor, att, acs_w, &charge, &load, &batt, veh.day_load, veh.night_load, veh.capacity);
     terminal = terminal || batt <= 0.0f;          // balloon.py:541-542
 
     // ---- commit (balloon.py:322-325): every RHS above used the old state
@@ -439,6 +466,7 @@ BLE_FN int agent_step(EnvRegs& s, const EnvConst& c, const EnvHoisted& hc, int a
       // the temperature range of the strides run so far: the reference stops after this one (kTermAbsBit: above status and strides)
       const int abs_bad = absorptivity_out_of_range(t_int_lo) || absorptivity_out_of_range(t_int_hi) ? kTermAbsBit : 0;
       *term_word = __builtin_bit_cast(float, st | (strides << 8) | abs_bad);
+      if constexpr (H::kOn) helper->park_reward_record(k + 1);      // the reward's sun of this lane: the record of the stride it did not run
     }
   };
   // two strides per iteration: the loop-carried values alternate between two sets of registers instead of being copied
@@ -453,6 +481,8 @@ BLE_FN int agent_step(EnvRegs& s, const EnvConst& c, const EnvHoisted& hc, int a
   int k = substeps;                      // strides this lane ran (>= 1: the host entry point checks substeps >= 1)
   const int word = __builtin_bit_cast(int, *term_word);
   const bool done = word != 0;
+  SunRecord rec_end;
+  if constexpr (H::kOn) rec_end = helper->record_end(substeps);
   bool abs_bad = absorptivity_out_of_range(t_int_lo) || absorptivity_out_of_range(t_int_hi);
   if (__builtin_expect(wave_any(done), 0)) if (done) {
     s.x = term_save[0]; s.y = term_save[kTermSaveStride]; s.p = term_save[2 * kTermSaveStride]; s.t_amb = term_save[3 * kTermSaveStride];
@@ -460,6 +490,7 @@ BLE_FN int agent_step(EnvRegs& s, const EnvConst& c, const EnvHoisted& hc, int a
     s.n_air = term_save[7 * kTermSaveStride]; s.batt = term_save[8 * kTermSaveStride]; s.acs_power = term_save[9 * kTermSaveStride];
     s.mdot = term_save[10 * kTermSaveStride]; s.charge = term_save[11 * kTermSaveStride]; s.load = term_save[12 * kTermSaveStride];
     status = word & 0xff; k = (word >> 8) & 0xff; abs_bad = (word & kTermAbsBit) != 0;
+    if constexpr (H::kOn) rec_end = helper->parked_reward_record();
   }
   s.t_elapsed += 10 * k;
   s.status = (uint8_t)status;
@@ -469,7 +500,13 @@ BLE_FN int agent_step(EnvRegs& s, const EnvConst& c, const EnvHoisted& hc, int a
   *flags |= (s.p > 101325.0f || s.p < 0.0f || p0_in > 101325.0f || p0_in < 0.0f) ? kFlagSolarRange : 0u;
 
   // ---- reward (env/balloon_env.py:44-102), on the post-step state
+  if constexpr (!H::kOn) {
   *reward = step_reward(action, s.x, s.y, s.p, s.batt, s.acs_power, [&]() { return sun_at(k); }, veh.day_load, veh.capacity_d);
+  } else {
+    *reward = step_reward_from_power(action, s.x, s.y, s.batt, s.acs_power, [&]() {
+      return solar_power_from_factor(rec_end.panel_factor, solar_attenuation_from_diff(rec_end.diff, s.p, (rec_end.bits & 1u) != 0));
+    }, veh.day_load, veh.capacity_d);
+  }
   BLE_STEP_TICK(6);
   return eff;
 }

@@ -170,9 +170,15 @@ typedef struct ble_state_f32 {
 /* Up to this many environments ble_step_f32 / ble_step_n_f32 -- with or without a wind-noise generator -- run the
  * four-wavefronts-per-environment form of the transition (csrc/ble_step_split.h: 4 x n / 64 waves -- one per SIMD up to
  * 16 384 environments, two up to 32 768), above it the one-lane-per-environment kernel (one wave per SIMD at 65 536).
+ * Above it, without a wind-noise generator and while ceil(n / 64) <= 4 x the device's compute units (every SIMD has a free
+ * second wave slot: n <= 65 536 on 256 CUs), the one-lane kernel flies with a helper wave per 64 environments that evaluates the
+ * strides' sun (csrc/ble_step_helper.h, BLE_STEP_FORM_HELPER).
  * The forms are bit-identical; ble_set_step_form() forces one.  A run-time vehicle (st->vehicle) or a fleet always flies the
  * one-lane form, whatever ble_set_step_form or the automatic choice says. */
 #define BLE_SPLIT_MAX_ENVS 32768
+/* ble_set_step_form's value for the one-lane form with a helper wave (not a number of wavefronts per environment; additive, ABI
+ * version unchanged).  A launch with a wind-noise generator flies the plain one-lane form when this is forced. */
+#define BLE_STEP_FORM_HELPER 12
 
 int ble_abi_version(void);
 
@@ -187,7 +193,8 @@ int ble_vehicle_default(ble_vehicle* v);
 int ble_last_hip_error(void);
 
 /* Which form of the transition kernel ble_step_f32 / ble_step_n_f32 launch: 0 = automatic (by batch size, above), 1 = one
- * lane per environment, 4 = four wavefronts per environment.  2 is refused with BLE_E_INVALID_ARG since ABI 5, like every other
+ * lane per environment, 4 = four wavefronts per environment, BLE_STEP_FORM_HELPER (12) = one lane per environment plus a helper
+ * wave per 64 environments.  2 is refused with BLE_E_INVALID_ARG since ABI 5, like every other
  * value: the two-wavefront form was never selected and measured slower at every batch size.
  * Process-global, thread-safe; takes effect with the next launch.  Returns the previous setting (>= 0) or
  * BLE_E_INVALID_ARG.  The initial value comes from BLE_STEP_SPLIT in the process environment when the library first looks at
@@ -195,6 +202,12 @@ int ble_last_hip_error(void);
  * unset -> automatic.  (ABI 4; ABI 3 re-read the variable on every launch.)  Honoured for the default vehicle only: a run-time
  * vehicle or a fleet always flies the one-lane form. */
 int ble_set_step_form(int waves_per_env);
+
+/* The form of the calling thread's most recent ble_step_f32 / ble_step_n_f32 launch (or of their fleet forms): 1, 4 or
+ * BLE_STEP_FORM_HELPER -- what was forced, or what the automatic choice took (above); 0 before the first launch.  A launch the
+ * automatic choice could not decide (the device would not tell its compute units) fails with BLE_E_NO_DEVICE and leaves this
+ * alone.  Diagnostic, like ble_last_hip_error.  Additive, ABI version unchanged. */
+int ble_last_step_form(void);
 
 /* Number of visible HIP devices (>= 0) or BLE_E_NO_DEVICE. */
 int ble_device_count(void);

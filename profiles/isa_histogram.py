@@ -16,7 +16,12 @@ the stride (`if (ks < substeps) stride(ks)`: an even `substeps` never runs it). 
 comments (`Loop Header`, `in Loop: Header=`): a profiling aid for this compiler, not a disassembler.  One table per revision, one column
 per part, the stride loop also per stride; --dump (--dump-step) prints the hot path of the stride loop (of the per-step part) with its line numbers in the .s file (kept in
 the temporary directory as isa_histogram_<rev>.s) for attribution to the
-source."""
+source.
+
+A kernel with a helper wave (--kernel ble_step_helper_kernel, csrc/ble_step_helper.h) holds TWO role loops.  The main wave's are found as
+above (its stride carries the fp64).  The helper wave's step loop is the other outermost loop of the kernel, and its record loop -- one
+SunRecord per iteration, i.e. per stride -- the loop inside it with the most instructions (the others are the polling loops of the
+hand-over, a handful of instructions each).  A second table gives the helper's record loop and per-step part."""
 import os
 import re
 import subprocess
@@ -152,9 +157,57 @@ def analyse(asm: str, key: str):
   for _, t, loop in body:
     if loop and '_f64' in t.split()[0]:
       f64[loop] = f64.get(loop, 0) + 1
-  stride = max((l for l in f64 if l not in parents.values()), key=f64.get)       # the innermost loop with the most fp64 work
+  # the innermost loop with the most fp64 work on its hot path (a rare fp64 chain kept inside another loop -- the helper wave's sun_exact --
+  # does not count); polling loops of a hand-over inside it (ble_step_helper.h: a few instructions, no fp64,
+  # behind a branch the hot path does not take) do not make it an outer loop
+  size = {}
+  for _, t, loop in body:
+    if loop and not t.endswith(':'):
+      size[loop] = size.get(loop, 0) + 1
+  def innermost(l):
+    return all(size.get(c, 0) < 30 and c not in f64 for c, p in parents.items() if p == l)
+  def hot_f64(l):
+    return sum('_f64' in body[k][1].split()[0] for k in hot_path(body, parents, l))
+  stride = max((l for l in f64 if innermost(l)), key=hot_f64)
   step = parents[stride]
   return name, body, hot_path(body, parents, stride), hot_path(body, parents, step, inner=stride)
+
+
+def analyse_helper_role(body, parents, main_step):
+  """(record loop's hot path, per-step hot path) of the helper wave: the loops outside the main wave's step loop; None if there are none"""
+  size = {}
+  for _, t, loop in body:
+    if loop and not t.endswith(':'):
+      size[loop] = size.get(loop, 0) + 1
+  def root(l):
+    while parents.get(l) is not None:
+      l = parents[l]
+    return l
+  total = {}
+  for l, v in size.items():
+    if root(l) != root(main_step):
+      total[root(l)] = total.get(root(l), 0) + v
+  if not total:
+    return None
+  step = max(total, key=total.get)
+  inner = [l for l in size if l != step and in_loop(l, step, parents)]
+  if not inner:
+    return None
+  record = max(inner, key=size.get)
+  return hot_path(body, parents, record), hot_path(body, parents, step, inner=record)
+
+
+def report_helper_role(body, record_path, step_path) -> None:
+  hr, hp = histogram(body, record_path), histogram(body, step_path)
+  print(f'helper wave: record loop .s lines {body[record_path[0]][0]}-{body[record_path[-1]][0]} (one record = one stride per iteration)')
+  print('| Class | Per record (stride) | Per-step part |')
+  print('|---|---|---|')
+  for c in CLASSES:
+    print(f'| {c} | {hr[c]} | {hp[c]} |')
+  print(f'| **all** | {len(record_path)} | {len(step_path)} |')
+  vec = lambda h: sum(v for c, v in h.items() if c in CLASSES[:9])
+  print(f'vector (incl. LDS, memory) / scalar per record: {vec(hr)} / {len(record_path) - vec(hr)}; per-step part: {vec(hp)} / {len(step_path) - vec(hp)}')
+  print()
 
 
 def report(rev: str, asm: str, key: str, dump: bool) -> None:
@@ -170,6 +223,13 @@ def report(rev: str, asm: str, key: str, dump: bool) -> None:
   vec = lambda h: sum(v for c, v in h.items() if c in CLASSES[:9])
   print(f'vector (incl. LDS, memory) / scalar per two strides: {vec(hs)} / {len(stride_path) - vec(hs)}; per-step part: {vec(hp)} / {len(step_path) - vec(hp)}')
   print()
+  _, _, parents = kernel_body(asm, key)
+  helper = analyse_helper_role(body, parents, body[step_path[0]][2] if body[step_path[0]][2] else None) if 'helper' in name else None
+  if helper:
+    report_helper_role(body, *helper)
+    if dump == 'helper':
+      for k in helper[0]:
+        print(f'{body[k][0]:7d}  {classify(body[k][1].split()[0]):16s} {body[k][1]}')
   if dump:
     for k in (step_path if dump == 'step' else stride_path):
       print(f'{body[k][0]:7d}  {classify(body[k][1].split()[0]):16s} {body[k][1]}')
@@ -177,7 +237,7 @@ def report(rev: str, asm: str, key: str, dump: bool) -> None:
 
 def main() -> int:
   args = sys.argv[1:]
-  dump = 'step' if '--dump-step' in args else '--dump' in args
+  dump = 'step' if '--dump-step' in args else ('helper' if '--dump-helper' in args else '--dump' in args)
   key = DEFAULT_KERNEL
   if '--kernel' in args:
     key = args[args.index('--kernel') + 1]
