@@ -340,6 +340,14 @@ BLE_FN int agent_step(EnvRegs& s, const EnvConst& c, const EnvHoisted& hc, int a
                       float noise_u, float noise_v, int substeps, const double* acs_poly, const StrideK& K, float* term_save,
                       float* reward, uint32_t* flags, const V& veh = V(), H* helper = nullptr) {
   BLE_STEP_TICK(0);
+  float u, v;
+  // With a helper wave the wind and the publication come first: the helper holds this step's ephemeris already and needs the position and
+  // the wind for the three solar nodes, which it computes while this wave runs the atmosphere and the safety layers below.
+  if constexpr (H::kOn) {
+    wind_blend_corners(corners, wq, &u, &v);
+    u += noise_u; v += noise_v;
+    helper->publish(s.x, s.y, u, v, s.t_elapsed);
+  }
   // ---- atmosphere at the pre-step pressure, fp64 (altitude layer + start of T(p) chain)
   const float p0_in = s.p;
   double p = (double)s.p;
@@ -363,18 +371,17 @@ BLE_FN int agent_step(EnvRegs& s, const EnvConst& c, const EnvHoisted& hc, int a
   const float step_s = (float)(10 * substeps);
   const float fl0 = e0.flux, dfl = e0.flux_rate * 10.0f;
   BLE_STEP_TICK(2);
-  float u, v;
-  wind_blend_corners(corners, wq, &u, &v);         // wind at the PRE-step position/time
-  u += noise_u; v += noise_v;                      // WindField.get_ground_truth = forecast + noise
+  if constexpr (!H::kOn) {
+    wind_blend_corners(corners, wq, &u, &v);         // wind at the PRE-step position/time
+    u += noise_u; v += noise_v;                      // WindField.get_ground_truth = forecast + noise
+  }
   BLE_STEP_TICK(3);
   // Solar geometry: 1 - sin(el_uncorrected) at substep indices 0, n/2, n in fp64, then a
   // quadratic in k evaluated in fp32 inside the loop (see sun_one_minus_sin_f64).
   const SolarNodes nodes = solar_nodes_time(e0, t0, c.lng0_deg, step_s);
   const SunQuadratic sq = solar_nodes_site(nodes, hc.sin_lat0, hc.cos_lat0, s.x, s.y, u, v, substeps);
   BLE_STEP_TICK(4);
-  // With a helper wave the block above is dead but for the wind (nothing below reads e0, nodes or sq): the helper holds this step's
-  // ephemeris already and needs the position and the wind for the three solar nodes.
-  if constexpr (H::kOn) helper->publish(s.x, s.y, u, v, s.t_elapsed);
+  // (with a helper wave the per-step constants above are dead: nothing below reads e0, nodes or sq)
   // (position and time at the START of the step, by value: the reward below calls this after s has been advanced)
   const float x_start = s.x, y_start = s.y;
   const int32_t t_start = s.t_elapsed;

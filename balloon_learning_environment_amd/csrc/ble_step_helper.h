@@ -8,7 +8,8 @@
 //   S  what does not depend on the state: the ephemeris (a step AHEAD of M), the three solar nodes, sun_at_stride for every stride and
 //      for the reward, the panel factor, the flux ramp and the attenuation's pressure-independent half -- one 16-byte SunRecord per stride.
 // S never reads anything M computes inside a step and M never waits for S inside a stride unless S is behind (stride 0 of a step at most):
-// no barrier after the prologue.  The hand-over is LDS: M publishes (x, y, u, v, t_elapsed, live lanes) once per step, S fills a ring of
+// no barrier after the prologue.  The hand-over is LDS: M publishes (x, y, u, v, t_elapsed, live lanes) once per step -- the first thing it
+// does in a step, as soon as the wind gather has landed: S computes the three site nodes while M runs its own per-step part --, S fills a ring of
 // kHelperRing records per lane; three monotonic counters per group (steps published, records ready, records taken) order it.  A write
 // is followed by s_waitcnt lgkmcnt(0) and then the counter's store; a wave's LDS operations execute in order.
 // Both loops are driven by the scalar n_steps and substeps alone; M publishes every step, also when none of its lanes is live (then S
@@ -21,7 +22,7 @@ namespace ble {
 
 constexpr int kHelperGroups = 4;                       // groups of 64 environments per workgroup: one per SIMD of a CU
 constexpr int kHelperBlock = 2 * 64 * kHelperGroups;   // M and S of every group
-constexpr int kHelperRing = 16;                        // records per lane S may be ahead of M (a power of two)
+constexpr int kHelperRing = 32;                        // records per lane S may be ahead of M (a power of two): more than the 19 of a default step
 
 struct alignas(16) HelperGroupShared {
   SunRecord ring[kHelperRing][64];
