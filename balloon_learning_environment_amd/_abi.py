@@ -93,6 +93,13 @@ class BleGpHistoryF32(ctypes.Structure):
               ('chol_stride', ctypes.c_int64)]
 
 
+class BleGpQueryF32(ctypes.Structure):
+  """struct ble_gp_query_f32: q query points per environment for ble_gp_query_f32 (device pointers)."""
+  _fields_ = [('n', ctypes.c_int64), ('q', ctypes.c_int32), ('add_forecast', ctypes.c_int32), ('xyp', ctypes.c_void_p),
+              ('time_s', ctypes.c_void_p), ('wind_grid', ctypes.c_void_p), ('grid_env_stride', ctypes.c_int64),
+              ('mean_uv', ctypes.c_void_p), ('deviation', ctypes.c_void_p)]
+
+
 class BleNoiseGen(ctypes.Structure):
   """struct ble_noise_gen: the wind-noise generator of a fused rollout (ble_step_n_f32, ABI 3)."""
   _fields_ = [('seed', ctypes.c_uint64), ('episode', ctypes.c_void_p), ('harmonic_cache', ctypes.c_void_p),

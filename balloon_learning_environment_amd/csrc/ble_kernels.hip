@@ -35,6 +35,7 @@
 #include "ble_step_split.h"
 #include "ble_step_helper.h"
 #include "ble_observe.h"
+#include "ble_gp_query.h"
 #include "ble_decode.h"
 #include "ble_agent.h"
 #include "ble_qnet.h"
@@ -1682,6 +1683,20 @@ int ble_observe_forecast_fleet_f32(const ble_state_f32* st, const ble_fleet* fle
                                    int append, float* obs, uint32_t* err_flags, int64_t n, void* stream) {
   return launch_observe<true, false>(st, fleet, wind_grid, grid_env_stride, forecast_levels, noise_uv, reset_mask, hist, append, obs, err_flags,
                                      n, stream);
+}
+
+int ble_gp_query_f32(const ble_gp_history_f32* hist, const uint8_t* reset_mask, const struct ble_gp_query_f32* query, uint32_t* err_flags,
+                     void* stream) {
+  // (the ring alone is read: the carried factor, whatever its stride, is none of this call's business)
+  if (!hist || !query || !hist->xyp || !hist->elapsed_s || !hist->err_uv || !hist->count) return BLE_E_INVALID_ARG;
+  if (!query->xyp || !query->time_s || !query->mean_uv || !query->deviation || query->n < 0 || query->q < 1 ||
+      query->n * (int64_t)query->q >= 2147483648LL || query->n >= 2147483648LL)
+    return BLE_E_INVALID_ARG;
+  if (query->add_forecast != 0 && (!query->wind_grid || query->grid_env_stride < 0)) return BLE_E_INVALID_ARG;
+  const GpHistory h{hist->xyp, hist->elapsed_s, hist->err_uv, hist->count, nullptr, nullptr, 0};
+  const GpQueryArgs a{query->n, query->q, query->add_forecast != 0 ? 1 : 0, query->xyp, query->time_s, query->wind_grid,
+                      query->grid_env_stride, query->mean_uv, query->deviation};
+  return launch(ble_gp_query_kernel, query->n, 1, kObsBlock, stream, h, reset_mask, a, err_flags);
 }
 
 }  // extern "C"

@@ -181,6 +181,11 @@ class VecBalloonArena:
     balloons' current positions."""
     return self.sim.observe(noise_uv, out=out)
 
+  def query_wind(self, xyp: torch.Tensor, time_s: Optional[torch.Tensor] = None, add_forecast: bool = True, out=None):
+    """The WindGP posterior of every env at the caller's points: xyp [N, q, 3] -> (mean_uv [N, q, 2], deviation [N, q]);
+    VecSimulator.query_wind."""
+    return self.sim.query_wind(xyp, time_s, add_forecast, out)
+
   # ---- per-env views -----------------------------------------------------------------
   def row(self, i: int) -> dict:
     """State of env i as Python scalars: ONE kernel (`ble_state_rows_f64`) and one device->host copy."""

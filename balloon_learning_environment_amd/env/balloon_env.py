@@ -211,6 +211,11 @@ class VecBalloonEnv:
     call (non-finite state, pressure out of range, WindGP window overflow, failed pressure-range search...)."""
     self.arena.sim.check_errors()
 
+  def query_wind(self, xyp, time_s=None, add_forecast: bool = True, out=None):
+    """The WindGP posterior of every environment at the caller's points -- "what wind, with what confidence, at these (x, y, p), at
+    that time?": xyp [N, q, 3] float32 device tensor -> (mean_uv [N, q, 2], deviation [N, q]); VecSimulator.query_wind."""
+    return self.arena.sim.query_wind(xyp, time_s, add_forecast, out)
+
   def _step_eager(self, actions, obs_out=None, end_mask=None):
     noise = None
     if self._wind_noise:

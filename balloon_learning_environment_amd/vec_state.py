@@ -48,6 +48,18 @@ def raise_for_flags(flags: int) -> None:
     raise OverflowError('WindGP window holds more than 120 observations (agent steps shorter than 180 s)')
 
 
+def gp_history_struct(tensors: Dict[str, torch.Tensor]) -> _abi.BleGpHistoryF32:
+  """The ble_gp_history_f32 over the given ring tensors (xyp, elapsed_s, err_uv, count; optionally chol and n_chol), which it keeps alive."""
+  h = _abi.BleGpHistoryF32()
+  for name, ct in (('xyp', ctypes.c_float), ('elapsed_s', ctypes.c_int32), ('err_uv', ctypes.c_float),
+                   ('count', ctypes.c_int32), ('chol', ctypes.c_double), ('n_chol', ctypes.c_int32)):
+    if name not in tensors:
+      continue
+    setattr(h, name, ctypes.cast(ctypes.c_void_p(tensors[name].data_ptr()), ctypes.POINTER(ct)))
+  h._tensors_keepalive = tensors
+  return h
+
+
 _on_own_device = dev.on_own_device
 
 
@@ -282,6 +294,50 @@ class VecSimulator:
     self._obs_reset.zero_()         # stream-ordered after the kernel
     return out
 
+  @_on_own_device
+  def query_wind(self, xyp: torch.Tensor, time_s: Optional[torch.Tensor] = None, add_forecast: bool = True, out=None):
+    """The WindGP posterior of every environment at the caller's points (the reference's WindGP.query_batch with one query time per
+    environment; `ble_gp_query_f32`): `xyp` [n, q, 3] float32 device tensor of (x m, y m, pressure Pa) -> (mean_uv [n, q, 2] m/s,
+    deviation [n, q] = variance / sigma^2).  time_s: int32 device tensor [n], the ONE query time of each environment in seconds elapsed
+    (past, now or future); None: every environment's current time_elapsed_s.  add_forecast: add the grid forecast at every point to the
+    mean (False: the modelled forecast ERROR alone).  out: (mean_uv, deviation) to write into.  An environment without observations --
+    none yet, or a history restart pending -- answers the forecast and deviation 0.  Reads the observation ring that observe()
+    keeps and changes nothing; asynchronous on the current stream, no host synchronisation (capturable in a HIP graph).  More than
+    120 observations inside the 6 h window, or a window that reaches observations the ring of 128 no longer holds (NaN for that
+    environment), set the flag that check_errors() raises as OverflowError."""
+    assert xyp.dtype == torch.float32 and xyp.is_contiguous() and xyp.dim() == 3 and xyp.shape[0] == self.n and xyp.shape[2] == 3, xyp.shape
+    assert xyp.device == self.device
+    q = int(xyp.shape[1])
+    if time_s is None:
+      time_s = self.state['time_elapsed_s']
+    assert time_s.dtype == torch.int32 and time_s.is_contiguous() and tuple(time_s.shape) == (self.n,) and time_s.device == self.device
+    if out is None:
+      out = (torch.empty(self.n, q, 2, dtype=torch.float32, device=self.device),
+             torch.empty(self.n, q, dtype=torch.float32, device=self.device))
+    mean_uv, deviation = out
+    assert mean_uv.dtype == torch.float32 and mean_uv.is_contiguous() and tuple(mean_uv.shape) == (self.n, q, 2)
+    assert deviation.dtype == torch.float32 and deviation.is_contiguous() and tuple(deviation.shape) == (self.n, q)
+    if add_forecast:
+      assert self.grid is not None, 'Must call set_grid (reset) before query_wind(add_forecast=True).'
+    if self._gp is not None:
+      hist, reset_mask = self._gp_struct, self._obs_reset.data_ptr()
+    else:
+      # before the first observe(): a history of zero counts (the kernel reads nothing else of it); the ring and the factor slab are
+      # observe()'s to allocate
+      if getattr(self, '_gp_empty', None) is None:
+        with torch.cuda.device(self.device):
+          self._gp_empty = gp_history_struct(dict(xyp=torch.zeros(3, dtype=torch.float32, device=self.device),
+                                                  elapsed_s=torch.zeros(1, dtype=torch.int32, device=self.device),
+                                                  err_uv=torch.zeros(2, dtype=torch.float32, device=self.device),
+                                                  count=torch.zeros(self.n, dtype=torch.int32, device=self.device)))
+      hist, reset_mask = self._gp_empty, None
+    query = _abi.BleGpQueryF32(self.n, q, 1 if add_forecast else 0, xyp.data_ptr(), time_s.data_ptr(),
+                               self.grid.data_ptr() if add_forecast else None, self.grid_env_stride if add_forecast else 0,
+                               mean_uv.data_ptr(), deviation.data_ptr())
+    _lib.check(self.lib.ble_gp_query_f32(ctypes.byref(hist), reset_mask, ctypes.byref(query), self.err_flags.data_ptr(),
+                                         dev.stream_ptr(self.device)), 'ble_gp_query_f32')
+    return mean_uv, deviation
+
 
   def _allocate_history(self, carry_factor: bool) -> None:
     """The WindGP ring of every environment (and, with carry_factor, the HBM-resident factor slab)."""
@@ -295,12 +351,7 @@ class VecSimulator:
         self._gp['chol'] = torch.zeros(self.n, _lib.GP_CHOL_STRIDE, dtype=torch.float64, device=self.device)
         self._gp['n_chol'] = torch.zeros(self.n, dtype=torch.int32, device=self.device)
       self._obs_reset = torch.zeros(self.n, dtype=torch.uint8, device=self.device)
-      self._gp_struct = _abi.BleGpHistoryF32()
-      for name, ct in (('xyp', ctypes.c_float), ('elapsed_s', ctypes.c_int32), ('err_uv', ctypes.c_float),
-                       ('count', ctypes.c_int32), ('chol', ctypes.c_double), ('n_chol', ctypes.c_int32)):
-        if name not in self._gp:
-          continue
-        setattr(self._gp_struct, name, ctypes.cast(ctypes.c_void_p(self._gp[name].data_ptr()), ctypes.POINTER(ct)))
+      self._gp_struct = gp_history_struct(self._gp)
       self._gp_struct.chol_stride = _lib.GP_CHOL_STRIDE if carry_factor else 0
 
   # ------------------------------------------------------------------ checkpoint / resume

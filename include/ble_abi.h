@@ -858,6 +858,38 @@ typedef struct ble_marco_polo_f32 {
 
 int ble_marco_polo_u8(const ble_marco_polo_f32* mp, uint8_t* action, void* stream);
 
+/*
+ * The WindGP posterior at caller-chosen points (the reference's WindGP.query_batch, env/wind_gp.py:126-241, with ONE query time per
+ * environment): q points per environment against the observation ring that ble_observe_f32 keeps.  Added without a new ABI version.
+ *
+ * Per environment e: the window holds every ring entry i < min(count, BLE_GP_CAPACITY) with |t_i - time_s[e]| < 21 600 s (strict);
+ *   K = 3.6^2 exp(-|(a - b) / (357 000 m, 357 000 m, 326 Pa, 34 560 s)|) + 0.05 I over the window, mean = K* K^-1 y (+ the grid
+ *   forecast at (x, y, p, time_s[e]) when add_forecast), deviation = max(3.6^2 - |L^-1 k*|^2, 0) / 3.6^2, all in fp64.
+ *   - an empty window, count == 0 or reset_mask[e] != 0 (a history restart is pending until the next observe): mean 0 (+ forecast),
+ *     deviation 0
+ *   - more than 120 entries in the window: the newest 120, and BLE_FLAG_GP_WINDOW (what ble_observe_f32 does)
+ *   - count > BLE_GP_CAPACITY and the oldest ring entry inside the window: observations the ring no longer holds may belong to the
+ *     window.  BLE_FLAG_GP_WINDOW, and NaN in that environment's mean_uv and deviation -- unless the window was cut to its newest 120
+ *     for a time_s[e] not earlier than the newest observation: the evicted ones, older still, would have been cut as well.
+ * The call reads `hist` (the ring and count; never chol / n_chol) and writes nothing but its outputs and err_flags.
+ * BLE_E_INVALID_ARG before any HIP call: NULL hist, query, ring pointer, xyp, time_s, mean_uv or deviation; n < 0, q < 1,
+ * n * q >= 2^31; add_forecast with a NULL grid.  n == 0: BLE_OK without a launch.  reset_mask and err_flags may be NULL.
+ */
+/* (a struct TAG only, no typedef: the entry point carries the same name, and tags live in a name space of their own) */
+struct ble_gp_query_f32 {
+  int64_t n;                 /* environments */
+  int32_t q;                 /* query points per environment, >= 1, n * q < 2^31 */
+  int32_t add_forecast;      /* 1: add the grid forecast at every point to the mean */
+  const float* xyp;          /* [n][q][3]  x m, y m, pressure Pa */
+  const int32_t* time_s;     /* [n] the ONE query time of each environment, seconds elapsed (past, now or future) */
+  const float* wind_grid;    /* required when add_forecast; else may be NULL */
+  int64_t grid_env_stride;   /* floats between the grids of consecutive environments; 0: one grid for all */
+  float* mean_uv;            /* [n][q][2] out, m/s */
+  float* deviation;          /* [n][q]    out, variance / sigma^2 as in the reference */
+};
+int ble_gp_query_f32(const ble_gp_history_f32* hist, const uint8_t* reset_mask, const struct ble_gp_query_f32* query, uint32_t* err_flags,
+                     void* stream);
+
 #ifdef __cplusplus
 }
 #endif
