@@ -100,6 +100,17 @@ class BleGpQueryF32(ctypes.Structure):
               ('mean_uv', ctypes.c_void_p), ('deviation', ctypes.c_void_p)]
 
 
+class BleRolloutF32(ctypes.Structure):
+  """struct ble_rollout_f32: K action plans per environment for ble_rollout_f32 (device pointers)."""
+  _fields_ = [('n', ctypes.c_int64), ('n_plans', ctypes.c_int32), ('n_plan_steps', ctypes.c_int32), ('action_repeat', ctypes.c_int32),
+              ('substeps', ctypes.c_int32), ('gamma', ctypes.c_double), ('plans', ctypes.c_void_p), ('wind_grid', ctypes.c_void_p),
+              ('grid_env_stride', ctypes.c_int64), ('ret', ctypes.c_void_p), ('steps_flown', ctypes.c_void_p), ('reward', ctypes.c_void_p),
+              ('final_state', ctypes.c_void_p)]
+
+
+ROLLOUT_MAX_STEPS = 960      # BLE_ROLLOUT_MAX_STEPS
+
+
 class BleNoiseGen(ctypes.Structure):
   """struct ble_noise_gen: the wind-noise generator of a fused rollout (ble_step_n_f32, ABI 3)."""
   _fields_ = [('seed', ctypes.c_uint64), ('episode', ctypes.c_void_p), ('harmonic_cache', ctypes.c_void_p),

@@ -813,6 +813,8 @@ __global__ __launch_bounds__(256) void ble_eval_accumulate_kernel(StateDev st, c
 }
 
 }  // namespace
+// ble_rollout_kernel (K action plans per environment, read-only on the state): here, after kStepBlock, StepNoiseShared and report_flags
+#include "ble_rollout.h"
 // fp64 primitive probe (test-only entry point): op 0 rcp seed, 1 d_rcp, 2 rsq seed, 3 d_rsqrt,
 // 4 d_sqrt_fast, 5 d_log_fast, 6 d_exp_fast, 7 sin (sincos_f64), 8 cos (sincos_f64)
 __global__ __launch_bounds__(256) void probe_f64_kernel(const double* x, double* y, int op, int64_t n) {
@@ -1697,6 +1699,26 @@ int ble_gp_query_f32(const ble_gp_history_f32* hist, const uint8_t* reset_mask, 
   const GpQueryArgs a{query->n, query->q, query->add_forecast != 0 ? 1 : 0, query->xyp, query->time_s, query->wind_grid,
                       query->grid_env_stride, query->mean_uv, query->deviation};
   return launch(ble_gp_query_kernel, query->n, 1, kObsBlock, stream, h, reset_mask, a, err_flags);
+}
+
+int ble_rollout_f32(const ble_state_f32* st, const struct ble_rollout_f32* ro, const ble_noise_gen* noise, uint32_t* err_flags, void* stream) {
+  if (!state_ok(st) || !ro || !ro->plans || !ro->wind_grid || !ro->ret || !ro->steps_flown) return BLE_E_INVALID_ARG;
+  if (ro->n < 0 || ro->n >= 2147483648LL || ro->n_plans < 1 || ro->n * (int64_t)ro->n_plans >= 2147483648LL || ro->n_plan_steps < 1 ||
+      ro->action_repeat < 1 || (int64_t)ro->n_plan_steps * ro->action_repeat > BLE_ROLLOUT_MAX_STEPS)
+    return BLE_E_INVALID_ARG;
+  if (ro->substeps < 1 || ro->substeps > BLE_MAX_SUBSTEPS || ro->grid_env_stride < 0 || (noise != nullptr && noise->env_offset < 0) ||
+      !(ro->gamma >= 0.0 && ro->gamma <= 1.0))                      // (a NaN gamma fails both comparisons)
+    return BLE_E_INVALID_ARG;
+  return with_vehicle<false>(st, nullptr, [&](auto veh) {
+    if (ro->n == 0) return BLE_OK;
+    const RolloutArgs a{ro->n, ro->n_plans, ro->n_plan_steps, ro->action_repeat, ro->substeps, ro->gamma, ro->plans, ro->wind_grid,
+                        ro->grid_env_stride, ro->ret, ro->steps_flown, ro->reward, ro->final_state};
+    // (the harmonic cache of `noise` is not handed on for writing: ble_rollout_kernel draws into LDS and fills no cache)
+    return with_noise(noise, [&](auto noise_on, StepNoise gen) {
+      return launch(ble_rollout_kernel<decltype(noise_on)::value, decltype(veh)>, ro->n * (int64_t)ro->n_plans, kStepBlock, kStepBlock, stream,
+                    state_dev(st), a, err_flags, gen, veh);
+    });
+  });
 }
 
 }  // extern "C"

@@ -186,6 +186,13 @@ class VecBalloonArena:
     VecSimulator.query_wind."""
     return self.sim.query_wind(xyp, time_s, add_forecast, out)
 
+  def lookahead(self, plans: torch.Tensor, gamma: float = 1.0, action_repeat: int = 1, noise_seed: Optional[int] = None,
+                want_rewards: bool = False, want_final: bool = False, out=None):
+    """K action plans per env flown from the current state without changing it: plans uint8 [H, N, K] -> Rollout(returns [N, K],
+    steps_flown [N, K], rewards or None, final or None); VecSimulator.rollout_plans.  noise_seed: None = the forecast; this arena's
+    `_seed` = the ground-truth wind its environments fly in when stepped with sim.wind_noise(_seed)."""
+    return self.sim.rollout_plans(plans, gamma, action_repeat, noise_seed, want_rewards=want_rewards, want_final=want_final, out=out)
+
   # ---- per-env views -----------------------------------------------------------------
   def row(self, i: int) -> dict:
     """State of env i as Python scalars: ONE kernel (`ble_state_rows_f64`) and one device->host copy."""

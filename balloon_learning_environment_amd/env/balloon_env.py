@@ -216,6 +216,19 @@ class VecBalloonEnv:
     that time?": xyp [N, q, 3] float32 device tensor -> (mean_uv [N, q, 2], deviation [N, q]); VecSimulator.query_wind."""
     return self.arena.sim.query_wind(xyp, time_s, add_forecast, out)
 
+  def lookahead(self, plans, gamma: float = 0.993, action_repeat: int = 1, wind: str = 'truth', want_rewards: bool = False,
+                want_final: bool = False, out=None):
+    """"From where each balloon is now, what happens under these K action sequences?": plans uint8 device tensor [H, N, K] ->
+    Rollout(returns [N, K], steps_flown [N, K], rewards or None, final or None), nothing of the environments changed
+    (VecSimulator.rollout_plans; no auto-reset inside a plan: a plan that goes terminal stops there).
+    wind='truth': the wind the environments themselves will fly -- forecast + this env's wind noise with wind_noise=True, the forecast
+    alone otherwise; what a simulator-side planner or a return estimator wants.  wind='forecast': the forecast alone, all an agent may
+    legitimately know.  Flags of the imagined flights go to arena.sim.rollout_flags, never to check_errors()."""
+    if wind not in ('truth', 'forecast'):
+      raise ValueError(f"lookahead: wind is 'truth' or 'forecast', not {wind!r}")
+    noise_seed = self.arena._seed if (wind == 'truth' and self._wind_noise) else None
+    return self.arena.lookahead(plans, gamma, action_repeat, noise_seed, want_rewards, want_final, out)
+
   def _step_eager(self, actions, obs_out=None, end_mask=None):
     noise = None
     if self._wind_noise:

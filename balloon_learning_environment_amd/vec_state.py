@@ -4,6 +4,7 @@
 (env/balloon/balloon.py:253-328) with their `Atmosphere` alphas and one shared (or
 per-env) wind grid.  It owns tensors only; all arithmetic happens in the HIP library.
 """
+import collections
 import ctypes
 from typing import Dict, Optional
 
@@ -17,6 +18,10 @@ from balloon_learning_environment_amd import device as dev
 GRID_SHAPE = (21, 21, 10, 9, 2)  # generative/vae.py:30-38 FieldShape.grid_shape()
 SUBSTEPS = 18                    # constants.AGENT_TIME_STEP (180 s) / 10 s stride
 COUNT_SLOTS = 64                 # BLE_COUNT_SLOTS in include/ble_abi.h
+
+
+# what rollout_plans returns: device tensors [n, K], [n, K], [H * action_repeat, n, K] or None, [4, n, K] or None
+Rollout = collections.namedtuple('Rollout', ('returns', 'steps_flown', 'rewards', 'final'))
 
 
 class ReferenceError_(Exception):
@@ -83,6 +88,7 @@ class VecSimulator:
       self.terminal = torch.zeros(self.n, dtype=torch.uint8, device=self.device)
       self.effective_action = torch.zeros(self.n, dtype=torch.uint8, device=self.device)
       self.err_flags = torch.zeros(1, dtype=torch.int32, device=self.device)
+      self.rollout_flags = torch.zeros(1, dtype=torch.int32, device=self.device)   # rollout_plans' own flag word: check_errors() never reads it
       self.active_slots = torch.zeros(COUNT_SLOTS, dtype=torch.int64, device=self.device)
       self.episode = torch.zeros(self.n, dtype=torch.int32, device=self.device)   # per-env episode counter
     self.grid: Optional[torch.Tensor] = None
@@ -530,6 +536,51 @@ class VecSimulator:
       if code != 0:
         _lib.check(code, fn.__name__)
     return launch
+
+  @_on_own_device
+  def rollout_plans(self, plans: torch.Tensor, gamma: float = 1.0, action_repeat: int = 1, noise_seed: Optional[int] = None,
+                    substeps: int = SUBSTEPS, want_rewards: bool = False, want_final: bool = False, out: Optional[tuple] = None) -> 'Rollout':
+    """Look ahead: flies K action plans per environment from the state where it lies, WITHOUT changing it (`ble_rollout_f32`).
+    `plans`: uint8 device tensor [H, n, K], contiguous -- entry h of plan k of environment e is flown action_repeat agent steps.  Returns
+    Rollout(returns [n, K] f32, steps_flown [n, K] i32, rewards [H * action_repeat, n, K] f32 or None, final [4, n, K] f32 or None):
+    the discounted return sum_t gamma^t r_t (fp64 sum, rounded once), the agent steps each plan flew before a terminal (0 for an
+    environment that is not OK now), with want_rewards every step's reward (0 after a terminal), with want_final (x, y, pressure,
+    battery_charge) after the last step flown.  Per step, bit for bit what step_n gives a copy of the environment.
+    noise_seed: fly in the ground-truth wind, the noise of wind_noise(noise_seed) -- keyed by the environment's own index and episode,
+    so every plan flies the noise the environment itself will fly; None: the forecast alone.
+    out: a Rollout (or tuple) of tensors to write into, None where an output is not wanted.
+    Nothing of the simulator is written: state, last_command, episode counters, both caches and the WindGP history stay as they are.
+    Error flags go to a word of their own, `rollout_flags` (int32 device tensor, OR-ed into, never cleared here), NOT to err_flags: a
+    hypothetical plan that leaves the valid range must not make check_errors() raise for a flight that never happened.
+    Asynchronous on the current stream, no host synchronisation (capturable in a HIP graph).  Not for fleets."""
+    if self.has_fleet:
+      raise ValueError('rollout_plans: a fleet (set_fleet) has no look-ahead kernel; fly one vehicle per batch (set_vehicle)')
+    assert self.grid is not None, 'Must call set_grid (reset) before rollout_plans.'
+    assert plans.dtype == torch.uint8 and plans.is_contiguous() and plans.dim() == 3 and plans.shape[1] == self.n, plans.shape
+    assert plans.device == self.device
+    h, k = int(plans.shape[0]), int(plans.shape[2])
+    steps = h * int(action_repeat)
+    if h < 1 or k < 1 or action_repeat < 1 or steps > _abi.ROLLOUT_MAX_STEPS or self.n * k >= 2 ** 31:
+      raise ValueError(f'rollout_plans: H >= 1, K >= 1, action_repeat >= 1, H * action_repeat <= {_abi.ROLLOUT_MAX_STEPS} and n * K < 2^31, '
+                       f'not H = {h}, K = {k}, action_repeat = {action_repeat}, n = {self.n}')
+    if not 0.0 <= float(gamma) <= 1.0:
+      raise ValueError(f'rollout_plans: gamma in [0, 1], not {gamma}')
+    if out is None:
+      out = (torch.empty(self.n, k, dtype=torch.float32, device=self.device), torch.empty(self.n, k, dtype=torch.int32, device=self.device),
+             torch.empty(steps, self.n, k, dtype=torch.float32, device=self.device) if want_rewards else None,
+             torch.empty(4, self.n, k, dtype=torch.float32, device=self.device) if want_final else None)
+    returns, flown, rewards, final = out
+    for t, dtype, shape in ((returns, torch.float32, (self.n, k)), (flown, torch.int32, (self.n, k)), (rewards, torch.float32, (steps, self.n, k)),
+                            (final, torch.float32, (4, self.n, k))):
+      assert t is None or (t.dtype == dtype and t.is_contiguous() and tuple(t.shape) == shape and t.device == self.device), (shape, t)
+    assert returns is not None and flown is not None
+    # (no harmonic cache: the kernel fills none, and wind_noise()'s stays byte for byte what it was)
+    gen = None if noise_seed is None else _abi.BleNoiseGen(int(noise_seed) & (2 ** 64 - 1), self.episode.data_ptr(), None, self.env_offset)
+    ro = _abi.BleRolloutF32(self.n, k, h, int(action_repeat), int(substeps), float(gamma), plans.data_ptr(), self.grid.data_ptr(),
+                            self.grid_env_stride, returns.data_ptr(), flown.data_ptr(), dev.ptr(rewards), dev.ptr(final))
+    _lib.check(self.lib.ble_rollout_f32(ctypes.byref(self._struct), ctypes.byref(ro), None if gen is None else ctypes.byref(gen),
+                                        self.rollout_flags.data_ptr(), dev.stream_ptr(self.device)), 'ble_rollout_f32')
+    return Rollout(returns, flown, rewards, final)
 
   @property
   def active_count(self) -> torch.Tensor:

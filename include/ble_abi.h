@@ -890,6 +890,49 @@ struct ble_gp_query_f32 {
 int ble_gp_query_f32(const ble_gp_history_f32* hist, const uint8_t* reset_mask, const struct ble_gp_query_f32* query, uint32_t* err_flags,
                      void* stream);
 
+/*
+ * Look ahead: K = n_plans action plans per environment, each flown for H = n_plan_steps entries x action_repeat agent steps from the
+ * state where it lies -- "from where each balloon is now, what happens under these K action sequences?".  One lane per
+ * (environment e, plan k); per agent step the semantics of ble_step_n_f32: the same lane functions on the same inputs, hence the same
+ * bits as a copy of environment e stepped with plan k's actions (tests/test_gpu_rollout.py).  A lane whose source status is not OK, or
+ * whose plan went terminal, is frozen: reward 0 from then on.  Actions are not range-checked (ble_step_f32).  Added without a new ABI
+ * version.
+ *   noise   NULL: every plan flies in the forecast.  Otherwise the ground-truth wind of ble_step_n_f32 with the same generator: the
+ *           noise field of environment e is keyed by (seed, env_offset + e, episode[e]) whatever k, so a plan flies exactly the noise
+ *           environment e itself will fly.  harmonic_cache is ignored: the call reads and fills no cache.
+ *   ret     the discounted return sum_t gamma^t r_t over the agent steps the plan flew, accumulated in fp64 in the order of t (the
+ *           product and the sum rounded separately), rounded to float once.
+ *   steps_flown  the number of agent steps entered with status OK: 0 for a non-OK source, t + 1 when step t went terminal,
+ *           H * action_repeat for a plan that survives.
+ * Window of validity: the call reads `st`, `plans` and the grid when the kernel runs (stream order) and NEVER writes the state: not the
+ * state arrays, not last_command, not episode_cache (a miss is recomputed, not stored).  It writes ret, steps_flown, the optional
+ * outputs and err_flags -- give it a flag word of its own: a hypothetical plan that leaves the valid range sets the BLE_FLAG_* of a
+ * flight that never happened (a non-finite state: BLE_FLAG_NONFINITE).  The WindGP history is not advanced.
+ * BLE_E_INVALID_ARG before any HIP call: NULL st, state array, ro, plans, wind_grid, ret or steps_flown; n < 0, n_plans < 1,
+ * n_plan_steps < 1, action_repeat < 1, n_plan_steps * action_repeat > BLE_ROLLOUT_MAX_STEPS, n * n_plans >= 2^31; substeps outside
+ * 1 .. BLE_MAX_SUBSTEPS; a negative grid_env_stride or noise->env_offset; gamma NaN or outside [0, 1]; an invalid st->vehicle.
+ * n == 0: BLE_OK without a launch.  A fleet has no form of this call.
+ */
+#define BLE_ROLLOUT_MAX_STEPS 960      /* agent steps per plan: two days of 180 s steps */
+/* (a struct TAG only, as for ble_gp_query_f32) */
+struct ble_rollout_f32 {
+  int64_t n;                 /* source environments */
+  int32_t n_plans;           /* K >= 1, n * K < 2^31 */
+  int32_t n_plan_steps;      /* H >= 1 */
+  int32_t action_repeat;     /* >= 1: every plan entry is flown this many agent steps; H * action_repeat <= BLE_ROLLOUT_MAX_STEPS */
+  int32_t substeps;          /* 1 .. BLE_MAX_SUBSTEPS */
+  double gamma;              /* finite, 0 <= gamma <= 1 */
+  const uint8_t* plans;      /* [H][n][K] */
+  const float* wind_grid;    /* as for ble_step_f32 */
+  int64_t grid_env_stride;
+  float* ret;                /* [n][K] out */
+  int32_t* steps_flown;      /* [n][K] out */
+  float* reward;             /* optional [H * action_repeat][n][K] out */
+  float* final_state;        /* optional [4][n][K] out: x, y, pressure, battery_charge after the last executed step */
+};
+int ble_rollout_f32(const ble_state_f32* st, const struct ble_rollout_f32* ro, const ble_noise_gen* noise, uint32_t* err_flags,
+                    void* stream);
+
 #ifdef __cplusplus
 }
 #endif
