@@ -109,6 +109,13 @@ class BleRolloutF32(ctypes.Structure):
 
 
 ROLLOUT_MAX_STEPS = 960      # BLE_ROLLOUT_MAX_STEPS
+GP_BELIEF_DOUBLES = 720      # BLE_GP_BELIEF_DOUBLES
+
+
+class BleGpBelief(ctypes.Structure):
+  """struct ble_gp_belief: a fitted WindGP kept on the device (ble_gp_fit_f32): the slab [n][stride] of float64 and n_obs [n] int32,
+  device pointers, and the number of environments (the sizes of the belief's calls travel in the struct)."""
+  _fields_ = [('slab', ctypes.c_void_p), ('stride', ctypes.c_int64), ('n_obs', ctypes.c_void_p), ('n', ctypes.c_int64)]
 
 
 class BleNoiseGen(ctypes.Structure):

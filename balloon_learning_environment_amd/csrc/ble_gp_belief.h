@@ -1,0 +1,410 @@
+// ble_gp_belief.h -- the wind an agent believes in: a WindGP fitted ONCE per environment and kept on the device (the belief), its
+// posterior mean as a lane function, and the look-ahead flown in forecast + that mean.  DESIGN.md 3j.
+//
+//   ble_gp_fit_kernel           one workgroup (4 waves) per environment: phases 0-2 of ble_gp_query_kernel -- the window at the anchor
+//                               time, K = L L^T, W = L^-1, alpha = K^-1 y -- and then, instead of query points, the compacted window
+//                               and alpha stored to the environment's slab in HBM.  A copy of those phases, on purpose: the query
+//                               kernel keeps its instructions (the note above ble_step_helper_kernel).
+//   gp_belief_mean              the lane function: sum_i k(loc_i, (x, y, p, t)) alpha_i for both components, fp64, i ascending, every
+//                               product an explicit d_fma, rounded to fp32 once.  No factor, no barrier: 120 kernel evaluations.
+//   ble_gp_belief_wind_kernel   one lane per environment at caller-chosen points (the shape of ble_wind_noise_kernel): what ble_step_f32
+//                               takes as noise_uv.
+//   ble_rollout_belief_kernel   ble_rollout_kernel's body (a fourth copy of the step kernel's, for the reason given there) with
+//                               gp_belief_mean in the slot of the noise term.
+//
+// The slab of an environment (kBeliefDoubles = BLE_GP_BELIEF_DOUBLES doubles, 16-byte aligned):
+//   [0, 480)     loc[120][4]: x, y, p, t of the window's observations, chronological, in units of ln2 / 32 length scales
+//                (ble_observe.h: twice the square root of the squared distance IS the exponent in units of ln2 / 64)
+//   [480, 720)   alpha[120][2]: (K^-1 y)_i of the u and of the v error, interleaved
+// Everything beyond the window is zero: a kernel evaluation against a zero row is finite and its alpha is +0.0, so the sum does not
+// change -- the trip count of the loop may be any multiple of 4 that covers n_obs, and a wave whose lanes belong to environments with
+// different windows runs ONE loop to the largest.
+//
+// The lane function and its constants build on the host as well (tests/emul/belief_emul.cpp): nothing above the kernels below uses
+// more than ble_intrinsics.h and ble_physics.h.
+#pragma once
+#include "ble_physics.h"
+
+namespace ble {
+
+constexpr int kBeliefRows = 120;                              // kGpMax
+constexpr int kBeliefAlphaAt = 4 * kBeliefRows;               // 480
+constexpr int kBeliefDoubles = kBeliefAlphaAt + 2 * kBeliefRows;      // 720: BLE_GP_BELIEF_DOUBLES
+// 32 / ln 2 over the WindGP's length scales (ble_observe.h's kGpKappa; the same expressions as ble_gp_query_kernel's)
+constexpr double kBeliefKappa = 46.16624130844683;
+constexpr double kBeliefScaleXY = kBeliefKappa / 357000.0, kBeliefScaleP = kBeliefKappa / 326.0, kBeliefScaleT = kBeliefKappa / 34560.0;
+
+// entry k of gp_exp_neg_scaled's table, s^2 2^(k / 64): 64 doubles the kernels keep in LDS
+BLE_FN double gp_belief_table_entry(int k) { return (3.6 * 3.6) * d_exp_fast((double)k * (6.93147180559945286227e-01 / 64.0)); }
+
+#if defined(__HIPCC__)
+BLE_FN double belief_fract(double x) { return __builtin_amdgcn_fract(x); }      // v_fract_f64
+#else
+BLE_FN double belief_fract(double x) { return x - floor(x); }
+#endif
+
+// s^2 exp(-|d|) from the scaled coordinate differences: two_sqrt and gp_exp_neg_scaled of ble_observe.h, every product a d_fma
+BLE_FN double gp_belief_kernel(double dx, double dy, double dp, double dt, const double* tab) {
+  const double X = d_fma(dx, dx, d_fma(dy, dy, d_fma(dp, dp, d_fma(dt, dt, 1e-300))));
+  const double y = d_rsq_seed(X);
+  const double g = X * y;
+  const double rs = g * d_fma(-g, y, 3.0);                    // 2 sqrt(X): one Newton step on the product
+  const double f = belief_fract(rs);
+  const int nn = (int)(-rs);                                  // -floor(rs)
+  const double t = tab[nn & 63];
+  const double q = d_fma(f, d_fma(f, d_fma(f, d_fma(f, 5.701900737872891e-10, -2.117286661914034e-07), 5.864904858491492e-05),
+                               -0.010830424696128488), 0.9999999999999976);
+  return d_ldexp(t * q, nn >> 6);
+}
+
+// The belief's mean forecast ERROR (u, v) [m/s] at (x, y, p, t_elapsed_s): the forecast is added where the wind is used, as the noise
+// term is.  slab: the environment's (16-byte aligned); n_obs: its window, 0 -> exactly +0.0f, < 0 -> NaN (a window the ring could not
+// tell: ble_gp_fit_kernel); n_trip: a multiple of 4, >= n_obs, <= 120 -- any such value gives the same bits (the note at the top);
+// tab: gp_belief_table_entry's 64 entries.  The window and alpha are frozen at the fit's anchor: only the query's time moves.
+BLE_FN void gp_belief_mean(const double* __restrict__ slab, int n_obs, int n_trip, float x, float y, float p, int32_t t_elapsed_s,
+                           const double* tab, float* u, float* v) {
+  const double* loc = (const double*)__builtin_assume_aligned(slab, 16);
+  const double* alpha = loc + kBeliefAlphaAt;
+  const double xq = (double)x * kBeliefScaleXY, yq = (double)y * kBeliefScaleXY, pq = (double)p * kBeliefScaleP,
+               tq = (double)t_elapsed_s * kBeliefScaleT;
+  double su = 0.0, sv = 0.0;
+#pragma unroll 1
+  for (int i0 = 0; i0 < n_trip; i0 += 4) {
+    double k[4];
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      const double* l = loc + 4 * (i0 + r);
+      k[r] = gp_belief_kernel(l[0] - xq, l[1] - yq, l[2] - pq, l[3] - tq, tab);
+    }
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {                             // (i ascending: one fixed order)
+      su = d_fma(k[r], alpha[2 * (i0 + r)], su);
+      sv = d_fma(k[r], alpha[2 * (i0 + r) + 1], sv);
+    }
+  }
+  const float fnan = __builtin_nanf("");
+  *u = n_obs < 0 ? fnan : (n_obs == 0 ? 0.0f : (float)su);
+  *v = n_obs < 0 ? fnan : (n_obs == 0 ? 0.0f : (float)sv);
+}
+
+// the loop's trip count for a window of n_obs (whatever the word holds: the slab is never overrun)
+BLE_FN int gp_belief_trip(int n_obs) {
+  const int m = n_obs < 0 ? 0 : (n_obs > kBeliefRows ? kBeliefRows : n_obs);
+  return (m + 3) & ~3;
+}
+
+}  // namespace ble
+
+#if defined(__HIPCC__)
+// ---------------------------------------------------------------------------------------------------------------- the kernels
+// Included by ble_kernels.hip after ble_rollout.h: ble_observe.h, ble_gp_query.h (GpQueryShared), kStepBlock and report_flags are there.
+namespace ble {
+
+// struct ble_gp_belief (include/ble_abi.h) as the kernels take it
+struct BeliefDev {
+  double* slab;          // [n][stride]
+  int64_t stride;        // >= kBeliefDoubles, even
+  int32_t* n_obs;        // [n]
+};
+static_assert(kBeliefRows == kGpMax && kBeliefKappa == kGpKappa, "ble_gp_belief.h and ble_observe.h disagree");
+
+// the largest trip count among the lanes of a wave (all 64 lanes call it)
+__device__ __forceinline__ int belief_wave_trip(int n_obs) {
+  int m = gp_belief_trip(n_obs);
+#pragma unroll
+  for (int d = 1; d < 64; d <<= 1) {
+    const int o = __shfl_xor(m, d);
+    m = o > m ? o : m;
+  }
+  return __builtin_amdgcn_readfirstlane(m);
+}
+
+// an environment without a posterior: a zero slab and n_obs (0, or -1: NaN)
+__device__ inline void gp_fit_empty(const BeliefDev& b, int64_t env, int tid, int n_obs) {
+  double* slab = b.slab + env * b.stride;
+  for (int q = tid; q < kBeliefDoubles; q += kObsBlock) slab[q] = 0.0;
+  if (tid == 0) b.n_obs[env] = n_obs;
+}
+
+__global__ __launch_bounds__(kObsBlock, 2) void ble_gp_fit_kernel(GpHistory hist, const uint8_t* __restrict__ reset_mask,
+                                                                 const int32_t* __restrict__ time_s, BeliefDev b, uint32_t* err_flags) {
+  __shared__ GpQueryShared sh;
+  const int64_t env = blockIdx.x;
+  const int tid = threadIdx.x, lane = tid & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  uint32_t flags = 0;
+
+  // ---- phase 0: the window at the anchor time (ble_gp_query_kernel's rules)
+  int count = hist.count[env];
+  if (reset_mask != nullptr && reset_mask[env] != 0) count = 0;       // a history restart is pending
+  const int32_t tq = time_s[env];
+  const int m = count < kGpCapacity ? count : kGpCapacity;
+  const float* h_xyp = hist.xyp + env * (kGpCapacity * 3);
+  const int32_t* h_t = hist.elapsed_s + env * kGpCapacity;
+  const float* h_err = hist.err_uv + env * (kGpCapacity * 2);
+  int32_t ta = tq, tb = tq;
+  if (lane < m) ta = h_t[(count - m + lane) % kGpCapacity];
+  if (lane + 64 < m) tb = h_t[(count - m + lane + 64) % kGpCapacity];
+  const int64_t age_a = (int64_t)ta - (int64_t)tq, age_b = (int64_t)tb - (int64_t)tq;
+  const unsigned long long b0 = __ballot(lane < m && (age_a < 0 ? -age_a : age_a) < kGpHorizonS);       // strict, like the reference
+  const unsigned long long b1 = __ballot(lane + 64 < m && (age_b < 0 ? -age_b : age_b) < kGpHorizonS);
+  int n_obs = __popcll(b0) + __popcll(b1);
+  int drop = 0;
+  if (n_obs > kGpMax) { drop = n_obs - kGpMax; n_obs = kGpMax; flags |= kFlagGpWindow; }
+  // observations the ring has evicted may belong to the window when its oldest entry does: the query kernel's NaN case
+  if (count > kGpCapacity && (b0 & 1ull) != 0) {
+    const int32_t t_newest = h_t[(count - 1) % kGpCapacity];
+    if (!(drop > 0 && tq >= t_newest)) {
+      if (tid == 0 && err_flags != nullptr) atomicOr(err_flags, (uint32_t)kFlagGpWindow);
+      gp_fit_empty(b, env, tid, -1);
+      return;
+    }
+  }
+  if (n_obs == 0) {         // (uniform over the workgroup: no barrier has been reached)
+    gp_fit_empty(b, env, tid, 0);
+    return;
+  }
+
+  // ---- compact the window into LDS (chronological), in units of the length scales; tables
+  if (wave == 2) sh.exp2_frac[lane] = kGpSigma2 * d_exp_fast((double)lane * (6.93147180559945286227e-01 / 64.0));
+  if (tid < kGpRows) {
+    sh.loc[tid][0] = 0.0; sh.loc[tid][1] = 0.0; sh.loc[tid][2] = 0.0; sh.loc[tid][3] = 0.0;
+    sh.z[0][tid] = 0.0; sh.z[1][tid] = 0.0; sh.alpha[0][tid] = 0.0; sh.alpha[1][tid] = 0.0;
+    sh.inv_diag[tid] = 0.0; sh.part[tid] = 0.0;
+  }
+  if (tid < 128) sh.W[kCholTri + tid] = 0.0;
+  __syncthreads();
+  if (wave < 2) {
+    const unsigned long long b_mine = wave == 0 ? b0 : b1;
+    const int e = tid;                                  // ring entry of this lane (waves 0 and 1: entries 0 .. 127)
+    if (((b_mine >> lane) & 1ull) != 0) {
+      const int at = __popcll(b_mine & ((1ull << lane) - 1ull)) + (wave == 1 ? __popcll(b0) : 0) - drop;
+      if (at >= 0) {
+        const int slot = (count - m + e) % kGpCapacity;
+        sh.loc[at][0] = (double)h_xyp[slot * 3] * (kGpKappa / 357000.0);
+        sh.loc[at][1] = (double)h_xyp[slot * 3 + 1] * (kGpKappa / 357000.0);
+        sh.loc[at][2] = (double)h_xyp[slot * 3 + 2] * (kGpKappa / 326.0);
+        sh.loc[at][3] = (double)h_t[slot] * (kGpKappa / 34560.0);
+        sh.z[0][at] = (double)h_err[slot * 2]; sh.z[1][at] = (double)h_err[slot * 2 + 1];
+      }
+    }
+  }
+  __syncthreads();
+
+  // ---- phase 1a: K, packed
+  const int n_tri = tri(n_obs);
+  for (int e = tid; e < n_tri; e += kObsBlock) {
+    int i = (int)((__builtin_sqrtf(8.0f * (float)e + 1.0f) - 1.0f) * 0.5f);
+    while (tri(i) > e) --i;
+    while (tri(i + 1) <= e) ++i;
+    const int j = e - tri(i);
+    const double dx = sh.loc[i][0] - sh.loc[j][0], dy = sh.loc[i][1] - sh.loc[j][1], dp = sh.loc[i][2] - sh.loc[j][2],
+                 dt = sh.loc[i][3] - sh.loc[j][3];
+    const double k = gp_exp_neg_scaled(two_sqrt(dx * dx + dy * dy + dp * dp + dt * dt + 1e-300), sh.exp2_frac);
+    sh.W[e] = i == j ? kGpSigma2 + kGpNoise2 : k;
+  }
+  __syncthreads();
+
+  // ---- phase 1b: K = L L^T, left-looking, column j per step; lane pair (i, i + 128) owns row i
+  {
+    const int i = tid & 127, h = tid >> 7;
+    double* ri = sh.W + tri(i);
+    double d_i = (i < n_obs) ? ri[i] : 1.0;
+    if (tid == 0) {
+      const double sq = __builtin_sqrt(d_i);
+      sh.inv_diag[0] = 1.0 / sq; ri[0] = sq;
+    }
+    __syncthreads();
+#pragma unroll 1
+    for (int j = 0; j + 1 < n_obs; ++j) {
+      const bool row = i > j && i < n_obs;
+      const double* rj = sh.W + tri(j);
+      const int kmid = j >> 1;
+      const int k0 = h ? kmid : 0, k1 = h ? j : kmid;
+      double s = 0.0;
+      if (row) {
+        for (int k = k0; k < k1; ++k) s = d_fma(ri[k], rj[k], s);
+        if (h) sh.part[i] = s;
+      }
+      __syncthreads();
+      if (row && !h) {
+        const double v = (ri[j] - (s + sh.part[i])) * sh.inv_diag[j];
+        ri[j] = v;
+        d_i = d_fma(-v, v, d_i);
+        if (i == j + 1) {
+          const double sq = __builtin_sqrt(d_i);
+          sh.inv_diag[i] = 1.0 / sq; ri[i] = sq;
+        }
+      }
+      __syncthreads();
+    }
+  }
+
+  // ---- phase 1c: W = L^-1 in place, row i per step; lane pair (j, j + 128) owns column j
+  {
+    const int j = tid & 127, h = tid >> 7;
+#pragma unroll 1
+    for (int i = 0; i < n_obs; ++i) {
+      const bool act = j < i;
+      const double* ri = sh.W + tri(i);
+      double s = 0.0;
+      if (act) {
+        const int kmid = (j + i + 1) >> 1;
+        const int k0 = h ? kmid : j, k1 = h ? i : kmid;
+        const double* wk = sh.W + tri(k0) + j;          // W[k][j], k = k0 ..: the next row's entry lies k + 1 further
+        for (int k = k0; k < k1; ++k) { s = d_fma(ri[k], *wk, s); wk += k + 1; }
+        if (h) sh.part[j] = s;
+      }
+      __syncthreads();
+      if (!h) {
+        if (act) sh.W[tri(i) + j] = -sh.inv_diag[i] * (s + sh.part[j]);
+        else if (j == i) sh.W[tri(i) + i] = sh.inv_diag[i];
+      }
+      __syncthreads();
+    }
+  }
+
+  // ---- phase 2: zeta = W y, alpha = W^T zeta -- component c on the lanes 128 c ..
+  {
+    const int i = tid & 127, c = tid >> 7;
+    double s = 0.0;
+    if (i < n_obs) {
+      const double* ri = sh.W + tri(i);
+      for (int k = 0; k <= i; ++k) s = d_fma(ri[k], sh.z[c][k], s);
+    }
+    __syncthreads();
+    if (i < n_obs) sh.z[c][i] = s;
+    __syncthreads();
+    if (i < n_obs) {
+      double t = 0.0;
+      const double* wk = sh.W + tri(i) + i;              // W[k][i], k = i ..
+      for (int k = i; k < n_obs; ++k) { t = d_fma(*wk, sh.z[c][k], t); wk += k + 1; }
+      sh.alpha[c][i] = t;
+    }
+    __syncthreads();
+  }
+
+  // ---- the belief: the compacted window and alpha (zero beyond the window: loc and alpha were cleared above)
+  double* slab = b.slab + env * b.stride;
+  for (int q = tid; q < kBeliefDoubles; q += kObsBlock) {
+    const int a = q - kBeliefAlphaAt;
+    slab[q] = a < 0 ? sh.loc[q >> 2][q & 3] : sh.alpha[a & 1][a >> 1];
+  }
+  if (tid == 0) b.n_obs[env] = n_obs;
+  if (tid == 0 && err_flags != nullptr && flags != 0) atomicOr(err_flags, flags);
+}
+
+constexpr int kBeliefWindBlock = 256;
+
+// the belief's mean error at one caller-chosen point per environment: uv [n][2], ble_step_f32's noise_uv
+__global__ __launch_bounds__(kBeliefWindBlock) void ble_gp_belief_wind_kernel(BeliefDev b, const float* __restrict__ x_m,
+                                                                             const float* __restrict__ y_m,
+                                                                             const float* __restrict__ pressure,
+                                                                             const int32_t* __restrict__ elapsed_s, float* __restrict__ uv,
+                                                                             int64_t n) {
+  __shared__ double tab[64];
+  if (threadIdx.x < 64) tab[threadIdx.x] = gp_belief_table_entry((int)threadIdx.x);
+  __syncthreads();
+  const int64_t e = (int64_t)blockIdx.x * kBeliefWindBlock + threadIdx.x;
+  const bool in_range = e < n;
+  const int n_obs = in_range ? b.n_obs[e] : 0;
+  const int n_trip = belief_wave_trip(n_obs);
+  if (in_range) {
+    float u, v;
+    gp_belief_mean(b.slab + e * b.stride, n_obs, n_trip, x_m[e], y_m[e], pressure[e], elapsed_s[e], tab, &u, &v);
+    uv[2 * e] = u; uv[2 * e + 1] = v;
+  }
+}
+
+// ble_rollout_kernel's body (ble_rollout.h) in forecast + the belief's mean: every lane of environment e evaluates gp_belief_mean on
+// e's slab at its own pre-step position and time.  Reads the belief, writes what ble_rollout_kernel writes.
+template <class V = VehicleDefault>
+__global__ __launch_bounds__(kStepBlock) void ble_rollout_belief_kernel(StateDev st, RolloutArgs a, BeliefDev b, uint32_t* err_flags, V veh) {
+  __shared__ double acs_poly[kAcsPolyDoubles];
+  __shared__ float term_save[kTermSaveRows * kStepBlock];
+  __shared__ double tab[64];
+  const int wave = (int)threadIdx.x >> 6, lane = (int)threadIdx.x & 63;
+  const int64_t lanes_total = a.n * (int64_t)a.n_plans;          // < 2^31 (the entry point checks)
+  const int64_t j = (int64_t)blockIdx.x * kStepBlock + threadIdx.x;
+  const bool in_range = j < lanes_total;
+  const int64_t e = in_range ? (int64_t)((uint32_t)j / (uint32_t)a.n_plans) : 0;
+  uint32_t flags = 0;
+  EnvRegs s;
+  EnvConst c;
+  EpisodeCacheRow cached = {};
+  bool live = false;
+  int n_obs = 0;
+  if (in_range) {
+    // environment e's state, every load issued up front (ble_step_kernel's loads at index e)
+    s.status = st.status[e];
+    s.x = st.x[e]; s.y = st.y[e]; s.p = st.pressure[e]; s.t_amb = st.ambient_temperature[e];
+    s.t_int = st.internal_temperature[e]; s.vol = st.envelope_volume[e]; s.sp = st.superpressure[e];
+    s.n_air = st.mols_air[e]; s.batt = st.battery_charge[e];
+    s.acs_power = 0.0f; s.mdot = 0.0f; s.charge = 0.0f; s.load = 0.0f;
+    s.t_elapsed = st.time_elapsed_s[e]; s.sunrise_h = st.sunrise_h_rel[e]; s.sunset = st.sunset_rel[e];
+    s.alt_fsm = st.alt_fsm[e]; s.env_fsm = st.env_fsm[e]; s.paused = st.power_paused[e];
+    c.lat0_deg = st.center_lat_deg[e]; c.lng0_deg = st.center_lng_deg[e];
+    c.ir = st.upwelling_infrared[e]; c.alpha = st.alpha[e]; c.start_unix = st.start_unix[e];
+    if (st.episode_cache != nullptr) cached = episode_cache_load(st.episode_cache, a.n, e);
+    n_obs = b.n_obs[e];
+    live = s.status == kOk;
+  }
+  for (int q = (int)threadIdx.x; q < kAcsPolyDoubles; q += kStepBlock) acs_poly[q] = kAcsPoly.c[q];
+  if (threadIdx.x < 64) tab[threadIdx.x] = gp_belief_table_entry((int)threadIdx.x);
+  __syncthreads();
+  EnvHoisted hc;
+  if (live) {
+    // per-episode constants: from the cache where its entry belongs to these constants; a miss recomputes and does NOT store
+    if (st.episode_cache != nullptr && episode_cache_hit(cached, c)) hc = hoisted_from_cache(cached, c);
+    else hc = hoist_constants(c);
+  }
+  const int n_trip = belief_wave_trip(n_obs);          // one loop for the wave, whatever environments its lanes belong to
+  const double* const slab = b.slab + e * b.stride;
+  const StrideK K = stride_k_vreg(veh.dry_mass, veh.lift, veh.v0);
+  const float* const grid = a.wind_grid + e * a.grid_env_stride;
+  float* const park = term_save + wave * (kTermSaveRows * kTermSaveStride) + lane;
+  // the discounted return: fp64, the product and the sum as two statements (two roundings under -ffp-contract=on), rounded to fp32 once
+  double acc = 0.0, disc = 1.0;
+  int flown = 0;
+  int64_t o = j;                                // (agent step t) * n K + j
+#pragma unroll 1
+  for (int h = 0; h < a.n_plan_steps; ++h) {
+    const int act = in_range ? (int)a.plans[(int64_t)h * lanes_total + j] : 0;
+#pragma unroll 1
+    for (int rep = 0; rep < a.action_repeat; ++rep, o += lanes_total) {
+      if (live) {
+        ++flown;
+        const WindQuery wq = wind_query(s.x, s.y, s.p, s.t_elapsed);
+        WindCorners corners;
+        wind_gather(grid, wq, &corners);
+        float nu, nv;
+        gp_belief_mean(slab, n_obs, n_trip, s.x, s.y, s.p, s.t_elapsed, tab, &nu, &nv);
+        // the belief's wind is a VALUE, as the noise is in ble_step_kernel: ble_gp_belief_wind_f32 + ble_step_f32 give the same bits
+        asm volatile("" : "+v"(nu), "+v"(nv));
+        float r;
+        agent_step(s, c, hc, act, corners, wq, nu, nv, a.substeps, acs_poly, K, park, &r, &flags, veh);
+        if (!(isfinite(s.p) && isfinite(s.t_int) && isfinite(s.x) && isfinite(s.y) && isfinite(s.batt)))
+          flags |= kFlagNonFinite;
+        if (a.reward) a.reward[o] = r;
+        const double term = disc * (double)r;
+        acc += term;
+        disc *= a.gamma;
+      } else if (in_range) {                    // a non-OK source, or a plan that went terminal: frozen, reward 0
+        if (a.reward) a.reward[o] = 0.0f;
+      }
+      live = live && s.status == kOk;
+    }
+  }
+  if (in_range) {
+    a.ret[j] = (float)acc;
+    a.steps_flown[j] = flown;
+    if (a.final_state) {
+      a.final_state[j] = s.x; a.final_state[lanes_total + j] = s.y; a.final_state[2 * lanes_total + j] = s.p;
+      a.final_state[3 * lanes_total + j] = s.batt;
+    }
+  }
+  report_flags(flags, err_flags);
+}
+
+}  // namespace ble
+#endif  // __HIPCC__

@@ -815,6 +815,8 @@ __global__ __launch_bounds__(256) void ble_eval_accumulate_kernel(StateDev st, c
 }  // namespace
 // ble_rollout_kernel (K action plans per environment, read-only on the state): here, after kStepBlock, StepNoiseShared and report_flags
 #include "ble_rollout.h"
+// the fitted WindGP kept on the device, its mean as a lane function, and the look-ahead flown in it: after ble_rollout.h (RolloutArgs)
+#include "ble_gp_belief.h"
 // fp64 primitive probe (test-only entry point): op 0 rcp seed, 1 d_rcp, 2 rsq seed, 3 d_rsqrt,
 // 4 d_sqrt_fast, 5 d_log_fast, 6 d_exp_fast, 7 sin (sincos_f64), 8 cos (sincos_f64)
 __global__ __launch_bounds__(256) void probe_f64_kernel(const double* x, double* y, int op, int64_t n) {
@@ -1079,6 +1081,17 @@ int launch_observe(const ble_state_f32* st, const ble_fleet* fleet, const float*
                   reset_mask, h, append, obs, err_flags, n, veh, forecast_levels);
   });
 }
+
+// ble_gp_belief -> the kernels' BeliefDev; false for a missing array, a slab that is not 16-byte aligned or a stride that is too short or odd
+// (a shorter slab would be overrun, an odd stride would misalign every second environment's)
+inline bool gp_belief(const ble_gp_belief* belief, BeliefDev* b) {
+  if (!belief || !belief->slab || !belief->n_obs || belief->stride < (int64_t)kBeliefDoubles || (belief->stride & 1) != 0 ||
+      (reinterpret_cast<uintptr_t>(belief->slab) & 15u) != 0 || belief->n < 0 || belief->n >= 2147483648LL)
+    return false;
+  *b = BeliefDev{belief->slab, belief->stride, belief->n_obs};
+  return true;
+}
+static_assert(kBeliefDoubles == BLE_GP_BELIEF_DOUBLES, "ble_gp_belief.h and ble_abi.h disagree on the slab");
 
 }  // namespace
 
@@ -1718,6 +1731,43 @@ int ble_rollout_f32(const ble_state_f32* st, const struct ble_rollout_f32* ro, c
       return launch(ble_rollout_kernel<decltype(noise_on)::value, decltype(veh)>, ro->n * (int64_t)ro->n_plans, kStepBlock, kStepBlock, stream,
                     state_dev(st), a, err_flags, gen, veh);
     });
+  });
+}
+
+int ble_gp_fit_f32(const ble_gp_history_f32* hist, const uint8_t* reset_mask, const int32_t* time_s, const ble_gp_belief* belief,
+                   uint32_t* err_flags, void* stream) {
+  // (the ring alone is read, as by ble_gp_query_f32; the number of environments is the belief's)
+  BeliefDev b;
+  if (!hist || !hist->xyp || !hist->elapsed_s || !hist->err_uv || !hist->count || !time_s || !gp_belief(belief, &b)) return BLE_E_INVALID_ARG;
+  const int64_t n = belief->n;
+  const GpHistory h{hist->xyp, hist->elapsed_s, hist->err_uv, hist->count, nullptr, nullptr, 0};
+  return launch(ble_gp_fit_kernel, n, 1, kObsBlock, stream, h, reset_mask, time_s, b, err_flags);
+}
+
+int ble_gp_belief_wind_f32(const ble_gp_belief* belief, const float* x_m, const float* y_m, const float* pressure, const int32_t* elapsed_s,
+                           float* uv, void* stream) {
+  BeliefDev b;
+  if (!gp_belief(belief, &b) || !x_m || !y_m || !pressure || !elapsed_s || !uv) return BLE_E_INVALID_ARG;
+  const int64_t n = belief->n;
+  return launch(ble_gp_belief_wind_kernel, n, kBeliefWindBlock, kBeliefWindBlock, stream, b, x_m, y_m, pressure, elapsed_s, uv, n);
+}
+
+int ble_rollout_belief_f32(const ble_state_f32* st, const struct ble_rollout_f32* ro, const ble_gp_belief* belief, uint32_t* err_flags,
+                           void* stream) {
+  BeliefDev b;
+  if (!state_ok(st) || !ro || !ro->plans || !ro->wind_grid || !ro->ret || !ro->steps_flown || !gp_belief(belief, &b)) return BLE_E_INVALID_ARG;
+  if (ro->n < 0 || ro->n >= 2147483648LL || ro->n_plans < 1 || ro->n * (int64_t)ro->n_plans >= 2147483648LL || ro->n_plan_steps < 1 ||
+      ro->action_repeat < 1 || (int64_t)ro->n_plan_steps * ro->action_repeat > BLE_ROLLOUT_MAX_STEPS)
+    return BLE_E_INVALID_ARG;
+  if (ro->substeps < 1 || ro->substeps > BLE_MAX_SUBSTEPS || ro->grid_env_stride < 0 || !(ro->gamma >= 0.0 && ro->gamma <= 1.0) ||
+      belief->n != ro->n)                                             // (a belief of another batch would be read out of bounds)
+    return BLE_E_INVALID_ARG;
+  return with_vehicle<false>(st, nullptr, [&](auto veh) {
+    if (ro->n == 0) return BLE_OK;
+    const RolloutArgs a{ro->n, ro->n_plans, ro->n_plan_steps, ro->action_repeat, ro->substeps, ro->gamma, ro->plans, ro->wind_grid,
+                        ro->grid_env_stride, ro->ret, ro->steps_flown, ro->reward, ro->final_state};
+    return launch(ble_rollout_belief_kernel<decltype(veh)>, ro->n * (int64_t)ro->n_plans, kStepBlock, kStepBlock, stream, state_dev(st), a, b,
+                  err_flags, veh);
   });
 }
 

@@ -187,11 +187,21 @@ class VecBalloonArena:
     return self.sim.query_wind(xyp, time_s, add_forecast, out)
 
   def lookahead(self, plans: torch.Tensor, gamma: float = 1.0, action_repeat: int = 1, noise_seed: Optional[int] = None,
-                want_rewards: bool = False, want_final: bool = False, out=None):
+                want_rewards: bool = False, want_final: bool = False, out=None, belief=None):
     """K action plans per env flown from the current state without changing it: plans uint8 [H, N, K] -> Rollout(returns [N, K],
     steps_flown [N, K], rewards or None, final or None); VecSimulator.rollout_plans.  noise_seed: None = the forecast; this arena's
-    `_seed` = the ground-truth wind its environments fly in when stepped with sim.wind_noise(_seed)."""
-    return self.sim.rollout_plans(plans, gamma, action_repeat, noise_seed, want_rewards=want_rewards, want_final=want_final, out=out)
+    `_seed` = the ground-truth wind its environments fly in when stepped with sim.wind_noise(_seed).  belief: a WindBelief
+    (fit_wind_belief) = forecast + the WindGP's mean."""
+    return self.sim.rollout_plans(plans, gamma, action_repeat, noise_seed, want_rewards=want_rewards, want_final=want_final, out=out,
+                                  belief=belief)
+
+  def fit_wind_belief(self, time_s: Optional[torch.Tensor] = None, out=None):
+    """Every env's WindGP fitted once and kept on the device: WindBelief(slab, n_obs); VecSimulator.fit_wind_belief."""
+    return self.sim.fit_wind_belief(time_s, out)
+
+  def belief_wind(self, belief, x=None, y=None, pressure=None, elapsed_s=None, out=None) -> torch.Tensor:
+    """The belief's mean forecast error at one point per env (default: where each balloon is): [N, 2]; VecSimulator.belief_wind."""
+    return self.sim.belief_wind(belief, x, y, pressure, elapsed_s, out)
 
   # ---- per-env views -----------------------------------------------------------------
   def row(self, i: int) -> dict:

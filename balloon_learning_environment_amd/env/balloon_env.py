@@ -167,6 +167,7 @@ class VecBalloonEnv:
     self._field_refresh_every, self._steps_since_refresh = int(field_refresh_every), 0
     self._noise = None
     self._graph = None
+    self._belief = None                      # lookahead(wind='belief')'s fitted WindGP: one slab, reused from call to call
     self._reseed = True               # the first reset() replays the constructor's seed
 
   def _noise_now(self):
@@ -222,10 +223,16 @@ class VecBalloonEnv:
     Rollout(returns [N, K], steps_flown [N, K], rewards or None, final or None), nothing of the environments changed
     (VecSimulator.rollout_plans; no auto-reset inside a plan: a plan that goes terminal stops there).
     wind='truth': the wind the environments themselves will fly -- forecast + this env's wind noise with wind_noise=True, the forecast
-    alone otherwise; what a simulator-side planner or a return estimator wants.  wind='forecast': the forecast alone, all an agent may
-    legitimately know.  Flags of the imagined flights go to arena.sim.rollout_flags, never to check_errors()."""
-    if wind not in ('truth', 'forecast'):
-      raise ValueError(f"lookahead: wind is 'truth' or 'forecast', not {wind!r}")
+    alone otherwise; what a simulator-side planner or a return estimator wants.  wind='forecast': the forecast alone, which ignores
+    what the balloon has measured.  wind='belief': forecast + the mean of the WindGP over the balloon's own measurements -- the wind
+    the observation is built on, all an agent may legitimately know; fitted now (arena.fit_wind_belief) and flown
+    (rollout_plans(belief=)): two launches, no host synchronisation, capturable in a HIP graph.
+    Flags of the imagined flights go to arena.sim.rollout_flags, never to check_errors()."""
+    if wind not in ('truth', 'forecast', 'belief'):
+      raise ValueError(f"lookahead: wind is 'truth', 'forecast' or 'belief', not {wind!r}")
+    if wind == 'belief':
+      self._belief = self.arena.fit_wind_belief(out=self._belief)
+      return self.arena.lookahead(plans, gamma, action_repeat, None, want_rewards, want_final, out, belief=self._belief)
     noise_seed = self.arena._seed if (wind == 'truth' and self._wind_noise) else None
     return self.arena.lookahead(plans, gamma, action_repeat, noise_seed, want_rewards, want_final, out)
 

@@ -22,6 +22,9 @@ COUNT_SLOTS = 64                 # BLE_COUNT_SLOTS in include/ble_abi.h
 
 # what rollout_plans returns: device tensors [n, K], [n, K], [H * action_repeat, n, K] or None, [4, n, K] or None
 Rollout = collections.namedtuple('Rollout', ('returns', 'steps_flown', 'rewards', 'final'))
+# what fit_wind_belief returns: the fitted WindGP of every environment, device tensors slab [n, 720] float64 (the library's own layout)
+# and n_obs [n] int32 (observations in the window; 0: no posterior, -1: a window the ring could not tell -- the belief's wind is NaN)
+WindBelief = collections.namedtuple('WindBelief', ('slab', 'n_obs'))
 
 
 class ReferenceError_(Exception):
@@ -325,18 +328,7 @@ class VecSimulator:
     assert deviation.dtype == torch.float32 and deviation.is_contiguous() and tuple(deviation.shape) == (self.n, q)
     if add_forecast:
       assert self.grid is not None, 'Must call set_grid (reset) before query_wind(add_forecast=True).'
-    if self._gp is not None:
-      hist, reset_mask = self._gp_struct, self._obs_reset.data_ptr()
-    else:
-      # before the first observe(): a history of zero counts (the kernel reads nothing else of it); the ring and the factor slab are
-      # observe()'s to allocate
-      if getattr(self, '_gp_empty', None) is None:
-        with torch.cuda.device(self.device):
-          self._gp_empty = gp_history_struct(dict(xyp=torch.zeros(3, dtype=torch.float32, device=self.device),
-                                                  elapsed_s=torch.zeros(1, dtype=torch.int32, device=self.device),
-                                                  err_uv=torch.zeros(2, dtype=torch.float32, device=self.device),
-                                                  count=torch.zeros(self.n, dtype=torch.int32, device=self.device)))
-      hist, reset_mask = self._gp_empty, None
+    hist, reset_mask = self._history_for_reading()
     query = _abi.BleGpQueryF32(self.n, q, 1 if add_forecast else 0, xyp.data_ptr(), time_s.data_ptr(),
                                self.grid.data_ptr() if add_forecast else None, self.grid_env_stride if add_forecast else 0,
                                mean_uv.data_ptr(), deviation.data_ptr())
@@ -344,6 +336,70 @@ class VecSimulator:
                                          dev.stream_ptr(self.device)), 'ble_gp_query_f32')
     return mean_uv, deviation
 
+  def _history_for_reading(self):
+    """(ble_gp_history_f32, address of the pending-restart mask or None) for a call that only reads the ring."""
+    if self._gp is not None:
+      return self._gp_struct, self._obs_reset.data_ptr()
+    # before the first observe(): a history of zero counts (the kernels read nothing else of it); the ring and the factor slab are
+    # observe()'s to allocate
+    if getattr(self, '_gp_empty', None) is None:
+      with torch.cuda.device(self.device):
+        self._gp_empty = gp_history_struct(dict(xyp=torch.zeros(3, dtype=torch.float32, device=self.device),
+                                                elapsed_s=torch.zeros(1, dtype=torch.int32, device=self.device),
+                                                err_uv=torch.zeros(2, dtype=torch.float32, device=self.device),
+                                                count=torch.zeros(self.n, dtype=torch.int32, device=self.device)))
+    return self._gp_empty, None
+
+  def _belief_struct(self, belief) -> _abi.BleGpBelief:
+    slab, n_obs = belief
+    assert slab.dtype == torch.float64 and slab.is_contiguous() and tuple(slab.shape) == (self.n, _lib.GP_BELIEF_DOUBLES), slab.shape
+    assert n_obs.dtype == torch.int32 and n_obs.is_contiguous() and tuple(n_obs.shape) == (self.n,), n_obs.shape
+    assert slab.device == self.device and n_obs.device == self.device and slab.data_ptr() % 16 == 0
+    return _abi.BleGpBelief(slab.data_ptr(), _lib.GP_BELIEF_DOUBLES, n_obs.data_ptr(), self.n)
+
+  @_on_own_device
+  def fit_wind_belief(self, time_s: Optional[torch.Tensor] = None, out: Optional[WindBelief] = None) -> WindBelief:
+    """Fits every environment's WindGP ONCE and keeps it on the device (`ble_gp_fit_f32`): WindBelief(slab [n, 720] float64,
+    n_obs [n] int32), the argument of belief_wind and rollout_plans(belief=).  time_s: int32 device tensor [n], the anchor time of each
+    environment's window in seconds elapsed; None: its current time_elapsed_s.  The window rules are query_wind's: |t_i - anchor| < 6 h;
+    more than 120 inside keeps the newest 120 and sets the flag check_errors() raises as OverflowError; no observations (none yet, or a
+    history restart pending): n_obs 0, the belief's wind is exactly 0; a window that reaches observations the ring of 128 no longer
+    holds: n_obs -1, the belief's wind is NaN, and the flag.  out: a WindBelief to write into.  The belief is a snapshot: later
+    observe() calls do not change it.  Reads the ring, changes nothing of the simulator; asynchronous, no host synchronisation."""
+    if time_s is None:
+      time_s = self.state['time_elapsed_s']
+    assert time_s.dtype == torch.int32 and time_s.is_contiguous() and tuple(time_s.shape) == (self.n,) and time_s.device == self.device
+    if out is None:
+      out = WindBelief(torch.empty(self.n, _lib.GP_BELIEF_DOUBLES, dtype=torch.float64, device=self.device),
+                       torch.empty(self.n, dtype=torch.int32, device=self.device))
+    b = self._belief_struct(out)
+    hist, reset_mask = self._history_for_reading()
+    _lib.check(self.lib.ble_gp_fit_f32(ctypes.byref(hist), reset_mask, time_s.data_ptr(), ctypes.byref(b), self.err_flags.data_ptr(),
+                                       dev.stream_ptr(self.device)), 'ble_gp_fit_f32')
+    return WindBelief(*out)
+
+  @_on_own_device
+  def belief_wind(self, belief, x: Optional[torch.Tensor] = None, y: Optional[torch.Tensor] = None, pressure: Optional[torch.Tensor] = None,
+                  elapsed_s: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The belief's mean forecast ERROR at one point per environment (`ble_gp_belief_wind_f32`): [n, 2] float32 m/s, the `noise_uv`
+    of step() -- the forecast is not added.  x, y [m], pressure [Pa]: float32 device tensors [n]; elapsed_s: int32 [n]; None: the
+    environment's own state.  The window and its weights are frozen at the belief's anchor, only the query's time moves: at the anchor
+    this is query_wind(add_forecast=False); later it is the posterior of the anchor's window, whose correction decays with the time
+    since the measurements (the belief relaxes to the forecast)."""
+    s = self.state
+    args = []
+    for t, name, dtype in ((x, 'x', torch.float32), (y, 'y', torch.float32), (pressure, 'pressure', torch.float32),
+                           (elapsed_s, 'time_elapsed_s', torch.int32)):
+      t = s[name] if t is None else t
+      assert t.dtype == dtype and t.is_contiguous() and tuple(t.shape) == (self.n,) and t.device == self.device, name
+      args.append(t.data_ptr())
+    if out is None:
+      out = torch.empty(self.n, 2, dtype=torch.float32, device=self.device)
+    assert out.dtype == torch.float32 and out.is_contiguous() and tuple(out.shape) == (self.n, 2) and out.device == self.device
+    b = self._belief_struct(belief)
+    _lib.check(self.lib.ble_gp_belief_wind_f32(ctypes.byref(b), *args, out.data_ptr(), dev.stream_ptr(self.device)),
+               'ble_gp_belief_wind_f32')
+    return out
 
   def _allocate_history(self, carry_factor: bool) -> None:
     """The WindGP ring of every environment (and, with carry_factor, the HBM-resident factor slab)."""
@@ -539,7 +595,8 @@ class VecSimulator:
 
   @_on_own_device
   def rollout_plans(self, plans: torch.Tensor, gamma: float = 1.0, action_repeat: int = 1, noise_seed: Optional[int] = None,
-                    substeps: int = SUBSTEPS, want_rewards: bool = False, want_final: bool = False, out: Optional[tuple] = None) -> 'Rollout':
+                    substeps: int = SUBSTEPS, want_rewards: bool = False, want_final: bool = False, out: Optional[tuple] = None,
+                    belief: Optional[WindBelief] = None) -> 'Rollout':
     """Look ahead: flies K action plans per environment from the state where it lies, WITHOUT changing it (`ble_rollout_f32`).
     `plans`: uint8 device tensor [H, n, K], contiguous -- entry h of plan k of environment e is flown action_repeat agent steps.  Returns
     Rollout(returns [n, K] f32, steps_flown [n, K] i32, rewards [H * action_repeat, n, K] f32 or None, final [4, n, K] f32 or None):
@@ -548,6 +605,9 @@ class VecSimulator:
     battery_charge) after the last step flown.  Per step, bit for bit what step_n gives a copy of the environment.
     noise_seed: fly in the ground-truth wind, the noise of wind_noise(noise_seed) -- keyed by the environment's own index and episode,
     so every plan flies the noise the environment itself will fly; None: the forecast alone.
+    belief: a WindBelief (fit_wind_belief): fly in the wind the agent believes, forecast + the belief's mean evaluated at every plan's
+    own position and time (`ble_rollout_belief_f32`); per step, bit for bit belief_wind at the plan's state + step(noise_uv=that).  Not
+    together with noise_seed.  An environment whose belief is NaN (n_obs -1) gets non-finite returns and FLAG_NONFINITE in rollout_flags.
     out: a Rollout (or tuple) of tensors to write into, None where an output is not wanted.
     Nothing of the simulator is written: state, last_command, episode counters, both caches and the WindGP history stay as they are.
     Error flags go to a word of their own, `rollout_flags` (int32 device tensor, OR-ed into, never cleared here), NOT to err_flags: a
@@ -555,6 +615,8 @@ class VecSimulator:
     Asynchronous on the current stream, no host synchronisation (capturable in a HIP graph).  Not for fleets."""
     if self.has_fleet:
       raise ValueError('rollout_plans: a fleet (set_fleet) has no look-ahead kernel; fly one vehicle per batch (set_vehicle)')
+    if belief is not None and noise_seed is not None:
+      raise ValueError('rollout_plans: belief and noise_seed are two winds; give one of them')
     assert self.grid is not None, 'Must call set_grid (reset) before rollout_plans.'
     assert plans.dtype == torch.uint8 and plans.is_contiguous() and plans.dim() == 3 and plans.shape[1] == self.n, plans.shape
     assert plans.device == self.device
@@ -578,6 +640,11 @@ class VecSimulator:
     gen = None if noise_seed is None else _abi.BleNoiseGen(int(noise_seed) & (2 ** 64 - 1), self.episode.data_ptr(), None, self.env_offset)
     ro = _abi.BleRolloutF32(self.n, k, h, int(action_repeat), int(substeps), float(gamma), plans.data_ptr(), self.grid.data_ptr(),
                             self.grid_env_stride, returns.data_ptr(), flown.data_ptr(), dev.ptr(rewards), dev.ptr(final))
+    if belief is not None:
+      b = self._belief_struct(belief)
+      _lib.check(self.lib.ble_rollout_belief_f32(ctypes.byref(self._struct), ctypes.byref(ro), ctypes.byref(b), self.rollout_flags.data_ptr(),
+                                                 dev.stream_ptr(self.device)), 'ble_rollout_belief_f32')
+      return Rollout(returns, flown, rewards, final)
     _lib.check(self.lib.ble_rollout_f32(ctypes.byref(self._struct), ctypes.byref(ro), None if gen is None else ctypes.byref(gen),
                                         self.rollout_flags.data_ptr(), dev.stream_ptr(self.device)), 'ble_rollout_f32')
     return Rollout(returns, flown, rewards, final)

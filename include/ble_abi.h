@@ -933,6 +933,61 @@ struct ble_rollout_f32 {
 int ble_rollout_f32(const ble_state_f32* st, const struct ble_rollout_f32* ro, const ble_noise_gen* noise, uint32_t* err_flags,
                     void* stream);
 
+/*
+ * The belief: a WindGP fitted ONCE per environment and kept on the device, so that its posterior mean can be evaluated again and again
+ * without a refit -- at caller-chosen points (ble_gp_belief_wind_f32) and inside a look-ahead (ble_rollout_belief_f32).  Added without a
+ * new ABI version.
+ *
+ * slab: BLE_GP_BELIEF_DOUBLES doubles per environment -- the window's 120 x 4 coordinates, then 2 x 120 of K^-1 y; the layout is the
+ * library's own.  Entries beyond the window are zero.  n_obs[e]: the observations in environment e's window; 0: no posterior (the mean
+ * is exactly 0); -1: the window reaches observations the ring no longer holds (the mean is NaN).
+ */
+#define BLE_GP_BELIEF_DOUBLES 720
+typedef struct ble_gp_belief {
+  double* slab;              /* device [n][stride], 16-byte aligned */
+  int64_t stride;            /* doubles between the slabs of consecutive environments: >= BLE_GP_BELIEF_DOUBLES and even */
+  int32_t* n_obs;            /* device [n] */
+  int64_t n;                 /* environments the belief holds (the sizes of these calls travel in the struct: no int64_t argument) */
+} ble_gp_belief;
+
+/*
+ * Fits the WindGP of every environment at the anchor time time_s[e] (seconds elapsed) and stores it in `belief`: the window rules of
+ * ble_gp_query_f32 -- |t_i - time_s[e]| < 21 600 s strict; more than 120 inside: the newest 120 and BLE_FLAG_GP_WINDOW; count == 0, a
+ * pending reset_mask[e] or an empty window: n_obs 0 and a zero slab; count > BLE_GP_CAPACITY with the oldest ring entry inside an uncut
+ * window: n_obs -1, a zero slab and BLE_FLAG_GP_WINDOW.  All algebra in fp64.  Reads the ring and count of `hist` (never chol / n_chol);
+ * writes the belief and err_flags, nothing else.
+ * BLE_E_INVALID_ARG before any HIP call: NULL hist, ring pointer, time_s, belief, slab or n_obs; a slab that is not 16-byte aligned, a
+ * stride below BLE_GP_BELIEF_DOUBLES or odd; belief->n < 0 or >= 2^31.  belief->n == 0: BLE_OK without a launch.  reset_mask and err_flags
+ * may be NULL.  hist, reset_mask and time_s hold belief->n environments.
+ */
+int ble_gp_fit_f32(const ble_gp_history_f32* hist, const uint8_t* reset_mask, const int32_t* time_s, const ble_gp_belief* belief,
+                   uint32_t* err_flags, void* stream);
+
+/*
+ * The belief's posterior mean of the forecast ERROR at one point per environment: uv [n][2] m/s = sum_i k(loc_i, (x, y, p, t)) alpha_i
+ * in fp64, rounded to float once -- the shape and role of ble_wind_noise_f32: what ble_step_f32 takes as noise_uv.  The forecast is NOT
+ * added.  The window and K^-1 y are those of the fit's anchor time; only the query's time moves: the mean equals the reference's
+ * WindGP.query at (x, y, p, t) whenever the reference's window at t is the anchor's window, and is the posterior of the anchor's
+ * window otherwise (its correction decays with |t - t_i| / 34 560 s: far from the measurements the belief relaxes to the forecast).
+ * n_obs 0: exactly +0.0f.  n_obs < 0: NaN.
+ * BLE_E_INVALID_ARG: NULL belief, slab, n_obs or array; a misaligned slab, a stride below BLE_GP_BELIEF_DOUBLES or odd; belief->n < 0
+ * or >= 2^31.  belief->n == 0: BLE_OK without a launch.  The arrays hold belief->n environments.
+ */
+int ble_gp_belief_wind_f32(const ble_gp_belief* belief, const float* x_m, const float* y_m, const float* pressure, const int32_t* elapsed_s,
+                           float* uv, void* stream);
+
+/*
+ * ble_rollout_f32 flown in the wind the agent believes: forecast + the belief's mean, evaluated by every lane at its own pre-step
+ * position and time (where ble_rollout_f32 with a generator evaluates the noise).  Per agent step the same bits as
+ * ble_gp_belief_wind_f32 at the lane's state followed by ble_step_f32 with that noise_uv.  `ro`, the outputs, the window of validity
+ * and the no-write rule are ble_rollout_f32's; the belief is read, never written.  An environment whose n_obs is -1 flies NaN: its
+ * returns are non-finite and BLE_FLAG_NONFINITE goes to err_flags (the call's own word).
+ * BLE_E_INVALID_ARG: everything ble_rollout_f32 refuses, and a NULL belief, slab or n_obs, a misaligned slab, a stride below
+ * BLE_GP_BELIEF_DOUBLES or odd, a belief->n other than ro->n.  n == 0: BLE_OK without a launch.  A fleet has no form of this call.
+ */
+int ble_rollout_belief_f32(const ble_state_f32* st, const struct ble_rollout_f32* ro, const ble_gp_belief* belief, uint32_t* err_flags,
+                           void* stream);
+
 #ifdef __cplusplus
 }
 #endif

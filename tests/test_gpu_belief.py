@@ -1,0 +1,476 @@
+"""The belief on the device: ble_gp_fit_f32 / ble_gp_belief_wind_f32 / ble_rollout_belief_f32 through VecSimulator.fit_wind_belief,
+belief_wind, rollout_plans(belief=) and VecBalloonEnv.lookahead(wind='belief').
+
+References.  (a) The fit and the mean: query_wind(add_forecast=False) at the anchor time, and a NumPy twin of the FROZEN window --
+alpha = cho_solve(chol(K + 0.05 I), y) over the anchor's window, mean = k*(x, y, p, t) alpha at any later t -- built from the ring's own
+float32 values read back from the device (tests/wind_gp_host.py's kernel).  The frozen window is the specification: at anchor + 6 h and
++ 12 h the reference's own window would be another.  Bar: the project's 1e-5 m/s absolute: the outputs are float32 (a mean of
+a few m/s rounds by 2.4e-7), the fp64 algebra at cond(K) ~ 3e4 contributes ~1e-11.  (b) The rollout: a copy of the source stepped H
+times with belief_wind at the copy's state as ble_step_f32's noise_uv, the belief fitted once on the source -- rewards, steps_flown and
+the final state BIT FOR BIT, the return within one float32 ulp of the float64 host sum of the rewards (the kernel's order, rounded
+once), as tests/test_gpu_rollout.py holds ble_rollout_f32 to ble_step_n_f32.
+
+Histories are written straight into the ring tensors (random positions, pressures and errors at 180 s spacing ending at the anchor)."""
+import numpy as np
+import pytest
+import scipy.linalg
+import torch
+
+import wind_gp_host
+from balloon_learning_environment_amd import _lib, device as dev, vec_state
+from balloon_learning_environment_amd.env import balloon_env
+
+pytestmark = pytest.mark.gpu
+
+TOL = 1e-5
+CAP = 128
+ROWS = 120
+FINAL_FIELDS = ('x', 'y', 'pressure', 'battery_charge')
+
+
+# ---------------------------------------------------------------------------------------------- rings and the host twin
+def _observations(rng, count, spacing, end=None):
+  """`count` observations in chronological order, the last at time `end` (default: spacing * (count - 1)):
+  (xyp [count, 3] f32, t [count] i32, err [count, 2] f32)."""
+  xyp = np.column_stack([rng.uniform(-2.0e5, 2.0e5, count), rng.uniform(-2.0e5, 2.0e5, count),
+                         rng.uniform(5000.0, 14000.0, count)]).astype(np.float32)
+  t = spacing * np.arange(count)
+  if end is not None:
+    t = t + (end - spacing * (count - 1))
+  return xyp, t.astype(np.int32), rng.normal(0.0, 2.0, (count, 2)).astype(np.float32)
+
+
+def _write_ring(sim, env, obs):
+  """Appends the observations the way ble_observe_f32 does: observation i in slot i % 128, count = their number."""
+  xyp, t, err = obs
+  count = len(t)
+  first = max(0, count - CAP)
+  slots = torch.from_numpy(np.arange(first, count) % CAP).to(sim.device)
+  sim._gp['xyp'][env, slots] = torch.from_numpy(xyp[first:]).to(sim.device)
+  sim._gp['elapsed_s'][env, slots] = torch.from_numpy(t[first:]).to(sim.device)
+  sim._gp['err_uv'][env, slots] = torch.from_numpy(err[first:]).to(sim.device)
+  sim._gp['count'][env] = count
+
+
+def _ring_back(sim, env):
+  """The ring of `env` as the device holds it, chronological: (xyp [m, 3], t [m], err [m, 2]) float64, m = min(count, 128)."""
+  count = int(sim._gp['count'][env].item())
+  m = min(count, CAP)
+  slots = (np.arange(count - m, count) % CAP)
+  g = {k: sim._gp[k][env].cpu().numpy() for k in ('xyp', 'elapsed_s', 'err_uv')}
+  return g['xyp'][slots].astype(np.float64), g['elapsed_s'][slots].astype(np.float64), g['err_uv'][slots].astype(np.float64)
+
+
+class _Twin:
+  """The posterior of the window FROZEN at `anchor`: the newest 120 ring entries with |t_i - anchor| < 6 h."""
+
+  def __init__(self, ring, anchor):
+    xyp, t, err = ring
+    keep = np.flatnonzero(np.abs(t - float(anchor)) < 6 * 3600)[-ROWS:]
+    self.n_obs = len(keep)
+    self.loc = np.column_stack([xyp[keep], t[keep]])
+    if self.n_obs:
+      k = wind_gp_host._kernel(self.loc, self.loc)
+      k[np.diag_indices_from(k)] += wind_gp_host._SIGMA_NOISE_SQUARED
+      self.alpha = scipy.linalg.cho_solve((scipy.linalg.cholesky(k, lower=True), True), err[keep])
+
+  def mean(self, points, t):
+    """points [q, 3] (float32 values), t [q] -> [q, 2] float64."""
+    points = np.asarray(points, np.float64)
+    if not self.n_obs:
+      return np.zeros((len(points), 2))
+    return wind_gp_host._kernel(np.column_stack([points, np.asarray(t, np.float64)]), self.loc) @ self.alpha
+
+
+def _points(rng, n, q):
+  return np.concatenate([rng.uniform(-2.5e5, 2.5e5, (n, q, 2)), rng.uniform(4000.0, 15000.0, (n, q, 1))], -1).astype(np.float32)
+
+
+def _sim(n):
+  sim = vec_state.VecSimulator(n, 'cuda:0')
+  sim._allocate_history(False)
+  return sim
+
+
+def _dev(a, sim, dtype=None):
+  t = torch.from_numpy(np.ascontiguousarray(a)).to(sim.device)
+  return t if dtype is None else t.to(dtype)
+
+
+def _belief_wind(sim, belief, pts, t):
+  """belief_wind at one point per environment: pts [n, 3] float32, t [n] -> [n, 2] float64 (host)."""
+  out = sim.belief_wind(belief, _dev(pts[:, 0], sim), _dev(pts[:, 1], sim), _dev(pts[:, 2], sim), _dev(np.asarray(t, np.int32), sim))
+  torch.cuda.synchronize()
+  return out.cpu().numpy().astype(np.float64)
+
+
+def _flags(sim, clear=True):
+  word = int(sim.err_flags.item())
+  if clear:
+    sim.err_flags.zero_()
+  return word
+
+
+def _close(got, want, what):
+  err = float(np.max(np.abs(got - want))) if got.size else 0.0
+  print(f'{what}: max |device - host| = {err:.3e}')
+  assert np.isfinite(got).all(), what
+  assert err <= TOL, (what, err)
+
+
+def _slab_is_zero_beyond(belief, e, m):
+  slab = belief.slab[e].cpu().numpy()
+  return not slab[4 * m:4 * ROWS].any() and not slab[4 * ROWS + 2 * m:].any()
+
+
+# ---------------------------------------------------------------------------------------------- 1. fit and mean against the host
+SIZES = (0, 1, 2, 15, 16, 17, 64, 120)
+OFFSETS = (0, 3600, 6 * 3600 - 60, 6 * 3600, 12 * 3600)
+
+
+def test_fit_and_mean_against_the_host():
+  rng = np.random.default_rng(40)
+  n, q = len(SIZES), 8
+  sim = _sim(n)
+  for e, m in enumerate(SIZES):
+    _write_ring(sim, e, _observations(rng, m, 180))
+  anchor = np.array([180 * max(m - 1, 0) for m in SIZES], np.int32)
+  sim.state['time_elapsed_s'].copy_(_dev(anchor, sim))
+  belief = sim.fit_wind_belief()                      # (time_s=None: every environment's clock)
+  pts = _points(rng, n, q)
+  queried, _ = sim.query_wind(_dev(pts, sim), add_forecast=False)
+  torch.cuda.synchronize()
+  assert _flags(sim) == 0
+  assert belief.slab.shape == (n, 720) and belief.slab.dtype == torch.float64 and belief.n_obs.dtype == torch.int32
+  assert belief.n_obs.cpu().numpy().tolist() == list(SIZES)
+  twins = [_Twin(_ring_back(sim, e), anchor[e]) for e in range(n)]
+  assert [t.n_obs for t in twins] == list(SIZES)
+  for e, m in enumerate(SIZES):
+    assert _slab_is_zero_beyond(belief, e, m), m
+    assert m == 0 or belief.slab[e, :4 * m].cpu().numpy().any()
+  queried = queried.cpu().numpy().astype(np.float64)
+  for offset in OFFSETS:
+    got = np.stack([_belief_wind(sim, belief, pts[:, j], anchor + offset) for j in range(q)], 1)          # [n, q, 2]
+    for e, m in enumerate(SIZES):
+      _close(got[e], twins[e].mean(pts[e], np.full(q, anchor[e] + offset)), f'm={m} anchor+{offset}s vs the frozen twin')
+      if offset == 0:
+        _close(got[e], queried[e], f'm={m} vs query_wind at the anchor')
+    assert not got[0].view(np.uint64).any()           # the empty window: exactly +0.0
+  # the correction decays with the time since the measurements
+  far = np.stack([_belief_wind(sim, belief, pts[:, j], anchor + 48 * 3600) for j in range(q)], 1)
+  near = np.stack([_belief_wind(sim, belief, pts[:, j], anchor) for j in range(q)], 1)
+  assert np.abs(far[7]).max() < 0.3 * np.abs(near[7]).max()
+  # the state's own point by default, and an explicit anchor equal to the clock gives the same belief
+  again = sim.fit_wind_belief(sim.state['time_elapsed_s'].clone())
+  assert torch.equal(again.slab, belief.slab) and torch.equal(again.n_obs, belief.n_obs)
+  sim.state['x'].copy_(_dev(pts[:, 0, 0], sim)); sim.state['y'].copy_(_dev(pts[:, 0, 1], sim)); sim.state['pressure'].copy_(_dev(pts[:, 0, 2], sim))
+  own = sim.belief_wind(belief)
+  torch.cuda.synchronize()
+  assert np.array_equal(own.cpu().numpy().astype(np.float64), near[:, 0])
+
+
+# ---------------------------------------------------------------------------------------------- 2. window rules
+def test_window_rules():
+  rng = np.random.default_rng(41)
+  n = 5
+  sim = _sim(n)
+  _write_ring(sim, 0, _observations(rng, 200, 180))           # wraps: observations 72 .. 199 in slots 72 .. 127, 0 .. 71
+  _write_ring(sim, 1, _observations(rng, 125, 60))            # 125 inside 6 h: the newest 120, and the flag
+  _write_ring(sim, 2, _observations(rng, 300, 180))           # asked about an hour ago: the window reaches evicted observations
+  _write_ring(sim, 3, _observations(rng, 40, 180))            # a restart is pending
+  _write_ring(sim, 4, _observations(rng, 40, 180))
+  anchor = np.array([180 * 199, 60 * 124, 180 * 299 - 3600, 180 * 39, 180 * 39], np.int32)
+  pts = _points(rng, n, 1)[:, 0]
+
+  # each rule on its own launch, so that the flag can be told apart
+  def fit(envs):
+    """The belief with only `envs` holding a history (the others' counts zeroed for the call)."""
+    count = sim._gp['count'].clone()
+    mask = torch.ones(n, dtype=torch.bool, device=sim.device)
+    mask[envs] = False
+    sim._gp['count'][mask] = 0
+    b = sim.fit_wind_belief(_dev(anchor, sim))
+    torch.cuda.synchronize()
+    sim._gp['count'].copy_(count)
+    return b
+
+  b = fit([0, 4])
+  assert _flags(sim) == 0 and b.n_obs.cpu().numpy().tolist() == [120, 0, 0, 0, 40]
+  twin = _Twin(_ring_back(sim, 0), anchor[0])
+  assert twin.n_obs == 120
+  _close(_belief_wind(sim, b, pts, anchor + 600)[0], twin.mean(pts[:1], anchor[:1] + 600)[0], 'ring wrap-around')
+
+  b = fit([1])
+  assert _flags(sim) == _lib.FLAG_GP_WINDOW and b.n_obs.cpu().numpy().tolist() == [0, 120, 0, 0, 0]
+  twin = _Twin(_ring_back(sim, 1), anchor[1])
+  _close(_belief_wind(sim, b, pts, anchor)[1], twin.mean(pts[1:2], anchor[1:2])[0], '125 inside 6 h: the newest 120')
+
+  b = fit([2, 4])
+  assert _flags(sim) == _lib.FLAG_GP_WINDOW and b.n_obs.cpu().numpy().tolist() == [0, 0, -1, 0, 40]
+  wind = _belief_wind(sim, b, pts, anchor)
+  assert np.isnan(wind[2]).all() and np.isfinite(wind[4]).all() and wind[4].any()
+  assert not b.slab[2].cpu().numpy().any()
+
+  sim.reset_observation_history(torch.tensor([0, 0, 0, 1, 0], dtype=torch.uint8, device=sim.device))
+  b = fit([3, 4])
+  assert _flags(sim) == 0 and b.n_obs.cpu().numpy().tolist() == [0, 0, 0, 0, 40]
+  wind = _belief_wind(sim, b, pts, anchor)
+  assert not wind[3].view(np.uint64).any() and not b.slab[3].cpu().numpy().any()
+  assert np.array_equal(sim._obs_reset.cpu().numpy(), [0, 0, 0, 1, 0])          # the restart stays pending: the fit only reads
+
+
+def test_before_any_observe_allocates_no_history():
+  sim = vec_state.VecSimulator(3, 'cuda:0')
+  sim.state['time_elapsed_s'].copy_(torch.tensor([0, 600, 7200], dtype=torch.int32))
+  b = sim.fit_wind_belief()
+  wind = sim.belief_wind(b)
+  torch.cuda.synchronize()
+  assert sim._gp is None and _flags(sim) == 0
+  assert b.n_obs.cpu().numpy().tolist() == [0, 0, 0] and not b.slab.cpu().numpy().any()
+  assert not wind.cpu().numpy().view(np.uint32).any()
+
+
+# ---------------------------------------------------------------------------------------------- 3. rollout == stepping a copy
+def _source(n, seed, window_sizes, per_env=False, vehicle=None, warm=4, carry_factor=False, newest_age=0):
+  """A simulator `warm` random agent steps into its episodes whose rings hold window_sizes[e] observations 180 s apart, the newest
+  `newest_age` seconds old (0: 120 of them span 21 420 s, all inside the strict 6 h window; 180: there is room for one more observe())."""
+  rng = np.random.default_rng(seed)
+  sim = vec_state.VecSimulator(n, 'cuda:0')
+  sim.set_grid(rng.uniform(-12.0, 12.0, ((n,) if per_env else ()) + vec_state.GRID_SHAPE).astype(np.float32), per_env=per_env)
+  if vehicle:
+    sim.set_vehicle(**vehicle)
+  sim.reset_device(seed)
+  a = _dev(rng.integers(0, 3, (warm, n)).astype(np.uint8), sim)
+  sim.step_n(a, torch.zeros(a.shape, dtype=torch.float32, device=sim.device), torch.zeros(a.shape, dtype=torch.uint8, device=sim.device))
+  sim.check_errors()
+  sim._allocate_history(carry_factor)
+  now = sim.state['time_elapsed_s'].cpu().numpy()
+  xy = np.stack([sim.state['x'].cpu().numpy(), sim.state['y'].cpu().numpy()], -1)
+  for e, m in enumerate(window_sizes):
+    xyp, t, err = _observations(rng, m, 180, end=int(now[e]) - newest_age)
+    xyp[:, :2] = (0.2 * xyp[:, :2] + xy[e]).astype(np.float32)          # measurements within 40 km of the balloon: a wind of m/s there
+    _write_ring(sim, e, (xyp, t, err))
+  return sim, rng
+
+
+def _reference(src, belief, plans, action_repeat):
+  """belief_wind + ble_step_f32 on a copy of the source, plan by plan: (rewards [T, n, K], steps_flown [n, K], final [4, n, K])."""
+  h, n, k_plans = plans.shape
+  steps = h * action_repeat
+  sd = src.state_dict()
+  ok = (sd['state']['status'] == 0).cpu().numpy()
+  ref = vec_state.VecSimulator(n, 'cuda:0')
+  rewards = torch.zeros(steps, n, k_plans, dtype=torch.float32, device=src.device)
+  term = torch.zeros(steps, n, k_plans, dtype=torch.uint8, device=src.device)
+  final = np.zeros((4, n, k_plans), np.float32)
+  actions = _dev(np.repeat(plans, action_repeat, axis=0), src)
+  uv = torch.zeros(n, 2, dtype=torch.float32, device=src.device)
+  for k in range(k_plans):
+    ref.load_state_dict(sd)
+    for t in range(steps):
+      ref.belief_wind(belief, out=uv)
+      r, tm = ref.step(actions[t, :, k].contiguous(), uv)
+      rewards[t, :, k] = r; term[t, :, k] = tm
+    final[:, :, k] = np.stack([ref.state[f].cpu().numpy() for f in FINAL_FIELDS])
+  term = term.cpu().numpy() != 0
+  flown = np.where(ok[:, None], np.where(term.any(0), term.argmax(0) + 1, steps), 0).astype(np.int32)
+  return rewards.cpu().numpy(), flown, final
+
+
+def _host_returns(rewards, gamma):
+  acc, disc = np.zeros(rewards.shape[1:], np.float64), 1.0
+  for t in range(rewards.shape[0]):
+    term = disc * rewards[t].astype(np.float64)
+    acc += term
+    disc *= gamma
+  return acc.astype(np.float32)
+
+
+def _bits(a):
+  return np.ascontiguousarray(a).view(np.uint32)
+
+
+# name: (n, K, H, action_repeat, window sizes, source arguments)
+CASES = {
+    'n5_k13_h6_a_wave_of_five_windows': (5, 13, 6, 1, (0, 1, 17, 120, 120), {}),
+    'n2_k64_h4_repeat_2_one_environment_per_wave': (2, 64, 4, 2, (120, 33), {}),
+    'n3_k100_h3_per_environment_grids_runtime_vehicle': (3, 100, 3, 1, (64, 120, 5),
+                                                         {'per_env': True, 'vehicle': {'payload_mass': 95.0, 'battery_capacity_wh': 2800.0}}),
+}
+
+
+@pytest.mark.parametrize('case', sorted(CASES))
+def test_rollout_equals_belief_wind_and_step_on_a_copy(case):
+  n, k, h, repeat, sizes, source = CASES[case]
+  steps, gamma = h * repeat, 0.993
+  src, rng = _source(n, 200 + sorted(CASES).index(case), sizes, **source)
+  if n == 5:
+    # environment 1: a source that is not OK flies nothing.  Environment 2: 30 000 mol of air too many in an envelope that holds ~8 000
+    # mol at its ceiling -- the superpressure is far above the 2 380 Pa limit, every plan bursts.  Environments 3, 4: at night a battery of 23 Wh runs out inside agent step 2
+    # (tests/test_gpu_rollout.py), a terminal in the middle of a plan
+    src.state['status'][1] = 1
+    src.state['mols_air'][2] += 30000.0
+    night = ((src.state['solar_charging'] == 0) & (src.state['status'] == 0)).cpu().numpy()
+    for e in (3, 4):
+      if night[e]:
+        src.state['battery_charge'][e] = 23.0
+  belief = src.fit_wind_belief()
+  torch.cuda.synchronize()
+  assert belief.n_obs.cpu().numpy().tolist() == list(sizes) and _flags(src) == 0
+  plans = rng.integers(0, 3, (h, n, k)).astype(np.uint8)
+  out = src.rollout_plans(_dev(plans, src), gamma=gamma, action_repeat=repeat, want_rewards=True, want_final=True, belief=belief)
+  rewards, flown, final = _reference(src, belief, plans, repeat)
+  torch.cuda.synchronize()
+  assert out.returns.shape == (n, k) and out.returns.dtype == torch.float32 and out.steps_flown.dtype == torch.int32
+  assert np.array_equal(out.steps_flown.cpu().numpy(), flown), case
+  bad = np.argwhere(_bits(out.rewards.cpu().numpy()) != _bits(rewards))
+  assert bad.size == 0, (case, 'rewards', bad[:4].tolist())
+  bad = np.argwhere(_bits(out.final.cpu().numpy()) != _bits(final))
+  assert bad.size == 0, (case, 'final', bad[:4].tolist())
+  want, got = _host_returns(rewards, gamma), out.returns.cpu().numpy()
+  err = np.abs(got.astype(np.float64) - want.astype(np.float64))
+  ulp = np.spacing(np.abs(want)).astype(np.float64)
+  print(f'{case}: returns max |diff| {err.max():.3e} = {np.max(err / ulp):.2f} ulp, exact in {np.mean(got == want):.3f}')
+  assert np.all(err <= ulp), (case, 'returns', float(np.max(err / ulp)))
+  # the belief is really flown: the forecast alone gives other rewards wherever there is a window
+  calm = src.rollout_plans(_dev(plans, src), gamma=gamma, action_repeat=repeat, want_rewards=True, want_final=True)
+  torch.cuda.synchronize()
+  calm_rewards, calm_final = calm.rewards.cpu().numpy(), calm.final.cpu().numpy()
+  for e, m in enumerate(sizes):
+    if m == 0:            # no posterior: exactly the forecast
+      assert np.array_equal(_bits(calm_rewards[:, e]), _bits(rewards[:, e])) and np.array_equal(_bits(calm_final[:, e]), _bits(final[:, e]))
+    elif np.all(flown[e] == steps):          # a wind of m/s over minutes: the plans end elsewhere
+      assert (_bits(calm_final[:2, e]) != _bits(final[:2, e])).any(), (case, e, m)
+  if n == 5:
+    assert np.all(flown[1] == 0) and np.all(rewards[:, 1] == 0.0) and np.all(got[1] == 0.0)
+    assert np.all((flown[2] >= 1) & (flown[2] < steps)), flown[2]          # a plan driven terminal: frozen from there
+    for p in range(k):
+      assert np.all(rewards[flown[2, p]:, 2, p] == 0.0)
+    assert np.all(flown[0] == steps)
+  else:
+    assert int(src.rollout_flags.item()) == 0
+
+
+# ---------------------------------------------------------------------------------------------- 4. no side effects
+def _tensors(d, prefix=''):
+  for key, v in d.items():
+    if isinstance(v, torch.Tensor):
+      yield prefix + str(key), v
+    elif isinstance(v, dict):
+      yield from _tensors(v, prefix + str(key) + '.')
+
+
+def _snapshot(sim, belief):
+  snap = dict(_tensors(sim.state_dict()))
+  snap.update(episode_cache=sim.episode_cache.clone(), noise_cache=sim._noise_cache.clone(), belief_slab=belief.slab.clone(),
+              belief_n_obs=belief.n_obs.clone())
+  return snap
+
+
+def test_no_side_effects_and_flags_of_its_own():
+  n, k, h = 6, 11, 4
+  src, rng = _source(n, 43, (30, 119, 60, 0, 7, 90), carry_factor=True, newest_age=180)
+  src.observe()                                      # a carried factor as well: ring, count and chol must all stay
+  src.wind_noise(9)
+  assert src._noise_cache is not None and bool((src._noise_cache != 0).any()) and 'chol' in src._gp
+  belief = src.fit_wind_belief()
+  sick = vec_state.WindBelief(belief.slab.clone(), belief.n_obs.clone())
+  sick.n_obs[2] = -1                                 # what the fit stores for a window the ring could not tell
+  torch.cuda.synchronize()
+  assert _flags(src) == 0
+  before = _snapshot(src, sick)
+  assert {'state.x', 'state.last_command', 'episode', 'err_flags', 'active_slots', 'grid', 'gp.xyp', 'gp.count', 'gp.chol'} <= set(before)
+  plans = _dev(rng.integers(0, 3, (h, n, k)).astype(np.uint8), src)
+  good = src.rollout_plans(plans, gamma=0.993, want_rewards=True, want_final=True, belief=belief)
+  torch.cuda.synchronize()
+  assert int(src.rollout_flags.item()) == 0 and bool(torch.isfinite(good.returns).all())
+  bad = src.rollout_plans(plans, gamma=0.993, want_rewards=True, want_final=True, belief=sick)
+  torch.cuda.synchronize()
+  after = _snapshot(src, sick)
+  assert sorted(before) == sorted(after)
+  for name in before:
+    assert before[name].dtype == after[name].dtype and torch.equal(before[name], after[name]), name
+  assert int(src.rollout_flags.item()) & _lib.FLAG_NONFINITE
+  assert int(src.err_flags.item()) == 0
+  src.check_errors()                                 # a flight that never happened raises nothing
+  assert not bool(torch.isfinite(bad.returns[2]).any())
+  others = [e for e in range(n) if e != 2]
+  for name, a, b in zip(good._fields, good, bad):
+    a, b = (a, b) if name in ('returns', 'steps_flown') else (a.movedim(-2, 0), b.movedim(-2, 0))
+    assert torch.equal(a[others], b[others]), name
+
+
+# ---------------------------------------------------------------------------------------------- 5. graph
+def test_graph_capture_of_fit_and_rollout():
+  n, k, h = 9, 8, 3
+  src, rng = _source(n, 44, (0, 3, 16, 40, 64, 100, 119, 120, 120), newest_age=180)
+  plans = _dev(rng.integers(0, 3, (h, n, k)).astype(np.uint8), src)
+  noise = _dev(rng.normal(0.0, 2.0, (n, 2)).astype(np.float32), src)
+
+  def eager():
+    return src.rollout_plans(plans, gamma=0.99, want_rewards=True, want_final=True, belief=src.fit_wind_belief())
+  first = eager()
+  torch.cuda.synchronize()
+  out = vec_state.Rollout(*[torch.zeros_like(t) for t in first])
+  belief = vec_state.WindBelief(torch.zeros(n, 720, dtype=torch.float64, device=src.device), torch.zeros(n, dtype=torch.int32, device=src.device))
+  graph, _ = dev.capture(src.device, lambda: src.rollout_plans(plans, gamma=0.99, want_rewards=True, want_final=True, out=out,
+                                                              belief=src.fit_wind_belief(out=belief)))
+  graph.replay()
+  torch.cuda.synchronize()
+  for name, a, b in zip(out._fields, out, first):
+    assert torch.equal(a, b), name
+  src.observe(noise, carry_factor=False)             # one more measurement: the history the graph reads has changed
+  graph.replay()
+  fresh = eager()
+  torch.cuda.synchronize()
+  assert belief.n_obs.cpu().numpy().tolist() == [1, 4, 17, 41, 65, 101, 120, 120, 120]
+  for name, a, b, c in zip(out._fields, out, fresh, first):
+    assert torch.equal(a, b), name
+    assert name == 'steps_flown' or not torch.equal(a, c), name
+  assert _flags(src) == 0
+
+
+# ---------------------------------------------------------------------------------------------- 6. VecBalloonEnv.lookahead
+def test_env_lookahead_in_the_belief():
+  n, h, k = 64, 3, 4
+  rng = np.random.default_rng(45)
+  env = balloon_env.VecBalloonEnv(n, seed=5, wind_noise=True, auto_reset=False)
+  env.reset()
+  for a in rng.integers(0, 3, (20, n)).astype(np.uint8):
+    env.step(torch.from_numpy(a).cuda())
+  env.check_errors()
+  sim = env.arena.sim
+  plans = torch.from_numpy(rng.integers(0, 3, (h, n, k)).astype(np.uint8)).cuda()
+  got = env.lookahead(plans, wind='belief', want_rewards=True, want_final=True)
+  belief = sim.fit_wind_belief()
+  want = sim.rollout_plans(plans, gamma=0.993, want_rewards=True, want_final=True, belief=belief)
+  via_arena = env.arena.lookahead(plans, 0.993, 1, None, True, True, belief=env.arena.fit_wind_belief())
+  forecast = env.lookahead(plans, wind='forecast', want_rewards=True)
+  torch.cuda.synchronize()
+  for name, a, b, c in zip(got._fields, got, want, via_arena):
+    assert torch.equal(a, b) and torch.equal(a, c), name
+  assert not torch.equal(got.rewards, forecast.rewards)
+  # The wind of the next step is evaluated exactly where the last observation was made: the belief there is nearer to the true noise
+  # than the forecast (error 0) is.  Were the belief wired to another point or time this would fail.
+  truth = sim.wind_noise(env.arena._seed).cpu().numpy().astype(np.float64)
+  believed = env.arena.belief_wind(belief).cpu().numpy().astype(np.float64)
+  live = sim.state['status'].cpu().numpy() == 0
+  miss = np.median(np.linalg.norm(believed - truth, axis=1)[live])
+  forecast_error = np.median(np.linalg.norm(truth, axis=1)[live])
+  print(f'median |belief wind - true noise| = {miss:.4f} m/s, median |true noise| = {forecast_error:.4f} m/s over {int(live.sum())} environments')
+  assert live.sum() > n // 2 and miss < forecast_error
+  env.check_errors()
+  with pytest.raises(ValueError, match='belief'):
+    env.lookahead(plans, wind='gp')
+
+
+# ---------------------------------------------------------------------------------------------- 7. refusals
+def test_a_fleet_and_two_winds_are_refused():
+  src, rng = _source(4, 46, (3, 3, 3, 3))
+  belief = src.fit_wind_belief()
+  plans = torch.zeros(2, 4, 3, dtype=torch.uint8, device=src.device)
+  with pytest.raises(ValueError, match='noise_seed'):
+    src.rollout_plans(plans, noise_seed=3, belief=belief)
+  src.set_fleet([{}, {'envelope_mass': 75.0}])
+  with pytest.raises(ValueError, match='fleet'):
+    src.rollout_plans(plans, belief=belief)
