@@ -10,14 +10,22 @@ times with belief_wind at the copy's state as ble_step_f32's noise_uv, the belie
 the final state BIT FOR BIT, the return within one float32 ulp of the float64 host sum of the rewards (the kernel's order, rounded
 once), as tests/test_gpu_rollout.py holds ble_rollout_f32 to ble_step_n_f32.
 
-Histories are written straight into the ring tensors (random positions, pressures and errors at 180 s spacing ending at the anchor)."""
+Histories are written straight into the ring tensors (random positions, pressures and errors at 180 s spacing ending at the anchor),
+except in test_a_ring_written_by_a_flight, whose ring 140 env.step() calls wrote: neighbouring observations 180 s and a few km apart
+on one trajectory, correlations near 1 -- the window a planner's belief is really built from.  Its bar is the same TOL: lambda_max(K +
+0.05 I) <= 120 x 12.96 + 0.05 and lambda_min >= 0.05, so cond <= 3.2e4 for ANY window of 120, flight-shaped or not.
+
+test_a_strided_slab goes through the documented ctypes binding (as tests/test_gpu_parity.py does): struct ble_gp_belief.stride may be
+any even value >= 720 and the Python wrapper only ever passes 720."""
+import ctypes
+
 import numpy as np
 import pytest
 import scipy.linalg
 import torch
 
 import wind_gp_host
-from balloon_learning_environment_amd import _lib, device as dev, vec_state
+from balloon_learning_environment_amd import _abi, _lib, device as dev, vec_state
 from balloon_learning_environment_amd.env import balloon_env
 
 pytestmark = pytest.mark.gpu
@@ -253,8 +261,9 @@ def _source(n, seed, window_sizes, per_env=False, vehicle=None, warm=4, carry_fa
   return sim, rng
 
 
-def _reference(src, belief, plans, action_repeat):
-  """belief_wind + ble_step_f32 on a copy of the source, plan by plan: (rewards [T, n, K], steps_flown [n, K], final [4, n, K])."""
+def _reference(src, belief, plans, action_repeat, substeps=18, want_alive=False):
+  """belief_wind + ble_step_f32 on a copy of the source, plan by plan: (rewards [T, n, K], steps_flown [n, K], final [4, n, K]); with
+  want_alive a fourth entry, alive [n, K] bool: the reference's status is OK after the last step."""
   h, n, k_plans = plans.shape
   steps = h * action_repeat
   sd = src.state_dict()
@@ -263,18 +272,20 @@ def _reference(src, belief, plans, action_repeat):
   rewards = torch.zeros(steps, n, k_plans, dtype=torch.float32, device=src.device)
   term = torch.zeros(steps, n, k_plans, dtype=torch.uint8, device=src.device)
   final = np.zeros((4, n, k_plans), np.float32)
+  alive = np.zeros((n, k_plans), bool)
   actions = _dev(np.repeat(plans, action_repeat, axis=0), src)
   uv = torch.zeros(n, 2, dtype=torch.float32, device=src.device)
   for k in range(k_plans):
     ref.load_state_dict(sd)
     for t in range(steps):
       ref.belief_wind(belief, out=uv)
-      r, tm = ref.step(actions[t, :, k].contiguous(), uv)
+      r, tm = ref.step(actions[t, :, k].contiguous(), uv, substeps=substeps)
       rewards[t, :, k] = r; term[t, :, k] = tm
     final[:, :, k] = np.stack([ref.state[f].cpu().numpy() for f in FINAL_FIELDS])
+    alive[:, k] = ref.state['status'].cpu().numpy() == 0
   term = term.cpu().numpy() != 0
   flown = np.where(ok[:, None], np.where(term.any(0), term.argmax(0) + 1, steps), 0).astype(np.int32)
-  return rewards.cpu().numpy(), flown, final
+  return (rewards.cpu().numpy(), flown, final, alive) if want_alive else (rewards.cpu().numpy(), flown, final)
 
 
 def _host_returns(rewards, gamma):
@@ -297,13 +308,24 @@ CASES = {
     'n3_k100_h3_per_environment_grids_runtime_vehicle': (3, 100, 3, 1, (64, 120, 5),
                                                          {'per_env': True, 'vehicle': {'payload_mass': 95.0, 'battery_capacity_wh': 2800.0}}),
 }
+SEEDS = {case: 200 + i for i, case in enumerate(sorted(CASES))}          # (the seeds these three have always had)
+# Step length and horizon: a seventh field, substeps.  h120_repeat_2: 6 x 11 = 66 lanes, one wave plus two; 240 agent steps are 12 h, twice
+# the GP's time scale past the anchor -- a belief evaluated at the anchor's time instead of the lane's own would fly another wind from
+# the second step on
+CASES.update({
+    'substeps_1': (3, 22, 3, 1, (0, 17, 120), {}, 1),
+    'substeps_60': (3, 22, 3, 1, (0, 17, 120), {}, 60),
+    'h120_repeat_2': (6, 11, 120, 2, (0, 1, 16, 64, 120, 120), {}, 18),
+})
+SEEDS.update(substeps_1=220, substeps_60=221, h120_repeat_2=222)
 
 
 @pytest.mark.parametrize('case', sorted(CASES))
 def test_rollout_equals_belief_wind_and_step_on_a_copy(case):
-  n, k, h, repeat, sizes, source = CASES[case]
+  n, k, h, repeat, sizes, source, *substeps = CASES[case]
+  substeps = substeps[0] if substeps else 18
   steps, gamma = h * repeat, 0.993
-  src, rng = _source(n, 200 + sorted(CASES).index(case), sizes, **source)
+  src, rng = _source(n, SEEDS[case], sizes, **source)
   if n == 5:
     # environment 1: a source that is not OK flies nothing.  Environment 2: 30 000 mol of air too many in an envelope that holds ~8 000
     # mol at its ceiling -- the superpressure is far above the 2 380 Pa limit, every plan bursts.  Environments 3, 4: at night a battery of 23 Wh runs out inside agent step 2
@@ -318,8 +340,9 @@ def test_rollout_equals_belief_wind_and_step_on_a_copy(case):
   torch.cuda.synchronize()
   assert belief.n_obs.cpu().numpy().tolist() == list(sizes) and _flags(src) == 0
   plans = rng.integers(0, 3, (h, n, k)).astype(np.uint8)
-  out = src.rollout_plans(_dev(plans, src), gamma=gamma, action_repeat=repeat, want_rewards=True, want_final=True, belief=belief)
-  rewards, flown, final = _reference(src, belief, plans, repeat)
+  out = src.rollout_plans(_dev(plans, src), gamma=gamma, action_repeat=repeat, substeps=substeps, want_rewards=True, want_final=True,
+                          belief=belief)
+  rewards, flown, final, alive = _reference(src, belief, plans, repeat, substeps, want_alive=True)
   torch.cuda.synchronize()
   assert out.returns.shape == (n, k) and out.returns.dtype == torch.float32 and out.steps_flown.dtype == torch.int32
   assert np.array_equal(out.steps_flown.cpu().numpy(), flown), case
@@ -333,7 +356,7 @@ def test_rollout_equals_belief_wind_and_step_on_a_copy(case):
   print(f'{case}: returns max |diff| {err.max():.3e} = {np.max(err / ulp):.2f} ulp, exact in {np.mean(got == want):.3f}')
   assert np.all(err <= ulp), (case, 'returns', float(np.max(err / ulp)))
   # the belief is really flown: the forecast alone gives other rewards wherever there is a window
-  calm = src.rollout_plans(_dev(plans, src), gamma=gamma, action_repeat=repeat, want_rewards=True, want_final=True)
+  calm = src.rollout_plans(_dev(plans, src), gamma=gamma, action_repeat=repeat, substeps=substeps, want_rewards=True, want_final=True)
   torch.cuda.synchronize()
   calm_rewards, calm_final = calm.rewards.cpu().numpy(), calm.final.cpu().numpy()
   for e, m in enumerate(sizes):
@@ -349,6 +372,13 @@ def test_rollout_equals_belief_wind_and_step_on_a_copy(case):
     assert np.all(flown[0] == steps)
   else:
     assert int(src.rollout_flags.item()) == 0
+  if substeps != 18:                  # the step length is really flown: 18 strides give another flight
+    other = src.rollout_plans(_dev(plans, src), gamma=gamma, action_repeat=repeat, want_rewards=True, want_final=True, belief=belief)
+    assert not torch.equal(other.final, out.final) and not torch.equal(other.rewards, out.rewards)
+  if case == 'h120_repeat_2':         # from the reference: a lane alive after all 240 steps in an environment with a window of 120
+    survivors = alive & (flown == steps)
+    print(f'{case}: plans alive after step {steps} per environment {survivors.sum(1).tolist()} of {k}')
+    assert any(survivors[e].any() for e, m in enumerate(sizes) if m == 120)
 
 
 # ---------------------------------------------------------------------------------------------- 4. no side effects
@@ -474,3 +504,140 @@ def test_a_fleet_and_two_winds_are_refused():
   src.set_fleet([{}, {'envelope_mass': 75.0}])
   with pytest.raises(ValueError, match='fleet'):
     src.rollout_plans(plans, belief=belief)
+
+
+# ---------------------------------------------------------------------------------------------- 8. a strided slab
+SENTINEL = 0x7FF8DEADBEEF0123          # a quiet NaN with a payload: no kernel computes it, and a zero does not equal it
+
+
+def _strided_belief(sim, stride):
+  """(slab [n, stride] float64 and n_obs [n] int32, both pre-filled, and their struct ble_gp_belief) for the ctypes binding."""
+  slab = torch.full((sim.n, stride), SENTINEL, dtype=torch.int64, device=sim.device).view(torch.float64)
+  n_obs = torch.full((sim.n,), -7, dtype=torch.int32, device=sim.device)
+  assert slab.data_ptr() % 16 == 0
+  return slab, n_obs, _abi.BleGpBelief(slab.data_ptr(), stride, n_obs.data_ptr(), sim.n)
+
+
+def _u64(t):
+  return t.contiguous().view(torch.int64).cpu().numpy()
+
+
+@pytest.mark.parametrize('stride', (1024, 722))
+def test_a_strided_slab(stride):
+  n, k, h = 6, 11, 3
+  sizes = (0, 1, 17, 120, 125, 300)
+  src, rng = _source(n, 47, sizes[:4] + (0, 0))
+  now = src.state['time_elapsed_s'].cpu().numpy()
+  _write_ring(src, 4, _observations(rng, 125, 60, end=int(now[4])))                    # 125 inside 6 h: the newest 120, and the flag
+  _write_ring(src, 5, _observations(rng, 300, 180, end=int(now[5]) + 3600))            # the window reaches evicted observations: -1, NaN
+  lib, stream = _lib.lib(), dev.stream_ptr(src.device)
+  flat = src.fit_wind_belief()                                                          # stride 720, through the wrapper
+  torch.cuda.synchronize()
+  assert _flags(src) == _lib.FLAG_GP_WINDOW and flat.n_obs.cpu().numpy().tolist() == [0, 1, 17, 120, 120, -1]
+
+  slab, n_obs, b = _strided_belief(src, stride)
+  hist, reset_mask = src._history_for_reading()
+  code = lib.ble_gp_fit_f32(ctypes.byref(hist), reset_mask, src.state['time_elapsed_s'].data_ptr(), ctypes.byref(b), src.err_flags.data_ptr(),
+                            stream)
+  torch.cuda.synchronize()
+  assert code == _lib.BLE_OK and _flags(src) == _lib.FLAG_GP_WINDOW
+  assert np.array_equal(_u64(slab[:, :720]), _u64(flat.slab)), 'columns [:720] are not the stride-720 fit'
+  assert torch.equal(n_obs, flat.n_obs)
+  beyond = _u64(slab[:, 720:])
+  assert beyond.shape == (n, stride - 720) and np.all(beyond == SENTINEL), np.argwhere(beyond != SENTINEL)[:4].tolist()
+  for e in (0, 5):                    # (gp_fit_empty's rows: zero up to 720, untouched from there)
+    assert not _u64(slab[e, :720]).any()
+
+  # the two readers: the bits of the contiguous belief
+  pts = _points(rng, n, 1)[:, 0]
+  at = [_dev(pts[:, j], src) for j in range(3)] + [_dev((now + 600).astype(np.int32), src)]
+  want = src.belief_wind(flat, *at)
+  got = torch.full((n, 2), 7.0, dtype=torch.float32, device=src.device)
+  code = lib.ble_gp_belief_wind_f32(ctypes.byref(b), *[t.data_ptr() for t in at], got.data_ptr(), stream)
+  torch.cuda.synchronize()
+  assert code == _lib.BLE_OK
+  assert np.array_equal(_bits(got.cpu().numpy()), _bits(want.cpu().numpy()))
+  assert np.isnan(want.cpu().numpy()[5]).all() and np.isfinite(want.cpu().numpy()[:5]).all() and not _bits(want.cpu().numpy()[0]).any()
+
+  plans = _dev(rng.integers(0, 3, (h, n, k)).astype(np.uint8), src)
+  flown_in = src.rollout_plans(plans, gamma=0.993, want_rewards=True, want_final=True, belief=flat)
+  out = vec_state.Rollout(*[torch.full_like(t, 7) for t in flown_in])
+  ro = _abi.BleRolloutF32(n, k, h, 1, 18, 0.993, plans.data_ptr(), src.grid.data_ptr(), src.grid_env_stride, out.returns.data_ptr(),
+                          out.steps_flown.data_ptr(), out.rewards.data_ptr(), out.final.data_ptr())
+  code = lib.ble_rollout_belief_f32(ctypes.byref(src._struct), ctypes.byref(ro), ctypes.byref(b), src.rollout_flags.data_ptr(), stream)
+  torch.cuda.synchronize()
+  assert code == _lib.BLE_OK
+  for name, a, c in zip(out._fields, out, flown_in):
+    assert np.array_equal(_bits(a.cpu().numpy()), _bits(c.cpu().numpy())), name
+  assert bool(torch.isfinite(out.returns[:5]).all()) and not bool(torch.isfinite(out.returns[5]).any())
+  # the readers wrote nothing either
+  assert np.all(_u64(slab[:, 720:]) == SENTINEL) and np.array_equal(_u64(slab[:, :720]), _u64(flat.slab))
+
+  # an odd stride, and one below 720: refused by all three, without a launch
+  for bad in (721, 719):
+    slab, n_obs, b = _strided_belief(src, 1024)
+    b.stride = bad
+    uv = torch.full((n, 2), 7.0, dtype=torch.float32, device=src.device)
+    ret = torch.full((n, k), 7.0, dtype=torch.float32, device=src.device)
+    ro.ret = ret.data_ptr()
+    codes = (lib.ble_gp_fit_f32(ctypes.byref(hist), reset_mask, src.state['time_elapsed_s'].data_ptr(), ctypes.byref(b),
+                                src.err_flags.data_ptr(), stream),
+             lib.ble_gp_belief_wind_f32(ctypes.byref(b), *[t.data_ptr() for t in at], uv.data_ptr(), stream),
+             lib.ble_rollout_belief_f32(ctypes.byref(src._struct), ctypes.byref(ro), ctypes.byref(b), src.rollout_flags.data_ptr(), stream))
+    torch.cuda.synchronize()
+    assert all(c < 0 for c in codes), (bad, codes)
+    assert np.all(_u64(slab) == SENTINEL) and bool((n_obs == -7).all()) and bool((uv == 7.0).all()) and bool((ret == 7.0).all())
+    assert _flags(src) == 0
+
+
+# ---------------------------------------------------------------------------------------------- 9. a ring written by a flight
+def test_a_ring_written_by_a_flight():
+  n, flight = 64, 140
+  rng = np.random.default_rng(48)
+  env = balloon_env.VecBalloonEnv(n, seed=6, wind_noise=True, auto_reset=False)
+  env.reset()                                        # (observes once: 141 observations after 140 steps, the ring of 128 has wrapped)
+  for a in rng.integers(0, 3, (flight, n)).astype(np.uint8):
+    env.step(torch.from_numpy(a).cuda())
+  env.check_errors()
+  sim = env.arena.sim
+  live = sim.state['status'].cpu().numpy() == 0
+  assert live.sum() >= n // 2, int(live.sum())
+  envs = np.flatnonzero(live)
+  # environments that ended during the flight are left out: no history for them, so that the flag word speaks of the live ones alone
+  sim._gp['count'][_dev(~live, sim)] = 0
+  anchor = sim.state['time_elapsed_s'].cpu().numpy()
+  assert np.all(anchor[live] == 180 * flight) and np.all(sim._gp['count'].cpu().numpy()[live] == flight + 1)
+  belief = sim.fit_wind_belief()
+  torch.cuda.synchronize()
+  assert _flags(sim) == 0
+  assert np.all(belief.n_obs.cpu().numpy()[live] == ROWS)
+  rings = {e: _ring_back(sim, e) for e in envs}
+  twins = {e: _Twin(rings[e], anchor[e]) for e in envs}
+  for e in envs:                                     # the window the flight wrote: 120 entries 180 s apart, the oldest ring entry outside
+    t = rings[e][1]
+    assert twins[e].n_obs == ROWS and len(t) == CAP and np.all(np.diff(t) == 180) and anchor[e] - t[0] == 22860
+
+  def compare(pts, offset, what):
+    """pts [n, q, 3] float32 at anchor + offset: the device's belief against the frozen twin (and query_wind at the anchor)."""
+    q = pts.shape[1]
+    got = np.stack([_belief_wind(sim, belief, pts[:, j], anchor + offset) for j in range(q)], 1)
+    want = np.stack([twins[e].mean(pts[e], np.full(q, anchor[e] + offset)) for e in envs])
+    _close(got[envs], want, f'{what} at anchor+{offset}s vs the frozen twin')
+    if offset == 0:
+      queried, _ = sim.query_wind(_dev(pts, sim), add_forecast=False)
+      torch.cuda.synchronize()
+      _close(got[envs], queried.cpu().numpy().astype(np.float64)[envs], f'{what} vs query_wind at the anchor')
+    return got
+
+  own = np.stack([sim.state[f].cpu().numpy() for f in ('x', 'y', 'pressure')], -1)[:, None, :]          # [n, 1, 3]
+  believed = [compare(own, offset, "the balloon's own position") for offset in (0, 180, 1800, 21600)]
+  assert np.abs(believed[0][envs]).max() > 100 * TOL    # (a correction the bar is small against, not a zero that any slab would give)
+  # 5 km and 50 Pa off the trajectory: beside its newest, its middle and its oldest window entry
+  beside = np.zeros((n, 3, 3), np.float32)
+  for e in envs:
+    beside[e] = (rings[e][0][[-1, -60, -ROWS]] + np.array([[5000.0, 0.0, 50.0], [0.0, -5000.0, -50.0], [-5000.0, 5000.0, 50.0]])).astype(np.float32)
+  for offset in (0, 1800):
+    compare(beside, offset, '5 km and 50 Pa off the trajectory')
+  far = _points(rng, n, 4)
+  for offset in (0, 1800):
+    compare(far, offset, 'far points')

@@ -10,7 +10,17 @@ the final rounding.  Parity with the fp64 oracle follows transitively: ble_step_
 this file holds the rollout to ble_step_n_f32 exactly.
 
 One reference simulator per case flies all K plans one after the other; sources are a few agent steps into a random rollout so that
-the environments differ."""
+the environments differ.
+
+Step length and horizon.  The cases named substeps_* fly agent steps of 1, 2 and 60 strides (RolloutArgs.substeps reaches agent_step in
+both kernels; a rollout that flew 18 strides whatever it was told would give other rewards than step_n(substeps=)).  The cases named
+h960 / h320 / h120 fly BLE_ROLLOUT_MAX_STEPS = 960 agent steps: the reward offset advances by n K 960 times, the discount is multiplied
+960 times, and the plans cross two sunsets, two sunrises and the 48 h end of the forecast's time axis.  Random plans alone never end a
+flight (the safety layers see to that: 300 environments x 960 steps in the fp64 oracle, at a third, a fifth and a tenth of DOWN
+actions, lost none), so the long cases give every environment that lies in the night (solar_charging == 0) a battery of 300 Wh, as
+test_terminals_freeze_a_plan_and_a_dead_source_flies_nothing gives 23 Wh: 98 minutes of the night load of 183.7 W, so those whose sun
+does not rise first run out of power at agent step 34 of 180 s (11 of 600 s), and the day's environments fly on.  The three
+conditions are asserted from the reference's own terminals (see the note above the cases)."""
 import numpy as np
 import pytest
 import torch
@@ -23,12 +33,12 @@ pytestmark = pytest.mark.gpu
 FINAL_FIELDS = ('x', 'y', 'pressure', 'battery_charge')
 
 
-def _fly(sim, actions, noise_seed):
+def _fly(sim, actions, noise_seed, substeps=18):
   """step_n over `actions` [T, n] (numpy): (rewards [T, n] f32, terminals [T, n] u8) device tensors."""
   a = torch.from_numpy(np.ascontiguousarray(actions, np.uint8)).to(sim.device)
   r = torch.zeros(a.shape, dtype=torch.float32, device=sim.device)
   t = torch.zeros(a.shape, dtype=torch.uint8, device=sim.device)
-  sim.step_n(a, r, t, noise_seed=noise_seed)
+  sim.step_n(a, r, t, substeps=substeps, noise_seed=noise_seed)
   return r, t
 
 
@@ -47,8 +57,9 @@ def _source(n, seed, env_offset=0, per_env=False, noise_seed=None, vehicle=None,
   return sim, rng
 
 
-def _reference(src, plans, action_repeat, noise_seed):
-  """ble_step_n_f32 on a copy of the source, plan by plan: (rewards [T, n, K] f32, steps_flown [n, K] i32, final [4, n, K] f32)."""
+def _reference(src, plans, action_repeat, noise_seed, substeps=18, want_alive=False):
+  """ble_step_n_f32 on a copy of the source, plan by plan: (rewards [T, n, K] f32, steps_flown [n, K] i32, final [4, n, K] f32); with
+  want_alive a fourth entry, alive [n, K] bool: the reference's status is OK after the last step."""
   h, n, k_plans = plans.shape
   steps = h * action_repeat
   sd = src.state_dict()
@@ -57,14 +68,16 @@ def _reference(src, plans, action_repeat, noise_seed):
   rewards = np.zeros((steps, n, k_plans), np.float32)
   flown = np.zeros((n, k_plans), np.int32)
   final = np.zeros((4, n, k_plans), np.float32)
+  alive = np.zeros((n, k_plans), bool)
   for k in range(k_plans):
     ref.load_state_dict(sd)
-    r, t = _fly(ref, np.repeat(plans[:, :, k], action_repeat, axis=0), noise_seed)
+    r, t = _fly(ref, np.repeat(plans[:, :, k], action_repeat, axis=0), noise_seed, substeps)
     term = t.cpu().numpy() != 0
     rewards[:, :, k] = r.cpu().numpy()
     flown[:, k] = np.where(ok, np.where(term.any(0), term.argmax(0) + 1, steps), 0)
     final[:, :, k] = np.stack([ref.state[f].cpu().numpy() for f in FINAL_FIELDS])
-  return rewards, flown, final
+    alive[:, k] = ref.state['status'].cpu().numpy() == 0
+  return (rewards, flown, final, alive) if want_alive else (rewards, flown, final)
 
 
 def _host_returns(rewards, gamma):
@@ -81,7 +94,7 @@ def _bits(a):
 
 
 def _compare(out, ref, gamma, what):
-  rewards, flown, final = ref
+  rewards, flown, final = ref[:3]
   torch.cuda.synchronize()
   got_rewards, got_final = out.rewards.cpu().numpy(), out.final.cpu().numpy()
   assert np.array_equal(out.steps_flown.cpu().numpy(), flown), what
@@ -97,10 +110,10 @@ def _compare(out, ref, gamma, what):
   assert np.all(err <= ulp), (what, 'returns', float(np.max(err / ulp)))
 
 
-def _check(src, plans, gamma, action_repeat, noise_seed, what):
+def _check(src, plans, gamma, action_repeat, noise_seed, what, substeps=18, want_alive=False):
   out = src.rollout_plans(torch.from_numpy(plans).to(src.device), gamma=gamma, action_repeat=action_repeat, noise_seed=noise_seed,
-                          want_rewards=True, want_final=True)
-  ref = _reference(src, plans, action_repeat, noise_seed)
+                          substeps=substeps, want_rewards=True, want_final=True)
+  ref = _reference(src, plans, action_repeat, noise_seed, substeps, want_alive)
   _compare(out, ref, gamma, what)
   assert out.returns.shape == plans.shape[1:] and out.returns.dtype == torch.float32 and out.steps_flown.dtype == torch.int32
   return out, ref
@@ -118,25 +131,85 @@ CASES = {
     'runtime_vehicle': (66, 3, 4, 1, 0.993, {'vehicle': {'payload_mass': 95.0, 'battery_capacity_wh': 2800.0}}, None),
     'runtime_vehicle_noise': (66, 3, 4, 1, 0.993, {'vehicle': {'payload_mass': 95.0, 'battery_capacity_wh': 2800.0}}, 5),
 }
+SEEDS = {case: 100 + i for i, case in enumerate(sorted(CASES))}          # (the seeds these nine have always had)
+
+# Step length and horizon: an eighth field of extras -- substeps (default 18), seed, and low_battery (the long cases: the environments in
+# the night get LOW_BATTERY_WH; see the docstring).
+# substeps_*: 70 x 3 = 210 lanes, a block boundary inside an environment's plans; 60 strides is where the solar band widens (sun_band).
+# h960 / h320 / h120: 960 agent steps.  22 x 3 = 66 lanes: one wave plus two lanes.  h960: 40 warm steps, so the last 40 of the 960 lie
+# beyond the forecast's 48 h; gamma^960 = 1.2e-3, every term still counts.  h320: the sum carries no decay.  h120: 960 steps of 10
+# minutes, 160 h.  The seeds' own counts (plans that fly all 960 steps / end at a step strictly inside (1, 959) / are alive after step
+# 960) are printed by every run of a long case; NOT YET RECORDED HERE: no MI355X run of these cases exists.  What the fp64 oracle gives
+# for 1 200 host-sampled initial states under the same treatment (a third of the actions DOWN): 48 % lie in the night; of those 85 - 88 %
+# end, all at agent step 34 or 35 of 180 s (11 of 600 s), the others see the sun first and survive; every environment of the day is alive
+# after 960 steps.  Groups of 22 drawn from them miss a condition in 0 - 1 of 20 000 draws, groups of 8 in 1.5 % (no or only night
+# environments, or every night one saved by the sunrise); a seed that does is replaced, the condition is not.
+_VEHICLE = {'vehicle': {'payload_mass': 95.0, 'battery_capacity_wh': 2800.0}}
+CASES.update({
+    'substeps_1': (70, 3, 3, 1, 0.993, {}, None, {'substeps': 1, 'seed': 120}),
+    'substeps_2': (70, 3, 3, 1, 0.993, {}, None, {'substeps': 2, 'seed': 121}),
+    'substeps_60': (70, 3, 3, 1, 0.993, {}, None, {'substeps': 60, 'seed': 122}),
+    'substeps_1_noise': (70, 3, 3, 1, 0.993, {}, 21, {'substeps': 1, 'seed': 123}),
+    'substeps_60_noise': (70, 3, 3, 1, 0.993, {}, 22, {'substeps': 60, 'seed': 124}),
+    'substeps_60_runtime_vehicle': (66, 3, 2, 1, 0.993, _VEHICLE, None, {'substeps': 60, 'seed': 125}),
+    'h960_full_horizon': (22, 3, 960, 1, 0.993, {'warm': 40}, None, {'seed': 140, 'low_battery': True}),
+    'h320_repeat_3': (22, 3, 320, 3, 1.0, {}, None, {'seed': 141, 'low_battery': True}),
+    'h320_repeat_3_noise': (22, 3, 320, 3, 1.0, {}, 33, {'seed': 142, 'low_battery': True}),
+    'h120_repeat_8_substeps_60': (8, 9, 120, 8, 1.0, {}, None, {'substeps': 60, 'seed': 143, 'low_battery': True}),
+})
+LOW_BATTERY_WH = 300.0
+MAX_STEPS = 960
 
 
-@pytest.mark.parametrize('case', sorted(CASES))
-def test_rollout_equals_step_n_on_a_copy(case):
-  n, k, h, repeat, gamma, source, noise_seed = CASES[case]
-  src, rng = _source(n, 100 + sorted(CASES).index(case), noise_seed=noise_seed, **source)
+def _long_counts(flown, alive, case, seed):
+  """The three counts the long cases' conditions are about, from the reference's terminals and final status."""
+  full, inside = flown == MAX_STEPS, (flown > 2) & (flown < MAX_STEPS - 1)          # (the terminal's step index is flown - 1)
+  counts = int(full.sum()), int(inside.sum()), int((alive & full).sum())
+  print(f'{case} seed {seed}: of {flown.size} plans {counts[0]} fly all {MAX_STEPS} steps, {counts[1]} end at a step inside (1, {MAX_STEPS - 1}), '
+        f'{counts[2]} are alive after step {MAX_STEPS}; steps flown by those that end {sorted(set(flown[~full].tolist()))}')
+  return counts
+
+
+def _run_case(case, seed=None):
+  """One of CASES, flown and checked; the long cases return their three counts.  seed: another source than the case's own (a seed scan)."""
+  n, k, h, repeat, gamma, source, noise_seed, *extras = CASES[case]
+  extras = extras[0] if extras else {}
+  substeps = extras.get('substeps', 18)
+  seed = extras.get('seed', SEEDS.get(case)) if seed is None else seed
+  src, rng = _source(n, seed, noise_seed=noise_seed, **source)
   if source.get('advance_episodes'):
     assert set(src.episode.cpu().numpy().tolist()) == {1, 2}
   if source.get('per_env'):
     assert src.grid_env_stride != 0
+  if extras.get('low_battery'):
+    src.state['battery_charge'][(src.state['solar_charging'] == 0) & (src.state['status'] == 0)] = LOW_BATTERY_WH
   plans = rng.integers(0, 3, (h, n, k)).astype(np.uint8)
-  out, _ = _check(src, plans, gamma, repeat, noise_seed, case)
+  out, ref = _check(src, plans, gamma, repeat, noise_seed, case, substeps, want_alive=True)
   assert int(src.rollout_flags.item()) == 0
   if noise_seed is not None:          # the noise is really flown: the forecast alone gives other rewards
-    calm = src.rollout_plans(torch.from_numpy(plans).to(src.device), gamma=gamma, action_repeat=repeat, want_rewards=True)
+    calm = src.rollout_plans(torch.from_numpy(plans).to(src.device), gamma=gamma, action_repeat=repeat, substeps=substeps, want_rewards=True)
     assert not torch.equal(calm.rewards, out.rewards)
   else:
-    bare = src.rollout_plans(torch.from_numpy(plans).to(src.device), gamma=gamma, action_repeat=repeat)
+    bare = src.rollout_plans(torch.from_numpy(plans).to(src.device), gamma=gamma, action_repeat=repeat, substeps=substeps)
     assert bare.rewards is None and bare.final is None and torch.equal(bare.returns, out.returns)
+  if substeps != 18:                  # the step length is really flown: 18 strides give another flight
+    other = src.rollout_plans(torch.from_numpy(plans).to(src.device), gamma=gamma, action_repeat=repeat, noise_seed=noise_seed,
+                              want_rewards=True, want_final=True)
+    assert not torch.equal(other.final, out.final) and not torch.equal(other.rewards, out.rewards)
+  if h * repeat == MAX_STEPS:         # the long cases' conditions, from the reference's own terminals and state, never from the rollout
+    rewards, flown, _, alive = ref
+    full, inside, survivors = _long_counts(flown, alive, case, seed)
+    assert full >= 1, 'no plan flies all 960 steps'
+    assert inside >= 1, 'no reference terminal at a step strictly inside (1, 959)'
+    assert survivors >= 1, 'no survivor of 960 steps: no live lane crossed sunset, sunrise and the 48 h end of the forecast'
+    e, p = np.argwhere(flown < MAX_STEPS)[0]
+    assert np.all(rewards[flown[e, p]:, e, p] == 0.0) and rewards[flown[e, p] - 1, e, p] != 0.0
+    return full, inside, survivors
+
+
+@pytest.mark.parametrize('case', sorted(CASES))
+def test_rollout_equals_step_n_on_a_copy(case):
+  _run_case(case)
 
 
 def test_terminals_freeze_a_plan_and_a_dead_source_flies_nothing():
@@ -246,6 +319,15 @@ def test_env_lookahead_predicts_the_rewards_step_returns():
   calm.reset()
   a, b = calm.lookahead(plans, want_rewards=True), calm.lookahead(plans, wind='forecast', want_rewards=True)
   assert torch.equal(a.rewards, b.rewards)          # without wind noise the truth IS the forecast
+
+
+def test_more_than_960_steps_are_refused():
+  src, rng = _source(2, 72)
+  for h, repeat in ((961, 1), (481, 2)):
+    with pytest.raises(ValueError, match='960'):
+      src.rollout_plans(torch.zeros(h, 2, 1, dtype=torch.uint8, device=src.device), action_repeat=repeat)
+  src.rollout_plans(torch.zeros(480, 2, 1, dtype=torch.uint8, device=src.device), action_repeat=2)
+  torch.cuda.synchronize()
 
 
 def test_a_fleet_is_refused():
