@@ -28,7 +28,8 @@
 // from the LDS slot of the lane's own last stride.
 //
 // Same lane functions as agent_step (ble_step_core.h), same expressions around them: the results are bit for bit those of
-// ble_step_kernel (tests/test_gpu_parity.py::test_split_kernel_equals_one_lane_kernel).  Selected by the host entry
+// ble_step_kernel (tests/test_gpu_parity.py::test_split_kernel_equals_one_lane_kernel at 18 strides; tests/test_gpu_split_form.py at
+// 1 .. 60 strides, odd and even, with lanes that end on the first and the last stride of a step).  Selected by the host entry
 // points for n <= BLE_SPLIT_MAX_ENVS = 32 768 (two waves per SIMD: measured 1.4x the one-lane kernel there, 1.9x at <= 16 384
 // environments where every wave has a SIMD to itself; at 65 536 -- four waves per SIMD -- the one-lane kernel wins).
 #pragma once
