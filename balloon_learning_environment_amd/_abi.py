@@ -118,6 +118,25 @@ class BleGpBelief(ctypes.Structure):
   _fields_ = [('slab', ctypes.c_void_p), ('stride', ctypes.c_int64), ('n_obs', ctypes.c_void_p), ('n', ctypes.c_int64)]
 
 
+PLAN_MAX_PLANS, PLAN_MAX_ITERATIONS = 1024, 16      # BLE_PLAN_MAX_PLANS, BLE_PLAN_MAX_ITERATIONS
+
+
+class BlePlanSample(ctypes.Structure):
+  """struct ble_plan_sample: K piecewise-constant action plans per environment for ble_plan_sample_u8 (device pointers)."""
+  _fields_ = [('n', ctypes.c_int64), ('n_plans', ctypes.c_int32), ('n_plan_steps', ctypes.c_int32), ('segment', ctypes.c_int32),
+              ('iteration', ctypes.c_int32), ('seed', ctypes.c_uint64), ('env_seed', ctypes.c_void_p), ('env_offset', ctypes.c_int64),
+              ('decision_counter', ctypes.c_void_p), ('elite_counts', ctypes.c_void_p), ('best_plan', ctypes.c_void_p),
+              ('plans', ctypes.c_void_p)]
+
+
+class BlePlanSelect(ctypes.Structure):
+  """struct ble_plan_select: the returns of those plans and what ble_plan_select_f32 writes (device pointers)."""
+  _fields_ = [('n', ctypes.c_int64), ('n_plans', ctypes.c_int32), ('n_plan_steps', ctypes.c_int32), ('segment', ctypes.c_int32),
+              ('iteration', ctypes.c_int32), ('elite', ctypes.c_int32), ('reserved_', ctypes.c_int32), ('ret', ctypes.c_void_p),
+              ('plans', ctypes.c_void_p), ('best_return', ctypes.c_void_p), ('best_k', ctypes.c_void_p), ('best_plan', ctypes.c_void_p),
+              ('action', ctypes.c_void_p), ('elite_counts', ctypes.c_void_p), ('advance_counter', ctypes.c_void_p)]
+
+
 class BleNoiseGen(ctypes.Structure):
   """struct ble_noise_gen: the wind-noise generator of a fused rollout (ble_step_n_f32, ABI 3)."""
   _fields_ = [('seed', ctypes.c_uint64), ('episode', ctypes.c_void_p), ('harmonic_cache', ctypes.c_void_p),

@@ -1,0 +1,166 @@
+"""A model-predictive agent that plans entirely on the device (no counterpart in the reference).
+
+Per decision: sample K piecewise-constant action plans per environment (`ble_plan_sample_u8`), fly them from the state where each
+balloon lies with the look-ahead kernels (`VecSimulator.rollout_plans`: `ble_rollout_f32` / `ble_rollout_belief_f32`), pick the best
+plan (`ble_plan_select_f32`) -- optionally refined by cross-entropy iterations: the next iteration samples around the elite plans of
+this one -- and emit the plan's first action.  No host synchronisation anywhere, so a decision is capturable in the same HIP graph
+as the step.  The agent needs no trained weights; it needs the simulator, which `bind` attaches (eval_lib.VecEvaluator does that for
+any agent with a `bind`; `VecBalloonEnv.planner()` returns a bound agent).
+"""
+import ctypes
+from typing import Callable, Optional, Tuple, Union
+
+import torch
+
+from balloon_learning_environment_amd import _abi
+from balloon_learning_environment_amd import _lib
+from balloon_learning_environment_amd import device as dev
+from balloon_learning_environment_amd import vec_state
+
+WINDS = ('belief', 'forecast', 'truth')
+STAY = 1
+
+
+class VecLookaheadAgent:
+  """Look-ahead planning for N environments at once: act(obs) -> uint8 [N] device actions.
+
+  num_plans K (<= 1024) plans per environment of `horizon` H entries, every entry flown action_repeat agent steps
+  (H * action_repeat <= 960); a plan is constant over `segment` entries.  gamma: the discount of a plan's return.
+  wind: 'belief' (default) -- forecast + the mean of the WindGP over the balloon's own measurements, fitted at every decision: all an
+  agent may legitimately know; 'forecast' -- the forecast alone; 'truth' -- the wind the environments will fly (bind(noise_seed=)):
+  a simulator-side upper bound.  iterations (<= 16): 1 picks the best of K; more refine by cross-entropy, each iteration drawing
+  every segment's action with probability (c_a + 1) / (E + 3) from the counts c_a of the E = min(elite, K) best plans of the one
+  before, the best plan so far always kept.  Iteration 0 always holds all-STAY, all-DOWN, all-UP and the previous decision's best
+  plan shifted by one entry (as far as K reaches).  seed: the plans' Philox streams are keyed by (seed, environment, decision
+  counter, iteration, k), or with bind(seeds=) by (that environment's seed, decision counter, iteration, k): then an environment
+  plans the same in any batch."""
+
+  def __init__(self, num_plans: int = 64, horizon: int = 24, action_repeat: int = 1, segment: int = 4, gamma: float = 0.993,
+               wind: str = 'belief', iterations: int = 1, elite: int = 8, seed: int = 0, device='cuda:0',
+               substeps: int = vec_state.SUBSTEPS):
+    if wind not in WINDS:
+      raise ValueError(f"VecLookaheadAgent: wind is 'belief', 'forecast' or 'truth', not {wind!r}")
+    if not 1 <= int(num_plans) <= _abi.PLAN_MAX_PLANS:
+      raise ValueError(f'VecLookaheadAgent: 1 <= num_plans <= {_abi.PLAN_MAX_PLANS}, not {num_plans}')
+    if int(horizon) < 1 or int(action_repeat) < 1 or int(horizon) * int(action_repeat) > _abi.ROLLOUT_MAX_STEPS:
+      raise ValueError(f'VecLookaheadAgent: horizon >= 1, action_repeat >= 1 and horizon * action_repeat <= {_abi.ROLLOUT_MAX_STEPS}, '
+                       f'not {horizon} x {action_repeat}')
+    if int(segment) < 1 or not 1 <= int(iterations) <= _abi.PLAN_MAX_ITERATIONS or int(elite) < 1:
+      raise ValueError(f'VecLookaheadAgent: segment >= 1, 1 <= iterations <= {_abi.PLAN_MAX_ITERATIONS} and elite >= 1, '
+                       f'not {segment}, {iterations}, {elite}')
+    if not 0.0 <= float(gamma) <= 1.0:
+      raise ValueError(f'VecLookaheadAgent: gamma in [0, 1], not {gamma}')
+    self.device = dev.require_gpu(device)
+    self.lib = _lib.lib()
+    self.num_plans, self.horizon, self.action_repeat, self.segment = int(num_plans), int(horizon), int(action_repeat), int(segment)
+    self.gamma, self.wind, self.iterations, self.seed, self.substeps = float(gamma), wind, int(iterations), int(seed), int(substeps)
+    self.elite = min(int(elite), self.num_plans)
+    self.segments = -(-self.horizon // self.segment)
+    self.sim: Optional[vec_state.VecSimulator] = None
+    self._seeds: Optional[torch.Tensor] = None
+    self._noise_seed: Union[None, int, Callable[[], int]] = None
+
+  # ------------------------------------------------------------------ attach a simulator
+  @dev.on_own_device
+  def bind(self, sim: vec_state.VecSimulator, seeds: Optional[torch.Tensor] = None, noise_seed=None) -> 'VecLookaheadAgent':
+    """Attaches the simulator whose environments this agent flies and starts a new run of decisions (counter 0, previous best plan all
+    STAY).  All buffers are allocated here, once: binding the same simulator (and the same `seeds` tensor) again only restarts the
+    run, so a captured graph stays valid.
+    seeds: int64 / uint64 device tensor [N], a seed per environment (read at every decision): the plans of an environment then do
+    not depend on its batch.  noise_seed: the seed of the environments' wind noise, or a callable returning it, for wind='truth'
+    (None there: the truth is the forecast)."""
+    if sim.has_fleet:
+      raise ValueError('VecLookaheadAgent: a fleet (set_fleet) has no look-ahead kernel; fly one vehicle per batch (set_vehicle)')
+    if sim.device != self.device:
+      raise ValueError(f'VecLookaheadAgent on {self.device} cannot plan for a simulator on {sim.device}')
+    if seeds is not None:
+      if self.wind == 'truth':
+        raise ValueError("VecLookaheadAgent: wind='truth' with per-environment seeds: the look-ahead's noise generator takes one seed")
+      assert seeds.dtype in (torch.int64, torch.uint64) and seeds.is_contiguous() and tuple(seeds.shape) == (sim.n,), seeds.shape
+      assert seeds.device == self.device
+    if sim.n * self.num_plans >= 2 ** 31:
+      raise ValueError(f'VecLookaheadAgent: n * num_plans < 2^31, not {sim.n} x {self.num_plans}')
+    same = self.sim is sim and self._seeds is seeds
+    self.sim, self._seeds, self._noise_seed = sim, seeds, noise_seed
+    if not same:
+      n, k, h = sim.n, self.num_plans, self.horizon
+      z = lambda dtype, *shape: torch.zeros(*shape, dtype=dtype, device=self.device)
+      self.counter = z(torch.int64, 1)                       # the decision counter: device memory, advanced by the last selection
+      self.plans = z(torch.uint8, h, n, k)
+      self.returns, self.steps_flown = z(torch.float32, n, k), z(torch.int32, n, k)
+      self.best_return, self.best_k = z(torch.float32, n), z(torch.int32, n)
+      self.best_plan = z(torch.uint8, h, n)
+      self.elite_counts = z(torch.int16, n, self.segments, 3)
+      self.action = z(torch.uint8, n)
+      self._belief = None
+      if self.wind == 'belief':
+        self._belief = vec_state.WindBelief(z(torch.float64, n, _lib.GP_BELIEF_DOUBLES), z(torch.int32, n))
+    self.counter.zero_()
+    self.best_plan.fill_(STAY)
+    self.best_return.zero_()
+    self.best_k.fill_(-1)
+    return self
+
+  def _bound(self) -> vec_state.VecSimulator:
+    if self.sim is None:
+      raise ValueError('VecLookaheadAgent.act before bind(sim): the agent plans in a simulator (VecBalloonEnv.planner() binds one)')
+    return self.sim
+
+  # ------------------------------------------------------------------ one decision
+  @dev.on_own_device
+  def act(self, obs: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """One decision for every environment of the bound simulator, from the state where it lies: uint8 [N] actions (device).  obs is
+    accepted and unused (the plans are flown from the state itself).  out: optional uint8 [N] for the actions.  Nothing of the
+    simulator is written; flags of the imagined flights go to sim.rollout_flags.  Asynchronous, capturable in a HIP graph."""
+    del obs
+    sim = self._bound()
+    if sim.has_fleet:
+      raise ValueError('VecLookaheadAgent: the bound simulator flies a fleet now; a fleet has no look-ahead kernel')
+    n = sim.n
+    if out is None:
+      out = self.action
+    assert out.dtype == torch.uint8 and out.is_contiguous() and out.numel() == n and out.device == self.device
+    stream = dev.stream_ptr(self.device)
+    belief, noise_seed = None, None
+    if self.wind == 'belief':
+      belief = sim.fit_wind_belief(out=self._belief)
+    elif self.wind == 'truth':
+      noise_seed = self._noise_seed() if callable(self._noise_seed) else self._noise_seed
+    rollout_out = (self.returns, self.steps_flown, None, None)
+    for it in range(self.iterations):
+      last = it + 1 == self.iterations
+      ps = _abi.BlePlanSample(n, self.num_plans, self.horizon, self.segment, it, self.seed & (2 ** 64 - 1), dev.ptr(self._seeds),
+                              0 if self._seeds is not None else sim.env_offset, self.counter.data_ptr(), self.elite_counts.data_ptr(),
+                              self.best_plan.data_ptr(), self.plans.data_ptr())
+      _lib.check(self.lib.ble_plan_sample_u8(ctypes.byref(ps), stream), 'ble_plan_sample_u8')
+      sim.rollout_plans(self.plans, self.gamma, self.action_repeat, noise_seed, self.substeps, out=rollout_out, belief=belief)
+      # (the elite counts are the next iteration's: the last selection writes none, and moves the decision counter on)
+      sel = _abi.BlePlanSelect(n, self.num_plans, self.horizon, self.segment, it, 0 if last else self.elite, 0, self.returns.data_ptr(),
+                               self.plans.data_ptr(), self.best_return.data_ptr(), self.best_k.data_ptr(), self.best_plan.data_ptr(),
+                               out.data_ptr(), self.elite_counts.data_ptr(), self.counter.data_ptr() if last else None)
+      _lib.check(self.lib.ble_plan_select_f32(ctypes.byref(sel), stream), 'ble_plan_select_f32')
+    return out
+
+  __call__ = act
+
+  def plan(self) -> Tuple[torch.Tensor, torch.Tensor]:
+    """(best_plan uint8 [H, N], best_return float32 [N]) of the last decision: the agent's own buffers, overwritten by the next one."""
+    self._bound()
+    return self.best_plan, self.best_return
+
+  def state_dict(self) -> dict:
+    """What a run of decisions carries from one to the next: the decision counter and the best plan (the warm start)."""
+    self._bound()
+    return {'counter': self.counter.clone(), 'best_plan': self.best_plan.clone()}
+
+  def load_state_dict(self, d: dict) -> None:
+    self._bound()
+    self.counter.copy_(d['counter'])
+    self.best_plan.copy_(d['best_plan'])
+
+  def check_errors(self) -> None:
+    """The agent latches no error of its own: its kernels cannot fail on valid buffers, and the flags of the flights it imagines stay
+    in sim.rollout_flags (a plan that leaves the valid range is no error of the flight that really happens)."""
+
+  def get_name(self) -> str:
+    return 'LookaheadAgent'

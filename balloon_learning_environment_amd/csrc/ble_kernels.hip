@@ -817,6 +817,7 @@ __global__ __launch_bounds__(256) void ble_eval_accumulate_kernel(StateDev st, c
 #include "ble_rollout.h"
 // the fitted WindGP kept on the device, its mean as a lane function, and the look-ahead flown in it: after ble_rollout.h (RolloutArgs)
 #include "ble_gp_belief.h"
+#include "ble_plan.h"
 // fp64 primitive probe (test-only entry point): op 0 rcp seed, 1 d_rcp, 2 rsq seed, 3 d_rsqrt,
 // 4 d_sqrt_fast, 5 d_log_fast, 6 d_exp_fast, 7 sin (sincos_f64), 8 cos (sincos_f64)
 __global__ __launch_bounds__(256) void probe_f64_kernel(const double* x, double* y, int op, int64_t n) {
@@ -1769,6 +1770,33 @@ int ble_rollout_belief_f32(const ble_state_f32* st, const struct ble_rollout_f32
     return launch(ble_rollout_belief_kernel<decltype(veh)>, ro->n * (int64_t)ro->n_plans, kStepBlock, kStepBlock, stream, state_dev(st), a, b,
                   err_flags, veh);
   });
+}
+
+// the sizes ble_plan_sample_u8 and ble_plan_select_f32 share
+inline bool plan_sizes_ok(int64_t n, int n_plans, int n_plan_steps, int segment, int iteration) {
+  return n >= 0 && n < 2147483648LL && n_plans >= 1 && n_plans <= BLE_PLAN_MAX_PLANS && n_plan_steps >= 1 &&
+         n_plan_steps <= BLE_ROLLOUT_MAX_STEPS && segment >= 1 && iteration >= 0 && iteration < BLE_PLAN_MAX_ITERATIONS &&
+         n * (int64_t)n_plans < 2147483648LL;
+}
+
+int ble_plan_sample_u8(const struct ble_plan_sample* ps, void* stream) {
+  if (!ps || !ps->plans || !ps->decision_counter || !ps->best_plan || (ps->iteration > 0 && !ps->elite_counts)) return BLE_E_INVALID_ARG;
+  if (!plan_sizes_ok(ps->n, ps->n_plans, ps->n_plan_steps, ps->segment, ps->iteration) || ps->env_offset < 0) return BLE_E_INVALID_ARG;
+  const PlanSampleArgs a{ps->n, ps->env_offset, ps->n_plans, ps->n_plan_steps, ps->segment, ps->iteration, ps->decision_counter,
+                         ps->iteration > 0 ? ps->elite_counts : nullptr, ps->best_plan, ps->plans};
+  const int64_t lanes = ps->n * (int64_t)ps->n_plans;
+  if (ps->env_seed != nullptr) return launch(ble_plan_sample_kernel<EnvSeed>, lanes, 256, 256, stream, a, EnvSeed{ps->env_seed});
+  return launch(ble_plan_sample_kernel<ScalarSeed>, lanes, 256, 256, stream, a, ScalarSeed{ps->seed});
+}
+
+int ble_plan_select_f32(const struct ble_plan_select* sel, void* stream) {
+  if (!sel || !sel->ret || !sel->plans || !sel->best_return || !sel->best_k || !sel->best_plan || !sel->action) return BLE_E_INVALID_ARG;
+  if (!plan_sizes_ok(sel->n, sel->n_plans, sel->n_plan_steps, sel->segment, sel->iteration) || sel->elite < 0 || sel->elite > sel->n_plans ||
+      (sel->elite >= 1 && !sel->elite_counts))
+    return BLE_E_INVALID_ARG;
+  const PlanSelectArgs a{sel->n, sel->n_plans, sel->n_plan_steps, sel->segment, sel->iteration, sel->elite, sel->ret, sel->plans,
+                         sel->best_return, sel->best_k, sel->best_plan, sel->action, sel->elite_counts, sel->advance_counter};
+  return launch(ble_plan_select_kernel, sel->n, 1, kPlanSelectBlock, stream, a);
 }
 
 }  // extern "C"

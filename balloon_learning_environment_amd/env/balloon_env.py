@@ -236,6 +236,16 @@ class VecBalloonEnv:
     noise_seed = self.arena._seed if (wind == 'truth' and self._wind_noise) else None
     return self.arena.lookahead(plans, gamma, action_repeat, noise_seed, want_rewards, want_final, out)
 
+  def planner(self, **kw):
+    """A look-ahead agent bound to these environments: agents.lookahead_agent.VecLookaheadAgent(**kw) -- num_plans, horizon,
+    action_repeat, segment, gamma, wind ('belief' by default), iterations, elite, seed -- planning in this batch's simulator.
+    wind='truth' flies the plans in the wind these environments fly, this env's wind noise included (with wind_noise=False the truth
+    is the forecast).  actions = agent.act(obs); obs, reward, terminal = env.step(actions): no host synchronisation in either."""
+    from balloon_learning_environment_amd.agents import lookahead_agent
+    kw.setdefault('device', self.device)
+    agent = lookahead_agent.VecLookaheadAgent(**kw)
+    return agent.bind(self.arena.sim, noise_seed=(lambda: self.arena._seed) if self._wind_noise else None)
+
   def _step_eager(self, actions, obs_out=None, end_mask=None):
     noise = None
     if self._wind_noise:

@@ -223,6 +223,8 @@ class VecEvaluator:
       self.sim.set_grid(self.grids, per_env=True)
     for t in (self.cumulative_reward, self.steps_within_radius, self.final_timestep, self.done, self.end_status):
       t.zero_()
+    if hasattr(self.agent, 'bind'):       # an agent that plans in the simulator (VecLookaheadAgent): this batch's, keyed by its seeds
+      self.agent.bind(self.sim, seeds=self.seeds)
     self._observe_and_act()
     if self.capture_graph and self._graph is None:
       self._capture()

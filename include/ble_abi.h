@@ -988,6 +988,78 @@ int ble_gp_belief_wind_f32(const ble_gp_belief* belief, const float* x_m, const 
 int ble_rollout_belief_f32(const ble_state_f32* st, const struct ble_rollout_f32* ro, const ble_gp_belief* belief, uint32_t* err_flags,
                            void* stream);
 
+/*
+ * Plan on the device: sample K action plans per environment, fly them (ble_rollout_f32 / ble_rollout_belief_f32) and pick the best --
+ * the two ends of a model-predictive decision, optionally iterated as a cross-entropy search.  Added without a new ABI version; every
+ * size travels in a struct (no int64_t argument).
+ *
+ * ble_plan_sample_u8 writes plans [H][n][K], the layout ble_rollout_f32 reads.  A plan is piecewise constant: entry h belongs to
+ * segment h / segment, each segment takes ONE 32-bit Philox word and draws
+ *     r = (word * (E + 3)) >> 32;   action = 0 if r < c0 + 1, 1 if r < c0 + c1 + 2, else 2
+ * where c0, c1, c2 are the segment's elite counts (iteration > 0; E their sum) or zero (iteration 0: uniform thirds).  Integers only.
+ * The stream of plan k of environment e: Philox4x32-10 with the key (seed_e ^ 0x504C414E53) -- its high word xor the high word of the
+ * decision counter -- and the counter (block, low word of the decision counter, low and high word of key_e); seed_e, key_e =
+ * seed, env_offset + e, or with env_seed: env_seed[e], 0.  Block = (iteration * 1024 + k) * 256 + s / 4 for segment s, which takes
+ * output word s % 4.  So a plan depends on (seed, the environment's key, decision counter, iteration, k, H, segment, its counts) and
+ * never on n, K or the other environments of the batch.
+ * Iteration 0 fixes the first slots, as far as K reaches: k = 0 all STAY (1), k = 1 all DOWN (0), k = 2 all UP (2), k = 3 the warm
+ * start: entry h = best_plan[min(h + 1, H - 1)][e].
+ * BLE_E_INVALID_ARG before any HIP call: NULL ps, plans, decision_counter or best_plan; iteration > 0 with NULL elite_counts; n < 0 or
+ * >= 2^31, n_plans outside 1 .. BLE_PLAN_MAX_PLANS, n_plan_steps outside 1 .. BLE_ROLLOUT_MAX_STEPS, segment < 1, iteration outside
+ * 0 .. BLE_PLAN_MAX_ITERATIONS - 1, n * n_plans >= 2^31, env_offset < 0.  n == 0: BLE_OK without a launch.
+ */
+#define BLE_PLAN_MAX_PLANS 1024
+#define BLE_PLAN_MAX_ITERATIONS 16
+/* (struct TAGS only, as for ble_rollout_f32) */
+struct ble_plan_sample {
+  int64_t n;                                 /* environments */
+  int32_t n_plans;                           /* K */
+  int32_t n_plan_steps;                      /* H entries per plan */
+  int32_t segment;                           /* entries per segment, >= 1 */
+  int32_t iteration;                         /* 0 .. BLE_PLAN_MAX_ITERATIONS - 1 */
+  unsigned long long seed;                   /* the batch's seed (env_seed == NULL) */
+  const unsigned long long* env_seed;        /* optional device [n]: a seed per environment, every stream keyed as environment 0 */
+  int64_t env_offset;                        /* index of environment 0 in the global batch (env_seed == NULL) */
+  const unsigned long long* decision_counter;/* device, one word: read, not written */
+  const uint16_t* elite_counts;              /* device [n][ceil(H / segment)][3]: read when iteration > 0 */
+  const uint8_t* best_plan;                  /* device [H][n]: read by the warm start */
+  uint8_t* plans;                            /* device [H][n][K] out */
+};
+int ble_plan_sample_u8(const struct ble_plan_sample* ps, void* stream);
+
+/*
+ * ble_plan_select_f32: one wavefront per environment over ret [n][K], the returns of the plans ble_plan_sample_u8 wrote.
+ * The order: a finite return before a non-finite one (Inf or NaN: all equal), then the return descending (-0 == +0), then k ascending.
+ * The first plan in that order is compared with the incumbent -- best_return[e] as the earlier iterations of this decision left it;
+ * none in iteration 0 -- and replaces it when it is finite and strictly greater, or the incumbent is not finite; a tie keeps the
+ * incumbent.  Written: best_return [n]; best_k [n], the plan's index or -1 when the incumbent stayed; best_plan [H][n] (only when
+ * replaced); action [n] = best_plan[0][e].  Iteration 0 without a finite plan: best_plan all STAY, best_return -Inf, best_k -1.
+ * elite = E >= 1: also elite_counts [n][ceil(H / segment)][3], per segment and action the number of the first E plans in the order
+ * that take it, for the next iteration's sampler.  advance_counter, when given, is incremented by one (the decision counter, after
+ * the decision's last sampler: stream order).
+ * BLE_E_INVALID_ARG before any HIP call: NULL sel, ret, plans, best_return, best_k, best_plan or action; the sampler's limits on n,
+ * n_plans, n_plan_steps, segment and iteration; elite < 0 or > n_plans; elite >= 1 with NULL elite_counts.  n == 0: BLE_OK without a
+ * launch (and without advancing the counter).
+ */
+struct ble_plan_select {
+  int64_t n;
+  int32_t n_plans;
+  int32_t n_plan_steps;
+  int32_t segment;
+  int32_t iteration;
+  int32_t elite;                             /* E: 0 .. n_plans */
+  int32_t reserved_;
+  const float* ret;                          /* device [n][K] */
+  const uint8_t* plans;                      /* device [H][n][K] */
+  float* best_return;                        /* device [n]: read when iteration > 0, written */
+  int32_t* best_k;                           /* device [n] out */
+  uint8_t* best_plan;                        /* device [H][n]: written where a plan replaces the incumbent */
+  uint8_t* action;                           /* device [n] out */
+  uint16_t* elite_counts;                    /* device [n][ceil(H / segment)][3] out, required when elite >= 1 */
+  unsigned long long* advance_counter;       /* optional device word */
+};
+int ble_plan_select_f32(const struct ble_plan_select* sel, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
