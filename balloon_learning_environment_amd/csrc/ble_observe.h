@@ -1426,9 +1426,14 @@ __global__ __launch_bounds__(kObsBlock, 2) void ble_observe_kernel(StateDev st, 
   // the factor of this window goes back to HBM for the next call
   __syncthreads();                                 // the bordering row is in LDS
   if (chol_g != nullptr) {
-    const int pairs = (tri(n_obs) + 1) >> 1;       // (an odd tail stores one unused double inside the slab)
+    // exactly the tri(n_obs) words of the triangle: whole pairs, and the last double of an odd triangle (n_obs % 4 in {1, 2}) on its
+    // own -- the word after it is nobody's in LDS (a refit never writes it) and stays what it was in the slab
+    const int words = tri(n_obs), pairs = words >> 1;
     for (int e2 = tid; e2 < pairs; e2 += kObsBlock) reinterpret_cast<double2*>(chol_g)[e2] = reinterpret_cast<const double2*>(sh.L)[e2];
-    if (tid == 0) hist.n_chol[env] = n_obs;
+    if (tid == 0) {
+      if (words & 1) chol_g[words - 1] = sh.L[words - 1];
+      hist.n_chol[env] = n_obs;
+    }
   }
   // every lane has read the old count long before this point (barriers above)
   if (tid == 0) hist.count[env] = count;

@@ -195,3 +195,74 @@ def f18_device_word(d, j, oracle_env):
 
 def f18_reference_class(d, j):
   return F18_CLASSES[int(d['exc'][j])]
+
+
+# WindGP history rings written straight into a simulator's ring tensors (tests/test_gpu_belief.py, test_gpu_gp_query.py,
+# test_gpu_carried_slab.py) -- random positions, pressures and errors instead of a flight.
+GP_CAPACITY = 128
+GP_HORIZON_S = 6 * 3600
+GP_ROWS = 120
+
+
+def observations(rng, count, spacing, end=None):
+  """`count` observations in chronological order, the last at time `end` (default: spacing * (count - 1)):
+  (xyp [count, 3] f32, t [count] i32, err [count, 2] f32)."""
+  xyp = np.column_stack([rng.uniform(-2.0e5, 2.0e5, count), rng.uniform(-2.0e5, 2.0e5, count),
+                         rng.uniform(5000.0, 14000.0, count)]).astype(np.float32)
+  t = spacing * np.arange(count)
+  if end is not None:
+    t = t + (end - spacing * (count - 1))
+  return xyp, t.astype(np.int32), rng.normal(0.0, 2.0, (count, 2)).astype(np.float32)
+
+
+def write_ring(sim, env, obs):
+  """Appends the observations the way ble_observe_f32 does: observation i in slot i % 128, count = their number."""
+  import torch
+  xyp, t, err = obs
+  count = len(t)
+  first = max(0, count - GP_CAPACITY)
+  slots = torch.from_numpy(np.arange(first, count) % GP_CAPACITY).to(sim.device)
+  sim._gp['xyp'][env, slots] = torch.from_numpy(xyp[first:]).to(sim.device)
+  sim._gp['elapsed_s'][env, slots] = torch.from_numpy(t[first:]).to(sim.device)
+  sim._gp['err_uv'][env, slots] = torch.from_numpy(err[first:]).to(sim.device)
+  sim._gp['count'][env] = count
+
+
+def ring_back(sim, env):
+  """The ring of `env` as the device holds it, chronological: (xyp [m, 3], t [m], err [m, 2]) float64, m = min(count, 128)."""
+  count = int(sim._gp['count'][env].item())
+  m = min(count, GP_CAPACITY)
+  slots = (np.arange(count - m, count) % GP_CAPACITY)
+  g = {k: sim._gp[k][env].cpu().numpy() for k in ('xyp', 'elapsed_s', 'err_uv')}
+  return g['xyp'][slots].astype(np.float64), g['elapsed_s'][slots].astype(np.float64), g['err_uv'][slots].astype(np.float64)
+
+
+def gp_window(t, now):
+  """WindGP's window at time `now` over observation times `t` (chronological): the indices with |t - now| < 6 h (strict,
+  wind_gp.py:183), the newest 120 of them."""
+  return np.flatnonzero(np.abs(np.asarray(t, np.float64) - float(now)) < GP_HORIZON_S)[-GP_ROWS:]
+
+
+def slide_times(m, now, leaving=1, step=180):
+  """Times of the m - 1 + (leaving - 1) observations to write BEFORE an observe() at `now` so that the call ends with a window of
+  m - 1 + leaving rows, all inside 6 h, and the observe() one agent step later (now + step) finds exactly `leaving` of them -- the
+  oldest ones -- outside the strict window while one row is appended: a window of m rows again for leaving = 1 (a slide at a
+  partial window), of m rows after `leaving` >= 2 left at once (a refit).  The leaving ones stand between now + step - 6 h
+  (excluded at now + step: age == 6 h is outside) and now - 6 h (still inside at now); the others 180 s apart up to now - 180."""
+  assert 2 <= m <= GP_ROWS and 1 <= leaving <= 8
+  stay = now - step * np.arange(m - 2, 0, -1)                  # m - 2 observations that stay: now - 180 (m - 2) .. now - 180
+  leave = now + step - GP_HORIZON_S - 10 * np.arange(leaving - 1, -1, -1)
+  return np.concatenate([leave, stay]).astype(np.int32)
+
+
+def rings_back(sim):
+  """ring_back of every environment from ONE copy of the ring tensors: a list of (xyp [m, 3], t [m], err [m, 2]) float64."""
+  g = {k: sim._gp[k].cpu().numpy() for k in ('xyp', 'elapsed_s', 'err_uv', 'count')}
+  out = []
+  for env in range(sim.n):
+    count = int(g['count'][env])
+    m = max(0, min(count, GP_CAPACITY))
+    slots = (np.arange(count - m, count) % GP_CAPACITY)
+    out.append((g['xyp'][env][slots].astype(np.float64), g['elapsed_s'][env][slots].astype(np.float64),
+                g['err_uv'][env][slots].astype(np.float64)))
+  return out

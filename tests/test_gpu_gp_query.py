@@ -16,6 +16,7 @@ import pytest
 import torch
 
 import wind_gp_host
+from helpers import observations as _observations, ring_back as _ring_back, write_ring as _write_ring
 from balloon_learning_environment_amd import _lib, device as dev, vec_state
 from balloon_learning_environment_amd.env import balloon_env
 from balloon_learning_environment_amd.env import wind_field
@@ -39,34 +40,6 @@ class _NoForecast(wind_field.WindField):
 
   def get_forecast(self, x, y, pressure, elapsed_time):
     return wind_field.WindVector(units.Velocity(mps=0.0), units.Velocity(mps=0.0))
-
-
-def _observations(rng, count, spacing):
-  """`count` observations in chronological order: (xyp [count, 3] f32, t [count] i32, err [count, 2] f32)."""
-  xyp = np.column_stack([rng.uniform(-2.0e5, 2.0e5, count), rng.uniform(-2.0e5, 2.0e5, count),
-                         rng.uniform(5000.0, 14000.0, count)]).astype(np.float32)
-  return xyp, (spacing * np.arange(count)).astype(np.int32), rng.normal(0.0, 2.0, (count, 2)).astype(np.float32)
-
-
-def _write_ring(sim, env, obs):
-  """Appends the observations the way ble_observe_f32 does: observation i in slot i % 128, count = their number."""
-  xyp, t, err = obs
-  count = len(t)
-  first = max(0, count - CAP)
-  slots = torch.from_numpy(np.arange(first, count) % CAP).to(sim.device)
-  sim._gp['xyp'][env, slots] = torch.from_numpy(xyp[first:]).to(sim.device)
-  sim._gp['elapsed_s'][env, slots] = torch.from_numpy(t[first:]).to(sim.device)
-  sim._gp['err_uv'][env, slots] = torch.from_numpy(err[first:]).to(sim.device)
-  sim._gp['count'][env] = count
-
-
-def _ring_back(sim, env):
-  """The ring of `env` as the device holds it, chronological: (xyp [m, 3], t [m], err [m, 2]) float64, m = min(count, 128)."""
-  count = int(sim._gp['count'][env].item())
-  m = min(count, CAP)
-  slots = (np.arange(count - m, count) % CAP)
-  g = {k: sim._gp[k][env].cpu().numpy() for k in ('xyp', 'elapsed_s', 'err_uv')}
-  return g['xyp'][slots].astype(np.float64), g['elapsed_s'][slots].astype(np.float64), g['err_uv'][slots].astype(np.float64)
 
 
 def _host(ring, points, tq, newest=None):
