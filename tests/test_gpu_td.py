@@ -4,7 +4,8 @@ with its tolerances:
 
  * loss, targets and dL/dlogits of each kind against the twin evaluated on the device's own float32 logits; exact zeros; a masked row;
  * returns scaled by 1e20: Huber stays finite and bounded, MSE gives no NaN;
- * the gradient image of SARSA's two branches against float64 backprop, within the magnitude bound; the padding exactly zero;
+ * the gradient image of SARSA's two branches and of DQN's losses against float64 backprop, within the magnitude bound, at
+   test_gpu_train.py's batch edges too; the padding exactly zero;
  * SGD against float64 arithmetic over 10 updates; the transposed image follows; the padding stays zero;
  * determinism: two instances, graph vs eager, a state_dict restored mid-run;
  * VecMLPAgent: pre-update actions, N = 1 against sequential twin updates, eval mode, masked rows' observations do not matter;
@@ -198,13 +199,17 @@ def _worst(got, want, mag, layers):
   return worst
 
 
-@pytest.mark.parametrize('layers,hidden,b', [(1, 0, 32), (2, 64, 32), (3, 37, 32), (8, 600, 32), (2, 64, 600)])
+EDGE_BATCHES = (1, 7, 9, 33, 129, 511, 513, 4097)          # test_gpu_train.py's batch edges of the backward pass
+
+
+@pytest.mark.parametrize('layers,hidden,b', [(1, 0, 32), (2, 64, 32), (3, 37, 32), (8, 600, 32), (2, 64, 600)] +
+                         [(2, 64, b) for b in EDGE_BATCHES])
 def test_sarsa_gradient_against_float64_backprop(mods, observations, layers, hidden, b):
   """Both branches into the one gradient image: |g - g64| <= 1e-5 S, S = train_host.backward_magnitude summed over the branches, on the
   device's own activations and dlogits.  B = 600 takes the slab path (2 slabs per branch)."""
   qnet, qnet_train = mods[0], mods[1]
   params, ag = _mlp(mods, b, layers, hidden)
-  t = _transitions(ag, observations, seed=layers)
+  t = _transitions(ag, observations, seed=layers, mask_p=0.25 if b > 1 else 0.0)      # (B = 1: the one row takes part)
   ag.train_on_transitions(apply_update=False)
   v = ag.views()
   width = lambda l: 3 if l == layers - 1 else hidden
@@ -215,17 +220,17 @@ def test_sarsa_gradient_against_float64_backprop(mods, observations, layers, hid
   g = ag.grad.cpu().numpy()
   got = qnet_train.unpack(ag._net, g)['params']
   worst = _worst(got, want, mag, layers)
-  print('worst |g - g64| / (1e-5 S)', worst)
+  print('B', b, 'worst |g - g64| / (1e-5 S)', worst)
   assert worst <= 1.0, worst
   assert any(np.abs(want[l][0]).max() > 0 for l in range(layers))
   # the padding of the gradient image is exactly zero: packing the unpacked gradient gives the image back
   assert np.array_equal(_repacked(qnet, {'params': got}).view(np.uint32), g.view(np.uint32))
 
 
-@pytest.mark.parametrize('kind', ['mse', 'huber'])
-def test_dqn_gradient_against_float64_backprop(mods, observations, kind):
+@pytest.mark.parametrize('kind,layers,hidden,b', [pytest.param(kind, 3, 37, 32, id=kind) for kind in ('mse', 'huber')] +
+                         [(kind, 2, 64, b) for kind in ('mse', 'huber') for b in EDGE_BATCHES])
+def test_dqn_gradient_against_float64_backprop(mods, observations, kind, layers, hidden, b):
   qnet, qnet_train = mods[0], mods[1]
-  layers, hidden, b = 3, 37, 32
   params, tr = _dqn(mods, layers, hidden, loss_type=kind)
   x, bt = _batch(mods, observations, b, seed=4)
   tr.train_on_batch(bt, apply_update=False)
@@ -236,7 +241,9 @@ def test_dqn_gradient_against_float64_backprop(mods, observations, kind):
   want, mag = train_host.backward(params, x, dlog, acts), train_host.backward_magnitude(params, x, dlog, acts)
   g = tr.grad.cpu().numpy()
   got = qnet_train.unpack(tr._net, g)['params']
-  assert _worst(got, want, mag, layers) <= 1.0
+  worst = _worst(got, want, mag, layers)
+  print(kind, 'B', b, 'worst |g - g64| / (1e-5 S)', worst)
+  assert worst <= 1.0, worst
   assert np.array_equal(_repacked(qnet, {'params': got}).view(np.uint32), g.view(np.uint32))
 
 

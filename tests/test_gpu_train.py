@@ -4,7 +4,8 @@ of Dopamine 4.0.0's update (train_host.py):
  * replay: sampled windows, returns, discounts, actions and rows equal a host restatement exactly; no invalid window is drawn;
  * the loss, the targets and dL/dlogits against the oracle evaluated on the device's own float32 logits and targets;
  * the gradient image against float64 backprop on the device's activations, within the magnitude bound; the padding exactly zero;
- * Adam against float64 optax arithmetic over 10 steps; the padding of the weights stays zero;
+   at B = 32 and 600 and at the batch edges 1, 7, 9, 33, 129, 511, 513 and 4097 (EDGE_BATCHES);
+ * Adam against float64 optax arithmetic over 10 steps, and over 3 on a two-slab gradient; the padding of the weights stays zero;
  * determinism: two trainers, graph vs eager, and a state_dict restored mid-run give the same bits;
  * it learns a contextual bandit over real observations;
  * run_training_loop_vec end to end, its policy through eval_agent_vec.
@@ -155,7 +156,13 @@ def _repacked(qnet, tree, atoms):
   return qnet.QNetwork.from_params(tree, num_atoms=atoms).packed_host
 
 
-@pytest.mark.parametrize('layers,hidden,atoms,b', [(2, 64, 51, 32), (3, 37, 7, 32), (8, 600, 51, 32), (2, 64, 51, 600)])
+# Batch edges of the backward pass: one row, either side of the 8-row MFMA step, a ragged last dX tile, the last size with one dW slab
+# and the first with two (slabs of ceil(513 / 2) = 257 rows), and the first size past 16 slabs (4097: slabs of 257 rows again).
+EDGE_BATCHES = (1, 7, 9, 33, 129, 511, 513, 4097)
+
+
+@pytest.mark.parametrize('layers,hidden,atoms,b', [(2, 64, 51, 32), (3, 37, 7, 32), (8, 600, 51, 32), (2, 64, 51, 600)] +
+                         [(2, 64, 51, b) for b in EDGE_BATCHES] + [(3, 37, 7, 1), (3, 37, 7, 513)])
 def test_gradient_against_float64_backprop(mods, observations, layers, hidden, atoms, b):
   qnet, qnet_train = mods
   params, tr = _trainer(mods, layers, hidden, atoms)
@@ -176,6 +183,7 @@ def test_gradient_against_float64_backprop(mods, observations, layers, hidden, a
       err = np.abs(got[f'Dense_{l}'][leaf] - want[l][i])
       bound = 1e-5 * mag[l][i] + 1e-30
       worst = max(worst, float((err / bound).max()))
+  print('B', b, 'worst |g - g64| / (1e-5 S)', worst)
   assert worst <= 1.0, worst
   # the padding of the gradient image is exactly zero: packing the unpacked gradient gives the image back
   assert np.array_equal(_repacked(qnet, {'params': got}, atoms).view(np.uint32), g.view(np.uint32))
@@ -183,11 +191,20 @@ def test_gradient_against_float64_backprop(mods, observations, layers, hidden, a
 
 # ------------------------------------------------------------------------------------------------------------------------------ Adam
 def test_adam_against_optax_arithmetic(mods, observations):
+  _adam_against_optax_arithmetic(mods, observations, 64, 10)
+
+
+def test_adam_against_optax_arithmetic_on_a_two_slab_gradient(mods, observations):
+  """B = 513: the gradient Adam reads is the sum of two slab images; three steps."""
+  _adam_against_optax_arithmetic(mods, observations, 513, 3)
+
+
+def _adam_against_optax_arithmetic(mods, observations, b, steps):
   qnet, qnet_train = mods
   _, tr = _trainer(mods, 3, 37, 7, lr=1e-3, eps=2e-5)
-  _, bt = _batch(mods, observations, 64, seed=3)
+  _, bt = _batch(mods, observations, b, seed=3)
   w, m, v = (t.cpu().numpy().astype(np.float64) for t in (tr.weights, tr.adam_m, tr.adam_v))
-  for t in range(1, 11):
+  for t in range(1, steps + 1):
     tr.train_on_batch(bt)
     g = tr.grad.cpu().numpy()
     w64, m64, v64 = train_host.adam(w, g, m, v, t, lr=1e-3, eps=2e-5)
@@ -198,7 +215,7 @@ def test_adam_against_optax_arithmetic(mods, observations):
     assert (np.abs(md - m64) <= 1e-6 * (0.1 * np.abs(g) + 0.9 * np.abs(m)) + 1e-38).all(), t
     assert (np.abs(vd - v64) <= 1e-6 * v64 + 1e-38).all(), t
     w, m, v = wd.astype(np.float64), md.astype(np.float64), vd.astype(np.float64)
-  assert int(tr.adam_step.item()) == 10
+  assert int(tr.adam_step.item()) == steps
   wd = tr.weights.cpu().numpy()
   assert np.array_equal(_repacked(qnet, qnet_train.unpack(tr._net, wd), 7).view(np.uint32), wd.view(np.uint32))
   assert not np.array_equal(wd, qnet.QNetwork.from_params(_params(qnet, 3, 37, 7)).packed_host)

@@ -1,10 +1,13 @@
 """Prioritized replay and Marco Polo, CPU only: the fp64 restatement of the sum tree (prio_replay_host.py) against hand-computed trees,
-and the argument checks of the new entry points (every one answers BLE_E_INVALID_ARG before any HIP call)."""
+its level-by-level rebuild against the node-by-node one, the host build of the replay's uniforms against plan_host.philox4x32, the
+precondition of the device draw test, and the argument checks of the new entry points (every one answers BLE_E_INVALID_ARG before any
+HIP call)."""
 import ctypes
 
 import numpy as np
 import pytest
 
+import plan_host
 import prio_replay_host as ph
 from balloon_learning_environment_amd import _abi, _lib
 
@@ -50,6 +53,91 @@ def test_stratified_walk_by_hand():
   tr.nodes[tr.P:tr.P + 4] = [0.0, 0.0, 0.0, 5.0]
   tr.rebuild()
   assert tr.find(0.0) == 3 and tr.find(7.0) == 3
+
+
+def test_rebuild_level_by_level_gives_the_node_by_node_bits():
+  """A random tree with padded leaves (5 x 13 = 65 leaves in 128) and some empty leaves, values that round in every sum."""
+  rng = np.random.default_rng(0)
+  a, b = ph.SumTree(5, 13, 2), ph.SumTree(5, 13, 2)
+  assert a.P == 128 and a.leaves == 65
+  leaves = np.where(rng.random(65) < 0.2, 0.0, np.sqrt(rng.random(65) * 4))
+  for tr in (a, b):
+    tr.nodes[:] = rng.random(2 * tr.P)                    # stale parents, and a stale node 0 that neither form touches
+    tr.nodes[tr.P:] = 0.0
+    tr.nodes[tr.P:tr.P + 65] = leaves
+  b.nodes[:b.P] = a.nodes[:a.P]
+  a.rebuild()
+  b.rebuild_node_by_node()
+  assert np.array_equal(a.nodes, b.nodes)
+  assert a.nodes[1] > 0 and a.nodes[1] != float(np.float32(a.nodes[1]))
+  assert not a.nodes[a.P + 65:].any()
+
+
+def test_windows_valid_is_window_valid_per_environment():
+  rng = np.random.default_rng(1)
+  term = (rng.random((7, 40)) < 0.15).astype(np.uint8)
+  end = np.maximum(term, (rng.random((7, 40)) < 0.15).astype(np.uint8))
+  for t in range(14):
+    for n in (1, 3, 5):
+      want = [ph.window_valid(term, end, t, e, n) for e in range(40)]
+      assert np.array_equal(ph.windows_valid(term, end, t, n), want), (t, n)
+
+
+def test_find_candidates():
+  tr = ph.SumTree(2, 2, 1)
+  tr.nodes[tr.P:tr.P + 4] = [1.0, 0.5, 2.0, 1.0]
+  tr.rebuild()
+  assert tr.find_candidates(0.5) == {0} and tr.find_candidates(3.0) == {2}
+  assert tr.find_candidates(1.0) == {0, 1} and tr.find_candidates(float(np.nextafter(1.5, 0.0))) == {1, 2}
+  q = tr.stratified_queries(np.array([0.5, 0.25, 0.0]))                   # total 4.5, three strata of 1.5
+  assert np.array_equal(q, [0.75, 1.875, 3.0])
+
+
+@pytest.fixture(scope='module')
+def draws(tmp_path_factory):
+  return ph.build_replay_draws(tmp_path_factory.mktemp('rpd'))
+
+
+@pytest.mark.parametrize('seed,b,counter', [(0, 0, 0), (11, 1, 0), (11, 64, 1), (0xFEDCBA9876543210, 3000, 7), (11, 5, 2 ** 32),
+                                            (11, 5, 2 ** 32 + 3), (3, 70000, 0xABCDEF0123456789)])
+def test_replay_draws_are_philox4x32(draws, seed, b, counter):
+  """Row b's stream: key = the seed's words, counter block j = (j, counter low, b, counter high); the words are used from the last to
+  the first, two per uniform (high word first), 53 bits."""
+  tries = 5
+  got = draws(seed, b + 1, counter, tries)[b]
+  key = np.array([seed & 0xFFFFFFFF, seed >> 32], np.uint64)
+  words = []
+  for j in range(3):
+    out = plan_host.philox4x32(np.array([j, counter & 0xFFFFFFFF, b & 0xFFFFFFFF, counter >> 32], np.uint64), key)
+    words += [int(w) for w in out[::-1]]
+  want = [(((words[2 * k] << 32) | words[2 * k + 1]) >> 11) / 2.0 ** 53 for k in range(tries)]
+  assert got.tolist() == want
+  assert all(0.0 <= u < 1.0 for u in want) and len(set(want)) == tries
+  if counter >= 2 ** 32:                                                   # the high word is part of the key
+    assert draws(seed, b + 1, counter & 0xFFFFFFFF, tries)[b].tolist() != want
+
+
+def test_draw_case_rows_have_one_candidate_leaf(draws):
+  """What test_gpu_prio_replay.py's draw test needs of its inputs: at every batch size and counter, every row's query and its two
+  neighbours walk to one leaf, and that leaf is a complete valid window -- so the device's leaf is determined whether or not it fuses a
+  product, and no row needs a second draw."""
+  c = ph.DRAW_CASE
+  h = ph.history(c['steps'], c['num_envs'], c['hist_seed'], obs=False, distinct_rewards=True)
+  fed, tree = ph.draw_case_tree(h)
+  last, lv = c['steps'] - 1, tree.leaf_view()
+  assert (fed.leaf_view() > 0).sum() > 300 and np.array_equal(fed.leaf_view() > 0, lv > 0)
+  for row in range(c['capacity']):
+    t = ph.newest_step(last, c['capacity'], row)
+    ok = np.array([t + c['horizon'] <= last and ph.window_valid(h['terminal'], h['episode_end'], t, e, c['horizon'])
+                   for e in range(c['num_envs'])]) if t + c['horizon'] <= last else np.zeros(c['num_envs'], bool)
+    assert np.array_equal(lv[row] > 0, ok), row
+  for b in c['batches']:
+    for counter in c['counters']:
+      q = tree.stratified_queries(draws(c['seed'], b, counter)[:, 0])
+      for i in range(b):
+        cand = tree.find_candidates(float(q[i]))
+        assert len(cand) == 1, (b, counter, i, cand)
+        assert tree.nodes[tree.P + next(iter(cand))] > 0
 
 
 def test_weighted_loss_formula():
