@@ -137,6 +137,33 @@ class BlePlanSelect(ctypes.Structure):
               ('action', ctypes.c_void_p), ('elite_counts', ctypes.c_void_p), ('advance_counter', ctypes.c_void_p)]
 
 
+SCENARIO_MAX = 16           # BLE_SCENARIO_MAX
+
+
+def gp_scenario_doubles(num: int) -> int:
+  """BLE_GP_SCENARIO_DOUBLES(num): the window's 120 x 4 coordinates, then 120 x 2 weights per scenario."""
+  return 480 + 240 * int(num)
+
+
+class BleGpScenarios(ctypes.Structure):
+  """struct ble_gp_scenarios: num scenario winds per environment (ble_gp_fit_scenarios_f32): the slab [n][stride] of float64 and
+  n_obs [n] int32, device pointers, the number of environments and the number of scenarios."""
+  _fields_ = [('slab', ctypes.c_void_p), ('stride', ctypes.c_int64), ('n_obs', ctypes.c_void_p), ('n', ctypes.c_int64),
+              ('num', ctypes.c_int32), ('reserved_', ctypes.c_int32)]
+
+
+class BleScenarioGen(ctypes.Structure):
+  """struct ble_scenario_gen: where the scenario streams come from: the batch's seed and env_offset, or a device seed per environment;
+  the device episode counters."""
+  _fields_ = [('seed', ctypes.c_uint64), ('env_seed', ctypes.c_void_p), ('episode', ctypes.c_void_p), ('env_offset', ctypes.c_int64)]
+
+
+class BlePlanRisk(ctypes.Structure):
+  """struct ble_plan_risk: ret [n][K][M] -> score [n][K], the mean of the `tail` smallest scenario returns (device pointers)."""
+  _fields_ = [('n', ctypes.c_int64), ('n_plans', ctypes.c_int32), ('num', ctypes.c_int32), ('tail', ctypes.c_int32),
+              ('reserved_', ctypes.c_int32), ('ret', ctypes.c_void_p), ('score', ctypes.c_void_p)]
+
+
 class BleNoiseGen(ctypes.Structure):
   """struct ble_noise_gen: the wind-noise generator of a fused rollout (ble_step_n_f32, ABI 3)."""
   _fields_ = [('seed', ctypes.c_uint64), ('episode', ctypes.c_void_p), ('harmonic_cache', ctypes.c_void_p),

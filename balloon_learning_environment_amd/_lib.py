@@ -19,7 +19,7 @@ from balloon_learning_environment_amd import _abi
 _PKG_DIR = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get('BLE_HIP_LIB') or os.path.join(_PKG_DIR, 'libble_hip.so')   # override: experiments only
 _SOURCES = [os.path.join(_PKG_DIR, 'csrc', f) for f in ('ble_kernels.hip', 'ble_step_core.h', 'ble_physics.h', 'ble_intrinsics.h', 'ble_reset.h',
-                                                          'ble_observe.h', 'ble_gp_query.h', 'ble_rollout.h', 'ble_gp_belief.h', 'ble_plan.h', 'ble_noise.h', 'ble_decode.h', 'ble_step_split.h', 'ble_step_helper.h', 'ble_agent.h', 'ble_qnet.h',
+                                                          'ble_observe.h', 'ble_gp_query.h', 'ble_rollout.h', 'ble_gp_belief.h', 'ble_plan.h', 'ble_scenarios.h', 'ble_noise.h', 'ble_decode.h', 'ble_step_split.h', 'ble_step_helper.h', 'ble_agent.h', 'ble_qnet.h',
                                                           'ble_train.h', 'ble_replay.h', 'ble_explore.h')]
 _HEADER = os.path.join(os.path.dirname(_PKG_DIR), 'include', 'ble_abi.h')
 
@@ -48,11 +48,13 @@ EXPORTS = ('ble_abi_version', 'ble_noise_primitive_version', 'ble_vehicle_defaul
            'ble_qnet_unpack_f32', 'ble_replay_sample_f32', 'ble_qnet_train_workspace_f32', 'ble_qnet_transpose_f32',
            'ble_qnet_train_step_f32', 'ble_qnet_explore_u8', 'ble_qnet_td_workspace_f32', 'ble_qnet_td_step_f32',
            'ble_replay_tree_add_f64', 'ble_replay_sample_prioritized_f32', 'ble_replay_set_priority_f32', 'ble_marco_polo_u8', 'ble_gp_query_f32', 'ble_rollout_f32',
-           'ble_gp_fit_f32', 'ble_gp_belief_wind_f32', 'ble_rollout_belief_f32', 'ble_plan_sample_u8', 'ble_plan_select_f32')
+           'ble_gp_fit_f32', 'ble_gp_belief_wind_f32', 'ble_rollout_belief_f32', 'ble_plan_sample_u8', 'ble_plan_select_f32',
+           'ble_gp_fit_scenarios_f32', 'ble_gp_scenario_wind_f32', 'ble_rollout_scenarios_f32', 'ble_plan_risk_f32')
 # Exports added without a new ABI version: a library of this ABI built before them (BLE_HIP_LIB: the parent's, in A/B runs) still loads.
 # build() checks every name of EXPORTS on the library it builds.
 ADDITIVE_EXPORTS = ('ble_last_step_form', 'ble_gp_query_f32', 'ble_rollout_f32', 'ble_gp_fit_f32', 'ble_gp_belief_wind_f32',
-                    'ble_rollout_belief_f32', 'ble_plan_sample_u8', 'ble_plan_select_f32')
+                    'ble_rollout_belief_f32', 'ble_plan_sample_u8', 'ble_plan_select_f32', 'ble_gp_fit_scenarios_f32',
+                    'ble_gp_scenario_wind_f32', 'ble_rollout_scenarios_f32', 'ble_plan_risk_f32')
 
 
 class BleLibraryError(RuntimeError):
@@ -180,6 +182,12 @@ def lib():
   if hasattr(l, 'ble_plan_sample_u8'):   # the planner's two ends (sizes in the structs: no int64_t argument)
     l.ble_plan_sample_u8.argtypes = [ctypes.POINTER(_abi.BlePlanSample), _vp]
     l.ble_plan_select_f32.argtypes = [ctypes.POINTER(_abi.BlePlanSelect), _vp]
+  if hasattr(l, 'ble_gp_fit_scenarios_f32'):      # scenario winds (sizes in the structs: no int64_t argument)
+    scn, sgen = ctypes.POINTER(_abi.BleGpScenarios), ctypes.POINTER(_abi.BleScenarioGen)
+    l.ble_gp_fit_scenarios_f32.argtypes = [ctypes.POINTER(_abi.BleGpHistoryF32), _vp, _vp, scn, sgen, _vp, _vp]
+    l.ble_gp_scenario_wind_f32.argtypes = [scn, sgen, _vp, _vp, _vp, _vp, _vp, _int, _vp, _vp]
+    l.ble_rollout_scenarios_f32.argtypes = [st, ctypes.POINTER(_abi.BleRolloutF32), scn, sgen, _vp, _vp]
+    l.ble_plan_risk_f32.argtypes = [ctypes.POINTER(_abi.BlePlanRisk), _vp]
   for name in EXPORTS:
     if hasattr(l, name) or name not in ADDITIVE_EXPORTS:
       getattr(l, name).restype = _int

@@ -1,8 +1,8 @@
 """A model-predictive agent that plans entirely on the device (no counterpart in the reference).
 
 Per decision: sample K piecewise-constant action plans per environment (`ble_plan_sample_u8`), fly them from the state where each
-balloon lies with the look-ahead kernels (`VecSimulator.rollout_plans`: `ble_rollout_f32` / `ble_rollout_belief_f32`), pick the best
-plan (`ble_plan_select_f32`) -- optionally refined by cross-entropy iterations: the next iteration samples around the elite plans of
+balloon lies with the look-ahead kernels (`VecSimulator.rollout_plans`: `ble_rollout_f32` / `ble_rollout_belief_f32` /
+`ble_rollout_scenarios_f32`, the last followed by `ble_plan_risk_f32`), pick the best (`ble_plan_select_f32`) -- optionally refined by cross-entropy iterations: the next iteration samples around the elite plans of
 this one -- and emit the plan's first action.  No host synchronisation anywhere, so a decision is capturable in the same HIP graph
 as the step.  The agent needs no trained weights; it needs the simulator, which `bind` attaches (eval_lib.VecEvaluator does that for
 any agent with a `bind`; `VecBalloonEnv.planner()` returns a bound agent).
@@ -17,7 +17,7 @@ from balloon_learning_environment_amd import _lib
 from balloon_learning_environment_amd import device as dev
 from balloon_learning_environment_amd import vec_state
 
-WINDS = ('belief', 'forecast', 'truth')
+WINDS = ('belief', 'forecast', 'truth', 'scenarios')
 STAY = 1
 
 
@@ -28,7 +28,11 @@ class VecLookaheadAgent:
   (H * action_repeat <= 960); a plan is constant over `segment` entries.  gamma: the discount of a plan's return.
   wind: 'belief' (default) -- forecast + the mean of the WindGP over the balloon's own measurements, fitted at every decision: all an
   agent may legitimately know; 'forecast' -- the forecast alone; 'truth' -- the wind the environments will fly (bind(noise_seed=)):
-  a simulator-side upper bound.  iterations (<= 16): 1 picks the best of K; more refine by cross-entropy, each iteration drawing
+  a simulator-side upper bound; 'scenarios' -- forecast + each of num_scenarios (<= 16) winds sampled from the WindGP's posterior (a draw
+  of the noise field conditioned on the measurements), fitted at every decision; the scenarios themselves are fixed over an
+  episode (common random numbers: only the conditioning moves).  A plan's score is then the mean of its risk_tail smallest scenario
+  returns: None = all of them, the expectation; 1 = the worst case; between them a CVaR.  The scenario streams are keyed by `seed`, or
+  with bind(seeds=) by each environment's own seed.  iterations (<= 16): 1 picks the best of K; more refine by cross-entropy, each iteration drawing
   every segment's action with probability (c_a + 1) / (E + 3) from the counts c_a of the E = min(elite, K) best plans of the one
   before, the best plan so far always kept.  Iteration 0 always holds all-STAY, all-DOWN, all-UP and the previous decision's best
   plan shifted by one entry (as far as K reaches).  seed: the plans' Philox streams are keyed by (seed, environment, decision
@@ -37,9 +41,14 @@ class VecLookaheadAgent:
 
   def __init__(self, num_plans: int = 64, horizon: int = 24, action_repeat: int = 1, segment: int = 4, gamma: float = 0.993,
                wind: str = 'belief', iterations: int = 1, elite: int = 8, seed: int = 0, device='cuda:0',
-               substeps: int = vec_state.SUBSTEPS):
+               substeps: int = vec_state.SUBSTEPS, num_scenarios: int = 8, risk_tail: Optional[int] = None):
     if wind not in WINDS:
-      raise ValueError(f"VecLookaheadAgent: wind is 'belief', 'forecast' or 'truth', not {wind!r}")
+      raise ValueError(f"VecLookaheadAgent: wind is 'belief', 'forecast', 'truth' or 'scenarios', not {wind!r}")
+    self.num_scenarios = int(num_scenarios) if wind == 'scenarios' else 0
+    self.risk_tail = self.num_scenarios if risk_tail is None else int(risk_tail)
+    if wind == 'scenarios' and not (1 <= self.num_scenarios <= _abi.SCENARIO_MAX and 1 <= self.risk_tail <= self.num_scenarios):
+      raise ValueError(f'VecLookaheadAgent: 1 <= num_scenarios <= {_abi.SCENARIO_MAX} and 1 <= risk_tail <= num_scenarios, '
+                       f'not {num_scenarios}, {risk_tail}')
     if not 1 <= int(num_plans) <= _abi.PLAN_MAX_PLANS:
       raise ValueError(f'VecLookaheadAgent: 1 <= num_plans <= {_abi.PLAN_MAX_PLANS}, not {num_plans}')
     if int(horizon) < 1 or int(action_repeat) < 1 or int(horizon) * int(action_repeat) > _abi.ROLLOUT_MAX_STEPS:
@@ -78,8 +87,8 @@ class VecLookaheadAgent:
         raise ValueError("VecLookaheadAgent: wind='truth' with per-environment seeds: the look-ahead's noise generator takes one seed")
       assert seeds.dtype in (torch.int64, torch.uint64) and seeds.is_contiguous() and tuple(seeds.shape) == (sim.n,), seeds.shape
       assert seeds.device == self.device
-    if sim.n * self.num_plans >= 2 ** 31:
-      raise ValueError(f'VecLookaheadAgent: n * num_plans < 2^31, not {sim.n} x {self.num_plans}')
+    if sim.n * self.num_plans * max(self.num_scenarios, 1) >= 2 ** 31:
+      raise ValueError(f'VecLookaheadAgent: n * num_plans * num_scenarios < 2^31, not {sim.n} x {self.num_plans} x {max(self.num_scenarios, 1)}')
     same = self.sim is sim and self._seeds is seeds
     self.sim, self._seeds, self._noise_seed = sim, seeds, noise_seed
     if not same:
@@ -95,6 +104,11 @@ class VecLookaheadAgent:
       self._belief = None
       if self.wind == 'belief':
         self._belief = vec_state.WindBelief(z(torch.float64, n, _lib.GP_BELIEF_DOUBLES), z(torch.int32, n))
+      self._scenarios = None
+      if self.wind == 'scenarios':
+        m = self.num_scenarios
+        self._scenarios = vec_state.WindScenarios(z(torch.float64, n, _abi.gp_scenario_doubles(m)), z(torch.int32, n), m, self.seed, seeds)
+        self.scenario_returns, self.scenario_steps = z(torch.float32, n, k, m), z(torch.int32, n, k, m)
     self.counter.zero_()
     self.best_plan.fill_(STAY)
     self.best_return.zero_()
@@ -121,9 +135,11 @@ class VecLookaheadAgent:
       out = self.action
     assert out.dtype == torch.uint8 and out.is_contiguous() and out.numel() == n and out.device == self.device
     stream = dev.stream_ptr(self.device)
-    belief, noise_seed = None, None
+    belief, noise_seed, scenarios = None, None, None
     if self.wind == 'belief':
       belief = sim.fit_wind_belief(out=self._belief)
+    elif self.wind == 'scenarios':
+      scenarios = sim.fit_wind_scenarios(self.num_scenarios, seed=self.seed, seeds=self._seeds, out=self._scenarios)
     elif self.wind == 'truth':
       noise_seed = self._noise_seed() if callable(self._noise_seed) else self._noise_seed
     rollout_out = (self.returns, self.steps_flown, None, None)
@@ -133,7 +149,12 @@ class VecLookaheadAgent:
                               0 if self._seeds is not None else sim.env_offset, self.counter.data_ptr(), self.elite_counts.data_ptr(),
                               self.best_plan.data_ptr(), self.plans.data_ptr())
       _lib.check(self.lib.ble_plan_sample_u8(ctypes.byref(ps), stream), 'ble_plan_sample_u8')
-      sim.rollout_plans(self.plans, self.gamma, self.action_repeat, noise_seed, self.substeps, out=rollout_out, belief=belief)
+      if scenarios is not None:      # every plan in every scenario wind, then one score per plan: the selection below runs on the scores
+        sim.rollout_plans(self.plans, self.gamma, self.action_repeat, None, self.substeps,
+                          out=(self.scenario_returns, self.scenario_steps, None, None), scenarios=scenarios)
+        sim.plan_risk(self.scenario_returns, self.risk_tail, out=self.returns)
+      else:
+        sim.rollout_plans(self.plans, self.gamma, self.action_repeat, noise_seed, self.substeps, out=rollout_out, belief=belief)
       # (the elite counts are the next iteration's: the last selection writes none, and moves the decision counter on)
       sel = _abi.BlePlanSelect(n, self.num_plans, self.horizon, self.segment, it, 0 if last else self.elite, 0, self.returns.data_ptr(),
                                self.plans.data_ptr(), self.best_return.data_ptr(), self.best_k.data_ptr(), self.best_plan.data_ptr(),

@@ -818,6 +818,9 @@ __global__ __launch_bounds__(256) void ble_eval_accumulate_kernel(StateDev st, c
 // the fitted WindGP kept on the device, its mean as a lane function, and the look-ahead flown in it: after ble_rollout.h (RolloutArgs)
 #include "ble_gp_belief.h"
 #include "ble_plan.h"
+// scenario winds (a prior draw of the noise field conditioned on the measurements), the look-ahead flown in them and the risk score: after
+// ble_gp_belief.h (belief_wave_trip) and ScalarSeed / EnvSeed
+#include "ble_scenarios.h"
 // fp64 primitive probe (test-only entry point): op 0 rcp seed, 1 d_rcp, 2 rsq seed, 3 d_rsqrt,
 // 4 d_sqrt_fast, 5 d_log_fast, 6 d_exp_fast, 7 sin (sincos_f64), 8 cos (sincos_f64)
 __global__ __launch_bounds__(256) void probe_f64_kernel(const double* x, double* y, int op, int64_t n) {
@@ -1093,6 +1096,26 @@ inline bool gp_belief(const ble_gp_belief* belief, BeliefDev* b) {
   return true;
 }
 static_assert(kBeliefDoubles == BLE_GP_BELIEF_DOUBLES, "ble_gp_belief.h and ble_abi.h disagree on the slab");
+
+// ble_gp_scenarios -> the kernels' ScenariosDev; false for a missing array, a scenario count outside 1 .. BLE_SCENARIO_MAX, a slab that is
+// not 16-byte aligned or a stride that is too short for that count or odd
+inline bool gp_scenarios(const ble_gp_scenarios* scn, ScenariosDev* b) {
+  if (!scn || !scn->slab || !scn->n_obs || scn->num < 1 || scn->num > BLE_SCENARIO_MAX || scn->stride < (int64_t)BLE_GP_SCENARIO_DOUBLES(scn->num) ||
+      (scn->stride & 1) != 0 || (reinterpret_cast<uintptr_t>(scn->slab) & 15u) != 0 || scn->n < 0 || scn->n >= 2147483648LL)
+    return false;
+  *b = ScenariosDev{scn->slab, scn->stride, scn->n_obs, scn->num};
+  return true;
+}
+inline bool scenario_gen_ok(const ble_scenario_gen* gen) { return gen != nullptr && gen->env_offset >= 0; }
+// The seed source of a scenario generator, handed to f as the kernels' S: EnvSeed (env_seed given: every stream keyed as environment 0) or
+// ScalarSeed (streams keyed by env_offset + e)
+template <class F>
+int with_scenario_seed(const ble_scenario_gen* gen, F&& f) {
+  if (gen->env_seed != nullptr) return f(EnvSeed{gen->env_seed}, ScenarioGen{gen->episode, 0});
+  return f(ScalarSeed{gen->seed}, ScenarioGen{gen->episode, gen->env_offset});
+}
+static_assert(kScenarioMax == BLE_SCENARIO_MAX && BLE_GP_SCENARIO_DOUBLES(3) == kBeliefAlphaAt + 3 * kScenarioAlphaDoubles,
+              "ble_scenarios.h and ble_abi.h disagree on the slab");
 
 }  // namespace
 
@@ -1797,6 +1820,62 @@ int ble_plan_select_f32(const struct ble_plan_select* sel, void* stream) {
   const PlanSelectArgs a{sel->n, sel->n_plans, sel->n_plan_steps, sel->segment, sel->iteration, sel->elite, sel->ret, sel->plans,
                          sel->best_return, sel->best_k, sel->best_plan, sel->action, sel->elite_counts, sel->advance_counter};
   return launch(ble_plan_select_kernel, sel->n, 1, kPlanSelectBlock, stream, a);
+}
+
+int ble_gp_fit_scenarios_f32(const ble_gp_history_f32* hist, const uint8_t* reset_mask, const int32_t* time_s, const ble_gp_scenarios* scn,
+                             const ble_scenario_gen* gen, uint32_t* err_flags, void* stream) {
+  ScenariosDev b;
+  if (!hist || !hist->xyp || !hist->elapsed_s || !hist->err_uv || !hist->count || !time_s || !gp_scenarios(scn, &b) || !scenario_gen_ok(gen))
+    return BLE_E_INVALID_ARG;
+  const GpHistory h{hist->xyp, hist->elapsed_s, hist->err_uv, hist->count, nullptr, nullptr, 0};
+  return with_scenario_seed(gen, [&](auto seed, ScenarioGen g) {
+    return launch(ble_gp_fit_scenarios_kernel<decltype(seed)>, scn->n, 1, kObsBlock, stream, h, reset_mask, time_s, b, seed, g, err_flags);
+  });
+}
+
+int ble_gp_scenario_wind_f32(const ble_gp_scenarios* scn, const ble_scenario_gen* gen, const int32_t* scenario_index, const float* x_m,
+                             const float* y_m, const float* pressure, const int32_t* elapsed_s, int prior_only, float* uv, void* stream) {
+  ScenariosDev b;
+  if (!gp_scenarios(scn, &b) || !scenario_gen_ok(gen) || !scenario_index || !x_m || !y_m || !pressure || !elapsed_s || !uv ||
+      (prior_only != 0 && prior_only != 1))
+    return BLE_E_INVALID_ARG;
+  const int64_t n = scn->n;
+  return with_scenario_seed(gen, [&](auto seed, ScenarioGen g) {
+    return launch(ble_gp_scenario_wind_kernel<decltype(seed)>, n, kScenarioWindBlock, kScenarioWindBlock, stream, b, seed, g, scenario_index, x_m,
+                  y_m, pressure, elapsed_s, prior_only, uv, n);
+  });
+}
+
+int ble_rollout_scenarios_f32(const ble_state_f32* st, const struct ble_rollout_f32* ro, const ble_gp_scenarios* scn,
+                              const ble_scenario_gen* gen, uint32_t* err_flags, void* stream) {
+  ScenariosDev b;
+  if (!state_ok(st) || !ro || !ro->plans || !ro->wind_grid || !ro->ret || !ro->steps_flown || !gp_scenarios(scn, &b) || !scenario_gen_ok(gen))
+    return BLE_E_INVALID_ARG;
+  if (ro->n < 0 || ro->n >= 2147483648LL || ro->n_plans < 1 || ro->n * (int64_t)ro->n_plans >= 2147483648LL ||
+      ro->n * (int64_t)ro->n_plans * scn->num >= 2147483648LL || ro->n_plan_steps < 1 || ro->action_repeat < 1 ||
+      (int64_t)ro->n_plan_steps * ro->action_repeat > BLE_ROLLOUT_MAX_STEPS)
+    return BLE_E_INVALID_ARG;
+  if (ro->substeps < 1 || ro->substeps > BLE_MAX_SUBSTEPS || ro->grid_env_stride < 0 || !(ro->gamma >= 0.0 && ro->gamma <= 1.0) ||
+      scn->n != ro->n)                                                // (scenarios of another batch would be read out of bounds)
+    return BLE_E_INVALID_ARG;
+  return with_vehicle<false>(st, nullptr, [&](auto veh) {
+    if (ro->n == 0) return BLE_OK;
+    const RolloutArgs a{ro->n, ro->n_plans, ro->n_plan_steps, ro->action_repeat, ro->substeps, ro->gamma, ro->plans, ro->wind_grid,
+                        ro->grid_env_stride, ro->ret, ro->steps_flown, ro->reward, ro->final_state};
+    return with_scenario_seed(gen, [&](auto seed, ScenarioGen g) {
+      return launch(ble_rollout_scenarios_kernel<decltype(veh), decltype(seed)>, ro->n * (int64_t)ro->n_plans * scn->num, kStepBlock, kStepBlock,
+                    stream, state_dev(st), a, b, seed, g, err_flags, veh);
+    });
+  });
+}
+
+int ble_plan_risk_f32(const struct ble_plan_risk* risk, void* stream) {
+  if (!risk || !risk->ret || !risk->score || risk->n < 0 || risk->n >= 2147483648LL || risk->n_plans < 1 || risk->n_plans > BLE_PLAN_MAX_PLANS ||
+      risk->num < 1 || risk->num > BLE_SCENARIO_MAX || risk->tail < 1 || risk->tail > risk->num ||
+      risk->n * (int64_t)risk->n_plans * risk->num >= 2147483648LL)
+    return BLE_E_INVALID_ARG;
+  const PlanRiskArgs a{risk->n, risk->n_plans, risk->num, risk->tail, risk->ret, risk->score};
+  return launch(ble_plan_risk_kernel, risk->n * (int64_t)risk->n_plans, 256, 256, stream, a);
 }
 
 }  // extern "C"

@@ -1,0 +1,554 @@
+// ble_scenarios.h -- plan against SAMPLED winds: M scenario winds per environment, each a draw of the noise field the
+// WindGP models, corrected so that it passes through the balloon's own measurements (pathwise conditioning, Matheron's rule):
+//
+//     error_m(x) = f_m(x) + sum_i k(loc_i, x) alpha^m_i,      alpha^m = (K + 0.05 I)^-1 (y - f_m(X))
+//
+// f_m: wind_noise_from_rows (ble_noise.h, unchanged bits) over harmonics drawn from the scenario stream of (e, m); X, y, K: the window
+// frozen at the anchor, as ble_gp_fit_kernel takes it; k: gp_belief_kernel.  The sum of the two terms is ONE fp32 addition of two fp32
+// values: the noise value and the correction rounded as gp_belief_mean rounds.
+//
+//   ble_gp_fit_scenarios_kernel   one workgroup (4 waves) per environment: phases 0-1 of ble_gp_fit_kernel (window, K, L, W = L^-1), then
+//                                 for each m: f_m at the window's points, the residual y - f_m, phase 2 -> alpha^m.  A copy of those
+//                                 phases, on purpose: ble_gp_fit_kernel keeps its instructions.
+//   gp_scenario_correction        gp_belief_mean with loc and alpha as two pointers (a copy, for the same reason).
+//   ble_gp_scenario_wind_kernel   one lane per environment at caller-chosen points and a scenario index per environment: what
+//                                 ble_step_f32 takes as noise_uv.  prior_only: f_m alone.
+//   ble_rollout_scenarios_kernel  ble_rollout_belief_kernel's body, one lane per (e, k, m), j = (e K + k) M + m.
+//   ble_plan_risk_kernel          one lane per (e, k): ret [n][K][M] -> score [n][K], the mean of the `tail` smallest scenario returns.
+//
+// The slab of an environment (stride doubles, 16-byte aligned, stride >= 480 + 240 M and even):
+//   [0, 480)                       loc[120][4], exactly ble_gp_fit_kernel's
+//   [480 + 240 m, 480 + 240 (m+1)) alpha^m[120][2], u and v interleaved
+// Everything beyond the window is zero (the note in ble_gp_belief.h: any trip count that covers n_obs gives the same bits).
+//
+// The stream, the risk order and the score build on the host as well (tests/emul/scenario_emul.cpp).
+#pragma once
+#include "ble_noise.h"
+#include "ble_gp_belief.h"
+
+namespace ble {
+
+constexpr int kScenarioMax = 16;                                  // BLE_SCENARIO_MAX
+constexpr unsigned long long kScenarioKey = 0x5343454E4152ull;    // "SCENAR": no scenario stream is the truth's (seed ^ 0x5EEDF00D)
+constexpr int kScenarioBlocks = 32;                               // Philox blocks per scenario: ten harmonics take 90 words = 23 blocks
+constexpr int kScenarioAlphaDoubles = 2 * kBeliefRows;            // 240
+BLE_FN int scenario_slab_doubles(int num) { return kBeliefAlphaAt + kScenarioAlphaDoubles * num; }
+
+// The generator of scenario m of an environment at its first block: the noise's own construction -- philox_init(seed ^ key constant,
+// the environment's key, episode) -- with the key constant kScenarioKey and the block counter started at 32 m.  A function of
+// (seed, key, episode, m) alone.
+BLE_FN Philox scenario_stream(uint64_t seed, uint64_t key, uint32_t episode, int m) {
+  Philox g = philox_init(seed ^ kScenarioKey, key, episode);
+  g.c0 = (uint32_t)(m * kScenarioBlocks);
+  return g;
+}
+// Harmonic k = 5 comp + h of that scenario, without drawing the ones before it: harmonic k starts at word 9 k of the stream (one
+// seed word and four 53-bit uniforms of two words each), i.e. in block 9 k / 4 with 9 k % 4 of its words already taken.
+BLE_FN HarmonicDraw scenario_harmonic(uint64_t seed, uint64_t key, uint32_t episode, int m, int k) {
+  Philox g = scenario_stream(seed, key, episode, m);
+  g.c0 += (uint32_t)((9 * k) >> 2);
+  philox_refill(g);
+  g.have = 4 - ((9 * k) & 3);
+  return harmonic_draw(g);
+}
+// The 50 words of scenario m into `dst`, `dst_stride` apart (rows 5 k .. 5 k + 4 = (seed, ox, oy, op, ot) of harmonic k): the layout
+// wind_noise_from_rows reads.  Drawn in order from one generator: the same words as scenario_harmonic's.
+BLE_FN void scenario_draws_fetch(uint64_t seed, uint64_t key, uint32_t episode, int m, uint32_t* dst, int64_t dst_stride) {
+  Philox g = scenario_stream(seed, key, episode, m);
+#pragma unroll 1
+  for (int k = 0; k < 10; ++k) {
+    const HarmonicDraw d = harmonic_draw(g);
+    uint32_t* o = dst + (int64_t)(5 * k) * dst_stride;
+    o[0] = d.hseed; o[dst_stride] = float_bits_u32(d.ox); o[2 * dst_stride] = float_bits_u32(d.oy);
+    o[3 * dst_stride] = float_bits_u32(d.op); o[4 * dst_stride] = float_bits_u32(d.ot);
+  }
+}
+
+// One component of wind_noise_from_rows: the same calls in the same order, hence the same bits as out[comp] there.
+BLE_FN float wind_noise_component_from_rows(int comp, float x_m, float y_m, float pressure, int32_t elapsed_s, const uint32_t* rows,
+                                            int64_t stride, const float* lut) {
+  BLE_NO_CONTRACT
+  float x_km, y_km, t_h;
+  noise_coords(x_m, y_m, elapsed_s, &x_km, &y_km, &t_h);
+  NoiseAccumulator a;
+#pragma unroll 1
+  for (int h = 0; h < 5; ++h)
+    noise_add_harmonic(a, comp, h, harmonic_draw_from_rows(rows, stride, 5 * comp + h), x_km, y_km, pressure, t_h, lut);
+  return noise_finish(a);
+}
+
+// gp_belief_mean with the window and the weights as two pointers (alpha^m lies 240 m doubles behind the belief's place): the same
+// loop, the same d_fma chain, rounded to fp32 once.  n_obs 0: exactly +0.0f; < 0: NaN.
+BLE_FN void gp_scenario_correction(const double* __restrict__ loc_, const double* __restrict__ alpha_, int n_obs, int n_trip, float x,
+                                   float y, float p, int32_t t_elapsed_s, const double* tab, float* u, float* v) {
+  const double* loc = (const double*)__builtin_assume_aligned(loc_, 16);
+  const double* alpha = (const double*)__builtin_assume_aligned(alpha_, 16);
+  const double xq = (double)x * kBeliefScaleXY, yq = (double)y * kBeliefScaleXY, pq = (double)p * kBeliefScaleP,
+               tq = (double)t_elapsed_s * kBeliefScaleT;
+  double su = 0.0, sv = 0.0;
+#pragma unroll 1
+  for (int i0 = 0; i0 < n_trip; i0 += 4) {
+    double k[4];
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      const double* l = loc + 4 * (i0 + r);
+      k[r] = gp_belief_kernel(l[0] - xq, l[1] - yq, l[2] - pq, l[3] - tq, tab);
+    }
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {                             // (i ascending: one fixed order)
+      su = d_fma(k[r], alpha[2 * (i0 + r)], su);
+      sv = d_fma(k[r], alpha[2 * (i0 + r) + 1], sv);
+    }
+  }
+  const float fnan = __builtin_nanf("");
+  *u = n_obs < 0 ? fnan : (n_obs == 0 ? 0.0f : (float)su);
+  *v = n_obs < 0 ? fnan : (n_obs == 0 ? 0.0f : (float)sv);
+}
+
+// ---------------------------------------------------------------------------------------------------------------- the risk score
+// The ascending sort key of a FINITE return (-0 counts as +0): key(a) < key(b) <=> a < b.
+BLE_FN uint32_t risk_key(float ret) {
+  uint32_t u = float_bits_u32(ret);
+  if (u == 0x80000000u) u = 0u;
+  return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+}
+BLE_FN bool risk_finite(float ret) { return (float_bits_u32(ret) & 0x7F800000u) != 0x7F800000u; }
+// scenario j comes before scenario m: the smaller return, then the smaller index
+BLE_FN bool risk_before(uint32_t key_j, int j, uint32_t key_m, int m) { return key_j < key_m || (key_j == key_m && j < m); }
+// The ranks of the M <= 16 returns at ret[0], ret[stride], ..., four bits each: nibble m = the number of scenarios in front of m.
+// Counted, as plan_rank counts; kept in one 64-bit word, so nothing is indexed at run time but the memory `ret` points to.
+BLE_FN uint64_t risk_ranks(const float* ret, int64_t stride, int num) {
+  uint64_t ranks = 0;
+#pragma unroll 1
+  for (int m = 0; m < num; ++m) {
+    const uint32_t mine = risk_key(ret[m * stride]);
+    uint64_t rank = 0;
+#pragma unroll 1
+    for (int j = 0; j < num; ++j) rank += risk_before(risk_key(ret[j * stride]), j, mine, m) ? 1u : 0u;
+    ranks |= rank << (4 * m);
+  }
+  return ranks;
+}
+// The mean of the `tail` smallest of the M returns: summed in fp64 in rank order from 0.0, divided once, rounded to fp32 once.  Any
+// non-finite return among the M: NaN (plan_key puts the plan last).  1 <= tail <= num <= 16.
+BLE_FN float plan_risk_score(const float* ret, int64_t stride, int num, int tail) {
+  bool finite = true;
+#pragma unroll 1
+  for (int m = 0; m < num; ++m) finite = finite && risk_finite(ret[m * stride]);
+  if (!finite) return __builtin_nanf("");
+  const uint64_t ranks = risk_ranks(ret, stride, num);
+  double sum = 0.0;
+#pragma unroll 1
+  for (int r = 0; r < tail; ++r) {
+#pragma unroll 1
+    for (int m = 0; m < num; ++m)
+      if ((int)((ranks >> (4 * m)) & 15u) == r) sum += (double)ret[m * stride];     // (ranks are a permutation: exactly one m)
+  }
+  return (float)(sum / (double)tail);
+}
+
+}  // namespace ble
+
+#if defined(__HIPCC__)
+// ---------------------------------------------------------------------------------------------------------------- the kernels
+// Included by ble_kernels.hip after ble_plan.h: ScalarSeed / EnvSeed, GpQueryShared, RolloutArgs, belief_wave_trip, kStepBlock and
+// report_flags are there.
+namespace ble {
+
+// struct ble_gp_scenarios (include/ble_abi.h) as the kernels take it
+struct ScenariosDev {
+  double* slab;          // [n][stride]
+  int64_t stride;        // >= 480 + 240 num, even
+  int32_t* n_obs;        // [n]
+  int num;               // M: 1 .. kScenarioMax
+};
+// struct ble_scenario_gen without its seed (S carries it)
+struct ScenarioGen {
+  const uint32_t* __restrict__ episode;        // [n] or NULL: episode 0
+  int64_t env_offset;
+};
+
+// an environment without a posterior: a zero slab and n_obs (0: every scenario is its prior; -1: NaN)
+__device__ inline void gp_fit_scenarios_empty(const ScenariosDev& b, int64_t env, int tid, int n_obs) {
+  double* slab = b.slab + env * b.stride;
+  const int doubles = scenario_slab_doubles(b.num);
+  for (int q = tid; q < doubles; q += kObsBlock) slab[q] = 0.0;
+  if (tid == 0) b.n_obs[env] = n_obs;
+}
+
+// what the scenario fit keeps in LDS next to the factor
+struct ScenarioFitShared {
+  __attribute__((aligned(16))) float grad_lut[kGradLutFloats];
+  double y[2][kGpRows];                        // the measurements: sh.z is overwritten by every scenario's phase 2
+  float px[kGpRows], py[kGpRows], pp[kGpRows]; // the ring's own float32 x, y, p of the window's points
+  int32_t pt[kGpRows];                         // and its int32 t
+  uint32_t draws[kScenarioMax][50];            // the harmonic words of every scenario (row m: 50 words, stride 1)
+};
+static_assert(sizeof(GpQueryShared) + sizeof(ScenarioFitShared) <= 80 * 1024, "two workgroups per CU need <= 80 KB of LDS each");
+
+template <class S>
+__global__ __launch_bounds__(kObsBlock, 2) void ble_gp_fit_scenarios_kernel(GpHistory hist, const uint8_t* __restrict__ reset_mask,
+                                                                           const int32_t* __restrict__ time_s, ScenariosDev b, S seed,
+                                                                           ScenarioGen gen, uint32_t* err_flags) {
+  __shared__ GpQueryShared sh;
+  __shared__ ScenarioFitShared sc;
+  const int64_t env = blockIdx.x;
+  const int tid = threadIdx.x, lane = tid & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  uint32_t flags = 0;
+
+  // ---- phase 0: the window at the anchor time (ble_gp_fit_kernel's rules)
+  int count = hist.count[env];
+  if (reset_mask != nullptr && reset_mask[env] != 0) count = 0;       // a history restart is pending
+  const int32_t tq = time_s[env];
+  const int m = count < kGpCapacity ? count : kGpCapacity;
+  const float* h_xyp = hist.xyp + env * (kGpCapacity * 3);
+  const int32_t* h_t = hist.elapsed_s + env * kGpCapacity;
+  const float* h_err = hist.err_uv + env * (kGpCapacity * 2);
+  int32_t ta = tq, tb = tq;
+  if (lane < m) ta = h_t[(count - m + lane) % kGpCapacity];
+  if (lane + 64 < m) tb = h_t[(count - m + lane + 64) % kGpCapacity];
+  const int64_t age_a = (int64_t)ta - (int64_t)tq, age_b = (int64_t)tb - (int64_t)tq;
+  const unsigned long long b0 = __ballot(lane < m && (age_a < 0 ? -age_a : age_a) < kGpHorizonS);       // strict, like the reference
+  const unsigned long long b1 = __ballot(lane + 64 < m && (age_b < 0 ? -age_b : age_b) < kGpHorizonS);
+  int n_obs = __popcll(b0) + __popcll(b1);
+  int drop = 0;
+  if (n_obs > kGpMax) { drop = n_obs - kGpMax; n_obs = kGpMax; flags |= kFlagGpWindow; }
+  if (count > kGpCapacity && (b0 & 1ull) != 0) {
+    const int32_t t_newest = h_t[(count - 1) % kGpCapacity];
+    if (!(drop > 0 && tq >= t_newest)) {
+      if (tid == 0 && err_flags != nullptr) atomicOr(err_flags, (uint32_t)kFlagGpWindow);
+      gp_fit_scenarios_empty(b, env, tid, -1);
+      return;
+    }
+  }
+  if (n_obs == 0) {         // (uniform over the workgroup: no barrier has been reached)
+    gp_fit_scenarios_empty(b, env, tid, 0);
+    return;
+  }
+
+  // ---- compact the window into LDS (chronological), in units of the length scales; tables; the harmonics of every scenario
+  if (wave == 2) sh.exp2_frac[lane] = kGpSigma2 * d_exp_fast((double)lane * (6.93147180559945286227e-01 / 64.0));
+  if (tid < kGpRows) {
+    sh.loc[tid][0] = 0.0; sh.loc[tid][1] = 0.0; sh.loc[tid][2] = 0.0; sh.loc[tid][3] = 0.0;
+    sh.z[0][tid] = 0.0; sh.z[1][tid] = 0.0; sh.alpha[0][tid] = 0.0; sh.alpha[1][tid] = 0.0;
+    sh.inv_diag[tid] = 0.0; sh.part[tid] = 0.0;
+    sc.y[0][tid] = 0.0; sc.y[1][tid] = 0.0;
+    sc.px[tid] = 0.0f; sc.py[tid] = 0.0f; sc.pp[tid] = 0.0f; sc.pt[tid] = 0;
+  }
+  if (tid < 128) sh.W[kCholTri + tid] = 0.0;
+  grad_lut_fill(sc.grad_lut, tid, kObsBlock);
+  if (tid < 10 * b.num) {                               // thread (m, k): harmonic k of scenario m, from its own place in the stream
+    const int sm = tid / 10, k = tid - 10 * sm;
+    const HarmonicDraw d = scenario_harmonic(seed.of(env), seed.key(env, gen.env_offset), gen.episode ? gen.episode[env] : 0u, sm, k);
+    uint32_t* o = sc.draws[sm] + 5 * k;
+    o[0] = d.hseed; o[1] = float_bits_u32(d.ox); o[2] = float_bits_u32(d.oy); o[3] = float_bits_u32(d.op); o[4] = float_bits_u32(d.ot);
+  }
+  __syncthreads();
+  if (wave < 2) {
+    const unsigned long long b_mine = wave == 0 ? b0 : b1;
+    const int e = tid;                                  // ring entry of this lane (waves 0 and 1: entries 0 .. 127)
+    if (((b_mine >> lane) & 1ull) != 0) {
+      const int at = __popcll(b_mine & ((1ull << lane) - 1ull)) + (wave == 1 ? __popcll(b0) : 0) - drop;
+      if (at >= 0) {
+        const int slot = (count - m + e) % kGpCapacity;
+        const float ox = h_xyp[slot * 3], oy = h_xyp[slot * 3 + 1], op = h_xyp[slot * 3 + 2];
+        const int32_t ot = h_t[slot];
+        sh.loc[at][0] = (double)ox * (kGpKappa / 357000.0);
+        sh.loc[at][1] = (double)oy * (kGpKappa / 357000.0);
+        sh.loc[at][2] = (double)op * (kGpKappa / 326.0);
+        sh.loc[at][3] = (double)ot * (kGpKappa / 34560.0);
+        sc.y[0][at] = (double)h_err[slot * 2]; sc.y[1][at] = (double)h_err[slot * 2 + 1];
+        sc.px[at] = ox; sc.py[at] = oy; sc.pp[at] = op; sc.pt[at] = ot;
+      }
+    }
+  }
+  __syncthreads();
+
+  // ---- phase 1a: K, packed
+  const int n_tri = tri(n_obs);
+  for (int e = tid; e < n_tri; e += kObsBlock) {
+    int i = (int)((__builtin_sqrtf(8.0f * (float)e + 1.0f) - 1.0f) * 0.5f);
+    while (tri(i) > e) --i;
+    while (tri(i + 1) <= e) ++i;
+    const int j = e - tri(i);
+    const double dx = sh.loc[i][0] - sh.loc[j][0], dy = sh.loc[i][1] - sh.loc[j][1], dp = sh.loc[i][2] - sh.loc[j][2],
+                 dt = sh.loc[i][3] - sh.loc[j][3];
+    const double k = gp_exp_neg_scaled(two_sqrt(dx * dx + dy * dy + dp * dp + dt * dt + 1e-300), sh.exp2_frac);
+    sh.W[e] = i == j ? kGpSigma2 + kGpNoise2 : k;
+  }
+  __syncthreads();
+
+  // ---- phase 1b: K = L L^T, left-looking, column j per step; lane pair (i, i + 128) owns row i
+  {
+    const int i = tid & 127, h = tid >> 7;
+    double* ri = sh.W + tri(i);
+    double d_i = (i < n_obs) ? ri[i] : 1.0;
+    if (tid == 0) {
+      const double sq = __builtin_sqrt(d_i);
+      sh.inv_diag[0] = 1.0 / sq; ri[0] = sq;
+    }
+    __syncthreads();
+#pragma unroll 1
+    for (int j = 0; j + 1 < n_obs; ++j) {
+      const bool row = i > j && i < n_obs;
+      const double* rj = sh.W + tri(j);
+      const int kmid = j >> 1;
+      const int k0 = h ? kmid : 0, k1 = h ? j : kmid;
+      double s = 0.0;
+      if (row) {
+        for (int k = k0; k < k1; ++k) s = d_fma(ri[k], rj[k], s);
+        if (h) sh.part[i] = s;
+      }
+      __syncthreads();
+      if (row && !h) {
+        const double v = (ri[j] - (s + sh.part[i])) * sh.inv_diag[j];
+        ri[j] = v;
+        d_i = d_fma(-v, v, d_i);
+        if (i == j + 1) {
+          const double sq = __builtin_sqrt(d_i);
+          sh.inv_diag[i] = 1.0 / sq; ri[i] = sq;
+        }
+      }
+      __syncthreads();
+    }
+  }
+
+  // ---- phase 1c: W = L^-1 in place, row i per step; lane pair (j, j + 128) owns column j
+  {
+    const int j = tid & 127, h = tid >> 7;
+#pragma unroll 1
+    for (int i = 0; i < n_obs; ++i) {
+      const bool act = j < i;
+      const double* ri = sh.W + tri(i);
+      double s = 0.0;
+      if (act) {
+        const int kmid = (j + i + 1) >> 1;
+        const int k0 = h ? kmid : j, k1 = h ? i : kmid;
+        const double* wk = sh.W + tri(k0) + j;          // W[k][j], k = k0 ..: the next row's entry lies k + 1 further
+        for (int k = k0; k < k1; ++k) { s = d_fma(ri[k], *wk, s); wk += k + 1; }
+        if (h) sh.part[j] = s;
+      }
+      __syncthreads();
+      if (!h) {
+        if (act) sh.W[tri(i) + j] = -sh.inv_diag[i] * (s + sh.part[j]);
+        else if (j == i) sh.W[tri(i) + i] = sh.inv_diag[i];
+      }
+      __syncthreads();
+    }
+  }
+
+  // ---- the window, once (zero beyond it: loc was cleared above)
+  double* slab = b.slab + env * b.stride;
+  for (int q = tid; q < kBeliefAlphaAt; q += kObsBlock) slab[q] = sh.loc[q >> 2][q & 3];
+
+  // ---- per scenario: f_m at the window's points, the residual, phase 2.  Component c on the lanes 128 c .., point i = tid & 127:
+  // 2 x 120 evaluations over the 256 threads, one each
+  {
+    const int i = tid & 127, c = tid >> 7;
+#pragma unroll 1
+    for (int sm = 0; sm < b.num; ++sm) {
+      if (i < n_obs) {
+        const float f = wind_noise_component_from_rows(c, sc.px[i], sc.py[i], sc.pp[i], sc.pt[i], sc.draws[sm], 1, sc.grad_lut);
+        sh.z[c][i] = sc.y[c][i] - (double)f;
+      }
+      __syncthreads();
+      // phase 2: zeta = W z, alpha = W^T zeta
+      double s = 0.0;
+      if (i < n_obs) {
+        const double* ri = sh.W + tri(i);
+        for (int k = 0; k <= i; ++k) s = d_fma(ri[k], sh.z[c][k], s);
+      }
+      __syncthreads();
+      if (i < n_obs) sh.z[c][i] = s;
+      __syncthreads();
+      double t = 0.0;
+      if (i < n_obs) {
+        const double* wk = sh.W + tri(i) + i;              // W[k][i], k = i ..
+        for (int k = i; k < n_obs; ++k) { t = d_fma(*wk, sh.z[c][k], t); wk += k + 1; }
+      }
+      if (i < kBeliefRows) slab[kBeliefAlphaAt + kScenarioAlphaDoubles * sm + 2 * i + c] = t;      // (0.0 beyond the window)
+      __syncthreads();                                     // (the next scenario overwrites z)
+    }
+  }
+  if (tid == 0) b.n_obs[env] = n_obs;
+  if (tid == 0 && err_flags != nullptr && flags != 0) atomicOr(err_flags, flags);
+}
+
+constexpr int kScenarioWindBlock = 256;
+struct ScenarioWindShared {
+  __attribute__((aligned(16))) float grad_lut[kGradLutFloats];
+  double tab[64];
+  uint32_t draws[50 * kScenarioWindBlock];
+};
+
+// The scenario wind's ERROR at one caller-chosen point per environment, scenario scenario_index[e]: uv [n][2], ble_step_f32's noise_uv.
+// An index outside 0 .. num - 1: NaN, nothing of the slab read.  prior_only: f_m alone (the slab is not read at all).
+template <class S>
+__global__ __launch_bounds__(kScenarioWindBlock) void ble_gp_scenario_wind_kernel(ScenariosDev b, S seed, ScenarioGen gen,
+                                                                                 const int32_t* __restrict__ scenario_index,
+                                                                                 const float* __restrict__ x_m, const float* __restrict__ y_m,
+                                                                                 const float* __restrict__ pressure,
+                                                                                 const int32_t* __restrict__ elapsed_s, int prior_only,
+                                                                                 float* __restrict__ uv, int64_t n) {
+  __shared__ ScenarioWindShared shm;
+  grad_lut_fill(shm.grad_lut, (int)threadIdx.x, kScenarioWindBlock);
+  if (threadIdx.x < 64) shm.tab[threadIdx.x] = gp_belief_table_entry((int)threadIdx.x);
+  __syncthreads();
+  const int64_t e = (int64_t)blockIdx.x * kScenarioWindBlock + threadIdx.x;
+  const bool in_range = e < n;
+  const int sm = in_range ? scenario_index[e] : 0;
+  const bool valid = in_range && sm >= 0 && sm < b.num;
+  const int n_obs = (valid && !prior_only) ? b.n_obs[e] : 0;
+  const int n_trip = belief_wave_trip(n_obs);          // (all 64 lanes)
+  uint32_t* const rows = shm.draws + threadIdx.x;
+  if (valid) scenario_draws_fetch(seed.of(e), seed.key(e, gen.env_offset), gen.episode ? gen.episode[e] : 0u, sm, rows, kScenarioWindBlock);
+  if (in_range) {
+    float u = __builtin_nanf(""), v = __builtin_nanf("");
+    if (valid) {
+      float fu, fv;
+      wind_noise_from_rows(x_m[e], y_m[e], pressure[e], elapsed_s[e], rows, kScenarioWindBlock, shm.grad_lut, &fu, &fv);
+      asm volatile("" : "+v"(fu), "+v"(fv));             // the prior is a VALUE (ble_wind_noise_kernel's bits)
+      if (prior_only) {
+        u = fu; v = fv;
+      } else {
+        const double* slab = b.slab + e * b.stride;
+        float cu, cv;
+        gp_scenario_correction(slab, slab + kBeliefAlphaAt + kScenarioAlphaDoubles * sm, n_obs, n_trip, x_m[e], y_m[e], pressure[e],
+                               elapsed_s[e], shm.tab, &cu, &cv);
+        asm volatile("" : "+v"(cu), "+v"(cv));           // and so is the correction: ONE fp32 addition of two fp32 values
+        u = fu + cu; v = fv + cv;
+      }
+    }
+    uv[2 * e] = u; uv[2 * e + 1] = v;
+  }
+}
+
+// ble_rollout_kernel<noise>'s LDS (StepNoiseShared) and the belief's table
+struct ScenarioRolloutShared {
+  __attribute__((aligned(16))) float grad_lut[kGradLutFloats];
+  double acs_poly[kAcsPolyDoubles];
+  double tab[64];
+  float term_save[kTermSaveRows * kStepBlock];
+  uint32_t draws[50 * kStepBlock];
+};
+
+// ble_rollout_belief_kernel's body in the scenario winds: one lane per (environment e, plan k, scenario m), j = (e K + k) M + m.  Plans are
+// read at [h][e K + k]; ret, steps_flown, reward and final_state are indexed by j (a.n_plans is K; lanes_total = n K M).  Per agent step
+// the lane evaluates f_m and the correction at its pre-step state behind the same value barrier: the bits of
+// ble_gp_scenario_wind_kernel followed by ble_step_f32.  Reads the state, the caches and the slab; writes none of them.
+template <class V, class S>
+__global__ __launch_bounds__(kStepBlock) void ble_rollout_scenarios_kernel(StateDev st, RolloutArgs a, ScenariosDev b, S seed, ScenarioGen gen,
+                                                                          uint32_t* err_flags, V veh) {
+  __shared__ ScenarioRolloutShared shm;
+  const int wave = (int)threadIdx.x >> 6, lane = (int)threadIdx.x & 63;
+  const int64_t plans_total = a.n * (int64_t)a.n_plans;
+  const int64_t lanes_total = plans_total * b.num;               // < 2^31 (the entry point checks)
+  const int64_t j = (int64_t)blockIdx.x * kStepBlock + threadIdx.x;
+  const bool in_range = j < lanes_total;
+  const int64_t ek = in_range ? (int64_t)((uint32_t)j / (uint32_t)b.num) : 0;
+  const int sm = in_range ? (int)(j - ek * b.num) : 0;
+  const int64_t e = (int64_t)((uint32_t)ek / (uint32_t)a.n_plans);
+  uint32_t flags = 0;
+  EnvRegs s;
+  EnvConst c;
+  EpisodeCacheRow cached = {};
+  bool live = false;
+  int n_obs = 0;
+  if (in_range) {
+    // environment e's state, every load issued up front (ble_step_kernel's loads at index e)
+    s.status = st.status[e];
+    s.x = st.x[e]; s.y = st.y[e]; s.p = st.pressure[e]; s.t_amb = st.ambient_temperature[e];
+    s.t_int = st.internal_temperature[e]; s.vol = st.envelope_volume[e]; s.sp = st.superpressure[e];
+    s.n_air = st.mols_air[e]; s.batt = st.battery_charge[e];
+    s.acs_power = 0.0f; s.mdot = 0.0f; s.charge = 0.0f; s.load = 0.0f;
+    s.t_elapsed = st.time_elapsed_s[e]; s.sunrise_h = st.sunrise_h_rel[e]; s.sunset = st.sunset_rel[e];
+    s.alt_fsm = st.alt_fsm[e]; s.env_fsm = st.env_fsm[e]; s.paused = st.power_paused[e];
+    c.lat0_deg = st.center_lat_deg[e]; c.lng0_deg = st.center_lng_deg[e];
+    c.ir = st.upwelling_infrared[e]; c.alpha = st.alpha[e]; c.start_unix = st.start_unix[e];
+    if (st.episode_cache != nullptr) cached = episode_cache_load(st.episode_cache, a.n, e);
+    n_obs = b.n_obs[e];
+    live = s.status == kOk;
+  }
+  for (int q = (int)threadIdx.x; q < kAcsPolyDoubles; q += kStepBlock) shm.acs_poly[q] = kAcsPoly.c[q];
+  grad_lut_fill(shm.grad_lut, (int)threadIdx.x, kStepBlock);
+  if (threadIdx.x < 64) shm.tab[threadIdx.x] = gp_belief_table_entry((int)threadIdx.x);
+  __syncthreads();
+  EnvHoisted hc;
+  if (live) {
+    // per-episode constants: from the cache where its entry belongs to these constants; a miss recomputes and does NOT store
+    if (st.episode_cache != nullptr && episode_cache_hit(cached, c)) hc = hoisted_from_cache(cached, c);
+    else hc = hoist_constants(c);
+  }
+  uint32_t* const rows = shm.draws + threadIdx.x;
+  if (in_range) scenario_draws_fetch(seed.of(e), seed.key(e, gen.env_offset), gen.episode ? gen.episode[e] : 0u, sm, rows, kStepBlock);
+  const int n_trip = belief_wave_trip(n_obs);          // one loop for the wave, whatever environments its lanes belong to
+  const double* const loc = b.slab + e * b.stride;
+  const double* const alpha = loc + kBeliefAlphaAt + kScenarioAlphaDoubles * sm;
+  const StrideK K = stride_k_vreg(veh.dry_mass, veh.lift, veh.v0);
+  const float* const grid = a.wind_grid + e * a.grid_env_stride;
+  float* const park = shm.term_save + wave * (kTermSaveRows * kTermSaveStride) + lane;
+  // the discounted return: fp64, the product and the sum as two statements (two roundings under -ffp-contract=on), rounded to fp32 once
+  double acc = 0.0, disc = 1.0;
+  int flown = 0;
+  int64_t o = j;                                // (agent step t) * n K M + j
+#pragma unroll 1
+  for (int h = 0; h < a.n_plan_steps; ++h) {
+    const int act = in_range ? (int)a.plans[(int64_t)h * plans_total + ek] : 0;
+#pragma unroll 1
+    for (int rep = 0; rep < a.action_repeat; ++rep, o += lanes_total) {
+      if (live) {
+        ++flown;
+        const WindQuery wq = wind_query(s.x, s.y, s.p, s.t_elapsed);
+        WindCorners corners;
+        wind_gather(grid, wq, &corners);
+        float fu, fv, cu, cv;
+        wind_noise_from_rows(s.x, s.y, s.p, s.t_elapsed, rows, kStepBlock, shm.grad_lut, &fu, &fv);
+        asm volatile("" : "+v"(fu), "+v"(fv));
+        gp_scenario_correction(loc, alpha, n_obs, n_trip, s.x, s.y, s.p, s.t_elapsed, shm.tab, &cu, &cv);
+        asm volatile("" : "+v"(cu), "+v"(cv));
+        float nu = fu + cu, nv = fv + cv;
+        // the scenario's wind is a VALUE, as the noise is in ble_step_kernel: ble_gp_scenario_wind_f32 + ble_step_f32 give the same bits
+        asm volatile("" : "+v"(nu), "+v"(nv));
+        float r;
+        agent_step(s, c, hc, act, corners, wq, nu, nv, a.substeps, shm.acs_poly, K, park, &r, &flags, veh);
+        if (!(isfinite(s.p) && isfinite(s.t_int) && isfinite(s.x) && isfinite(s.y) && isfinite(s.batt)))
+          flags |= kFlagNonFinite;
+        if (a.reward) a.reward[o] = r;
+        const double term = disc * (double)r;
+        acc += term;
+        disc *= a.gamma;
+      } else if (in_range) {                    // a non-OK source, or a plan that went terminal: frozen, reward 0
+        if (a.reward) a.reward[o] = 0.0f;
+      }
+      live = live && s.status == kOk;
+    }
+  }
+  if (in_range) {
+    a.ret[j] = (float)acc;
+    a.steps_flown[j] = flown;
+    if (a.final_state) {
+      a.final_state[j] = s.x; a.final_state[lanes_total + j] = s.y; a.final_state[2 * lanes_total + j] = s.p;
+      a.final_state[3 * lanes_total + j] = s.batt;
+    }
+  }
+  report_flags(flags, err_flags);
+}
+
+// struct ble_plan_risk (include/ble_abi.h) as the kernel takes it
+struct PlanRiskArgs {
+  int64_t n;
+  int n_plans, num, tail;
+  const float* __restrict__ ret;               // [n][K][M]
+  float* __restrict__ score;                   // [n][K]
+};
+
+__global__ __launch_bounds__(256) void ble_plan_risk_kernel(PlanRiskArgs a) {
+  const int64_t lanes_total = a.n * (int64_t)a.n_plans;          // n K M < 2^31 (the entry point checks)
+  const int64_t j = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (j >= lanes_total) return;
+  a.score[j] = plan_risk_score(a.ret + j * a.num, 1, a.num, a.tail);
+}
+
+}  // namespace ble
+#endif  // __HIPCC__

@@ -187,17 +187,31 @@ class VecBalloonArena:
     return self.sim.query_wind(xyp, time_s, add_forecast, out)
 
   def lookahead(self, plans: torch.Tensor, gamma: float = 1.0, action_repeat: int = 1, noise_seed: Optional[int] = None,
-                want_rewards: bool = False, want_final: bool = False, out=None, belief=None):
+                want_rewards: bool = False, want_final: bool = False, out=None, scenarios=None, belief=None):
     """K action plans per env flown from the current state without changing it: plans uint8 [H, N, K] -> Rollout(returns [N, K],
     steps_flown [N, K], rewards or None, final or None); VecSimulator.rollout_plans.  noise_seed: None = the forecast; this arena's
     `_seed` = the ground-truth wind its environments fly in when stepped with sim.wind_noise(_seed).  belief: a WindBelief
-    (fit_wind_belief) = forecast + the WindGP's mean."""
+    (fit_wind_belief) = forecast + the WindGP's mean.  scenarios: a WindScenarios (fit_wind_scenarios) = forecast + each of M sampled
+    winds; the outputs are then [N, K, M]."""
     return self.sim.rollout_plans(plans, gamma, action_repeat, noise_seed, want_rewards=want_rewards, want_final=want_final, out=out,
-                                  belief=belief)
+                                  belief=belief, scenarios=scenarios)
 
   def fit_wind_belief(self, time_s: Optional[torch.Tensor] = None, out=None):
     """Every env's WindGP fitted once and kept on the device: WindBelief(slab, n_obs); VecSimulator.fit_wind_belief."""
     return self.sim.fit_wind_belief(time_s, out)
+
+  def fit_wind_scenarios(self, num_scenarios: int, seed: int = 0, seeds=None, time_s: Optional[torch.Tensor] = None, out=None):
+    """num_scenarios winds per env sampled from the WindGP's posterior: WindScenarios(slab, n_obs, num, seed, seeds);
+    VecSimulator.fit_wind_scenarios."""
+    return self.sim.fit_wind_scenarios(num_scenarios, seed, seeds, time_s, out)
+
+  def scenario_wind(self, scn, m, x=None, y=None, pressure=None, elapsed_s=None, prior_only: bool = False, out=None) -> torch.Tensor:
+    """Scenario m's forecast error at one point per env (default: where each balloon is): [N, 2]; VecSimulator.scenario_wind."""
+    return self.sim.scenario_wind(scn, m, x, y, pressure, elapsed_s, prior_only, out)
+
+  def plan_risk(self, returns: torch.Tensor, tail: Optional[int] = None, out=None) -> torch.Tensor:
+    """Scenario returns [N, K, M] -> score [N, K], the mean of the `tail` smallest per plan; VecSimulator.plan_risk."""
+    return self.sim.plan_risk(returns, tail, out)
 
   def belief_wind(self, belief, x=None, y=None, pressure=None, elapsed_s=None, out=None) -> torch.Tensor:
     """The belief's mean forecast error at one point per env (default: where each balloon is): [N, 2]; VecSimulator.belief_wind."""

@@ -168,6 +168,7 @@ class VecBalloonEnv:
     self._noise = None
     self._graph = None
     self._belief = None                      # lookahead(wind='belief')'s fitted WindGP: one slab, reused from call to call
+    self._scenarios = None                   # lookahead(wind='scenarios')'s scenario winds, reused while their number stays
     self._reseed = True               # the first reset() replays the constructor's seed
 
   def _noise_now(self):
@@ -218,7 +219,7 @@ class VecBalloonEnv:
     return self.arena.sim.query_wind(xyp, time_s, add_forecast, out)
 
   def lookahead(self, plans, gamma: float = 0.993, action_repeat: int = 1, wind: str = 'truth', want_rewards: bool = False,
-                want_final: bool = False, out=None):
+                want_final: bool = False, out=None, num_scenarios: int = 8, risk_tail: Optional[int] = None):
     """"From where each balloon is now, what happens under these K action sequences?": plans uint8 device tensor [H, N, K] ->
     Rollout(returns [N, K], steps_flown [N, K], rewards or None, final or None), nothing of the environments changed
     (VecSimulator.rollout_plans; no auto-reset inside a plan: a plan that goes terminal stops there).
@@ -227,9 +228,19 @@ class VecBalloonEnv:
     what the balloon has measured.  wind='belief': forecast + the mean of the WindGP over the balloon's own measurements -- the wind
     the observation is built on, all an agent may legitimately know; fitted now (arena.fit_wind_belief) and flown
     (rollout_plans(belief=)): two launches, no host synchronisation, capturable in a HIP graph.
+    wind='scenarios': forecast + each of num_scenarios (<= 16) winds SAMPLED from the WindGP's posterior -- draws of the noise field
+    conditioned on the balloon's measurements, from streams of their own keyed by this env's seed (never the truth's draw): fitted now
+    (arena.fit_wind_scenarios), flown (rollout_plans(scenarios=)) and scored (arena.plan_risk).  Returns (Rollout with returns
+    [N, K, M], steps_flown [N, K, M], ..., score [N, K]): score is the mean of the risk_tail smallest scenario returns of every plan
+    (None: all M, the expectation; 1: the worst case).
     Flags of the imagined flights go to arena.sim.rollout_flags, never to check_errors()."""
-    if wind not in ('truth', 'forecast', 'belief'):
-      raise ValueError(f"lookahead: wind is 'truth', 'forecast' or 'belief', not {wind!r}")
+    if wind not in ('truth', 'forecast', 'belief', 'scenarios'):
+      raise ValueError(f"lookahead: wind is 'truth', 'forecast', 'belief' or 'scenarios', not {wind!r}")
+    if wind == 'scenarios':
+      reuse = self._scenarios if (self._scenarios is not None and self._scenarios.num == int(num_scenarios)) else None
+      self._scenarios = self.arena.fit_wind_scenarios(num_scenarios, seed=self.arena._seed, out=reuse)
+      ro = self.arena.lookahead(plans, gamma, action_repeat, None, want_rewards, want_final, out, scenarios=self._scenarios)
+      return ro, self.arena.plan_risk(ro.returns, risk_tail)
     if wind == 'belief':
       self._belief = self.arena.fit_wind_belief(out=self._belief)
       return self.arena.lookahead(plans, gamma, action_repeat, None, want_rewards, want_final, out, belief=self._belief)
@@ -238,7 +249,7 @@ class VecBalloonEnv:
 
   def planner(self, **kw):
     """A look-ahead agent bound to these environments: agents.lookahead_agent.VecLookaheadAgent(**kw) -- num_plans, horizon,
-    action_repeat, segment, gamma, wind ('belief' by default), iterations, elite, seed -- planning in this batch's simulator.
+    action_repeat, segment, gamma, wind ('belief' by default; 'scenarios' with num_scenarios, risk_tail), iterations, elite, seed -- planning in this batch's simulator.
     wind='truth' flies the plans in the wind these environments fly, this env's wind noise included (with wind_noise=False the truth
     is the forecast).  actions = agent.act(obs); obs, reward, terminal = env.step(actions): no host synchronisation in either."""
     from balloon_learning_environment_amd.agents import lookahead_agent

@@ -25,6 +25,9 @@ Rollout = collections.namedtuple('Rollout', ('returns', 'steps_flown', 'rewards'
 # what fit_wind_belief returns: the fitted WindGP of every environment, device tensors slab [n, 720] float64 (the library's own layout)
 # and n_obs [n] int32 (observations in the window; 0: no posterior, -1: a window the ring could not tell -- the belief's wind is NaN)
 WindBelief = collections.namedtuple('WindBelief', ('slab', 'n_obs'))
+# what fit_wind_scenarios returns: num scenario winds per environment, device tensors slab [n, 480 + 240 num] float64 (the window once,
+# then every scenario's weights) and n_obs [n] int32 as in WindBelief; seed / seeds: where the scenario streams come from (one of them)
+WindScenarios = collections.namedtuple('WindScenarios', ('slab', 'n_obs', 'num', 'seed', 'seeds'), defaults=(0, None))
 
 
 class ReferenceError_(Exception):
@@ -401,6 +404,95 @@ class VecSimulator:
                'ble_gp_belief_wind_f32')
     return out
 
+  def _scenario_structs(self, scn):
+    """(ble_gp_scenarios, ble_scenario_gen) of a WindScenarios."""
+    slab, n_obs, num, seed, seeds = scn
+    num = int(num)
+    if not 1 <= num <= _abi.SCENARIO_MAX:
+      raise ValueError(f'1 <= num_scenarios <= {_abi.SCENARIO_MAX}, not {num}')
+    doubles = _abi.gp_scenario_doubles(num)
+    assert slab.dtype == torch.float64 and slab.is_contiguous() and tuple(slab.shape) == (self.n, doubles), slab.shape
+    assert n_obs.dtype == torch.int32 and n_obs.is_contiguous() and tuple(n_obs.shape) == (self.n,), n_obs.shape
+    assert slab.device == self.device and n_obs.device == self.device and slab.data_ptr() % 16 == 0
+    if seeds is not None:
+      assert seeds.dtype in (torch.int64, torch.uint64) and seeds.is_contiguous() and tuple(seeds.shape) == (self.n,), seeds.shape
+      assert seeds.device == self.device
+    gen = _abi.BleScenarioGen(int(seed or 0) & (2 ** 64 - 1), dev.ptr(seeds), self.episode.data_ptr(), 0 if seeds is not None else self.env_offset)
+    return _abi.BleGpScenarios(slab.data_ptr(), doubles, n_obs.data_ptr(), self.n, num, 0), gen
+
+  @_on_own_device
+  def fit_wind_scenarios(self, num_scenarios: int, seed: int = 0, seeds: Optional[torch.Tensor] = None,
+                         time_s: Optional[torch.Tensor] = None, out: Optional[WindScenarios] = None) -> WindScenarios:
+    """num_scenarios (<= 16) SAMPLED winds per environment instead of the belief's one mean (`ble_gp_fit_scenarios_f32`): scenario m is
+    a draw of the wind-noise field -- the generator of wind_noise() with harmonics from a stream of its own, never the truth's --
+    corrected so that it passes through the balloon's measurements (pathwise conditioning on the window fit_wind_belief takes, same
+    rules, same flags).  Returns WindScenarios(slab [n, 480 + 240 M] float64, n_obs [n] int32, M, seed, seeds), the argument of
+    scenario_wind and rollout_plans(scenarios=).  seed: the batch's seed, streams keyed by (seed, env_offset + e, episode[e], m); seeds:
+    int64 device tensor [n], a seed per environment, streams keyed by (seeds[e], 0, episode[e], m) -- an environment then gets the same
+    scenarios in any batch, at any position.  Scenario m does not depend on M.  time_s, out: as for fit_wind_belief (out's slab and
+    n_obs are written; its num must be num_scenarios).  Reads the ring, changes nothing of the simulator; asynchronous."""
+    num = int(num_scenarios)
+    if time_s is None:
+      time_s = self.state['time_elapsed_s']
+    assert time_s.dtype == torch.int32 and time_s.is_contiguous() and tuple(time_s.shape) == (self.n,) and time_s.device == self.device
+    if out is None:
+      if not 1 <= num <= _abi.SCENARIO_MAX:
+        raise ValueError(f'fit_wind_scenarios: 1 <= num_scenarios <= {_abi.SCENARIO_MAX}, not {num}')
+      out = (torch.empty(self.n, _abi.gp_scenario_doubles(num), dtype=torch.float64, device=self.device),
+             torch.empty(self.n, dtype=torch.int32, device=self.device))
+    else:
+      assert int(out[2]) == num, (out[2], num)
+    scn = WindScenarios(out[0], out[1], num, int(seed), seeds)
+    b, gen = self._scenario_structs(scn)
+    hist, reset_mask = self._history_for_reading()
+    _lib.check(self.lib.ble_gp_fit_scenarios_f32(ctypes.byref(hist), reset_mask, time_s.data_ptr(), ctypes.byref(b), ctypes.byref(gen),
+                                                 self.err_flags.data_ptr(), dev.stream_ptr(self.device)), 'ble_gp_fit_scenarios_f32')
+    return scn
+
+  @_on_own_device
+  def scenario_wind(self, scn: WindScenarios, m, x: Optional[torch.Tensor] = None, y: Optional[torch.Tensor] = None,
+                    pressure: Optional[torch.Tensor] = None, elapsed_s: Optional[torch.Tensor] = None, prior_only: bool = False,
+                    out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Scenario m's forecast ERROR at one point per environment (`ble_gp_scenario_wind_f32`): [n, 2] float32 m/s, the `noise_uv` of
+    step() -- the forecast is not added.  m: an int, or an int32 device tensor [n] (a scenario per environment; an index outside
+    0 .. M - 1 gives NaN).  x, y, pressure, elapsed_s: as for belief_wind (None: the environment's own state).  prior_only: the
+    unconditioned draw f_m alone -- what the fit subtracted from the measurements at the window's points."""
+    if not torch.is_tensor(m):
+      m = torch.full((self.n,), int(m), dtype=torch.int32, device=self.device)
+    assert m.dtype == torch.int32 and m.is_contiguous() and tuple(m.shape) == (self.n,) and m.device == self.device
+    s = self.state
+    args = []
+    for t, name, dtype in ((x, 'x', torch.float32), (y, 'y', torch.float32), (pressure, 'pressure', torch.float32),
+                           (elapsed_s, 'time_elapsed_s', torch.int32)):
+      t = s[name] if t is None else t
+      assert t.dtype == dtype and t.is_contiguous() and tuple(t.shape) == (self.n,) and t.device == self.device, name
+      args.append(t.data_ptr())
+    if out is None:
+      out = torch.empty(self.n, 2, dtype=torch.float32, device=self.device)
+    assert out.dtype == torch.float32 and out.is_contiguous() and tuple(out.shape) == (self.n, 2) and out.device == self.device
+    b, gen = self._scenario_structs(scn)
+    _lib.check(self.lib.ble_gp_scenario_wind_f32(ctypes.byref(b), ctypes.byref(gen), m.data_ptr(), *args, 1 if prior_only else 0,
+                                                 out.data_ptr(), dev.stream_ptr(self.device)), 'ble_gp_scenario_wind_f32')
+    return out
+
+  @_on_own_device
+  def plan_risk(self, returns: torch.Tensor, tail: Optional[int] = None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """returns [n, K, M] float32 (rollout_plans(scenarios=)) -> score [n, K] float32 (`ble_plan_risk_f32`): the mean of the `tail`
+    smallest scenario returns of every plan -- None or M: the expectation; 1: the worst case; between them a CVaR.  A plan with a
+    non-finite scenario return scores NaN."""
+    assert returns.dtype == torch.float32 and returns.is_contiguous() and returns.dim() == 3 and returns.shape[0] == self.n, returns.shape
+    assert returns.device == self.device
+    k, num = int(returns.shape[1]), int(returns.shape[2])
+    tail = num if tail is None else int(tail)
+    if not 1 <= num <= _abi.SCENARIO_MAX or not 1 <= tail <= num:
+      raise ValueError(f'plan_risk: 1 <= M <= {_abi.SCENARIO_MAX} and 1 <= tail <= M, not M = {num}, tail = {tail}')
+    if out is None:
+      out = torch.empty(self.n, k, dtype=torch.float32, device=self.device)
+    assert out.dtype == torch.float32 and out.is_contiguous() and tuple(out.shape) == (self.n, k) and out.device == self.device
+    risk = _abi.BlePlanRisk(self.n, k, num, tail, 0, returns.data_ptr(), out.data_ptr())
+    _lib.check(self.lib.ble_plan_risk_f32(ctypes.byref(risk), dev.stream_ptr(self.device)), 'ble_plan_risk_f32')
+    return out
+
   def _allocate_history(self, carry_factor: bool) -> None:
     """The WindGP ring of every environment (and, with carry_factor, the HBM-resident factor slab)."""
     with torch.cuda.device(self.device):
@@ -596,7 +688,7 @@ class VecSimulator:
   @_on_own_device
   def rollout_plans(self, plans: torch.Tensor, gamma: float = 1.0, action_repeat: int = 1, noise_seed: Optional[int] = None,
                     substeps: int = SUBSTEPS, want_rewards: bool = False, want_final: bool = False, out: Optional[tuple] = None,
-                    belief: Optional[WindBelief] = None) -> 'Rollout':
+                    scenarios: Optional[WindScenarios] = None, belief: Optional[WindBelief] = None) -> 'Rollout':
     """Look ahead: flies K action plans per environment from the state where it lies, WITHOUT changing it (`ble_rollout_f32`).
     `plans`: uint8 device tensor [H, n, K], contiguous -- entry h of plan k of environment e is flown action_repeat agent steps.  Returns
     Rollout(returns [n, K] f32, steps_flown [n, K] i32, rewards [H * action_repeat, n, K] f32 or None, final [4, n, K] f32 or None):
@@ -608,6 +700,9 @@ class VecSimulator:
     belief: a WindBelief (fit_wind_belief): fly in the wind the agent believes, forecast + the belief's mean evaluated at every plan's
     own position and time (`ble_rollout_belief_f32`); per step, bit for bit belief_wind at the plan's state + step(noise_uv=that).  Not
     together with noise_seed.  An environment whose belief is NaN (n_obs -1) gets non-finite returns and FLAG_NONFINITE in rollout_flags.
+    scenarios: a WindScenarios (fit_wind_scenarios): every plan is flown in each of its M scenario winds (`ble_rollout_scenarios_f32`),
+    and the outputs get one axis more: returns [n, K, M], steps_flown [n, K, M], rewards [H * action_repeat, n, K, M], final
+    [4, n, K, M]; per step, bit for bit scenario_wind at the plan's state + step(noise_uv=that).  Not together with noise_seed or belief.
     out: a Rollout (or tuple) of tensors to write into, None where an output is not wanted.
     Nothing of the simulator is written: state, last_command, episode counters, both caches and the WindGP history stay as they are.
     Error flags go to a word of their own, `rollout_flags` (int32 device tensor, OR-ed into, never cleared here), NOT to err_flags: a
@@ -617,6 +712,8 @@ class VecSimulator:
       raise ValueError('rollout_plans: a fleet (set_fleet) has no look-ahead kernel; fly one vehicle per batch (set_vehicle)')
     if belief is not None and noise_seed is not None:
       raise ValueError('rollout_plans: belief and noise_seed are two winds; give one of them')
+    if scenarios is not None and (belief is not None or noise_seed is not None):
+      raise ValueError('rollout_plans: scenarios, belief and noise_seed are three winds; give one of them')
     assert self.grid is not None, 'Must call set_grid (reset) before rollout_plans.'
     assert plans.dtype == torch.uint8 and plans.is_contiguous() and plans.dim() == 3 and plans.shape[1] == self.n, plans.shape
     assert plans.device == self.device
@@ -627,19 +724,27 @@ class VecSimulator:
                        f'not H = {h}, K = {k}, action_repeat = {action_repeat}, n = {self.n}')
     if not 0.0 <= float(gamma) <= 1.0:
       raise ValueError(f'rollout_plans: gamma in [0, 1], not {gamma}')
+    lanes = (self.n, k) if scenarios is None else (self.n, k, int(scenarios.num))
+    if scenarios is not None and self.n * k * int(scenarios.num) >= 2 ** 31:
+      raise ValueError(f'rollout_plans: n * K * M < 2^31, not {self.n} x {k} x {scenarios.num}')
     if out is None:
-      out = (torch.empty(self.n, k, dtype=torch.float32, device=self.device), torch.empty(self.n, k, dtype=torch.int32, device=self.device),
-             torch.empty(steps, self.n, k, dtype=torch.float32, device=self.device) if want_rewards else None,
-             torch.empty(4, self.n, k, dtype=torch.float32, device=self.device) if want_final else None)
+      out = (torch.empty(*lanes, dtype=torch.float32, device=self.device), torch.empty(*lanes, dtype=torch.int32, device=self.device),
+             torch.empty(steps, *lanes, dtype=torch.float32, device=self.device) if want_rewards else None,
+             torch.empty(4, *lanes, dtype=torch.float32, device=self.device) if want_final else None)
     returns, flown, rewards, final = out
-    for t, dtype, shape in ((returns, torch.float32, (self.n, k)), (flown, torch.int32, (self.n, k)), (rewards, torch.float32, (steps, self.n, k)),
-                            (final, torch.float32, (4, self.n, k))):
+    for t, dtype, shape in ((returns, torch.float32, lanes), (flown, torch.int32, lanes), (rewards, torch.float32, (steps,) + lanes),
+                            (final, torch.float32, (4,) + lanes)):
       assert t is None or (t.dtype == dtype and t.is_contiguous() and tuple(t.shape) == shape and t.device == self.device), (shape, t)
     assert returns is not None and flown is not None
     # (no harmonic cache: the kernel fills none, and wind_noise()'s stays byte for byte what it was)
     gen = None if noise_seed is None else _abi.BleNoiseGen(int(noise_seed) & (2 ** 64 - 1), self.episode.data_ptr(), None, self.env_offset)
     ro = _abi.BleRolloutF32(self.n, k, h, int(action_repeat), int(substeps), float(gamma), plans.data_ptr(), self.grid.data_ptr(),
                             self.grid_env_stride, returns.data_ptr(), flown.data_ptr(), dev.ptr(rewards), dev.ptr(final))
+    if scenarios is not None:
+      b, sgen = self._scenario_structs(scenarios)
+      _lib.check(self.lib.ble_rollout_scenarios_f32(ctypes.byref(self._struct), ctypes.byref(ro), ctypes.byref(b), ctypes.byref(sgen),
+                                                    self.rollout_flags.data_ptr(), dev.stream_ptr(self.device)), 'ble_rollout_scenarios_f32')
+      return Rollout(returns, flown, rewards, final)
     if belief is not None:
       b = self._belief_struct(belief)
       _lib.check(self.lib.ble_rollout_belief_f32(ctypes.byref(self._struct), ctypes.byref(ro), ctypes.byref(b), self.rollout_flags.data_ptr(),

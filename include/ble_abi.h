@@ -1060,6 +1060,92 @@ struct ble_plan_select {
 };
 int ble_plan_select_f32(const struct ble_plan_select* sel, void* stream);
 
+/*
+ * Scenario winds: M = num sampled winds per environment instead of the belief's one mean.  Scenario m of environment e
+ * is a draw f_m of the wind-noise field (the generator of ble_wind_noise_f32 with harmonics from the scenario stream below) corrected
+ * so that it passes through the balloon's measurements (pathwise conditioning):
+ *     error_m(x) = f_m(x) + sum_i k(loc_i, x) alpha^m_i,      alpha^m = (K + 0.05 I)^-1 (y - f_m(X))
+ * with X, y, K the window of ble_gp_fit_f32 frozen at the anchor.  f_m(x) and the correction are each rounded to float (the
+ * correction as ble_gp_belief_wind_f32 rounds) and added in ONE float addition.  The forecast is NOT added.  n_obs 0: the correction is
+ * exactly +0.0f, a scenario is its prior draw; n_obs -1: NaN.  Added without a new ABI version; every size travels in a struct.
+ *
+ * The stream of (e, m): Philox4x32-10 with the key (seed_e ^ 0x5343454E4152) and the counter (block, episode[e], low and high word of
+ * key_e), block = 32 m + b for the stream's b-th block; seed_e, key_e = seed, env_offset + e, or with env_seed: env_seed[e], 0.  Words
+ * are taken from a block in the order 3, 2, 1, 0; harmonic k = 5 comp + h takes nine words from word 9 k on: the generator seed, then
+ * four uniforms (hi, lo) -> ((hi << 32 | lo) >> 11) * 2^-53, offset = (float)(2 u - 1) for x, y, pressure, time -- the draws of the
+ * true noise, whose key constant is 0x5EEDF00D: no scenario is the truth.  A function of (seed_e, key_e, episode[e], m) alone.
+ *
+ * slab: BLE_GP_SCENARIO_DOUBLES(num) doubles per environment -- the window's 120 x 4 coordinates once (bit for bit ble_gp_fit_f32's),
+ * then per scenario 120 x 2 of alpha^m.  Entries beyond the window are zero.  n_obs[e]: as in ble_gp_belief.
+ */
+#define BLE_SCENARIO_MAX 16
+#define BLE_GP_SCENARIO_DOUBLES(num) (480 + 240 * (num))
+typedef struct ble_gp_scenarios {
+  double* slab;              /* device [n][stride], 16-byte aligned */
+  int64_t stride;            /* doubles between the slabs of consecutive environments: >= BLE_GP_SCENARIO_DOUBLES(num) and even */
+  int32_t* n_obs;            /* device [n] */
+  int64_t n;                 /* environments */
+  int32_t num;               /* M: 1 .. BLE_SCENARIO_MAX */
+  int32_t reserved_;
+} ble_gp_scenarios;
+typedef struct ble_scenario_gen {
+  unsigned long long seed;                   /* the batch's seed (env_seed == NULL) */
+  const unsigned long long* env_seed;        /* optional device [n]: a seed per environment, every stream keyed as environment 0 */
+  const uint32_t* episode;                   /* optional device [n]: the episode counters (NULL: 0) */
+  int64_t env_offset;                        /* index of environment 0 in the global batch (env_seed == NULL), >= 0 */
+} ble_scenario_gen;
+
+/*
+ * ble_gp_fit_scenarios_f32: the window, K and its factor once per environment (the rules of ble_gp_fit_f32, BLE_FLAG_GP_WINDOW
+ * included), then alpha^m for m = 0 .. num - 1; f_m(X) is evaluated from the ring's own float32 x, y, p and int32 t, bit for bit what
+ * ble_gp_scenario_wind_f32(prior_only = 1) returns there.  Reads the ring and count of `hist`; writes scn and err_flags.
+ * BLE_E_INVALID_ARG before any HIP call: NULL hist, ring pointer, time_s, scn, slab, n_obs or gen; num outside 1 .. BLE_SCENARIO_MAX; a
+ * slab that is not 16-byte aligned, a stride below BLE_GP_SCENARIO_DOUBLES(num) or odd; scn->n < 0 or >= 2^31; gen->env_offset < 0.
+ * scn->n == 0: BLE_OK without a launch.  reset_mask and err_flags may be NULL.
+ */
+int ble_gp_fit_scenarios_f32(const ble_gp_history_f32* hist, const uint8_t* reset_mask, const int32_t* time_s, const ble_gp_scenarios* scn,
+                             const ble_scenario_gen* gen, uint32_t* err_flags, void* stream);
+
+/*
+ * The scenario wind's forecast ERROR at one point per environment, scenario scenario_index[e] (device int32 [n]): uv [n][2] m/s, what
+ * ble_step_f32 takes as noise_uv -- the shape and role of ble_gp_belief_wind_f32.  prior_only = 1: f_m alone (the slab is not read).  An
+ * index outside 0 .. num - 1: NaN.
+ * BLE_E_INVALID_ARG: what ble_gp_fit_scenarios_f32 refuses of scn and gen; a NULL array; prior_only other than 0 or 1.
+ */
+int ble_gp_scenario_wind_f32(const ble_gp_scenarios* scn, const ble_scenario_gen* gen, const int32_t* scenario_index, const float* x_m,
+                             const float* y_m, const float* pressure, const int32_t* elapsed_s, int prior_only, float* uv, void* stream);
+
+/*
+ * ble_rollout_belief_f32 flown in the scenario winds: one lane per (environment e, plan k, scenario m), lane index
+ * j = (e * K + k) * M + m.  `ro` is ble_rollout_f32's with plans [H][n][K] as there and the outputs one axis longer: ret [n][K][M],
+ * steps_flown [n][K][M], optional reward [H * action_repeat][n][K][M] and final_state [4][n][K][M].  Per agent step the same bits as
+ * ble_gp_scenario_wind_f32 at the lane's pre-step state followed by ble_step_f32 with that noise_uv.  The state, its caches and scn are
+ * read, never written.  An environment whose n_obs is -1 flies NaN (BLE_FLAG_NONFINITE in err_flags, the call's own word).
+ * BLE_E_INVALID_ARG: everything ble_rollout_f32 refuses; what ble_gp_fit_scenarios_f32 refuses of scn and gen; scn->n other than
+ * ro->n; n * K * M >= 2^31.  n == 0: BLE_OK without a launch.  A fleet has no form of this call.
+ */
+int ble_rollout_scenarios_f32(const ble_state_f32* st, const struct ble_rollout_f32* ro, const ble_gp_scenarios* scn,
+                              const ble_scenario_gen* gen, uint32_t* err_flags, void* stream);
+
+/*
+ * ble_plan_risk_f32: ret [n][K][M] -> score [n][K], the mean of the `tail` smallest scenario returns of every plan: tail = M the
+ * expectation, tail = 1 the worst case, between them a CVaR.  The order: the return ascending (-0 == +0), then m ascending; the sum is
+ * taken in that order in double from 0.0, divided by tail once and rounded to float once.  Any non-finite scenario return: NaN (which
+ * ble_plan_select_f32 puts last).  ble_plan_select_f32 then runs on score as on any ret [n][K].
+ * BLE_E_INVALID_ARG before any HIP call: NULL risk, ret or score; n < 0 or >= 2^31; n_plans outside 1 .. BLE_PLAN_MAX_PLANS; num outside
+ * 1 .. BLE_SCENARIO_MAX; tail outside 1 .. num; n * n_plans * num >= 2^31.  n == 0: BLE_OK without a launch.
+ */
+struct ble_plan_risk {
+  int64_t n;
+  int32_t n_plans;                           /* K */
+  int32_t num;                               /* M */
+  int32_t tail;                              /* 1 .. M */
+  int32_t reserved_;
+  const float* ret;                          /* device [n][K][M] */
+  float* score;                              /* device [n][K] out */
+};
+int ble_plan_risk_f32(const struct ble_plan_risk* risk, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
