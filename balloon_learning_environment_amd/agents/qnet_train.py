@@ -394,6 +394,8 @@ def unpack(net: _abi.BleQnetF32, packed: np.ndarray) -> dict:
 
 def explore(actions: torch.Tensor, epsilon: float, seed: int, step: int) -> torch.Tensor:
   """epsilon-greedy in place on uint8 device actions (ble_qnet_explore_u8): keyed by (seed, environment, step)."""
+  if actions.dtype != torch.uint8 or not actions.is_contiguous():
+    raise ValueError('explore: actions must be a contiguous uint8 tensor (the kernel writes numel() bytes from data_ptr())')
   ex = _abi.BleExploreF32(actions.numel(), float(epsilon), 0, int(seed) & (2 ** 64 - 1), int(step) & (2 ** 64 - 1))
   _lib.call('ble_qnet_explore_u8', ctypes.byref(ex), actions.data_ptr(), dev.stream_ptr(actions.device))
   return actions

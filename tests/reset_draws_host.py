@@ -33,9 +33,10 @@ def u64(a):
 
 class Streams:
   """One word stream per environment: key (seed lo, seed hi), counter (block, episode, key lo, key hi); words are popped from out[3]
-  down to out[0], then the block advances."""
+  down to out[0], then the block advances.  blocks: how many blocks are generated at a time (a caller that reads few words asks
+  for few)."""
 
-  def __init__(self, seed, key, episode):
+  def __init__(self, seed, key, episode, blocks=16):
     seed, key, episode = np.broadcast_arrays(np.atleast_1d(u64(seed)), np.atleast_1d(u64(key)), np.atleast_1d(u64(episode)))
     self.n = seed.size
     self._key = np.stack([seed & M32, seed >> np.uint64(32)], -1)
@@ -43,8 +44,10 @@ class Streams:
     self._words = np.empty((self.n, 0), np.uint64)
     self.pos = np.zeros(self.n, np.int64)             # words consumed so far
     self._rows = np.arange(self.n)
+    self._blocks = blocks
 
-  def _extend(self, blocks=16):
+  def _extend(self):
+    blocks = self._blocks
     first = self._words.shape[1] // 4
     counter = np.empty((self.n, blocks, 4), np.uint64)
     counter[..., 0] = np.arange(first, first + blocks, dtype=np.uint64)[None, :]
