@@ -265,3 +265,27 @@ class BleMarcoPoloF32(ctypes.Structure):
               ('exploratory_episode_probability', ctypes.c_double), ('seed', ctypes.c_uint64), ('obs', ctypes.c_void_p),
               ('begin', ctypes.c_void_p), ('step', ctypes.c_void_p), ('phase_clock', ctypes.c_void_p), ('walk_clock', ctypes.c_void_p),
               ('exploratory_episode', ctypes.c_void_p), ('exploratory_phase', ctypes.c_void_p), ('target', ctypes.c_void_p)]
+
+
+class BleAcRowsF32(ctypes.Structure):
+  """struct ble_ac_rows_f32: n observation rows and what ble_ac_act_f32 writes for each (device pointers)."""
+  _fields_ = [('n', ctypes.c_int64), ('obs_row_stride', ctypes.c_int64), ('obs', ctypes.c_void_p), ('action', ctypes.c_void_p),
+              ('logp', ctypes.c_void_p), ('value', ctypes.c_void_p), ('probs', ctypes.c_void_p)]
+
+
+class BleAcSample(ctypes.Structure):
+  """struct ble_ac_sample: the sampled head's stream, keyed by (seed, env_offset + row, *step); step is a device pointer."""
+  _fields_ = [('seed', ctypes.c_uint64), ('env_offset', ctypes.c_int64), ('step', ctypes.c_void_p), ('reserved_', ctypes.c_int64)]
+
+
+class BleGaeBlockF32(ctypes.Structure):
+  """struct ble_gae_block_f32: a rollout block of T steps of N environments, arrays [T][N] (device pointers)."""
+  _fields_ = [('steps', ctypes.c_int64), ('num_envs', ctypes.c_int64), ('gamma', ctypes.c_float), ('lam', ctypes.c_float),
+              ('reward', ctypes.c_void_p), ('value', ctypes.c_void_p), ('boot_value', ctypes.c_void_p), ('terminal', ctypes.c_void_p),
+              ('episode_end', ctypes.c_void_p), ('advantage', ctypes.c_void_p), ('ret', ctypes.c_void_p)]
+
+
+class BlePpoF32(ctypes.Structure):
+  """struct ble_ppo_f32: the clipped-PPO loss's coefficients and the batch rows' old log-probabilities and advantages (device)."""
+  _fields_ = [('clip', ctypes.c_float), ('value_coef', ctypes.c_float), ('entropy_coef', ctypes.c_float), ('reserved_', ctypes.c_int32),
+              ('old_logp', ctypes.c_void_p), ('advantage', ctypes.c_void_p)]

@@ -41,6 +41,7 @@
 #include "ble_qnet.h"
 #include "ble_train.h"
 #include "ble_explore.h"
+#include "ble_actor.h"
 #include "ble_replay.h"
 
 using namespace ble;
@@ -1338,9 +1339,10 @@ bool replay_ok(const ble_replay_f32* rp) {
          rp->obs_stride % 4 == 0 && std::isfinite(rp->gamma) && rp->max_tries >= 1 && rp->max_tries <= BLE_REPLAY_MAX_TRIES && rp->obs &&
          aligned(15, rp->obs) && rp->action && rp->reward && rp->terminal && rp->episode_end && rp->count && rp->counter;
 }
-bool batch_ok(const ble_train_batch_f32* bt) {
+// transitions: a batch of (state, next_state) pairs; an on-policy batch (PPO) has no next_state and no discount
+bool batch_ok(const ble_train_batch_f32* bt, bool transitions = true) {
   return bt != nullptr && bt->batch >= 0 && bt->batch <= BLE_TRAIN_MAX_BATCH && bt->state_stride >= BLE_OBS_DIM && bt->state_stride % 4 == 0 &&
-         bt->state_stride <= (1LL << 20) && bt->state && bt->next_state && bt->ret && bt->discount && bt->action &&
+         bt->state_stride <= (1LL << 20) && bt->state && (!transitions || (bt->next_state && bt->discount)) && bt->ret && bt->action &&
          aligned(15, bt->state, bt->next_state);
 }
 // The workspace of one update on n rows.  branches: how often the online network runs -- 1, or 2 for SARSA (state, then next_state),
@@ -1420,9 +1422,15 @@ bool td_ok(const ble_td_f32* td) {
   return td_kind_ok(td) && (td->optimizer == BLE_TD_OPT_ADAM || td->optimizer == BLE_TD_OPT_SGD) &&
          (td->kind != BLE_TD_SARSA_MSE || (td->next_action != nullptr && std::isfinite(td->gamma)));
 }
-// The loss of an update: a kind of ble_td_f32, or QR-DQN's (ble_qnet_train_step_f32, which has no ble_td_f32: td == nullptr).
-constexpr int kKindQr = -1;
-int update_kind(const ble_td_f32* td) { return td != nullptr ? td->kind : kKindQr; }
+// The descriptor of ble_qnet_ppo_step_f32.
+bool ppo_ok(const ble_ppo_f32* ppo) {
+  return ppo != nullptr && std::isfinite(ppo->clip) && ppo->clip > 0.0f && std::isfinite(ppo->value_coef) && std::isfinite(ppo->entropy_coef) &&
+         ppo->old_logp != nullptr && ppo->advantage != nullptr;
+}
+// The loss of an update: a kind of ble_td_f32, PPO's (ble_qnet_ppo_step_f32: ppo != nullptr), or QR-DQN's (ble_qnet_train_step_f32,
+// which has neither descriptor).
+constexpr int kKindQr = -1, kKindPpo = -2;
+int update_kind(const ble_td_f32* td, const ble_ppo_f32* ppo = nullptr) { return ppo != nullptr ? kKindPpo : td != nullptr ? td->kind : kKindQr; }
 int update_branches(int kind) { return kind == BLE_TD_SARSA_MSE ? 2 : 1; }
 
 // The arguments of one update, td == nullptr for ble_qnet_train_step_f32.  Where the two entry points differ, each keeps the answer
@@ -1431,10 +1439,16 @@ int update_branches(int kind) { return kind == BLE_TD_SARSA_MSE ? 2 : 1; }
 //  * SARSA has no target network, so it alone accepts target == NULL;
 //  * lr: the QR form's only reader is Adam, so it checks lr under apply_update; the TD form, which has SGD too, checks it always;
 //  * Adam's state and hyperparameters are wanted when Adam runs: under apply_update, and not with BLE_TD_OPT_SGD.
-bool update_ok(const ble_qnet_train_f32* tr, const ble_td_f32* td, const ble_train_batch_f32* bt, const float* loss) {
-  if (!tr || !qnet_ok(&tr->net) || !batch_ok(bt) || !loss || !tr->net.weights || !tr->grad || !tr->workspace) return false;
-  if (td == nullptr ? (!(tr->kappa > 0.0f) || !std::isfinite(tr->kappa)) : (tr->net.num_atoms != 1 || !td_ok(td))) return false;
-  if (update_branches(update_kind(td)) == 1 && !tr->target) return false;
+// PPO (ppo != nullptr, td == nullptr) needs a two-atom network and its own descriptor; it has no target network, no next_state and no
+// kappa, and is the QR form in what it asks of lr and Adam.
+bool update_ok(const ble_qnet_train_f32* tr, const ble_td_f32* td, const ble_ppo_f32* ppo, const ble_train_batch_f32* bt, const float* loss) {
+  if (!tr || !qnet_ok(&tr->net) || !batch_ok(bt, ppo == nullptr) || !loss || !tr->net.weights || !tr->grad || !tr->workspace) return false;
+  if (ppo != nullptr) {
+    if (tr->net.num_atoms != 2 || !ppo_ok(ppo)) return false;
+  } else {
+    if (td == nullptr ? (!(tr->kappa > 0.0f) || !std::isfinite(tr->kappa)) : (tr->net.num_atoms != 1 || !td_ok(td))) return false;
+    if (update_branches(update_kind(td)) == 1 && !tr->target) return false;
+  }
   if (tr->net.num_layers > 1 && !tr->weights_t) return false;
   if ((td != nullptr || tr->apply_update) && !std::isfinite(tr->lr)) return false;
   if (tr->apply_update && (td == nullptr || td->optimizer == BLE_TD_OPT_ADAM) &&
@@ -1449,6 +1463,7 @@ bool update_ok(const ble_qnet_train_f32* tr, const ble_td_f32* td, const ble_tra
 struct TrainStep {
   const ble_qnet_train_f32* tr;
   const ble_td_f32* td;
+  const ble_ppo_f32* ppo;
   const ble_train_batch_f32* bt;
   void* stream;
   const QnetShape s;
@@ -1457,15 +1472,15 @@ struct TrainStep {
   const int64_t n, ld;
   float* const ws;
 
-  TrainStep(const ble_qnet_train_f32* tr_, const ble_td_f32* td_, const ble_train_batch_f32* bt_, void* stream_)
-      : tr(tr_), td(td_), bt(bt_), stream(stream_), s(qnet_shape(&tr_->net)), kind(update_kind(td_)), branches(update_branches(kind)),
+  TrainStep(const ble_qnet_train_f32* tr_, const ble_td_f32* td_, const ble_ppo_f32* ppo_, const ble_train_batch_f32* bt_, void* stream_)
+      : tr(tr_), td(td_), ppo(ppo_), bt(bt_), stream(stream_), s(qnet_shape(&tr_->net)), kind(update_kind(td_, ppo_)), branches(update_branches(kind)),
         lay(train_layout(s, branches, tr_->net.num_atoms, bt_->batch)), n(bt_->batch), ld(lay.ld), ws(tr_->workspace) {}
   float* acts(int l, int br = 0) const { return ws + lay.acts + (branches * l + br) * n * ld; }      // the online network's kept output of layer l
 
   // a kind with a target network: the target's pass on next_state (ping-pong, its logits end in target_logits); then the online
-  // network once per branch, on state and (SARSA) on next_state, every layer kept
+  // network once per branch, on state and (SARSA) on next_state, every layer kept.  PPO has no target pass.
   int forward() const {
-    if (branches == 1) {
+    if (branches == 1 && kind != kKindPpo) {
       const int status = launch_dense_stack(s, tr->target, bt->next_state, bt->state_stride, n,
                                             DenseOut{ws + lay.scratch, false, ws + lay.target_logits}, stream);
       if (status != BLE_OK) return status;
@@ -1481,6 +1496,10 @@ struct TrainStep {
   int loss(float* row_loss, uint32_t* err_flags) const {
     const float* logits = acts(s.layers - 1);
     const float* other = branches == 2 ? acts(s.layers - 1, 1) : ws + lay.target_logits;
+    if (kind == kKindPpo)      // (aux where the other kinds write targets)
+      return launch_grid(ble_ppo_loss_kernel, dim3((unsigned)n), kTrainLossBlock, stream, logits, ld, (const float*)bt->ret,
+                         (const uint8_t*)bt->action, ppo->old_logp, ppo->advantage, ppo->clip, ppo->value_coef, ppo->entropy_coef, n,
+                         ws + lay.targets, ws + lay.dlogits, row_loss, err_flags);
     if (kind == kKindQr)
       return launch_grid(ble_qr_loss_kernel, dim3((unsigned)n), kTrainLossBlock, stream, logits, other, ld, tr->net.num_actions,
                          tr->net.num_atoms, (const float*)bt->ret, (const float*)bt->discount, (const uint8_t*)bt->action, tr->kappa, n,
@@ -1540,12 +1559,13 @@ struct TrainStep {
   }
 };
 
-// ble_qnet_train_step_f32 (td == nullptr) and ble_qnet_td_step_f32: forward, loss, backward, optimiser.
+// ble_qnet_train_step_f32 (td == nullptr), ble_qnet_td_step_f32 and ble_qnet_ppo_step_f32 (ppo != nullptr): forward, loss, backward,
+// optimiser.
 int launch_update(const ble_qnet_train_f32* tr, const ble_td_f32* td, const ble_train_batch_f32* bt, float* loss, uint32_t* err_flags,
-                  void* stream) {
-  if (!update_ok(tr, td, bt, loss)) return BLE_E_INVALID_ARG;
+                  void* stream, const ble_ppo_f32* ppo = nullptr) {
+  if (!update_ok(tr, td, ppo, bt, loss)) return BLE_E_INVALID_ARG;
   if (bt->batch == 0) return BLE_OK;
-  const TrainStep t(tr, td, bt, stream);
+  const TrainStep t(tr, td, ppo, bt, stream);
   if (const int status = t.forward(); status != BLE_OK) return status;
   if (const int status = t.loss(loss, err_flags); status != BLE_OK) return status;
   if (const int status = t.backward(); status != BLE_OK) return status;
@@ -1628,6 +1648,52 @@ int ble_qnet_td_step_f32(const ble_qnet_train_f32* tr, const ble_td_f32* td, con
 int ble_qnet_explore_u8(const ble_explore_f32* ex, uint8_t* action, void* stream) {
   if (!ex || !action || ex->n < 0 || ex->n > 4LL * 2147483647LL * 256 || !(ex->epsilon >= 0.0f && ex->epsilon <= 1.0f)) return BLE_E_INVALID_ARG;
   return launch(ble_explore_kernel, ex->n, 256, 256, stream, action, (int64_t)ex->n, ex->epsilon, (uint64_t)ex->seed, (uint64_t)ex->step);
+}
+
+// ---------------------------------------------------------------------------------------------------------------- on-policy training
+int ble_ac_act_f32(const ble_qnet_f32* net, const ble_ac_rows_f32* rows, float* scratch, const ble_ac_sample* sample, void* stream) {
+  if (!qnet_ok(net) || net->num_atoms != 2 || !net->weights || !rows || !rows->obs || !scratch || !rows->action || !rows->logp || !rows->value ||
+      rows->n < 0 || rows->obs_row_stride < BLE_OBS_DIM)
+    return BLE_E_INVALID_ARG;
+  if (sample != nullptr && (!sample->step || sample->env_offset < 0)) return BLE_E_INVALID_ARG;
+  if (!aligned(15, net->weights, scratch)) return BLE_E_INVALID_ARG;
+  const QnetShape s = qnet_shape(net);
+  const int64_t ld = s.ld, n = rows->n;
+  if ((ld / kQnetCols) * ((n + kQnetRows - 1) / kQnetRows) > 2147483647LL) return BLE_E_INVALID_ARG;
+  if (n == 0) return BLE_OK;
+  const int status = launch_dense_stack(s, net->weights, rows->obs, rows->obs_row_stride, n, DenseOut{scratch, false, nullptr}, stream);
+  if (status != BLE_OK) return status;
+  return launch(ble_ac_head_kernel, n, kQnetHeadBlock, kQnetHeadBlock, stream, (const float*)(scratch + ((s.layers - 1) & 1) * n * ld), ld,
+                (uint64_t)(sample ? sample->seed : 0), (int64_t)(sample ? sample->env_offset : 0),
+                (const unsigned long long*)(sample ? sample->step : nullptr), rows->action, rows->logp, rows->value, rows->probs, n);
+}
+
+namespace {
+bool gae_sizes_ok(const ble_gae_block_f32* g) {
+  return g != nullptr && g->steps >= 0 && g->num_envs >= 0 && g->num_envs <= (1LL << 32) && g->steps <= (1LL << 40) &&
+         (g->num_envs == 0 || g->steps <= (1LL << 40) / g->num_envs);
+}
+}  // namespace
+
+int ble_gae_f32(const ble_gae_block_f32* g, void* stream) {
+  if (!gae_sizes_ok(g) || !std::isfinite(g->gamma) || !std::isfinite(g->lambda) || !g->reward || !g->value || !g->boot_value || !g->terminal ||
+      !g->episode_end || !g->advantage || !g->ret)
+    return BLE_E_INVALID_ARG;
+  if (g->steps == 0) return BLE_OK;
+  return launch(ble_gae_kernel, g->num_envs, 256, 256, stream, g->reward, g->value, g->boot_value, g->terminal, g->episode_end, g->gamma,
+                g->lambda, g->advantage, g->ret, (int64_t)g->steps, (int64_t)g->num_envs);
+}
+
+int ble_adv_normalize_f32(const ble_gae_block_f32* g, void* stream) {
+  if (!gae_sizes_ok(g) || !g->advantage) return BLE_E_INVALID_ARG;
+  const int64_t m = g->steps * g->num_envs;
+  if (m == 0) return BLE_OK;
+  return launch_grid(ble_adv_normalize_kernel, dim3(1), kAdvNormBlock, stream, g->advantage, m);
+}
+
+int ble_qnet_ppo_step_f32(const ble_qnet_train_f32* tr, const ble_ppo_f32* ppo, const ble_train_batch_f32* bt, float* loss, uint32_t* err_flags,
+                          void* stream) {
+  return ppo != nullptr ? launch_update(tr, nullptr, bt, loss, err_flags, stream, ppo) : BLE_E_INVALID_ARG;
 }
 
 // ---------------------------------------------------------------------------------------------------------------- prioritized replay

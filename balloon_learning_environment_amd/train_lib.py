@@ -159,3 +159,48 @@ def run_online_loop_vec(env, agent, *, num_iterations: int, steps_per_iteration:
     agent.check_errors()
     stats.append(book.finish_iteration(steps_per_iteration))
   return stats
+
+
+def run_ppo_loop_vec(env, trainer, rollout, *, num_iterations: int, epochs: int = 4, batch_size: int, max_episode_length: int = 960,
+                     capture_graph: bool = True) -> List[dict]:
+  """Trains an on-policy learner (agents/actor_critic.py: PPOTrainer with a VecRolloutBuffer of T steps) on `env` (auto_reset).  Each
+  iteration collects T vector steps with the sampled policy -- the episode limit as in run_training_loop_vec: a lane reaching it ends
+  its episode without a terminal and restarts --, takes the bootstrap value from one more act on the last observation (its draw is not
+  used), computes the advantages over the [T, N] block (rollout.finish) and runs `epochs` passes of minibatches of batch_size rows, each
+  one update; then the block is discarded.
+
+  Returns run_training_loop_vec's dicts (mean_loss over the iteration's updates; transitions counts the collected ones).  The only host
+  synchronisation is the end of an iteration."""
+  n, dev_ = env.num_envs, env.device
+  assert rollout.num_envs == n, 'the rollout block has one column per environment'
+  steps = rollout.horizon
+  obs = env.reset()
+  actions = torch.zeros(n, dtype=torch.uint8, device=dev_)
+  logp = torch.zeros(n, dtype=torch.float32, device=dev_)
+  value = torch.zeros(n, dtype=torch.float32, device=dev_)
+  book = _EpisodeBook(n, dev_, max_episode_length)
+  captured = False
+  stats = []
+  for _ in range(num_iterations):
+    for t in range(steps):
+      trainer.act(obs, actions, logp, value)
+      end_mask = book.end_mask()
+      next_obs, reward, terminal = env.step(actions, end_mask=end_mask)
+      episode_end = terminal | end_mask
+      rollout.add(t, obs, actions, logp, value, reward, terminal, episode_end)
+      book.step(reward, episode_end)
+      obs = next_obs
+    trainer.act(obs, actions, logp, value)
+    rollout.finish(value, trainer.gamma, trainer.lam, trainer.normalize_advantage)
+    for _ in range(epochs):
+      for batch in rollout.minibatches(batch_size):
+        if capture_graph and not captured:
+          loss = trainer.capture(batch)                     # (its first, eager update is a real one)
+          captured = True
+        else:
+          loss = trainer.train_step(batch)
+        book.update(loss)
+    env.check_errors()
+    trainer.check_errors()
+    stats.append(book.finish_iteration(steps))
+  return stats

@@ -788,6 +788,95 @@ typedef struct ble_explore_f32 {
 int ble_qnet_explore_u8(const ble_explore_f32* ex, uint8_t* action, void* stream);
 
 /*
+ * On-policy training (additive to ABI 5): an actor-critic is a network with num_atoms == 2 whose six outputs z[a * 2 + j]
+ * are read as: policy logit of action a = z[2a], state value V = z[1]; z[3] and z[5] are not read and receive a zero gradient.
+ * fp32, one rounding per operation, every branch a select, no floating-point atomics.  As with the other training entry points every
+ * size travels in a descriptor (no int64_t argument).
+ *
+ * log-softmax of the three policy logits (both heads): m = max z, e_a = expf(z_a - m), S = (e0 + e1) + e2, lp_a = (z_a - m) - logf(S),
+ * p_a = e_a / S.  Finite logits give finite lp_a.
+ */
+typedef struct ble_ac_rows_f32 {
+  int64_t n;                   /* rows, >= 0 */
+  int64_t obs_row_stride;      /* floats between rows, >= BLE_OBS_DIM */
+  const float* obs;            /* device [n] rows of BLE_OBS_DIM features */
+  uint8_t* action;             /* device [n] */
+  float* logp;                 /* device [n]: lp of the action */
+  float* value;                /* device [n]: z[1] */
+  float* probs;                /* optional device [n][3] */
+} ble_ac_rows_f32;
+
+/* The sampled head: row i draws u = (w >> 8) 2^-24, w the first 32-bit word of the Philox stream keyed by (seed ^ 0x4143544F52,
+ * env_offset + i, *step) (ble_qnet_explore_u8's keying under another constant), and takes action = u < p0 ? 0 : (u < p0 + p1 ? 1 : 2).
+ * The draw of environment env_offset + i at *step does not depend on n or on the row's position.  *step is read, not advanced. */
+typedef struct ble_ac_sample {
+  unsigned long long seed;
+  int64_t env_offset;          /* >= 0 */
+  const unsigned long long* step; /* device */
+  int64_t reserved_;           /* 0 */
+} ble_ac_sample;
+
+/*
+ * ble_ac_act_f32: ble_qnet_forward_f32's Dense stack on rows->obs (the same instructions: the same logits' bits), then one lane per
+ * row.  sample == NULL: greedy, argmax over z[0], z[2], z[4] with ble_qnet_forward_f32's rule (the lowest index among equal maxima;
+ * the first NaN).  scratch: ble_qnet_workspace_f32(net, n)'s scratch_floats, 16-byte aligned.  net->num_atoms must be 2.
+ */
+int ble_ac_act_f32(const ble_qnet_f32* net, const ble_ac_rows_f32* rows, float* scratch, const ble_ac_sample* sample, void* stream);
+
+/*
+ * A rollout block of T steps of N environments, every array [T][N] (boot_value [N]): generalised advantage estimation, t descending
+ * from T - 1 with A_next = 0:
+ *   nv = t == T - 1 ? boot_value[e] : value[t + 1][e];  boot = terminal ? 0 : (episode_end ? value[t][e] : nv);
+ *   delta = (reward + gamma boot) - value[t][e];  A = delta + (gamma lambda) (episode_end ? 0 : A_next);
+ *   advantage[t][e] = A;  ret[t][e] = A + value[t][e].
+ * episode_end is terminal | time limit.  A terminal step bootstraps nothing; a step cut by the time limit, whose next observation
+ * already belongs to the new episode, bootstraps from its own value; both cut the trace.
+ */
+typedef struct ble_gae_block_f32 {
+  int64_t steps;               /* T, >= 0 */
+  int64_t num_envs;            /* N, >= 0; T N <= 2^40 */
+  float gamma, lambda;         /* finite */
+  const float* reward;
+  const float* value;
+  const float* boot_value;
+  const uint8_t* terminal;
+  const uint8_t* episode_end;
+  float* advantage;
+  float* ret;
+} ble_gae_block_f32;
+
+/* Writes advantage and ret, nothing else.  T N == 0 launches nothing. */
+int ble_gae_f32(const ble_gae_block_f32* gae, void* stream);
+
+/* In place over the M = T N advantages of the block, float64, one 256-thread workgroup in a fixed order (thread k sums elements k,
+ * k + 256, ... ascending, thread 0 adds the 256 partials ascending): mean = S / M, var = sum (A - mean)^2 / M by a second pass of the
+ * same shape, A <- (float)((A - mean) / (sqrt(var) + 1e-8)).  Reads only gae->steps, num_envs and advantage. */
+int ble_adv_normalize_f32(const ble_gae_block_f32* gae, void* stream);
+
+typedef struct ble_ppo_f32 {
+  float clip;                  /* epsilon: finite, > 0 */
+  float value_coef;            /* c_v, finite */
+  float entropy_coef;          /* c_e, finite */
+  int32_t reserved_;           /* 0 */
+  const float* old_logp;       /* device [B]: lp of the batch action when it was taken */
+  const float* advantage;      /* device [B] */
+} ble_ppo_f32;
+
+/*
+ * ble_qnet_ppo_step_f32: one clipped-PPO update of a two-atom network on batch: ble_qnet_train_step_f32's stages without the target
+ * pass -- the online forward on batch->state with every layer kept, the loss below and its dL/dlogits, the same backward, then Adam
+ * under apply_update.  tr->target, batch->next_state, batch->discount and tr->kappa are not read and may be NULL; batch->ret is R.
+ * The workspace is ble_qnet_train_workspace_f32's; where the other kinds write targets ([B][2] floats) it writes aux[b] = (lp_act, H).
+ * Per row, with A = advantage[b], (lp, p) the log-softmax of z[0], z[2], z[4]:
+ *   H = -((p0 lp0 + p1 lp1) + p2 lp2);  rho = expf(lp_act - old_logp[b]);  s1 = rho A;  s2 = clamp(rho, 1 - clip, 1 + clip) A;
+ *   active = s1 <= s2;  L_b = (-(active ? s1 : s2) + c_v (z[1] - R)^2) - c_e H;
+ *   dL/dz[2a] = ((active ? -((A rho) ((a == act) - p_a)) : 0) + c_e (p_a (lp_a + H))) / B;  dL/dz[1] = (2 c_v (z[1] - R)) / B.
+ * An action >= 3 sets BLE_FLAG_TRAIN_ACTION and zeroes the row.  B == 0 launches nothing.
+ */
+int ble_qnet_ppo_step_f32(const ble_qnet_train_f32* tr, const ble_ppo_f32* ppo, const ble_train_batch_f32* batch, float* loss,
+                          uint32_t* err_flags, void* stream);
+
+/*
  * Prioritized n-step replay (additive to ABI 5): Dopamine 4.0.0's OutOfGraphPrioritizedReplayBuffer over the ring above.
  * An fp64 sum tree over capacity x num_envs leaves: leaf (t % capacity) num_envs + env is the n-step window that starts at ring row t
  * of that environment.  A heap padded to a power of two: nodes[1] is the root, nodes[padded + i] leaf i, nodes[0] unused, the padded
