@@ -1,7 +1,8 @@
 """A NumPy restatement of the on-policy kernels (csrc/ble_actor.h), written from their contract: the log-softmax of the
 three policy logits, the float32 inverse-CDF draw, generalised advantage estimation in float32 (one rounding per operation, the
-kernel's order) and in float64, the float64 advantage normalisation, the float64 PPO loss with its dL/dlogits, and the actor stream's
-Philox words from a g++ build of the generator (actor_draws.cpp).  TEST TOOLING."""
+kernel's order) and in float64 with the bound float32 arithmetic puts between them, the float64 advantage normalisation, its
+restatement in the kernel's summation order and the inputs that tell it from its likely mistakes, the float64 PPO loss with its
+dL/dlogits, and the actor stream's Philox words from a g++ build of the generator (actor_draws.cpp).  TEST TOOLING."""
 import ctypes
 import os
 import subprocess
@@ -86,12 +87,85 @@ def gae_f64(reward, value, boot_value, terminal, episode_end, gamma, lam):
   return _gae(reward, value, boot_value, terminal, episode_end, gamma, lam, np.float64)
 
 
+def gae_f32_error_bound(reward, value, boot_value, terminal, episode_end, gamma, lam):
+  """E [T, N] float64 with |gae_f32 - gae_f64| <= E for the advantages, to first order in u = 2^-24.  A step rounds five operations
+  (gamma boot, r + ., . - v, gl carry, delta + .), each by at most u times a magnitude that
+    M_t = |r_t| + gamma |boot_t| + |v_t| + gamma lambda (end_t ? 0 : M_{t+1})
+  bounds, and carries gamma lambda of the error of step t + 1 unless an end cuts the trace:
+    E_t = gamma lambda (end_t ? 0 : E_{t+1}) + 5 u M_t."""
+  reward, value, boot_value = (np.asarray(x, np.float64) for x in (reward, value, boot_value))
+  terminal, episode_end = np.asarray(terminal).astype(bool), np.asarray(episode_end).astype(bool)
+  steps, n = reward.shape
+  gl = float(gamma) * float(lam)
+  u = 2.0 ** -24
+  bound = np.zeros((steps, n))
+  m_next, e_next = np.zeros(n), np.zeros(n)
+  for t in range(steps - 1, -1, -1):
+    nv = boot_value if t == steps - 1 else value[t + 1]
+    boot = np.where(terminal[t], 0.0, np.where(episode_end[t], value[t], nv))
+    m = np.abs(reward[t]) + gamma * np.abs(boot) + np.abs(value[t]) + gl * np.where(episode_end[t], 0.0, m_next)
+    e = gl * np.where(episode_end[t], 0.0, e_next) + 5.0 * u * m
+    bound[t] = e
+    m_next, e_next = m, e
+  return bound
+
+
 def normalize_f64(adv):
   """(A - mean) / (sqrt(var) + 1e-8) in float64 (var / M), any summation order."""
   a = np.asarray(adv, np.float64)
   mean = a.sum() / a.size
   var = ((a - mean) ** 2).sum() / a.size
   return (a - mean) / (np.sqrt(var) + 1e-8)
+
+
+NORM_BLOCK = 256
+
+
+def strided_sum(x):
+  """ble_adv_normalize_kernel's sum of a float64 vector: thread k adds elements k, k + 256, ... ascending from 0.0, then the 256
+  partials are added ascending from 0.0."""
+  x = np.asarray(x, np.float64).ravel()
+  padded = np.zeros(-(-max(x.size, 1) // NORM_BLOCK) * NORM_BLOCK)
+  padded[:x.size] = x                                 # (a trailing + 0.0 changes no partial: none is -0.0)
+  part = np.zeros(NORM_BLOCK)
+  for row in padded.reshape(-1, NORM_BLOCK):
+    part = part + row
+  total = 0.0
+  for p in part:
+    total = total + p
+  return total
+
+
+def normalize_ordered(adv):
+  """float32: ble_adv_normalize_kernel's stated order.  mean = strided_sum(A) / M; var = strided_sum((A - mean)^2) / M by a second
+  pass; (float)((A - mean) / (sqrt(var) + 1e-8)), all in float64 before the one rounding."""
+  a = np.asarray(adv, np.float32).astype(np.float64)
+  mean = strided_sum(a) / a.size
+  d = a - mean
+  den = np.sqrt(strided_sum(d * d) / a.size) + 1e-8
+  return (d / den).astype(np.float32)
+
+
+def normalisation_cases():
+  """{name: float32 advantages}: the inputs at which a mistake in the normalisation leaves the one-ulp bound (test_ppo_host.py shows
+  that each does, and that the stated order alone stays inside).  'normal_M': the block edges of the 256-thread stride; 'equal': all
+  advantages 1.75 (every partial sum exact, so mean == A and the outputs are 0 / 1e-8); 'tiny': sigma = 3e-8, where the 1e-8 is a
+  quarter of the denominator; 'offset': 1e4 +- 1e-2, where E[x^2] - mean^2 cancels; 'pair' and 'triple': M - 1 against M."""
+  cases = {}
+  for m in (1, 2, 255, 256, 257, 511, 513, 65537):
+    cases[f'normal_{m}'] = np.random.default_rng(m).standard_normal(m).astype(np.float32)
+  cases['equal'] = np.full(300, 1.75, np.float32)
+  cases['tiny'] = (np.random.default_rng(11).standard_normal(1025) * 3e-8).astype(np.float32)
+  cases['offset'] = (1e4 + np.random.default_rng(12).standard_normal(4097) * 1e-2).astype(np.float32)
+  cases['pair'] = np.array([1.0, 3.0], np.float32)
+  cases['triple'] = np.array([1.0, 2.0, 4.5], np.float32)
+  return cases
+
+
+def ulps_from(got, want64):
+  """|got - want| in float32 ulps of want (float64 array); where want == 0 the ulp is the smallest subnormal."""
+  ulp = np.spacing(np.abs(want64).astype(np.float32)).astype(np.float64)
+  return np.abs(np.asarray(got, np.float64) - want64) / ulp
 
 
 def ppo_loss(logits, action, old_logp, advantage, ret, clip=0.2, value_coef=0.5, entropy_coef=0.01):

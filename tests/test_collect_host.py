@@ -1,5 +1,5 @@
 """The twins of the acting and collecting half of training (collect_host.py: epsilon-greedy and the uniform replay draw)
-held to their own laws, and run_training_loop_vec's schedule on CPU tensors with recording fakes.  No GPU.
+held to their own laws, and run_training_loop_vec's schedule on CPU tensors with recording fakes (loop_fakes.py).  No GPU.
 
  * the twins' Philox is the published one (test_plan_host's known answers) and Streams pops out[3] first;
  * epsilon-greedy: explored count, chi-squared of the actions, correlations of the masks; the strict threshold uf < epsilon;
@@ -13,6 +13,7 @@ import scipy.stats
 import torch
 
 import collect_host
+import loop_fakes
 import plan_host
 import reset_draws_host
 import test_plan_host
@@ -144,82 +145,12 @@ def test_retry_and_failure_rings():
 
 
 # ------------------------------------------------------------------------------------------------- the schedule of run_training_loop_vec
-N_ENV, STEPS = 3, 14
-TERMINALS = {(0, 1), (1, 2), (5, 0)}                   # (step, env): staggers the three episode clocks
-# max_episode_length = 4: an environment's end_mask is set on the 4th step of its own episode
-END_MASK = {3: (1, 0, 0), 4: (0, 1, 0), 5: (0, 0, 1), 8: (0, 1, 0), 9: (1, 0, 1), 12: (0, 1, 0), 13: (1, 0, 1)}
+STEPS = 14
+N_ENV, END_MASK = loop_fakes.N_ENV, loop_fakes.END_MASK      # (three environments whose terminals stagger their episode clocks)
 # min_replay_history = 9 holds after step 2 (9 transitions), cursor > update_horizon = 4 after step 4: from step 4 on, 3 / 4 of an
 # update per step with the fraction carried: 0.75 -> 0, 1.5 -> 1, 1.25 -> 1, 1.0 -> 1, 0.75 -> 0, ...
 UPDATES = (0, 0, 0, 0, 0, 1, 1, 1, 0, 1, 1, 1, 0, 1)
-
-
-class _Log(list):
-  def named(self, name):
-    return [e[1:] for e in self if e[0] == name]
-
-
-class _FakeEnv:
-  num_envs, device = N_ENV, torch.device('cpu')
-
-  def __init__(self, log):
-    self.log, self.s = log, 0
-
-  def _obs(self):
-    return torch.full((N_ENV, 2), float(self.s))
-
-  def reset(self):
-    self.log.append(('reset',))
-    return self._obs()
-
-  def step(self, actions, end_mask=None):
-    s = self.s
-    terminal = torch.tensor([1 if (s, e) in TERMINALS else 0 for e in range(N_ENV)], dtype=torch.uint8)
-    reward = torch.tensor([1.0, 0.25, 0.0]) + s
-    self.log.append(('step', s, actions.clone(), end_mask.clone(), terminal.clone()))
-    self.s += 1
-    return self._obs(), reward, terminal
-
-  def check_errors(self):
-    self.log.append(('env_check',))
-
-
-class _FakeTrainer:
-  def __init__(self, log):
-    self.log, self.acts = log, 0
-
-  def act(self, obs, out):
-    out.copy_(torch.tensor([(self.acts + e) % 3 for e in range(N_ENV)], dtype=torch.uint8))
-    self.log.append(('act', self.acts, obs.clone()))
-    self.acts += 1
-    return out
-
-  def capture(self, replay, batch_size):
-    self.log.append(('update', 'capture', batch_size))
-    return torch.ones(batch_size)
-
-  def train_step(self, replay, batch_size):
-    self.log.append(('update', 'train_step', batch_size))
-    return torch.full((batch_size,), 3.0)
-
-  def sync_target(self):
-    self.log.append(('sync',))
-
-  def check_errors(self):
-    self.log.append(('trainer_check',))
-
-
-class _FakeReplay:
-  num_envs = N_ENV
-
-  def __init__(self, log, update_horizon=4):
-    self.log, self.cursor, self.update_horizon = log, 0, update_horizon
-
-  def add(self, obs, action, reward, terminal, episode_end=None):
-    self.log.append(('add', obs.clone(), action.clone(), reward.clone(), terminal.clone(), episode_end.clone()))
-    self.cursor += 1
-
-  def check_errors(self):
-    self.log.append(('replay_check',))
+_Log, _FakeEnv, _FakeTrainer, _FakeReplay = loop_fakes.Log, loop_fakes.FakeEnv, loop_fakes.FakeTrainer, loop_fakes.FakeReplay
 
 
 def _run(monkeypatch, epsilon, exploration=False, update_horizon=4, **kw):
@@ -241,8 +172,7 @@ def _run(monkeypatch, epsilon, exploration=False, update_horizon=4, **kw):
   return log, stats
 
 
-def _u8(values):
-  return torch.tensor(values, dtype=torch.uint8)
+_u8 = loop_fakes.u8
 
 
 def test_training_loop_schedule(monkeypatch):

@@ -3,14 +3,19 @@ restatement (ppo_host.py) and the float64 twins of the backward pass and Adam (t
 with its tolerances:
 
  * the head: probs, logp and value against the twin on the device's own float32 logits; the sampled action equals the float32 inverse
-   CDF of the device's probs at the twin's Philox uniform, exactly; a row's action at any n, position, stride and env_offset split;
-   the greedy rule with ties and NaN logits; the action frequencies over 64 steps x 300 rows;
- * generalised advantage estimation bit for bit against the float32 restatement, ends at t = 0, t = T - 1 and in runs, a NaN a select
-   must discard; the normalisation within one float32 ulp of float64;
- * loss, aux and dL/dlogits against the twin; exact zeros; clipped rows keep the entropy term alone; an action of 3; saturated logits;
+   CDF of the device's probs at the twin's Philox uniform, exactly, at the 256-lane block's edges too; a row's action at any n,
+   position, stride and env_offset split; the greedy rule with ties and NaN logits; the action frequencies over 64 steps x 300 rows;
+ * generalised advantage estimation bit for bit against the float32 restatement (T up to 960, N at the block's edges), ends at t = 0,
+   t = T - 1 and in runs, a NaN a select must discard; float32 against float64 inside a derived running bound;
+ * the normalisation within one float32 ulp of float64 on inputs that three mistakes (no 1e-8, M - 1, a one-pass variance) fail;
+ * minibatches: the five gathered tensors name the same rows, every kept row once per pass;
+ * loss, aux and dL/dlogits against the twin; exact zeros up to ld; clipped rows keep the entropy term alone; an action of 3;
+   saturated logits;
  * rows fed back with unchanged weights: the training forward's log-probability is the acting forward's, bit for bit (rho == 1);
  * the gradient image against float64 backprop at test_gpu_train.py's batch edges; Adam over 10 updates;
+ * head, loss, rho == 1 and gradient at the default (3, 256) and the reference-sized (8, 600) stack as well (WIDE);
  * determinism: two trainers, graph vs eager, a state_dict of trainer and rollout restored mid-iteration;
+ * run_ppo_loop_vec's block against a recording environment and a second trainer: obs, action, logp, value, ends, bootstrap, stats;
  * it learns test_gpu_train.py's contextual bandit on-policy; run_ppo_loop_vec end to end, its policy through eval_agent_vec.
 """
 import numpy as np
@@ -24,6 +29,7 @@ pytestmark = pytest.mark.gpu
 
 POLICY = [0, 2, 4]
 SHAPES = [(2, 64), (1, 0)]          # (layers, hidden): two Dense layers of 64, and the one-layer 1099 -> 6
+WIDE = [(3, 256), (8, 600)]         # actor_critic.init_params' default and the reference-sized stack: more than one column group
 
 
 @pytest.fixture(scope='module')
@@ -81,6 +87,13 @@ def _bits(a):
   return np.ascontiguousarray(a).view(np.uint32)
 
 
+def _rows(observations, start, n):
+  """n rows of the fixture from `start` on, tiled where it is too short."""
+  if start + n <= len(observations):
+    return observations[start:start + n]
+  return observations[(start + torch.arange(n, device=observations.device)) % len(observations)]
+
+
 def _logits(tr, ac, x):
   """The device's float32 logits [n, 6] of rows x (the training forward: an update that applies nothing)."""
   n = len(x)
@@ -99,12 +112,14 @@ def _act(agent, obs, probs=True):
 
 
 # ------------------------------------------------------------------------------------------------------------------------------ head
-@pytest.mark.parametrize('layers,hidden', SHAPES)
-@pytest.mark.parametrize('n', [1, 65, 300])
+@pytest.mark.parametrize('n,layers,hidden', [(n, l, h) for l, h in SHAPES for n in (1, 65, 300)] + [(65, l, h) for l, h in WIDE] +
+                         [(n, 2, 64) for n in (255, 256, 257, 1025)])      # (the 256-lane block's edges, and past four blocks)
 def test_head_against_twin(mods, observations, draws, layers, hidden, n):
+  """Measured on an MI355X at (3, 256) | (8, 600), n = 65, the worst |device - twin|: probs 6.0e-8 | 6.0e-8 (half an ulp of a
+  probability), logp 2.4e-7 | 2.4e-7 at |logp| <= 1.24 | 1.12 -- what (2, 64) gives at n = 65 to 1025 too."""
   _, _, ac = mods
   _, tr = _trainer(mods, layers, hidden, seed=13)
-  obs = observations[100:100 + n]
+  obs = _rows(observations, 100, n)
   z = _logits(tr, ac, obs.cpu().numpy())
   lp64, p64 = ppo_host.log_softmax(z[:, POLICY])
   for step in range(3):
@@ -258,7 +273,7 @@ def _device_gae(ac, b, gamma, lam, normalize=False):
   return ro.advantage.cpu().numpy(), ro.ret.cpu().numpy()
 
 
-@pytest.mark.parametrize('steps,n', [(1, 1), (2, 65), (17, 300)])
+@pytest.mark.parametrize('steps,n', [(1, 1), (2, 65), (17, 300), (960, 3), (3, 255), (3, 256), (3, 257), (5, 1025)])
 def test_gae_bit_equal_to_float32_twin(mods, steps, n):
   ac = mods[2]
   for gamma, lam in ((0.993, 0.95), (0.9, 1.0), (0.5, 0.0)):
@@ -270,6 +285,10 @@ def test_gae_bit_equal_to_float32_twin(mods, steps, n):
       assert np.array_equal(_bits(g), _bits(w)), (name, gamma, lam, np.abs(g - w).max())
     w64 = ppo_host.gae_f64(b['reward'], b['value'], b['boot'], b['terminal'], b['episode_end'], float(np.float32(gamma)), float(np.float32(lam)))
     assert np.allclose(got[0], w64[0], rtol=1e-4, atol=1e-4)
+    # what float32 allows: the running bound 5 u M_t, carried by gamma lambda and cut at an end (ppo_host.gae_f32_error_bound)
+    bound = ppo_host.gae_f32_error_bound(b['reward'], b['value'], b['boot'], b['terminal'], b['episode_end'], float(np.float32(gamma)),
+                                         float(np.float32(lam)))
+    assert (np.abs(got[0].astype(np.float64) - w64[0]) <= bound).all(), (gamma, lam, (np.abs(got[0] - w64[0]) / bound).max())
 
 
 @pytest.mark.parametrize('steps,n', [(1, 1), (2, 65), (17, 300)])
@@ -314,6 +333,80 @@ def test_normalisation_within_one_ulp_of_float64(mods, steps, n):
   assert abs(got.astype(np.float64).mean()) < 1e-6 and abs(got.astype(np.float64).std() - 1.0) < 1e-5
 
 
+NORM_CASES = ppo_host.normalisation_cases()
+
+
+@pytest.mark.parametrize('name', sorted(NORM_CASES))
+def test_normalisation_held_to_what_it_computes(mods, name):
+  """ppo_host.normalisation_cases through finish(normalize=True): within one float32 ulp of normalize_f64 and finite; exactly 0.0 for
+  M = 1 and for equal advantages.  test_ppo_host.py shows that dropping the 1e-8, dividing by M - 1 and a one-pass variance each leave
+  the bound on one of these inputs, and that the stated order stays inside on all.  A block of T = 1 whose every step is terminal with
+  value 0 has A = reward bit for bit (delta = (r + gamma 0) - 0, nothing carried), so the reward written is the advantage normalised:
+  ret, which is not normalised, shows it."""
+  ac = mods[2]
+  a = NORM_CASES[name]
+  m = len(a)
+  ro = ac.VecRolloutBuffer(m, 1, 'cuda')
+  ro.reward.copy_(torch.from_numpy(a).view(1, m))
+  ro.terminal.fill_(1)
+  ro.episode_end.fill_(1)
+  ro.finish(torch.zeros(m, device='cuda'), 0.993, 0.95, normalize=False)
+  assert np.array_equal(_bits(ro.advantage.cpu().numpy().ravel()), _bits(a))
+  ro.finish(torch.zeros(m, device='cuda'), 0.993, 0.95, normalize=True)
+  got = ro.advantage.cpu().numpy().ravel()
+  assert np.array_equal(_bits(ro.ret.cpu().numpy().ravel()), _bits(a))
+  want = ppo_host.normalize_f64(a)
+  err = ppo_host.ulps_from(got, want)
+  print(name, 'M', m, 'worst |A - A64| / ulp', err.max())
+  assert np.isfinite(got).all()
+  assert (err <= 1.0).all(), (name, err.max())
+  if name in ('normal_1', 'equal'):
+    assert not got.any() and not np.signbit(got).any()                 # exactly 0.0: (A - mean) = 0 over sqrt(0) + 1e-8
+  elif name == 'pair':
+    assert np.array_equal(got, np.array([-1.0, 1.0], np.float32) / np.float32(1 + 1e-8))      # var = 1 (/ M), not 2
+
+
+# -------------------------------------------------------------------------------------------------------------------------- minibatches
+def test_minibatches_gather_the_same_rows_once_per_pass(mods):
+  """N = 64, T = 8 with the row id written into every buffer a minibatch gathers: the five tensors of a minibatch name the same rows;
+  the 5 x 96 kept rows of a pass are distinct (32 dropped); the yielded object is one PPOBatch; a second pass has another order; a
+  generator restored with set_state repeats the first."""
+  ac = mods[2]
+  ro = ac.VecRolloutBuffer(64, 8, 'cuda')
+  ids = torch.arange(512, device='cuda')
+  ro.ret.view(-1).copy_(ids)
+  ro.advantage.view(-1).copy_(ids + 0.5)
+  ro.logp.view(-1).copy_(-ids)
+  ro.action.view(-1).copy_(ids % 3)
+  ro.obs.view(512, -1)[:, 0].copy_(ids)
+  state = ro.generator.get_state().clone()
+
+  def one_pass():
+    seen, first = [], None
+    for bt in ro.minibatches(96):
+      first = bt if first is None else first
+      assert bt is first and isinstance(bt, ac.PPOBatch) and bt.batch_size == 96
+      i = bt.ret.cpu().numpy()
+      assert np.array_equal(bt.advantage.cpu().numpy(), i + 0.5) and np.array_equal(bt.old_logp.cpu().numpy(), -i)
+      assert np.array_equal(bt.action.cpu().numpy(), i.astype(np.int64) % 3) and np.array_equal(bt.state[:, 0].cpu().numpy(), i)
+      assert not bt.state[:, 1:].any()
+      seen.append(i.astype(np.int64))
+    assert len(seen) == 5
+    seen = np.concatenate(seen)
+    assert len(set(seen.tolist())) == 480 and seen.min() >= 0 and seen.max() < 512
+    return seen
+
+  a, b = one_pass(), one_pass()
+  assert not np.array_equal(a, b) and not np.array_equal(a, np.sort(a))
+  ro.generator.set_state(state)
+  assert np.array_equal(one_pass(), a)
+  own = torch.Generator(device='cuda').manual_seed(5)                  # a generator handed in is the one used
+  state = own.get_state().clone()
+  c = np.concatenate([bt.ret.cpu().numpy() for bt in ro.minibatches(96, own)])
+  own.set_state(state)
+  assert np.array_equal(np.concatenate([bt.ret.cpu().numpy() for bt in ro.minibatches(96, own)]), c)
+
+
 # ------------------------------------------------------------------------------------------------------------------------------ loss
 _SHIFTS = np.array([0.05, 0.5, -0.5, -0.05, 0.4, -0.6, 0.0])          # log rho: inside the band, above it, below it
 _ADVS = np.array([1.3, 0.7, -0.9, -1.1, -0.4, 0.8, 0.6])
@@ -336,13 +429,13 @@ def _ppo_batch(mods, tr, observations, b, seed, invalid=()):
   return x, ac.PPOBatch.from_tensors(x, ret, act, old, adv, 'cuda'), (act, old, adv, ret)
 
 
-@pytest.mark.parametrize('layers,hidden', SHAPES)
-@pytest.mark.parametrize('b', [1, 32, 300])
+@pytest.mark.parametrize('b,layers,hidden', [(b, l, h) for l, h in SHAPES for b in (1, 32, 300)] + [(32, l, h) for l, h in WIDE])
 def test_loss_and_dlogits(mods, observations, layers, hidden, b):
   """Measured on an MI355X (both networks, B = 1, 32, 300), the worst |device - twin| / (2e-6 |twin| + 1e-7 scale): loss 0.26 (B = 300),
   aux 0.10, dlogits 0.15.  expf / logf keep every case inside test_gpu_td.py's _close bounds, which stand unwidened."""
   _, tr = _trainer(mods, layers, hidden)
   _, bt, (act, old, adv, ret) = _ppo_batch(mods, tr, observations, b, seed=b)
+  tr.views(b)['dlogits'].fill_(float('nan'))                           # every column up to ld is written by the call
   loss_d = tr.train_on_batch(bt, apply_update=False).cpu().numpy()
   tr.check_errors()
   v = {k: t.cpu().numpy() for k, t in tr.views(b).items() if k != 'acts'}
@@ -356,6 +449,7 @@ def test_loss_and_dlogits(mods, observations, layers, hidden, b):
   _close(v['aux'][:, 1], aux[:, 1], 'entropy')
   _close(v['dlogits'][:, :6], dlog, 'dlogits')
   assert not v['dlogits'][:, [3, 5]].any() and not v['dlogits'][:, 6:].any()
+  assert v['dlogits'].shape[1] >= max(hidden, 6) and not np.isnan(v['dlogits']).any()      # (the whole [B, ld] view)
   # clipped rows: the policy gradient is the entropy term alone -- what the same rows give at A = 0
   rho = np.exp(aux[:, 0] - old.astype(np.float64))
   clipped = ((rho > 1 + tr.clip) & (adv > 0)) | ((rho < 1 - tr.clip) & (adv < 0))
@@ -401,8 +495,8 @@ def test_saturated_logits_give_finite_loss_and_gradient(mods, observations, laye
 
 
 # -------------------------------------------------------------------------------------------------------------------------- rho == 1
-@pytest.mark.parametrize('layers,hidden', SHAPES)
-@pytest.mark.parametrize('n', [1, 65, 300])
+@pytest.mark.parametrize('n,layers,hidden', [(n, l, h) for l, h in SHAPES for n in (1, 65, 300)] +
+                         [(n, l, h) for l, h in WIDE for n in (1, 129, 300)])
 def test_rows_fed_back_unchanged_have_ratio_one(mods, observations, layers, hidden, n):
   """The training forward's log-probability of the action taken is the acting forward's, bit for bit: rho = exp(0) = 1 exactly, no row
   is clipped, and the policy loss is -A."""
@@ -418,6 +512,7 @@ def test_rows_fed_back_unchanged_have_ratio_one(mods, observations, layers, hidd
   assert np.array_equal(_bits(v['aux'][:, 0]), _bits(logp))
   assert np.array_equal(_bits(v['logits'][:, 1]), _bits(value))
   assert np.array_equal(loss, -adv)                                    # rho = 1, c_v = c_e = 0
+  assert adv.all() and np.array_equal(-loss / adv, np.ones(n, np.float32))      # rho = 1.0f exactly: the loss is -(rho A)
   _, _, dlog = ppo_host.ppo_loss(v['logits'], act, logp, adv, value, tr.clip, 0.0, 0.0)
   _close(v['dlogits'][:, :6], dlog, 'dlogits')
   assert (v['dlogits'][:, POLICY] != 0).any(axis=1).all()              # the unclipped gradient
@@ -427,8 +522,11 @@ def test_rows_fed_back_unchanged_have_ratio_one(mods, observations, layers, hidd
 EDGE_BATCHES = (1, 7, 9, 33, 129, 511, 513, 4097)          # test_gpu_train.py's batch edges of the backward pass
 
 
-@pytest.mark.parametrize('layers,hidden,b', [(1, 0, 32), (3, 37, 32), (2, 64, 600)] + [(2, 64, b) for b in EDGE_BATCHES])
+@pytest.mark.parametrize('layers,hidden,b', [(1, 0, 32), (3, 37, 32), (2, 64, 600)] + [(2, 64, b) for b in EDGE_BATCHES] +
+                         [(3, 256, 32), (8, 600, 32), (3, 256, 4097)])      # (4097: kWgradMaxSlabs' cap, at a wider ld than 64)
 def test_gradient_against_float64_backprop(mods, observations, layers, hidden, b):
+  """Measured on an MI355X, the worst |g - g64| / (1e-5 S): 0.015 at (3, 256, 32), 0.017 at (8, 600, 32), 0.018 at (3, 256, 4097);
+  0.023 (B = 511) is the worst at (2, 64)."""
   qnet, qnet_train, _ = mods
   params, tr = _trainer(mods, layers, hidden)
   x, bt, _ = _ppo_batch(mods, tr, observations, b, seed=4)
@@ -523,6 +621,118 @@ def test_determinism_graph_and_resume(mods):
   assert not np.array_equal(a.weights.cpu().numpy(), wa)
   obs = ro_a.obs[0]
   assert np.array_equal(_act(a, obs)[0], _act(d, obs)[0]) and int(d.act_step.item()) == int(a.act_step.item())
+
+
+# -------------------------------------------------------------------------------------------------------------- the loop's block contract
+class _RecordingEnv:
+  """Forwards reset, step, num_envs, device and check_errors of a VecBalloonEnv and keeps clones of what went in and out.  Before it
+  forwards step `burst_step` it adds 30 000 mol to mols_air of `burst_lanes` (far above the superpressure limit, as
+  test_gpu_scenarios.py does): those balloons burst in that step, so the block holds real terminals and their auto-resets."""
+
+  def __init__(self, env, burst_step, burst_lanes):
+    self.env, self.num_envs, self.device = env, env.num_envs, env.device
+    self.burst_step, self.burst_lanes = burst_step, list(burst_lanes)
+    self.reset_obs, self.steps = None, []
+
+  def reset(self):
+    obs = self.env.reset()
+    self.reset_obs = obs.clone()
+    return obs
+
+  def step(self, actions, end_mask=None):
+    if len(self.steps) == self.burst_step:
+      self.env.arena.sim.state['mols_air'][self.burst_lanes] += 30000.0
+    went_in = {'actions': actions.clone(), 'end_mask': end_mask.clone()}
+    obs, reward, terminal = self.env.step(actions, end_mask=end_mask)
+    self.steps.append({**went_in, 'obs': obs.clone(), 'reward': reward.clone(), 'terminal': terminal.clone()})
+    return obs, reward, terminal
+
+  def check_errors(self):
+    self.env.check_errors()
+
+
+LOOP_T, LOOP_N, LOOP_LIMIT, LOOP_SEED, BURST = 8, 64, 5, 4, (5, 40)
+
+
+def _recorded_loop(mods, normalize):
+  qnet, _, ac = mods
+  from balloon_learning_environment_amd import train_lib
+  from balloon_learning_environment_amd.env import balloon_env
+  env = _RecordingEnv(balloon_env.VecBalloonEnv(LOOP_N, seed=1), 2, BURST)
+  kw = {} if normalize else {'normalize_advantage': False}            # (True is the default)
+  tr = ac.PPOTrainer(qnet.QNetwork.from_params(ac.init_params('actor_critic', 2, 2, 64), num_atoms=2), lr=1e-3, seed=LOOP_SEED, **kw)
+  ro = ac.VecRolloutBuffer(LOOP_N, LOOP_T, 'cuda')
+  stats = train_lib.run_ppo_loop_vec(env, tr, ro, num_iterations=1, epochs=2, batch_size=128, max_episode_length=LOOP_LIMIT,
+                                     capture_graph=False)
+  return env, tr, ro, stats
+
+
+def test_loop_block_is_what_happened(mods, draws):
+  """One iteration of run_ppo_loop_vec through a recording environment, against a second trainer of the same parameters and seed whose
+  act_step is set to t: row t of the block is the observation the action was taken on (across auto-resets too) with that trainer's
+  action, logp and value there; reward and terminal are the environment's; episode_end = terminal | end_mask with the limit counted
+  per environment; boot_value is the value of act number T on the last observation; advantage and ret are gae_f32 of the block; the
+  stats count what happened.  With normalize_advantage (the default) ret stays and advantage is normalize_f64 of the twin's within
+  one ulp."""
+  qnet, _, ac = mods
+  env, tr, ro, stats = _recorded_loop(mods, normalize=False)
+  steps_n, n = LOOP_T, LOOP_N
+  assert len(env.steps) == steps_n and len(stats) == 1
+  twin = ac.PPOTrainer(qnet.QNetwork.from_params(ac.init_params('actor_critic', 2, 2, 64), num_atoms=2), lr=1e-3, seed=LOOP_SEED)
+  blk = {k: getattr(ro, k).cpu().numpy() for k in ('action', 'logp', 'value', 'reward', 'terminal', 'episode_end', 'boot_value', 'advantage', 'ret')}
+  ep_steps = np.zeros(n, np.int64)
+  limit_ends = 0
+  for t in range(steps_n):
+    rec = env.steps[t]
+    seen = env.reset_obs if t == 0 else env.steps[t - 1]['obs']
+    assert torch.equal(ro.obs[t, :, :1099].view(torch.int32), seen.view(torch.int32)), (t, 'obs[t] is not the observation acted on')
+    assert not ro.obs[t, :, 1099:].any()
+    twin.act_step.fill_(t)
+    act, logp, value, probs = _act(twin, seen)
+    assert np.array_equal(act, ppo_host.sample(probs, ppo_host.uniform24(draws(LOOP_SEED, 0, n, t)))), t
+    assert np.array_equal(blk['action'][t], act) and np.array_equal(rec['actions'].cpu().numpy(), act), t
+    assert np.array_equal(_bits(blk['logp'][t]), _bits(logp)) and np.array_equal(_bits(blk['value'][t]), _bits(value)), t
+    assert np.array_equal(_bits(blk['reward'][t]), _bits(rec['reward'].cpu().numpy())), t
+    terminal, end_mask = rec['terminal'].cpu().numpy(), rec['end_mask'].cpu().numpy()
+    assert np.array_equal(blk['terminal'][t], terminal), t
+    want_mask = (ep_steps + 1 >= LOOP_LIMIT).astype(np.uint8)          # the 5th step of the environment's own episode
+    assert np.array_equal(end_mask, want_mask), (t, end_mask)
+    assert np.array_equal(blk['episode_end'][t], terminal | end_mask), t
+    limit_ends += int((want_mask & ~terminal & 1).sum())
+    ep_steps = np.where((terminal | end_mask) != 0, 0, ep_steps + 1)
+  assert blk['terminal'][2, list(BURST)].all() and blk['terminal'].sum() >= 2, 'the burst lanes are terminal at t = 2'
+  others = np.setdiff1d(np.arange(n), BURST)
+  if not blk['terminal'][:, others].any():                             # (no other balloon died: the two clocks, spelt out)
+    assert np.flatnonzero(blk['episode_end'][:, others].any(axis=1)).tolist() == [4]
+    assert [np.flatnonzero(blk['episode_end'][:, e]).tolist() for e in BURST] == [[2, 7], [2, 7]]
+  assert limit_ends >= n - 2
+  # the bootstrap: act number T on the last returned observation; the counter ends at T + 1
+  twin.act_step.fill_(steps_n)
+  _, _, boot, _ = _act(twin, env.steps[-1]['obs'])
+  assert np.array_equal(_bits(blk['boot_value']), _bits(boot))
+  assert int(tr.act_step.item()) == steps_n + 1
+  adv, ret = ppo_host.gae_f32(blk['reward'], blk['value'], blk['boot_value'], blk['terminal'], blk['episode_end'], tr.gamma, tr.lam)
+  assert np.array_equal(_bits(blk['advantage']), _bits(adv)) and np.array_equal(_bits(blk['ret']), _bits(ret))
+  # the stats count what happened
+  s = stats[0]
+  assert s['episodes'] == int(blk['episode_end'].astype(bool).sum()) and s['transitions'] == steps_n * n == 512
+  assert s['updates'] == 2 * (512 // 128) and np.isfinite(s['mean_loss'])
+  assert s['time_within_radius'] == float((blk['reward'] > 0.5).mean())
+  running, done = np.zeros(n), []
+  for t in range(steps_n):
+    running += blk['reward'][t].astype(np.float64)
+    ended = blk['episode_end'][t] != 0
+    done += running[ended].tolist()
+    running[ended] = 0.0
+  # (torch's float32 reduction order is not ours: at most ~100 terms of magnitude at most 5 keep it three orders inside 1e-5)
+  assert len(done) == s['episodes'] and abs(s['mean_return'] - np.mean(done)) <= 1e-5 * abs(np.mean(done)), (s['mean_return'], np.mean(done))
+  # the same loop with the normalisation
+  env_n, _, ro_n, stats_n = _recorded_loop(mods, normalize=True)
+  assert np.array_equal(_bits(ro_n.ret.cpu().numpy()), _bits(ret)), 'the returns are not normalised'
+  err = ppo_host.ulps_from(ro_n.advantage.cpu().numpy(), ppo_host.normalize_f64(adv))
+  print('loop: episodes', s['episodes'], 'terminals', int(blk['terminal'].sum()), 'normalised advantage, worst ulp', err.max())
+  assert (err <= 1.0).all(), err.max()
+  assert stats_n[0]['episodes'] == s['episodes'] and stats_n[0]['mean_return'] == s['mean_return']
 
 
 # ---------------------------------------------------------------------------------------------------------------------------- learns

@@ -1,5 +1,7 @@
 """The float64 / float32 restatement of the on-policy kernels (ppo_host.py), CPU only: its dL/dlogits against torch autograd of the same
-objective, generalised advantage estimation on cases worked by hand and its two limits, the actor stream against the epsilon-greedy
+objective, generalised advantage estimation on cases worked by hand and its two limits, float32 against float64 inside the derived
+running bound, the normalisation's stated order against float64 and against three mistakes on the inputs the GPU test uses,
+run_ppo_loop_vec's call order and block contract on recording fakes (loop_fakes.py), the actor stream against the epsilon-greedy
 stream, the descriptors against the header, and init_params('actor_critic')."""
 import ctypes
 import os
@@ -168,6 +170,180 @@ def test_normalize_f64():
   a = np.random.default_rng(2).standard_normal(1000).astype(np.float32) * 3 + 5
   out = ppo_host.normalize_f64(a)
   assert abs(out.mean()) < 1e-12 and abs(out.std() - 1.0) < 1e-7
+
+
+def _flight_block(steps, n, seed):
+  """A block at the flight's scale: rewards in [0, 1], values about 60 +- 30, 1 % terminals and 1 % time-limit ends."""
+  rng = np.random.default_rng(seed)
+  term = rng.random((steps, n)) < 0.01
+  end = term | (rng.random((steps, n)) < 0.01)
+  return (rng.random((steps, n)).astype(np.float32), (60 + 30 * rng.standard_normal((steps, n))).astype(np.float32),
+          (60 + 30 * rng.standard_normal(n)).astype(np.float32), term.astype(np.uint8), end.astype(np.uint8))
+
+
+@pytest.mark.parametrize('steps,n', [(960, 7), (17, 300), (64, 1025)])
+def test_gae_f32_within_its_derived_bound_of_f64(steps, n):
+  """|gae_f32 - gae_f64| <= gae_f32_error_bound, the running bound 5 u M_t carried by gamma lambda and cut at an end.  Measured: at
+  most 0.40 of the bound over these blocks (the worst at 17 x 300)."""
+  worst = 0.0
+  for gamma, lam in ((0.993, 0.95), (0.999, 1.0), (0.5, 0.0)):
+    block = _flight_block(steps, n, seed=steps + n)
+    g64, l64 = float(np.float32(gamma)), float(np.float32(lam))
+    a32, _ = ppo_host.gae_f32(*block, gamma, lam)
+    a64, _ = ppo_host.gae_f64(*block, g64, l64)
+    bound = ppo_host.gae_f32_error_bound(*block, g64, l64)
+    assert block[3].any() and (block[4] != block[3]).any() and (bound > 0).all()
+    share = float((np.abs(a32.astype(np.float64) - a64) / bound).max())
+    worst = max(worst, share)
+    assert share <= 1.0, (gamma, lam, share)
+  print('T x N', steps, n, 'worst |a32 - a64| / E', worst)
+
+
+def test_gae_bound_is_cut_at_an_end():
+  """By hand, gamma = lambda = 0.5, T = 2, one environment: without an end M_1 = 1 + .5 * 8 + 2 = 7, M_0 = 1 + .5 * 2 + 4 + .25 * 7 =
+  7.75, E_0 = .25 * 5u * 7 + 5u * 7.75; with a time-limit end at t = 0 the step bootstraps from its own value and carries nothing."""
+  u = 2.0 ** -24
+  r, v, boot, none = np.ones((2, 1)), np.array([[4.0], [2.0]]), np.array([8.0]), np.zeros((2, 1), np.uint8)
+  e = ppo_host.gae_f32_error_bound(r, v, boot, none, none, 0.5, 0.5)
+  assert e[1, 0] == 5 * u * 7 and e[0, 0] == 0.25 * (5 * u * 7) + 5 * u * 7.75
+  end = np.array([[1], [0]], np.uint8)
+  e = ppo_host.gae_f32_error_bound(r, v, boot, none, end, 0.5, 0.5)
+  assert e[0, 0] == 5 * u * (1 + 0.5 * 4 + 4)
+  e = ppo_host.gae_f32_error_bound(r, v, boot, end, end, 0.5, 0.5)
+  assert e[0, 0] == 5 * u * (1 + 4)
+
+
+# ---- the advantage normalisation -----------------------------------------------------------------------------------------------------
+def test_strided_sum_is_the_stated_order():
+  """Thread k owns k, k + 256, ...; the partials are added ascending.  1e16 and ones: the order decides which ones are absorbed."""
+  x = np.zeros(513)
+  x[0], x[256], x[512], x[1] = 1e16, 1.0, 1.0, 2.0
+  # thread 0: (1e16 + 1) + 1 = 1e16 (each 1 is absorbed); then + thread 1's 2 = 1e16 + 2
+  assert ppo_host.strided_sum(x) == 1e16 + 2.0
+  assert ppo_host.strided_sum(np.arange(1, 1001)) == 500500.0 and ppo_host.strided_sum([3.0]) == 3.0
+
+
+def test_normalisation_inputs_tell_the_stated_kernel_from_three_mistakes():
+  """On every input of ppo_host.normalisation_cases the stated order lies within one float32 ulp of normalize_f64 (measured: at most
+  0.5); each mistake lies outside on the input that names it.  So the GPU test's one-ulp bound over these inputs passes the kernel
+  as stated and nothing else.  Measured ulps here (NumPy's default_rng as it is today): no epsilon 5.5e6 ('tiny'), 17 ('offset'),
+  NaN where every advantage is equal; M - 1 at least 1.2e2 (M = 65 537) on every input with M > 1 that is not constant, 2.5e6 on
+  'pair'; one pass 1.7e3 ('offset')."""
+  def no_epsilon(a):
+    a = a.astype(np.float64)
+    d = a - ppo_host.strided_sum(a) / a.size
+    with np.errstate(invalid='ignore', divide='ignore'):
+      return (d / np.sqrt(ppo_host.strided_sum(d * d) / a.size)).astype(np.float32)
+
+  def m_minus_one(a):
+    a = a.astype(np.float64)
+    d = a - ppo_host.strided_sum(a) / a.size
+    with np.errstate(invalid='ignore', divide='ignore'):
+      return (d / (np.sqrt(ppo_host.strided_sum(d * d) / (a.size - 1)) + 1e-8)).astype(np.float32)
+
+  def one_pass(a):
+    a = a.astype(np.float64)
+    mean = ppo_host.strided_sum(a) / a.size
+    var = ppo_host.strided_sum(a * a) / a.size - mean * mean
+    with np.errstate(invalid='ignore'):
+      return ((a - mean) / (np.sqrt(var) + 1e-8)).astype(np.float32)
+
+  def worst(f, a):
+    err = ppo_host.ulps_from(f(a), ppo_host.normalize_f64(a))
+    return float('inf') if np.isnan(err).any() else float(err.max())
+
+  cases = ppo_host.normalisation_cases()
+  assert [len(cases[f'normal_{m}']) for m in (1, 2, 255, 256, 257, 511, 513, 65537)] == [1, 2, 255, 256, 257, 511, 513, 65537]
+  assert (len(cases['equal']), len(cases['tiny']), len(cases['offset'])) == (300, 1025, 4097)
+  assert cases['pair'].tolist() == [1.0, 3.0] and cases['triple'].tolist() == [1.0, 2.0, 4.5]
+  for name, a in cases.items():
+    got = ppo_host.normalize_ordered(a)
+    w = worst(ppo_host.normalize_ordered, a)
+    print(name, 'ordered', w, 'no epsilon', worst(no_epsilon, a), 'M - 1', worst(m_minus_one, a), 'one pass', worst(one_pass, a))
+    assert got.dtype == np.float32 and np.isfinite(got).all() and w <= 1.0, (name, w)
+    if len(a) > 1:
+      assert worst(m_minus_one, a) > 1.0 or name == 'equal', name
+  assert not ppo_host.normalize_ordered(cases['normal_1']).any() and not ppo_host.normalize_ordered(cases['equal']).any()
+  assert not np.isfinite(no_epsilon(cases['equal'])).any() and not np.isfinite(no_epsilon(cases['normal_1'])).any()      # 0 / 0
+  assert worst(no_epsilon, cases['tiny']) > 1e3
+  assert worst(one_pass, cases['offset']) > 1e2
+  assert worst(m_minus_one, cases['pair']) > 1e3 and worst(m_minus_one, cases['triple']) > 1e3
+  # the pair by hand: mean 2, var 1 (not 2): -1 and 1 over 1 + 1e-8
+  assert np.array_equal(ppo_host.normalize_ordered(cases['pair']), np.array([-1.0, 1.0], np.float32) / np.float32(1 + 1e-8))
+
+
+# ---- the loop's schedule -------------------------------------------------------------------------------------------------------------
+def test_ppo_loop_call_order_and_block_contract():
+  """run_ppo_loop_vec on CPU tensors with recording fakes (loop_fakes.py), max_episode_length = 4, T = 7, two iterations: per step act,
+  end_mask, env.step(actions, end_mask=), add, book.step; one more act after step T - 1 whose value goes to finish; epochs x
+  (T N // batch_size) updates; the end_mask of an environment on the 4th step of its own episode, restarting after a terminal."""
+  import loop_fakes as lf
+  from balloon_learning_environment_amd import train_lib
+  horizon, epochs, batch = 7, 2, 4
+  log = lf.Log()
+  trainer = lf.FakePPOTrainer(log)
+  stats = train_lib.run_ppo_loop_vec(lf.FakeEnv(log), trainer, lf.FakeRollout(log, horizon), num_iterations=2, epochs=epochs,
+                                     batch_size=batch, max_episode_length=4)
+  per_pass = horizon * lf.N_ENV // batch
+  assert per_pass == 5
+  # the order of the calls of one iteration, twice; one reset
+  one = ['act', 'step', 'add'] * horizon + ['act', 'finish'] + (['pass'] + ['update'] * per_pass) * epochs + ['env_check', 'trainer_check']
+  assert [e[0] for e in log] == ['reset'] + one * 2
+  acts, steps, adds, finishes = log.named('act'), log.named('step'), log.named('add'), log.named('finish')
+  assert len(acts) == 2 * (horizon + 1) and trainer.acts == 2 * (horizon + 1)
+  s = 0
+  for it in range(2):
+    for t in range(horizon):
+      k = it * (horizon + 1) + t                        # (the bootstrap act of iteration 0 is act number T)
+      assert acts[k][0] == k and torch.equal(acts[k][1], torch.full((lf.N_ENV, 2), float(s))), 'act sees the last returned observation'
+      a, l, v = lf.ppo_act(k)
+      _, actions, end_mask, terminal = steps[s]
+      assert steps[s][0] == s and torch.equal(actions, a)
+      assert torch.equal(end_mask, lf.u8(lf.END_MASK.get(s, (0, 0, 0)))), (s, end_mask)
+      at, obs, action, logp, value, reward, term, episode_end = adds[s]
+      assert at == t
+      assert torch.equal(obs, torch.full((lf.N_ENV, 2), float(s))), 'the block stores the observation the action was taken on'
+      assert torch.equal(action, a) and torch.equal(logp, l) and torch.equal(value, v), 'the policy at that observation and draw'
+      assert torch.equal(reward, lf.reward_of(s)) and torch.equal(term, terminal)
+      assert torch.equal(episode_end, terminal | end_mask), s
+      s += 1
+    k = it * (horizon + 1) + horizon
+    assert torch.equal(acts[k][1], torch.full((lf.N_ENV, 2), float(s))), 'the bootstrap act sees the observation after the last step'
+    boot, gamma, lam, normalize = finishes[it]
+    assert torch.equal(boot, lf.ppo_act(k)[2]) and (gamma, lam, normalize) == (0.75, 0.5, True)
+  assert s == 14 and len(finishes) == 2
+  # the updates: every token of every pass once, in order; the first update captures, the others replay
+  updates = log.named('update')
+  assert [u[1] for u in updates] == [(p, j) for p in range(2 * epochs) for j in range(per_pass)]
+  assert [u[0] for u in updates] == ['capture'] + ['train_step'] * (2 * epochs * per_pass - 1)
+  assert all(p[1] == batch for p in log.named('pass'))
+  # the iteration dicts (test_collect_host.py's episodes: the same environment and limit)
+  assert [d['updates'] for d in stats] == [epochs * per_pass] * 2
+  assert [d['episodes'] for d in stats] == [6, 6] and [d['transitions'] for d in stats] == [21, 42]
+  assert stats[0]['mean_loss'] == pytest.approx((1.0 + 3.0 * 9) / 10) and stats[1]['mean_loss'] == pytest.approx(3.0)
+  rewards = torch.stack([lf.reward_of(i) for i in range(14)])
+  assert [d['time_within_radius'] for d in stats] == [int((rewards[:7] > 0.5).sum()) / 21, int((rewards[7:] > 0.5).sum()) / 21]
+  # mean_return: the summed rewards of the episodes that ended in the iteration
+  ends = torch.stack([a[7] for a in adds]).bool()
+  want, running = [], torch.zeros(lf.N_ENV, dtype=torch.float64)
+  for it in range(2):
+    done = []
+    for i in range(it * 7, it * 7 + 7):
+      running += rewards[i].double()
+      done += running[ends[i]].tolist()
+      running[ends[i]] = 0.0
+    want.append(sum(done) / len(done))
+  assert [d['mean_return'] for d in stats] == pytest.approx(want, rel=1e-6)
+
+
+def test_ppo_loop_without_capture():
+  import loop_fakes as lf
+  from balloon_learning_environment_amd import train_lib
+  log = lf.Log()
+  train_lib.run_ppo_loop_vec(lf.FakeEnv(log), lf.FakePPOTrainer(log), lf.FakeRollout(log, 4), num_iterations=1, epochs=3, batch_size=6,
+                             max_episode_length=4, capture_graph=False)
+  assert [u[0] for u in log.named('update')] == ['train_step'] * (3 * 2)
+  assert [int(s[2].sum()) for s in log.named('step')] == [0, 0, 0, 1]
 
 
 # ---- the actor stream ----------------------------------------------------------------------------------------------------------------
