@@ -289,3 +289,16 @@ class BlePpoF32(ctypes.Structure):
   """struct ble_ppo_f32: the clipped-PPO loss's coefficients and the batch rows' old log-probabilities and advantages (device)."""
   _fields_ = [('clip', ctypes.c_float), ('value_coef', ctypes.c_float), ('entropy_coef', ctypes.c_float), ('reserved_', ctypes.c_int32),
               ('old_logp', ctypes.c_void_p), ('advantage', ctypes.c_void_p)]
+
+
+class BleBcF32(ctypes.Structure):
+  """struct ble_bc_f32: the cloning loss's label smoothing and value coefficient."""
+  _fields_ = [('label_smoothing', ctypes.c_float), ('value_coef', ctypes.c_float), ('reserved_', ctypes.c_int64)]
+
+
+class BleDaggerMixF32(ctypes.Structure):
+  """struct ble_dagger_mix_f32: the DAgger mixture of n learner and expert actions, keyed by (seed, env_offset + row, *step); step,
+  learner, expert, action and took_expert are device pointers."""
+  _fields_ = [('n', ctypes.c_int64), ('beta', ctypes.c_float), ('reserved_', ctypes.c_int32), ('seed', ctypes.c_uint64),
+              ('env_offset', ctypes.c_int64), ('step', ctypes.c_void_p), ('learner', ctypes.c_void_p), ('expert', ctypes.c_void_p),
+              ('action', ctypes.c_void_p), ('took_expert', ctypes.c_void_p)]

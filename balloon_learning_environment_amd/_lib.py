@@ -20,7 +20,7 @@ _PKG_DIR = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get('BLE_HIP_LIB') or os.path.join(_PKG_DIR, 'libble_hip.so')   # override: experiments only
 _SOURCES = [os.path.join(_PKG_DIR, 'csrc', f) for f in ('ble_kernels.hip', 'ble_step_core.h', 'ble_physics.h', 'ble_intrinsics.h', 'ble_reset.h',
                                                           'ble_observe.h', 'ble_gp_query.h', 'ble_rollout.h', 'ble_gp_belief.h', 'ble_plan.h', 'ble_scenarios.h', 'ble_noise.h', 'ble_decode.h', 'ble_step_split.h', 'ble_step_helper.h', 'ble_agent.h', 'ble_qnet.h',
-                                                          'ble_train.h', 'ble_replay.h', 'ble_explore.h', 'ble_actor.h')]
+                                                          'ble_train.h', 'ble_replay.h', 'ble_explore.h', 'ble_actor.h', 'ble_imitate.h')]
 _HEADER = os.path.join(os.path.dirname(_PKG_DIR), 'include', 'ble_abi.h')
 
 ABI_VERSION = 5
@@ -50,13 +50,13 @@ EXPORTS = ('ble_abi_version', 'ble_noise_primitive_version', 'ble_vehicle_defaul
            'ble_replay_tree_add_f64', 'ble_replay_sample_prioritized_f32', 'ble_replay_set_priority_f32', 'ble_marco_polo_u8', 'ble_gp_query_f32', 'ble_rollout_f32',
            'ble_gp_fit_f32', 'ble_gp_belief_wind_f32', 'ble_rollout_belief_f32', 'ble_plan_sample_u8', 'ble_plan_select_f32',
            'ble_gp_fit_scenarios_f32', 'ble_gp_scenario_wind_f32', 'ble_rollout_scenarios_f32', 'ble_plan_risk_f32',
-           'ble_ac_act_f32', 'ble_gae_f32', 'ble_adv_normalize_f32', 'ble_qnet_ppo_step_f32')
+           'ble_ac_act_f32', 'ble_gae_f32', 'ble_adv_normalize_f32', 'ble_qnet_ppo_step_f32', 'ble_qnet_bc_step_f32', 'ble_dagger_mix_u8')
 # Exports added without a new ABI version: a library of this ABI built before them (BLE_HIP_LIB: the parent's, in A/B runs) still loads.
 # build() checks every name of EXPORTS on the library it builds.
 ADDITIVE_EXPORTS = ('ble_last_step_form', 'ble_gp_query_f32', 'ble_rollout_f32', 'ble_gp_fit_f32', 'ble_gp_belief_wind_f32',
                     'ble_rollout_belief_f32', 'ble_plan_sample_u8', 'ble_plan_select_f32', 'ble_gp_fit_scenarios_f32',
                     'ble_gp_scenario_wind_f32', 'ble_rollout_scenarios_f32', 'ble_plan_risk_f32', 'ble_ac_act_f32', 'ble_gae_f32',
-                    'ble_adv_normalize_f32', 'ble_qnet_ppo_step_f32')
+                    'ble_adv_normalize_f32', 'ble_qnet_ppo_step_f32', 'ble_qnet_bc_step_f32', 'ble_dagger_mix_u8')
 
 
 class BleLibraryError(RuntimeError):
@@ -196,6 +196,9 @@ def lib():
     l.ble_gae_f32.argtypes = [gae, _vp]
     l.ble_adv_normalize_f32.argtypes = [gae, _vp]
     l.ble_qnet_ppo_step_f32.argtypes = [train, ctypes.POINTER(_abi.BlePpoF32), batch, _vp, _vp, _vp]
+  if hasattr(l, 'ble_qnet_bc_step_f32'):      # imitation (sizes in the structs: no int64_t argument)
+    l.ble_qnet_bc_step_f32.argtypes = [train, ctypes.POINTER(_abi.BleBcF32), batch, _vp, _vp, _vp]
+    l.ble_dagger_mix_u8.argtypes = [ctypes.POINTER(_abi.BleDaggerMixF32), _vp]
   for name in EXPORTS:
     if hasattr(l, name) or name not in ADDITIVE_EXPORTS:
       getattr(l, name).restype = _int

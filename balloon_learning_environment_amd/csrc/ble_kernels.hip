@@ -42,6 +42,7 @@
 #include "ble_train.h"
 #include "ble_explore.h"
 #include "ble_actor.h"
+#include "ble_imitate.h"
 #include "ble_replay.h"
 
 using namespace ble;
@@ -1339,10 +1340,11 @@ bool replay_ok(const ble_replay_f32* rp) {
          rp->obs_stride % 4 == 0 && std::isfinite(rp->gamma) && rp->max_tries >= 1 && rp->max_tries <= BLE_REPLAY_MAX_TRIES && rp->obs &&
          aligned(15, rp->obs) && rp->action && rp->reward && rp->terminal && rp->episode_end && rp->count && rp->counter;
 }
-// transitions: a batch of (state, next_state) pairs; an on-policy batch (PPO) has no next_state and no discount
-bool batch_ok(const ble_train_batch_f32* bt, bool transitions = true) {
+// transitions: a batch of (state, next_state) pairs; an on-policy batch (PPO, cloning) has no next_state and no discount, and cloning
+// without a value term (returns == false) no ret
+bool batch_ok(const ble_train_batch_f32* bt, bool transitions = true, bool returns = true) {
   return bt != nullptr && bt->batch >= 0 && bt->batch <= BLE_TRAIN_MAX_BATCH && bt->state_stride >= BLE_OBS_DIM && bt->state_stride % 4 == 0 &&
-         bt->state_stride <= (1LL << 20) && bt->state && (!transitions || (bt->next_state && bt->discount)) && bt->ret && bt->action &&
+         bt->state_stride <= (1LL << 20) && bt->state && (!transitions || (bt->next_state && bt->discount)) && (!returns || bt->ret) && bt->action &&
          aligned(15, bt->state, bt->next_state);
 }
 // The workspace of one update on n rows.  branches: how often the online network runs -- 1, or 2 for SARSA (state, then next_state),
@@ -1427,10 +1429,17 @@ bool ppo_ok(const ble_ppo_f32* ppo) {
   return ppo != nullptr && std::isfinite(ppo->clip) && ppo->clip > 0.0f && std::isfinite(ppo->value_coef) && std::isfinite(ppo->entropy_coef) &&
          ppo->old_logp != nullptr && ppo->advantage != nullptr;
 }
-// The loss of an update: a kind of ble_td_f32, PPO's (ble_qnet_ppo_step_f32: ppo != nullptr), or QR-DQN's (ble_qnet_train_step_f32,
-// which has neither descriptor).
-constexpr int kKindQr = -1, kKindPpo = -2;
-int update_kind(const ble_td_f32* td, const ble_ppo_f32* ppo = nullptr) { return ppo != nullptr ? kKindPpo : td != nullptr ? td->kind : kKindQr; }
+// The descriptor of ble_qnet_bc_step_f32.
+bool bc_ok(const ble_bc_f32* bc) {
+  return bc != nullptr && std::isfinite(bc->label_smoothing) && bc->label_smoothing >= 0.0f && bc->label_smoothing < 1.0f &&
+         std::isfinite(bc->value_coef);
+}
+// The loss of an update: a kind of ble_td_f32, PPO's (ble_qnet_ppo_step_f32: ppo != nullptr), cloning's (ble_qnet_bc_step_f32:
+// bc != nullptr), or QR-DQN's (ble_qnet_train_step_f32, which has no descriptor).
+constexpr int kKindQr = -1, kKindPpo = -2, kKindBc = -3;
+int update_kind(const ble_td_f32* td, const ble_ppo_f32* ppo = nullptr, const ble_bc_f32* bc = nullptr) {
+  return bc != nullptr ? kKindBc : ppo != nullptr ? kKindPpo : td != nullptr ? td->kind : kKindQr;
+}
 int update_branches(int kind) { return kind == BLE_TD_SARSA_MSE ? 2 : 1; }
 
 // The arguments of one update, td == nullptr for ble_qnet_train_step_f32.  Where the two entry points differ, each keeps the answer
@@ -1440,10 +1449,16 @@ int update_branches(int kind) { return kind == BLE_TD_SARSA_MSE ? 2 : 1; }
 //  * lr: the QR form's only reader is Adam, so it checks lr under apply_update; the TD form, which has SGD too, checks it always;
 //  * Adam's state and hyperparameters are wanted when Adam runs: under apply_update, and not with BLE_TD_OPT_SGD.
 // PPO (ppo != nullptr, td == nullptr) needs a two-atom network and its own descriptor; it has no target network, no next_state and no
-// kappa, and is the QR form in what it asks of lr and Adam.
-bool update_ok(const ble_qnet_train_f32* tr, const ble_td_f32* td, const ble_ppo_f32* ppo, const ble_train_batch_f32* bt, const float* loss) {
-  if (!tr || !qnet_ok(&tr->net) || !batch_ok(bt, ppo == nullptr) || !loss || !tr->net.weights || !tr->grad || !tr->workspace) return false;
-  if (ppo != nullptr) {
+// kappa, and is the QR form in what it asks of lr and Adam.  Cloning (bc != nullptr, td == ppo == nullptr) is PPO in all of that, and
+// reads batch->ret only under a value coefficient other than 0.
+bool update_ok(const ble_qnet_train_f32* tr, const ble_td_f32* td, const ble_ppo_f32* ppo, const ble_bc_f32* bc, const ble_train_batch_f32* bt,
+               const float* loss) {
+  const bool on_policy = ppo != nullptr || bc != nullptr;
+  const bool returns = bc == nullptr || !(bc->value_coef == 0.0f);      // (a NaN coefficient is refused below, whatever ret is)
+  if (!tr || !qnet_ok(&tr->net) || !batch_ok(bt, !on_policy, returns) || !loss || !tr->net.weights || !tr->grad || !tr->workspace) return false;
+  if (bc != nullptr) {
+    if (tr->net.num_atoms != 2 || !bc_ok(bc)) return false;
+  } else if (ppo != nullptr) {
     if (tr->net.num_atoms != 2 || !ppo_ok(ppo)) return false;
   } else {
     if (td == nullptr ? (!(tr->kappa > 0.0f) || !std::isfinite(tr->kappa)) : (tr->net.num_atoms != 1 || !td_ok(td))) return false;
@@ -1464,6 +1479,7 @@ struct TrainStep {
   const ble_qnet_train_f32* tr;
   const ble_td_f32* td;
   const ble_ppo_f32* ppo;
+  const ble_bc_f32* bc;
   const ble_train_batch_f32* bt;
   void* stream;
   const QnetShape s;
@@ -1472,15 +1488,17 @@ struct TrainStep {
   const int64_t n, ld;
   float* const ws;
 
-  TrainStep(const ble_qnet_train_f32* tr_, const ble_td_f32* td_, const ble_ppo_f32* ppo_, const ble_train_batch_f32* bt_, void* stream_)
-      : tr(tr_), td(td_), ppo(ppo_), bt(bt_), stream(stream_), s(qnet_shape(&tr_->net)), kind(update_kind(td_, ppo_)), branches(update_branches(kind)),
+  TrainStep(const ble_qnet_train_f32* tr_, const ble_td_f32* td_, const ble_ppo_f32* ppo_, const ble_bc_f32* bc_,
+            const ble_train_batch_f32* bt_, void* stream_)
+      : tr(tr_), td(td_), ppo(ppo_), bc(bc_), bt(bt_), stream(stream_), s(qnet_shape(&tr_->net)), kind(update_kind(td_, ppo_, bc_)),
+        branches(update_branches(kind)),
         lay(train_layout(s, branches, tr_->net.num_atoms, bt_->batch)), n(bt_->batch), ld(lay.ld), ws(tr_->workspace) {}
   float* acts(int l, int br = 0) const { return ws + lay.acts + (branches * l + br) * n * ld; }      // the online network's kept output of layer l
 
   // a kind with a target network: the target's pass on next_state (ping-pong, its logits end in target_logits); then the online
-  // network once per branch, on state and (SARSA) on next_state, every layer kept.  PPO has no target pass.
+  // network once per branch, on state and (SARSA) on next_state, every layer kept.  PPO and cloning have no target pass.
   int forward() const {
-    if (branches == 1 && kind != kKindPpo) {
+    if (branches == 1 && kind != kKindPpo && kind != kKindBc) {
       const int status = launch_dense_stack(s, tr->target, bt->next_state, bt->state_stride, n,
                                             DenseOut{ws + lay.scratch, false, ws + lay.target_logits}, stream);
       if (status != BLE_OK) return status;
@@ -1500,6 +1518,10 @@ struct TrainStep {
       return launch_grid(ble_ppo_loss_kernel, dim3((unsigned)n), kTrainLossBlock, stream, logits, ld, (const float*)bt->ret,
                          (const uint8_t*)bt->action, ppo->old_logp, ppo->advantage, ppo->clip, ppo->value_coef, ppo->entropy_coef, n,
                          ws + lay.targets, ws + lay.dlogits, row_loss, err_flags);
+    if (kind == kKindBc)       // (aux where PPO writes its own)
+      return launch_grid(ble_bc_loss_kernel, dim3((unsigned)n), kTrainLossBlock, stream, logits, ld, (const float*)bt->ret,
+                         (const uint8_t*)bt->action, bc->label_smoothing, bc->value_coef, n, ws + lay.targets, ws + lay.dlogits, row_loss,
+                         err_flags);
     if (kind == kKindQr)
       return launch_grid(ble_qr_loss_kernel, dim3((unsigned)n), kTrainLossBlock, stream, logits, other, ld, tr->net.num_actions,
                          tr->net.num_atoms, (const float*)bt->ret, (const float*)bt->discount, (const uint8_t*)bt->action, tr->kappa, n,
@@ -1559,13 +1581,13 @@ struct TrainStep {
   }
 };
 
-// ble_qnet_train_step_f32 (td == nullptr), ble_qnet_td_step_f32 and ble_qnet_ppo_step_f32 (ppo != nullptr): forward, loss, backward,
-// optimiser.
+// ble_qnet_train_step_f32 (td == nullptr), ble_qnet_td_step_f32, ble_qnet_ppo_step_f32 (ppo != nullptr) and ble_qnet_bc_step_f32
+// (bc != nullptr): forward, loss, backward, optimiser.
 int launch_update(const ble_qnet_train_f32* tr, const ble_td_f32* td, const ble_train_batch_f32* bt, float* loss, uint32_t* err_flags,
-                  void* stream, const ble_ppo_f32* ppo = nullptr) {
-  if (!update_ok(tr, td, ppo, bt, loss)) return BLE_E_INVALID_ARG;
+                  void* stream, const ble_ppo_f32* ppo = nullptr, const ble_bc_f32* bc = nullptr) {
+  if (!update_ok(tr, td, ppo, bc, bt, loss)) return BLE_E_INVALID_ARG;
   if (bt->batch == 0) return BLE_OK;
-  const TrainStep t(tr, td, ppo, bt, stream);
+  const TrainStep t(tr, td, ppo, bc, bt, stream);
   if (const int status = t.forward(); status != BLE_OK) return status;
   if (const int status = t.loss(loss, err_flags); status != BLE_OK) return status;
   if (const int status = t.backward(); status != BLE_OK) return status;
@@ -1694,6 +1716,20 @@ int ble_adv_normalize_f32(const ble_gae_block_f32* g, void* stream) {
 int ble_qnet_ppo_step_f32(const ble_qnet_train_f32* tr, const ble_ppo_f32* ppo, const ble_train_batch_f32* bt, float* loss, uint32_t* err_flags,
                           void* stream) {
   return ppo != nullptr ? launch_update(tr, nullptr, bt, loss, err_flags, stream, ppo) : BLE_E_INVALID_ARG;
+}
+
+// ---------------------------------------------------------------------------------------------------------------- imitation
+int ble_qnet_bc_step_f32(const ble_qnet_train_f32* tr, const ble_bc_f32* bc, const ble_train_batch_f32* bt, float* loss, uint32_t* err_flags,
+                         void* stream) {
+  return bc != nullptr ? launch_update(tr, nullptr, bt, loss, err_flags, stream, nullptr, bc) : BLE_E_INVALID_ARG;
+}
+
+int ble_dagger_mix_u8(const ble_dagger_mix_f32* mix, void* stream) {
+  if (!mix || mix->n < 0 || mix->n > 2147483647LL * kDaggerMixBlock || mix->env_offset < 0 || !(mix->beta >= 0.0f && mix->beta <= 1.0f))
+    return BLE_E_INVALID_ARG;
+  if (mix->n > 0 && (!mix->step || !mix->learner || !mix->expert || !mix->action)) return BLE_E_INVALID_ARG;
+  return launch(ble_dagger_mix_kernel, mix->n, kDaggerMixBlock, kDaggerMixBlock, stream, mix->learner, mix->expert, mix->beta,
+                (uint64_t)mix->seed, (int64_t)mix->env_offset, mix->step, mix->action, mix->took_expert, (int64_t)mix->n);
 }
 
 // ---------------------------------------------------------------------------------------------------------------- prioritized replay

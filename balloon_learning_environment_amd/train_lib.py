@@ -1,6 +1,7 @@
 """The training loops of the device learners over a VecBalloonEnv: the reference's train_lib.run_training_loop with Dopamine's
 schedule (min_replay_history, update_period, target_update_period counted in transitions) for the replay learners (QNetworkTrainer,
-DQNTrainer), and the loop of an online learner (VecMLPAgent); N environments per step.
+DQNTrainer), the loop of an online learner (VecMLPAgent), the on-policy loop (PPOTrainer) and the DAgger loop of an imitation learner
+(BCTrainer); N environments per step.
 """
 from typing import Callable, List, Optional, Union
 
@@ -203,4 +204,72 @@ def run_ppo_loop_vec(env, trainer, rollout, *, num_iterations: int, epochs: int 
     env.check_errors()
     trainer.check_errors()
     stats.append(book.finish_iteration(steps))
+  return stats
+
+
+def run_dagger_loop_vec(env, trainer, expert, rollout, *, num_iterations: int, beta: Union[float, Callable[[int], float]], epochs: int = 1,
+                        batch_size: int, max_episode_length: int = 960, gamma: float = 0.993, lam: float = 0.95,
+                        capture_graph: bool = True) -> List[dict]:
+  """Clones `expert` into an imitation learner (agents/imitation.py: BCTrainer with a VecRolloutBuffer of T steps) on `env`
+  (auto_reset) by DAgger.  expert: anything with act(obs, out) -- VecStationSeekerAgent, a venv.planner(...) bound to env's simulator
+  (it plans from the state, so its labels are on the states visited), VecQNetworkAgent, VecActorCriticAgent.  Each step the learner
+  samples its action, the expert labels the same observation, and the action flown is the expert's with probability beta_i (drawn per
+  environment and step, trainer.mix), else the learner's; the block stores the label, not the action flown.  beta: a float or a
+  function of the iteration index (a common choice: lambda i: 0.5 ** i).  The episode limit is run_training_loop_vec's.
+
+  After the T steps one more act gives the bootstrap value, rollout.finish(value, gamma, lam, normalize=False) gives ret, the
+  lambda-return of the policy flown (the value target under trainer.value_coef), and `epochs` passes of minibatches of batch_size rows
+  follow, each one update; then the block is discarded.
+
+  Returns run_training_loop_vec's dicts plus agreement (the mean over the iteration's updates of the fraction of rows whose greedy
+  action is the label) and expert_share (the fraction of the block's actions that were the expert's).  The only host synchronisation is
+  the end of an iteration."""
+  n, dev_ = env.num_envs, env.device
+  assert rollout.num_envs == n, 'the rollout block has one column per environment'
+  steps = rollout.horizon
+  obs = env.reset()
+  learner = torch.zeros(n, dtype=torch.uint8, device=dev_)
+  label = torch.zeros(n, dtype=torch.uint8, device=dev_)
+  actions = torch.zeros(n, dtype=torch.uint8, device=dev_)
+  took = torch.zeros(n, dtype=torch.uint8, device=dev_)
+  logp = torch.zeros(n, dtype=torch.float32, device=dev_)
+  value = torch.zeros(n, dtype=torch.float32, device=dev_)
+  book = _EpisodeBook(n, dev_, max_episode_length)
+  captured = False
+  stats = []
+  for it in range(num_iterations):
+    beta_i = float(beta(it) if callable(beta) else beta)
+    took_sum = torch.zeros((), dtype=torch.int64, device=dev_)
+    agree_sum = torch.zeros((), dtype=torch.float32, device=dev_)
+    for t in range(steps):
+      trainer.act(obs, learner, logp, value)
+      expert.act(obs, label)
+      trainer.mix(learner, label, beta_i, actions, took)
+      end_mask = book.end_mask()
+      next_obs, reward, terminal = env.step(actions, end_mask=end_mask)
+      episode_end = terminal | end_mask
+      rollout.add(t, obs, label, logp, value, reward, terminal, episode_end)
+      book.step(reward, episode_end)
+      took_sum += took.sum()
+      obs = next_obs
+    trainer.act(obs, learner, logp, value)
+    rollout.finish(value, gamma, lam, normalize=False)
+    for _ in range(epochs):
+      for batch in rollout.minibatches(batch_size):
+        if capture_graph and not captured:
+          loss = trainer.capture(batch)                     # (its first, eager update is a real one)
+          captured = True
+        else:
+          loss = trainer.train_step(batch)
+        book.update(loss)
+        agree_sum += trainer.views(batch_size)['aux'][:, 1].mean()
+    env.check_errors()
+    trainer.check_errors()
+    if hasattr(expert, 'check_errors'):
+      expert.check_errors()
+    updates = book.updates
+    s = book.finish_iteration(steps)
+    s['agreement'] = float(agree_sum.item()) / max(updates, 1)
+    s['expert_share'] = float(took_sum.item()) / (n * steps)
+    stats.append(s)
   return stats

@@ -877,6 +877,51 @@ int ble_qnet_ppo_step_f32(const ble_qnet_train_f32* tr, const ble_ppo_f32* ppo, 
                           uint32_t* err_flags, void* stream);
 
 /*
+ * Imitation (additive to ABI 5): behaviour cloning of the actor-critic above on labelled rows, and the DAgger mixture of
+ * the learner's and the expert's actions.  §3m's arithmetic rules; both heads share the log-softmax above.
+ */
+typedef struct ble_bc_f32 {
+  float label_smoothing;       /* s: finite, in [0, 1) */
+  float value_coef;            /* c_v, finite; 0: no value term, batch->ret is not read and may be NULL */
+  int64_t reserved_;           /* 0 */
+} ble_bc_f32;
+
+/*
+ * ble_qnet_bc_step_f32: one cloning update of a two-atom network on batch, batch->action holding the expert's labels:
+ * ble_qnet_ppo_step_f32's stages with another loss -- no target pass; tr->target, batch->next_state, batch->discount and tr->kappa
+ * are not read and may be NULL; lr and Adam as ble_qnet_ppo_step_f32 asks.  The workspace is ble_qnet_train_workspace_f32's; where
+ * the other kinds write targets ([B][2] floats) it writes aux[b] = (lp_act, agree).
+ * Per row, with act = action[b], R = ret[b], (lp, p) the log-softmax of z[0], z[2], z[4]:
+ *   s3 = s / 3;  hi = (1 - s) + s3;  q_a = (a == act) ? hi : s3;  CE = -((q0 lp0 + q1 lp1) + q2 lp2);
+ *   L_b = CE + c_v (z[1] - R)^2;  dL/dz[2a] = (p_a - q_a) / B;  dL/dz[1] = (2 c_v (z[1] - R)) / B;
+ *   agree = 1.0f when the greedy action of these logits (ble_ac_act_f32's rule) equals act, else 0.0f.
+ * c_v == 0: L_b = CE and dL/dz[1] is exactly 0.  z[3], z[5] and the padded columns receive zero.
+ * An action >= 3 sets BLE_FLAG_TRAIN_ACTION and zeroes the row's loss, aux and gradient.  B == 0 launches nothing.
+ */
+int ble_qnet_bc_step_f32(const ble_qnet_train_f32* tr, const ble_bc_f32* bc, const ble_train_batch_f32* batch, float* loss,
+                         uint32_t* err_flags, void* stream);
+
+/* Row i draws u = (w >> 8) 2^-24, w the first 32-bit word of the Philox stream keyed by (seed ^ 0x444147474552, env_offset + i, *step)
+ * (ble_ac_act_f32's keying under another constant), and takes action[i] = u < beta ? expert[i] : learner[i]; took_expert[i] = u < beta.
+ * beta = 0 copies the learner, beta = 1 the expert.  The draw of environment env_offset + i at *step does not depend on n or on the
+ * row's position.  *step is read, not advanced.  action may alias learner. */
+typedef struct ble_dagger_mix_f32 {
+  int64_t n;                   /* rows, >= 0 */
+  float beta;                  /* finite, in [0, 1] */
+  int32_t reserved_;           /* 0 */
+  unsigned long long seed;
+  int64_t env_offset;          /* >= 0 */
+  const unsigned long long* step; /* device */
+  const uint8_t* learner;      /* device [n] */
+  const uint8_t* expert;       /* device [n] */
+  uint8_t* action;             /* device [n] */
+  uint8_t* took_expert;        /* optional device [n] */
+} ble_dagger_mix_f32;
+
+/* n == 0 launches nothing and needs no pointer. */
+int ble_dagger_mix_u8(const ble_dagger_mix_f32* mix, void* stream);
+
+/*
  * Prioritized n-step replay (additive to ABI 5): Dopamine 4.0.0's OutOfGraphPrioritizedReplayBuffer over the ring above.
  * An fp64 sum tree over capacity x num_envs leaves: leaf (t % capacity) num_envs + env is the n-step window that starts at ring row t
  * of that environment.  A heap padded to a power of two: nodes[1] is the root, nodes[padded + i] leaf i, nodes[0] unused, the padded
