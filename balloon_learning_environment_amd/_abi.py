@@ -137,6 +137,23 @@ class BlePlanSelect(ctypes.Structure):
               ('action', ctypes.c_void_p), ('elite_counts', ctypes.c_void_p), ('advance_counter', ctypes.c_void_p)]
 
 
+class BlePlanPrior(ctypes.Structure):
+  """struct ble_plan_prior: probs [n][3] -> prior counts [n][segments][3] for ble_plan_prior_u16 (device pointers)."""
+  _fields_ = [('n', ctypes.c_int64), ('segments', ctypes.c_int32), ('strength', ctypes.c_int32), ('probs', ctypes.c_void_p),
+              ('prior_counts', ctypes.c_void_p)]
+
+
+class BlePlanSamplePrior(ctypes.Structure):
+  """struct ble_plan_sample_prior: BlePlanSample's fields, then the prior counts iteration 0 draws from (ble_plan_sample_prior_u8)."""
+  _fields_ = BlePlanSample._fields_ + [('prior_counts', ctypes.c_void_p)]
+
+
+class BlePlanActionValues(ctypes.Structure):
+  """struct ble_plan_action_values: ret [n][K] and the plans' first actions -> q, q_k, visits [n][3] (device pointers)."""
+  _fields_ = [('n', ctypes.c_int64), ('n_plans', ctypes.c_int32), ('accumulate', ctypes.c_int32), ('ret', ctypes.c_void_p),
+              ('first_action', ctypes.c_void_p), ('q', ctypes.c_void_p), ('q_k', ctypes.c_void_p), ('visits', ctypes.c_void_p)]
+
+
 SCENARIO_MAX = 16           # BLE_SCENARIO_MAX
 
 
@@ -294,6 +311,13 @@ class BlePpoF32(ctypes.Structure):
 class BleBcF32(ctypes.Structure):
   """struct ble_bc_f32: the cloning loss's label smoothing and value coefficient."""
   _fields_ = [('label_smoothing', ctypes.c_float), ('value_coef', ctypes.c_float), ('reserved_', ctypes.c_int64)]
+
+
+class BleSoftBcF32(ctypes.Structure):
+  """struct ble_soft_bc_f32: the soft cloning loss's inverse temperature, label smoothing and value coefficient, and the rows'
+  per-action values target_q [B][3] (device)."""
+  _fields_ = [('inv_temperature', ctypes.c_float), ('label_smoothing', ctypes.c_float), ('value_coef', ctypes.c_float),
+              ('reserved_', ctypes.c_int32), ('target_q', ctypes.c_void_p)]
 
 
 class BleDaggerMixF32(ctypes.Structure):

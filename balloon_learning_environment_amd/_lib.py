@@ -50,13 +50,15 @@ EXPORTS = ('ble_abi_version', 'ble_noise_primitive_version', 'ble_vehicle_defaul
            'ble_replay_tree_add_f64', 'ble_replay_sample_prioritized_f32', 'ble_replay_set_priority_f32', 'ble_marco_polo_u8', 'ble_gp_query_f32', 'ble_rollout_f32',
            'ble_gp_fit_f32', 'ble_gp_belief_wind_f32', 'ble_rollout_belief_f32', 'ble_plan_sample_u8', 'ble_plan_select_f32',
            'ble_gp_fit_scenarios_f32', 'ble_gp_scenario_wind_f32', 'ble_rollout_scenarios_f32', 'ble_plan_risk_f32',
-           'ble_ac_act_f32', 'ble_gae_f32', 'ble_adv_normalize_f32', 'ble_qnet_ppo_step_f32', 'ble_qnet_bc_step_f32', 'ble_dagger_mix_u8')
+           'ble_ac_act_f32', 'ble_gae_f32', 'ble_adv_normalize_f32', 'ble_qnet_ppo_step_f32', 'ble_qnet_bc_step_f32', 'ble_dagger_mix_u8',
+           'ble_plan_prior_u16', 'ble_plan_sample_prior_u8', 'ble_plan_action_values_f32', 'ble_qnet_soft_bc_step_f32')
 # Exports added without a new ABI version: a library of this ABI built before them (BLE_HIP_LIB: the parent's, in A/B runs) still loads.
 # build() checks every name of EXPORTS on the library it builds.
 ADDITIVE_EXPORTS = ('ble_last_step_form', 'ble_gp_query_f32', 'ble_rollout_f32', 'ble_gp_fit_f32', 'ble_gp_belief_wind_f32',
                     'ble_rollout_belief_f32', 'ble_plan_sample_u8', 'ble_plan_select_f32', 'ble_gp_fit_scenarios_f32',
                     'ble_gp_scenario_wind_f32', 'ble_rollout_scenarios_f32', 'ble_plan_risk_f32', 'ble_ac_act_f32', 'ble_gae_f32',
-                    'ble_adv_normalize_f32', 'ble_qnet_ppo_step_f32', 'ble_qnet_bc_step_f32', 'ble_dagger_mix_u8')
+                    'ble_adv_normalize_f32', 'ble_qnet_ppo_step_f32', 'ble_qnet_bc_step_f32', 'ble_dagger_mix_u8', 'ble_plan_prior_u16',
+                    'ble_plan_sample_prior_u8', 'ble_plan_action_values_f32', 'ble_qnet_soft_bc_step_f32')
 
 
 class BleLibraryError(RuntimeError):
@@ -199,6 +201,11 @@ def lib():
   if hasattr(l, 'ble_qnet_bc_step_f32'):      # imitation (sizes in the structs: no int64_t argument)
     l.ble_qnet_bc_step_f32.argtypes = [train, ctypes.POINTER(_abi.BleBcF32), batch, _vp, _vp, _vp]
     l.ble_dagger_mix_u8.argtypes = [ctypes.POINTER(_abi.BleDaggerMixF32), _vp]
+  if hasattr(l, 'ble_plan_prior_u16'):        # expert iteration (sizes in the structs: no int64_t argument)
+    l.ble_plan_prior_u16.argtypes = [ctypes.POINTER(_abi.BlePlanPrior), _vp]
+    l.ble_plan_sample_prior_u8.argtypes = [ctypes.POINTER(_abi.BlePlanSamplePrior), _vp]
+    l.ble_plan_action_values_f32.argtypes = [ctypes.POINTER(_abi.BlePlanActionValues), _vp]
+    l.ble_qnet_soft_bc_step_f32.argtypes = [train, ctypes.POINTER(_abi.BleSoftBcF32), batch, _vp, _vp, _vp]
   for name in EXPORTS:
     if hasattr(l, name) or name not in ADDITIVE_EXPORTS:
       getattr(l, name).restype = _int

@@ -37,11 +37,17 @@ class VecLookaheadAgent:
   before, the best plan so far always kept.  Iteration 0 always holds all-STAY, all-DOWN, all-UP and the previous decision's best
   plan shifted by one entry (as far as K reaches).  seed: the plans' Philox streams are keyed by (seed, environment, decision
   counter, iteration, k), or with bind(seeds=) by (that environment's seed, decision counter, iteration, k): then an environment
-  plans the same in any batch."""
+  plans the same in any batch.
+  prior_strength (0 .. 65 535): with a value above 0 and act(prior_probs=) given, iteration 0 draws its free plans around a
+  policy prior instead of from uniform thirds: segment s draws action a with probability (c_a + 1) / (c_0 + c_1 + c_2 + 3),
+  c_a = trunc(p_a * (prior_strength >> s)) -- the prior's weight halves per segment.  0, or no prior_probs: today's calls.
+  action_values: True computes, after every selection of a decision, the best return among the plans that begin with each action
+  (action_values()); False (the default) adds no launch."""
 
   def __init__(self, num_plans: int = 64, horizon: int = 24, action_repeat: int = 1, segment: int = 4, gamma: float = 0.993,
                wind: str = 'belief', iterations: int = 1, elite: int = 8, seed: int = 0, device='cuda:0',
-               substeps: int = vec_state.SUBSTEPS, num_scenarios: int = 8, risk_tail: Optional[int] = None):
+               substeps: int = vec_state.SUBSTEPS, num_scenarios: int = 8, risk_tail: Optional[int] = None, prior_strength: int = 0,
+               action_values: bool = False):
     if wind not in WINDS:
       raise ValueError(f"VecLookaheadAgent: wind is 'belief', 'forecast', 'truth' or 'scenarios', not {wind!r}")
     self.num_scenarios = int(num_scenarios) if wind == 'scenarios' else 0
@@ -59,6 +65,9 @@ class VecLookaheadAgent:
                        f'not {segment}, {iterations}, {elite}')
     if not 0.0 <= float(gamma) <= 1.0:
       raise ValueError(f'VecLookaheadAgent: gamma in [0, 1], not {gamma}')
+    if not 0 <= int(prior_strength) <= 65535:
+      raise ValueError(f'VecLookaheadAgent: 0 <= prior_strength <= 65535, not {prior_strength}')
+    self.prior_strength, self.with_action_values = int(prior_strength), bool(action_values)
     self.device = dev.require_gpu(device)
     self.lib = _lib.lib()
     self.num_plans, self.horizon, self.action_repeat, self.segment = int(num_plans), int(horizon), int(action_repeat), int(segment)
@@ -101,6 +110,9 @@ class VecLookaheadAgent:
       self.best_plan = z(torch.uint8, h, n)
       self.elite_counts = z(torch.int16, n, self.segments, 3)
       self.action = z(torch.uint8, n)
+      self.prior_counts = z(torch.int16, n, self.segments, 3) if self.prior_strength > 0 else None
+      self.q, self.q_k, self.visits = ((z(torch.float32, n, 3), z(torch.int32, n, 3), z(torch.int32, n, 3)) if self.with_action_values
+                                       else (None, None, None))
       self._belief = None
       if self.wind == 'belief':
         self._belief = vec_state.WindBelief(z(torch.float64, n, _lib.GP_BELIEF_DOUBLES), z(torch.int32, n))
@@ -122,10 +134,13 @@ class VecLookaheadAgent:
 
   # ------------------------------------------------------------------ one decision
   @dev.on_own_device
-  def act(self, obs: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+  def act(self, obs: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None,
+          prior_probs: Optional[torch.Tensor] = None) -> torch.Tensor:
     """One decision for every environment of the bound simulator, from the state where it lies: uint8 [N] actions (device).  obs is
-    accepted and unused (the plans are flown from the state itself).  out: optional uint8 [N] for the actions.  Nothing of the
-    simulator is written; flags of the imagined flights go to sim.rollout_flags.  Asynchronous, capturable in a HIP graph."""
+    accepted and unused (the plans are flown from the state itself).  out: optional uint8 [N] for the actions.  prior_probs: optional
+    float32 [N, 3] device tensor, a policy's probabilities of the three actions (an actor-critic's probs, a softmax of Q-values): read
+    by iteration 0 of an agent built with prior_strength > 0, ignored otherwise.  Nothing of the simulator is written; flags of the
+    imagined flights go to sim.rollout_flags.  Asynchronous, capturable in a HIP graph."""
     del obs
     sim = self._bound()
     if sim.has_fleet:
@@ -135,6 +150,12 @@ class VecLookaheadAgent:
       out = self.action
     assert out.dtype == torch.uint8 and out.is_contiguous() and out.numel() == n and out.device == self.device
     stream = dev.stream_ptr(self.device)
+    with_prior = self.prior_strength > 0 and prior_probs is not None
+    if with_prior:
+      assert prior_probs.dtype == torch.float32 and prior_probs.is_contiguous() and tuple(prior_probs.shape) == (n, 3), prior_probs.shape
+      assert prior_probs.device == self.device
+      pr = _abi.BlePlanPrior(n, self.segments, self.prior_strength, prior_probs.data_ptr(), self.prior_counts.data_ptr())
+      _lib.check(self.lib.ble_plan_prior_u16(ctypes.byref(pr), stream), 'ble_plan_prior_u16')
     belief, noise_seed, scenarios = None, None, None
     if self.wind == 'belief':
       belief = sim.fit_wind_belief(out=self._belief)
@@ -148,7 +169,11 @@ class VecLookaheadAgent:
       ps = _abi.BlePlanSample(n, self.num_plans, self.horizon, self.segment, it, self.seed & (2 ** 64 - 1), dev.ptr(self._seeds),
                               0 if self._seeds is not None else sim.env_offset, self.counter.data_ptr(), self.elite_counts.data_ptr(),
                               self.best_plan.data_ptr(), self.plans.data_ptr())
-      _lib.check(self.lib.ble_plan_sample_u8(ctypes.byref(ps), stream), 'ble_plan_sample_u8')
+      if with_prior and it == 0:
+        pp = _abi.BlePlanSamplePrior(*(getattr(ps, name) for name, _ in _abi.BlePlanSample._fields_), self.prior_counts.data_ptr())
+        _lib.check(self.lib.ble_plan_sample_prior_u8(ctypes.byref(pp), stream), 'ble_plan_sample_prior_u8')
+      else:
+        _lib.check(self.lib.ble_plan_sample_u8(ctypes.byref(ps), stream), 'ble_plan_sample_u8')
       if scenarios is not None:      # every plan in every scenario wind, then one score per plan: the selection below runs on the scores
         sim.rollout_plans(self.plans, self.gamma, self.action_repeat, None, self.substeps,
                           out=(self.scenario_returns, self.scenario_steps, None, None), scenarios=scenarios)
@@ -160,6 +185,10 @@ class VecLookaheadAgent:
                                self.plans.data_ptr(), self.best_return.data_ptr(), self.best_k.data_ptr(), self.best_plan.data_ptr(),
                                out.data_ptr(), self.elite_counts.data_ptr(), self.counter.data_ptr() if last else None)
       _lib.check(self.lib.ble_plan_select_f32(ctypes.byref(sel), stream), 'ble_plan_select_f32')
+      if self.with_action_values:      # (plans[0] is [n][K]: the plans' first entries)
+        av = _abi.BlePlanActionValues(n, self.num_plans, 1 if it > 0 else 0, self.returns.data_ptr(), self.plans.data_ptr(),
+                                      self.q.data_ptr(), self.q_k.data_ptr(), self.visits.data_ptr())
+        _lib.check(self.lib.ble_plan_action_values_f32(ctypes.byref(av), stream), 'ble_plan_action_values_f32')
     return out
 
   __call__ = act
@@ -168,6 +197,16 @@ class VecLookaheadAgent:
     """(best_plan uint8 [H, N], best_return float32 [N]) of the last decision: the agent's own buffers, overwritten by the next one."""
     self._bound()
     return self.best_plan, self.best_return
+
+  def action_values(self) -> Tuple[torch.Tensor, torch.Tensor]:
+    """(q float32 [N, 3], visits int32 [N, 3]) of the last decision, for an agent built with action_values=True: q[e, a] the best
+    return (or risk score) among the plans of the decision that begin with action a, -Inf when none with a finite return does;
+    visits[e, a] how many plans began with a.  q[e, action[e]] is best_return[e].  The agent's own buffers, overwritten by the next
+    decision."""
+    self._bound()
+    if not self.with_action_values:
+      raise ValueError('VecLookaheadAgent.action_values: build the agent with action_values=True')
+    return self.q, self.visits
 
   def state_dict(self) -> dict:
     """What a run of decisions carries from one to the next: the decision counter and the best plan (the warm start)."""

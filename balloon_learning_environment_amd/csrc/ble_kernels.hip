@@ -1341,10 +1341,11 @@ bool replay_ok(const ble_replay_f32* rp) {
          aligned(15, rp->obs) && rp->action && rp->reward && rp->terminal && rp->episode_end && rp->count && rp->counter;
 }
 // transitions: a batch of (state, next_state) pairs; an on-policy batch (PPO, cloning) has no next_state and no discount, and cloning
-// without a value term (returns == false) no ret
-bool batch_ok(const ble_train_batch_f32* bt, bool transitions = true, bool returns = true) {
+// without a value term (returns == false) no ret; the soft cloning loss reads no action (actions == false)
+bool batch_ok(const ble_train_batch_f32* bt, bool transitions = true, bool returns = true, bool actions = true) {
   return bt != nullptr && bt->batch >= 0 && bt->batch <= BLE_TRAIN_MAX_BATCH && bt->state_stride >= BLE_OBS_DIM && bt->state_stride % 4 == 0 &&
-         bt->state_stride <= (1LL << 20) && bt->state && (!transitions || (bt->next_state && bt->discount)) && (!returns || bt->ret) && bt->action &&
+         bt->state_stride <= (1LL << 20) && bt->state && (!transitions || (bt->next_state && bt->discount)) && (!returns || bt->ret) &&
+         (!actions || bt->action) &&
          aligned(15, bt->state, bt->next_state);
 }
 // The workspace of one update on n rows.  branches: how often the online network runs -- 1, or 2 for SARSA (state, then next_state),
@@ -1434,11 +1435,17 @@ bool bc_ok(const ble_bc_f32* bc) {
   return bc != nullptr && std::isfinite(bc->label_smoothing) && bc->label_smoothing >= 0.0f && bc->label_smoothing < 1.0f &&
          std::isfinite(bc->value_coef);
 }
+// The descriptor of ble_qnet_soft_bc_step_f32.
+bool soft_ok(const ble_soft_bc_f32* soft) {
+  return soft != nullptr && std::isfinite(soft->inv_temperature) && soft->inv_temperature > 0.0f && std::isfinite(soft->label_smoothing) &&
+         soft->label_smoothing >= 0.0f && soft->label_smoothing < 1.0f && std::isfinite(soft->value_coef) && soft->target_q != nullptr;
+}
 // The loss of an update: a kind of ble_td_f32, PPO's (ble_qnet_ppo_step_f32: ppo != nullptr), cloning's (ble_qnet_bc_step_f32:
-// bc != nullptr), or QR-DQN's (ble_qnet_train_step_f32, which has no descriptor).
-constexpr int kKindQr = -1, kKindPpo = -2, kKindBc = -3;
-int update_kind(const ble_td_f32* td, const ble_ppo_f32* ppo = nullptr, const ble_bc_f32* bc = nullptr) {
-  return bc != nullptr ? kKindBc : ppo != nullptr ? kKindPpo : td != nullptr ? td->kind : kKindQr;
+// bc != nullptr), soft cloning's (ble_qnet_soft_bc_step_f32: soft != nullptr), or QR-DQN's (ble_qnet_train_step_f32, which has no
+// descriptor).
+constexpr int kKindQr = -1, kKindPpo = -2, kKindBc = -3, kKindSoftBc = -4;
+int update_kind(const ble_td_f32* td, const ble_ppo_f32* ppo = nullptr, const ble_bc_f32* bc = nullptr, const ble_soft_bc_f32* soft = nullptr) {
+  return soft != nullptr ? kKindSoftBc : bc != nullptr ? kKindBc : ppo != nullptr ? kKindPpo : td != nullptr ? td->kind : kKindQr;
 }
 int update_branches(int kind) { return kind == BLE_TD_SARSA_MSE ? 2 : 1; }
 
@@ -1450,13 +1457,18 @@ int update_branches(int kind) { return kind == BLE_TD_SARSA_MSE ? 2 : 1; }
 //  * Adam's state and hyperparameters are wanted when Adam runs: under apply_update, and not with BLE_TD_OPT_SGD.
 // PPO (ppo != nullptr, td == nullptr) needs a two-atom network and its own descriptor; it has no target network, no next_state and no
 // kappa, and is the QR form in what it asks of lr and Adam.  Cloning (bc != nullptr, td == ppo == nullptr) is PPO in all of that, and
-// reads batch->ret only under a value coefficient other than 0.
+// reads batch->ret only under a value coefficient other than 0.  Soft cloning (soft != nullptr, the others NULL) is cloning in all of
+// that, and reads no batch->action.
 bool update_ok(const ble_qnet_train_f32* tr, const ble_td_f32* td, const ble_ppo_f32* ppo, const ble_bc_f32* bc, const ble_train_batch_f32* bt,
-               const float* loss) {
-  const bool on_policy = ppo != nullptr || bc != nullptr;
-  const bool returns = bc == nullptr || !(bc->value_coef == 0.0f);      // (a NaN coefficient is refused below, whatever ret is)
-  if (!tr || !qnet_ok(&tr->net) || !batch_ok(bt, !on_policy, returns) || !loss || !tr->net.weights || !tr->grad || !tr->workspace) return false;
-  if (bc != nullptr) {
+               const float* loss, const ble_soft_bc_f32* soft = nullptr) {
+  const bool on_policy = ppo != nullptr || bc != nullptr || soft != nullptr;
+  const bool returns = soft != nullptr ? !(soft->value_coef == 0.0f)
+                                       : (bc == nullptr || !(bc->value_coef == 0.0f));      // (a NaN coefficient is refused below, whatever ret is)
+  if (!tr || !qnet_ok(&tr->net) || !batch_ok(bt, !on_policy, returns, soft == nullptr) || !loss || !tr->net.weights || !tr->grad || !tr->workspace)
+    return false;
+  if (soft != nullptr) {
+    if (tr->net.num_atoms != 2 || !soft_ok(soft)) return false;
+  } else if (bc != nullptr) {
     if (tr->net.num_atoms != 2 || !bc_ok(bc)) return false;
   } else if (ppo != nullptr) {
     if (tr->net.num_atoms != 2 || !ppo_ok(ppo)) return false;
@@ -1480,6 +1492,7 @@ struct TrainStep {
   const ble_td_f32* td;
   const ble_ppo_f32* ppo;
   const ble_bc_f32* bc;
+  const ble_soft_bc_f32* soft;
   const ble_train_batch_f32* bt;
   void* stream;
   const QnetShape s;
@@ -1489,16 +1502,17 @@ struct TrainStep {
   float* const ws;
 
   TrainStep(const ble_qnet_train_f32* tr_, const ble_td_f32* td_, const ble_ppo_f32* ppo_, const ble_bc_f32* bc_,
-            const ble_train_batch_f32* bt_, void* stream_)
-      : tr(tr_), td(td_), ppo(ppo_), bc(bc_), bt(bt_), stream(stream_), s(qnet_shape(&tr_->net)), kind(update_kind(td_, ppo_, bc_)),
+            const ble_train_batch_f32* bt_, void* stream_, const ble_soft_bc_f32* soft_ = nullptr)
+      : tr(tr_), td(td_), ppo(ppo_), bc(bc_), soft(soft_), bt(bt_), stream(stream_), s(qnet_shape(&tr_->net)),
+        kind(update_kind(td_, ppo_, bc_, soft_)),
         branches(update_branches(kind)),
         lay(train_layout(s, branches, tr_->net.num_atoms, bt_->batch)), n(bt_->batch), ld(lay.ld), ws(tr_->workspace) {}
   float* acts(int l, int br = 0) const { return ws + lay.acts + (branches * l + br) * n * ld; }      // the online network's kept output of layer l
 
   // a kind with a target network: the target's pass on next_state (ping-pong, its logits end in target_logits); then the online
-  // network once per branch, on state and (SARSA) on next_state, every layer kept.  PPO and cloning have no target pass.
+  // network once per branch, on state and (SARSA) on next_state, every layer kept.  PPO and cloning (hard or soft) have no target pass.
   int forward() const {
-    if (branches == 1 && kind != kKindPpo && kind != kKindBc) {
+    if (branches == 1 && kind != kKindPpo && kind != kKindBc && kind != kKindSoftBc) {
       const int status = launch_dense_stack(s, tr->target, bt->next_state, bt->state_stride, n,
                                             DenseOut{ws + lay.scratch, false, ws + lay.target_logits}, stream);
       if (status != BLE_OK) return status;
@@ -1522,6 +1536,10 @@ struct TrainStep {
       return launch_grid(ble_bc_loss_kernel, dim3((unsigned)n), kTrainLossBlock, stream, logits, ld, (const float*)bt->ret,
                          (const uint8_t*)bt->action, bc->label_smoothing, bc->value_coef, n, ws + lay.targets, ws + lay.dlogits, row_loss,
                          err_flags);
+    if (kind == kKindSoftBc)   // (aux where cloning writes its own; no flag to set)
+      return launch_grid(ble_soft_bc_loss_kernel, dim3((unsigned)n), kTrainLossBlock, stream, logits, ld, (const float*)bt->ret,
+                         soft->target_q, soft->inv_temperature, soft->label_smoothing, soft->value_coef, n, ws + lay.targets,
+                         ws + lay.dlogits, row_loss);
     if (kind == kKindQr)
       return launch_grid(ble_qr_loss_kernel, dim3((unsigned)n), kTrainLossBlock, stream, logits, other, ld, tr->net.num_actions,
                          tr->net.num_atoms, (const float*)bt->ret, (const float*)bt->discount, (const uint8_t*)bt->action, tr->kappa, n,
@@ -1581,13 +1599,13 @@ struct TrainStep {
   }
 };
 
-// ble_qnet_train_step_f32 (td == nullptr), ble_qnet_td_step_f32, ble_qnet_ppo_step_f32 (ppo != nullptr) and ble_qnet_bc_step_f32
-// (bc != nullptr): forward, loss, backward, optimiser.
+// ble_qnet_train_step_f32 (td == nullptr), ble_qnet_td_step_f32, ble_qnet_ppo_step_f32 (ppo != nullptr), ble_qnet_bc_step_f32
+// (bc != nullptr) and ble_qnet_soft_bc_step_f32 (soft != nullptr): forward, loss, backward, optimiser.
 int launch_update(const ble_qnet_train_f32* tr, const ble_td_f32* td, const ble_train_batch_f32* bt, float* loss, uint32_t* err_flags,
-                  void* stream, const ble_ppo_f32* ppo = nullptr, const ble_bc_f32* bc = nullptr) {
-  if (!update_ok(tr, td, ppo, bc, bt, loss)) return BLE_E_INVALID_ARG;
+                  void* stream, const ble_ppo_f32* ppo = nullptr, const ble_bc_f32* bc = nullptr, const ble_soft_bc_f32* soft = nullptr) {
+  if (!update_ok(tr, td, ppo, bc, bt, loss, soft)) return BLE_E_INVALID_ARG;
   if (bt->batch == 0) return BLE_OK;
-  const TrainStep t(tr, td, ppo, bc, bt, stream);
+  const TrainStep t(tr, td, ppo, bc, bt, stream, soft);
   if (const int status = t.forward(); status != BLE_OK) return status;
   if (const int status = t.loss(loss, err_flags); status != BLE_OK) return status;
   if (const int status = t.backward(); status != BLE_OK) return status;
@@ -1722,6 +1740,11 @@ int ble_qnet_ppo_step_f32(const ble_qnet_train_f32* tr, const ble_ppo_f32* ppo, 
 int ble_qnet_bc_step_f32(const ble_qnet_train_f32* tr, const ble_bc_f32* bc, const ble_train_batch_f32* bt, float* loss, uint32_t* err_flags,
                          void* stream) {
   return bc != nullptr ? launch_update(tr, nullptr, bt, loss, err_flags, stream, nullptr, bc) : BLE_E_INVALID_ARG;
+}
+
+int ble_qnet_soft_bc_step_f32(const ble_qnet_train_f32* tr, const ble_soft_bc_f32* soft, const ble_train_batch_f32* bt, float* loss,
+                              uint32_t* err_flags, void* stream) {
+  return soft != nullptr ? launch_update(tr, nullptr, bt, loss, err_flags, stream, nullptr, nullptr, soft) : BLE_E_INVALID_ARG;
 }
 
 int ble_dagger_mix_u8(const ble_dagger_mix_f32* mix, void* stream) {
@@ -1922,6 +1945,35 @@ int ble_plan_select_f32(const struct ble_plan_select* sel, void* stream) {
   const PlanSelectArgs a{sel->n, sel->n_plans, sel->n_plan_steps, sel->segment, sel->iteration, sel->elite, sel->ret, sel->plans,
                          sel->best_return, sel->best_k, sel->best_plan, sel->action, sel->elite_counts, sel->advance_counter};
   return launch(ble_plan_select_kernel, sel->n, 1, kPlanSelectBlock, stream, a);
+}
+
+// ---- expert iteration
+int ble_plan_prior_u16(const struct ble_plan_prior* pr, void* stream) {
+  if (!pr || !pr->probs || !pr->prior_counts || pr->n < 0 || pr->segments < 1 || pr->segments > BLE_ROLLOUT_MAX_STEPS || pr->strength < 0 ||
+      pr->strength > 65535 || pr->n * (int64_t)pr->segments >= 2147483648LL)
+    return BLE_E_INVALID_ARG;
+  const int64_t total = pr->n * (int64_t)pr->segments;
+  return launch(ble_plan_prior_kernel, total, 256, 256, stream, pr->probs, (int)pr->strength, (int)pr->segments, pr->prior_counts, total);
+}
+
+int ble_plan_sample_prior_u8(const struct ble_plan_sample_prior* ps, void* stream) {
+  if (!ps || !ps->plans || !ps->decision_counter || !ps->best_plan || (ps->iteration > 0 && !ps->elite_counts) || !ps->prior_counts)
+    return BLE_E_INVALID_ARG;
+  if (!plan_sizes_ok(ps->n, ps->n_plans, ps->n_plan_steps, ps->segment, ps->iteration) || ps->env_offset < 0) return BLE_E_INVALID_ARG;
+  const PlanSampleArgs a{ps->n, ps->env_offset, ps->n_plans, ps->n_plan_steps, ps->segment, ps->iteration, ps->decision_counter,
+                         ps->iteration > 0 ? ps->elite_counts : nullptr, ps->best_plan, ps->plans};
+  const int64_t lanes = ps->n * (int64_t)ps->n_plans;
+  if (ps->env_seed != nullptr)
+    return launch(ble_plan_sample_prior_kernel<EnvSeed>, lanes, 256, 256, stream, a, ps->prior_counts, EnvSeed{ps->env_seed});
+  return launch(ble_plan_sample_prior_kernel<ScalarSeed>, lanes, 256, 256, stream, a, ps->prior_counts, ScalarSeed{ps->seed});
+}
+
+int ble_plan_action_values_f32(const struct ble_plan_action_values* av, void* stream) {
+  if (!av || !av->ret || !av->first_action || !av->q || !av->q_k || !av->visits || av->n < 0 || av->n >= 2147483648LL || av->n_plans < 1 ||
+      av->n_plans > BLE_PLAN_MAX_PLANS || av->n * (int64_t)av->n_plans >= 2147483648LL)
+    return BLE_E_INVALID_ARG;
+  const PlanActionValuesArgs a{av->n, av->n_plans, av->accumulate, av->ret, av->first_action, av->q, av->q_k, av->visits};
+  return launch(ble_plan_action_values_kernel, av->n, 1, kPlanSelectBlock, stream, a);
 }
 
 int ble_gp_fit_scenarios_f32(const ble_gp_history_f32* hist, const uint8_t* reset_mask, const int32_t* time_s, const ble_gp_scenarios* scn,

@@ -8,7 +8,11 @@
 // plans (lanes stride over K; K <= 1024: at most 16 plans per lane), the plans of rank < max(elite, 1) are listed in rank order, and
 // the rest reads that list.  No atomics, no cross-lane arithmetic: the order is a function of the returns alone.
 //
-// The lane functions below build for the host as well (tests/emul/plan_emul.cpp); the kernels need hipcc.
+// Expert iteration adds a prior to iteration 0 of the sampler (ble_plan_prior_u16 -> ble_plan_sample_prior_u8: counts made
+// from a policy's probabilities where iteration 0 has zeros) and the best return among the plans that begin with each action
+// (ble_plan_action_values_f32: one wavefront per environment, the selection's own order).
+//
+// The lane functions below build for the host as well (tests/emul/plan_emul.cpp, exit_emul.cpp); the kernels need hipcc.
 #pragma once
 #include "ble_reset.h"
 
@@ -100,6 +104,77 @@ BLE_FN void plan_elite_segment(const uint16_t* order, int elite, const uint8_t* 
   counts3[0] = (uint16_t)c0; counts3[1] = (uint16_t)c1; counts3[2] = (uint16_t)c2;
 }
 
+// ---- expert iteration: a prior for iteration 0, and the per-action values of the plans flown
+constexpr int kPlanActions = 3;
+constexpr int kPlanNoPlan = 0x7FFFFFFF;          // the index of "no plan yet": behind every real plan of the same key
+
+// The prior count of one action in segment s: trunc(p * (strength >> s)), at most 65 535; the weight is zero from s = 16.  A NaN or
+// negative p gives 0, and so does a NaN product.
+BLE_FN uint16_t plan_prior_count(float p, int strength, int s) {
+  const uint32_t w = s < 16 ? ((uint32_t)strength >> s) : 0u;
+  const float v = p * (float)w;
+  const uint32_t c = v >= 65535.0f ? 65535u : (v >= 1.0f ? (uint32_t)v : 0u);
+  return p > 0.0f ? (uint16_t)c : (uint16_t)0;
+}
+
+// plan_sample_lane with a prior: iteration 0 draws its free plans (k >= 4) from `prior` [segments][3] where plan_sample_lane draws
+// from zeros.  Everything else -- the fixed slots, the streams, the later iterations -- is plan_sample_lane itself.
+BLE_FN void plan_sample_prior_lane(uint64_t seed, uint64_t key, uint64_t decision, int iteration, int k, int n_entries, int segment,
+                                   const uint16_t* counts, const uint16_t* prior, const uint8_t* prev, int64_t prev_stride, uint8_t* out,
+                                   int64_t out_stride) {
+  if (iteration > 0 || k < 4) {
+    plan_sample_lane(seed, key, decision, iteration, k, n_entries, segment, counts, prev, prev_stride, out, out_stride);
+    return;
+  }
+  Philox g = plan_stream(seed, key, decision, iteration, k);
+  int a = kPlanStay, left = 0, s = 0;
+#pragma unroll 1
+  for (int h = 0; h < n_entries; ++h) {
+    if (left == 0) {                             // entry h opens segment s
+      const int w = s & 3;
+      if (w == 0) philox_refill(g);
+      const uint32_t word = w == 0 ? g.out[0] : (w == 1 ? g.out[1] : (w == 2 ? g.out[2] : g.out[3]));
+      a = plan_draw(word, prior[3 * s], prior[3 * s + 1], prior[3 * s + 2]);
+      ++s; left = segment;
+    }
+    --left;
+    out[h * out_stride] = (uint8_t)a;
+  }
+}
+
+// The first plan in the selection's order among `n` plans (index k0, k0 + stride, ...) whose first action is a, as a (key, k) pair per
+// action, and how many take a.  best_k starts at kPlanNoPlan with the non-finite key.
+struct PlanActionBest {
+  uint32_t key[kPlanActions];
+  int k[kPlanActions], visits[kPlanActions];
+};
+BLE_FN void plan_action_best_init(PlanActionBest& b) {
+  for (int a = 0; a < kPlanActions; ++a) { b.key[a] = kPlanKeyNonFinite; b.k[a] = kPlanNoPlan; b.visits[a] = 0; }
+}
+BLE_FN void plan_action_best_take(PlanActionBest& b, int a, uint32_t key, int k, int visits) {
+  const bool better = plan_before(key, k, b.key[a], b.k[a]);
+  b.key[a] = better ? key : b.key[a];
+  b.k[a] = better ? k : b.k[a];
+  b.visits[a] += visits;
+}
+// One action's entry from the best pair of this call: (q, q_k) as written; ret_best is ret[k] (read only when the key is finite).
+// accumulate: the stored q stays unless plan_replaces says otherwise.
+BLE_FN void plan_action_write(uint32_t key, int k, float ret_best, int visits, bool accumulate, float* q, int32_t* q_k, int32_t* n_visits) {
+  const bool finite = key != kPlanKeyNonFinite;
+  if (!accumulate) {
+    union { uint32_t u; float f; } ninf;
+    ninf.u = 0xFF800000u;
+    *q = finite ? ret_best : ninf.f;
+    *q_k = finite ? k : -1;
+    *n_visits = visits;
+    return;
+  }
+  const bool replace = plan_replaces(key, true, plan_key(*q));
+  if (replace) *q = ret_best;
+  *q_k = replace ? k : -1;
+  *n_visits += visits;
+}
+
 #if defined(__HIPCC__)
 // struct ble_plan_sample (include/ble_abi.h) as the kernel takes it
 struct PlanSampleArgs {
@@ -176,6 +251,74 @@ __global__ __launch_bounds__(kPlanSelectBlock) void ble_plan_select_kernel(PlanS
     for (int s = lane; s < segments; s += kPlanSelectBlock)
       plan_elite_segment(order, a.elite, a.plans + (int64_t)(s * a.segment) * lanes_total + e * K, a.counts + (e * segments + s) * 3);
   }
+}
+// ---- expert iteration
+// One lane per (environment, segment): probs [n][3] -> counts [n][segments][3].
+__global__ __launch_bounds__(256) void ble_plan_prior_kernel(const float* __restrict__ probs, int strength, int segments,
+                                                             uint16_t* __restrict__ counts, int64_t total) {
+  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (i >= total) return;
+  const int64_t e = (int64_t)((uint32_t)i / (uint32_t)segments);      // (total < 2^31: the entry point checks)
+  const int s = (int)(i - e * segments);
+  for (int a = 0; a < kPlanActions; ++a) counts[3 * i + a] = plan_prior_count(probs[3 * e + a], strength, s);
+}
+
+// ble_plan_sample_kernel with a prior: an instantiation of its own, so that the kernels without one keep their instructions.
+template <class S>
+__global__ __launch_bounds__(256) void ble_plan_sample_prior_kernel(PlanSampleArgs a, const uint16_t* __restrict__ prior, S seed) {
+  const int64_t lanes_total = a.n * (int64_t)a.n_plans;          // < 2^31 (the entry point checks)
+  const int64_t j = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (j >= lanes_total) return;
+  const int64_t e = (int64_t)((uint32_t)j / (uint32_t)a.n_plans);
+  const int k = (int)(j - e * a.n_plans);
+  const int segments = (a.n_entries + a.segment - 1) / a.segment;
+  plan_sample_prior_lane(seed.of(e), seed.key(e, a.env_offset), *a.decision, a.iteration, k, a.n_entries, a.segment,
+                         a.counts ? a.counts + e * (int64_t)(3 * segments) : nullptr, prior + e * (int64_t)(3 * segments), a.best_plan + e,
+                         a.n, a.plans + j, lanes_total);
+}
+
+// struct ble_plan_action_values (include/ble_abi.h) as the kernel takes it
+struct PlanActionValuesArgs {
+  int64_t n;
+  int n_plans, accumulate;
+  const float* __restrict__ ret;               // [n][K]
+  const uint8_t* __restrict__ first;           // [n][K]
+  float* q;                                    // [n][3]
+  int32_t* q_k;                                // [n][3]
+  int32_t* visits;                             // [n][3]
+};
+
+// One wavefront per environment: every lane folds its plans (k = lane, lane + 64, ...) into a (key, k) pair and a count per action,
+// the 64 partial results meet in LDS, and lane a folds them for action a, in lane order.  Integer compares only; no atomics.
+__global__ __launch_bounds__(kPlanSelectBlock) void ble_plan_action_values_kernel(PlanActionValuesArgs a) {
+  __shared__ uint32_t s_key[kPlanActions][kPlanSelectBlock];
+  __shared__ int s_k[kPlanActions][kPlanSelectBlock];
+  __shared__ int s_visits[kPlanActions][kPlanSelectBlock];
+  const int64_t e = blockIdx.x;
+  const int lane = (int)threadIdx.x, K = a.n_plans;
+  PlanActionBest mine;
+  plan_action_best_init(mine);
+  for (int k = lane; k < K; k += kPlanSelectBlock) {
+    const uint32_t key = plan_key(a.ret[e * K + k]);
+    const int first = a.first[e * K + k];
+    const int act = first >= 2 ? 2 : first;
+#pragma unroll
+    for (int c = 0; c < kPlanActions; ++c) plan_action_best_take(mine, c, act == c ? key : kPlanKeyNonFinite, act == c ? k : kPlanNoPlan, act == c ? 1 : 0);
+  }
+#pragma unroll
+  for (int c = 0; c < kPlanActions; ++c) { s_key[c][lane] = mine.key[c]; s_k[c][lane] = mine.k[c]; s_visits[c][lane] = mine.visits[c]; }
+  __syncthreads();
+  if (lane >= kPlanActions) return;
+  uint32_t key = kPlanKeyNonFinite;
+  int k = kPlanNoPlan, visits = 0;
+  for (int l = 0; l < kPlanSelectBlock; ++l) {
+    const bool better = plan_before(s_key[lane][l], s_k[lane][l], key, k);
+    key = better ? s_key[lane][l] : key;
+    k = better ? s_k[lane][l] : k;
+    visits += s_visits[lane][l];
+  }
+  const float ret_best = key != kPlanKeyNonFinite ? a.ret[e * K + k] : 0.0f;      // (a finite key names a real plan: k < K)
+  plan_action_write(key, k, ret_best, visits, a.accumulate != 0, a.q + 3 * e + lane, a.q_k + 3 * e + lane, a.visits + 3 * e + lane);
 }
 #endif  // __HIPCC__
 

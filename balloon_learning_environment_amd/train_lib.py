@@ -1,7 +1,8 @@
 """The training loops of the device learners over a VecBalloonEnv: the reference's train_lib.run_training_loop with Dopamine's
 schedule (min_replay_history, update_period, target_update_period counted in transitions) for the replay learners (QNetworkTrainer,
-DQNTrainer), the loop of an online learner (VecMLPAgent), the on-policy loop (PPOTrainer) and the DAgger loop of an imitation learner
-(BCTrainer); N environments per step.
+DQNTrainer), the loop of an online learner (VecMLPAgent), the on-policy loop (PPOTrainer), the DAgger loop of an imitation learner
+(BCTrainer) and the expert-iteration loop of a soft-target learner and a planner (SoftBCTrainer, VecLookaheadAgent); N environments per
+step.
 """
 from typing import Callable, List, Optional, Union
 
@@ -271,5 +272,82 @@ def run_dagger_loop_vec(env, trainer, expert, rollout, *, num_iterations: int, b
     s = book.finish_iteration(steps)
     s['agreement'] = float(agree_sum.item()) / max(updates, 1)
     s['expert_share'] = float(took_sum.item()) / (n * steps)
+    stats.append(s)
+  return stats
+
+
+def run_exit_loop_vec(env, trainer, planner, buffer, *, num_iterations: int, beta: Union[float, Callable[[int], float]], epochs: int,
+                      batch_size: int, max_episode_length: int = 960, capture_graph: bool = True) -> List[dict]:
+  """Expert iteration of a soft-target learner (agents/expert_iteration.py: SoftBCTrainer with a VecPlanLabelBuffer of T
+  steps) and a planner (a venv.planner(prior_strength=..., action_values=True) bound to env's simulator) on `env` (auto_reset).  Each
+  step, in this order: the learner samples its action on the observation and gives its probabilities (trainer.act(..., probs=));
+  the planner decides on the same observation with those probabilities as its prior (planner.act(obs, label, prior_probs=probs)); the
+  action flown is the planner's with probability beta_i, else the learner's (trainer.mix, the DAgger mixture); env.step; the block
+  stores the observation acted on, the planner's per-action values and its best return there (buffer.add(t, obs, q, best_return)).
+  beta: a float or a function of the iteration index.  The episode limit is run_training_loop_vec's.
+
+  After the T steps `epochs` passes of minibatches of batch_size rows follow, each one soft update (epochs x (T N // batch_size) in
+  all); then the block is discarded.
+
+  Returns run_training_loop_vec's dicts plus loss (mean_loss under the issue's name), agreement (the mean over the iteration's updates
+  of the fraction of rows whose greedy action is the best-valued one), expert_share (the fraction of the block's actions that were the
+  planner's) and mean_best_return (the mean over the block of the planner's finite best returns).  The only host synchronisation is the
+  end of an iteration."""
+  n, dev_ = env.num_envs, env.device
+  assert buffer.num_envs == n, 'the label block has one column per environment'
+  steps = buffer.horizon
+  obs = env.reset()
+  learner = torch.zeros(n, dtype=torch.uint8, device=dev_)
+  label = torch.zeros(n, dtype=torch.uint8, device=dev_)
+  actions = torch.zeros(n, dtype=torch.uint8, device=dev_)
+  took = torch.zeros(n, dtype=torch.uint8, device=dev_)
+  logp = torch.zeros(n, dtype=torch.float32, device=dev_)
+  value = torch.zeros(n, dtype=torch.float32, device=dev_)
+  probs = torch.zeros(n, 3, dtype=torch.float32, device=dev_)
+  book = _EpisodeBook(n, dev_, max_episode_length)
+  captured = False
+  stats = []
+  for it in range(num_iterations):
+    beta_i = float(beta(it) if callable(beta) else beta)
+    took_sum = torch.zeros((), dtype=torch.int64, device=dev_)
+    agree_sum = torch.zeros((), dtype=torch.float32, device=dev_)
+    best_sum = torch.zeros((), dtype=torch.float32, device=dev_)
+    best_count = torch.zeros((), dtype=torch.int64, device=dev_)
+    for t in range(steps):
+      trainer.act(obs, learner, logp, value, probs)
+      planner.act(obs, label, prior_probs=probs)
+      trainer.mix(learner, label, beta_i, actions, took)
+      end_mask = book.end_mask()
+      next_obs, reward, terminal = env.step(actions, end_mask=end_mask)
+      episode_end = terminal | end_mask
+      q, _ = planner.action_values()
+      _, best_return = planner.plan()
+      buffer.add(t, obs, q, best_return)
+      book.step(reward, episode_end)
+      took_sum += took.sum()
+      finite = torch.isfinite(best_return)
+      best_sum += torch.where(finite, best_return, torch.zeros_like(best_return)).sum()
+      best_count += finite.sum()
+      obs = next_obs
+    for _ in range(epochs):
+      for batch in buffer.minibatches(batch_size):
+        if capture_graph and not captured:
+          loss = trainer.capture(batch)                     # (its first, eager update is a real one)
+          captured = True
+        else:
+          loss = trainer.train_step(batch)
+        book.update(loss)
+        agree_sum += trainer.views(batch_size)['aux'][:, 1].mean()
+    env.check_errors()
+    trainer.check_errors()
+    if hasattr(planner, 'check_errors'):
+      planner.check_errors()
+    updates = book.updates
+    s = book.finish_iteration(steps)
+    s['loss'] = s['mean_loss']
+    s['agreement'] = float(agree_sum.item()) / max(updates, 1)
+    s['expert_share'] = float(took_sum.item()) / (n * steps)
+    count = int(best_count.item())
+    s['mean_best_return'] = float(best_sum.item()) / count if count else float('nan')
     stats.append(s)
   return stats

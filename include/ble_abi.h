@@ -922,6 +922,35 @@ typedef struct ble_dagger_mix_f32 {
 int ble_dagger_mix_u8(const ble_dagger_mix_f32* mix, void* stream);
 
 /*
+ * Soft targets (additive to ABI 5): cloning against a distribution over the three actions made from per-action values
+ * target_q [B][3] -- a planner's per-action plan returns (ble_plan_action_values_f32), Q-values -- where ble_qnet_bc_step_f32 takes one
+ * label.  §3m's arithmetic rules; the log-softmax is the heads' own.
+ */
+typedef struct ble_soft_bc_f32 {
+  float inv_temperature;       /* beta: finite, > 0 */
+  float label_smoothing;       /* s: finite, in [0, 1) */
+  float value_coef;            /* c_v, finite; 0: no value term, batch->ret is not read and may be NULL */
+  int32_t reserved_;           /* 0 */
+  const float* target_q;       /* device [B][3]; a non-finite entry marks an action without a value */
+} ble_soft_bc_f32;
+
+/*
+ * ble_qnet_soft_bc_step_f32: ble_qnet_bc_step_f32's stages with the soft loss; batch->action is not read and may be NULL.
+ * Per row, with q = target_q[b], R = ret[b], (lp, p) the log-softmax of z[0], z[2], z[4]:
+ *   valid_a = isfinite(q_a);  y_a = valid_a ? q_a beta : -Inf;  (lt, t) = the log-softmax of y (an invalid action: t_a = 0 exactly);
+ *   u_a = (1 - s) t_a;  t'_a = u_a + s / 3;  CE = -((t'0 lp0 + t'1 lp1) + t'2 lp2);  L_b = CE + c_v (z[1] - R)^2;
+ *   dL/dz[2a] = (p_a - t'_a) / B;  dL/dz[1] = (2 c_v (z[1] - R)) / B;
+ *   aux[b] = (lp[a*], agree), a* the valid action whose q comes first in ble_plan_select_f32's order (the value descending, -0 == +0,
+ *   then a ascending), agree = 1.0f when the greedy action of these logits equals a*.
+ * No valid action: the row's loss, aux and gradient are exactly 0 and no flag is set.  Exactly one valid action a: the row's loss, aux
+ * and gradient are ble_qnet_bc_step_f32's with the label a, bit for bit.  B == 0 launches nothing.
+ * BLE_E_INVALID_ARG before any HIP call: what ble_qnet_bc_step_f32 refuses (but a NULL batch->action); a NULL soft or target_q; beta not
+ * finite or <= 0.
+ */
+int ble_qnet_soft_bc_step_f32(const ble_qnet_train_f32* tr, const ble_soft_bc_f32* soft, const ble_train_batch_f32* batch, float* loss,
+                              uint32_t* err_flags, void* stream);
+
+/*
  * Prioritized n-step replay (additive to ABI 5): Dopamine 4.0.0's OutOfGraphPrioritizedReplayBuffer over the ring above.
  * An fp64 sum tree over capacity x num_envs leaves: leaf (t % capacity) num_envs + env is the n-step window that starts at ring row t
  * of that environment.  A heap padded to a power of two: nodes[1] is the root, nodes[padded + i] leaf i, nodes[0] unused, the padded
@@ -1279,6 +1308,76 @@ struct ble_plan_risk {
   float* score;                              /* device [n][K] out */
 };
 int ble_plan_risk_f32(const struct ble_plan_risk* risk, void* stream);
+
+/*
+ * Expert iteration: a policy prior for the sampler and per-action values of the plans flown.  Added without a new ABI
+ * version; every size travels in a struct.
+ *
+ * ble_plan_prior_u16: probabilities probs [n][3] -> counts [n][segments][3], the layout of elite_counts, one lane per (e, s):
+ *     w_s = s < 16 ? strength >> s : 0;   v = p_a * (float)w_s (one fp32 product);   c = p_a > 0 ? min(65535, trunc(v)) : 0
+ * (a NaN or negative p_a, and a v that is NaN, give 0).  The sampler's P(a) = (c_a + 1) / (c_0 + c_1 + c_2 + 3) then leans towards the
+ * prior with a weight that halves per segment.
+ * BLE_E_INVALID_ARG before any HIP call: NULL pr, probs or prior_counts; n < 0; segments outside 1 .. BLE_ROLLOUT_MAX_STEPS; strength
+ * outside 0 .. 65 535; n * segments >= 2^31.  n == 0: BLE_OK without a launch.
+ */
+struct ble_plan_prior {
+  int64_t n;                                 /* environments */
+  int32_t segments;                          /* ceil(H / segment) of the sampler */
+  int32_t strength;                          /* 0 .. 65 535 */
+  const float* probs;                        /* device [n][3] */
+  uint16_t* prior_counts;                    /* device [n][segments][3] out */
+};
+int ble_plan_prior_u16(const struct ble_plan_prior* pr, void* stream);
+
+/*
+ * ble_plan_sample_prior_u8: ble_plan_sample_u8, except that iteration 0 draws its free plans (k >= 4) from prior_counts where
+ * ble_plan_sample_u8 draws from zeros; the fixed slots, the streams, the keying and the warm start are the same, iterations >= 1 read
+ * elite_counts, and all-zero prior_counts give ble_plan_sample_u8's plans bit for bit.  The fields before prior_counts are struct
+ * ble_plan_sample's, in its order.
+ * BLE_E_INVALID_ARG before any HIP call: what ble_plan_sample_u8 refuses, and a NULL prior_counts.
+ */
+struct ble_plan_sample_prior {
+  int64_t n;
+  int32_t n_plans;
+  int32_t n_plan_steps;
+  int32_t segment;
+  int32_t iteration;
+  unsigned long long seed;
+  const unsigned long long* env_seed;
+  int64_t env_offset;
+  const unsigned long long* decision_counter;
+  const uint16_t* elite_counts;
+  const uint8_t* best_plan;
+  uint8_t* plans;
+  const uint16_t* prior_counts;              /* device [n][ceil(H / segment)][3]: read in iteration 0 */
+};
+int ble_plan_sample_prior_u8(const struct ble_plan_sample_prior* ps, void* stream);
+
+/*
+ * ble_plan_action_values_f32: one wavefront per environment over ret [n][K] (the returns, or the risk scores) and the plans' first
+ * entries first_action [n][K] (plans[0]; an entry >= 2 counts as 2).  Per action a, the plan that comes first in ble_plan_select_f32's
+ * order among those whose first action is a:
+ *   q [n][3]       its return, bits unchanged; -Inf when no plan with a finite return takes a
+ *   q_k [n][3]     its index; -1 when q is -Inf
+ *   visits [n][3]  how many of the K plans take a
+ * accumulate != 0 (the later iterations of a decision): q[e][a] is replaced only by ble_plan_select_f32's incumbent rule -- the new
+ * value is finite and strictly better, or the stored one is not finite -- and q_k then names the new plan; otherwise q stays and q_k
+ * is -1.  visits adds up.  Integer compares of (key, k) pairs only.  After a decision, an environment with a finite best_return has
+ * q[e][action[e]] == best_return[e] bit for bit, and no other entry of q[e] before it in the order.
+ * BLE_E_INVALID_ARG before any HIP call: NULL av, ret, first_action, q, q_k or visits; n < 0 or >= 2^31; n_plans outside
+ * 1 .. BLE_PLAN_MAX_PLANS; n * n_plans >= 2^31.  n == 0: BLE_OK without a launch.
+ */
+struct ble_plan_action_values {
+  int64_t n;
+  int32_t n_plans;                           /* K */
+  int32_t accumulate;                        /* 0: write; else: merge into q, q_k, visits */
+  const float* ret;                          /* device [n][K] */
+  const uint8_t* first_action;               /* device [n][K] */
+  float* q;                                  /* device [n][3] */
+  int32_t* q_k;                              /* device [n][3] */
+  int32_t* visits;                           /* device [n][3] */
+};
+int ble_plan_action_values_f32(const struct ble_plan_action_values* av, void* stream);
 
 #ifdef __cplusplus
 }
