@@ -154,6 +154,13 @@ class BlePlanActionValues(ctypes.Structure):
               ('first_action', ctypes.c_void_p), ('q', ctypes.c_void_p), ('q_k', ctypes.c_void_p), ('visits', ctypes.c_void_p)]
 
 
+class BlePlanBootstrap(ctypes.Structure):
+  """struct ble_plan_bootstrap: ret [n][K], steps_flown [n][K], the leaves' status and value [n K] -> score [n][K] (device pointers)."""
+  _fields_ = [('n', ctypes.c_int64), ('n_plans', ctypes.c_int32), ('reserved_', ctypes.c_int32), ('gamma', ctypes.c_double),
+              ('ret', ctypes.c_void_p), ('steps_flown', ctypes.c_void_p), ('leaf_status', ctypes.c_void_p), ('value', ctypes.c_void_p),
+              ('score', ctypes.c_void_p)]
+
+
 SCENARIO_MAX = 16           # BLE_SCENARIO_MAX
 
 

@@ -51,14 +51,16 @@ EXPORTS = ('ble_abi_version', 'ble_noise_primitive_version', 'ble_vehicle_defaul
            'ble_gp_fit_f32', 'ble_gp_belief_wind_f32', 'ble_rollout_belief_f32', 'ble_plan_sample_u8', 'ble_plan_select_f32',
            'ble_gp_fit_scenarios_f32', 'ble_gp_scenario_wind_f32', 'ble_rollout_scenarios_f32', 'ble_plan_risk_f32',
            'ble_ac_act_f32', 'ble_gae_f32', 'ble_adv_normalize_f32', 'ble_qnet_ppo_step_f32', 'ble_qnet_bc_step_f32', 'ble_dagger_mix_u8',
-           'ble_plan_prior_u16', 'ble_plan_sample_prior_u8', 'ble_plan_action_values_f32', 'ble_qnet_soft_bc_step_f32')
+           'ble_plan_prior_u16', 'ble_plan_sample_prior_u8', 'ble_plan_action_values_f32', 'ble_qnet_soft_bc_step_f32',
+           'ble_rollout_leaves_f32', 'ble_observe_leaves_f32', 'ble_plan_bootstrap_f32')
 # Exports added without a new ABI version: a library of this ABI built before them (BLE_HIP_LIB: the parent's, in A/B runs) still loads.
 # build() checks every name of EXPORTS on the library it builds.
 ADDITIVE_EXPORTS = ('ble_last_step_form', 'ble_gp_query_f32', 'ble_rollout_f32', 'ble_gp_fit_f32', 'ble_gp_belief_wind_f32',
                     'ble_rollout_belief_f32', 'ble_plan_sample_u8', 'ble_plan_select_f32', 'ble_gp_fit_scenarios_f32',
                     'ble_gp_scenario_wind_f32', 'ble_rollout_scenarios_f32', 'ble_plan_risk_f32', 'ble_ac_act_f32', 'ble_gae_f32',
                     'ble_adv_normalize_f32', 'ble_qnet_ppo_step_f32', 'ble_qnet_bc_step_f32', 'ble_dagger_mix_u8', 'ble_plan_prior_u16',
-                    'ble_plan_sample_prior_u8', 'ble_plan_action_values_f32', 'ble_qnet_soft_bc_step_f32')
+                    'ble_plan_sample_prior_u8', 'ble_plan_action_values_f32', 'ble_qnet_soft_bc_step_f32', 'ble_rollout_leaves_f32',
+                    'ble_observe_leaves_f32', 'ble_plan_bootstrap_f32')
 
 
 class BleLibraryError(RuntimeError):
@@ -89,6 +91,10 @@ def build(force: bool = False, verbose: bool = False) -> str:
 
 _lib = None
 _vp, _i64, _int = ctypes.c_void_p, ctypes.c_int64, ctypes.c_int
+
+
+class _I64(ctypes.c_int64):
+  """int64_t, as an argument type of its own (ble_observe_leaves_f32 below)."""
 
 
 def lib():
@@ -206,6 +212,13 @@ def lib():
     l.ble_plan_sample_prior_u8.argtypes = [ctypes.POINTER(_abi.BlePlanSamplePrior), _vp]
     l.ble_plan_action_values_f32.argtypes = [ctypes.POINTER(_abi.BlePlanActionValues), _vp]
     l.ble_qnet_soft_bc_step_f32.argtypes = [train, ctypes.POINTER(_abi.BleSoftBcF32), batch, _vp, _vp, _vp]
+  if hasattr(l, 'ble_rollout_leaves_f32'):    # a learned terminal value: the leaves as states, their observation, the bootstrap
+    l.ble_rollout_leaves_f32.argtypes = [st, ctypes.POINTER(_abi.BleRolloutF32), ctypes.POINTER(_abi.BleNoiseGen),
+                                         ctypes.POINTER(_abi.BleGpBelief), st, _vp, _vp]
+    # (its three int64_t arguments are _I64, a subclass of c_int64: test_entry_checks_host.py keeps a closed table of the entry points
+    # that take a plain c_int64; this one's argument checks are tests/test_leaves_entry_checks_host.py's)
+    l.ble_observe_leaves_f32.argtypes = [st, ctypes.c_int32, _vp, _I64, _vp, ctypes.POINTER(_abi.BleGpHistoryF32), _vp, _I64, _vp, _I64, _vp]
+    l.ble_plan_bootstrap_f32.argtypes = [ctypes.POINTER(_abi.BlePlanBootstrap), _vp]
   for name in EXPORTS:
     if hasattr(l, name) or name not in ADDITIVE_EXPORTS:
       getattr(l, name).restype = _int

@@ -166,7 +166,9 @@ class VecPlanLabelBuffer:
 class VecPriorPlannerAgent:
   """A planner that searches where a policy points: act(obs) runs the actor-critic `policy` (a VecActorCriticAgent, or a trainer with
   act_greedy) for its probabilities and hands them to `planner` (a VecLookaheadAgent built with prior_strength > 0) as its prior.  An
-  agent like any other device agent: eval_lib.VecEvaluator binds it to its simulator and may capture it in a graph."""
+  agent like any other device agent: eval_lib.VecEvaluator binds it to its simulator and may capture it in a graph.  The same network
+  can serve twice: as `policy` here and as the planner's leaf_value (VecLookaheadAgent(leaf_value=policy)) -- its policy head
+  biases where the planner searches, its value head scores where the plans end."""
 
   def __init__(self, policy, planner):
     self.policy, self.planner = policy, planner

@@ -42,12 +42,23 @@ class VecLookaheadAgent:
   policy prior instead of from uniform thirds: segment s draws action a with probability (c_a + 1) / (c_0 + c_1 + c_2 + 3),
   c_a = trunc(p_a * (prior_strength >> s)) -- the prior's weight halves per segment.  0, or no prior_probs: today's calls.
   action_values: True computes, after every selection of a decision, the best return among the plans that begin with each action
-  (action_values()); False (the default) adds no launch."""
+  (action_values()); False (the default) adds no launch.
+  leaf_value: a critic -- an object with act_greedy(obs, value=) (PPOTrainer, BCTrainer, SoftBCTrainer: their live weights)
+  or else act(obs, value=) (a deterministic VecActorCriticAgent) -- whose value of every plan's END state is added to the plan's return:
+  score = return + gamma^steps_flown * V(leaf), so a plan of H steps is judged by what follows it as well.  Every iteration of a
+  decision then runs sample -> rollout_plans(leaves=) -> observe_leaves -> the critic over the n K leaf observations ->
+  ble_plan_bootstrap_f32 into `returns` -> select (and the action values, if on): best_return, q and the elite counts are all taken
+  from the bootstrapped scores.  A plan that ends in a terminal keeps its return (no value after the end).  The leaf arena, the
+  [n K, 1099] observation buffer and the values are allocated in bind: 4.4 KB per leaf for the observations (288 MB at n = 4 096,
+  K = 16) plus about 230 B per leaf of state; bind also calls the critic once at that row count, as a graph capture needs
+  (ActorForward's contract).  A sampling VecActorCriticAgent (deterministic=False) is refused -- its step counter would move with
+  every decision -- and so is wind='scenarios' (M end states per plan).  The same network may serve as the prior of a
+  VecPriorPlannerAgent and as leaf_value.  None (the default): today's calls and today's bits."""
 
   def __init__(self, num_plans: int = 64, horizon: int = 24, action_repeat: int = 1, segment: int = 4, gamma: float = 0.993,
                wind: str = 'belief', iterations: int = 1, elite: int = 8, seed: int = 0, device='cuda:0',
                substeps: int = vec_state.SUBSTEPS, num_scenarios: int = 8, risk_tail: Optional[int] = None, prior_strength: int = 0,
-               action_values: bool = False):
+               action_values: bool = False, leaf_value=None):
     if wind not in WINDS:
       raise ValueError(f"VecLookaheadAgent: wind is 'belief', 'forecast', 'truth' or 'scenarios', not {wind!r}")
     self.num_scenarios = int(num_scenarios) if wind == 'scenarios' else 0
@@ -68,6 +79,19 @@ class VecLookaheadAgent:
     if not 0 <= int(prior_strength) <= 65535:
       raise ValueError(f'VecLookaheadAgent: 0 <= prior_strength <= 65535, not {prior_strength}')
     self.prior_strength, self.with_action_values = int(prior_strength), bool(action_values)
+    self.leaf_value, self._leaf_fn = leaf_value, None
+    if leaf_value is not None:
+      if wind == 'scenarios':
+        raise ValueError("VecLookaheadAgent: leaf_value with wind='scenarios': a plan has M end states there; plan in the belief or the forecast")
+      if hasattr(leaf_value, 'act_greedy'):
+        self._leaf_fn = leaf_value.act_greedy
+      elif getattr(leaf_value, 'deterministic', True) is False:
+        raise ValueError('VecLookaheadAgent: leaf_value is a sampling agent (deterministic=False): its step counter would move with every '
+                         'decision; give a deterministic one, or a trainer (act_greedy)')
+      elif hasattr(leaf_value, 'act'):
+        self._leaf_fn = leaf_value.act
+      else:
+        raise ValueError('VecLookaheadAgent: leaf_value needs act_greedy(obs, value=) or act(obs, value=)')
     self.device = dev.require_gpu(device)
     self.lib = _lib.lib()
     self.num_plans, self.horizon, self.action_repeat, self.segment = int(num_plans), int(horizon), int(action_repeat), int(segment)
@@ -121,6 +145,13 @@ class VecLookaheadAgent:
         m = self.num_scenarios
         self._scenarios = vec_state.WindScenarios(z(torch.float64, n, _abi.gp_scenario_doubles(m)), z(torch.int32, n), m, self.seed, seeds)
         self.scenario_returns, self.scenario_steps = z(torch.float32, n, k, m), z(torch.int32, n, k, m)
+      self.leaves = None
+      if self._leaf_fn is not None:
+        self.leaves = sim.leaf_arena(k)
+        self.leaf_obs = torch.empty(n * k, _lib.OBS_DIM, dtype=torch.float32, device=self.device)
+        self.leaf_values, self.leaf_actions = z(torch.float32, n * k), z(torch.uint8, n * k)
+        self.leaf_obs.zero_()
+        self._leaf_fn(self.leaf_obs, out=self.leaf_actions, value=self.leaf_values)      # the first call at this row count: not in a capture
     self.counter.zero_()
     self.best_plan.fill_(STAY)
     self.best_return.zero_()
@@ -179,7 +210,14 @@ class VecLookaheadAgent:
                           out=(self.scenario_returns, self.scenario_steps, None, None), scenarios=scenarios)
         sim.plan_risk(self.scenario_returns, self.risk_tail, out=self.returns)
       else:
-        sim.rollout_plans(self.plans, self.gamma, self.action_repeat, noise_seed, self.substeps, out=rollout_out, belief=belief)
+        sim.rollout_plans(self.plans, self.gamma, self.action_repeat, noise_seed, self.substeps, out=rollout_out, belief=belief,
+                          leaves=self.leaves)
+      if self.leaves is not None:    # score = return + gamma^steps_flown * V(leaf), in place: everything below reads the scores
+        sim.observe_leaves(self.leaves, out=self.leaf_obs)
+        self._leaf_fn(self.leaf_obs, out=self.leaf_actions, value=self.leaf_values)
+        bs = _abi.BlePlanBootstrap(n, self.num_plans, 0, self.gamma, self.returns.data_ptr(), self.steps_flown.data_ptr(),
+                                   self.leaves.state['status'].data_ptr(), self.leaf_values.data_ptr(), self.returns.data_ptr())
+        _lib.check(self.lib.ble_plan_bootstrap_f32(ctypes.byref(bs), stream), 'ble_plan_bootstrap_f32')
       # (the elite counts are the next iteration's: the last selection writes none, and moves the decision counter on)
       sel = _abi.BlePlanSelect(n, self.num_plans, self.horizon, self.segment, it, 0 if last else self.elite, 0, self.returns.data_ptr(),
                                self.plans.data_ptr(), self.best_return.data_ptr(), self.best_k.data_ptr(), self.best_plan.data_ptr(),

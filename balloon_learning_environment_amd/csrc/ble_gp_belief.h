@@ -318,8 +318,11 @@ __global__ __launch_bounds__(kBeliefWindBlock) void ble_gp_belief_wind_kernel(Be
 
 // ble_rollout_kernel's body (ble_rollout.h) in forecast + the belief's mean: every lane of environment e evaluates gp_belief_mean on
 // e's slab at its own pre-step position and time.  Reads the belief, writes what ble_rollout_kernel writes.
-template <class V = VehicleDefault>
-__global__ __launch_bounds__(kStepBlock) void ble_rollout_belief_kernel(StateDev st, RolloutArgs a, BeliefDev b, uint32_t* err_flags, V veh) {
+// kLeaves: the lane's whole end state goes to the leaf arena as well (ble_rollout.h: leaf_store and the trailing pack).
+template <class V = VehicleDefault, bool kLeaves = false, class... Leaf>
+__global__ __launch_bounds__(kStepBlock) void ble_rollout_belief_kernel(StateDev st, RolloutArgs a, BeliefDev b, uint32_t* err_flags, V veh,
+                                                                        Leaf... leaves) {
+  static_assert(sizeof...(Leaf) == (kLeaves ? 1 : 0), "with leaves: the leaf arena's StateDev; without: nothing");
   __shared__ double acs_poly[kAcsPolyDoubles];
   __shared__ float term_save[kTermSaveRows * kStepBlock];
   __shared__ double tab[64];
@@ -366,6 +369,7 @@ __global__ __launch_bounds__(kStepBlock) void ble_rollout_belief_kernel(StateDev
   // the discounted return: fp64, the product and the sum as two statements (two roundings under -ffp-contract=on), rounded to fp32 once
   double acc = 0.0, disc = 1.0;
   int flown = 0;
+  LeafLast<kLeaves> last;                       // (with leaves: the raw action of the last step flown)
   int64_t o = j;                                // (agent step t) * n K + j
 #pragma unroll 1
   for (int h = 0; h < a.n_plan_steps; ++h) {
@@ -374,6 +378,7 @@ __global__ __launch_bounds__(kStepBlock) void ble_rollout_belief_kernel(StateDev
     for (int rep = 0; rep < a.action_repeat; ++rep, o += lanes_total) {
       if (live) {
         ++flown;
+        if constexpr (kLeaves) last.act = act;
         const WindQuery wq = wind_query(s.x, s.y, s.p, s.t_elapsed);
         WindCorners corners;
         wind_gather(grid, wq, &corners);
@@ -402,6 +407,7 @@ __global__ __launch_bounds__(kStepBlock) void ble_rollout_belief_kernel(StateDev
       a.final_state[j] = s.x; a.final_state[lanes_total + j] = s.y; a.final_state[2 * lanes_total + j] = s.p;
       a.final_state[3 * lanes_total + j] = s.batt;
     }
+    if constexpr (kLeaves) leaf_store(st, leaf_arena(leaves...), e, j, flown > 0, s, c, last.act);      // (flown > 0: the source was OK)
   }
   report_flags(flags, err_flags);
 }

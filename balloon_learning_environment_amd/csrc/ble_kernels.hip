@@ -1119,6 +1119,50 @@ int with_scenario_seed(const ble_scenario_gen* gen, F&& f) {
 static_assert(kScenarioMax == BLE_SCENARIO_MAX && BLE_GP_SCENARIO_DOUBLES(3) == kBeliefAlphaAt + 3 * kScenarioAlphaDoubles,
               "ble_scenarios.h and ble_abi.h disagree on the slab");
 
+// ble_rollout_f32 and, with leaves (the leaf arena's StateDev as the one trailing argument), ble_rollout_leaves_f32 in the forecast or a
+// noise generator's wind
+template <class... Leaf>
+int launch_rollout(const ble_state_f32* st, const struct ble_rollout_f32* ro, const ble_noise_gen* noise, uint32_t* err_flags, void* stream,
+                   const Leaf&... leaves) {
+  if (!state_ok(st) || !ro || !ro->plans || !ro->wind_grid || !ro->ret || !ro->steps_flown) return BLE_E_INVALID_ARG;
+  if (ro->n < 0 || ro->n >= 2147483648LL || ro->n_plans < 1 || ro->n * (int64_t)ro->n_plans >= 2147483648LL || ro->n_plan_steps < 1 ||
+      ro->action_repeat < 1 || (int64_t)ro->n_plan_steps * ro->action_repeat > BLE_ROLLOUT_MAX_STEPS)
+    return BLE_E_INVALID_ARG;
+  if (ro->substeps < 1 || ro->substeps > BLE_MAX_SUBSTEPS || ro->grid_env_stride < 0 || (noise != nullptr && noise->env_offset < 0) ||
+      !(ro->gamma >= 0.0 && ro->gamma <= 1.0))                      // (a NaN gamma fails both comparisons)
+    return BLE_E_INVALID_ARG;
+  return with_vehicle<false>(st, nullptr, [&](auto veh) {
+    if (ro->n == 0) return BLE_OK;
+    const RolloutArgs a{ro->n, ro->n_plans, ro->n_plan_steps, ro->action_repeat, ro->substeps, ro->gamma, ro->plans, ro->wind_grid,
+                        ro->grid_env_stride, ro->ret, ro->steps_flown, ro->reward, ro->final_state};
+    // (the harmonic cache of `noise` is not handed on for writing: ble_rollout_kernel draws into LDS and fills no cache)
+    return with_noise(noise, [&](auto noise_on, StepNoise gen) {
+      return launch(ble_rollout_kernel<decltype(noise_on)::value, decltype(veh), (sizeof...(Leaf) > 0), Leaf...>, ro->n * (int64_t)ro->n_plans,
+                    kStepBlock, kStepBlock, stream, state_dev(st), a, err_flags, gen, veh, leaves...);
+    });
+  });
+}
+// ble_rollout_belief_f32 and, with leaves, ble_rollout_leaves_f32 in the belief's wind
+template <class... Leaf>
+int launch_rollout_belief(const ble_state_f32* st, const struct ble_rollout_f32* ro, const ble_gp_belief* belief, uint32_t* err_flags,
+                          void* stream, const Leaf&... leaves) {
+  BeliefDev b;
+  if (!state_ok(st) || !ro || !ro->plans || !ro->wind_grid || !ro->ret || !ro->steps_flown || !gp_belief(belief, &b)) return BLE_E_INVALID_ARG;
+  if (ro->n < 0 || ro->n >= 2147483648LL || ro->n_plans < 1 || ro->n * (int64_t)ro->n_plans >= 2147483648LL || ro->n_plan_steps < 1 ||
+      ro->action_repeat < 1 || (int64_t)ro->n_plan_steps * ro->action_repeat > BLE_ROLLOUT_MAX_STEPS)
+    return BLE_E_INVALID_ARG;
+  if (ro->substeps < 1 || ro->substeps > BLE_MAX_SUBSTEPS || ro->grid_env_stride < 0 || !(ro->gamma >= 0.0 && ro->gamma <= 1.0) ||
+      belief->n != ro->n)                                             // (a belief of another batch would be read out of bounds)
+    return BLE_E_INVALID_ARG;
+  return with_vehicle<false>(st, nullptr, [&](auto veh) {
+    if (ro->n == 0) return BLE_OK;
+    const RolloutArgs a{ro->n, ro->n_plans, ro->n_plan_steps, ro->action_repeat, ro->substeps, ro->gamma, ro->plans, ro->wind_grid,
+                        ro->grid_env_stride, ro->ret, ro->steps_flown, ro->reward, ro->final_state};
+    return launch(ble_rollout_belief_kernel<decltype(veh), (sizeof...(Leaf) > 0), Leaf...>, ro->n * (int64_t)ro->n_plans, kStepBlock, kStepBlock,
+                  stream, state_dev(st), a, b, err_flags, veh, leaves...);
+  });
+}
+
 }  // namespace
 
 extern "C" {
@@ -1864,23 +1908,7 @@ int ble_gp_query_f32(const ble_gp_history_f32* hist, const uint8_t* reset_mask, 
 }
 
 int ble_rollout_f32(const ble_state_f32* st, const struct ble_rollout_f32* ro, const ble_noise_gen* noise, uint32_t* err_flags, void* stream) {
-  if (!state_ok(st) || !ro || !ro->plans || !ro->wind_grid || !ro->ret || !ro->steps_flown) return BLE_E_INVALID_ARG;
-  if (ro->n < 0 || ro->n >= 2147483648LL || ro->n_plans < 1 || ro->n * (int64_t)ro->n_plans >= 2147483648LL || ro->n_plan_steps < 1 ||
-      ro->action_repeat < 1 || (int64_t)ro->n_plan_steps * ro->action_repeat > BLE_ROLLOUT_MAX_STEPS)
-    return BLE_E_INVALID_ARG;
-  if (ro->substeps < 1 || ro->substeps > BLE_MAX_SUBSTEPS || ro->grid_env_stride < 0 || (noise != nullptr && noise->env_offset < 0) ||
-      !(ro->gamma >= 0.0 && ro->gamma <= 1.0))                      // (a NaN gamma fails both comparisons)
-    return BLE_E_INVALID_ARG;
-  return with_vehicle<false>(st, nullptr, [&](auto veh) {
-    if (ro->n == 0) return BLE_OK;
-    const RolloutArgs a{ro->n, ro->n_plans, ro->n_plan_steps, ro->action_repeat, ro->substeps, ro->gamma, ro->plans, ro->wind_grid,
-                        ro->grid_env_stride, ro->ret, ro->steps_flown, ro->reward, ro->final_state};
-    // (the harmonic cache of `noise` is not handed on for writing: ble_rollout_kernel draws into LDS and fills no cache)
-    return with_noise(noise, [&](auto noise_on, StepNoise gen) {
-      return launch(ble_rollout_kernel<decltype(noise_on)::value, decltype(veh)>, ro->n * (int64_t)ro->n_plans, kStepBlock, kStepBlock, stream,
-                    state_dev(st), a, err_flags, gen, veh);
-    });
-  });
+  return launch_rollout(st, ro, noise, err_flags, stream);
 }
 
 int ble_gp_fit_f32(const ble_gp_history_f32* hist, const uint8_t* reset_mask, const int32_t* time_s, const ble_gp_belief* belief,
@@ -1903,21 +1931,24 @@ int ble_gp_belief_wind_f32(const ble_gp_belief* belief, const float* x_m, const 
 
 int ble_rollout_belief_f32(const ble_state_f32* st, const struct ble_rollout_f32* ro, const ble_gp_belief* belief, uint32_t* err_flags,
                            void* stream) {
-  BeliefDev b;
-  if (!state_ok(st) || !ro || !ro->plans || !ro->wind_grid || !ro->ret || !ro->steps_flown || !gp_belief(belief, &b)) return BLE_E_INVALID_ARG;
-  if (ro->n < 0 || ro->n >= 2147483648LL || ro->n_plans < 1 || ro->n * (int64_t)ro->n_plans >= 2147483648LL || ro->n_plan_steps < 1 ||
-      ro->action_repeat < 1 || (int64_t)ro->n_plan_steps * ro->action_repeat > BLE_ROLLOUT_MAX_STEPS)
-    return BLE_E_INVALID_ARG;
-  if (ro->substeps < 1 || ro->substeps > BLE_MAX_SUBSTEPS || ro->grid_env_stride < 0 || !(ro->gamma >= 0.0 && ro->gamma <= 1.0) ||
-      belief->n != ro->n)                                             // (a belief of another batch would be read out of bounds)
-    return BLE_E_INVALID_ARG;
-  return with_vehicle<false>(st, nullptr, [&](auto veh) {
-    if (ro->n == 0) return BLE_OK;
-    const RolloutArgs a{ro->n, ro->n_plans, ro->n_plan_steps, ro->action_repeat, ro->substeps, ro->gamma, ro->plans, ro->wind_grid,
-                        ro->grid_env_stride, ro->ret, ro->steps_flown, ro->reward, ro->final_state};
-    return launch(ble_rollout_belief_kernel<decltype(veh)>, ro->n * (int64_t)ro->n_plans, kStepBlock, kStepBlock, stream, state_dev(st), a, b,
-                  err_flags, veh);
-  });
+  return launch_rollout_belief(st, ro, belief, err_flags, stream);
+}
+
+// The look-ahead with its leaves handed back as full states: ble_rollout_f32 (noise, or neither wind) or
+// ble_rollout_belief_f32 (belief) with the leaf arena as the kernels' last argument.
+int ble_rollout_leaves_f32(const ble_state_f32* st, const struct ble_rollout_f32* ro, const ble_noise_gen* noise, const ble_gp_belief* belief,
+                           const ble_state_f32* leaves, uint32_t* err_flags, void* stream) {
+  if (noise != nullptr && belief != nullptr) return BLE_E_INVALID_ARG;                  // two winds
+  if (!state_ok(st) || !state_ok(leaves)) return BLE_E_INVALID_ARG;                     // (the leaves' vehicle and episode cache are not read)
+  {
+    const void* const* ps = reinterpret_cast<const void* const*>(st);
+    const void* const* pl = reinterpret_cast<const void* const*>(leaves);
+    for (size_t k = 0; k < offsetof(ble_state_f32, episode_cache) / sizeof(void*); ++k)
+      if (ps[k] == pl[k]) return BLE_E_INVALID_ARG;                                     // a leaf array that IS the source's: st is never written
+  }
+  const StateDev lf = state_dev(leaves);
+  if (belief != nullptr) return launch_rollout_belief(st, ro, belief, err_flags, stream, lf);
+  return launch_rollout(st, ro, noise, err_flags, stream, lf);
 }
 
 // the sizes ble_plan_sample_u8 and ble_plan_select_f32 share
@@ -1974,6 +2005,33 @@ int ble_plan_action_values_f32(const struct ble_plan_action_values* av, void* st
     return BLE_E_INVALID_ARG;
   const PlanActionValuesArgs a{av->n, av->n_plans, av->accumulate, av->ret, av->first_action, av->q, av->q_k, av->visits};
   return launch(ble_plan_action_values_kernel, av->n, 1, kPlanSelectBlock, stream, a);
+}
+
+// ---- a learned terminal value
+int ble_plan_bootstrap_f32(const struct ble_plan_bootstrap* b, void* stream) {
+  if (!b || !b->ret || !b->steps_flown || !b->leaf_status || !b->value || !b->score || b->n < 0 || b->n >= 2147483648LL || b->n_plans < 1 ||
+      b->n_plans > BLE_PLAN_MAX_PLANS || b->n * (int64_t)b->n_plans >= 2147483648LL || !(b->gamma >= 0.0 && b->gamma <= 1.0))
+    return BLE_E_INVALID_ARG;                                         // (a NaN gamma fails both comparisons)
+  const int64_t total = b->n * (int64_t)b->n_plans;
+  const PlanBootstrapArgs a{total, b->gamma, b->ret, b->steps_flown, b->leaf_status, b->value, b->score};
+  return launch(ble_plan_bootstrap_kernel, total, 256, 256, stream, a);
+}
+
+// The observation of imagined states: one workgroup per leaf, the leaf form of ble_observe_kernel -- `append` carries
+// leaves_per_env and `n` the row stride (the note above the kernel).  The ring alone is handed on: the carried factor is never read.
+int ble_observe_leaves_f32(const ble_state_f32* leaves, int32_t leaves_per_env, const float* wind_grid, int64_t grid_env_stride,
+                           const uint8_t* reset_mask, const ble_gp_history_f32* hist, float* obs, int64_t obs_row_stride, uint32_t* err_flags,
+                           int64_t n_leaves, void* stream) {
+  if (!state_ok(leaves) || !wind_grid || !obs || !hist || !hist->xyp || !hist->elapsed_s || !hist->err_uv || !hist->count)
+    return BLE_E_INVALID_ARG;
+  if (leaves_per_env < 1 || n_leaves < 0 || n_leaves >= 2147483648LL || n_leaves % leaves_per_env != 0 || obs_row_stride < BLE_OBS_DIM ||
+      grid_env_stride < 0)
+    return BLE_E_INVALID_ARG;
+  const GpHistory h{hist->xyp, hist->elapsed_s, hist->err_uv, hist->count, nullptr, nullptr, 0};
+  return with_vehicle<false>(leaves, nullptr, [&](auto veh) {
+    return launch(ble_observe_kernel<decltype(veh), false, true>, n_leaves, 1, kObsBlock, stream, state_dev(leaves), wind_grid, grid_env_stride,
+                  (const float*)nullptr, reset_mask, h, (int)leaves_per_env, obs, err_flags, obs_row_stride, veh, (const float*)nullptr);
+  });
 }
 
 int ble_gp_fit_scenarios_f32(const ble_gp_history_f32* hist, const uint8_t* reset_mask, const int32_t* time_s, const ble_gp_scenarios* scn,

@@ -338,21 +338,32 @@ __device__ inline double safe_pressure_search_wave(double lev_l, double sp_l, in
 
 // kLiveOnly (ble_observe_live_f32): an environment whose status is not OK is not observed -- the whole workgroup leaves before it
 // touches the history or the observation row, as the fleet form leaves for an index outside the palette.
-template <class Veh = VehicleDefault, bool kLiveOnly = false>
+//
+// kLeaf (ble_observe_leaves_f32): workgroup j observes leaf j of a leaf arena -- an imagined state -- against the history of
+// its PARENT e = j / leaves_per_env: the state words are read at j; the ring, reset_mask and the grid at e.  The argument list is the
+// other instantiations' (they keep their layout and their instructions), two of its words read differently: `append` carries
+// leaves_per_env (a leaf never appends) and `n` the row stride of obs in floats.  The window is refitted in LDS: chol / n_chol are
+// never read, and NOTHING of hist is written -- the K workgroups of one parent share its ring -- the append block and the two stores at
+// the end are compiled out.  A leaf whose status is not OK gets a row of +0.0f and its workgroup leaves before any barrier, no flag.
+template <class Veh = VehicleDefault, bool kLiveOnly = false, bool kLeaf = false>
 __global__ __launch_bounds__(kObsBlock, 2) void ble_observe_kernel(StateDev st, const float* __restrict__ wind_grid,
                                                                 int64_t grid_env_stride,
                                                                 const float* __restrict__ noise_uv,
                                                                 const uint8_t* __restrict__ reset_mask, GpHistory hist,
-                                                                int append, float* __restrict__ obs,
+                                                                int append_arg, float* __restrict__ obs,
                                                                 uint32_t* err_flags, int64_t n, Veh veh_arg,
                                                                 const float* __restrict__ forecast_levels) {
   __shared__ ObsShared sh;
+  const int append = kLeaf ? 0 : append_arg;
+  if constexpr (kLeaf) { hist.chol = nullptr; hist.n_chol = nullptr; }      // (the refit path, whatever the parent carries)
   BLE_OBS_INSTR_BEGIN();        // (profiling builds only; nothing in the product build)
   BLE_MARK();
   // The phases before the sweep are latency-bound chains on few lanes; the sweep of the other resident workgroup
   // is throughput work.  Priority 1 here, 0 from the sweep on: -3 % per launch (measured).
   __builtin_amdgcn_s_setprio(1);
   const int64_t env = blockIdx.x;
+  // the environment whose history, pending restart and grid this workgroup reads: env itself, or (a leaf) its parent
+  const int64_t henv = kLeaf ? (int64_t)((uint32_t)env / (uint32_t)append_arg) : env;      // (n_leaves < 2^31: the entry point checks)
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);          // scalar: `if (wave == ...)` is a real branch, not an exec mask
   uint32_t flags = 0;
@@ -383,7 +394,13 @@ __global__ __launch_bounds__(kObsBlock, 2) void ble_observe_kernel(StateDev st, 
   const int cmd = st.last_command[env];
   const int paused_bits = (int)st.power_paused[env] | (int)st.env_fsm[env] | (int)st.alt_fsm[env];
   const double x = (double)xf, y = (double)yf, p = (double)pf;
-  float* out = obs + env * kObsDim;
+  float* out = obs + env * (kLeaf ? n : (int64_t)kObsDim);
+  if constexpr (kLeaf) {
+    if (st.status[env] != kOk) {                   // a dead leaf: a row of +0.0f (uniform over the workgroup: no barrier has been reached)
+      for (int q = tid; q < kObsDim; q += kObsBlock) out[q] = 0.0f;
+      return;
+    }
+  }
 
   SunSite site;
   if (wave == 1) {           // BalloonState.latlng once per environment (one wave; the others get it through LDS)
@@ -395,13 +412,13 @@ __global__ __launch_bounds__(kObsBlock, 2) void ble_observe_kernel(StateDev st, 
   }
 
   // ---- phase 0a: history ring
-  int count = hist.count[env];
-  int n_chol0 = hist.chol != nullptr ? hist.n_chol[env] : 0;
-  if (reset_mask != nullptr && reset_mask[env] != 0) { count = 0; n_chol0 = 0; }
+  int count = hist.count[henv];
+  int n_chol0 = hist.chol != nullptr ? hist.n_chol[henv] : 0;
+  if (reset_mask != nullptr && reset_mask[henv] != 0) { count = 0; n_chol0 = 0; }
   const int count0 = count;
   // The stored factor (58 KB of the 61 KB slab) is requested now, 16 B per lane and 15 loads in flight, and lands in
   // LDS after the solar table has been computed: its HBM latency hides behind phase 0b.
-  double* chol_g = hist.chol != nullptr ? hist.chol + env * hist.chol_stride : nullptr;
+  double* chol_g = hist.chol != nullptr ? hist.chol + henv * hist.chol_stride : nullptr;
   const int chol_pairs = (tri(n_chol0 <= kGpMax ? n_chol0 : 0) + 1) >> 1;
   double2 chol_pre[kCholPrefetch];
 #pragma unroll
@@ -415,17 +432,19 @@ __global__ __launch_bounds__(kObsBlock, 2) void ble_observe_kernel(StateDev st, 
   const double zu_pre = (chol_g != nullptr && tid < kGpMax) ? chol_g[kCholTri + kGpMax + tid] : 0.0;          // carried zeta / d
   const double zv_pre = (chol_g != nullptr && tid < kGpMax) ? chol_g[kCholTri + 2 * kGpMax + tid] : 0.0;
   const float err_u = noise_uv ? noise_uv[env * 2] : 0.0f, err_v = noise_uv ? noise_uv[env * 2 + 1] : 0.0f;
-  float* h_xyp = hist.xyp + env * (kGpCapacity * 3);
-  int32_t* h_t = hist.elapsed_s + env * kGpCapacity;
-  float* h_err = hist.err_uv + env * (kGpCapacity * 2);
-  if (append) {
-    if (tid == 0) {
-      const int slot = count % kGpCapacity;
-      h_xyp[slot * 3] = xf; h_xyp[slot * 3 + 1] = yf; h_xyp[slot * 3 + 2] = pf;
-      h_t[slot] = elapsed;
-      h_err[slot * 2] = err_u; h_err[slot * 2 + 1] = err_v;
+  float* h_xyp = hist.xyp + henv * (kGpCapacity * 3);
+  int32_t* h_t = hist.elapsed_s + henv * kGpCapacity;
+  float* h_err = hist.err_uv + henv * (kGpCapacity * 2);
+  if constexpr (!kLeaf) {
+    if (append) {
+      if (tid == 0) {
+        const int slot = count % kGpCapacity;
+        h_xyp[slot * 3] = xf; h_xyp[slot * 3 + 1] = yf; h_xyp[slot * 3 + 2] = pf;
+        h_t[slot] = elapsed;
+        h_err[slot * 2] = err_u; h_err[slot * 2 + 1] = err_v;
+      }
+      count += 1;
     }
-    count += 1;
   }
   const int m = count < kGpCapacity ? count : kGpCapacity;
   bool valid = false;
@@ -477,7 +496,7 @@ __global__ __launch_bounds__(kObsBlock, 2) void ble_observe_kernel(StateDev st, 
     // the float32-packed query like scipy's interpn (the bearing feature is an arccos of this wind: an fp32 blend,
     // 1e-6 m/s off, moved it by up to 2e-4 where the wind points at or away from the station)
     const WindQueryD wq = wind_query_xyt_f64(xf, yf, elapsed);
-    const float* grid = wind_grid + env * grid_env_stride;
+    const float* grid = wind_grid + henv * grid_env_stride;
     const int ip = lane >> 1, comp = lane & 1;
     double acc = 0.0;
 #pragma unroll
@@ -1432,11 +1451,13 @@ __global__ __launch_bounds__(kObsBlock, 2) void ble_observe_kernel(StateDev st, 
     for (int e2 = tid; e2 < pairs; e2 += kObsBlock) reinterpret_cast<double2*>(chol_g)[e2] = reinterpret_cast<const double2*>(sh.L)[e2];
     if (tid == 0) {
       if (words & 1) chol_g[words - 1] = sh.L[words - 1];
-      hist.n_chol[env] = n_obs;
+      if constexpr (!kLeaf) hist.n_chol[env] = n_obs;
     }
   }
   // every lane has read the old count long before this point (barriers above)
-  if (tid == 0) hist.count[env] = count;
+  if constexpr (!kLeaf) {
+    if (tid == 0) hist.count[env] = count;
+  }
   if (err_flags != nullptr && flags != 0) atomicOr(err_flags, flags);
 }
 

@@ -175,7 +175,38 @@ BLE_FN void plan_action_write(uint32_t key, int k, float ret_best, int visits, b
   *n_visits += visits;
 }
 
+// ---- a learned terminal value: ret + gamma^steps_flown * V(leaf)
+// The score of one plan.  The discount is the rollout's own sequence -- 1.0 multiplied steps_flown times by gamma -- hence its `disc`
+// bit for bit; the product and the sum are two statements (two roundings under -ffp-contract=on), rounded to fp32 once.  A leaf that
+// is not OK keeps the plan's return: a select, so its value may hold anything.
+BLE_FN float plan_bootstrap_lane(float ret, int steps_flown, uint8_t leaf_status, float value, double gamma) {
+  double d = 1.0;
+#pragma unroll 1
+  for (int i = 0; i < steps_flown; ++i) d *= gamma;
+  const double t = d * (double)value;
+  const double s = (double)ret + t;
+  return leaf_status == 0 ? (float)s : ret;
+}
+
 #if defined(__HIPCC__)
+// struct ble_plan_bootstrap (include/ble_abi.h) as the kernel takes it; score may be ret (no __restrict__)
+struct PlanBootstrapArgs {
+  int64_t total;                               // n K
+  double gamma;
+  const float* ret;                            // [n][K]
+  const int32_t* __restrict__ steps_flown;     // [n][K]
+  const uint8_t* __restrict__ leaf_status;     // [n K]
+  const float* __restrict__ value;             // [n K]
+  float* score;                                // [n][K]
+};
+
+// One lane per (environment, plan).
+__global__ __launch_bounds__(256) void ble_plan_bootstrap_kernel(PlanBootstrapArgs a) {
+  const int64_t j = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (j >= a.total) return;
+  a.score[j] = plan_bootstrap_lane(a.ret[j], a.steps_flown[j], a.leaf_status[j], a.value[j], a.gamma);
+}
+
 // struct ble_plan_sample (include/ble_abi.h) as the kernel takes it
 struct PlanSampleArgs {
   int64_t n, env_offset;

@@ -16,6 +16,12 @@
 // ble_step_helper_kernel's, on purpose: sharing the load code changes the register allocation of the existing instantiations (the note
 // above ble_step_helper_kernel).
 //
+// kLeaves (ble_rollout_leaves_f32): the lane also hands back the WHOLE state it ends with -- the EnvRegs after its last
+// executed step, the raw action of that step as last_command, the five per-episode constants -- into index j of a second state, the leaf
+// arena, after the loop and coalesced in j (leaf_store below).  A lane that flew nothing (a non-OK source) copies the source's words.
+// The leaf arena is the kernels' LAST argument, a parameter pack that holds one StateDev with leaves and nothing without: the
+// instantiations without leaves keep their argument list, their kernel descriptor and their instructions (profiles/isa_compare.py).
+//
 // Included by ble_kernels.hip after ble_step_kernel: kStepBlock, StepNoiseShared and report_flags are that file's.
 #pragma once
 #include "ble_noise.h"
@@ -37,8 +43,44 @@ struct RolloutArgs {
   float* __restrict__ final_state;            // optional [4][n][n_plans]
 };
 
-template <bool kNoise, class V = VehicleDefault>
-__global__ __launch_bounds__(kStepBlock) void ble_rollout_kernel(StateDev st, RolloutArgs a, uint32_t* err_flags, StepNoise gen, V veh) {
+template <bool kLeaves> struct LeafLast {};
+template <> struct LeafLast<true> { int act = 0; };
+
+// Lane j's leaf: every array ble_step_kernel's write-back stores, and the per-episode constants.  flew: the lane executed a step (its
+// source was OK) -- s and last_act are what it holds; otherwise the source's own words at e.  Never the episode cache.
+__device__ __forceinline__ void leaf_store(const StateDev& st, const StateDev& lf, int64_t e, int64_t j, bool flew, const EnvRegs& s,
+                                           const EnvConst& c, int last_act) {
+  if (flew) {
+    lf.x[j] = s.x; lf.y[j] = s.y; lf.pressure[j] = s.p; lf.ambient_temperature[j] = s.t_amb;
+    lf.internal_temperature[j] = s.t_int; lf.envelope_volume[j] = s.vol; lf.superpressure[j] = s.sp;
+    lf.mols_air[j] = s.n_air; lf.battery_charge[j] = s.batt;
+    lf.acs_power[j] = s.acs_power; lf.acs_mass_flow[j] = s.mdot; lf.solar_charging[j] = s.charge;
+    lf.power_load[j] = s.load;
+    lf.time_elapsed_s[j] = s.t_elapsed; lf.sunrise_h_rel[j] = s.sunrise_h; lf.sunset_rel[j] = s.sunset;
+    lf.status[j] = s.status; lf.last_command[j] = (uint8_t)last_act;
+    lf.alt_fsm[j] = s.alt_fsm; lf.env_fsm[j] = s.env_fsm; lf.power_paused[j] = s.paused;
+  } else {
+    lf.x[j] = st.x[e]; lf.y[j] = st.y[e]; lf.pressure[j] = st.pressure[e]; lf.ambient_temperature[j] = st.ambient_temperature[e];
+    lf.internal_temperature[j] = st.internal_temperature[e]; lf.envelope_volume[j] = st.envelope_volume[e];
+    lf.superpressure[j] = st.superpressure[e]; lf.mols_air[j] = st.mols_air[e]; lf.battery_charge[j] = st.battery_charge[e];
+    lf.acs_power[j] = st.acs_power[e]; lf.acs_mass_flow[j] = st.acs_mass_flow[e]; lf.solar_charging[j] = st.solar_charging[e];
+    lf.power_load[j] = st.power_load[e];
+    lf.time_elapsed_s[j] = st.time_elapsed_s[e]; lf.sunrise_h_rel[j] = st.sunrise_h_rel[e]; lf.sunset_rel[j] = st.sunset_rel[e];
+    lf.status[j] = st.status[e]; lf.last_command[j] = st.last_command[e];
+    lf.alt_fsm[j] = st.alt_fsm[e]; lf.env_fsm[j] = st.env_fsm[e]; lf.power_paused[j] = st.power_paused[e];
+  }
+  // (the constants' members are pointers to const: a state is read-only there for every other kernel)
+  const_cast<float*>(lf.center_lat_deg)[j] = c.lat0_deg; const_cast<float*>(lf.center_lng_deg)[j] = c.lng0_deg;
+  const_cast<float*>(lf.upwelling_infrared)[j] = c.ir; const_cast<float*>(lf.alpha)[j] = c.alpha;
+  const_cast<int64_t*>(lf.start_unix)[j] = c.start_unix;
+}
+// the one element of the kernels' trailing pack
+__device__ __forceinline__ const StateDev& leaf_arena(const StateDev& lf) { return lf; }
+
+template <bool kNoise, class V = VehicleDefault, bool kLeaves = false, class... Leaf>
+__global__ __launch_bounds__(kStepBlock) void ble_rollout_kernel(StateDev st, RolloutArgs a, uint32_t* err_flags, StepNoise gen, V veh,
+                                                                 Leaf... leaves) {
+  static_assert(sizeof...(Leaf) == (kLeaves ? 1 : 0), "with leaves: the leaf arena's StateDev; without: nothing");
   double* acs_poly; float* term_save; float* grad_lut = nullptr; uint32_t* noise_draws = nullptr;
   if constexpr (kNoise) {
     __shared__ StepNoiseShared shm;
@@ -90,6 +132,7 @@ __global__ __launch_bounds__(kStepBlock) void ble_rollout_kernel(StateDev st, Ro
   // the discounted return: fp64, the product and the sum as two statements (two roundings under -ffp-contract=on), rounded to fp32 once
   double acc = 0.0, disc = 1.0;
   int flown = 0;
+  LeafLast<kLeaves> last;                       // (with leaves: the raw action of the last step flown)
   int64_t o = j;                                // (agent step t) * n K + j
 #pragma unroll 1
   for (int h = 0; h < a.n_plan_steps; ++h) {
@@ -98,6 +141,7 @@ __global__ __launch_bounds__(kStepBlock) void ble_rollout_kernel(StateDev st, Ro
     for (int rep = 0; rep < a.action_repeat; ++rep, o += lanes_total) {
       if (live) {
         ++flown;
+        if constexpr (kLeaves) last.act = act;
         const WindQuery wq = wind_query(s.x, s.y, s.p, s.t_elapsed);
         WindCorners corners;
         wind_gather(grid, wq, &corners);
@@ -128,6 +172,7 @@ __global__ __launch_bounds__(kStepBlock) void ble_rollout_kernel(StateDev st, Ro
       a.final_state[j] = s.x; a.final_state[lanes_total + j] = s.y; a.final_state[2 * lanes_total + j] = s.p;
       a.final_state[3 * lanes_total + j] = s.batt;
     }
+    if constexpr (kLeaves) leaf_store(st, leaf_arena(leaves...), e, j, flown > 0, s, c, last.act);      // (flown > 0: the source was OK)
   }
   report_flags(flags, err_flags);
 }

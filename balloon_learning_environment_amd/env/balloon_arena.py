@@ -187,14 +187,15 @@ class VecBalloonArena:
     return self.sim.query_wind(xyp, time_s, add_forecast, out)
 
   def lookahead(self, plans: torch.Tensor, gamma: float = 1.0, action_repeat: int = 1, noise_seed: Optional[int] = None,
-                want_rewards: bool = False, want_final: bool = False, out=None, scenarios=None, belief=None):
+                want_rewards: bool = False, want_final: bool = False, out=None, scenarios=None, leaves=None, belief=None):
     """K action plans per env flown from the current state without changing it: plans uint8 [H, N, K] -> Rollout(returns [N, K],
     steps_flown [N, K], rewards or None, final or None); VecSimulator.rollout_plans.  noise_seed: None = the forecast; this arena's
     `_seed` = the ground-truth wind its environments fly in when stepped with sim.wind_noise(_seed).  belief: a WindBelief
     (fit_wind_belief) = forecast + the WindGP's mean.  scenarios: a WindScenarios (fit_wind_scenarios) = forecast + each of M sampled
-    winds; the outputs are then [N, K, M]."""
+    winds; the outputs are then [N, K, M].  leaves: a leaf arena (sim.leaf_arena(K)) that receives every plan's end state as a full
+    state (Rollout.leaves; not with scenarios)."""
     return self.sim.rollout_plans(plans, gamma, action_repeat, noise_seed, want_rewards=want_rewards, want_final=want_final, out=out,
-                                  belief=belief, scenarios=scenarios)
+                                  belief=belief, scenarios=scenarios, leaves=leaves)
 
   def fit_wind_belief(self, time_s: Optional[torch.Tensor] = None, out=None):
     """Every env's WindGP fitted once and kept on the device: WindBelief(slab, n_obs); VecSimulator.fit_wind_belief."""

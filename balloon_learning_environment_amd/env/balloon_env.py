@@ -219,7 +219,7 @@ class VecBalloonEnv:
     return self.arena.sim.query_wind(xyp, time_s, add_forecast, out)
 
   def lookahead(self, plans, gamma: float = 0.993, action_repeat: int = 1, wind: str = 'truth', want_rewards: bool = False,
-                want_final: bool = False, out=None, num_scenarios: int = 8, risk_tail: Optional[int] = None):
+                want_final: bool = False, out=None, num_scenarios: int = 8, risk_tail: Optional[int] = None, want_leaves: bool = False):
     """"From where each balloon is now, what happens under these K action sequences?": plans uint8 device tensor [H, N, K] ->
     Rollout(returns [N, K], steps_flown [N, K], rewards or None, final or None), nothing of the environments changed
     (VecSimulator.rollout_plans; no auto-reset inside a plan: a plan that goes terminal stops there).
@@ -233,9 +233,20 @@ class VecBalloonEnv:
     (arena.fit_wind_scenarios), flown (rollout_plans(scenarios=)) and scored (arena.plan_risk).  Returns (Rollout with returns
     [N, K, M], steps_flown [N, K, M], ..., score [N, K]): score is the mean of the risk_tail smallest scenario returns of every plan
     (None: all M, the expectation; 1: the worst case).
+    want_leaves: every plan's end state as a full state, Rollout.leaves: a VecSimulator of N K environments (environment e K + k is
+    plan k of environment e; kept and reused per K), which arena.sim.observe_leaves() observes against these environments' histories.
+    Not with wind='scenarios' (ValueError).
     Flags of the imagined flights go to arena.sim.rollout_flags, never to check_errors()."""
     if wind not in ('truth', 'forecast', 'belief', 'scenarios'):
       raise ValueError(f"lookahead: wind is 'truth', 'forecast', 'belief' or 'scenarios', not {wind!r}")
+    leaves = None
+    if want_leaves:
+      if wind == 'scenarios':
+        raise ValueError("lookahead: wind='scenarios' hands back no leaves (M end states per plan)")
+      k = int(plans.shape[2])
+      if getattr(self, '_leaf_arena', None) is None or self._leaf_arena.leaves_per_env != k:
+        self._leaf_arena = self.arena.sim.leaf_arena(k)
+      leaves = self._leaf_arena
     if wind == 'scenarios':
       reuse = self._scenarios if (self._scenarios is not None and self._scenarios.num == int(num_scenarios)) else None
       self._scenarios = self.arena.fit_wind_scenarios(num_scenarios, seed=self.arena._seed, out=reuse)
@@ -243,13 +254,14 @@ class VecBalloonEnv:
       return ro, self.arena.plan_risk(ro.returns, risk_tail)
     if wind == 'belief':
       self._belief = self.arena.fit_wind_belief(out=self._belief)
-      return self.arena.lookahead(plans, gamma, action_repeat, None, want_rewards, want_final, out, belief=self._belief)
+      return self.arena.lookahead(plans, gamma, action_repeat, None, want_rewards, want_final, out, belief=self._belief, leaves=leaves)
     noise_seed = self.arena._seed if (wind == 'truth' and self._wind_noise) else None
-    return self.arena.lookahead(plans, gamma, action_repeat, noise_seed, want_rewards, want_final, out)
+    return self.arena.lookahead(plans, gamma, action_repeat, noise_seed, want_rewards, want_final, out, leaves=leaves)
 
   def planner(self, **kw):
     """A look-ahead agent bound to these environments: agents.lookahead_agent.VecLookaheadAgent(**kw) -- num_plans, horizon,
-    action_repeat, segment, gamma, wind ('belief' by default; 'scenarios' with num_scenarios, risk_tail), iterations, elite, seed -- planning in this batch's simulator.
+    action_repeat, segment, gamma, wind ('belief' by default; 'scenarios' with num_scenarios, risk_tail), iterations, elite, seed,
+    leaf_value (a critic whose value of every plan's end state is added to its return) -- planning in this batch's simulator.
     wind='truth' flies the plans in the wind these environments fly, this env's wind noise included (with wind_noise=False the truth
     is the forecast).  actions = agent.act(obs); obs, reward, terminal = env.step(actions): no host synchronisation in either."""
     from balloon_learning_environment_amd.agents import lookahead_agent

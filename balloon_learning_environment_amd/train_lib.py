@@ -285,6 +285,9 @@ def run_exit_loop_vec(env, trainer, planner, buffer, *, num_iterations: int, bet
   action flown is the planner's with probability beta_i, else the learner's (trainer.mix, the DAgger mixture); env.step; the block
   stores the observation acted on, the planner's per-action values and its best return there (buffer.add(t, obs, q, best_return)).
   beta: a float or a function of the iteration index.  The episode limit is run_training_loop_vec's.
+  With a bootstrapped planner (VecLookaheadAgent(leaf_value=)) nothing here changes, but the stored best return -- the
+  value target under value_coef -- is then an H-step BOOTSTRAPPED return, sum_{t<H} gamma^t r_t + gamma^H V(s_H), and so are the
+  per-action values; with leaf_value=trainer the target moves with the learner's own value column.
 
   After the T steps `epochs` passes of minibatches of batch_size rows follow, each one soft update (epochs x (T N // batch_size) in
   all); then the block is discarded.

@@ -21,7 +21,16 @@ COUNT_SLOTS = 64                 # BLE_COUNT_SLOTS in include/ble_abi.h
 
 
 # what rollout_plans returns: device tensors [n, K], [n, K], [H * action_repeat, n, K] or None, [4, n, K] or None
-Rollout = collections.namedtuple('Rollout', ('returns', 'steps_flown', 'rewards', 'final'))
+class Rollout(collections.namedtuple('Rollout', ('returns', 'steps_flown', 'rewards', 'final'))):
+  """The four tensors, by position as they always were, and `leaves`: the leaf arena (a VecSimulator of n K environments, leaf_arena)
+  the plans' end states were written into, or None.  leaves is reached by name only -- callers iterate over a Rollout's tensors."""
+
+  def __new__(cls, returns, steps_flown, rewards=None, final=None, leaves=None):
+    self = super().__new__(cls, returns, steps_flown, rewards, final)
+    self.leaves = leaves
+    return self
+
+
 # what fit_wind_belief returns: the fitted WindGP of every environment, device tensors slab [n, 720] float64 (the library's own layout)
 # and n_obs [n] int32 (observations in the window; 0: no posterior, -1: a window the ring could not tell -- the belief's wind is NaN)
 WindBelief = collections.namedtuple('WindBelief', ('slab', 'n_obs'))
@@ -688,7 +697,8 @@ class VecSimulator:
   @_on_own_device
   def rollout_plans(self, plans: torch.Tensor, gamma: float = 1.0, action_repeat: int = 1, noise_seed: Optional[int] = None,
                     substeps: int = SUBSTEPS, want_rewards: bool = False, want_final: bool = False, out: Optional[tuple] = None,
-                    scenarios: Optional[WindScenarios] = None, belief: Optional[WindBelief] = None) -> 'Rollout':
+                    scenarios: Optional[WindScenarios] = None, leaves: Optional['VecSimulator'] = None,
+                    belief: Optional[WindBelief] = None) -> 'Rollout':
     """Look ahead: flies K action plans per environment from the state where it lies, WITHOUT changing it (`ble_rollout_f32`).
     `plans`: uint8 device tensor [H, n, K], contiguous -- entry h of plan k of environment e is flown action_repeat agent steps.  Returns
     Rollout(returns [n, K] f32, steps_flown [n, K] i32, rewards [H * action_repeat, n, K] f32 or None, final [4, n, K] f32 or None):
@@ -703,6 +713,10 @@ class VecSimulator:
     scenarios: a WindScenarios (fit_wind_scenarios): every plan is flown in each of its M scenario winds (`ble_rollout_scenarios_f32`),
     and the outputs get one axis more: returns [n, K, M], steps_flown [n, K, M], rewards [H * action_repeat, n, K, M], final
     [4, n, K, M]; per step, bit for bit scenario_wind at the plan's state + step(noise_uv=that).  Not together with noise_seed or belief.
+    leaves: a leaf arena (leaf_arena(K)): every plan's end state is written into it as a full state (`ble_rollout_leaves_f32`) --
+    environment e K + k of the arena is what a copy of environment e holds after flying plan k: its state, the raw action of the last
+    step flown as last_command, the status it ended with, the per-episode constants; an environment that is not OK now is copied as
+    it is.  Everything else is written exactly as without leaves.  Not with scenarios (ValueError).  Returned as Rollout.leaves.
     out: a Rollout (or tuple) of tensors to write into, None where an output is not wanted.
     Nothing of the simulator is written: state, last_command, episode counters, both caches and the WindGP history stay as they are.
     Error flags go to a word of their own, `rollout_flags` (int32 device tensor, OR-ed into, never cleared here), NOT to err_flags: a
@@ -714,6 +728,8 @@ class VecSimulator:
       raise ValueError('rollout_plans: belief and noise_seed are two winds; give one of them')
     if scenarios is not None and (belief is not None or noise_seed is not None):
       raise ValueError('rollout_plans: scenarios, belief and noise_seed are three winds; give one of them')
+    if leaves is not None and scenarios is not None:
+      raise ValueError('rollout_plans: scenario winds hand back no leaves (M end states per plan); fly the belief or the forecast')
     assert self.grid is not None, 'Must call set_grid (reset) before rollout_plans.'
     assert plans.dtype == torch.uint8 and plans.is_contiguous() and plans.dim() == 3 and plans.shape[1] == self.n, plans.shape
     assert plans.device == self.device
@@ -731,7 +747,7 @@ class VecSimulator:
       out = (torch.empty(*lanes, dtype=torch.float32, device=self.device), torch.empty(*lanes, dtype=torch.int32, device=self.device),
              torch.empty(steps, *lanes, dtype=torch.float32, device=self.device) if want_rewards else None,
              torch.empty(4, *lanes, dtype=torch.float32, device=self.device) if want_final else None)
-    returns, flown, rewards, final = out
+    returns, flown, rewards, final = tuple(out)[:4]
     for t, dtype, shape in ((returns, torch.float32, lanes), (flown, torch.int32, lanes), (rewards, torch.float32, (steps,) + lanes),
                             (final, torch.float32, (4,) + lanes)):
       assert t is None or (t.dtype == dtype and t.is_contiguous() and tuple(t.shape) == shape and t.device == self.device), (shape, t)
@@ -740,6 +756,13 @@ class VecSimulator:
     gen = None if noise_seed is None else _abi.BleNoiseGen(int(noise_seed) & (2 ** 64 - 1), self.episode.data_ptr(), None, self.env_offset)
     ro = _abi.BleRolloutF32(self.n, k, h, int(action_repeat), int(substeps), float(gamma), plans.data_ptr(), self.grid.data_ptr(),
                             self.grid_env_stride, returns.data_ptr(), flown.data_ptr(), dev.ptr(rewards), dev.ptr(final))
+    if leaves is not None:
+      self._check_leaf_arena(leaves, k)
+      b = None if belief is None else self._belief_struct(belief)
+      _lib.check(self.lib.ble_rollout_leaves_f32(ctypes.byref(self._struct), ctypes.byref(ro), None if gen is None else ctypes.byref(gen),
+                                                 None if b is None else ctypes.byref(b), ctypes.byref(leaves._struct),
+                                                 self.rollout_flags.data_ptr(), dev.stream_ptr(self.device)), 'ble_rollout_leaves_f32')
+      return Rollout(returns, flown, rewards, final, leaves)
     if scenarios is not None:
       b, sgen = self._scenario_structs(scenarios)
       _lib.check(self.lib.ble_rollout_scenarios_f32(ctypes.byref(self._struct), ctypes.byref(ro), ctypes.byref(b), ctypes.byref(sgen),
@@ -753,6 +776,54 @@ class VecSimulator:
     _lib.check(self.lib.ble_rollout_f32(ctypes.byref(self._struct), ctypes.byref(ro), None if gen is None else ctypes.byref(gen),
                                         self.rollout_flags.data_ptr(), dev.stream_ptr(self.device)), 'ble_rollout_f32')
     return Rollout(returns, flown, rewards, final)
+
+  # ------------------------------------------------------------------ imagined states
+  def leaf_arena(self, num_plans: int) -> 'VecSimulator':
+    """A VecSimulator of n * num_plans environments for the end states of rollout_plans(leaves=): environment e K + k is plan k of this
+    simulator's environment e.  It flies this simulator's vehicle and, where the grid is shared, reads this simulator's grid tensor, so
+    it is a simulator like any other: it can be stepped, observed, looked ahead from.  With per-environment grids it gets no grid of
+    its own (leaf j would need the grid of environment j // K): observe_leaves reads the parent's.  No WindGP history is allocated
+    until someone calls observe() on the arena itself.  About 120 B of state per leaf, plus 104 B of per-episode cache."""
+    k = int(num_plans)
+    if k < 1 or self.n * k >= 2 ** 31:
+      raise ValueError(f'leaf_arena: num_plans >= 1 and n * num_plans < 2^31, not {self.n} x {k}')
+    if self.has_fleet:
+      raise ValueError('leaf_arena: a fleet (set_fleet) has no look-ahead kernel')
+    arena = VecSimulator(self.n * k, self.device)
+    arena.set_vehicle(**self.vehicle)
+    if self.grid is not None and self.grid_env_stride == 0:
+      arena.grid, arena.grid_env_stride = self.grid, 0
+    arena.leaf_parent, arena.leaves_per_env = self, k
+    return arena
+
+  def _check_leaf_arena(self, arena: 'VecSimulator', k: int) -> None:
+    if getattr(arena, 'leaf_parent', None) is not self or arena.leaves_per_env != k or arena.n != self.n * k:
+      raise ValueError(f'not a leaf arena of this simulator for {k} plans per environment (leaf_arena({k}))')
+    if arena.vehicle != self.vehicle:           # the parent's vehicle changed since: the leaves fly what their parents fly
+      arena.set_vehicle(**self.vehicle)
+    if self.grid_env_stride == 0 and arena.grid is not self.grid:
+      arena.grid, arena.grid_env_stride = self.grid, 0
+
+  @_on_own_device
+  def observe_leaves(self, arena: 'VecSimulator', out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The observation of every imagined state of a leaf arena: [n * K, 1099] float32 (`ble_observe_leaves_f32`).  Leaf e K + k is
+    observed against THIS simulator's history of environment e, its pending history restart and its grid: what get_features() gives
+    a balloon that arrived at the leaf's state at the leaf's time having measured nothing on the way.  Nothing is appended, nothing
+    of the history -- ring, carried factor, counts -- is written; on a live leaf the row is bit for bit what observe(append=False,
+    carry_factor=False) gives a simulator in the leaf's state with the parent's ring.  A leaf that is not OK gets a row of zeros.
+    Flags go to rollout_flags, never err_flags: an imagined state must not make check_errors() raise.  Asynchronous on the current
+    stream, no host synchronisation (capturable in a HIP graph)."""
+    assert self.grid is not None, 'Must call set_grid (reset) before observe_leaves.'
+    k = int(getattr(arena, 'leaves_per_env', 0))
+    self._check_leaf_arena(arena, k)
+    if out is None:
+      out = torch.empty(arena.n, _lib.OBS_DIM, dtype=torch.float32, device=self.device)
+    assert out.dtype == torch.float32 and out.is_contiguous() and tuple(out.shape) == (arena.n, _lib.OBS_DIM) and out.device == self.device
+    hist, reset_mask = self._history_for_reading()
+    _lib.check(self.lib.ble_observe_leaves_f32(ctypes.byref(arena._struct), k, self.grid.data_ptr(), self.grid_env_stride, reset_mask,
+                                               ctypes.byref(hist), out.data_ptr(), _lib.OBS_DIM, self.rollout_flags.data_ptr(), arena.n,
+                                               dev.stream_ptr(self.device)), 'ble_observe_leaves_f32')
+    return out
 
   @property
   def active_count(self) -> torch.Tensor:

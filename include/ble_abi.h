@@ -1379,6 +1379,64 @@ struct ble_plan_action_values {
 };
 int ble_plan_action_values_f32(const struct ble_plan_action_values* av, void* stream);
 
+/*
+ * A learned terminal value: the look-ahead hands its leaves back as full states, the observation kernel observes them
+ * against the parent's history, and a critic's value of every leaf is added to the plan's return.  Added without a new ABI version.
+ *
+ * ble_rollout_leaves_f32: ble_rollout_f32 (noise, or neither wind: the forecast) or ble_rollout_belief_f32 (belief) -- never both winds
+ * -- writing ret, steps_flown, reward and final_state exactly as those calls do, bit for bit, and in addition every lane's end state
+ * into `leaves`, an ordinary ble_state_f32 whose arrays hold n * n_plans environments.  Lane j = e * n_plans + k stores into index j
+ * the state it holds after its last executed step: every array ble_step_f32 writes back (x .. power_load, time_elapsed_s,
+ * sunrise_h_rel, sunset_rel, status, last_command, alt_fsm, env_fsm, power_paused), last_command being the RAW action of the last step
+ * flown and status the lane's own (terminal if the plan went terminal), and the five per-episode constants center_lat_deg,
+ * center_lng_deg, upwelling_infrared, alpha and start_unix.  A lane that flew nothing (a source that is not OK) stores the source's own
+ * values, last_command included.  A leaf arena is therefore a valid state for every entry point.  leaves->vehicle is not read;
+ * leaves->episode_cache is neither read nor written and may be NULL.  st is never written.  Scenarios and fleets have no such form.
+ * BLE_E_INVALID_ARG before any HIP call: everything the underlying call refuses; both noise and belief given; a NULL leaves or leaf
+ * array; a leaf array that is the same array of st.  n == 0: BLE_OK without a launch.
+ */
+int ble_rollout_leaves_f32(const ble_state_f32* st, const struct ble_rollout_f32* ro, const ble_noise_gen* noise,
+                           const ble_gp_belief* belief, const ble_state_f32* leaves, uint32_t* err_flags, void* stream);
+
+/*
+ * ble_observe_leaves_f32: the 1099 features of n_leaves imagined states, one workgroup per leaf j.  The state words are read at index
+ * j of `leaves`; the history ring, reset_mask and the grid (wind_grid + e * grid_env_stride) belong to the parent e = j /
+ * leaves_per_env.  The semantics are get_features() of a balloon that arrived at the leaf's state at the leaf's time having measured
+ * nothing on the way: the window is |t_i - t_leaf| < 6 h over the parent's ring, a pending reset_mask[e] gives an empty history, nothing
+ * is appended and the window is refitted -- hist->chol and hist->n_chol are never read, and NOTHING of hist is written.  On a live
+ * leaf the row equals ble_observe_f32(append = 0) without a carried factor on the same state and ring, bit for bit.  A leaf whose
+ * status is not OK gets +0.0f in all 1099 entries and sets no flag.  Row j of obs starts at obs + j * obs_row_stride.  The vehicle is
+ * leaves->vehicle (NULL: the default); there is no fleet form and no forecast_levels.
+ * BLE_E_INVALID_ARG before any HIP call: NULL leaves, leaf array, hist, ring pointer (xyp, elapsed_s, err_uv, count), wind_grid or obs;
+ * leaves_per_env < 1; n_leaves < 0, >= 2^31 or not a multiple of leaves_per_env; obs_row_stride < BLE_OBS_DIM; grid_env_stride < 0.
+ * n_leaves == 0: BLE_OK without a launch.
+ */
+int ble_observe_leaves_f32(const ble_state_f32* leaves, int32_t leaves_per_env, const float* wind_grid, int64_t grid_env_stride,
+                           const uint8_t* reset_mask, const ble_gp_history_f32* hist, float* obs, int64_t obs_row_stride,
+                           uint32_t* err_flags, int64_t n_leaves, void* stream);
+
+/*
+ * ble_plan_bootstrap_f32: one lane per (e, k):
+ *     d = 1.0; repeat steps_flown times: d *= gamma     (the rollout's own sequence: its discount after steps_flown steps, bit for bit)
+ *     t = d * (double)value;   s = (double)ret + t      (two roundings)
+ *     score = leaf_status == 0 ? (float)s : ret         (a select: a dead leaf's value is never looked at)
+ * A non-finite value on a live leaf gives a non-finite score, which ble_plan_select_f32 orders last.  score may alias ret.
+ * BLE_E_INVALID_ARG before any HIP call: NULL b or array; n < 0 or >= 2^31; n_plans outside 1 .. BLE_PLAN_MAX_PLANS; n * n_plans >=
+ * 2^31; gamma not in [0, 1] (NaN included).  n == 0: BLE_OK without a launch.
+ */
+struct ble_plan_bootstrap {
+  int64_t n;
+  int32_t n_plans;                           /* K */
+  int32_t reserved_;
+  double gamma;
+  const float* ret;                          /* device [n][K] */
+  const int32_t* steps_flown;                /* device [n][K] */
+  const uint8_t* leaf_status;                /* device [n * K]: the leaf arena's status */
+  const float* value;                        /* device [n * K]: V(leaf) */
+  float* score;                              /* device [n][K] out; may be ret */
+};
+int ble_plan_bootstrap_f32(const struct ble_plan_bootstrap* b, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -7,7 +7,9 @@ every kernel's body is cut out of the two .s files by its symbol, and the bodies
 line by line (comments and blank lines dropped; the function's ordinal in its local labels, .LBB<ordinal>_<block>, is dropped too: it
 counts the functions emitted before this one, so a kernel added to the file renumbers the labels of every later one without changing
 an instruction).  Prints one line per kernel and exits 1 if any common kernel differs.  Kernels present
-on one side only are listed, not compared."""
+on one side only are listed, not compared -- except those a new trailing template parameter renamed: a kernel of REV whose demangled
+name equals a kernel's of the tree once that one's trailing `false` template arguments (and the empty parameter pack behind them)
+are dropped is compared with it, body against body (the lines that carry the symbol itself aside), and reported as `renamed`."""
 import os
 import re
 import subprocess
@@ -40,6 +42,15 @@ def kernels(asm: str) -> dict:
   return out
 
 
+def demangle(names):
+  return subprocess.run(['c++filt'], input='\n'.join(names), capture_output=True, text=True, check=True).stdout.splitlines() if names else []
+
+
+def short_name(demangled: str) -> str:
+  """The kernel's name with its template arguments, without its parameter list."""
+  return re.sub(r'^void ', '', demangled.split('(')[0])
+
+
 def main() -> int:
   rev = sys.argv[1] if len(sys.argv) > 1 else 'HEAD'
   with tempfile.TemporaryDirectory() as tmp:
@@ -54,9 +65,25 @@ def main() -> int:
     same = a[name] == b[name]
     differ += not same
     print(f'{"identical" if same else "DIFFERS  "} {len(a[name]):6d} / {len(b[name]):6d} lines  {name}')
-  for name in sorted(set(a) ^ set(b)):
-    print(f'only in {"the tree" if name in b else rev}: {name}')
-  print(f'{len(set(a) & set(b)) - differ} of {len(set(a) & set(b))} common kernels identical')
+  only_a, only_b = sorted(set(a) - set(b)), sorted(set(b) - set(a))
+  old_name = {short_name(d): n for n, d in zip(only_a, demangle(only_a))}
+  renamed = 0
+  for name, d in zip(only_b, demangle(only_b)):
+    d = short_name(d)
+    while d not in old_name and re.search(r', false>', d):
+      d = re.sub(r', false>', '>', d, count=1)
+    if d in old_name:
+      old = old_name.pop(d)
+      strip = lambda lines, sym: [l for l in lines if sym not in l]
+      same = strip(a[old], old) == strip(b[name], name)
+      differ += not same
+      renamed += 1
+      print(f'{"identical" if same else "DIFFERS  "} {len(a[old]):6d} / {len(b[name]):6d} lines  renamed: {d}')
+    else:
+      print(f'only in the tree: {name}')
+  for name in old_name.values():
+    print(f'only in {rev}: {name}')
+  print(f'{len(set(a) & set(b)) + renamed - differ} of {len(set(a) & set(b))} common and {renamed} renamed kernels identical')
   return 1 if differ else 0
 
 
