@@ -333,3 +333,22 @@ class BleDaggerMixF32(ctypes.Structure):
   _fields_ = [('n', ctypes.c_int64), ('beta', ctypes.c_float), ('reserved_', ctypes.c_int32), ('seed', ctypes.c_uint64),
               ('env_offset', ctypes.c_int64), ('step', ctypes.c_void_p), ('learner', ctypes.c_void_p), ('expert', ctypes.c_void_p),
               ('action', ctypes.c_void_p), ('took_expert', ctypes.c_void_p)]
+
+
+POP_HEAD_Q, POP_HEAD_ACTOR_GREEDY = 0, 1             # BLE_POP_HEAD_*
+
+
+class BleQnetGroupedF32(ctypes.Structure):
+  """struct ble_qnet_grouped_f32: P networks of one shape over P * R rows, rows [p R, (p + 1) R) through image p (device pointers)."""
+  _fields_ = [('net', BleQnetF32), ('members', ctypes.c_int32), ('head', ctypes.c_int32), ('member_stride', ctypes.c_int64),
+              ('rows_per_member', ctypes.c_int64), ('obs_row_stride', ctypes.c_int64), ('obs', ctypes.c_void_p),
+              ('scratch', ctypes.c_void_p), ('action', ctypes.c_void_p), ('q_values', ctypes.c_void_p), ('value', ctypes.c_void_p),
+              ('probs', ctypes.c_void_p)]
+
+
+class BleEsF32(ctypes.Structure):
+  """struct ble_es_f32: an evolution strategy's centre image (net.weights), its population of images, sigma, weight decay, the seed and
+  the device generation counter."""
+  _fields_ = [('net', BleQnetF32), ('members', ctypes.c_int32), ('antithetic', ctypes.c_int32), ('member_stride', ctypes.c_int64),
+              ('population', ctypes.c_void_p), ('sigma', ctypes.c_float), ('weight_decay', ctypes.c_float), ('seed', ctypes.c_uint64),
+              ('generation', ctypes.c_void_p)]

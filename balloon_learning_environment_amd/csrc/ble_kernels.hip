@@ -44,6 +44,7 @@
 #include "ble_actor.h"
 #include "ble_imitate.h"
 #include "ble_replay.h"
+#include "ble_population.h"
 
 using namespace ble;
 
@@ -1750,6 +1751,107 @@ int ble_ac_act_f32(const ble_qnet_f32* net, const ble_ac_rows_f32* rows, float* 
   return launch(ble_ac_head_kernel, n, kQnetHeadBlock, kQnetHeadBlock, stream, (const float*)(scratch + ((s.layers - 1) & 1) * n * ld), ld,
                 (uint64_t)(sample ? sample->seed : 0), (int64_t)(sample ? sample->env_offset : 0),
                 (const unsigned long long*)(sample ? sample->step : nullptr), rows->action, rows->logp, rows->value, rows->probs, n);
+}
+
+// ---------------------------------------------------------------------------------------------------------------- populations
+namespace {
+// the stride between the images of a population: room for one image, every image 256-byte aligned when image 0 is
+bool member_stride_ok(const QnetShape& s, int64_t member_stride) { return member_stride >= s.offset[s.layers] && member_stride % 64 == 0; }
+
+// launch_dense_stack for a population: P members of R rows each, member p on the image w + p member_stride; two buffers in turn.
+int launch_dense_stack_grouped(const QnetShape& s, const float* w, int64_t member_stride, const float* x, int64_t ldx, int64_t members,
+                               int64_t rows_per_member, float* base, void* stream) {
+  const int64_t n = members * rows_per_member;
+  const int64_t tiles_per_member = (rows_per_member + kQnetRows - 1) / kQnetRows;
+  for (int l = 0; l < s.layers; ++l) {
+    const int groups = s.mp[l] / kQnetCols;
+    const bool first = l == 0, last = l == s.layers - 1;
+    const auto dense = first ? (last ? ble_qnet_dense_grouped_kernel<true, false> : ble_qnet_dense_grouped_kernel<true, true>)
+                             : (last ? ble_qnet_dense_grouped_kernel<false, false> : ble_qnet_dense_grouped_kernel<false, true>);
+    float* y = base + (l & 1) * n * s.ld;
+    const int status = launch_grid(dense, dim3((unsigned)(groups * tiles_per_member * members)), kQnetBlock, stream, x, ldx, s.k[l], s.kp[l],
+                                   w + s.offset[l], member_stride, y, s.ld, groups, rows_per_member, tiles_per_member);
+    if (status != BLE_OK) return status;
+    x = y;
+    ldx = s.ld;
+  }
+  return BLE_OK;
+}
+
+// the shape table the evolution kernels take by value: the layers' packed blocks and the first logical parameter of each
+EsDims es_dims(const QnetShape& s) {
+  EsDims d{};
+  d.d = s;
+  for (int l = 0; l < s.layers; ++l) d.logical[l + 1] = d.logical[l] + (int64_t)s.k[l] * s.m[l] + s.m[l];
+  return d;
+}
+bool es_ok(const ble_es_f32* es) {
+  return es != nullptr && qnet_ok(&es->net) && es->generation != nullptr && es->members >= 1 && (!es->antithetic || es->members % 2 == 0) &&
+         std::isfinite(es->sigma) && es->sigma > 0.0f && std::isfinite(es->weight_decay);
+}
+bool same_shape(const ble_qnet_f32& a, const ble_qnet_f32& b) {
+  return a.num_layers == b.num_layers && a.input_dim == b.input_dim && a.hidden_units == b.hidden_units && a.num_actions == b.num_actions &&
+         a.num_atoms == b.num_atoms;
+}
+const ble_train_batch_f32 kNoBatch{};      // batch 0: the layout ble_qnet_apply_grad_f32's workspace has
+}  // namespace
+
+int ble_qnet_forward_grouped_f32(const ble_qnet_grouped_f32* pop, void* stream) {
+  if (!pop || !qnet_ok(&pop->net) || !pop->net.weights || !pop->obs || !pop->scratch || !pop->action || pop->obs_row_stride < BLE_OBS_DIM)
+    return BLE_E_INVALID_ARG;
+  if (!aligned(15, pop->net.weights, pop->scratch)) return BLE_E_INVALID_ARG;
+  if (pop->members < 1 || pop->rows_per_member < 1 || pop->rows_per_member > 2147483647LL) return BLE_E_INVALID_ARG;
+  if (pop->head != BLE_POP_HEAD_Q && pop->head != BLE_POP_HEAD_ACTOR_GREEDY) return BLE_E_INVALID_ARG;
+  if (pop->head == BLE_POP_HEAD_Q ? (pop->value != nullptr || pop->probs != nullptr) : (pop->net.num_atoms != 2 || pop->q_values != nullptr))
+    return BLE_E_INVALID_ARG;
+  const QnetShape s = qnet_shape(&pop->net);
+  if (!member_stride_ok(s, pop->member_stride)) return BLE_E_INVALID_ARG;
+  const int64_t ld = s.ld, groups = ld / kQnetCols, P = pop->members, R = pop->rows_per_member;
+  const int64_t n = P * R;                                                       // (< 2^62)
+  if (n >= 2147483648LL / groups) return BLE_E_INVALID_ARG;                      // (so groups * P * ceil(R / 128) < 2^31 as well)
+  int status = launch_dense_stack_grouped(s, pop->net.weights, pop->member_stride, pop->obs, pop->obs_row_stride, P, R, pop->scratch, stream);
+  if (status != BLE_OK) return status;
+  const float* logits = pop->scratch + ((s.layers - 1) & 1) * n * ld;
+  if (pop->head == BLE_POP_HEAD_Q)
+    return launch(ble_qnet_head_kernel, n, kQnetHeadBlock, kQnetHeadBlock, stream, logits, ld, pop->net.num_actions, pop->net.num_atoms,
+                  pop->action, pop->q_values, n);
+  // the greedy actor head writes a log-probability and a value per row: into the activation buffer the last layer did not write
+  // (n * ld >= 64 n floats), unless the caller wants the values
+  float* spare = pop->scratch + (s.layers & 1) * n * ld;
+  return launch(ble_ac_head_kernel, n, kQnetHeadBlock, kQnetHeadBlock, stream, logits, ld, (uint64_t)0, (int64_t)0,
+                (const unsigned long long*)nullptr, pop->action, spare, pop->value ? pop->value : spare + n, pop->probs, n);
+}
+
+int ble_es_perturb_f32(const ble_es_f32* es, void* stream) {
+  if (!es_ok(es) || !es->net.weights || !es->population || !aligned(15, es->net.weights, es->population)) return BLE_E_INVALID_ARG;
+  const QnetShape s = qnet_shape(&es->net);
+  if (!member_stride_ok(s, es->member_stride)) return BLE_E_INVALID_ARG;
+  return launch(ble_es_perturb_kernel, s.offset[s.layers], kEsBlock, kEsBlock, stream, es->net.weights, es->population, es->member_stride,
+                (int)es->members, (int)(es->antithetic != 0), es->sigma, (uint64_t)es->seed, (const unsigned long long*)es->generation,
+                es_dims(s));
+}
+
+int ble_es_gradient_f32(const ble_es_f32* es, const ble_qnet_train_f32* tr, const float* w, void* stream) {
+  if (!es_ok(es) || !tr || !qnet_ok(&tr->net) || !same_shape(es->net, tr->net) || !tr->net.weights || !tr->grad || !w ||
+      !aligned(15, tr->net.weights, tr->grad))
+    return BLE_E_INVALID_ARG;
+  const QnetShape s = qnet_shape(&tr->net);
+  const int streams = es->antithetic ? es->members / 2 : es->members;
+  const int status = launch(ble_es_gradient_kernel, s.offset[s.layers], kEsBlock, kEsBlock, stream, tr->net.weights, tr->grad, w, streams,
+                            es->sigma, es->weight_decay, (uint64_t)es->seed, (const unsigned long long*)es->generation, es_dims(s));
+  if (status != BLE_OK) return status;
+  return launch_grid(ble_train_advance_kernel, dim3(1), 1, stream, es->generation);
+}
+
+int ble_qnet_apply_grad_f32(const ble_qnet_train_f32* tr, void* stream) {
+  if (!tr || !qnet_ok(&tr->net) || !tr->net.weights || !tr->grad || !tr->workspace) return BLE_E_INVALID_ARG;
+  if (tr->net.num_layers > 1 && !tr->weights_t) return BLE_E_INVALID_ARG;
+  if (tr->apply_update && (!std::isfinite(tr->lr) || !tr->adam_m || !tr->adam_v || !tr->adam_step || !std::isfinite(tr->adam_b1) ||
+                           !std::isfinite(tr->adam_b2) || !std::isfinite(tr->adam_eps)))
+    return BLE_E_INVALID_ARG;
+  if (!aligned(15, tr->net.weights, tr->grad, tr->workspace, tr->adam_m, tr->adam_v, tr->weights_t)) return BLE_E_INVALID_ARG;
+  if (!tr->apply_update) return BLE_OK;
+  return TrainStep(tr, nullptr, nullptr, nullptr, &kNoBatch, stream).optimise();
 }
 
 namespace {

@@ -295,3 +295,40 @@ def eval_agent_vec(agent, suite: suites.EvaluationSuite, *, batch_size: Optional
     ev.launch(chunk)
     results.extend(ev.results(chunk))
   return results
+
+
+def eval_population_vec(population, suite: suites.EvaluationSuite, *, head: str = 'q', batch_size: Optional[int] = None, wind_field=None,
+                        wind_noise: bool = True, radius_km: float = 50.0, calculate_flight_path: bool = False, capture_graph: bool = True,
+                        device=None) -> List[List[EvaluationResult]]:
+  """Flies every member of a QNetworkPopulation over every seed of `suite` in one batch: one list of EvaluationResult per member, in the
+  suite's order -- member p's list is eval_agent_vec(VecQNetworkAgent(population.member(p)), suite), field for field (head 'actor': the
+  greedy VecActorCriticAgent's).  Row p S + s of a batch flies seed s under member p: every member flies the same seeds, so the members
+  compare paired.  The seeds are flown `batch_size // P` at a time (batch_size: the rows of one batch, default at most 16 384); the
+  other arguments are eval_agent_vec's."""
+  from balloon_learning_environment_amd.agents import population as population_lib
+  device = dev.require_gpu(population.device if device is None else device)
+  seeds = list(suite.seeds)
+  members = population.members
+  assert suite.max_episode_length > 0, 'max_episode_length must be > 0.'
+  if not seeds:
+    return [[] for _ in range(members)]
+  batch_size = 16384 if batch_size is None else int(batch_size)
+  per_batch = min(len(seeds), batch_size // members)
+  assert per_batch > 0, f'batch_size {batch_size} has no room for one seed of each of {members} members'
+  evaluators = {}
+  results: List[List[EvaluationResult]] = [[] for _ in range(members)]
+  for lo in range(0, len(seeds), per_batch):
+    chunk = seeds[lo:lo + per_batch]
+    s = len(chunk)
+    ev = evaluators.get(s)
+    if ev is None:
+      agent = population_lib.VecPopulationAgent(population, s, head=head)
+      ev = evaluators[s] = VecEvaluator(members * s, agent, suite.max_episode_length, wind_field=wind_field, wind_noise=wind_noise,
+                                        radius_km=radius_km, calculate_flight_path=calculate_flight_path, capture_graph=capture_graph,
+                                        device=device)
+    rows = chunk * members                     # row p s + j flies chunk[j]
+    ev.launch(rows)
+    flown = ev.results(rows)
+    for p in range(members):
+      results[p].extend(flown[p * s:(p + 1) * s])
+  return results

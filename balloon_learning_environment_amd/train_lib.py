@@ -354,3 +354,49 @@ def run_exit_loop_vec(env, trainer, planner, buffer, *, num_iterations: int, bet
     s['mean_best_return'] = float(best_sum.item()) / count if count else float('nan')
     stats.append(s)
   return stats
+
+
+def run_es_loop_vec(trainer, *, num_generations: int, seeds_per_member: int, max_episode_length: int = 960, first_seed: int = 0,
+                    wind_field=None, wind_noise: bool = True, eval_center_every: int = 0, head: str = 'q') -> List[dict]:
+  """The loop of an evolution strategy (agents/evolution.py's ESTrainer) over seeded evaluation flights.  Per generation g: perturb;
+  one VecEvaluator flight of P * S rows -- row p S + s flies seed first_seed + g S + s under member p, so every member flies the same
+  fresh seeds; fitness[p] = the mean of member p's cumulative rewards (float64 on the device, then float32); update.  The host
+  synchronises once per generation, for its dict: mean_fitness, max_fitness, min_fitness, transitions (the steps flown so far) and,
+  every eval_center_every generations, center_score: the greedy centre's mean cumulative reward on the generation's seeds; fitness: the
+  float32 [P] device tensor the update was given."""
+  from balloon_learning_environment_amd.agents import population as population_lib
+  from balloon_learning_environment_amd.agents import qnet
+  from balloon_learning_environment_amd.eval import eval_lib
+  from balloon_learning_environment_amd.eval import suites
+  pop = trainer.population
+  members, per = pop.members, int(seeds_per_member)
+  assert num_generations >= 0 and per >= 1
+  agent = population_lib.VecPopulationAgent(pop, per, head=head)
+  ev = eval_lib.VecEvaluator(members * per, agent, max_episode_length, wind_field=wind_field, wind_noise=wind_noise,
+                             device=trainer.device)
+  stats, transitions = [], 0
+  for g in range(num_generations):
+    seeds = [first_seed + g * per + s for s in range(per)]
+    trainer.perturb()
+    ev.launch(seeds * members)
+    fitness = ev.cumulative_reward.view(members, per).mean(dim=1).to(torch.float32)
+    trainer.update(fitness)
+    flown = ev.final_timestep.sum()
+    row = {'mean_fitness': float(fitness.mean().item()), 'max_fitness': float(fitness.max().item()),
+           'min_fitness': float(fitness.min().item())}
+    transitions += int(flown.item())
+    row['transitions'] = transitions
+    ev.sim.check_errors()
+    if eval_center_every and (g + 1) % eval_center_every == 0:
+      center = trainer.network()
+      if head == 'actor':
+        from balloon_learning_environment_amd.agents import actor_critic
+        center_agent = actor_critic.VecActorCriticAgent(center, deterministic=True)
+      else:
+        center_agent = qnet.VecQNetworkAgent(center)
+      flights = eval_lib.eval_agent_vec(center_agent, suites.EvaluationSuite(seeds, max_episode_length), wind_field=wind_field,
+                                        wind_noise=wind_noise, device=trainer.device)
+      row['center_score'] = sum(f.cumulative_reward for f in flights) / len(flights)
+    row['fitness'] = fitness.clone()
+    stats.append(row)
+  return stats

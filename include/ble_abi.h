@@ -1437,6 +1437,76 @@ struct ble_plan_bootstrap {
 };
 int ble_plan_bootstrap_f32(const struct ble_plan_bootstrap* b, void* stream);
 
+/* ------------------------------------------------------------------------------------------------ a population of policies
+ * ble_qnet_forward_grouped_f32: P = members networks of ONE shape in one batch of P * R rows: rows [p R, (p + 1) R) go through weight
+ * image p, which starts at net.weights + p * member_stride floats.  Row p R + r gets the bits ble_qnet_forward_f32 (head = BLE_POP_HEAD_Q)
+ * or greedy ble_ac_act_f32 (head = BLE_POP_HEAD_ACTOR_GREEDY) of member p alone gives row r: the forward's batch-invariance contract, so
+ * there is no tolerance.  scratch: the floats ble_qnet_workspace_f32 reports for n = P * R; the last layer's output (the logits) is
+ * rows of ld floats at scratch + ((num_layers - 1) & 1) * P * R * ld.  Nothing outside rows [0, P R) of an output is written.
+ * BLE_E_INVALID_ARG before any HIP call: what ble_qnet_forward_f32 refuses (descriptor, NULL net.weights / obs / scratch / action,
+ * obs_row_stride < BLE_OBS_DIM, net.weights or scratch not 16-byte aligned); members < 1 or rows_per_member < 1; P * R >= 2^31 / groups
+ * (groups = the widest padded layer / 64); member_stride < the image's size or not a multiple of 64; a head outside the two below;
+ * BLE_POP_HEAD_ACTOR_GREEDY on a network whose num_atoms != 2, or with q_values; value or probs with BLE_POP_HEAD_Q.  There is no
+ * sampling head.
+ */
+#define BLE_POP_HEAD_Q 0
+#define BLE_POP_HEAD_ACTOR_GREEDY 1
+typedef struct ble_qnet_grouped_f32 {
+  ble_qnet_f32 net;                          /* the members' shape, and weights = image 0 (device) */
+  int32_t members;                           /* P >= 1 */
+  int32_t head;                              /* BLE_POP_HEAD_* */
+  int64_t member_stride;                     /* floats between images: >= packed_floats, a multiple of 64 */
+  int64_t rows_per_member;                   /* R >= 1 */
+  int64_t obs_row_stride;                    /* floats between observation rows, >= BLE_OBS_DIM */
+  const float* obs;                          /* device [P * R] rows */
+  float* scratch;                            /* device, 2 * P * R * ld floats */
+  uint8_t* action;                           /* device [P * R] out */
+  float* q_values;                           /* device [P * R][3] out, or NULL (BLE_POP_HEAD_Q) */
+  float* value;                              /* device [P * R] out, or NULL (BLE_POP_HEAD_ACTOR_GREEDY) */
+  float* probs;                              /* device [P * R][3] out, or NULL (BLE_POP_HEAD_ACTOR_GREEDY) */
+} ble_qnet_grouped_f32;
+int ble_qnet_forward_grouped_f32(const ble_qnet_grouped_f32* pop, void* stream);
+
+/*
+ * An evolution strategy over a packed image.  eps_i[q], the noise of stream i on LOGICAL parameter q (layer by layer, the kernel
+ * row-major [in][out], then the bias: ble_qnet_unpack_f32's order), is (float) of the normal deviate (Box-Muller, cosine branch, of two
+ * 53-bit uniforms) made from the four words of ONE Philox4x32-10 block: key = (seed ^ 0x45564F4C5645) with bits 32..63 of *generation
+ * XORed into its high word, counter = (q & 0xFFFFFFFF, *generation & 0xFFFFFFFF, i, q >> 32).  It depends on nothing else: not on the
+ * population's size, the launch, or sigma.
+ * ble_es_perturb_f32: antithetic: image 2i = theta + fl(sigma * eps_i), image 2i + 1 = theta - fl(sigma * eps_i), i < members / 2
+ * (members even); otherwise image i = theta + fl(sigma * eps_i), i < members.  theta: net.weights (packed).  Padding slots of every
+ * image get +0.0f; the floats between images are not written.
+ * ble_es_gradient_f32: tr->grad[q] = (float)(-(1 / (streams * sigma)) * sum_i (double)w[i] * (double)eps_i[q]), i ascending in float64
+ * (each product rounded, then each sum), rounded once; with weight_decay != 0, then + fl(weight_decay * theta[q]) (theta:
+ * tr->net.weights).  streams = members / 2 (antithetic; w[i] = (u_2i - u_2i+1) / 2) or members.  Padding slots of tr->grad get +0.0f.
+ * Then *generation += 1 in stream order (device memory: a captured graph advances it on replay).
+ * BLE_E_INVALID_ARG before any HIP call: NULL es, net.weights (perturb), population (perturb), generation, tr / tr->grad /
+ * tr->net.weights / w (gradient); a bad network descriptor, or (gradient) one that differs from tr->net in shape; members < 1, or odd
+ * with antithetic; member_stride < the image's size or not a multiple of 64 (perturb); sigma not finite or <= 0; weight_decay not finite.
+ */
+typedef struct ble_es_f32 {
+  ble_qnet_f32 net;                          /* the shape, and weights = the centre image theta (device) */
+  int32_t members;                           /* P */
+  int32_t antithetic;                        /* != 0: pairs (P even) */
+  int64_t member_stride;                     /* floats between images of `population` */
+  float* population;                         /* device: image 0 (ble_es_perturb_f32 writes P images) */
+  float sigma;
+  float weight_decay;
+  uint64_t seed;
+  unsigned long long* generation;            /* device [1] */
+} ble_es_f32;
+int ble_es_perturb_f32(const ble_es_f32* es, void* stream);
+int ble_es_gradient_f32(const ble_es_f32* es, const ble_qnet_train_f32* tr, const float* w, void* stream);
+
+/*
+ * ble_qnet_apply_grad_f32: the optimiser stage of ble_qnet_train_step_f32 alone, on whatever tr->grad holds: Adam's prologue
+ * (*adam_step += 1, the bias corrections), Adam, the weights_t mirror -- the same kernels with the same arguments.  tr->workspace: at
+ * least 64 floats (the layout of batch 0; the first 4 hold the corrections).  tr->apply_update == 0: BLE_OK, nothing launched.
+ * BLE_E_INVALID_ARG before any HIP call: NULL tr, net.weights, grad or workspace; a bad network descriptor; weights_t NULL with more than
+ * one layer; under apply_update: lr or an Adam hyperparameter not finite, NULL adam_m / adam_v / adam_step; a pointer not 16-byte aligned.
+ */
+int ble_qnet_apply_grad_f32(const ble_qnet_train_f32* tr, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
