@@ -352,3 +352,12 @@ class BleEsF32(ctypes.Structure):
   _fields_ = [('net', BleQnetF32), ('members', ctypes.c_int32), ('antithetic', ctypes.c_int32), ('member_stride', ctypes.c_int64),
               ('population', ctypes.c_void_p), ('sigma', ctypes.c_float), ('weight_decay', ctypes.c_float), ('seed', ctypes.c_uint64),
               ('generation', ctypes.c_void_p)]
+
+
+class BlePpoGroupedF32(ctypes.Structure):
+  """struct ble_ppo_grouped_f32: a grouped PPO update of P networks of one shape on P * B rows: member 0's buffers and the strides
+  between members, the per-member hyperparameters [P] and the rows' old log-probabilities and advantages [P * B] (device pointers)."""
+  _fields_ = [('tr', BleQnetTrainF32), ('members', ctypes.c_int32), ('reserved_', ctypes.c_int32), ('member_stride', ctypes.c_int64),
+              ('transposed_stride', ctypes.c_int64), ('rows_per_member', ctypes.c_int64), ('lr', ctypes.c_void_p),
+              ('clip', ctypes.c_void_p), ('value_coef', ctypes.c_void_p), ('entropy_coef', ctypes.c_void_p), ('old_logp', ctypes.c_void_p),
+              ('advantage', ctypes.c_void_p)]

@@ -241,6 +241,91 @@ class VecRolloutBuffer:
     self.generator.set_state(d['generator'])
 
 
+class VecPopulationRolloutBuffer:
+  """VecRolloutBuffer for a population (agents/population.py: PopulationPPOTrainer): T steps of P * R environments, environment rows
+  [p R, (p + 1) R) member p's, held member-major -- obs [P, T, R, ROW_FLOATS], the others [P, T, R], boot_value [P, R] -- so each
+  member's [T, R] block is contiguous and is what that member's own VecRolloutBuffer(R, T) holds.
+
+  add(t, ...) takes one vector step of all P * R environments; finish runs ble_gae_f32 and (if asked) ble_adv_normalize_f32 once per
+  member on its block: each member's advantages are normalised over its own T R rows.  minibatches(B) draws ONE torch.randperm(T R) per
+  pass from a generator seeded 0 (VecRolloutBuffer's stream), shared by all members, and yields a PopulationPPOBatch of P * B rows
+  whose member-p rows are that member's rows perm[k B:(k + 1) B].  No call synchronises with the host."""
+
+  _TENSORS = VecRolloutBuffer._TENSORS
+
+  def __init__(self, members: int, rows_per_member: int, horizon: int, device='cuda:0'):
+    from balloon_learning_environment_amd.agents import population
+    self._batch_type = population.PopulationPPOBatch
+    self.device = d = dev.require_gpu(device)
+    self.members, self.rows_per_member, self.horizon = int(members), int(rows_per_member), int(horizon)
+    if self.members < 1 or self.rows_per_member < 1 or self.horizon < 1:
+      raise ValueError('members, rows_per_member and horizon must be at least 1')
+    self.num_envs = self.members * self.rows_per_member
+    p, t, r = self.members, self.horizon, self.rows_per_member
+    with torch.cuda.device(d):
+      self.obs = torch.zeros(p, t, r, ROW_FLOATS, dtype=torch.float32, device=d)
+      self.action = torch.zeros(p, t, r, dtype=torch.uint8, device=d)
+      self.terminal = torch.zeros(p, t, r, dtype=torch.uint8, device=d)
+      self.episode_end = torch.zeros(p, t, r, dtype=torch.uint8, device=d)
+      self.logp, self.value, self.reward, self.advantage, self.ret = (torch.zeros(p, t, r, dtype=torch.float32, device=d) for _ in range(5))
+      self.boot_value = torch.zeros(p, r, dtype=torch.float32, device=d)
+      self.generator = torch.Generator(device=d)
+    self.generator.manual_seed(0)
+    self._batches: Dict[int, object] = {}
+
+  @dev.on_own_device
+  def add(self, t: int, obs: torch.Tensor, action: torch.Tensor, logp: torch.Tensor, value: torch.Tensor, reward: torch.Tensor,
+          terminal: torch.Tensor, episode_end: Optional[torch.Tensor] = None) -> None:
+    """Step t of the block, every argument over the P * R environments."""
+    p, r = self.members, self.rows_per_member
+    self.obs[:, t, :, :_lib.OBS_DIM].copy_(obs[:, :_lib.OBS_DIM].view(p, r, _lib.OBS_DIM))
+    for name, src in (('action', action), ('logp', logp), ('value', value), ('reward', reward), ('terminal', terminal),
+                      ('episode_end', terminal if episode_end is None else episode_end)):
+      getattr(self, name)[:, t].copy_(src.view(p, r))
+
+  @dev.on_own_device
+  def finish(self, boot_value: torch.Tensor, gamma: float, lam: float, normalize: bool = True) -> None:
+    """boot_value [P * R]: the value of the observation after the last step.  Writes advantage and ret, member by member."""
+    self.boot_value.copy_(boot_value.view(self.members, self.rows_per_member))
+    stream = dev.stream_ptr(self.device)
+    for p in range(self.members):
+      blk = _abi.BleGaeBlockF32(self.horizon, self.rows_per_member, float(gamma), float(lam), self.reward[p].data_ptr(),
+                                self.value[p].data_ptr(), self.boot_value[p].data_ptr(), self.terminal[p].data_ptr(),
+                                self.episode_end[p].data_ptr(), self.advantage[p].data_ptr(), self.ret[p].data_ptr())
+      _lib.call('ble_gae_f32', ctypes.byref(blk), stream)
+      if normalize:
+        _lib.call('ble_adv_normalize_f32', ctypes.byref(blk), stream)
+
+  def batch_buffers(self, batch_size: int):
+    return dev.first_use(self._batches, batch_size, lambda: self._batch_type(self.members, batch_size, self.device),
+                         f'VecPopulationRolloutBuffer: draw minibatches once at batch size {batch_size} before capturing an update')
+
+  @dev.on_own_device
+  def minibatches(self, batch_size: int, generator: Optional[torch.Generator] = None):
+    """One pass over the block in a random order, batch_size rows PER MEMBER: the same buffers, refilled for every minibatch."""
+    b, m, p = int(batch_size), self.horizon * self.rows_per_member, self.members
+    bt = self.batch_buffers(b)
+    perm = torch.randperm(m, device=self.device, generator=self.generator if generator is None else generator)
+    flat = {'state': self.obs.view(p, m, ROW_FLOATS), 'ret': self.ret.view(p, m), 'action': self.action.view(p, m),
+            'old_logp': self.logp.view(p, m), 'advantage': self.advantage.view(p, m)}
+    outs = {name: getattr(bt, name).view(p, b, *src.shape[2:]) for name, src in flat.items()}
+    for k in range(m // b):
+      idx = perm[k * b:(k + 1) * b]
+      for name, src in flat.items():
+        torch.index_select(src, 1, idx, out=outs[name])
+      yield bt
+
+  def state_dict(self) -> dict:
+    return {'members': self.members, 'rows_per_member': self.rows_per_member, 'horizon': self.horizon,
+            'generator': self.generator.get_state().clone(), **{k: getattr(self, k).clone() for k in self._TENSORS}}
+
+  def load_state_dict(self, d: dict) -> None:
+    assert (d['members'], d['rows_per_member'], d['horizon']) == (self.members, self.rows_per_member, self.horizon)
+    for k in self._TENSORS:
+      getattr(self, k).copy_(d[k])
+    self.generator.set_state(d['generator'])
+
+
 class PPOTrainer(qnet_train.QNetworkLearner):
   """Clipped-PPO training of an actor-critic's parameters on its device.
 
@@ -253,7 +338,8 @@ class PPOTrainer(qnet_train.QNetworkLearner):
 
   def __init__(self, network: qnet.QNetwork, *, lr: float = 3e-4, eps: float = 1e-5, gamma: float = 0.993, lam: float = 0.95,
                clip: float = 0.2, value_coef: float = 0.5, entropy_coef: float = 0.01, normalize_advantage: bool = True, seed: int = 0,
-               b1: float = 0.9, b2: float = 0.999):
+               b1: float = 0.9, b2: float = 0.999, env_offset: int = 0):
+    """env_offset: the index of row 0's environment in the sampled head's keying (VecActorCriticAgent's)."""
     _require_actor_critic(network, 'PPOTrainer')
     super().__init__(network)
     self.lr, self.eps, self.b1, self.b2 = float(lr), float(eps), float(b1), float(b2)
@@ -265,7 +351,7 @@ class PPOTrainer(qnet_train.QNetworkLearner):
       self.adam_m = torch.zeros_like(self.weights)
       self.adam_v = torch.zeros_like(self.weights)
       self.adam_step = torch.zeros(1, dtype=torch.int64, device=d)
-    self._sampler = _Sampler(self.seed, d)
+    self._sampler = _Sampler(self.seed, d, env_offset)
     self.act_step = self._sampler.step
     self._actor = ActorForward(self._net, d, 'PPOTrainer')
     self._ws: Dict[int, tuple] = {}

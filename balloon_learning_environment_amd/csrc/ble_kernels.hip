@@ -45,6 +45,7 @@
 #include "ble_imitate.h"
 #include "ble_replay.h"
 #include "ble_population.h"
+#include "ble_population_train.h"
 
 using namespace ble;
 
@@ -1758,9 +1759,10 @@ namespace {
 // the stride between the images of a population: room for one image, every image 256-byte aligned when image 0 is
 bool member_stride_ok(const QnetShape& s, int64_t member_stride) { return member_stride >= s.offset[s.layers] && member_stride % 64 == 0; }
 
-// launch_dense_stack for a population: P members of R rows each, member p on the image w + p member_stride; two buffers in turn.
+// launch_dense_stack for a population: P members of R rows each, member p on the image w + p member_stride; two buffers in turn, or
+// (keep) every layer kept: layer l of all P R rows at base + l P R ld.
 int launch_dense_stack_grouped(const QnetShape& s, const float* w, int64_t member_stride, const float* x, int64_t ldx, int64_t members,
-                               int64_t rows_per_member, float* base, void* stream) {
+                               int64_t rows_per_member, float* base, void* stream, bool keep = false) {
   const int64_t n = members * rows_per_member;
   const int64_t tiles_per_member = (rows_per_member + kQnetRows - 1) / kQnetRows;
   for (int l = 0; l < s.layers; ++l) {
@@ -1768,7 +1770,7 @@ int launch_dense_stack_grouped(const QnetShape& s, const float* w, int64_t membe
     const bool first = l == 0, last = l == s.layers - 1;
     const auto dense = first ? (last ? ble_qnet_dense_grouped_kernel<true, false> : ble_qnet_dense_grouped_kernel<true, true>)
                              : (last ? ble_qnet_dense_grouped_kernel<false, false> : ble_qnet_dense_grouped_kernel<false, true>);
-    float* y = base + (l & 1) * n * s.ld;
+    float* y = base + (keep ? l : l & 1) * n * s.ld;
     const int status = launch_grid(dense, dim3((unsigned)(groups * tiles_per_member * members)), kQnetBlock, stream, x, ldx, s.k[l], s.kp[l],
                                    w + s.offset[l], member_stride, y, s.ld, groups, rows_per_member, tiles_per_member);
     if (status != BLE_OK) return status;
@@ -1796,30 +1798,51 @@ bool same_shape(const ble_qnet_f32& a, const ble_qnet_f32& b) {
 const ble_train_batch_f32 kNoBatch{};      // batch 0: the layout ble_qnet_apply_grad_f32's workspace has
 }  // namespace
 
-int ble_qnet_forward_grouped_f32(const ble_qnet_grouped_f32* pop, void* stream) {
+namespace {
+// what ble_qnet_forward_grouped_f32 refuses
+bool grouped_ok(const ble_qnet_grouped_f32* pop) {
   if (!pop || !qnet_ok(&pop->net) || !pop->net.weights || !pop->obs || !pop->scratch || !pop->action || pop->obs_row_stride < BLE_OBS_DIM)
-    return BLE_E_INVALID_ARG;
-  if (!aligned(15, pop->net.weights, pop->scratch)) return BLE_E_INVALID_ARG;
-  if (pop->members < 1 || pop->rows_per_member < 1 || pop->rows_per_member > 2147483647LL) return BLE_E_INVALID_ARG;
-  if (pop->head != BLE_POP_HEAD_Q && pop->head != BLE_POP_HEAD_ACTOR_GREEDY) return BLE_E_INVALID_ARG;
+    return false;
+  if (!aligned(15, pop->net.weights, pop->scratch)) return false;
+  if (pop->members < 1 || pop->rows_per_member < 1 || pop->rows_per_member > 2147483647LL) return false;
+  if (pop->head != BLE_POP_HEAD_Q && pop->head != BLE_POP_HEAD_ACTOR_GREEDY) return false;
   if (pop->head == BLE_POP_HEAD_Q ? (pop->value != nullptr || pop->probs != nullptr) : (pop->net.num_atoms != 2 || pop->q_values != nullptr))
-    return BLE_E_INVALID_ARG;
+    return false;
   const QnetShape s = qnet_shape(&pop->net);
-  if (!member_stride_ok(s, pop->member_stride)) return BLE_E_INVALID_ARG;
-  const int64_t ld = s.ld, groups = ld / kQnetCols, P = pop->members, R = pop->rows_per_member;
-  const int64_t n = P * R;                                                       // (< 2^62)
-  if (n >= 2147483648LL / groups) return BLE_E_INVALID_ARG;                      // (so groups * P * ceil(R / 128) < 2^31 as well)
+  if (!member_stride_ok(s, pop->member_stride)) return false;
+  const int64_t groups = s.ld / kQnetCols;
+  return pop->members * pop->rows_per_member < 2147483648LL / groups;      // (P R < 2^62; so groups * P * ceil(R / 128) < 2^31 as well)
+}
+
+// The grouped Dense stack of a checked population, then its head.  An actor head (greedy: sample == nullptr) writes a log-probability
+// and a value per row: without the caller's arrays, into the activation buffer the last layer did not write (n * ld >= 64 n floats).
+int launch_grouped_forward(const ble_qnet_grouped_f32* pop, const ble_ac_sample* sample, float* logp, void* stream) {
+  const QnetShape s = qnet_shape(&pop->net);
+  const int64_t ld = s.ld, P = pop->members, R = pop->rows_per_member, n = P * R;
   int status = launch_dense_stack_grouped(s, pop->net.weights, pop->member_stride, pop->obs, pop->obs_row_stride, P, R, pop->scratch, stream);
   if (status != BLE_OK) return status;
   const float* logits = pop->scratch + ((s.layers - 1) & 1) * n * ld;
   if (pop->head == BLE_POP_HEAD_Q)
     return launch(ble_qnet_head_kernel, n, kQnetHeadBlock, kQnetHeadBlock, stream, logits, ld, pop->net.num_actions, pop->net.num_atoms,
                   pop->action, pop->q_values, n);
-  // the greedy actor head writes a log-probability and a value per row: into the activation buffer the last layer did not write
-  // (n * ld >= 64 n floats), unless the caller wants the values
   float* spare = pop->scratch + (s.layers & 1) * n * ld;
-  return launch(ble_ac_head_kernel, n, kQnetHeadBlock, kQnetHeadBlock, stream, logits, ld, (uint64_t)0, (int64_t)0,
-                (const unsigned long long*)nullptr, pop->action, spare, pop->value ? pop->value : spare + n, pop->probs, n);
+  return launch(ble_ac_head_kernel, n, kQnetHeadBlock, kQnetHeadBlock, stream, logits, ld, (uint64_t)(sample ? sample->seed : 0),
+                (int64_t)(sample ? sample->env_offset : 0), (const unsigned long long*)(sample ? sample->step : nullptr), pop->action,
+                logp ? logp : spare, pop->value ? pop->value : spare + n, pop->probs, n);
+}
+}  // namespace
+
+int ble_qnet_forward_grouped_f32(const ble_qnet_grouped_f32* pop, void* stream) {
+  if (!grouped_ok(pop)) return BLE_E_INVALID_ARG;
+  return launch_grouped_forward(pop, nullptr, nullptr, stream);
+}
+
+// The sampled (or, sample == NULL, greedy) actor head over a population: row p R + r is keyed by (seed, env_offset + p R + r, *step),
+// what member p alone draws at env_offset + p R.
+int ble_ac_act_grouped_f32(const ble_qnet_grouped_f32* pop, const ble_ac_sample* sample, float* logp, void* stream) {
+  if (!grouped_ok(pop) || pop->head != BLE_POP_HEAD_ACTOR_GREEDY || !logp) return BLE_E_INVALID_ARG;
+  if (sample != nullptr && (!sample->step || sample->env_offset < 0)) return BLE_E_INVALID_ARG;
+  return launch_grouped_forward(pop, sample, logp, stream);
 }
 
 int ble_es_perturb_f32(const ble_es_f32* es, void* stream) {
@@ -1880,6 +1903,138 @@ int ble_adv_normalize_f32(const ble_gae_block_f32* g, void* stream) {
 int ble_qnet_ppo_step_f32(const ble_qnet_train_f32* tr, const ble_ppo_f32* ppo, const ble_train_batch_f32* bt, float* loss, uint32_t* err_flags,
                           void* stream) {
   return ppo != nullptr ? launch_update(tr, nullptr, bt, loss, err_flags, stream, ppo) : BLE_E_INVALID_ARG;
+}
+
+// ---------------------------------------------------------------------------------------------------------------- populations, by gradient
+namespace {
+// The sizes of a grouped update: what the workspace query reads.
+bool grouped_sizes_ok(const ble_ppo_grouped_f32* g) {
+  if (!g || !qnet_ok(&g->tr.net) || g->tr.net.num_atoms != 2 || g->reserved_ != 0) return false;
+  const int64_t P = g->members, B = g->rows_per_member;
+  if (P < 1 || B < 1 || P > 65535 || B > BLE_TRAIN_MAX_BATCH || P * B > BLE_TRAIN_MAX_BATCH) return false;
+  if (P * wgrad_slabs(B) > 65535) return false;                                          // (grid z of dW)
+  const int64_t groups = qnet_shape(&g->tr.net).ld / kQnetCols;
+  return groups * P * ((B + kQnetRows - 1) / kQnetRows) < 2147483648LL;
+}
+// train_layout at n = P B, but the slabs are the member's (a function of B) and every member has its own partial sums.
+ble_qnet_train_layout grouped_train_layout(const QnetShape& s, int64_t P, int64_t B) {
+  ble_qnet_train_layout y{};
+  const int64_t ld = s.ld, L = s.layers, n = P * B;
+  y.ld = ld;
+  y.slabs = wgrad_slabs(B);
+  int64_t at = 0;
+  auto take = [&](int64_t floats) { const int64_t o = at; at += qnet_round_up(floats, 64); return o; };
+  y.acts = take(L * n * ld);
+  y.target_logits = take(n * ld);
+  y.targets = take(n * 2);
+  y.dlogits = take(n * ld);
+  y.scratch = take(4 * n * ld);
+  y.partial = take(y.slabs > 1 ? P * y.slabs * s.max_block : 0);
+  y.corrections = take(4);
+  y.total = at;
+  y.transposed_floats = s.transposed_floats;
+  return y;
+}
+bool grouped_update_ok(const ble_ppo_grouped_f32* g, const ble_train_batch_f32* bt, const float* loss) {
+  if (!grouped_sizes_ok(g) || !batch_ok(bt, false, true, true) || !loss) return false;
+  const ble_qnet_train_f32& tr = g->tr;
+  if (!tr.net.weights || !tr.grad || !tr.workspace) return false;
+  if (bt->batch != (int64_t)g->members * g->rows_per_member) return false;
+  const QnetShape s = qnet_shape(&tr.net);
+  if (!member_stride_ok(s, g->member_stride)) return false;
+  if (tr.net.num_layers > 1 && (!tr.weights_t || g->transposed_stride < s.transposed_floats || g->transposed_stride % 64 != 0)) return false;
+  if (!g->lr || !g->clip || !g->value_coef || !g->entropy_coef || !g->old_logp || !g->advantage) return false;
+  if (tr.apply_update &&
+      (!tr.adam_m || !tr.adam_v || !tr.adam_step || !std::isfinite(tr.adam_b1) || !std::isfinite(tr.adam_b2) || !std::isfinite(tr.adam_eps)))
+    return false;
+  return aligned(15, tr.net.weights, tr.grad, tr.workspace, tr.adam_m, tr.adam_v, tr.weights_t) &&
+         aligned(3, g->lr, g->clip, g->value_coef, g->entropy_coef, g->old_logp, g->advantage);
+}
+
+// One grouped update on a checked batch, beside TrainStep: the shape, the workspace's parts and the stages in launch order.
+struct GroupedTrainStep {
+  const ble_ppo_grouped_f32* g;
+  const ble_qnet_train_f32* tr;
+  const ble_train_batch_f32* bt;
+  void* stream;
+  const QnetShape s;
+  const int64_t P, B, n;
+  const ble_qnet_train_layout lay;
+  const int64_t ld, tstride;
+  float* const ws;
+
+  GroupedTrainStep(const ble_ppo_grouped_f32* g_, const ble_train_batch_f32* bt_, void* stream_)
+      : g(g_), tr(&g_->tr), bt(bt_), stream(stream_), s(qnet_shape(&g_->tr.net)), P(g_->members), B(g_->rows_per_member), n(P * B),
+        lay(grouped_train_layout(s, P, B)), ld(lay.ld), tstride(s.layers > 1 ? g_->transposed_stride : 0), ws(g_->tr.workspace) {}
+  float* acts(int l) const { return ws + lay.acts + l * n * ld; }
+
+  int forward() const {
+    return launch_dense_stack_grouped(s, tr->net.weights, g->member_stride, bt->state, bt->state_stride, P, B, acts(0), stream, true);
+  }
+  int loss(float* row_loss, uint32_t* err_flags) const {
+    return launch_grid(ble_ppo_loss_grouped_kernel, dim3((unsigned)n), kTrainLossBlock, stream, (const float*)acts(s.layers - 1), ld,
+                       (const float*)bt->ret, (const uint8_t*)bt->action, g->old_logp, g->advantage, g->clip, g->value_coef, g->entropy_coef,
+                       B, ws + lay.targets, ws + lay.dlogits, row_loss, err_flags);
+  }
+  // TrainStep::backward with the member coordinate: the slabs and their rows come from B
+  int backward() const {
+    float* dyb[2] = {ws + lay.scratch + 2 * n * ld, ws + lay.scratch + 3 * n * ld};
+    const int64_t tiles_per_member = (B + kQnetRows - 1) / kQnetRows;
+    const int slabs = (int)lay.slabs;
+    const int64_t slab_rows = slabs == 1 ? B : (B + slabs - 1) / slabs;
+    const float* dy = ws + lay.dlogits;
+    for (int l = s.layers - 1; l >= 0; --l) {
+      const int64_t blk = s.block(l);
+      float* grad = tr->grad + s.offset[l];
+      const float* x = l == 0 ? bt->state : acts(l - 1);
+      int status = launch_grid(ble_qnet_wgrad_grouped_kernel,
+                               dim3((unsigned)((s.kp[l] + 31) / 32), (unsigned)(s.mp[l] / kQnetCols), (unsigned)(P * slabs)), 64, stream, x,
+                               l == 0 ? bt->state_stride : ld, s.k[l], s.kp[l], dy, ld, s.m[l], s.mp[l], B, slab_rows, slabs,
+                               slabs == 1 ? grad : ws + lay.partial, slabs == 1 ? g->member_stride : slabs * blk,
+                               slabs == 1 ? (int64_t)0 : blk);
+      if (status != BLE_OK) return status;
+      if (slabs > 1) {
+        status = launch_grid(ble_wgrad_reduce_grouped_kernel, dim3((unsigned)((blk + 255) / 256), (unsigned)P), 256, stream,
+                             (const float*)(ws + lay.partial), slabs, blk, blk, grad, g->member_stride);
+        if (status != BLE_OK) return status;
+      }
+      if (l == 0) break;
+      const int groups = s.mpt(l) / kQnetCols;
+      float* dx = dyb[l & 1];
+      status = launch_grid(ble_qnet_dgrad_grouped_kernel, dim3((unsigned)(groups * tiles_per_member * P)), kQnetBlock, stream, dy, ld,
+                           s.kpt(l), (const float*)(tr->weights_t + s.toffset[l]), tstride, (const float*)acts(l - 1), dx, groups, B,
+                           tiles_per_member);
+      if (status != BLE_OK) return status;
+      dy = dx;
+    }
+    return BLE_OK;
+  }
+  int optimise() const {
+    float* corr = ws + lay.corrections;
+    const int status = launch_grid(ble_adam_prologue_kernel, dim3(1), 1, stream, tr->adam_step, tr->adam_b1, tr->adam_b2, corr);
+    if (status != BLE_OK) return status;
+    const int64_t image = s.offset[s.layers];
+    return launch_grid(ble_adam_grouped_kernel, dim3((unsigned)((image + kAdamBlock - 1) / kAdamBlock), (unsigned)P), kAdamBlock, stream,
+                       const_cast<float*>(tr->net.weights), tr->weights_t, (const float*)tr->grad, tr->adam_m, tr->adam_v, (const float*)corr,
+                       g->lr, g->member_stride, tstride, (float)tr->adam_b1, (float)(1.0 - tr->adam_b1), (float)tr->adam_b2,
+                       (float)(1.0 - tr->adam_b2), tr->adam_eps, s);
+  }
+};
+}  // namespace
+
+int ble_qnet_ppo_grouped_workspace_f32(const ble_ppo_grouped_f32* g, ble_qnet_train_layout* layout) {
+  if (!grouped_sizes_ok(g) || !layout) return BLE_E_INVALID_ARG;
+  *layout = grouped_train_layout(qnet_shape(&g->tr.net), g->members, g->rows_per_member);
+  return BLE_OK;
+}
+
+int ble_qnet_ppo_step_grouped_f32(const ble_ppo_grouped_f32* g, const ble_train_batch_f32* bt, float* loss, uint32_t* err_flags, void* stream) {
+  if (!grouped_update_ok(g, bt, loss)) return BLE_E_INVALID_ARG;
+  const GroupedTrainStep t(g, bt, stream);
+  if (const int status = t.forward(); status != BLE_OK) return status;
+  if (const int status = t.loss(loss, err_flags); status != BLE_OK) return status;
+  if (const int status = t.backward(); status != BLE_OK) return status;
+  return g->tr.apply_update ? t.optimise() : BLE_OK;
 }
 
 // ---------------------------------------------------------------------------------------------------------------- imitation

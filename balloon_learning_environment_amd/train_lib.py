@@ -1,10 +1,10 @@
 """The training loops of the device learners over a VecBalloonEnv: the reference's train_lib.run_training_loop with Dopamine's
 schedule (min_replay_history, update_period, target_update_period counted in transitions) for the replay learners (QNetworkTrainer,
 DQNTrainer), the loop of an online learner (VecMLPAgent), the on-policy loop (PPOTrainer), the DAgger loop of an imitation learner
-(BCTrainer) and the expert-iteration loop of a soft-target learner and a planner (SoftBCTrainer, VecLookaheadAgent); N environments per
-step.
+(BCTrainer), the expert-iteration loop of a soft-target learner and a planner (SoftBCTrainer, VecLookaheadAgent) and population-based
+training of P on-policy learners in one batch (PopulationPPOTrainer); N environments per step.
 """
-from typing import Callable, List, Optional, Union
+from typing import Callable, List, Optional, Sequence, Tuple, Union
 
 import torch
 
@@ -205,6 +205,161 @@ def run_ppo_loop_vec(env, trainer, rollout, *, num_iterations: int, epochs: int 
     env.check_errors()
     trainer.check_errors()
     stats.append(book.finish_iteration(steps))
+  return stats
+
+
+def pbt_decide(fitness: torch.Tensor, truncation: float, generator: Optional[torch.Generator] = None,
+               num_explored: int = 1) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+  """One round of population-based training (Jaderberg et al. 2017, truncation selection) as a pure function, on fitness's device
+  and without a host synchronisation: (src, dst, factor_index).
+
+  fitness [P] float: higher is better; NaN marks a member without a finished episode, which ranks lowest.  The members are ranked best
+  first by a stable sort, so ties break by member index.  k = floor(truncation * P), at most P // 2.  dst int64 [k]: the k lowest-ranked
+  members, in rank order; src int64 [k]: for each a member of the k highest-ranked drawn uniformly with `generator`; factor_index
+  int64 [k, num_explored] in {0, 1}: which of the two perturbation factors each explored hyperparameter of the copy takes.  k == 0
+  (truncation 0, or P too small): three empty tensors, nothing drawn."""
+  assert fitness.dim() == 1 and fitness.is_floating_point() and 0.0 <= truncation <= 0.5
+  p, d = fitness.numel(), fitness.device
+  k = min(int(truncation * p + 1e-9), p // 2)
+  if k == 0:
+    e = torch.zeros(0, dtype=torch.int64, device=d)
+    return e, e.clone(), torch.zeros(0, num_explored, dtype=torch.int64, device=d)
+  none = torch.isnan(fitness)
+  order = torch.sort(torch.where(none, torch.zeros_like(fitness), fitness), descending=True, stable=True).indices
+  order = order[torch.sort(none[order].to(torch.int8), stable=True).indices]      # (below every fitness, -inf too; both sorts stable)
+  dst = order[p - k:]
+  src = order[:k][torch.randint(0, k, (k,), generator=generator, device=d)]
+  factor_index = torch.randint(0, 2, (k, num_explored), generator=generator, device=d)
+  return src, dst, factor_index
+
+
+class PBTController:
+  """The state of population-based training between iterations, all on the device: the per-member sums of finished episodes' returns
+  and their counts since the last round, the lineage (int64 [P]: the initial member each one descends from), the decisions' generator
+  and the iteration count.  state_dict / load_state_dict: a resumed run continues to the same bytes."""
+
+  def __init__(self, members: int, device, *, ready_every: int, truncation: float = 0.25, perturb: Sequence[float] = (0.8, 1.25),
+               explore: Sequence[str] = ('lr', 'entropy_coef'), seed: int = 0):
+    if ready_every < 1 or not 0.0 <= truncation <= 0.5 or len(perturb) != 2:
+      raise ValueError('ready_every >= 1, 0 <= truncation <= 0.5 and two perturbation factors')
+    self.members, self.device = int(members), torch.device(device)
+    self.ready_every, self.truncation, self.explore = int(ready_every), float(truncation), tuple(explore)
+    self.perturb = torch.tensor([float(f) for f in perturb], dtype=torch.float32, device=self.device)
+    self.generator = torch.Generator(device=self.device)
+    self.generator.manual_seed(int(seed))
+    self.lineage = torch.arange(self.members, dtype=torch.int64, device=self.device)
+    self.return_sum = torch.zeros(self.members, dtype=torch.float32, device=self.device)
+    self.episodes = torch.zeros(self.members, dtype=torch.int64, device=self.device)
+    self.iteration = 0
+    self.rounds = 0
+
+  def step(self, ended_returns: torch.Tensor, ended: torch.Tensor) -> None:
+    """One vector step: ended_returns [P, R] float32 (the return of an episode that ended in this step, else 0), ended [P, R] bool."""
+    self.return_sum += ended_returns.sum(dim=1)
+    self.episodes += ended.sum(dim=1)
+
+  def fitness(self) -> torch.Tensor:
+    """[P] float32: the mean return of the episodes each member finished since the last round; NaN without one."""
+    return torch.where(self.episodes > 0, self.return_sum / self.episodes.clamp(min=1).to(torch.float32),
+                       torch.full_like(self.return_sum, float('nan')))
+
+  def end_iteration(self, trainer) -> Optional[dict]:
+    """Counts the iteration; every ready_every-th runs a round on `trainer` (copy_members, scale_hyper) and returns its device
+    tensors {'fitness', 'src', 'dst'}, else None."""
+    self.iteration += 1
+    if self.iteration % self.ready_every:
+      return None
+    fitness = self.fitness()
+    src, dst, factor_index = pbt_decide(fitness, self.truncation, self.generator, len(self.explore))
+    if dst.numel():
+      trainer.copy_members(src, dst)
+      for j, name in enumerate(self.explore):
+        trainer.scale_hyper(name, dst, self.perturb[factor_index[:, j]])
+      self.lineage.index_copy_(0, dst, self.lineage.index_select(0, src))
+    self.return_sum.zero_()
+    self.episodes.zero_()
+    self.rounds += 1
+    return {'fitness': fitness, 'src': src, 'dst': dst}
+
+  def state_dict(self) -> dict:
+    return {'members': self.members, 'iteration': self.iteration, 'rounds': self.rounds, 'generator': self.generator.get_state().clone(),
+            'lineage': self.lineage.clone(), 'return_sum': self.return_sum.clone(), 'episodes': self.episodes.clone()}
+
+  def load_state_dict(self, d: dict) -> None:
+    assert int(d['members']) == self.members
+    self.iteration, self.rounds = int(d['iteration']), int(d['rounds'])
+    self.generator.set_state(d['generator'])
+    for k in ('lineage', 'return_sum', 'episodes'):
+      getattr(self, k).copy_(d[k])
+
+
+def run_pbt_loop_vec(env, trainer, rollout, *, num_iterations: int, epochs: int = 4, batch_size: int, ready_every: int,
+                     truncation: float = 0.25, perturb: Sequence[float] = (0.8, 1.25), explore: Sequence[str] = ('lr', 'entropy_coef'),
+                     seed: int = 0, max_episode_length: int = 960, capture_graph: bool = True,
+                     controller: Optional[PBTController] = None) -> List[dict]:
+  """Population-based training of P on-policy learners in one batch (agents/population.py: PopulationPPOTrainer with a
+  VecPopulationRolloutBuffer(P, R, T)) on `env` (auto_reset) of P * R environments, environment rows [p R, (p + 1) R) member p's.
+
+  Each iteration is run_ppo_loop_vec's with grouped calls: T vector steps with every member's sampled policy, the bootstrap act,
+  rollout.finish (advantages per member), then `epochs` passes of minibatches of batch_size rows PER MEMBER, each one grouped update.
+  Every ready_every iterations a round follows (pbt_decide): fitness[p] is the mean return of the episodes member p finished since the
+  last round; the members in the bottom `truncation` share each become a copy of a uniformly drawn member of the top share (weights,
+  Adam moments and hyperparameters: trainer.copy_members), and each hyperparameter named in `explore` of the copy is multiplied by one of
+  the two `perturb` factors (trainer.scale_hyper).  truncation = 0 is a plain P-seed study.  controller: a PBTController to continue
+  (its settings then replace ready_every, truncation, perturb, explore and seed).
+
+  Returns run_training_loop_vec's dicts (mean_loss: the mean over the members' rows) plus member_episodes and member_mean_return
+  (lists of P, this iteration's), lineage (a list of P: the initial member each one descends from), lr (a list of P) and, on a round's
+  iteration, round = {'fitness', 'src', 'dst'} as lists (else None).  One host synchronisation per iteration: its end."""
+  n, dev_ = env.num_envs, env.device
+  p, r, steps = rollout.members, rollout.rows_per_member, rollout.horizon
+  assert trainer.members == p and rollout.num_envs == n == p * r, 'the rollout block has one column per environment, R per member'
+  pbt = controller if controller is not None else PBTController(p, dev_, ready_every=ready_every, truncation=truncation, perturb=perturb,
+                                                                explore=explore, seed=seed)
+  obs = env.reset()
+  actions = torch.zeros(n, dtype=torch.uint8, device=dev_)
+  logp = torch.zeros(n, dtype=torch.float32, device=dev_)
+  value = torch.zeros(n, dtype=torch.float32, device=dev_)
+  book = _EpisodeBook(n, dev_, max_episode_length)
+  captured = False
+  stats = []
+  for _ in range(num_iterations):
+    it_sum = torch.zeros(p, dtype=torch.float32, device=dev_)
+    it_episodes = torch.zeros(p, dtype=torch.int64, device=dev_)
+    for t in range(steps):
+      trainer.act(obs, actions, logp, value)
+      end_mask = book.end_mask()
+      next_obs, reward, terminal = env.step(actions, end_mask=end_mask)
+      episode_end = terminal | end_mask
+      rollout.add(t, obs, actions, logp, value, reward, terminal, episode_end)
+      ended = episode_end.bool().view(p, r)
+      ended_returns = torch.where(ended, (book.ep_return + reward).view(p, r), torch.zeros((), dtype=torch.float32, device=dev_))
+      pbt.step(ended_returns, ended)
+      it_sum += ended_returns.sum(dim=1)
+      it_episodes += ended.sum(dim=1)
+      book.step(reward, episode_end)
+      obs = next_obs
+    trainer.act(obs, actions, logp, value)
+    rollout.finish(value, trainer.gamma, trainer.lam, trainer.normalize_advantage)
+    for _ in range(epochs):
+      for batch in rollout.minibatches(batch_size):
+        if capture_graph and not captured:
+          loss = trainer.capture(batch)                     # (its first, eager update is a real one)
+          captured = True
+        else:
+          loss = trainer.train_step(batch)
+        book.update(loss)
+    rnd = pbt.end_iteration(trainer)
+    env.check_errors()
+    trainer.check_errors()
+    s = book.finish_iteration(steps)
+    eps = it_episodes.tolist()
+    s['member_episodes'] = eps
+    s['member_mean_return'] = [v / e if e else float('nan') for v, e in zip(it_sum.tolist(), eps)]
+    s['lineage'] = pbt.lineage.tolist()
+    s['lr'] = trainer.lr.tolist()
+    s['round'] = None if rnd is None else {k: v.tolist() for k, v in rnd.items()}
+    stats.append(s)
   return stats
 
 

@@ -1446,8 +1446,8 @@ int ble_plan_bootstrap_f32(const struct ble_plan_bootstrap* b, void* stream);
  * BLE_E_INVALID_ARG before any HIP call: what ble_qnet_forward_f32 refuses (descriptor, NULL net.weights / obs / scratch / action,
  * obs_row_stride < BLE_OBS_DIM, net.weights or scratch not 16-byte aligned); members < 1 or rows_per_member < 1; P * R >= 2^31 / groups
  * (groups = the widest padded layer / 64); member_stride < the image's size or not a multiple of 64; a head outside the two below;
- * BLE_POP_HEAD_ACTOR_GREEDY on a network whose num_atoms != 2, or with q_values; value or probs with BLE_POP_HEAD_Q.  There is no
- * sampling head.
+ * BLE_POP_HEAD_ACTOR_GREEDY on a network whose num_atoms != 2, or with q_values; value or probs with BLE_POP_HEAD_Q.  The sampling
+ * head of a population is ble_ac_act_grouped_f32 (below).
  */
 #define BLE_POP_HEAD_Q 0
 #define BLE_POP_HEAD_ACTOR_GREEDY 1
@@ -1506,6 +1506,57 @@ int ble_es_gradient_f32(const ble_es_f32* es, const ble_qnet_train_f32* tr, cons
  * one layer; under apply_update: lr or an Adam hyperparameter not finite, NULL adam_m / adam_v / adam_step; a pointer not 16-byte aligned.
  */
 int ble_qnet_apply_grad_f32(const ble_qnet_train_f32* tr, void* stream);
+
+/* ------------------------------------------------------------------------------------- a population trained by gradient
+ * ble_qnet_ppo_step_grouped_f32: one clipped-PPO update of P = members two-atom networks of ONE shape on a batch of P * B rows, rows
+ * [p B, (p + 1) B) member p's.  Member p's part of every result -- rows [p B, (p + 1) B) of loss and of the workspace's acts, aux
+ * (`targets`) and dlogits; the image-sized blocks at + p * member_stride of grad, net.weights, adam_m, adam_v and at
+ * + p * transposed_stride of weights_t -- holds the bytes ble_qnet_ppo_step_f32 gives member p's own trainer on those B rows with
+ * lr[p], clip[p], value_coef[p], entropy_coef[p]: the objective of member p is the mean over ITS B rows, the dW slabs are
+ * wgrad_slabs(B)'s, and every sum runs in the plain update's order.  No tolerance.  The floats between images are neither read nor
+ * written; the padding inside a gradient image is written as 0.  One Adam step counter serves the population (*adam_step += 1 per
+ * update; the members update in lockstep).  An action >= 3 sets BLE_FLAG_TRAIN_ACTION and zeroes that row only.
+ *
+ * The workspace (ble_qnet_ppo_grouped_workspace_f32) is ble_qnet_train_workspace_f32's layout at a batch of P * B rows with two
+ * differences: slabs = the dW slabs of B rows (not of P * B), and partial holds P * slabs blocks when slabs > 1.
+ *
+ * BLE_E_INVALID_ARG before any HIP call: what ble_qnet_ppo_step_f32 refuses for the corresponding fields (descriptor, batch, NULL
+ * net.weights / grad / workspace / loss, weights_t NULL with more than one layer, under apply_update NULL adam_m / adam_v / adam_step
+ * or a non-finite Adam hyperparameter, a pointer not 16-byte aligned); num_atoms != 2; members < 1 or rows_per_member < 1;
+ * batch->batch != P * B; P * B > BLE_TRAIN_MAX_BATCH; P > 65 535 or P * slabs > 65 535; groups * P * ceil(B / 128) >= 2^31 (groups =
+ * the widest padded layer / 64); member_stride < the image or not a multiple of 64; with more than one layer transposed_stride <
+ * transposed_floats or not a multiple of 64; a NULL among lr, clip, value_coef, entropy_coef, old_logp, advantage, or one that is not
+ * 4-byte aligned; reserved_ != 0.  The per-member arrays are DEVICE memory: the entry cannot see their values (a clip <= 0, a NaN
+ * learning rate); the caller validates what it uploads (agents/population.py does).
+ */
+typedef struct ble_ppo_grouped_f32 {
+  ble_qnet_train_f32 tr;        /* the members' shape; net.weights, weights_t, grad, adam_m, adam_v = member 0's; adam_step, workspace,
+                                   adam_b1/b2/eps, apply_update shared; tr.lr, tr.target, tr.kappa not read */
+  int32_t members;              /* P >= 1 */
+  int32_t reserved_;            /* 0 */
+  int64_t member_stride;        /* floats between members in weights, grad, adam_m, adam_v: >= the image, a multiple of 64 */
+  int64_t transposed_stride;    /* floats between members' weights_t: >= transposed_floats, a multiple of 64 (any value with one layer) */
+  int64_t rows_per_member;      /* B >= 1; batch->batch must equal P * B; rows [p B, (p + 1) B) are member p's */
+  const float* lr;              /* device [P] */
+  const float* clip;            /* device [P] */
+  const float* value_coef;      /* device [P] */
+  const float* entropy_coef;    /* device [P] */
+  const float* old_logp;        /* device [P * B] */
+  const float* advantage;       /* device [P * B] */
+} ble_ppo_grouped_f32;
+/* Reads the network descriptor, members, rows_per_member and reserved_ only; refuses what the update refuses of them. */
+int ble_qnet_ppo_grouped_workspace_f32(const ble_ppo_grouped_f32* g, ble_qnet_train_layout* layout);
+int ble_qnet_ppo_step_grouped_f32(const ble_ppo_grouped_f32* g, const ble_train_batch_f32* batch, float* loss, uint32_t* err_flags, void* stream);
+
+/*
+ * ble_ac_act_grouped_f32: ble_qnet_forward_grouped_f32's Dense stack, then ble_ac_act_f32's head over all P * R rows.  pop->head must
+ * be BLE_POP_HEAD_ACTOR_GREEDY (a two-atom network read as an actor).  sample == NULL: the greedy result of
+ * ble_qnet_forward_grouped_f32.  Otherwise row p R + r draws with the key (seed, env_offset + p R + r, *step): what member p's own
+ * ble_ac_act_f32 on its R rows draws with env_offset + p R.  logp: device [P * R], required; pop->value and pop->probs are optional.
+ * BLE_E_INVALID_ARG before any HIP call: what ble_qnet_forward_grouped_f32 refuses; another head; NULL logp; a sample with a NULL step
+ * or env_offset < 0.
+ */
+int ble_ac_act_grouped_f32(const ble_qnet_grouped_f32* pop, const ble_ac_sample* sample, float* logp, void* stream);
 
 #ifdef __cplusplus
 }
