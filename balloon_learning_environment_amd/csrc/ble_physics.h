@@ -186,7 +186,7 @@ struct StrideK {
   double ra_t0, five, eleven, emit_b, emit_c;          // thermal_increment_f64
   double dry_mass;                                     // stride_pressure
   double lg5, lg4, lg3, ex4, ex3;                      // atm_temperature_advance
-  double acs_x0, forty;                                // acs_down_poly
+  double forty;                                        // acs_down_poly
   // ... and multiplicands / offsets whose scalar-register pairs the stride loop had to re-assemble (more constants than scalar registers)
   double t110, cond_tenth;                             // thermal_increment_f64
   double m_over_r, ten;                                // stride_pressure
@@ -198,7 +198,7 @@ BLE_FN StrideK stride_k_literal(double dry_mass = VehicleDefault::dry_mass, doub
   k.ra_t0 = kRayleighT0; k.five = 5.0; k.eleven = 11.0; k.emit_b = kEmitB; k.emit_c = kEmitC;
   k.dry_mass = dry_mass;
   k.lg5 = 0.2; k.lg4 = -0.25; k.lg3 = 1.0 / 3.0; k.ex4 = 1.0 / 24.0; k.ex3 = 1.0 / 6.0;
-  k.acs_x0 = 0.05; k.forty = 40.0;
+  k.forty = 40.0;
   k.t110 = 110.4; k.cond_tenth = kCondTenth;
   k.m_over_r = kAirMolarMassD / kGasConstantD; k.ten = 10.0;
   k.lg6 = -1.0 / 6.0; k.ex5 = 1.0 / 120.0;
@@ -210,7 +210,7 @@ BLE_FN StrideK stride_k_vreg(double dry_mass = VehicleDefault::dry_mass, double 
   k.ra_t0 = d_vreg(k.ra_t0); k.five = d_vreg(k.five); k.eleven = d_vreg(k.eleven); k.emit_b = d_vreg(k.emit_b); k.emit_c = d_vreg(k.emit_c);
   k.dry_mass = d_vreg(k.dry_mass);
   k.lg5 = d_vreg(k.lg5); k.lg4 = d_vreg(k.lg4); k.lg3 = d_vreg(k.lg3); k.ex4 = d_vreg(k.ex4); k.ex3 = d_vreg(k.ex3);
-  k.acs_x0 = d_vreg(k.acs_x0); k.forty = d_vreg(k.forty);
+  k.forty = d_vreg(k.forty);
   k.t110 = d_vreg(k.t110); k.cond_tenth = d_vreg(k.cond_tenth);
   k.m_over_r = d_vreg(k.m_over_r); k.ten = d_vreg(k.ten);
   k.lg6 = d_vreg(k.lg6); k.ex5 = d_vreg(k.ex5);
@@ -577,22 +577,27 @@ BLE_FN double atm_height_rel_boundary_f64(double q, double pb, double r_pb, doub
   const double em1 = y * d_fma(y, d_fma(y, d_fma(y, 1.0 / 24.0, 1.0 / 6.0), 0.5), 1.0);
   return (tb * em1) * d_rcp(lapse);          // (reciprocal + Newton, 2e-15: a true fp64 division is ~30 instructions)
 }
-// 1 / (H(p + d) - H(p)), d = +-1 Pa (balloon.py:438-442), fp64.  j = layer of p in the
-// window, t_p = T(p), rp = 1/p.  The cancellation-free form
+// sqrt(a) / (H(p + d) - H(p)), d = +-1 Pa (balloon.py:438-442), fp64: the climb rate sqrt(a) over the height step, the only form
+// in which the stride uses either.  j = layer of p in the window, t_p = T(p), rp = 1/p, a > 0.  The cancellation-free form
 //   dH = (T(p)/L) expm1(k log1p(d/p)),  k = -R_d L / g
 // replaces the difference of two ~17 km heights; when p and p + d lie on different sides
 // of a layer transition both heights are measured from that transition.
-BLE_FN double atm_inv_delta_height_f64(const AtmWindow& w, int j, double lapse, double kl, double cur_hi, double cur_lo,
-                                       double p, double rp, double d, double t_p, const StrideK& K = stride_k_literal()) {
+// With wd = T(p) expm1(..):  sqrt(a) L / wd = L copysign(a rsqrt(a wd^2), wd) -- ONE reciprocal square root where sqrt(a) and 1 / wd
+// took a seed and a Newton step each.  Range of its argument: |wd| is 4.9e-4 (108.9 kPa, L = -0.0058 K/m) ... 7e-3 (1 kPa), so a wd^2
+// is 2.4e-37 at the caller's floor a = 1e-30 and below 1 at a = 6 700 (82 m/s: the corners of the tests' widest state domain; a balloon
+// reaches 5 m/s): normal numbers, and normal in float32 too, which the host build's seed goes through.
+BLE_FN double atm_rate_over_delta_height_f64(const AtmWindow& w, int j, double lapse, double kl, double cur_hi, double cur_lo,
+                                             double p, double rp, double d, double t_p, double a, const StrideK& K = stride_k_literal()) {
   const double x = d * rp;                      // |x| ~ 1e-4: log1p to x^3 (next term 2.5e-13 relative)
   const double lg = x * d_fma(x, d_fma(x, K.lg3, -0.5), 1.0);
   const bool iso = lapse == 0.0;
   const double y = kl * lg;                     // kl = (-R_d / g) lapse; |y| ~ 2e-5: expm1 to y^3
   const double em1 = y * d_fma(y, d_fma(y, K.ex3, 0.5), 1.0);
-  // dH = t_p em1 / L  ->  1/dH; in an isothermal layer (the one at 47-51 km: no balloon flies there, the reference's atmosphere has it)
-  // dH = -(R/g) t_p lg, rare path (the common expression gives NaN there: 0 * 1/0, replaced)
-  double inv = lapse * d_rcp(t_p * em1);
-  if (__builtin_expect(wave_any(iso), 0)) if (iso) inv = d_rcp(t_p * ((-kAirSpecificGasD / 9.80665) * lg));
+  // dH = t_p em1 / L; in an isothermal layer (the one at 47-51 km: no balloon flies there, the reference's atmosphere has it)
+  // dH = -(R/g) t_p lg, rare path (the common expression gives NaN there: 0 * rsqrt(0), replaced)
+  const double wd = t_p * em1;
+  double inv = lapse * __builtin_copysign(a * d_rsqrt(a * (wd * wd)), wd);
+  if (__builtin_expect(wave_any(iso), 0)) if (iso) inv = d_rcp(t_p * ((-kAirSpecificGasD / 9.80665) * lg)) * d_sqrt_rs(a);
   const double q = p + d;
   // cur_hi / cur_lo: the transition pressures that bound the layer of p (+-inf if unknown/far)
   const bool below = q > cur_hi;            // q in the layer with higher pressure
@@ -605,7 +610,7 @@ BLE_FN double atm_inv_delta_height_f64(const AtmWindow& w, int j, double lapse, 
     const double lapse_q = pick3(below ? j - 1 : j + 1, w.lapse_m1, w.lapse_0, w.lapse_p1);
     const double dh = atm_height_rel_boundary_f64(q, pb, r_pb, tb, lapse_q) -
                       atm_height_rel_boundary_f64(p, pb, r_pb, tb, lapse);
-    inv = d_rcp(dh);
+    inv = d_rcp(dh) * d_sqrt_rs(a);
   }
   return inv;
 }
@@ -1274,9 +1279,14 @@ BLE_FN double thermal_increment_f64(double vol, double yc, double t_int, double 
   // there the twelfth root is fp64 too)
   // kExactTwelfthRoot: the fp32 root (1e-7 relative) refined by one Newton step on y^12 = x in fp64 -- 5e-14, a quarter
   // of the instructions of exp(log(x) / 12)
-  const double tw_arg = d_fma(2.69e-8, ra, 1.0);
-  double tw = (double)f_pow((float)tw_arg, 1.0f / 12.0f);
-  if (kExactTwelfthRoot) {
+  // The fp32 root's argument is formed in fp32 from the (float)ra that d_inv_root4 converts anyway: its rounding (6e-8 of the
+  // argument, 5e-9 of the root) is below the root's own 1e-7, and an fp64 fma and a conversion go.
+  double tw;
+  if (!kExactTwelfthRoot) {
+    tw = (double)f_pow(f_fma(2.69e-8f, (float)ra, 1.0f), 1.0f / 12.0f);
+  } else {
+    const double tw_arg = d_fma(2.69e-8, ra, 1.0);
+    tw = (double)f_pow((float)tw_arg, 1.0f / 12.0f);
     const double y2 = tw * tw, y4r = y2 * y2, y8 = y4r * y4r;
     tw = d_fma(-tw * (1.0 / 12.0), d_fma(y8 * y4r, d_rcp(tw_arg), -1.0), tw);       // y - y (y^12 / x - 1) / 12
   }
@@ -1356,8 +1366,16 @@ BLE_FN double acs_efficiency_f64(const float* tab, double prm1, double power) {
 // w0, w1 of the power [W] in t = prm1 - (0.05 + 0.025 i), t clamped to [0, 0.025] (flat outside the table,
 // acs.py:44-68 `fill_value=None` / the flat end segments of the power curve).  Identical to the two-table
 // form to 1e-16 (tests: probe vs oracle); 3 LDS reads + 5 FMAs instead of two dependent table walks.
-constexpr int kAcsPolyDoubles = 12 * 6;
-// The 12 x 6 coefficients are a COMPILE-TIME table (constexpr evaluation: plain IEEE double arithmetic, no FMA
+// Every row carries its node position 0.05 + 0.025 i as a seventh double (an eighth pads the row to two 32-byte halves): the
+// polynomial's argument needs it, and reading it with the coefficients replaces a conversion of the index and an fma per stride.
+// The values are fma(0.025, i, 0.05) as the device rounds it -- i = 5, 7 and 10 differ from the two-rounding sum, so they are
+// spelled out (tests/test_stride_seeds_host.py holds them to the fma bit for bit).
+constexpr int kAcsPolyRow = 8;
+constexpr int kAcsPolyDoubles = 12 * kAcsPolyRow;
+constexpr double kAcsNode[12] = {0x1.999999999999ap-5, 0x1.3333333333334p-4, 0x1.999999999999ap-4, 0x1.0000000000000p-3,
+                                 0x1.3333333333334p-3, 0x1.6666666666667p-3, 0x1.999999999999ap-3, 0x1.ccccccccccccdp-3,
+                                 0x1.0000000000000p-2, 0x1.199999999999ap-2, 0x1.3333333333334p-2, 0x1.4cccccccccccdp-2};
+// The 12 rows are a COMPILE-TIME table (constexpr evaluation: plain IEEE double arithmetic, no FMA
 // contraction, the same numbers on the device and in the host build of the test tooling); the transition copies it from
 // constant memory into LDS at kernel entry instead of rebuilding it per launch.
 struct AcsPolyTable { double c[kAcsPolyDoubles]; };
@@ -1368,8 +1386,9 @@ constexpr double acs_power_constexpr(double prm1) {        // acs.py:44-50 == ac
 constexpr AcsPolyTable make_acs_poly_table() {
   AcsPolyTable t = {};
   for (int i = 0; i < 12; ++i) {
-    double* c = t.c + 6 * i;
+    double* c = t.c + kAcsPolyRow * i;
     const double x0 = 0.05 + 0.025 * (double)i;
+    c[6] = kAcsNode[i];
     const double w0 = acs_power_constexpr(x0), w1 = (acs_power_constexpr(x0 + 0.025) - w0) * 40.0;
     const double wm = acs_power_constexpr(x0 + 0.0125);
     double fy = (wm - 100.0) * 0.01;
@@ -1389,11 +1408,18 @@ constexpr AcsPolyTable make_acs_poly_table() {
 }
 constexpr AcsPolyTable kAcsPolyValues = make_acs_poly_table();
 BLE_CONST_TABLE AcsPolyTable kAcsPoly = kAcsPolyValues;
+// kNodeFromTable = false: the node position from the index instead, fma(0.025, i, 0.05) -- the table's very bits; for a wave that waits on
+// nothing else, where the table read would sit on its critical path (ble_step_split.h)
+template <bool kNodeFromTable = true>
 BLE_FN void acs_down_poly(const double* poly, double prm1, double* power_w, double* mdot, const StrideK& K = stride_k_literal()) {
-  int i = (int)((prm1 - K.acs_x0) * K.forty);      // truncation: [-1, 1) -> 0
+  // the interval: (prm1 - 0.05) x 40 as one fma with the inline constant -2 (no 0.05 to keep in a register pair across the strides; an
+  // argument within an ulp of a node may land in the neighbouring interval, whose cubic meets this one there);  truncation towards
+  // zero: (-1, 1) -> 0, and everything below the table (down to -2 at prm1 = 0) is clamped to interval 0 like before
+  int i = (int)d_fma(prm1, K.forty, -2.0);
   i = i < 0 ? 0 : (i > 11 ? 11 : i);
-  const double t = d_max(d_min(prm1 - d_fma(0.025, (double)i, K.acs_x0), 0.025), 0.0);
-  const double* c = poly + 6 * i;
+  const double* c = poly + kAcsPolyRow * i;
+  const double node = kNodeFromTable ? c[6] : d_fma(0.025, (double)i, 0.05);
+  const double t = d_max(d_min(prm1 - node, 0.025), 0.0);
   *mdot = d_fma(d_fma(d_fma(c[3], t, c[2]), t, c[1]), t, c[0]);
   *power_w = d_fma(c[5], t, c[4]);
 }

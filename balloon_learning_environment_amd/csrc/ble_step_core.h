@@ -151,9 +151,11 @@ BLE_FN double stride_pressure(const AtmWindow& win, const LayerCursor& lc, doubl
   const double dir = __builtin_copysign(1.0, num);
   // dh/dt = dir sqrt(|2 (rho V - m) g / (rho drag)|) = dir sqrt(2 g |num| (R/M) (1/p) V^(-2/3) / cod); drag_arg = 2 g (R/M) / cod (cod = 0.25: 8 g R/M)
   const double arg = drag_arg * __builtin_fabs(num) * rp * (yc * yc);
-  const double dh_dt = d_sqrt_rs(d_max(arg, 1e-30));                      // arg == 0 (exact equilibrium): 1e-15 m/s, p unchanged
-  const double inv_dh = atm_inv_delta_height_f64(win, lc.lay, lc.lapse_cur, lc.kl_cur, lc.cur_hi, lc.cur_lo, p, rp, dir, t_at_p, K);
-  return d_fma(inv_dh * dh_dt, K.ten, p);                                 // dir * dir == 1
+  // |dh/dt| = sqrt(arg) and 1 / dH are only ever used as their product: one reciprocal square root for both
+  // (arg == 0, exact equilibrium: 1e-15 m/s, p unchanged)
+  const double rate = atm_rate_over_delta_height_f64(win, lc.lay, lc.lapse_cur, lc.kl_cur, lc.cur_hi, lc.cur_lo, p, rp, dir, t_at_p,
+                                                     d_max(arg, 1e-30), K);
+  return d_fma(rate, K.ten, p);                                           // dir * dir == 1
 }
 // step 3: internal temperature (balloon.py:451-467)
 BLE_FN double stride_internal_temperature(double vol, double yc, double t_int, double t_amb, double p, float flux, float att,
@@ -162,6 +164,7 @@ BLE_FN double stride_internal_temperature(double vol, double yc, double t_int, d
 }
 // step 5: ACS (balloon.py:487-519); both branches evaluated, selected per lane.  fp64: the mass flow changes rho V - m by
 // ~1e-2 kg per stride, an fp32 rounding of it (~1e-9 kg) is amplified like the thermal increment's.
+template <bool kNodeFromTable = true>
 BLE_FN void stride_acs(const double* acs_poly, int eff, double sp, double p, double rp, double t_int, float* acs_w, double* mdot_d,
                        const StrideK& K, double valve_k = VehicleDefault::valve_k) {
   // -0.62 A sqrt(2 sp rho_gas), rho_gas = (sp + p) M / (R T_int):  sqrt(a / T) = a rsqrt(a T)
@@ -169,7 +172,7 @@ BLE_FN void stride_acs(const double* acs_poly, int eff, double sp, double p, dou
   const double mdot_up = (valve_k * a2) * d_rsqrt(a2 * t_int);                        // valve_k = -0.62 A;  sp == 0: -1e-17 kg/s
   const double prm1 = d_max(sp * rp, 0.0);                // pressure_ratio - 1 = max(sp, 0) / p (balloon.py:247-250; rp > 0)
   double w_down, mdot_down;
-  acs_down_poly(acs_poly, prm1, &w_down, &mdot_down, K);
+  acs_down_poly<kNodeFromTable>(acs_poly, prm1, &w_down, &mdot_down, K);
   *acs_w = eff == kDown ? (float)w_down : 0.0f;
   *mdot_d = eff == kUp ? mdot_up : (eff == kDown ? mdot_down : 0.0);
 }

@@ -1,6 +1,6 @@
 """Instruction-class histogram of the fused step kernel's stride loop and of its per-step part (no GPU needed):
 
-    python profiles/isa_histogram.py [REV ...] [--kernel SUBSTRING] [--dump | --dump-step]
+    python profiles/isa_histogram.py [REV ...] [--kernel SUBSTRING] [--dump | --dump-step | --dump-helper] [--cost]
 
 Every REV (a git revision; `tree` = the working tree, the default) is compiled to gfx950 assembly with the flags of
 balloon_learning_environment_amd/_lib.py::build (profiles/isa_compare.py::assemble), the kernel whose symbol contains SUBSTRING
@@ -21,7 +21,16 @@ source.
 A kernel with a helper wave (--kernel ble_step_helper_kernel, csrc/ble_step_helper.h) holds TWO role loops.  The main wave's are found as
 above (its stride carries the fp64).  The helper wave's step loop is the other outermost loop of the kernel, and its record loop -- one
 SunRecord per iteration, i.e. per stride -- the loop inside it with the most instructions (the others are the polling loops of the
-hand-over, a handful of instructions each).  A second table gives the helper's record loop and per-step part."""
+hand-over, a handful of instructions each).  A second table gives the helper's record loop and per-step part.
+
+--cost weights the hot paths with the issue costs of profiles/r02_microbench.md (`valu_op_cost`, ns per wave instruction) and prints them
+per stride and per agent step (18 strides + the per-step part) in two columns:
+  * ONE WAVE: what a wave alone on its SIMD needs to issue the path -- 2.1 ns per instruction of any kind, 7.0 for an fp64 seed
+    (v_rcp / v_rsq / v_sqrt_f64), 4.15 for an fp32 transcendental, 3.1 for a conversion to or from fp64;
+  * TWO WAVES: the VALU pipe time of the path when a second wave shares the SIMD -- 2.05 ns per fp64 instruction, 6.85 per fp64 seed, 3.5 per
+    fp32 transcendental, 1.6 per conversion to or from fp64, 1.05 per other vector instruction; scalar instructions, branches, waits, LDS
+    and memory instructions do not occupy the pipe.
+With a helper wave the two-waves column also gets the sum over both waves: the pipe time M and S need together per stride and per step."""
 import os
 import re
 import subprocess
@@ -144,6 +153,52 @@ def hot_path(body, parents, header, inner=None):
     k += 1
 
 
+SEEDS_F64 = ('v_rcp_f64', 'v_rsq_f64', 'v_sqrt_f64')
+TRANS_F32 = ('v_exp_f32', 'v_log_f32', 'v_rcp_f32', 'v_rsq_f32', 'v_sqrt_f32', 'v_sin_f32', 'v_cos_f32', 'v_rcp_iflag_f32')
+COST_ROWS = ['fp64 seeds', 'fp32 transcendentals', 'conversions to / from fp64', 'other fp64', 'other vector', 'not on the VALU pipe']
+COST_NS = {'fp64 seeds': (7.0, 6.85), 'fp32 transcendentals': (4.15, 3.5), 'conversions to / from fp64': (3.1, 1.6), 'other fp64': (2.1, 2.05),
+           'other vector': (2.1, 1.05), 'not on the VALU pipe': (2.1, 0.0)}       # (one wave per SIMD, two waves per SIMD)
+
+
+def cost_class(op: str) -> str:
+  base = op.split('_e32')[0].split('_e64')[0].split('_sdwa')[0].split('_dpp')[0]
+  if base in SEEDS_F64:
+    return 'fp64 seeds'
+  if base in TRANS_F32:
+    return 'fp32 transcendentals'
+  if op.startswith('v_cvt') and 'f64' in op:
+    return 'conversions to / from fp64'
+  if op.startswith('v_'):
+    return 'other fp64' if ('_f64' in op or '_b64' in op) else 'other vector'
+  return 'not on the VALU pipe'
+
+
+def cost(body, path):
+  """{row: (count, ns one wave, ns two waves)} of a hot path, and the totals"""
+  rows = {r: [0, 0.0, 0.0] for r in COST_ROWS}
+  for k in path:
+    r = cost_class(body[k][1].split()[0])
+    rows[r][0] += 1; rows[r][1] += COST_NS[r][0]; rows[r][2] += COST_NS[r][1]
+  return rows, sum(v[1] for v in rows.values()), sum(v[2] for v in rows.values())
+
+
+def report_cost(title, body, stride_path, strides_per_iteration, step_path):
+  """the cost-weighted hot path per stride and per agent step (18 strides + the per-step part); returns (one wave, two waves) per step"""
+  rs, s1, s2 = cost(body, stride_path)
+  rp, p1, p2 = cost(body, step_path)
+  d = float(strides_per_iteration)
+  print(f'{title}: cost-weighted hot path (ns; `valu_op_cost` of r02_microbench.md)')
+  print('| Class | Per stride: count | one wave | two waves | Per-step part: count | one wave | two waves |')
+  print('|---|---|---|---|---|---|---|')
+  for r in COST_ROWS:
+    print(f'| {r} | {rs[r][0] / d:g} | {rs[r][1] / d:.1f} | {rs[r][2] / d:.1f} | {rp[r][0]} | {rp[r][1]:.1f} | {rp[r][2]:.1f} |')
+  print(f'| **all** | {len(stride_path) / d:g} | {s1 / d:.1f} | {s2 / d:.1f} | {len(step_path)} | {p1:.1f} | {p2:.1f} |')
+  step1, step2 = 18 * s1 / d + p1, 18 * s2 / d + p2
+  print(f'per agent step (18 strides + the per-step part): one wave {step1 / 1e3:.2f} us, two waves (pipe time) {step2 / 1e3:.2f} us')
+  print()
+  return step1, step2
+
+
 def histogram(body, path):
   h = dict.fromkeys(CLASSES, 0)
   for k in path:
@@ -197,7 +252,7 @@ def analyse_helper_role(body, parents, main_step):
   return hot_path(body, parents, record), hot_path(body, parents, step, inner=record)
 
 
-def report_helper_role(body, record_path, step_path) -> None:
+def report_helper_role(body, record_path, step_path, with_cost=False):
   hr, hp = histogram(body, record_path), histogram(body, step_path)
   print(f'helper wave: record loop .s lines {body[record_path[0]][0]}-{body[record_path[-1]][0]} (one record = one stride per iteration)')
   print('| Class | Per record (stride) | Per-step part |')
@@ -208,9 +263,10 @@ def report_helper_role(body, record_path, step_path) -> None:
   vec = lambda h: sum(v for c, v in h.items() if c in CLASSES[:9])
   print(f'vector (incl. LDS, memory) / scalar per record: {vec(hr)} / {len(record_path) - vec(hr)}; per-step part: {vec(hp)} / {len(step_path) - vec(hp)}')
   print()
+  return report_cost('helper wave', body, record_path, 1, step_path) if with_cost else None
 
 
-def report(rev: str, asm: str, key: str, dump: bool) -> None:
+def report(rev: str, asm: str, key: str, dump: bool, with_cost: bool = False) -> None:
   name, body, stride_path, step_path = analyse(asm, key)
   hs, hp = histogram(body, stride_path), histogram(body, step_path)
   print(f'## {rev}: {name[:90]}')
@@ -223,10 +279,14 @@ def report(rev: str, asm: str, key: str, dump: bool) -> None:
   vec = lambda h: sum(v for c, v in h.items() if c in CLASSES[:9])
   print(f'vector (incl. LDS, memory) / scalar per two strides: {vec(hs)} / {len(stride_path) - vec(hs)}; per-step part: {vec(hp)} / {len(step_path) - vec(hp)}')
   print()
+  main_cost = report_cost('main wave', body, stride_path, 2, step_path) if with_cost else None
   _, _, parents = kernel_body(asm, key)
   helper = analyse_helper_role(body, parents, body[step_path[0]][2] if body[step_path[0]][2] else None) if 'helper' in name else None
   if helper:
-    report_helper_role(body, *helper)
+    helper_cost = report_helper_role(body, *helper, with_cost=with_cost)
+    if with_cost:
+      print(f'both waves, pipe time per agent step (two-waves column, main + helper): {(main_cost[1] + helper_cost[1]) / 1e3:.2f} us')
+      print()
     if dump == 'helper':
       for k in helper[0]:
         print(f'{body[k][0]:7d}  {classify(body[k][1].split()[0]):16s} {body[k][1]}')
@@ -242,12 +302,13 @@ def main() -> int:
   if '--kernel' in args:
     key = args[args.index('--kernel') + 1]
     del args[args.index('--kernel'):args.index('--kernel') + 2]
+  with_cost = '--cost' in args
   revs = [a for a in args if not a.startswith('--')] or ['tree']
   with tempfile.TemporaryDirectory() as tmp:
     for rev in revs:
       tree = ROOT
       if rev.endswith('.s'):             # an assembly file made earlier
-        report(rev, open(rev).read(), key, dump)
+        report(rev, open(rev).read(), key, dump, with_cost)
         continue
       if rev != 'tree':
         tree = os.path.join(tmp, re.sub(r'\W', '_', rev))
@@ -255,7 +316,7 @@ def main() -> int:
         archive = subprocess.check_output(['git', '-C', ROOT, 'archive', rev, 'balloon_learning_environment_amd/csrc', 'include'])
         subprocess.run(['tar', 'x', '-C', tree], input=archive, check=True)
       out = os.path.join(tempfile.gettempdir(), 'isa_histogram_' + re.sub(r'\W', '_', rev) + '.s')
-      report(rev, assemble(tree, out), key, dump)
+      report(rev, assemble(tree, out), key, dump, with_cost)
   return 0
 
 
