@@ -3,10 +3,12 @@
 //
 //   ble_gp_fit_kernel           one workgroup (4 waves) per environment: phases 0-2 of ble_gp_query_kernel -- the window at the anchor
 //                               time, K = L L^T, W = L^-1, alpha = K^-1 y -- and then, instead of query points, the compacted window
-//                               and alpha stored to the environment's slab in HBM.  A copy of those phases, on purpose: the query
-//                               kernel keeps its instructions (the note above ble_step_helper_kernel).
+//                               and alpha stored to the environment's slab in HBM.  The phases are ble_gp_factor.h's functions, the
+//                               ones the query kernel calls: one window rule and one factor for both.
 //   gp_belief_mean              the lane function: sum_i k(loc_i, (x, y, p, t)) alpha_i for both components, fp64, i ascending, every
 //                               product an explicit d_fma, rounded to fp32 once.  No factor, no barrier: 120 kernel evaluations.
+//                               One body, gp_scenario_correction: (loc, alpha) as two pointers, to which the scenario winds pass
+//                               alpha^m; gp_belief_mean calls it with the alpha of its slab.
 //   ble_gp_belief_wind_kernel   one lane per environment at caller-chosen points (the shape of ble_wind_noise_kernel): what ble_step_f32
 //                               takes as noise_uv.
 //   ble_rollout_belief_kernel   ble_rollout_kernel's body (a fourth copy of the step kernel's, for the reason given there) with
@@ -57,14 +59,15 @@ BLE_FN double gp_belief_kernel(double dx, double dy, double dp, double dt, const
   return d_ldexp(t * q, nn >> 6);
 }
 
-// The belief's mean forecast ERROR (u, v) [m/s] at (x, y, p, t_elapsed_s): the forecast is added where the wind is used, as the noise
-// term is.  slab: the environment's (16-byte aligned); n_obs: its window, 0 -> exactly +0.0f, < 0 -> NaN (a window the ring could not
-// tell: ble_gp_fit_kernel); n_trip: a multiple of 4, >= n_obs, <= 120 -- any such value gives the same bits (the note at the top);
-// tab: gp_belief_table_entry's 64 entries.  The window and alpha are frozen at the fit's anchor: only the query's time moves.
-BLE_FN void gp_belief_mean(const double* __restrict__ slab, int n_obs, int n_trip, float x, float y, float p, int32_t t_elapsed_s,
-                           const double* tab, float* u, float* v) {
-  const double* loc = (const double*)__builtin_assume_aligned(slab, 16);
-  const double* alpha = loc + kBeliefAlphaAt;
+// The posterior mean of the forecast ERROR (u, v) [m/s] at (x, y, p, t_elapsed_s): the forecast is added where the wind is used, as the
+// noise term is.  loc: the window (the front of an environment's slab: 16-byte aligned); alpha: K^-1 y of that window, u and v
+// interleaved (16-byte aligned); n_obs: the window, 0 -> exactly +0.0f, < 0 -> NaN (a window the ring could not tell:
+// ble_gp_fit_kernel); n_trip: a multiple of 4, >= n_obs, <= 120 -- any such value gives the same bits (the note at the top); tab:
+// gp_belief_table_entry's 64 entries.  The window and alpha are frozen at the fit's anchor: only the query's time moves.
+BLE_FN void gp_scenario_correction(const double* __restrict__ loc_, const double* __restrict__ alpha_, int n_obs, int n_trip, float x,
+                                   float y, float p, int32_t t_elapsed_s, const double* tab, float* u, float* v) {
+  const double* loc = (const double*)__builtin_assume_aligned(loc_, 16);
+  const double* alpha = (const double*)__builtin_assume_aligned(alpha_, 16);
   const double xq = (double)x * kBeliefScaleXY, yq = (double)y * kBeliefScaleXY, pq = (double)p * kBeliefScaleP,
                tq = (double)t_elapsed_s * kBeliefScaleT;
   double su = 0.0, sv = 0.0;
@@ -86,6 +89,11 @@ BLE_FN void gp_belief_mean(const double* __restrict__ slab, int n_obs, int n_tri
   *u = n_obs < 0 ? fnan : (n_obs == 0 ? 0.0f : (float)su);
   *v = n_obs < 0 ? fnan : (n_obs == 0 ? 0.0f : (float)sv);
 }
+// the belief's: the window and alpha of one slab
+BLE_FN void gp_belief_mean(const double* __restrict__ slab, int n_obs, int n_trip, float x, float y, float p, int32_t t_elapsed_s,
+                           const double* tab, float* u, float* v) {
+  gp_scenario_correction(slab, slab + kBeliefAlphaAt, n_obs, n_trip, x, y, p, t_elapsed_s, tab, u, v);
+}
 
 // the loop's trip count for a window of n_obs (whatever the word holds: the slab is never overrun)
 BLE_FN int gp_belief_trip(int n_obs) {
@@ -97,7 +105,8 @@ BLE_FN int gp_belief_trip(int n_obs) {
 
 #if defined(__HIPCC__)
 // ---------------------------------------------------------------------------------------------------------------- the kernels
-// Included by ble_kernels.hip after ble_rollout.h: ble_observe.h, ble_gp_query.h (GpQueryShared), kStepBlock and report_flags are there.
+// Included by ble_kernels.hip after ble_rollout.h: ble_observe.h, ble_gp_query.h (GpQueryShared, ble_gp_factor.h), kStepBlock and report_flags
+// are there.
 namespace ble {
 
 // struct ble_gp_belief (include/ble_abi.h) as the kernels take it
@@ -134,155 +143,27 @@ __global__ __launch_bounds__(kObsBlock, 2) void ble_gp_fit_kernel(GpHistory hist
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   uint32_t flags = 0;
 
-  // ---- phase 0: the window at the anchor time (ble_gp_query_kernel's rules)
-  int count = hist.count[env];
-  if (reset_mask != nullptr && reset_mask[env] != 0) count = 0;       // a history restart is pending
+  // ---- phases 0 - 2 (ble_gp_factor.h) at the anchor time: the window, the exit without a posterior, the window compacted with y in sh.z, the factor, alpha
   const int32_t tq = time_s[env];
-  const int m = count < kGpCapacity ? count : kGpCapacity;
-  const float* h_xyp = hist.xyp + env * (kGpCapacity * 3);
-  const int32_t* h_t = hist.elapsed_s + env * kGpCapacity;
-  const float* h_err = hist.err_uv + env * (kGpCapacity * 2);
-  int32_t ta = tq, tb = tq;
-  if (lane < m) ta = h_t[(count - m + lane) % kGpCapacity];
-  if (lane + 64 < m) tb = h_t[(count - m + lane + 64) % kGpCapacity];
-  const int64_t age_a = (int64_t)ta - (int64_t)tq, age_b = (int64_t)tb - (int64_t)tq;
-  const unsigned long long b0 = __ballot(lane < m && (age_a < 0 ? -age_a : age_a) < kGpHorizonS);       // strict, like the reference
-  const unsigned long long b1 = __ballot(lane + 64 < m && (age_b < 0 ? -age_b : age_b) < kGpHorizonS);
-  int n_obs = __popcll(b0) + __popcll(b1);
-  int drop = 0;
-  if (n_obs > kGpMax) { drop = n_obs - kGpMax; n_obs = kGpMax; flags |= kFlagGpWindow; }
-  // observations the ring has evicted may belong to the window when its oldest entry does: the query kernel's NaN case
-  if (count > kGpCapacity && (b0 & 1ull) != 0) {
-    const int32_t t_newest = h_t[(count - 1) % kGpCapacity];
-    if (!(drop > 0 && tq >= t_newest)) {
-      if (tid == 0 && err_flags != nullptr) atomicOr(err_flags, (uint32_t)kFlagGpWindow);
-      gp_fit_empty(b, env, tid, -1);
-      return;
-    }
-  }
-  if (n_obs == 0) {         // (uniform over the workgroup: no barrier has been reached)
-    gp_fit_empty(b, env, tid, 0);
+  const GpWindow w = gp_window(hist, reset_mask, env, tq, lane);
+  const int n_obs = w.n_obs;
+  if (w.cut) flags |= kFlagGpWindow;
+  const bool untold = gp_window_untold(hist, env, tq, w);
+  if (untold || n_obs == 0) {         // no posterior (uniform over the workgroup: no barrier has been reached)
+    if (untold && tid == 0 && err_flags != nullptr) atomicOr(err_flags, (uint32_t)kFlagGpWindow);
+    gp_fit_empty(b, env, tid, untold ? -1 : 0);
     return;
   }
-
-  // ---- compact the window into LDS (chronological), in units of the length scales; tables
-  if (wave == 2) sh.exp2_frac[lane] = kGpSigma2 * d_exp_fast((double)lane * (6.93147180559945286227e-01 / 64.0));
-  if (tid < kGpRows) {
-    sh.loc[tid][0] = 0.0; sh.loc[tid][1] = 0.0; sh.loc[tid][2] = 0.0; sh.loc[tid][3] = 0.0;
-    sh.z[0][tid] = 0.0; sh.z[1][tid] = 0.0; sh.alpha[0][tid] = 0.0; sh.alpha[1][tid] = 0.0;
-    sh.inv_diag[tid] = 0.0; sh.part[tid] = 0.0;
-  }
-  if (tid < 128) sh.W[kCholTri + tid] = 0.0;
+  gp_clear(sh, tid, lane, wave);
   __syncthreads();
-  if (wave < 2) {
-    const unsigned long long b_mine = wave == 0 ? b0 : b1;
-    const int e = tid;                                  // ring entry of this lane (waves 0 and 1: entries 0 .. 127)
-    if (((b_mine >> lane) & 1ull) != 0) {
-      const int at = __popcll(b_mine & ((1ull << lane) - 1ull)) + (wave == 1 ? __popcll(b0) : 0) - drop;
-      if (at >= 0) {
-        const int slot = (count - m + e) % kGpCapacity;
-        sh.loc[at][0] = (double)h_xyp[slot * 3] * (kGpKappa / 357000.0);
-        sh.loc[at][1] = (double)h_xyp[slot * 3 + 1] * (kGpKappa / 357000.0);
-        sh.loc[at][2] = (double)h_xyp[slot * 3 + 2] * (kGpKappa / 326.0);
-        sh.loc[at][3] = (double)h_t[slot] * (kGpKappa / 34560.0);
-        sh.z[0][at] = (double)h_err[slot * 2]; sh.z[1][at] = (double)h_err[slot * 2 + 1];
-      }
-    }
-  }
+  gp_compact(sh, hist, env, w, tid, lane, wave, [&](int at, float, float, float, int32_t, float err_u, float err_v) {
+    sh.z[0][at] = (double)err_u; sh.z[1][at] = (double)err_v;
+  });
   __syncthreads();
-
-  // ---- phase 1a: K, packed
-  const int n_tri = tri(n_obs);
-  for (int e = tid; e < n_tri; e += kObsBlock) {
-    int i = (int)((__builtin_sqrtf(8.0f * (float)e + 1.0f) - 1.0f) * 0.5f);
-    while (tri(i) > e) --i;
-    while (tri(i + 1) <= e) ++i;
-    const int j = e - tri(i);
-    const double dx = sh.loc[i][0] - sh.loc[j][0], dy = sh.loc[i][1] - sh.loc[j][1], dp = sh.loc[i][2] - sh.loc[j][2],
-                 dt = sh.loc[i][3] - sh.loc[j][3];
-    const double k = gp_exp_neg_scaled(two_sqrt(dx * dx + dy * dy + dp * dp + dt * dt + 1e-300), sh.exp2_frac);
-    sh.W[e] = i == j ? kGpSigma2 + kGpNoise2 : k;
-  }
+  gp_factor(sh, n_obs, tid);
+  const double alpha_i = gp_solve(sh, n_obs, tid);
+  if ((tid & 127) < n_obs) sh.alpha[tid >> 7][tid & 127] = alpha_i;      // (zero beyond the window: gp_clear)
   __syncthreads();
-
-  // ---- phase 1b: K = L L^T, left-looking, column j per step; lane pair (i, i + 128) owns row i
-  {
-    const int i = tid & 127, h = tid >> 7;
-    double* ri = sh.W + tri(i);
-    double d_i = (i < n_obs) ? ri[i] : 1.0;
-    if (tid == 0) {
-      const double sq = __builtin_sqrt(d_i);
-      sh.inv_diag[0] = 1.0 / sq; ri[0] = sq;
-    }
-    __syncthreads();
-#pragma unroll 1
-    for (int j = 0; j + 1 < n_obs; ++j) {
-      const bool row = i > j && i < n_obs;
-      const double* rj = sh.W + tri(j);
-      const int kmid = j >> 1;
-      const int k0 = h ? kmid : 0, k1 = h ? j : kmid;
-      double s = 0.0;
-      if (row) {
-        for (int k = k0; k < k1; ++k) s = d_fma(ri[k], rj[k], s);
-        if (h) sh.part[i] = s;
-      }
-      __syncthreads();
-      if (row && !h) {
-        const double v = (ri[j] - (s + sh.part[i])) * sh.inv_diag[j];
-        ri[j] = v;
-        d_i = d_fma(-v, v, d_i);
-        if (i == j + 1) {
-          const double sq = __builtin_sqrt(d_i);
-          sh.inv_diag[i] = 1.0 / sq; ri[i] = sq;
-        }
-      }
-      __syncthreads();
-    }
-  }
-
-  // ---- phase 1c: W = L^-1 in place, row i per step; lane pair (j, j + 128) owns column j
-  {
-    const int j = tid & 127, h = tid >> 7;
-#pragma unroll 1
-    for (int i = 0; i < n_obs; ++i) {
-      const bool act = j < i;
-      const double* ri = sh.W + tri(i);
-      double s = 0.0;
-      if (act) {
-        const int kmid = (j + i + 1) >> 1;
-        const int k0 = h ? kmid : j, k1 = h ? i : kmid;
-        const double* wk = sh.W + tri(k0) + j;          // W[k][j], k = k0 ..: the next row's entry lies k + 1 further
-        for (int k = k0; k < k1; ++k) { s = d_fma(ri[k], *wk, s); wk += k + 1; }
-        if (h) sh.part[j] = s;
-      }
-      __syncthreads();
-      if (!h) {
-        if (act) sh.W[tri(i) + j] = -sh.inv_diag[i] * (s + sh.part[j]);
-        else if (j == i) sh.W[tri(i) + i] = sh.inv_diag[i];
-      }
-      __syncthreads();
-    }
-  }
-
-  // ---- phase 2: zeta = W y, alpha = W^T zeta -- component c on the lanes 128 c ..
-  {
-    const int i = tid & 127, c = tid >> 7;
-    double s = 0.0;
-    if (i < n_obs) {
-      const double* ri = sh.W + tri(i);
-      for (int k = 0; k <= i; ++k) s = d_fma(ri[k], sh.z[c][k], s);
-    }
-    __syncthreads();
-    if (i < n_obs) sh.z[c][i] = s;
-    __syncthreads();
-    if (i < n_obs) {
-      double t = 0.0;
-      const double* wk = sh.W + tri(i) + i;              // W[k][i], k = i ..
-      for (int k = i; k < n_obs; ++k) { t = d_fma(*wk, sh.z[c][k], t); wk += k + 1; }
-      sh.alpha[c][i] = t;
-    }
-    __syncthreads();
-  }
 
   // ---- the belief: the compacted window and alpha (zero beyond the window: loc and alpha were cleared above)
   double* slab = b.slab + env * b.stride;

@@ -18,6 +18,8 @@
 // The explicit inverse of the factor is safe in fp64 at cond(K) ~ 3e4 and turns the part of the work that grows with q into plain
 // MFMA products (144 per tile of 16 points at a full window) with no dependency between row blocks.  All GP algebra is fp64.
 // LDS 69 KB and <= 256 registers: two workgroups per CU.  DESIGN.md 3h.
+//
+// Phases 0 - 2 are ble_gp_factor.h's, shared with the two fits (ble_gp_belief.h, ble_scenarios.h); phase 3 is this kernel's own.
 #pragma once
 #include "ble_observe.h"
 
@@ -47,6 +49,10 @@ struct alignas(16) GpQueryShared {
 };
 static_assert(sizeof(GpQueryShared) <= 80 * 1024, "two workgroups per CU need <= 80 KB of LDS each");
 
+}  // namespace ble
+#include "ble_gp_factor.h"          // phases 0 - 2 over a GpQueryShared
+namespace ble {
+
 // the outputs of an environment without a posterior: the forecast alone (or 0) and `dev`, or NaN
 __device__ inline void gp_query_fill(const GpQueryArgs& a, int64_t env, int tid, int32_t tq, bool nan) {
   const float fnan = __builtin_nanf("");
@@ -69,162 +75,27 @@ __global__ __launch_bounds__(kObsBlock, 2) void ble_gp_query_kernel(GpHistory hi
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   uint32_t flags = 0;
 
-  // ---- phase 0: the window
-  int count = hist.count[env];
-  if (reset_mask != nullptr && reset_mask[env] != 0) count = 0;       // a history restart is pending: the next observe() starts afresh
+  // ---- phases 0 - 2 (ble_gp_factor.h): the window, the exit without a posterior, the window compacted with y in sh.z, the factor, alpha
   const int32_t tq = a.time_s[env];
-  const int m = count < kGpCapacity ? count : kGpCapacity;
-  const float* h_xyp = hist.xyp + env * (kGpCapacity * 3);
-  const int32_t* h_t = hist.elapsed_s + env * kGpCapacity;
-  const float* h_err = hist.err_uv + env * (kGpCapacity * 2);
-  // chronological entry e of the ring sits in slot (count - m + e) % 128; every wave reads the times of entries lane and lane + 64
-  int32_t ta = tq, tb = tq;
-  if (lane < m) ta = h_t[(count - m + lane) % kGpCapacity];
-  if (lane + 64 < m) tb = h_t[(count - m + lane + 64) % kGpCapacity];
-  const int64_t age_a = (int64_t)ta - (int64_t)tq, age_b = (int64_t)tb - (int64_t)tq;
-  const unsigned long long b0 = __ballot(lane < m && (age_a < 0 ? -age_a : age_a) < kGpHorizonS);       // strict, like the reference
-  const unsigned long long b1 = __ballot(lane + 64 < m && (age_b < 0 ? -age_b : age_b) < kGpHorizonS);
-  int n_obs = __popcll(b0) + __popcll(b1);
-  int drop = 0;
-  if (n_obs > kGpMax) { drop = n_obs - kGpMax; n_obs = kGpMax; flags |= kFlagGpWindow; }
-  // Observations the ring has evicted may belong to the window when its oldest entry does.  They are older than everything in the
-  // ring: where the window is cut to its newest 120 for a query that is not earlier than the newest observation they would have
-  // been cut as well (that is ble_observe_kernel's own answer at that time); everywhere else the ring cannot tell: NaN.
-  if (count > kGpCapacity && (b0 & 1ull) != 0) {
-    const int32_t t_newest = h_t[(count - 1) % kGpCapacity];
-    if (!(drop > 0 && tq >= t_newest)) {
-      if (tid == 0 && err_flags != nullptr) atomicOr(err_flags, (uint32_t)kFlagGpWindow);
-      gp_query_fill(a, env, tid, tq, true);
-      return;
-    }
-  }
-  if (n_obs == 0) {         // (uniform over the workgroup: no barrier has been reached)
-    gp_query_fill(a, env, tid, tq, false);
+  const GpWindow w = gp_window(hist, reset_mask, env, tq, lane);
+  const int n_obs = w.n_obs;
+  if (w.cut) flags |= kFlagGpWindow;
+  const bool untold = gp_window_untold(hist, env, tq, w);
+  if (untold || n_obs == 0) {         // no posterior (uniform over the workgroup: no barrier has been reached)
+    if (untold && tid == 0 && err_flags != nullptr) atomicOr(err_flags, (uint32_t)kFlagGpWindow);
+    gp_query_fill(a, env, tid, tq, untold);
     return;
   }
-
-  // ---- compact the window into LDS (chronological), in units of the length scales; tables
-  if (wave == 2) sh.exp2_frac[lane] = kGpSigma2 * d_exp_fast((double)lane * (6.93147180559945286227e-01 / 64.0));
-  if (tid < kGpRows) {
-    sh.loc[tid][0] = 0.0; sh.loc[tid][1] = 0.0; sh.loc[tid][2] = 0.0; sh.loc[tid][3] = 0.0;
-    sh.z[0][tid] = 0.0; sh.z[1][tid] = 0.0; sh.alpha[0][tid] = 0.0; sh.alpha[1][tid] = 0.0;
-    sh.inv_diag[tid] = 0.0; sh.part[tid] = 0.0;
-  }
-  if (tid < 128) sh.W[kCholTri + tid] = 0.0;
+  gp_clear(sh, tid, lane, wave);
   __syncthreads();
-  if (wave < 2) {
-    const unsigned long long b_mine = wave == 0 ? b0 : b1;
-    const int e = tid;                                  // ring entry of this lane (waves 0 and 1: entries 0 .. 127)
-    if (((b_mine >> lane) & 1ull) != 0) {
-      const int at = __popcll(b_mine & ((1ull << lane) - 1ull)) + (wave == 1 ? __popcll(b0) : 0) - drop;
-      if (at >= 0) {
-        const int slot = (count - m + e) % kGpCapacity;
-        sh.loc[at][0] = (double)h_xyp[slot * 3] * (kGpKappa / 357000.0);
-        sh.loc[at][1] = (double)h_xyp[slot * 3 + 1] * (kGpKappa / 357000.0);
-        sh.loc[at][2] = (double)h_xyp[slot * 3 + 2] * (kGpKappa / 326.0);
-        sh.loc[at][3] = (double)h_t[slot] * (kGpKappa / 34560.0);
-        sh.z[0][at] = (double)h_err[slot * 2]; sh.z[1][at] = (double)h_err[slot * 2 + 1];
-      }
-    }
-  }
+  gp_compact(sh, hist, env, w, tid, lane, wave, [&](int at, float, float, float, int32_t, float err_u, float err_v) {
+    sh.z[0][at] = (double)err_u; sh.z[1][at] = (double)err_v;
+  });
   __syncthreads();
-
-  // ---- phase 1a: K, packed
-  const int n_tri = tri(n_obs);            // entries of the packed triangle (tri(i) is the start of row i)
-  for (int e = tid; e < n_tri; e += kObsBlock) {
-    int i = (int)((__builtin_sqrtf(8.0f * (float)e + 1.0f) - 1.0f) * 0.5f);
-    while (tri(i) > e) --i;
-    while (tri(i + 1) <= e) ++i;
-    const int j = e - tri(i);
-    const double dx = sh.loc[i][0] - sh.loc[j][0], dy = sh.loc[i][1] - sh.loc[j][1], dp = sh.loc[i][2] - sh.loc[j][2],
-                 dt = sh.loc[i][3] - sh.loc[j][3];
-    const double k = gp_exp_neg_scaled(two_sqrt(dx * dx + dy * dy + dp * dp + dt * dt + 1e-300), sh.exp2_frac);
-    sh.W[e] = i == j ? kGpSigma2 + kGpNoise2 : k;
-  }
+  gp_factor(sh, n_obs, tid);
+  const double alpha_i = gp_solve(sh, n_obs, tid);
+  if ((tid & 127) < n_obs) sh.alpha[tid >> 7][tid & 127] = alpha_i;      // (zero beyond the window: gp_clear)
   __syncthreads();
-
-  // ---- phase 1b: K = L L^T, left-looking, column j per step.  Lane pair (i, i + 128) owns row i: the lower lane the first half of
-  // the dot product over the columns already done, the upper lane the second.  The running diagonal d_i = K_ii - sum_k L_ik^2 stays
-  // in the lower lane's register; the owner of row j + 1 finishes its diagonal inside step j, so no step waits for a square root
-  // it has not overlapped with a barrier.
-  {
-    const int i = tid & 127, h = tid >> 7;
-    double* ri = sh.W + tri(i);
-    double d_i = (i < n_obs) ? ri[i] : 1.0;
-    if (tid == 0) {
-      const double sq = __builtin_sqrt(d_i);
-      sh.inv_diag[0] = 1.0 / sq; ri[0] = sq;
-    }
-    __syncthreads();
-#pragma unroll 1
-    for (int j = 0; j + 1 < n_obs; ++j) {
-      const bool row = i > j && i < n_obs;
-      const double* rj = sh.W + tri(j);
-      const int kmid = j >> 1;
-      const int k0 = h ? kmid : 0, k1 = h ? j : kmid;
-      double s = 0.0;
-      if (row) {
-        for (int k = k0; k < k1; ++k) s = d_fma(ri[k], rj[k], s);
-        if (h) sh.part[i] = s;
-      }
-      __syncthreads();
-      if (row && !h) {
-        const double v = (ri[j] - (s + sh.part[i])) * sh.inv_diag[j];
-        ri[j] = v;
-        d_i = d_fma(-v, v, d_i);
-        if (i == j + 1) {
-          const double sq = __builtin_sqrt(d_i);
-          sh.inv_diag[i] = 1.0 / sq; ri[i] = sq;
-        }
-      }
-      __syncthreads();
-    }
-  }
-
-  // ---- phase 1c: W = L^-1 in place, row i per step: W[i][j] = -(1 / L_ii) sum_{k = j}^{i - 1} L[i][k] W[k][j], W[i][i] = 1 / L_ii.
-  // Lane pair (j, j + 128) owns column j.  Reads of row i of L come before the step's first barrier, the writes of row i of W after.
-  {
-    const int j = tid & 127, h = tid >> 7;
-#pragma unroll 1
-    for (int i = 0; i < n_obs; ++i) {
-      const bool act = j < i;
-      const double* ri = sh.W + tri(i);
-      double s = 0.0;
-      if (act) {
-        const int kmid = (j + i + 1) >> 1;
-        const int k0 = h ? kmid : j, k1 = h ? i : kmid;
-        const double* wk = sh.W + tri(k0) + j;          // W[k][j], k = k0 ..: the next row's entry lies k + 1 further
-        for (int k = k0; k < k1; ++k) { s = d_fma(ri[k], *wk, s); wk += k + 1; }
-        if (h) sh.part[j] = s;
-      }
-      __syncthreads();
-      if (!h) {
-        if (act) sh.W[tri(i) + j] = -sh.inv_diag[i] * (s + sh.part[j]);
-        else if (j == i) sh.W[tri(i) + i] = sh.inv_diag[i];
-      }
-      __syncthreads();
-    }
-  }
-
-  // ---- phase 2: zeta = W y, alpha = W^T zeta -- component c on the lanes 128 c ..
-  {
-    const int i = tid & 127, c = tid >> 7;
-    double s = 0.0;
-    if (i < n_obs) {
-      const double* ri = sh.W + tri(i);
-      for (int k = 0; k <= i; ++k) s = d_fma(ri[k], sh.z[c][k], s);
-    }
-    __syncthreads();
-    if (i < n_obs) sh.z[c][i] = s;
-    __syncthreads();
-    if (i < n_obs) {
-      double t = 0.0;
-      const double* wk = sh.W + tri(i) + i;              // W[k][i], k = i ..
-      for (int k = i; k < n_obs; ++k) { t = d_fma(*wk, sh.z[c][k], t); wk += k + 1; }
-      sh.alpha[c][i] = t;
-    }
-    __syncthreads();
-  }
 
   // ---- phase 3: the query points, 16 per wave and pass.  MFMA register layout (ble_observe.h, measured on gfx950): A lane l holds
   // A[l % 16][l / 16], B lane l holds B[l / 16][l % 16], every register of D lane l an entry of column l % 16.

@@ -8,9 +8,9 @@
 // values: the noise value and the correction rounded as gp_belief_mean rounds.
 //
 //   ble_gp_fit_scenarios_kernel   one workgroup (4 waves) per environment: phases 0-1 of ble_gp_fit_kernel (window, K, L, W = L^-1), then
-//                                 for each m: f_m at the window's points, the residual y - f_m, phase 2 -> alpha^m.  A copy of those
-//                                 phases, on purpose: ble_gp_fit_kernel keeps its instructions.
-//   gp_scenario_correction        gp_belief_mean with loc and alpha as two pointers (a copy, for the same reason).
+//                                 for each m: f_m at the window's points, the residual y - f_m, phase 2 -> alpha^m.  The phases are
+//                                 ble_gp_factor.h's functions, the ones ble_gp_fit_kernel and the query kernel call.
+//   gp_scenario_correction        (ble_gp_belief.h) gp_belief_mean's body with the slab's window and alpha^m as its two pointers.
 //   ble_gp_scenario_wind_kernel   one lane per environment at caller-chosen points and a scenario index per environment: what
 //                                 ble_step_f32 takes as noise_uv.  prior_only: f_m alone.
 //   ble_rollout_scenarios_kernel  ble_rollout_belief_kernel's body, one lane per (e, k, m), j = (e K + k) M + m.
@@ -75,34 +75,6 @@ BLE_FN float wind_noise_component_from_rows(int comp, float x_m, float y_m, floa
   for (int h = 0; h < 5; ++h)
     noise_add_harmonic(a, comp, h, harmonic_draw_from_rows(rows, stride, 5 * comp + h), x_km, y_km, pressure, t_h, lut);
   return noise_finish(a);
-}
-
-// gp_belief_mean with the window and the weights as two pointers (alpha^m lies 240 m doubles behind the belief's place): the same
-// loop, the same d_fma chain, rounded to fp32 once.  n_obs 0: exactly +0.0f; < 0: NaN.
-BLE_FN void gp_scenario_correction(const double* __restrict__ loc_, const double* __restrict__ alpha_, int n_obs, int n_trip, float x,
-                                   float y, float p, int32_t t_elapsed_s, const double* tab, float* u, float* v) {
-  const double* loc = (const double*)__builtin_assume_aligned(loc_, 16);
-  const double* alpha = (const double*)__builtin_assume_aligned(alpha_, 16);
-  const double xq = (double)x * kBeliefScaleXY, yq = (double)y * kBeliefScaleXY, pq = (double)p * kBeliefScaleP,
-               tq = (double)t_elapsed_s * kBeliefScaleT;
-  double su = 0.0, sv = 0.0;
-#pragma unroll 1
-  for (int i0 = 0; i0 < n_trip; i0 += 4) {
-    double k[4];
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      const double* l = loc + 4 * (i0 + r);
-      k[r] = gp_belief_kernel(l[0] - xq, l[1] - yq, l[2] - pq, l[3] - tq, tab);
-    }
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {                             // (i ascending: one fixed order)
-      su = d_fma(k[r], alpha[2 * (i0 + r)], su);
-      sv = d_fma(k[r], alpha[2 * (i0 + r) + 1], sv);
-    }
-  }
-  const float fnan = __builtin_nanf("");
-  *u = n_obs < 0 ? fnan : (n_obs == 0 ? 0.0f : (float)su);
-  *v = n_obs < 0 ? fnan : (n_obs == 0 ? 0.0f : (float)sv);
 }
 
 // ---------------------------------------------------------------------------------------------------------------- the risk score
@@ -197,46 +169,23 @@ __global__ __launch_bounds__(kObsBlock, 2) void ble_gp_fit_scenarios_kernel(GpHi
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   uint32_t flags = 0;
 
-  // ---- phase 0: the window at the anchor time (ble_gp_fit_kernel's rules)
-  int count = hist.count[env];
-  if (reset_mask != nullptr && reset_mask[env] != 0) count = 0;       // a history restart is pending
+  // ---- phases 0 - 1 (ble_gp_factor.h) at the anchor time: the window, the exit without a posterior, the window compacted, the factor
   const int32_t tq = time_s[env];
-  const int m = count < kGpCapacity ? count : kGpCapacity;
-  const float* h_xyp = hist.xyp + env * (kGpCapacity * 3);
-  const int32_t* h_t = hist.elapsed_s + env * kGpCapacity;
-  const float* h_err = hist.err_uv + env * (kGpCapacity * 2);
-  int32_t ta = tq, tb = tq;
-  if (lane < m) ta = h_t[(count - m + lane) % kGpCapacity];
-  if (lane + 64 < m) tb = h_t[(count - m + lane + 64) % kGpCapacity];
-  const int64_t age_a = (int64_t)ta - (int64_t)tq, age_b = (int64_t)tb - (int64_t)tq;
-  const unsigned long long b0 = __ballot(lane < m && (age_a < 0 ? -age_a : age_a) < kGpHorizonS);       // strict, like the reference
-  const unsigned long long b1 = __ballot(lane + 64 < m && (age_b < 0 ? -age_b : age_b) < kGpHorizonS);
-  int n_obs = __popcll(b0) + __popcll(b1);
-  int drop = 0;
-  if (n_obs > kGpMax) { drop = n_obs - kGpMax; n_obs = kGpMax; flags |= kFlagGpWindow; }
-  if (count > kGpCapacity && (b0 & 1ull) != 0) {
-    const int32_t t_newest = h_t[(count - 1) % kGpCapacity];
-    if (!(drop > 0 && tq >= t_newest)) {
-      if (tid == 0 && err_flags != nullptr) atomicOr(err_flags, (uint32_t)kFlagGpWindow);
-      gp_fit_scenarios_empty(b, env, tid, -1);
-      return;
-    }
-  }
-  if (n_obs == 0) {         // (uniform over the workgroup: no barrier has been reached)
-    gp_fit_scenarios_empty(b, env, tid, 0);
+  const GpWindow w = gp_window(hist, reset_mask, env, tq, lane);
+  const int n_obs = w.n_obs;
+  if (w.cut) flags |= kFlagGpWindow;
+  const bool untold = gp_window_untold(hist, env, tq, w);
+  if (untold || n_obs == 0) {         // no posterior (uniform over the workgroup: no barrier has been reached)
+    if (untold && tid == 0 && err_flags != nullptr) atomicOr(err_flags, (uint32_t)kFlagGpWindow);
+    gp_fit_scenarios_empty(b, env, tid, untold ? -1 : 0);
     return;
   }
-
-  // ---- compact the window into LDS (chronological), in units of the length scales; tables; the harmonics of every scenario
-  if (wave == 2) sh.exp2_frac[lane] = kGpSigma2 * d_exp_fast((double)lane * (6.93147180559945286227e-01 / 64.0));
+  // the zeros and tables of the factor and this kernel's own; the harmonics of every scenario
+  gp_clear(sh, tid, lane, wave);
   if (tid < kGpRows) {
-    sh.loc[tid][0] = 0.0; sh.loc[tid][1] = 0.0; sh.loc[tid][2] = 0.0; sh.loc[tid][3] = 0.0;
-    sh.z[0][tid] = 0.0; sh.z[1][tid] = 0.0; sh.alpha[0][tid] = 0.0; sh.alpha[1][tid] = 0.0;
-    sh.inv_diag[tid] = 0.0; sh.part[tid] = 0.0;
     sc.y[0][tid] = 0.0; sc.y[1][tid] = 0.0;
     sc.px[tid] = 0.0f; sc.py[tid] = 0.0f; sc.pp[tid] = 0.0f; sc.pt[tid] = 0;
   }
-  if (tid < 128) sh.W[kCholTri + tid] = 0.0;
   grad_lut_fill(sc.grad_lut, tid, kObsBlock);
   if (tid < 10 * b.num) {                               // thread (m, k): harmonic k of scenario m, from its own place in the stream
     const int sm = tid / 10, k = tid - 10 * sm;
@@ -245,98 +194,13 @@ __global__ __launch_bounds__(kObsBlock, 2) void ble_gp_fit_scenarios_kernel(GpHi
     o[0] = d.hseed; o[1] = float_bits_u32(d.ox); o[2] = float_bits_u32(d.oy); o[3] = float_bits_u32(d.op); o[4] = float_bits_u32(d.ot);
   }
   __syncthreads();
-  if (wave < 2) {
-    const unsigned long long b_mine = wave == 0 ? b0 : b1;
-    const int e = tid;                                  // ring entry of this lane (waves 0 and 1: entries 0 .. 127)
-    if (((b_mine >> lane) & 1ull) != 0) {
-      const int at = __popcll(b_mine & ((1ull << lane) - 1ull)) + (wave == 1 ? __popcll(b0) : 0) - drop;
-      if (at >= 0) {
-        const int slot = (count - m + e) % kGpCapacity;
-        const float ox = h_xyp[slot * 3], oy = h_xyp[slot * 3 + 1], op = h_xyp[slot * 3 + 2];
-        const int32_t ot = h_t[slot];
-        sh.loc[at][0] = (double)ox * (kGpKappa / 357000.0);
-        sh.loc[at][1] = (double)oy * (kGpKappa / 357000.0);
-        sh.loc[at][2] = (double)op * (kGpKappa / 326.0);
-        sh.loc[at][3] = (double)ot * (kGpKappa / 34560.0);
-        sc.y[0][at] = (double)h_err[slot * 2]; sc.y[1][at] = (double)h_err[slot * 2 + 1];
-        sc.px[at] = ox; sc.py[at] = oy; sc.pp[at] = op; sc.pt[at] = ot;
-      }
-    }
-  }
+  // y is kept apart from sh.z (every scenario's phase 2 overwrites that), with the ring's own float x, y, p and int t for f_m
+  gp_compact(sh, hist, env, w, tid, lane, wave, [&](int at, float ox, float oy, float op, int32_t ot, float err_u, float err_v) {
+    sc.y[0][at] = (double)err_u; sc.y[1][at] = (double)err_v;
+    sc.px[at] = ox; sc.py[at] = oy; sc.pp[at] = op; sc.pt[at] = ot;
+  });
   __syncthreads();
-
-  // ---- phase 1a: K, packed
-  const int n_tri = tri(n_obs);
-  for (int e = tid; e < n_tri; e += kObsBlock) {
-    int i = (int)((__builtin_sqrtf(8.0f * (float)e + 1.0f) - 1.0f) * 0.5f);
-    while (tri(i) > e) --i;
-    while (tri(i + 1) <= e) ++i;
-    const int j = e - tri(i);
-    const double dx = sh.loc[i][0] - sh.loc[j][0], dy = sh.loc[i][1] - sh.loc[j][1], dp = sh.loc[i][2] - sh.loc[j][2],
-                 dt = sh.loc[i][3] - sh.loc[j][3];
-    const double k = gp_exp_neg_scaled(two_sqrt(dx * dx + dy * dy + dp * dp + dt * dt + 1e-300), sh.exp2_frac);
-    sh.W[e] = i == j ? kGpSigma2 + kGpNoise2 : k;
-  }
-  __syncthreads();
-
-  // ---- phase 1b: K = L L^T, left-looking, column j per step; lane pair (i, i + 128) owns row i
-  {
-    const int i = tid & 127, h = tid >> 7;
-    double* ri = sh.W + tri(i);
-    double d_i = (i < n_obs) ? ri[i] : 1.0;
-    if (tid == 0) {
-      const double sq = __builtin_sqrt(d_i);
-      sh.inv_diag[0] = 1.0 / sq; ri[0] = sq;
-    }
-    __syncthreads();
-#pragma unroll 1
-    for (int j = 0; j + 1 < n_obs; ++j) {
-      const bool row = i > j && i < n_obs;
-      const double* rj = sh.W + tri(j);
-      const int kmid = j >> 1;
-      const int k0 = h ? kmid : 0, k1 = h ? j : kmid;
-      double s = 0.0;
-      if (row) {
-        for (int k = k0; k < k1; ++k) s = d_fma(ri[k], rj[k], s);
-        if (h) sh.part[i] = s;
-      }
-      __syncthreads();
-      if (row && !h) {
-        const double v = (ri[j] - (s + sh.part[i])) * sh.inv_diag[j];
-        ri[j] = v;
-        d_i = d_fma(-v, v, d_i);
-        if (i == j + 1) {
-          const double sq = __builtin_sqrt(d_i);
-          sh.inv_diag[i] = 1.0 / sq; ri[i] = sq;
-        }
-      }
-      __syncthreads();
-    }
-  }
-
-  // ---- phase 1c: W = L^-1 in place, row i per step; lane pair (j, j + 128) owns column j
-  {
-    const int j = tid & 127, h = tid >> 7;
-#pragma unroll 1
-    for (int i = 0; i < n_obs; ++i) {
-      const bool act = j < i;
-      const double* ri = sh.W + tri(i);
-      double s = 0.0;
-      if (act) {
-        const int kmid = (j + i + 1) >> 1;
-        const int k0 = h ? kmid : j, k1 = h ? i : kmid;
-        const double* wk = sh.W + tri(k0) + j;          // W[k][j], k = k0 ..: the next row's entry lies k + 1 further
-        for (int k = k0; k < k1; ++k) { s = d_fma(ri[k], *wk, s); wk += k + 1; }
-        if (h) sh.part[j] = s;
-      }
-      __syncthreads();
-      if (!h) {
-        if (act) sh.W[tri(i) + j] = -sh.inv_diag[i] * (s + sh.part[j]);
-        else if (j == i) sh.W[tri(i) + i] = sh.inv_diag[i];
-      }
-      __syncthreads();
-    }
-  }
+  gp_factor(sh, n_obs, tid);
 
   // ---- the window, once (zero beyond it: loc was cleared above)
   double* slab = b.slab + env * b.stride;
@@ -353,20 +217,7 @@ __global__ __launch_bounds__(kObsBlock, 2) void ble_gp_fit_scenarios_kernel(GpHi
         sh.z[c][i] = sc.y[c][i] - (double)f;
       }
       __syncthreads();
-      // phase 2: zeta = W z, alpha = W^T zeta
-      double s = 0.0;
-      if (i < n_obs) {
-        const double* ri = sh.W + tri(i);
-        for (int k = 0; k <= i; ++k) s = d_fma(ri[k], sh.z[c][k], s);
-      }
-      __syncthreads();
-      if (i < n_obs) sh.z[c][i] = s;
-      __syncthreads();
-      double t = 0.0;
-      if (i < n_obs) {
-        const double* wk = sh.W + tri(i) + i;              // W[k][i], k = i ..
-        for (int k = i; k < n_obs; ++k) { t = d_fma(*wk, sh.z[c][k], t); wk += k + 1; }
-      }
+      const double t = gp_solve(sh, n_obs, tid);          // phase 2: alpha^m = K^-1 (y - f_m)
       if (i < kBeliefRows) slab[kBeliefAlphaAt + kScenarioAlphaDoubles * sm + 2 * i + c] = t;      // (0.0 beyond the window)
       __syncthreads();                                     // (the next scenario overwrites z)
     }

@@ -1,5 +1,5 @@
-"""ONE table of WindGP rings and anchors for the kernels that each carry their own copy of the window (ble_gp_query.h, ble_gp_belief.h's
-ble_gp_fit_kernel, ble_scenarios.h's ble_gp_fit_scenarios_kernel): windows that end at the wave boundary of the ballot pair, anchors
+"""ONE table of WindGP rings and anchors for the kernels that take their window from ble_gp_factor.h (ble_gp_query.h, ble_gp_belief.h's
+ble_gp_fit_kernel, ble_scenarios.h's ble_gp_fit_scenarios_kernel: one copy of the rule, three callers with exits of their own): windows that end at the wave boundary of the ballot pair, anchors
 that make the window a suffix, an interior slice or a prefix of the ring, the strict < 21 600 s edge from both sides, the wrapped and
 over-full ring with and without the documented exception.  Host only (NumPy); tests/test_gp_window_cases_host.py checks the table
 itself, tests/test_gpu_gp_windows.py holds the three kernels to it.  TEST TOOLING.

@@ -1,6 +1,6 @@
-"""The three kernels that each carry their own copy of the WindGP window -- ble_gp_query_kernel (ble_gp_query.h), ble_gp_fit_kernel
+"""The three kernels that call the WindGP window of ble_gp_factor.h -- ble_gp_query_kernel (ble_gp_query.h), ble_gp_fit_kernel
 (ble_gp_belief.h) and ble_gp_fit_scenarios_kernel (ble_scenarios.h): ballot pair, `drop`, the evicted-entries rule, popcount compaction
--- held to ONE table of rings and anchors (tests/gp_window_cases.py; the table itself is checked by
+in one copy, the exits and what is kept of an entry per kernel -- held to ONE table of rings and anchors (tests/gp_window_cases.py; the table itself is checked by
 tests/test_gp_window_cases_host.py).  One environment per case on one simulator.
 
 References.  n_obs and BLE_FLAG_GP_WINDOW: include/ble_abi.h's rule restated over the held entries (gp_window_cases.expected).  The
