@@ -161,6 +161,39 @@ class BlePlanBootstrap(ctypes.Structure):
               ('score', ctypes.c_void_p)]
 
 
+TREE_MAX_BEAM = 256         # BLE_TREE_MAX_BEAM
+
+
+class BleTreeArena(ctypes.Structure):
+  """struct ble_tree_arena: the nodes of one level of a beam search: a leaf arena's state and, per node, the rollout lane's acc and disc
+  (float64), flown (int32) and ret = (float)acc (device pointers)."""
+  _fields_ = [('state', ctypes.POINTER(BleStateF32)), ('acc', ctypes.c_void_p), ('disc', ctypes.c_void_p), ('flown', ctypes.c_void_p),
+              ('ret', ctypes.c_void_p)]
+
+
+class BleTreeExpand(ctypes.Structure):
+  """struct ble_tree_expand: one level of a beam search: every selected parent's three children flown for one edge (ble_tree_expand_f32)."""
+  _fields_ = [('n', ctypes.c_int64), ('beam', ctypes.c_int32), ('depth', ctypes.c_int32), ('n_parents', ctypes.c_int32),
+              ('parent_children', ctypes.c_int32), ('segment', ctypes.c_int32), ('action_repeat', ctypes.c_int32), ('substeps', ctypes.c_int32),
+              ('reserved_', ctypes.c_int32), ('gamma', ctypes.c_double), ('wind_grid', ctypes.c_void_p), ('grid_env_stride', ctypes.c_int64),
+              ('parent', ctypes.c_void_p), ('src', BleTreeArena), ('dst', BleTreeArena)]
+
+
+class BleTreeSelect(ctypes.Structure):
+  """struct ble_tree_select: a level's returns [n][C] -> the next level's parents and this level's choice list [n][beam]."""
+  _fields_ = [('n', ctypes.c_int64), ('n_children', ctypes.c_int32), ('beam', ctypes.c_int32), ('ret', ctypes.c_void_p),
+              ('parent', ctypes.c_void_p), ('choice', ctypes.c_void_p)]
+
+
+class BleTreeFinish(ctypes.Structure):
+  """struct ble_tree_finish: the last level's returns (and optional scores) and the choice lists -> best_plan, action, best_return and,
+  on request, q and visits [n][3] (device pointers)."""
+  _fields_ = [('n', ctypes.c_int64), ('n_children', ctypes.c_int32), ('beam', ctypes.c_int32), ('depth', ctypes.c_int32),
+              ('segment', ctypes.c_int32), ('ret', ctypes.c_void_p), ('score', ctypes.c_void_p), ('source_status', ctypes.c_void_p),
+              ('choice', ctypes.c_void_p), ('best_plan', ctypes.c_void_p), ('action', ctypes.c_void_p), ('best_return', ctypes.c_void_p),
+              ('q', ctypes.c_void_p), ('visits', ctypes.c_void_p)]
+
+
 SCENARIO_MAX = 16           # BLE_SCENARIO_MAX
 
 

@@ -19,7 +19,7 @@ from balloon_learning_environment_amd import _abi
 _PKG_DIR = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get('BLE_HIP_LIB') or os.path.join(_PKG_DIR, 'libble_hip.so')   # override: experiments only
 _SOURCES = [os.path.join(_PKG_DIR, 'csrc', f) for f in ('ble_kernels.hip', 'ble_step_core.h', 'ble_physics.h', 'ble_intrinsics.h', 'ble_reset.h',
-                                                          'ble_observe.h', 'ble_gp_query.h', 'ble_gp_factor.h', 'ble_rollout.h', 'ble_gp_belief.h', 'ble_plan.h', 'ble_scenarios.h', 'ble_noise.h', 'ble_decode.h', 'ble_step_split.h', 'ble_step_helper.h', 'ble_agent.h', 'ble_qnet.h',
+                                                          'ble_observe.h', 'ble_gp_query.h', 'ble_gp_factor.h', 'ble_rollout.h', 'ble_gp_belief.h', 'ble_plan.h', 'ble_tree.h', 'ble_scenarios.h', 'ble_noise.h', 'ble_decode.h', 'ble_step_split.h', 'ble_step_helper.h', 'ble_agent.h', 'ble_qnet.h',
                                                           'ble_train.h', 'ble_replay.h', 'ble_explore.h', 'ble_actor.h', 'ble_imitate.h', 'ble_population.h',
                                                           'ble_population_train.h')]
 _HEADER = os.path.join(os.path.dirname(_PKG_DIR), 'include', 'ble_abi.h')
@@ -55,7 +55,8 @@ EXPORTS = ('ble_abi_version', 'ble_noise_primitive_version', 'ble_vehicle_defaul
            'ble_plan_prior_u16', 'ble_plan_sample_prior_u8', 'ble_plan_action_values_f32', 'ble_qnet_soft_bc_step_f32',
            'ble_rollout_leaves_f32', 'ble_observe_leaves_f32', 'ble_plan_bootstrap_f32',
            'ble_qnet_forward_grouped_f32', 'ble_es_perturb_f32', 'ble_es_gradient_f32', 'ble_qnet_apply_grad_f32',
-           'ble_qnet_ppo_grouped_workspace_f32', 'ble_qnet_ppo_step_grouped_f32', 'ble_ac_act_grouped_f32')
+           'ble_qnet_ppo_grouped_workspace_f32', 'ble_qnet_ppo_step_grouped_f32', 'ble_ac_act_grouped_f32',
+           'ble_tree_expand_f32', 'ble_tree_select_f32', 'ble_tree_finish_f32')
 # Exports added without a new ABI version: a library of this ABI built before them (BLE_HIP_LIB: the parent's, in A/B runs) still loads.
 # build() checks every name of EXPORTS on the library it builds.
 ADDITIVE_EXPORTS = ('ble_last_step_form', 'ble_gp_query_f32', 'ble_rollout_f32', 'ble_gp_fit_f32', 'ble_gp_belief_wind_f32',
@@ -65,7 +66,8 @@ ADDITIVE_EXPORTS = ('ble_last_step_form', 'ble_gp_query_f32', 'ble_rollout_f32',
                     'ble_plan_sample_prior_u8', 'ble_plan_action_values_f32', 'ble_qnet_soft_bc_step_f32', 'ble_rollout_leaves_f32',
                     'ble_observe_leaves_f32', 'ble_plan_bootstrap_f32', 'ble_qnet_forward_grouped_f32', 'ble_es_perturb_f32',
                     'ble_es_gradient_f32', 'ble_qnet_apply_grad_f32', 'ble_qnet_ppo_grouped_workspace_f32',
-                    'ble_qnet_ppo_step_grouped_f32', 'ble_ac_act_grouped_f32')
+                    'ble_qnet_ppo_step_grouped_f32', 'ble_ac_act_grouped_f32', 'ble_tree_expand_f32', 'ble_tree_select_f32',
+                    'ble_tree_finish_f32')
 
 
 class BleLibraryError(RuntimeError):
@@ -235,6 +237,11 @@ def lib():
     l.ble_qnet_ppo_grouped_workspace_f32.argtypes = [grouped, ctypes.POINTER(_abi.BleQnetTrainLayout)]
     l.ble_qnet_ppo_step_grouped_f32.argtypes = [grouped, batch, _vp, _vp, _vp]
     l.ble_ac_act_grouped_f32.argtypes = [ctypes.POINTER(_abi.BleQnetGroupedF32), ctypes.POINTER(_abi.BleAcSample), _vp, _vp]
+  if hasattr(l, 'ble_tree_expand_f32'):               # plan by beam search (sizes in the structs: no int64_t argument)
+    l.ble_tree_expand_f32.argtypes = [st, ctypes.POINTER(_abi.BleTreeExpand), ctypes.POINTER(_abi.BleNoiseGen),
+                                      ctypes.POINTER(_abi.BleGpBelief), _vp, _vp]
+    l.ble_tree_select_f32.argtypes = [ctypes.POINTER(_abi.BleTreeSelect), _vp]
+    l.ble_tree_finish_f32.argtypes = [ctypes.POINTER(_abi.BleTreeFinish), _vp]
   for name in EXPORTS:
     if hasattr(l, name) or name not in ADDITIVE_EXPORTS:
       getattr(l, name).restype = _int

@@ -168,7 +168,8 @@ class VecPriorPlannerAgent:
   act_greedy) for its probabilities and hands them to `planner` (a VecLookaheadAgent built with prior_strength > 0) as its prior.  An
   agent like any other device agent: eval_lib.VecEvaluator binds it to its simulator and may capture it in a graph.  The same network
   can serve twice: as `policy` here and as the planner's leaf_value (VecLookaheadAgent(leaf_value=policy)) -- its policy head
-  biases where the planner searches, its value head scores where the plans end."""
+  biases where the planner searches, its value head scores where the plans end.  A VecBeamSearchAgent is accepted as
+  `planner` too: it takes prior_probs and ignores them (a beam search has no prior), so the pair then acts as the beam search alone."""
 
   def __init__(self, policy, planner):
     self.policy, self.planner = policy, planner

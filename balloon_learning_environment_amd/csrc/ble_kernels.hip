@@ -822,6 +822,8 @@ __global__ __launch_bounds__(256) void ble_eval_accumulate_kernel(StateDev st, c
 // the fitted WindGP kept on the device, its mean as a lane function, and the look-ahead flown in it: after ble_rollout.h (RolloutArgs)
 #include "ble_gp_belief.h"
 #include "ble_plan.h"
+// plan by beam search: the expand, select and finish kernels of a shared-prefix tree of plans: after ble_plan.h (the key and rank functions)
+#include "ble_tree.h"
 // scenario winds (a prior draw of the noise field conditioned on the measurements), the look-ahead flown in them and the risk score: after
 // ble_gp_belief.h (belief_wave_trip) and ScalarSeed / EnvSeed
 #include "ble_scenarios.h"
@@ -2289,6 +2291,90 @@ int ble_observe_leaves_f32(const ble_state_f32* leaves, int32_t leaves_per_env, 
     return launch(ble_observe_kernel<decltype(veh), false, true>, n_leaves, 1, kObsBlock, stream, state_dev(leaves), wind_grid, grid_env_stride,
                   (const float*)nullptr, reset_mask, h, (int)leaves_per_env, obs, err_flags, obs_row_stride, veh, (const float*)nullptr);
   });
+}
+
+// ---- plan by beam search
+namespace {
+// an arena's pointers as the kernels take them; `state` has been checked by the caller
+inline TreeArenaDev tree_arena_dev(const struct ble_tree_arena& a) { return TreeArenaDev{state_dev(a.state), a.acc, a.disc, a.flown, a.ret}; }
+// the sizes the three calls share: n, the beam, and a level's number of children
+inline bool tree_sizes_ok(int64_t n, int beam) {
+  return n >= 0 && n < 2147483648LL && beam >= 1 && beam <= BLE_TREE_MAX_BEAM && n * (int64_t)(3 * beam) < 2147483648LL;
+}
+inline bool tree_children_ok(int n_children, int beam) { return n_children >= 3 && n_children <= 3 * beam && n_children % 3 == 0; }
+// an array of `a` that is the same array of `b`
+inline bool state_arrays_shared(const ble_state_f32* a, const ble_state_f32* b) {
+  const void* const* pa = reinterpret_cast<const void* const*>(a);
+  const void* const* pb = reinterpret_cast<const void* const*>(b);
+  for (size_t k = 0; k < offsetof(ble_state_f32, episode_cache) / sizeof(void*); ++k)
+    if (pa[k] == pb[k]) return true;
+  return false;
+}
+static_assert(kTreeMaxBeam == BLE_TREE_MAX_BEAM && kTreeMaxDepth == BLE_ROLLOUT_MAX_STEPS, "ble_tree.h and ble_abi.h disagree");
+}  // namespace
+
+int ble_tree_expand_f32(const ble_state_f32* st, const struct ble_tree_expand* ex, const ble_noise_gen* noise, const ble_gp_belief* belief,
+                        uint32_t* err_flags, void* stream) {
+  if (noise != nullptr && belief != nullptr) return BLE_E_INVALID_ARG;                  // two winds
+  if (!state_ok(st) || !ex || !ex->wind_grid || !state_ok(ex->dst.state) || !ex->dst.acc || !ex->dst.disc || !ex->dst.flown || !ex->dst.ret)
+    return BLE_E_INVALID_ARG;
+  if (!tree_sizes_ok(ex->n, ex->beam) || ex->segment < 1 || ex->action_repeat < 1 || ex->depth < 1 ||
+      (int64_t)ex->depth * ex->segment * ex->action_repeat > BLE_ROLLOUT_MAX_STEPS || ex->reserved_ != 0)
+    return BLE_E_INVALID_ARG;
+  if (ex->substeps < 1 || ex->substeps > BLE_MAX_SUBSTEPS || ex->grid_env_stride < 0 || (noise != nullptr && noise->env_offset < 0) ||
+      !(ex->gamma >= 0.0 && ex->gamma <= 1.0))                       // (a NaN gamma fails both comparisons)
+    return BLE_E_INVALID_ARG;
+  BeliefDev b{nullptr, 0, nullptr};
+  if (belief != nullptr && (!gp_belief(belief, &b) || belief->n != ex->n)) return BLE_E_INVALID_ARG;      // (a belief of another batch would be read out of bounds)
+  if (state_arrays_shared(ex->dst.state, st)) return BLE_E_INVALID_ARG;                 // st is never written
+  const bool first = ex->parent_children == 0;
+  if (first) {
+    if (ex->n_parents != 1) return BLE_E_INVALID_ARG;
+  } else {
+    if (!ex->parent || !state_ok(ex->src.state) || !ex->src.acc || !ex->src.disc || !ex->src.flown) return BLE_E_INVALID_ARG;
+    if (!tree_children_ok(ex->parent_children, ex->beam) || ex->n_parents < 1 || ex->n_parents > ex->parent_children || ex->n_parents > ex->beam)
+      return BLE_E_INVALID_ARG;
+    if (state_arrays_shared(ex->dst.state, ex->src.state) || ex->dst.acc == ex->src.acc || ex->dst.disc == ex->src.disc ||
+        ex->dst.flown == ex->src.flown)
+      return BLE_E_INVALID_ARG;                                                         // a level is not expanded in place
+  }
+  return with_vehicle<false>(st, nullptr, [&](auto veh) {
+    if (ex->n == 0) return BLE_OK;
+    const TreeExpandArgs a{ex->n, ex->n_parents, ex->parent_children, ex->beam, ex->segment * ex->action_repeat, ex->substeps, ex->gamma,
+                           ex->wind_grid, ex->grid_env_stride, ex->parent};
+    // level 1: the parents are st's environments (src.acc == NULL tells the kernel)
+    const TreeArenaDev src = first ? TreeArenaDev{state_dev(st), nullptr, nullptr, nullptr, nullptr} : tree_arena_dev(ex->src);
+    const TreeArenaDev dst = tree_arena_dev(ex->dst);
+    const int64_t lanes = ex->n * (int64_t)(3 * ex->n_parents);
+    const StepNoise none{0ull, nullptr, nullptr, 0ll};
+    if (belief != nullptr)
+      return launch(ble_tree_expand_kernel<kTreeWindBelief, decltype(veh)>, lanes, kStepBlock, kStepBlock, stream, state_dev(st), a, src, dst, b,
+                    none, err_flags, veh);
+    if (noise != nullptr)      // (the harmonic cache is not handed on: the kernel draws into LDS and fills no cache)
+      return launch(ble_tree_expand_kernel<kTreeWindNoise, decltype(veh)>, lanes, kStepBlock, kStepBlock, stream, state_dev(st), a, src, dst, b,
+                    StepNoise{noise->seed, noise->episode, nullptr, (long long)noise->env_offset}, err_flags, veh);
+    return launch(ble_tree_expand_kernel<kTreeWindForecast, decltype(veh)>, lanes, kStepBlock, kStepBlock, stream, state_dev(st), a, src, dst, b,
+                  none, err_flags, veh);
+  });
+}
+
+int ble_tree_select_f32(const struct ble_tree_select* sel, void* stream) {
+  if (!sel || !sel->ret || !sel->parent || !sel->choice || !tree_sizes_ok(sel->n, sel->beam) || !tree_children_ok(sel->n_children, sel->beam))
+    return BLE_E_INVALID_ARG;
+  const TreeSelectArgs a{sel->n, sel->n_children, sel->beam, sel->ret, sel->parent, sel->choice};
+  return launch(ble_tree_select_kernel, sel->n, 1, kPlanSelectBlock, stream, a);
+}
+
+int ble_tree_finish_f32(const struct ble_tree_finish* fin, void* stream) {
+  if (!fin || !fin->ret || !fin->source_status || !fin->choice || !fin->best_plan || !fin->action || !fin->best_return ||
+      (fin->q == nullptr) != (fin->visits == nullptr))
+    return BLE_E_INVALID_ARG;
+  if (!tree_sizes_ok(fin->n, fin->beam) || !tree_children_ok(fin->n_children, fin->beam) || fin->depth < 1 || fin->segment < 1 ||
+      (int64_t)fin->depth * fin->segment > BLE_ROLLOUT_MAX_STEPS || (fin->depth == 1 && fin->n_children != 3))
+    return BLE_E_INVALID_ARG;
+  const TreeFinishArgs a{fin->n, fin->n_children, fin->beam, fin->depth, fin->segment, fin->ret, fin->score ? fin->score : fin->ret,
+                         fin->source_status, fin->choice, fin->best_plan, fin->action, fin->best_return, fin->q, fin->visits};
+  return launch(ble_tree_finish_kernel, fin->n, 1, kPlanSelectBlock, stream, a);
 }
 
 int ble_gp_fit_scenarios_f32(const ble_gp_history_f32* hist, const uint8_t* reset_mask, const int32_t* time_s, const ble_gp_scenarios* scn,

@@ -197,6 +197,13 @@ class VecBalloonArena:
     return self.sim.rollout_plans(plans, gamma, action_repeat, noise_seed, want_rewards=want_rewards, want_final=want_final, out=out,
                                   belief=belief, scenarios=scenarios, leaves=leaves)
 
+  def tree_search(self, depth: int, beam_width: int, segment: int = 4, action_repeat: int = 1, gamma: float = 0.993,
+                  noise_seed: Optional[int] = None, belief=None, **kw):
+    """Plan by beam search from the current states without changing them: depth levels of one action flown segment * action_repeat
+    agent steps, the best beam_width nodes kept per env and level -> TreeSearch(action, best_plan, best_return, q, visits, returns,
+    steps_flown, leaves); VecSimulator.tree_search.  noise_seed / belief: lookahead's winds."""
+    return self.sim.tree_search(depth, beam_width, segment, action_repeat, gamma, noise_seed=noise_seed, belief=belief, **kw)
+
   def fit_wind_belief(self, time_s: Optional[torch.Tensor] = None, out=None):
     """Every env's WindGP fitted once and kept on the device: WindBelief(slab, n_obs); VecSimulator.fit_wind_belief."""
     return self.sim.fit_wind_belief(time_s, out)

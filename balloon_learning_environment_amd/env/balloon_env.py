@@ -258,15 +258,37 @@ class VecBalloonEnv:
     noise_seed = self.arena._seed if (wind == 'truth' and self._wind_noise) else None
     return self.arena.lookahead(plans, gamma, action_repeat, noise_seed, want_rewards, want_final, out, leaves=leaves)
 
-  def planner(self, **kw):
-    """A look-ahead agent bound to these environments: agents.lookahead_agent.VecLookaheadAgent(**kw) -- num_plans, horizon,
-    action_repeat, segment, gamma, wind ('belief' by default; 'scenarios' with num_scenarios, risk_tail), iterations, elite, seed,
+  def tree_search(self, depth: int, beam_width: int, segment: int = 4, action_repeat: int = 1, gamma: float = 0.993, wind: str = 'truth',
+                  **kw):
+    """Plan by beam search from where each balloon is now, nothing of the environments changed: depth levels of one action flown
+    segment * action_repeat agent steps, the best beam_width nodes kept per environment and level -> TreeSearch(action, best_plan,
+    best_return, q, visits, returns, steps_flown, leaves) (VecSimulator.tree_search; action_values=, leaf_score=, buffers= go through).
+    wind: lookahead's 'truth', 'forecast' or 'belief' (fitted now); scenario winds have no tree."""
+    if wind not in ('truth', 'forecast', 'belief'):
+      raise ValueError(f"tree_search: wind is 'truth', 'forecast' or 'belief', not {wind!r}")
+    if wind == 'belief':
+      self._belief = self.arena.fit_wind_belief(out=self._belief)
+      return self.arena.tree_search(depth, beam_width, segment, action_repeat, gamma, belief=self._belief, **kw)
+    noise_seed = self.arena._seed if (wind == 'truth' and self._wind_noise) else None
+    return self.arena.tree_search(depth, beam_width, segment, action_repeat, gamma, noise_seed=noise_seed, **kw)
+
+  def planner(self, search: str = 'sample', **kw):
+    """A look-ahead agent bound to these environments.  search='sample' (the default): agents.lookahead_agent.VecLookaheadAgent(**kw)
+    -- num_plans, horizon, action_repeat, segment, gamma, wind ('belief' by default; 'scenarios' with num_scenarios, risk_tail), iterations, elite, seed,
     leaf_value (a critic whose value of every plan's end state is added to its return) -- planning in this batch's simulator.
+    search='beam': agents.beam_agent.VecBeamSearchAgent(**kw) -- beam_width, depth, segment, action_repeat, gamma, wind ('belief' by
+    default, 'forecast' or 'truth'), leaf_value, action_values: a systematic, deterministic search of a shared-prefix tree of plans.
     wind='truth' flies the plans in the wind these environments fly, this env's wind noise included (with wind_noise=False the truth
     is the forecast).  actions = agent.act(obs); obs, reward, terminal = env.step(actions): no host synchronisation in either."""
-    from balloon_learning_environment_amd.agents import lookahead_agent
+    if search not in ('sample', 'beam'):
+      raise ValueError(f"planner: search is 'sample' or 'beam', not {search!r}")
     kw.setdefault('device', self.device)
-    agent = lookahead_agent.VecLookaheadAgent(**kw)
+    if search == 'beam':
+      from balloon_learning_environment_amd.agents import beam_agent
+      agent = beam_agent.VecBeamSearchAgent(**kw)
+    else:
+      from balloon_learning_environment_amd.agents import lookahead_agent
+      agent = lookahead_agent.VecLookaheadAgent(**kw)
     return agent.bind(self.arena.sim, noise_seed=(lambda: self.arena._seed) if self._wind_noise else None)
 
   def _step_eager(self, actions, obs_out=None, end_mask=None):

@@ -443,6 +443,8 @@ def run_exit_loop_vec(env, trainer, planner, buffer, *, num_iterations: int, bet
   With a bootstrapped planner (VecLookaheadAgent(leaf_value=)) nothing here changes, but the stored best return -- the
   value target under value_coef -- is then an H-step BOOTSTRAPPED return, sum_{t<H} gamma^t r_t + gamma^H V(s_H), and so are the
   per-action values; with leaf_value=trainer the target moves with the learner's own value column.
+  A beam-search planner (venv.planner(search='beam', action_values=True)) serves as `planner` as well: the loop uses its
+  act, action_values and plan alone; it takes the prior and ignores it.
 
   After the T steps `epochs` passes of minibatches of batch_size rows follow, each one soft update (epochs x (T N // batch_size) in
   all); then the block is discarded.

@@ -39,6 +39,67 @@ WindBelief = collections.namedtuple('WindBelief', ('slab', 'n_obs'))
 WindScenarios = collections.namedtuple('WindScenarios', ('slab', 'n_obs', 'num', 'seed', 'seeds'), defaults=(0, None))
 
 
+class TreeSearch(collections.namedtuple('TreeSearch', ('action', 'best_plan', 'best_return', 'q', 'visits', 'returns', 'steps_flown', 'leaves'))):
+  """What tree_search returns: action [n] u8, best_plan [depth * segment, n] u8, best_return [n] f32, q and visits [n, 3] or None, and
+  the last level: returns [n, C] f32, steps_flown [n, C] i32 and leaves, its arena (a leaf arena of C leaves per environment).
+  buffers, reached by name: the TreeBuffers the search wrote into (choice [depth, n, beam_width], the lists of every selection)."""
+
+  def __new__(cls, *fields, buffers=None):
+    self = super().__new__(cls, *fields)
+    self.buffers = buffers
+    return self
+
+
+def tree_level_sizes(depth: int, beam_width: int):
+  """[(P_{d-1}, C_d)] for d = 1 .. depth: P_0 = 1, C_d = 3 P_{d-1}, P_d = min(C_d, beam_width)."""
+  sizes, parents = [], 1
+  for _ in range(int(depth)):
+    sizes.append((parents, 3 * parents))
+    parents = min(3 * parents, int(beam_width))
+  return sizes
+
+
+class TreeBuffers:
+  """The device memory of a beam search of one depth and beam width over one simulator (VecSimulator.tree_buffers): two node arenas
+  that alternate level by level -- arenas[d & 1] holds level d: a leaf arena of C_d leaves per environment plus, per node, acc and
+  disc (float64), flown (int32) and ret (float32); the last level's arena is sized for exactly that level, so it is a leaf arena of
+  the simulator like any other --, parent [n, beam_width] and choice [depth, n, beam_width] (int32), and the results, best_plan [depth * segment, n] among them."""
+
+  def __init__(self, sim: 'VecSimulator', depth: int, beam_width: int, segment: int = 4, action_values: bool = False):
+    depth, beam, self.segment = int(depth), int(beam_width), int(segment)
+    if self.segment < 1 or depth * self.segment > _abi.ROLLOUT_MAX_STEPS:
+      raise ValueError(f'tree_search: segment >= 1 and depth * segment <= {_abi.ROLLOUT_MAX_STEPS}, not {depth} x {segment}')
+    if depth < 1 or depth > _abi.ROLLOUT_MAX_STEPS or not 1 <= beam <= _abi.TREE_MAX_BEAM or sim.n * 3 * beam >= 2 ** 31:
+      raise ValueError(f'tree_search: 1 <= depth <= {_abi.ROLLOUT_MAX_STEPS}, 1 <= beam_width <= {_abi.TREE_MAX_BEAM} and n * 3 * beam_width < 2^31, '
+                       f'not depth {depth}, beam_width {beam}, n {sim.n}')
+    self.sim, self.depth, self.beam = sim, depth, beam
+    sizes = tree_level_sizes(depth, beam)
+    n, device = sim.n, sim.device
+    self.arenas, self.acc, self.disc, self.flown, self.ret, self._structs = [None, None], [None, None], [None, None], [None, None], [None, None], [None, None]
+    with torch.cuda.device(device):
+      for level in (depth - 1, depth):           # (children per level never shrink: the last level of each parity is its largest)
+        if level < 1:
+          continue
+        p, nodes = level & 1, n * sizes[level - 1][1]
+        self.arenas[p] = sim.leaf_arena(sizes[level - 1][1])
+        self.acc[p] = torch.zeros(nodes, dtype=torch.float64, device=device)
+        self.disc[p] = torch.zeros(nodes, dtype=torch.float64, device=device)
+        self.flown[p] = torch.zeros(nodes, dtype=torch.int32, device=device)
+        self.ret[p] = torch.zeros(nodes, dtype=torch.float32, device=device)
+        self._structs[p] = _abi.BleTreeArena(ctypes.pointer(self.arenas[p]._struct), self.acc[p].data_ptr(), self.disc[p].data_ptr(),
+                                             self.flown[p].data_ptr(), self.ret[p].data_ptr())
+      self.parent = torch.zeros(n, beam, dtype=torch.int32, device=device)
+      self.choice = torch.zeros(depth, n, beam, dtype=torch.int32, device=device)
+      self.action = torch.zeros(n, dtype=torch.uint8, device=device)
+      self.best_plan = torch.zeros(depth * self.segment, n, dtype=torch.uint8, device=device)
+      self.best_return = torch.zeros(n, dtype=torch.float32, device=device)
+      self.q = torch.zeros(n, 3, dtype=torch.float32, device=device) if action_values else None
+      self.visits = torch.zeros(n, 3, dtype=torch.int32, device=device) if action_values else None
+
+  def node_struct(self, level: int) -> _abi.BleTreeArena:
+    return self._structs[level & 1]
+
+
 class ReferenceError_(Exception):
   """Base for conditions on which the reference raises inside the transition."""
 
@@ -824,6 +885,88 @@ class VecSimulator:
                                                ctypes.byref(hist), out.data_ptr(), _lib.OBS_DIM, self.rollout_flags.data_ptr(), arena.n,
                                                dev.stream_ptr(self.device)), 'ble_observe_leaves_f32')
     return out
+
+  # ------------------------------------------------------------------ plan by beam search
+  def tree_buffers(self, depth: int, beam_width: int, segment: int = 4, action_values: bool = False) -> 'TreeBuffers':
+    """Everything a tree_search of this depth, beam width and segment writes, allocated once (TreeBuffers): two node arenas, the parent and
+    choice lists and the results.  A search that is given its buffers allocates nothing, as a graph capture needs."""
+    if self.has_fleet:
+      raise ValueError('tree_search: a fleet (set_fleet) has no look-ahead kernel; fly one vehicle per batch (set_vehicle)')
+    return TreeBuffers(self, depth, beam_width, segment, action_values)
+
+  @_on_own_device
+  def tree_search(self, depth: int, beam_width: int, segment: int = 4, action_repeat: int = 1, gamma: float = 0.993,
+                  noise_seed: Optional[int] = None, belief: Optional[WindBelief] = None, substeps: int = SUBSTEPS,
+                  action_values: bool = False, leaf_score=None, buffers: Optional['TreeBuffers'] = None,
+                  trace: Optional[list] = None) -> 'TreeSearch':
+    """Plan by beam search: a shared-prefix tree of action plans, `depth` levels of one action flown segment * action_repeat agent
+    steps each, the best `beam_width` nodes of every level kept per environment -- depth x (`ble_tree_expand_f32`,
+    `ble_tree_select_f32`), then `ble_tree_finish_f32`.  Systematic and deterministic: there is no random stream.  With
+    3^depth <= 3 * beam_width nothing is cut and the search is the enumeration of all 3^depth plans at the cost of flying every prefix
+    once.  A node reached by actions (a_1 .. a_d) holds bit for bit the state, return and steps_flown rollout_plans(leaves=) gives
+    the plan a_1 x segment, .., a_d x segment; the children of a node that is not OK are the node carried on (a = 0) and two void
+    nodes (return NaN), which order last.
+    noise_seed / belief: rollout_plans' winds (neither: the forecast; never both).
+    leaf_score: a callable (leaves, returns [n, C], steps_flown [n, C]) -> score [n, C] float32 that the finish orders by in place of
+    the returns -- a learned terminal value (VecBeamSearchAgent(leaf_value=)); leaves is the last level's arena, a leaf arena of this
+    simulator with C = leaves.leaves_per_env leaves per environment (observe_leaves takes it).
+    action_values: also q [n, 3], the best key among the last level's nodes under each first action (-Inf: none finite), and visits
+    [n, 3], the number of its non-void nodes.  buffers: tree_buffers(depth, beam_width, segment, action_values) to write into.  trace: a list
+    that receives (level, returns [n, C_d] clone, parent [n, beam_width] clone) after every selection (tests; not capturable).
+    Returns TreeSearch(action [n] u8, best_plan [depth * segment, n] u8, best_return [n] f32, q, visits, returns [n, C] f32,
+    steps_flown [n, C] i32, leaves): an environment that is not OK gets all STAY and best_return 0, one without a finite return all
+    STAY and -Inf.  The tensors are the buffers' own, overwritten by the next search.
+    Nothing of the simulator is written; flags of the imagined flights go to rollout_flags, never err_flags.  Asynchronous on the
+    current stream, no host synchronisation (capturable in a HIP graph).  Not for fleets."""
+    if self.has_fleet:
+      raise ValueError('tree_search: a fleet (set_fleet) has no look-ahead kernel; fly one vehicle per batch (set_vehicle)')
+    if belief is not None and noise_seed is not None:
+      raise ValueError('tree_search: belief and noise_seed are two winds; give one of them')
+    assert self.grid is not None, 'Must call set_grid (reset) before tree_search.'
+    depth, beam, segment, action_repeat = int(depth), int(beam_width), int(segment), int(action_repeat)
+    if segment < 1 or action_repeat < 1 or depth < 1 or depth * segment * action_repeat > _abi.ROLLOUT_MAX_STEPS:
+      raise ValueError(f'tree_search: depth, segment, action_repeat >= 1 and depth * segment * action_repeat <= {_abi.ROLLOUT_MAX_STEPS}, '
+                       f'not {depth} x {segment} x {action_repeat}')
+    if not 0.0 <= float(gamma) <= 1.0:
+      raise ValueError(f'tree_search: gamma in [0, 1], not {gamma}')
+    if buffers is None:
+      buffers = self.tree_buffers(depth, beam, segment, action_values)
+    if (buffers.sim is not self or buffers.depth != depth or buffers.beam != beam or buffers.segment != segment or
+        (action_values and buffers.q is None)):
+      raise ValueError(f'tree_search: buffers of another search (tree_buffers({depth}, {beam}, {segment}, action_values={bool(action_values)}) '
+                       'of this simulator)')
+    bf, n, stream = buffers, self.n, dev.stream_ptr(self.device)
+    for arena in bf.arenas:
+      if arena is not None:
+        self._check_leaf_arena(arena, arena.leaves_per_env)
+    gen = None if noise_seed is None else _abi.BleNoiseGen(int(noise_seed) & (2 ** 64 - 1), self.episode.data_ptr(), None, self.env_offset)
+    b = None if belief is None else self._belief_struct(belief)
+    parents, children = 1, 0                       # P_{d-1}, C_{d-1}
+    for level in range(1, depth + 1):
+      dst, src = bf.node_struct(level), bf.node_struct(level - 1) if level > 1 else _abi.BleTreeArena()
+      ex = _abi.BleTreeExpand(n, beam, depth, parents, children, segment, action_repeat, int(substeps), 0, float(gamma), self.grid.data_ptr(),
+                              self.grid_env_stride, bf.parent.data_ptr(), src, dst)
+      _lib.check(self.lib.ble_tree_expand_f32(ctypes.byref(self._struct), ctypes.byref(ex), None if gen is None else ctypes.byref(gen),
+                                              None if b is None else ctypes.byref(b), self.rollout_flags.data_ptr(), stream), 'ble_tree_expand_f32')
+      children = 3 * parents
+      sel = _abi.BleTreeSelect(n, children, beam, bf.ret[level & 1].data_ptr(), bf.parent.data_ptr(), bf.choice[level - 1].data_ptr())
+      _lib.check(self.lib.ble_tree_select_f32(ctypes.byref(sel), stream), 'ble_tree_select_f32')
+      if trace is not None:
+        trace.append((level, bf.ret[level & 1][:n * children].view(n, children).clone(), bf.parent.clone()))
+      parents = min(children, beam)
+    last = depth & 1
+    leaves = bf.arenas[last]
+    returns, flown = bf.ret[last].view(n, children), bf.flown[last].view(n, children)
+    score = None
+    if leaf_score is not None:
+      score = leaf_score(leaves, returns, flown)
+      assert score.dtype == torch.float32 and score.is_contiguous() and tuple(score.shape) == (n, children) and score.device == self.device
+    fin = _abi.BleTreeFinish(n, children, beam, depth, segment, returns.data_ptr(), dev.ptr(score), self.state['status'].data_ptr(),
+                             bf.choice.data_ptr(), bf.best_plan.data_ptr(), bf.action.data_ptr(), bf.best_return.data_ptr(),
+                             dev.ptr(bf.q) if action_values else None, dev.ptr(bf.visits) if action_values else None)
+    _lib.check(self.lib.ble_tree_finish_f32(ctypes.byref(fin), stream), 'ble_tree_finish_f32')
+    return TreeSearch(bf.action, bf.best_plan, bf.best_return, bf.q if action_values else None, bf.visits if action_values else None, returns,
+                      flown, leaves, buffers=bf)
 
   @property
   def active_count(self) -> torch.Tensor:

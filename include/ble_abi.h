@@ -1558,6 +1558,114 @@ int ble_qnet_ppo_step_grouped_f32(const ble_ppo_grouped_f32* g, const ble_train_
  */
 int ble_ac_act_grouped_f32(const ble_qnet_grouped_f32* pop, const ble_ac_sample* sample, float* logp, void* stream);
 
+/* ----------------------------------------------------------------------------------------------- plan by beam search
+ * A shared-prefix tree of action plans, searched level by level: D levels, one EDGE = one action flown segment * action_repeat agent
+ * steps.  Per environment P_0 = 1 (the environment itself), C_d = 3 P_{d-1} children at level d, P_d = min(C_d, B) parents for the next;
+ * child index c = 3 r + a, r the parent's rank in the previous selection, a in {0 DOWN, 1 STAY, 2 UP}.  A level is ble_tree_expand_f32
+ * followed by ble_tree_select_f32; ble_tree_finish_f32 closes the search.  Added without a new ABI version.
+ *
+ * A node arena (ble_tree_arena) holds the nodes of one level, node (e, c) at index e * C_d + c: `state`, a leaf arena in the sense of
+ * ble_rollout_leaves_f32 (every array that call writes), and what the rollout lane keeps in registers across steps: acc (the discounted
+ * return so far, fp64), disc (gamma^flown as the rollout multiplies it up, fp64), flown (int32), and ret = (float)acc.  Two arenas of
+ * n * 3 B nodes serve a whole search, alternating as source and destination.
+ *
+ * ble_tree_expand_f32: one lane per (e, r, a).  The lane loads node parent[e][r] of `src` -- at level 1 (parent_children == 0)
+ * environment e of `st`, with acc 0, disc 1, flown 0 --, flies the edge with ble_rollout_f32's / ble_rollout_belief_f32's loop body and
+ * stores the child into index e * 3 n_parents + c of `dst`.  The grid, the noise key (seed, env_offset + e, episode[e]), the belief slab
+ * and the per-episode cache are environment e's, whatever the node.  A non-void node reached by (a_1 .. a_d) holds, bit for bit, the
+ * state, (float)acc and flown ble_rollout_leaves_f32 gives the plan a_1 x segment, .., a_d x segment flown from environment e in the same
+ * wind.  A parent whose status is not OK flies nothing: its a = 0 child is the parent carried on unchanged (state, acc, disc, flown), its
+ * a = 1 and a = 2 children are VOID: the same copy with acc = NaN.  A node whose acc is NaN is void: it flies nothing and all its
+ * children are void.  st, the history and every cache are never written; flags go to err_flags -- give it a word of its own, as for
+ * ble_rollout_f32.  noise / belief: ble_rollout_leaves_f32's two winds (neither: the forecast).
+ * BLE_E_INVALID_ARG before any HIP call: NULL st, state array, ex, wind_grid, dst.state or an array of it, dst.acc / disc / flown / ret;
+ * n < 0; beam outside 1 .. BLE_TREE_MAX_BEAM; n * 3 * beam >= 2^31; segment < 1, action_repeat < 1, depth < 1 or
+ * depth * segment * action_repeat > BLE_ROLLOUT_MAX_STEPS; substeps outside 1 .. BLE_MAX_SUBSTEPS; gamma NaN or outside [0, 1]; a
+ * negative grid_env_stride or noise->env_offset; both noise and belief; what ble_rollout_belief_f32 refuses of a belief, a belief whose n
+ * is not ex->n included; an invalid st->vehicle; reserved_ != 0; level 1 (parent_children == 0) with n_parents != 1; a later level with a
+ * NULL parent, src.state (or an array of it), src.acc / disc / flown, parent_children not a multiple of 3 in 3 .. 3 * beam, or n_parents
+ * outside 1 .. min(parent_children, beam); an array of dst.state that is the same array of st or of src.state (st is never written, and
+ * a level is not expanded in place).  n == 0: BLE_OK without a launch.  A fleet has no form of this call.
+ */
+#define BLE_TREE_MAX_BEAM 256
+struct ble_tree_arena {
+  const ble_state_f32* state;                /* a leaf arena of n * 3 * beam environments (its vehicle and episode cache are not read) */
+  double* acc;                               /* device [n * 3 * beam] */
+  double* disc;                              /* device [n * 3 * beam] */
+  int32_t* flown;                            /* device [n * 3 * beam] */
+  float* ret;                                /* device [n * 3 * beam]: (float)acc; of a level, [n][C_d] */
+};
+struct ble_tree_expand {
+  int64_t n;                                 /* source environments */
+  int32_t beam;                              /* B, 1 .. BLE_TREE_MAX_BEAM: the row length of parent */
+  int32_t depth;                             /* D >= 1: the levels of the whole search (bounds the plan: D * segment * action_repeat) */
+  int32_t n_parents;                         /* P_{d-1}: 1 at level 1 */
+  int32_t parent_children;                   /* C_{d-1}: 0 at level 1 (the parents are st's environments) */
+  int32_t segment;                           /* >= 1 plan entries per edge */
+  int32_t action_repeat;                     /* >= 1 agent steps per plan entry */
+  int32_t substeps;                          /* 1 .. BLE_MAX_SUBSTEPS */
+  int32_t reserved_;                         /* 0 */
+  double gamma;                              /* finite, 0 <= gamma <= 1 */
+  const float* wind_grid;                    /* as for ble_step_f32 */
+  int64_t grid_env_stride;
+  const int32_t* parent;                     /* device [n][beam]: ble_tree_select_f32's list of the level above; level 1: not read */
+  struct ble_tree_arena src;                 /* the level above; level 1: not read */
+  struct ble_tree_arena dst;                 /* this level, written */
+};
+int ble_tree_expand_f32(const ble_state_f32* st, const struct ble_tree_expand* ex, const ble_noise_gen* noise, const ble_gp_belief* belief,
+                        uint32_t* err_flags, void* stream);
+
+/*
+ * ble_tree_select_f32: one wavefront per environment over ret [n][C], the returns of a level's children, in ble_plan_select_f32's order
+ * with k := c: a finite return before a non-finite one, then the return descending (-0 == +0), then c ascending.  The first
+ * min(C, beam) children in that order become parent[e][0 ..] and, the same numbers, choice[e][0 ..] -- the caller keeps one choice list
+ * per level, [D][n][beam], for the walk back.  Entries from min(C, beam) on are not written.  Integer compares only, no atomics.
+ * BLE_E_INVALID_ARG before any HIP call: NULL sel, ret, parent or choice; n < 0; beam outside 1 .. BLE_TREE_MAX_BEAM; n_children not a
+ * multiple of 3 in 3 .. 3 * beam; n * 3 * beam >= 2^31.  n == 0: BLE_OK without a launch.
+ */
+struct ble_tree_select {
+  int64_t n;
+  int32_t n_children;                        /* C_d */
+  int32_t beam;                              /* B */
+  const float* ret;                          /* device [n][C_d] */
+  int32_t* parent;                           /* device [n][beam] out */
+  int32_t* choice;                           /* device [n][beam] out: this level's list */
+};
+int ble_tree_select_f32(const struct ble_tree_select* sel, void* stream);
+
+/*
+ * ble_tree_finish_f32: one wavefront per environment over the C_D children of the last level.  The key of a child is score[e][c]
+ * (NULL: ret[e][c]; with a leaf value, ble_plan_bootstrap_f32's score of the last arena) in the order above.  The child of rank 0 is
+ * walked back through choice -- the action of level d is c_d % 3 and c_{d-1} = choice[d - 1][e][c_d / 3] -- giving
+ *   best_plan [D * segment][n]   each level's action repeated over its segment
+ *   action [n]                   the first of them
+ *   best_return [n]              the key of that child, bits unchanged
+ * An environment whose source is not OK (source_status[e] != 0) gets best_plan all STAY, action STAY and best_return +0.0f; one with no
+ * finite key gets all STAY and best_return -Inf (ble_plan_select_f32's answer).  On request (q and visits both given), with the meaning
+ * and encoding of ble_plan_action_values_f32: q[e][a] the best key among the children whose level-1 action is a, -Inf when none of them
+ * has a finite key; visits[e][a] the number of non-void children (ret not NaN) whose level-1 action is a.
+ * BLE_E_INVALID_ARG before any HIP call: NULL fin, ret, source_status, choice, best_plan, action or best_return; exactly one of q and
+ * visits; n < 0; beam outside 1 .. BLE_TREE_MAX_BEAM; n_children not a multiple of 3 in 3 .. 3 * beam; depth < 1, segment < 1 or
+ * depth * segment > BLE_ROLLOUT_MAX_STEPS; depth == 1 with n_children != 3; n * 3 * beam >= 2^31.  n == 0: BLE_OK without a launch.
+ */
+struct ble_tree_finish {
+  int64_t n;
+  int32_t n_children;                        /* C_D */
+  int32_t beam;                              /* B */
+  int32_t depth;                             /* D */
+  int32_t segment;
+  const float* ret;                          /* device [n][C_D]: the last arena's ret */
+  const float* score;                        /* device [n][C_D], or NULL: ret */
+  const uint8_t* source_status;              /* device [n]: st->status */
+  const int32_t* choice;                     /* device [D][n][beam]: levels 1 .. D - 1 are read */
+  uint8_t* best_plan;                        /* device [D * segment][n] out */
+  uint8_t* action;                           /* device [n] out */
+  float* best_return;                        /* device [n] out */
+  float* q;                                  /* device [n][3] out, or NULL */
+  int32_t* visits;                           /* device [n][3] out, or NULL */
+};
+int ble_tree_finish_f32(const struct ble_tree_finish* fin, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
