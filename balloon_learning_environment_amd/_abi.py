@@ -394,3 +394,22 @@ class BlePpoGroupedF32(ctypes.Structure):
               ('transposed_stride', ctypes.c_int64), ('rows_per_member', ctypes.c_int64), ('lr', ctypes.c_void_p),
               ('clip', ctypes.c_void_p), ('value_coef', ctypes.c_void_p), ('entropy_coef', ctypes.c_void_p), ('old_logp', ctypes.c_void_p),
               ('advantage', ctypes.c_void_p)]
+
+
+TD_GROUPED_QUANTILE = 0                              # BLE_TD_GROUPED_QUANTILE; the DQN kinds are TD_DQN_* + 1
+
+
+class BleTdGroupedF32(ctypes.Structure):
+  """struct ble_td_grouped_f32: a grouped QR-DQN / DQN update of P networks of one shape on P * B rows: member 0's buffers (the target
+  image among them) and the strides between members, the loss kind and the per-member learning rates and Huber thresholds [P] (device
+  pointers)."""
+  _fields_ = [('tr', BleQnetTrainF32), ('members', ctypes.c_int32), ('reserved_', ctypes.c_int32), ('member_stride', ctypes.c_int64),
+              ('transposed_stride', ctypes.c_int64), ('rows_per_member', ctypes.c_int64), ('kind', ctypes.c_int32),
+              ('reserved2_', ctypes.c_int32), ('lr', ctypes.c_void_p), ('kappa', ctypes.c_void_p)]
+
+
+class BleExploreGroupedF32(ctypes.Structure):
+  """struct ble_explore_grouped_f32: epsilon-greedy over n = P * R actions, row p R + r keyed by (seed[p], r, step) at epsilon[p];
+  epsilon (float32 [P]) and seed (uint64 [P]) are device pointers."""
+  _fields_ = [('n', ctypes.c_int64), ('members', ctypes.c_int32), ('reserved_', ctypes.c_int32), ('epsilon', ctypes.c_void_p),
+              ('seed', ctypes.c_void_p), ('step', ctypes.c_uint64)]

@@ -10,6 +10,11 @@ the flights they would fly alone, P at a time.
 (`ble_qnet_ppo_step_grouped_f32`) gives member p the bytes its own `PPOTrainer` gives it on its B rows, with its own learning rate, clip
 and coefficients; `copy_members` and `scale_hyper` are the exploit and explore steps of population-based training
 (train_lib.run_pbt_loop_vec).
+
+`PopulationQTrainer` is the same for the replay learners: one grouped QR-DQN or DQN update
+(`ble_qnet_td_step_grouped_f32`) on P * B rows drawn from one `VecPopulationReplayBuffer` gives member p the bytes its own
+`QNetworkTrainer` / `DQNTrainer` gives it, with its own learning rate, Huber threshold, replay seed and target image
+(train_lib.run_population_training_loop_vec).
 """
 import ctypes
 from typing import Dict, Optional, Sequence, Union
@@ -399,6 +404,227 @@ class PopulationPPOTrainer:
       self._graphs.clear()                     # (Adam's constants are arguments of the captured launches)
     self.seed = int(d['seed'])
     self.eps, self.b1, self.b2, self.gamma, self.lam, self.normalize_advantage = hyper
+    self.population.images.copy_(d['images'])
+    for k in self._TENSORS:
+      getattr(self, k).copy_(d[k])
+
+
+Q_KINDS = {'quantile': _abi.TD_GROUPED_QUANTILE, 'dqn_mse': _abi.TD_DQN_MSE + 1, 'dqn_huber': _abi.TD_DQN_HUBER + 1}
+Q_HYPER = ('lr', 'kappa')                                 # the replay learners' per-member hyperparameters, device [P] float32 each
+
+
+def _per_member_q(name: str, value, members: int) -> np.ndarray:
+  """_per_member for Q_HYPER: finite, and a Huber threshold > 0."""
+  a = _per_member(name, value, members)
+  if name == 'kappa' and not (a > 0).all():
+    raise ValueError(f'kappa must be > 0, not {a.tolist()}')
+  return a
+
+
+class PopulationQTrainer:
+  """QR-DQN / DQN training of a QNetworkPopulation, all P members in one update.
+
+    pop = QNetworkPopulation(qnet.QNetwork.from_params(qnet.init_params('quantile')), 16)
+    trainer = PopulationQTrainer(pop, kind='quantile', lr=[2e-6 * 1.5 ** p for p in range(16)], seed=0)
+    replay = qnet_train.VecPopulationReplayBuffer(16, env.num_envs // 16, 1024)
+    train_lib.run_population_training_loop_vec(env, trainer, replay, num_iterations=..., steps_per_iteration=..., epsilon=[...])
+
+  kind: 'quantile' (QNetworkTrainer's update), 'dqn_mse' or 'dqn_huber' (DQNTrainer's, one-atom networks).  lr, kappa: scalars or
+  length-P sequences, held as device [P] float32 tensors of those names (kappa is read by the quantile loss alone).  seed: a scalar
+  (member p draws its replay batches and explores with seed + p) or a length-P sequence, held as `seeds`, device int64 [P] read as
+  uint64.  The trainer trains population.images in place; it owns target, weights_t, grad, adam_m, adam_v ([P, stride] each), one
+  adam_step and one replay counter (the members update in lockstep).  Member p's images hold the bytes a QNetworkTrainer / DQNTrainer
+  of member p with lr[p], kappa[p] and seed seeds[p] holds after the same rows (member_trainer_state(p) is that trainer's state_dict)."""
+
+  _TENSORS = ('target', 'weights_t', 'adam_m', 'adam_v', 'adam_step', 'counter', 'seeds') + Q_HYPER
+
+  def __init__(self, population: QNetworkPopulation, *, kind: str = 'quantile', lr: Union[float, Sequence[float]] = 2e-6,
+               kappa: Union[float, Sequence[float]] = 1.0, eps: float = 2e-5, gamma: float = 0.993, update_horizon: int = 5,
+               seed: Union[int, Sequence[int]] = 0, b1: float = 0.9, b2: float = 0.999):
+    if kind not in Q_KINDS:
+      raise ValueError(f'kind is one of {sorted(Q_KINDS)}, not {kind!r}')
+    if kind != 'quantile' and population.num_atoms != 1:
+      raise ValueError(f'{kind!r} trains one-atom networks, not {population.num_atoms} atoms')
+    self.population, self.kind = population, kind
+    self.device = d = population.device
+    self.members = p = population.members
+    self.num_layers, self.hidden_units, self.num_atoms = population.shape
+    self.eps, self.b1, self.b2 = float(eps), float(b1), float(b2)
+    self.gamma, self.update_horizon = float(gamma), int(update_horizon)
+    self._net = population._net
+    lay = self._layout(1)
+    self.transposed_floats = int(lay.transposed_floats)
+    self.transposed_stride = member_stride_for(max(self.transposed_floats, 64))
+    with torch.cuda.device(d):
+      for name, value in zip(Q_HYPER, (lr, kappa)):
+        setattr(self, name, torch.from_numpy(_per_member_q(name, value, p)).to(d))
+      self.seeds = qnet_train.member_seeds(seed, p, d)
+      self.target = population.images.clone()
+      self.weights_t = torch.zeros(p, self.transposed_stride, dtype=torch.float32, device=d)
+      self.grad = torch.zeros_like(population.images)
+      self.adam_m = torch.zeros_like(population.images)
+      self.adam_v = torch.zeros_like(population.images)
+      self.adam_step = torch.zeros(1, dtype=torch.int64, device=d)
+      self.counter = torch.zeros(1, dtype=torch.int64, device=d)       # the update counter every member's replay draw is keyed by
+      self.err_flags = torch.zeros(1, dtype=torch.int32, device=d)
+    self._retranspose()
+    self._agents: Dict[int, VecPopulationAgent] = {}
+    self._ws: Dict[int, tuple] = {}
+    self._graphs: dict = {}
+
+  # ---- plumbing
+  @property
+  def images(self) -> torch.Tensor:
+    return self.population.images
+
+  def _struct(self, batch_rows: int, workspace: Optional[torch.Tensor] = None, apply_update: bool = True) -> _abi.BleTdGroupedF32:
+    pop = self.population
+    tr = _abi.BleQnetTrainF32(pop._net, self.target.data_ptr(), self.weights_t.data_ptr(), self.grad.data_ptr(), self.adam_m.data_ptr(),
+                              self.adam_v.data_ptr(), self.adam_step.data_ptr(), dev.ptr(workspace) or None, self.b1, self.b2, 0.0, self.eps,
+                              0.0, 1 if apply_update else 0)
+    return _abi.BleTdGroupedF32(tr, self.members, 0, pop.member_stride, self.transposed_stride, int(batch_rows), Q_KINDS[self.kind], 0,
+                                self.lr.data_ptr(), self.kappa.data_ptr())
+
+  def _layout(self, batch_rows: int) -> _abi.BleQnetTrainLayout:
+    out = _abi.BleQnetTrainLayout()
+    g = _abi.BleTdGroupedF32(_abi.BleQnetTrainF32(self._net), self.members, 0, 0, 0, int(batch_rows), Q_KINDS[self.kind])
+    _lib.call('ble_qnet_td_grouped_workspace_f32', ctypes.byref(g), ctypes.byref(out))
+    return out
+
+  _retranspose = PopulationPPOTrainer._retranspose
+
+  def workspace(self, batch_rows: int):
+    """(workspace tensor, layout, loss [P * B]) of B rows per member (allocated on first use, which must not be inside a capture)."""
+    def make():
+      lay = self._layout(batch_rows)
+      with torch.cuda.device(self.device):
+        return (torch.zeros(max(lay.total, 64), dtype=torch.float32, device=self.device), lay,
+                torch.zeros(self.members * batch_rows, dtype=torch.float32, device=self.device))
+    return dev.first_use(self._ws, int(batch_rows), make,
+                         f'PopulationQTrainer: run one update at {batch_rows} rows per member before capturing it')
+
+  def check_errors(self) -> None:
+    qnet_train._check_flags(self.err_flags)
+
+  # ---- acting
+  @dev.on_own_device
+  def act(self, obs: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The live images' greedy actions over P * R rows, rows [p R, (p + 1) R) member p's (ble_qnet_forward_grouped_f32,
+    BLE_POP_HEAD_Q): what member p's own trainer's act gives its rows.  No host synchronisation."""
+    n = obs.shape[0]
+    assert n >= self.members and n % self.members == 0, f'{n} rows for {self.members} members'
+    agent = self._agents.get(n)
+    if agent is None:
+      agent = self._agents[n] = VecPopulationAgent(self.population, n // self.members, 'q')
+    return agent.act(obs, out)
+
+  # ---- the update
+  @dev.on_own_device
+  def train_on_batch(self, batch: qnet_train.TrainBatch, apply_update: bool = True) -> torch.Tensor:
+    """One grouped update on a batch of P * B rows (rows [p B, (p + 1) B) member p's): the per-row losses [P * B] (a view of a buffer
+    the next update at this size overwrites)."""
+    assert batch.batch_size >= self.members and batch.batch_size % self.members == 0, f'{batch.batch_size} rows for {self.members} members'
+    rows = batch.batch_size // self.members
+    ws, _, loss = self.workspace(rows)
+    g = self._struct(rows, ws, apply_update)
+    _lib.call('ble_qnet_td_step_grouped_f32', ctypes.byref(g), ctypes.byref(batch.struct), loss.data_ptr(), self.err_flags.data_ptr(),
+              dev.stream_ptr(self.device))
+    return loss
+
+  @dev.on_own_device
+  def train_step(self, replay: 'qnet_train.VecPopulationReplayBuffer', batch_size: int = 32) -> torch.Tensor:
+    """Sample B rows per member (member p keyed by (seeds[p], update counter)) and update: per-row losses [P * B] on the device, no
+    host synchronisation.  A captured graph of this batch size (capture()) replays it."""
+    g = self._graphs.get(batch_size)
+    if g is not None and g[1] is replay:
+      g[0].replay()
+      return g[2]
+    return self._update(replay, batch_size)
+
+  def _update(self, replay, batch_size: int) -> torch.Tensor:
+    if replay.prioritized or getattr(replay, 'members', None) != self.members:
+      raise ValueError(f'PopulationQTrainer samples a VecPopulationReplayBuffer of its {self.members} members')
+    return self.train_on_batch(replay.sample(batch_size, self.seeds, self.counter))
+
+  def capture(self, replay, batch_size: int = 32) -> torch.Tensor:
+    """Records one update (grouped sample + grouped train step) into a HIP graph that train_step(replay, batch_size) replays from then
+    on: the counters, seeds and hyperparameters are device memory, so each replay draws a new batch, takes a new Adam step and reads
+    their current values.  Runs one eager update first (the lazy allocations) -- a real update; returns its per-row losses."""
+    first = self.train_step(replay, batch_size)
+    graph, loss = dev.capture(self.device, lambda: self._update(replay, batch_size))
+    self._graphs[batch_size] = (graph, replay, loss)
+    return first
+
+  @dev.on_own_device
+  def sync_target(self) -> None:
+    """Every member's target image = its online image, in one copy."""
+    self.target.copy_(self.population.images)
+
+  def views(self, batch_rows: int) -> dict:
+    """The workspace's tensors of the last update at B rows per member, member-major: 'acts' (every online layer's output, [P, B, ld]
+    each), 'logits' and 'target_logits' [P, B, 3 * atoms], 'targets' [P, B, atoms], 'dlogits' [P, B, ld], 'loss' [P, B]."""
+    ws, lay, loss = self.workspace(batch_rows)
+    p, b, ld, out = self.members, int(batch_rows), lay.ld, qnet.NUM_ACTIONS * self.num_atoms
+    n = p * b
+
+    def mat(off, cols, width):
+      return ws[off:off + n * cols].view(p, b, cols)[:, :, :width]
+    return {'acts': [mat(lay.acts + l * n * ld, ld, ld) for l in range(self.num_layers)],
+            'logits': mat(lay.acts + (self.num_layers - 1) * n * ld, ld, out), 'target_logits': mat(lay.target_logits, ld, out),
+            'targets': mat(lay.targets, self.num_atoms, self.num_atoms), 'dlogits': mat(lay.dlogits, ld, ld), 'loss': loss.view(p, b)}
+
+  # ---- population-based training
+  @dev.on_own_device
+  def copy_members(self, src: torch.Tensor, dst: torch.Tensor) -> None:
+    """Rows dst of the images, the target, weights_t, adam_m, adam_v and the hyperparameter tensors become rows src (device int64
+    index tensors of one length, dst without repeats).  The seeds stay: a copy draws its own batches and explores its own way.  No host
+    synchronisation."""
+    assert src.shape == dst.shape and src.dim() == 1 and src.dtype == dst.dtype == torch.int64
+    for t in (self.population.images, self.target, self.weights_t, self.adam_m, self.adam_v) + tuple(getattr(self, k) for k in Q_HYPER):
+      t.index_copy_(0, dst, t.index_select(0, src))
+
+  @dev.on_own_device
+  def scale_hyper(self, name: str, dst: torch.Tensor, factor) -> None:
+    """hyper[name][dst] *= factor (a float, or a float32 device tensor of dst's length): a float32 product on the device."""
+    if name not in Q_HYPER:
+      raise ValueError(f'scale_hyper: {name!r} is not one of {Q_HYPER}')
+    t = getattr(self, name)
+    f = factor if isinstance(factor, torch.Tensor) else torch.full((dst.numel(),), float(factor), dtype=torch.float32, device=self.device)
+    assert f.dtype == torch.float32 and f.shape == dst.shape
+    t.index_copy_(0, dst, t.index_select(0, dst) * f)
+
+  # ---- export and checkpoints
+  def member(self, p: int) -> qnet.QNetwork:
+    """A copy of member p's live parameters as a QNetwork."""
+    return self.population.member(p)
+
+  def member_trainer_state(self, p: int) -> dict:
+    """Member p's part as the state_dict() of its own trainer -- QNetworkTrainer (kind 'quantile') or DQNTrainer (loss_type 'mse' /
+    'huber'): that trainer's load_state_dict of it continues member p alone, on member_buffer(p) of the replay."""
+    p = self.population._index(p)
+    n = self.population.packed_floats
+    seed = int(self.seeds[p].item()) & (2 ** 64 - 1)
+    d = {'shape': self.population.shape, 'seed': seed, 'weights': self.population.images[p, :n].clone(), 'target': self.target[p, :n].clone(),
+         'adam_m': self.adam_m[p, :n].clone(), 'adam_v': self.adam_v[p, :n].clone(), 'adam_step': self.adam_step.clone(),
+         'counter': self.counter.clone(),
+         'hyper': (float(self.lr[p].item()), self.eps, self.b1, self.b2, float(self.kappa[p].item()), self.gamma, self.update_horizon)}
+    if self.kind != 'quantile':
+      d['loss_type'] = self.kind[len('dqn_'):]
+    return d
+
+  def state_dict(self) -> dict:
+    return {'shape': self.population.shape, 'members': self.members, 'kind': self.kind, 'images': self.population.images.clone(),
+            'hyper': (self.eps, self.b1, self.b2, self.gamma, self.update_horizon),
+            **{k: getattr(self, k).clone() for k in self._TENSORS}}
+
+  def load_state_dict(self, d: dict) -> None:
+    """Restores in place (every tensor keeps its address: captured graphs stay valid unless a host-side argument changed)."""
+    assert tuple(d['shape']) == self.population.shape and int(d['members']) == self.members, 'checkpoint of another population'
+    assert d['kind'] == self.kind, f"checkpoint of a {d['kind']!r} trainer"
+    hyper = tuple(d['hyper'])
+    if hyper != (self.eps, self.b1, self.b2, self.gamma, self.update_horizon):
+      self._graphs.clear()                     # (Adam's constants are arguments of the captured launches)
+    self.eps, self.b1, self.b2, self.gamma, self.update_horizon = hyper
     self.population.images.copy_(d['images'])
     for k in self._TENSORS:
       getattr(self, k).copy_(d[k])

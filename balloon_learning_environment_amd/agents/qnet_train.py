@@ -399,3 +399,96 @@ def explore(actions: torch.Tensor, epsilon: float, seed: int, step: int) -> torc
   ex = _abi.BleExploreF32(actions.numel(), float(epsilon), 0, int(seed) & (2 ** 64 - 1), int(step) & (2 ** 64 - 1))
   _lib.call('ble_qnet_explore_u8', ctypes.byref(ex), actions.data_ptr(), dev.stream_ptr(actions.device))
   return actions
+
+
+def member_seeds(seed, members: int, device) -> torch.Tensor:
+  """The per-member seeds of a population as a device int64 [P] tensor (the kernels read the bits as uint64): a scalar s gives member p
+  s + p, a length-P sequence is taken as given; both modulo 2^64."""
+  a = np.asarray(seed, dtype=object)
+  vals = [int(a) + p for p in range(members)] if a.ndim == 0 else [int(v) for v in a.reshape(-1)]
+  if len(vals) != members:
+    raise ValueError(f'seed: a scalar or {members} values, not {len(vals)}')
+  return torch.from_numpy(np.array([v & (2 ** 64 - 1) for v in vals], np.uint64).view(np.int64)).to(device)
+
+
+class VecPopulationReplayBuffer(VecReplayBuffer):
+  """The replay memory of a population of P learners of R environments each: ONE VecReplayBuffer ring of P * R columns,
+  columns [p R, (p + 1) R) member p's, filled by add() with the P * R rows of a VecBalloonEnv step.  sample(B, seeds, counter) draws B
+  rows PER MEMBER into a TrainBatch of P * B rows (ble_replay_sample_grouped_f32): rows [p B, (p + 1) B) are what member p's own
+  VecReplayBuffer of its R columns (member_buffer(p)) gives sample(B, seeds[p], counter), with the index's column + p R.  Prioritized
+  replay has no grouped form."""
+
+  def __init__(self, members: int, rows_per_member: int, capacity_steps: int, update_horizon: int = 5, gamma: float = 0.993,
+               device='cuda:0'):
+    self.members, self.rows_per_member = int(members), int(rows_per_member)
+    if self.members < 1 or self.rows_per_member < 1:
+      raise ValueError('a population replay has at least one member of at least one environment')
+    super().__init__(self.members * self.rows_per_member, capacity_steps, update_horizon, gamma, device)
+
+  def batch_buffers(self, batch_size: int) -> TrainBatch:
+    """The TrainBatch of P * B rows of B rows per member."""
+    rows = self.members * int(batch_size)
+    return dev.first_use(self._batches, rows, lambda: TrainBatch(rows, self.device),
+                         f'VecPopulationReplayBuffer: sample once at {batch_size} rows per member before capturing it in a graph')
+
+  @dev.on_own_device
+  def sample(self, batch_size: int, seeds: torch.Tensor, counter: Optional[torch.Tensor] = None) -> TrainBatch:
+    """B transitions per member into this buffer's batch of P * B rows (overwritten by the next sample at that size).  seeds: device
+    int64 [P] (member_seeds), read as uint64; counter: the int64 [1] device update counter every member's draw is keyed by, advanced
+    once (default: the buffer's own).  No host synchronisation."""
+    assert seeds.dtype == torch.int64 and seeds.is_contiguous() and seeds.numel() == self.members and seeds.device == self.device
+    bt = self.batch_buffers(int(batch_size))
+    rp = self.struct(self.counter if counter is None else counter)
+    _lib.call('ble_replay_sample_grouped_f32', ctypes.byref(rp), self.members, seeds.data_ptr(), ctypes.byref(bt.struct),
+              self.err_flags.data_ptr(), dev.stream_ptr(self.device))
+    return bt
+
+  def member_buffer(self, p: int) -> VecReplayBuffer:
+    """A copy of member p's R columns as a VecReplayBuffer of its own (same steps written, its own update counter at 0)."""
+    if not 0 <= int(p) < self.members:
+      raise IndexError(f'member {p} of a population of {self.members}')
+    r = self.rows_per_member
+    cols = slice(int(p) * r, (int(p) + 1) * r)
+    solo = VecReplayBuffer(r, self.capacity, self.update_horizon, self.gamma, self.device)
+    for k in ('obs', 'action', 'reward', 'terminal', 'episode_end'):
+      getattr(solo, k).copy_(getattr(self, k)[:, cols])
+    solo.cursor = self.cursor
+    solo.count.fill_(self.cursor)
+    return solo
+
+  def state_dict(self) -> dict:
+    return {**super().state_dict(), 'members': self.members}
+
+  def load_state_dict(self, d: dict) -> None:
+    assert int(d['members']) == self.members, 'checkpoint of another population'
+    super().load_state_dict(d)
+
+
+def _epsilons(epsilon, members: int) -> np.ndarray:
+  """A scalar or a length-P sequence as float32 [P], each in [0, 1] (the entry point cannot see device values)."""
+  a = np.asarray(epsilon, np.float64)
+  a = np.full(members, float(a)) if a.ndim == 0 else a.reshape(-1)
+  if a.shape != (members,):
+    raise ValueError(f'epsilon: a scalar or {members} values, not {a.shape[0]}')
+  if not ((a >= 0.0) & (a <= 1.0)).all():
+    raise ValueError(f'epsilon must lie in [0, 1], not {a.tolist()}')
+  return a.astype(np.float32)
+
+
+def explore_grouped(actions: torch.Tensor, epsilon, seeds: torch.Tensor, step: int) -> torch.Tensor:
+  """epsilon-greedy in place on the uint8 device actions of a population, P = len(seeds) members of actions.numel() / P rows each
+  (ble_qnet_explore_grouped_u8): row p R + r is keyed by (seeds[p], r, step) and explores at epsilon[p] -- member p's own explore() on
+  its rows.  epsilon: a scalar or a length-P sequence (validated, then uploaded), or a float32 device tensor [P] the caller keeps in
+  [0, 1] (no upload, no host synchronisation); seeds: device int64 [P] (member_seeds)."""
+  if actions.dtype != torch.uint8 or not actions.is_contiguous():
+    raise ValueError('explore_grouped: actions must be a contiguous uint8 tensor (the kernel writes numel() bytes from data_ptr())')
+  members = int(seeds.numel())
+  if seeds.dtype != torch.int64 or not seeds.is_contiguous() or seeds.device != actions.device or members < 1 or actions.numel() % members:
+    raise ValueError('explore_grouped: seeds is a contiguous int64 [P] tensor on the actions\' device, P dividing the number of actions')
+  if not isinstance(epsilon, torch.Tensor):
+    epsilon = torch.from_numpy(_epsilons(epsilon, members)).to(actions.device)
+  if epsilon.dtype != torch.float32 or not epsilon.is_contiguous() or epsilon.numel() != members or epsilon.device != actions.device:
+    raise ValueError('explore_grouped: epsilon is a scalar, P values, or a contiguous float32 [P] tensor on the actions\' device')
+  ex = _abi.BleExploreGroupedF32(actions.numel(), members, 0, epsilon.data_ptr(), seeds.data_ptr(), int(step) & (2 ** 64 - 1))
+  _lib.call('ble_qnet_explore_grouped_u8', ctypes.byref(ex), actions.data_ptr(), dev.stream_ptr(actions.device))
+  return actions

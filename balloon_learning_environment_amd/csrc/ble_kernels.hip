@@ -46,6 +46,7 @@
 #include "ble_replay.h"
 #include "ble_population.h"
 #include "ble_population_train.h"
+#include "ble_population_td.h"
 
 using namespace ble;
 
@@ -1762,9 +1763,9 @@ namespace {
 bool member_stride_ok(const QnetShape& s, int64_t member_stride) { return member_stride >= s.offset[s.layers] && member_stride % 64 == 0; }
 
 // launch_dense_stack for a population: P members of R rows each, member p on the image w + p member_stride; two buffers in turn, or
-// (keep) every layer kept: layer l of all P R rows at base + l P R ld.
+// (keep) every layer kept: layer l of all P R rows at base + l P R ld; the last layer to `last_out` instead when that is set.
 int launch_dense_stack_grouped(const QnetShape& s, const float* w, int64_t member_stride, const float* x, int64_t ldx, int64_t members,
-                               int64_t rows_per_member, float* base, void* stream, bool keep = false) {
+                               int64_t rows_per_member, float* base, void* stream, bool keep = false, float* last_out = nullptr) {
   const int64_t n = members * rows_per_member;
   const int64_t tiles_per_member = (rows_per_member + kQnetRows - 1) / kQnetRows;
   for (int l = 0; l < s.layers; ++l) {
@@ -1772,7 +1773,7 @@ int launch_dense_stack_grouped(const QnetShape& s, const float* w, int64_t membe
     const bool first = l == 0, last = l == s.layers - 1;
     const auto dense = first ? (last ? ble_qnet_dense_grouped_kernel<true, false> : ble_qnet_dense_grouped_kernel<true, true>)
                              : (last ? ble_qnet_dense_grouped_kernel<false, false> : ble_qnet_dense_grouped_kernel<false, true>);
-    float* y = base + (keep ? l : l & 1) * n * s.ld;
+    float* y = last && last_out ? last_out : base + (keep ? l : l & 1) * n * s.ld;
     const int status = launch_grid(dense, dim3((unsigned)(groups * tiles_per_member * members)), kQnetBlock, stream, x, ldx, s.k[l], s.kp[l],
                                    w + s.offset[l], member_stride, y, s.ld, groups, rows_per_member, tiles_per_member);
     if (status != BLE_OK) return status;
@@ -1908,18 +1909,29 @@ int ble_qnet_ppo_step_f32(const ble_qnet_train_f32* tr, const ble_ppo_f32* ppo, 
 }
 
 // ---------------------------------------------------------------------------------------------------------------- populations, by gradient
+extern "C++" {      // (templates: this block sits inside the file's extern "C")
 namespace {
-// The sizes of a grouped update: what the workspace query reads.
-bool grouped_sizes_ok(const ble_ppo_grouped_f32* g) {
-  if (!g || !qnet_ok(&g->tr.net) || g->tr.net.num_atoms != 2 || g->reserved_ != 0) return false;
+// The loss of a grouped TD update from its descriptor's kind: kKindQr, BLE_TD_DQN_MSE or BLE_TD_DQN_HUBER; anything else is refused.
+bool td_grouped_kind_ok(int32_t kind) { return kind == BLE_TD_GROUPED_QUANTILE || kind == BLE_TD_DQN_MSE + 1 || kind == BLE_TD_DQN_HUBER + 1; }
+int td_grouped_kind(int32_t kind) { return kind == BLE_TD_GROUPED_QUANTILE ? kKindQr : kind - 1; }
+// what each grouped descriptor asks of the network's atoms: PPO an actor-critic's two, a DQN kind one, the quantile loss any
+bool grouped_atoms_ok(const ble_ppo_grouped_f32* g) { return g->tr.net.num_atoms == 2; }
+bool grouped_atoms_ok(const ble_td_grouped_f32* g) {
+  return g->reserved2_ == 0 && td_grouped_kind_ok(g->kind) && (g->kind == BLE_TD_GROUPED_QUANTILE || g->tr.net.num_atoms == 1);
+}
+// The sizes of a grouped update (G: ble_ppo_grouped_f32 or ble_td_grouped_f32): what the workspace query reads.
+template <class G>
+bool grouped_sizes_ok(const G* g) {
+  if (!g || !qnet_ok(&g->tr.net) || !grouped_atoms_ok(g) || g->reserved_ != 0) return false;
   const int64_t P = g->members, B = g->rows_per_member;
   if (P < 1 || B < 1 || P > 65535 || B > BLE_TRAIN_MAX_BATCH || P * B > BLE_TRAIN_MAX_BATCH) return false;
   if (P * wgrad_slabs(B) > 65535) return false;                                          // (grid z of dW)
   const int64_t groups = qnet_shape(&g->tr.net).ld / kQnetCols;
   return groups * P * ((B + kQnetRows - 1) / kQnetRows) < 2147483648LL;
 }
-// train_layout at n = P B, but the slabs are the member's (a function of B) and every member has its own partial sums.
-ble_qnet_train_layout grouped_train_layout(const QnetShape& s, int64_t P, int64_t B) {
+// train_layout at n = P B, but the slabs are the member's (a function of B) and every member has its own partial sums.  num_atoms:
+// the floats per row of `targets` (PPO's aux: 2).
+ble_qnet_train_layout grouped_train_layout(const QnetShape& s, int64_t P, int64_t B, int num_atoms) {
   ble_qnet_train_layout y{};
   const int64_t ld = s.ld, L = s.layers, n = P * B;
   y.ld = ld;
@@ -1928,7 +1940,7 @@ ble_qnet_train_layout grouped_train_layout(const QnetShape& s, int64_t P, int64_
   auto take = [&](int64_t floats) { const int64_t o = at; at += qnet_round_up(floats, 64); return o; };
   y.acts = take(L * n * ld);
   y.target_logits = take(n * ld);
-  y.targets = take(n * 2);
+  y.targets = take(n * num_atoms);
   y.dlogits = take(n * ld);
   y.scratch = take(4 * n * ld);
   y.partial = take(y.slabs > 1 ? P * y.slabs * s.max_block : 0);
@@ -1937,25 +1949,44 @@ ble_qnet_train_layout grouped_train_layout(const QnetShape& s, int64_t P, int64_
   y.transposed_floats = s.transposed_floats;
   return y;
 }
-bool grouped_update_ok(const ble_ppo_grouped_f32* g, const ble_train_batch_f32* bt, const float* loss) {
-  if (!grouped_sizes_ok(g) || !batch_ok(bt, false, true, true) || !loss) return false;
+// the per-member arrays and per-row inputs of each descriptor beyond lr: all there, 4-byte aligned (lr: grouped_update_ok)
+bool grouped_arrays_ok(const ble_ppo_grouped_f32* g) {
+  return g->clip && g->value_coef && g->entropy_coef && g->old_logp && g->advantage &&
+         aligned(3, g->clip, g->value_coef, g->entropy_coef, g->old_logp, g->advantage);
+}
+// (kappa is the quantile loss's alone, as in the plain entry points; a target network is what every grouped TD kind has)
+bool grouped_arrays_ok(const ble_td_grouped_f32* g) {
+  return (g->kind != BLE_TD_GROUPED_QUANTILE || g->kappa) && aligned(3, g->kappa) && g->tr.target && aligned(15, g->tr.target);
+}
+template <class G>
+bool grouped_update_ok(const G* g, const ble_train_batch_f32* bt, const float* loss) {
+  constexpr bool kTd = std::is_same<G, ble_td_grouped_f32>::value;
+  if (!grouped_sizes_ok(g) || !batch_ok(bt, kTd, true, true) || !loss) return false;
   const ble_qnet_train_f32& tr = g->tr;
   if (!tr.net.weights || !tr.grad || !tr.workspace) return false;
   if (bt->batch != (int64_t)g->members * g->rows_per_member) return false;
   const QnetShape s = qnet_shape(&tr.net);
   if (!member_stride_ok(s, g->member_stride)) return false;
   if (tr.net.num_layers > 1 && (!tr.weights_t || g->transposed_stride < s.transposed_floats || g->transposed_stride % 64 != 0)) return false;
-  if (!g->lr || !g->clip || !g->value_coef || !g->entropy_coef || !g->old_logp || !g->advantage) return false;
+  if (!g->lr || !aligned(3, g->lr) || !grouped_arrays_ok(g)) return false;
   if (tr.apply_update &&
       (!tr.adam_m || !tr.adam_v || !tr.adam_step || !std::isfinite(tr.adam_b1) || !std::isfinite(tr.adam_b2) || !std::isfinite(tr.adam_eps)))
     return false;
-  return aligned(15, tr.net.weights, tr.grad, tr.workspace, tr.adam_m, tr.adam_v, tr.weights_t) &&
-         aligned(3, g->lr, g->clip, g->value_coef, g->entropy_coef, g->old_logp, g->advantage);
+  return aligned(15, tr.net.weights, tr.grad, tr.workspace, tr.adam_m, tr.adam_v, tr.weights_t);
 }
 
-// One grouped update on a checked batch, beside TrainStep: the shape, the workspace's parts and the stages in launch order.
+// One grouped update on a checked batch, beside TrainStep: the shape, the workspace's parts and the stages in launch order.  It serves
+// both grouped descriptors: PPO's (ppo != nullptr) and the TD one (td != nullptr), which differ in the loss stage and in the TD kinds'
+// target pass; the online forward, the backward and the optimiser read the fields the two descriptors share.
 struct GroupedTrainStep {
-  const ble_ppo_grouped_f32* g;
+  // what the stages after the loss read of either descriptor
+  struct Members {
+    int64_t member_stride, transposed_stride;
+    const float* lr;
+  };
+  const ble_ppo_grouped_f32* ppo;
+  const ble_td_grouped_f32* td;
+  const Members g;
   const ble_qnet_train_f32* tr;
   const ble_train_batch_f32* bt;
   void* stream;
@@ -1965,18 +1996,44 @@ struct GroupedTrainStep {
   const int64_t ld, tstride;
   float* const ws;
 
-  GroupedTrainStep(const ble_ppo_grouped_f32* g_, const ble_train_batch_f32* bt_, void* stream_)
-      : g(g_), tr(&g_->tr), bt(bt_), stream(stream_), s(qnet_shape(&g_->tr.net)), P(g_->members), B(g_->rows_per_member), n(P * B),
-        lay(grouped_train_layout(s, P, B)), ld(lay.ld), tstride(s.layers > 1 ? g_->transposed_stride : 0), ws(g_->tr.workspace) {}
+  template <class G>
+  GroupedTrainStep(const G* g_, const ble_train_batch_f32* bt_, void* stream_)
+      : ppo(pick<ble_ppo_grouped_f32>(g_)), td(pick<ble_td_grouped_f32>(g_)), g{g_->member_stride, g_->transposed_stride, g_->lr}, tr(&g_->tr),
+        bt(bt_), stream(stream_), s(qnet_shape(&g_->tr.net)), P(g_->members), B(g_->rows_per_member), n(P * B),
+        lay(grouped_train_layout(s, P, B, ppo != nullptr ? 2 : g_->tr.net.num_atoms)), ld(lay.ld),
+        tstride(s.layers > 1 ? g_->transposed_stride : 0), ws(g_->tr.workspace) {}
+  template <class W, class G>
+  static const W* pick(const G* g_) {
+    if constexpr (std::is_same<W, G>::value) return g_;
+    else return nullptr;
+  }
   float* acts(int l) const { return ws + lay.acts + l * n * ld; }
 
+  // a TD kind: the target images' pass on next_state first (ping-pong in scratch, its logits end in target_logits); then the online
+  // images on state, every layer kept
   int forward() const {
-    return launch_dense_stack_grouped(s, tr->net.weights, g->member_stride, bt->state, bt->state_stride, P, B, acts(0), stream, true);
+    if (td != nullptr) {
+      const int status = launch_dense_stack_grouped(s, tr->target, g.member_stride, bt->next_state, bt->state_stride, P, B, ws + lay.scratch,
+                                                    stream, false, ws + lay.target_logits);
+      if (status != BLE_OK) return status;
+    }
+    return launch_dense_stack_grouped(s, tr->net.weights, g.member_stride, bt->state, bt->state_stride, P, B, acts(0), stream, true);
   }
   int loss(float* row_loss, uint32_t* err_flags) const {
-    return launch_grid(ble_ppo_loss_grouped_kernel, dim3((unsigned)n), kTrainLossBlock, stream, (const float*)acts(s.layers - 1), ld,
-                       (const float*)bt->ret, (const uint8_t*)bt->action, g->old_logp, g->advantage, g->clip, g->value_coef, g->entropy_coef,
-                       B, ws + lay.targets, ws + lay.dlogits, row_loss, err_flags);
+    const float* logits = acts(s.layers - 1);
+    if (ppo != nullptr)
+      return launch_grid(ble_ppo_loss_grouped_kernel, dim3((unsigned)n), kTrainLossBlock, stream, logits, ld, (const float*)bt->ret,
+                         (const uint8_t*)bt->action, ppo->old_logp, ppo->advantage, ppo->clip, ppo->value_coef, ppo->entropy_coef, B,
+                         ws + lay.targets, ws + lay.dlogits, row_loss, err_flags);
+    const float* other = ws + lay.target_logits;
+    const int kind = td_grouped_kind(td->kind);
+    if (kind == kKindQr)
+      return launch_grid(ble_qr_loss_grouped_kernel, dim3((unsigned)n), kTrainLossBlock, stream, logits, other, ld, tr->net.num_actions,
+                         tr->net.num_atoms, (const float*)bt->ret, (const float*)bt->discount, (const uint8_t*)bt->action, td->kappa, B,
+                         ws + lay.targets, ws + lay.dlogits, row_loss, err_flags);
+    const auto kernel = kind == BLE_TD_DQN_MSE ? ble_td_loss_grouped_kernel<kTdDqnMse> : ble_td_loss_grouped_kernel<kTdDqnHuber>;
+    return launch_grid(kernel, dim3((unsigned)n), kTrainLossBlock, stream, logits, other, ld, tr->net.num_actions, (const float*)bt->ret,
+                       (const float*)bt->discount, (const uint8_t*)bt->action, B, ws + lay.targets, ws + lay.dlogits, row_loss, err_flags);
   }
   // TrainStep::backward with the member coordinate: the slabs and their rows come from B
   int backward() const {
@@ -1992,12 +2049,12 @@ struct GroupedTrainStep {
       int status = launch_grid(ble_qnet_wgrad_grouped_kernel,
                                dim3((unsigned)((s.kp[l] + 31) / 32), (unsigned)(s.mp[l] / kQnetCols), (unsigned)(P * slabs)), 64, stream, x,
                                l == 0 ? bt->state_stride : ld, s.k[l], s.kp[l], dy, ld, s.m[l], s.mp[l], B, slab_rows, slabs,
-                               slabs == 1 ? grad : ws + lay.partial, slabs == 1 ? g->member_stride : slabs * blk,
+                               slabs == 1 ? grad : ws + lay.partial, slabs == 1 ? g.member_stride : slabs * blk,
                                slabs == 1 ? (int64_t)0 : blk);
       if (status != BLE_OK) return status;
       if (slabs > 1) {
         status = launch_grid(ble_wgrad_reduce_grouped_kernel, dim3((unsigned)((blk + 255) / 256), (unsigned)P), 256, stream,
-                             (const float*)(ws + lay.partial), slabs, blk, blk, grad, g->member_stride);
+                             (const float*)(ws + lay.partial), slabs, blk, blk, grad, g.member_stride);
         if (status != BLE_OK) return status;
       }
       if (l == 0) break;
@@ -2018,25 +2075,59 @@ struct GroupedTrainStep {
     const int64_t image = s.offset[s.layers];
     return launch_grid(ble_adam_grouped_kernel, dim3((unsigned)((image + kAdamBlock - 1) / kAdamBlock), (unsigned)P), kAdamBlock, stream,
                        const_cast<float*>(tr->net.weights), tr->weights_t, (const float*)tr->grad, tr->adam_m, tr->adam_v, (const float*)corr,
-                       g->lr, g->member_stride, tstride, (float)tr->adam_b1, (float)(1.0 - tr->adam_b1), (float)tr->adam_b2,
+                       g.lr, g.member_stride, tstride, (float)tr->adam_b1, (float)(1.0 - tr->adam_b1), (float)tr->adam_b2,
                        (float)(1.0 - tr->adam_b2), tr->adam_eps, s);
   }
 };
-}  // namespace
 
-int ble_qnet_ppo_grouped_workspace_f32(const ble_ppo_grouped_f32* g, ble_qnet_train_layout* layout) {
-  if (!grouped_sizes_ok(g) || !layout) return BLE_E_INVALID_ARG;
-  *layout = grouped_train_layout(qnet_shape(&g->tr.net), g->members, g->rows_per_member);
-  return BLE_OK;
-}
-
-int ble_qnet_ppo_step_grouped_f32(const ble_ppo_grouped_f32* g, const ble_train_batch_f32* bt, float* loss, uint32_t* err_flags, void* stream) {
+// ble_qnet_ppo_step_grouped_f32 and ble_qnet_td_step_grouped_f32: forward, loss, backward, optimiser.
+template <class G>
+int launch_grouped_update(const G* g, const ble_train_batch_f32* bt, float* loss, uint32_t* err_flags, void* stream) {
   if (!grouped_update_ok(g, bt, loss)) return BLE_E_INVALID_ARG;
   const GroupedTrainStep t(g, bt, stream);
   if (const int status = t.forward(); status != BLE_OK) return status;
   if (const int status = t.loss(loss, err_flags); status != BLE_OK) return status;
   if (const int status = t.backward(); status != BLE_OK) return status;
   return g->tr.apply_update ? t.optimise() : BLE_OK;
+}
+}  // namespace
+}  // extern "C++"
+
+int ble_qnet_ppo_grouped_workspace_f32(const ble_ppo_grouped_f32* g, ble_qnet_train_layout* layout) {
+  if (!grouped_sizes_ok(g) || !layout) return BLE_E_INVALID_ARG;
+  *layout = grouped_train_layout(qnet_shape(&g->tr.net), g->members, g->rows_per_member, 2);
+  return BLE_OK;
+}
+
+int ble_qnet_ppo_step_grouped_f32(const ble_ppo_grouped_f32* g, const ble_train_batch_f32* bt, float* loss, uint32_t* err_flags, void* stream) {
+  return launch_grouped_update(g, bt, loss, err_flags, stream);
+}
+
+// ---------------------------------------------------------------------------------------------------------------- populations of replay learners
+int ble_qnet_td_grouped_workspace_f32(const ble_td_grouped_f32* g, ble_qnet_train_layout* layout) {
+  if (!grouped_sizes_ok(g) || !layout) return BLE_E_INVALID_ARG;
+  *layout = grouped_train_layout(qnet_shape(&g->tr.net), g->members, g->rows_per_member, g->tr.net.num_atoms);
+  return BLE_OK;
+}
+
+int ble_qnet_td_step_grouped_f32(const ble_td_grouped_f32* g, const ble_train_batch_f32* bt, float* loss, uint32_t* err_flags, void* stream) {
+  return launch_grouped_update(g, bt, loss, err_flags, stream);
+}
+
+int ble_replay_sample_grouped_f32(const ble_replay_f32* rp, int32_t members, const unsigned long long* seeds, const ble_train_batch_f32* bt,
+                                  uint32_t* err_flags, void* stream) {
+  if (!replay_ok(rp) || !batch_ok(bt) || members < 1 || rp->num_envs % members != 0 || bt->batch % members != 0 || !seeds || !aligned(7, seeds))
+    return BLE_E_INVALID_ARG;
+  return launch_sample_then_advance(ble_replay_sample_grouped_kernel, rp, bt, stream, *rp, *bt, seeds, (int64_t)(bt->batch / members),
+                                    (int64_t)(rp->num_envs / members), err_flags);
+}
+
+int ble_qnet_explore_grouped_u8(const ble_explore_grouped_f32* ex, uint8_t* action, void* stream) {
+  if (!ex || !action || ex->n < 0 || ex->n > 4LL * 2147483647LL * 256 || ex->members < 1 || ex->n % ex->members != 0 || ex->reserved_ != 0 ||
+      !ex->epsilon || !ex->seed || !aligned(3, ex->epsilon) || !aligned(7, ex->seed))
+    return BLE_E_INVALID_ARG;
+  return launch(ble_explore_grouped_kernel, ex->n, 256, 256, stream, action, (int64_t)ex->n, (int64_t)(ex->n / ex->members), ex->epsilon,
+                ex->seed, (uint64_t)ex->step);
 }
 
 // ---------------------------------------------------------------------------------------------------------------- imitation

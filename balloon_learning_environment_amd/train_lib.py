@@ -2,7 +2,8 @@
 schedule (min_replay_history, update_period, target_update_period counted in transitions) for the replay learners (QNetworkTrainer,
 DQNTrainer), the loop of an online learner (VecMLPAgent), the on-policy loop (PPOTrainer), the DAgger loop of an imitation learner
 (BCTrainer), the expert-iteration loop of a soft-target learner and a planner (SoftBCTrainer, VecLookaheadAgent) and population-based
-training of P on-policy learners in one batch (PopulationPPOTrainer); N environments per step.
+training of P on-policy learners in one batch (PopulationPPOTrainer) and of P replay learners in one batch (PopulationQTrainer);
+N environments per step.
 """
 from typing import Callable, List, Optional, Sequence, Tuple, Union
 
@@ -359,6 +360,106 @@ def run_pbt_loop_vec(env, trainer, rollout, *, num_iterations: int, epochs: int 
     s['lineage'] = pbt.lineage.tolist()
     s['lr'] = trainer.lr.tolist()
     s['round'] = None if rnd is None else {k: v.tolist() for k, v in rnd.items()}
+    stats.append(s)
+  return stats
+
+
+def run_population_training_loop_vec(env, trainer, replay, *, num_iterations: int, steps_per_iteration: int,
+                                     max_episode_length: int = 960, min_replay_history: int = 500, update_period: int = 4,
+                                     target_update_period: int = 100,
+                                     epsilon: Union[float, Sequence[float], Callable[[int], float]] = 0.01,
+                                     updates_per_step: Optional[int] = None, batch_size: int = 32, capture_graph: bool = True,
+                                     ready_every: Optional[int] = None, truncation: float = 0.0, perturb: Sequence[float] = (0.8, 1.25),
+                                     seed: int = 0, controller: Optional[PBTController] = None) -> List[dict]:
+  """Trains P replay learners in one batch (agents/population.py: PopulationQTrainer with a qnet_train.VecPopulationReplayBuffer(P, R,
+  ...)) on `env` (auto_reset) of P * R environments, environment rows [p R, (p + 1) R) member p's, for num_iterations x
+  steps_per_iteration vector steps.  Each step: every member's greedy actions (trainer.act), epsilon-greedy per member
+  (qnet_train.explore_grouped, member p keyed by (trainer.seeds[p], its row, step) at its own rate), env.step, replay.add, then the
+  grouped updates -- each one update of every member on batch_size rows of its own columns.
+
+  The schedule is run_training_loop_vec's, applied PER MEMBER: a vector step adds R transitions to each member, so it runs
+  R / update_period grouped updates (the fraction carried over; updates_per_step overrides that count) once each member holds
+  min_replay_history transitions; every member's target is synced every target_update_period // update_period updates.  The 960-step
+  episode limit is enforced per environment.  epsilon: a float, a length-P sequence (an epsilon ladder: member p explores at
+  epsilon[p]) or a function of the transitions a member has added so far.  The update is captured into one graph on first use.
+
+  ready_every with truncation > 0 makes it population-based training: every ready_every iterations a round (pbt_decide through a
+  PBTController) on the mean return of the episodes each member finished since the last round; each of the bottom `truncation` share
+  becomes a copy of a member of the top share (trainer.copy_members: images, targets, Adam moments, lr and kappa -- NOT the replay
+  contents, which stay the columns' own, and not the seeds) with its lr multiplied by one of the two `perturb` factors
+  (trainer.scale_hyper).  truncation = 0, the default, is a plain P-seed study.  controller: a PBTController to continue.
+
+  Returns run_training_loop_vec's dicts (mean_loss: the mean over all members' rows; transitions: all members') plus, as lists of P,
+  member_mean_loss, member_mean_return and member_episodes (this iteration's), lr, and with a controller lineage and round
+  ({'fitness', 'src', 'dst'} as lists on a round's iteration, else None).  One host synchronisation per iteration: its end."""
+  n, dev_ = env.num_envs, env.device
+  p, r = replay.members, replay.rows_per_member
+  assert trainer.members == p and replay.num_envs == n == p * r, 'the replay ring has one column per environment, R per member'
+  pbt = controller
+  if pbt is None and ready_every is not None:
+    pbt = PBTController(p, dev_, ready_every=ready_every, truncation=truncation, perturb=perturb, explore=('lr',), seed=seed)
+  sync_every = max(1, target_update_period // update_period)
+  ladder = None if callable(epsilon) else torch.from_numpy(qnet_train._epsilons(epsilon, p)).to(dev_)
+  obs = env.reset()
+  actions = torch.zeros(n, dtype=torch.uint8, device=dev_)
+  book = _EpisodeBook(n, dev_, max_episode_length)
+  zero = torch.zeros((), dtype=torch.float32, device=dev_)
+  updates, pending, step, member_transitions = 0, 0.0, 0, 0
+  captured = False
+  stats = []
+  for _ in range(num_iterations):
+    it_sum = torch.zeros(p, dtype=torch.float32, device=dev_)
+    it_episodes = torch.zeros(p, dtype=torch.int64, device=dev_)
+    it_loss = torch.zeros(p, dtype=torch.float32, device=dev_)
+    for _ in range(steps_per_iteration):
+      trainer.act(obs, actions)
+      qnet_train.explore_grouped(actions, epsilon(member_transitions) if ladder is None else ladder, trainer.seeds, step)
+      end_mask = book.end_mask()
+      next_obs, reward, terminal = env.step(actions, end_mask=end_mask)
+      episode_end = terminal | end_mask
+      replay.add(obs, actions, reward, terminal, episode_end)
+      ended = episode_end.bool().view(p, r)
+      ended_returns = torch.where(ended, (book.ep_return + reward).view(p, r), zero)
+      if pbt is not None:
+        pbt.step(ended_returns, ended)
+      it_sum += ended_returns.sum(dim=1)
+      it_episodes += ended.sum(dim=1)
+      book.step(reward, episode_end)
+      obs = next_obs
+      step += 1
+      member_transitions += r
+      if member_transitions >= min_replay_history and replay.cursor > replay.update_horizon:
+        if updates_per_step is not None:
+          todo = int(updates_per_step)
+        else:
+          pending += r / update_period
+          todo = int(pending)
+          pending -= todo
+        for _ in range(todo):
+          if capture_graph and not captured:
+            loss = trainer.capture(replay, batch_size)        # (its first, eager update is a real one)
+            captured = True
+          else:
+            loss = trainer.train_step(replay, batch_size)
+          book.update(loss)
+          it_loss += loss.view(p, -1).mean(dim=1)
+          updates += 1
+          if updates % sync_every == 0:
+            trainer.sync_target()
+    rnd = pbt.end_iteration(trainer) if pbt is not None else None
+    env.check_errors()
+    replay.check_errors()
+    trainer.check_errors()
+    done = book.updates
+    s = book.finish_iteration(steps_per_iteration)
+    eps = it_episodes.tolist()
+    s['member_mean_loss'] = [v / max(done, 1) for v in it_loss.tolist()]
+    s['member_episodes'] = eps
+    s['member_mean_return'] = [v / e if e else float('nan') for v, e in zip(it_sum.tolist(), eps)]
+    s['lr'] = trainer.lr.tolist()
+    if pbt is not None:
+      s['lineage'] = pbt.lineage.tolist()
+      s['round'] = None if rnd is None else {k: v.tolist() for k, v in rnd.items()}
     stats.append(s)
   return stats
 

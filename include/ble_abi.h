@@ -1558,6 +1558,79 @@ int ble_qnet_ppo_step_grouped_f32(const ble_ppo_grouped_f32* g, const ble_train_
  */
 int ble_ac_act_grouped_f32(const ble_qnet_grouped_f32* pop, const ble_ac_sample* sample, float* logp, void* stream);
 
+/* --------------------------------------------------------------------------------- a population of replay learners
+ * ble_qnet_td_step_grouped_f32: one QR-DQN or DQN update of P = members networks of ONE shape on a batch of P * B rows, rows
+ * [p B, (p + 1) B) member p's.  The contract is §3q's and §3r's: member p's part of every result -- rows [p B, (p + 1) B) of loss and of
+ * the workspace's acts, target_logits, targets and dlogits; the image-sized blocks at + p * member_stride of grad, net.weights, adam_m,
+ * adam_v and at + p * transposed_stride of weights_t -- holds the bytes ble_qnet_train_step_f32 (kind BLE_TD_GROUPED_QUANTILE) or
+ * ble_qnet_td_step_f32 with BLE_TD_DQN_MSE / BLE_TD_DQN_HUBER and BLE_TD_OPT_ADAM (kind = that BLE_TD_* + 1) gives member p's own
+ * trainer -- its online image, its target image tr.target + p * member_stride, lr[p], kappa[p] -- on those B rows: the objective of
+ * member p is the mean over ITS B rows, the dW slabs are wgrad_slabs(B)'s, every sum runs in the plain update's order.  No tolerance,
+ * no floating-point atomics.  The floats between images are neither read nor written; the padding inside a gradient image is written as
+ * 0.  One Adam step counter serves the population.  An action >= 3 sets BLE_FLAG_TRAIN_ACTION and zeroes that row only.  SARSA and
+ * BLE_TD_OPT_SGD have no grouped form.
+ *
+ * The workspace (ble_qnet_td_grouped_workspace_f32) is ble_qnet_train_workspace_f32's layout at a batch of P * B rows with
+ * ble_qnet_ppo_grouped_workspace_f32's two differences: slabs = the dW slabs of B rows, and partial holds P * slabs blocks when
+ * slabs > 1.  The query reads the network descriptor, members, rows_per_member, kind and both reserved fields only.
+ *
+ * BLE_E_INVALID_ARG before any HIP call: what ble_qnet_ppo_step_grouped_f32 refuses of the fields the two descriptors share and what
+ * ble_qnet_train_step_f32 / ble_qnet_td_step_f32 refuse of the batch (NULL next_state or discount among it); a kind outside the three;
+ * a DQN kind on a network whose num_atoms != 1; NULL tr.target, or one not 16-byte aligned; NULL lr; NULL kappa with the quantile kind
+ * (the DQN kinds do not read it); lr or kappa not 4-byte aligned; reserved_ or reserved2_ != 0.  The per-member arrays are DEVICE
+ * memory: the entry cannot see their values (a NaN learning rate, a kappa <= 0); the caller validates what it uploads
+ * (agents/population.py does: finite lr, kappa > 0).
+ */
+#define BLE_TD_GROUPED_QUANTILE 0            /* ble_td_grouped_f32.kind: this, BLE_TD_DQN_MSE + 1 or BLE_TD_DQN_HUBER + 1 */
+typedef struct ble_td_grouped_f32 {
+  ble_qnet_train_f32 tr;        /* the members' shape; net.weights, target, weights_t, grad, adam_m, adam_v = member 0's (target at the
+                                   images' member_stride); adam_step, workspace, adam_b1/b2/eps, apply_update shared; tr.lr and
+                                   tr.kappa not read */
+  int32_t members;              /* P >= 1 */
+  int32_t reserved_;            /* 0 */
+  int64_t member_stride;        /* floats between members in weights, target, grad, adam_m, adam_v: >= the image, a multiple of 64 */
+  int64_t transposed_stride;    /* floats between members' weights_t: >= transposed_floats, a multiple of 64 (any value with one layer) */
+  int64_t rows_per_member;      /* B >= 1; batch->batch must equal P * B; rows [p B, (p + 1) B) are member p's */
+  int32_t kind;                 /* BLE_TD_GROUPED_QUANTILE, BLE_TD_DQN_MSE + 1, BLE_TD_DQN_HUBER + 1 */
+  int32_t reserved2_;           /* 0 */
+  const float* lr;              /* device [P] */
+  const float* kappa;           /* device [P], > 0: the quantile kind's Huber thresholds (not read by the DQN kinds; may be NULL there) */
+} ble_td_grouped_f32;
+int ble_qnet_td_grouped_workspace_f32(const ble_td_grouped_f32* g, ble_qnet_train_layout* layout);
+int ble_qnet_td_step_grouped_f32(const ble_td_grouped_f32* g, const ble_train_batch_f32* batch, float* loss, uint32_t* err_flags, void* stream);
+
+/*
+ * ble_replay_sample_grouped_f32: ble_replay_sample_f32 for a population over ONE ring of N = replay->num_envs = P * R columns, columns
+ * [p R, (p + 1) R) member p's, into a batch of batch->batch = P * B rows.  Row p B + b draws from the Philox stream keyed by
+ * (seeds[p], b, *counter) exactly as the plain sampler does on a ring of R columns -- t over the same span, the column
+ * e = (e32 * R) >> 32, the window tested, emitted and gathered at column p R + e -- so rows [p B, (p + 1) B) are what
+ * ble_replay_sample_f32 writes from a ring holding only member p's R columns with seed seeds[p] and the same counter, with the index's
+ * column + p R.  A failed draw gives zeros, index (-1, -1) and BLE_FLAG_REPLAY_EMPTY for that row only.  The counter advances once per
+ * call (two launches; batch 0: none, as the plain call).
+ * BLE_E_INVALID_ARG before any HIP call: what ble_replay_sample_f32 refuses; members < 1; num_envs % members != 0;
+ * batch->batch % members != 0; NULL seeds or seeds not 8-byte aligned.  seeds: device uint64 [P].
+ */
+int ble_replay_sample_grouped_f32(const ble_replay_f32* replay, int32_t members, const unsigned long long* seeds,
+                                  const ble_train_batch_f32* batch, uint32_t* err_flags, void* stream);
+
+/*
+ * ble_qnet_explore_grouped_u8: ble_qnet_explore_u8 for a population of P members of R = n / P rows: row p R + r draws from the stream
+ * keyed by (seed[p], r, step) and becomes uniform in {0, 1, 2} when u < epsilon[p] -- member p's own ble_qnet_explore_u8 on its R
+ * rows, each member at its own exploration rate.
+ * BLE_E_INVALID_ARG before any HIP call: NULL ex or action; n < 0 or past ble_qnet_explore_u8's limit; members < 1; n % members != 0;
+ * NULL epsilon or seed; epsilon not 4-byte or seed not 8-byte aligned; reserved_ != 0.  epsilon and seed are DEVICE memory: the caller
+ * validates 0 <= epsilon <= 1 (agents/qnet_train.py's explore_grouped does, of what it uploads).
+ */
+typedef struct ble_explore_grouped_f32 {
+  int64_t n;                           /* P * R actions */
+  int32_t members;                     /* P >= 1 */
+  int32_t reserved_;                   /* 0 */
+  const float* epsilon;                /* device [P], each 0 .. 1 */
+  const unsigned long long* seed;      /* device [P] */
+  unsigned long long step;
+} ble_explore_grouped_f32;
+int ble_qnet_explore_grouped_u8(const ble_explore_grouped_f32* ex, uint8_t* action, void* stream);
+
 /* ----------------------------------------------------------------------------------------------- plan by beam search
  * A shared-prefix tree of action plans, searched level by level: D levels, one EDGE = one action flown segment * action_repeat agent
  * steps.  Per environment P_0 = 1 (the environment itself), C_d = 3 P_{d-1} children at level d, P_d = min(C_d, B) parents for the next;
