@@ -172,7 +172,8 @@ class BleTreeArena(ctypes.Structure):
 
 
 class BleTreeExpand(ctypes.Structure):
-  """struct ble_tree_expand: one level of a beam search: every selected parent's three children flown for one edge (ble_tree_expand_f32)."""
+  """struct ble_tree_expand: one level of a beam search: every selected parent's three children flown for one edge (ble_tree_expand_f32;
+  ble_tree_expand_scenarios_f32 takes the same struct with arenas of n * 3 * beam * M nodes, node (e, c, m) at (e C + c) M + m)."""
   _fields_ = [('n', ctypes.c_int64), ('beam', ctypes.c_int32), ('depth', ctypes.c_int32), ('n_parents', ctypes.c_int32),
               ('parent_children', ctypes.c_int32), ('segment', ctypes.c_int32), ('action_repeat', ctypes.c_int32), ('substeps', ctypes.c_int32),
               ('reserved_', ctypes.c_int32), ('gamma', ctypes.c_double), ('wind_grid', ctypes.c_void_p), ('grid_env_stride', ctypes.c_int64),

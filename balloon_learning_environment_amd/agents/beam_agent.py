@@ -28,7 +28,7 @@ class VecBeamSearchAgent:
   best beam_width B (<= 256) nodes of a level are expanded into 3 B children.  gamma: the discount of a plan's return.
   wind: 'belief' (default) -- forecast + the mean of the WindGP over the balloon's own measurements, fitted at every decision;
   'forecast' -- the forecast alone; 'truth' -- the wind the environments will fly (bind(noise_seed=)): a simulator-side upper bound.
-  Scenario winds have no tree ('scenarios' is refused).
+  Scenario winds are VecScenarioBeamSearchAgent's ('scenarios' is refused here).
   leaf_value: a critic -- an object with act_greedy(obs, value=) or else act(obs, value=), VecLookaheadAgent's rule --
   whose value of every node of the LAST level is added to its return before the final order: score = return + gamma^steps_flown *
   V(node) (`observe_leaves` -> the critic -> `ble_plan_bootstrap_f32`); the inner levels are ordered by their returns alone.  A node
@@ -39,8 +39,8 @@ class VecBeamSearchAgent:
   def __init__(self, beam_width: int = 27, depth: int = 6, segment: int = 4, action_repeat: int = 1, gamma: float = 0.993,
                wind: str = 'belief', leaf_value=None, action_values: bool = False, device='cuda:0', substeps: int = vec_state.SUBSTEPS):
     if wind == 'scenarios':
-      raise ValueError("VecBeamSearchAgent: wind='scenarios' has no tree (M end states per node); plan in the belief, or sample "
-                       "(VecLookaheadAgent)")
+      raise ValueError("VecBeamSearchAgent: wind='scenarios' is VecScenarioBeamSearchAgent's tree (M end states per node); here plan in "
+                       "the belief, the forecast or the truth")
     if wind not in WINDS:
       raise ValueError(f"VecBeamSearchAgent: wind is 'belief', 'forecast' or 'truth', not {wind!r}")
     if not 1 <= int(beam_width) <= _abi.TREE_MAX_BEAM:
@@ -175,3 +175,90 @@ class VecBeamSearchAgent:
 
   def get_name(self) -> str:
     return 'BeamSearchAgent'
+
+
+class VecScenarioBeamSearchAgent(VecBeamSearchAgent):
+  """VecBeamSearchAgent in SAMPLED winds: every edge of the tree is flown in each of num_scenarios (<= 16) winds drawn
+  from the WindGP's posterior, fitted at every decision (`fit_wind_scenarios`; the scenarios themselves are fixed over an
+  episode, only the conditioning moves), and every level is ordered by the risk score of its groups: the mean of the risk_tail smallest
+  scenario returns -- None = all of them, the expectation; 1 = the worst case; between them a CVaR.  The scenario streams are keyed as
+  VecLookaheadAgent keys them: by `seed`, or with bind(seeds=) by each environment's own seed -- an environment then plans the same in
+  any batch.  beam_width, depth, segment, action_repeat, gamma, action_values: the parent's; n * 3 * beam_width * num_scenarios < 2^31.
+  No leaf_value: it would need C * M observations per environment and decision."""
+
+  def __init__(self, beam_width: int = 27, depth: int = 6, segment: int = 4, action_repeat: int = 1, gamma: float = 0.993,
+               num_scenarios: int = 8, risk_tail: Optional[int] = None, seed: int = 0, leaf_value=None, action_values: bool = False,
+               device='cuda:0', substeps: int = vec_state.SUBSTEPS):
+    if leaf_value is not None:
+      raise ValueError('VecScenarioBeamSearchAgent: leaf_value has no scenario tree (C * M observations per environment and decision); '
+                       'plan in the belief (VecBeamSearchAgent)')
+    self.num_scenarios = int(num_scenarios)
+    self.risk_tail = self.num_scenarios if risk_tail is None else int(risk_tail)
+    if not (1 <= self.num_scenarios <= _abi.SCENARIO_MAX and 1 <= self.risk_tail <= self.num_scenarios):
+      raise ValueError(f'VecScenarioBeamSearchAgent: 1 <= num_scenarios <= {_abi.SCENARIO_MAX} and 1 <= risk_tail <= num_scenarios, '
+                       f'not {num_scenarios}, {risk_tail}')
+    # (the parent checks the shape of the tree and opens the device; of its winds it keeps refusing 'scenarios', so it is given another)
+    super().__init__(beam_width, depth, segment, action_repeat, gamma, 'forecast', None, action_values, device, substeps)
+    self.wind, self.seed = 'scenarios', int(seed)
+    self._seeds: Optional[torch.Tensor] = None
+
+  @dev.on_own_device
+  def bind(self, sim: vec_state.VecSimulator, seeds: Optional[torch.Tensor] = None, noise_seed=None) -> 'VecScenarioBeamSearchAgent':
+    """Attaches the simulator.  All buffers are allocated here, once: binding the same simulator (and the same `seeds` tensor) again
+    changes nothing.  seeds: int64 / uint64 device tensor [N], a seed per environment (read at every decision).  noise_seed: accepted
+    for the planners' common signature and unused -- no scenario is the truth."""
+    del noise_seed
+    if sim.has_fleet:
+      raise ValueError('VecScenarioBeamSearchAgent: a fleet (set_fleet) has no look-ahead kernel; fly one vehicle per batch (set_vehicle)')
+    if sim.device != self.device:
+      raise ValueError(f'VecScenarioBeamSearchAgent on {self.device} cannot plan for a simulator on {sim.device}')
+    if seeds is not None:
+      assert seeds.dtype in (torch.int64, torch.uint64) and seeds.is_contiguous() and tuple(seeds.shape) == (sim.n,), seeds.shape
+      assert seeds.device == self.device
+    same = self.sim is sim and self._seeds is seeds
+    self.sim, self._seeds = sim, seeds
+    if not same:
+      n, m = sim.n, self.num_scenarios
+      self.buffers = sim.tree_buffers(self.depth, self.beam_width, self.segment, self.with_action_values, m)
+      self.action, self.best_plan, self.best_return = self.buffers.action, self.buffers.best_plan, self.buffers.best_return
+      self.q, self.visits = self.buffers.q, self.buffers.visits
+      self._scenarios = vec_state.WindScenarios(torch.zeros(n, _abi.gp_scenario_doubles(m), dtype=torch.float64, device=self.device),
+                                                torch.zeros(n, dtype=torch.int32, device=self.device), m, self.seed, seeds)
+    return self
+
+  @dev.on_own_device
+  def act(self, obs: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None,
+          prior_probs: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """One decision for every environment of the bound simulator: the scenarios fitted now, the tree searched in them.  The parent's
+    contract: uint8 [N] device actions, nothing of the simulator written, asynchronous, capturable in a HIP graph."""
+    del obs, prior_probs
+    sim = self._bound()
+    if sim.has_fleet:
+      raise ValueError('VecScenarioBeamSearchAgent: the bound simulator flies a fleet now; a fleet has no look-ahead kernel')
+    scenarios = sim.fit_wind_scenarios(self.num_scenarios, seed=self.seed, seeds=self._seeds, out=self._scenarios)
+    self.result = sim.tree_search(self.depth, self.beam_width, self.segment, self.action_repeat, self.gamma, substeps=self.substeps,
+                                  action_values=self.with_action_values, buffers=self.buffers, scenarios=scenarios,
+                                  risk_tail=self.risk_tail)
+    if out is None:
+      return self.action
+    assert out.dtype == torch.uint8 and out.is_contiguous() and out.numel() == sim.n and out.device == self.device
+    out.view(-1).copy_(self.action)
+    return out
+
+  __call__ = act
+
+  def state_dict(self) -> dict:
+    """Nothing moves from one decision to the next -- the scenarios are refitted from the simulator's own history and their streams are
+    keyed by the environments' episode counters -- so a resume needs what keys the streams and shapes the score, to hold the resumed
+    agent to them."""
+    self._bound()
+    return {'seed': self.seed, 'num_scenarios': self.num_scenarios, 'risk_tail': self.risk_tail}
+
+  def load_state_dict(self, d: dict) -> None:
+    self._bound()
+    mine = self.state_dict()
+    if any(k in d and int(d[k]) != mine[k] for k in mine):
+      raise ValueError(f'VecScenarioBeamSearchAgent: a checkpoint of another agent ({ {k: d[k] for k in mine if k in d} }, this one {mine})')
+
+  def get_name(self) -> str:
+    return 'ScenarioBeamSearchAgent'

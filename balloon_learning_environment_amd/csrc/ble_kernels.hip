@@ -828,6 +828,8 @@ __global__ __launch_bounds__(256) void ble_eval_accumulate_kernel(StateDev st, c
 // scenario winds (a prior draw of the noise field conditioned on the measurements), the look-ahead flown in them and the risk score: after
 // ble_gp_belief.h (belief_wave_trip) and ScalarSeed / EnvSeed
 #include "ble_scenarios.h"
+// the beam search flown in the scenario winds: after ble_tree.h (the arenas) and ble_scenarios.h (the slab, the rollout's LDS)
+#include "ble_tree_scenarios.h"
 // fp64 primitive probe (test-only entry point): op 0 rcp seed, 1 d_rcp, 2 rsq seed, 3 d_rsqrt,
 // 4 d_sqrt_fast, 5 d_log_fast, 6 d_exp_fast, 7 sin (sincos_f64), 8 cos (sincos_f64)
 __global__ __launch_bounds__(256) void probe_f64_kernel(const double* x, double* y, int op, int64_t n) {
@@ -2402,37 +2404,43 @@ inline bool state_arrays_shared(const ble_state_f32* a, const ble_state_f32* b) 
   return false;
 }
 static_assert(kTreeMaxBeam == BLE_TREE_MAX_BEAM && kTreeMaxDepth == BLE_ROLLOUT_MAX_STEPS, "ble_tree.h and ble_abi.h disagree");
+
+// what both expand calls refuse of st and ex; nodes_per_child: 1, or the scenarios of a group
+inline bool tree_expand_ok(const ble_state_f32* st, const struct ble_tree_expand* ex, int nodes_per_child) {
+  if (!state_ok(st) || !ex || !ex->wind_grid || !state_ok(ex->dst.state) || !ex->dst.acc || !ex->dst.disc || !ex->dst.flown || !ex->dst.ret)
+    return false;
+  if (!tree_sizes_ok(ex->n, ex->beam) || ex->n * (int64_t)(3 * ex->beam) * nodes_per_child >= 2147483648LL || ex->segment < 1 ||
+      ex->action_repeat < 1 || ex->depth < 1 || (int64_t)ex->depth * ex->segment * ex->action_repeat > BLE_ROLLOUT_MAX_STEPS ||
+      ex->reserved_ != 0)
+    return false;
+  if (ex->substeps < 1 || ex->substeps > BLE_MAX_SUBSTEPS || ex->grid_env_stride < 0 ||
+      !(ex->gamma >= 0.0 && ex->gamma <= 1.0))                       // (a NaN gamma fails both comparisons)
+    return false;
+  if (state_arrays_shared(ex->dst.state, st)) return false;                             // st is never written
+  if (ex->parent_children == 0) return ex->n_parents == 1;                              // level 1
+  if (!ex->parent || !state_ok(ex->src.state) || !ex->src.acc || !ex->src.disc || !ex->src.flown) return false;
+  if (!tree_children_ok(ex->parent_children, ex->beam) || ex->n_parents < 1 || ex->n_parents > ex->parent_children || ex->n_parents > ex->beam)
+    return false;
+  return !(state_arrays_shared(ex->dst.state, ex->src.state) || ex->dst.acc == ex->src.acc || ex->dst.disc == ex->src.disc ||
+           ex->dst.flown == ex->src.flown);                                             // a level is not expanded in place
+}
+// struct ble_tree_expand as the expand kernels take it
+inline TreeExpandArgs tree_expand_args(const struct ble_tree_expand* ex) {
+  return TreeExpandArgs{ex->n, ex->n_parents, ex->parent_children, ex->beam, ex->segment * ex->action_repeat, ex->substeps, ex->gamma,
+                        ex->wind_grid, ex->grid_env_stride, ex->parent};
+}
 }  // namespace
 
 int ble_tree_expand_f32(const ble_state_f32* st, const struct ble_tree_expand* ex, const ble_noise_gen* noise, const ble_gp_belief* belief,
                         uint32_t* err_flags, void* stream) {
   if (noise != nullptr && belief != nullptr) return BLE_E_INVALID_ARG;                  // two winds
-  if (!state_ok(st) || !ex || !ex->wind_grid || !state_ok(ex->dst.state) || !ex->dst.acc || !ex->dst.disc || !ex->dst.flown || !ex->dst.ret)
-    return BLE_E_INVALID_ARG;
-  if (!tree_sizes_ok(ex->n, ex->beam) || ex->segment < 1 || ex->action_repeat < 1 || ex->depth < 1 ||
-      (int64_t)ex->depth * ex->segment * ex->action_repeat > BLE_ROLLOUT_MAX_STEPS || ex->reserved_ != 0)
-    return BLE_E_INVALID_ARG;
-  if (ex->substeps < 1 || ex->substeps > BLE_MAX_SUBSTEPS || ex->grid_env_stride < 0 || (noise != nullptr && noise->env_offset < 0) ||
-      !(ex->gamma >= 0.0 && ex->gamma <= 1.0))                       // (a NaN gamma fails both comparisons)
-    return BLE_E_INVALID_ARG;
+  if (!tree_expand_ok(st, ex, 1) || (noise != nullptr && noise->env_offset < 0)) return BLE_E_INVALID_ARG;
   BeliefDev b{nullptr, 0, nullptr};
   if (belief != nullptr && (!gp_belief(belief, &b) || belief->n != ex->n)) return BLE_E_INVALID_ARG;      // (a belief of another batch would be read out of bounds)
-  if (state_arrays_shared(ex->dst.state, st)) return BLE_E_INVALID_ARG;                 // st is never written
   const bool first = ex->parent_children == 0;
-  if (first) {
-    if (ex->n_parents != 1) return BLE_E_INVALID_ARG;
-  } else {
-    if (!ex->parent || !state_ok(ex->src.state) || !ex->src.acc || !ex->src.disc || !ex->src.flown) return BLE_E_INVALID_ARG;
-    if (!tree_children_ok(ex->parent_children, ex->beam) || ex->n_parents < 1 || ex->n_parents > ex->parent_children || ex->n_parents > ex->beam)
-      return BLE_E_INVALID_ARG;
-    if (state_arrays_shared(ex->dst.state, ex->src.state) || ex->dst.acc == ex->src.acc || ex->dst.disc == ex->src.disc ||
-        ex->dst.flown == ex->src.flown)
-      return BLE_E_INVALID_ARG;                                                         // a level is not expanded in place
-  }
   return with_vehicle<false>(st, nullptr, [&](auto veh) {
     if (ex->n == 0) return BLE_OK;
-    const TreeExpandArgs a{ex->n, ex->n_parents, ex->parent_children, ex->beam, ex->segment * ex->action_repeat, ex->substeps, ex->gamma,
-                           ex->wind_grid, ex->grid_env_stride, ex->parent};
+    const TreeExpandArgs a = tree_expand_args(ex);
     // level 1: the parents are st's environments (src.acc == NULL tells the kernel)
     const TreeArenaDev src = first ? TreeArenaDev{state_dev(st), nullptr, nullptr, nullptr, nullptr} : tree_arena_dev(ex->src);
     const TreeArenaDev dst = tree_arena_dev(ex->dst);
@@ -2446,6 +2454,25 @@ int ble_tree_expand_f32(const ble_state_f32* st, const struct ble_tree_expand* e
                     StepNoise{noise->seed, noise->episode, nullptr, (long long)noise->env_offset}, err_flags, veh);
     return launch(ble_tree_expand_kernel<kTreeWindForecast, decltype(veh)>, lanes, kStepBlock, kStepBlock, stream, state_dev(st), a, src, dst, b,
                   none, err_flags, veh);
+  });
+}
+
+int ble_tree_expand_scenarios_f32(const ble_state_f32* st, const struct ble_tree_expand* ex, const ble_gp_scenarios* scn,
+                                  const ble_scenario_gen* gen, uint32_t* err_flags, void* stream) {
+  ScenariosDev b;
+  if (!gp_scenarios(scn, &b) || !scenario_gen_ok(gen) || !tree_expand_ok(st, ex, scn->num) || scn->n != ex->n)
+    return BLE_E_INVALID_ARG;                                         // (scenarios of another batch would be read out of bounds)
+  const bool first = ex->parent_children == 0;
+  return with_vehicle<false>(st, nullptr, [&](auto veh) {
+    if (ex->n == 0) return BLE_OK;
+    const TreeExpandArgs a = tree_expand_args(ex);
+    // level 1: the parents are st's environments (src.acc == NULL tells the kernel)
+    const TreeArenaDev src = first ? TreeArenaDev{state_dev(st), nullptr, nullptr, nullptr, nullptr} : tree_arena_dev(ex->src);
+    const TreeArenaDev dst = tree_arena_dev(ex->dst);
+    return with_scenario_seed(gen, [&](auto seed, ScenarioGen g) {
+      return launch(ble_tree_expand_scenarios_kernel<decltype(veh), decltype(seed)>, ex->n * (int64_t)(3 * ex->n_parents) * scn->num, kStepBlock,
+                    kStepBlock, stream, state_dev(st), a, src, dst, b, seed, g, err_flags, veh);
+    });
   });
 }
 

@@ -201,7 +201,8 @@ class VecBalloonArena:
                   noise_seed: Optional[int] = None, belief=None, **kw):
     """Plan by beam search from the current states without changing them: depth levels of one action flown segment * action_repeat
     agent steps, the best beam_width nodes kept per env and level -> TreeSearch(action, best_plan, best_return, q, visits, returns,
-    steps_flown, leaves); VecSimulator.tree_search.  noise_seed / belief: lookahead's winds."""
+    steps_flown, leaves, score); VecSimulator.tree_search.  noise_seed / belief: lookahead's winds; scenarios=, risk_tail= (a
+    WindScenarios of fit_wind_scenarios): the tree flown in M sampled winds and ordered by the risk score."""
     return self.sim.tree_search(depth, beam_width, segment, action_repeat, gamma, noise_seed=noise_seed, belief=belief, **kw)
 
   def fit_wind_belief(self, time_s: Optional[torch.Tensor] = None, out=None):

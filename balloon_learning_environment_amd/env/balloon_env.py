@@ -263,9 +263,17 @@ class VecBalloonEnv:
     """Plan by beam search from where each balloon is now, nothing of the environments changed: depth levels of one action flown
     segment * action_repeat agent steps, the best beam_width nodes kept per environment and level -> TreeSearch(action, best_plan,
     best_return, q, visits, returns, steps_flown, leaves) (VecSimulator.tree_search; action_values=, leaf_score=, buffers= go through).
-    wind: lookahead's 'truth', 'forecast' or 'belief' (fitted now); scenario winds have no tree."""
-    if wind not in ('truth', 'forecast', 'belief'):
-      raise ValueError(f"tree_search: wind is 'truth', 'forecast' or 'belief', not {wind!r}")
+    wind: lookahead's 'truth', 'forecast' or 'belief' (fitted now), or 'scenarios': num_scenarios (<= 16) winds sampled from the
+    WindGP's posterior, fitted now from streams keyed by this env's seed (arena.fit_wind_scenarios), every edge flown in each of them
+    and every level ordered by the mean of the risk_tail smallest scenario returns of a node (None: all of them); TreeSearch.returns is
+    then [N, C, M] and TreeSearch.score [N, C]."""
+    if wind not in ('truth', 'forecast', 'belief', 'scenarios'):
+      raise ValueError(f"tree_search: wind is 'truth', 'forecast', 'belief' or 'scenarios', not {wind!r}")
+    if wind == 'scenarios':
+      num_scenarios, risk_tail = kw.pop('num_scenarios', 8), kw.pop('risk_tail', None)
+      reuse = self._scenarios if (self._scenarios is not None and self._scenarios.num == int(num_scenarios)) else None
+      self._scenarios = self.arena.fit_wind_scenarios(num_scenarios, seed=self.arena._seed, out=reuse)
+      return self.arena.tree_search(depth, beam_width, segment, action_repeat, gamma, scenarios=self._scenarios, risk_tail=risk_tail, **kw)
     if wind == 'belief':
       self._belief = self.arena.fit_wind_belief(out=self._belief)
       return self.arena.tree_search(depth, beam_width, segment, action_repeat, gamma, belief=self._belief, **kw)
@@ -277,7 +285,9 @@ class VecBalloonEnv:
     -- num_plans, horizon, action_repeat, segment, gamma, wind ('belief' by default; 'scenarios' with num_scenarios, risk_tail), iterations, elite, seed,
     leaf_value (a critic whose value of every plan's end state is added to its return) -- planning in this batch's simulator.
     search='beam': agents.beam_agent.VecBeamSearchAgent(**kw) -- beam_width, depth, segment, action_repeat, gamma, wind ('belief' by
-    default, 'forecast' or 'truth'), leaf_value, action_values: a systematic, deterministic search of a shared-prefix tree of plans.
+    default, 'forecast' or 'truth'), leaf_value, action_values: a systematic, deterministic search of a shared-prefix tree of plans;
+    with wind='scenarios' agents.beam_agent.VecScenarioBeamSearchAgent -- the same tree flown in num_scenarios sampled winds and ordered
+    by risk_tail's score (seed keys the scenario streams; no leaf_value).
     wind='truth' flies the plans in the wind these environments fly, this env's wind noise included (with wind_noise=False the truth
     is the forecast).  actions = agent.act(obs); obs, reward, terminal = env.step(actions): no host synchronisation in either."""
     if search not in ('sample', 'beam'):
@@ -285,7 +295,10 @@ class VecBalloonEnv:
     kw.setdefault('device', self.device)
     if search == 'beam':
       from balloon_learning_environment_amd.agents import beam_agent
-      agent = beam_agent.VecBeamSearchAgent(**kw)
+      if kw.get('wind') == 'scenarios':
+        agent = beam_agent.VecScenarioBeamSearchAgent(**{k: v for k, v in kw.items() if k != 'wind'})
+      else:
+        agent = beam_agent.VecBeamSearchAgent(**kw)
     else:
       from balloon_learning_environment_amd.agents import lookahead_agent
       agent = lookahead_agent.VecLookaheadAgent(**kw)

@@ -39,9 +39,12 @@ WindBelief = collections.namedtuple('WindBelief', ('slab', 'n_obs'))
 WindScenarios = collections.namedtuple('WindScenarios', ('slab', 'n_obs', 'num', 'seed', 'seeds'), defaults=(0, None))
 
 
-class TreeSearch(collections.namedtuple('TreeSearch', ('action', 'best_plan', 'best_return', 'q', 'visits', 'returns', 'steps_flown', 'leaves'))):
+class TreeSearch(collections.namedtuple('TreeSearch', ('action', 'best_plan', 'best_return', 'q', 'visits', 'returns', 'steps_flown', 'leaves', 'score'),
+                                        defaults=(None,))):
   """What tree_search returns: action [n] u8, best_plan [depth * segment, n] u8, best_return [n] f32, q and visits [n, 3] or None, and
   the last level: returns [n, C] f32, steps_flown [n, C] i32 and leaves, its arena (a leaf arena of C leaves per environment).
+  In scenario winds (tree_search(scenarios=)) returns and steps_flown are [n, C, M], leaves holds C M leaves per environment and score
+  [n, C] f32 is the risk score of every group of the last level, the finish's keys; None otherwise.
   buffers, reached by name: the TreeBuffers the search wrote into (choice [depth, n, beam_width], the lists of every selection)."""
 
   def __new__(cls, *fields, buffers=None):
@@ -63,10 +66,19 @@ class TreeBuffers:
   """The device memory of a beam search of one depth and beam width over one simulator (VecSimulator.tree_buffers): two node arenas
   that alternate level by level -- arenas[d & 1] holds level d: a leaf arena of C_d leaves per environment plus, per node, acc and
   disc (float64), flown (int32) and ret (float32); the last level's arena is sized for exactly that level, so it is a leaf arena of
-  the simulator like any other --, parent [n, beam_width] and choice [depth, n, beam_width] (int32), and the results, best_plan [depth * segment, n] among them."""
+  the simulator like any other --, parent [n, beam_width] and choice [depth, n, beam_width] (int32), and the results, best_plan [depth * segment, n] among them.
+  num_scenarios M > 0: every node is a group of M scenario nodes, node (e, c, m) at index (e C_d + c) M + m -- the arenas
+  hold M times the nodes, the last level's is a leaf arena of C M leaves per environment -- and score [n, 3 beam_width] float32 takes
+  every level's risk scores."""
 
-  def __init__(self, sim: 'VecSimulator', depth: int, beam_width: int, segment: int = 4, action_values: bool = False):
+  def __init__(self, sim: 'VecSimulator', depth: int, beam_width: int, segment: int = 4, action_values: bool = False, num_scenarios: int = 0):
     depth, beam, self.segment = int(depth), int(beam_width), int(segment)
+    self.num_scenarios = int(num_scenarios)
+    if not 0 <= self.num_scenarios <= _abi.SCENARIO_MAX:
+      raise ValueError(f'tree_search: 1 <= num_scenarios <= {_abi.SCENARIO_MAX} (0: one wind), not {num_scenarios}')
+    group = max(self.num_scenarios, 1)
+    if 1 <= beam <= _abi.TREE_MAX_BEAM and sim.n * 3 * beam * group >= 2 ** 31:
+      raise ValueError(f'tree_search: n * 3 * beam_width * num_scenarios < 2^31, not {sim.n} x 3 x {beam} x {group}')
     if self.segment < 1 or depth * self.segment > _abi.ROLLOUT_MAX_STEPS:
       raise ValueError(f'tree_search: segment >= 1 and depth * segment <= {_abi.ROLLOUT_MAX_STEPS}, not {depth} x {segment}')
     if depth < 1 or depth > _abi.ROLLOUT_MAX_STEPS or not 1 <= beam <= _abi.TREE_MAX_BEAM or sim.n * 3 * beam >= 2 ** 31:
@@ -80,8 +92,8 @@ class TreeBuffers:
       for level in (depth - 1, depth):           # (children per level never shrink: the last level of each parity is its largest)
         if level < 1:
           continue
-        p, nodes = level & 1, n * sizes[level - 1][1]
-        self.arenas[p] = sim.leaf_arena(sizes[level - 1][1])
+        p, nodes = level & 1, n * sizes[level - 1][1] * group
+        self.arenas[p] = sim.leaf_arena(sizes[level - 1][1] * group)
         self.acc[p] = torch.zeros(nodes, dtype=torch.float64, device=device)
         self.disc[p] = torch.zeros(nodes, dtype=torch.float64, device=device)
         self.flown[p] = torch.zeros(nodes, dtype=torch.int32, device=device)
@@ -95,6 +107,7 @@ class TreeBuffers:
       self.best_return = torch.zeros(n, dtype=torch.float32, device=device)
       self.q = torch.zeros(n, 3, dtype=torch.float32, device=device) if action_values else None
       self.visits = torch.zeros(n, 3, dtype=torch.int32, device=device) if action_values else None
+      self.score = torch.zeros(n, 3 * beam, dtype=torch.float32, device=device) if self.num_scenarios else None
 
   def node_struct(self, level: int) -> _abi.BleTreeArena:
     return self._structs[level & 1]
@@ -887,18 +900,19 @@ class VecSimulator:
     return out
 
   # ------------------------------------------------------------------ plan by beam search
-  def tree_buffers(self, depth: int, beam_width: int, segment: int = 4, action_values: bool = False) -> 'TreeBuffers':
+  def tree_buffers(self, depth: int, beam_width: int, segment: int = 4, action_values: bool = False, num_scenarios: int = 0) -> 'TreeBuffers':
     """Everything a tree_search of this depth, beam width and segment writes, allocated once (TreeBuffers): two node arenas, the parent and
-    choice lists and the results.  A search that is given its buffers allocates nothing, as a graph capture needs."""
+    choice lists and the results.  A search that is given its buffers allocates nothing, as a graph capture needs.  num_scenarios: M of
+    a search in scenario winds (tree_search(scenarios=)): arenas of M nodes per child and score [n, 3 beam_width]; 0: one wind."""
     if self.has_fleet:
       raise ValueError('tree_search: a fleet (set_fleet) has no look-ahead kernel; fly one vehicle per batch (set_vehicle)')
-    return TreeBuffers(self, depth, beam_width, segment, action_values)
+    return TreeBuffers(self, depth, beam_width, segment, action_values, num_scenarios)
 
   @_on_own_device
   def tree_search(self, depth: int, beam_width: int, segment: int = 4, action_repeat: int = 1, gamma: float = 0.993,
                   noise_seed: Optional[int] = None, belief: Optional[WindBelief] = None, substeps: int = SUBSTEPS,
                   action_values: bool = False, leaf_score=None, buffers: Optional['TreeBuffers'] = None,
-                  trace: Optional[list] = None) -> 'TreeSearch':
+                  trace: Optional[list] = None, scenarios: Optional[WindScenarios] = None, risk_tail: Optional[int] = None) -> 'TreeSearch':
     """Plan by beam search: a shared-prefix tree of action plans, `depth` levels of one action flown segment * action_repeat agent
     steps each, the best `beam_width` nodes of every level kept per environment -- depth x (`ble_tree_expand_f32`,
     `ble_tree_select_f32`), then `ble_tree_finish_f32`.  Systematic and deterministic: there is no random stream.  With
@@ -913,6 +927,14 @@ class VecSimulator:
     action_values: also q [n, 3], the best key among the last level's nodes under each first action (-Inf: none finite), and visits
     [n, 3], the number of its non-void nodes.  buffers: tree_buffers(depth, beam_width, segment, action_values) to write into.  trace: a list
     that receives (level, returns [n, C_d] clone, parent [n, beam_width] clone) after every selection (tests; not capturable).
+    scenarios: a WindScenarios (fit_wind_scenarios): every edge is flown in each of its M scenario winds
+    (`ble_tree_expand_scenarios_f32`) -- a child is a GROUP of M scenario nodes --, every level's returns [n, C_d, M] are scored by
+    `ble_plan_risk_f32` (risk_tail: plan_risk's tail; None: the expectation), and select and finish order the groups by that score.  A
+    scenario node that stopped is carried on unchanged under every action; a group whose M nodes all stopped has the carry (a = 0) and two
+    void groups as children.  A node of a non-void group holds bit for bit what rollout_plans(scenarios=) gives its plan in its
+    scenario.  returns and steps_flown are then [n, C, M], leaves has C M leaves per environment, score [n, C] is the last level's,
+    best_return and q are scores, visits counts the groups whose score is not NaN, and trace receives (level, score clone, parent
+    clone, returns clone).  Not together with belief, noise_seed or leaf_score (a leaf value would need C M observations).
     Returns TreeSearch(action [n] u8, best_plan [depth * segment, n] u8, best_return [n] f32, q, visits, returns [n, C] f32,
     steps_flown [n, C] i32, leaves): an environment that is not OK gets all STAY and best_return 0, one without a finite return all
     STAY and -Inf.  The tensors are the buffers' own, overwritten by the next search.
@@ -922,6 +944,18 @@ class VecSimulator:
       raise ValueError('tree_search: a fleet (set_fleet) has no look-ahead kernel; fly one vehicle per batch (set_vehicle)')
     if belief is not None and noise_seed is not None:
       raise ValueError('tree_search: belief and noise_seed are two winds; give one of them')
+    num = 0
+    if scenarios is not None:
+      if belief is not None or noise_seed is not None:
+        raise ValueError('tree_search: scenarios, belief and noise_seed are three winds; give one of them')
+      if leaf_score is not None:
+        raise ValueError('tree_search: leaf_score with scenarios: a group has M end states (C * M observations per environment)')
+      num = int(scenarios.num)
+      tail = num if risk_tail is None else int(risk_tail)
+      if not 1 <= num <= _abi.SCENARIO_MAX or not 1 <= tail <= num:
+        raise ValueError(f'tree_search: 1 <= M <= {_abi.SCENARIO_MAX} and 1 <= risk_tail <= M, not M = {num}, risk_tail = {risk_tail}')
+    elif risk_tail is not None:
+      raise ValueError('tree_search: risk_tail scores scenario winds; give scenarios')
     assert self.grid is not None, 'Must call set_grid (reset) before tree_search.'
     depth, beam, segment, action_repeat = int(depth), int(beam_width), int(segment), int(action_repeat)
     if segment < 1 or action_repeat < 1 or depth < 1 or depth * segment * action_repeat > _abi.ROLLOUT_MAX_STEPS:
@@ -930,17 +964,19 @@ class VecSimulator:
     if not 0.0 <= float(gamma) <= 1.0:
       raise ValueError(f'tree_search: gamma in [0, 1], not {gamma}')
     if buffers is None:
-      buffers = self.tree_buffers(depth, beam, segment, action_values)
+      buffers = self.tree_buffers(depth, beam, segment, action_values, num)
     if (buffers.sim is not self or buffers.depth != depth or buffers.beam != beam or buffers.segment != segment or
-        (action_values and buffers.q is None)):
-      raise ValueError(f'tree_search: buffers of another search (tree_buffers({depth}, {beam}, {segment}, action_values={bool(action_values)}) '
-                       'of this simulator)')
+        (action_values and buffers.q is None) or buffers.num_scenarios != num):
+      raise ValueError(f'tree_search: buffers of another search (tree_buffers({depth}, {beam}, {segment}, action_values={bool(action_values)}, '
+                       f'num_scenarios={num}) of this simulator)')
     bf, n, stream = buffers, self.n, dev.stream_ptr(self.device)
     for arena in bf.arenas:
       if arena is not None:
         self._check_leaf_arena(arena, arena.leaves_per_env)
     gen = None if noise_seed is None else _abi.BleNoiseGen(int(noise_seed) & (2 ** 64 - 1), self.episode.data_ptr(), None, self.env_offset)
     b = None if belief is None else self._belief_struct(belief)
+    if scenarios is not None:
+      return self._tree_search_scenarios(bf, scenarios, tail, action_repeat, float(gamma), int(substeps), action_values, trace)
     parents, children = 1, 0                       # P_{d-1}, C_{d-1}
     for level in range(1, depth + 1):
       dst, src = bf.node_struct(level), bf.node_struct(level - 1) if level > 1 else _abi.BleTreeArena()
@@ -967,6 +1003,38 @@ class VecSimulator:
     _lib.check(self.lib.ble_tree_finish_f32(ctypes.byref(fin), stream), 'ble_tree_finish_f32')
     return TreeSearch(bf.action, bf.best_plan, bf.best_return, bf.q if action_values else None, bf.visits if action_values else None, returns,
                       flown, leaves, buffers=bf)
+
+  def _tree_search_scenarios(self, bf: 'TreeBuffers', scenarios: WindScenarios, tail: int, action_repeat: int, gamma: float, substeps: int,
+                             action_values: bool, trace: Optional[list]) -> 'TreeSearch':
+    """tree_search in scenario winds, its arguments checked: depth x (expand, risk, select), then the finish on the last level's scores."""
+    n, num, depth, beam, stream = self.n, bf.num_scenarios, bf.depth, bf.beam, dev.stream_ptr(self.device)
+    scn, sgen = self._scenario_structs(scenarios)
+    parents, children = 1, 0                       # P_{d-1}, C_{d-1}
+    for level in range(1, depth + 1):
+      dst, src = bf.node_struct(level), bf.node_struct(level - 1) if level > 1 else _abi.BleTreeArena()
+      ex = _abi.BleTreeExpand(n, beam, depth, parents, children, bf.segment, action_repeat, substeps, 0, gamma, self.grid.data_ptr(),
+                              self.grid_env_stride, bf.parent.data_ptr(), src, dst)
+      _lib.check(self.lib.ble_tree_expand_scenarios_f32(ctypes.byref(self._struct), ctypes.byref(ex), ctypes.byref(scn), ctypes.byref(sgen),
+                                                        self.rollout_flags.data_ptr(), stream), 'ble_tree_expand_scenarios_f32')
+      children = 3 * parents
+      ret = bf.ret[level & 1]
+      risk = _abi.BlePlanRisk(n, children, num, tail, 0, ret.data_ptr(), bf.score.data_ptr())          # ret [n][C][M] -> score [n][C]
+      _lib.check(self.lib.ble_plan_risk_f32(ctypes.byref(risk), stream), 'ble_plan_risk_f32')
+      sel = _abi.BleTreeSelect(n, children, beam, bf.score.data_ptr(), bf.parent.data_ptr(), bf.choice[level - 1].data_ptr())
+      _lib.check(self.lib.ble_tree_select_f32(ctypes.byref(sel), stream), 'ble_tree_select_f32')
+      if trace is not None:
+        trace.append((level, bf.score.view(-1)[:n * children].view(n, children).clone(), bf.parent.clone(),
+                      ret[:n * children * num].view(n, children, num).clone()))
+      parents = min(children, beam)
+    last = depth & 1
+    score = bf.score.view(-1)[:n * children].view(n, children)
+    # the finish on the scores alone: a group is void to it where its score is NaN
+    fin = _abi.BleTreeFinish(n, children, beam, depth, bf.segment, score.data_ptr(), None, self.state['status'].data_ptr(),
+                             bf.choice.data_ptr(), bf.best_plan.data_ptr(), bf.action.data_ptr(), bf.best_return.data_ptr(),
+                             dev.ptr(bf.q) if action_values else None, dev.ptr(bf.visits) if action_values else None)
+    _lib.check(self.lib.ble_tree_finish_f32(ctypes.byref(fin), stream), 'ble_tree_finish_f32')
+    return TreeSearch(bf.action, bf.best_plan, bf.best_return, bf.q if action_values else None, bf.visits if action_values else None,
+                      bf.ret[last].view(n, children, num), bf.flown[last].view(n, children, num), bf.arenas[last], score, buffers=bf)
 
   @property
   def active_count(self) -> torch.Tensor:

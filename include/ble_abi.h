@@ -1739,6 +1739,30 @@ struct ble_tree_finish {
 };
 int ble_tree_finish_f32(const struct ble_tree_finish* fin, void* stream);
 
+/* ------------------------------------------------------------------------------ beam search in scenario winds
+ * The tree above flown in the M = scn->num scenario winds of ble_gp_fit_scenarios_f32.  A GROUP (e, c) is M scenario nodes, node
+ * (e, c, m) at index (e * C_d + c) * M + m of the level's arena; the arenas of `ex` hold n * 3 * beam * M nodes, and the last level's
+ * is a leaf arena of C_D * M leaves per environment.  Added without a new ABI version.
+ *
+ * ble_tree_expand_scenarios_f32: one lane per (e, r, a, m), lane index = destination node index.  The lane loads node
+ * (e * C_{d-1} + parent[e][r]) * M + m of `src` -- at level 1 environment e of `st`, with acc 0, disc 1, flown 0 --, flies the edge with
+ * ble_rollout_scenarios_f32's loop body in scenario m of environment e and stores the child as ble_tree_expand_f32 does.  A scenario
+ * node is STOPPED when its status is not OK or its acc is NaN: it flies nothing and is carried on unchanged (state, acc, disc, flown)
+ * under EVERY action, as a frozen lane of ble_rollout_scenarios_f32 is.  A group whose M nodes are all stopped is SPENT: its a = 0 child
+ * group is the carry, its a = 1 and a = 2 child groups are VOID -- the same copies with acc = NaN in all M nodes.  A void group is spent,
+ * so all its descendants are void.  At level 1 the group is spent exactly when st->status[e] is not OK.  A node of a non-void group
+ * reached by (a_1 .. a_d) holds, bit for bit, the ret, steps_flown and final_state words ble_rollout_scenarios_f32 gives the plan
+ * a_1 x segment, .., a_d x segment in scenario m from environment e, and as its state what ble_gp_scenario_wind_f32 followed by
+ * ble_step_f32 leave on a copy.  A level's ret is [n][C_d][M]: ble_plan_risk_f32 (n_plans = C_d) maps it to the [n][C_d] that
+ * ble_tree_select_f32 and ble_tree_finish_f32 take.  st, the history, the slab and every cache are never written; flags go to err_flags
+ * -- give it a word of its own.
+ * BLE_E_INVALID_ARG before any HIP call: everything ble_tree_expand_f32 refuses of st and ex, with the bound n * 3 * beam * num >= 2^31;
+ * what ble_gp_fit_scenarios_f32 refuses of scn and gen; scn->n other than ex->n.  n == 0: BLE_OK without a launch.  A fleet has no form
+ * of this call.
+ */
+int ble_tree_expand_scenarios_f32(const ble_state_f32* st, const struct ble_tree_expand* ex, const ble_gp_scenarios* scn,
+                                  const ble_scenario_gen* gen, uint32_t* err_flags, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
