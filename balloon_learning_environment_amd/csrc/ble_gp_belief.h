@@ -11,8 +11,8 @@
 //                               alpha^m; gp_belief_mean calls it with the alpha of its slab.
 //   ble_gp_belief_wind_kernel   one lane per environment at caller-chosen points (the shape of ble_wind_noise_kernel): what ble_step_f32
 //                               takes as noise_uv.
-//   ble_rollout_belief_kernel   ble_rollout_kernel's body (a fourth copy of the step kernel's, for the reason given there) with
-//                               gp_belief_mean in the slot of the noise term.
+//   WindBelief                  the look-ahead's wind policy (ble_lookahead.h): gp_belief_mean in the slot of the noise term.
+//   ble_rollout_belief_kernel   ble_rollout_kernel's lanes (rollout_lane) in that wind: the lane map and nothing else.
 //
 // The slab of an environment (kBeliefDoubles = BLE_GP_BELIEF_DOUBLES doubles, 16-byte aligned):
 //   [0, 480)     loc[120][4]: x, y, p, t of the window's observations, chronological, in units of ln2 / 32 length scales
@@ -105,8 +105,8 @@ BLE_FN int gp_belief_trip(int n_obs) {
 
 #if defined(__HIPCC__)
 // ---------------------------------------------------------------------------------------------------------------- the kernels
-// Included by ble_kernels.hip after ble_rollout.h: ble_observe.h, ble_gp_query.h (GpQueryShared, ble_gp_factor.h), kStepBlock and report_flags
-// are there.
+// Included by ble_kernels.hip after ble_rollout.h (RolloutArgs, rollout_lane): ble_observe.h, ble_gp_query.h (GpQueryShared,
+// ble_gp_factor.h), kStepBlock and report_flags are there.
 namespace ble {
 
 // struct ble_gp_belief (include/ble_abi.h) as the kernels take it
@@ -197,100 +197,44 @@ __global__ __launch_bounds__(kBeliefWindBlock) void ble_gp_belief_wind_kernel(Be
   }
 }
 
-// ble_rollout_kernel's body (ble_rollout.h) in forecast + the belief's mean: every lane of environment e evaluates gp_belief_mean on
-// e's slab at its own pre-step position and time.  Reads the belief, writes what ble_rollout_kernel writes.
+// The look-ahead's wind (ble_lookahead.h) in forecast + the belief's mean: every lane of environment e evaluates gp_belief_mean on e's
+// slab at its own pre-step position and time.
+struct WindBelief {
+  struct Shared {
+    __attribute__((aligned(16))) double acs_poly[kAcsPolyDoubles];      // (WindForecast's, and the table)
+    float term_save[kTermSaveRows * kStepBlock];
+    double tab[64];
+  };
+  BeliefDev b;
+  int n_obs = 0, n_trip = 0;
+  const double* slab = nullptr;
+  __device__ __forceinline__ void load(int64_t e) { n_obs = b.n_obs[e]; }
+  static __device__ __forceinline__ void fill(Shared& shm) {
+    if (threadIdx.x < 64) shm.tab[threadIdx.x] = gp_belief_table_entry((int)threadIdx.x);
+  }
+  __device__ __forceinline__ void fetch(Shared&, int64_t e, bool, int64_t) {
+    n_trip = belief_wave_trip(n_obs);          // one loop for the wave, whatever environments its lanes belong to
+    slab = b.slab + e * b.stride;
+  }
+  __device__ __forceinline__ void uv(const Shared& shm, const EnvRegs& s, float& nu, float& nv) const {
+    gp_belief_mean(slab, n_obs, n_trip, s.x, s.y, s.p, s.t_elapsed, shm.tab, &nu, &nv);
+    // the belief's wind is a VALUE, as the noise is in ble_step_kernel: ble_gp_belief_wind_f32 + ble_step_f32 give the same bits
+    asm volatile("" : "+v"(nu), "+v"(nv));
+  }
+};
+
+// ble_rollout_kernel's lanes (ble_rollout.h: rollout_lane) in that wind.  Reads the belief, writes what ble_rollout_kernel writes.
 // kLeaves: the lane's whole end state goes to the leaf arena as well (ble_rollout.h: leaf_store and the trailing pack).
 template <class V = VehicleDefault, bool kLeaves = false, class... Leaf>
 __global__ __launch_bounds__(kStepBlock) void ble_rollout_belief_kernel(StateDev st, RolloutArgs a, BeliefDev b, uint32_t* err_flags, V veh,
                                                                         Leaf... leaves) {
   static_assert(sizeof...(Leaf) == (kLeaves ? 1 : 0), "with leaves: the leaf arena's StateDev; without: nothing");
-  __shared__ double acs_poly[kAcsPolyDoubles];
-  __shared__ float term_save[kTermSaveRows * kStepBlock];
-  __shared__ double tab[64];
-  const int wave = (int)threadIdx.x >> 6, lane = (int)threadIdx.x & 63;
+  __shared__ WindBelief::Shared shm;
   const int64_t lanes_total = a.n * (int64_t)a.n_plans;          // < 2^31 (the entry point checks)
   const int64_t j = (int64_t)blockIdx.x * kStepBlock + threadIdx.x;
-  const bool in_range = j < lanes_total;
-  const int64_t e = in_range ? (int64_t)((uint32_t)j / (uint32_t)a.n_plans) : 0;
-  uint32_t flags = 0;
-  EnvRegs s;
-  EnvConst c;
-  EpisodeCacheRow cached = {};
-  bool live = false;
-  int n_obs = 0;
-  if (in_range) {
-    // environment e's state, every load issued up front (ble_step_kernel's loads at index e)
-    s.status = st.status[e];
-    s.x = st.x[e]; s.y = st.y[e]; s.p = st.pressure[e]; s.t_amb = st.ambient_temperature[e];
-    s.t_int = st.internal_temperature[e]; s.vol = st.envelope_volume[e]; s.sp = st.superpressure[e];
-    s.n_air = st.mols_air[e]; s.batt = st.battery_charge[e];
-    s.acs_power = 0.0f; s.mdot = 0.0f; s.charge = 0.0f; s.load = 0.0f;
-    s.t_elapsed = st.time_elapsed_s[e]; s.sunrise_h = st.sunrise_h_rel[e]; s.sunset = st.sunset_rel[e];
-    s.alt_fsm = st.alt_fsm[e]; s.env_fsm = st.env_fsm[e]; s.paused = st.power_paused[e];
-    c.lat0_deg = st.center_lat_deg[e]; c.lng0_deg = st.center_lng_deg[e];
-    c.ir = st.upwelling_infrared[e]; c.alpha = st.alpha[e]; c.start_unix = st.start_unix[e];
-    if (st.episode_cache != nullptr) cached = episode_cache_load(st.episode_cache, a.n, e);
-    n_obs = b.n_obs[e];
-    live = s.status == kOk;
-  }
-  for (int q = (int)threadIdx.x; q < kAcsPolyDoubles; q += kStepBlock) acs_poly[q] = kAcsPoly.c[q];
-  if (threadIdx.x < 64) tab[threadIdx.x] = gp_belief_table_entry((int)threadIdx.x);
-  __syncthreads();
-  EnvHoisted hc;
-  if (live) {
-    // per-episode constants: from the cache where its entry belongs to these constants; a miss recomputes and does NOT store
-    if (st.episode_cache != nullptr && episode_cache_hit(cached, c)) hc = hoisted_from_cache(cached, c);
-    else hc = hoist_constants(c);
-  }
-  const int n_trip = belief_wave_trip(n_obs);          // one loop for the wave, whatever environments its lanes belong to
-  const double* const slab = b.slab + e * b.stride;
-  const StrideK K = stride_k_vreg(veh.dry_mass, veh.lift, veh.v0);
-  const float* const grid = a.wind_grid + e * a.grid_env_stride;
-  float* const park = term_save + wave * (kTermSaveRows * kTermSaveStride) + lane;
-  // the discounted return: fp64, the product and the sum as two statements (two roundings under -ffp-contract=on), rounded to fp32 once
-  double acc = 0.0, disc = 1.0;
-  int flown = 0;
-  LeafLast<kLeaves> last;                       // (with leaves: the raw action of the last step flown)
-  int64_t o = j;                                // (agent step t) * n K + j
-#pragma unroll 1
-  for (int h = 0; h < a.n_plan_steps; ++h) {
-    const int act = in_range ? (int)a.plans[(int64_t)h * lanes_total + j] : 0;
-#pragma unroll 1
-    for (int rep = 0; rep < a.action_repeat; ++rep, o += lanes_total) {
-      if (live) {
-        ++flown;
-        if constexpr (kLeaves) last.act = act;
-        const WindQuery wq = wind_query(s.x, s.y, s.p, s.t_elapsed);
-        WindCorners corners;
-        wind_gather(grid, wq, &corners);
-        float nu, nv;
-        gp_belief_mean(slab, n_obs, n_trip, s.x, s.y, s.p, s.t_elapsed, tab, &nu, &nv);
-        // the belief's wind is a VALUE, as the noise is in ble_step_kernel: ble_gp_belief_wind_f32 + ble_step_f32 give the same bits
-        asm volatile("" : "+v"(nu), "+v"(nv));
-        float r;
-        agent_step(s, c, hc, act, corners, wq, nu, nv, a.substeps, acs_poly, K, park, &r, &flags, veh);
-        if (!(isfinite(s.p) && isfinite(s.t_int) && isfinite(s.x) && isfinite(s.y) && isfinite(s.batt)))
-          flags |= kFlagNonFinite;
-        if (a.reward) a.reward[o] = r;
-        const double term = disc * (double)r;
-        acc += term;
-        disc *= a.gamma;
-      } else if (in_range) {                    // a non-OK source, or a plan that went terminal: frozen, reward 0
-        if (a.reward) a.reward[o] = 0.0f;
-      }
-      live = live && s.status == kOk;
-    }
-  }
-  if (in_range) {
-    a.ret[j] = (float)acc;
-    a.steps_flown[j] = flown;
-    if (a.final_state) {
-      a.final_state[j] = s.x; a.final_state[lanes_total + j] = s.y; a.final_state[2 * lanes_total + j] = s.p;
-      a.final_state[3 * lanes_total + j] = s.batt;
-    }
-    if constexpr (kLeaves) leaf_store(st, leaf_arena(leaves...), e, j, flown > 0, s, c, last.act);      // (flown > 0: the source was OK)
-  }
-  report_flags(flags, err_flags);
+  const int64_t e = j < lanes_total ? (int64_t)((uint32_t)j / (uint32_t)a.n_plans) : 0;
+  WindBelief wind{b};
+  rollout_lane<kLeaves>(st, a, wind, shm, j, lanes_total, e, j, lanes_total, err_flags, veh, leaves...);
 }
 
 }  // namespace ble

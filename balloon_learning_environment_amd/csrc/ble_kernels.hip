@@ -818,7 +818,8 @@ __global__ __launch_bounds__(256) void ble_eval_accumulate_kernel(StateDev st, c
 }
 
 }  // namespace
-// ble_rollout_kernel (K action plans per environment, read-only on the state): here, after kStepBlock, StepNoiseShared and report_flags
+// the look-ahead kernels' one lane body (ble_lookahead.h, through ble_rollout.h) and ble_rollout_kernel (K action plans per environment,
+// read-only on the state): here, after kStepBlock, StepNoiseShared and report_flags
 #include "ble_rollout.h"
 // the fitted WindGP kept on the device, its mean as a lane function, and the look-ahead flown in it: after ble_rollout.h (RolloutArgs)
 #include "ble_gp_belief.h"
@@ -1126,22 +1127,31 @@ int with_scenario_seed(const ble_scenario_gen* gen, F&& f) {
 static_assert(kScenarioMax == BLE_SCENARIO_MAX && BLE_GP_SCENARIO_DOUBLES(3) == kBeliefAlphaAt + 3 * kScenarioAlphaDoubles,
               "ble_scenarios.h and ble_abi.h disagree on the slab");
 
+// what the three rollout calls refuse of st and ro; lanes_per_plan: 1, or the scenarios of a plan
+inline bool rollout_ok(const ble_state_f32* st, const struct ble_rollout_f32* ro, int lanes_per_plan) {
+  if (!state_ok(st) || !ro || !ro->plans || !ro->wind_grid || !ro->ret || !ro->steps_flown) return false;
+  if (ro->n < 0 || ro->n >= 2147483648LL || ro->n_plans < 1 || ro->n * (int64_t)ro->n_plans >= 2147483648LL ||
+      ro->n * (int64_t)ro->n_plans * lanes_per_plan >= 2147483648LL || ro->n_plan_steps < 1 || ro->action_repeat < 1 ||
+      (int64_t)ro->n_plan_steps * ro->action_repeat > BLE_ROLLOUT_MAX_STEPS)
+    return false;
+  return ro->substeps >= 1 && ro->substeps <= BLE_MAX_SUBSTEPS && ro->grid_env_stride >= 0 &&
+         ro->gamma >= 0.0 && ro->gamma <= 1.0;                        // (a NaN gamma fails both comparisons)
+}
+// struct ble_rollout_f32 as the rollout kernels take it
+inline RolloutArgs rollout_args(const struct ble_rollout_f32* ro) {
+  return RolloutArgs{ro->n, ro->n_plans, ro->n_plan_steps, ro->action_repeat, ro->substeps, ro->gamma, ro->plans, ro->wind_grid,
+                     ro->grid_env_stride, ro->ret, ro->steps_flown, ro->reward, ro->final_state};
+}
+
 // ble_rollout_f32 and, with leaves (the leaf arena's StateDev as the one trailing argument), ble_rollout_leaves_f32 in the forecast or a
 // noise generator's wind
 template <class... Leaf>
 int launch_rollout(const ble_state_f32* st, const struct ble_rollout_f32* ro, const ble_noise_gen* noise, uint32_t* err_flags, void* stream,
                    const Leaf&... leaves) {
-  if (!state_ok(st) || !ro || !ro->plans || !ro->wind_grid || !ro->ret || !ro->steps_flown) return BLE_E_INVALID_ARG;
-  if (ro->n < 0 || ro->n >= 2147483648LL || ro->n_plans < 1 || ro->n * (int64_t)ro->n_plans >= 2147483648LL || ro->n_plan_steps < 1 ||
-      ro->action_repeat < 1 || (int64_t)ro->n_plan_steps * ro->action_repeat > BLE_ROLLOUT_MAX_STEPS)
-    return BLE_E_INVALID_ARG;
-  if (ro->substeps < 1 || ro->substeps > BLE_MAX_SUBSTEPS || ro->grid_env_stride < 0 || (noise != nullptr && noise->env_offset < 0) ||
-      !(ro->gamma >= 0.0 && ro->gamma <= 1.0))                      // (a NaN gamma fails both comparisons)
-    return BLE_E_INVALID_ARG;
+  if (!rollout_ok(st, ro, 1) || (noise != nullptr && noise->env_offset < 0)) return BLE_E_INVALID_ARG;
   return with_vehicle<false>(st, nullptr, [&](auto veh) {
     if (ro->n == 0) return BLE_OK;
-    const RolloutArgs a{ro->n, ro->n_plans, ro->n_plan_steps, ro->action_repeat, ro->substeps, ro->gamma, ro->plans, ro->wind_grid,
-                        ro->grid_env_stride, ro->ret, ro->steps_flown, ro->reward, ro->final_state};
+    const RolloutArgs a = rollout_args(ro);
     // (the harmonic cache of `noise` is not handed on for writing: ble_rollout_kernel draws into LDS and fills no cache)
     return with_noise(noise, [&](auto noise_on, StepNoise gen) {
       return launch(ble_rollout_kernel<decltype(noise_on)::value, decltype(veh), (sizeof...(Leaf) > 0), Leaf...>, ro->n * (int64_t)ro->n_plans,
@@ -1154,19 +1164,12 @@ template <class... Leaf>
 int launch_rollout_belief(const ble_state_f32* st, const struct ble_rollout_f32* ro, const ble_gp_belief* belief, uint32_t* err_flags,
                           void* stream, const Leaf&... leaves) {
   BeliefDev b;
-  if (!state_ok(st) || !ro || !ro->plans || !ro->wind_grid || !ro->ret || !ro->steps_flown || !gp_belief(belief, &b)) return BLE_E_INVALID_ARG;
-  if (ro->n < 0 || ro->n >= 2147483648LL || ro->n_plans < 1 || ro->n * (int64_t)ro->n_plans >= 2147483648LL || ro->n_plan_steps < 1 ||
-      ro->action_repeat < 1 || (int64_t)ro->n_plan_steps * ro->action_repeat > BLE_ROLLOUT_MAX_STEPS)
-    return BLE_E_INVALID_ARG;
-  if (ro->substeps < 1 || ro->substeps > BLE_MAX_SUBSTEPS || ro->grid_env_stride < 0 || !(ro->gamma >= 0.0 && ro->gamma <= 1.0) ||
-      belief->n != ro->n)                                             // (a belief of another batch would be read out of bounds)
+  if (!rollout_ok(st, ro, 1) || !gp_belief(belief, &b) || belief->n != ro->n)      // (a belief of another batch would be read out of bounds)
     return BLE_E_INVALID_ARG;
   return with_vehicle<false>(st, nullptr, [&](auto veh) {
     if (ro->n == 0) return BLE_OK;
-    const RolloutArgs a{ro->n, ro->n_plans, ro->n_plan_steps, ro->action_repeat, ro->substeps, ro->gamma, ro->plans, ro->wind_grid,
-                        ro->grid_env_stride, ro->ret, ro->steps_flown, ro->reward, ro->final_state};
     return launch(ble_rollout_belief_kernel<decltype(veh), (sizeof...(Leaf) > 0), Leaf...>, ro->n * (int64_t)ro->n_plans, kStepBlock, kStepBlock,
-                  stream, state_dev(st), a, b, err_flags, veh, leaves...);
+                  stream, state_dev(st), rollout_args(ro), b, err_flags, veh, leaves...);
   });
 }
 
@@ -2522,22 +2525,13 @@ int ble_gp_scenario_wind_f32(const ble_gp_scenarios* scn, const ble_scenario_gen
 int ble_rollout_scenarios_f32(const ble_state_f32* st, const struct ble_rollout_f32* ro, const ble_gp_scenarios* scn,
                               const ble_scenario_gen* gen, uint32_t* err_flags, void* stream) {
   ScenariosDev b;
-  if (!state_ok(st) || !ro || !ro->plans || !ro->wind_grid || !ro->ret || !ro->steps_flown || !gp_scenarios(scn, &b) || !scenario_gen_ok(gen))
-    return BLE_E_INVALID_ARG;
-  if (ro->n < 0 || ro->n >= 2147483648LL || ro->n_plans < 1 || ro->n * (int64_t)ro->n_plans >= 2147483648LL ||
-      ro->n * (int64_t)ro->n_plans * scn->num >= 2147483648LL || ro->n_plan_steps < 1 || ro->action_repeat < 1 ||
-      (int64_t)ro->n_plan_steps * ro->action_repeat > BLE_ROLLOUT_MAX_STEPS)
-    return BLE_E_INVALID_ARG;
-  if (ro->substeps < 1 || ro->substeps > BLE_MAX_SUBSTEPS || ro->grid_env_stride < 0 || !(ro->gamma >= 0.0 && ro->gamma <= 1.0) ||
-      scn->n != ro->n)                                                // (scenarios of another batch would be read out of bounds)
-    return BLE_E_INVALID_ARG;
+  if (!gp_scenarios(scn, &b) || !scenario_gen_ok(gen) || !rollout_ok(st, ro, scn->num) || scn->n != ro->n)
+    return BLE_E_INVALID_ARG;                                         // (scenarios of another batch would be read out of bounds)
   return with_vehicle<false>(st, nullptr, [&](auto veh) {
     if (ro->n == 0) return BLE_OK;
-    const RolloutArgs a{ro->n, ro->n_plans, ro->n_plan_steps, ro->action_repeat, ro->substeps, ro->gamma, ro->plans, ro->wind_grid,
-                        ro->grid_env_stride, ro->ret, ro->steps_flown, ro->reward, ro->final_state};
     return with_scenario_seed(gen, [&](auto seed, ScenarioGen g) {
       return launch(ble_rollout_scenarios_kernel<decltype(veh), decltype(seed)>, ro->n * (int64_t)ro->n_plans * scn->num, kStepBlock, kStepBlock,
-                    stream, state_dev(st), a, b, seed, g, err_flags, veh);
+                    stream, state_dev(st), rollout_args(ro), b, seed, g, err_flags, veh);
     });
   });
 }

@@ -13,7 +13,8 @@
 //   gp_scenario_correction        (ble_gp_belief.h) gp_belief_mean's body with the slab's window and alpha^m as its two pointers.
 //   ble_gp_scenario_wind_kernel   one lane per environment at caller-chosen points and a scenario index per environment: what
 //                                 ble_step_f32 takes as noise_uv.  prior_only: f_m alone.
-//   ble_rollout_scenarios_kernel  ble_rollout_belief_kernel's body, one lane per (e, k, m), j = (e K + k) M + m.
+//   WindScenario                  the look-ahead's wind policy (ble_lookahead.h): f_m + the correction in the slot of the noise term.
+//   ble_rollout_scenarios_kernel  ble_rollout_kernel's lanes (rollout_lane) in that wind, one lane per (e, k, m), j = (e K + k) M + m.
 //   ble_plan_risk_kernel          one lane per (e, k): ret [n][K][M] -> score [n][K], the mean of the `tail` smallest scenario returns.
 //
 // The slab of an environment (stride doubles, 16-byte aligned, stride >= 480 + 240 M and even):
@@ -123,8 +124,8 @@ BLE_FN float plan_risk_score(const float* ret, int64_t stride, int num, int tail
 
 #if defined(__HIPCC__)
 // ---------------------------------------------------------------------------------------------------------------- the kernels
-// Included by ble_kernels.hip after ble_plan.h: ScalarSeed / EnvSeed, GpQueryShared, RolloutArgs, belief_wave_trip, kStepBlock and
-// report_flags are there.
+// Included by ble_kernels.hip after ble_plan.h: ScalarSeed / EnvSeed, GpQueryShared, RolloutArgs and rollout_lane, belief_wave_trip,
+// kStepBlock and report_flags are there.
 namespace ble {
 
 // struct ble_gp_scenarios (include/ble_abi.h) as the kernels take it
@@ -275,7 +276,7 @@ __global__ __launch_bounds__(kScenarioWindBlock) void ble_gp_scenario_wind_kerne
   }
 }
 
-// ble_rollout_kernel<noise>'s LDS (StepNoiseShared) and the belief's table
+// WindScenario's LDS: WindNoise's (StepNoiseShared, in its order) and the belief's table
 struct ScenarioRolloutShared {
   __attribute__((aligned(16))) float grad_lut[kGradLutFloats];
   double acs_poly[kAcsPolyDoubles];
@@ -284,106 +285,58 @@ struct ScenarioRolloutShared {
   uint32_t draws[50 * kStepBlock];
 };
 
-// ble_rollout_belief_kernel's body in the scenario winds: one lane per (environment e, plan k, scenario m), j = (e K + k) M + m.  Plans are
-// read at [h][e K + k]; ret, steps_flown, reward and final_state are indexed by j (a.n_plans is K; lanes_total = n K M).  Per agent step
-// the lane evaluates f_m and the correction at its pre-step state behind the same value barrier: the bits of
-// ble_gp_scenario_wind_kernel followed by ble_step_f32.  Reads the state, the caches and the slab; writes none of them.
+// The look-ahead's wind (ble_lookahead.h) in scenario sm of the lane's environment: per agent step f_m and the correction at the
+// pre-step state, each a VALUE, their ONE fp32 addition a value again: the bits of ble_gp_scenario_wind_kernel followed by
+// ble_step_f32.  Reads the slab; writes nothing but its LDS rows.
+template <class S>
+struct WindScenario {
+  using Shared = ScenarioRolloutShared;
+  ScenariosDev b;
+  S seed;
+  ScenarioGen gen;
+  int sm;
+  int n_obs = 0, n_trip = 0;
+  const double* loc = nullptr;
+  const double* alpha = nullptr;
+  __device__ __forceinline__ void load(int64_t e) { n_obs = b.n_obs[e]; }
+  static __device__ __forceinline__ void fill(Shared& shm) {
+    grad_lut_fill(shm.grad_lut, (int)threadIdx.x, kStepBlock);
+    if (threadIdx.x < 64) shm.tab[threadIdx.x] = gp_belief_table_entry((int)threadIdx.x);
+  }
+  __device__ __forceinline__ void fetch(Shared& shm, int64_t e, bool in_range, int64_t) {
+    if (in_range)
+      scenario_draws_fetch(seed.of(e), seed.key(e, gen.env_offset), gen.episode ? gen.episode[e] : 0u, sm, shm.draws + threadIdx.x, kStepBlock);
+    n_trip = belief_wave_trip(n_obs);          // one loop for the wave, whatever environments its lanes belong to
+    loc = b.slab + e * b.stride;
+    alpha = loc + kBeliefAlphaAt + kScenarioAlphaDoubles * sm;
+  }
+  __device__ __forceinline__ void uv(const Shared& shm, const EnvRegs& s, float& nu, float& nv) const {
+    float fu, fv, cu, cv;
+    wind_noise_from_rows(s.x, s.y, s.p, s.t_elapsed, shm.draws + threadIdx.x, kStepBlock, shm.grad_lut, &fu, &fv);
+    asm volatile("" : "+v"(fu), "+v"(fv));
+    gp_scenario_correction(loc, alpha, n_obs, n_trip, s.x, s.y, s.p, s.t_elapsed, shm.tab, &cu, &cv);
+    asm volatile("" : "+v"(cu), "+v"(cv));
+    nu = fu + cu; nv = fv + cv;
+    // the scenario's wind is a VALUE, as the noise is in ble_step_kernel: ble_gp_scenario_wind_f32 + ble_step_f32 give the same bits
+    asm volatile("" : "+v"(nu), "+v"(nv));
+  }
+};
+
+// ble_rollout_kernel's lanes (ble_rollout.h: rollout_lane) in the scenario winds: one lane per (environment e, plan k, scenario m),
+// j = (e K + k) M + m.  Plans are read at [h][e K + k]; ret, steps_flown, reward and final_state are indexed by j (a.n_plans is K;
+// lanes_total = n K M).  Reads the state, the caches and the slab; writes none of them.
 template <class V, class S>
 __global__ __launch_bounds__(kStepBlock) void ble_rollout_scenarios_kernel(StateDev st, RolloutArgs a, ScenariosDev b, S seed, ScenarioGen gen,
                                                                           uint32_t* err_flags, V veh) {
   __shared__ ScenarioRolloutShared shm;
-  const int wave = (int)threadIdx.x >> 6, lane = (int)threadIdx.x & 63;
   const int64_t plans_total = a.n * (int64_t)a.n_plans;
   const int64_t lanes_total = plans_total * b.num;               // < 2^31 (the entry point checks)
   const int64_t j = (int64_t)blockIdx.x * kStepBlock + threadIdx.x;
-  const bool in_range = j < lanes_total;
-  const int64_t ek = in_range ? (int64_t)((uint32_t)j / (uint32_t)b.num) : 0;
-  const int sm = in_range ? (int)(j - ek * b.num) : 0;
+  const int64_t ek = j < lanes_total ? (int64_t)((uint32_t)j / (uint32_t)b.num) : 0;
+  const int sm = j < lanes_total ? (int)(j - ek * b.num) : 0;
   const int64_t e = (int64_t)((uint32_t)ek / (uint32_t)a.n_plans);
-  uint32_t flags = 0;
-  EnvRegs s;
-  EnvConst c;
-  EpisodeCacheRow cached = {};
-  bool live = false;
-  int n_obs = 0;
-  if (in_range) {
-    // environment e's state, every load issued up front (ble_step_kernel's loads at index e)
-    s.status = st.status[e];
-    s.x = st.x[e]; s.y = st.y[e]; s.p = st.pressure[e]; s.t_amb = st.ambient_temperature[e];
-    s.t_int = st.internal_temperature[e]; s.vol = st.envelope_volume[e]; s.sp = st.superpressure[e];
-    s.n_air = st.mols_air[e]; s.batt = st.battery_charge[e];
-    s.acs_power = 0.0f; s.mdot = 0.0f; s.charge = 0.0f; s.load = 0.0f;
-    s.t_elapsed = st.time_elapsed_s[e]; s.sunrise_h = st.sunrise_h_rel[e]; s.sunset = st.sunset_rel[e];
-    s.alt_fsm = st.alt_fsm[e]; s.env_fsm = st.env_fsm[e]; s.paused = st.power_paused[e];
-    c.lat0_deg = st.center_lat_deg[e]; c.lng0_deg = st.center_lng_deg[e];
-    c.ir = st.upwelling_infrared[e]; c.alpha = st.alpha[e]; c.start_unix = st.start_unix[e];
-    if (st.episode_cache != nullptr) cached = episode_cache_load(st.episode_cache, a.n, e);
-    n_obs = b.n_obs[e];
-    live = s.status == kOk;
-  }
-  for (int q = (int)threadIdx.x; q < kAcsPolyDoubles; q += kStepBlock) shm.acs_poly[q] = kAcsPoly.c[q];
-  grad_lut_fill(shm.grad_lut, (int)threadIdx.x, kStepBlock);
-  if (threadIdx.x < 64) shm.tab[threadIdx.x] = gp_belief_table_entry((int)threadIdx.x);
-  __syncthreads();
-  EnvHoisted hc;
-  if (live) {
-    // per-episode constants: from the cache where its entry belongs to these constants; a miss recomputes and does NOT store
-    if (st.episode_cache != nullptr && episode_cache_hit(cached, c)) hc = hoisted_from_cache(cached, c);
-    else hc = hoist_constants(c);
-  }
-  uint32_t* const rows = shm.draws + threadIdx.x;
-  if (in_range) scenario_draws_fetch(seed.of(e), seed.key(e, gen.env_offset), gen.episode ? gen.episode[e] : 0u, sm, rows, kStepBlock);
-  const int n_trip = belief_wave_trip(n_obs);          // one loop for the wave, whatever environments its lanes belong to
-  const double* const loc = b.slab + e * b.stride;
-  const double* const alpha = loc + kBeliefAlphaAt + kScenarioAlphaDoubles * sm;
-  const StrideK K = stride_k_vreg(veh.dry_mass, veh.lift, veh.v0);
-  const float* const grid = a.wind_grid + e * a.grid_env_stride;
-  float* const park = shm.term_save + wave * (kTermSaveRows * kTermSaveStride) + lane;
-  // the discounted return: fp64, the product and the sum as two statements (two roundings under -ffp-contract=on), rounded to fp32 once
-  double acc = 0.0, disc = 1.0;
-  int flown = 0;
-  int64_t o = j;                                // (agent step t) * n K M + j
-#pragma unroll 1
-  for (int h = 0; h < a.n_plan_steps; ++h) {
-    const int act = in_range ? (int)a.plans[(int64_t)h * plans_total + ek] : 0;
-#pragma unroll 1
-    for (int rep = 0; rep < a.action_repeat; ++rep, o += lanes_total) {
-      if (live) {
-        ++flown;
-        const WindQuery wq = wind_query(s.x, s.y, s.p, s.t_elapsed);
-        WindCorners corners;
-        wind_gather(grid, wq, &corners);
-        float fu, fv, cu, cv;
-        wind_noise_from_rows(s.x, s.y, s.p, s.t_elapsed, rows, kStepBlock, shm.grad_lut, &fu, &fv);
-        asm volatile("" : "+v"(fu), "+v"(fv));
-        gp_scenario_correction(loc, alpha, n_obs, n_trip, s.x, s.y, s.p, s.t_elapsed, shm.tab, &cu, &cv);
-        asm volatile("" : "+v"(cu), "+v"(cv));
-        float nu = fu + cu, nv = fv + cv;
-        // the scenario's wind is a VALUE, as the noise is in ble_step_kernel: ble_gp_scenario_wind_f32 + ble_step_f32 give the same bits
-        asm volatile("" : "+v"(nu), "+v"(nv));
-        float r;
-        agent_step(s, c, hc, act, corners, wq, nu, nv, a.substeps, shm.acs_poly, K, park, &r, &flags, veh);
-        if (!(isfinite(s.p) && isfinite(s.t_int) && isfinite(s.x) && isfinite(s.y) && isfinite(s.batt)))
-          flags |= kFlagNonFinite;
-        if (a.reward) a.reward[o] = r;
-        const double term = disc * (double)r;
-        acc += term;
-        disc *= a.gamma;
-      } else if (in_range) {                    // a non-OK source, or a plan that went terminal: frozen, reward 0
-        if (a.reward) a.reward[o] = 0.0f;
-      }
-      live = live && s.status == kOk;
-    }
-  }
-  if (in_range) {
-    a.ret[j] = (float)acc;
-    a.steps_flown[j] = flown;
-    if (a.final_state) {
-      a.final_state[j] = s.x; a.final_state[lanes_total + j] = s.y; a.final_state[2 * lanes_total + j] = s.p;
-      a.final_state[3 * lanes_total + j] = s.batt;
-    }
-  }
-  report_flags(flags, err_flags);
+  WindScenario<S> wind{b, seed, gen, sm};
+  rollout_lane<false>(st, a, wind, shm, j, lanes_total, e, ek, plans_total, err_flags, veh);
 }
 
 // struct ble_plan_risk (include/ble_abi.h) as the kernel takes it

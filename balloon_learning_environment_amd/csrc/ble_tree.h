@@ -4,10 +4,10 @@
 // lane per (environment e, parent rank r, action a), child index c = 3 r + a, lane index j = e C + c with C = 3 P children per
 // environment: the lane loads node parent[e][r] of the previous level's arena (at level 1: environment e of the state itself), flies the
 // edge in ENVIRONMENT e's wind -- its grid, its noise key, its belief slab, whatever the node -- and stores the child as a full state plus
-// what the rollout lane keeps in registers across steps (acc, disc in fp64, flown) into index j of the other arena.  The loop body is
-// ble_rollout_kernel's / ble_rollout_belief_kernel's, a further copy on purpose (the note at the top of ble_rollout.h): the same lane
-// functions, the same frozen rule, the same order of the three return statements -- hence, for a node reached by (a_1 .. a_d), the bits
-// ble_rollout_leaves_f32 gives the plan a_1 x segment, .., a_d x segment: fp32 state and fp64 acc / disc pass through memory exactly.
+// what the rollout lane keeps in registers across steps (acc, disc in fp64, flown) into index j of the other arena.  The load, the wind
+// and the flown step are the rollouts' own (ble_lookahead.h: one text for all of them), the frozen rule is theirs -- hence, for a node
+// reached by (a_1 .. a_d), the bits ble_rollout_leaves_f32 gives the plan a_1 x segment, .., a_d x segment: fp32 state and fp64 acc /
+// disc pass through memory exactly.
 // ble_tree_select_kernel then orders the C children of every environment by §3k's order (the key and rank lane functions of ble_plan.h,
 // one wavefront per environment, no atomics) and lists the first min(C, B) as the next level's parents.  After the last level
 // ble_tree_finish_kernel orders once more -- by the returns or by a caller's scores -- and walks the best child back through `choice`.
@@ -96,21 +96,11 @@ struct TreeExpandArgs {
 template <int kWind, class V = VehicleDefault>
 __global__ __launch_bounds__(kStepBlock) void ble_tree_expand_kernel(StateDev st, TreeExpandArgs a, TreeArenaDev src, TreeArenaDev dst,
                                                                      BeliefDev b, StepNoise gen, uint32_t* err_flags, V veh) {
-  constexpr bool kNoise = kWind == kTreeWindNoise, kBelief = kWind == kTreeWindBelief;
-  double* acs_poly; float* term_save; float* grad_lut = nullptr; uint32_t* noise_draws = nullptr; double* tab = nullptr;
-  if constexpr (kNoise) {
-    __shared__ StepNoiseShared shm;
-    acs_poly = shm.acs_poly; term_save = shm.term_save; grad_lut = shm.grad_lut; noise_draws = shm.draws;
-  } else {
-    __shared__ double acs_poly_lds[kAcsPolyDoubles];
-    __shared__ float term_save_lds[kTermSaveRows * kStepBlock];
-    acs_poly = acs_poly_lds; term_save = term_save_lds;
-  }
-  if constexpr (kBelief) {
-    __shared__ double tab_lds[64];
-    tab = tab_lds;
-  }
-  const int wave = (int)threadIdx.x >> 6, lane = (int)threadIdx.x & 63;
+  using W = std::conditional_t<kWind == kTreeWindNoise, WindNoise, std::conditional_t<kWind == kTreeWindBelief, WindBelief, WindForecast>>;
+  __shared__ typename W::Shared shm;
+  W wind;
+  if constexpr (kWind == kTreeWindNoise) wind.gen = gen;
+  if constexpr (kWind == kTreeWindBelief) wind.b = b;
   const int n_children = 3 * a.n_parents;
   const int64_t lanes_total = a.n * (int64_t)n_children;         // < 2^31 (the entry point checks)
   const int64_t j = (int64_t)blockIdx.x * kStepBlock + threadIdx.x;
@@ -121,92 +111,33 @@ __global__ __launch_bounds__(kStepBlock) void ble_tree_expand_kernel(StateDev st
   const bool first = src.acc == nullptr;
   int64_t pj = e;                                // the parent node's index in src
   if (in_range && !first) pj = e * a.parent_children + tree_clamp(a.parent[e * a.beam + child / 3], a.parent_children);
-  uint32_t flags = 0;
-  EnvRegs s;
-  EnvConst c;
-  EpisodeCacheRow cached = {};
+  LookaheadLane l;
   bool live = false;
-  int n_obs = 0;
-  // the discounted return: fp64, the product and the sum as two statements (two roundings under -ffp-contract=on), rounded to fp32 once
-  double acc = 0.0, disc = 1.0;
-  int flown = 0;
   if (in_range) {
-    // the parent node's state, every load issued up front (ble_step_kernel's loads at index pj)
-    s.status = src.s.status[pj];
-    s.x = src.s.x[pj]; s.y = src.s.y[pj]; s.p = src.s.pressure[pj]; s.t_amb = src.s.ambient_temperature[pj];
-    s.t_int = src.s.internal_temperature[pj]; s.vol = src.s.envelope_volume[pj]; s.sp = src.s.superpressure[pj];
-    s.n_air = src.s.mols_air[pj]; s.batt = src.s.battery_charge[pj];
-    s.acs_power = 0.0f; s.mdot = 0.0f; s.charge = 0.0f; s.load = 0.0f;
-    s.t_elapsed = src.s.time_elapsed_s[pj]; s.sunrise_h = src.s.sunrise_h_rel[pj]; s.sunset = src.s.sunset_rel[pj];
-    s.alt_fsm = src.s.alt_fsm[pj]; s.env_fsm = src.s.env_fsm[pj]; s.paused = src.s.power_paused[pj];
-    c.lat0_deg = src.s.center_lat_deg[pj]; c.lng0_deg = src.s.center_lng_deg[pj];
-    c.ir = src.s.upwelling_infrared[pj]; c.alpha = src.s.alpha[pj]; c.start_unix = src.s.start_unix[pj];
-    if (!first) { acc = src.acc[pj]; disc = src.disc[pj]; flown = src.flown[pj]; }
-    // (the per-episode cache is environment e's: a node holds its environment's constants)
-    if (st.episode_cache != nullptr) cached = episode_cache_load(st.episode_cache, a.n, e);
-    if constexpr (kBelief) n_obs = b.n_obs[e];
-    live = s.status == kOk && !(acc != acc);     // a dead or void parent flies nothing
+    // the parent node's state; the per-episode cache is environment e's: a node holds its environment's constants
+    lookahead_load(l, src.s, pj, st, a.n, e);
+    if (!first) { l.acc = src.acc[pj]; l.disc = src.disc[pj]; l.flown = src.flown[pj]; }
+    wind.load(e);
+    live = l.s.status == kOk && !(l.acc != l.acc);     // a dead or void parent flies nothing
   }
   const bool flew = live;                        // (edge_steps >= 1: a live parent enters its first step)
-  for (int q = (int)threadIdx.x; q < kAcsPolyDoubles; q += kStepBlock) acs_poly[q] = kAcsPoly.c[q];
-  if constexpr (kNoise) grad_lut_fill(grad_lut, (int)threadIdx.x, kStepBlock);
-  if constexpr (kBelief) { if (threadIdx.x < 64) tab[threadIdx.x] = gp_belief_table_entry((int)threadIdx.x); }
+  lookahead_fill<W>(shm);
   __syncthreads();
-  EnvHoisted hc;
-  if (live) {
-    // per-episode constants: from the cache where its entry belongs to these constants; a miss recomputes and does NOT store
-    if (st.episode_cache != nullptr && episode_cache_hit(cached, c)) hc = hoisted_from_cache(cached, c);
-    else hc = hoist_constants(c);
-  }
-  if (kNoise && in_range)
-    noise_draws_fetch(gen.seed, (uint64_t)e, (uint64_t)(e + gen.env_offset), gen.episode ? gen.episode[e] : 0u, nullptr, a.n,
-                      noise_draws + threadIdx.x, kStepBlock);
-  int n_trip = 0;
-  const double* slab = nullptr;
-  if constexpr (kBelief) {
-    n_trip = belief_wave_trip(n_obs);            // one loop for the wave, whatever environments its lanes belong to
-    slab = b.slab + e * b.stride;
-  }
-  const StrideK K = stride_k_vreg(veh.dry_mass, veh.lift, veh.v0);
-  const float* const grid = a.wind_grid + e * a.grid_env_stride;
-  float* const park = term_save + wave * (kTermSaveRows * kTermSaveStride) + lane;
+  lookahead_begin(l, wind, shm, st, a, e, in_range, live, veh);
 #pragma unroll 1
   for (int t = 0; t < a.edge_steps; ++t) {
-    if (live) {
-      ++flown;
-      const WindQuery wq = wind_query(s.x, s.y, s.p, s.t_elapsed);
-      WindCorners corners;
-      wind_gather(grid, wq, &corners);
-      float nu = 0.0f, nv = 0.0f;
-      if constexpr (kNoise) {
-        wind_noise_from_rows(s.x, s.y, s.p, s.t_elapsed, noise_draws + threadIdx.x, kStepBlock, grad_lut, &nu, &nv);
-        // the noise is a VALUE, as in ble_step_kernel: no fusing of the generator's last multiplication into agent_step's sum
-        asm volatile("" : "+v"(nu), "+v"(nv));
-      }
-      if constexpr (kBelief) {
-        gp_belief_mean(slab, n_obs, n_trip, s.x, s.y, s.p, s.t_elapsed, tab, &nu, &nv);
-        // the belief's wind is a VALUE, as the noise is in ble_step_kernel
-        asm volatile("" : "+v"(nu), "+v"(nv));
-      }
-      float r;
-      agent_step(s, c, hc, act, corners, wq, nu, nv, a.substeps, acs_poly, K, park, &r, &flags, veh);
-      if (!(isfinite(s.p) && isfinite(s.t_int) && isfinite(s.x) && isfinite(s.y) && isfinite(s.batt)))
-        flags |= kFlagNonFinite;
-      const double term = disc * (double)r;
-      acc += term;
-      disc *= a.gamma;
-    }
-    live = live && s.status == kOk;              // a plan that went terminal: frozen, reward 0
+    if (live) lookahead_step(l, wind, shm, a, act, veh);
+    live = live && l.s.status == kOk;            // a plan that went terminal: frozen, reward 0
   }
   if (in_range) {
     // the child: what the lane holds after its last executed step, or -- a dead or void parent -- the parent's own words (leaf_store)
-    leaf_store(src.s, dst.s, pj, j, flew, s, c, act);
+    leaf_store(src.s, dst.s, pj, j, flew, l.s, l.c, act);
     // a parent that flew nothing is carried on by its a = 0 child alone; the others, and every child of a void parent, are void
-    if (!flew && act != 0) acc = __builtin_nan("");
-    dst.acc[j] = acc; dst.disc[j] = disc; dst.flown[j] = flown;
-    dst.ret[j] = (float)acc;
+    if (!flew && act != 0) l.acc = __builtin_nan("");
+    dst.acc[j] = l.acc; dst.disc[j] = l.disc; dst.flown[j] = l.flown;
+    dst.ret[j] = (float)l.acc;
   }
-  report_flags(flags, err_flags);
+  report_flags(l.flags, err_flags);
 }
 
 // struct ble_tree_select (include/ble_abi.h) as the kernel takes it

@@ -3,9 +3,9 @@
 // A GROUP (e, c) is M scenario nodes, node (e, c, m) at index (e C_d + c) M + m of the level's arena: the same child of the same
 // environment, flown in scenario m.  ble_tree_expand_scenarios_kernel flies one edge per lane, one lane per (e, r, a, m), lane index =
 // destination node index: the lane loads node (e C_{d-1} + parent[e][r]) M + m of the previous level's arena (at level 1: environment e
-// of the state itself) and flies the edge with the loop body of ble_rollout_scenarios_kernel, a further copy on purpose (the note at the
-// top of ble_rollout.h) -- the same draws, the same noise and correction behind the same three value barriers, the single float add, the
-// same order of the three return statements -- and stores the child as ble_tree_expand_kernel does.  Hence a node of a non-void group
+// of the state itself) and flies the edge with the lane body of ble_rollout_scenarios_kernel (ble_lookahead.h with WindScenario: one
+// text for both -- the same draws, the same noise and correction behind the same three value barriers, the single float add, the same
+// order of the three return statements) and stores the child as ble_tree_expand_kernel does.  Hence a node of a non-void group
 // reached by (a_1 .. a_d) holds the bits ble_rollout_scenarios_f32 gives the plan a_1 x segment, .., a_d x segment in scenario m.
 // The level's ret is [n][C_d][M]: ble_plan_risk_kernel maps it to [n][C_d], which ble_tree_select_kernel and ble_tree_finish_kernel
 // take as their keys.  No arithmetic of its own.
@@ -47,8 +47,8 @@ template <class V, class S>
 __global__ __launch_bounds__(kStepBlock) void ble_tree_expand_scenarios_kernel(StateDev st, TreeExpandArgs a, TreeArenaDev src, TreeArenaDev dst,
                                                                               ScenariosDev b, S seed, ScenarioGen gen, uint32_t* err_flags,
                                                                               V veh) {
+  using W = WindScenario<S>;
   __shared__ ScenarioRolloutShared shm;
-  const int wave = (int)threadIdx.x >> 6, lane = (int)threadIdx.x & 63;
   const int n_children = 3 * a.n_parents;
   const int64_t groups_total = a.n * (int64_t)n_children;
   const int64_t lanes_total = groups_total * b.num;              // < 2^31 (the entry point checks)
@@ -63,88 +63,37 @@ __global__ __launch_bounds__(kStepBlock) void ble_tree_expand_scenarios_kernel(S
   int64_t pg = e;                                // the parent group's first node in src (level 1: the environment)
   if (in_range && !first) pg = (e * a.parent_children + tree_clamp(a.parent[e * a.beam + child / 3], a.parent_children)) * b.num;
   const int64_t pj = first ? pg : pg + sm;       // the parent node
-  uint32_t flags = 0;
-  EnvRegs s;
-  EnvConst c;
-  EpisodeCacheRow cached = {};
+  W wind{b, seed, gen, sm};
+  LookaheadLane l;
   bool live = false;
   int rule = kTreeLaneCarry;
-  int n_obs = 0;
-  // the discounted return: fp64, the product and the sum as two statements (two roundings under -ffp-contract=on), rounded to fp32 once
-  double acc = 0.0, disc = 1.0;
-  int flown = 0;
   if (in_range) {
     // fly, carry or void: from the parent group's M status bytes and M acc words, once per edge
     rule = tree_scenario_lane(src.s.status + pg, first ? nullptr : src.acc + pg, b.num, sm, act);
-    // the parent node's state, every load issued up front (ble_step_kernel's loads at index pj)
-    s.status = src.s.status[pj];
-    s.x = src.s.x[pj]; s.y = src.s.y[pj]; s.p = src.s.pressure[pj]; s.t_amb = src.s.ambient_temperature[pj];
-    s.t_int = src.s.internal_temperature[pj]; s.vol = src.s.envelope_volume[pj]; s.sp = src.s.superpressure[pj];
-    s.n_air = src.s.mols_air[pj]; s.batt = src.s.battery_charge[pj];
-    s.acs_power = 0.0f; s.mdot = 0.0f; s.charge = 0.0f; s.load = 0.0f;
-    s.t_elapsed = src.s.time_elapsed_s[pj]; s.sunrise_h = src.s.sunrise_h_rel[pj]; s.sunset = src.s.sunset_rel[pj];
-    s.alt_fsm = src.s.alt_fsm[pj]; s.env_fsm = src.s.env_fsm[pj]; s.paused = src.s.power_paused[pj];
-    c.lat0_deg = src.s.center_lat_deg[pj]; c.lng0_deg = src.s.center_lng_deg[pj];
-    c.ir = src.s.upwelling_infrared[pj]; c.alpha = src.s.alpha[pj]; c.start_unix = src.s.start_unix[pj];
-    if (!first) { acc = src.acc[pj]; disc = src.disc[pj]; flown = src.flown[pj]; }
-    // (the per-episode cache is environment e's: a node holds its environment's constants)
-    if (st.episode_cache != nullptr) cached = episode_cache_load(st.episode_cache, a.n, e);
-    n_obs = b.n_obs[e];
+    // the parent node's state; the per-episode cache is environment e's: a node holds its environment's constants
+    lookahead_load(l, src.s, pj, st, a.n, e);
+    if (!first) { l.acc = src.acc[pj]; l.disc = src.disc[pj]; l.flown = src.flown[pj]; }
+    wind.load(e);
     live = rule == kTreeLaneFly;                 // a stopped node flies nothing
   }
   const bool flew = live;                        // (edge_steps >= 1: a live parent enters its first step)
-  for (int q = (int)threadIdx.x; q < kAcsPolyDoubles; q += kStepBlock) shm.acs_poly[q] = kAcsPoly.c[q];
-  grad_lut_fill(shm.grad_lut, (int)threadIdx.x, kStepBlock);
-  if (threadIdx.x < 64) shm.tab[threadIdx.x] = gp_belief_table_entry((int)threadIdx.x);
+  lookahead_fill<W>(shm);
   __syncthreads();
-  EnvHoisted hc;
-  if (live) {
-    // per-episode constants: from the cache where its entry belongs to these constants; a miss recomputes and does NOT store
-    if (st.episode_cache != nullptr && episode_cache_hit(cached, c)) hc = hoisted_from_cache(cached, c);
-    else hc = hoist_constants(c);
-  }
-  uint32_t* const rows = shm.draws + threadIdx.x;
-  if (in_range) scenario_draws_fetch(seed.of(e), seed.key(e, gen.env_offset), gen.episode ? gen.episode[e] : 0u, sm, rows, kStepBlock);
-  const int n_trip = belief_wave_trip(n_obs);          // one loop for the wave, whatever environments its lanes belong to
-  const double* const loc = b.slab + e * b.stride;
-  const double* const alpha = loc + kBeliefAlphaAt + kScenarioAlphaDoubles * sm;
-  const StrideK K = stride_k_vreg(veh.dry_mass, veh.lift, veh.v0);
-  const float* const grid = a.wind_grid + e * a.grid_env_stride;
-  float* const park = shm.term_save + wave * (kTermSaveRows * kTermSaveStride) + lane;
+  lookahead_begin(l, wind, shm, st, a, e, in_range, live, veh);
 #pragma unroll 1
   for (int t = 0; t < a.edge_steps; ++t) {
-    if (live) {
-      ++flown;
-      const WindQuery wq = wind_query(s.x, s.y, s.p, s.t_elapsed);
-      WindCorners corners;
-      wind_gather(grid, wq, &corners);
-      float fu, fv, cu, cv;
-      wind_noise_from_rows(s.x, s.y, s.p, s.t_elapsed, rows, kStepBlock, shm.grad_lut, &fu, &fv);
-      asm volatile("" : "+v"(fu), "+v"(fv));
-      gp_scenario_correction(loc, alpha, n_obs, n_trip, s.x, s.y, s.p, s.t_elapsed, shm.tab, &cu, &cv);
-      asm volatile("" : "+v"(cu), "+v"(cv));
-      float nu = fu + cu, nv = fv + cv;
-      // the scenario's wind is a VALUE, as the noise is in ble_step_kernel: ble_gp_scenario_wind_f32 + ble_step_f32 give the same bits
-      asm volatile("" : "+v"(nu), "+v"(nv));
-      float r;
-      agent_step(s, c, hc, act, corners, wq, nu, nv, a.substeps, shm.acs_poly, K, park, &r, &flags, veh);
-      if (!(isfinite(s.p) && isfinite(s.t_int) && isfinite(s.x) && isfinite(s.y) && isfinite(s.batt)))
-        flags |= kFlagNonFinite;
-      const double term = disc * (double)r;
-      acc += term;
-      disc *= a.gamma;
-    }
-    live = live && s.status == kOk;              // a scenario that went terminal: frozen, reward 0
+    if (live) lookahead_step(l, wind, shm, a, act, veh);
+    live = live && l.s.status == kOk;            // a scenario that went terminal: frozen, reward 0
   }
   if (in_range) {
     // the child: what the lane holds after its last executed step, or -- a stopped parent -- the parent's own words (leaf_store)
-    leaf_store(src.s, dst.s, pj, j, flew, s, c, act);
+    leaf_store(src.s, dst.s, pj, j, flew, l.s, l.c, act);
     // a spent group is carried on by its a = 0 child group alone; the others, and every child group of a void group, are void
-    if (rule == kTreeLaneVoid) acc = __builtin_nan("");
-    dst.acc[j] = acc; dst.disc[j] = disc; dst.flown[j] = flown;
-    dst.ret[j] = (float)acc;
+    if (rule == kTreeLaneVoid) l.acc = __builtin_nan("");
+    dst.acc[j] = l.acc; dst.disc[j] = l.disc; dst.flown[j] = l.flown;
+    dst.ret[j] = (float)l.acc;
   }
-  report_flags(flags, err_flags);
+  report_flags(l.flags, err_flags);
 }
 #endif  // __HIPCC__
 

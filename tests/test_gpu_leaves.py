@@ -157,6 +157,72 @@ def test_leaf_states_are_a_stepped_copys_state(n, k, wind, repeat):
   assert np.array_equal(again.steps_flown.cpu().numpy()[:, 0] == 1, status.reshape(-1) == 0)
 
 
+VEHICLE = {'payload_mass': 95.0, 'battery_capacity_wh': 2800.0}          # test_gpu_rollout.py's run-time vehicle
+RT_NIGHT, RT_DEAD = 0, 4
+
+
+def _five_with_a_vehicle(seed=77):
+  """Five environments that fly a run-time vehicle (the VehicleRt instantiations), picked with their rings from a batch of 64:
+  environment RT_NIGHT flies in the dark on a battery of 23 Wh, which the night load of 183.7 W drains in 45 strides of 10 s, inside the
+  third agent step; three fly in daylight; environment RT_DEAD is not OK.  (sim, rng)"""
+  big, rng, field = _parent(64, seed, steps=4)
+  night = torch.nonzero((big.state['solar_charging'] == 0) & (big.state['status'] == 0)).view(-1)
+  day = torch.nonzero((big.state['solar_charging'] > 0) & (big.state['status'] == 0)).view(-1)
+  assert night.numel() >= 1 and day.numel() >= 4, (night.numel(), day.numel())
+  pick = torch.cat([night[:1], day[:4]])
+  src = vec_state.VecSimulator(5, DEVICE)
+  for name, t in src.state.items():
+    t.copy_(big.state[name][pick])
+  src.set_grid(field)
+  src.set_vehicle(**VEHICLE)
+  src._allocate_history(True)
+  for name, t in src._gp.items():
+    t.copy_(big._gp[name][pick])
+  src._obs_reset.copy_(big._obs_reset[pick])
+  src.state['battery_charge'][RT_NIGHT] = 23.0
+  src.state['status'][RT_DEAD] = 2
+  src.state['last_command'][RT_DEAD] = 2
+  return src, rng
+
+
+@pytest.mark.parametrize('wind', ['forecast', 'noise', 'belief'])
+def test_leaf_states_with_a_runtime_vehicle_are_a_stepped_copys_state(wind):
+  """The leaf rollouts' VehicleRt instantiations, 15 lanes: every array of the arena against copies stepped with the same vehicle."""
+  n, k, h, repeat = 5, 3, 2, 2                     # four agent steps: the night environment ends inside them
+  src, rng = _five_with_a_vehicle()
+  plans = rng.integers(0, 3, (h, n, k)).astype(np.uint8)
+  belief = src.fit_wind_belief() if wind == 'belief' else None
+  kw = dict(gamma=0.993, action_repeat=repeat, noise_seed=NOISE_SEED if wind == 'noise' else None, belief=belief, want_rewards=True,
+            want_final=True)
+  before = _snapshot(src)
+  plain = src.rollout_plans(_dev(plans), **kw)
+  arena = src.leaf_arena(k)
+  for t in arena.state.values():
+    t.fill_(77)
+  got = src.rollout_plans(_dev(plans), leaves=arena, **kw)
+  _assert_untouched(src, before, 'the source')
+  for name, a, b in zip(got._fields, got, plain):          # ret, steps_flown, reward, final_state: the non-leaf entry's bits
+    assert torch.equal(a.view(torch.int32), b.view(torch.int32)), name
+  want = _stepped_copies(src, plans, repeat, wind, belief)
+  torch.cuda.synchronize()
+  for name in _abi.FIELD_NAMES:
+    a, b = arena.state[name].view(n, k), want[name]
+    assert a.dtype == b.dtype
+    bad = torch.nonzero(a.view(torch.uint8) != b.contiguous().view(torch.uint8))
+    assert bad.numel() == 0, (wind, name, bad[:4].tolist())
+  flown = got.steps_flown.cpu().numpy()
+  status = arena.state['status'].view(n, k).cpu().numpy()
+  assert np.all(flown[RT_DEAD] == 0) and np.all(status[RT_DEAD] == 2)
+  assert np.all((flown[RT_NIGHT] > 0) & (flown[RT_NIGHT] < h * repeat)) and np.all(status[RT_NIGHT] != 0)          # out of power inside the plan
+  live = [e for e in range(n) if e not in (RT_NIGHT, RT_DEAD)]
+  assert np.all(flown[live] == h * repeat) and np.all(status[live] == 0)
+  # the vehicle is really flown: the default vehicle's leaves are other leaves
+  src.set_vehicle()
+  default_arena = src.leaf_arena(k)
+  src.rollout_plans(_dev(plans), leaves=default_arena, **kw)
+  assert not torch.equal(default_arena.state['pressure'].view(n, k)[live], arena.state['pressure'].view(n, k)[live])
+
+
 def test_leaves_refusals():
   src, rng, _ = _parent(3, 5, steps=2)
   plans = torch.ones(H, 3, 5, dtype=torch.uint8, device=DEVICE)

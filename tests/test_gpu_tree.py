@@ -17,7 +17,7 @@ from balloon_learning_environment_amd import _abi, _lib, device as dev, vec_stat
 from balloon_learning_environment_amd.agents import actor_critic, beam_agent, qnet
 from balloon_learning_environment_amd.env import balloon_env
 from balloon_learning_environment_amd.eval import eval_lib, suites
-from test_gpu_leaves import _assert_untouched, _parent, _snapshot
+from test_gpu_leaves import RT_DEAD, RT_NIGHT, _assert_untouched, _five_with_a_vehicle, _parent, _snapshot
 
 pytestmark = pytest.mark.gpu
 
@@ -88,6 +88,33 @@ def test_one_level_equals_the_rollout(wind, segment):
   assert np.array_equal(_bits(got.q.cpu().numpy()), _bits(q)) and np.array_equal(got.visits.cpu().numpy(), visits)
   assert action[1] == 1 and best[1] == 0.0 and visits[1].tolist() == [1, 0, 0]
   print(f'{wind} segment {segment}: plans that went terminal {int(((flown > 0) & (flown < segment)).sum())} of {3 * n}')
+
+
+@pytest.mark.parametrize('wind', ['forecast', 'noise', 'belief'])
+def test_one_level_with_a_runtime_vehicle_equals_the_rollout(wind):
+  """ble_tree_expand_kernel's VehicleRt instantiations, 15 lanes: one level of edges of segment 2 x action_repeat 2 against the leaf
+  rollout flown with the same vehicle (which test_gpu_leaves.py holds to stepped copies)."""
+  n, segment, repeat = 5, 2, 2
+  src, _ = _five_with_a_vehicle()
+  kw = _winds(src, wind)
+  plans = np.broadcast_to(np.arange(3, dtype=np.uint8), (segment, n, 3))
+  want_arena = src.leaf_arena(3)
+  want = src.rollout_plans(_dev(plans), gamma=GAMMA, action_repeat=repeat, leaves=want_arena, **kw)
+  before = _snapshot(src)
+  got = src.tree_search(1, 1, segment=segment, action_repeat=repeat, gamma=GAMMA, **kw)
+  _assert_untouched(src, before, 'the source')
+  assert got.leaves.n == 3 * n and got.leaves.leaves_per_env == 3
+  void = np.zeros((n, 3), bool)
+  void[RT_DEAD, 1:] = True                        # a dead source: the a = 0 child carries it on, the other two stand for nothing
+  live = _dev(~void)
+  for name in _abi.FIELD_NAMES:
+    _same_words(got.leaves.state[name].view(n, 3), want_arena.state[name].view(n, 3), (wind, name))      # (a void node is the same copy)
+  _same_words(got.returns[live], want.returns[live], 'returns')
+  assert bool(torch.isnan(got.returns[~live]).all())
+  _same_words(got.steps_flown, want.steps_flown, 'steps_flown')
+  flown = want.steps_flown.cpu().numpy()
+  assert np.all(flown[RT_DEAD] == 0) and np.all((flown[RT_NIGHT] > 0) & (flown[RT_NIGHT] < segment * repeat))      # it ends inside the edge
+  assert np.all(np.delete(flown, [RT_NIGHT, RT_DEAD], 0) == segment * repeat)
 
 
 # ------------------------------------------------------------------------------------------------ 2: the exhaustive tree is the enumeration

@@ -120,6 +120,67 @@ def test_one_level_is_the_rollout(five, segment):
   assert action[DEAD] == 1 and best[DEAD] == 0.0 and visits[DEAD].tolist() == [1, 0, 0]
 
 
+VEHICLE = {'payload_mass': 95.0, 'battery_capacity_wh': 2800.0}          # test_gpu_rollout.py's run-time vehicle
+VEHICLE_SEED = 526                                # environment 3 flies in the dark, environments 0 and 4 in daylight
+
+
+@pytest.mark.parametrize('per_env_seeds', [False, True])
+def test_one_level_with_a_runtime_vehicle_is_the_rollout_and_a_stepped_copy(per_env_seeds):
+  """The VehicleRt instantiations of ble_tree_expand_scenarios_kernel and ble_rollout_scenarios_kernel under a scalar seed and under
+  per-environment seeds, 30 lanes: one level of edges of segment 2 x action_repeat 2 against the scenario rollout flown with the same
+  vehicle, and every state word of every node against scenario_wind + step on a copy that flies that vehicle."""
+  n, M, segment, repeat = 5, 2, 2, 2
+  src, _ = tgs._source(n, VEHICLE_SEED, RINGS, vehicle=VEHICLE)
+  night = (src.state['solar_charging'] == 0) & (src.state['status'] == 0)
+  night[DEAD] = False
+  night[BURST] = False
+  assert bool(night.any()), 'no environment flies in the dark'
+  src.state['battery_charge'][night] = 23.0       # the night load drains it inside the third agent step: inside the edge
+  src.state['status'][DEAD] = 1
+  src.state['mols_air'][BURST] += 30000.0
+  fit = dict(seeds=_dev(np.array([101, 102, 103, 104, 105], np.int64))) if per_env_seeds else dict(seed=33)
+  scn = src.fit_wind_scenarios(M, **fit)
+  plans = np.ascontiguousarray(np.broadcast_to(np.arange(3, dtype=np.uint8), (segment, n, 3)))
+  want = src.rollout_plans(_dev(plans), gamma=GAMMA, action_repeat=repeat, scenarios=scn, want_final=True)
+  before = _guard(src, scn)
+  got = src.tree_search(1, 1, segment=segment, action_repeat=repeat, gamma=GAMMA, scenarios=scn)
+  _assert_guarded(src, scn, before, 'the source')
+  ret, want_ret = got.returns.cpu().numpy(), want.returns.cpu().numpy()
+  void = np.zeros((n, 3), bool)
+  void[DEAD, 1:] = True
+  assert np.isnan(ret[void]).all() and not np.isnan(ret[~void]).any()
+  assert np.array_equal(_bits(ret[~void]), _bits(want_ret[~void]))
+  flown = want.steps_flown.cpu().numpy()
+  assert np.array_equal(got.steps_flown.cpu().numpy(), flown)
+  assert np.array_equal(_bits(_final(got.leaves, (n, 3, M))), _bits(want.final.cpu().numpy()))       # (a void node is the same copy)
+  dark = night.cpu().numpy()
+  assert (flown[DEAD] == 0).all() and (flown[BURST] == 1).all()
+  assert ((flown[dark] > 0) & (flown[dark] < segment * repeat)).all()
+  rest = ~dark
+  rest[[DEAD, BURST]] = False
+  assert rest.any() and (flown[rest] == segment * repeat).all()
+  # every state word of every node, the void ones included: a copy of the source flown in scenario m's wind by the step kernel
+  sd = src.state_dict()
+  ref = vec_state.VecSimulator(n, DEVICE, env_offset=src.env_offset)
+  uv = torch.zeros(n, 2, dtype=torch.float32, device=DEVICE)
+  rows = torch.arange(n, device=DEVICE)
+  for a in range(3):
+    for m in range(M):
+      index = torch.full((n,), m, dtype=torch.int32, device=DEVICE)
+      ref.load_state_dict(sd)
+      for _ in range(segment * repeat):
+        ref.scenario_wind(scn, index, out=uv)
+        ref.step(torch.full((n,), a, dtype=torch.uint8, device=DEVICE), uv)
+      at = (rows * 3 + a) * M + m
+      for name, w in ref.state.items():
+        _same_words(got.leaves.state[name][at], w, (per_env_seeds, a, m, name))
+  # the vehicle is really flown: the default vehicle's nodes are other nodes
+  src.set_vehicle()
+  default = src.tree_search(1, 1, segment=segment, action_repeat=repeat, gamma=GAMMA, scenarios=scn)
+  torch.cuda.synchronize()
+  assert not np.array_equal(_bits(default.returns.cpu().numpy()[rest]), _bits(ret[rest]))
+
+
 # ------------------------------------------------------------------------------------------------ 2: the full node state
 def test_every_array_of_every_node_is_a_stepped_copy():
   n, D, segment, B, M = 3, 2, 2, 3, 3
