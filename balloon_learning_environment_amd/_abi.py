@@ -195,6 +195,32 @@ class BleTreeFinish(ctypes.Structure):
               ('q', ctypes.c_void_p), ('visits', ctypes.c_void_p)]
 
 
+MCTS_MAX_LEAVES = 256       # BLE_MCTS_MAX_LEAVES
+MCTS_EMPTY, MCTS_EXPAND, MCTS_REVISIT = 0, 1, 2      # BLE_MCTS_EMPTY / EXPAND / REVISIT
+
+
+class BleMctsPool(ctypes.Structure):
+  """struct ble_mcts_pool: the node pool of a guided tree search: cap = 1 + 3 L R ids per environment, the nodes [R][n][3L] as a
+  ble_tree_arena, the statistics [n][cap], the round's slots [n][L] (device pointers)."""
+  _fields_ = [('n', ctypes.c_int64), ('num_rounds', ctypes.c_int32), ('leaves_per_round', ctypes.c_int32), ('max_depth', ctypes.c_int32),
+              ('segment', ctypes.c_int32), ('reserved_', ctypes.c_int64), ('nodes', BleTreeArena), ('parent', ctypes.c_void_p),
+              ('first_child', ctypes.c_void_p), ('depth', ctypes.c_void_p), ('visits', ctypes.c_void_p), ('pending', ctypes.c_void_p),
+              ('value_sum', ctypes.c_void_p), ('g', ctypes.c_void_p), ('prior', ctypes.c_void_p), ('g_range', ctypes.c_void_p),
+              ('leaf', ctypes.c_void_p), ('kind', ctypes.c_void_p)]
+
+
+class BleMctsExpand(ctypes.Structure):
+  """struct ble_mcts_expand: what one round's flights need beside the pool (ble_mcts_expand_f32)."""
+  _fields_ = [('round', ctypes.c_int32), ('action_repeat', ctypes.c_int32), ('substeps', ctypes.c_int32), ('reserved_', ctypes.c_int32),
+              ('gamma', ctypes.c_double), ('wind_grid', ctypes.c_void_p), ('grid_env_stride', ctypes.c_int64)]
+
+
+class BleMctsFinish(ctypes.Structure):
+  """struct ble_mcts_finish: the source's status and what ble_mcts_finish_f32 writes (device pointers)."""
+  _fields_ = [('source_status', ctypes.c_void_p), ('best_plan', ctypes.c_void_p), ('action', ctypes.c_void_p), ('best_return', ctypes.c_void_p),
+              ('q', ctypes.c_void_p), ('visits', ctypes.c_void_p), ('pv_length', ctypes.c_void_p)]
+
+
 SCENARIO_MAX = 16           # BLE_SCENARIO_MAX
 
 

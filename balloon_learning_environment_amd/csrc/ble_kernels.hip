@@ -831,6 +831,8 @@ __global__ __launch_bounds__(256) void ble_eval_accumulate_kernel(StateDev st, c
 #include "ble_scenarios.h"
 // the beam search flown in the scenario winds: after ble_tree.h (the arenas) and ble_scenarios.h (the slab, the rollout's LDS)
 #include "ble_tree_scenarios.h"
+// guided tree search: PUCT over a node pool; after ble_tree.h (the arenas) and ble_gp_belief.h
+#include "ble_mcts.h"
 // fp64 primitive probe (test-only entry point): op 0 rcp seed, 1 d_rcp, 2 rsq seed, 3 d_rsqrt,
 // 4 d_sqrt_fast, 5 d_log_fast, 6 d_exp_fast, 7 sin (sincos_f64), 8 cos (sincos_f64)
 __global__ __launch_bounds__(256) void probe_f64_kernel(const double* x, double* y, int op, int64_t n) {
@@ -2496,6 +2498,78 @@ int ble_tree_finish_f32(const struct ble_tree_finish* fin, void* stream) {
   const TreeFinishArgs a{fin->n, fin->n_children, fin->beam, fin->depth, fin->segment, fin->ret, fin->score ? fin->score : fin->ret,
                          fin->source_status, fin->choice, fin->best_plan, fin->action, fin->best_return, fin->q, fin->visits};
   return launch(ble_tree_finish_kernel, fin->n, 1, kPlanSelectBlock, stream, a);
+}
+
+// ---- guided tree search
+namespace {
+static_assert(kMctsMaxLeaves == BLE_MCTS_MAX_LEAVES && kMctsEmpty == BLE_MCTS_EMPTY && kMctsExpand == BLE_MCTS_EXPAND &&
+              kMctsRevisit == BLE_MCTS_REVISIT, "ble_mcts.h and ble_abi.h disagree");
+// what all four calls refuse of the pool
+inline bool mcts_pool_ok(const struct ble_mcts_pool* p) {
+  if (!p || !state_ok(p->nodes.state) || !p->nodes.acc || !p->nodes.disc || !p->nodes.flown || !p->nodes.ret || !p->parent ||
+      !p->first_child || !p->depth || !p->visits || !p->pending || !p->value_sum || !p->g || !p->prior || !p->g_range || !p->leaf || !p->kind)
+    return false;
+  if (p->n < 0 || p->n >= 2147483648LL || p->num_rounds < 1 || p->leaves_per_round < 1 ||
+      (int64_t)p->num_rounds * p->leaves_per_round > BLE_MCTS_MAX_LEAVES || p->max_depth < 1 || p->segment < 1 ||
+      (int64_t)p->max_depth * p->segment > BLE_ROLLOUT_MAX_STEPS || p->reserved_ != 0)
+    return false;
+  return p->n * (int64_t)(1 + 3 * p->num_rounds * p->leaves_per_round) < 2147483648LL;
+}
+inline bool mcts_round_ok(const struct ble_mcts_pool* p, int32_t round) { return round >= 0 && round < p->num_rounds; }
+inline MctsPoolDev mcts_pool_dev(const struct ble_mcts_pool* p) {
+  return MctsPoolDev{p->n, p->num_rounds, p->leaves_per_round, p->max_depth, p->segment, tree_arena_dev(p->nodes),
+                     MctsStats{p->parent, p->first_child, p->depth, p->visits, p->pending, p->value_sum, p->g, p->prior, p->g_range},
+                     p->leaf, p->kind};
+}
+constexpr int kMctsEnvsPerBlock = kMctsBlock;    // select, backup, finish: one lane per environment
+}  // namespace
+
+int ble_mcts_select_f32(const struct ble_mcts_pool* pool, int32_t round, double c_puct, const uint8_t* source_status, const float* root_prior,
+                        void* stream) {
+  if (!mcts_pool_ok(pool) || !mcts_round_ok(pool, round) || !source_status || !(c_puct >= 0.0 && c_puct <= 1.7976931348623157e308))
+    return BLE_E_INVALID_ARG;                                         // (a NaN c_puct fails both comparisons)
+  return launch(ble_mcts_select_kernel, pool->n, kMctsEnvsPerBlock, kMctsBlock, stream, mcts_pool_dev(pool), (int)round, c_puct, source_status,
+                root_prior);
+}
+
+int ble_mcts_expand_f32(const ble_state_f32* st, const struct ble_mcts_pool* pool, const struct ble_mcts_expand* ex, const ble_noise_gen* noise,
+                        const ble_gp_belief* belief, uint32_t* err_flags, void* stream) {
+  if (noise != nullptr && belief != nullptr) return BLE_E_INVALID_ARG;                  // two winds
+  if (!state_ok(st) || !mcts_pool_ok(pool) || !ex || !ex->wind_grid || !mcts_round_ok(pool, ex->round) || ex->action_repeat < 1 ||
+      (int64_t)pool->max_depth * pool->segment * ex->action_repeat > BLE_ROLLOUT_MAX_STEPS || ex->substeps < 1 ||
+      ex->substeps > BLE_MAX_SUBSTEPS || ex->reserved_ != 0 || ex->grid_env_stride < 0 || !(ex->gamma >= 0.0 && ex->gamma <= 1.0) ||
+      (noise != nullptr && noise->env_offset < 0) || state_arrays_shared(pool->nodes.state, st))
+    return BLE_E_INVALID_ARG;
+  BeliefDev b{nullptr, 0, nullptr};
+  if (belief != nullptr && (!gp_belief(belief, &b) || belief->n != pool->n)) return BLE_E_INVALID_ARG;   // (a belief of another batch would be read out of bounds)
+  return with_vehicle<false>(st, nullptr, [&](auto veh) {
+    if (pool->n == 0) return BLE_OK;
+    const MctsExpandArgs a{pool->n, ex->round, pool->segment * ex->action_repeat, ex->substeps, ex->gamma, ex->wind_grid, ex->grid_env_stride};
+    const MctsPoolDev p = mcts_pool_dev(pool);
+    const int64_t lanes = pool->n * (int64_t)(3 * pool->leaves_per_round);
+    const StepNoise none{0ull, nullptr, nullptr, 0ll};
+    if (belief != nullptr)
+      return launch(ble_mcts_expand_kernel<kTreeWindBelief, decltype(veh)>, lanes, kStepBlock, kStepBlock, stream, state_dev(st), a, p, b, none,
+                    err_flags, veh);
+    if (noise != nullptr)      // (the harmonic cache is not handed on: the kernel draws into LDS and fills no cache)
+      return launch(ble_mcts_expand_kernel<kTreeWindNoise, decltype(veh)>, lanes, kStepBlock, kStepBlock, stream, state_dev(st), a, p, b,
+                    StepNoise{noise->seed, noise->episode, nullptr, (long long)noise->env_offset}, err_flags, veh);
+    return launch(ble_mcts_expand_kernel<kTreeWindForecast, decltype(veh)>, lanes, kStepBlock, kStepBlock, stream, state_dev(st), a, p, b, none,
+                  err_flags, veh);
+  });
+}
+
+int ble_mcts_backup_f32(const struct ble_mcts_pool* pool, int32_t round, const float* value, const float* probs, void* stream) {
+  if (!mcts_pool_ok(pool) || !mcts_round_ok(pool, round) || (value == nullptr) != (probs == nullptr)) return BLE_E_INVALID_ARG;
+  return launch(ble_mcts_backup_kernel, pool->n, kMctsEnvsPerBlock, kMctsBlock, stream, mcts_pool_dev(pool), (int)round, value, probs);
+}
+
+int ble_mcts_finish_f32(const struct ble_mcts_pool* pool, const struct ble_mcts_finish* fin, void* stream) {
+  if (!mcts_pool_ok(pool) || !fin || !fin->source_status || !fin->best_plan || !fin->action || !fin->best_return || !fin->q || !fin->visits ||
+      !fin->pv_length)
+    return BLE_E_INVALID_ARG;
+  const MctsFinishArgs a{fin->source_status, fin->best_plan, fin->action, fin->best_return, fin->q, fin->visits, fin->pv_length};
+  return launch(ble_mcts_finish_kernel, pool->n, kMctsEnvsPerBlock, kMctsBlock, stream, mcts_pool_dev(pool), a);
 }
 
 int ble_gp_fit_scenarios_f32(const ble_gp_history_f32* hist, const uint8_t* reset_mask, const int32_t* time_s, const ble_gp_scenarios* scn,

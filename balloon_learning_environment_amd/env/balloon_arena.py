@@ -205,6 +205,14 @@ class VecBalloonArena:
     WindScenarios of fit_wind_scenarios): the tree flown in M sampled winds and ordered by the risk score."""
     return self.sim.tree_search(depth, beam_width, segment, action_repeat, gamma, noise_seed=noise_seed, belief=belief, **kw)
 
+  def mcts_search(self, num_rounds: int, leaves_per_round: int, max_depth: int, segment: int = 4, action_repeat: int = 1,
+                  gamma: float = 0.993, c_puct: float = 1.25, noise_seed: Optional[int] = None, belief=None, **kw):
+    """Guided tree search from the current states without changing them: num_rounds rounds of leaves_per_round PUCT descents per env
+    over a node pool -> MCTSSearch(action, q, visits, best_return, best_plan, pv_length, pool); VecSimulator.mcts_search (guide_fn=,
+    root_prior=, buffers=, trace= go through).  noise_seed / belief: lookahead's winds."""
+    return self.sim.mcts_search(num_rounds, leaves_per_round, max_depth, segment, action_repeat, gamma, c_puct, noise_seed=noise_seed,
+                                belief=belief, **kw)
+
   def fit_wind_belief(self, time_s: Optional[torch.Tensor] = None, out=None):
     """Every env's WindGP fitted once and kept on the device: WindBelief(slab, n_obs); VecSimulator.fit_wind_belief."""
     return self.sim.fit_wind_belief(time_s, out)

@@ -280,6 +280,21 @@ class VecBalloonEnv:
     noise_seed = self.arena._seed if (wind == 'truth' and self._wind_noise) else None
     return self.arena.tree_search(depth, beam_width, segment, action_repeat, gamma, noise_seed=noise_seed, **kw)
 
+  def mcts_search(self, num_rounds: int, leaves_per_round: int, max_depth: int, segment: int = 4, action_repeat: int = 1,
+                  gamma: float = 0.993, c_puct: float = 1.25, wind: str = 'truth', **kw):
+    """Guided tree search from where each balloon is now, nothing of the environments changed -> MCTSSearch(action, q,
+    visits, best_return, best_plan, pv_length, pool) (VecSimulator.mcts_search; guide_fn=, root_prior=, buffers=, trace= go through).
+    wind: lookahead's 'truth', 'forecast' or 'belief' (fitted now); scenario winds have no node pool."""
+    if wind == 'scenarios':
+      raise ValueError("mcts_search: wind='scenarios' has no node pool (M end states per node); search in the belief, the forecast or the truth")
+    if wind not in ('truth', 'forecast', 'belief'):
+      raise ValueError(f"mcts_search: wind is 'truth', 'forecast' or 'belief', not {wind!r}")
+    if wind == 'belief':
+      self._belief = self.arena.fit_wind_belief(out=self._belief)
+      return self.arena.mcts_search(num_rounds, leaves_per_round, max_depth, segment, action_repeat, gamma, c_puct, belief=self._belief, **kw)
+    noise_seed = self.arena._seed if (wind == 'truth' and self._wind_noise) else None
+    return self.arena.mcts_search(num_rounds, leaves_per_round, max_depth, segment, action_repeat, gamma, c_puct, noise_seed=noise_seed, **kw)
+
   def planner(self, search: str = 'sample', **kw):
     """A look-ahead agent bound to these environments.  search='sample' (the default): agents.lookahead_agent.VecLookaheadAgent(**kw)
     -- num_plans, horizon, action_repeat, segment, gamma, wind ('belief' by default; 'scenarios' with num_scenarios, risk_tail), iterations, elite, seed,
@@ -288,12 +303,21 @@ class VecBalloonEnv:
     default, 'forecast' or 'truth'), leaf_value, action_values: a systematic, deterministic search of a shared-prefix tree of plans;
     with wind='scenarios' agents.beam_agent.VecScenarioBeamSearchAgent -- the same tree flown in num_scenarios sampled winds and ordered
     by risk_tail's score (seed keys the scenario streams; no leaf_value).
+    search='mcts': agents.mcts_agent.VecMCTSAgent(**kw) -- num_rounds, leaves_per_round, max_depth (all three required), segment, action_repeat, gamma, c_puct,
+    wind ('belief' by default, 'forecast' or 'truth'), guide (a device agent or trainer whose prior and value steer the search): PUCT over
+    a node pool, the root's visit counts as the answer.
     wind='truth' flies the plans in the wind these environments fly, this env's wind noise included (with wind_noise=False the truth
     is the forecast).  actions = agent.act(obs); obs, reward, terminal = env.step(actions): no host synchronisation in either."""
-    if search not in ('sample', 'beam'):
-      raise ValueError(f"planner: search is 'sample' or 'beam', not {search!r}")
+    if search not in ('sample', 'beam', 'mcts'):
+      raise ValueError(f"planner: search is 'sample', 'beam' or 'mcts', not {search!r}")
     kw.setdefault('device', self.device)
-    if search == 'beam':
+    if search == 'mcts':
+      from balloon_learning_environment_amd.agents import mcts_agent
+      missing = [k for k in ('num_rounds', 'leaves_per_round', 'max_depth') if k not in kw]
+      if missing:                  # (VecMCTSAgent's three arguments without a default)
+        raise ValueError(f"planner: search='mcts' needs {', '.join(missing)}: the budget of a guided tree search has no default")
+      agent = mcts_agent.VecMCTSAgent(**kw)
+    elif search == 'beam':
       from balloon_learning_environment_amd.agents import beam_agent
       if kw.get('wind') == 'scenarios':
         agent = beam_agent.VecScenarioBeamSearchAgent(**{k: v for k, v in kw.items() if k != 'wind'})

@@ -113,6 +113,84 @@ class TreeBuffers:
     return self._structs[level & 1]
 
 
+class MCTSSearch(collections.namedtuple('MCTSSearch', ('action', 'q', 'visits', 'best_return', 'best_plan', 'pv_length', 'pool'))):
+  """What mcts_search returns: action [n] u8, q [n, 3] f32 (the mean value of the root's children, -Inf: void), visits [n, 3] i32,
+  best_return [n] f32 = q[action], best_plan [max_depth * segment, n] u8 (the principal variation, padded with STAY), pv_length [n] i32
+  (its edges) and pool, the MCTSBuffers the search wrote into (the nodes, their statistics, the last round's slots)."""
+
+
+class MCTSBuffers:
+  """The device memory of a guided tree search over one simulator (VecSimulator.mcts_buffers): the node pool -- cap = 1 + 3 L R ids per
+  environment, id 0 the environment itself, the others stored round-major [R][n][3L] as full states plus acc, disc (float64), flown
+  (int32), ret (float32) --, `arenas[r]`, round r's slice as a leaf arena of 3L leaves per environment (a view: observe_leaves takes it),
+  the statistics [n, cap] (parent, first_child, depth, visits, pending int32; value_sum, g float64; prior [n, cap, 3] float32), g_range
+  [n, 2], the slots leaf and kind [n, L], the results, and -- with guide=True -- the network's rows: obs [n 3L, 1099], value [n 3L],
+  probs [n 3L, 3], guide_action [n 3L]."""
+
+  def __init__(self, sim: 'VecSimulator', num_rounds: int, leaves_per_round: int, max_depth: int, segment: int = 4, guide: bool = False):
+    R, L, D, self.segment = int(num_rounds), int(leaves_per_round), int(max_depth), int(segment)
+    if R < 1 or L < 1 or L * R > _abi.MCTS_MAX_LEAVES:
+      raise ValueError(f'mcts_search: num_rounds >= 1, leaves_per_round >= 1 and their product <= {_abi.MCTS_MAX_LEAVES}, not {R} x {L}')
+    if D < 1 or self.segment < 1 or D * self.segment > _abi.ROLLOUT_MAX_STEPS:
+      raise ValueError(f'mcts_search: max_depth >= 1, segment >= 1 and max_depth * segment <= {_abi.ROLLOUT_MAX_STEPS}, not {D} x {segment}')
+    cap = 1 + 3 * L * R
+    if sim.n * cap >= 2 ** 31:
+      raise ValueError(f'mcts_search: n * (1 + 3 * leaves_per_round * num_rounds) < 2^31, not {sim.n} x {cap}')
+    self.sim, self.rounds, self.leaves, self.max_depth, self.cap, self.with_guide = sim, R, L, D, cap, bool(guide)
+    n, device, per_round = sim.n, sim.device, sim.n * 3 * L
+    with torch.cuda.device(device):
+      self.node_state = {name: torch.zeros(R * per_round, dtype=dev.torch_dtype(_abi.FIELD_DTYPES[name]), device=device)
+                         for name in _abi.FIELD_NAMES}
+      self._node_struct = dev.state_struct(self.node_state)
+      self.acc = torch.zeros(R * per_round, dtype=torch.float64, device=device)
+      self.disc = torch.zeros(R * per_round, dtype=torch.float64, device=device)
+      self.flown = torch.zeros(R * per_round, dtype=torch.int32, device=device)
+      self.ret = torch.zeros(R * per_round, dtype=torch.float32, device=device)
+      self.arenas = []
+      for r in range(R):              # round r's slice of every array, as a leaf arena of the simulator
+        arena = sim.leaf_arena(3 * L)
+        arena.state = {name: t[r * per_round:(r + 1) * per_round] for name, t in self.node_state.items()}
+        arena._struct = dev.state_struct(arena.state, arena.episode_cache)
+        arena.set_vehicle(**sim.vehicle)
+        self.arenas.append(arena)
+      self.parent, self.first_child, self.depth, self.visits, self.pending = (torch.zeros(n, cap, dtype=torch.int32, device=device)
+                                                                              for _ in range(5))
+      self.value_sum = torch.zeros(n, cap, dtype=torch.float64, device=device)
+      self.g = torch.zeros(n, cap, dtype=torch.float64, device=device)
+      self.prior = torch.zeros(n, cap, 3, dtype=torch.float32, device=device)
+      self.g_range = torch.zeros(n, 2, dtype=torch.float64, device=device)
+      self.leaf = torch.zeros(n, L, dtype=torch.int32, device=device)
+      self.kind = torch.zeros(n, L, dtype=torch.int32, device=device)
+      self.action = torch.zeros(n, dtype=torch.uint8, device=device)
+      self.best_plan = torch.zeros(D * self.segment, n, dtype=torch.uint8, device=device)
+      self.best_return = torch.zeros(n, dtype=torch.float32, device=device)
+      self.q = torch.zeros(n, 3, dtype=torch.float32, device=device)
+      self.root_visits = torch.zeros(n, 3, dtype=torch.int32, device=device)
+      self.pv_length = torch.zeros(n, dtype=torch.int32, device=device)
+      self.obs = self.value = self.probs = self.guide_action = None
+      if guide:
+        self.obs = torch.zeros(per_round, _lib.OBS_DIM, dtype=torch.float32, device=device)
+        self.value = torch.zeros(per_round, dtype=torch.float32, device=device)
+        self.probs = torch.zeros(per_round, 3, dtype=torch.float32, device=device)
+        self.guide_action = torch.zeros(per_round, dtype=torch.uint8, device=device)
+    nodes = _abi.BleTreeArena(ctypes.pointer(self._node_struct), self.acc.data_ptr(), self.disc.data_ptr(), self.flown.data_ptr(),
+                              self.ret.data_ptr())
+    self._struct = _abi.BleMctsPool(n, R, L, D, self.segment, 0, nodes, self.parent.data_ptr(), self.first_child.data_ptr(),
+                                    self.depth.data_ptr(), self.visits.data_ptr(), self.pending.data_ptr(), self.value_sum.data_ptr(),
+                                    self.g.data_ptr(), self.prior.data_ptr(), self.g_range.data_ptr(), self.leaf.data_ptr(),
+                                    self.kind.data_ptr())
+
+  def node_index(self, node_id: int, env: int) -> int:
+    """Where node node_id >= 1 of environment env lies in the pool's node arrays."""
+    r, within = divmod(int(node_id) - 1, 3 * self.leaves)
+    return (r * self.sim.n + int(env)) * 3 * self.leaves + within
+
+  def statistics(self) -> Dict[str, torch.Tensor]:
+    """Clones of the statistics (tests and traces)."""
+    return {name: getattr(self, name).clone() for name in ('parent', 'first_child', 'depth', 'visits', 'pending', 'value_sum', 'g', 'prior',
+                                                           'g_range')}
+
+
 class ReferenceError_(Exception):
   """Base for conditions on which the reference raises inside the transition."""
 
@@ -1003,6 +1081,84 @@ class VecSimulator:
     _lib.check(self.lib.ble_tree_finish_f32(ctypes.byref(fin), stream), 'ble_tree_finish_f32')
     return TreeSearch(bf.action, bf.best_plan, bf.best_return, bf.q if action_values else None, bf.visits if action_values else None, returns,
                       flown, leaves, buffers=bf)
+
+  # ------------------------------------------------------------------ guided tree search
+  def mcts_buffers(self, num_rounds: int, leaves_per_round: int, max_depth: int, segment: int = 4, guide: bool = False) -> 'MCTSBuffers':
+    """Everything an mcts_search of these sizes writes, allocated once (MCTSBuffers): the node pool with its per-round leaf-arena views,
+    the statistics, the slots and the results; guide=True: also the network's observation, value, probs and action rows.  A search that
+    is given its buffers allocates nothing, as a graph capture needs."""
+    if self.has_fleet:
+      raise ValueError('mcts_search: a fleet (set_fleet) has no look-ahead kernel; fly one vehicle per batch (set_vehicle)')
+    return MCTSBuffers(self, num_rounds, leaves_per_round, max_depth, segment, guide)
+
+  @_on_own_device
+  def mcts_search(self, num_rounds: int, leaves_per_round: int, max_depth: int, segment: int = 4, action_repeat: int = 1,
+                  gamma: float = 0.993, c_puct: float = 1.25, noise_seed: Optional[int] = None, belief: Optional[WindBelief] = None,
+                  substeps: int = SUBSTEPS, guide_fn=None, root_prior: Optional[torch.Tensor] = None,
+                  buffers: Optional['MCTSBuffers'] = None, trace: Optional[list] = None) -> 'MCTSSearch':
+    """Guided tree search: num_rounds rounds of leaves_per_round PUCT descents per environment over a persistent node pool, every new
+    node flown for one edge of segment * action_repeat agent steps (the rollouts' own lane body: a node reached by (a_1 .. a_d) holds
+    bit for bit what rollout_plans(leaves=) gives the plan a_1 x segment, .., a_d x segment), evaluated once by guide_fn, and backed up
+    as G = acc + disc * V along its path -- `ble_mcts_select_f32`, `ble_mcts_expand_f32`, `ble_mcts_backup_f32` per round, then
+    `ble_mcts_finish_f32`: the root's visit counts are the answer.  Deterministic: no random stream, no seed.
+    guide_fn: a callable (obs [n 3L, 1099], out= uint8 [n 3L], value= f32 [n 3L], probs= f32 [n 3L, 3]) -- a device agent's act_greedy --
+    called once per round on the observation of the round's nodes (observe_leaves on the round's slice of the pool); None: no observation
+    and no forward at all, V = 0 and every prior uniform.  root_prior: f32 [n, 3] for the root's children; None: uniform.
+    noise_seed / belief: rollout_plans' winds (neither: the forecast; never both).  c_puct: finite, >= 0.
+    buffers: mcts_buffers(num_rounds, leaves_per_round, max_depth, segment, guide=guide_fn is not None) to write into.  trace: a list that
+    receives (round, leaf [n, L] clone, kind [n, L] clone, statistics clones, value clone or None, probs clone or None) after every
+    backup (tests; not capturable).
+    Returns MCTSSearch(action, q, visits, best_return, best_plan, pv_length, pool): an environment that is not OK gets all STAY and
+    best_return 0, one whose root has no visited child all STAY and -Inf.  The tensors are the buffers' own, overwritten by the next search.
+    Nothing of the simulator is written; flags of the imagined flights go to rollout_flags, never err_flags.  Asynchronous on the
+    current stream, no host synchronisation (capturable in a HIP graph).  Not for fleets."""
+    if self.has_fleet:
+      raise ValueError('mcts_search: a fleet (set_fleet) has no look-ahead kernel; fly one vehicle per batch (set_vehicle)')
+    if belief is not None and noise_seed is not None:
+      raise ValueError('mcts_search: belief and noise_seed are two winds; give one of them')
+    assert self.grid is not None, 'Must call set_grid (reset) before mcts_search.'
+    R, L, D, segment, action_repeat = int(num_rounds), int(leaves_per_round), int(max_depth), int(segment), int(action_repeat)
+    if action_repeat < 1 or D * segment * action_repeat > _abi.ROLLOUT_MAX_STEPS:
+      raise ValueError(f'mcts_search: action_repeat >= 1 and max_depth * segment * action_repeat <= {_abi.ROLLOUT_MAX_STEPS}, '
+                       f'not {D} x {segment} x {action_repeat}')
+    if not 0.0 <= float(gamma) <= 1.0:
+      raise ValueError(f'mcts_search: gamma in [0, 1], not {gamma}')
+    if not 0.0 <= float(c_puct) < float('inf'):
+      raise ValueError(f'mcts_search: c_puct finite and >= 0, not {c_puct}')
+    if buffers is None:
+      buffers = self.mcts_buffers(R, L, D, segment, guide_fn is not None)
+    bf = buffers
+    if (bf.sim is not self or bf.rounds != R or bf.leaves != L or bf.max_depth != D or bf.segment != segment or
+        (guide_fn is not None and not bf.with_guide)):
+      raise ValueError(f'mcts_search: buffers of another search (mcts_buffers({R}, {L}, {D}, {segment}, guide={guide_fn is not None}) of this '
+                       f'simulator)')
+    n, stream = self.n, dev.stream_ptr(self.device)
+    if root_prior is not None:
+      assert (root_prior.dtype == torch.float32 and root_prior.is_contiguous() and tuple(root_prior.shape) == (n, 3) and
+              root_prior.device == self.device), root_prior.shape
+    for arena in bf.arenas:
+      self._check_leaf_arena(arena, 3 * L)
+    gen = None if noise_seed is None else _abi.BleNoiseGen(int(noise_seed) & (2 ** 64 - 1), self.episode.data_ptr(), None, self.env_offset)
+    b = None if belief is None else self._belief_struct(belief)
+    pool, status = ctypes.byref(bf._struct), self.state['status'].data_ptr()
+    for r in range(R):
+      _lib.check(self.lib.ble_mcts_select_f32(pool, r, float(c_puct), status, dev.ptr(root_prior), stream), 'ble_mcts_select_f32')
+      ex = _abi.BleMctsExpand(r, action_repeat, int(substeps), 0, float(gamma), self.grid.data_ptr(), self.grid_env_stride)
+      _lib.check(self.lib.ble_mcts_expand_f32(ctypes.byref(self._struct), pool, ctypes.byref(ex), None if gen is None else ctypes.byref(gen),
+                                              None if b is None else ctypes.byref(b), self.rollout_flags.data_ptr(), stream),
+                 'ble_mcts_expand_f32')
+      if guide_fn is not None:
+        self.observe_leaves(bf.arenas[r], out=bf.obs)
+        guide_fn(bf.obs, out=bf.guide_action, value=bf.value, probs=bf.probs)
+      _lib.check(self.lib.ble_mcts_backup_f32(pool, r, dev.ptr(bf.value) if guide_fn is not None else None,
+                                              dev.ptr(bf.probs) if guide_fn is not None else None, stream), 'ble_mcts_backup_f32')
+      if trace is not None:
+        trace.append((r, bf.leaf.clone(), bf.kind.clone(), bf.statistics(), bf.value.clone() if guide_fn is not None else None,
+                      bf.probs.clone() if guide_fn is not None else None))
+    fin = _abi.BleMctsFinish(status, bf.best_plan.data_ptr(), bf.action.data_ptr(), bf.best_return.data_ptr(), bf.q.data_ptr(),
+                             bf.root_visits.data_ptr(), bf.pv_length.data_ptr())
+    _lib.check(self.lib.ble_mcts_finish_f32(pool, ctypes.byref(fin), stream), 'ble_mcts_finish_f32')
+    return MCTSSearch(bf.action, bf.q, bf.root_visits, bf.best_return, bf.best_plan, bf.pv_length, bf)
 
   def _tree_search_scenarios(self, bf: 'TreeBuffers', scenarios: WindScenarios, tail: int, action_repeat: int, gamma: float, substeps: int,
                              action_values: bool, trace: Optional[list]) -> 'TreeSearch':

@@ -1763,6 +1763,109 @@ int ble_tree_finish_f32(const struct ble_tree_finish* fin, void* stream);
 int ble_tree_expand_scenarios_f32(const ble_state_f32* st, const struct ble_tree_expand* ex, const ble_gp_scenarios* scn,
                                   const ble_scenario_gen* gen, uint32_t* err_flags, void* stream);
 
+/* ------------------------------------------------------------------------------------------- guided tree search
+ * PUCT over a persistent node pool: R rounds of L descents per environment, every new node evaluated once by the caller's network, mean
+ * backups, the root's visit counts as the answer.  Deterministic: no random stream.  Added without a new ABI version.
+ *
+ * The pool (ble_mcts_pool) holds cap = 1 + 3 L R node ids per environment.  Id 0 is the root: environment e of `st` itself, never copied,
+ * read as level 1 of ble_tree_expand_f32 reads st.  Id 1 + r 3L + 3l + a is the child under action a of the l-th leaf chosen in round r.
+ * `nodes` is a ble_tree_arena of R * n * 3L entries stored round-major, [R][n][3L]: node id >= 1 of environment e lies at
+ * ((id - 1) / 3L * n + e) * 3L + (id - 1) % 3L, so the nodes born in round r are the contiguous slice [r n 3L, (r + 1) n 3L) -- a leaf
+ * arena of 3L leaves per environment (ble_observe_leaves_f32 takes it as it is).  The statistics lie [n][cap]: parent (-1: the root, or
+ * a node that was never grown), first_child (0: not expanded), depth, visits, pending (int32), value_sum and g (fp64), prior [n][cap][3]
+ * (fp32); per environment g_range [n][2] = (g_lo, g_hi), the smallest and largest G seen; leaf and kind [n][L] are the round's slots.
+ * G = acc + disc * V(node), fp64, the product and the sum two statements; V = 0 where the node's status is not OK and where there is no
+ * value.  A node whose acc is NaN is VOID: no G, visits 0, never selected.
+ *
+ * ble_mcts_select_f32(round): L descents per environment in order l = 0 .. L - 1; round 0 first initialises the root (visits 0, prior
+ * root_prior[e] or, NULL, uniform; g_range empty).  At an expanded node a descent takes the non-void child of the largest
+ *   score = Qn + c_puct * prior[a] * sqrt(Nv(node)) / (1 + Nv(child)),   Nv = visits + pending,
+ *   Qn = (value_sum / visits - g_lo) / (g_hi - g_lo) * (visits / Nv)      (0 unless g_hi > g_lo)
+ * in fp64, one operation per statement, ties to the lower action.  It ends as kind[e][l] =
+ *   BLE_MCTS_EXPAND   at a node that is not expanded, OK, of depth < max_depth, not chosen by an earlier slot of this round; pending += 3
+ *                     on the node and all its ancestors
+ *   BLE_MCTS_EMPTY    at a node an earlier slot of this round chose (and every slot of a root that is not OK or has three void children)
+ *   BLE_MCTS_REVISIT  at a node that cannot grow: status not OK, depth == max_depth, or three void children; pending += 1 on its path
+ * with leaf[e][l] the node.  source_status: st->status.
+ *
+ * ble_mcts_expand_f32(round): one lane per (e, l, a).  The lanes of an EXPAND slot load node leaf[e][l] (id 0: environment e of st, acc 0,
+ * disc 1, flown 0), fly one edge of segment * action_repeat agent steps under action a with ble_rollout_f32's loop body in environment e's
+ * wind, and store the child -- state, acc, disc, flown, ret -- at index e 3L + 3l + a of the round's slice.  The lanes of any other slot
+ * fly nothing and store void nodes (the source's words, acc NaN).  A non-void node reached by (a_1 .. a_d) holds, bit for bit, the state,
+ * (float)acc and flown ble_rollout_leaves_f32 gives the plan a_1 x segment, .., a_d x segment from environment e in the same wind.  st,
+ * the history, the belief slab and every cache are never written; flags go to err_flags.  noise / belief: ble_tree_expand_f32's winds.
+ *
+ * ble_mcts_backup_f32(round): per environment, slots in order l, then a.  value [n 3L] and probs [n 3L][3] are the network's answers
+ * on the round's slice (both NULL: V = 0, uniform priors).  A non-void newborn gets parent, depth, first_child 0, prior = its probs row (a
+ * row with a non-finite or negative entry: uniform), g = G, visits 1, value_sum G; g_range takes G; every ancestor gets visits += 1 and
+ * value_sum += G; the leaf's first_child is set.  A REVISIT slot adds (1, g of its node) to the node and its ancestors.  pending is cleared.
+ * After any round visits[node] is the number of non-void nodes in its subtree (itself included; the root: excluded) plus the revisits in
+ * it, and value_sum the sum of their G in backup order.
+ *
+ * ble_mcts_finish_f32: visits [n][3] and q [n][3] of the root's children (q: the mean value as fp32, -Inf for a void child: the encoding
+ * of ble_tree_finish_f32); action: the child with the most visits, ties to the larger q, then to the lower action; best_return =
+ * q[action]; the principal variation -- that rule followed down to a node without visited children -- as best_plan [D * segment][n],
+ * padded with STAY, and pv_length [n] (edges).  A source that is not OK: all STAY, +0.0f; a root without a visited child: all STAY, -Inf.
+ *
+ * BLE_E_INVALID_ARG before any HIP call, all four: NULL pool or any pointer of it (nodes.state or an array of it, acc, disc, flown, ret
+ * included); n < 0; num_rounds < 1, leaves_per_round < 1 or their product > BLE_MCTS_MAX_LEAVES; max_depth < 1, segment < 1 or
+ * max_depth * segment > BLE_ROLLOUT_MAX_STEPS; n * cap >= 2^31; reserved_ != 0.  select, expand, backup: round outside 0 .. num_rounds - 1.
+ * select: NULL source_status; c_puct NaN, infinite or negative.  backup: exactly one of value and probs.  finish: NULL fin or any pointer
+ * of it.  expand: NULL st, state array, ex or wind_grid; action_repeat < 1 or max_depth * segment * action_repeat >
+ * BLE_ROLLOUT_MAX_STEPS; substeps outside 1 .. BLE_MAX_SUBSTEPS; gamma NaN or outside [0, 1]; a negative grid_env_stride or
+ * noise->env_offset; both noise and belief; what ble_rollout_belief_f32 refuses of a belief, a belief whose n is not the pool's included;
+ * an invalid st->vehicle; ex->reserved_ != 0; an array of nodes.state that is the same array of st.  n == 0: BLE_OK without a launch.
+ * A fleet has no form of these calls.
+ */
+#define BLE_MCTS_MAX_LEAVES 256
+#define BLE_MCTS_EMPTY 0
+#define BLE_MCTS_EXPAND 1
+#define BLE_MCTS_REVISIT 2
+struct ble_mcts_pool {
+  int64_t n;                                 /* source environments */
+  int32_t num_rounds;                        /* R >= 1 */
+  int32_t leaves_per_round;                  /* L >= 1, L * R <= BLE_MCTS_MAX_LEAVES */
+  int32_t max_depth;                         /* D >= 1 edges */
+  int32_t segment;                           /* >= 1 plan entries per edge */
+  int64_t reserved_;                         /* 0 */
+  struct ble_tree_arena nodes;               /* R * n * 3L entries, [R][n][3L] */
+  int32_t* parent;                           /* device [n][cap] */
+  int32_t* first_child;                      /* device [n][cap] */
+  int32_t* depth;                            /* device [n][cap] */
+  int32_t* visits;                           /* device [n][cap] */
+  int32_t* pending;                          /* device [n][cap] */
+  double* value_sum;                         /* device [n][cap] */
+  double* g;                                 /* device [n][cap] */
+  float* prior;                              /* device [n][cap][3] */
+  double* g_range;                           /* device [n][2] */
+  int32_t* leaf;                             /* device [n][L] */
+  int32_t* kind;                             /* device [n][L] */
+};
+struct ble_mcts_expand {
+  int32_t round;                             /* 0 .. R - 1 */
+  int32_t action_repeat;                     /* >= 1 agent steps per plan entry */
+  int32_t substeps;                          /* 1 .. BLE_MAX_SUBSTEPS */
+  int32_t reserved_;                         /* 0 */
+  double gamma;                              /* finite, 0 <= gamma <= 1 */
+  const float* wind_grid;                    /* as for ble_step_f32 */
+  int64_t grid_env_stride;
+};
+struct ble_mcts_finish {
+  const uint8_t* source_status;              /* device [n]: st->status */
+  uint8_t* best_plan;                        /* device [D * segment][n] out */
+  uint8_t* action;                           /* device [n] out */
+  float* best_return;                        /* device [n] out */
+  float* q;                                  /* device [n][3] out */
+  int32_t* visits;                           /* device [n][3] out */
+  int32_t* pv_length;                        /* device [n] out */
+};
+int ble_mcts_select_f32(const struct ble_mcts_pool* pool, int32_t round, double c_puct, const uint8_t* source_status, const float* root_prior,
+                        void* stream);
+int ble_mcts_expand_f32(const ble_state_f32* st, const struct ble_mcts_pool* pool, const struct ble_mcts_expand* ex, const ble_noise_gen* noise,
+                        const ble_gp_belief* belief, uint32_t* err_flags, void* stream);
+int ble_mcts_backup_f32(const struct ble_mcts_pool* pool, int32_t round, const float* value, const float* probs, void* stream);
+int ble_mcts_finish_f32(const struct ble_mcts_pool* pool, const struct ble_mcts_finish* fin, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
