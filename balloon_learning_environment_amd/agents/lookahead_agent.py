@@ -8,7 +8,7 @@ as the step.  The agent needs no trained weights; it needs the simulator, which 
 any agent with a `bind`; `VecBalloonEnv.planner()` returns a bound agent).
 """
 import ctypes
-from typing import Callable, Optional, Tuple, Union
+from typing import Optional
 
 import torch
 
@@ -16,12 +16,13 @@ from balloon_learning_environment_amd import _abi
 from balloon_learning_environment_amd import _lib
 from balloon_learning_environment_amd import device as dev
 from balloon_learning_environment_amd import vec_state
+from balloon_learning_environment_amd.agents import planner
 
 WINDS = ('belief', 'forecast', 'truth', 'scenarios')
 STAY = 1
 
 
-class VecLookaheadAgent:
+class VecLookaheadAgent(planner.VecPlanner):
   """Look-ahead planning for N environments at once: act(obs) -> uint8 [N] device actions.
 
   num_plans K (<= 1024) plans per environment of `horizon` H entries, every entry flown action_repeat agent steps
@@ -55,12 +56,12 @@ class VecLookaheadAgent:
   every decision -- and so is wind='scenarios' (M end states per plan).  The same network may serve as the prior of a
   VecPriorPlannerAgent and as leaf_value.  None (the default): today's calls and today's bits."""
 
+  WINDS, SEEDED = WINDS, True
+
   def __init__(self, num_plans: int = 64, horizon: int = 24, action_repeat: int = 1, segment: int = 4, gamma: float = 0.993,
                wind: str = 'belief', iterations: int = 1, elite: int = 8, seed: int = 0, device='cuda:0',
                substeps: int = vec_state.SUBSTEPS, num_scenarios: int = 8, risk_tail: Optional[int] = None, prior_strength: int = 0,
                action_values: bool = False, leaf_value=None):
-    if wind not in WINDS:
-      raise ValueError(f"VecLookaheadAgent: wind is 'belief', 'forecast', 'truth' or 'scenarios', not {wind!r}")
     self.num_scenarios = int(num_scenarios) if wind == 'scenarios' else 0
     self.risk_tail = self.num_scenarios if risk_tail is None else int(risk_tail)
     if wind == 'scenarios' and not (1 <= self.num_scenarios <= _abi.SCENARIO_MAX and 1 <= self.risk_tail <= self.num_scenarios):
@@ -68,100 +69,56 @@ class VecLookaheadAgent:
                        f'not {num_scenarios}, {risk_tail}')
     if not 1 <= int(num_plans) <= _abi.PLAN_MAX_PLANS:
       raise ValueError(f'VecLookaheadAgent: 1 <= num_plans <= {_abi.PLAN_MAX_PLANS}, not {num_plans}')
-    if int(horizon) < 1 or int(action_repeat) < 1 or int(horizon) * int(action_repeat) > _abi.ROLLOUT_MAX_STEPS:
-      raise ValueError(f'VecLookaheadAgent: horizon >= 1, action_repeat >= 1 and horizon * action_repeat <= {_abi.ROLLOUT_MAX_STEPS}, '
+    if int(horizon) < 1 or int(horizon) * int(action_repeat) > _abi.ROLLOUT_MAX_STEPS:
+      raise ValueError(f'VecLookaheadAgent: horizon >= 1 and horizon * action_repeat <= {_abi.ROLLOUT_MAX_STEPS}, '
                        f'not {horizon} x {action_repeat}')
-    if int(segment) < 1 or not 1 <= int(iterations) <= _abi.PLAN_MAX_ITERATIONS or int(elite) < 1:
-      raise ValueError(f'VecLookaheadAgent: segment >= 1, 1 <= iterations <= {_abi.PLAN_MAX_ITERATIONS} and elite >= 1, '
-                       f'not {segment}, {iterations}, {elite}')
-    if not 0.0 <= float(gamma) <= 1.0:
-      raise ValueError(f'VecLookaheadAgent: gamma in [0, 1], not {gamma}')
+    if not 1 <= int(iterations) <= _abi.PLAN_MAX_ITERATIONS or int(elite) < 1:
+      raise ValueError(f'VecLookaheadAgent: 1 <= iterations <= {_abi.PLAN_MAX_ITERATIONS} and elite >= 1, not {iterations}, {elite}')
     if not 0 <= int(prior_strength) <= 65535:
       raise ValueError(f'VecLookaheadAgent: 0 <= prior_strength <= 65535, not {prior_strength}')
+    if leaf_value is not None and wind == 'scenarios':
+      raise ValueError("VecLookaheadAgent: leaf_value with wind='scenarios': a plan has M end states there; plan in the belief or the forecast")
     self.prior_strength, self.with_action_values = int(prior_strength), bool(action_values)
-    self.leaf_value, self._leaf_fn = leaf_value, None
-    if leaf_value is not None:
-      if wind == 'scenarios':
-        raise ValueError("VecLookaheadAgent: leaf_value with wind='scenarios': a plan has M end states there; plan in the belief or the forecast")
-      if hasattr(leaf_value, 'act_greedy'):
-        self._leaf_fn = leaf_value.act_greedy
-      elif getattr(leaf_value, 'deterministic', True) is False:
-        raise ValueError('VecLookaheadAgent: leaf_value is a sampling agent (deterministic=False): its step counter would move with every '
-                         'decision; give a deterministic one, or a trainer (act_greedy)')
-      elif hasattr(leaf_value, 'act'):
-        self._leaf_fn = leaf_value.act
-      else:
-        raise ValueError('VecLookaheadAgent: leaf_value needs act_greedy(obs, value=) or act(obs, value=)')
-    self.device = dev.require_gpu(device)
-    self.lib = _lib.lib()
-    self.num_plans, self.horizon, self.action_repeat, self.segment = int(num_plans), int(horizon), int(action_repeat), int(segment)
-    self.gamma, self.wind, self.iterations, self.seed, self.substeps = float(gamma), wind, int(iterations), int(seed), int(substeps)
+    self.leaf_value, self._leaf_fn = leaf_value, self._critic('leaf_value', leaf_value, '(obs, value=)')
+    super().__init__(wind, gamma, action_repeat, segment, device, substeps)
+    self.num_plans, self.horizon, self.iterations, self.seed = int(num_plans), int(horizon), int(iterations), int(seed)
     self.elite = min(int(elite), self.num_plans)
     self.segments = -(-self.horizon // self.segment)
-    self.sim: Optional[vec_state.VecSimulator] = None
-    self._seeds: Optional[torch.Tensor] = None
-    self._noise_seed: Union[None, int, Callable[[], int]] = None
 
   # ------------------------------------------------------------------ attach a simulator
-  @dev.on_own_device
   def bind(self, sim: vec_state.VecSimulator, seeds: Optional[torch.Tensor] = None, noise_seed=None) -> 'VecLookaheadAgent':
-    """Attaches the simulator whose environments this agent flies and starts a new run of decisions (counter 0, previous best plan all
-    STAY).  All buffers are allocated here, once: binding the same simulator (and the same `seeds` tensor) again only restarts the
-    run, so a captured graph stays valid.
-    seeds: int64 / uint64 device tensor [N], a seed per environment (read at every decision): the plans of an environment then do
-    not depend on its batch.  noise_seed: the seed of the environments' wind noise, or a callable returning it, for wind='truth'
-    (None there: the truth is the forecast)."""
-    if sim.has_fleet:
-      raise ValueError('VecLookaheadAgent: a fleet (set_fleet) has no look-ahead kernel; fly one vehicle per batch (set_vehicle)')
-    if sim.device != self.device:
-      raise ValueError(f'VecLookaheadAgent on {self.device} cannot plan for a simulator on {sim.device}')
-    if seeds is not None:
-      if self.wind == 'truth':
-        raise ValueError("VecLookaheadAgent: wind='truth' with per-environment seeds: the look-ahead's noise generator takes one seed")
-      assert seeds.dtype in (torch.int64, torch.uint64) and seeds.is_contiguous() and tuple(seeds.shape) == (sim.n,), seeds.shape
-      assert seeds.device == self.device
+    """VecPlanner.bind, and a new run of decisions (counter 0, previous best plan all STAY): binding the same simulator and the same
+    `seeds` tensor again only restarts the run.  With seeds, the plans of an environment do not depend on its batch."""
     if sim.n * self.num_plans * max(self.num_scenarios, 1) >= 2 ** 31:
       raise ValueError(f'VecLookaheadAgent: n * num_plans * num_scenarios < 2^31, not {sim.n} x {self.num_plans} x {max(self.num_scenarios, 1)}')
-    same = self.sim is sim and self._seeds is seeds
-    self.sim, self._seeds, self._noise_seed = sim, seeds, noise_seed
-    if not same:
-      n, k, h = sim.n, self.num_plans, self.horizon
-      z = lambda dtype, *shape: torch.zeros(*shape, dtype=dtype, device=self.device)
-      self.counter = z(torch.int64, 1)                       # the decision counter: device memory, advanced by the last selection
-      self.plans = z(torch.uint8, h, n, k)
-      self.returns, self.steps_flown = z(torch.float32, n, k), z(torch.int32, n, k)
-      self.best_return, self.best_k = z(torch.float32, n), z(torch.int32, n)
-      self.best_plan = z(torch.uint8, h, n)
-      self.elite_counts = z(torch.int16, n, self.segments, 3)
-      self.action = z(torch.uint8, n)
-      self.prior_counts = z(torch.int16, n, self.segments, 3) if self.prior_strength > 0 else None
-      self.q, self.q_k, self.visits = ((z(torch.float32, n, 3), z(torch.int32, n, 3), z(torch.int32, n, 3)) if self.with_action_values
-                                       else (None, None, None))
-      self._belief = None
-      if self.wind == 'belief':
-        self._belief = vec_state.WindBelief(z(torch.float64, n, _lib.GP_BELIEF_DOUBLES), z(torch.int32, n))
-      self._scenarios = None
-      if self.wind == 'scenarios':
-        m = self.num_scenarios
-        self._scenarios = vec_state.WindScenarios(z(torch.float64, n, _abi.gp_scenario_doubles(m)), z(torch.int32, n), m, self.seed, seeds)
-        self.scenario_returns, self.scenario_steps = z(torch.float32, n, k, m), z(torch.int32, n, k, m)
-      self.leaves = None
-      if self._leaf_fn is not None:
-        self.leaves = sim.leaf_arena(k)
-        self.leaf_obs = torch.empty(n * k, _lib.OBS_DIM, dtype=torch.float32, device=self.device)
-        self.leaf_values, self.leaf_actions = z(torch.float32, n * k), z(torch.uint8, n * k)
-        self.leaf_obs.zero_()
-        self._leaf_fn(self.leaf_obs, out=self.leaf_actions, value=self.leaf_values)      # the first call at this row count: not in a capture
+    super().bind(sim, seeds, noise_seed)
     self.counter.zero_()
     self.best_plan.fill_(STAY)
     self.best_return.zero_()
     self.best_k.fill_(-1)
     return self
 
-  def _bound(self) -> vec_state.VecSimulator:
-    if self.sim is None:
-      raise ValueError('VecLookaheadAgent.act before bind(sim): the agent plans in a simulator (VecBalloonEnv.planner() binds one)')
-    return self.sim
+  def _allocate(self, sim: vec_state.VecSimulator) -> None:
+    n, k, h = sim.n, self.num_plans, self.horizon
+    z = lambda dtype, *shape: torch.zeros(*shape, dtype=dtype, device=self.device)
+    self.counter = z(torch.int64, 1)                       # the decision counter: device memory, advanced by the last selection
+    self.plans = z(torch.uint8, h, n, k)
+    self.returns, self.steps_flown = z(torch.float32, n, k), z(torch.int32, n, k)
+    self.best_return, self.best_k = z(torch.float32, n), z(torch.int32, n)
+    self.best_plan = z(torch.uint8, h, n)
+    self.elite_counts = z(torch.int16, n, self.segments, 3)
+    self.action = z(torch.uint8, n)
+    self.prior_counts = z(torch.int16, n, self.segments, 3) if self.prior_strength > 0 else None
+    self.q, self.q_k, self.visits = ((z(torch.float32, n, 3), z(torch.int32, n, 3), z(torch.int32, n, 3)) if self.with_action_values
+                                     else (None, None, None))
+    self._allocate_wind()
+    if self.wind == 'scenarios':
+      m = self.num_scenarios
+      self.scenario_returns, self.scenario_steps = z(torch.float32, n, k, m), z(torch.int32, n, k, m)
+    self.leaves = None
+    if self._leaf_fn is not None:
+      self.leaves = sim.leaf_arena(k)
+      self._allocate_leaf_rows(n * k)
 
   # ------------------------------------------------------------------ one decision
   @dev.on_own_device
@@ -173,13 +130,9 @@ class VecLookaheadAgent:
     by iteration 0 of an agent built with prior_strength > 0, ignored otherwise.  Nothing of the simulator is written; flags of the
     imagined flights go to sim.rollout_flags.  Asynchronous, capturable in a HIP graph."""
     del obs
-    sim = self._bound()
-    if sim.has_fleet:
-      raise ValueError('VecLookaheadAgent: the bound simulator flies a fleet now; a fleet has no look-ahead kernel')
+    sim = self._flying()
     n = sim.n
-    if out is None:
-      out = self.action
-    assert out.dtype == torch.uint8 and out.is_contiguous() and out.numel() == n and out.device == self.device
+    out = self.action if out is None else self._checked_out(out)
     stream = dev.stream_ptr(self.device)
     with_prior = self.prior_strength > 0 and prior_probs is not None
     if with_prior:
@@ -187,14 +140,9 @@ class VecLookaheadAgent:
       assert prior_probs.device == self.device
       pr = _abi.BlePlanPrior(n, self.segments, self.prior_strength, prior_probs.data_ptr(), self.prior_counts.data_ptr())
       _lib.check(self.lib.ble_plan_prior_u16(ctypes.byref(pr), stream), 'ble_plan_prior_u16')
-    belief, noise_seed, scenarios = None, None, None
-    if self.wind == 'belief':
-      belief = sim.fit_wind_belief(out=self._belief)
-    elif self.wind == 'scenarios':
-      scenarios = sim.fit_wind_scenarios(self.num_scenarios, seed=self.seed, seeds=self._seeds, out=self._scenarios)
-    elif self.wind == 'truth':
-      noise_seed = self._noise_seed() if callable(self._noise_seed) else self._noise_seed
-    rollout_out = (self.returns, self.steps_flown, None, None)
+    wind = self._wind()
+    in_scenarios = self.wind == 'scenarios'
+    rollout_out = (self.scenario_returns, self.scenario_steps, None, None) if in_scenarios else (self.returns, self.steps_flown, None, None)
     for it in range(self.iterations):
       last = it + 1 == self.iterations
       ps = _abi.BlePlanSample(n, self.num_plans, self.horizon, self.segment, it, self.seed & (2 ** 64 - 1), dev.ptr(self._seeds),
@@ -205,19 +153,11 @@ class VecLookaheadAgent:
         _lib.check(self.lib.ble_plan_sample_prior_u8(ctypes.byref(pp), stream), 'ble_plan_sample_prior_u8')
       else:
         _lib.check(self.lib.ble_plan_sample_u8(ctypes.byref(ps), stream), 'ble_plan_sample_u8')
-      if scenarios is not None:      # every plan in every scenario wind, then one score per plan: the selection below runs on the scores
-        sim.rollout_plans(self.plans, self.gamma, self.action_repeat, None, self.substeps,
-                          out=(self.scenario_returns, self.scenario_steps, None, None), scenarios=scenarios)
+      sim.rollout_plans(self.plans, self.gamma, self.action_repeat, substeps=self.substeps, out=rollout_out, leaves=self.leaves, **wind)
+      if in_scenarios:      # every plan was flown in every scenario wind; one score per plan: the selection below runs on the scores
         sim.plan_risk(self.scenario_returns, self.risk_tail, out=self.returns)
-      else:
-        sim.rollout_plans(self.plans, self.gamma, self.action_repeat, noise_seed, self.substeps, out=rollout_out, belief=belief,
-                          leaves=self.leaves)
-      if self.leaves is not None:    # score = return + gamma^steps_flown * V(leaf), in place: everything below reads the scores
-        sim.observe_leaves(self.leaves, out=self.leaf_obs)
-        self._leaf_fn(self.leaf_obs, out=self.leaf_actions, value=self.leaf_values)
-        bs = _abi.BlePlanBootstrap(n, self.num_plans, 0, self.gamma, self.returns.data_ptr(), self.steps_flown.data_ptr(),
-                                   self.leaves.state['status'].data_ptr(), self.leaf_values.data_ptr(), self.returns.data_ptr())
-        _lib.check(self.lib.ble_plan_bootstrap_f32(ctypes.byref(bs), stream), 'ble_plan_bootstrap_f32')
+      if self.leaves is not None:    # in place: everything below reads the scores
+        self._leaf_score(self.leaves, self.returns, self.steps_flown, self.returns)
       # (the elite counts are the next iteration's: the last selection writes none, and moves the decision counter on)
       sel = _abi.BlePlanSelect(n, self.num_plans, self.horizon, self.segment, it, 0 if last else self.elite, 0, self.returns.data_ptr(),
                                self.plans.data_ptr(), self.best_return.data_ptr(), self.best_k.data_ptr(), self.best_plan.data_ptr(),
@@ -229,23 +169,6 @@ class VecLookaheadAgent:
         _lib.check(self.lib.ble_plan_action_values_f32(ctypes.byref(av), stream), 'ble_plan_action_values_f32')
     return out
 
-  __call__ = act
-
-  def plan(self) -> Tuple[torch.Tensor, torch.Tensor]:
-    """(best_plan uint8 [H, N], best_return float32 [N]) of the last decision: the agent's own buffers, overwritten by the next one."""
-    self._bound()
-    return self.best_plan, self.best_return
-
-  def action_values(self) -> Tuple[torch.Tensor, torch.Tensor]:
-    """(q float32 [N, 3], visits int32 [N, 3]) of the last decision, for an agent built with action_values=True: q[e, a] the best
-    return (or risk score) among the plans of the decision that begin with action a, -Inf when none with a finite return does;
-    visits[e, a] how many plans began with a.  q[e, action[e]] is best_return[e].  The agent's own buffers, overwritten by the next
-    decision."""
-    self._bound()
-    if not self.with_action_values:
-      raise ValueError('VecLookaheadAgent.action_values: build the agent with action_values=True')
-    return self.q, self.visits
-
   def state_dict(self) -> dict:
     """What a run of decisions carries from one to the next: the decision counter and the best plan (the warm start)."""
     self._bound()
@@ -255,10 +178,3 @@ class VecLookaheadAgent:
     self._bound()
     self.counter.copy_(d['counter'])
     self.best_plan.copy_(d['best_plan'])
-
-  def check_errors(self) -> None:
-    """The agent latches no error of its own: its kernels cannot fail on valid buffers, and the flags of the flights it imagines stay
-    in sim.rollout_flags (a plan that leaves the valid range is no error of the flight that really happens)."""
-
-  def get_name(self) -> str:
-    return 'LookaheadAgent'

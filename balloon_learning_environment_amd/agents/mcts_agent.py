@@ -10,7 +10,7 @@ Without a guide the search needs no trained weights (V = 0, uniform priors: the 
 iteration's learner steers its own expert.  `bind` attaches the simulator (`VecBalloonEnv.planner(search='mcts', num_rounds=, leaves_per_round=, max_depth=)` returns a bound
 agent).
 """
-from typing import Callable, Optional, Tuple, Union
+from typing import Optional, Tuple
 
 import torch
 
@@ -18,11 +18,12 @@ from balloon_learning_environment_amd import _abi
 from balloon_learning_environment_amd import _lib
 from balloon_learning_environment_amd import device as dev
 from balloon_learning_environment_amd import vec_state
+from balloon_learning_environment_amd.agents import planner
 
 WINDS = ('belief', 'forecast', 'truth')
 
 
-class VecMCTSAgent:
+class VecMCTSAgent(planner.VecPlanner):
   """Guided tree search for N environments at once: act(obs) -> uint8 [N] device actions.
 
   num_rounds R rounds of leaves_per_round L descents (L * R <= 256): at most 3 L R edges flown per environment and decision, each one
@@ -35,84 +36,40 @@ class VecMCTSAgent:
   guide: an actor-critic -- an object with act_greedy(obs, out=, value=, probs=) or else act(obs, out=, value=, probs=), a sampling agent
   refused (VecBeamSearchAgent's rule) -- whose value of every new node enters its G = return + gamma^steps * V(node) (a node that ended
   in a terminal keeps its return) and whose probabilities are the node's prior over its children; on act's own observation they are the
-  root's prior unless act is given prior_probs.  None: no observation and no forward at all."""
+  root's prior unless act is given prior_probs.  None: no observation and no forward at all.
+  plan() is the principal variation -- the most visited child followed down, padded with STAY -- and the mean value of its first node."""
+
+  WINDS, PLANNER = WINDS, "planner(search='mcts')"
 
   def __init__(self, num_rounds: int, leaves_per_round: int, max_depth: int, segment: int = 4, action_repeat: int = 1,
                gamma: float = 0.993, c_puct: float = 1.25, wind: str = 'belief', guide=None, device='cuda:0',
                substeps: int = vec_state.SUBSTEPS):
-    if wind == 'scenarios':
-      raise ValueError("VecMCTSAgent: wind='scenarios' is VecScenarioBeamSearchAgent's tree (M end states per node); here plan in "
-                       "the belief, the forecast or the truth")
-    if wind not in WINDS:
-      raise ValueError(f"VecMCTSAgent: wind is 'belief', 'forecast' or 'truth', not {wind!r}")
     if int(num_rounds) < 1 or int(leaves_per_round) < 1 or int(num_rounds) * int(leaves_per_round) > _abi.MCTS_MAX_LEAVES:
       raise ValueError(f'VecMCTSAgent: num_rounds >= 1, leaves_per_round >= 1 and their product <= {_abi.MCTS_MAX_LEAVES}, '
                        f'not {num_rounds} x {leaves_per_round}')
-    if (int(max_depth) < 1 or int(segment) < 1 or int(action_repeat) < 1 or
-        int(max_depth) * int(segment) * int(action_repeat) > _abi.ROLLOUT_MAX_STEPS):
-      raise ValueError(f'VecMCTSAgent: max_depth, segment, action_repeat >= 1 and max_depth * segment * action_repeat <= '
-                       f'{_abi.ROLLOUT_MAX_STEPS}, not {max_depth} x {segment} x {action_repeat}')
-    if not 0.0 <= float(gamma) <= 1.0:
-      raise ValueError(f'VecMCTSAgent: gamma in [0, 1], not {gamma}')
+    if int(max_depth) < 1 or int(max_depth) * int(segment) * int(action_repeat) > _abi.ROLLOUT_MAX_STEPS:
+      raise ValueError(f'VecMCTSAgent: max_depth >= 1 and max_depth * segment * action_repeat <= {_abi.ROLLOUT_MAX_STEPS}, '
+                       f'not {max_depth} x {segment} x {action_repeat}')
     if not 0.0 <= float(c_puct) < float('inf'):
       raise ValueError(f'VecMCTSAgent: c_puct finite and >= 0, not {c_puct}')
-    self.guide, self._guide_fn = guide, None
-    if guide is not None:
-      if hasattr(guide, 'act_greedy'):
-        self._guide_fn = guide.act_greedy
-      elif getattr(guide, 'deterministic', True) is False:
-        raise ValueError('VecMCTSAgent: guide is a sampling agent (deterministic=False): its step counter would move with every '
-                         'decision; give a deterministic one, or a trainer (act_greedy)')
-      elif hasattr(guide, 'act'):
-        self._guide_fn = guide.act
-      else:
-        raise ValueError('VecMCTSAgent: guide needs act_greedy(obs, out=, value=, probs=) or act(obs, out=, value=, probs=)')
-    self.device = dev.require_gpu(device)
-    self.lib = _lib.lib()
-    self.num_rounds, self.leaves_per_round, self.max_depth = int(num_rounds), int(leaves_per_round), int(max_depth)
-    self.segment, self.action_repeat = int(segment), int(action_repeat)
-    self.gamma, self.c_puct, self.wind, self.substeps = float(gamma), float(c_puct), wind, int(substeps)
+    self.guide, self._guide_fn = guide, self._critic('guide', guide, '(obs, out=, value=, probs=)')
+    super().__init__(wind, gamma, action_repeat, segment, device, substeps)
+    self.num_rounds, self.leaves_per_round, self.max_depth, self.c_puct = int(num_rounds), int(leaves_per_round), int(max_depth), float(c_puct)
     self.horizon = self.max_depth * self.segment
-    self.sim: Optional[vec_state.VecSimulator] = None
-    self._noise_seed: Union[None, int, Callable[[], int]] = None
 
-  # ------------------------------------------------------------------ attach a simulator
-  @dev.on_own_device
-  def bind(self, sim: vec_state.VecSimulator, seeds: Optional[torch.Tensor] = None, noise_seed=None) -> 'VecMCTSAgent':
-    """Attaches the simulator whose environments this agent flies.  All buffers are allocated here, once: binding the same simulator
-    again changes nothing, so a captured graph stays valid.  With a guide it is called once at each of its two row counts (n 3L: a
-    round's nodes; n: the root), as a graph capture needs.  seeds: accepted for the planners' common signature; the search draws nothing
-    -- except with wind='truth', which is refused with a seed per environment (the look-ahead's noise generator takes one seed).
-    noise_seed: the seed of the environments' wind noise, or a callable returning it, for wind='truth'."""
-    if sim.has_fleet:
-      raise ValueError('VecMCTSAgent: a fleet (set_fleet) has no look-ahead kernel; fly one vehicle per batch (set_vehicle)')
-    if sim.device != self.device:
-      raise ValueError(f'VecMCTSAgent on {self.device} cannot plan for a simulator on {sim.device}')
-    if seeds is not None and self.wind == 'truth':
-      raise ValueError("VecMCTSAgent: wind='truth' with per-environment seeds: the look-ahead's noise generator takes one seed")
-    same = self.sim is sim
-    self.sim, self._noise_seed = sim, noise_seed
-    if not same:
-      n = sim.n
-      self.buffers = sim.mcts_buffers(self.num_rounds, self.leaves_per_round, self.max_depth, self.segment, self._guide_fn is not None)
-      bf = self.buffers
-      self.action, self.best_plan, self.best_return, self.q, self.visits = bf.action, bf.best_plan, bf.best_return, bf.q, bf.root_visits
-      self._belief = None
-      if self.wind == 'belief':
-        self._belief = vec_state.WindBelief(torch.zeros(n, _lib.GP_BELIEF_DOUBLES, dtype=torch.float64, device=self.device),
-                                            torch.zeros(n, dtype=torch.int32, device=self.device))
-      self._root_probs = self._root_action = self._root_obs = None
-      if self._guide_fn is not None:
-        self._root_probs = torch.zeros(n, 3, dtype=torch.float32, device=self.device)
-        self._root_action = torch.zeros(n, dtype=torch.uint8, device=self.device)
-        self._guide_fn(bf.obs, out=bf.guide_action, value=bf.value, probs=bf.probs)      # the first calls at these row counts: not in a capture
-        self._guide_fn(torch.zeros(n, _lib.OBS_DIM, dtype=torch.float32, device=self.device), out=self._root_action, probs=self._root_probs)
-    return self
-
-  def _bound(self) -> vec_state.VecSimulator:
-    if self.sim is None:
-      raise ValueError("VecMCTSAgent.act before bind(sim): the agent plans in a simulator (VecBalloonEnv.planner(search='mcts') binds one)")
-    return self.sim
+  def _allocate(self, sim: vec_state.VecSimulator) -> None:
+    """With a guide it is called once at each of its two row counts (n 3L: a round's nodes; n: the root), as a graph capture needs."""
+    n = sim.n
+    self.buffers = sim.mcts_buffers(self.num_rounds, self.leaves_per_round, self.max_depth, self.segment, self._guide_fn is not None)
+    bf = self.buffers
+    self.action, self.best_plan, self.best_return, self.q, self.visits = bf.action, bf.best_plan, bf.best_return, bf.q, bf.root_visits
+    self._allocate_wind()
+    self._root_probs = self._root_action = self._root_obs = None
+    if self._guide_fn is not None:
+      self._root_probs = torch.zeros(n, 3, dtype=torch.float32, device=self.device)
+      self._root_action = torch.zeros(n, dtype=torch.uint8, device=self.device)
+      self._guide_fn(bf.obs, out=bf.guide_action, value=bf.value, probs=bf.probs)      # the first calls at these row counts: not in a capture
+      self._guide_fn(torch.zeros(n, _lib.OBS_DIM, dtype=torch.float32, device=self.device), out=self._root_action, probs=self._root_probs)
 
   # ------------------------------------------------------------------ one decision
   @dev.on_own_device
@@ -122,34 +79,16 @@ class VecMCTSAgent:
     prior: prior_probs (float32 [N, 3]) if given; else the guide's probabilities on obs; else uniform.  out: optional uint8 [N] for the
     actions.  trace: mcts_search's (tests).  Nothing of the simulator is written; flags of the imagined flights go to sim.rollout_flags.
     Asynchronous, capturable in a HIP graph."""
-    sim = self._bound()
-    if sim.has_fleet:
-      raise ValueError('VecMCTSAgent: the bound simulator flies a fleet now; a fleet has no look-ahead kernel')
-    belief, noise_seed = None, None
-    if self.wind == 'belief':
-      belief = sim.fit_wind_belief(out=self._belief)
-    elif self.wind == 'truth':
-      noise_seed = self._noise_seed() if callable(self._noise_seed) else self._noise_seed
+    sim = self._flying()
+    wind = self._wind()
     root_prior = prior_probs
     if root_prior is None and self._guide_fn is not None and obs is not None:
       self._guide_fn(obs, out=self._root_action, probs=self._root_probs)
       root_prior = self._root_probs
     self.result = sim.mcts_search(self.num_rounds, self.leaves_per_round, self.max_depth, self.segment, self.action_repeat, self.gamma,
-                                  self.c_puct, noise_seed=noise_seed, belief=belief, substeps=self.substeps, guide_fn=self._guide_fn,
-                                  root_prior=root_prior, buffers=self.buffers, trace=trace)
-    if out is None:
-      return self.action
-    assert out.dtype == torch.uint8 and out.is_contiguous() and out.numel() == sim.n and out.device == self.device
-    out.view(-1).copy_(self.action)
-    return out
-
-  __call__ = act
-
-  def plan(self) -> Tuple[torch.Tensor, torch.Tensor]:
-    """(best_plan uint8 [max_depth * segment, N], best_return float32 [N]) of the last decision: the principal variation -- the most
-    visited child followed down, padded with STAY -- and the mean value of its first node.  The agent's own buffers."""
-    self._bound()
-    return self.best_plan, self.best_return
+                                  self.c_puct, substeps=self.substeps, guide_fn=self._guide_fn, root_prior=root_prior,
+                                  buffers=self.buffers, trace=trace, **wind)
+    return self._emit(out)
 
   def action_values(self) -> Tuple[torch.Tensor, torch.Tensor]:
     """(q float32 [N, 3], visits int32 [N, 3]) of the last decision: the mean value of the root's child under each action (-Inf: a void
@@ -162,17 +101,3 @@ class VecMCTSAgent:
     self._bound()
     visits = self.visits.to(torch.float32)
     return visits / visits.sum(1, keepdim=True).clamp_min(1.0)
-
-  def state_dict(self) -> dict:
-    """Nothing is carried from one decision to the next: every search starts at the state itself with an empty pool."""
-    self._bound()
-    return {}
-
-  def load_state_dict(self, d: dict) -> None:
-    self._bound()
-
-  def check_errors(self) -> None:
-    """The agent latches no error of its own: the flags of the flights it imagines stay in sim.rollout_flags."""
-
-  def get_name(self) -> str:
-    return 'MCTSAgent'

@@ -1030,10 +1030,17 @@ int with_noise(const ble_noise_gen* g, F&& f) {
   if (g == nullptr) return f(std::false_type{}, StepNoise{0ull, nullptr, nullptr, 0ll});
   return f(std::true_type{}, StepNoise{g->seed, g->episode, g->harmonic_cache, (long long)g->env_offset});
 }
+// ble_gp_history_f32 -> a GpHistory of the ring alone, for the calls that never read the carried factor (whatever its stride, it is none
+// of their business); false for a missing array
+inline bool gp_ring(const ble_gp_history_f32* hist, GpHistory* h) {
+  if (!hist || !hist->xyp || !hist->elapsed_s || !hist->err_uv || !hist->count) return false;
+  *h = GpHistory{hist->xyp, hist->elapsed_s, hist->err_uv, hist->count, nullptr, nullptr, 0};
+  return true;
+}
 // ble_gp_history_f32 -> the observation kernel's GpHistory; false for a missing array or a carried factor whose slab is too short or
 // misaligned (a slab shorter than the kernel's layout would be overrun, and overlap the next environment's)
 inline bool gp_history(const ble_gp_history_f32* hist, GpHistory* h) {
-  if (!hist || !hist->xyp || !hist->elapsed_s || !hist->err_uv || !hist->count) return false;
+  if (!gp_ring(hist, h)) return false;
   if (hist->chol != nullptr && (hist->n_chol == nullptr || hist->chol_stride < (int64_t)kCholStride || (hist->chol_stride & 1) != 0))
     return false;
   *h = GpHistory{hist->xyp, hist->elapsed_s, hist->err_uv, hist->count, hist->chol, hist->n_chol, hist->chol_stride};
@@ -1145,34 +1152,70 @@ inline RolloutArgs rollout_args(const struct ble_rollout_f32* ro) {
                      ro->grid_env_stride, ro->ret, ro->steps_flown, ro->reward, ro->final_state};
 }
 
-// ble_rollout_f32 and, with leaves (the leaf arena's StateDev as the one trailing argument), ble_rollout_leaves_f32 in the forecast or a
-// noise generator's wind
+// The wind a look-ahead call flies -- a noise generator's, a belief's, or with neither the forecast; never both -- checked and handed to f
+// as the kernels' wind tag (kTreeWindForecast / kTreeWindNoise / kTreeWindBelief), their BeliefDev and their StepNoise.  n: the call's batch
+template <class F>
+int with_wind(const ble_noise_gen* noise, const ble_gp_belief* belief, int64_t n, F&& f) {
+  if (noise != nullptr && belief != nullptr) return BLE_E_INVALID_ARG;                  // two winds
+  BeliefDev b{nullptr, 0, nullptr};
+  const StepNoise none{0ull, nullptr, nullptr, 0ll};
+  if (belief != nullptr) {
+    if (!gp_belief(belief, &b) || belief->n != n) return BLE_E_INVALID_ARG;             // (a belief of another batch would be read out of bounds)
+    return f(std::integral_constant<int, kTreeWindBelief>{}, b, none);
+  }
+  if (noise == nullptr) return f(std::integral_constant<int, kTreeWindForecast>{}, b, none);
+  if (noise->env_offset < 0) return BLE_E_INVALID_ARG;      // (a negative offset would key other streams than the reset did)
+  // (the harmonic cache is not handed on: the look-ahead kernels draw into LDS and fill no cache)
+  return f(std::integral_constant<int, kTreeWindNoise>{}, b, StepNoise{noise->seed, noise->episode, nullptr, (long long)noise->env_offset});
+}
+
+// ble_rollout_f32, ble_rollout_belief_f32 and, with leaves (the leaf arena's StateDev as the one trailing argument), ble_rollout_leaves_f32
 template <class... Leaf>
-int launch_rollout(const ble_state_f32* st, const struct ble_rollout_f32* ro, const ble_noise_gen* noise, uint32_t* err_flags, void* stream,
-                   const Leaf&... leaves) {
-  if (!rollout_ok(st, ro, 1) || (noise != nullptr && noise->env_offset < 0)) return BLE_E_INVALID_ARG;
-  return with_vehicle<false>(st, nullptr, [&](auto veh) {
-    if (ro->n == 0) return BLE_OK;
-    const RolloutArgs a = rollout_args(ro);
-    // (the harmonic cache of `noise` is not handed on for writing: ble_rollout_kernel draws into LDS and fills no cache)
-    return with_noise(noise, [&](auto noise_on, StepNoise gen) {
-      return launch(ble_rollout_kernel<decltype(noise_on)::value, decltype(veh), (sizeof...(Leaf) > 0), Leaf...>, ro->n * (int64_t)ro->n_plans,
-                    kStepBlock, kStepBlock, stream, state_dev(st), a, err_flags, gen, veh, leaves...);
+int launch_rollout(const ble_state_f32* st, const struct ble_rollout_f32* ro, const ble_noise_gen* noise, const ble_gp_belief* belief,
+                   uint32_t* err_flags, void* stream, const Leaf&... leaves) {
+  if (!rollout_ok(st, ro, 1)) return BLE_E_INVALID_ARG;
+  return with_wind(noise, belief, ro->n, [&](auto wind, BeliefDev b, StepNoise gen) {
+    return with_vehicle<false>(st, nullptr, [&](auto veh) {
+      if (ro->n == 0) return BLE_OK;
+      constexpr int kWind = decltype(wind)::value;
+      constexpr bool kLeaves = sizeof...(Leaf) > 0;
+      const int64_t lanes = ro->n * (int64_t)ro->n_plans;
+      if constexpr (kWind == kTreeWindBelief)
+        return launch(ble_rollout_belief_kernel<decltype(veh), kLeaves, Leaf...>, lanes, kStepBlock, kStepBlock, stream, state_dev(st),
+                      rollout_args(ro), b, err_flags, veh, leaves...);
+      else
+        return launch(ble_rollout_kernel<kWind == kTreeWindNoise, decltype(veh), kLeaves, Leaf...>, lanes, kStepBlock, kStepBlock, stream,
+                      state_dev(st), rollout_args(ro), err_flags, gen, veh, leaves...);
     });
   });
 }
-// ble_rollout_belief_f32 and, with leaves, ble_rollout_leaves_f32 in the belief's wind
-template <class... Leaf>
-int launch_rollout_belief(const ble_state_f32* st, const struct ble_rollout_f32* ro, const ble_gp_belief* belief, uint32_t* err_flags,
-                          void* stream, const Leaf&... leaves) {
-  BeliefDev b;
-  if (!rollout_ok(st, ro, 1) || !gp_belief(belief, &b) || belief->n != ro->n)      // (a belief of another batch would be read out of bounds)
-    return BLE_E_INVALID_ARG;
-  return with_vehicle<false>(st, nullptr, [&](auto veh) {
-    if (ro->n == 0) return BLE_OK;
-    return launch(ble_rollout_belief_kernel<decltype(veh), (sizeof...(Leaf) > 0), Leaf...>, ro->n * (int64_t)ro->n_plans, kStepBlock, kStepBlock,
-                  stream, state_dev(st), rollout_args(ro), b, err_flags, veh, leaves...);
-  });
+
+// the sizes ble_plan_sample_u8 and ble_plan_select_f32 share
+inline bool plan_sizes_ok(int64_t n, int n_plans, int n_plan_steps, int segment, int iteration) {
+  return n >= 0 && n < 2147483648LL && n_plans >= 1 && n_plans <= BLE_PLAN_MAX_PLANS && n_plan_steps >= 1 &&
+         n_plan_steps <= BLE_ROLLOUT_MAX_STEPS && segment >= 1 && iteration >= 0 && iteration < BLE_PLAN_MAX_ITERATIONS &&
+         n * (int64_t)n_plans < 2147483648LL;
+}
+
+// ble_plan_sample_u8 and ble_plan_sample_prior_u8: D is the descriptor, which with a prior carries its counts as well
+template <class D>
+int launch_plan_sample(const D* ps, void* stream) {
+  constexpr bool kPrior = std::is_same_v<D, struct ble_plan_sample_prior>;
+  if (!ps || !ps->plans || !ps->decision_counter || !ps->best_plan || (ps->iteration > 0 && !ps->elite_counts)) return BLE_E_INVALID_ARG;
+  if constexpr (kPrior)
+    if (!ps->prior_counts) return BLE_E_INVALID_ARG;
+  if (!plan_sizes_ok(ps->n, ps->n_plans, ps->n_plan_steps, ps->segment, ps->iteration) || ps->env_offset < 0) return BLE_E_INVALID_ARG;
+  const PlanSampleArgs a{ps->n, ps->env_offset, ps->n_plans, ps->n_plan_steps, ps->segment, ps->iteration, ps->decision_counter,
+                         ps->iteration > 0 ? ps->elite_counts : nullptr, ps->best_plan, ps->plans};
+  const int64_t lanes = ps->n * (int64_t)ps->n_plans;
+  const auto sample = [&](auto seed) {
+    if constexpr (kPrior)
+      return launch(ble_plan_sample_prior_kernel<decltype(seed)>, lanes, 256, 256, stream, a, ps->prior_counts, seed);
+    else
+      return launch(ble_plan_sample_kernel<decltype(seed)>, lanes, 256, 256, stream, a, seed);
+  };
+  if (ps->env_seed != nullptr) return sample(EnvSeed{ps->env_seed});
+  return sample(ScalarSeed{ps->seed});
 }
 
 }  // namespace
@@ -2252,29 +2295,28 @@ int ble_observe_forecast_fleet_f32(const ble_state_f32* st, const ble_fleet* fle
 
 int ble_gp_query_f32(const ble_gp_history_f32* hist, const uint8_t* reset_mask, const struct ble_gp_query_f32* query, uint32_t* err_flags,
                      void* stream) {
-  // (the ring alone is read: the carried factor, whatever its stride, is none of this call's business)
-  if (!hist || !query || !hist->xyp || !hist->elapsed_s || !hist->err_uv || !hist->count) return BLE_E_INVALID_ARG;
+  GpHistory h;
+  if (!gp_ring(hist, &h) || !query) return BLE_E_INVALID_ARG;
   if (!query->xyp || !query->time_s || !query->mean_uv || !query->deviation || query->n < 0 || query->q < 1 ||
       query->n * (int64_t)query->q >= 2147483648LL || query->n >= 2147483648LL)
     return BLE_E_INVALID_ARG;
   if (query->add_forecast != 0 && (!query->wind_grid || query->grid_env_stride < 0)) return BLE_E_INVALID_ARG;
-  const GpHistory h{hist->xyp, hist->elapsed_s, hist->err_uv, hist->count, nullptr, nullptr, 0};
   const GpQueryArgs a{query->n, query->q, query->add_forecast != 0 ? 1 : 0, query->xyp, query->time_s, query->wind_grid,
                       query->grid_env_stride, query->mean_uv, query->deviation};
   return launch(ble_gp_query_kernel, query->n, 1, kObsBlock, stream, h, reset_mask, a, err_flags);
 }
 
 int ble_rollout_f32(const ble_state_f32* st, const struct ble_rollout_f32* ro, const ble_noise_gen* noise, uint32_t* err_flags, void* stream) {
-  return launch_rollout(st, ro, noise, err_flags, stream);
+  return launch_rollout(st, ro, noise, nullptr, err_flags, stream);
 }
 
 int ble_gp_fit_f32(const ble_gp_history_f32* hist, const uint8_t* reset_mask, const int32_t* time_s, const ble_gp_belief* belief,
                    uint32_t* err_flags, void* stream) {
-  // (the ring alone is read, as by ble_gp_query_f32; the number of environments is the belief's)
+  // (the number of environments is the belief's)
+  GpHistory h;
   BeliefDev b;
-  if (!hist || !hist->xyp || !hist->elapsed_s || !hist->err_uv || !hist->count || !time_s || !gp_belief(belief, &b)) return BLE_E_INVALID_ARG;
+  if (!gp_ring(hist, &h) || !time_s || !gp_belief(belief, &b)) return BLE_E_INVALID_ARG;
   const int64_t n = belief->n;
-  const GpHistory h{hist->xyp, hist->elapsed_s, hist->err_uv, hist->count, nullptr, nullptr, 0};
   return launch(ble_gp_fit_kernel, n, 1, kObsBlock, stream, h, reset_mask, time_s, b, err_flags);
 }
 
@@ -2288,42 +2330,31 @@ int ble_gp_belief_wind_f32(const ble_gp_belief* belief, const float* x_m, const 
 
 int ble_rollout_belief_f32(const ble_state_f32* st, const struct ble_rollout_f32* ro, const ble_gp_belief* belief, uint32_t* err_flags,
                            void* stream) {
-  return launch_rollout_belief(st, ro, belief, err_flags, stream);
+  if (belief == nullptr) return BLE_E_INVALID_ARG;                                      // (no belief is no forecast here: ble_rollout_f32's)
+  return launch_rollout(st, ro, nullptr, belief, err_flags, stream);
 }
+
+namespace {
+// an array of `a` that is the same array of `b`
+inline bool state_arrays_shared(const ble_state_f32* a, const ble_state_f32* b) {
+  const void* const* pa = reinterpret_cast<const void* const*>(a);
+  const void* const* pb = reinterpret_cast<const void* const*>(b);
+  for (size_t k = 0; k < offsetof(ble_state_f32, episode_cache) / sizeof(void*); ++k)
+    if (pa[k] == pb[k]) return true;
+  return false;
+}
+}  // namespace
 
 // The look-ahead with its leaves handed back as full states: ble_rollout_f32 (noise, or neither wind) or
 // ble_rollout_belief_f32 (belief) with the leaf arena as the kernels' last argument.
 int ble_rollout_leaves_f32(const ble_state_f32* st, const struct ble_rollout_f32* ro, const ble_noise_gen* noise, const ble_gp_belief* belief,
                            const ble_state_f32* leaves, uint32_t* err_flags, void* stream) {
-  if (noise != nullptr && belief != nullptr) return BLE_E_INVALID_ARG;                  // two winds
   if (!state_ok(st) || !state_ok(leaves)) return BLE_E_INVALID_ARG;                     // (the leaves' vehicle and episode cache are not read)
-  {
-    const void* const* ps = reinterpret_cast<const void* const*>(st);
-    const void* const* pl = reinterpret_cast<const void* const*>(leaves);
-    for (size_t k = 0; k < offsetof(ble_state_f32, episode_cache) / sizeof(void*); ++k)
-      if (ps[k] == pl[k]) return BLE_E_INVALID_ARG;                                     // a leaf array that IS the source's: st is never written
-  }
-  const StateDev lf = state_dev(leaves);
-  if (belief != nullptr) return launch_rollout_belief(st, ro, belief, err_flags, stream, lf);
-  return launch_rollout(st, ro, noise, err_flags, stream, lf);
+  if (state_arrays_shared(leaves, st)) return BLE_E_INVALID_ARG;                        // a leaf array that IS the source's: st is never written
+  return launch_rollout(st, ro, noise, belief, err_flags, stream, state_dev(leaves));
 }
 
-// the sizes ble_plan_sample_u8 and ble_plan_select_f32 share
-inline bool plan_sizes_ok(int64_t n, int n_plans, int n_plan_steps, int segment, int iteration) {
-  return n >= 0 && n < 2147483648LL && n_plans >= 1 && n_plans <= BLE_PLAN_MAX_PLANS && n_plan_steps >= 1 &&
-         n_plan_steps <= BLE_ROLLOUT_MAX_STEPS && segment >= 1 && iteration >= 0 && iteration < BLE_PLAN_MAX_ITERATIONS &&
-         n * (int64_t)n_plans < 2147483648LL;
-}
-
-int ble_plan_sample_u8(const struct ble_plan_sample* ps, void* stream) {
-  if (!ps || !ps->plans || !ps->decision_counter || !ps->best_plan || (ps->iteration > 0 && !ps->elite_counts)) return BLE_E_INVALID_ARG;
-  if (!plan_sizes_ok(ps->n, ps->n_plans, ps->n_plan_steps, ps->segment, ps->iteration) || ps->env_offset < 0) return BLE_E_INVALID_ARG;
-  const PlanSampleArgs a{ps->n, ps->env_offset, ps->n_plans, ps->n_plan_steps, ps->segment, ps->iteration, ps->decision_counter,
-                         ps->iteration > 0 ? ps->elite_counts : nullptr, ps->best_plan, ps->plans};
-  const int64_t lanes = ps->n * (int64_t)ps->n_plans;
-  if (ps->env_seed != nullptr) return launch(ble_plan_sample_kernel<EnvSeed>, lanes, 256, 256, stream, a, EnvSeed{ps->env_seed});
-  return launch(ble_plan_sample_kernel<ScalarSeed>, lanes, 256, 256, stream, a, ScalarSeed{ps->seed});
-}
+int ble_plan_sample_u8(const struct ble_plan_sample* ps, void* stream) { return launch_plan_sample(ps, stream); }
 
 int ble_plan_select_f32(const struct ble_plan_select* sel, void* stream) {
   if (!sel || !sel->ret || !sel->plans || !sel->best_return || !sel->best_k || !sel->best_plan || !sel->action) return BLE_E_INVALID_ARG;
@@ -2344,17 +2375,7 @@ int ble_plan_prior_u16(const struct ble_plan_prior* pr, void* stream) {
   return launch(ble_plan_prior_kernel, total, 256, 256, stream, pr->probs, (int)pr->strength, (int)pr->segments, pr->prior_counts, total);
 }
 
-int ble_plan_sample_prior_u8(const struct ble_plan_sample_prior* ps, void* stream) {
-  if (!ps || !ps->plans || !ps->decision_counter || !ps->best_plan || (ps->iteration > 0 && !ps->elite_counts) || !ps->prior_counts)
-    return BLE_E_INVALID_ARG;
-  if (!plan_sizes_ok(ps->n, ps->n_plans, ps->n_plan_steps, ps->segment, ps->iteration) || ps->env_offset < 0) return BLE_E_INVALID_ARG;
-  const PlanSampleArgs a{ps->n, ps->env_offset, ps->n_plans, ps->n_plan_steps, ps->segment, ps->iteration, ps->decision_counter,
-                         ps->iteration > 0 ? ps->elite_counts : nullptr, ps->best_plan, ps->plans};
-  const int64_t lanes = ps->n * (int64_t)ps->n_plans;
-  if (ps->env_seed != nullptr)
-    return launch(ble_plan_sample_prior_kernel<EnvSeed>, lanes, 256, 256, stream, a, ps->prior_counts, EnvSeed{ps->env_seed});
-  return launch(ble_plan_sample_prior_kernel<ScalarSeed>, lanes, 256, 256, stream, a, ps->prior_counts, ScalarSeed{ps->seed});
-}
+int ble_plan_sample_prior_u8(const struct ble_plan_sample_prior* ps, void* stream) { return launch_plan_sample(ps, stream); }
 
 int ble_plan_action_values_f32(const struct ble_plan_action_values* av, void* stream) {
   if (!av || !av->ret || !av->first_action || !av->q || !av->q_k || !av->visits || av->n < 0 || av->n >= 2147483648LL || av->n_plans < 1 ||
@@ -2379,12 +2400,11 @@ int ble_plan_bootstrap_f32(const struct ble_plan_bootstrap* b, void* stream) {
 int ble_observe_leaves_f32(const ble_state_f32* leaves, int32_t leaves_per_env, const float* wind_grid, int64_t grid_env_stride,
                            const uint8_t* reset_mask, const ble_gp_history_f32* hist, float* obs, int64_t obs_row_stride, uint32_t* err_flags,
                            int64_t n_leaves, void* stream) {
-  if (!state_ok(leaves) || !wind_grid || !obs || !hist || !hist->xyp || !hist->elapsed_s || !hist->err_uv || !hist->count)
-    return BLE_E_INVALID_ARG;
+  GpHistory h;
+  if (!state_ok(leaves) || !wind_grid || !obs || !gp_ring(hist, &h)) return BLE_E_INVALID_ARG;
   if (leaves_per_env < 1 || n_leaves < 0 || n_leaves >= 2147483648LL || n_leaves % leaves_per_env != 0 || obs_row_stride < BLE_OBS_DIM ||
       grid_env_stride < 0)
     return BLE_E_INVALID_ARG;
-  const GpHistory h{hist->xyp, hist->elapsed_s, hist->err_uv, hist->count, nullptr, nullptr, 0};
   return with_vehicle<false>(leaves, nullptr, [&](auto veh) {
     return launch(ble_observe_kernel<decltype(veh), false, true>, n_leaves, 1, kObsBlock, stream, state_dev(leaves), wind_grid, grid_env_stride,
                   (const float*)nullptr, reset_mask, h, (int)leaves_per_env, obs, err_flags, obs_row_stride, veh, (const float*)nullptr);
@@ -2400,14 +2420,6 @@ inline bool tree_sizes_ok(int64_t n, int beam) {
   return n >= 0 && n < 2147483648LL && beam >= 1 && beam <= BLE_TREE_MAX_BEAM && n * (int64_t)(3 * beam) < 2147483648LL;
 }
 inline bool tree_children_ok(int n_children, int beam) { return n_children >= 3 && n_children <= 3 * beam && n_children % 3 == 0; }
-// an array of `a` that is the same array of `b`
-inline bool state_arrays_shared(const ble_state_f32* a, const ble_state_f32* b) {
-  const void* const* pa = reinterpret_cast<const void* const*>(a);
-  const void* const* pb = reinterpret_cast<const void* const*>(b);
-  for (size_t k = 0; k < offsetof(ble_state_f32, episode_cache) / sizeof(void*); ++k)
-    if (pa[k] == pb[k]) return true;
-  return false;
-}
 static_assert(kTreeMaxBeam == BLE_TREE_MAX_BEAM && kTreeMaxDepth == BLE_ROLLOUT_MAX_STEPS, "ble_tree.h and ble_abi.h disagree");
 
 // what both expand calls refuse of st and ex; nodes_per_child: 1, or the scenarios of a group
@@ -2429,6 +2441,11 @@ inline bool tree_expand_ok(const ble_state_f32* st, const struct ble_tree_expand
   return !(state_arrays_shared(ex->dst.state, ex->src.state) || ex->dst.acc == ex->src.acc || ex->dst.disc == ex->src.disc ||
            ex->dst.flown == ex->src.flown);                                             // a level is not expanded in place
 }
+// the arena an expand reads its parents from: ex->src, or on level 1 st's own environments (src.acc == NULL tells the kernel)
+inline TreeArenaDev tree_source_dev(const ble_state_f32* st, const struct ble_tree_expand* ex) {
+  if (ex->parent_children == 0) return TreeArenaDev{state_dev(st), nullptr, nullptr, nullptr, nullptr};
+  return tree_arena_dev(ex->src);
+}
 // struct ble_tree_expand as the expand kernels take it
 inline TreeExpandArgs tree_expand_args(const struct ble_tree_expand* ex) {
   return TreeExpandArgs{ex->n, ex->n_parents, ex->parent_children, ex->beam, ex->segment * ex->action_repeat, ex->substeps, ex->gamma,
@@ -2438,27 +2455,13 @@ inline TreeExpandArgs tree_expand_args(const struct ble_tree_expand* ex) {
 
 int ble_tree_expand_f32(const ble_state_f32* st, const struct ble_tree_expand* ex, const ble_noise_gen* noise, const ble_gp_belief* belief,
                         uint32_t* err_flags, void* stream) {
-  if (noise != nullptr && belief != nullptr) return BLE_E_INVALID_ARG;                  // two winds
-  if (!tree_expand_ok(st, ex, 1) || (noise != nullptr && noise->env_offset < 0)) return BLE_E_INVALID_ARG;
-  BeliefDev b{nullptr, 0, nullptr};
-  if (belief != nullptr && (!gp_belief(belief, &b) || belief->n != ex->n)) return BLE_E_INVALID_ARG;      // (a belief of another batch would be read out of bounds)
-  const bool first = ex->parent_children == 0;
-  return with_vehicle<false>(st, nullptr, [&](auto veh) {
-    if (ex->n == 0) return BLE_OK;
-    const TreeExpandArgs a = tree_expand_args(ex);
-    // level 1: the parents are st's environments (src.acc == NULL tells the kernel)
-    const TreeArenaDev src = first ? TreeArenaDev{state_dev(st), nullptr, nullptr, nullptr, nullptr} : tree_arena_dev(ex->src);
-    const TreeArenaDev dst = tree_arena_dev(ex->dst);
-    const int64_t lanes = ex->n * (int64_t)(3 * ex->n_parents);
-    const StepNoise none{0ull, nullptr, nullptr, 0ll};
-    if (belief != nullptr)
-      return launch(ble_tree_expand_kernel<kTreeWindBelief, decltype(veh)>, lanes, kStepBlock, kStepBlock, stream, state_dev(st), a, src, dst, b,
-                    none, err_flags, veh);
-    if (noise != nullptr)      // (the harmonic cache is not handed on: the kernel draws into LDS and fills no cache)
-      return launch(ble_tree_expand_kernel<kTreeWindNoise, decltype(veh)>, lanes, kStepBlock, kStepBlock, stream, state_dev(st), a, src, dst, b,
-                    StepNoise{noise->seed, noise->episode, nullptr, (long long)noise->env_offset}, err_flags, veh);
-    return launch(ble_tree_expand_kernel<kTreeWindForecast, decltype(veh)>, lanes, kStepBlock, kStepBlock, stream, state_dev(st), a, src, dst, b,
-                  none, err_flags, veh);
+  if (!tree_expand_ok(st, ex, 1)) return BLE_E_INVALID_ARG;
+  return with_wind(noise, belief, ex->n, [&](auto wind, BeliefDev b, StepNoise gen) {
+    return with_vehicle<false>(st, nullptr, [&](auto veh) {
+      if (ex->n == 0) return BLE_OK;
+      return launch(ble_tree_expand_kernel<decltype(wind)::value, decltype(veh)>, ex->n * (int64_t)(3 * ex->n_parents), kStepBlock, kStepBlock,
+                    stream, state_dev(st), tree_expand_args(ex), tree_source_dev(st, ex), tree_arena_dev(ex->dst), b, gen, err_flags, veh);
+    });
   });
 }
 
@@ -2467,16 +2470,12 @@ int ble_tree_expand_scenarios_f32(const ble_state_f32* st, const struct ble_tree
   ScenariosDev b;
   if (!gp_scenarios(scn, &b) || !scenario_gen_ok(gen) || !tree_expand_ok(st, ex, scn->num) || scn->n != ex->n)
     return BLE_E_INVALID_ARG;                                         // (scenarios of another batch would be read out of bounds)
-  const bool first = ex->parent_children == 0;
   return with_vehicle<false>(st, nullptr, [&](auto veh) {
     if (ex->n == 0) return BLE_OK;
-    const TreeExpandArgs a = tree_expand_args(ex);
-    // level 1: the parents are st's environments (src.acc == NULL tells the kernel)
-    const TreeArenaDev src = first ? TreeArenaDev{state_dev(st), nullptr, nullptr, nullptr, nullptr} : tree_arena_dev(ex->src);
-    const TreeArenaDev dst = tree_arena_dev(ex->dst);
     return with_scenario_seed(gen, [&](auto seed, ScenarioGen g) {
       return launch(ble_tree_expand_scenarios_kernel<decltype(veh), decltype(seed)>, ex->n * (int64_t)(3 * ex->n_parents) * scn->num, kStepBlock,
-                    kStepBlock, stream, state_dev(st), a, src, dst, b, seed, g, err_flags, veh);
+                    kStepBlock, stream, state_dev(st), tree_expand_args(ex), tree_source_dev(st, ex), tree_arena_dev(ex->dst), b, seed, g,
+                    err_flags, veh);
     });
   });
 }
@@ -2534,28 +2533,18 @@ int ble_mcts_select_f32(const struct ble_mcts_pool* pool, int32_t round, double 
 
 int ble_mcts_expand_f32(const ble_state_f32* st, const struct ble_mcts_pool* pool, const struct ble_mcts_expand* ex, const ble_noise_gen* noise,
                         const ble_gp_belief* belief, uint32_t* err_flags, void* stream) {
-  if (noise != nullptr && belief != nullptr) return BLE_E_INVALID_ARG;                  // two winds
   if (!state_ok(st) || !mcts_pool_ok(pool) || !ex || !ex->wind_grid || !mcts_round_ok(pool, ex->round) || ex->action_repeat < 1 ||
       (int64_t)pool->max_depth * pool->segment * ex->action_repeat > BLE_ROLLOUT_MAX_STEPS || ex->substeps < 1 ||
       ex->substeps > BLE_MAX_SUBSTEPS || ex->reserved_ != 0 || ex->grid_env_stride < 0 || !(ex->gamma >= 0.0 && ex->gamma <= 1.0) ||
-      (noise != nullptr && noise->env_offset < 0) || state_arrays_shared(pool->nodes.state, st))
+      state_arrays_shared(pool->nodes.state, st))
     return BLE_E_INVALID_ARG;
-  BeliefDev b{nullptr, 0, nullptr};
-  if (belief != nullptr && (!gp_belief(belief, &b) || belief->n != pool->n)) return BLE_E_INVALID_ARG;   // (a belief of another batch would be read out of bounds)
-  return with_vehicle<false>(st, nullptr, [&](auto veh) {
-    if (pool->n == 0) return BLE_OK;
-    const MctsExpandArgs a{pool->n, ex->round, pool->segment * ex->action_repeat, ex->substeps, ex->gamma, ex->wind_grid, ex->grid_env_stride};
-    const MctsPoolDev p = mcts_pool_dev(pool);
-    const int64_t lanes = pool->n * (int64_t)(3 * pool->leaves_per_round);
-    const StepNoise none{0ull, nullptr, nullptr, 0ll};
-    if (belief != nullptr)
-      return launch(ble_mcts_expand_kernel<kTreeWindBelief, decltype(veh)>, lanes, kStepBlock, kStepBlock, stream, state_dev(st), a, p, b, none,
-                    err_flags, veh);
-    if (noise != nullptr)      // (the harmonic cache is not handed on: the kernel draws into LDS and fills no cache)
-      return launch(ble_mcts_expand_kernel<kTreeWindNoise, decltype(veh)>, lanes, kStepBlock, kStepBlock, stream, state_dev(st), a, p, b,
-                    StepNoise{noise->seed, noise->episode, nullptr, (long long)noise->env_offset}, err_flags, veh);
-    return launch(ble_mcts_expand_kernel<kTreeWindForecast, decltype(veh)>, lanes, kStepBlock, kStepBlock, stream, state_dev(st), a, p, b, none,
-                  err_flags, veh);
+  return with_wind(noise, belief, pool->n, [&](auto wind, BeliefDev b, StepNoise gen) {
+    return with_vehicle<false>(st, nullptr, [&](auto veh) {
+      if (pool->n == 0) return BLE_OK;
+      const MctsExpandArgs a{pool->n, ex->round, pool->segment * ex->action_repeat, ex->substeps, ex->gamma, ex->wind_grid, ex->grid_env_stride};
+      return launch(ble_mcts_expand_kernel<decltype(wind)::value, decltype(veh)>, pool->n * (int64_t)(3 * pool->leaves_per_round), kStepBlock,
+                    kStepBlock, stream, state_dev(st), a, mcts_pool_dev(pool), b, gen, err_flags, veh);
+    });
   });
 }
 
@@ -2574,10 +2563,9 @@ int ble_mcts_finish_f32(const struct ble_mcts_pool* pool, const struct ble_mcts_
 
 int ble_gp_fit_scenarios_f32(const ble_gp_history_f32* hist, const uint8_t* reset_mask, const int32_t* time_s, const ble_gp_scenarios* scn,
                              const ble_scenario_gen* gen, uint32_t* err_flags, void* stream) {
+  GpHistory h;
   ScenariosDev b;
-  if (!hist || !hist->xyp || !hist->elapsed_s || !hist->err_uv || !hist->count || !time_s || !gp_scenarios(scn, &b) || !scenario_gen_ok(gen))
-    return BLE_E_INVALID_ARG;
-  const GpHistory h{hist->xyp, hist->elapsed_s, hist->err_uv, hist->count, nullptr, nullptr, 0};
+  if (!gp_ring(hist, &h) || !time_s || !gp_scenarios(scn, &b) || !scenario_gen_ok(gen)) return BLE_E_INVALID_ARG;
   return with_scenario_seed(gen, [&](auto seed, ScenarioGen g) {
     return launch(ble_gp_fit_scenarios_kernel<decltype(seed)>, scn->n, 1, kObsBlock, stream, h, reset_mask, time_s, b, seed, g, err_flags);
   });

@@ -846,6 +846,25 @@ class VecSimulator:
         _lib.check(code, fn.__name__)
     return launch
 
+  def _ready_for_lookahead(self, method: str, gamma: float) -> None:
+    """What rollout_plans, tree_search and mcts_search (`method`) need of the simulator and the discount before they fly anything."""
+    if self.has_fleet:
+      raise ValueError(f'{method}: a fleet (set_fleet) has no look-ahead kernel; fly one vehicle per batch (set_vehicle)')
+    assert self.grid is not None, f'Must call set_grid (reset) before {method}.'
+    if not 0.0 <= float(gamma) <= 1.0:
+      raise ValueError(f'{method}: gamma in [0, 1], not {gamma}')
+
+  def _lookahead_wind(self, method: str, noise_seed: Optional[int], belief: Optional[WindBelief], scenarios: Optional[WindScenarios] = None):
+    """The one wind of a look-ahead (`method`: its caller), refused if there are two or three: (the ble_noise_gen of noise_seed, the
+    ble_gp_belief of belief), each by reference as the library takes it, or None where that wind is not given."""
+    if belief is not None and noise_seed is not None:
+      raise ValueError(f'{method}: belief and noise_seed are two winds; give one of them')
+    if scenarios is not None and (belief is not None or noise_seed is not None):
+      raise ValueError(f'{method}: scenarios, belief and noise_seed are three winds; give one of them')
+    # (no harmonic cache: the kernel fills none, and wind_noise()'s stays byte for byte what it was)
+    gen = None if noise_seed is None else _abi.BleNoiseGen(int(noise_seed) & (2 ** 64 - 1), self.episode.data_ptr(), None, self.env_offset)
+    return None if gen is None else ctypes.byref(gen), None if belief is None else ctypes.byref(self._belief_struct(belief))
+
   @_on_own_device
   def rollout_plans(self, plans: torch.Tensor, gamma: float = 1.0, action_repeat: int = 1, noise_seed: Optional[int] = None,
                     substeps: int = SUBSTEPS, want_rewards: bool = False, want_final: bool = False, out: Optional[tuple] = None,
@@ -874,15 +893,10 @@ class VecSimulator:
     Error flags go to a word of their own, `rollout_flags` (int32 device tensor, OR-ed into, never cleared here), NOT to err_flags: a
     hypothetical plan that leaves the valid range must not make check_errors() raise for a flight that never happened.
     Asynchronous on the current stream, no host synchronisation (capturable in a HIP graph).  Not for fleets."""
-    if self.has_fleet:
-      raise ValueError('rollout_plans: a fleet (set_fleet) has no look-ahead kernel; fly one vehicle per batch (set_vehicle)')
-    if belief is not None and noise_seed is not None:
-      raise ValueError('rollout_plans: belief and noise_seed are two winds; give one of them')
-    if scenarios is not None and (belief is not None or noise_seed is not None):
-      raise ValueError('rollout_plans: scenarios, belief and noise_seed are three winds; give one of them')
+    self._ready_for_lookahead('rollout_plans', gamma)
+    gen, b = self._lookahead_wind('rollout_plans', noise_seed, belief, scenarios)
     if leaves is not None and scenarios is not None:
       raise ValueError('rollout_plans: scenario winds hand back no leaves (M end states per plan); fly the belief or the forecast')
-    assert self.grid is not None, 'Must call set_grid (reset) before rollout_plans.'
     assert plans.dtype == torch.uint8 and plans.is_contiguous() and plans.dim() == 3 and plans.shape[1] == self.n, plans.shape
     assert plans.device == self.device
     h, k = int(plans.shape[0]), int(plans.shape[2])
@@ -890,8 +904,6 @@ class VecSimulator:
     if h < 1 or k < 1 or action_repeat < 1 or steps > _abi.ROLLOUT_MAX_STEPS or self.n * k >= 2 ** 31:
       raise ValueError(f'rollout_plans: H >= 1, K >= 1, action_repeat >= 1, H * action_repeat <= {_abi.ROLLOUT_MAX_STEPS} and n * K < 2^31, '
                        f'not H = {h}, K = {k}, action_repeat = {action_repeat}, n = {self.n}')
-    if not 0.0 <= float(gamma) <= 1.0:
-      raise ValueError(f'rollout_plans: gamma in [0, 1], not {gamma}')
     lanes = (self.n, k) if scenarios is None else (self.n, k, int(scenarios.num))
     if scenarios is not None and self.n * k * int(scenarios.num) >= 2 ** 31:
       raise ValueError(f'rollout_plans: n * K * M < 2^31, not {self.n} x {k} x {scenarios.num}')
@@ -904,29 +916,24 @@ class VecSimulator:
                             (final, torch.float32, (4,) + lanes)):
       assert t is None or (t.dtype == dtype and t.is_contiguous() and tuple(t.shape) == shape and t.device == self.device), (shape, t)
     assert returns is not None and flown is not None
-    # (no harmonic cache: the kernel fills none, and wind_noise()'s stays byte for byte what it was)
-    gen = None if noise_seed is None else _abi.BleNoiseGen(int(noise_seed) & (2 ** 64 - 1), self.episode.data_ptr(), None, self.env_offset)
     ro = _abi.BleRolloutF32(self.n, k, h, int(action_repeat), int(substeps), float(gamma), plans.data_ptr(), self.grid.data_ptr(),
                             self.grid_env_stride, returns.data_ptr(), flown.data_ptr(), dev.ptr(rewards), dev.ptr(final))
     if leaves is not None:
       self._check_leaf_arena(leaves, k)
-      b = None if belief is None else self._belief_struct(belief)
-      _lib.check(self.lib.ble_rollout_leaves_f32(ctypes.byref(self._struct), ctypes.byref(ro), None if gen is None else ctypes.byref(gen),
-                                                 None if b is None else ctypes.byref(b), ctypes.byref(leaves._struct),
+      _lib.check(self.lib.ble_rollout_leaves_f32(ctypes.byref(self._struct), ctypes.byref(ro), gen, b, ctypes.byref(leaves._struct),
                                                  self.rollout_flags.data_ptr(), dev.stream_ptr(self.device)), 'ble_rollout_leaves_f32')
       return Rollout(returns, flown, rewards, final, leaves)
     if scenarios is not None:
-      b, sgen = self._scenario_structs(scenarios)
-      _lib.check(self.lib.ble_rollout_scenarios_f32(ctypes.byref(self._struct), ctypes.byref(ro), ctypes.byref(b), ctypes.byref(sgen),
+      scn, sgen = self._scenario_structs(scenarios)
+      _lib.check(self.lib.ble_rollout_scenarios_f32(ctypes.byref(self._struct), ctypes.byref(ro), ctypes.byref(scn), ctypes.byref(sgen),
                                                     self.rollout_flags.data_ptr(), dev.stream_ptr(self.device)), 'ble_rollout_scenarios_f32')
       return Rollout(returns, flown, rewards, final)
     if belief is not None:
-      b = self._belief_struct(belief)
-      _lib.check(self.lib.ble_rollout_belief_f32(ctypes.byref(self._struct), ctypes.byref(ro), ctypes.byref(b), self.rollout_flags.data_ptr(),
+      _lib.check(self.lib.ble_rollout_belief_f32(ctypes.byref(self._struct), ctypes.byref(ro), b, self.rollout_flags.data_ptr(),
                                                  dev.stream_ptr(self.device)), 'ble_rollout_belief_f32')
       return Rollout(returns, flown, rewards, final)
-    _lib.check(self.lib.ble_rollout_f32(ctypes.byref(self._struct), ctypes.byref(ro), None if gen is None else ctypes.byref(gen),
-                                        self.rollout_flags.data_ptr(), dev.stream_ptr(self.device)), 'ble_rollout_f32')
+    _lib.check(self.lib.ble_rollout_f32(ctypes.byref(self._struct), ctypes.byref(ro), gen, self.rollout_flags.data_ptr(),
+                                        dev.stream_ptr(self.device)), 'ble_rollout_f32')
     return Rollout(returns, flown, rewards, final)
 
   # ------------------------------------------------------------------ imagined states
@@ -1018,14 +1025,10 @@ class VecSimulator:
     STAY and -Inf.  The tensors are the buffers' own, overwritten by the next search.
     Nothing of the simulator is written; flags of the imagined flights go to rollout_flags, never err_flags.  Asynchronous on the
     current stream, no host synchronisation (capturable in a HIP graph).  Not for fleets."""
-    if self.has_fleet:
-      raise ValueError('tree_search: a fleet (set_fleet) has no look-ahead kernel; fly one vehicle per batch (set_vehicle)')
-    if belief is not None and noise_seed is not None:
-      raise ValueError('tree_search: belief and noise_seed are two winds; give one of them')
+    self._ready_for_lookahead('tree_search', gamma)
+    gen, b = self._lookahead_wind('tree_search', noise_seed, belief, scenarios)
     num = 0
     if scenarios is not None:
-      if belief is not None or noise_seed is not None:
-        raise ValueError('tree_search: scenarios, belief and noise_seed are three winds; give one of them')
       if leaf_score is not None:
         raise ValueError('tree_search: leaf_score with scenarios: a group has M end states (C * M observations per environment)')
       num = int(scenarios.num)
@@ -1034,13 +1037,10 @@ class VecSimulator:
         raise ValueError(f'tree_search: 1 <= M <= {_abi.SCENARIO_MAX} and 1 <= risk_tail <= M, not M = {num}, risk_tail = {risk_tail}')
     elif risk_tail is not None:
       raise ValueError('tree_search: risk_tail scores scenario winds; give scenarios')
-    assert self.grid is not None, 'Must call set_grid (reset) before tree_search.'
     depth, beam, segment, action_repeat = int(depth), int(beam_width), int(segment), int(action_repeat)
     if segment < 1 or action_repeat < 1 or depth < 1 or depth * segment * action_repeat > _abi.ROLLOUT_MAX_STEPS:
       raise ValueError(f'tree_search: depth, segment, action_repeat >= 1 and depth * segment * action_repeat <= {_abi.ROLLOUT_MAX_STEPS}, '
                        f'not {depth} x {segment} x {action_repeat}')
-    if not 0.0 <= float(gamma) <= 1.0:
-      raise ValueError(f'tree_search: gamma in [0, 1], not {gamma}')
     if buffers is None:
       buffers = self.tree_buffers(depth, beam, segment, action_values, num)
     if (buffers.sim is not self or buffers.depth != depth or buffers.beam != beam or buffers.segment != segment or
@@ -1051,36 +1051,44 @@ class VecSimulator:
     for arena in bf.arenas:
       if arena is not None:
         self._check_leaf_arena(arena, arena.leaves_per_env)
-    gen = None if noise_seed is None else _abi.BleNoiseGen(int(noise_seed) & (2 ** 64 - 1), self.episode.data_ptr(), None, self.env_offset)
-    b = None if belief is None else self._belief_struct(belief)
-    if scenarios is not None:
-      return self._tree_search_scenarios(bf, scenarios, tail, action_repeat, float(gamma), int(substeps), action_values, trace)
+    expand, wind = self.lib.ble_tree_expand_f32, (gen, b)
+    if num:
+      scn, sgen = self._scenario_structs(scenarios)
+      expand, wind = self.lib.ble_tree_expand_scenarios_f32, (ctypes.byref(scn), ctypes.byref(sgen))
+    group = (num,) if num else ()                  # the axis of a group's scenario nodes
     parents, children = 1, 0                       # P_{d-1}, C_{d-1}
     for level in range(1, depth + 1):
       dst, src = bf.node_struct(level), bf.node_struct(level - 1) if level > 1 else _abi.BleTreeArena()
       ex = _abi.BleTreeExpand(n, beam, depth, parents, children, segment, action_repeat, int(substeps), 0, float(gamma), self.grid.data_ptr(),
                               self.grid_env_stride, bf.parent.data_ptr(), src, dst)
-      _lib.check(self.lib.ble_tree_expand_f32(ctypes.byref(self._struct), ctypes.byref(ex), None if gen is None else ctypes.byref(gen),
-                                              None if b is None else ctypes.byref(b), self.rollout_flags.data_ptr(), stream), 'ble_tree_expand_f32')
+      _lib.check(expand(ctypes.byref(self._struct), ctypes.byref(ex), *wind, self.rollout_flags.data_ptr(), stream), expand.__name__)
       children = 3 * parents
-      sel = _abi.BleTreeSelect(n, children, beam, bf.ret[level & 1].data_ptr(), bf.parent.data_ptr(), bf.choice[level - 1].data_ptr())
+      key = ret = bf.ret[level & 1]                # what the select orders by: the returns, or the groups' risk scores
+      if num:
+        key = bf.score
+        risk = _abi.BlePlanRisk(n, children, num, tail, 0, ret.data_ptr(), key.data_ptr())          # ret [n][C][M] -> score [n][C]
+        _lib.check(self.lib.ble_plan_risk_f32(ctypes.byref(risk), stream), 'ble_plan_risk_f32')
+      sel = _abi.BleTreeSelect(n, children, beam, key.data_ptr(), bf.parent.data_ptr(), bf.choice[level - 1].data_ptr())
       _lib.check(self.lib.ble_tree_select_f32(ctypes.byref(sel), stream), 'ble_tree_select_f32')
       if trace is not None:
-        trace.append((level, bf.ret[level & 1][:n * children].view(n, children).clone(), bf.parent.clone()))
+        trace.append((level, key.view(-1)[:n * children].view(n, children).clone(), bf.parent.clone()) +
+                     ((ret[:n * children * num].view(n, children, num).clone(),) if num else ()))
       parents = min(children, beam)
     last = depth & 1
     leaves = bf.arenas[last]
-    returns, flown = bf.ret[last].view(n, children), bf.flown[last].view(n, children)
-    score = None
-    if leaf_score is not None:
+    returns, flown = bf.ret[last].view(n, children, *group), bf.flown[last].view(n, children, *group)
+    key, score = returns, None
+    if num:      # the finish on the scores alone: a group is void to it where its score is NaN
+      key = bf.score.view(-1)[:n * children].view(n, children)
+    elif leaf_score is not None:
       score = leaf_score(leaves, returns, flown)
       assert score.dtype == torch.float32 and score.is_contiguous() and tuple(score.shape) == (n, children) and score.device == self.device
-    fin = _abi.BleTreeFinish(n, children, beam, depth, segment, returns.data_ptr(), dev.ptr(score), self.state['status'].data_ptr(),
+    fin = _abi.BleTreeFinish(n, children, beam, depth, segment, key.data_ptr(), dev.ptr(score), self.state['status'].data_ptr(),
                              bf.choice.data_ptr(), bf.best_plan.data_ptr(), bf.action.data_ptr(), bf.best_return.data_ptr(),
                              dev.ptr(bf.q) if action_values else None, dev.ptr(bf.visits) if action_values else None)
     _lib.check(self.lib.ble_tree_finish_f32(ctypes.byref(fin), stream), 'ble_tree_finish_f32')
     return TreeSearch(bf.action, bf.best_plan, bf.best_return, bf.q if action_values else None, bf.visits if action_values else None, returns,
-                      flown, leaves, buffers=bf)
+                      flown, leaves, key if num else None, buffers=bf)
 
   # ------------------------------------------------------------------ guided tree search
   def mcts_buffers(self, num_rounds: int, leaves_per_round: int, max_depth: int, segment: int = 4, guide: bool = False) -> 'MCTSBuffers':
@@ -1112,17 +1120,12 @@ class VecSimulator:
     best_return 0, one whose root has no visited child all STAY and -Inf.  The tensors are the buffers' own, overwritten by the next search.
     Nothing of the simulator is written; flags of the imagined flights go to rollout_flags, never err_flags.  Asynchronous on the
     current stream, no host synchronisation (capturable in a HIP graph).  Not for fleets."""
-    if self.has_fleet:
-      raise ValueError('mcts_search: a fleet (set_fleet) has no look-ahead kernel; fly one vehicle per batch (set_vehicle)')
-    if belief is not None and noise_seed is not None:
-      raise ValueError('mcts_search: belief and noise_seed are two winds; give one of them')
-    assert self.grid is not None, 'Must call set_grid (reset) before mcts_search.'
+    self._ready_for_lookahead('mcts_search', gamma)
+    gen, b = self._lookahead_wind('mcts_search', noise_seed, belief)
     R, L, D, segment, action_repeat = int(num_rounds), int(leaves_per_round), int(max_depth), int(segment), int(action_repeat)
     if action_repeat < 1 or D * segment * action_repeat > _abi.ROLLOUT_MAX_STEPS:
       raise ValueError(f'mcts_search: action_repeat >= 1 and max_depth * segment * action_repeat <= {_abi.ROLLOUT_MAX_STEPS}, '
                        f'not {D} x {segment} x {action_repeat}')
-    if not 0.0 <= float(gamma) <= 1.0:
-      raise ValueError(f'mcts_search: gamma in [0, 1], not {gamma}')
     if not 0.0 <= float(c_puct) < float('inf'):
       raise ValueError(f'mcts_search: c_puct finite and >= 0, not {c_puct}')
     if buffers is None:
@@ -1138,14 +1141,11 @@ class VecSimulator:
               root_prior.device == self.device), root_prior.shape
     for arena in bf.arenas:
       self._check_leaf_arena(arena, 3 * L)
-    gen = None if noise_seed is None else _abi.BleNoiseGen(int(noise_seed) & (2 ** 64 - 1), self.episode.data_ptr(), None, self.env_offset)
-    b = None if belief is None else self._belief_struct(belief)
     pool, status = ctypes.byref(bf._struct), self.state['status'].data_ptr()
     for r in range(R):
       _lib.check(self.lib.ble_mcts_select_f32(pool, r, float(c_puct), status, dev.ptr(root_prior), stream), 'ble_mcts_select_f32')
       ex = _abi.BleMctsExpand(r, action_repeat, int(substeps), 0, float(gamma), self.grid.data_ptr(), self.grid_env_stride)
-      _lib.check(self.lib.ble_mcts_expand_f32(ctypes.byref(self._struct), pool, ctypes.byref(ex), None if gen is None else ctypes.byref(gen),
-                                              None if b is None else ctypes.byref(b), self.rollout_flags.data_ptr(), stream),
+      _lib.check(self.lib.ble_mcts_expand_f32(ctypes.byref(self._struct), pool, ctypes.byref(ex), gen, b, self.rollout_flags.data_ptr(), stream),
                  'ble_mcts_expand_f32')
       if guide_fn is not None:
         self.observe_leaves(bf.arenas[r], out=bf.obs)
@@ -1159,38 +1159,6 @@ class VecSimulator:
                              bf.root_visits.data_ptr(), bf.pv_length.data_ptr())
     _lib.check(self.lib.ble_mcts_finish_f32(pool, ctypes.byref(fin), stream), 'ble_mcts_finish_f32')
     return MCTSSearch(bf.action, bf.q, bf.root_visits, bf.best_return, bf.best_plan, bf.pv_length, bf)
-
-  def _tree_search_scenarios(self, bf: 'TreeBuffers', scenarios: WindScenarios, tail: int, action_repeat: int, gamma: float, substeps: int,
-                             action_values: bool, trace: Optional[list]) -> 'TreeSearch':
-    """tree_search in scenario winds, its arguments checked: depth x (expand, risk, select), then the finish on the last level's scores."""
-    n, num, depth, beam, stream = self.n, bf.num_scenarios, bf.depth, bf.beam, dev.stream_ptr(self.device)
-    scn, sgen = self._scenario_structs(scenarios)
-    parents, children = 1, 0                       # P_{d-1}, C_{d-1}
-    for level in range(1, depth + 1):
-      dst, src = bf.node_struct(level), bf.node_struct(level - 1) if level > 1 else _abi.BleTreeArena()
-      ex = _abi.BleTreeExpand(n, beam, depth, parents, children, bf.segment, action_repeat, substeps, 0, gamma, self.grid.data_ptr(),
-                              self.grid_env_stride, bf.parent.data_ptr(), src, dst)
-      _lib.check(self.lib.ble_tree_expand_scenarios_f32(ctypes.byref(self._struct), ctypes.byref(ex), ctypes.byref(scn), ctypes.byref(sgen),
-                                                        self.rollout_flags.data_ptr(), stream), 'ble_tree_expand_scenarios_f32')
-      children = 3 * parents
-      ret = bf.ret[level & 1]
-      risk = _abi.BlePlanRisk(n, children, num, tail, 0, ret.data_ptr(), bf.score.data_ptr())          # ret [n][C][M] -> score [n][C]
-      _lib.check(self.lib.ble_plan_risk_f32(ctypes.byref(risk), stream), 'ble_plan_risk_f32')
-      sel = _abi.BleTreeSelect(n, children, beam, bf.score.data_ptr(), bf.parent.data_ptr(), bf.choice[level - 1].data_ptr())
-      _lib.check(self.lib.ble_tree_select_f32(ctypes.byref(sel), stream), 'ble_tree_select_f32')
-      if trace is not None:
-        trace.append((level, bf.score.view(-1)[:n * children].view(n, children).clone(), bf.parent.clone(),
-                      ret[:n * children * num].view(n, children, num).clone()))
-      parents = min(children, beam)
-    last = depth & 1
-    score = bf.score.view(-1)[:n * children].view(n, children)
-    # the finish on the scores alone: a group is void to it where its score is NaN
-    fin = _abi.BleTreeFinish(n, children, beam, depth, bf.segment, score.data_ptr(), None, self.state['status'].data_ptr(),
-                             bf.choice.data_ptr(), bf.best_plan.data_ptr(), bf.action.data_ptr(), bf.best_return.data_ptr(),
-                             dev.ptr(bf.q) if action_values else None, dev.ptr(bf.visits) if action_values else None)
-    _lib.check(self.lib.ble_tree_finish_f32(ctypes.byref(fin), stream), 'ble_tree_finish_f32')
-    return TreeSearch(bf.action, bf.best_plan, bf.best_return, bf.q if action_values else None, bf.visits if action_values else None,
-                      bf.ret[last].view(n, children, num), bf.flown[last].view(n, children, num), bf.arenas[last], score, buffers=bf)
 
   @property
   def active_count(self) -> torch.Tensor:

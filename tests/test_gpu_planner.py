@@ -316,3 +316,58 @@ def test_refusals():
   first = agent.act(None).clone()
   agent.load_state_dict(saved)
   assert torch.equal(agent.act(None), first) and int(agent.counter.item()) == 2
+
+
+# ---------------------------------------------------------------------------------------------- what the four planners share
+SHELL_CASES = {
+    'sampler': dict(search='sample', num_plans=5, horizon=4, iterations=2),
+    'sampler in scenarios': dict(search='sample', num_plans=5, horizon=4, iterations=2, wind='scenarios', num_scenarios=2),
+    'beam': dict(search='beam', beam_width=2, depth=2),
+    'scenario beam': dict(search='beam', beam_width=2, depth=2, wind='scenarios', num_scenarios=2),
+    'guided search': dict(search='mcts', num_rounds=2, leaves_per_round=1, max_depth=2),
+}
+
+
+@pytest.mark.parametrize('case', list(SHELL_CASES))
+def test_the_planner_shell(case):
+  """What VecPlanner owns, held for every planner at a batch of 3 with one environment that is not OK: __call__ is act, out= is
+  returned and holds the same bytes, a second bind of the same simulator (and seeds) allocates nothing, wind='truth' refuses a seed
+  per environment, and the fleet refusal names the class."""
+  kw = dict(SHELL_CASES[case], segment=2, action_repeat=1)
+  n = 3
+  env = _env(n)
+  sim = env.arena.sim
+  sim.state['status'][1] = 2                                 # not OK: the frozen path
+  obs = sim.observe(append=False)
+  agent = env.planner(**kw)
+  cls = type(agent)
+  noise_seed = lambda: env.arena._seed
+  seeded = 'scenarios' in kw.get('wind', '') or kw['search'] == 'sample'       # the agents whose streams bind(seeds=) keys
+  seeds = torch.arange(n, dtype=torch.int64, device=DEVICE)
+  for s in (None, seeds):
+    rebind = lambda: agent.bind(sim, seeds=s, noise_seed=noise_seed)           # (the sampler's run restarts: counter 0 every time)
+    called = rebind()(obs).clone()
+    acted = rebind().act(obs).clone()
+    buf = torch.full((n,), 7, dtype=torch.uint8, device=DEVICE)
+    assert rebind().act(obs, out=buf) is buf
+    torch.cuda.synchronize()
+    print(case, 'seeds' if s is not None else 'no seeds', 'actions', called.cpu().numpy())
+    assert called.cpu().numpy().tobytes() == acted.cpu().numpy().tobytes() == buf.cpu().numpy().tobytes()
+    assert int(called[1]) == 1                               # STAY where nothing is flown
+    held = [agent.action] + [w.slab for w in (agent._belief, agent._scenarios) if w is not None]
+    assert len(held) == 2                                    # every case here fits a belief or scenarios
+    before = [t.data_ptr() for t in held]
+    rebind()
+    after = [agent.action] + [w.slab for w in (agent._belief, agent._scenarios) if w is not None]
+    assert [t.data_ptr() for t in after] == before and all(a is b for a, b in zip(after, held))
+  if not seeded:                                             # seeds that key nothing are no new binding either
+    agent.bind(sim, noise_seed=noise_seed)
+    assert agent.action.data_ptr() == before[0]
+  env.check_errors()
+  shape = {k: v for k, v in kw.items() if k not in ('search', 'wind', 'num_scenarios')}
+  if 'truth' in cls.WINDS:
+    with pytest.raises(ValueError, match='truth'):
+      cls(wind='truth', **shape).bind(sim, seeds=seeds)
+  fleet = balloon_env.VecBalloonEnv(n, seed=1, vehicles=[{}, {'envelope_mass': 75.0}], vehicle_index=[0, 1, 0], auto_reset=False)
+  with pytest.raises(ValueError, match=cls.__name__ + r': a fleet \(set_fleet\) has no look-ahead kernel'):
+    fleet.planner(**kw)
