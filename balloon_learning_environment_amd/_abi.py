@@ -201,7 +201,9 @@ MCTS_EMPTY, MCTS_EXPAND, MCTS_REVISIT = 0, 1, 2      # BLE_MCTS_EMPTY / EXPAND /
 
 class BleMctsPool(ctypes.Structure):
   """struct ble_mcts_pool: the node pool of a guided tree search: cap = 1 + 3 L R ids per environment, the nodes [R][n][3L] as a
-  ble_tree_arena, the statistics [n][cap], the round's slots [n][L] (device pointers)."""
+  ble_tree_arena, the statistics [n][cap], the round's slots [n][L] (device pointers).  In scenario winds (ble_mcts_expand_scenarios_f32,
+  ble_mcts_backup_scenarios_f32) a node id is a group of M scenario nodes: the nodes are [R][n][3L][M], the statistics stay per group, and
+  select and finish take a copy of the struct whose nodes.state->status is the groups' status [R][n][3L]."""
   _fields_ = [('n', ctypes.c_int64), ('num_rounds', ctypes.c_int32), ('leaves_per_round', ctypes.c_int32), ('max_depth', ctypes.c_int32),
               ('segment', ctypes.c_int32), ('reserved_', ctypes.c_int64), ('nodes', BleTreeArena), ('parent', ctypes.c_void_p),
               ('first_child', ctypes.c_void_p), ('depth', ctypes.c_void_p), ('visits', ctypes.c_void_p), ('pending', ctypes.c_void_p),

@@ -8,7 +8,7 @@ guide's prior -- to leaves_per_round leaves, flies their three children for one 
 no random stream and no seed.  No host synchronisation anywhere, so a decision is capturable in the same HIP graph as the step.
 Without a guide the search needs no trained weights (V = 0, uniform priors: the returns alone steer it); with guide=trainer an expert
 iteration's learner steers its own expert.  `bind` attaches the simulator (`VecBalloonEnv.planner(search='mcts', num_rounds=, leaves_per_round=, max_depth=)` returns a bound
-agent).
+agent).  VecScenarioMCTSAgent is the same search in sampled winds: a node is a group of M scenario nodes.
 """
 from typing import Optional, Tuple
 
@@ -32,7 +32,7 @@ class VecMCTSAgent(planner.VecPlanner):
   guide, 3 L R observations and forward rows per environment and decision).  gamma: the discount of a return.  c_puct >= 0: the
   weight of the exploration term (0: by value alone).
   wind: 'belief' (default) -- forecast + the mean of the WindGP over the balloon's own measurements, fitted at every decision;
-  'forecast'; 'truth' -- the wind the environments will fly (bind(noise_seed=)).  'scenarios' is refused: a node is one state.
+  'forecast'; 'truth' -- the wind the environments will fly (bind(noise_seed=)).  'scenarios' is refused: a node is one state (VecScenarioMCTSAgent's is a group).
   guide: an actor-critic -- an object with act_greedy(obs, out=, value=, probs=) or else act(obs, out=, value=, probs=), a sampling agent
   refused (VecBeamSearchAgent's rule) -- whose value of every new node enters its G = return + gamma^steps * V(node) (a node that ended
   in a terminal keeps its return) and whose probabilities are the node's prior over its children; on act's own observation they are the
@@ -40,6 +40,7 @@ class VecMCTSAgent(planner.VecPlanner):
   plan() is the principal variation -- the most visited child followed down, padded with STAY -- and the mean value of its first node."""
 
   WINDS, PLANNER = WINDS, "planner(search='mcts')"
+  num_scenarios, risk_tail = 0, None      # (VecScenarioMCTSAgent's)
 
   def __init__(self, num_rounds: int, leaves_per_round: int, max_depth: int, segment: int = 4, action_repeat: int = 1,
                gamma: float = 0.993, c_puct: float = 1.25, wind: str = 'belief', guide=None, device='cuda:0',
@@ -58,9 +59,11 @@ class VecMCTSAgent(planner.VecPlanner):
     self.horizon = self.max_depth * self.segment
 
   def _allocate(self, sim: vec_state.VecSimulator) -> None:
-    """With a guide it is called once at each of its two row counts (n 3L: a round's nodes; n: the root), as a graph capture needs."""
+    """With a guide it is called once at each of its two row counts (n 3L, in scenario winds n 3L M: a round's nodes; n: the root), as a
+    graph capture needs."""
     n = sim.n
-    self.buffers = sim.mcts_buffers(self.num_rounds, self.leaves_per_round, self.max_depth, self.segment, self._guide_fn is not None)
+    self.buffers = sim.mcts_buffers(self.num_rounds, self.leaves_per_round, self.max_depth, self.segment, self._guide_fn is not None,
+                                    self.num_scenarios)
     bf = self.buffers
     self.action, self.best_plan, self.best_return, self.q, self.visits = bf.action, bf.best_plan, bf.best_return, bf.q, bf.root_visits
     self._allocate_wind()
@@ -87,7 +90,7 @@ class VecMCTSAgent(planner.VecPlanner):
       root_prior = self._root_probs
     self.result = sim.mcts_search(self.num_rounds, self.leaves_per_round, self.max_depth, self.segment, self.action_repeat, self.gamma,
                                   self.c_puct, substeps=self.substeps, guide_fn=self._guide_fn, root_prior=root_prior,
-                                  buffers=self.buffers, trace=trace, **wind)
+                                  buffers=self.buffers, trace=trace, risk_tail=self.risk_tail, **wind)
     return self._emit(out)
 
   def action_values(self) -> Tuple[torch.Tensor, torch.Tensor]:
@@ -101,3 +104,43 @@ class VecMCTSAgent(planner.VecPlanner):
     self._bound()
     visits = self.visits.to(torch.float32)
     return visits / visits.sum(1, keepdim=True).clamp_min(1.0)
+
+
+class VecScenarioMCTSAgent(VecMCTSAgent):
+  """VecMCTSAgent in SAMPLED winds: a node of the pool is a GROUP of num_scenarios (<= 16) scenario nodes, every edge is
+  flown in each of that many winds drawn from the WindGP's posterior, fitted at every decision (`fit_wind_scenarios`; the
+  scenarios themselves are fixed over an episode, only the conditioning moves), and a group backs up ONE value: the mean of the
+  risk_tail smallest of its M values G_m = return_m + gamma^steps_m * V(node m) -- None = all of them, the expectation; 1 = the worst
+  case; between them a CVaR.  A scenario node that stopped is carried on unchanged under every action; a group whose nodes all stopped is
+  never expanded again.  With a guide every one of the M nodes of a group is observed and evaluated; the group's prior is the mean of
+  the probability rows of its nodes that are OK.  The scenario streams are keyed as VecScenarioBeamSearchAgent keys them: by `seed`, or
+  with bind(seeds=) by each environment's own seed -- an environment then plans the same in any batch.
+  num_rounds, leaves_per_round, max_depth and num_scenarios have no default: the budget of a search is the caller's decision.
+  Memory: the pool is 3 * leaves_per_round * num_rounds * num_scenarios nodes per environment (about 150 B each); with a guide, 3 *
+  leaves_per_round * num_scenarios observation rows of 4.4 KB per environment on top.  n * 3 * leaves_per_round * num_scenarios < 2^31.
+  act, plan, action_values and visit_probs: the parent's; q and best_return are means of group values, that is, risk scores.
+  bind(noise_seed=) is accepted for the planners' common signature and unused -- no scenario is the truth."""
+
+  WINDS, SEEDED = ('scenarios',), True
+
+  def __init__(self, num_rounds: int, leaves_per_round: int, max_depth: int, num_scenarios: int, risk_tail: Optional[int] = None,
+               seed: int = 0, segment: int = 4, action_repeat: int = 1, gamma: float = 0.993, c_puct: float = 1.25, guide=None,
+               device='cuda:0', substeps: int = vec_state.SUBSTEPS):
+    self.num_scenarios = int(num_scenarios)
+    self.risk_tail = self.num_scenarios if risk_tail is None else int(risk_tail)
+    if not (1 <= self.num_scenarios <= _abi.SCENARIO_MAX and 1 <= self.risk_tail <= self.num_scenarios):
+      raise ValueError(f'VecScenarioMCTSAgent: 1 <= num_scenarios <= {_abi.SCENARIO_MAX} and 1 <= risk_tail <= num_scenarios, '
+                       f'not {num_scenarios}, {risk_tail}')
+    super().__init__(num_rounds, leaves_per_round, max_depth, segment, action_repeat, gamma, c_puct, 'scenarios', guide, device, substeps)
+    self.seed = int(seed)
+
+  def state_dict(self) -> dict:
+    """Nothing moves from one decision to the next; a resume needs what keys the scenario streams and shapes the score."""
+    self._bound()
+    return {'seed': self.seed, 'num_scenarios': self.num_scenarios, 'risk_tail': self.risk_tail}
+
+  def load_state_dict(self, d: dict) -> None:
+    self._bound()
+    mine = self.state_dict()
+    if any(k in d and int(d[k]) != mine[k] for k in mine):
+      raise ValueError(f'VecScenarioMCTSAgent: a checkpoint of another agent ({ {k: d[k] for k in mine if k in d} }, this one {mine})')

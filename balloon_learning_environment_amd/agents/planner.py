@@ -1,5 +1,5 @@
-"""What the look-ahead planners share: VecLookaheadAgent, VecBeamSearchAgent, VecScenarioBeamSearchAgent and VecMCTSAgent
-derive from VecPlanner and differ in their search alone.  The shell owns the critic rule, the shared constructor checks, bind, the wind
+"""What the look-ahead planners share: VecLookaheadAgent, VecBeamSearchAgent, VecScenarioBeamSearchAgent, VecMCTSAgent and
+VecScenarioMCTSAgent derive from VecPlanner and differ in their search alone.  The shell owns the critic rule, the shared constructor checks, bind, the wind
 of a decision with its buffers, the leaf score and the small methods; a subclass checks its own sizes, allocates its own buffers
 (`_allocate`) and searches (`act`).
 """

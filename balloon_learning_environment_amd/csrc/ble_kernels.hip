@@ -833,6 +833,8 @@ __global__ __launch_bounds__(256) void ble_eval_accumulate_kernel(StateDev st, c
 #include "ble_tree_scenarios.h"
 // guided tree search: PUCT over a node pool; after ble_tree.h (the arenas) and ble_gp_belief.h
 #include "ble_mcts.h"
+// the guided tree search flown in the scenario winds: a node is a group of M scenario nodes; after ble_mcts.h and ble_tree_scenarios.h
+#include "ble_mcts_scenarios.h"
 // fp64 primitive probe (test-only entry point): op 0 rcp seed, 1 d_rcp, 2 rsq seed, 3 d_rsqrt,
 // 4 d_sqrt_fast, 5 d_log_fast, 6 d_exp_fast, 7 sin (sincos_f64), 8 cos (sincos_f64)
 __global__ __launch_bounds__(256) void probe_f64_kernel(const double* x, double* y, int op, int64_t n) {
@@ -2559,6 +2561,42 @@ int ble_mcts_finish_f32(const struct ble_mcts_pool* pool, const struct ble_mcts_
     return BLE_E_INVALID_ARG;
   const MctsFinishArgs a{fin->source_status, fin->best_plan, fin->action, fin->best_return, fin->q, fin->visits, fin->pv_length};
   return launch(ble_mcts_finish_kernel, pool->n, kMctsEnvsPerBlock, kMctsBlock, stream, mcts_pool_dev(pool), a);
+}
+
+// ---- guided tree search in scenario winds
+namespace {
+// what both scenario calls refuse of the pool and M: the pool's own checks, M, and the node count of a round's slice
+inline bool mcts_groups_ok(const struct ble_mcts_pool* p, int64_t num) {
+  return mcts_pool_ok(p) && num >= 1 && num <= BLE_SCENARIO_MAX && p->n * (int64_t)(3 * p->leaves_per_round) * num < 2147483648LL;
+}
+}  // namespace
+
+int ble_mcts_expand_scenarios_f32(const ble_state_f32* st, const struct ble_mcts_pool* pool, const struct ble_mcts_expand* ex,
+                                  const ble_gp_scenarios* scn, const ble_scenario_gen* gen, uint32_t* err_flags, void* stream) {
+  ScenariosDev b;
+  if (!gp_scenarios(scn, &b) || !scenario_gen_ok(gen) || !state_ok(st) || !mcts_groups_ok(pool, scn->num) || scn->n != pool->n || !ex ||
+      !ex->wind_grid || !mcts_round_ok(pool, ex->round) || ex->action_repeat < 1 ||
+      (int64_t)pool->max_depth * pool->segment * ex->action_repeat > BLE_ROLLOUT_MAX_STEPS || ex->substeps < 1 ||
+      ex->substeps > BLE_MAX_SUBSTEPS || ex->reserved_ != 0 || ex->grid_env_stride < 0 || !(ex->gamma >= 0.0 && ex->gamma <= 1.0) ||
+      state_arrays_shared(pool->nodes.state, st))
+    return BLE_E_INVALID_ARG;                                         // (scenarios of another batch would be read out of bounds)
+  return with_vehicle<false>(st, nullptr, [&](auto veh) {
+    if (pool->n == 0) return BLE_OK;
+    return with_scenario_seed(gen, [&](auto seed, ScenarioGen g) {
+      const MctsExpandArgs a{pool->n, ex->round, pool->segment * ex->action_repeat, ex->substeps, ex->gamma, ex->wind_grid, ex->grid_env_stride};
+      return launch(ble_mcts_expand_scenarios_kernel<decltype(veh), decltype(seed)>, pool->n * (int64_t)(3 * pool->leaves_per_round) * scn->num,
+                    kStepBlock, kStepBlock, stream, state_dev(st), a, mcts_pool_dev(pool), b, seed, g, err_flags, veh);
+    });
+  });
+}
+
+int ble_mcts_backup_scenarios_f32(const struct ble_mcts_pool* pool, int32_t round, int32_t num, int32_t tail, const float* value,
+                                  const float* probs, uint8_t* group_status, double* group_g, void* stream) {
+  if (!mcts_groups_ok(pool, num) || !mcts_round_ok(pool, round) || tail < 1 || tail > num || (value == nullptr) != (probs == nullptr) ||
+      !group_status || !group_g)
+    return BLE_E_INVALID_ARG;
+  return launch(ble_mcts_backup_scenarios_kernel, pool->n, kMctsEnvsPerBlock, kMctsBlock, stream, mcts_pool_dev(pool), (int)round, (int)num,
+                (int)tail, value, probs, group_status, group_g);
 }
 
 int ble_gp_fit_scenarios_f32(const ble_gp_history_f32* hist, const uint8_t* reset_mask, const int32_t* time_s, const ble_gp_scenarios* scn,

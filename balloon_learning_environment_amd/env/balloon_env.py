@@ -284,11 +284,22 @@ class VecBalloonEnv:
                   gamma: float = 0.993, c_puct: float = 1.25, wind: str = 'truth', **kw):
     """Guided tree search from where each balloon is now, nothing of the environments changed -> MCTSSearch(action, q,
     visits, best_return, best_plan, pv_length, pool) (VecSimulator.mcts_search; guide_fn=, root_prior=, buffers=, trace= go through).
-    wind: lookahead's 'truth', 'forecast' or 'belief' (fitted now); scenario winds have no node pool."""
+    wind: lookahead's 'truth', 'forecast' or 'belief' (fitted now), or 'scenarios' with num_scenarios=M (required: the budget of a
+    search is the caller's decision) and risk_tail (None: M): M winds sampled from the WindGP's posterior, fitted now from streams keyed
+    by this env's seed (arena.fit_wind_scenarios) into a kept WindScenarios; a node is a group of M scenario nodes, backed up by the mean
+    of the risk_tail smallest of its M values.  The pool is 3 L R M nodes per environment; with a guide, 3 L M observation
+    rows of 4.4 KB per environment on top."""
     if wind == 'scenarios':
-      raise ValueError("mcts_search: wind='scenarios' has no node pool (M end states per node); search in the belief, the forecast or the truth")
+      if 'num_scenarios' not in kw:
+        raise ValueError("mcts_search: wind='scenarios' needs num_scenarios (the pool holds M nodes per group: the budget of a search has no "
+                         "default); or search in the belief, the forecast or the truth")
+      num_scenarios, risk_tail = kw.pop('num_scenarios'), kw.pop('risk_tail', None)
+      reuse = self._scenarios if (self._scenarios is not None and self._scenarios.num == int(num_scenarios)) else None
+      self._scenarios = self.arena.fit_wind_scenarios(num_scenarios, seed=self.arena._seed, out=reuse)
+      return self.arena.mcts_search(num_rounds, leaves_per_round, max_depth, segment, action_repeat, gamma, c_puct, scenarios=self._scenarios,
+                                    risk_tail=risk_tail, **kw)
     if wind not in ('truth', 'forecast', 'belief'):
-      raise ValueError(f"mcts_search: wind is 'truth', 'forecast' or 'belief', not {wind!r}")
+      raise ValueError(f"mcts_search: wind is 'truth', 'forecast', 'belief' or 'scenarios', not {wind!r}")
     if wind == 'belief':
       self._belief = self.arena.fit_wind_belief(out=self._belief)
       return self.arena.mcts_search(num_rounds, leaves_per_round, max_depth, segment, action_repeat, gamma, c_puct, belief=self._belief, **kw)
@@ -305,7 +316,9 @@ class VecBalloonEnv:
     by risk_tail's score (seed keys the scenario streams; no leaf_value).
     search='mcts': agents.mcts_agent.VecMCTSAgent(**kw) -- num_rounds, leaves_per_round, max_depth (all three required), segment, action_repeat, gamma, c_puct,
     wind ('belief' by default, 'forecast' or 'truth'), guide (a device agent or trainer whose prior and value steer the search): PUCT over
-    a node pool, the root's visit counts as the answer.
+    a node pool, the root's visit counts as the answer; with wind='scenarios' agents.mcts_agent.VecScenarioMCTSAgent -- the
+    same search over groups of num_scenarios (required) scenario nodes, a group backed up by risk_tail's score (seed keys the scenario
+    streams).
     wind='truth' flies the plans in the wind these environments fly, this env's wind noise included (with wind_noise=False the truth
     is the forecast).  actions = agent.act(obs); obs, reward, terminal = env.step(actions): no host synchronisation in either."""
     if search not in ('sample', 'beam', 'mcts'):
@@ -316,7 +329,12 @@ class VecBalloonEnv:
       missing = [k for k in ('num_rounds', 'leaves_per_round', 'max_depth') if k not in kw]
       if missing:                  # (VecMCTSAgent's three arguments without a default)
         raise ValueError(f"planner: search='mcts' needs {', '.join(missing)}: the budget of a guided tree search has no default")
-      agent = mcts_agent.VecMCTSAgent(**kw)
+      if kw.get('wind') == 'scenarios':
+        if 'num_scenarios' not in kw:
+          raise ValueError("planner: search='mcts' with wind='scenarios' needs num_scenarios: the budget of a guided tree search has no default")
+        agent = mcts_agent.VecScenarioMCTSAgent(**{k: v for k, v in kw.items() if k != 'wind'})
+      else:
+        agent = mcts_agent.VecMCTSAgent(**kw)
     elif search == 'beam':
       from balloon_learning_environment_amd.agents import beam_agent
       if kw.get('wind') == 'scenarios':

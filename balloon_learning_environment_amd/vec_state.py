@@ -125,10 +125,19 @@ class MCTSBuffers:
   (int32), ret (float32) --, `arenas[r]`, round r's slice as a leaf arena of 3L leaves per environment (a view: observe_leaves takes it),
   the statistics [n, cap] (parent, first_child, depth, visits, pending int32; value_sum, g float64; prior [n, cap, 3] float32), g_range
   [n, 2], the slots leaf and kind [n, L], the results, and -- with guide=True -- the network's rows: obs [n 3L, 1099], value [n 3L],
-  probs [n 3L, 3], guide_action [n 3L]."""
+  probs [n 3L, 3], guide_action [n 3L].
+  num_scenarios M > 0: node id i is a GROUP of M scenario nodes, node (i, m) at node_index(i, e) M + m -- the node arrays
+  are [R][n][3L][M], `arenas[r]` is a leaf arena of 3L M leaves per environment, the network's rows are n 3L M -- while the statistics
+  stay [n, cap] per group; group_status [R, n, 3L] uint8 (0: live, 1: spent) and group_g [R, n, 3L] float64 are the groups' own.
+  Memory: 3 L R M nodes per environment (about 150 B each) and, with a guide, 3 L M observation rows of 4.4 KB per environment."""
 
-  def __init__(self, sim: 'VecSimulator', num_rounds: int, leaves_per_round: int, max_depth: int, segment: int = 4, guide: bool = False):
+  def __init__(self, sim: 'VecSimulator', num_rounds: int, leaves_per_round: int, max_depth: int, segment: int = 4, guide: bool = False,
+               num_scenarios: int = 0):
     R, L, D, self.segment = int(num_rounds), int(leaves_per_round), int(max_depth), int(segment)
+    self.num_scenarios = int(num_scenarios)
+    if not 0 <= self.num_scenarios <= _abi.SCENARIO_MAX:
+      raise ValueError(f'mcts_search: 1 <= num_scenarios <= {_abi.SCENARIO_MAX} (0: one wind), not {num_scenarios}')
+    group = max(self.num_scenarios, 1)
     if R < 1 or L < 1 or L * R > _abi.MCTS_MAX_LEAVES:
       raise ValueError(f'mcts_search: num_rounds >= 1, leaves_per_round >= 1 and their product <= {_abi.MCTS_MAX_LEAVES}, not {R} x {L}')
     if D < 1 or self.segment < 1 or D * self.segment > _abi.ROLLOUT_MAX_STEPS:
@@ -136,8 +145,10 @@ class MCTSBuffers:
     cap = 1 + 3 * L * R
     if sim.n * cap >= 2 ** 31:
       raise ValueError(f'mcts_search: n * (1 + 3 * leaves_per_round * num_rounds) < 2^31, not {sim.n} x {cap}')
+    if sim.n * 3 * L * group >= 2 ** 31:
+      raise ValueError(f'mcts_search: n * 3 * leaves_per_round * num_scenarios < 2^31, not {sim.n} x 3 x {L} x {group}')
     self.sim, self.rounds, self.leaves, self.max_depth, self.cap, self.with_guide = sim, R, L, D, cap, bool(guide)
-    n, device, per_round = sim.n, sim.device, sim.n * 3 * L
+    n, device, per_round = sim.n, sim.device, sim.n * 3 * L * group
     with torch.cuda.device(device):
       self.node_state = {name: torch.zeros(R * per_round, dtype=dev.torch_dtype(_abi.FIELD_DTYPES[name]), device=device)
                          for name in _abi.FIELD_NAMES}
@@ -148,7 +159,7 @@ class MCTSBuffers:
       self.ret = torch.zeros(R * per_round, dtype=torch.float32, device=device)
       self.arenas = []
       for r in range(R):              # round r's slice of every array, as a leaf arena of the simulator
-        arena = sim.leaf_arena(3 * L)
+        arena = sim.leaf_arena(3 * L * group)
         arena.state = {name: t[r * per_round:(r + 1) * per_round] for name, t in self.node_state.items()}
         arena._struct = dev.state_struct(arena.state, arena.episode_cache)
         arena.set_vehicle(**sim.vehicle)
@@ -167,6 +178,10 @@ class MCTSBuffers:
       self.q = torch.zeros(n, 3, dtype=torch.float32, device=device)
       self.root_visits = torch.zeros(n, 3, dtype=torch.int32, device=device)
       self.pv_length = torch.zeros(n, dtype=torch.int32, device=device)
+      self.group_status = self.group_g = None
+      if self.num_scenarios:
+        self.group_status = torch.zeros(R, n, 3 * L, dtype=torch.uint8, device=device)
+        self.group_g = torch.zeros(R, n, 3 * L, dtype=torch.float64, device=device)
       self.obs = self.value = self.probs = self.guide_action = None
       if guide:
         self.obs = torch.zeros(per_round, _lib.OBS_DIM, dtype=torch.float32, device=device)
@@ -179,11 +194,18 @@ class MCTSBuffers:
                                     self.depth.data_ptr(), self.visits.data_ptr(), self.pending.data_ptr(), self.value_sum.data_ptr(),
                                     self.g.data_ptr(), self.prior.data_ptr(), self.g_range.data_ptr(), self.leaf.data_ptr(),
                                     self.kind.data_ptr())
+    self._group_struct = None
+    if self.num_scenarios:     # what select and finish take: the same pool with the groups' status in the place of the nodes'
+      self._group_state = dev.state_struct({**self.node_state, 'status': self.group_status.view(-1)})
+      self._group_struct = _abi.BleMctsPool.from_buffer_copy(self._struct)
+      self._group_struct.nodes.state = ctypes.pointer(self._group_state)
 
-  def node_index(self, node_id: int, env: int) -> int:
-    """Where node node_id >= 1 of environment env lies in the pool's node arrays."""
+  def node_index(self, node_id: int, env: int, scenario: Optional[int] = None) -> int:
+    """Where node node_id >= 1 of environment env lies in the pool's node arrays; in a pool of groups: where the group lies in
+    group_status and group_g (flattened), or with `scenario` = m where its node m lies in the node arrays."""
     r, within = divmod(int(node_id) - 1, 3 * self.leaves)
-    return (r * self.sim.n + int(env)) * 3 * self.leaves + within
+    at = (r * self.sim.n + int(env)) * 3 * self.leaves + within
+    return at if scenario is None else at * max(self.num_scenarios, 1) + int(scenario)
 
   def statistics(self) -> Dict[str, torch.Tensor]:
     """Clones of the statistics (tests and traces)."""
@@ -1091,19 +1113,22 @@ class VecSimulator:
                       flown, leaves, key if num else None, buffers=bf)
 
   # ------------------------------------------------------------------ guided tree search
-  def mcts_buffers(self, num_rounds: int, leaves_per_round: int, max_depth: int, segment: int = 4, guide: bool = False) -> 'MCTSBuffers':
+  def mcts_buffers(self, num_rounds: int, leaves_per_round: int, max_depth: int, segment: int = 4, guide: bool = False,
+                   num_scenarios: int = 0) -> 'MCTSBuffers':
     """Everything an mcts_search of these sizes writes, allocated once (MCTSBuffers): the node pool with its per-round leaf-arena views,
     the statistics, the slots and the results; guide=True: also the network's observation, value, probs and action rows.  A search that
-    is given its buffers allocates nothing, as a graph capture needs."""
+    is given its buffers allocates nothing, as a graph capture needs.  num_scenarios: M of a search in scenario winds
+    (mcts_search(scenarios=)): a pool of groups, 3 L R M nodes per environment, and with a guide n 3L M rows; 0: one wind."""
     if self.has_fleet:
       raise ValueError('mcts_search: a fleet (set_fleet) has no look-ahead kernel; fly one vehicle per batch (set_vehicle)')
-    return MCTSBuffers(self, num_rounds, leaves_per_round, max_depth, segment, guide)
+    return MCTSBuffers(self, num_rounds, leaves_per_round, max_depth, segment, guide, num_scenarios)
 
   @_on_own_device
   def mcts_search(self, num_rounds: int, leaves_per_round: int, max_depth: int, segment: int = 4, action_repeat: int = 1,
                   gamma: float = 0.993, c_puct: float = 1.25, noise_seed: Optional[int] = None, belief: Optional[WindBelief] = None,
                   substeps: int = SUBSTEPS, guide_fn=None, root_prior: Optional[torch.Tensor] = None,
-                  buffers: Optional['MCTSBuffers'] = None, trace: Optional[list] = None) -> 'MCTSSearch':
+                  buffers: Optional['MCTSBuffers'] = None, trace: Optional[list] = None, scenarios: Optional[WindScenarios] = None,
+                  risk_tail: Optional[int] = None) -> 'MCTSSearch':
     """Guided tree search: num_rounds rounds of leaves_per_round PUCT descents per environment over a persistent node pool, every new
     node flown for one edge of segment * action_repeat agent steps (the rollouts' own lane body: a node reached by (a_1 .. a_d) holds
     bit for bit what rollout_plans(leaves=) gives the plan a_1 x segment, .., a_d x segment), evaluated once by guide_fn, and backed up
@@ -1116,12 +1141,30 @@ class VecSimulator:
     buffers: mcts_buffers(num_rounds, leaves_per_round, max_depth, segment, guide=guide_fn is not None) to write into.  trace: a list that
     receives (round, leaf [n, L] clone, kind [n, L] clone, statistics clones, value clone or None, probs clone or None) after every
     backup (tests; not capturable).
+    scenarios: a WindScenarios (fit_wind_scenarios): a node is a GROUP of M scenario nodes, every edge is flown in each of
+    the M scenario winds (`ble_mcts_expand_scenarios_f32`; a scenario node that stopped is carried on unchanged under every action, a
+    group whose M nodes all stopped is spent: never expanded, revisited), guide_fn sees all n 3L M nodes of a round, and
+    `ble_mcts_backup_scenarios_f32` turns a group's M values G_m = acc_m + disc_m V_m into the one G it backs up -- the mean of the
+    risk_tail smallest (None: all M, the expectation; 1: the worst case) in plan_risk's order, kept in fp64 -- and its M probability
+    rows into one prior (their mean over the nodes that are OK).  Select and finish run unchanged on the groups.  A node of a non-void
+    group holds bit for bit what rollout_plans(scenarios=) gives its plan in its scenario; q and best_return are risk scores.  buffers:
+    mcts_buffers(..., num_scenarios=M); trace also receives group_g and group_status clones [R, n, 3L] as its seventh and eighth
+    entries.  Not together with belief or noise_seed.  Memory: 3 L R M nodes per environment and, with a guide, 3 L M observation rows
+    of 4.4 KB per environment.
     Returns MCTSSearch(action, q, visits, best_return, best_plan, pv_length, pool): an environment that is not OK gets all STAY and
     best_return 0, one whose root has no visited child all STAY and -Inf.  The tensors are the buffers' own, overwritten by the next search.
     Nothing of the simulator is written; flags of the imagined flights go to rollout_flags, never err_flags.  Asynchronous on the
     current stream, no host synchronisation (capturable in a HIP graph).  Not for fleets."""
     self._ready_for_lookahead('mcts_search', gamma)
-    gen, b = self._lookahead_wind('mcts_search', noise_seed, belief)
+    gen, b = self._lookahead_wind('mcts_search', noise_seed, belief, scenarios)
+    num = 0
+    if scenarios is not None:
+      num = int(scenarios.num)
+      tail = num if risk_tail is None else int(risk_tail)
+      if not 1 <= num <= _abi.SCENARIO_MAX or not 1 <= tail <= num:
+        raise ValueError(f'mcts_search: 1 <= M <= {_abi.SCENARIO_MAX} and 1 <= risk_tail <= M, not M = {num}, risk_tail = {risk_tail}')
+    elif risk_tail is not None:
+      raise ValueError('mcts_search: risk_tail scores scenario winds; give scenarios')
     R, L, D, segment, action_repeat = int(num_rounds), int(leaves_per_round), int(max_depth), int(segment), int(action_repeat)
     if action_repeat < 1 or D * segment * action_repeat > _abi.ROLLOUT_MAX_STEPS:
       raise ValueError(f'mcts_search: action_repeat >= 1 and max_depth * segment * action_repeat <= {_abi.ROLLOUT_MAX_STEPS}, '
@@ -1129,35 +1172,49 @@ class VecSimulator:
     if not 0.0 <= float(c_puct) < float('inf'):
       raise ValueError(f'mcts_search: c_puct finite and >= 0, not {c_puct}')
     if buffers is None:
-      buffers = self.mcts_buffers(R, L, D, segment, guide_fn is not None)
+      buffers = self.mcts_buffers(R, L, D, segment, guide_fn is not None, num)
     bf = buffers
     if (bf.sim is not self or bf.rounds != R or bf.leaves != L or bf.max_depth != D or bf.segment != segment or
-        (guide_fn is not None and not bf.with_guide)):
-      raise ValueError(f'mcts_search: buffers of another search (mcts_buffers({R}, {L}, {D}, {segment}, guide={guide_fn is not None}) of this '
-                       f'simulator)')
+        (guide_fn is not None and not bf.with_guide) or bf.num_scenarios != num):
+      raise ValueError(f'mcts_search: buffers of another search (mcts_buffers({R}, {L}, {D}, {segment}, guide={guide_fn is not None}'
+                       f'{f", num_scenarios={num}" if num or bf.num_scenarios else ""}) of this simulator)')
     n, stream = self.n, dev.stream_ptr(self.device)
     if root_prior is not None:
       assert (root_prior.dtype == torch.float32 and root_prior.is_contiguous() and tuple(root_prior.shape) == (n, 3) and
               root_prior.device == self.device), root_prior.shape
     for arena in bf.arenas:
-      self._check_leaf_arena(arena, 3 * L)
+      self._check_leaf_arena(arena, 3 * L * max(num, 1))
     pool, status = ctypes.byref(bf._struct), self.state['status'].data_ptr()
+    groups = pool                                  # the pool as select and finish see it: in scenario winds the groups' status
+    if num:
+      scn, sgen = self._scenario_structs(scenarios)
+      groups = ctypes.byref(bf._group_struct)
     for r in range(R):
-      _lib.check(self.lib.ble_mcts_select_f32(pool, r, float(c_puct), status, dev.ptr(root_prior), stream), 'ble_mcts_select_f32')
+      _lib.check(self.lib.ble_mcts_select_f32(groups, r, float(c_puct), status, dev.ptr(root_prior), stream), 'ble_mcts_select_f32')
       ex = _abi.BleMctsExpand(r, action_repeat, int(substeps), 0, float(gamma), self.grid.data_ptr(), self.grid_env_stride)
-      _lib.check(self.lib.ble_mcts_expand_f32(ctypes.byref(self._struct), pool, ctypes.byref(ex), gen, b, self.rollout_flags.data_ptr(), stream),
-                 'ble_mcts_expand_f32')
+      if num:
+        _lib.check(self.lib.ble_mcts_expand_scenarios_f32(ctypes.byref(self._struct), pool, ctypes.byref(ex), ctypes.byref(scn),
+                                                          ctypes.byref(sgen), self.rollout_flags.data_ptr(), stream),
+                   'ble_mcts_expand_scenarios_f32')
+      else:
+        _lib.check(self.lib.ble_mcts_expand_f32(ctypes.byref(self._struct), pool, ctypes.byref(ex), gen, b, self.rollout_flags.data_ptr(), stream),
+                   'ble_mcts_expand_f32')
       if guide_fn is not None:
         self.observe_leaves(bf.arenas[r], out=bf.obs)
         guide_fn(bf.obs, out=bf.guide_action, value=bf.value, probs=bf.probs)
-      _lib.check(self.lib.ble_mcts_backup_f32(pool, r, dev.ptr(bf.value) if guide_fn is not None else None,
-                                              dev.ptr(bf.probs) if guide_fn is not None else None, stream), 'ble_mcts_backup_f32')
+      value, probs = (dev.ptr(bf.value), dev.ptr(bf.probs)) if guide_fn is not None else (None, None)
+      if num:
+        _lib.check(self.lib.ble_mcts_backup_scenarios_f32(pool, r, num, tail, value, probs, bf.group_status.data_ptr(),
+                                                          bf.group_g.data_ptr(), stream), 'ble_mcts_backup_scenarios_f32')
+      else:
+        _lib.check(self.lib.ble_mcts_backup_f32(pool, r, value, probs, stream), 'ble_mcts_backup_f32')
       if trace is not None:
         trace.append((r, bf.leaf.clone(), bf.kind.clone(), bf.statistics(), bf.value.clone() if guide_fn is not None else None,
-                      bf.probs.clone() if guide_fn is not None else None))
+                      bf.probs.clone() if guide_fn is not None else None) +
+                     ((bf.group_g.clone(), bf.group_status.clone()) if num else ()))
     fin = _abi.BleMctsFinish(status, bf.best_plan.data_ptr(), bf.action.data_ptr(), bf.best_return.data_ptr(), bf.q.data_ptr(),
                              bf.root_visits.data_ptr(), bf.pv_length.data_ptr())
-    _lib.check(self.lib.ble_mcts_finish_f32(pool, ctypes.byref(fin), stream), 'ble_mcts_finish_f32')
+    _lib.check(self.lib.ble_mcts_finish_f32(groups, ctypes.byref(fin), stream), 'ble_mcts_finish_f32')
     return MCTSSearch(bf.action, bf.q, bf.root_visits, bf.best_return, bf.best_plan, bf.pv_length, bf)
 
   @property

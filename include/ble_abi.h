@@ -1866,6 +1866,56 @@ int ble_mcts_expand_f32(const ble_state_f32* st, const struct ble_mcts_pool* poo
 int ble_mcts_backup_f32(const struct ble_mcts_pool* pool, int32_t round, const float* value, const float* probs, void* stream);
 int ble_mcts_finish_f32(const struct ble_mcts_pool* pool, const struct ble_mcts_finish* fin, void* stream);
 
+/* ---------------------------------------------------------------------------- guided tree search in scenario winds
+ * The search above flown in the M = scn->num scenario winds of ble_gp_fit_scenarios_f32.  Added without a new ABI version.
+ *
+ * The pool of groups.  Node id i of environment e is a GROUP of M scenario nodes.  `nodes` of the ble_mcts_pool holds R * n * 3L * M
+ * entries laid out [R][n][3L][M]: node (id, m) lies at (((id - 1) / 3L * n + e) * 3L + (id - 1) % 3L) * M + m, so the nodes born in
+ * round r are one contiguous leaf arena of 3L * M leaves per environment (ble_observe_leaves_f32 takes the slice as it is).  Id 0 is
+ * environment e of `st` itself for every m, with acc 0, disc 1, flown 0.  The statistics, leaf and kind stay per group, [n][cap] with
+ * cap = 1 + 3 L R, and mean what they mean above.  Two more arrays per group, each [R][n][3L] (a group's index is its node index
+ * without M): group_status (uint8; 0: live, 1: spent) and group_g (fp64).
+ *
+ * Stopped, spent, void (§3u's definitions).  A scenario node is STOPPED when its status is not OK or its acc is NaN.  A group is SPENT
+ * when all M of its nodes are stopped, VOID when its acc is NaN in all M nodes.  For the select a group's "status OK" is "not spent": a
+ * spent group is never EXPAND, it is REVISIT.
+ *
+ * ble_mcts_expand_scenarios_f32(round): one lane per (e, l, a, m); the lane index within the round's slice, (e * 3L + 3l + a) * M + m,
+ * is the destination node index.  The lanes of an EXPAND slot take their rule from the parent group's M status bytes and acc words
+ * (the root: st->status[e]): a live node flies one edge of segment * action_repeat agent steps under action a in scenario m of
+ * environment e, with ble_rollout_scenarios_f32's loop body; a stopped node inside a live group is carried on unchanged -- state, acc,
+ * disc, flown -- under every action.  The lanes of any other slot fly nothing and store void nodes (the source's words, acc NaN).  No
+ * arithmetic of its own: a node of a non-void group reached by (a_1 .. a_d) holds, bit for bit, the state words, (float)acc and flown
+ * ble_rollout_scenarios_f32 gives the plan a_1 x segment, .., a_d x segment in scenario m from environment e.  st, the history, the
+ * scenario slab and every cache are never written; flags go to err_flags -- give it a word of its own.
+ *
+ * ble_mcts_backup_scenarios_f32(round): per environment, slots in order l, then a; per group first the group step over its M nodes:
+ *   G_m = acc_m + disc_m * V_m, fp64, the product and the sum two statements; V_m = value[node] where value is given and the node's
+ *         status is OK, else 0 (a value on a node that is not OK is never read into G);
+ *   G   = the mean of the `tail` smallest G_m in ble_plan_risk_f32's order -- G_m ascending with -0 equal to +0, then m ascending --,
+ *         summed in that order in double from 0.0 and divided by tail once; kept in fp64, never rounded to float.  tail = num: the
+ *         expectation; tail = 1: the worst case.  Any non-finite G_m: the group is treated as void -- visits 0, g NaN, never selected;
+ *   prior = uniform where probs is NULL; else the mean of the probs rows of the group's nodes whose status is OK, m ascending, each
+ *         component summed in double from 0.0, divided by their number once and rounded to float once; uniform if there is no such
+ *         node or if one of those rows has a non-finite or negative entry;
+ *   group_status = 1 if all M nodes are stopped, else 0; group_g = G (NaN: void).
+ * Then ble_mcts_backup_f32's rules with that G, prior and status: parent, depth, first_child, visits, value_sum, g, g_range, the path
+ * to the root, REVISIT, pending cleared.  value [n * 3L * M] and probs [n * 3L * M][3] are the network's answers on the round's slice,
+ * both NULL or both given.  q and best_return of the finish are means of group Gs: risk scores.
+ *
+ * Select and finish: ble_mcts_select_f32 and ble_mcts_finish_f32 on a second ble_mcts_pool -- the same statistics, leaf and kind --
+ * whose nodes.state->status points at group_status (the other arrays of that state are not read; they must not be NULL).
+ *
+ * BLE_E_INVALID_ARG before any HIP call: expand -- everything ble_mcts_expand_f32 refuses of st, pool and ex; what
+ * ble_gp_fit_scenarios_f32 refuses of scn and gen; scn->n other than pool->n; n * 3L * num >= 2^31.  backup -- everything
+ * ble_mcts_backup_f32 refuses; num outside 1 .. BLE_SCENARIO_MAX; tail outside 1 .. num; n * 3L * num >= 2^31; NULL group_status or
+ * group_g.  n == 0: BLE_OK without a launch.  A fleet has no form of these calls.
+ */
+int ble_mcts_expand_scenarios_f32(const ble_state_f32* st, const struct ble_mcts_pool* pool, const struct ble_mcts_expand* ex,
+                                  const ble_gp_scenarios* scn, const ble_scenario_gen* gen, uint32_t* err_flags, void* stream);
+int ble_mcts_backup_scenarios_f32(const struct ble_mcts_pool* pool, int32_t round, int32_t num, int32_t tail, const float* value,
+                                  const float* probs, uint8_t* group_status, double* group_g, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
