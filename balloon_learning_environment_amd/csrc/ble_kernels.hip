@@ -2523,6 +2523,17 @@ inline MctsPoolDev mcts_pool_dev(const struct ble_mcts_pool* p) {
                      p->leaf, p->kind};
 }
 constexpr int kMctsEnvsPerBlock = kMctsBlock;    // select, backup, finish: one lane per environment
+// what both expand calls refuse of st and ex, the pool having passed its own checks
+inline bool mcts_expand_ok(const ble_state_f32* st, const struct ble_mcts_pool* pool, const struct ble_mcts_expand* ex) {
+  return state_ok(st) && ex && ex->wind_grid && mcts_round_ok(pool, ex->round) && ex->action_repeat >= 1 &&
+         (int64_t)pool->max_depth * pool->segment * ex->action_repeat <= BLE_ROLLOUT_MAX_STEPS && ex->substeps >= 1 &&
+         ex->substeps <= BLE_MAX_SUBSTEPS && ex->reserved_ == 0 && ex->grid_env_stride >= 0 && ex->gamma >= 0.0 && ex->gamma <= 1.0 &&
+         !state_arrays_shared(pool->nodes.state, st);                 // (a NaN gamma fails both comparisons)
+}
+// struct ble_mcts_expand as the expand kernels take it
+inline MctsExpandArgs mcts_expand_args(const struct ble_mcts_pool* pool, const struct ble_mcts_expand* ex) {
+  return MctsExpandArgs{pool->n, ex->round, pool->segment * ex->action_repeat, ex->substeps, ex->gamma, ex->wind_grid, ex->grid_env_stride};
+}
 }  // namespace
 
 int ble_mcts_select_f32(const struct ble_mcts_pool* pool, int32_t round, double c_puct, const uint8_t* source_status, const float* root_prior,
@@ -2535,17 +2546,12 @@ int ble_mcts_select_f32(const struct ble_mcts_pool* pool, int32_t round, double 
 
 int ble_mcts_expand_f32(const ble_state_f32* st, const struct ble_mcts_pool* pool, const struct ble_mcts_expand* ex, const ble_noise_gen* noise,
                         const ble_gp_belief* belief, uint32_t* err_flags, void* stream) {
-  if (!state_ok(st) || !mcts_pool_ok(pool) || !ex || !ex->wind_grid || !mcts_round_ok(pool, ex->round) || ex->action_repeat < 1 ||
-      (int64_t)pool->max_depth * pool->segment * ex->action_repeat > BLE_ROLLOUT_MAX_STEPS || ex->substeps < 1 ||
-      ex->substeps > BLE_MAX_SUBSTEPS || ex->reserved_ != 0 || ex->grid_env_stride < 0 || !(ex->gamma >= 0.0 && ex->gamma <= 1.0) ||
-      state_arrays_shared(pool->nodes.state, st))
-    return BLE_E_INVALID_ARG;
+  if (!mcts_pool_ok(pool) || !mcts_expand_ok(st, pool, ex)) return BLE_E_INVALID_ARG;
   return with_wind(noise, belief, pool->n, [&](auto wind, BeliefDev b, StepNoise gen) {
     return with_vehicle<false>(st, nullptr, [&](auto veh) {
       if (pool->n == 0) return BLE_OK;
-      const MctsExpandArgs a{pool->n, ex->round, pool->segment * ex->action_repeat, ex->substeps, ex->gamma, ex->wind_grid, ex->grid_env_stride};
       return launch(ble_mcts_expand_kernel<decltype(wind)::value, decltype(veh)>, pool->n * (int64_t)(3 * pool->leaves_per_round), kStepBlock,
-                    kStepBlock, stream, state_dev(st), a, mcts_pool_dev(pool), b, gen, err_flags, veh);
+                    kStepBlock, stream, state_dev(st), mcts_expand_args(pool, ex), mcts_pool_dev(pool), b, gen, err_flags, veh);
     });
   });
 }
@@ -2574,18 +2580,13 @@ inline bool mcts_groups_ok(const struct ble_mcts_pool* p, int64_t num) {
 int ble_mcts_expand_scenarios_f32(const ble_state_f32* st, const struct ble_mcts_pool* pool, const struct ble_mcts_expand* ex,
                                   const ble_gp_scenarios* scn, const ble_scenario_gen* gen, uint32_t* err_flags, void* stream) {
   ScenariosDev b;
-  if (!gp_scenarios(scn, &b) || !scenario_gen_ok(gen) || !state_ok(st) || !mcts_groups_ok(pool, scn->num) || scn->n != pool->n || !ex ||
-      !ex->wind_grid || !mcts_round_ok(pool, ex->round) || ex->action_repeat < 1 ||
-      (int64_t)pool->max_depth * pool->segment * ex->action_repeat > BLE_ROLLOUT_MAX_STEPS || ex->substeps < 1 ||
-      ex->substeps > BLE_MAX_SUBSTEPS || ex->reserved_ != 0 || ex->grid_env_stride < 0 || !(ex->gamma >= 0.0 && ex->gamma <= 1.0) ||
-      state_arrays_shared(pool->nodes.state, st))
+  if (!gp_scenarios(scn, &b) || !scenario_gen_ok(gen) || !mcts_groups_ok(pool, scn->num) || scn->n != pool->n || !mcts_expand_ok(st, pool, ex))
     return BLE_E_INVALID_ARG;                                         // (scenarios of another batch would be read out of bounds)
   return with_vehicle<false>(st, nullptr, [&](auto veh) {
     if (pool->n == 0) return BLE_OK;
     return with_scenario_seed(gen, [&](auto seed, ScenarioGen g) {
-      const MctsExpandArgs a{pool->n, ex->round, pool->segment * ex->action_repeat, ex->substeps, ex->gamma, ex->wind_grid, ex->grid_env_stride};
       return launch(ble_mcts_expand_scenarios_kernel<decltype(veh), decltype(seed)>, pool->n * (int64_t)(3 * pool->leaves_per_round) * scn->num,
-                    kStepBlock, kStepBlock, stream, state_dev(st), a, mcts_pool_dev(pool), b, seed, g, err_flags, veh);
+                    kStepBlock, kStepBlock, stream, state_dev(st), mcts_expand_args(pool, ex), mcts_pool_dev(pool), b, seed, g, err_flags, veh);
     });
   });
 }

@@ -1,11 +1,14 @@
 // ble_lookahead.h -- the ONE lane body of the kernels that fly agent steps from a state without writing it: the rollouts
 // (ble_rollout_kernel, ble_rollout_belief_kernel, ble_rollout_scenarios_kernel) and the tree expands (ble_tree_expand_kernel,
-// ble_tree_expand_scenarios_kernel).  DESIGN.md 3i, "One look-ahead lane body".
+// ble_tree_expand_scenarios_kernel, ble_mcts_expand_kernel, ble_mcts_expand_scenarios_kernel).  DESIGN.md 3i, "One look-ahead lane body".
 //
-// What the five share is here once, and every bit-for-bit guarantee between them rests on that: the state load, the per-episode
+// What the seven share is here once, and every bit-for-bit guarantee between them rests on that: the state load, the per-episode
 // constants (read from the cache, never stored), the LDS fills, the wind term behind its value barriers, the flown step with its
-// non-finite check and the three fp64 return statements.  A kernel keeps what is its own: the lane map, the rule by which a lane
-// flies, is carried or is void, the loop shell and the stores -- and `live = live && s.status == kOk`, the freeze rule, next to them.
+// non-finite check and the three fp64 return statements.  The loop shell, the stores and `live = live && s.status == kOk`, the freeze
+// rule, next to them are shared where that costs nothing: rollout_lane (ble_rollout.h) for the three rollouts, expand_lane (ble_tree.h)
+// for the two scenario expands.  ble_tree_expand_kernel and ble_mcts_expand_kernel keep that shell as text: through expand_lane they
+// were 0.9 - 2.2 % slower.  A kernel keeps what is its own: its wind object and LDS declaration, its lane map and -- an
+// expand -- where the parent lies and the rule by which the lane flies, is carried or is void.
 //
 // A WIND is a small policy: its LDS object `Shared` (acs_poly and term_save are members of every one, in StepNoiseShared's order: the
 // note above that struct), what it loads with the state (`load`), fills before the barrier (`fill`) and fetches after it (`fetch`),
@@ -17,8 +20,11 @@
 // on the same inputs, hence the same bits per step.  The step kernels themselves (ble_step_kernel, ble_step_helper_kernel,
 // ble_step_split_kernel) keep their bodies as text: sharing with THEM changed the register allocation of the kernels bench.py times
 // (the note above ble_step_helper_kernel).  Sharing among the look-ahead kernels touches none of those: profiles/isa_compare.py
-// reports every other kernel identical, profiles/lookahead_resource_usage.txt the 26 look-ahead instantiations before and after.
-// Timed against the parent's library (profiles/lookahead_refactor_ab.jsonl): the forecast rollouts and the expands 0.5 - 1.8 % faster,
+// reports every other kernel identical, profiles/lookahead_resource_usage.txt the 26 look-ahead instantiations before and after
+// (profiles/expand_lane_resource_usage.txt: the eight scenario expand instantiations before and after expand_lane; timed in
+// profiles/expand_lane_ab.jsonl: the scenario pool expand 0.9 - 1.0 % faster, the scenario beam 0.2 - 0.3 %, the one-wind expands
+// instruction-identical and within 0.4 %).
+// When the lane body was shared, timed against that parent's library (profiles/lookahead_refactor_ab.jsonl): the forecast rollouts and the expands 0.5 - 1.8 % faster,
 // the noise rollout and the scenario kernels within 0.3 %, the belief rollout 0.1 - 0.5 % slower -- more than two runs of one library
 // differ (0.1 %), about what instruction-identical kernels of the two libraries differ by (up to 0.3 %).  Three pieces put back as text
 // one at a time -- the reward store ahead of the return's statements, the constants block in the kernels, the wind handed to
@@ -27,6 +33,7 @@
 //
 // Device only.  Included by ble_kernels.hip after ble_step_kernel: kStepBlock, StepNoiseShared and report_flags are that file's.
 #pragma once
+#include <type_traits>
 #include "ble_noise.h"
 #include "ble_step_core.h"
 
@@ -79,6 +86,8 @@ struct WindForecast {
   __device__ __forceinline__ void uv(const Shared&, const EnvRegs&, float& nu, float& nv) const { nu = 0.0f; nv = 0.0f; }
 };
 
+struct WindBelief;               // ble_gp_belief.h
+
 // forecast + the noise generator's field.  noise_draws_fetch WITHOUT a cache: its fill path is a per-lane write on which the lanes of
 // one environment would race; every lane draws its environment's harmonics from the Philox stream keyed by (seed, env_offset + e,
 // episode[e]), the key of environment e's own flight, into LDS.
@@ -99,6 +108,11 @@ struct WindNoise {
   }
 };
 
+// The wind of a kernel that takes its wind as a tag (the host's with_wind picks it).  The kernel fills the object from its arguments.
+constexpr int kTreeWindForecast = 0, kTreeWindNoise = 1, kTreeWindBelief = 2;
+template <int kWind>
+using LookaheadWind = std::conditional_t<kWind == kTreeWindNoise, WindNoise, std::conditional_t<kWind == kTreeWindBelief, WindBelief, WindForecast>>;
+
 // ---------------------------------------------------------------------------------------------------------------- the lane body
 // Before the barrier (the caller's __syncthreads): the ACS table's cubics and the wind's tables into LDS.
 template <class W>
@@ -108,7 +122,7 @@ __device__ __forceinline__ void lookahead_fill(typename W::Shared& shm) {
 }
 
 // After the barrier, all lanes: the per-episode constants of a live lane, the wind's fetch, the stride constants, the lane's grid and
-// parking block.  A: RolloutArgs or TreeExpandArgs.
+// parking block.  A: RolloutArgs, TreeExpandArgs or MctsExpandArgs.
 template <class W, class A, class V>
 __device__ __forceinline__ void lookahead_begin(LookaheadLane& l, W& wind, typename W::Shared& shm, const StateDev& st, const A& a, int64_t e,
                                                 bool in_range, bool live, const V& veh) {

@@ -142,33 +142,40 @@ BLE_FN void mcts_select_slot(const MctsStats& s, int count, int max_depth, doubl
   if (what != kMctsEmpty) mcts_pend_path(s, v, what == kMctsExpand ? 3 : 1, max_depth, count);
 }
 
+// The newborn c of both backups (this file's and ble_mcts_scenarios.h's), born under node v by a slot that grew or not: its links, and
+// -- unless it is void: no G, never selected -- one visit worth G on itself, in the range, and on v and every ancestor.
+BLE_FN void mcts_newborn(const MctsStats& s, int count, int max_depth, int c, int v, bool grown, bool is_void, double G) {
+  union { uint64_t u; double f; } nan;
+  nan.u = 0x7FF8000000000000ull;
+  s.parent[c] = grown ? v : -1;
+  s.depth[c] = grown ? s.depth[v] + 1 : 0;
+  s.first_child[c] = 0;
+  s.pending[c] = 0;
+  if (is_void) { s.visits[c] = 0; s.value_sum[c] = 0.0; s.g[c] = nan.f; return; }
+  s.g[c] = G; s.visits[c] = 1; s.value_sum[c] = G;
+  if (G < s.g_range[0]) s.g_range[0] = G;
+  if (G > s.g_range[1]) s.g_range[1] = G;
+  mcts_add_path(s, v, G, max_depth, count);
+}
+
 // Backup of slot l of a round, whose three nodes have ids first_id + a and lie next to each other in the pool: acc, disc, status point
 // at the first of them, value (NULL: no guide, V = 0) and probs (NULL: uniform) at the slot's first row.  count: the ids born before
 // this round.
 BLE_FN void mcts_backup_slot(const MctsStats& s, int count, int max_depth, int first_id, int v, int what, const double* acc,
                              const double* disc, const uint8_t* status, const float* value, const float* probs) {
-  union { uint64_t u; double f; } nan;
-  nan.u = 0x7FF8000000000000ull;
   const bool grown = what == kMctsExpand;
   for (int a = 0; a < 3; ++a) {
     const int c = first_id + a;
     const double acc_c = acc[a];
-    s.parent[c] = grown ? v : -1;
-    s.depth[c] = grown ? s.depth[v] + 1 : 0;
-    s.first_child[c] = 0;
-    s.pending[c] = 0;
     mcts_prior_row(probs != nullptr ? probs + 3 * a : nullptr, s.prior + 3 * c);
-    if (!grown || acc_c != acc_c) {              // void: no G, never selected
-      s.visits[c] = 0; s.value_sum[c] = 0.0; s.g[c] = nan.f;
-      continue;
+    const bool is_void = !grown || acc_c != acc_c;
+    double G = 0.0;
+    if (!is_void) {
+      const float v_c = (value != nullptr && status[a] == 0) ? value[a] : 0.0f;      // a terminal keeps its return
+      const double tail = disc[a] * (double)v_c;
+      G = acc_c + tail;
     }
-    const float v_c = (value != nullptr && status[a] == 0) ? value[a] : 0.0f;        // a terminal keeps its return
-    const double tail = disc[a] * (double)v_c;
-    const double G = acc_c + tail;
-    s.g[c] = G; s.visits[c] = 1; s.value_sum[c] = G;
-    if (G < s.g_range[0]) s.g_range[0] = G;
-    if (G > s.g_range[1]) s.g_range[1] = G;
-    mcts_add_path(s, v, G, max_depth, count);
+    mcts_newborn(s, count, max_depth, c, v, grown, is_void, G);
   }
   if (grown) s.first_child[v] = first_id;
   if (what == kMctsRevisit) mcts_add_path(s, v, s.g[v], max_depth, count);
@@ -299,13 +306,21 @@ struct MctsExpandArgs {
   int64_t grid_env_stride;
 };
 
-// ble_tree_expand_kernel's shell with the pool's lane map: lane j = e 3L + 3l + a of the round's slice.  An EXPAND slot's lane loads
+// expand_lane's source in the pool: the pool, or -- id 0, a slot that does not grow -- the state itself.  The choice is formed again at
+// each use: bound once to a `const StateDev&` it is a StateDev of its own, 584 bytes of scratch per lane.
+struct ExpandFromPool {
+  const StateDev &st, &pool;
+  bool from_pool;
+  __device__ __forceinline__ const StateDev& state() const { return from_pool ? pool : st; }
+};
+
+// ble_tree_expand_kernel's shell (text, as there: the note above expand_lane) with the pool's lane map: lane j = e 3L + 3l + a.  An EXPAND slot's lane loads
 // node leaf[e][l] (id 0: environment e of st, with acc 0, disc 1, flown 0), flies the edge and stores the child; every other lane
 // stores a void node (the source's words, acc NaN).
 template <int kWind, class V = VehicleDefault>
 __global__ __launch_bounds__(kStepBlock) void ble_mcts_expand_kernel(StateDev st, MctsExpandArgs a, MctsPoolDev p, BeliefDev b, StepNoise gen,
                                                                      uint32_t* err_flags, V veh) {
-  using W = std::conditional_t<kWind == kTreeWindNoise, WindNoise, std::conditional_t<kWind == kTreeWindBelief, WindBelief, WindForecast>>;
+  using W = LookaheadWind<kWind>;
   __shared__ typename W::Shared shm;
   W wind;
   if constexpr (kWind == kTreeWindNoise) wind.gen = gen;

@@ -6,14 +6,15 @@
 // 1 spent) and group_g (fp64) are [R][n][3L], the layout §3v's pool_status has: ble_mcts_select_kernel and ble_mcts_finish_kernel
 // take a pool view whose status array is group_status and run unchanged -- "status OK" of a group is "not spent".
 //
-//   ble_mcts_expand_scenarios_kernel   one lane per (e, l, a, m), lane index within the round's slice = destination node index: the
-//                                      body of ble_tree_expand_scenarios_kernel with ble_mcts_expand_kernel's lane map times M.  An
-//                                      EXPAND slot's lanes take their rule from tree_scenario_lane on the parent group's M status bytes
+//   ble_mcts_expand_scenarios_kernel   one lane per (e, l, a, m), lane index within the round's slice = destination node index:
+//                                      expand_lane (ble_tree.h) with ble_mcts_expand_kernel's lane map times M.  An EXPAND slot's
+//                                      lanes take their rule from tree_scenario_lane on the parent group's M status bytes
 //                                      and acc words (a live node flies one edge in scenario m, a stopped node of a live group is
 //                                      carried on unchanged under every action); any other slot's lanes store void nodes.  No arithmetic
 //                                      of its own.
 //   ble_mcts_backup_scenarios_kernel   one lane per environment, looping l, a, m: the group step -- M nodes to one G, one prior row, one
-//                                      status byte (mcts_group_g, mcts_group_prior, mcts_group_spent) -- and then §3v's backup of that G.
+//                                      status byte (mcts_group_g, mcts_group_prior, mcts_group_spent) -- and then §3v's backup of that G
+//                                      (mcts_newborn, ble_mcts.h).
 //
 // The group's G.  G_m = acc_m + disc_m V_m, fp64, two statements; V_m the guide's value of node (id, m) where there is one and the node's
 // status is OK, else 0.  G: the mean of the `tail` smallest G_m in ble_plan_risk_f32's order -- G_m ascending with -0 equal to +0, then
@@ -125,7 +126,7 @@ BLE_FN void mcts_group_prior(const uint8_t* status, const float* probs, int num,
 
 // Backup of slot l of a round, whose three GROUPS have ids first_id + a: acc, disc, status point at the first node of the first of them
 // ([3][num] nodes next to each other), value (NULL: no guide) and probs at the slot's first row, group_status and group_g at the slot's
-// first group.  mcts_backup_slot with the group step in front: the newborn's G, prior and status come from its M nodes.
+// first group.  The group step -- the newborn's G, prior and status from its M nodes -- and then mcts_backup_slot's own mcts_newborn.
 BLE_FN void mcts_backup_group_slot(const MctsStats& s, int count, int max_depth, int first_id, int v, int what, const double* acc,
                                    const double* disc, const uint8_t* status, const float* value, const float* probs, int num, int tail,
                                    uint8_t* group_status, double* group_g) {
@@ -134,22 +135,11 @@ BLE_FN void mcts_backup_group_slot(const MctsStats& s, int count, int max_depth,
   const bool grown = what == kMctsExpand;
   for (int a = 0; a < 3; ++a) {
     const int c = first_id + a, at = a * num;
-    s.parent[c] = grown ? v : -1;
-    s.depth[c] = grown ? s.depth[v] + 1 : 0;
-    s.first_child[c] = 0;
-    s.pending[c] = 0;
     mcts_group_prior(status + at, probs != nullptr ? probs + 3 * at : nullptr, num, s.prior + 3 * c);
     group_status[a] = mcts_group_spent(status + at, acc + at, num) ? 1 : 0;
     const double G = grown ? mcts_group_g(acc + at, disc + at, status + at, value != nullptr ? value + at : nullptr, num, tail) : nan.f;
     group_g[a] = G;
-    if (G != G) {                                // void: no G, never selected
-      s.visits[c] = 0; s.value_sum[c] = 0.0; s.g[c] = nan.f;
-      continue;
-    }
-    s.g[c] = G; s.visits[c] = 1; s.value_sum[c] = G;
-    if (G < s.g_range[0]) s.g_range[0] = G;
-    if (G > s.g_range[1]) s.g_range[1] = G;
-    mcts_add_path(s, v, G, max_depth, count);
+    mcts_newborn(s, count, max_depth, c, v, grown, G != G, G);
   }
   if (grown) s.first_child[v] = first_id;
   if (what == kMctsRevisit) mcts_add_path(s, v, s.g[v], max_depth, count);
@@ -173,7 +163,7 @@ __global__ __launch_bounds__(kMctsBlock) void ble_mcts_backup_scenarios_kernel(M
   for (int i = 0; i < count; ++i) g.pending[i] = 0;
 }
 
-// ble_tree_expand_scenarios_kernel's body with the pool's lane map: lane j = ((e 3L + 3l + a) M + m) of the round's slice.
+// expand_lane (ble_tree.h) under tree_scenario_lane's rule with the pool's lane map: lane j = ((e 3L + 3l + a) M + m) of the round's slice.
 template <class V, class S>
 __global__ __launch_bounds__(kStepBlock) void ble_mcts_expand_scenarios_kernel(StateDev st, MctsExpandArgs a, MctsPoolDev p, ScenariosDev b, S seed,
                                                                               ScenarioGen gen, uint32_t* err_flags, V veh) {
@@ -191,8 +181,7 @@ __global__ __launch_bounds__(kStepBlock) void ble_mcts_expand_scenarios_kernel(S
   const int act = slot % 3;
   const int64_t dj = (int64_t)a.round * lanes_total + j;         // the child's index in the pool
   W wind{b, seed, gen, sm};
-  LookaheadLane l;
-  bool live = false, from_pool = false;
+  bool from_pool = false;
   int rule = kTreeLaneVoid;
   int64_t pj = e;                                // the parent node's index: in st, or in the pool
   if (in_range) {
@@ -204,29 +193,9 @@ __global__ __launch_bounds__(kStepBlock) void ble_mcts_expand_scenarios_kernel(S
     if (from_pool) { pg = mcts_node_index(id, e, a.n, leaves3) * b.num; pj = pg + sm; }
     // fly or carry: from the parent group's M status bytes and M acc words, once per edge; a slot that does not grow: void
     if (grow) rule = tree_scenario_lane((from_pool ? p.nodes.s.status : st.status) + pg, from_pool ? p.nodes.acc + pg : nullptr, b.num, sm, act);
-    // the parent node's state; the per-episode cache is environment e's: a node holds its environment's constants
-    lookahead_load(l, from_pool ? p.nodes.s : st, pj, st, a.n, e);
-    if (from_pool) { l.acc = p.nodes.acc[pj]; l.disc = p.nodes.disc[pj]; l.flown = p.nodes.flown[pj]; }
-    wind.load(e);
-    live = rule == kTreeLaneFly;                 // a stopped node flies nothing
   }
-  const bool flew = live;                        // (edge_steps >= 1: a live parent enters its first step)
-  lookahead_fill<W>(shm);
-  __syncthreads();
-  lookahead_begin(l, wind, shm, st, a, e, in_range, live, veh);
-#pragma unroll 1
-  for (int t = 0; t < a.edge_steps; ++t) {
-    if (live) lookahead_step(l, wind, shm, a, act, veh);
-    live = live && l.s.status == kOk;            // a scenario that went terminal: frozen, reward 0
-  }
-  if (in_range) {
-    // the child: what the lane holds after its last executed step, or -- a stopped parent, a slot that does not grow -- the source's words
-    leaf_store(from_pool ? p.nodes.s : st, p.nodes.s, pj, dj, flew, l.s, l.c, act);
-    if (rule == kTreeLaneVoid) l.acc = __builtin_nan("");
-    p.nodes.acc[dj] = l.acc; p.nodes.disc[dj] = l.disc; p.nodes.flown[dj] = l.flown;
-    p.nodes.ret[dj] = (float)l.acc;
-  }
-  report_flags(l.flags, err_flags);
+  expand_lane(st, a, wind, shm, ExpandFromPool{st, p.nodes.s, from_pool}, pj, from_pool ? p.nodes.acc : nullptr, p.nodes.disc, p.nodes.flown,
+              p.nodes, dj, e, in_range, act, rule, err_flags, veh);
 }
 #endif  // __HIPCC__
 

@@ -66,9 +66,10 @@ BLE_FN bool tree_finish_best(bool source_ok, uint32_t key_best, float value_best
   return true;
 }
 
-#if defined(__HIPCC__)
-constexpr int kTreeWindForecast = 0, kTreeWindNoise = 1, kTreeWindBelief = 2;
+// What an expand lane does with its parent node.  Fly: one edge.  Carry: the child is the node unchanged.  Void: the same with acc = NaN.
+constexpr int kTreeLaneFly = 0, kTreeLaneCarry = 1, kTreeLaneVoid = 2;
 
+#if defined(__HIPCC__)
 // A node arena as the kernels take it: a leaf arena (every array leaf_store writes) and the rollout lane's registers
 struct TreeArenaDev {
   StateDev s;
@@ -92,11 +93,52 @@ struct TreeExpandArgs {
   const int32_t* __restrict__ parent;      // [n][beam]; level 1: not read
 };
 
+// A SOURCE tells expand_lane where its parent's state arrays lie, at each of its two uses.  The beam's: one arena (ble_mcts.h: the pool's).
+struct ExpandFromArena {
+  const StateDev& s;
+  __device__ __forceinline__ const StateDev& state() const { return s; }
+};
+
+// THE edge of the two scenario expands (ble_tree_expand_scenarios_kernel, ble_mcts_expand_scenarios_kernel): the parent is node pj of
+// src with the words acc / disc / flown [pj] (acc == nullptr: a node of the state itself, with acc 0, disc 1, flown 0), the per-episode
+// cache environment e's; the child goes to index dj of dst.  rule: kTreeLaneFly, Carry or Void.  A lane that does not fly stores the
+// parent's own words; the child's acc is NaN exactly where the rule is Void.  All lanes of the workgroup call it.  The two one-wind
+// expands (below, ble_mcts.h) keep this shell as text: through it, with the rule decided by the loaded node, they were 0.9 - 2.2 % slower.
+template <class W, class A, class Src, class V>
+__device__ __forceinline__ void expand_lane(const StateDev& st, const A& a, W& wind, typename W::Shared& shm, const Src& src, int64_t pj,
+                                            const double* acc, const double* disc, const int32_t* flown, const TreeArenaDev& dst, int64_t dj,
+                                            int64_t e, bool in_range, int act, int rule, uint32_t* err_flags, const V& veh) {
+  LookaheadLane l;
+  bool live = false;
+  if (in_range) {
+    lookahead_load(l, src.state(), pj, st, a.n, e);
+    if (acc != nullptr) { l.acc = acc[pj]; l.disc = disc[pj]; l.flown = flown[pj]; }
+    wind.load(e);
+    live = rule == kTreeLaneFly;                 // a stopped node flies nothing
+  }
+  const bool flew = live;                        // (edge_steps >= 1: a live parent enters its first step)
+  lookahead_fill<W>(shm);
+  __syncthreads();
+  lookahead_begin(l, wind, shm, st, a, e, in_range, live, veh);
+#pragma unroll 1
+  for (int t = 0; t < a.edge_steps; ++t) {
+    if (live) lookahead_step(l, wind, shm, a, act, veh);
+    live = live && l.s.status == kOk;            // a scenario that went terminal: frozen, reward 0
+  }
+  if (in_range) {
+    leaf_store(src.state(), dst.s, pj, dj, flew, l.s, l.c, act);
+    if (rule == kTreeLaneVoid) l.acc = __builtin_nan("");
+    dst.acc[dj] = l.acc; dst.disc[dj] = l.disc; dst.flown[dj] = l.flown;
+    dst.ret[dj] = (float)l.acc;
+  }
+  report_flags(l.flags, err_flags);
+}
+
 // src.acc == nullptr: level 1 -- src.s is the state itself, node e, with acc 0, disc 1, flown 0.
 template <int kWind, class V = VehicleDefault>
 __global__ __launch_bounds__(kStepBlock) void ble_tree_expand_kernel(StateDev st, TreeExpandArgs a, TreeArenaDev src, TreeArenaDev dst,
                                                                      BeliefDev b, StepNoise gen, uint32_t* err_flags, V veh) {
-  using W = std::conditional_t<kWind == kTreeWindNoise, WindNoise, std::conditional_t<kWind == kTreeWindBelief, WindBelief, WindForecast>>;
+  using W = LookaheadWind<kWind>;
   __shared__ typename W::Shared shm;
   W wind;
   if constexpr (kWind == kTreeWindNoise) wind.gen = gen;

@@ -5,7 +5,7 @@
 // destination node index: the lane loads node (e C_{d-1} + parent[e][r]) M + m of the previous level's arena (at level 1: environment e
 // of the state itself) and flies the edge with the lane body of ble_rollout_scenarios_kernel (ble_lookahead.h with WindScenario: one
 // text for both -- the same draws, the same noise and correction behind the same three value barriers, the single float add, the same
-// order of the three return statements) and stores the child as ble_tree_expand_kernel does.  Hence a node of a non-void group
+// order of the three return statements) and stores the child, both in ble_tree_expand_kernel's expand_lane.  Hence a node of a non-void group
 // reached by (a_1 .. a_d) holds the bits ble_rollout_scenarios_f32 gives the plan a_1 x segment, .., a_d x segment in scenario m.
 // The level's ret is [n][C_d][M]: ble_plan_risk_kernel maps it to [n][C_d], which ble_tree_select_kernel and ble_tree_finish_kernel
 // take as their keys.  No arithmetic of its own.
@@ -23,8 +23,6 @@
 #include "ble_scenarios.h"
 
 namespace ble {
-
-constexpr int kTreeLaneFly = 0, kTreeLaneCarry = 1, kTreeLaneVoid = 2;
 
 BLE_FN bool tree_node_stopped(uint8_t status, double acc) { return status != 0 || acc != acc; }
 
@@ -64,36 +62,10 @@ __global__ __launch_bounds__(kStepBlock) void ble_tree_expand_scenarios_kernel(S
   if (in_range && !first) pg = (e * a.parent_children + tree_clamp(a.parent[e * a.beam + child / 3], a.parent_children)) * b.num;
   const int64_t pj = first ? pg : pg + sm;       // the parent node
   W wind{b, seed, gen, sm};
-  LookaheadLane l;
-  bool live = false;
+  // fly, carry or void: from the parent group's M status bytes and M acc words, once per edge (the note above tree_scenario_lane)
   int rule = kTreeLaneCarry;
-  if (in_range) {
-    // fly, carry or void: from the parent group's M status bytes and M acc words, once per edge
-    rule = tree_scenario_lane(src.s.status + pg, first ? nullptr : src.acc + pg, b.num, sm, act);
-    // the parent node's state; the per-episode cache is environment e's: a node holds its environment's constants
-    lookahead_load(l, src.s, pj, st, a.n, e);
-    if (!first) { l.acc = src.acc[pj]; l.disc = src.disc[pj]; l.flown = src.flown[pj]; }
-    wind.load(e);
-    live = rule == kTreeLaneFly;                 // a stopped node flies nothing
-  }
-  const bool flew = live;                        // (edge_steps >= 1: a live parent enters its first step)
-  lookahead_fill<W>(shm);
-  __syncthreads();
-  lookahead_begin(l, wind, shm, st, a, e, in_range, live, veh);
-#pragma unroll 1
-  for (int t = 0; t < a.edge_steps; ++t) {
-    if (live) lookahead_step(l, wind, shm, a, act, veh);
-    live = live && l.s.status == kOk;            // a scenario that went terminal: frozen, reward 0
-  }
-  if (in_range) {
-    // the child: what the lane holds after its last executed step, or -- a stopped parent -- the parent's own words (leaf_store)
-    leaf_store(src.s, dst.s, pj, j, flew, l.s, l.c, act);
-    // a spent group is carried on by its a = 0 child group alone; the others, and every child group of a void group, are void
-    if (rule == kTreeLaneVoid) l.acc = __builtin_nan("");
-    dst.acc[j] = l.acc; dst.disc[j] = l.disc; dst.flown[j] = l.flown;
-    dst.ret[j] = (float)l.acc;
-  }
-  report_flags(l.flags, err_flags);
+  if (in_range) rule = tree_scenario_lane(src.s.status + pg, first ? nullptr : src.acc + pg, b.num, sm, act);
+  expand_lane(st, a, wind, shm, ExpandFromArena{src.s}, pj, src.acc, src.disc, src.flown, dst, j, e, in_range, act, rule, err_flags, veh);
 }
 #endif  // __HIPCC__
 
