@@ -442,3 +442,19 @@ class BleExploreGroupedF32(ctypes.Structure):
   epsilon (float32 [P]) and seed (uint64 [P]) are device pointers."""
   _fields_ = [('n', ctypes.c_int64), ('members', ctypes.c_int32), ('reserved_', ctypes.c_int32), ('epsilon', ctypes.c_void_p),
               ('seed', ctypes.c_void_p), ('step', ctypes.c_uint64)]
+
+
+class BleSumTreeGroupedF64(ctypes.Structure):
+  """struct ble_sum_tree_grouped_f64: P solo sum-tree images over one population ring; leaves and padded are per member, member_stride
+  the doubles between trees; nodes [P][member_stride] and max_priority [P] are device pointers."""
+  _fields_ = [('members', ctypes.c_int64), ('leaves', ctypes.c_int64), ('padded', ctypes.c_int64), ('member_stride', ctypes.c_int64),
+              ('nodes', ctypes.c_void_p), ('max_priority', ctypes.c_void_p)]
+
+
+class BleMarcoPoloGroupedF32(ctypes.Structure):
+  """struct ble_marco_polo_grouped_f32: Marco Polo exploration over n = P * R lanes, lane p R + r keyed by (seed[p], r, *step) at
+  probability[p]; probability (float64 [P]) and seed (uint64 [P]) are device pointers."""
+  _fields_ = [('n', ctypes.c_int64), ('obs_stride', ctypes.c_int32), ('reserved_', ctypes.c_int32), ('members', ctypes.c_int64),
+              ('probability', ctypes.c_void_p), ('seed', ctypes.c_void_p), ('obs', ctypes.c_void_p), ('begin', ctypes.c_void_p),
+              ('step', ctypes.c_void_p), ('phase_clock', ctypes.c_void_p), ('walk_clock', ctypes.c_void_p),
+              ('exploratory_episode', ctypes.c_void_p), ('exploratory_phase', ctypes.c_void_p), ('target', ctypes.c_void_p)]

@@ -21,7 +21,7 @@ LIB_PATH = os.environ.get('BLE_HIP_LIB') or os.path.join(_PKG_DIR, 'libble_hip.s
 _SOURCES = [os.path.join(_PKG_DIR, 'csrc', f) for f in ('ble_kernels.hip', 'ble_step_core.h', 'ble_physics.h', 'ble_intrinsics.h', 'ble_reset.h',
                                                           'ble_observe.h', 'ble_gp_query.h', 'ble_gp_factor.h', 'ble_lookahead.h', 'ble_rollout.h', 'ble_gp_belief.h', 'ble_plan.h', 'ble_tree.h', 'ble_scenarios.h', 'ble_tree_scenarios.h', 'ble_mcts.h', 'ble_mcts_scenarios.h', 'ble_noise.h', 'ble_decode.h', 'ble_step_split.h', 'ble_step_helper.h', 'ble_agent.h', 'ble_qnet.h',
                                                           'ble_train.h', 'ble_replay.h', 'ble_explore.h', 'ble_actor.h', 'ble_imitate.h', 'ble_population.h',
-                                                          'ble_population_train.h', 'ble_population_td.h')]
+                                                          'ble_population_train.h', 'ble_population_td.h', 'ble_population_prio.h')]
 _HEADER = os.path.join(os.path.dirname(_PKG_DIR), 'include', 'ble_abi.h')
 
 ABI_VERSION = 5
@@ -60,7 +60,9 @@ EXPORTS = ('ble_abi_version', 'ble_noise_primitive_version', 'ble_vehicle_defaul
            'ble_qnet_td_grouped_workspace_f32', 'ble_qnet_td_step_grouped_f32', 'ble_replay_sample_grouped_f32',
            'ble_qnet_explore_grouped_u8', 'ble_tree_expand_scenarios_f32',
            'ble_mcts_select_f32', 'ble_mcts_expand_f32', 'ble_mcts_backup_f32', 'ble_mcts_finish_f32',
-           'ble_mcts_expand_scenarios_f32', 'ble_mcts_backup_scenarios_f32')
+           'ble_mcts_expand_scenarios_f32', 'ble_mcts_backup_scenarios_f32',
+           'ble_replay_tree_add_grouped_f64', 'ble_replay_sample_prioritized_grouped_f32', 'ble_replay_set_priority_grouped_f32',
+           'ble_marco_polo_grouped_u8')
 # Exports added without a new ABI version: a library of this ABI built before them (BLE_HIP_LIB: the parent's, in A/B runs) still loads.
 # build() checks every name of EXPORTS on the library it builds.
 ADDITIVE_EXPORTS = ('ble_last_step_form', 'ble_gp_query_f32', 'ble_rollout_f32', 'ble_gp_fit_f32', 'ble_gp_belief_wind_f32',
@@ -74,7 +76,8 @@ ADDITIVE_EXPORTS = ('ble_last_step_form', 'ble_gp_query_f32', 'ble_rollout_f32',
                     'ble_tree_finish_f32', 'ble_qnet_td_grouped_workspace_f32', 'ble_qnet_td_step_grouped_f32',
                     'ble_replay_sample_grouped_f32', 'ble_qnet_explore_grouped_u8', 'ble_tree_expand_scenarios_f32',
                     'ble_mcts_select_f32', 'ble_mcts_expand_f32', 'ble_mcts_backup_f32', 'ble_mcts_finish_f32',
-                    'ble_mcts_expand_scenarios_f32', 'ble_mcts_backup_scenarios_f32')
+                    'ble_mcts_expand_scenarios_f32', 'ble_mcts_backup_scenarios_f32', 'ble_replay_tree_add_grouped_f64',
+                    'ble_replay_sample_prioritized_grouped_f32', 'ble_replay_set_priority_grouped_f32', 'ble_marco_polo_grouped_u8')
 
 
 class BleLibraryError(RuntimeError):
@@ -270,6 +273,12 @@ def lib():
     l.ble_mcts_expand_scenarios_f32.argtypes = [st, pool, ctypes.POINTER(_abi.BleMctsExpand), ctypes.POINTER(_abi.BleGpScenarios),
                                                 ctypes.POINTER(_abi.BleScenarioGen), _vp, _vp]
     l.ble_mcts_backup_scenarios_f32.argtypes = [pool, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, _vp, _vp, _vp, _vp, _vp]
+  if hasattr(l, 'ble_replay_tree_add_grouped_f64'):   # a population's prioritized replay and Marco Polo (sizes in the structs)
+    trees = ctypes.POINTER(_abi.BleSumTreeGroupedF64)
+    l.ble_replay_tree_add_grouped_f64.argtypes = [replay, trees, _vp]
+    l.ble_replay_sample_prioritized_grouped_f32.argtypes = [replay, trees, _vp, batch, _vp, _vp, _vp]
+    l.ble_replay_set_priority_grouped_f32.argtypes = [replay, trees, batch, _vp, _vp, _vp, _vp, _vp]
+    l.ble_marco_polo_grouped_u8.argtypes = [ctypes.POINTER(_abi.BleMarcoPoloGroupedF32), _vp, _vp]
   for name in EXPORTS:
     if hasattr(l, name) or name not in ADDITIVE_EXPORTS:
       getattr(l, name).restype = _int

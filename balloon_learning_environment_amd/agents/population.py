@@ -534,7 +534,10 @@ class PopulationQTrainer:
   @dev.on_own_device
   def train_step(self, replay: 'qnet_train.VecPopulationReplayBuffer', batch_size: int = 32) -> torch.Tensor:
     """Sample B rows per member (member p keyed by (seeds[p], update counter)) and update: per-row losses [P * B] on the device, no
-    host synchronisation.  A captured graph of this batch size (capture()) replays it."""
+    host synchronisation.  A captured graph of this batch size (capture()) replays it.  With a VecPopulationPrioritizedReplayBuffer of
+    this population's member count the update is followed by the grouped set_priority and the losses returned are the
+    importance-weighted ones, each member's normalised by its own largest weight; a plain VecPrioritizedReplayBuffer, or a
+    buffer of another member count, is refused."""
     g = self._graphs.get(batch_size)
     if g is not None and g[1] is replay:
       g[0].replay()
@@ -542,13 +545,17 @@ class PopulationQTrainer:
     return self._update(replay, batch_size)
 
   def _update(self, replay, batch_size: int) -> torch.Tensor:
-    if replay.prioritized or getattr(replay, 'members', None) != self.members:
+    if getattr(replay, 'members', None) != self.members:      # (a plain VecPrioritizedReplayBuffer has no members)
       raise ValueError(f'PopulationQTrainer samples a VecPopulationReplayBuffer of its {self.members} members')
-    return self.train_on_batch(replay.sample(batch_size, self.seeds, self.counter))
+    batch = replay.sample(batch_size, self.seeds, self.counter)
+    loss = self.train_on_batch(batch)
+    if replay.prioritized:                          # sample -> grouped update -> set_priority; the reported loss is the weighted one
+      return replay.set_priority(batch, loss)
+    return loss
 
   def capture(self, replay, batch_size: int = 32) -> torch.Tensor:
-    """Records one update (grouped sample + grouped train step) into a HIP graph that train_step(replay, batch_size) replays from then
-    on: the counters, seeds and hyperparameters are device memory, so each replay draws a new batch, takes a new Adam step and reads
+    """Records one update (grouped sample + grouped train step, + the grouped set_priority with a prioritized population buffer) into
+    a HIP graph that train_step(replay, batch_size) replays from then on: the counters, seeds and hyperparameters are device memory, so each replay draws a new batch, takes a new Adam step and reads
     their current values.  Runs one eager update first (the lazy allocations) -- a real update; returns its per-row losses."""
     first = self.train_step(replay, batch_size)
     graph, loss = dev.capture(self.device, lambda: self._update(replay, batch_size))
@@ -577,8 +584,9 @@ class PopulationQTrainer:
   @dev.on_own_device
   def copy_members(self, src: torch.Tensor, dst: torch.Tensor) -> None:
     """Rows dst of the images, the target, weights_t, adam_m, adam_v and the hyperparameter tensors become rows src (device int64
-    index tensors of one length, dst without repeats).  The seeds stay: a copy draws its own batches and explores its own way.  No host
-    synchronisation."""
+    index tensors of one length, dst without repeats).  The seeds stay: a copy draws its own batches and explores its own way.  The
+    replay contents stay the columns' own, and with them the priorities of a VecPopulationPrioritizedReplayBuffer (trees and maxima)
+    and the state of a VecPopulationMarcoPoloExploration, which belong to the environment rows.  No host synchronisation."""
     assert src.shape == dst.shape and src.dim() == 1 and src.dtype == dst.dtype == torch.int64
     for t in (self.population.images, self.target, self.weights_t, self.adam_m, self.adam_v) + tuple(getattr(self, k) for k in Q_HYPER):
       t.index_copy_(0, dst, t.index_select(0, src))

@@ -416,7 +416,7 @@ class VecPopulationReplayBuffer(VecReplayBuffer):
   columns [p R, (p + 1) R) member p's, filled by add() with the P * R rows of a VecBalloonEnv step.  sample(B, seeds, counter) draws B
   rows PER MEMBER into a TrainBatch of P * B rows (ble_replay_sample_grouped_f32): rows [p B, (p + 1) B) are what member p's own
   VecReplayBuffer of its R columns (member_buffer(p)) gives sample(B, seeds[p], counter), with the index's column + p R.  Prioritized
-  replay has no grouped form."""
+  replay per member is VecPopulationPrioritizedReplayBuffer's."""
 
   def __init__(self, members: int, rows_per_member: int, capacity_steps: int, update_horizon: int = 5, gamma: float = 0.993,
                device='cuda:0'):
@@ -462,6 +462,84 @@ class VecPopulationReplayBuffer(VecReplayBuffer):
   def load_state_dict(self, d: dict) -> None:
     assert int(d['members']) == self.members, 'checkpoint of another population'
     super().load_state_dict(d)
+
+
+class VecPopulationPrioritizedReplayBuffer(VecPopulationReplayBuffer):
+  """VecPopulationReplayBuffer with prioritized replay per member: P fp64 sum trees, `tree` [P, 2 * padded], each a solo
+  VecPrioritizedReplayBuffer's tree image over capacity_steps x R leaves -- leaf (t % T) R + r the window of column p R + r -- with its
+  own max recorded priority, `max_priority` [P].  add() also enters every member's newly complete windows at that member's max priority
+  (ble_replay_tree_add_grouped_f64); sample(B, seeds, counter) draws B rows per member stratified by its own priorities, the batch
+  carrying each row's priority; set_priority(batch, loss) sets the leaves per member and returns the importance-weighted losses
+  [P * B], each member's normalised by its own largest weight.  Rows [p B, (p + 1) B), tree p and max_priority[p] hold the bytes
+  member_buffer(p) -- a VecPrioritizedReplayBuffer of member p's columns -- holds after the same calls with seeds[p]."""
+
+  prioritized = True
+  _TENSORS = VecPopulationReplayBuffer._TENSORS + ('tree', 'max_priority')
+
+  def __init__(self, members: int, rows_per_member: int, capacity_steps: int, update_horizon: int = 5, gamma: float = 0.993,
+               device='cuda:0'):
+    super().__init__(members, rows_per_member, capacity_steps, update_horizon, gamma, device)
+    leaves = self.capacity * self.rows_per_member
+    if leaves > 2 ** 31:
+      raise ValueError('capacity_steps x rows_per_member must be at most 2^31')
+    self.padded = 1 << (leaves - 1).bit_length()
+    with torch.cuda.device(self.device):
+      self.tree = torch.zeros(self.members, 2 * self.padded, dtype=torch.float64, device=self.device)
+      self.max_priority = torch.ones(self.members, dtype=torch.float64, device=self.device)
+    self._tree = _abi.BleSumTreeGroupedF64(self.members, leaves, self.padded, 2 * self.padded, self.tree.data_ptr(),
+                                           self.max_priority.data_ptr())
+
+  def batch_buffers(self, batch_size: int) -> TrainBatch:
+    """The prioritized TrainBatch of P * B rows of B rows per member."""
+    rows = self.members * int(batch_size)
+    return dev.first_use(self._batches, rows, lambda: TrainBatch(rows, self.device, True),
+                         f'VecPopulationPrioritizedReplayBuffer: sample once at {batch_size} rows per member before capturing it in a graph')
+
+  def leaf_priorities(self) -> torch.Tensor:
+    """The leaves as [members, capacity_steps, rows_per_member] (a view)."""
+    t, r = self.capacity, self.rows_per_member
+    return self.tree[:, self.padded:self.padded + t * r].view(self.members, t, r)
+
+  @dev.on_own_device
+  def add(self, obs, action, reward, terminal, episode_end=None) -> None:
+    super().add(obs, action, reward, terminal, episode_end)
+    _lib.call('ble_replay_tree_add_grouped_f64', ctypes.byref(self.struct(self.counter)), ctypes.byref(self._tree),
+              dev.stream_ptr(self.device))
+
+  @dev.on_own_device
+  def sample(self, batch_size: int, seeds: torch.Tensor, counter: Optional[torch.Tensor] = None) -> TrainBatch:
+    """B stratified prioritized draws per member (ble_replay_sample_prioritized_grouped_f32) into this buffer's batch of P * B rows;
+    batch.priority [P * B] holds each row's leaf (fp32).  seeds and counter as VecPopulationReplayBuffer.sample."""
+    assert seeds.dtype == torch.int64 and seeds.is_contiguous() and seeds.numel() == self.members and seeds.device == self.device
+    bt = self.batch_buffers(int(batch_size))
+    rp = self.struct(self.counter if counter is None else counter)
+    _lib.call('ble_replay_sample_prioritized_grouped_f32', ctypes.byref(rp), ctypes.byref(self._tree), seeds.data_ptr(),
+              ctypes.byref(bt.struct), bt.priority.data_ptr(), self.err_flags.data_ptr(), dev.stream_ptr(self.device))
+    return bt
+
+  @dev.on_own_device
+  def set_priority(self, batch: TrainBatch, loss: torch.Tensor) -> torch.Tensor:
+    """Member p's leaves of its rows = sqrt(loss + 1e-10) (ble_replay_set_priority_grouped_f32); returns the weighted per-row losses
+    [P * B] (a buffer the next call at this size overwrites)."""
+    _lib.call('ble_replay_set_priority_grouped_f32', ctypes.byref(self.struct(self.counter)), ctypes.byref(self._tree),
+              ctypes.byref(batch.struct), batch.priority.data_ptr(), loss.data_ptr(), batch.weighted_loss.data_ptr(),
+              self.err_flags.data_ptr(), dev.stream_ptr(self.device))
+    return batch.weighted_loss
+
+  def member_buffer(self, p: int) -> VecPrioritizedReplayBuffer:
+    """A copy of member p's R columns as a VecPrioritizedReplayBuffer of its own, with tree p and max_priority[p] copied in."""
+    if not 0 <= int(p) < self.members:
+      raise IndexError(f'member {p} of a population of {self.members}')
+    r = self.rows_per_member
+    cols = slice(int(p) * r, (int(p) + 1) * r)
+    solo = VecPrioritizedReplayBuffer(r, self.capacity, self.update_horizon, self.gamma, self.device)
+    for k in ('obs', 'action', 'reward', 'terminal', 'episode_end'):
+      getattr(solo, k).copy_(getattr(self, k)[:, cols])
+    solo.tree.copy_(self.tree[int(p)])
+    solo.max_priority.copy_(self.max_priority[int(p):int(p) + 1])
+    solo.cursor = self.cursor
+    solo.count.fill_(self.cursor)
+    return solo
 
 
 def _epsilons(epsilon, members: int) -> np.ndarray:

@@ -47,6 +47,7 @@
 #include "ble_population.h"
 #include "ble_population_train.h"
 #include "ble_population_td.h"
+#include "ble_population_prio.h"
 
 using namespace ble;
 
@@ -2228,6 +2229,57 @@ int ble_marco_polo_u8(const ble_marco_polo_f32* mp, uint8_t* action, void* strea
     return BLE_E_INVALID_ARG;
   if (mp->n == 0) return BLE_OK;
   const int status = launch(ble_marco_polo_kernel, mp->n, 256, 256, stream, *mp, action);
+  if (status != BLE_OK) return status;
+  return launch_grid(ble_train_advance_kernel, dim3(1), 1, stream, mp->step);
+}
+
+// ---------------------------------------------------------------------------------------------------------------- a population's prioritized replay
+extern "C++" {
+namespace {
+// P solo tree images over the one ring of a population: per-member sizes, as tree_ok's
+bool tree_grouped_ok(const ble_replay_f32* rp, const ble_sum_tree_grouped_f64* tr) {
+  return tr != nullptr && tr->members >= 1 && tr->members <= 2147483647LL && rp->num_envs % tr->members == 0 &&
+         tr->leaves == rp->capacity * (rp->num_envs / tr->members) && tr->leaves <= BLE_SUM_TREE_MAX_LEAVES && tr->padded >= tr->leaves &&
+         (tr->padded & (tr->padded - 1)) == 0 && (tr->padded == 1 || tr->padded / 2 < tr->leaves) && tr->member_stride >= 2 * tr->padded &&
+         tr->nodes && tr->max_priority && aligned(7, tr->nodes, tr->max_priority);
+}
+}  // namespace
+}  // extern "C++"
+
+int ble_replay_tree_add_grouped_f64(const ble_replay_f32* rp, const ble_sum_tree_grouped_f64* tr, void* stream) {
+  if (!replay_ok(rp) || !tree_grouped_ok(rp, tr)) return BLE_E_INVALID_ARG;
+  return launch_grid(ble_tree_add_grouped_kernel, dim3((unsigned)tr->members), kTreeBlock, stream, *rp, *tr,
+                     (int64_t)(rp->num_envs / tr->members));
+}
+
+int ble_replay_sample_prioritized_grouped_f32(const ble_replay_f32* rp, const ble_sum_tree_grouped_f64* tr, const unsigned long long* seeds,
+                                              const ble_train_batch_f32* bt, float* priority, uint32_t* err_flags, void* stream) {
+  if (!replay_ok(rp) || !tree_grouped_ok(rp, tr) || !batch_ok(bt) || bt->batch % tr->members != 0 || !bt->index || !priority || !seeds ||
+      !aligned(7, seeds))
+    return BLE_E_INVALID_ARG;
+  return launch_sample_then_advance(ble_replay_sample_prio_grouped_kernel, rp, bt, stream, *rp, *tr, *bt, priority, seeds,
+                                    (int64_t)(bt->batch / tr->members), (int64_t)(rp->num_envs / tr->members), err_flags);
+}
+
+int ble_replay_set_priority_grouped_f32(const ble_replay_f32* rp, const ble_sum_tree_grouped_f64* tr, const ble_train_batch_f32* bt,
+                                        const float* priority, const float* loss, float* weighted_loss, uint32_t* err_flags, void* stream) {
+  if (!replay_ok(rp) || !tree_grouped_ok(rp, tr) || !batch_ok(bt) || bt->batch % tr->members != 0 || !bt->index || !priority || !loss ||
+      !weighted_loss)
+    return BLE_E_INVALID_ARG;
+  if (bt->batch == 0) return BLE_OK;
+  return launch_grid(ble_set_priority_grouped_kernel, dim3((unsigned)tr->members), kTreeBlock, stream, (int64_t)rp->capacity,
+                     (int64_t)(rp->num_envs / tr->members), *tr, (const int64_t*)bt->index, (int64_t)(bt->batch / tr->members), priority, loss,
+                     weighted_loss, err_flags);
+}
+
+int ble_marco_polo_grouped_u8(const ble_marco_polo_grouped_f32* mp, uint8_t* action, void* stream) {
+  if (!mp || !action || mp->n < 0 || mp->n > 4LL * 2147483647LL * 256 || mp->obs_stride < 1 || mp->reserved_ != 0 || mp->members < 1 ||
+      mp->n % mp->members != 0 || !mp->probability || !mp->seed || !aligned(7, mp->probability, mp->seed) || !mp->obs || !mp->begin ||
+      !mp->step || !mp->phase_clock || !mp->walk_clock || !mp->exploratory_episode || !mp->exploratory_phase || !mp->target ||
+      !aligned(7, mp->target))
+    return BLE_E_INVALID_ARG;
+  if (mp->n == 0) return BLE_OK;
+  const int status = launch(ble_marco_polo_grouped_kernel, mp->n, 256, 256, stream, *mp, (int64_t)(mp->n / mp->members), action);
   if (status != BLE_OK) return status;
   return launch_grid(ble_train_advance_kernel, dim3(1), 1, stream, mp->step);
 }

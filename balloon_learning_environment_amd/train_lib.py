@@ -370,7 +370,7 @@ def run_population_training_loop_vec(env, trainer, replay, *, num_iterations: in
                                      epsilon: Union[float, Sequence[float], Callable[[int], float]] = 0.01,
                                      updates_per_step: Optional[int] = None, batch_size: int = 32, capture_graph: bool = True,
                                      ready_every: Optional[int] = None, truncation: float = 0.0, perturb: Sequence[float] = (0.8, 1.25),
-                                     seed: int = 0, controller: Optional[PBTController] = None) -> List[dict]:
+                                     seed: int = 0, controller: Optional[PBTController] = None, exploration=None) -> List[dict]:
   """Trains P replay learners in one batch (agents/population.py: PopulationQTrainer with a qnet_train.VecPopulationReplayBuffer(P, R,
   ...)) on `env` (auto_reset) of P * R environments, environment rows [p R, (p + 1) R) member p's, for num_iterations x
   steps_per_iteration vector steps.  Each step: every member's greedy actions (trainer.act), epsilon-greedy per member
@@ -389,6 +389,12 @@ def run_population_training_loop_vec(env, trainer, replay, *, num_iterations: in
   contents, which stay the columns' own, and not the seeds) with its lr multiplied by one of the two `perturb` factors
   (trainer.scale_hyper).  truncation = 0, the default, is a plain P-seed study.  controller: a PBTController to continue.
 
+  exploration: None, or a marco_polo.VecPopulationMarcoPoloExploration(P, R, ...) with run_training_loop_vec's semantics
+  (configs/quantile.gin for a population: with epsilon=0.0 and a qnet_train.VecPopulationPrioritizedReplayBuffer).  After the greedy
+  actions and the grouped epsilon-greedy (at rate 0 it changes nothing; its draws are addressed, not consumed) the explorer rewrites the
+  actions; its begin mask is all ones at the first step and the previous step's episode_end after; the replay stores the action taken.
+  Priorities and the explorer's state belong to the columns: a PBT round copies neither.
+
   Returns run_training_loop_vec's dicts (mean_loss: the mean over all members' rows; transitions: all members') plus, as lists of P,
   member_mean_loss, member_mean_return and member_episodes (this iteration's), lr, and with a controller lineage and round
   ({'fitness', 'src', 'dst'} as lists on a round's iteration, else None).  One host synchronisation per iteration: its end."""
@@ -404,6 +410,7 @@ def run_population_training_loop_vec(env, trainer, replay, *, num_iterations: in
   actions = torch.zeros(n, dtype=torch.uint8, device=dev_)
   book = _EpisodeBook(n, dev_, max_episode_length)
   zero = torch.zeros((), dtype=torch.float32, device=dev_)
+  begin = torch.ones(n, dtype=torch.uint8, device=dev_) if exploration is not None else None
   updates, pending, step, member_transitions = 0, 0.0, 0, 0
   captured = False
   stats = []
@@ -414,9 +421,13 @@ def run_population_training_loop_vec(env, trainer, replay, *, num_iterations: in
     for _ in range(steps_per_iteration):
       trainer.act(obs, actions)
       qnet_train.explore_grouped(actions, epsilon(member_transitions) if ladder is None else ladder, trainer.seeds, step)
+      if exploration is not None:
+        exploration(obs, actions, begin)
       end_mask = book.end_mask()
       next_obs, reward, terminal = env.step(actions, end_mask=end_mask)
       episode_end = terminal | end_mask
+      if exploration is not None:
+        begin.copy_(episode_end)
       replay.add(obs, actions, reward, terminal, episode_end)
       ended = episode_end.bool().view(p, r)
       ended_returns = torch.where(ended, (book.ep_return + reward).view(p, r), zero)

@@ -1631,6 +1631,73 @@ typedef struct ble_explore_grouped_f32 {
 } ble_explore_grouped_f32;
 int ble_qnet_explore_grouped_u8(const ble_explore_grouped_f32* ex, uint8_t* action, void* stream);
 
+/* ------------------------------------------------- prioritized replay and Marco Polo for a population
+ * P = members sum trees over the ONE ring of ble_replay_sample_grouped_f32 (N = replay->num_envs = P * R columns, columns
+ * [p R, (p + 1) R) member p's).  Member p's tree is a solo tree image in the sense of ble_sum_tree_f64 over leaves = capacity * R
+ * leaves, leaf (t % capacity) R + r the window of column p R + r, at nodes + p * member_stride, with its own max_priority[p].  The
+ * contract is §3t's: member p's block of nodes, max_priority[p] and rows [p B, (p + 1) B) of every batch array hold the bytes the plain
+ * entry point gives a ring of member p's R columns with that tree, seeds[p] and the same counter (the index's column + p R).  The
+ * doubles between the trees (member_stride > 2 padded) are neither read nor written.  No floating-point atomics; err_flags is set with
+ * an integer atomic OR.  Added without a new ABI version.
+ */
+typedef struct ble_sum_tree_grouped_f64 {
+  int64_t members;           /* P >= 1, dividing replay->num_envs (and batch->batch where a batch is given) */
+  int64_t leaves;            /* PER MEMBER: capacity x num_envs / members */
+  int64_t padded;            /* PER MEMBER: the smallest power of two >= leaves */
+  int64_t member_stride;     /* doubles between members' trees, >= 2 padded */
+  double* nodes;             /* device [P][member_stride], 8-byte aligned: member p's heap in its first 2 padded doubles */
+  double* max_priority;      /* device [P], 8-byte aligned: each member's max_recorded_priority, never falls */
+} ble_sum_tree_grouped_f64;
+
+/*
+ * ble_replay_tree_add_grouped_f64: ble_replay_tree_add_f64 for every member after one vector step was added, one workgroup per member.
+ * ble_replay_sample_prioritized_grouped_f32: batch->batch = P * B rows, one workgroup per row; row p B + b draws from the Philox stream
+ *   keyed by (seeds[p], b, *counter), q = total_p (b + u) / B over member p's tree, redrawn from that tree on an invalid window;
+ *   priority [P * B] (device float32): the sampled leaf, 0 for a failed row, which fails alone (zeros, index (-1, -1),
+ *   BLE_FLAG_REPLAY_EMPTY).  Advances *counter once.  seeds: device uint64 [P].
+ * ble_replay_set_priority_grouped_f32: ble_replay_set_priority_f32 per member, one workgroup per member over rows [p B, (p + 1) B): the
+ *   weights are normalised by the largest over member p's valid rows; leaves in batch order; a row whose index is -1 or whose column
+ *   lies outside [p R, (p + 1) R) is skipped; a non-finite or negative loss leaves its leaf and sets BLE_FLAG_REPLAY_PRIORITY;
+ *   max_priority[p] rises to member p's largest new leaf.
+ * BLE_E_INVALID_ARG before any HIP call: what the plain entry points and ble_replay_sample_grouped_f32 refuse of the corresponding
+ * fields; members < 1; num_envs % members != 0; batch->batch % members != 0; leaves != capacity * num_envs / members; padded not the
+ * smallest power of two >= leaves; leaves > BLE_SUM_TREE_MAX_LEAVES; member_stride < 2 padded; NULL or misaligned nodes, max_priority
+ * or seeds; a missing batch->index.  A batch of 0 rows: BLE_OK, nothing launched.
+ */
+int ble_replay_tree_add_grouped_f64(const ble_replay_f32* replay, const ble_sum_tree_grouped_f64* tree, void* stream);
+int ble_replay_sample_prioritized_grouped_f32(const ble_replay_f32* replay, const ble_sum_tree_grouped_f64* tree,
+                                              const unsigned long long* seeds, const ble_train_batch_f32* batch, float* priority,
+                                              uint32_t* err_flags, void* stream);
+int ble_replay_set_priority_grouped_f32(const ble_replay_f32* replay, const ble_sum_tree_grouped_f64* tree,
+                                        const ble_train_batch_f32* batch, const float* priority, const float* loss, float* weighted_loss,
+                                        uint32_t* err_flags, void* stream);
+
+/*
+ * ble_marco_polo_grouped_u8: ble_marco_polo_u8 for P members of R = n / P lanes: lane p R + r draws from the stream keyed by
+ * (seed[p], r, *step) and its episode is exploratory when u <= probability[p] -- member p's own explorer on its R rows.  The state
+ * arrays hold n = P * R lanes; one step counter, advanced once per call.
+ * BLE_E_INVALID_ARG before any HIP call: what ble_marco_polo_u8 refuses of the shared fields; members < 1; n % members != 0; NULL
+ * probability or seed, or either not 8-byte aligned; reserved_ != 0.  probability and seed are DEVICE memory: the caller validates
+ * 0 <= probability <= 1 (agents/marco_polo.py does, of what it uploads).
+ */
+typedef struct ble_marco_polo_grouped_f32 {
+  int64_t n;                               /* P * R lanes */
+  int32_t obs_stride;                      /* floats between observation rows, >= 1 (feature 0 is read) */
+  int32_t reserved_;                       /* 0 */
+  int64_t members;                         /* P >= 1 */
+  const double* probability;               /* device [P], each 0 .. 1: exploratory_episode_probability per member */
+  const unsigned long long* seed;          /* device [P] */
+  const float* obs;                        /* device [n][obs_stride] */
+  const uint8_t* begin;                    /* device [n] */
+  unsigned long long* step;                /* device: the draw key's step */
+  int32_t* phase_clock;                    /* device [n] */
+  int32_t* walk_clock;                     /* device [n] */
+  uint8_t* exploratory_episode;            /* device [n] */
+  uint8_t* exploratory_phase;              /* device [n] */
+  double* target;                          /* device [n] */
+} ble_marco_polo_grouped_f32;
+int ble_marco_polo_grouped_u8(const ble_marco_polo_grouped_f32* mp, uint8_t* action, void* stream);
+
 /* ----------------------------------------------------------------------------------------------- plan by beam search
  * A shared-prefix tree of action plans, searched level by level: D levels, one EDGE = one action flown segment * action_repeat agent
  * steps.  Per environment P_0 = 1 (the environment itself), C_d = 3 P_{d-1} children at level d, P_d = min(C_d, B) parents for the next;
