@@ -911,30 +911,37 @@ BLE_FN Ephemeris ephemeris(int64_t unix_s) {
 //   hour_angle = (B + d_lng) -+ 180  -> cos(hour_angle) = -cos(B + d_lng)   (solar.py:113-120)
 // (sin_b, cos_b) of b = 360 frac_day + eot/4 + lng0 [deg]; the three nodes of a step share
 // one sincos and rotate by the half-step angle.
+// No reciprocal root either: with a = d / R, sin_lat = cos_a sin_lat0 + sin_a cos_lat0 cos_h and the reference's
+// (xx, yy) = (cos_a - sin_lat0 sin_lat, sin_a cos_lat0 sin_h),
+//   (xx, yy) = cos_lat0 cos_lat (cos d_lng, sin d_lng), so sqrt(xx^2 + yy^2) = cos_lat0 cos_lat and
+//       cos_lat cos(B + d_lng) = (cos_b xx - sin_b yy) / cos_lat0: neither cos_lat nor 1 / |(xx, yy)| is formed;
+//   cos_a - sin_lat0 sin_lat = cos_lat0 (cos_a cos_lat0 - sin_lat0 sin_a cos_h) because sin_lat0^2 + cos_lat0^2 = 1, so the
+//       division by cos_lat0 cancels too;
+//   sin_a cos_h = sinc(a) y / R and sin_a sin_h = sinc(a) x / R with sinc(a) = sin(a) / a, a polynomial in a^2 = d^2 / R^2:
+//       no 1 / d, and d = 0 needs no case (sinc = 1, both products 0).
+// Precondition: (sin_lat0, cos_lat0) is a normalised fp64 pair, i.e. it comes from sincos_f64.  Every contraction is an explicit
+// fma, so the function rounds the same way in every kernel it is inlined into and on the host.
 // Within one agent step x, y move linearly (constant wind) and the ephemeris is linear,
 // so S(t) is smooth: agent_step evaluates this at 3 nodes and interpolates quadratically
 // (|error| <= |d3S/dt3| h^3 * 0.064 <= 1.8e-8, and ~0 around local noon where d3S/dt3 -> 0).
 struct SunSC { float sin_el, cos_el; };
 BLE_FN double sun_one_minus_sin_f64(double sin_lat0, double cos_lat0, double x, double y, double sin_b, double cos_b,
                                     double sin_decl, double cos_decl) {
-  const double d2 = x * x + y * y;
-  const bool moved = d2 > 0.0;
-  const double inv_d = moved ? d_rsqrt(moved ? d2 : 1.0) : 0.0;
-  const double cos_h = moved ? y * inv_d : 1.0;      // heading = atan2(x, y); atan2(0, 0) = 0
-  const double sin_h = x * inv_d;
-  const double a = (d2 * inv_d) * (1.0 / 6371000.0);  // angle = |(x, y)| / R_earth  (< 0.2 rad)
-  const double a2 = a * a;
-  // Taylor to a^13 / a^12: |a| < 0.2 -> truncation < 1e-17
-  double sin_a = d_fma(a2, d_fma(a2, d_fma(a2, d_fma(a2, d_fma(a2, d_fma(a2, 1.0 / 6227020800.0, -1.0 / 39916800.0),
-                                                         1.0 / 362880.0), -1.0 / 5040.0), 1.0 / 120.0), -1.0 / 6.0), 1.0) * a;
-  double cos_a = d_fma(a2, d_fma(a2, d_fma(a2, d_fma(a2, d_fma(a2, d_fma(a2, 1.0 / 479001600.0, -1.0 / 3628800.0),
-                                                         1.0 / 40320.0), -1.0 / 720.0), 1.0 / 24.0), -0.5), 1.0);
-  const double sin_lat = cos_a * sin_lat0 + sin_a * cos_lat0 * cos_h;
-  const double cos_lat = d_sqrt_fast(d_fma(-sin_lat, sin_lat, 1.0));
-  const double yy = sin_a * cos_lat0 * sin_h;
-  const double xx = cos_a - sin_lat0 * sin_lat;
-  const double cos_bl = (cos_b * xx - sin_b * yy) * d_rsqrt(xx * xx + yy * yy);
-  const double s = sin_lat * sin_decl - cos_lat * cos_decl * cos_bl;
+  BLE_NO_CONTRACT
+  const double kInvR = 1.0 / 6371000.0;
+  const double d2 = d_fma(x, x, y * y);
+  const double a2 = d2 * (kInvR * kInvR);             // a = |(x, y)| / R_earth  (< 0.2 rad)
+  // Taylor to a^12: |a| < 0.2 -> truncation < 1e-17.  sinc(a) = sin(a) / a is a polynomial in a^2: a itself is never formed
+  const double sinc = d_fma(a2, d_fma(a2, d_fma(a2, d_fma(a2, d_fma(a2, d_fma(a2, 1.0 / 6227020800.0, -1.0 / 39916800.0),
+                                                          1.0 / 362880.0), -1.0 / 5040.0), 1.0 / 120.0), -1.0 / 6.0), 1.0);
+  const double cos_a = d_fma(a2, d_fma(a2, d_fma(a2, d_fma(a2, d_fma(a2, d_fma(a2, 1.0 / 479001600.0, -1.0 / 3628800.0),
+                                                           1.0 / 40320.0), -1.0 / 720.0), 1.0 / 24.0), -0.5), 1.0);
+  const double sy = sinc * (y * kInvR);               // sin(a) cos(heading)
+  const double sx = sinc * (x * kInvR);               // sin(a) sin(heading)
+  const double sin_lat = d_fma(cos_a, sin_lat0, cos_lat0 * sy);
+  const double xx = d_fma(cos_a, cos_lat0, -(sin_lat0 * sy));      // (cos_a - sin_lat0 sin_lat) / cos_lat0
+  const double inner = d_fma(cos_b, xx, -(sin_b * sx));            // cos_lat cos(B + d_lng)
+  const double s = d_fma(sin_lat, sin_decl, -(cos_decl * inner));
   return 1.0 - s;
 }
 BLE_FN SunSC sun_from_one_minus_sin(float oms) {

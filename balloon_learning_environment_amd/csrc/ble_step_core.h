@@ -242,8 +242,13 @@ BLE_FN SolarNodes solar_nodes_time(const Ephemeris& e0, int64_t t0, float lng0_d
   // (sin, cos) of the declination as an exactly normalised fp64 pair: with the fp32 pair
   // (|sd^2 + cd^2 - 1| ~ 6e-8) the error of 1 - sin(el) near the zenith (el > 89.8 deg, 1 - sin(el)
   // < 1e-6) was ~10 % and cos(el) -- hence the panel power -- was off by 2e-5
-  const double sd0 = (double)e0.sin_decl, cd0 = d_sqrt_fast(d_fma(-sd0, sd0, 1.0));
-  const double hsd = 0.5 * (double)(e0.sin_decl_rate * step_s), hcd = -(sd0 * d_rcp(cd0)) * hsd;
+  // d_sqrt_fast spelled out: its y = rsqrt(1 - sd0^2) is also 1 / cd0 for the rate, no second seed.  y is good to 1.5 e^2 of its seed
+  // (2e-14); the root's own residual res = cd2 - sq^2 corrects it to the rounding: sq = cd0 (1 + eps) with eps = -res y^2 / 2, y = sq / cd2,
+  // so 1 / cd0 = y / (1 + eps) = y + (y res / 2) y^2 up to eps^2
+  const double sd0 = (double)e0.sin_decl, cd2 = d_fma(-sd0, sd0, 1.0);
+  const double y = d_rsqrt(cd2), sq = cd2 * y, res = d_fma(-sq, sq, cd2), cd0 = d_fma(0.5 * y, res, sq);
+  const double rcd = d_fma((0.5 * y) * res, y * y, y);
+  const double hsd = 0.5 * (double)(e0.sin_decl_rate * step_s), hcd = -(sd0 * rcd) * hsd;
   n.sd0 = sd0; n.cd0 = cd0; n.hsd = hsd; n.hcd = hcd;
   return n;
 }
